@@ -7,8 +7,14 @@ cornell, 1920x1080, spp 1024, max-bounces 8, UsdPreviewSurface model); scene ing
 before the timed region (the scene is resident in HBM), the timed region contains every bounce stage, the
 per-pixel accumulation, for N>1 the RCCL tile gather, and the final D2H of the colour AOV.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c1|c3|c4|c5] [--spp S]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c1|c3|c4|c5] [--spp S] [--dump-outputs DIR] [--full]
   N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets the scene up, warms up, times the K steps and prints the line: metric, value, unit, ms_per_step, config and the first-frame
+clocks.  `--dump-outputs DIR` then writes what the last timed step returned to its caller -- the colour AOV, float32 [rows, width, 4] -- as
+DIR/color.npy (a fixed, seeded sample of its pixels when it exceeds 64 MB); the inputs are seeded, so two builds can be compared output by output.
+Everything below -- the roofline object and its counter passes, the CPU baseline, the reference probe, the `also` legs and the side file of
+raw counters -- is measured only with `--full`.
 
 N>1 is strong scaling: the rows of the same frame are dealt round-robin to the N ranks (rank r renders rows r, r+N, ...:
 every share samples the whole image; one rank per GPU, scene replicated) and gathered to rank 0 with
@@ -22,7 +28,7 @@ side is reported in wall-clock terms against ceilings MEASURED by tools/valu_cal
 the nearer of the two rooflines as THIS run measured them; `bound_note` is set when neither is near; `prior_experiment_note` names what earlier calibration runs found for the
 kernel family (the big-scene traversal followed its instruction count one to one, profiles/r04k_valu_sensitivity.txt) -- a citation, not a result of the run.
 
-At N = 1 the default line carries, under `also`, compact objects for configs C3 and C4 -- the wavefront pipeline (k_raygen / k_trace_dyn / k_route / k_shade /
+With `--full`, at N = 1 the line carries, under `also`, compact objects for configs C3 and C4 -- the wavefront pipeline (k_raygen / k_trace_dyn / k_route / k_shade /
 k_trace_dyn<any>) -- and for `c5share`, one rank's share of C5's 8-GPU partition at full spp (`projected_8gpu` = 8 x its rate), each with its own roofline fractions;
 at N >= 8 config C5 itself, tiled across the ranks.  Raw counters and every kernel's time share / VALU rate / lanes / L2 hit go to profiles/bench_last_pmc.json
 (and gpurun_out/ when it exists), not into the line.  The big-scene legs are timed with the per-launch HIP events OFF (hundreds of stage launches per step: the event pairs
@@ -68,6 +74,21 @@ def make_workload(name, spp_override=None):
         rs.spp = spp_override
         label += f" [spp overridden to {spp_override}]"
     return desc, rs, w, h, label
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, img):
+    """--dump-outputs: the colour AOV the last timed step handed its caller, float32 [rows, width, 4] as d/color.npy.  Above 64 MB (C5's 4K frame)
+    a fixed, seeded sample of its pixels, in frame order, [n, 4]: the same pixels for every run of the same size."""
+    import numpy as np
+    a = np.ascontiguousarray(img.numpy() if hasattr(img, "numpy") else img, dtype=np.float32)
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        px = a.reshape(-1, a.shape[-1])
+        a = px[np.sort(np.random.default_rng(0).choice(len(px), (DUMP_LIMIT_BYTES - 4096) // px[0].nbytes, replace=False))]
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "color.npy"), a)
 
 
 def cpu_baseline(desc, rs, w, h, budget_s=7.0):
@@ -238,6 +259,8 @@ def main():
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc passes (roofline.traffic / frac become null)")
     ap.add_argument("--in-process", action="store_true", help="ONE process driving --gpus N devices inside the library (giCInitializeDevices: rows dealt to the devices per "
                     "giCRender, shares copied into place on device 0) instead of one rank per GPU + RCCL gather; for comparing the two multi-GPU forms")
+    ap.add_argument("--full", action="store_true", help="also measure the roofline (counter passes), the CPU baseline, the reference probe and the further legs ('also')")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the colour AOV of the last timed step as DIR/color.npy (float32)")
     ap.add_argument("--probe", action="store_true", help=argparse.SUPPRESS)  # internal: one untimed step, no output (the --pmc passes run this)
     args = ap.parse_args()
     if args.probe:
@@ -370,15 +393,19 @@ def main():
         if args.probe:
             scene.close()
             return None, R
-        # --- roofline inputs: one extra (untimed) step with the traversal counters on
-        scene.set_option(capi.OPTION_COUNT_TRAVERSAL, 1)
-        scene.render(rs, w, h, rows=(r0, r1), device_only=True, row_stride=rstride)
-        cst = scene.stats()
-        scene.set_option(capi.OPTION_COUNT_TRAVERSAL, 0)
-        out = None
-        if rank == 0:
-            samples_per_step = (w * h if (world > 1 or rstride == 1) else len(range(r0, r1, rstride)) * w) * rs.spp  # (a share leg on one GPU counts the share's samples)
-            value = samples_per_step * steps / dt / 1e6
+        if args.dump_outputs and main_line and rank == 0:  # before any further render of this scene reuses the buffer
+            dump_outputs(args.dump_outputs, last["img"])
+        if args.full:
+            # --- roofline inputs: one extra (untimed) step with the traversal counters on
+            scene.set_option(capi.OPTION_COUNT_TRAVERSAL, 1)
+            scene.render(rs, w, h, rows=(r0, r1), device_only=True, row_stride=rstride)
+            cst = scene.stats()
+            scene.set_option(capi.OPTION_COUNT_TRAVERSAL, 0)
+
+        def roofline_of(samples_per_step):
+            """The roofline object of the line and the raw counters of the side file (--full): the timed steps' stage clocks, the counting step,
+            and at N = 1 the live --pmc passes (which close the scene first)."""
+            nonlocal scene
             # dominant traversal kernel k_trace<closest>: algorithmic bytes per launch (SURVEY 8d): ray 32 + hit 20 per ray,
             # 80 B per BVH8 node visited, 48 B per triangle tested; divided by its mean launch time (HIP events).
             launches = sum(s["traceLaunches"] for s in tstats)  # traceMs is the sampled total scaled to all launches
@@ -475,15 +502,22 @@ def main():
                                     "l2_hit": round(v.get("TCC_HIT_sum", 0.0) / (v.get("TCC_HIT_sum", 0.0) + v.get("TCC_MISS_sum", 0.0)), 4) if (v.get("TCC_HIT_sum", 0.0) + v.get("TCC_MISS_sum", 0.0)) else None,
                                     "fetch_GB": round(v.get("FETCH_SIZE", 0.0) * 1024.0 / 1e9, 3), "write_GB": round(v.get("WRITE_SIZE", 0.0) * 1024.0 / 1e9, 3)}
                                 for k, v in sorted(pmc.items(), key=lambda kv: -kv[1].get("pmc_us", 0.0) * kv[1].get("dispatches", 0))[:10]}
+            return roofline, raw
+
+        out = None
+        if rank == 0:
+            samples_per_step = (w * h if (world > 1 or rstride == 1) else len(range(r0, r1, rstride)) * w) * rs.spp  # (a share leg on one GPU counts the share's samples)
+            value = samples_per_step * steps / dt / 1e6
+            seg_per_sample = sum(s["segments"] for s in tstats) / max(1, sum(s["samples"] for s in tstats))
             out = {"metric": "Msamples/s (spp x pixels / s) at 8 bounces, 1920x1080", "value": round(value, 2), "unit": "Msamples/s",
                    "n_gpus": args.gpus if args.in_process else world, "steps": steps, "warmup": warmup, "ms_per_step": round(dt * 1e3 / steps, 3),
                    "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
                    "config": {"workload": label, "width": w, "height": h, "spp": rs.spp, "max_bounces": rs.max_bounces,
                               "parallelism": f"rows-interleaved{world}" if world > 1 else (f"in-process rows-interleaved{args.gpus}" if args.in_process and args.gpus > 1 else "single"), "segments_per_sample": round(seg_per_sample, 4),
-                              "triangles": cst["triangleCount"], "bvh8_nodes": cst["nodeCount"], "iterations_per_step": stats[-1]["iterations"]},
-                   "roofline": roofline}
+                              "triangles": stats[-1]["triangleCount"], "bvh8_nodes": stats[-1]["nodeCount"], "iterations_per_step": stats[-1]["iterations"]}}
+            if args.full:
+                out["roofline"], out["_raw"] = roofline_of(samples_per_step)
             out.update(R["first"])  # build_ms / upload_ms / first_frame_ms (outside the timed region)
-            out["_raw"] = raw
             if os.environ.get("GATLING_BENCH_CHECKSUM"):  # tests: the frame rank 0 ends up with (host memory), as a checksum
                 import hashlib
                 img = last["img"]
@@ -497,12 +531,12 @@ def main():
     if args.probe:
         return
     raws = {}
-    if out is not None:
+    if out is not None and args.full:
         raws[args.workload] = out.pop("_raw", {})
         for k in ("calibration", "valu_calibration"):  # constants of the calibration files: kept in the side file, not in the line
             if k in out["roofline"]:
                 raws[args.workload][k] = out["roofline"].pop(k)
-    if out is not None and world == 1 and not args.no_cpu_baseline:
+    if out is not None and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(R["desc"], R["rs"], R["w"], R["h"])
         out["cpu_baseline"]["reference"] = reference_probe()
     # Further measurements in the same line ("also"), so the driver's record covers every BASELINE config a single GPU can run:
@@ -512,7 +546,7 @@ def main():
     #   N = 8: the tiled 4K interior itself.
     # Each leg is a COMPACT object (value, ms_per_step, stage times, roofline fractions); raw counters and per-kernel tables go to profiles/bench_last_pmc.json.
     # Every rank takes part (collectives inside); a failure is reported in the line instead of losing the headline number.
-    also = os.environ.get("GATLING_BENCH_ALSO", ("c1,c3,c4,c5share,c5@64" if args.workload == "c2" and not args.spp else "") if world == 1 else ("c5" if world >= 8 else ""))
+    also = os.environ.get("GATLING_BENCH_ALSO", ("c1,c3,c4,c5share,c5@64" if args.workload == "c2" and not args.spp else "") if world == 1 else ("c5" if world >= 8 else "")) if args.full else ""
     extras = []
     for wl_spec in [x for x in also.split(",") if x and x != args.workload]:
         wl, _, wl_spp = wl_spec.partition("@")  # "c5@64": the workload at a reduced spp (the whole 4K frame of C5 on ONE GPU is 8.5 G samples at its own spp)
@@ -541,7 +575,7 @@ def main():
         extras.append(extra)
     # The delegate's own default workload (hdGatling: ONE sample per pixel and giRender call, 13 bounces, progressive accumulation, renderDelegate.cpp:93-110):
     # milliseconds of one blocking giCRender call incl. the D2H of the colour AOV, bounce-loop iterations per call -- compact legs c3@spp1 / c4@spp1 (tools/lowspp.py)
-    if out is not None and world == 1 and args.workload == "c2" and not args.spp and not os.environ.get("GATLING_BENCH_ALSO"):
+    if out is not None and world == 1 and args.full and args.workload == "c2" and not args.spp and not os.environ.get("GATLING_BENCH_ALSO"):
         try:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import lowspp
@@ -557,14 +591,15 @@ def main():
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
-    if out is not None:
-        import ctypes
+    if out is not None and args.full:
         for d in (os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")):  # (gpurun_out/ is what travels back from a GPU box)
             try:
                 if os.path.isdir(d):
                     json.dump(raws, open(os.path.join(d, "bench_last_pmc.json"), "w"), indent=1)
             except Exception:  # noqa: BLE001
                 pass
+    if out is not None:
+        import ctypes
         sys.stderr.flush()
         ctypes.CDLL(None).fflush(None)  # flush C stdio (RCCL prints a version banner there) so the JSON is the LAST line
         print(json.dumps(out), flush=True)

@@ -133,7 +133,7 @@ def test_bench_distributed_path_on_rccl_one_rank(gi):
     """bench.py's N>1 code path -- strided device view of the library's render buffer, RowGather over RCCL ("nccl" backend), pinned D2H
     on rank 0 -- driven on ONE GPU with a world of one (GATLING_BENCH_FORCE_DIST), and its image checksum against the plain path."""
     args = ["--workload", "c1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-pmc"]
-    out_d, jd = _run_bench({"GATLING_BENCH_FORCE_DIST": "1", "GATLING_BENCH_CHECKSUM": "1", "GATLING_BENCH_ALSO": "c2", "GATLING_BENCH_ALSO_SPP": "4"}, args)
+    out_d, jd = _run_bench({"GATLING_BENCH_FORCE_DIST": "1", "GATLING_BENCH_CHECKSUM": "1", "GATLING_BENCH_ALSO": "c2", "GATLING_BENCH_ALSO_SPP": "4"}, args + ["--full"])
     out_s, js = _run_bench({"GATLING_BENCH_CHECKSUM": "1"}, args)
     assert out_d.returncode == 0 and jd is not None, out_d.stdout[-2000:] + out_d.stderr[-2000:]
     assert out_s.returncode == 0 and js is not None, out_s.stdout[-2000:] + out_s.stderr[-2000:]

@@ -62,11 +62,11 @@ overlap)  # two-stream evidence: kernel trace of spp-1 calls with and without th
   done
   ;;
 bench)
-  timeout 2400 python bench.py ${BENCH_ARGS:-} > $O/${TAG}_bench_c2.log 2>&1; tail -1 $O/${TAG}_bench_c2.log | python -c "$J"
+  timeout 2400 python bench.py --full ${BENCH_ARGS:-} > $O/${TAG}_bench_c2.log 2>&1; tail -1 $O/${TAG}_bench_c2.log | python -c "$J"
   cp $O/bench_last_pmc.json $O/${TAG}_bench_pmc.json 2>/dev/null
   ;;
 benchquick)  # no PMC passes, no CPU baseline
-  timeout 900 python bench.py --no-pmc --no-cpu-baseline > $O/${TAG}_benchq_c2.log 2>&1; tail -1 $O/${TAG}_benchq_c2.log | python -c "$J"
+  timeout 900 python bench.py --full --no-pmc --no-cpu-baseline > $O/${TAG}_benchq_c2.log 2>&1; tail -1 $O/${TAG}_benchq_c2.log | python -c "$J"
   ;;
 prof)  # rocprofv3 --kernel-trace --stats of the bench command, per workload -> profiles/<tag>_<w>_rocprofv3_summary.*
   for WS in ${PROF_WORKLOADS:-c2:1024 c3:256 c4:256}; do W=${WS%%:*}; S=${WS##*:}
