@@ -22,6 +22,7 @@ GI_C_OK = 0
 AOV_COLOR = 0
 FORMAT_INT32, FORMAT_FLOAT32, FORMAT_FLOAT32_VEC4 = 0, 1, 2
 OPTION_COUNT_TRAVERSAL, OPTION_KERNEL_TIMERS, OPTION_POOL_SLOTS, OPTION_SAMPLE_BUFFER_MB, OPTION_TRACE_DYNAMIC, OPTION_TWO_LEVEL, OPTION_FUSED_PATH, OPTION_DEVICES = 1, 2, 3, 4, 5, 6, 7, 8
+OPTION_BVH_BUILD = 9  # 0 = host BVH builder (default), 1 = device builder (flat-layout scenes of more than 128 triangles)
 
 
 class GiCCameraDesc(C.Structure):
@@ -149,6 +150,7 @@ SYMBOLS = [
     ("giCDebugCheckSqrt", C.c_int64, [C.c_uint32, C.c_uint64]),
     ("giCDebugValidateBvh", C.c_int, [_FP, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("giCDebugValidatePartitionedBvh", C.c_int, [_FP, _U, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("giCDebugValidateSceneBvh", C.c_int, [_P, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     ("giCDebugTexRuntime", C.c_int, [_FP, _U, _U, _U, _U, _FP, _FP]),
 ]
 
@@ -447,6 +449,15 @@ class Scene:
         if rc < 0:
             raise GiError("giCTraceRays failed: " + self.L.giCGetLastError().decode())
         return tuv, ip
+
+    def validate_bvh(self, device: int = 0) -> dict:
+        """giCDebugValidateSceneBvh: the tree resident on `device` (0 = primary) of a scene rendered at least once, downloaded and checked.
+        Returns {"violations", "nodes", "depth", "device_built", "digest"}."""
+        nodes, depth, built, digest = C.c_uint32(0), C.c_uint32(0), C.c_int32(0), C.c_uint64(0)
+        v = self.L.giCDebugValidateSceneBvh(self.handle, device, C.byref(nodes), C.byref(depth), C.byref(built), C.byref(digest))
+        if v < 0:
+            raise GiError("giCDebugValidateSceneBvh failed: " + self.L.giCGetLastError().decode())
+        return {"violations": v, "nodes": nodes.value, "depth": depth.value, "device_built": bool(built.value), "digest": digest.value}
 
     def close(self):
         if self.handle:

@@ -1,6 +1,7 @@
 // gi_build.cpp -- scene build (flatten, pack, BVH8, two-level layout, upload) and incremental transform updates (Gi.cpp:784-1315)
 // (one of the translation units gi_c.cpp was split into in round 6; shared declarations: gi_host.h)
 #include "gi_host.h"
+#include "gi_bvh_build.h"
 
 // ---------------------------------------------------------------------------------------------------------------
 // scene build: flatten instances into world space, pack vertex data, build + upload the BVH8
@@ -215,7 +216,8 @@ int uploadSceneTo(GiCScene* s, SceneDevice& D, const SceneHost& H)
         D.dInstTrav.upload(H.two.instTrav, st) || D.dFlatOfOrig.upload(H.flatOfOrig, st))
       return GI_C_ERROR;
   }
-  if (D.dTriFaceId.upload(H.triFaceId, st) || D.dTriShade.upload(H.triShade, st) || D.dTriGeomNormal.upload(H.triGeomNormal, st)) return GI_C_ERROR;
+  if ((!H.deviceBuilt && D.dTriFaceId.upload(H.triFaceId, st)) || D.dTriShade.upload(H.triShade, st) || D.dTriGeomNormal.upload(H.triGeomNormal, st))
+    return GI_C_ERROR;
   if (D.dMeshes.upload(H.meshRecs, st) || D.dSceneData.upload(H.sceneData, st)) return GI_C_ERROR;
   { // textures: one device array per image + the TextureRec table
     for (auto* b : D.dTexels) { b->release(); delete b; }
@@ -230,9 +232,8 @@ int uploadSceneTo(GiCScene* s, SceneDevice& D, const SceneHost& H)
     if (D.dTextures.upload(recs, st)) return GI_C_ERROR;
     HIP_TRY(hipStreamSynchronize(st)); // `recs` goes out of scope
   }
-  if (D.dNodes.upload(H.bvh.nodes, st) || D.dTris.upload(H.bvh.tris, st) || D.dInstances.upload(H.instances, st) ||
-      D.dVerts.upload(H.verts, st) || D.dMaterials.upload(H.mats, st))
-    return GI_C_ERROR;
+  if (!H.deviceBuilt && (D.dNodes.upload(H.bvh.nodes, st) || D.dTris.upload(H.bvh.tris, st))) return GI_C_ERROR; // (device-built: the builder writes them)
+  if (D.dInstances.upload(H.instances, st) || D.dVerts.upload(H.verts, st) || D.dMaterials.upload(H.mats, st)) return GI_C_ERROR;
   HIP_TRY(hipStreamSynchronize(st)); // host vectors may go out of scope
   return GI_C_OK;
 }
@@ -259,6 +260,114 @@ static void setSceneBounds(GiCScene* s, const std::vector<Node8>& nodes)
     s->bounds[a] = b[a] - pad; s->bounds[3 + a] = b[3 + a] + pad;
   }
   s->boundsValid = true;
+}
+
+// one line per mesh with inactive triangles (bvh8.h "Inactive items"); perMesh[meshIdx] = its inactive count
+static void warnInactive(const std::vector<MeshBuild>& meshBuilds, const std::vector<uint32_t>& perMesh)
+{
+  for (const MeshBuild& mb : meshBuilds)
+    if (perMesh[mb.meshIdx]) fprintf(stderr, "[gatling_gi] warning: mesh %s: %u of %zu instanced triangle(s) have a non-finite or out-of-range (> 1e18) "
+                                              "vertex or a non-invertible transform and are inactive\n",
+                                     mb.m->name.c_str(), perMesh[mb.meshIdx], mb.m->faces.size() * (size_t)mb.instCount);
+}
+
+// Scenes beyond LDS: one 160-byte shading record per mesh triangle (gi_types.h TriShade), meshes in build order; returns each mesh's first record by meshIdx
+static std::vector<uint32_t> buildShadeRecords(SceneHost& H)
+{
+  std::vector<uint32_t> shadeBaseOfMesh(H.meshBuilds.size(), 0u);
+  for (MeshBuild& mb : H.meshBuilds) {
+    mb.shadeBase = (uint32_t)H.triShade.size(); shadeBaseOfMesh[mb.meshIdx] = mb.shadeBase;
+    const GiCMesh* m = mb.m;
+    for (const GiCFace& f : m->faces) {
+      TriShade q{};
+      for (int k = 0; k < 3; k++) {
+        const GiCVertex v = usableShadingAttributes(m->vertices[f.v_i[k]]);
+        // (Gi.cpp:848-861: quantised, then decoded once)
+        memcpy(q.p[k], v.pos, 12); decodeDirection(encodeDirection(v.norm), q.n[k]); decodeDirection(encodeDirection(v.tangent), q.t[k]);
+        q.uv[k][0] = v.u; q.uv[k][1] = v.v; q.bsign[k] = v.bitangentSign; q.vi[k] = mb.vertexOffset + f.v_i[k];
+      }
+      H.triShade.push_back(q);
+    }
+  }
+  return shadeBaseOfMesh;
+}
+
+// The device builder's side of buildScene (GI_C_SCENE_OPTION_BVH_BUILD; gi_bvh_build.hip): the flattened scene-order triangles and face ids are uploaded to
+// every device and each device builds its own tree over them (the builder is deterministic: the copies are identical).  Nothing of the tree is kept on the
+// host.  Returns GI_C_OK / GI_C_ERROR, or DEVICE_BUILD_FALLBACK when the host builder must take over (out of device memory, a tree deeper than the traversal
+// stack): not an error.
+constexpr int DEVICE_BUILD_FALLBACK = 1;
+static int buildSceneOnDevice(GiCScene* s, std::unique_ptr<SceneHost>& hostPtr, std::vector<TriRec>& tris, const std::vector<int32_t>& faceIdOf, double t0)
+{
+  SceneHost& H = *hostPtr;
+  const uint32_t n = (uint32_t)tris.size();
+  // inactive triangles by bvh8.cpp's rule (prepareRange), counted here as well: the statistic and the per-mesh warnings are the host path's
+  uint32_t inactive = 0;
+  std::vector<uint32_t> perMesh(H.meshBuilds.size(), 0u);
+  for (const TriRec& t : tris) {
+    bool ok = true;
+    for (int a = 0; a < 3; a++) ok = ok && usableCoordinate(t.v0[a]) && usableCoordinate(t.v0[a] + t.e1[a]) && usableCoordinate(t.v0[a] + t.e2[a]);
+    if (!ok) { inactive++; perMesh[H.instances[t.instance].mesh]++; }
+  }
+  s->twoLevel = false;
+  // (bvhBuildMs / uploadMs split as on the host path: flattening and the build, then the shading records and the uploads)
+  double buildMs = nowMs() - t0;
+  // beyond LDS by construction (more than 128 triangles): shading records, and TriRec::vi[0] names the triangle's record -- set in scene order, the gather
+  // carries it along
+  H.shadePacked = true; H.triShade.clear(); H.triGeomNormal.clear();
+  const std::vector<uint32_t> shadeBaseOfMesh = buildShadeRecords(H);
+  for (TriRec& t : tris) t.vi[0] = shadeBaseOfMesh[H.instances[t.instance].mesh] + t.prim;
+  H.deviceBuilt = true;
+  const bool timing = getenv("GATLING_BUILD_TIMING") != nullptr;
+  double uploadMs = nowMs() - t0 - buildMs;
+  const uint32_t nDev = sceneDeviceCount(s);
+  while (s->replicas.size() + 1u < nDev) { s->replicas.emplace_back(new SceneDevice()); s->replicas.back()->slot = (uint32_t)s->replicas.size();
+      s->dirty |= DIRTY_LIGHTS; }
+  DeviceBvhResult first;
+  for (uint32_t d = 0; d < nDev; d++) {
+    SceneDevice& D = sceneDevice(s, d);
+    const double ta = nowMs();
+    if (uploadSceneTo(s, D, H) != GI_C_OK) { (void)hipSetDevice(g_ctx.device); return GI_C_ERROR; }
+    hipStream_t st = g_ctx.devs[D.slot].stream;
+    if (D.dTris.upload(tris, st) || D.dTriFaceId.upload(faceIdOf, st)) { (void)hipSetDevice(g_ctx.device); return GI_C_ERROR; }
+    HIP_TRY(hipStreamSynchronize(st));
+    const double tb = nowMs();
+    DeviceBvhResult r;
+    const int rc = buildBvh8Device(st, D.dTris.ptr, D.dTriFaceId.ptr, n, 1u + 8u + 40u, r);
+    uploadMs += tb - ta; buildMs += nowMs() - tb;
+    if (rc == DEVICE_BVH_OUT_OF_MEMORY || rc == DEVICE_BVH_TOO_DEEP) {
+      if (timing || rc == DEVICE_BVH_TOO_DEEP) fprintf(stderr, "[gatling_gi] device BVH build on device %u: %s; the host builder takes over\n", d,
+          rc == DEVICE_BVH_TOO_DEEP ? "the tree is deeper than the traversal stack (49 levels)" : "out of device memory");
+      for (uint32_t k = 0; k <= d; k++) sceneDevice(s, k).dNodes.release(); // (no tree of the wrong shape left behind)
+      H.deviceBuilt = false; H.triShade.clear();
+      (void)hipSetDevice(g_ctx.device);
+      return DEVICE_BUILD_FALLBACK;
+    }
+    if (rc != DEVICE_BVH_OK) { setError(std::string("device BVH build failed: ") + r.error); (void)hipSetDevice(g_ctx.device); return GI_C_ERROR; }
+    D.dNodes.release(); D.dNodes.ptr = r.nodes; D.dNodes.count = r.nodeCount;
+    if (d == 0) first = r;
+    else if (r.nodeCount != first.nodeCount || r.maxDepth != first.maxDepth) { setError("internal: device BVH builds differ between devices");
+        (void)hipSetDevice(g_ctx.device); return GI_C_ERROR; }
+    if (timing) fprintf(stderr, "[gatling_gi] device bvh8 (device %u): boxes %.1f ms, sort %.1f ms, PLOC + collapse DP %.1f ms (%u passes; the DP is filled by "
+                                "the merge kernel), emission %.1f ms (%u levels, %u nodes, %u active of %u triangles)\n", d, r.ms[0], r.ms[1], r.ms[2],
+                        r.plocIterations, r.ms[3], r.maxDepth, r.nodeCount, r.activeTris, n);
+  }
+  HIP_TRY(hipSetDevice(g_ctx.device));
+  if (first.activeTris != n - inactive) { setError("internal: device and host disagree on the inactive triangles"); return GI_C_ERROR; }
+  s->stats.inactiveTriangleCount = inactive;
+  if (inactive) warnInactive(H.meshBuilds, perMesh);
+  H.bvh = Bvh8{}; H.bvh.maxDepth = first.maxDepth; H.bvh.activeTris = first.activeTris;
+  H.triFaceId.clear(); H.flatOfOrig.clear();
+  s->shadePacked = true;
+  s->shadowOrder = -1; s->shadowOrderRays[0] = s->shadowOrderRays[1] = s->shadowOrderSteps[0] = s->shadowOrderSteps[1] = 0;
+  s->nodeCount = first.nodeCount; s->triCount = n; s->bvhDepth = first.maxDepth > 1u ? first.maxDepth - 1u : 1u;
+  setSceneBounds(s, std::vector<Node8>{first.root});
+  s->stats.bvhBuildMs = buildMs; s->stats.uploadMs = uploadMs;
+  s->stats.nodeCount = s->nodeCount; s->stats.triangleCount = s->triCount;
+  if (timing) fprintf(stderr, "[gatling_gi] scene (device build): %u nodes, %u triangles, %u levels (traversal stack need %u)\n", s->nodeCount, s->triCount,
+      first.maxDepth, s->bvhDepth);
+  s->host = std::move(hostPtr);
+  return GI_C_OK;
 }
 
 int buildScene(GiCScene* s)
@@ -383,6 +492,16 @@ int buildScene(GiCScene* s)
     }
     meshIdx++;
   }
+  { // the device builder (GI_C_SCENE_OPTION_BVH_BUILD / device_build): scenes that take the flat layout and do not fit LDS.  (Fewer triangles than 2^32 / 80
+    // bytes: the automatic two-level rules below cannot apply -- an 8-wide tree has fewer nodes than triangles.)
+    const long want = optionValue("device_build", -1);
+    const bool device = (want < 0 ? s->optBvhBuild == 1 : want == 1) && tris.size() > 128u && optionValue("two_level", s->optTwoLevel) <= 0
+        && tris.size() * sizeof(Node8) < ((size_t)1 << 32);
+    if (device) {
+      const int rc = buildSceneOnDevice(s, hostPtr, tris, faceIdOf, t0);
+      if (rc != DEVICE_BUILD_FALLBACK) return rc;
+    }
+  }
   Bvh8& bvh = H.bvh;
   buildBvh8(tris, bvh);
   { std::vector<TriRec>().swap(tris); } // the BVH holds its own (leaf-ordered) copy
@@ -390,10 +509,7 @@ int buildScene(GiCScene* s)
   if (bvh.activeTris < bvh.tris.size()) { // one line per mesh (bvh8.h "Inactive items")
     std::vector<uint32_t> perMesh(meshBuilds.size(), 0u);
     for (size_t i = bvh.activeTris; i < bvh.tris.size(); i++) perMesh[instances[bvh.tris[i].instance].mesh]++;
-    for (const MeshBuild& mb : meshBuilds)
-      if (perMesh[mb.meshIdx]) fprintf(stderr, "[gatling_gi] warning: mesh %s: %u of %zu instanced triangle(s) have a non-finite or out-of-range (> 1e18) "
-                                                "vertex or a non-invertible transform and are inactive\n",
-                                       mb.m->name.c_str(), perMesh[mb.meshIdx], mb.m->faces.size() * (size_t)mb.instCount);
+    warnInactive(meshBuilds, perMesh);
   }
   if (buildTwoLevel(s, meshBuilds, instances, bvh.tris.size(), bvh.nodes.size(), H.two) != GI_C_OK) return GI_C_ERROR;
   if (s->twoLevel) {
@@ -420,21 +536,7 @@ int buildScene(GiCScene* s)
   H.shadePacked = bvh.nodes.size() > 384u || bvh.tris.size() > 128u;
   H.triShade.clear();
   if (H.shadePacked) {
-    std::vector<uint32_t> shadeBaseOfMesh(meshBuilds.size(), 0u);
-    for (MeshBuild& mb : meshBuilds) {
-      mb.shadeBase = (uint32_t)H.triShade.size(); shadeBaseOfMesh[mb.meshIdx] = mb.shadeBase;
-      const GiCMesh* m = mb.m;
-      for (const GiCFace& f : m->faces) {
-        TriShade q{};
-        for (int k = 0; k < 3; k++) {
-          const GiCVertex v = usableShadingAttributes(m->vertices[f.v_i[k]]);
-          // (Gi.cpp:848-861: quantised, then decoded once)
-          memcpy(q.p[k], v.pos, 12); decodeDirection(encodeDirection(v.norm), q.n[k]); decodeDirection(encodeDirection(v.tangent), q.t[k]);
-          q.uv[k][0] = v.u; q.uv[k][1] = v.v; q.bsign[k] = v.bitangentSign; q.vi[k] = mb.vertexOffset + f.v_i[k];
-        }
-        H.triShade.push_back(q);
-      }
-    }
+    const std::vector<uint32_t> shadeBaseOfMesh = buildShadeRecords(H);
     for (TriRec& t : bvh.tris) t.vi[0] = shadeBaseOfMesh[instances[t.instance].mesh] + t.prim;
   }
   // LDS-resident scenes (the fused kernels' and k_trace's shading path reads FVertex records): the world-space geometric normal of every flattened triangle,
@@ -595,6 +697,7 @@ int updateTransforms(GiCScene* s, bool& handled)
           parts.push_back(P); }
     }
     if (parts.empty()) return GI_C_OK;
+    if (H.deviceBuilt) { H.bvh.tris.resize(s->triCount); H.triFaceId.resize(s->triCount); } // (a device-built tree has no host copy: placePart fills them)
     std::vector<PartBuild> built(parts.size());
     parallelOver(parts.size(), [&](size_t i) { buildPart(H.meshBuilds[parts[i].meshBuild], parts[i].instInMesh, H.shadePacked, built[i]); });
     H.topCap = (uint32_t)parts.size() * 2u + 16u; // top nodes <= internal top nodes + one copied root per part
@@ -604,7 +707,7 @@ int updateTransforms(GiCScene* s, bool& handled)
     H.bvh.nodes.assign(off, Node8{});
     H.parts.swap(parts);
     parallelOver(H.parts.size(), [&](size_t i) { placePart(H, H.parts[i], built[i]); });
-    H.partitioned = true; converted = true;
+    H.partitioned = true; converted = true; H.deviceBuilt = false; // host-built from here on; the upload below sends every array
   } else {
     for (uint32_t i = 0; i < (uint32_t)H.parts.size(); i++) {
       const GiCMesh* m = H.meshBuilds[H.parts[i].meshBuild].m;

@@ -190,6 +190,80 @@ extern "C" int giCDebugValidatePartitionedBvh(const float* triVerts, uint32_t tr
   return validateTree(nodes, trisAll, triCount);
 }
 
+// giCDebugValidateSceneBvh: the tree a device holds for a built scene -- whichever builder made it -- downloaded, checked and hashed
+extern "C" int giCDebugValidateSceneBvh(const GiCScene* scene, uint32_t deviceIndex, uint32_t* outNodeCount, uint32_t* outMaxDepth, int32_t* outBuiltOnDevice,
+    uint64_t* outDigest)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!g_ctx.initialized || !s) { setError("giCDebugValidateSceneBvh: bad arguments"); return -1; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  if (!s->host) { setError("giCDebugValidateSceneBvh: the scene has not been built (render it once)"); return -1; }
+  if (deviceIndex > s->replicas.size() || deviceIndex >= sceneDeviceCount(s)) { setError("giCDebugValidateSceneBvh: no such device copy"); return -1; }
+  SceneDevice& D = sceneDevice(s, deviceIndex);
+  const uint32_t nodeCount = s->nodeCount, triCount = s->triCount;
+  std::vector<Node8> nodes(nodeCount); std::vector<TriRec> tris(triCount);
+  if (hipSetDevice(g_ctx.devs[D.slot].device) != hipSuccess || D.dNodes.count < nodeCount || D.dTris.count < triCount ||
+      (nodeCount && hipMemcpy(nodes.data(), D.dNodes.ptr, (size_t)nodeCount * sizeof(Node8), hipMemcpyDeviceToHost) != hipSuccess) ||
+      (triCount && hipMemcpy(tris.data(), D.dTris.ptr, (size_t)triCount * sizeof(TriRec), hipMemcpyDeviceToHost) != hipSuccess)) {
+    (void)hipSetDevice(g_ctx.device); setError("giCDebugValidateSceneBvh: download failed"); return -1;
+  }
+  (void)hipSetDevice(g_ctx.device);
+  // digest of the node and triangle bytes (64-bit FNV-1a over 8-byte words)
+  uint64_t h = 0xcbf29ce484222325ull;
+  auto mix = [&h](const void* p, size_t bytes) { const uint8_t* b = (const uint8_t*)p;
+      for (size_t i = 0; i + 8 <= bytes; i += 8) { uint64_t w; memcpy(&w, b + i, 8); h = (h ^ w) * 0x100000001b3ull; } };
+  mix(nodes.data(), nodes.size() * sizeof(Node8)); mix(tris.data(), tris.size() * sizeof(TriRec));
+  int violations = 0;
+  // depth, and every internal child after its parent (both layouts place children behind their parent, which also keeps the walks below finite)
+  uint32_t maxDepth = 0;
+  if (nodeCount) {
+    std::vector<uint32_t> depth(nodeCount, 0u); depth[0] = 1u;
+    for (uint32_t i = 0; i < nodeCount; i++) {
+      if (depth[i] == 0u) continue; // (partitioned layout: reserved, unused node slots)
+      maxDepth = std::max(maxDepth, depth[i]);
+      const uint32_t internal = (uint32_t)__builtin_popcount(nodes[i].imask);
+      for (uint32_t k = 0; k < internal; k++) {
+        const uint64_t c = (uint64_t)nodes[i].childBase + k;
+        if (c <= i || c >= nodeCount) { violations++; continue; }
+        depth[c] = depth[i] + 1u;
+      }
+    }
+  }
+  if (maxDepth > 1u + 8u + 40u) violations++;
+  uint32_t activeTris = triCount;
+  if (!s->host->partitioned) {
+    // breadth-first: in index order, every node's internal children are the next unassigned indices and its leaf triangles the next unreferenced ones
+    uint32_t nextChild = 1, nextTri = 0;
+    for (uint32_t i = 0; i < nodeCount; i++) {
+      const Node8& n = nodes[i];
+      const uint32_t internal = (uint32_t)__builtin_popcount(n.imask);
+      if (internal && n.childBase != nextChild) violations++;
+      nextChild += internal;
+      if (n.triBase != nextTri) violations++;
+      uint32_t off = 0;
+      for (int sl = 0; sl < 8; sl++) {
+        if (n.meta[sl] == 0 || ((n.imask >> sl) & 1u)) continue;
+        const uint32_t unary = n.meta[sl] >> 5, cnt = unary == 1u ? 1u : unary == 3u ? 2u : unary == 7u ? 3u : 0u;
+        if ((n.meta[sl] & 31u) != off) violations++;
+        off += cnt;
+      }
+      nextTri = n.triBase + off;
+    }
+    if (nextChild != nodeCount || nextTri > triCount) violations++;
+    activeTris = std::min(nextTri, triCount);
+    // every active id once in [0, activeTris); the inactive ones behind, ids in increasing (input) order
+    std::vector<uint8_t> seen(triCount, 0);
+    for (uint32_t k = 0; k < activeTris; k++) { const uint32_t id = tris[k].origId; if (id >= triCount || seen[id]) violations++; else seen[id] = 1; }
+    for (uint32_t k = activeTris; k < triCount; k++) if (tris[k].origId >= triCount || (k > activeTris && tris[k].origId <= tris[k - 1].origId)) violations++;
+  }
+  if (violations == 0) violations = validateTree(nodes, tris, triCount); // (reachability + conservativeness; needs a well-formed tree)
+  if (outNodeCount) *outNodeCount = nodeCount;
+  if (outMaxDepth) *outMaxDepth = maxDepth;
+  if (outBuiltOnDevice) *outBuiltOnDevice = s->host->deviceBuilt ? 1 : 0;
+  if (outDigest) *outDigest = h;
+  return violations;
+}
+
 // giCDebugShadeClass: which k_shade variant an (untextured) material's hits are binned for -- host only
 extern "C" int giCDebugShadeClass(const GiCMaterialDesc* desc)
 {

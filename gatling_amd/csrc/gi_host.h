@@ -254,6 +254,8 @@ struct SceneHost {
   std::vector<F4> triGeomNormal; // LDS-resident scenes: per flattened triangle (gi_build.cpp)
   std::vector<TriShade> triShade; bool shadePacked = false; // one-line shading records per mesh triangle (scenes beyond LDS): TriRec::vi[0] indexes them
   bool partitioned = false; std::vector<InstPart> parts; uint32_t topCap = 0; // partitioned layout: nodes [0, topCap) = top tree, then the parts' ranges
+  // the device builder made the tree: it exists only in device memory (dNodes / dTris / dTriFaceId); `bvh` keeps its sizes (maxDepth, activeTris) alone
+  bool deviceBuilt = false;
 };
 
 struct GiCScene : SceneDevice {
@@ -279,6 +281,7 @@ struct GiCScene : SceneDevice {
   // the scene as built (the same on every device)
   uint32_t nodeCount = 0, triCount = 0, bvhDepth = 0;
   float bounds[6] = {0, 0, 0, 0, 0, 0}; bool boundsValid = false; // the flat tree's root bounds (nodeBounds + a relative pad), for FLAG_BOUNDS_RETIRE
+  int optBvhBuild = 0; // GI_C_SCENE_OPTION_BVH_BUILD: 1 = the device builder for flat-layout scenes beyond LDS (gi_bvh_build.hip)
   bool twoLevel = false; int optTwoLevel = -1; // 1: build and use the two-level layout (scenes beyond LDS); otherwise the flat one
   bool hasCutouts = false;
   bool shadePacked = false; // the built scene carries TriShade records (beyond LDS)

@@ -24,6 +24,9 @@
 //   assume_free_mb       0         tests: plan as if this many MiB were free on the device
 //   incremental          1         transform-only edits update the tree in place
 //   bvh_collapse         1         1 = cost-optimal collapse to 8-wide nodes, 0 = greedy
+//   device_build         -1        -1 = the scene option decides (GI_C_SCENE_OPTION_BVH_BUILD), 0 / 1 = force the host / the device BVH builder
+//                                  (flat-layout scenes of more than 128 triangles; read at build time)
+//   ploc_radius          16        device builder: PLOC's nearest-neighbour search radius (positions either side in Morton order, 1 .. 256)
 //   shadow_order         -1        visiting order of shadow walks: -1 = measured per scene (gi_render.cpp shadowOrder), 0 = near-to-far, 1 = slot order
 //   peer_copies          1         multi-device gather: 0 = stage every device's row share through pinned host memory even where peer access exists
 //   shade_variants       1         OpenPBR materials without optional lobes are binned and shaded by the BASE variant of k_shade (gi_shading.h);

@@ -318,7 +318,7 @@ int giCSetMaterialPrimvarInput(GiCMaterial* material, int32_t input, const char*
 /* [ext] per-frame statistics of the last giCRender on a scene (measurement) */
 typedef struct GiCRenderStats {
   double renderMs;       /* wall time of the bounce loop incl. final D2H of the colour AOV */
-  double bvhBuildMs;     /* host BVH8 build (0 if not rebuilt)                              */
+  double bvhBuildMs;     /* BVH8 build on whichever side ran it, host or device (GI_C_SCENE_OPTION_BVH_BUILD); 0 if not rebuilt */
   double uploadMs;       /* scene upload (0 if not rebuilt)                                 */
   double traceMs;        /* sum of closest-hit traversal kernel time (HIP events)           */
   double shadeMs;        /* sum of shade kernel time                                        */
@@ -355,8 +355,9 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
 /* [ext] Version of this header's ABI: bumped whenever a struct grows or an entry point changes meaning (5: GiCRenderStats gained batches / poolSlots, GI_C_TEX_SLOT_COUNT 9,
  * the subsurface radius slots of GiCMaterialDesc, the asset-reader / image-loader hooks; 6: GiCRenderStats.reserved0 became inactiveTriangleCount,
  * giCDebugShadeClass, an all-zero subsurface radius is no longer read as "unset", the hostile-input rules above giCRender;
- * 7: GI_C_P_COAT_ROTATION / GI_C_P_SPECULAR_ROTATION, slots that were reserved).  A caller compares giCGetApiVersion() with the GI_C_API_VERSION it was built with. */
-#define GI_C_API_VERSION 7u
+ * 7: GI_C_P_COAT_ROTATION / GI_C_P_SPECULAR_ROTATION, slots that were reserved; 8: GI_C_SCENE_OPTION_BVH_BUILD, giCDebugValidateSceneBvh, bvhBuildMs counts
+ * the device build when one ran).  A caller compares giCGetApiVersion() with the GI_C_API_VERSION it was built with. */
+#define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
 /* [ext] can the primary device and device `index` of the list address each other's memory?  1 = yes (peer access enabled both ways, or the same physical device):
@@ -478,6 +479,11 @@ int giCGetRenderStats(const GiCScene* scene, GiCRenderStats* out);
 #define GI_C_SCENE_OPTION_FUSED_PATH 7
 /* [ext] upper bound on the devices a giCRender of this scene uses (0 = all the library was initialised on; 1 = primary only). */
 #define GI_C_SCENE_OPTION_DEVICES 8
+/* [ext] who builds the flat BVH8: 0 (default) = the host builder; 1 = the device builder (Morton sort, PLOC, the same cost-optimal 8-wide collapse, written
+ * straight into device memory).  It applies to scenes that take the flat layout and have more than 128 flattened triangles; every other
+ * scene (the two-level layout, small LDS-resident scenes) keeps the host builder.  Out of device memory during the build falls back to the host builder.
+ * GATLING_OPTIONS=device_build=0|1 overrides it.  The image does not depend on it. */
+#define GI_C_SCENE_OPTION_BVH_BUILD 9
 int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value);
 /* [ext] closest hit of one ray through the device traversal kernel (parity tests of the BVH8 path).
  * Returns 1 on hit (t,u,v, instance, prim written), 0 on miss, <0 on error.  Candidates on cut-out materials pass the any-hit test of the render
@@ -509,6 +515,12 @@ int giCDebugValidateBvh(const float* triVerts, uint32_t triCount, uint32_t* outN
  * subtree each, joined by a top tree over the subtree roots.  Returns the violations of the assembled tree (0 = every triangle reachable and inside every
  * ancestor slot's box), <0 on error. */
 int giCDebugValidatePartitionedBvh(const float* triVerts, uint32_t triCount, uint32_t partCount, uint32_t* outNodeCount, uint32_t* outMaxDepth);
+/* [ext] the tree resident on device `deviceIndex` (0 = primary) of a scene rendered at least once, downloaded and checked: every active triangle reachable and
+ * inside every ancestor slot's box; and (flat, unpartitioned layout) nodes breadth-first, internal children contiguous in slot order at childBase, leaf
+ * triangles contiguous at triBase, every active id once in [0, activeTris), the inactive ones behind in id order; depth <= 49.  outBuiltOnDevice: 1 when the
+ * device builder made it; outDigest: a 64-bit hash of the node and triangle bytes.  Returns the number of violations, <0 on error. */
+int giCDebugValidateSceneBvh(const GiCScene* scene, uint32_t deviceIndex, uint32_t* outNodeCount, uint32_t* outMaxDepth, int32_t* outBuiltOnDevice,
+                             uint64_t* outDigest);
 
 #ifdef __cplusplus
 }
