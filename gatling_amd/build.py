@@ -13,7 +13,7 @@ OBJDIR = os.path.join(CSRC, "build")
 LIB = os.path.join(_HERE, "libgatling_gi.so")
 # the host side of the C ABI (gi_c.cpp until round 6): built with -fvisibility=hidden, the API keeps default visibility through gi_host.h
 HOST_SOURCES = ["gi_c.cpp", "gi_scene.cpp", "gi_textures.cpp", "gi_lights.cpp", "gi_build.cpp", "gi_render.cpp", "gi_debug.cpp"]
-SOURCES = HOST_SOURCES + ["gi_image.cpp", "bvh8.cpp", "gi_kernels.hip", "gi_trace.hip", "gi_shade.hip", "gi_aov.hip", "gi_path.hip", "gi_path_bw.hip", "gi_bvh_build.hip", "gtl_shim.cpp"]
+SOURCES = HOST_SOURCES + ["gi_image.cpp", "bvh8.cpp", "gi_kernels.hip", "gi_trace.hip", "gi_shade.hip", "gi_aov.hip", "gi_path.hip", "gi_bvh_build.hip", "gtl_shim.cpp"]
 HEADERS = ["gi_host.h", "gi_types.h", "gi_kernels.h", "gi_device_math.h", "gi_queues.h", "gi_traversal.h", "gi_texture.h", "gi_shading.h", "gi_stages.h", "gi_image.h", "gi_options.h", "bvh8.h", "gi_bvh_build.h",
            os.path.join("..", "..", "include", "gi_c.h"), os.path.join("..", "..", "include", "gtl", "gi", "Gi.h"),
            os.path.join("..", "..", "include", "gtl", "gb", "ParamTypes.h")]
@@ -21,8 +21,8 @@ HEADERS = ["gi_host.h", "gi_types.h", "gi_kernels.h", "gi_device_math.h", "gi_qu
 INCLUDE = os.path.join(_HERE, "..", "include")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-I", INCLUDE]
 # Kernel translation units: no SLP vectorisation.  The vectoriser packs pairs of independent fp32 operations into v_pk_mul / v_pk_add / v_pk_fma, which on
-# gfx950 issue at the rate of the scalar forms (tools/valu_calib.hip) but need their operands in aligned register pairs -- the packing costs v_mov's (k_path_bw:
-# 313 -> 153 static moves, k_trace_dyn 238 -> 161) and registers.  Measured (r03c): C2 7 034 -> 7 506 Msamples/s at spp 128, C3 / C4 unchanged.  Results are
+# gfx950 issue at the rate of the scalar forms (tools/valu_calib.hip) but need their operands in aligned register pairs -- the packing costs v_mov's (k_trace_dyn:
+# 238 -> 161 static moves) and registers.  Measured (r03c): C2 7 034 -> 7 506 Msamples/s at spp 128, C3 / C4 unchanged.  Results are
 # bit-identical (packed and scalar fp32 operations round the same way); the hand-written packed fma of the box test stays.
 KERNEL_FLAGS = ["-fno-slp-vectorize"]
 

@@ -1,4 +1,4 @@
-// bvh8.cpp -- binned-SAH BVH2 -> greedy collapse to 8-wide -> octant slot assignment -> 8-bit quantisation.
+// bvh8.cpp -- binned-SAH BVH2 -> cost-optimal collapse to 8-wide -> octant slot assignment -> 8-bit quantisation.
 //
 // Replaces the opaque driver build behind cgpuCreateBlas/cgpuCreateTlas
 // (/root/reference/src/cgpu/impl/CgpuVk.cpp:2561-2854, PREFER_FAST_TRACE at :2575).  Instances are flattened into
@@ -8,7 +8,6 @@
 // it, so the traversal kernel can never cull a triangle the exact Moeller-Trumbore test would accept.
 
 #include "bvh8.h"
-#include "gi_options.h"
 
 #include <algorithm>
 #include <cmath>
@@ -67,10 +66,9 @@ struct Builder {
 
   // (cutting the bottom 24 triangles of a subtree into full leaves of three by object-median splits -- nodes per ray 16.6 / 6.9 / 20.1 -> 16.0 / 6.8 / 20.0 on
   // C3 / C4 / C5 but triangles per ray 13.1 / 3.4 / 10.8 -> 18.5 / 5.1 / 22.4, traversal 8-20 % slower: SAH leaves win, r02)
-  // (not zero-initialised: 44 B per BVH2 node) filled bottom-up by build() when leafSize == 1 (each thread completes its own subtrees)
+  // (not zero-initialised: 44 B per BVH2 node) filled bottom-up by build() (each thread completes its own subtrees)
   std::unique_ptr<Dp[]> dp; float cPrim = 0.5f;
   uint32_t maxLeaf = kMaxLeaf;  // references a leaf slot may hold (1 for the top tree over subtrees: every leaf slot is then exactly one item)
-  uint32_t leafSize = kMaxLeaf; // the BVH2 stops splitting at this many references (1 for the cost-optimal collapse, which forms the leaves itself)
   const float* extBoxes = nullptr; size_t extCount = 0; // box mode (TLAS over instances, BLAS over pre-padded triangle boxes): 6 floats per item
   size_t itemCount() const { return extBoxes ? extCount : tris.size(); }
   // Items the tree does not hold (bvh8.h "Inactive items"): refs[0, activeCount) are the active ones after prepare(), `inactive` the rest in input order.
@@ -97,7 +95,7 @@ struct Builder {
     for (size_t i = 0; i < n; i++) { if (dead[i]) inactive.push_back((uint32_t)i); else refs[k++] = (uint32_t)i; }
     activeCount = k; refs.resize(k);
     nodes.assign(k ? 2 * k - 1 : 1, Node2{});
-    if (leafSize == 1u) dp.reset(new Dp[nodes.size()]);
+    dp.reset(new Dp[nodes.size()]);
   }
 
   // a coordinate the build can work with: finite and small enough that extents, areas and the padded planes stay far from overflow
@@ -136,7 +134,7 @@ struct Builder {
     Box box; box.reset(); Box cb; cb.reset();
     for (uint32_t i = first; i < first + count; i++) { box.grow(triBox[refs[i]]); cb.grow(&centroid[3 * refs[i]]); }
     nodes[idx].box = box; nodes[idx].first = first; nodes[idx].total = count;
-    if (count <= leafSize) { nodes[idx].count = count; if (dp) dpNode(idx); return idx; }
+    if (count <= 1u) { nodes[idx].count = count; dpNode(idx); return idx; } // down to single references: the collapse forms the leaves itself
     // binned SAH over the longest centroid axes
     int bestAxis = -1; int bestSplit = -1; float bestCost = 3.0e38f;
     for (int a = 0; a < 3; a++) {
@@ -186,7 +184,7 @@ struct Builder {
       r = build(mid, count - leftCount, rightIdx);
     }
     nodes[idx].left = l; nodes[idx].right = r;
-    if (dp) dpNode(idx);
+    dpNode(idx);
     return idx;
   }
 
@@ -250,16 +248,12 @@ static void buildCore(const std::vector<TriRec>& trisIn, const float* boxes, siz
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double tA = now();
   Builder B(trisIn, boxes, boxCount);
-  // Collapse rule.  1 (default): cost-optimal -- the BVH2 is built down to single references and a dynamic programme over it (Ylitie,
-  // Karras, Laine 2017, section 3.1, implemented from the paper) chooses per BVH2 node whether its subtree becomes a leaf slot (<= 3
-  // references), an 8-wide node, or part of its parent's child list, minimising  sum(area * (c_node | c_prim * references)).
-  // 0: the round-1 rule (SAH leaves of <= 3, then greedily open the child with the largest area until 8 slots are used).
-  int collapse = 1;
-  collapse = (int)optionValue("bvh_collapse", collapse);
-  // a triangle test costs about half a node test (~110 vs ~214 VALU instructions); measured flat between 0.2 and 0.5 (profiles/r02j_bvh_collapse.txt)
-  float cPrim = 0.5f;
-  if (itemRoots) { collapse = 1; cPrim = 1.0f; B.maxLeaf = 1u; } // an item costs (at least) a node visit; one item per leaf slot
-  if (collapse == 1) { B.leafSize = 1; B.cPrim = cPrim; }
+  // Collapse rule: cost-optimal -- the BVH2 is built down to single references and a dynamic programme over it (Ylitie, Karras, Laine
+  // 2017, section 3.1, implemented from the paper) chooses per BVH2 node whether its subtree becomes a leaf slot (<= 3 references), an
+  // 8-wide node, or part of its parent's child list, minimising  sum(area * (c_node | c_prim * references)).
+  // a triangle test costs about half a node test (~110 vs ~214 VALU instructions); measured flat between 0.2 and 0.5 (r02j)
+  B.cPrim = 0.5f;
+  if (itemRoots) { B.cPrim = 1.0f; B.maxLeaf = 1u; } // an item costs (at least) a node visit; one item per leaf slot
   B.prepare();
   // inactive items (bvh8.h) take no part in the tree; they keep their place in the numbering and sit, unreferenced, behind the leaf-ordered items
   auto appendInactive = [&] {
@@ -326,23 +320,10 @@ static void buildCore(const std::vector<TriRec>& trisIn, const float* boxes, siz
       if (itemRoots && r.count > 0) { P.n = 0; P.internal = 0; P.tris = 0; P.leafMask = 0; return; } // a copied item root: written below, nothing to plan
       // root that is itself a leaf (level 0 only: below the root the DP's own choice stands -- a subtree of <= 3 references it made an 8-wide
       // node of is cheaper that way than as a node holding one 3-reference leaf slot, which is what this shortcut would emit)
-      if (r.count > 0 || (collapse == 1 && r.total <= B.maxLeaf && out.maxDepth == 1u)) { ch[0] = n2; chLeaf[0] = true; n = 1; }
-      else if (collapse == 1) {
+      if (r.count > 0 || (r.total <= B.maxLeaf && out.maxDepth == 1u)) { ch[0] = n2; chLeaf[0] = true; n = 1; }
+      else {
         Child cs[8]; n = gatherOptimal(n2, cs);
         for (int i = 0; i < n; i++) { ch[i] = cs[i].n2; chLeaf[i] = cs[i].leaf; }
-      } else { // by opening the largest internal child
-        ch[n++] = r.left; ch[n++] = r.right;
-        while (n < 8) {
-          int best = -1; float bestArea = -1.0f;
-          for (int i = 0; i < n; i++) {
-            const Node2& c = B.nodes[ch[i]];
-            if (c.count == 0 && c.box.area() > bestArea) { bestArea = c.box.area(); best = i; }
-          }
-          if (best < 0) break;
-          uint32_t opened = ch[best];
-          ch[best] = B.nodes[opened].left; ch[n++] = B.nodes[opened].right;
-        }
-        for (int i = 0; i < n; i++) chLeaf[i] = B.nodes[ch[i]].count > 0;
       }
       // --- node box + slot assignment (greedy max of centroid projection on the slot's octant direction)
       Box nb; nb.reset();

@@ -295,8 +295,7 @@ struct GiCScene : SceneDevice {
   bool countTraversal = false, kernelTimers = false;
   uint32_t kernelTimerStride = 1;
   uint64_t optPoolSlots = 0, optSampleBufferMb = 0; // 0 = default
-  // -1 = default: LDS-resident scenes run the fused persistent kernel k_path; 1 = k_path_bw (wave-local wavefront) when NEE is off; 2 = k_path; 0 = always the
-  // wavefront stage kernels
+  // -1 (default), 1, 2: LDS-resident scenes run the fused persistent kernel k_path; 0 = always the wavefront stage kernels
   int32_t optFusedPath = -1;
   int32_t optTraceDyn = -1; // -1 = default; 0 = block-synchronous k_trace everywhere; N = k_trace_dyn refill threshold
   // Visiting order of shadow walks (k_trace_dyn<any>; any order gives the same image): -1 = not chosen yet -- launches alternate between near-to-far (0) and

@@ -17,13 +17,11 @@
 //   work_order           1         1 = pixel-major work items, 0 = sample-major
 //   defer_slot           1         path slots are written where a path first hits
 //   bounds_retire        1         camera rays that cannot reach the scene's bounds retire in k_raygen
-//   fused                1         LDS-resident scenes run the fused persistent kernels
-//   path_bw              -1        which fused kernel: -1 = the scene option decides (k_path), 1 = k_path_bw
+//   fused                1         LDS-resident scenes run the fused persistent kernel
 //   pool_slots           0         pin the path pool (slots); 0 = the memory plan decides
 //   sample_buffer_mb     0         pin the per-sample buffer (MiB); 0 = the memory plan decides
 //   assume_free_mb       0         tests: plan as if this many MiB were free on the device
 //   incremental          1         transform-only edits update the tree in place
-//   bvh_collapse         1         1 = cost-optimal collapse to 8-wide nodes, 0 = greedy
 //   device_build         -1        -1 = the scene option decides (GI_C_SCENE_OPTION_BVH_BUILD), 0 / 1 = force the host / the device BVH builder
 //                                  (flat-layout scenes of more than 128 triangles; read at build time)
 //   ploc_radius          16        device builder: PLOC's nearest-neighbour search radius (positions either side in Morton order, 1 .. 256)

@@ -419,16 +419,7 @@ static int renderOnDevice(GiCScene* s, SceneDevice& D, const RenderJob& job)
         chunk = (uint32_t)std::min<uint64_t>(chunk, std::max<uint64_t>(64u, ((uint64_t)U.workTotal / (waves * 16u)) & ~63ull));
         curIter = totalIters; if (timers) sampledIters++;
         if (timers) { (void)hipEventRecord(poolEvent(&D, ev), st); }
-        // which fused kernel: k_path (one path per lane, in registers) unless the wave-local wavefront k_path_bw is asked for (GI_C_SCENE_OPTION_FUSED_PATH = 1
-        // / GATLING_OPTIONS=path_bw=1). Measured r03 on C2 (1080p, spp 256, SLP vectorisation off): k_path 55.4 ms per batch, k_path_bw 57.3 -- k_path's 114
-        // VGPRs give 4 resident waves per SIMD (3 blocks per CU cost 11 %), k_path_bw's 168 VGPRs and 50 KB of LDS per block give 3; at 128 VGPRs k_path_bw
-        // spills 43 registers and falls to 84 ms.
-        const int envBw = (int)optionValue("path_bw", -1);
-        const bool useBw = !nee && (envBw >= 0 ? envBw != 0 : s->optFusedPath == 1);
-        if (useBw) launchPathBw(st, (uint32_t)ctx.cuCount, s->classMask, s->classTextured != 0u, s->countTraversal, chunk, U, view, ps, D.dCounters.ptr,
-            D.sampleBuf.ptr);
-        else launchPath(st, (uint32_t)ctx.cuCount, s->classMask, s->classTextured != 0u, s->countTraversal, chunk, U, view, ps, D.dCounters.ptr,
-            D.sampleBuf.ptr);
+        launchPath(st, (uint32_t)ctx.cuCount, s->classMask, s->classTextured != 0u, s->countTraversal, chunk, U, view, ps, D.dCounters.ptr, D.sampleBuf.ptr);
         if (timers) { (void)hipEventRecord(poolEvent(&D, ev + 1), st); ev += 2; evKind.push_back(1); }
         iters++; totalIters++; traceLaunches++;
         launchAccumulate(st, U, D.sampleBuf.ptr, D.accum.ptr, colorOut, batch == 0, batch + 1 == numBatches);

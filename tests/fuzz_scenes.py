@@ -270,7 +270,7 @@ def random_case(seed: int):
     opts = []
     if rng.uniform() < 0.5:
         for key, values in (("trace_dyn", [0, 8, 32]), ("trace_dyn_spill8", [1]), ("two_level", [1]), ("work_order", [0]), ("defer_slot", [0]), ("bounds_retire", [0]),
-                            ("fused", [0]), ("path_bw", [1]), ("pool_slots", [4096, 65536]), ("bvh_collapse", [0]), ("shadow_order", [0, 1]), ("shade_variants", [0]),
+                            ("fused", [0]), ("pool_slots", [4096, 65536]), ("shadow_order", [0, 1]), ("shade_variants", [0]),
                             ("merge_shade_variants", [0, 1]), ("two_stream", [0]), ("two_stream_delay", [1, 2])):
             if rng.uniform() < 0.2: opts.append(f"{key}={int(rng.choice(values))}")
     extras["options"] = ",".join(opts)

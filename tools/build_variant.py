@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from gatling_amd import build as B  # noqa: E402
 
-KERNEL_TUS = ["gi_kernels.hip", "gi_trace.hip", "gi_shade.hip", "gi_aov.hip", "gi_path.hip", "gi_path_bw.hip"]
+KERNEL_TUS = ["gi_kernels.hip", "gi_trace.hip", "gi_shade.hip", "gi_aov.hip", "gi_path.hip"]
 
 
 def main():

@@ -2,7 +2,8 @@
 
 Measured (r02, 1 x MI355X, spp 256): max_bounces 1 / 2 / 3 / 4 / 6 / 8 -> 1.000 / 1.377 / 1.663 / 1.896 / 2.141 / 2.204 segments per sample,
 43.3 / 63.9 / 83.0 / 98.7 / 117.1 / 121.3 ps per sample: the first segment (coherent camera ray, regeneration and finish included) costs 43 ps, every
-further one 65 ps -- secondary rays, not regeneration, are where k_path_bw's time goes."""
+further one 65 ps -- secondary rays, not regeneration, are where the fused kernel's time goes (measured on r02's wave-local variant of it, since
+removed)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gatling_amd import capi
