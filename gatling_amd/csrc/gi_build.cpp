@@ -517,7 +517,8 @@ int buildScene(GiCScene* s)
     for (size_t i = 0; i < bvh.tris.size(); i++) H.flatOfOrig[bvh.tris[i].origId] = (uint32_t)i;
   }
   double t1 = nowMs();
-  // the deepest traversal variant keeps 8 (SPILL8) or 16 stack entries in LDS and OVF_STACK = 40 in scratch; trav_node_pick does not bound-check the spill
+  // the deepest traversal variant keeps 16 stack entries in LDS and OVF_STACK = 40 in scratch; trav_node_pick does not bound-check the spill.  The limit stays
+  // at 1 + 8 + 40 levels, the depth the 8-entry spilling variant of earlier versions could hold
   if (bvh.maxDepth > 1u + 8u + 40u) { setError("scene BVH is deeper than the traversal stack (49 levels): degenerate geometry (long chains of nested splits)");
       return GI_C_ERROR; }
   if (bvh.tris.size() >= (1u << 26) && !s->twoLevel) {

@@ -297,7 +297,7 @@ struct GiCScene : SceneDevice {
   uint64_t optPoolSlots = 0, optSampleBufferMb = 0; // 0 = default
   // -1 (default), 1, 2: LDS-resident scenes run the fused persistent kernel k_path; 0 = always the wavefront stage kernels
   int32_t optFusedPath = -1;
-  int32_t optTraceDyn = -1; // -1 = default; 0 = block-synchronous k_trace everywhere; N = k_trace_dyn refill threshold
+  int32_t optTraceDyn = -1; // k_trace_dyn refill threshold N in 1..64; -1 or 0 = default
   // Visiting order of shadow walks (k_trace_dyn<any>; any order gives the same image): -1 = not chosen yet -- launches alternate between near-to-far (0) and
   // slot order (1) and the frame's node-visit counts are added up below; once both orders have walked enough rays the cheaper one is kept until the tree is
   // rebuilt.

@@ -13,6 +13,8 @@ void launchInit(hipStream_t s, const PathState& st, const QueueSet& qs, Counters
 // REGEN[par^1]; k_shade reads HIT and appends TRACE[par^1], REGEN[par^1], SHADOW.
 void launchRaygen(hipStream_t s, uint32_t blocks, const FrameUniforms& U, const PathState& st, const QueueSet& qs, Counters* cnt, uint32_t par, F4* sampleBuf);
 void launchAccumulate(hipStream_t s, const FrameUniforms& U, const F4* sampleBuf, F4* accum, F4* colorOut, bool firstBatch, bool lastBatch);
+// launchTrace runs the block-synchronous k_trace on this scene (staged whole in LDS, at most 8 levels deep) rather than k_trace_dyn + k_route
+bool traceBlockSync(const SceneView& sc);
 // LDS bytes one k_trace block needs for this scene (stack + staged nodes + staged triangles)
 uint32_t traceStaticLdsBytes(); // static LDS of the traversal kernels on top of traceLdsLayout's dynamic bytes
 void traceLdsLayout(const SceneView& sc, uint32_t& ldsNodes, uint32_t& ldsTris, uint32_t& bytes);
@@ -26,8 +28,7 @@ void launchRoute(hipStream_t s, uint32_t blocks, const SceneView& sc, const Path
 constexpr uint32_t APPEND_ITEMS_MAX = 4u;
 // flag in dynRefill (shadow launches): children are visited in slot order instead of near-to-far (k_trace_dyn: DYN_SLOT_ORDER)
 constexpr uint32_t TRACE_DYN_SLOT_ORDER = 0x200u;
-constexpr uint32_t TRACE_DYN_SPILL8 = 0x100u; // flag in dynRefill: 8 LDS stack entries + scratch overflow instead of 16 LDS entries
-// dynRefill: 0 = block-synchronous k_trace; N = scenes that do not fit LDS use k_trace_dyn (a wave refills once N lanes are idle) + k_route
+// dynRefill: N in 1..64 = a k_trace_dyn wave refills once N of its lanes are idle
 // one launch per material class present in the scene (the class is the sort key between k_trace and k_shade)
 void launchShade(hipStream_t s, uint32_t blocks, uint32_t klass, bool textured /* some material of the class has textured inputs */,
     bool volume /* mediumStackSize > 0 */, const FrameUniforms& U, const SceneView& sc, const PathState& st, const QueueSet& qs, Counters* cnt, uint32_t par);

@@ -4,9 +4,9 @@
 //
 // Replaces the Vulkan ray-tracing megakernel of the reference:
 //   rp_main.rgen  (/root/reference/src/gi/shaders/rp_main.rgen:185-521)  -> k_raygen + the host bounce loop
-//   traceRayEXT   (rp_main.rgen:381-393, 412-424; HW BVH traversal)        -> k_trace<closest>, k_trace<any>
+//   traceRayEXT   (rp_main.rgen:381-393, 412-424; HW BVH traversal)        -> k_trace / k_trace_dyn, closest hit and any hit
 //   rp_main.chit  (rp_main.chit:132-493)                                   -> k_shade
-//   rp_main.miss  (:55-86), rp_main_shadow.miss, the NEE add (rgen:426-429) -> k_raygen (miss term), k_trace<any> epilogue
+//   rp_main.miss  (:55-86), rp_main_shadow.miss, the NEE add (rgen:426-429) -> k_raygen (miss term), the any-hit traversal's epilogue
 // One slot per pixel of the tile walks its samples in order, so the per-pixel float accumulation order of
 // rp_main.rgen:498 is preserved exactly while different slots sit in different stages/queues.
 //

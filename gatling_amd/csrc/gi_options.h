@@ -10,9 +10,8 @@
 //                          bit for bit); they select between equivalent schedules, or pin sizes the library otherwise plans itself.
 //
 //   key                  default   meaning
-//   trace_dyn            8         refill threshold of k_trace_dyn; 0 = the block-synchronous k_trace for scenes beyond LDS too
+//   trace_dyn            8         refill threshold of k_trace_dyn, 1 .. 64; 0 or below = the default
 //                                  (same as GI_C_SCENE_OPTION_TRACE_DYNAMIC)
-//   trace_dyn_spill8     0         trees deeper than 8 levels keep 8 stack entries in LDS and spill the rest to scratch
 //   two_level            -1        -1 = automatic (from 2^26 flattened triangles), 0 / 1 = force the flat / the two-level layout
 //   work_order           1         1 = pixel-major work items, 0 = sample-major
 //   defer_slot           1         path slots are written where a path first hits

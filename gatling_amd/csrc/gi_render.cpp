@@ -21,13 +21,12 @@ SceneView makeView(GiCScene* s, SceneDevice& D)
 }
 SceneView makeView(GiCScene* s) { return makeView(s, *s); }
 
-// k_trace_dyn refill threshold for scenes that do not fit LDS (0 = use the block-synchronous k_trace)
+// k_trace_dyn refill threshold, 1..64 (0 or below: the default, 8)
 uint32_t traceDynRefill(const GiCScene* s)
 {
-  uint32_t r = s->optTraceDyn >= 0 ? (uint32_t)s->optTraceDyn : 8u;
-  if (optionSet("trace_dyn")) r = (uint32_t)std::max(0L, std::min(64L, optionValue("trace_dyn", 8)));
-  if (r && optionValue("trace_dyn_spill8", 0)) r |= TRACE_DYN_SPILL8;
-  return r;
+  long r = s->optTraceDyn;
+  if (optionSet("trace_dyn")) r = optionValue("trace_dyn", 8);
+  return r > 0 ? (uint32_t)std::min(64L, r) : 8u;
 }
 
 uint32_t shardCapacity(size_t slots, uint32_t gridA, uint32_t gridB)
@@ -283,14 +282,13 @@ static int renderOnDevice(GiCScene* s, SceneDevice& D, const RenderJob& job)
     // persistent grids: blocks per CU limited by registers (<= 6 waves/SIMD for k_trace) and, for k_trace, by the LDS it stages
     uint32_t wideBlocks = 1u, traceBlocks = 1u;
     auto sizeGrids = [&]() {
-      SceneView v0 = makeView(s, D);
-      uint32_t ln, lt, ldsBytes; traceLdsLayout(v0, ln, lt, ldsBytes);
-      uint32_t perCu = std::min<uint32_t>(6u, (160u * 1024u) / (ldsBytes + traceStaticLdsBytes() + 256u));
-      const bool allLds = ln == v0.nodeCount && lt == v0.triCount && v0.triCount > 0u;
-      if (!allLds && traceDynRefill(s)) perCu = 8u; // k_trace_dyn is persistent per wave: blocks beyond what is resident find the cursor exhausted
-      uint32_t widePerCu = 8u;
-      perCu = std::max(perCu, 1u); widePerCu = std::max(widePerCu, 1u);
-      wideBlocks = (uint32_t)std::min<size_t>((slots + 255) / 256, (size_t)ctx.cuCount * widePerCu);
+      const SceneView v0 = makeView(s, D);
+      uint32_t perCu = 8u; // k_trace_dyn is persistent per wave: blocks beyond what is resident find the cursor exhausted
+      if (traceBlockSync(v0)) {
+        uint32_t ln, lt, ldsBytes; traceLdsLayout(v0, ln, lt, ldsBytes);
+        perCu = std::max(1u, std::min<uint32_t>(6u, (160u * 1024u) / (ldsBytes + traceStaticLdsBytes() + 256u)));
+      }
+      wideBlocks = (uint32_t)std::min<size_t>((slots + 255) / 256, (size_t)ctx.cuCount * 8u);
       traceBlocks = (uint32_t)std::min<size_t>((slots + 255) / 256, (size_t)ctx.cuCount * perCu);
     };
     sizeGrids();
@@ -357,19 +355,14 @@ static int renderOnDevice(GiCScene* s, SceneDevice& D, const RenderJob& job)
     const uint32_t dynRefill = traceDynRefill(s);
     // (GATLING_OPTIONS=shadow_order=0|1 pins it)
     const int32_t shadowOrderNow = optionSet("shadow_order") ? (int32_t)optionValue("shadow_order", -1) : s->shadowOrder.load();
-    // Bounds retire (r04n): on the k_trace_dyn path a deferred-slot camera ray that cannot reach the scene's bounds is retired by k_raygen itself (C4: 58 % of
-    // the camera rays, C3: ~45 %) -- same sample, same segment count, no ray record, no traversal step, no routing. Not with a dome image / medium stack (a
-    // miss needs the slot), not in counting builds (the root visit of such a ray is part of nodes-per-ray), not on the two-level layout (bounds of the TLAS
-    // root: not kept).
-    {
-      SceneView v0 = view; uint32_t ln, lt, ldsBytes; traceLdsLayout(v0, ln, lt, ldsBytes);
-      const bool allLds = ln == v0.nodeCount && lt == v0.triCount && v0.triCount > 0u;
-      if ((U.flags & FLAG_DEFER_SLOT) && !allLds && dynRefill && !view.twoLevel && view.domeTexture == 0u && rs.mediumStackSize == 0u && !s->countTraversal
-          && s->boundsValid &&
-          optionValue("bounds_retire", 1) != 0) {
-        U.flags |= FLAG_BOUNDS_RETIRE;
-        for (int a = 0; a < 3; a++) { U.sceneLo[a] = s->bounds[a]; U.sceneHi[a] = s->bounds[3 + a]; }
-      }
+    // Bounds retire (r04n): on the k_trace_dyn path (k_route zeroes the regen counter k_raygen then appends to) a deferred-slot camera ray that cannot reach
+    // the scene's bounds is retired by k_raygen itself (C4: 58 % of the camera rays, C3: ~45 %) -- same sample, same segment count, no ray record, no traversal
+    // step, no routing. Not with a dome image / medium stack (a miss needs the slot), not in counting builds (the root visit of such a ray is part of
+    // nodes-per-ray), not on the two-level layout (bounds of the TLAS root: not kept).
+    if ((U.flags & FLAG_DEFER_SLOT) && !traceBlockSync(view) && !view.twoLevel && view.domeTexture == 0u && rs.mediumStackSize == 0u && !s->countTraversal
+        && s->boundsValid && optionValue("bounds_retire", 1) != 0) {
+      U.flags |= FLAG_BOUNDS_RETIRE;
+      for (int a = 0; a < 3; a++) { U.sceneLo[a] = s->bounds[a]; U.sceneHi[a] = s->bounds[3 + a]; }
     }
 
     // --- the bounce loop (rp_main.rgen:215, 295): every pool slot advances one stage per iteration
@@ -496,9 +489,8 @@ static int renderOnDevice(GiCScene* s, SceneDevice& D, const RenderJob& job)
               [&] { launchShade(st, wideBlocks, klass, (s->shadeClassTextured & (1u << klass)) != 0u, rs.mediumStackSize != 0u, U, view, ps, qs,
               D.dCounters.ptr, par); });
         if (nee) {
-          // (the slot-order flag belongs to k_trace_dyn: with dynamic refill off -- TRACE_DYNAMIC 0 -- dynRefill stays 0 so that launchTrace picks the
-          // block-synchronous k_trace the grid was sized for, and there is no order to measure) not chosen yet: alternate, and count (below)
-          const int32_t order = (dynRefill & 0xffu) == 0u ? 0 : (shadowOrderNow >= 0 ? shadowOrderNow : (int32_t)(totalIters & 1u));
+          // not chosen yet: alternate, and count (below)
+          const int32_t order = shadowOrderNow >= 0 ? shadowOrderNow : (int32_t)(totalIters & 1u);
           hipStream_t on = st;
           if (two) { // the shadow launch moves to the second stream, behind this iteration's k_shade
             HIP_TRY(hipEventRecord(D.evShade, st)); HIP_TRY(hipStreamWaitEvent(st2, D.evShade, 0));

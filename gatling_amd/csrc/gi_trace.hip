@@ -1,4 +1,4 @@
-// gi_trace.hip -- the traversal kernels of the wavefront path tracer (gfx950): k_trace (block-synchronous, scenes staged in LDS), k_trace_dyn / k_trace_dyn2
+// gi_trace.hip -- the traversal kernels of the wavefront path tracer (gfx950): k_trace (block-synchronous, scenes staged whole in LDS), k_trace_dyn / k_trace_dyn2
 // (persistent waves with dynamic ray fetch for scenes that do not fit; results routed by gi_kernels.hip k_route).  They replace the two traceRayEXT calls of
 // the reference's ray generation shader (/root/reference/src/gi/shaders/rp_main.rgen:381-393, 412-424: closest hit and shadow test; hardware BVH traversal
 // there).  The walk itself is gi_traversal.h.  Built with -ffp-contract=off (arithmetic contract, gi_device_math.h); the box tests use explicit fmaf: they are
@@ -17,7 +17,7 @@
 
 namespace gi {
 
-template <bool ANYHIT, bool COUNT, uint32_t STACK, bool OVERFLOW, bool ALL_LDS, bool CUTOUT, bool DOME>
+template <bool ANYHIT, bool COUNT, uint32_t STACK, bool CUTOUT, bool DOME>
 __global__ __launch_bounds__(TRACE_BLOCK) void k_trace(SceneView sc, PathState st, QueueSet qs, Counters* cnt, uint32_t qIn, uint32_t qMiss, uint32_t ldsNodes,
     uint32_t ldsTris,
                                                        FrameUniforms U, F4* __restrict__ sampleBuf)
@@ -40,7 +40,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace(SceneView sc, PathState s
 
   TraceCounters tc{0u, 0u};
   RayTrav R; trav_init(R, v3(0.0f, 0.0f, 0.0f), v3(0.0f, 0.0f, 1.0f), 0.0f, 0.0f);
-  uint2 overflow[OVERFLOW ? OVF_STACK : 1];
+  uint2 overflow[1];
   const uint32_t stride = gridDim.x * TRACE_BLOCK;
   uint32_t trip = 0;
   for (uint32_t base = blockIdx.x * TRACE_BLOCK; base < n; base += stride, trip++) {
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace(SceneView sc, PathState s
       alive = true;
     }
     while (__ballot(alive)) {
-      if (wave_step<ANYHIT, COUNT, STACK, OVERFLOW, ALL_LDS,
+      if (wave_step<ANYHIT, COUNT, STACK, false, true,
           CUTOUT>(R, alive, W, sc, s_nodes, ldsNodes, s_tris, ldsTris, s_stack, overflow, tc, rng)) alive = false;
     }
     if (i < n) {
@@ -125,8 +125,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace(SceneView sc, PathState s
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_trace_dyn: traversal for scenes that do not fit LDS.  Ray cost has a long tail there (a ray through dense geometry
-// visits several times the average node count), so "one ray per lane until the whole block is done" leaves most lanes
+// k_trace_dyn: traversal for scenes that do not fit LDS (and LDS-resident trees deeper than 8 levels).  Ray cost has a long tail there (a ray
+// through dense geometry visits several times the average node count), so "one ray per lane until the whole block is done" leaves most lanes
 // idle.  Here every wave is persistent and independent: lanes that finish write their result IN PLACE over the ray
 // record (a = (t, u, v, triangle | class << 28) or (tMax, origin.xy, MISS)) and, once `refill` lanes of the wave are idle, the wave hands
 // them new rays.  No barriers, no appends; k_route then streams the results into the per-class shade queues / the regen queue.
@@ -453,6 +453,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 
 // host-callable launchers
 // ------------------------------------------------------------------------------------------------
 static bool sceneFitsLds(const SceneView& sc) { return sc.nodeCount <= LDS_NODES && sc.triCount <= LDS_TRIS && sc.triCount > 0u; }
+bool traceBlockSync(const SceneView& sc) { return sceneFitsLds(sc) && sc.bvhDepth <= 8u; }
 static uint32_t traceStackEntries(const SceneView& sc) { return (sc.bvhDepth <= 4u && sceneFitsLds(sc)) ? 4u : (sc.bvhDepth <= 8u ? 8u : 16u); }
 uint32_t traceStaticLdsBytes() { return (uint32_t)(sizeof(WaveTri) * (TRACE_BLOCK / 64) + sizeof(AppendScratch<1 + MAT_CLASS_COUNT>)); }
 void traceLdsLayout(const SceneView& sc, uint32_t& ldsNodes, uint32_t& ldsTris, uint32_t& bytes)
@@ -467,50 +468,40 @@ static void launchTraceVariant(hipStream_t s, uint32_t blocks, const SceneView& 
     uint32_t qMiss,
                                uint32_t dynRefill, uint32_t routeBlocks, const FrameUniforms& U, F4* sampleBuf)
 {
-  uint32_t ln, lt, bytes; traceLdsLayout(sc, ln, lt, bytes);
-  const bool allLds = ln == sc.nodeCount && lt == sc.triCount && sc.triCount > 0u; // the whole scene is staged in LDS
-  if (!allLds && dynRefill) { // big scene: persistent waves with dynamic ray fetch, results routed by a streaming pass
-    // persistent waves pay the scratch set-up once, so trees deeper than 8 levels may keep 8 entries in LDS (more
-    // resident waves) and spill the rest (TRACE_DYN_SPILL8), or keep 16 in LDS
-    const uint32_t refill = (dynRefill & 0xffu) | (ANYHIT ? (dynRefill & DYN_SLOT_ORDER) : 0u);
-    if (sc.twoLevel) { // instanced scene: TLAS + shared per-mesh BLASes
-      hipLaunchKernelGGL((k_trace_dyn2<ANYHIT, COUNT, CUTOUT>), dim3(blocks), dim3(TRACE_BLOCK), 16u * TRACE_BLOCK * (uint32_t)sizeof(uint2), s, sc, st, qs,
-          cnt, qIn, refill);
-      if (!ANYHIT) launchRoute(s, routeBlocks, sc, st, qs, cnt, qIn, qMiss, U, sampleBuf);
-      return;
-    }
-    const bool spill8 = (dynRefill & TRACE_DYN_SPILL8) != 0u;
-    // 8 entries (16 KB per block), 12 (24 KB: 5 blocks per CU still fit next to the 8 KB of WaveTri) or 16 (32 KB: 4 blocks -- one wave per SIMD fewer)
-    const uint32_t entries = (sc.bvhDepth <= 8u || spill8) ? 8u : (sc.bvhDepth <= 12u ? 12u : 16u);
-    const uint32_t stackBytes = entries * TRACE_BLOCK * (uint32_t)sizeof(uint2);
-#define GI_LAUNCH_DYN(STACK, OVF) do { \
-      if (ANYHIT && (refill & DYN_SLOT_ORDER)) \
-        hipLaunchKernelGGL((k_trace_dyn<ANYHIT, COUNT, STACK, OVF, CUTOUT, ANYHIT>), dim3(blocks), dim3(TRACE_BLOCK), stackBytes, s, sc, st, qs, cnt, qIn, \
-                           refill); \
-      else hipLaunchKernelGGL((k_trace_dyn<ANYHIT, COUNT, STACK, OVF, CUTOUT, false>), dim3(blocks), dim3(TRACE_BLOCK), stackBytes, s, sc, st, qs, cnt, qIn, \
-          refill); } while (0)
-    if (sc.bvhDepth <= 8u) GI_LAUNCH_DYN(8, false);
-    else if (spill8) GI_LAUNCH_DYN(8, true);
-    else if (sc.bvhDepth <= 12u) GI_LAUNCH_DYN(12, false);
-    else if (sc.bvhDepth <= 16u) GI_LAUNCH_DYN(16, false);
-    else GI_LAUNCH_DYN(16, true);
-#undef GI_LAUNCH_DYN
-    if (!ANYHIT) launchRoute(s, routeBlocks, sc, st, qs, cnt, qIn, qMiss, U, sampleBuf);
+  if (traceBlockSync(sc)) { // the whole scene is staged in LDS
+    uint32_t ln, lt, bytes; traceLdsLayout(sc, ln, lt, bytes);
+    const bool dome = !ANYHIT && (sc.domeTexture != 0u || sc.mediumStackSize != 0u); // misses need the slot: dome image lookup / scattering events
+#define GI_LAUNCH_TRACE(STACK) do { \
+      if (dome) \
+        hipLaunchKernelGGL((k_trace<ANYHIT, COUNT, STACK, CUTOUT, !ANYHIT>), dim3(blocks), dim3(TRACE_BLOCK), bytes, s, sc, st, qs, cnt, qIn, qMiss, ln, lt, U, \
+                           sampleBuf); \
+      else hipLaunchKernelGGL((k_trace<ANYHIT, COUNT, STACK, CUTOUT, false>), dim3(blocks), dim3(TRACE_BLOCK), bytes, s, sc, st, qs, cnt, qIn, qMiss, ln, lt, U, \
+          sampleBuf); } while (0)
+    if (sc.bvhDepth <= 4u) GI_LAUNCH_TRACE(4);
+    else GI_LAUNCH_TRACE(8);
+#undef GI_LAUNCH_TRACE
     return;
   }
-  const bool dome = !ANYHIT && (sc.domeTexture != 0u || sc.mediumStackSize != 0u); // misses need the slot: dome image lookup / scattering events
-#define GI_LAUNCH_TRACE(STACK, OVF, LDS) do { \
-    if (dome) \
-      hipLaunchKernelGGL((k_trace<ANYHIT, COUNT, STACK, OVF, LDS, CUTOUT, !ANYHIT>), dim3(blocks), dim3(TRACE_BLOCK), bytes, s, sc, st, qs, cnt, qIn, qMiss, \
-                         ln, lt, U, sampleBuf); \
-    else hipLaunchKernelGGL((k_trace<ANYHIT, COUNT, STACK, OVF, LDS, CUTOUT, false>), dim3(blocks), dim3(TRACE_BLOCK), bytes, s, sc, st, qs, cnt, qIn, qMiss, \
-        ln, lt, U, sampleBuf); } while (0)
-  if (allLds && sc.bvhDepth <= 4u) GI_LAUNCH_TRACE(4, false, true);
-  else if (allLds && sc.bvhDepth <= 8u) GI_LAUNCH_TRACE(8, false, true);
-  else if (sc.bvhDepth <= 8u) GI_LAUNCH_TRACE(8, false, false);
-  else if (sc.bvhDepth <= 16u) GI_LAUNCH_TRACE(16, false, false);
-  else GI_LAUNCH_TRACE(16, true, false);
-#undef GI_LAUNCH_TRACE
+  // persistent waves with dynamic ray fetch, results routed by a streaming pass
+  const uint32_t refill = (dynRefill & 0xffu) | (ANYHIT ? (dynRefill & DYN_SLOT_ORDER) : 0u);
+  // 8 entries (16 KB per block), 12 (24 KB: 5 blocks per CU still fit next to the 8 KB of WaveTri) or 16 (32 KB: 4 blocks -- one wave per SIMD fewer); trees
+  // deeper than 16 levels spill the rest to scratch (persistent waves pay its set-up once)
+  const uint32_t stackBytes = (sc.bvhDepth <= 8u ? 8u : (sc.bvhDepth <= 12u ? 12u : 16u)) * TRACE_BLOCK * (uint32_t)sizeof(uint2);
+#define GI_LAUNCH_DYN(STACK, OVF) do { \
+    if (ANYHIT && (refill & DYN_SLOT_ORDER)) \
+      hipLaunchKernelGGL((k_trace_dyn<ANYHIT, COUNT, STACK, OVF, CUTOUT, ANYHIT>), dim3(blocks), dim3(TRACE_BLOCK), stackBytes, s, sc, st, qs, cnt, qIn, \
+                         refill); \
+    else hipLaunchKernelGGL((k_trace_dyn<ANYHIT, COUNT, STACK, OVF, CUTOUT, false>), dim3(blocks), dim3(TRACE_BLOCK), stackBytes, s, sc, st, qs, cnt, qIn, \
+        refill); } while (0)
+  if (sc.twoLevel) // instanced scene: TLAS + shared per-mesh BLASes
+    hipLaunchKernelGGL((k_trace_dyn2<ANYHIT, COUNT, CUTOUT>), dim3(blocks), dim3(TRACE_BLOCK), 16u * TRACE_BLOCK * (uint32_t)sizeof(uint2), s, sc, st, qs,
+        cnt, qIn, refill);
+  else if (sc.bvhDepth <= 8u) GI_LAUNCH_DYN(8, false);
+  else if (sc.bvhDepth <= 12u) GI_LAUNCH_DYN(12, false);
+  else if (sc.bvhDepth <= 16u) GI_LAUNCH_DYN(16, false);
+  else GI_LAUNCH_DYN(16, true);
+#undef GI_LAUNCH_DYN
+  if (!ANYHIT) launchRoute(s, routeBlocks, sc, st, qs, cnt, qIn, qMiss, U, sampleBuf);
 }
 template <bool ANYHIT, bool COUNT>
 static void launchTraceCutout(hipStream_t s, uint32_t blocks, const SceneView& sc, const PathState& st, const QueueSet& qs, Counters* cnt, uint32_t qIn,

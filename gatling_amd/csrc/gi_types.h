@@ -281,7 +281,7 @@ constexpr uint32_t VOLUME_MISS = 0xfffffffeu; // "triangle" id of a hit record t
 // Debug AOVs that follow whole paths (only when bound): Bounces = inferno colour of the bounce count of the pixel's LAST
 // sample (rp_main.rgen:483-486, written by k_raygen when that sample retires); NEE = outcome of the shadow test at bounce 0 of the
 // pixel's last sample (rp_main.rgen:431-435; untraced = not shadowed): per tile pixel the maximum of (sample + 1) << 1 | shadowed over
-// all bounce-0 outcomes (k_shade, k_trace<any>, primary misses), which k_resolve_nee turns into red / green.  neeKey is null unless
+// all bounce-0 outcomes (k_shade, the shadow-ray traversal, primary misses), which k_resolve_nee turns into red / green.  neeKey is null unless
 // the AOV is bound and next-event estimation is on.
 struct PathState {
   Slot* slots; float* media; uint32_t mediaStride;

@@ -468,8 +468,8 @@ int giCGetRenderStats(const GiCScene* scene, GiCRenderStats* out);
  * do not depend on either (tests/test_gpu_parity.py::test_pool_and_batch_invariance); 0 restores the default */
 #define GI_C_SCENE_OPTION_POOL_SLOTS 3
 #define GI_C_SCENE_OPTION_SAMPLE_BUFFER_MB 4
-/* Traversal kernel for scenes whose BVH does not fit LDS: 0 = block-synchronous k_trace; N in 1..64 = persistent waves that
- * claim new rays once N lanes are idle (k_trace_dyn, default 8); -1 = default.  Results are identical either way. */
+/* Refill threshold of k_trace_dyn, the traversal kernel for scenes beyond LDS and LDS-resident trees deeper than 8 levels: N in 1..64 = its persistent
+ * waves claim new rays once N lanes are idle (default 8); -1 or 0 = default (0 is kept for existing callers).  The image does not depend on N. */
 #define GI_C_SCENE_OPTION_TRACE_DYNAMIC 5
 #define GI_C_SCENE_OPTION_TWO_LEVEL 6     /* [ext] 1: two-level BVH (TLAS over instances + one object-space BLAS per mesh) for scenes beyond LDS; default 0: one
                                              flat BVH over the instanced triangles (faster today); the image does not depend on it */

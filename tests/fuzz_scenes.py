@@ -269,7 +269,7 @@ def random_case(seed: int):
     # equivalent schedules of the library ($GATLING_OPTIONS, gi_options.h): none may change a bit
     opts = []
     if rng.uniform() < 0.5:
-        for key, values in (("trace_dyn", [0, 8, 32]), ("trace_dyn_spill8", [1]), ("two_level", [1]), ("work_order", [0]), ("defer_slot", [0]), ("bounds_retire", [0]),
+        for key, values in (("trace_dyn", [1, 8, 32]), ("two_level", [1]), ("work_order", [0]), ("defer_slot", [0]), ("bounds_retire", [0]),
                             ("fused", [0]), ("pool_slots", [4096, 65536]), ("shadow_order", [0, 1]), ("shade_variants", [0]),
                             ("merge_shade_variants", [0, 1]), ("two_stream", [0]), ("two_stream_delay", [1, 2])):
             if rng.uniform() < 0.2: opts.append(f"{key}={int(rng.choice(values))}")
@@ -343,7 +343,7 @@ def random_case(seed: int):
     # scene options of the C ABI (include/gi_c.h GI_C_SCENE_OPTION_*): the counting instantiations of the kernels, the stage timers, the schedules by option
     extras["scene_options"] = []
     if rng.uniform() < 0.25:
-        for opt, values in ((1, [1]), (2, [1, 4]), (5, [0, 16]), (6, [1]), (7, [0, 1, 2])):   # COUNT_TRAVERSAL, KERNEL_TIMERS, TRACE_DYNAMIC, TWO_LEVEL, FUSED_PATH
+        for opt, values in ((1, [1]), (2, [1, 4]), (5, [1, 16]), (6, [1]), (7, [0, 1, 2])):   # COUNT_TRAVERSAL, KERNEL_TIMERS, TRACE_DYNAMIC, TWO_LEVEL, FUSED_PATH
             if rng.uniform() < 0.35: extras["scene_options"].append((opt, int(rng.choice(values))))
     extras["trace_rays"] = int(rng.integers(1, 3000)) if rng.uniform() < 0.15 else 0
     extras["trace_seed"] = int(rng.integers(1 << 30))

@@ -263,10 +263,11 @@ def test_deferred_slot_initialisation_is_invisible(gi, monkeypatch, name):
     """FLAG_DEFER_SLOT (r04): k_raygen no longer writes a new path's Slot; its rng / work item travel beside the camera ray and the slot is written where the first
     segment hits -- a camera ray that leaves the scene retires in k_route / k_trace without one.  Every golden fixture (open cornell box, dome image, medium stacks,
     instanced spheres under a constant background, cutout cards, interior with NEE) through the wavefront stage kernels with the deferral on (default), off, with
-    a small pool (slots recycled many times: stale slot contents must never be read) and with the block-synchronous k_trace: the committed image, bit for bit."""
+    a small pool (slots recycled many times: stale slot contents must never be read) and with refill threshold 1 (scenes on k_trace_dyn refill a wave at
+    every idle lane): the committed image, bit for bit."""
     desc, rs, w, h = build_case(name)
     g = np.load(os.path.join(GOLDEN, name + ".npz"))
-    for defer, pool, dyn in (("1", 0, -1), ("0", 0, -1), ("1", 301, -1), ("1", 0, 0), ("0", 301, 0), ("1", 64, -2)):
+    for defer, pool, dyn in (("1", 0, -1), ("0", 0, -1), ("1", 301, -1), ("1", 0, 1), ("0", 301, 1), ("1", 64, -2)):
         monkeypatch.setenv("GATLING_OPTIONS", f"defer_slot={defer},bounds_retire={0 if dyn == -2 else 1}")  # (r04n: camera rays that miss the scene's bounds retire in k_raygen; -2 = default traversal without it)
         dyn = -1 if dyn == -2 else dyn
         sc = gi.Scene(desc)
@@ -933,18 +934,18 @@ def _telescope(n, ratio):
     return desc
 
 
-@pytest.mark.parametrize("n,ratio,spill8", [(100, 1.1, False), (400, 1.03, False), (2000, 1.006, False), (2000, 1.006, True), (400, 1.2, False)])
-def test_deep_trees_parity(gi, orc, monkeypatch, n, ratio, spill8):
-    """Trees deeper than BASELINE's scenes give (host-side depth 7 / 11 / 12 / 39): 100 triangles run the fused kernels with the 8-entry
-    stack nearly full, 400 and 2000 the 16-entry stack, `spill8` the 8-entry stack with the scratch overflow, the last case the deepest
+@pytest.mark.parametrize("n,ratio", [(100, 1.1), (120, 1.2), (400, 1.03), (2000, 1.006), (400, 1.2)])
+def test_deep_trees_parity(gi, orc, n, ratio):
+    """Trees deeper than BASELINE's scenes give (host-side depth 7 / 13 / 11 / 12 / 39): 100 triangles run the fused kernels with the 8-entry
+    stack nearly full, 120 triangles an LDS-resident tree too deep for them and for k_trace (k_trace_dyn + k_route, 12 entries), 400 and 2000
+    the 16-entry stack, the last case the deepest
     tree the builder produces here (16 entries + overflow) -- images with shadow rays, and random rays, against the oracle.
-    The last case is compared by image only: its triangles shrink to 1e-32 at the origin, and a ray that passes within float resolution of
+    The 120-triangle case and the last one are compared by image only: their triangles shrink to 3e-10 and 1e-32 at the origin, and a ray that passes within float resolution of
     the origin makes the exact test's `dot(o - v0, d x e2)` cancel to exactly 0, so it "hits" a 5e-14-sized triangle it geometrically misses
     by 1e-7 -- a hit no box test can promise to keep (3 of 4000 such rays differ between this tree and the oracle's)."""
-    if spill8:
-        monkeypatch.setenv("GATLING_OPTIONS", "trace_dyn_spill8=1")
     desc = _telescope(n, ratio)
-    render_both(gi, orc, desc, RenderSettings(spp=3, max_bounces=4, next_event_estimation=True), 80, 45)
+    _, _, st = render_both(gi, orc, desc, RenderSettings(spp=3, max_bounces=4, next_event_estimation=True), 80, 45)
+    assert st["fusedPath"] == (1 if n == 100 else 0)
     if ratio ** (-n) < 1e-7:
         return
     rng = np.random.default_rng(n)
@@ -1301,8 +1302,8 @@ def test_interior_scene_parity(gi, orc):
 
 @pytest.mark.parametrize("scene_kind", ["soup", "instances"])
 def test_traversal_kernel_variants_agree(gi, orc, scene_kind):
-    """Scenes beyond LDS: the block-synchronous k_trace, k_trace_dyn (any refill threshold) and the oracle give the
-    same image bit for bit -- the kernels differ in scheduling (who tests which triangle when), never in arithmetic."""
+    """Scenes beyond LDS: k_trace_dyn (any refill threshold) and the oracle give the
+    same image bit for bit -- the thresholds differ in scheduling (who tests which triangle when), never in arithmetic."""
     from gatling_amd import capi
     if scene_kind == "soup":
         desc, rs, w, h = _soup(6000, seed=5), RenderSettings(spp=3, max_bounces=6, next_event_estimation=True), 80, 45
@@ -1312,7 +1313,7 @@ def test_traversal_kernel_variants_agree(gi, orc, scene_kind):
     ref, _ = orc.render(desc, rs, w, h, threads=4)
     scene = gi.Scene(desc)
     try:
-        for refill in (0, 1, 8, 33, 64):
+        for refill in (1, 8, 33, 64):
             scene.set_option(capi.OPTION_TRACE_DYNAMIC, refill)
             img = scene.render(rs, w, h)
             assert np.array_equal(img, ref), f"refill={refill}"

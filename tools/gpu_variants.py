@@ -1,6 +1,6 @@
 """One process, one scene build, many option variants of the render loop (gi_options.h: $GATLING_OPTIONS is read per giCRender).
 
-  python tools/gpu_variants.py c3 16 - trace_dyn=0 trace_dyn=32,trace_dyn_spill8=1        ("-" = defaults)
+  python tools/gpu_variants.py c3 16 - trace_dyn=1 trace_dyn=32,shadow_order=1        ("-" = defaults)
 
 Prints per variant: Msamples/s, wall ms, per-stage ms (HIP events, every 4th iteration), and whether the image is
 bit-identical to the first variant's (it must be: the knobs change scheduling, never arithmetic)."""

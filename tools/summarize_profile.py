@@ -73,8 +73,8 @@ def main():
     open(txt, "w").write("\n".join(lines) + "\n")
     js = {"tag": args.tag, "kernels": ks, "pmc": pmc}
     if pmc:
-        # the traversal stage's launches: k_trace<closest> (scene in LDS) or k_trace_dyn<closest> + its k_route pass
-        tk = [v for k, v in pmc.items() if (k.startswith("k_trace<false") or k.startswith("k_trace_dyn<false")) and ", true," not in k[:30]]
+        # the traversal stage's launches: k_trace_dyn<closest> + its k_route pass
+        tk = [v for k, v in pmc.items() if k.startswith("k_trace_dyn<false") and ", true," not in k[:30]]
         if tk:
             js["trace_bytes_per_launch"] = max(v["hbm_bytes_per_launch"] for v in tk) + (pmc["k_route"]["hbm_bytes_per_launch"] if "k_route" in pmc else 0.0)
     json.dump(js, open(os.path.join(ROOT, "profiles", f"{args.tag}_rocprofv3_summary.json"), "w"), indent=1)
