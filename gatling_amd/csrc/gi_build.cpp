@@ -107,7 +107,7 @@ int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vec
   want = (int)optionValue("two_level", want);
   size_t uniqueTris = 0;
   for (const MB& mb : meshBuilds) uniqueTris += mb.instCount ? mb.m->faces.size() : 0;
-  const bool beyondLds = flatNodes > 384u || flatTris > 128u;
+  const bool beyondLds = !sceneFitsLds(flatNodes, flatTris);
   (void)uniqueTris;
   // Opt-in only. Measured (r01k): although its working set is tiny (C4: 1.5 MB of BLAS nodes + 2.6 MB of mesh triangles instead of 41 + 335 MB) the first
   // version is SLOWER than the flat layout -- C4 trace 185 -> 207 ms, C5 834 -> 1945 ms (29 instead of 20 nodes per ray: overlapping instance boxes, each visit
@@ -534,7 +534,7 @@ int buildScene(GiCScene* s)
   for (size_t i = 0; i < bvh.tris.size(); i++) H.triFaceId[i] = faceIdOf[bvh.tris[i].origId];
   // Scenes beyond LDS: one 160-byte shading record per mesh triangle (gi_types.h TriShade); the flattened triangles name theirs in vi[0].  LDS-resident
   // scenes keep vertex indices there: the fused kernels are VALU-bound and read the host-decoded FVertex records.
-  H.shadePacked = bvh.nodes.size() > 384u || bvh.tris.size() > 128u;
+  H.shadePacked = !sceneFitsLds(bvh.nodes.size(), bvh.tris.size());
   H.triShade.clear();
   if (H.shadePacked) {
     const std::vector<uint32_t> shadeBaseOfMesh = buildShadeRecords(H);

@@ -19,7 +19,7 @@ static int giCTraceRaysImpl(GiCScene* s, uint32_t count, const float* origins, c
   hipStream_t st = g_ctx.stream;
   if (syncSceneGeometry(s) != GI_C_OK) return -1;
   // the render loop's grids: k_trace_dyn (scenes beyond LDS) is persistent per wave and wants every resident wave slot filled (8 blocks per CU offered)
-  const bool inLds = s->nodeCount <= 384u && s->triCount <= 128u;
+  const bool inLds = sceneFitsLds(s->nodeCount, s->triCount);
   const uint32_t blocks = std::min<uint32_t>((count + 255u) / 256u, (uint32_t)g_ctx.cuCount * (inLds ? 3u : 8u));
   if (ensurePathState(s, count, blocks, blocks) != GI_C_OK) return -1;
   // ray records go straight into the TRACE_A queue (segment k holds rays [k*per, (k+1)*per))

@@ -59,7 +59,7 @@ void setError(const std::string& e);
 // One entry per HIP device the library renders on (giCInitializeDevices / $GATLING_DEVICES; giCInitialize: one).  devs[0] is the PRIMARY device:
 // render buffers, textures and every single-device entry point live there; the others hold replicas of the scene and render row shares.
 struct DevCtx { int device = 0; int cuCount = 256; hipStream_t stream = nullptr; hipStream_t stream2 = nullptr;
-    /* the shadow launches of two-stream batches (renderOnDevice "two streams") */
+    /* the shadow launches of two-stream batches (gi_render.cpp scheduleFrame "Two streams", runWavefrontBatch) */
                 /* 1: the primary device and this one address each other's memory (peer access enabled both ways, or the same physical device); 0: no peer
                    access -- the device's row shares travel through pinned host memory; -1: hipDeviceCanAccessPeer / EnablePeerAccess failed with an error */
                 int peer = 1; };
@@ -102,7 +102,7 @@ struct DeviceBuffer {
     const hipError_t e = hipMalloc((void**)&ptr, n * sizeof(T));
     if (e != hipSuccess) {
       ptr = nullptr;
-      // out of memory is an answer the render loop acts on (more batches, a smaller pool: renderOnDevice), not yet an error
+      // out of memory is an answer the render loop acts on (more batches, a smaller pool: gi_render.cpp allocatePathPlan), not yet an error
       if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); t_lastError = "hipMalloc: out of memory"; return GI_C_OUT_OF_MEMORY_INTERNAL; }
       setError(std::string("hipMalloc: ") + hipGetErrorString(e)); return GI_C_ERROR;
     }
@@ -229,13 +229,22 @@ struct SceneDevice {
   DeviceBuffer<Counters> dCounters;
   Counters* hCounters = nullptr; // pinned
   uint64_t memTotalMb = 0;       // the device's memory (hipMemGetInfo, asked once): sizes the default sample-buffer budget
-  // drain test of the bounce loop: iteration it reads the queue sizes of iteration it - POLL_LAG (giCRenderImpl)
+  // drain test of the bounce loop: iteration it reads the queue sizes of iteration it - POLL_LAG (gi_render.cpp runWavefrontBatch)
   static constexpr uint32_t POLL_RING = 4, POLL_LAG = 2;
   PaddedCounter* hPoll = nullptr; hipEvent_t pollEvent[POLL_RING] = {}; // pinned ring of queue-size snapshots + their completion events
   // two-stream batches: k_shade(i) done (the second stream's shadow launch waits for it) / shadow launch (i) done (k_raygen(i + 1) waits for it)
   hipEvent_t evShade = nullptr, evShadow = nullptr;
   GiCRenderStats stats{};
   std::vector<hipEvent_t> eventPool;
+  // the resizable path state (what the memory plan of a render sizes: slots, media, sampleBuf, the queues) -- the ONE list of these buffers
+  template <typename Fn> void forEachPathBuffer(Fn&& fn)
+  {
+    fn(slots); fn(media); fn(sampleBuf);
+    for (uint32_t q = 0; q < Q_COUNT; q++) { fn(qSlot[q]); fn(qA[q]); fn(qB[q]); fn(qC[q]); }
+    fn(qFresh[0]); fn(qFresh[1]);
+  }
+  uint64_t pathStateBytes() { uint64_t n = 0; forEachPathBuffer([&](auto& b) { n += b.bytes(); }); return n; }
+  void releasePathState() { forEachPathBuffer([](auto& b) { b.release(); }); queueCap = 0; }
   void releaseAll();
 };
 

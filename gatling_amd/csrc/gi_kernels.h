@@ -15,6 +15,9 @@ void launchRaygen(hipStream_t s, uint32_t blocks, const FrameUniforms& U, const 
 void launchAccumulate(hipStream_t s, const FrameUniforms& U, const F4* sampleBuf, F4* accum, F4* colorOut, bool firstBatch, bool lastBatch);
 // launchTrace runs the block-synchronous k_trace on this scene (staged whole in LDS, at most 8 levels deep) rather than k_trace_dyn + k_route
 bool traceBlockSync(const SceneView& sc);
+// a tree of this many nodes and triangles is staged whole in LDS (gi_traversal.h LDS_NODES / LDS_TRIS); beyond it the host packs shading records, sizes a
+// larger path pool and may build the two-level layout
+bool sceneFitsLds(size_t nodeCount, size_t triCount);
 // LDS bytes one k_trace block needs for this scene (stack + staged nodes + staged triangles)
 uint32_t traceStaticLdsBytes(); // static LDS of the traversal kernels on top of traceLdsLayout's dynamic bytes
 void traceLdsLayout(const SceneView& sc, uint32_t& ldsNodes, uint32_t& ldsTris, uint32_t& bytes);

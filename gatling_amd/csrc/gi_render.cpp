@@ -1,4 +1,6 @@
-// gi_render.cpp -- giCRender: dirty handling, uniforms, memory plan, the bounce loop on one / several devices (Gi.cpp:1989-2524)
+// gi_render.cpp -- giCRender (Gi.cpp:1989-2524): validation and dirty handling (giCRenderImpl), the rows dealt to several devices (renderOnDevices), and one
+// device's render (renderOnDevice) as a sequence of phases: bindAovs, makeUniforms, makeFrameView, planPathMemory / allocatePathPlan, scheduleFrame /
+// scheduleBatch, runFusedBatch | runZeroBounceBatch | runWavefrontBatch (the bounce loop), finishPathAovs, runAovPass, readBackAndWait, the statistics
 // (one of the translation units gi_c.cpp was split into in round 6; shared declarations: gi_host.h)
 #include "gi_host.h"
 
@@ -103,528 +105,733 @@ struct RenderJob { const GiCRenderParams* params; const GiCAovBinding* colorBind
 
 static void* rbMem(GiCRenderBuffer* rb, uint32_t slot) { return (slot == 0u || rb->scratch) ? rb->deviceMem : rb->replicaMem[slot - 1u]; }
 
-static int renderOnDevice(GiCScene* s, SceneDevice& D, const RenderJob& job)
+// ---------------------------------------------------------------------------------------------------------------
+// renderOnDevice and its phases, in the order they run
+// ---------------------------------------------------------------------------------------------------------------
+// What the bindings of a render resolve to on one device (Gi.h:36-56).  NEE, Bounces and ClockCycles follow whole paths: they are filled by the colour pass
+// (clear value first), see PathState.  ClockCycles is a deterministic cost proxy (ray segments per pixel), heat-mapped like the reference.
+struct BoundAovs {
+  AovTargets targets{};                          // what k_aov writes ...
+  std::vector<GiCRenderBuffer*> produced;        // ... and the buffers behind it
+  GiCRenderBuffer* nee = nullptr; GiCRenderBuffer* bounces = nullptr; GiCRenderBuffer* clock = nullptr; // the path-following AOVs
+  GiCRenderBuffer* color = nullptr;              // the colour AOV's buffer, or `scratchColor` when only path-following AOVs need the colour pass
+  GiCRenderBuffer scratchColor{};
+};
+
+static int bindAovs(SceneDevice& D, const RenderJob& job, hipStream_t st, BoundAovs& A)
 {
-  const DevCtx& ctx = g_ctx.devs[D.slot];
-  HIP_TRY(hipSetDevice(ctx.device));
-  hipStream_t st = ctx.stream;
   const GiCRenderParams* params = job.params;
-  const GiCRenderSettings& rs = params->renderSettings;
-  const GiCAovBinding* colorBinding = job.colorBinding;
-  const uint32_t width = job.width, height = job.height, rowBegin = job.rowBegin, rowEnd = job.rowEnd, rowStride = job.rowStride, tileRows = job.tileRows;
-  const uint8_t* clear = job.clear;
-  (void)height; (void)rowEnd;
-  D.stats.bvhBuildMs = s->stats.bvhBuildMs; D.stats.uploadMs = s->stats.uploadMs;
-  // --- non-colour AOV bindings (Gi.h:36-56).  NEE, Bounces and ClockCycles follow whole paths: they are filled by the colour pass
-  // (clear value first), see PathState.  ClockCycles is a deterministic cost proxy (ray segments per pixel), heat-mapped like the reference.
-  AovTargets aovT{}; bool anyAov = false;
-  GiCRenderBuffer* neeRb = nullptr; GiCRenderBuffer* bouncesRb = nullptr; GiCRenderBuffer* clockRb = nullptr;
-  std::vector<GiCRenderBuffer*> aovBuffers;
   for (uint32_t i = 0; i < params->aovBindingCount; i++) {
     const GiCAovBinding& b = params->aovBindings[i];
     if (b.aovId == GI_C_AOV_COLOR) continue;
     GiCRenderBuffer* rb = b.renderBuffer;
-    if (rb->width != width || rb->height != height) { setError("giCRender: AOV buffers must share one size"); return GI_C_ERROR; }
+    if (rb->width != job.width || rb->height != job.height) { setError("giCRender: AOV buffers must share one size"); return GI_C_ERROR; }
     if (b.aovId < 0 || b.aovId >= GI_C_AOV_COUNT) { setError("giCRender: bad AOV id"); return GI_C_ERROR; }
-    memcpy(aovT.clear[b.aovId], b.clearValue, 16);
+    AovTargets& T = A.targets;
+    memcpy(T.clear[b.aovId], b.clearValue, 16);
     const bool vec = rb->stride == 16;
     F4* v4 = vec ? reinterpret_cast<F4*>(rbMem(rb, D.slot)) : nullptr;
     bool produced = true;
     switch (b.aovId) {
-      case GI_C_AOV_NORMAL: aovT.normal = v4; break; case GI_C_AOV_BARYCENTRICS: aovT.barycentrics = v4; break;
-      case GI_C_AOV_TEXCOORDS: aovT.texcoords = v4; break; case GI_C_AOV_OPACITY: aovT.opacity = v4; break;
-      case GI_C_AOV_TANGENTS: aovT.tangents = v4; break; case GI_C_AOV_BITANGENTS: aovT.bitangents = v4; break;
-      case GI_C_AOV_THIN_WALLED: aovT.thinWalled = v4; break; case GI_C_AOV_DOUBLE_SIDED: aovT.doubleSided = v4; break;
-      case GI_C_AOV_ALBEDO: aovT.albedo = v4; break;
-      case GI_C_AOV_DEPTH: aovT.depth = vec ? nullptr : reinterpret_cast<float*>(rbMem(rb, D.slot)); break;
-      case GI_C_AOV_OBJECT_ID: aovT.objectId = vec ? nullptr : reinterpret_cast<int32_t*>(rbMem(rb, D.slot)); break;
-      case GI_C_AOV_FACE_ID: aovT.faceId = vec ? nullptr : reinterpret_cast<int32_t*>(rbMem(rb, D.slot)); break;
-      case GI_C_AOV_INSTANCE_ID: aovT.instanceId = vec ? nullptr : reinterpret_cast<int32_t*>(rbMem(rb, D.slot)); break;
-      case GI_C_AOV_NEE: if (vec) neeRb = rb; produced = false; break;
-      case GI_C_AOV_BOUNCES: if (vec) bouncesRb = rb; produced = false; break;
-      case GI_C_AOV_CLOCK_CYCLES: if (vec) clockRb = rb; produced = false; break;
+      case GI_C_AOV_NORMAL: T.normal = v4; break; case GI_C_AOV_BARYCENTRICS: T.barycentrics = v4; break;
+      case GI_C_AOV_TEXCOORDS: T.texcoords = v4; break; case GI_C_AOV_OPACITY: T.opacity = v4; break;
+      case GI_C_AOV_TANGENTS: T.tangents = v4; break; case GI_C_AOV_BITANGENTS: T.bitangents = v4; break;
+      case GI_C_AOV_THIN_WALLED: T.thinWalled = v4; break; case GI_C_AOV_DOUBLE_SIDED: T.doubleSided = v4; break;
+      case GI_C_AOV_ALBEDO: T.albedo = v4; break;
+      case GI_C_AOV_DEPTH: T.depth = vec ? nullptr : reinterpret_cast<float*>(rbMem(rb, D.slot)); break;
+      case GI_C_AOV_OBJECT_ID: T.objectId = vec ? nullptr : reinterpret_cast<int32_t*>(rbMem(rb, D.slot)); break;
+      case GI_C_AOV_FACE_ID: T.faceId = vec ? nullptr : reinterpret_cast<int32_t*>(rbMem(rb, D.slot)); break;
+      case GI_C_AOV_INSTANCE_ID: T.instanceId = vec ? nullptr : reinterpret_cast<int32_t*>(rbMem(rb, D.slot)); break;
+      case GI_C_AOV_NEE: if (vec) A.nee = rb; produced = false; break;
+      case GI_C_AOV_BOUNCES: if (vec) A.bounces = rb; produced = false; break;
+      case GI_C_AOV_CLOCK_CYCLES: if (vec) A.clock = rb; produced = false; break;
       default: produced = false; break;
     }
     if (produced) {
       const bool wantsVec = !(b.aovId == GI_C_AOV_DEPTH || b.aovId == GI_C_AOV_OBJECT_ID || b.aovId == GI_C_AOV_FACE_ID || b.aovId == GI_C_AOV_INSTANCE_ID);
       if (wantsVec != vec) { setError("giCRender: AOV render buffer format does not match the AOV (Gi.cpp:302-316)"); return GI_C_ERROR; }
-      anyAov = true; aovBuffers.push_back(rb);
+      A.produced.push_back(rb);
     } else { // clear value everywhere (the host copy was filled by fillClearValues before the device threads started)
       HIP_TRY(hipMemcpyAsync(rbMem(rb, D.slot), rb->hostMem, rb->size, hipMemcpyHostToDevice, st));
     }
   }
-  if (!colorBinding && !anyAov && !neeRb && !bouncesRb && !clockRb) { HIP_TRY(hipStreamSynchronize(st)); return GI_C_OK; }
-  GiCRenderBuffer dummyColor{};
-  GiCRenderBuffer* colorRb = colorBinding ? colorBinding->renderBuffer : nullptr;
-  if (!colorRb && (neeRb || bouncesRb || clockRb)) { // the path-following debug AOVs need the colour pass: render it into a scratch buffer
-    if (D.scratchColor.alloc((size_t)width * height)) return GI_C_ERROR;
-    dummyColor.width = width; dummyColor.height = height; dummyColor.stride = 16; dummyColor.size = (size_t)width * height * 16;
-    dummyColor.deviceMem = D.scratchColor.ptr; dummyColor.deviceOnly = true; dummyColor.scratch = true;
-    colorRb = &dummyColor;
+  A.color = job.colorBinding ? job.colorBinding->renderBuffer : nullptr;
+  if (!A.color && (A.nee || A.bounces || A.clock)) { // the path-following debug AOVs need the colour pass: render it into a scratch buffer
+    const size_t n = (size_t)job.width * job.height;
+    if (D.scratchColor.alloc(n)) return GI_C_ERROR;
+    GiCRenderBuffer& c = A.scratchColor;
+    c.width = job.width; c.height = job.height; c.stride = 16; c.size = n * 16;
+    c.deviceMem = D.scratchColor.ptr; c.deviceOnly = true; c.scratch = true;
+    A.color = &c;
   }
-  if (colorRb && colorRb->stride != 16) { setError("giCRender: colour AOV needs a Float32Vec4 buffer"); return GI_C_ERROR; }
-  (void)dummyColor;
+  if (A.color && A.color->stride != 16) { setError("giCRender: colour AOV needs a Float32Vec4 buffer"); return GI_C_ERROR; }
+  return GI_C_OK;
+}
 
-  // --- uniforms (Gi.cpp:2373-2426; camera terms rp_main.rgen:199-212 evaluated once on the host)
-  const size_t pixels = (size_t)tileRows * width;
-  // device -> host copy of the tile's rows (one 2D copy: the rows are rowStride image rows apart)
-  auto copyTileRows = [&](GiCRenderBuffer* rb, size_t texel) -> hipError_t {
-    const size_t off = (size_t)rowBegin * width * texel, rowBytes = (size_t)width * texel, pitch = rowBytes * rowStride;
-    if (rowStride == 1u) return hipMemcpyAsync((uint8_t*)rb->hostMem + off, (uint8_t*)rbMem(rb, D.slot) + off, rowBytes * tileRows, hipMemcpyDeviceToHost, st);
-    return hipMemcpy2DAsync((uint8_t*)rb->hostMem + off, pitch, (uint8_t*)rbMem(rb, D.slot) + off, pitch, rowBytes, tileRows, hipMemcpyDeviceToHost, st);
-  };
-  if (pixels == 0) return GI_C_OK;
+// device -> host copy of the tile's rows (one 2D copy: the rows are rowStride image rows apart)
+static hipError_t copyTileRows(GiCRenderBuffer* rb, size_t texel, const RenderJob& job, uint32_t slot, hipStream_t st)
+{
+  const size_t off = (size_t)job.rowBegin * job.width * texel, rowBytes = (size_t)job.width * texel, pitch = rowBytes * job.rowStride;
+  if (job.rowStride == 1u) {
+    return hipMemcpyAsync((uint8_t*)rb->hostMem + off, (uint8_t*)rbMem(rb, slot) + off, rowBytes * job.tileRows, hipMemcpyDeviceToHost, st);
+  }
+  return hipMemcpy2DAsync((uint8_t*)rb->hostMem + off, pitch, (uint8_t*)rbMem(rb, slot) + off, pitch, rowBytes, job.tileRows, hipMemcpyDeviceToHost, st);
+}
+
+// Uniforms (Gi.cpp:2373-2426; camera terms rp_main.rgen:199-212 evaluated once on the host).  The schedule adds its flags later (scheduleFrame /
+// scheduleBatch).
+static FrameUniforms makeUniforms(const GiCRenderParams& params, const RenderJob& job, const GiCScene* s)
+{
+  const GiCRenderSettings& rs = params.renderSettings;
+  const GiCCameraDesc& c = params.camera;
+  const uint32_t width = job.width, height = job.height;
   FrameUniforms U{};
-  {
-    const GiCCameraDesc& c = params->camera;
-    auto norm3 = [](const float* v, float* o) { float inv = 1.0f / sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]); o[0] = v[0] * inv; o[1] = v[1] * inv;
-        o[2] = v[2] * inv; };
-    norm3(c.forward, U.camFwd); norm3(c.up, U.camUp);
-    memcpy(U.camPos, c.position, 12);
-    U.camRight[0] = U.camFwd[1] * U.camUp[2] - U.camFwd[2] * U.camUp[1];
-    U.camRight[1] = U.camFwd[2] * U.camUp[0] - U.camFwd[0] * U.camUp[2];
-    U.camRight[2] = U.camFwd[0] * U.camUp[1] - U.camFwd[1] * U.camUp[0];
-    float aspect = (float)width / (float)height;
-    float H = 1.0f, W = H * aspect;
-    float d = H / (2.0f * tanf(c.vfov * 0.5f));
-    U.WX = W / (float)width; U.HY = H / (float)height;
-    for (int a = 0; a < 3; a++) {
-      float C = U.camPos[a] + U.camFwd[a] * d;
-      U.L[a] = (C - U.camRight[a] * W * 0.5f) - U.camUp[a] * H * 0.5f;
-    }
-    U.lensRadius = (c.fStop > 0.0f) ? c.focalLength / (2.0f * c.fStop) : 0.0f;
-    U.focusDistance = c.focusDistance;
-    uint32_t cr = packHalf2x16(c.clipStart, c.clipEnd);
-    U.clipNear = f16ToF32((uint16_t)(cr & 0xffffu)); U.clipFar = f16ToF32((uint16_t)(cr >> 16));
-    float cv[4]; memcpy(cv, clear, 16);
-    for (int a = 0; a < 3; a++) { // fallback dome texel: glm::u8vec4(bg * 255) as RGBA8 unorm (Gi.cpp:2194-2199)
-      int q = (int)(cv[a] * 255.0f); if (q < 0) q = 0; if (q > 255) q &= 255;
-      U.background[a] = (float)q / 255.0f;
-    }
-    U.exposureScale = exp2f(c.exposure);
-    U.spp = rs.spp; U.sampleOffset = s->sampleOffset; U.invSpp = 1.0f / (float)rs.spp; U.sppF = (float)rs.spp; U.sampleOffsetF = (float)s->sampleOffset;
-    U.invTotalSampleCount = 1.0f / float(s->sampleOffset + rs.spp);
-    U.maxSampleValue = rs.maxSampleValue; U.rrInvMinTermProb = rs.rrInvMinTermProb; U.lightIntensityMultiplier = rs.lightIntensityMultiplier;
-    U.metersPerSceneUnit = rs.metersPerSceneUnit;
-    U.mediumStackSize = rs.mediumStackSize; U.maxVolumeWalkLength = rs.maxVolumeWalkLength;
-    U.mediumStackSize = rs.mediumStackSize; U.maxVolumeWalkLength = rs.maxVolumeWalkLength;
-    U.maxBounces = std::min(rs.maxBounces, 0xfffu); U.rrBounceOffset = rs.rrBounceOffset & 0xffffu;
-    U.imageWidth = width; U.imageHeight = height; U.rowBegin = rowBegin; U.rowStride = rowStride; U.pixelCount = (uint32_t)pixels;
-    U.flags = (rs.jitteredSampling ? FLAG_JITTER : 0u) | (rs.filterImportanceSampling ? FLAG_FIS : 0u) | (rs.depthOfField ? FLAG_DOF : 0u) |
-              (rs.clippingPlanes ? FLAG_CLIP : 0u) | (rs.nextEventEstimation ? FLAG_NEE : 0u) | (rs.progressiveAccumulation ? FLAG_PROGRESSIVE : 0u);
-    U.sphereCount = s->lightCounts[0]; U.distantCount = s->lightCounts[1]; U.rectCount = s->lightCounts[2]; U.diskCount = s->lightCounts[3]; // (uploadLights)
-    U.totalLightCount = U.sphereCount + U.distantCount + U.rectCount + U.diskCount;
+  auto norm3 = [](const float* v, float* o) {
+    float inv = 1.0f / sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+    o[0] = v[0] * inv; o[1] = v[1] * inv; o[2] = v[2] * inv;
+  };
+  norm3(c.forward, U.camFwd); norm3(c.up, U.camUp);
+  memcpy(U.camPos, c.position, 12);
+  U.camRight[0] = U.camFwd[1] * U.camUp[2] - U.camFwd[2] * U.camUp[1];
+  U.camRight[1] = U.camFwd[2] * U.camUp[0] - U.camFwd[0] * U.camUp[2];
+  U.camRight[2] = U.camFwd[0] * U.camUp[1] - U.camFwd[1] * U.camUp[0];
+  float aspect = (float)width / (float)height;
+  float H = 1.0f, W = H * aspect;
+  float d = H / (2.0f * tanf(c.vfov * 0.5f));
+  U.WX = W / (float)width; U.HY = H / (float)height;
+  for (int a = 0; a < 3; a++) {
+    float C = U.camPos[a] + U.camFwd[a] * d;
+    U.L[a] = (C - U.camRight[a] * W * 0.5f) - U.camUp[a] * H * 0.5f;
   }
+  U.lensRadius = (c.fStop > 0.0f) ? c.focalLength / (2.0f * c.fStop) : 0.0f;
+  U.focusDistance = c.focusDistance;
+  uint32_t cr = packHalf2x16(c.clipStart, c.clipEnd);
+  U.clipNear = f16ToF32((uint16_t)(cr & 0xffffu)); U.clipFar = f16ToF32((uint16_t)(cr >> 16));
+  float cv[4]; memcpy(cv, job.clear, 16);
+  for (int a = 0; a < 3; a++) { // fallback dome texel: glm::u8vec4(bg * 255) as RGBA8 unorm (Gi.cpp:2194-2199)
+    int q = (int)(cv[a] * 255.0f); if (q < 0) q = 0; if (q > 255) q &= 255;
+    U.background[a] = (float)q / 255.0f;
+  }
+  U.exposureScale = exp2f(c.exposure);
+  U.spp = rs.spp; U.sampleOffset = s->sampleOffset; U.invSpp = 1.0f / (float)rs.spp; U.sppF = (float)rs.spp; U.sampleOffsetF = (float)s->sampleOffset;
+  U.invTotalSampleCount = 1.0f / float(s->sampleOffset + rs.spp);
+  U.maxSampleValue = rs.maxSampleValue; U.rrInvMinTermProb = rs.rrInvMinTermProb; U.lightIntensityMultiplier = rs.lightIntensityMultiplier;
+  U.metersPerSceneUnit = rs.metersPerSceneUnit;
+  U.mediumStackSize = rs.mediumStackSize; U.maxVolumeWalkLength = rs.maxVolumeWalkLength;
+  U.maxBounces = std::min(rs.maxBounces, 0xfffu); U.rrBounceOffset = rs.rrBounceOffset & 0xffffu;
+  U.imageWidth = width; U.imageHeight = height; U.rowBegin = job.rowBegin; U.rowStride = job.rowStride; U.pixelCount = (uint32_t)((size_t)job.tileRows * width);
+  U.flags = (rs.jitteredSampling ? FLAG_JITTER : 0u) | (rs.filterImportanceSampling ? FLAG_FIS : 0u) | (rs.depthOfField ? FLAG_DOF : 0u) |
+            (rs.clippingPlanes ? FLAG_CLIP : 0u) | (rs.nextEventEstimation ? FLAG_NEE : 0u) | (rs.progressiveAccumulation ? FLAG_PROGRESSIVE : 0u);
+  U.sphereCount = s->lightCounts[0]; U.distantCount = s->lightCounts[1]; U.rectCount = s->lightCounts[2]; U.diskCount = s->lightCounts[3]; // (uploadLights)
+  U.totalLightCount = U.sphereCount + U.distantCount + U.rectCount + U.diskCount;
+  return U;
+}
 
-  double tStart = nowMs();
-  uint32_t iters = 0, traceLaunches = 0;
-  bool usedFused = false;
-  size_t ev = 0;
-  std::vector<int> evKind; // 0 raygen, 1 trace, 2 shade, 3 shadow
-  struct IterRow { size_t evEnd; uint64_t traced, hits, shadow, ended, cont; };
-  std::vector<IterRow> iterRows; // (GATLING_ITER_LOG)
-  const bool timers = s->kernelTimers;
-  uint64_t sampledIters = 0, totalIters = 0;
+// The scene as this render sees it: D's arrays plus the dome light (Gi.cpp:2201-2238, 2384-2396): an image-less dome light is ignored, like one whose file
+// failed to load.  (mediumStackSize is the colour pass's: renderOnDevice sets it there.)
+static SceneView makeFrameView(GiCScene* s, SceneDevice& D, const GiCRenderParams& params, const FrameUniforms& U)
+{
   SceneView view = makeView(s, D);
-  { // dome light (Gi.cpp:2201-2238, 2384-2396): an image-less dome light is ignored, like one whose file failed to load
-    const GiCDomeLight* dl = params->domeLight;
-    auto tit = (dl && dl->texture) ? std::find(s->textures.begin(), s->textures.end(), dl->texture) : s->textures.end();
-    view.domeTexture = tit != s->textures.end() ? (uint32_t)(tit - s->textures.begin()) + 1u : 0u;
-    view.domeCameraVisible = rs.domeLightCameraVisible ? 1u : 0u;
-    for (int a = 0; a < 4; a++) view.domeRotation[a] = dl ? dl->rotation[a] : (a == 3 ? 1.0f : 0.0f);
-    for (int a = 0; a < 3; a++) { view.domeEmission[a] = dl ? dl->baseEmission[a] : 1.0f; view.background[a] = U.background[a];
-        view.cameraPosition[a] = params->camera.position[a]; }
-    view.frame = rs.frame;
+  const GiCDomeLight* dl = params.domeLight;
+  auto tit = (dl && dl->texture) ? std::find(s->textures.begin(), s->textures.end(), dl->texture) : s->textures.end();
+  view.domeTexture = tit != s->textures.end() ? (uint32_t)(tit - s->textures.begin()) + 1u : 0u;
+  view.domeCameraVisible = params.renderSettings.domeLightCameraVisible ? 1u : 0u;
+  for (int a = 0; a < 4; a++) view.domeRotation[a] = dl ? dl->rotation[a] : (a == 3 ? 1.0f : 0.0f);
+  for (int a = 0; a < 3; a++) {
+    view.domeEmission[a] = dl ? dl->baseEmission[a] : 1.0f; view.background[a] = U.background[a];
+    view.cameraPosition[a] = params.camera.position[a];
   }
-  if (ensurePathState(&D, 1, 1, 1) != GI_C_OK) return GI_C_ERROR; // counters / pinned mirror exist even for AOV-only renders
-  if (colorRb) {
-    // --- work decomposition (DESIGN.md "Persistent path pool"): work item = (pixel, sample); the frame is cut into batches of
-    // consecutive samples whose per-sample colour buffer fits the budget; a pool of `slots` paths is kept full from a running
-    // work counter until the batch's items run out.
-    auto envU64 = [](const char* key, uint64_t def) { return optionSet(key) ? (uint64_t)optionValue(key, 0) : def; };
-    // Memory plan (r04). The per-sample colour buffer wants to hold the whole frame's samples (every batch ends in a drain / a kernel tail: C2's 34 GB for 1024
-    // spp at 1080p in one batch 213.4 ms per step, in four 215.5) and scenes beyond LDS want a 64 Mi-slot pool (17 GB with its queues) -- on an empty 288 GB
-    // device. A Hydra plugin shares the device with other scenes, other processes and the host application, so the plan starts from what is FREE now (plus what
-    // this scene already holds in these buffers, which is reused), and an allocation that still fails (someone else was faster) is answered with a smaller plan
-    // -- more batches first, then a smaller pool -- never with a failed render while a workable plan exists. Results do not depend on the plan
-    // (test_pool_and_batch_invariance).
-    size_t memFree = 0, memTotal = 0; (void)hipMemGetInfo(&memFree, &memTotal);
-    // tests: plan as if this much were free (a planner overtaken by another allocation: the fallback below must recover)
-    if (optionSet("assume_free_mb")) memFree = (size_t)optionValue("assume_free_mb", 0) << 20;
-    if (!D.memTotalMb) D.memTotalMb = std::max<uint64_t>(1, (uint64_t)(memTotal >> 20));
-    uint64_t held = D.sampleBuf.bytes() + D.slots.bytes() + D.media.bytes();
-    for (uint32_t q = 0; q < Q_COUNT; q++) held += D.qSlot[q].bytes() + D.qA[q].bytes() + D.qB[q].bytes() + D.qC[q].bytes();
-    held += D.qFresh[0].bytes() + D.qFresh[1].bytes();
-    const uint64_t availMb = ((uint64_t)memFree + held) >> 20;
-    const uint64_t capMb = std::max<uint64_t>(1024, std::min<uint64_t>(49152, D.memTotalMb / 6)); // the budget of an empty device: 48 GiB of 288 GB
-    const uint64_t defaultMb = std::max<uint64_t>(256, std::min<uint64_t>(capMb, availMb / 3));    // ... and a third of what is available now, 256 MiB at least
-    const uint64_t budgetBytes = envU64("sample_buffer_mb", s->optSampleBufferMb ? s->optSampleBufferMb : defaultMb) << 20;
-    // Pool size: a launch of k_trace_dyn ends when its longest ray ends, and ray cost is heavy-tailed in scenes beyond LDS
-    // (a 100-step ray outlives the average one six times over), so those scenes get a pool large enough to amortise that
-    // tail (measured on C3 at spp 64 / 256: 4 Mi slots 630, 16 Mi 790, 32 Mi 831 / 810, 64 Mi - / 868 Msamples/s); LDS-resident scenes have uniform, short
-    // rays.
-    const bool sceneInLds = s->nodeCount <= 384u && s->triCount <= 128u;
-    const uint64_t poolDefault = sceneInLds ? (4u << 20) : (64u << 20);
-    const uint64_t poolMax = std::min<uint64_t>((1ull << 30) - 1ull, // regen-queue entries keep two flag bits above the slot index (REGEN_MISSED, REGEN_FRESH)
-                                                std::max<uint64_t>(64, envU64("pool_slots", s->optPoolSlots ? s->optPoolSlots : poolDefault)));
-    uint64_t batchSamples = std::min<uint64_t>(rs.spp, std::max<uint64_t>(1, budgetBytes / (pixels * 16)));
-    batchSamples = std::min<uint64_t>(batchSamples, std::max<uint64_t>(1, 0xffffffffull / pixels)); // work ids stay 32-bit
-    // LDS-resident scenes without medium stacks / dome images: the fused persistent kernel k_path (gi_path.hip) keeps the paths in
-    // registers -- no pool, no queues; the stage kernels below remain the path for everything else (and on request: option / env)
-    view.mediumStackSize = rs.mediumStackSize;
-    bool fused = pathKernelSupports(view) && s->optFusedPath != 0;
-    fused = fused && optionValue("fused", 1) != 0;
-    usedFused = fused;
-    // work order of the wavefront pipeline and layout of its per-sample buffer (gi_queues.h work_item); the fused kernels hand work out sample-major
-    if (!fused && optionValue("work_order", WORK_ORDER_PIXEL_MAJOR_DEFAULT ? 1 : 0) != 0) U.flags |= FLAG_PIXEL_MAJOR;
-    size_t slots = fused ? 1 : (size_t)std::min<uint64_t>(poolMax, (uint64_t)pixels * batchSamples);
+  view.frame = params.renderSettings.frame;
+  return view;
+}
 
-    // persistent grids: blocks per CU limited by registers (<= 6 waves/SIMD for k_trace) and, for k_trace, by the LDS it stages
-    uint32_t wideBlocks = 1u, traceBlocks = 1u;
-    auto sizeGrids = [&]() {
-      const SceneView v0 = makeView(s, D);
-      uint32_t perCu = 8u; // k_trace_dyn is persistent per wave: blocks beyond what is resident find the cursor exhausted
-      if (traceBlockSync(v0)) {
-        uint32_t ln, lt, ldsBytes; traceLdsLayout(v0, ln, lt, ldsBytes);
-        perCu = std::max(1u, std::min<uint32_t>(6u, (160u * 1024u) / (ldsBytes + traceStaticLdsBytes() + 256u)));
+// --- memory plan (r04).  Work decomposition (DESIGN.md "Persistent path pool"): work item = (pixel, sample); the frame is cut into batches of
+// consecutive samples whose per-sample colour buffer fits the budget; a pool of `slots` paths is kept full from a running
+// work counter until the batch's items run out.
+struct PathPlan {
+  size_t slots = 1;                            // paths in the pool (the fused kernel keeps its paths in registers: 1)
+  uint64_t batchSamples = 1;                   // samples per pixel and batch: sizes the per-sample colour buffer
+  uint32_t wideBlocks = 1u, traceBlocks = 1u;  // persistent grids of the streaming kernels / of the traversal kernels
+  uint32_t mediaStride = 0u;                   // floats of a slot's medium stack
+  bool fused = false;                          // the batches run k_path (gi_path.hip) instead of the stage kernels
+  bool pinned = false;                         // the caller gave the pool or the sample buffer a size: taken as given
+};
+// what the plan's arithmetic needs to know of the frame and the device
+struct PlanInputs { size_t pixels; uint32_t cuCount, tracePerCu; };
+
+static uint64_t optionU64(const char* key, uint64_t def) { return optionSet(key) ? (uint64_t)optionValue(key, 0) : def; }
+
+// persistent grids: blocks per CU limited by registers (<= 6 waves/SIMD for k_trace) and, for k_trace, by the LDS it stages
+static uint32_t traceBlocksPerCu(const SceneView& v)
+{
+  if (!traceBlockSync(v)) return 8u; // k_trace_dyn is persistent per wave: blocks beyond what is resident find the cursor exhausted
+  uint32_t ln, lt, ldsBytes; traceLdsLayout(v, ln, lt, ldsBytes);
+  return std::max(1u, std::min<uint32_t>(6u, (160u * 1024u) / (ldsBytes + traceStaticLdsBytes() + 256u)));
+}
+static void sizeGrids(PathPlan& p, const PlanInputs& in)
+{
+  p.wideBlocks = (uint32_t)std::min<size_t>((p.slots + 255) / 256, (size_t)in.cuCount * 8u);
+  p.traceBlocks = (uint32_t)std::min<size_t>((p.slots + 255) / 256, (size_t)in.cuCount * in.tracePerCu);
+}
+// what a plan costs: the slot pool with its queues (per slot: the Slot, the medium stack, and a share of every queue's records) and the sample buffer
+static uint64_t planBytes(const PathPlan& p, size_t pixels)
+{
+  const uint64_t cap = shardCapacity(p.slots, p.wideBlocks, p.traceBlocks);
+  const uint64_t perQueueEntry = 4ull * Q_COUNT + 32ull * (2 + 1) + 16ull + 8ull * 2;
+  return (p.fused ? 0ull : (uint64_t)p.slots * (sizeof(Slot) + 4ull * p.mediaStride) + cap * NSHARD * perQueueEntry) + (uint64_t)pixels * p.batchSamples * 16ull
+         + (uint64_t)pixels * 16ull;
+}
+// the next smaller plan: halve the sample buffer down to 64 MiB (more batches), then the pool down to 64 Ki slots (the caller sizes the grids again)
+static bool shrinkPlan(PathPlan& p, size_t pixels)
+{
+  if (p.batchSamples > 1 && (uint64_t)pixels * p.batchSamples * 16ull > (64ull << 20)) {
+    p.batchSamples = std::max<uint64_t>(1, p.batchSamples / 2);
+    if (!p.fused) p.slots = (size_t)std::min<uint64_t>(p.slots, (uint64_t)pixels * p.batchSamples);
+    return true;
+  }
+  if (!p.fused && p.slots > (64u << 10)) { p.slots /= 2; return true; }
+  return false;
+}
+
+// The plan's arithmetic. The per-sample colour buffer wants to hold the whole frame's samples (every batch ends in a drain / a kernel tail: C2's 34 GB for 1024
+// spp at 1080p in one batch 213.4 ms per step, in four 215.5) and scenes beyond LDS want a 64 Mi-slot pool (17 GB with its queues) -- on an empty 288 GB
+// device. A Hydra plugin shares the device with other scenes, other processes and the host application, so the plan starts from what is FREE now (plus what
+// this scene already holds in these buffers, which is reused), and an allocation that still fails (someone else was faster) is answered with a smaller plan
+// -- more batches first, then a smaller pool -- never with a failed render while a workable plan exists (allocatePathPlan). Results do not depend on the plan
+// (test_pool_and_batch_invariance).
+static PathPlan planPathMemory(const GiCScene* s, const GiCRenderSettings& rs, const SceneView& view, const PlanInputs& in, uint64_t freeBytes,
+                               uint64_t heldBytes, uint64_t memTotalMb)
+{
+  const size_t pixels = in.pixels;
+  const uint64_t availMb = (freeBytes + heldBytes) >> 20;
+  const uint64_t capMb = std::max<uint64_t>(1024, std::min<uint64_t>(49152, memTotalMb / 6)); // the budget of an empty device: 48 GiB of 288 GB
+  const uint64_t defaultMb = std::max<uint64_t>(256, std::min<uint64_t>(capMb, availMb / 3));  // ... and a third of what is available now, 256 MiB at least
+  const uint64_t budgetBytes = optionU64("sample_buffer_mb", s->optSampleBufferMb ? s->optSampleBufferMb : defaultMb) << 20;
+  // Pool size: a launch of k_trace_dyn ends when its longest ray ends, and ray cost is heavy-tailed in scenes beyond LDS
+  // (a 100-step ray outlives the average one six times over), so those scenes get a pool large enough to amortise that
+  // tail (measured on C3 at spp 64 / 256: 4 Mi slots 630, 16 Mi 790, 32 Mi 831 / 810, 64 Mi - / 868 Msamples/s); LDS-resident scenes have uniform, short
+  // rays.
+  const uint64_t poolDefault = sceneFitsLds(s->nodeCount, s->triCount) ? (4u << 20) : (64u << 20);
+  const uint64_t poolMax = std::min<uint64_t>((1ull << 30) - 1ull, // regen-queue entries keep two flag bits above the slot index (REGEN_MISSED, REGEN_FRESH)
+                                              std::max<uint64_t>(64, optionU64("pool_slots", s->optPoolSlots ? s->optPoolSlots : poolDefault)));
+  PathPlan p;
+  p.batchSamples = std::min<uint64_t>(rs.spp, std::max<uint64_t>(1, budgetBytes / (pixels * 16)));
+  p.batchSamples = std::min<uint64_t>(p.batchSamples, std::max<uint64_t>(1, 0xffffffffull / pixels)); // work ids stay 32-bit
+  // LDS-resident scenes without medium stacks / dome images: the fused persistent kernel k_path (gi_path.hip) keeps the paths in
+  // registers -- no pool, no queues; the stage kernels remain the path for everything else (and on request: option / env)
+  p.fused = pathKernelSupports(view) && s->optFusedPath != 0 && optionValue("fused", 1) != 0;
+  p.slots = p.fused ? 1 : (size_t)std::min<uint64_t>(poolMax, (uint64_t)pixels * p.batchSamples);
+  sizeGrids(p, in);
+  // HIT-queue entries (and giCTraceRays) hold a TRACE-queue RECORD index in 30 bits (HIT_INDEX_MASK); records run up to shardCapacity * NSHARD, which exceeds
+  // the slot count by the shards' slack -- a pinned pool near 2^30 would push indices past the mask and k_shade would gather the wrong record
+  while (!p.fused && (uint64_t)shardCapacity(p.slots, p.wideBlocks, p.traceBlocks) * NSHARD > 0x3fffffffull /* HIT_INDEX_MASK, gi_queues.h */) {
+    p.slots -= p.slots / 8;
+    sizeGrids(p, in);
+  }
+  p.mediaStride = rs.mediumStackSize ? rs.mediumStackSize * MEDIUM_FLOATS + 4u : 0u;
+  // the caller's sizes are taken as given
+  p.pinned = optionSet("pool_slots") || s->optPoolSlots || optionSet("sample_buffer_mb") || s->optSampleBufferMb;
+  // (leave 512 MiB, or half of a tiny remainder)
+  if (!p.pinned) while (planBytes(p, pixels) > (availMb << 20) - std::min<uint64_t>(availMb << 19, 512ull << 20) && shrinkPlan(p, pixels)) sizeGrids(p, in);
+  return p;
+}
+
+// Plans from what is free on the device now and allocates the plan; an allocation that fails with out-of-memory releases the resizable path state and tries
+// the next smaller plan.
+static int allocatePathPlan(GiCScene* s, SceneDevice& D, const GiCRenderSettings& rs, const SceneView& view, const PlanInputs& in, PathPlan& plan)
+{
+  size_t memFree = 0, memTotal = 0; (void)hipMemGetInfo(&memFree, &memTotal);
+  // tests: plan as if this much were free (a planner overtaken by another allocation: the fallback below must recover)
+  if (optionSet("assume_free_mb")) memFree = (size_t)optionValue("assume_free_mb", 0) << 20;
+  if (!D.memTotalMb) D.memTotalMb = std::max<uint64_t>(1, (uint64_t)(memTotal >> 20));
+  plan = planPathMemory(s, rs, view, in, memFree, D.pathStateBytes(), D.memTotalMb);
+  for (int attempt = 0;; attempt++) {
+    int rc = plan.fused ? GI_C_OK : ensurePathState(&D, plan.slots, plan.wideBlocks, plan.traceBlocks);
+    if (rc == GI_C_OK) rc = D.sampleBuf.alloc(in.pixels * plan.batchSamples);
+    if (rc == GI_C_OK) rc = D.accum.alloc(in.pixels);
+    if (rc == GI_C_OK && plan.mediaStride) rc = D.media.alloc(plan.slots * plan.mediaStride);
+    // (a smaller plan fitted: the "out of memory" of the larger ones is not this render's error)
+    if (rc == GI_C_OK) { if (attempt > 0) t_lastError.clear(); return GI_C_OK; }
+    if (rc != GI_C_OUT_OF_MEMORY_INTERNAL) return GI_C_ERROR;
+    // out of memory: drop what this scene holds in the resizable buffers (a half-grown plan must not stand in the way of the smaller one) and try the next
+    // plan
+    D.releasePathState();
+    if (attempt >= 40 || !shrinkPlan(plan, in.pixels)) {
+      setError("giCRender: out of device memory even with the smallest sample buffer and path pool");
+      return GI_C_ERROR;
+    }
+    sizeGrids(plan, in);
+  }
+}
+
+// --- stage timers: HIP events around the stage launches of every `stride`-th iteration (events on every launch cost ~16 % of the
+// frame); per-stage totals are scaled back up by the sampling factor.
+struct StageTimers {
+  enum Kind { RAYGEN = 0, TRACE = 1, SHADE = 2, SHADOW = 3 };
+  struct IterRow { size_t evEnd; uint64_t traced, hits, shadow, ended, cont; };
+  SceneDevice& D;
+  bool on; uint32_t stride;
+  bool iterLog;                  // GATLING_ITER_LOG, with timers on every iteration: one row per iteration (and one sync: for measurements only)
+  bool sampling = false;         // the current iteration's launches are timed
+  size_t ev = 0; std::vector<int> evKind;
+  std::vector<IterRow> iterRows;
+  uint64_t totalIters = 0, sampledIters = 0;
+
+  StageTimers(const GiCScene* s, SceneDevice& d) : D(d), on(s->kernelTimers), stride(std::max(1u, s->kernelTimerStride)),
+      iterLog(on && stride == 1u && getenv("GATLING_ITER_LOG") && atoi(getenv("GATLING_ITER_LOG")) != 0) {}
+  void beginIteration(bool always = false) { sampling = on && (always || (totalIters % stride) == 0u); if (sampling) sampledIters++; }
+  template <typename Fn> void timed(hipStream_t stream, int kind, Fn&& fn)
+  {
+    if (!sampling) { fn(); return; }
+    (void)hipEventRecord(poolEvent(&D, ev), stream); fn(); (void)hipEventRecord(poolEvent(&D, ev + 1), stream);
+    ev += 2; evKind.push_back(kind);
+  }
+  void finish(GiCRenderStats& S) const;
+};
+
+void StageTimers::finish(GiCRenderStats& S) const
+{
+  S.traceMs = S.shadeMs = S.raygenMs = S.shadowMs = 0.0;
+  if (!on) return;
+  auto elapsed = [&](size_t k) { float ms = 0.0f; (void)hipEventElapsedTime(&ms, D.eventPool[2 * k], D.eventPool[2 * k + 1]); return ms; };
+  for (size_t k = 0; k < evKind.size(); k++) {
+    const float ms = elapsed(k);
+    if (evKind[k] == RAYGEN) S.raygenMs += ms; else if (evKind[k] == TRACE) S.traceMs += ms; else if (evKind[k] == SHADE) S.shadeMs += ms;
+    else S.shadowMs += ms;
+  }
+  size_t k = 0;
+  for (size_t r = 0; r < iterRows.size(); r++) { // per iteration: the stage times of its launches and what its queues held
+    const IterRow& row = iterRows[r];
+    double ms4[4] = {0.0, 0.0, 0.0, 0.0};
+    for (; 2 * k < row.evEnd && k < evKind.size(); k++) ms4[evKind[k]] += elapsed(k);
+    fprintf(stderr, "[gatling_gi] iter %3zu: rays %9llu hits %9llu shadow %9llu ended %9llu continuing %9llu | raygen %7.3f trace+route %7.3f shade %7.3f "
+                    "shadow %7.3f ms\n", r,
+            (unsigned long long)row.traced, (unsigned long long)row.hits, (unsigned long long)row.shadow, (unsigned long long)row.ended,
+            (unsigned long long)row.cont, ms4[0], ms4[1], ms4[2], ms4[3]);
+  }
+  // scale the sampled totals to the whole frame (the early-exit poll can leave one raygen-only iteration unsampled)
+  const double scale = sampledIters ? (double)totalIters / (double)sampledIters : 1.0;
+  S.raygenMs *= scale; S.traceMs *= scale; S.shadeMs *= scale; S.shadowMs *= scale;
+}
+
+// --- what the phases of the colour pass share
+struct Schedule {
+  bool twoStreamOk = false;     // batches whose work fits the pool may run their shadow launches on the second stream (scheduleFrame)
+  long twoStreamDelay = 0;      // test hook: 1 | 2 holds the main | the second stream back
+  uint32_t dynRefill = 8u;      // k_trace_dyn refill threshold
+  int32_t shadowOrderNow = -1;  // visiting order of the shadow walks; -1: not chosen yet -- alternate, and count (chooseShadowOrder)
+};
+struct Frame {
+  GiCScene* s; SceneDevice& D; const DevCtx& ctx; const RenderJob& job; const GiCRenderSettings& rs;
+  hipStream_t st;
+  size_t pixels;
+  StageTimers tm;
+  FrameUniforms U{}; SceneView view{};
+  PathPlan plan; PathState ps{}; QueueSet qs{}; Schedule sch;
+  F4* colorOut = nullptr;
+  uint32_t numBatches = 0;
+  uint32_t iters = 0, traceLaunches = 0; // GiCRenderStats::iterations / traceLaunches
+  double tStart = 0.0;
+};
+
+// The PathState of the colour pass: the pool, and what the path-following AOVs bound to this render need beside it.
+static int bindPathAovs(Frame& f, const BoundAovs& A)
+{
+  SceneDevice& D = f.D;
+  f.ps = PathState{D.slots.ptr, D.media.ptr, f.plan.mediaStride, nullptr, 0u, nullptr};
+  if (A.nee && f.rs.nextEventEstimation) { // the reference compiles the NEE AOV write out with NEXT_EVENT_ESTIMATION (rp_main.rgen:397, 431)
+    if (D.neeKey.alloc(f.pixels)) return GI_C_ERROR;
+    HIP_TRY(hipMemsetAsync(D.neeKey.ptr, 0, f.pixels * sizeof(unsigned long long), f.st));
+    f.ps.neeKey = D.neeKey.ptr;
+  }
+  if (A.bounces) f.ps.bouncesAov = reinterpret_cast<F4*>(rbMem(A.bounces, D.slot));
+  if (A.clock) {
+    if (D.pathSegments.alloc(f.pixels)) return GI_C_ERROR;
+    HIP_TRY(hipMemsetAsync(D.pathSegments.ptr, 0, f.pixels * sizeof(uint32_t), f.st));
+    f.ps.pathSegments = D.pathSegments.ptr;
+  }
+  return GI_C_OK;
+}
+
+// --- the schedule: every rule that decides HOW the planned work runs, derived from (plan, view, settings, options).  scheduleFrame: once per render;
+// scheduleBatch: the two bits that depend on a batch's size.
+static Schedule scheduleFrame(Frame& f)
+{
+  const GiCScene* s = f.s; const GiCRenderSettings& rs = f.rs; FrameUniforms& U = f.U;
+  const bool fused = f.plan.fused;
+  // work order of the wavefront pipeline and layout of its per-sample buffer (gi_queues.h work_item); the fused kernels hand work out sample-major
+  if (!fused && optionValue("work_order", WORK_ORDER_PIXEL_MAJOR_DEFAULT ? 1 : 0) != 0) U.flags |= FLAG_PIXEL_MAJOR;
+  // Deferred Slot initialisation (r04): k_raygen hands a camera ray its (rng, work item) beside the ray record instead of writing the path's 64-byte Slot;
+  // the slot is written where the first segment hits (k_route / k_trace) and a camera ray that leaves the scene retires there without ever touching one. The
+  // debug AOVs that follow whole paths read the slot when a sample retires (NEE / Bounces / ClockCycles): renders that bind them keep the eager form.
+  if (!fused && optionValue("defer_slot", 1) != 0 && !f.ps.neeKey && !f.ps.bouncesAov && !f.ps.pathSegments) U.flags |= FLAG_DEFER_SLOT;
+  // Bounds retire (r04n): on the k_trace_dyn path (k_route zeroes the regen counter k_raygen then appends to) a deferred-slot camera ray that cannot reach
+  // the scene's bounds is retired by k_raygen itself (C4: 58 % of the camera rays, C3: ~45 %) -- same sample, same segment count, no ray record, no traversal
+  // step, no routing. Not with a dome image / medium stack (a miss needs the slot), not in counting builds (the root visit of such a ray is part of
+  // nodes-per-ray), not on the two-level layout (bounds of the TLAS root: not kept).
+  if ((U.flags & FLAG_DEFER_SLOT) && !traceBlockSync(f.view) && !f.view.twoLevel && f.view.domeTexture == 0u && rs.mediumStackSize == 0u && !s->countTraversal
+      && s->boundsValid && optionValue("bounds_retire", 1) != 0) {
+    U.flags |= FLAG_BOUNDS_RETIRE;
+    for (int a = 0; a < 3; a++) { U.sceneLo[a] = s->bounds[a]; U.sceneHi[a] = s->bounds[3 + a]; }
+  }
+  Schedule sch;
+  sch.dynRefill = traceDynRefill(s);
+  // (GATLING_OPTIONS=shadow_order=0|1 pins it)
+  sch.shadowOrderNow = optionSet("shadow_order") ? (int32_t)optionValue("shadow_order", -1) : s->shadowOrder.load();
+  // Two streams (the reference's default frame is ONE sample per pixel, renderDelegate.cpp:93-110). In a batch
+  // whose work fits the pool every path starts in iteration 0, so from iteration 1 on k_raygen only FINISHES samples and the closest-hit launch of iteration
+  // i + 1 needs nothing from the shadow launch of iteration i -- which k_raygen(i + 1) (it reads the radiance of paths that ended) and k_shade(i + 1) (it
+  // goes on adding to it: the float order of rp_main.rgen:397-480) do need. Such batches run
+  //     main stream:    Z(i)  [R(0)]  T(i) + route(i)   <wait for Sh(i-1)>   [R(i), i > 0]   S(i)
+  //     second stream:                                  <wait for S(i)>  Sh(i)
+  // so that Sh(i) runs beside T(i + 1): an iteration lasts max(trace, shadow) + raygen + shade instead of their sum. Per-path arithmetic and per-pixel sample
+  // order are untouched (same kernels, same records); what changes is who zeroes which queue counter (gi_queues.h zero_next_counters / zero_closest_counters:
+  // Z = k_zero_closest). Not with a dome image (a miss adds the dome's radiance to the Slot in k_route while the previous bounce's shadow launch may still be
+  // adding to it: two float additions in an order that would depend on timing) or a medium stack. GATLING_OPTIONS=two_stream=0 switches it off;
+  // two_stream_delay=1|2 (tests) holds the main | the second stream back for 0.3 ms per iteration so that the other one runs ahead.
+  // Invariant this rests on: with cutouts T(i + 1) reads Slot::rad.w (the any-hit rng) while Sh(i) may be doing its 16-byte read-modify-write of the same
+  // Slot::rad -- the shadow kernels write rad.w back with the value they read, so the closest-hit launch sees ONE value whatever the timing. A shadow kernel
+  // that ever changes rad.w must store .xyz alone, or scenes with cutouts must leave this rule.
+  sch.twoStreamOk = rs.nextEventEstimation != 0 && rs.mediumStackSize == 0u && f.view.domeTexture == 0u && optionValue("two_stream", 1) != 0
+                    && f.ctx.stream2 != nullptr;
+  sch.twoStreamDelay = optionValue("two_stream_delay", 0);
+  return sch;
+}
+// `rounds`: k_raygen rounds the batch needs to hand out all its work (1: the work fits the pool).  Returns whether the batch runs on two streams.
+static bool scheduleBatch(Frame& f, uint64_t rounds)
+{
+  const GiCScene* s = f.s; FrameUniforms& U = f.U;
+  // A thin batch (its work fits the pool and is small: the delegate's one sample per
+  // pixel and call) launches every kernel of an iteration for a few thousand hits:
+  // a further k_shade launch per iteration costs it more (C4: 13 x ~9 us of a 2.7 ms call) than the BASE variant saves, so its BASE hits are binned with
+  // class 2 (GATLING_OPTIONS=merge_shade_variants=0 | 1: never | always)
+  const long mergeOpt = optionValue("merge_shade_variants", -1);
+  const bool thinBatch = rounds == 1 && U.workTotal <= (8u << 20);
+  if ((mergeOpt < 0 ? thinBatch : mergeOpt != 0) && (s->shadeClassMask & (1u << SHADE_CLASS_OPBR_BASE)) && (s->shadeClassMask & 4u)) {
+    U.flags |= FLAG_MERGE_SHADE_VARIANTS;
+  } else U.flags &= ~FLAG_MERGE_SHADE_VARIANTS;
+  // (the iteration log synchronises the main stream every iteration: it would only ever see one stream's work)
+  const bool two = f.sch.twoStreamOk && rounds == 1 && !f.tm.iterLog;
+  if (two) U.flags |= FLAG_TWO_STREAM; else U.flags &= ~FLAG_TWO_STREAM;
+  return two;
+}
+
+// --- the three kinds of batch.  renderOnDevice has set the batch's uniforms and launched k_init; each ends in the batch's accumulation.
+static void accumulateBatch(Frame& f, uint32_t batch)
+{
+  launchAccumulate(f.st, f.U, f.D.sampleBuf.ptr, f.D.accum.ptr, f.colorOut, batch == 0, batch + 1 == f.numBatches);
+}
+
+// LDS-resident scenes: one launch of the fused persistent kernel k_path runs the batch's paths from camera ray to retirement
+static int runFusedBatch(Frame& f, uint32_t batch)
+{
+  const GiCScene* s = f.s; SceneDevice& D = f.D; const FrameUniforms& U = f.U;
+  // work items are claimed in chunks of consecutive ids; small frames get small chunks so that every resident wave finds work
+  uint32_t chunk = 2048u;
+  const uint64_t waves = (uint64_t)f.ctx.cuCount * 16u;
+  // (a wave's last chunk is the launch's tail: 16 claims per wave keep it at ~6 % of a small frame -- C1 5 895 -> 6 360 Msamples/s; C2 does not care, 256
+  // ... 2048 measure the same)
+  chunk = (uint32_t)std::min<uint64_t>(chunk, std::max<uint64_t>(64u, ((uint64_t)U.workTotal / (waves * 16u)) & ~63ull));
+  f.tm.beginIteration(true); // one launch per batch: timed whatever the stride
+  f.tm.timed(f.st, StageTimers::TRACE, [&] {
+    launchPath(f.st, (uint32_t)f.ctx.cuCount, s->classMask, s->classTextured != 0u, s->countTraversal, chunk, U, f.view, f.ps, D.dCounters.ptr,
+               D.sampleBuf.ptr);
+  });
+  f.iters++; f.tm.totalIters++; f.traceLaunches++;
+  accumulateBatch(f, batch);
+  return GI_C_OK;
+}
+
+// rp_main.rgen:298-304: the bounce loop's exit test comes first, so with max-bounces 0 no ray is traced at all and every sample is
+// black (no emission at the primary hit, no dome / background term); the accumulation still runs (progressive blend, alpha 1)
+static int runZeroBounceBatch(Frame& f, uint32_t batch)
+{
+  HIP_TRY(hipMemsetAsync(f.D.sampleBuf.ptr, 0, f.pixels * f.U.batchSamples * sizeof(F4), f.st));
+  accumulateBatch(f, batch);
+  return GI_C_OK;
+}
+
+// The bounce loop (rp_main.rgen:215, 295) of the wavefront pipeline: every pool slot advances one stage per iteration, until the batch's work is handed out and
+// the pool has drained.  This function owns the second stream: whichever way it returns, no shadow launch of its is still running unjoined -- on success the
+// main stream waits for the last one (an event wait, as ever); on an error it makes the second stream idle first (JoinShadow), so that the caller's error
+// and shrink paths never release buffers under a running kernel.
+static int runWavefrontBatch(Frame& f, uint32_t batch, uint32_t poolNow)
+{
+  GiCScene* s = f.s; SceneDevice& D = f.D; FrameUniforms& U = f.U; StageTimers& tm = f.tm;
+  const GiCRenderSettings& rs = f.rs; const PathPlan& plan = f.plan; const Schedule& sch = f.sch;
+  hipStream_t st = f.st, st2 = f.ctx.stream2;
+  const uint64_t rounds = ((uint64_t)U.workTotal + poolNow - 1) / poolNow; // raygen rounds needed to hand out all work
+  const uint64_t maxIters = (rounds + 2) * (std::max(1u, U.maxBounces) + 1) + 8;
+  const bool two = scheduleBatch(f, rounds);
+  const bool nee = rs.nextEventEstimation != 0;
+  bool shadowInFlight = false; // a shadow launch on st2 that st has not been made to wait for yet
+  struct JoinShadow {
+    hipStream_t st2; const bool& inFlight;
+    ~JoinShadow() { if (inFlight) (void)hipStreamSynchronize(st2); } // (false on every successful return: nothing is added there)
+  } joinOnError{st2, shadowInFlight};
+  auto joinShadow = [&]() -> hipError_t { // the main stream goes on behind the shadow launch in flight
+    if (!shadowInFlight) return hipSuccess;
+    const hipError_t e = hipStreamWaitEvent(st, D.evShadow, 0);
+    if (e == hipSuccess) shadowInFlight = false;
+    return e;
+  };
+  for (uint64_t it = 0; it < maxIters; it++) {
+    const uint32_t par = (uint32_t)(it & 1u);
+    tm.beginIteration();
+    auto raygen = [&] { tm.timed(st, StageTimers::RAYGEN, [&] { launchRaygen(st, plan.wideBlocks, U, f.ps, f.qs, D.dCounters.ptr, par, D.sampleBuf.ptr); }); };
+    if (two) launchZeroClosest(st, D.dCounters.ptr, par);
+    if (!two || it == 0) raygen();
+    // (the last k_raygen of the batch: the test below ends the loop) k_raygen(it) after the shadow launch of it - 1 (two streams, it > 0)
+    else if (rounds == 1 && it == (uint64_t)std::max(1u, U.maxBounces)) { HIP_TRY(joinShadow()); raygen(); }
+    // A batch whose work fits the pool (a low-spp frame: hdGatling renders ONE sample per pixel and call) starts every path in iteration 0, a path traces
+    // at most maxBounces segments, one per iteration (the bounce counter, rp_main.rgen:298-304) -- so k_raygen(maxBounces) has just retired the last
+    // samples and nothing is in flight: no need to find that out two empty iterations later through the poll below (10 launches of ~90 in a spp-1 call).
+    if (rounds == 1 && it == (uint64_t)std::max(1u, U.maxBounces) && rs.mediumStackSize == 0u) { tm.totalIters++; break; }
+    if (it >= rounds) {
+      // All work cannot be handed out earlier. From here on every iteration snapshots the queue sizes behind its k_raygen (asynchronous copy into a pinned
+      // ring) and tests the snapshot of POLL_LAG iterations ago: the wait is for work the GPU finished long ago -- it still holds the iterations in
+      // between, so the stream never runs dry -- and the loop stops at most POLL_LAG empty iterations after the pool drained. (Until r03 the loop
+      // synchronised every 16th iteration: C4 ran 15 empty iterations of 0.2 ms each, `tools/exp_iter_log.py`.)
+      constexpr uint32_t R = SceneDevice::POLL_RING, LAG = SceneDevice::POLL_LAG;
+      constexpr size_t snapshot = (size_t)Q_COUNT * NSHARD;
+      HIP_TRY(hipMemcpyAsync(D.hPoll + (it % R) * snapshot, D.dCounters.ptr, sizeof(PaddedCounter) * snapshot, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipEventRecord(D.pollEvent[it % R], st));
+      if (it >= rounds + LAG) {
+        const uint64_t j = it - LAG;
+        HIP_TRY(hipEventSynchronize(D.pollEvent[j % R]));
+        const PaddedCounter* snap = D.hPoll + (j % R) * snapshot + (size_t)(Q_TRACE_A + (uint32_t)(j & 1u)) * NSHARD;
+        // (FLAG_BOUNDS_RETIRE: a k_raygen whose camera rays all miss the scene's bounds queues no ray either, but hands its slots on -- REGEN[(j&1)^1],
+        // zero at this point otherwise -- and work is left)
+        const PaddedCounter* again = D.hPoll + (j % R) * snapshot + (size_t)(Q_REGEN_A + (uint32_t)((j & 1u) ^ 1u)) * NSHARD;
+        uint32_t pending = 0; for (uint32_t k = 0; k < NSHARD; k++) pending += snap[k].v + again[k].v;
+        if (pending == 0) { tm.totalIters++; break; } // k_raygen(j) consumed the regen queue and produced no rays: the pool had drained
       }
-      wideBlocks = (uint32_t)std::min<size_t>((slots + 255) / 256, (size_t)ctx.cuCount * 8u);
-      traceBlocks = (uint32_t)std::min<size_t>((slots + 255) / 256, (size_t)ctx.cuCount * perCu);
-    };
-    sizeGrids();
-    // HIT-queue entries (and giCTraceRays) hold a TRACE-queue RECORD index in 30 bits (HIT_INDEX_MASK); records run up to shardCapacity * NSHARD, which exceeds
-    // the slot count by the shards' slack -- a pinned pool near 2^30 would push indices past the mask and k_shade would gather the wrong record
-    while (!fused && (uint64_t)shardCapacity(slots, wideBlocks, traceBlocks) * NSHARD > 0x3fffffffull /* HIT_INDEX_MASK, gi_queues.h */) { slots -= slots / 8;
-        sizeGrids(); }
-    const uint32_t mediaStride = rs.mediumStackSize ? rs.mediumStackSize * MEDIUM_FLOATS + 4u : 0u;
-    // what a plan costs: the slot pool with its queues (per slot: the Slot, the medium stack, and a share of every queue's records) and the sample buffer
-    auto planBytes = [&](size_t nSlots, uint64_t nBatch) -> uint64_t {
-      const uint64_t cap = shardCapacity(nSlots, wideBlocks, traceBlocks);
-      const uint64_t perQueueEntry = 4ull * Q_COUNT + 32ull * (2 + 1) + 16ull + 8ull * 2;
-      return (fused ? 0ull : (uint64_t)nSlots * (sizeof(Slot) + 4ull * mediaStride) + cap * NSHARD * perQueueEntry) + (uint64_t)pixels * nBatch * 16ull
-             + (uint64_t)pixels * 16ull;
-    };
-    // the caller's sizes are taken as given
-    const bool pinnedPlan = optionSet("pool_slots") || s->optPoolSlots || optionSet("sample_buffer_mb") || s->optSampleBufferMb;
-    auto shrink = [&]() -> bool { // the next smaller plan: halve the sample buffer down to 64 MiB (more batches), then the pool down to 64 Ki slots
-      if (batchSamples > 1 && (uint64_t)pixels * batchSamples * 16ull > (64ull << 20)) { batchSamples = std::max<uint64_t>(1, batchSamples / 2);
-          if (!fused) slots = (size_t)std::min<uint64_t>(slots, (uint64_t)pixels * batchSamples); return true; }
-      if (!fused && slots > (64u << 10)) { slots /= 2; return true; }
-      return false;
-    };
-    // (leave 512 MiB, or half of a tiny remainder)
-    if (!pinnedPlan) while (planBytes(slots, batchSamples) > (availMb << 20) - std::min<uint64_t>(availMb << 19, 512ull << 20) && shrink()) sizeGrids();
-    for (int attempt = 0;; attempt++) {
-      int rc = fused ? GI_C_OK : ensurePathState(&D, slots, wideBlocks, traceBlocks);
-      if (rc == GI_C_OK) rc = D.sampleBuf.alloc(pixels * batchSamples);
-      if (rc == GI_C_OK) rc = D.accum.alloc(pixels);
-      if (rc == GI_C_OK && mediaStride) rc = D.media.alloc(slots * mediaStride);
-      // (a smaller plan fitted: the "out of memory" of the larger ones is not this render's error)
-      if (rc == GI_C_OK) { if (attempt > 0) t_lastError.clear(); break; }
-      if (rc != GI_C_OUT_OF_MEMORY_INTERNAL) return GI_C_ERROR;
-      // out of memory: drop what this scene holds in the resizable buffers (a half-grown plan must not stand in the way of the smaller one) and try the next
-      // plan
-      D.sampleBuf.release(); D.slots.release(); D.media.release();
-      for (uint32_t q = 0; q < Q_COUNT; q++) { D.qSlot[q].release(); D.qA[q].release(); D.qB[q].release(); D.qC[q].release(); }
-      D.qFresh[0].release(); D.qFresh[1].release(); D.queueCap = 0;
-      if (attempt >= 40 || !shrink()) { setError("giCRender: out of device memory even with the smallest sample buffer and path pool"); return GI_C_ERROR; }
-      sizeGrids();
     }
-    const uint32_t numBatches = (uint32_t)((rs.spp + batchSamples - 1) / batchSamples);
-    D.stats.poolSlots = fused ? 0u : (uint32_t)slots; D.stats.batches = numBatches;
-    PathState ps{D.slots.ptr, D.media.ptr, mediaStride, nullptr, 0u, nullptr};
-    if (neeRb && rs.nextEventEstimation) { // the reference compiles the NEE AOV write out with NEXT_EVENT_ESTIMATION (rp_main.rgen:397, 431)
-      if (D.neeKey.alloc(pixels)) return GI_C_ERROR;
-      HIP_TRY(hipMemsetAsync(D.neeKey.ptr, 0, pixels * sizeof(unsigned long long), st));
-      ps.neeKey = D.neeKey.ptr;
+    if (two && sch.twoStreamDelay == 1) launchSpin(st, 300000ull);
+    tm.timed(st, StageTimers::TRACE, [&] {
+      launchTrace(st, plan.traceBlocks, false, s->countTraversal, f.view, f.ps, f.qs, D.dCounters.ptr, Q_TRACE_A + par, Q_REGEN_A + (par ^ 1u), sch.dynRefill,
+                  plan.wideBlocks, U, D.sampleBuf.ptr);
+    });
+    f.traceLaunches++;
+    if (two && it > 0) { HIP_TRY(joinShadow()); raygen(); } // k_raygen(it) runs behind this iteration's closest-hit launch, after the shadow launch of it - 1
+    // one launch per shade class in use (scattering events inside a medium are routed to class 2, k_route: it is launched whenever a medium stack exists
+    // and OpenPBR does)
+    uint32_t shadeMask = s->shadeClassMask | ((rs.mediumStackSize != 0u && (s->shadeClassMask & (1u << SHADE_CLASS_OPBR_BASE))) ? 4u : 0u);
+    // BASE hits sit in class 2's queue
+    if (U.flags & FLAG_MERGE_SHADE_VARIANTS) shadeMask = (shadeMask & ~(1u << SHADE_CLASS_OPBR_BASE)) | ((shadeMask >> SHADE_CLASS_OPBR_BASE) & 1u) << 2;
+    for (uint32_t klass = 0; klass < MAT_CLASS_COUNT; klass++) {
+      if (!(shadeMask & (1u << klass))) continue;
+      tm.timed(st, StageTimers::SHADE, [&] {
+        launchShade(st, plan.wideBlocks, klass, (s->shadeClassTextured & (1u << klass)) != 0u, rs.mediumStackSize != 0u, U, f.view, f.ps, f.qs, D.dCounters.ptr,
+                    par);
+      });
     }
-    if (bouncesRb) ps.bouncesAov = reinterpret_cast<F4*>(rbMem(bouncesRb, D.slot));
-    if (clockRb) {
-      if (D.pathSegments.alloc(pixels)) return GI_C_ERROR;
-      HIP_TRY(hipMemsetAsync(D.pathSegments.ptr, 0, pixels * sizeof(uint32_t), st));
-      ps.pathSegments = D.pathSegments.ptr;
+    if (nee) {
+      // not chosen yet: alternate, and count (chooseShadowOrder)
+      const int32_t order = sch.shadowOrderNow >= 0 ? sch.shadowOrderNow : (int32_t)(tm.totalIters & 1u);
+      hipStream_t on = st;
+      if (two) { // the shadow launch moves to the second stream, behind this iteration's k_shade
+        HIP_TRY(hipEventRecord(D.evShade, st)); HIP_TRY(hipStreamWaitEvent(st2, D.evShade, 0));
+        if (sch.twoStreamDelay == 2) launchSpin(st2, 300000ull);
+        on = st2;
+      }
+      tm.timed(on, StageTimers::SHADOW, [&] {
+        launchTrace(on, plan.traceBlocks, true, s->countTraversal, f.view, f.ps, f.qs, D.dCounters.ptr, Q_SHADOW, Q_SHADOW,
+                    sch.dynRefill | (order ? TRACE_DYN_SLOT_ORDER : 0u), plan.wideBlocks, U, D.sampleBuf.ptr);
+      });
+      if (two) { shadowInFlight = true; HIP_TRY(hipEventRecord(D.evShadow, st2)); }
     }
-    view.mediumStackSize = rs.mediumStackSize;
-    // Deferred Slot initialisation (r04): k_raygen hands a camera ray its (rng, work item) beside the ray record instead of writing the path's 64-byte Slot;
-    // the slot is written where the first segment hits (k_route / k_trace) and a camera ray that leaves the scene retires there without ever touching one. The
-    // debug AOVs that follow whole paths read the slot when a sample retires (NEE / Bounces / ClockCycles): renders that bind them keep the eager form.
-    if (!fused && optionValue("defer_slot", 1) != 0 && !ps.neeKey && !ps.bouncesAov && !ps.pathSegments) U.flags |= FLAG_DEFER_SLOT;
-    QueueSet qs = makeQueueSet(&D);
-    F4* colorOut = reinterpret_cast<F4*>(rbMem(colorRb, D.slot));
-    const bool nee = rs.nextEventEstimation != 0;
-    const uint32_t dynRefill = traceDynRefill(s);
-    // (GATLING_OPTIONS=shadow_order=0|1 pins it)
-    const int32_t shadowOrderNow = optionSet("shadow_order") ? (int32_t)optionValue("shadow_order", -1) : s->shadowOrder.load();
-    // Bounds retire (r04n): on the k_trace_dyn path (k_route zeroes the regen counter k_raygen then appends to) a deferred-slot camera ray that cannot reach
-    // the scene's bounds is retired by k_raygen itself (C4: 58 % of the camera rays, C3: ~45 %) -- same sample, same segment count, no ray record, no traversal
-    // step, no routing. Not with a dome image / medium stack (a miss needs the slot), not in counting builds (the root visit of such a ray is part of
-    // nodes-per-ray), not on the two-level layout (bounds of the TLAS root: not kept).
-    if ((U.flags & FLAG_DEFER_SLOT) && !traceBlockSync(view) && !view.twoLevel && view.domeTexture == 0u && rs.mediumStackSize == 0u && !s->countTraversal
-        && s->boundsValid && optionValue("bounds_retire", 1) != 0) {
-      U.flags |= FLAG_BOUNDS_RETIRE;
-      for (int a = 0; a < 3; a++) { U.sceneLo[a] = s->bounds[a]; U.sceneHi[a] = s->bounds[3 + a]; }
+    // (GATLING_ITER_LOG, with kernel timers on every iteration: what each iteration's queues held -- one sync per iteration, for measurements only)
+    if (tm.iterLog) {
+      HIP_TRY(hipMemcpyAsync(D.hCounters, D.dCounters.ptr, sizeof(PaddedCounter) * Q_COUNT * NSHARD, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      auto total = [&](uint32_t q) { uint64_t n = 0; for (uint32_t k = 0; k < NSHARD; k++) n += D.hCounters->count[q][k].v; return n; };
+      uint64_t hits = 0; for (uint32_t c = 0; c < MAT_CLASS_COUNT; c++) hits += total(Q_HIT + c);
+      tm.iterRows.push_back({tm.ev, total(Q_TRACE_A + par), hits, total(Q_SHADOW), total(Q_REGEN_A + (par ^ 1u)), total(Q_TRACE_A + (par ^ 1u))});
     }
+    f.iters++; tm.totalIters++;
+  }
+  HIP_TRY(joinShadow()); // (a batch that ended through the poll: its last shadow launches were empty)
+  accumulateBatch(f, batch);
+  return GI_C_OK;
+}
 
-    // --- the bounce loop (rp_main.rgen:215, 295): every pool slot advances one stage per iteration
+// --- epilogue: the path-following AOVs are finished on the host (NEE resolve on the device, ClockCycles heat map, Bounces NaN fill) and their rows read back
+static int finishPathAovs(Frame& f, const BoundAovs& A)
+{
+  SceneDevice& D = f.D; const RenderJob& job = f.job; hipStream_t st = f.st;
+  const size_t pixels = f.pixels; const uint32_t width = job.width, rowBegin = job.rowBegin, rowStride = job.rowStride;
+  if (A.nee && f.ps.neeKey) launchResolveNee(st, f.U, D.neeKey.ptr, reinterpret_cast<F4*>(rbMem(A.nee, D.slot)), (uint32_t)pixels);
+  if (GiCRenderBuffer* clockRb = A.clock) {
+    // ClockCycles: per-pixel cost -> heat map normalised to the frame maximum, on the host like _EncodeRenderBufferAsHeatmap (Gi.cpp:327-343)
+    std::vector<uint32_t> counts(pixels);
+    HIP_TRY(hipMemcpyAsync(counts.data(), D.pathSegments.ptr, pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    tStart = nowMs();
-    // HIP events around the stage launches of every `timerStride`-th iteration (events on every launch cost ~16 % of the
-    // frame); per-stage totals are scaled back up by the sampling factor.
-    const uint32_t timerStride = std::max(1u, s->kernelTimerStride);
-    uint64_t curIter = 0;
-    auto timedOn = [&](hipStream_t on, int kind, auto&& fn) {
-      if (timers && (curIter % timerStride) == 0u) { (void)hipEventRecord(poolEvent(&D, ev), on); fn(); (void)hipEventRecord(poolEvent(&D, ev + 1), on);
-          ev += 2; evKind.push_back(kind); }
-      else fn();
-    };
-    auto timed = [&](int kind, auto&& fn) { timedOn(st, kind, fn); };
-    // Two streams (the reference's default frame is ONE sample per pixel, renderDelegate.cpp:93-110). In a batch
-    // whose work fits the pool every path starts in iteration 0, so from iteration 1 on k_raygen only FINISHES samples and the closest-hit launch of iteration
-    // i + 1 needs nothing from the shadow launch of iteration i -- which k_raygen(i + 1) (it reads the radiance of paths that ended) and k_shade(i + 1) (it
-    // goes on adding to it: the float order of rp_main.rgen:397-480) do need. Such batches run
-    //     main stream:    Z(i)  [R(0)]  T(i) + route(i)   <wait for Sh(i-1)>   [R(i), i > 0]   S(i)
-    //     second stream:                                  <wait for S(i)>  Sh(i)
-    // so that Sh(i) runs beside T(i + 1): an iteration lasts max(trace, shadow) + raygen + shade instead of their sum. Per-path arithmetic and per-pixel sample
-    // order are untouched (same kernels, same records); what changes is who zeroes which queue counter (gi_queues.h zero_next_counters / zero_closest_counters:
-    // Z = k_zero_closest). Not with a dome image (a miss adds the dome's radiance to the Slot in k_route while the previous bounce's shadow launch may still be
-    // adding to it: two float additions in an order that would depend on timing) or a medium stack. GATLING_OPTIONS=two_stream=0 switches it off;
-    // two_stream_delay=1|2 (tests) holds the main | the second stream back for 0.3 ms per iteration so that the other one runs ahead.
-    const bool twoStreamOk = nee && rs.mediumStackSize == 0u && view.domeTexture == 0u && optionValue("two_stream", 1) != 0 && ctx.stream2 != nullptr;
-    const long twoStreamDelay = optionValue("two_stream_delay", 0);
-    hipStream_t st2 = ctx.stream2;
-    if (twoStreamOk && !D.evShade) { HIP_TRY(hipEventCreateWithFlags(&D.evShade, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&D.evShadow, hipEventDisableTiming)); }
-    const bool iterLog = timers && timerStride == 1u && getenv("GATLING_ITER_LOG") && atoi(getenv("GATLING_ITER_LOG")) != 0;
-    for (uint32_t batch = 0; batch < numBatches; batch++) {
+    float maxValue = 0.0f;
+    for (uint32_t c : counts) maxValue = std::max(maxValue, (float)c);
+    float* img = reinterpret_cast<float*>(clockRb->hostMem);
+    for (size_t p = 0; p < pixels; p++) {
+      const size_t y = rowBegin + (p / width) * rowStride, x = p % width;
+      float* o = img + (y * width + x) * 4;
+      if (maxValue > 0.0f) {
+        const int idx = std::min((int)(((float)counts[p] / maxValue) * 255.0), 255);
+        turboColormap((float)idx / 255.0f, o);
+        o[3] = 255.0f;
+      } else { o[0] = (float)counts[p]; o[1] = 0.0f; o[2] = 0.0f; }
+    }
+    HIP_TRY(hipMemcpyAsync(rbMem(clockRb, D.slot), clockRb->hostMem, clockRb->size, hipMemcpyHostToDevice, st));
+  }
+  if (A.bounces && f.U.maxBounces == 0u) { // rp_main.rgen:483-486 evaluates inferno(0 / 0) = NaN for every pixel of the tile
+    float* img = reinterpret_cast<float*>(A.bounces->hostMem);
+    for (size_t p = 0; p < pixels; p++) { float* o = img + ((rowBegin + (p / width) * rowStride) * width + p % width) * 4; o[0] = o[1] = o[2] = NAN; }
+    HIP_TRY(hipMemcpyAsync(rbMem(A.bounces, D.slot), A.bounces->hostMem, A.bounces->size, hipMemcpyHostToDevice, st));
+  }
+  for (GiCRenderBuffer* rb : {A.nee, A.bounces}) {
+    if (!rb || rb->deviceOnly || !job.readback) continue;
+    HIP_TRY(copyTileRows(rb, rb->stride, job, D.slot, st));
+  }
+  return GI_C_OK;
+}
+
+// the non-colour AOV pass (k_aov) + read-back of the rows of this tile
+static int runAovPass(Frame& f, const BoundAovs& A)
+{
+  launchAov(f.st, f.U, f.view, A.targets);
+  if (hipGetLastError() != hipSuccess) { setError("k_aov launch failed"); return GI_C_ERROR; }
+  for (GiCRenderBuffer* rb : A.produced) {
+    if (rb->deviceOnly || !f.job.readback) continue;
+    HIP_TRY(copyTileRows(rb, rb->stride, f.job, f.D.slot, f.st));
+  }
+  return GI_C_OK;
+}
+
+// the counters and the colour rows come back, and the render ends: everything this device was given has run
+static int readBackAndWait(Frame& f, GiCRenderBuffer* colorRb)
+{
+  SceneDevice& D = f.D;
+  HIP_TRY(hipMemcpyAsync(D.hCounters, D.dCounters.ptr, sizeof(Counters), hipMemcpyDeviceToHost, f.st));
+  if (colorRb && !colorRb->deviceOnly && f.job.readback) HIP_TRY(copyTileRows(colorRb, 16, f.job, D.slot, f.st));
+  HIP_TRY(hipStreamSynchronize(f.st));
+  HIP_TRY(hipGetLastError());
+  return GI_C_OK;
+}
+
+static void fillStats(const Frame& f, double tEnd)
+{
+  GiCRenderStats& S = f.D.stats; const Counters& c = *f.D.hCounters;
+  S.renderMs = tEnd - f.tStart; S.samples = (uint64_t)f.pixels * f.rs.spp; S.iterations = f.iters; S.traceLaunches = f.traceLaunches;
+  S.fusedPath = f.plan.fused ? 1u : 0u;
+  S.segments = c.segments; S.shadowRays = c.shadowRays; S.nodesVisited = c.nodesVisited; S.trisTested = c.trisTested;
+  S.shadowNodesVisited = c.shadowNodesVisited; S.shadowTrisTested = c.shadowTrisTested;
+}
+
+// choose the shadow walks' order once both have been measured on enough rays of this scene: fewer node visits per ray wins
+static void chooseShadowOrder(GiCScene* s, const Counters& c)
+{
+  if (s->shadowOrder.load() >= 0) return;
+  for (int m = 0; m < 2; m++) {
+    s->shadowOrderRays[m] += c.shadowOrderRays[m];
+    for (int k = 0; k < 16; k++) s->shadowOrderSteps[m] += c.shadowOrderSteps[m][k].v;
+  }
+  constexpr uint64_t ENOUGH = 1u << 16;
+  if (s->shadowOrderRays[0] < ENOUGH || s->shadowOrderRays[1] < ENOUGH) return;
+  s->shadowOrder = (double)s->shadowOrderSteps[1] * (double)s->shadowOrderRays[0] < (double)s->shadowOrderSteps[0] * (double)s->shadowOrderRays[1] ? 1 : 0;
+  if (getenv("GATLING_BUILD_TIMING")) {
+    fprintf(stderr, "[gatling_gi] shadow walks: near-to-far %.3f node visits per ray (%llu rays), slot order %.3f (%llu rays) -> %s\n",
+            (double)s->shadowOrderSteps[0] / (double)s->shadowOrderRays[0], (unsigned long long)s->shadowOrderRays[0],
+            (double)s->shadowOrderSteps[1] / (double)s->shadowOrderRays[1], (unsigned long long)s->shadowOrderRays[1],
+            s->shadowOrder.load() ? "slot order" : "near-to-far");
+  }
+}
+
+// counting builds with GATLING_OPTIONS=phase_stats=1: k_path's phase split, k_trace_dyn's lane accounting
+static void printPhaseStats(const GiCScene* s, const Counters& c)
+{
+  if (!s->countTraversal || !optionValue("phase_stats", 0)) return;
+  if (c.phaseTrips) { // k_path's phase split
+    const double tot = (double)(c.phaseCycles[0] + c.phaseCycles[1] + c.phaseCycles[2] + c.phaseCycles[3]);
+    static const char* names[4] = {"regen", "trace", "shade", "shadow+finish"};
+    for (int k = 0; k < 4; k++) {
+      fprintf(stderr, "[gatling_gi] k_path phase %-14s %5.1f %% of wave cycles, %5.1f of 64 lanes busy per trip\n", names[k],
+              100.0 * (double)c.phaseCycles[k] / tot, (double)c.phaseLanes[k] / (double)c.phaseTrips);
+    }
+    fprintf(stderr, "[gatling_gi] k_path trips %llu, %.0f cycles per trip and wave\n", (unsigned long long)c.phaseTrips, tot / (double)c.phaseTrips);
+  }
+  if (c.dynStats[0]) { // k_trace_dyn's lane accounting (closest-hit launches)
+    const unsigned long long* d = c.dynStats; const double st = (double)d[0];
+    fprintf(stderr, "[gatling_gi] k_trace_dyn<closest> %llu wave steps: per step %.1f lanes hold a ray, %.1f run the node test, %.1f wait for the triangle "
+                    "ring; %.3f batches per step of %.1f pairs; "
+                    "a refill every %.2f steps, %.1f lanes each\n",
+            d[0], (double)d[1] / st, (double)d[2] / st, (double)d[3] / st, (double)d[4] / st, d[4] ? (double)d[5] / (double)d[4] : 0.0,
+            d[6] ? st / (double)d[6] : 0.0, d[6] ? (double)d[7] / (double)d[6] : 0.0);
+  }
+}
+
+static int renderOnDevice(GiCScene* s, SceneDevice& D, const RenderJob& job)
+{
+  const DevCtx& ctx = g_ctx.devs[D.slot];
+  HIP_TRY(hipSetDevice(ctx.device));
+  hipStream_t st = ctx.stream;
+  const GiCRenderSettings& rs = job.params->renderSettings;
+  D.stats.bvhBuildMs = s->stats.bvhBuildMs; D.stats.uploadMs = s->stats.uploadMs;
+
+  BoundAovs aov;
+  if (bindAovs(D, job, st, aov) != GI_C_OK) return GI_C_ERROR;
+  if (!aov.color && aov.produced.empty()) { HIP_TRY(hipStreamSynchronize(st)); return GI_C_OK; } // (nothing this library produces is bound)
+  const size_t pixels = (size_t)job.tileRows * job.width;
+  if (pixels == 0) return GI_C_OK;
+
+  Frame f{s, D, ctx, job, rs, st, pixels, StageTimers(s, D)};
+  f.U = makeUniforms(*job.params, job, s);
+  f.tStart = nowMs();
+  f.view = makeFrameView(s, D, *job.params, f.U);
+  if (ensurePathState(&D, 1, 1, 1) != GI_C_OK) return GI_C_ERROR; // counters / pinned mirror exist even for AOV-only renders
+  if (aov.color) {
+    f.view.mediumStackSize = rs.mediumStackSize;
+    const PlanInputs in{pixels, (uint32_t)ctx.cuCount, traceBlocksPerCu(f.view)};
+    if (allocatePathPlan(s, D, rs, f.view, in, f.plan) != GI_C_OK) return GI_C_ERROR;
+    const uint64_t batchSamples = f.plan.batchSamples;
+    f.numBatches = (uint32_t)((rs.spp + batchSamples - 1) / batchSamples);
+    D.stats.poolSlots = f.plan.fused ? 0u : (uint32_t)f.plan.slots; D.stats.batches = f.numBatches;
+    if (bindPathAovs(f, aov) != GI_C_OK) return GI_C_ERROR;
+    f.sch = scheduleFrame(f);
+    f.qs = makeQueueSet(&D);
+    f.colorOut = reinterpret_cast<F4*>(rbMem(aov.color, D.slot));
+
+    HIP_TRY(hipStreamSynchronize(st));
+    f.tStart = nowMs();
+    if (f.sch.twoStreamOk && !D.evShade) {
+      HIP_TRY(hipEventCreateWithFlags(&D.evShade, hipEventDisableTiming));
+      HIP_TRY(hipEventCreateWithFlags(&D.evShadow, hipEventDisableTiming));
+    }
+    FrameUniforms& U = f.U;
+    for (uint32_t batch = 0; batch < f.numBatches; batch++) {
       U.batchFirstSample = (uint32_t)(batch * batchSamples);
       U.batchSamples = (uint32_t)std::min<uint64_t>(batchSamples, rs.spp - (uint64_t)batch * batchSamples);
       U.workTotal = (uint32_t)(pixels * U.batchSamples);
-      ps.neeSampleBase = U.batchFirstSample;
-      const uint32_t poolNow = (uint32_t)std::min<uint64_t>(slots, U.workTotal);
+      f.ps.neeSampleBase = U.batchFirstSample;
+      const uint32_t poolNow = (uint32_t)std::min<uint64_t>(f.plan.slots, U.workTotal);
       U.poolSlots = poolNow;
-      launchInit(st, ps, qs, D.dCounters.ptr, fused ? 0u : poolNow, batch == 0);
-      if (fused && U.maxBounces != 0u) {
-        // work items are claimed in chunks of consecutive ids; small frames get small chunks so that every resident wave finds work
-        uint32_t chunk = 2048u;
-        const uint64_t waves = (uint64_t)ctx.cuCount * 16u;
-        // (a wave's last chunk is the launch's tail: 16 claims per wave keep it at ~6 % of a small frame -- C1 5 895 -> 6 360 Msamples/s; C2 does not care, 256
-        // ... 2048 measure the same)
-        chunk = (uint32_t)std::min<uint64_t>(chunk, std::max<uint64_t>(64u, ((uint64_t)U.workTotal / (waves * 16u)) & ~63ull));
-        curIter = totalIters; if (timers) sampledIters++;
-        if (timers) { (void)hipEventRecord(poolEvent(&D, ev), st); }
-        launchPath(st, (uint32_t)ctx.cuCount, s->classMask, s->classTextured != 0u, s->countTraversal, chunk, U, view, ps, D.dCounters.ptr, D.sampleBuf.ptr);
-        if (timers) { (void)hipEventRecord(poolEvent(&D, ev + 1), st); ev += 2; evKind.push_back(1); }
-        iters++; totalIters++; traceLaunches++;
-        launchAccumulate(st, U, D.sampleBuf.ptr, D.accum.ptr, colorOut, batch == 0, batch + 1 == numBatches);
-        continue;
-      }
-      if (U.maxBounces == 0u) {
-        // rp_main.rgen:298-304: the bounce loop's exit test comes first, so with max-bounces 0 no ray is traced at all and every sample is
-        // black (no emission at the primary hit, no dome / background term); the accumulation still runs (progressive blend, alpha 1)
-        HIP_TRY(hipMemsetAsync(D.sampleBuf.ptr, 0, pixels * U.batchSamples * sizeof(F4), st));
-        launchAccumulate(st, U, D.sampleBuf.ptr, D.accum.ptr, colorOut, batch == 0, batch + 1 == numBatches);
-        continue;
-      }
-      const uint64_t rounds = ((uint64_t)U.workTotal + poolNow - 1) / poolNow; // raygen rounds needed to hand out all work
-      const uint64_t maxIters = (rounds + 2) * (std::max(1u, U.maxBounces) + 1) + 8;
-      // A thin batch (its work fits the pool and is small: the delegate's one sample per
-      // pixel and call) launches every kernel of an iteration for a few thousand hits:
-      // a further k_shade launch per iteration costs it more (C4: 13 x ~9 us of a 2.7 ms call) than the BASE variant saves, so its BASE hits are binned with
-      // class 2 (GATLING_OPTIONS=merge_shade_variants=0 | 1: never | always)
-      const long mergeOpt = optionValue("merge_shade_variants", -1);
-      const bool thinBatch = rounds == 1 && U.workTotal <= (8u << 20);
-      if ((mergeOpt < 0 ? thinBatch : mergeOpt != 0) && (s->shadeClassMask & (1u << SHADE_CLASS_OPBR_BASE))
-          && (s->shadeClassMask & 4u)) U.flags |= FLAG_MERGE_SHADE_VARIANTS;
-      else U.flags &= ~FLAG_MERGE_SHADE_VARIANTS;
-      const bool two = twoStreamOk && rounds == 1 && !iterLog;
-      if (two) U.flags |= FLAG_TWO_STREAM; else U.flags &= ~FLAG_TWO_STREAM;
-      bool shadowInFlight = false;
-      for (uint64_t it = 0; it < maxIters; it++) {
-        const uint32_t par = (uint32_t)(it & 1u);
-        curIter = totalIters; if (timers && (totalIters % timerStride) == 0u) sampledIters++;
-        auto raygen = [&] { timed(0, [&] { launchRaygen(st, wideBlocks, U, ps, qs, D.dCounters.ptr, par, D.sampleBuf.ptr); }); };
-        // k_raygen(it) after the shadow launch of it - 1 (two streams, it > 0: it runs behind this iteration's closest-hit launch)
-        auto raygenBehindShadow = [&] { if (shadowInFlight) { (void)hipStreamWaitEvent(st, D.evShadow, 0); shadowInFlight = false; } raygen(); };
-        if (two) launchZeroClosest(st, D.dCounters.ptr, par);
-        if (!two || it == 0) raygen();
-        // (the last k_raygen of the batch: the test below ends the loop)
-        else if (rounds == 1 && it == (uint64_t)std::max(1u, U.maxBounces)) raygenBehindShadow();
-        // A batch whose work fits the pool (a low-spp frame: hdGatling renders ONE sample per pixel and call) starts every path in iteration 0, a path traces
-        // at most maxBounces segments, one per iteration (the bounce counter, rp_main.rgen:298-304) -- so k_raygen(maxBounces) has just retired the last
-        // samples and nothing is in flight: no need to find that out two empty iterations later through the poll below (10 launches of ~90 in a spp-1 call).
-        if (rounds == 1 && it == (uint64_t)std::max(1u, U.maxBounces) && rs.mediumStackSize == 0u) { totalIters++; break; }
-        if (it >= rounds) {
-          // All work cannot be handed out earlier. From here on every iteration snapshots the queue sizes behind its k_raygen (asynchronous copy into a pinned
-          // ring) and tests the snapshot of POLL_LAG iterations ago: the wait is for work the GPU finished long ago -- it still holds the iterations in
-          // between, so the stream never runs dry -- and the loop stops at most POLL_LAG empty iterations after the pool drained. (Until r03 the loop
-          // synchronised every 16th iteration: C4 ran 15 empty iterations of 0.2 ms each, `tools/exp_iter_log.py`.)
-          constexpr uint32_t R = SceneDevice::POLL_RING, LAG = SceneDevice::POLL_LAG;
-          constexpr size_t snapshot = (size_t)Q_COUNT * NSHARD;
-          HIP_TRY(hipMemcpyAsync(D.hPoll + (it % R) * snapshot, D.dCounters.ptr, sizeof(PaddedCounter) * snapshot, hipMemcpyDeviceToHost, st));
-          HIP_TRY(hipEventRecord(D.pollEvent[it % R], st));
-          if (it >= rounds + LAG) {
-            const uint64_t j = it - LAG;
-            HIP_TRY(hipEventSynchronize(D.pollEvent[j % R]));
-            const PaddedCounter* snap = D.hPoll + (j % R) * snapshot + (size_t)(Q_TRACE_A + (uint32_t)(j & 1u)) * NSHARD;
-            // (FLAG_BOUNDS_RETIRE: a k_raygen whose camera rays all miss the scene's bounds queues no ray either, but hands its slots on -- REGEN[(j&1)^1],
-            // zero at this point otherwise -- and work is left)
-            const PaddedCounter* again = D.hPoll + (j % R) * snapshot + (size_t)(Q_REGEN_A + (uint32_t)((j & 1u) ^ 1u)) * NSHARD;
-            uint32_t pending = 0; for (uint32_t k = 0; k < NSHARD; k++) pending += snap[k].v + again[k].v;
-            if (pending == 0) { totalIters++; break; } // k_raygen(j) consumed the regen queue and produced no rays: the pool had drained
-          }
-        }
-        if (two && twoStreamDelay == 1) launchSpin(st, 300000ull);
-        timed(1,
-            [&] { launchTrace(st, traceBlocks, false, s->countTraversal, view, ps, qs, D.dCounters.ptr, Q_TRACE_A + par, Q_REGEN_A + (par ^ 1u), dynRefill,
-            wideBlocks, U, D.sampleBuf.ptr); });
-        traceLaunches++;
-        if (two && it > 0) raygenBehindShadow();
-        // one launch per shade class in use (scattering events inside a medium are routed to class 2, k_route: it is launched whenever a medium stack exists
-        // and OpenPBR does)
-        uint32_t shadeMask = s->shadeClassMask | ((rs.mediumStackSize != 0u && (s->shadeClassMask & (1u << SHADE_CLASS_OPBR_BASE))) ? 4u : 0u);
-        // BASE hits sit in class 2's queue
-        if (U.flags & FLAG_MERGE_SHADE_VARIANTS) shadeMask = (shadeMask & ~(1u << SHADE_CLASS_OPBR_BASE)) | ((shadeMask >> SHADE_CLASS_OPBR_BASE) & 1u) << 2;
-        for (uint32_t klass = 0; klass < MAT_CLASS_COUNT; klass++)
-          if (shadeMask & (1u << klass)) timed(2,
-              [&] { launchShade(st, wideBlocks, klass, (s->shadeClassTextured & (1u << klass)) != 0u, rs.mediumStackSize != 0u, U, view, ps, qs,
-              D.dCounters.ptr, par); });
-        if (nee) {
-          // not chosen yet: alternate, and count (below)
-          const int32_t order = shadowOrderNow >= 0 ? shadowOrderNow : (int32_t)(totalIters & 1u);
-          hipStream_t on = st;
-          if (two) { // the shadow launch moves to the second stream, behind this iteration's k_shade
-            HIP_TRY(hipEventRecord(D.evShade, st)); HIP_TRY(hipStreamWaitEvent(st2, D.evShade, 0));
-            if (twoStreamDelay == 2) launchSpin(st2, 300000ull);
-            on = st2;
-          }
-          timedOn(on, 3,
-              [&] { launchTrace(on, traceBlocks, true, s->countTraversal, view, ps, qs, D.dCounters.ptr, Q_SHADOW, Q_SHADOW,
-              dynRefill | (order ? TRACE_DYN_SLOT_ORDER : 0u), wideBlocks, U, D.sampleBuf.ptr); });
-          if (two) { HIP_TRY(hipEventRecord(D.evShadow, st2)); shadowInFlight = true; }
-        }
-        // (GATLING_ITER_LOG, with kernel timers on every iteration: what each iteration's queues held -- one sync per iteration, for measurements only)
-        if (iterLog) {
-          HIP_TRY(hipMemcpyAsync(D.hCounters, D.dCounters.ptr, sizeof(PaddedCounter) * Q_COUNT * NSHARD, hipMemcpyDeviceToHost, st));
-          HIP_TRY(hipStreamSynchronize(st));
-          auto total = [&](uint32_t q) { uint64_t n = 0; for (uint32_t k = 0; k < NSHARD; k++) n += D.hCounters->count[q][k].v; return n; };
-          uint64_t hits = 0; for (uint32_t c = 0; c < MAT_CLASS_COUNT; c++) hits += total(Q_HIT + c);
-          iterRows.push_back({ev, total(Q_TRACE_A + par), hits, total(Q_SHADOW), total(Q_REGEN_A + (par ^ 1u)), total(Q_TRACE_A + (par ^ 1u))});
-        }
-        iters++; totalIters++;
-      }
-      // (a batch that ended through the poll: its last shadow launches were empty)
-      if (shadowInFlight) { (void)hipStreamWaitEvent(st, D.evShadow, 0); shadowInFlight = false; }
-      launchAccumulate(st, U, D.sampleBuf.ptr, D.accum.ptr, colorOut, batch == 0, batch + 1 == numBatches);
+      launchInit(st, f.ps, f.qs, D.dCounters.ptr, f.plan.fused ? 0u : poolNow, batch == 0);
+      const int rc = U.maxBounces == 0u ? runZeroBounceBatch(f, batch) : f.plan.fused ? runFusedBatch(f, batch) : runWavefrontBatch(f, batch, poolNow);
+      if (rc != GI_C_OK) return rc;
     }
     U.flags &= ~FLAG_TWO_STREAM;
-    if (neeRb && ps.neeKey) launchResolveNee(st, U, D.neeKey.ptr, reinterpret_cast<F4*>(rbMem(neeRb, D.slot)), (uint32_t)pixels);
-    if (clockRb) { // ClockCycles: per-pixel cost -> heat map normalised to the frame maximum, on the host like _EncodeRenderBufferAsHeatmap (Gi.cpp:327-343)
-      std::vector<uint32_t> counts(pixels);
-      HIP_TRY(hipMemcpyAsync(counts.data(), D.pathSegments.ptr, pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      float maxValue = 0.0f;
-      for (uint32_t c : counts) maxValue = std::max(maxValue, (float)c);
-      float* img = reinterpret_cast<float*>(clockRb->hostMem);
-      for (size_t p = 0; p < pixels; p++) {
-        const size_t y = rowBegin + (p / width) * rowStride, x = p % width;
-        float* o = img + (y * width + x) * 4;
-        if (maxValue > 0.0f) {
-          const int idx = std::min((int)(((float)counts[p] / maxValue) * 255.0), 255);
-          turboColormap((float)idx / 255.0f, o);
-          o[3] = 255.0f;
-        } else { o[0] = (float)counts[p]; o[1] = 0.0f; o[2] = 0.0f; }
-      }
-      HIP_TRY(hipMemcpyAsync(rbMem(clockRb, D.slot), clockRb->hostMem, clockRb->size, hipMemcpyHostToDevice, st));
-    }
-    if (bouncesRb && U.maxBounces == 0u) { // rp_main.rgen:483-486 evaluates inferno(0 / 0) = NaN for every pixel of the tile
-      float* img = reinterpret_cast<float*>(bouncesRb->hostMem);
-      for (size_t p = 0; p < pixels; p++) { float* o = img + ((rowBegin + (p / width) * rowStride) * width + p % width) * 4; o[0] = o[1] = o[2] = NAN; }
-      HIP_TRY(hipMemcpyAsync(rbMem(bouncesRb, D.slot), bouncesRb->hostMem, bouncesRb->size, hipMemcpyHostToDevice, st));
-    }
-    for (GiCRenderBuffer* rb : {neeRb, bouncesRb}) {
-      if (!rb || rb->deviceOnly || !job.readback) continue;
-      HIP_TRY(copyTileRows(rb, rb->stride));
-    }
+    if (finishPathAovs(f, aov) != GI_C_OK) return GI_C_ERROR;
   }
-  if (anyAov) { // the non-colour AOV pass (k_aov) + read-back of the rows of this tile
-    launchAov(st, U, view, aovT);
-    if (hipGetLastError() != hipSuccess) { setError("k_aov launch failed"); return GI_C_ERROR; }
-    for (GiCRenderBuffer* rb : aovBuffers) {
-      if (rb->deviceOnly || !job.readback) continue;
-      HIP_TRY(copyTileRows(rb, rb->stride));
-    }
-  }
-  HIP_TRY(hipMemcpyAsync(D.hCounters, D.dCounters.ptr, sizeof(Counters), hipMemcpyDeviceToHost, st));
-  if (colorRb && !colorRb->deviceOnly && job.readback) {
-    HIP_TRY(copyTileRows(colorRb, 16));
-  }
-  HIP_TRY(hipStreamSynchronize(st));
-  HIP_TRY(hipGetLastError());
-  double tEnd = nowMs();
+  if (!aov.produced.empty() && runAovPass(f, aov) != GI_C_OK) return GI_C_ERROR;
+  if (readBackAndWait(f, aov.color) != GI_C_OK) return GI_C_ERROR;
+  const double tEnd = nowMs();
 
-  GiCRenderStats& S = D.stats;
-  S.renderMs = tEnd - tStart; S.samples = (uint64_t)pixels * rs.spp; S.iterations = iters; S.traceLaunches = traceLaunches; S.fusedPath = usedFused ? 1u : 0u;
-  S.segments = D.hCounters->segments; S.shadowRays = D.hCounters->shadowRays; S.nodesVisited = D.hCounters->nodesVisited;
-      S.trisTested = D.hCounters->trisTested;
-  S.shadowNodesVisited = D.hCounters->shadowNodesVisited; S.shadowTrisTested = D.hCounters->shadowTrisTested;
-  // (colorRb: an AOV-only render never ran k_init -- the counters would be the previous render's) choose the shadow walks' order once both have been measured
-  // on enough rays of this scene: fewer node visits per ray wins
-  if (D.slot == 0u && colorRb && s->shadowOrder.load() < 0) {
-    for (int m = 0; m < 2; m++) {
-      s->shadowOrderRays[m] += D.hCounters->shadowOrderRays[m];
-      for (int k = 0; k < 16; k++) s->shadowOrderSteps[m] += D.hCounters->shadowOrderSteps[m][k].v;
-    }
-    constexpr uint64_t ENOUGH = 1u << 16;
-    if (s->shadowOrderRays[0] >= ENOUGH && s->shadowOrderRays[1] >= ENOUGH)
-    {
-      s->shadowOrder = (double)s->shadowOrderSteps[1] * (double)s->shadowOrderRays[0] < (double)s->shadowOrderSteps[0] * (double)s->shadowOrderRays[1] ? 1 : 0;
-      if (getenv("GATLING_BUILD_TIMING")) fprintf(stderr,
-          "[gatling_gi] shadow walks: near-to-far %.3f node visits per ray (%llu rays), slot order %.3f (%llu rays) -> %s\n",
-                                                  (double)s->shadowOrderSteps[0] / (double)s->shadowOrderRays[0], (unsigned long long)s->shadowOrderRays[0],
-                                                  (double)s->shadowOrderSteps[1] / (double)s->shadowOrderRays[1], (unsigned long long)s->shadowOrderRays[1],
-                                                      s->shadowOrder.load() ? "slot order" : "near-to-far");
-    }
+  fillStats(f, tEnd);
+  // (aov.color: an AOV-only render never ran k_init -- the counters would be the previous render's)
+  if (D.slot == 0u && aov.color) chooseShadowOrder(s, *D.hCounters);
+  printPhaseStats(s, *D.hCounters);
+  if (D.hCounters->overflow) {
+    setError("giCRender: a work-queue shard overflowed its capacity (internal sizing error); the image is invalid");
+    return GI_C_ERROR;
   }
-  if (s->countTraversal && D.hCounters->phaseTrips && optionValue("phase_stats", 0)) { // k_path's phase split (counting build)
-    const Counters& c = *D.hCounters; const double tot = (double)(c.phaseCycles[0] + c.phaseCycles[1] + c.phaseCycles[2] + c.phaseCycles[3]);
-    static const char* names[4] = {"regen", "trace", "shade", "shadow+finish"};
-    for (int k = 0; k < 4; k++) fprintf(stderr, "[gatling_gi] k_path phase %-14s %5.1f %% of wave cycles, %5.1f of 64 lanes busy per trip\n", names[k],
-        100.0 * (double)c.phaseCycles[k] / tot, (double)c.phaseLanes[k] / (double)c.phaseTrips);
-    fprintf(stderr, "[gatling_gi] k_path trips %llu, %.0f cycles per trip and wave\n", (unsigned long long)c.phaseTrips, tot / (double)c.phaseTrips);
-  }
-  if (s->countTraversal && D.hCounters->dynStats[0] && optionValue("phase_stats", 0)) { // k_trace_dyn's lane accounting (counting build, closest-hit launches)
-    const unsigned long long* d = D.hCounters->dynStats; const double st = (double)d[0];
-    fprintf(stderr, "[gatling_gi] k_trace_dyn<closest> %llu wave steps: per step %.1f lanes hold a ray, %.1f run the node test, %.1f wait for the triangle "
-                    "ring; %.3f batches per step of %.1f pairs; "
-                    "a refill every %.2f steps, %.1f lanes each\n", d[0], (double)d[1] / st, (double)d[2] / st, (double)d[3] / st, (double)d[4] / st, d[4]
-                        ? (double)d[5] / (double)d[4] : 0.0,
-            d[6] ? st / (double)d[6] : 0.0, d[6] ? (double)d[7] / (double)d[6] : 0.0);
-  }
-  if (D.hCounters->overflow) { setError("giCRender: a work-queue shard overflowed its capacity (internal sizing error); the image is invalid");
-      return GI_C_ERROR; }
-  S.traceMs = S.shadeMs = S.raygenMs = S.shadowMs = 0.0;
-  if (timers) {
-    for (size_t k = 0; k < evKind.size(); k++) {
-      float ms = 0.0f; (void)hipEventElapsedTime(&ms, D.eventPool[2 * k], D.eventPool[2 * k + 1]);
-      if (evKind[k] == 0) S.raygenMs += ms; else if (evKind[k] == 1) S.traceMs += ms; else if (evKind[k] == 2) S.shadeMs += ms; else S.shadowMs += ms;
-    }
-    if (!iterRows.empty()) { // per iteration: the stage times of its launches and what its queues held
-      size_t k = 0;
-      for (size_t r = 0; r < iterRows.size(); r++) {
-        double ms4[4] = {0.0, 0.0, 0.0, 0.0};
-        for (; 2 * k < iterRows[r].evEnd && k < evKind.size(); k++) { float ms = 0.0f;
-            (void)hipEventElapsedTime(&ms, D.eventPool[2 * k], D.eventPool[2 * k + 1]); ms4[evKind[k]] += ms; }
-        fprintf(stderr, "[gatling_gi] iter %3zu: rays %9llu hits %9llu shadow %9llu ended %9llu continuing %9llu | raygen %7.3f trace+route %7.3f shade %7.3f "
-                        "shadow %7.3f ms\n", r,
-                (unsigned long long)iterRows[r].traced, (unsigned long long)iterRows[r].hits, (unsigned long long)iterRows[r].shadow,
-                    (unsigned long long)iterRows[r].ended,
-                (unsigned long long)iterRows[r].cont, ms4[0], ms4[1], ms4[2], ms4[3]);
-      }
-    }
-    // scale the sampled totals to the whole frame (the early-exit poll can leave one raygen-only iteration unsampled)
-    const double scale = sampledIters ? (double)totalIters / (double)sampledIters : 1.0;
-    S.raygenMs *= scale; S.traceMs *= scale; S.shadeMs *= scale; S.shadowMs *= scale;
-  }
+  f.tm.finish(D.stats);
   return GI_C_OK;
 }
 

@@ -452,7 +452,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 
 // ------------------------------------------------------------------------------------------------
 // host-callable launchers
 // ------------------------------------------------------------------------------------------------
-static bool sceneFitsLds(const SceneView& sc) { return sc.nodeCount <= LDS_NODES && sc.triCount <= LDS_TRIS && sc.triCount > 0u; }
+bool sceneFitsLds(size_t nodeCount, size_t triCount) { return nodeCount <= LDS_NODES && triCount <= LDS_TRIS; }
+static bool sceneFitsLds(const SceneView& sc) { return sceneFitsLds(sc.nodeCount, sc.triCount) && sc.triCount > 0u; }
 bool traceBlockSync(const SceneView& sc) { return sceneFitsLds(sc) && sc.bvhDepth <= 8u; }
 static uint32_t traceStackEntries(const SceneView& sc) { return (sc.bvhDepth <= 4u && sceneFitsLds(sc)) ? 4u : (sc.bvhDepth <= 8u ? 8u : 16u); }
 uint32_t traceStaticLdsBytes() { return (uint32_t)(sizeof(WaveTri) * (TRACE_BLOCK / 64) + sizeof(AppendScratch<1 + MAT_CLASS_COUNT>)); }
