@@ -22,6 +22,7 @@ GI_C_OK = 0
 AOV_COLOR = 0
 FORMAT_INT32, FORMAT_FLOAT32, FORMAT_FLOAT32_VEC4 = 0, 1, 2
 OPTION_COUNT_TRAVERSAL, OPTION_KERNEL_TIMERS, OPTION_POOL_SLOTS, OPTION_SAMPLE_BUFFER_MB, OPTION_TRACE_DYNAMIC, OPTION_TWO_LEVEL, OPTION_FUSED_PATH, OPTION_DEVICES = 1, 2, 3, 4, 5, 6, 7, 8
+OPTION_SAMPLE_LOOKAHEAD = 10  # N >= 2: a progressive call may trace the samples of up to N calls in one batch (include/gi_c.h); 0 / 1 = off (default)
 OPTION_BVH_BUILD = 9  # 0 = host BVH builder (default), 1 = device builder (flat-layout scenes of more than 128 triangles)
 
 
@@ -67,6 +68,11 @@ class GiCRenderStats(C.Structure):
                 ("trisTested", C.c_uint64), ("shadowNodesVisited", C.c_uint64), ("shadowTrisTested", C.c_uint64),
                 ("iterations", C.c_uint32), ("traceLaunches", C.c_uint32), ("nodeCount", C.c_uint32), ("triangleCount", C.c_uint32),
                 ("fusedPath", C.c_uint32), ("batches", C.c_uint32), ("poolSlots", C.c_uint32), ("inactiveTriangleCount", C.c_uint32)]
+
+
+class GiCLookaheadStats(C.Structure):
+    _fields_ = [("windowCalls", C.c_uint32), ("windowServed", C.c_uint32), ("traced", C.c_uint32), ("reserved", C.c_uint32),
+                ("windowsTraced", C.c_uint64), ("callsServed", C.c_uint64), ("windowsDiscarded", C.c_uint64), ("samplesUnused", C.c_uint64)]
 
 
 # every symbol include/gi_c.h declares: (name, restype, argtypes)
@@ -144,6 +150,7 @@ SYMBOLS = [
     ("giCCreateRenderBuffer", _P, [_U, _U, _I]), ("giCDestroyRenderBuffer", None, [_P]), ("giCGetRenderBufferMem", _P, [_P]),
     ("giCGetRenderBufferDeviceMem", _P, [_P]), ("giCSetRenderBufferDeviceOnly", None, [_P, _I]),
     ("giCGetRenderStats", C.c_int, [_P, C.POINTER(GiCRenderStats)]), ("giCSetSceneOption", C.c_int, [_P, _I, _I]),
+    ("giCGetLookaheadStats", C.c_int, [_P, C.POINTER(GiCLookaheadStats)]),
     ("giCTraceRays", C.c_int, [_P, _U, _FP, _FP, _F, _F, _FP, C.POINTER(C.c_int32)]),
     ("giCDebugEvalBsdf", C.c_int, [C.POINTER(GiCMaterialDesc), _U, _FP, _FP]),
     ("giCDebugShadeClass", C.c_int, [C.POINTER(GiCMaterialDesc)]),
@@ -437,6 +444,13 @@ class Scene:
         if self.L.giCGetRenderStats(self.handle, C.byref(s)) != GI_C_OK:
             raise GiError("giCGetRenderStats failed")
         return {name: getattr(s, name) for name, _ in GiCRenderStats._fields_}
+
+    def lookahead_stats(self) -> dict:
+        """giCGetLookaheadStats: the sample look-ahead window as the last render left it, and the totals since the scene was created."""
+        s = GiCLookaheadStats()
+        if self.L.giCGetLookaheadStats(self.handle, C.byref(s)) != GI_C_OK:
+            raise GiError("giCGetLookaheadStats failed")
+        return {name: getattr(s, name) for name, _ in GiCLookaheadStats._fields_ if name != "reserved"}
 
     def trace_rays(self, origins, dirs, t_min=0.0, t_max=3.0e38):
         o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)

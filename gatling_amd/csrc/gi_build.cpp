@@ -761,11 +761,13 @@ int syncSceneGeometry(GiCScene* s)
 {
   if ((s->dirty & DIRTY_XFORM) && !(s->dirty & (DIRTY_BVH | DIRTY_MATERIALS))) { // only transforms changed: re-transform / re-braid those instances
     bool handled = false;
+    s->generation++;
     if (updateTransforms(s, handled) != GI_C_OK) return GI_C_ERROR;
     if (!handled) s->dirty |= DIRTY_BVH;
     s->dirty |= DIRTY_FRAMEBUFFER;
   }
   if (s->dirty & (DIRTY_BVH | DIRTY_MATERIALS)) {
+    s->generation++;
     if (buildScene(s) != GI_C_OK) return GI_C_ERROR;
     s->dirty &= ~(DIRTY_BVH | DIRTY_MATERIALS); s->dirty |= DIRTY_FRAMEBUFFER;
   }

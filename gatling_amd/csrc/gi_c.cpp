@@ -337,7 +337,17 @@ int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value)
   if (option == GI_C_SCENE_OPTION_BVH_BUILD) { scene->optBvhBuild = value == 1 ? 1 : 0; scene->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER; return GI_C_OK; }
   if (option == GI_C_SCENE_OPTION_DEVICES) { scene->optDevices = value > 0 ? value : 0; scene->dirty |= DIRTY_BVH | DIRTY_LIGHTS | DIRTY_FRAMEBUFFER;
       /* replicas are made with the build; a NEW replica also needs the lights, which travel under DIRTY_LIGHTS only */ return GI_C_OK; }
+  // (no dirty flag: a window in flight stays valid -- the option decides how FUTURE samples are traced, never what they are)
+  if (option == GI_C_SCENE_OPTION_SAMPLE_LOOKAHEAD) { scene->optLookahead = value > 1 ? value : 0; return GI_C_OK; }
   setError("unknown scene option"); return GI_C_ERROR;
+}
+
+int giCGetLookaheadStats(const GiCScene* scene, GiCLookaheadStats* out)
+{
+  if (!scene || !out) return GI_C_ERROR;
+  const Lookahead& L = scene->lookahead;
+  *out = GiCLookaheadStats{L.valid ? L.calls : 0u, L.valid ? L.served : 0u, L.traced, 0u, L.windowsTraced, L.callsServed, L.windowsDiscarded, L.samplesUnused};
+  return GI_C_OK;
 }
 
 int giCGetRenderStats(const GiCScene* scene, GiCRenderStats* out)

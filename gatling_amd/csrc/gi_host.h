@@ -201,6 +201,30 @@ struct GiCRenderBuffer {
   void* stageMem = nullptr; // pinned, rb->size: where the row shares of devices WITHOUT peer access to the primary pass through (allocated on first use)
 };
 
+// Sample look-ahead (GI_C_SCENE_OPTION_SAMPLE_LOOKAHEAD; gi_render.cpp planLookahead / serveFromWindow): the window one device holds in its per-sample buffer --
+// the samples [firstOffset, firstOffset + calls * spp) of every pixel of its rows, traced as ONE batch by the window's first call -- and what it was traced
+// with.  A call is served from it only if it would have traced the same samples: `key` is everything the path kernels were given, compared whole.
+struct LookaheadKey {
+  FrameUniforms U;          // the call's uniforms before the schedule adds its flags, without the fields derived from the sample offset (camera, settings,
+                            // spp, image size, rows, light counts)
+  SceneView view;           // the device arrays, the dome light, the background, the frame number
+  uint64_t generation;      // GiCScene::generation: the contents of the device arrays
+};
+struct Lookahead {
+  bool valid = false;       // `key`, `calls` ... describe what sampleBuf holds (a window of one call holds nothing: it is only the ramp's memory)
+  uint32_t calls = 0, served = 0, firstOffset = 0;
+  uint32_t pixelMajor = 0;  // layout of the window in sampleBuf: [pixel][calls * spp] or [calls * spp][pixel]
+  LookaheadKey key{};
+  uint32_t traced = 0;      // the last render on this device traced (1) or was served (0)
+  uint64_t windowsTraced = 0, callsServed = 0, windowsDiscarded = 0, samplesUnused = 0;
+  // the window is gone (an edit, another size, the buffer released or about to be written): calls nobody asked for are counted as thrown away
+  void drop()
+  {
+    if (valid && served < calls) { windowsDiscarded++; samplesUnused += (uint64_t)(calls - served) * key.U.spp; }
+    valid = false; calls = served = 0;
+  }
+};
+
 // Everything a scene keeps in ONE device's memory: the scene arrays, the path pool, the queues, the per-render scratch.  GiCScene IS the primary
 // device's (inheritance keeps the single-device code reading `s->dNodes`); multi-device renders add one replica per further device.
 struct SceneDevice {
@@ -221,6 +245,7 @@ struct SceneDevice {
   // per-sample colours of the current batch (rgb, -): [pixel][sample] under the pixel-major work order of the stage kernels, [sample][pixel] otherwise
   // (gi_queues.h sample_record)
   DeviceBuffer<F4> sampleBuf;
+  Lookahead lookahead;           // the look-ahead window sampleBuf holds between calls
   DeviceBuffer<F4> accum;        // per-pixel running sum across batches
   DeviceBuffer<uint32_t> qSlot[Q_COUNT]; // NSHARD segments of queueCap records each
   DeviceBuffer<F4> qA[Q_COUNT], qB[Q_COUNT], qC[Q_COUNT];
@@ -244,7 +269,7 @@ struct SceneDevice {
     fn(qFresh[0]); fn(qFresh[1]);
   }
   uint64_t pathStateBytes() { uint64_t n = 0; forEachPathBuffer([&](auto& b) { n += b.bytes(); }); return n; }
-  void releasePathState() { forEachPathBuffer([](auto& b) { b.release(); }); queueCap = 0; }
+  void releasePathState() { forEachPathBuffer([](auto& b) { b.release(); }); queueCap = 0; lookahead.drop(); }
   void releaseAll();
 };
 
@@ -316,6 +341,10 @@ struct GiCScene : SceneDevice {
   int32_t optDevices = 0;   // 0 = every device the library was initialised on; N = at most N of them
   // devices the previous giCRender used: progressive accumulation blends against each device's own buffer, so a change restarts it
   uint32_t lastRenderDevices = 0;
+  int32_t optLookahead = 0; // GI_C_SCENE_OPTION_SAMPLE_LOOKAHEAD: calls a look-ahead window may hold; 0 = off
+  // contents of the device arrays: bumped by every scene build, transform update and light upload (materials, textures and primvars travel with the build) --
+  // a look-ahead window traced under another generation is not served from
+  uint64_t generation = 0;
 };
 
 

@@ -13,6 +13,8 @@ void launchInit(hipStream_t s, const PathState& st, const QueueSet& qs, Counters
 // REGEN[par^1]; k_shade reads HIT and appends TRACE[par^1], REGEN[par^1], SHADOW.
 void launchRaygen(hipStream_t s, uint32_t blocks, const FrameUniforms& U, const PathState& st, const QueueSet& qs, Counters* cnt, uint32_t par, F4* sampleBuf);
 void launchAccumulate(hipStream_t s, const FrameUniforms& U, const F4* sampleBuf, F4* accum, F4* colorOut, bool firstBatch, bool lastBatch);
+// sample look-ahead: folds the samples [first, first + U.spp) of a window of `windowSamples` samples per pixel into the colour AOV of the call `U` describes
+void launchFoldWindow(hipStream_t s, const FrameUniforms& U, const F4* sampleBuf, F4* colorOut, uint32_t windowSamples, uint32_t first, bool pixelMajor);
 // launchTrace runs the block-synchronous k_trace on this scene (staged whole in LDS, at most 8 levels deep) rather than k_trace_dyn + k_route
 bool traceBlockSync(const SceneView& sc);
 // a tree of this many nodes and triangles is staged whole in LDS (gi_traversal.h LDS_NODES / LDS_TRIS); beyond it the host packs shading records, sizes a

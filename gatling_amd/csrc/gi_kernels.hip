@@ -237,6 +237,32 @@ __global__ __launch_bounds__(BLOCK) void k_accumulate(FrameUniforms U, const F4*
   st4(&colorOut[pixelIndex], c.x, c.y, c.z, 1.0f);
 }
 
+// ------------------------------------------------------------------------------------------------
+// k_fold_window (sample look-ahead): one call's share of a window that an earlier call traced as ONE batch of `windowSamples` samples per pixel.  The call
+// `U` describes owns the samples [first, first + U.spp) of every pixel; they are summed from zero in sample order and blended with the call's own sample
+// offset -- the operations and the order of k_accumulate's single-batch case, so the image is the one the call would have traced itself.  The window's layout
+// is the tracing batch's: [pixel][windowSamples] (pixel-major) or [windowSamples][pixel].  One thread per pixel; with spp 1 and the pixel-major layout
+// neighbouring threads read 16 bytes windowSamples * 16 bytes apart (a 64-byte sector per pixel at worst).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(BLOCK) void k_fold_window(FrameUniforms U, const F4* __restrict__ sampleBuf, F4* __restrict__ colorOut, uint32_t windowSamples,
+                                                       uint32_t first, uint32_t pixelMajor)
+{
+  const uint32_t p = blockIdx.x * BLOCK + threadIdx.x;
+  if (p >= U.pixelCount) return;
+  const F4* src = pixelMajor ? sampleBuf + ((size_t)p * windowSamples + first) : sampleBuf + ((size_t)first * U.pixelCount + p);
+  const size_t step = pixelMajor ? (size_t)1 : (size_t)U.pixelCount;
+  V3 pixelColor = v3(0.0f, 0.0f, 0.0f);
+  for (uint32_t s = 0; s < U.spp; s++) {
+    const F4 r = ld4(&src[(size_t)s * step]);
+    pixelColor = pixelColor + v3(r.x, r.y, r.z) * U.invSpp;
+  }
+  const uint32_t pixelIndex = tile_to_image_pixel(U, p);
+  V3 prev = pixelColor;
+  if ((U.flags & FLAG_PROGRESSIVE) && U.sampleOffset > 0u) { const F4 q = ld4(&colorOut[pixelIndex]); prev = v3(q.x, q.y, q.z); }
+  const V3 c = (prev * U.sampleOffsetF + pixelColor * U.sppF) * U.invTotalSampleCount;
+  st4(&colorOut[pixelIndex], c.x, c.y, c.z, 1.0f);
+}
+
 __global__ void k_resolve_nee(FrameUniforms U, const unsigned long long* __restrict__ key, F4* __restrict__ aov, uint32_t pixelCount)
 {
   const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -349,6 +375,11 @@ void launchAccumulate(hipStream_t s, const FrameUniforms& U, const F4* sampleBuf
 {
   hipLaunchKernelGGL(k_accumulate, dim3((U.pixelCount + BLOCK - 1u) / BLOCK), dim3(BLOCK), 0, s, U, sampleBuf, accum, colorOut, firstBatch ? 1u : 0u, lastBatch
       ? 1u : 0u);
+}
+void launchFoldWindow(hipStream_t s, const FrameUniforms& U, const F4* sampleBuf, F4* colorOut, uint32_t windowSamples, uint32_t first, bool pixelMajor)
+{
+  hipLaunchKernelGGL(k_fold_window, dim3((U.pixelCount + BLOCK - 1u) / BLOCK), dim3(BLOCK), 0, s, U, sampleBuf, colorOut, windowSamples, first,
+                     pixelMajor ? 1u : 0u);
 }
 // k_route behind a k_trace_dyn launch (gi_trace.hip launchTrace)
 void launchRoute(hipStream_t s, uint32_t blocks, const SceneView& sc, const PathState& st, const QueueSet& qs, Counters* cnt, uint32_t qIn, uint32_t qMiss,

@@ -216,6 +216,7 @@ template <class Rec> static std::vector<LightFrame> lightFrames(const std::vecto
 
 int uploadLights(GiCScene* s)
 {
+  s->generation++; // the light arrays change in place: no look-ahead window traced before this is served from
   const std::vector<SphereLightRec> sphere = usableLights(s->sphereLights.recs, "sphere");
   const std::vector<DistantLightRec> distant = usableLights(s->distantLights.recs, "distant");
   const std::vector<RectLightRec> rect = usableLights(s->rectLights.recs, "rect");

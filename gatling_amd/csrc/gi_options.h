@@ -33,6 +33,8 @@
 //   two_stream           1         batches whose work fits the pool run their shadow launches on a second stream beside the next closest-hit launch
 //                                  (gi_render.cpp "two streams")
 //   two_stream_delay     0         tests: 1 / 2 = hold the main / the second stream back 0.3 ms per iteration so that the other one runs ahead
+//   lookahead            -1        sample look-ahead of progressive low-spp calls: -1 = the scene option decides (GI_C_SCENE_OPTION_SAMPLE_LOOKAHEAD),
+//                                  0 / 1 = off, N >= 2 = a call may trace the samples of up to N calls in one batch (gi_render.cpp planLookahead)
 //   phase_stats          0         counting builds: print k_path's phase split / k_trace_dyn's lane accounting
 #pragma once
 

@@ -1,6 +1,7 @@
 // gi_render.cpp -- giCRender (Gi.cpp:1989-2524): validation and dirty handling (giCRenderImpl), the rows dealt to several devices (renderOnDevices), and one
-// device's render (renderOnDevice) as a sequence of phases: bindAovs, makeUniforms, makeFrameView, planPathMemory / allocatePathPlan, scheduleFrame /
-// scheduleBatch, runFusedBatch | runZeroBounceBatch | runWavefrontBatch (the bounce loop), finishPathAovs, runAovPass, readBackAndWait, the statistics
+// device's render (renderOnDevice) as a sequence of phases: bindAovs, makeUniforms, makeFrameView, planLookahead, then either serveFromWindow or the colour
+// pass (traceColour: planPathMemory / allocatePathPlan, scheduleFrame / scheduleBatch, runFusedBatch | runZeroBounceBatch | runWavefrontBatch (the bounce
+// loop), finishPathAovs), runAovPass, readBackAndWait, the statistics
 // (one of the translation units gi_c.cpp was split into in round 6; shared declarations: gi_host.h)
 #include "gi_host.h"
 
@@ -299,8 +300,9 @@ static bool shrinkPlan(PathPlan& p, size_t pixels)
 // this scene already holds in these buffers, which is reused), and an allocation that still fails (someone else was faster) is answered with a smaller plan
 // -- more batches first, then a smaller pool -- never with a failed render while a workable plan exists (allocatePathPlan). Results do not depend on the plan
 // (test_pool_and_batch_invariance).
-static PathPlan planPathMemory(const GiCScene* s, const GiCRenderSettings& rs, const SceneView& view, const PlanInputs& in, uint64_t freeBytes,
-                               uint64_t heldBytes, uint64_t memTotalMb)
+// `samples`: samples per pixel the render wants in its buffer -- the call's spp, or a look-ahead window's.
+static PathPlan planPathMemory(const GiCScene* s, const GiCRenderSettings& rs, uint64_t samples, const SceneView& view, const PlanInputs& in,
+                               uint64_t freeBytes, uint64_t heldBytes, uint64_t memTotalMb)
 {
   const size_t pixels = in.pixels;
   const uint64_t availMb = (freeBytes + heldBytes) >> 20;
@@ -315,7 +317,7 @@ static PathPlan planPathMemory(const GiCScene* s, const GiCRenderSettings& rs, c
   const uint64_t poolMax = std::min<uint64_t>((1ull << 30) - 1ull, // regen-queue entries keep two flag bits above the slot index (REGEN_MISSED, REGEN_FRESH)
                                               std::max<uint64_t>(64, optionU64("pool_slots", s->optPoolSlots ? s->optPoolSlots : poolDefault)));
   PathPlan p;
-  p.batchSamples = std::min<uint64_t>(rs.spp, std::max<uint64_t>(1, budgetBytes / (pixels * 16)));
+  p.batchSamples = std::min<uint64_t>(samples, std::max<uint64_t>(1, budgetBytes / (pixels * 16)));
   p.batchSamples = std::min<uint64_t>(p.batchSamples, std::max<uint64_t>(1, 0xffffffffull / pixels)); // work ids stay 32-bit
   // LDS-resident scenes without medium stacks / dome images: the fused persistent kernel k_path (gi_path.hip) keeps the paths in
   // registers -- no pool, no queues; the stage kernels remain the path for everything else (and on request: option / env)
@@ -338,13 +340,14 @@ static PathPlan planPathMemory(const GiCScene* s, const GiCRenderSettings& rs, c
 
 // Plans from what is free on the device now and allocates the plan; an allocation that fails with out-of-memory releases the resizable path state and tries
 // the next smaller plan.
-static int allocatePathPlan(GiCScene* s, SceneDevice& D, const GiCRenderSettings& rs, const SceneView& view, const PlanInputs& in, PathPlan& plan)
+static int allocatePathPlan(GiCScene* s, SceneDevice& D, const GiCRenderSettings& rs, uint64_t samples, const SceneView& view, const PlanInputs& in,
+                            PathPlan& plan)
 {
   size_t memFree = 0, memTotal = 0; (void)hipMemGetInfo(&memFree, &memTotal);
   // tests: plan as if this much were free (a planner overtaken by another allocation: the fallback below must recover)
   if (optionSet("assume_free_mb")) memFree = (size_t)optionValue("assume_free_mb", 0) << 20;
   if (!D.memTotalMb) D.memTotalMb = std::max<uint64_t>(1, (uint64_t)(memTotal >> 20));
-  plan = planPathMemory(s, rs, view, in, memFree, D.pathStateBytes(), D.memTotalMb);
+  plan = planPathMemory(s, rs, samples, view, in, memFree, D.pathStateBytes(), D.memTotalMb);
   for (int attempt = 0;; attempt++) {
     int rc = plan.fused ? GI_C_OK : ensurePathState(&D, plan.slots, plan.wideBlocks, plan.traceBlocks);
     if (rc == GI_C_OK) rc = D.sampleBuf.alloc(in.pixels * plan.batchSamples);
@@ -432,6 +435,8 @@ struct Frame {
   uint32_t numBatches = 0;
   uint32_t iters = 0, traceLaunches = 0; // GiCRenderStats::iterations / traceLaunches
   double tStart = 0.0;
+  uint32_t windowCalls = 0;     // sample look-ahead: >= 2 = the colour pass traces ONE batch of windowCalls * spp samples; this call folds the first spp
+  bool served = false;          // ... or this call traced nothing: its samples came out of the window (serveFromWindow)
 };
 
 // The PathState of the colour pass: the pool, and what the path-following AOVs bound to this render need beside it.
@@ -519,6 +524,10 @@ static bool scheduleBatch(Frame& f, uint64_t rounds)
 // --- the three kinds of batch.  renderOnDevice has set the batch's uniforms and launched k_init; each ends in the batch's accumulation.
 static void accumulateBatch(Frame& f, uint32_t batch)
 {
+  if (f.windowCalls >= 2u) { // a look-ahead window (one batch): this call's samples are its first spp
+    launchFoldWindow(f.st, f.U, f.D.sampleBuf.ptr, f.colorOut, f.U.batchSamples, 0u, (f.U.flags & FLAG_PIXEL_MAJOR) != 0u);
+    return;
+  }
   launchAccumulate(f.st, f.U, f.D.sampleBuf.ptr, f.D.accum.ptr, f.colorOut, batch == 0, batch + 1 == f.numBatches);
 }
 
@@ -720,6 +729,11 @@ static void fillStats(const Frame& f, double tEnd)
 {
   GiCRenderStats& S = f.D.stats; const Counters& c = *f.D.hCounters;
   S.renderMs = tEnd - f.tStart; S.samples = (uint64_t)f.pixels * f.rs.spp; S.iterations = f.iters; S.traceLaunches = f.traceLaunches;
+  if (f.served) { // nothing was launched but the fold: the counters on the device are still those of the call that traced the window
+    S.fusedPath = S.batches = S.poolSlots = 0u;
+    S.segments = S.shadowRays = S.nodesVisited = S.trisTested = S.shadowNodesVisited = S.shadowTrisTested = 0u;
+    return;
+  }
   S.fusedPath = f.plan.fused ? 1u : 0u;
   S.segments = c.segments; S.shadowRays = c.shadowRays; S.nodesVisited = c.nodesVisited; S.trisTested = c.trisTested;
   S.shadowNodesVisited = c.shadowNodesVisited; S.shadowTrisTested = c.shadowTrisTested;
@@ -767,6 +781,117 @@ static void printPhaseStats(const GiCScene* s, const Counters& c)
   }
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------
+// Sample look-ahead (GI_C_SCENE_OPTION_SAMPLE_LOOKAHEAD, GATLING_OPTIONS=lookahead=N).  A path's arithmetic depends on its GLOBAL sample
+// index alone, never on spp (the Bounces AOV apart), so K consecutive progressive calls of spp samples are, to the path kernels, one batch of K * spp samples
+// starting at the first call's sample offset -- only the fold into the image differs per call.  planLookahead decides what this call does with that:
+//   serve   the device holds a window traced with exactly what this call would trace with, and this call's samples are the next in it: fold them
+//           (serveFromWindow), launch nothing else of the colour pass;
+//   trace   a window of `calls` calls -- 1 after any reset (the first frame after an edit costs what it costs today), then 2, 4, 8 ... N as long as every call
+//           continues the previous window -- through the colour pass with batchSamples = calls * spp, as ONE batch (traceColour bounds it by the memory plan);
+//   decline calls == 0: the call renders as without the option and leaves no window.
+// Validity is never inferred from which setter ran: the window keeps what it was traced WITH (LookaheadKey) and the call compares what it would trace with.
+// ---------------------------------------------------------------------------------------------------------------
+struct LookaheadPlan { bool serve = false; uint32_t calls = 0; LookaheadKey key{}; };
+
+static long lookaheadOption(const GiCScene* s)
+{
+  const long o = optionSet("lookahead") ? optionValue("lookahead", -1) : -1;
+  return o >= 0 ? o : (long)s->optLookahead;
+}
+
+static LookaheadPlan planLookahead(Frame& f, const BoundAovs& A)
+{
+  Lookahead& L = f.D.lookahead;
+  const GiCRenderSettings& rs = f.rs;
+  LookaheadPlan la;
+  const uint64_t N = (uint64_t)std::max(0L, lookaheadOption(f.s));
+  // the path-following AOVs read path state when a sample retires, Bounces reads U.spp: such renders keep today's form
+  if (N < 2u || !rs.progressiveAccumulation || A.nee || A.bounces || A.clock) { L.drop(); return la; }
+  memset(&la.key, 0, sizeof(la.key));
+  la.key.U = f.U; la.key.view = f.view; la.key.generation = f.s->generation;
+  la.key.U.sampleOffset = 0u; la.key.U.sampleOffsetF = 0.0f; la.key.U.invTotalSampleCount = 0.0f; // (spp, invSpp, sppF stay: another spp is another window)
+  // this call's samples are the next the previous window's calls left off at, and everything else is what that window was traced with
+  const bool continues = L.valid && (uint64_t)f.U.sampleOffset == (uint64_t)L.firstOffset + (uint64_t)L.served * rs.spp
+                         && memcmp(&la.key.U, &L.key.U, sizeof(FrameUniforms)) == 0 && memcmp(&la.key.view, &L.key.view, sizeof(SceneView)) == 0
+                         && la.key.generation == L.key.generation;
+  if (continues && L.served < L.calls) { la.serve = true; la.calls = L.calls; return la; }
+  // a new window: twice the previous one's calls if this call continues it, else one call.  One batch: 32-bit work ids, and the sample index must not wrap
+  uint64_t want = continues ? std::min<uint64_t>(N, 2ull * L.calls) : 1ull;
+  want = std::min<uint64_t>(want, 0xffffffffull / ((uint64_t)f.pixels * rs.spp));
+  want = std::min<uint64_t>(want, (0xffffffffull - f.U.sampleOffset) / rs.spp);
+  L.drop(); // (whatever this call traces is written over the old window)
+  la.calls = (uint32_t)std::max<uint64_t>(1, want);
+  return la;
+}
+
+// the serve phase: this call's spp samples out of the window, blended with its own sample offset
+static int serveFromWindow(Frame& f, const BoundAovs& A)
+{
+  SceneDevice& D = f.D; Lookahead& L = D.lookahead;
+  const uint64_t windowSamples = (uint64_t)L.calls * f.rs.spp, first = (uint64_t)L.served * f.rs.spp;
+  if (!D.sampleBuf.ptr || (uint64_t)f.pixels * windowSamples > D.sampleBuf.count || first + f.rs.spp > windowSamples) {
+    setError("giCRender: the look-ahead window does not lie inside the per-sample buffer (internal error)");
+    return GI_C_ERROR;
+  }
+  f.served = true;
+  f.colorOut = reinterpret_cast<F4*>(rbMem(A.color, D.slot));
+  launchFoldWindow(f.st, f.U, D.sampleBuf.ptr, f.colorOut, (uint32_t)windowSamples, (uint32_t)first, L.pixelMajor != 0u);
+  if (hipGetLastError() != hipSuccess) { setError("k_fold_window launch failed"); return GI_C_ERROR; }
+  L.served++; L.callsServed++; L.traced = 0u;
+  return GI_C_OK;
+}
+
+// the colour pass: the memory plan, the schedule, the batches -- the call's own spp samples, or (la.calls >= 2) a look-ahead window of la.calls * spp samples
+// as one batch, of which this call folds the first spp -- and the path-following AOVs
+static int traceColour(Frame& f, const BoundAovs& aov, const LookaheadPlan& la)
+{
+  GiCScene* s = f.s; SceneDevice& D = f.D; const DevCtx& ctx = f.ctx; const GiCRenderSettings& rs = f.rs; hipStream_t st = f.st;
+  const size_t pixels = f.pixels;
+  D.lookahead.traced = 1u;
+  const PlanInputs in{pixels, (uint32_t)ctx.cuCount, traceBlocksPerCu(f.view)};
+  if (allocatePathPlan(s, D, rs, (uint64_t)std::max(1u, la.calls) * rs.spp, f.view, in, f.plan) != GI_C_OK) return GI_C_ERROR;
+  const uint64_t batchSamples = f.plan.batchSamples;
+  // the window is what the plan's buffer holds of it (SAMPLE_BUFFER_MB, assume_free_mb, the shrink on out-of-memory); a call that needs several batches
+  // itself declines
+  const uint32_t calls = (uint32_t)std::min<uint64_t>(la.calls, batchSamples / rs.spp);
+  f.windowCalls = calls >= 2u ? calls : 0u;
+  const uint64_t samples = calls >= 2u ? (uint64_t)calls * rs.spp : (uint64_t)rs.spp;
+  f.numBatches = (uint32_t)((samples + batchSamples - 1) / batchSamples);
+  D.stats.poolSlots = f.plan.fused ? 0u : (uint32_t)f.plan.slots; D.stats.batches = f.numBatches;
+  if (bindPathAovs(f, aov) != GI_C_OK) return GI_C_ERROR;
+  f.sch = scheduleFrame(f);
+  f.qs = makeQueueSet(&D);
+  f.colorOut = reinterpret_cast<F4*>(rbMem(aov.color, D.slot));
+
+  HIP_TRY(hipStreamSynchronize(st));
+  f.tStart = nowMs();
+  if (f.sch.twoStreamOk && !D.evShade) {
+    HIP_TRY(hipEventCreateWithFlags(&D.evShade, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&D.evShadow, hipEventDisableTiming));
+  }
+  FrameUniforms& U = f.U;
+  for (uint32_t batch = 0; batch < f.numBatches; batch++) {
+    U.batchFirstSample = (uint32_t)(batch * batchSamples);
+    U.batchSamples = (uint32_t)std::min<uint64_t>(batchSamples, samples - (uint64_t)batch * batchSamples);
+    U.workTotal = (uint32_t)(pixels * U.batchSamples);
+    f.ps.neeSampleBase = U.batchFirstSample;
+    const uint32_t poolNow = (uint32_t)std::min<uint64_t>(f.plan.slots, U.workTotal);
+    U.poolSlots = poolNow;
+    launchInit(st, f.ps, f.qs, D.dCounters.ptr, f.plan.fused ? 0u : poolNow, batch == 0);
+    const int rc = U.maxBounces == 0u ? runZeroBounceBatch(f, batch) : f.plan.fused ? runFusedBatch(f, batch) : runWavefrontBatch(f, batch, poolNow);
+    if (rc != GI_C_OK) return rc;
+  }
+  if (calls >= 1u) { // what the device now holds (a window of one call holds nothing: it is where the ramp starts)
+    Lookahead& L = D.lookahead;
+    L.valid = true; L.calls = calls; L.served = 1u; L.firstOffset = U.sampleOffset; L.pixelMajor = (U.flags & FLAG_PIXEL_MAJOR) ? 1u : 0u; L.key = la.key;
+    L.windowsTraced++;
+  }
+  U.flags &= ~FLAG_TWO_STREAM;
+  return finishPathAovs(f, aov);
+}
+
 static int renderOnDevice(GiCScene* s, SceneDevice& D, const RenderJob& job)
 {
   const DevCtx& ctx = g_ctx.devs[D.slot];
@@ -786,48 +911,23 @@ static int renderOnDevice(GiCScene* s, SceneDevice& D, const RenderJob& job)
   f.tStart = nowMs();
   f.view = makeFrameView(s, D, *job.params, f.U);
   if (ensurePathState(&D, 1, 1, 1) != GI_C_OK) return GI_C_ERROR; // counters / pinned mirror exist even for AOV-only renders
+  LookaheadPlan la;
   if (aov.color) {
     f.view.mediumStackSize = rs.mediumStackSize;
-    const PlanInputs in{pixels, (uint32_t)ctx.cuCount, traceBlocksPerCu(f.view)};
-    if (allocatePathPlan(s, D, rs, f.view, in, f.plan) != GI_C_OK) return GI_C_ERROR;
-    const uint64_t batchSamples = f.plan.batchSamples;
-    f.numBatches = (uint32_t)((rs.spp + batchSamples - 1) / batchSamples);
-    D.stats.poolSlots = f.plan.fused ? 0u : (uint32_t)f.plan.slots; D.stats.batches = f.numBatches;
-    if (bindPathAovs(f, aov) != GI_C_OK) return GI_C_ERROR;
-    f.sch = scheduleFrame(f);
-    f.qs = makeQueueSet(&D);
-    f.colorOut = reinterpret_cast<F4*>(rbMem(aov.color, D.slot));
-
-    HIP_TRY(hipStreamSynchronize(st));
-    f.tStart = nowMs();
-    if (f.sch.twoStreamOk && !D.evShade) {
-      HIP_TRY(hipEventCreateWithFlags(&D.evShade, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&D.evShadow, hipEventDisableTiming));
-    }
-    FrameUniforms& U = f.U;
-    for (uint32_t batch = 0; batch < f.numBatches; batch++) {
-      U.batchFirstSample = (uint32_t)(batch * batchSamples);
-      U.batchSamples = (uint32_t)std::min<uint64_t>(batchSamples, rs.spp - (uint64_t)batch * batchSamples);
-      U.workTotal = (uint32_t)(pixels * U.batchSamples);
-      f.ps.neeSampleBase = U.batchFirstSample;
-      const uint32_t poolNow = (uint32_t)std::min<uint64_t>(f.plan.slots, U.workTotal);
-      U.poolSlots = poolNow;
-      launchInit(st, f.ps, f.qs, D.dCounters.ptr, f.plan.fused ? 0u : poolNow, batch == 0);
-      const int rc = U.maxBounces == 0u ? runZeroBounceBatch(f, batch) : f.plan.fused ? runFusedBatch(f, batch) : runWavefrontBatch(f, batch, poolNow);
-      if (rc != GI_C_OK) return rc;
-    }
-    U.flags &= ~FLAG_TWO_STREAM;
-    if (finishPathAovs(f, aov) != GI_C_OK) return GI_C_ERROR;
+    la = planLookahead(f, aov);
+    const int rc = la.serve ? serveFromWindow(f, aov) : traceColour(f, aov, la);
+    if (rc != GI_C_OK) { D.lookahead.drop(); return rc; }
   }
-  if (!aov.produced.empty() && runAovPass(f, aov) != GI_C_OK) return GI_C_ERROR;
-  if (readBackAndWait(f, aov.color) != GI_C_OK) return GI_C_ERROR;
+  if (!aov.produced.empty() && runAovPass(f, aov) != GI_C_OK) { D.lookahead.drop(); return GI_C_ERROR; }
+  if (readBackAndWait(f, aov.color) != GI_C_OK) { D.lookahead.drop(); return GI_C_ERROR; }
   const double tEnd = nowMs();
 
   fillStats(f, tEnd);
-  // (aov.color: an AOV-only render never ran k_init -- the counters would be the previous render's)
-  if (D.slot == 0u && aov.color) chooseShadowOrder(s, *D.hCounters);
-  printPhaseStats(s, *D.hCounters);
-  if (D.hCounters->overflow) {
+  // (aov.color: an AOV-only render never ran k_init -- the counters would be the previous render's; so would a served call's)
+  if (D.slot == 0u && aov.color && !f.served) chooseShadowOrder(s, *D.hCounters);
+  if (!f.served) printPhaseStats(s, *D.hCounters);
+  if (D.hCounters->overflow && !f.served) {
+    D.lookahead.drop();
     setError("giCRender: a work-queue shard overflowed its capacity (internal sizing error); the image is invalid");
     return GI_C_ERROR;
   }

@@ -340,6 +340,23 @@ typedef struct GiCRenderStats {
   uint32_t poolSlots;    /* slots of the persistent path pool this render used (0: fused kernel)                              */
   uint32_t inactiveTriangleCount; /* instanced triangles left out of the BVH: a non-finite or out-of-range (> 1e18) vertex, a non-invertible transform (was reserved0) */
 } GiCRenderStats;
+/* With GI_C_SCENE_OPTION_SAMPLE_LOOKAHEAD the counts and stage times (segments, shadowRays, the node / triangle counters, iterations, traceLaunches, batches,
+ * poolSlots, fusedPath, traceMs ...) describe the work the call LAUNCHED: the whole window for a call that traced one, zero for a call that was served from it.
+ * `samples` stays the call's own pixels * spp and `renderMs` its own wall time.  Summed over the calls of a window, segments / shadowRays are what the same calls
+ * count without look-ahead. */
+
+/* [ext] sample look-ahead (GI_C_SCENE_OPTION_SAMPLE_LOOKAHEAD) as the last giCRender on the scene left it (of a multi-device render: the primary device's share;
+ * every device looks ahead for its own rows, in step) */
+typedef struct GiCLookaheadStats {
+  uint32_t windowCalls;      /* calls the current window holds (1: the call traced itself alone; 0: no window -- look-ahead off or declined by this call) */
+  uint32_t windowServed;     /* calls of it served so far, this one included                                                                              */
+  uint32_t traced;           /* 1: this call traced (its window, or itself as without look-ahead); 0: it was served without tracing a ray                 */
+  uint32_t reserved;
+  uint64_t windowsTraced;    /* since the scene was created: windows traced (those of one call included) ...                                              */
+  uint64_t callsServed;      /* ... calls served without tracing ...                                                                                      */
+  uint64_t windowsDiscarded; /* ... windows dropped while they still held calls nobody had asked for (an edit, another size, released memory) ...         */
+  uint64_t samplesUnused;    /* ... and the samples per pixel traced for those calls                                                                      */
+} GiCLookaheadStats;
 
 /* Gi.h:199-200.  deviceOrdinal selects the HIP device (the reference picks one Vulkan device by score,
  * CgpuVk.cpp:892-909).  One giCInitialize per process, like the reference's global state (Gi.cpp:244-259). */
@@ -356,7 +373,9 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * the subsurface radius slots of GiCMaterialDesc, the asset-reader / image-loader hooks; 6: GiCRenderStats.reserved0 became inactiveTriangleCount,
  * giCDebugShadeClass, an all-zero subsurface radius is no longer read as "unset", the hostile-input rules above giCRender;
  * 7: GI_C_P_COAT_ROTATION / GI_C_P_SPECULAR_ROTATION, slots that were reserved; 8: GI_C_SCENE_OPTION_BVH_BUILD, giCDebugValidateSceneBvh, bvhBuildMs counts
- * the device build when one ran).  A caller compares giCGetApiVersion() with the GI_C_API_VERSION it was built with. */
+ * the device build when one ran).  A caller compares giCGetApiVersion() with the GI_C_API_VERSION it was built with.
+ * Still 8 with GI_C_SCENE_OPTION_SAMPLE_LOOKAHEAD and giCGetLookaheadStats: no struct grew and no entry point changed meaning -- both are additions that a caller
+ * built against an earlier header never sees.  A caller probes for them: giCSetSceneOption answers GI_C_ERROR for an option the library does not know. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -484,6 +503,17 @@ int giCGetRenderStats(const GiCScene* scene, GiCRenderStats* out);
  * scene (the two-level layout, small LDS-resident scenes) keeps the host builder.  Out of device memory during the build falls back to the host builder.
  * GATLING_OPTIONS=device_build=0|1 overrides it.  The image does not depend on it. */
 #define GI_C_SCENE_OPTION_BVH_BUILD 9
+/* [ext] Sample look-ahead for progressive low-spp rendering (hdGatling's default frame is one sample per pixel and call): value N >= 2 = a giCRender call may trace
+ * the samples of the next calls as well, in one batch (a "window" of at most N calls), keep them in the scene's per-sample buffer and serve each following call --
+ * as long as nothing that enters an image has changed -- by folding ITS spp samples into the colour AOV without tracing a ray.  0 or 1 = off (default 0).
+ * Windows ramp up 1, 2, 4 ... N calls after every reset of the accumulation, so an edit throws away fewer samples than were served since the previous one, and
+ * never more than N - 1 calls' worth.  Every image of every call is the image the library returns without the option.  Look-ahead declines (the call renders as
+ * without it) when progressiveAccumulation is off, a NEE / Bounces / ClockCycles AOV is bound, or the call itself needs more than one batch; the memory plan
+ * (GI_C_SCENE_OPTION_SAMPLE_BUFFER_MB, free device memory) bounds the window.  Cost: the call that traces a window of K takes about K calls' samples at batch
+ * rate and the K - 1 after it are short -- mean latency falls, per-call latency becomes uneven -- and the window holds pixels * K * spp * 16 bytes between
+ * calls.  GATLING_OPTIONS=lookahead=N overrides it.  See giCGetLookaheadStats and the note below GiCRenderStats. */
+#define GI_C_SCENE_OPTION_SAMPLE_LOOKAHEAD 10
+int giCGetLookaheadStats(const GiCScene* scene, GiCLookaheadStats* out);
 int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value);
 /* [ext] closest hit of one ray through the device traversal kernel (parity tests of the BVH8 path).
  * Returns 1 on hit (t,u,v, instance, prim written), 0 on miss, <0 on error.  Candidates on cut-out materials pass the any-hit test of the render
