@@ -159,6 +159,7 @@ SYMBOLS = [
     ("giCDebugValidatePartitionedBvh", C.c_int, [_FP, _U, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("giCDebugValidateSceneBvh", C.c_int, [_P, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     ("giCDebugTexRuntime", C.c_int, [_FP, _U, _U, _U, _U, _FP, _FP]),
+    ("giCDebugEditDirtyFlags", C.c_int32, [_I, _I]), ("giCDebugSceneUpdateCounts", C.c_int, [_P, C.POINTER(C.c_uint64)]),
 ]
 
 _lib = None
@@ -256,19 +257,7 @@ class Scene:
                     raise GiError("gtl::giCreateMaterialFromMtlxStr refused the document of material %d" % mi)
                 self.materials.append(h)
                 continue
-            md = GiCMaterialDesc(m.klass, 0, (C.c_float * P_COUNT)(*np.asarray(m.params, np.float32)))
-            h = L.giCCreateMaterial(self.handle, m.name.encode(), C.byref(md))
-            if not h:
-                raise GiError("giCCreateMaterial failed: " + L.giCGetLastError().decode())
-            for slot, b in getattr(m, "textures", {}).items():
-                tb = GiCTextureBinding(self.textures[b.texture], int(b.wrap_s), int(b.wrap_t), int(b.channel), (C.c_float * 4)(*b.scale), (C.c_float * 4)(*b.bias))
-                if L.giCSetMaterialTexture(h, int(slot), C.byref(tb)) != GI_C_OK:
-                    raise GiError("giCSetMaterialTexture failed: " + L.giCGetLastError().decode())
-                if getattr(b, "transform", None) is not None and L.giCSetMaterialTextureTransform(h, int(slot), _fp(b.transform)) != GI_C_OK:
-                    raise GiError("giCSetMaterialTextureTransform failed: " + L.giCGetLastError().decode())
-            for slot, name in getattr(m, "primvar_inputs", {}).items():
-                if L.giCSetMaterialPrimvarInput(h, int(slot), name.encode()) != GI_C_OK:
-                    raise GiError("giCSetMaterialPrimvarInput failed: " + L.giCGetLastError().decode())
+            h = self._material_handle(m)
             self.materials.append(h)
         if getattr(desc, "dome_light", None) is not None:
             d = desc.dome_light
@@ -341,6 +330,110 @@ class Scene:
         t = np.ascontiguousarray(transforms, np.float32).reshape(-1, 16)
         self.desc.meshes[mesh_index].instance_transforms = t.reshape(-1, 4, 4).copy()
         self.L.giCSetMeshInstanceTransforms(self.meshes[mesh_index], len(t), t.ctypes.data_as(_FP))
+
+    def _material_handle(self, m):
+        """giCCreateMaterial + texture bindings + primvar inputs of one MaterialDesc (texture indices name self.textures)."""
+        L = self.L
+        md = GiCMaterialDesc(m.klass, 0, (C.c_float * P_COUNT)(*np.asarray(m.params, np.float32)))
+        h = L.giCCreateMaterial(self.handle, m.name.encode(), C.byref(md))
+        if not h:
+            raise GiError("giCCreateMaterial failed: " + L.giCGetLastError().decode())
+        for slot, b in getattr(m, "textures", {}).items():
+            self._bind_texture(h, slot, b)
+        for slot, name in getattr(m, "primvar_inputs", {}).items():
+            if L.giCSetMaterialPrimvarInput(h, int(slot), name.encode()) != GI_C_OK:
+                raise GiError("giCSetMaterialPrimvarInput failed: " + L.giCGetLastError().decode())
+        return h
+
+    def _bind_texture(self, h, slot, b):
+        L = self.L
+        tb = GiCTextureBinding(self.textures[b.texture], int(b.wrap_s), int(b.wrap_t), int(b.channel), (C.c_float * 4)(*b.scale), (C.c_float * 4)(*b.bias))
+        if L.giCSetMaterialTexture(h, int(slot), C.byref(tb)) != GI_C_OK:
+            raise GiError("giCSetMaterialTexture failed: " + L.giCGetLastError().decode())
+        if L.giCSetMaterialTextureTransform(h, int(slot), _fp(b.transform) if getattr(b, "transform", None) is not None else None) != GI_C_OK:
+            raise GiError("giCSetMaterialTextureTransform failed: " + L.giCGetLastError().decode())
+
+    def set_mesh_material(self, mesh_index: int, material_index: int):
+        """giSetMeshMaterial (Gi.h:215); material_index < 0 = NULL (the mesh drops out of the scene).  A material-side edit: the next render patches the scene
+        in place."""
+        self.desc.meshes[mesh_index].material = int(material_index)
+        self.L.giCSetMeshMaterial(self.meshes[mesh_index], self.materials[material_index] if material_index >= 0 else None)
+
+    def replace_material(self, material_index: int, desc):
+        """Edits a material the way hdGatling does: destroy it, create the new one, re-assign the meshes that were bound to it."""
+        self.L.giCDestroyMaterial(self.materials[material_index])
+        self.materials[material_index] = None
+        self.materials[material_index] = self._material_handle(desc)
+        self.desc.materials[material_index] = desc
+        for i, m in enumerate(self.desc.meshes):
+            if m.material == material_index:
+                self.L.giCSetMeshMaterial(self.meshes[i], self.materials[material_index])
+
+    def destroy_material(self, material_index: int):
+        """giDestroyMaterial alone: the meshes bound to it are left without a material (and out of the scene) until they get another."""
+        self.L.giCDestroyMaterial(self.materials[material_index])
+        self.materials[material_index] = None
+
+    def set_material_texture(self, material_index: int, slot: int, binding):
+        """giCSetMaterialTexture on a live material; binding None unbinds the input."""
+        m = self.desc.materials[material_index]
+        if binding is None:
+            m.textures.pop(slot, None)
+            if self.L.giCSetMaterialTexture(self.materials[material_index], int(slot), None) != GI_C_OK:
+                raise GiError("giCSetMaterialTexture failed: " + self.L.giCGetLastError().decode())
+        else:
+            m.textures[slot] = binding
+            self._bind_texture(self.materials[material_index], slot, binding)
+
+    def add_texture(self, image) -> int:
+        """giCCreateTexture on a live scene; returns the index into desc.textures."""
+        a = np.ascontiguousarray(image, np.float32)
+        td = GiCTextureDesc(a.shape[1], a.shape[0], a.ctypes.data)
+        h = self.L.giCCreateTexture(self.handle, C.byref(td))
+        if not h:
+            raise GiError("giCCreateTexture failed: " + self.L.giCGetLastError().decode())
+        self.textures.append(h); self.desc.textures.append(a)
+        return len(self.textures) - 1
+
+    def set_material_primvar_input(self, material_index: int, slot: int, name):
+        """giCSetMaterialPrimvarInput on a live material; name None / "" disconnects the input."""
+        m = self.desc.materials[material_index]
+        if name:
+            m.primvar_inputs[slot] = name
+        else:
+            m.primvar_inputs.pop(slot, None)
+        if self.L.giCSetMaterialPrimvarInput(self.materials[material_index], int(slot), name.encode() if name else None) != GI_C_OK:
+            raise GiError("giCSetMaterialPrimvarInput failed: " + self.L.giCGetLastError().decode())
+
+    def _set_primvars(self, fn, h, pvs):
+        arr, keep = (GiCPrimvarData * max(len(pvs), 1))(), []
+        for k, pv in enumerate(pvs):
+            d = np.ascontiguousarray(pv.data, np.int32 if int(pv.type) >= 4 else np.float32).reshape(-1)  # Int..Int4 (Gi.h:76-79)
+            keep.append(d)
+            arr[k] = GiCPrimvarData(pv.name.encode(), int(pv.type), int(pv.interpolation), d.ctypes.data, d.nbytes)
+        if fn(h, len(pvs), arr) != GI_C_OK:  # copies the data
+            raise GiError("giCSetMesh*Primvars failed: " + self.L.giCGetLastError().decode())
+
+    def set_mesh_primvars(self, mesh_index: int, primvars):
+        """giCSetMeshPrimvars on a live mesh (replaces the mesh's primvar list)."""
+        self.desc.meshes[mesh_index].primvars = list(primvars)
+        self._set_primvars(self.L.giCSetMeshPrimvars, self.meshes[mesh_index], list(primvars))
+
+    def set_mesh_instancer_primvars(self, mesh_index: int, primvars):
+        self.desc.meshes[mesh_index].instancer_primvars = list(primvars)
+        self._set_primvars(self.L.giCSetMeshInstancerPrimvars, self.meshes[mesh_index], list(primvars))
+
+    def set_mesh_visibility(self, mesh_index: int, visible: bool):
+        """giSetMeshVisibility (Gi.h:216): a geometry-side edit, the next render rebuilds the scene."""
+        self.desc.meshes[mesh_index].visible = bool(visible)
+        self.L.giCSetMeshVisibility(self.meshes[mesh_index], int(bool(visible)))
+
+    def update_counts(self) -> dict:
+        """giCDebugSceneUpdateCounts: how often the scene was brought up to date by a full build / a transform update / a material update."""
+        c = (C.c_uint64 * 3)()
+        if self.L.giCDebugSceneUpdateCounts(self.handle, c) != GI_C_OK:
+            raise GiError("giCDebugSceneUpdateCounts failed")
+        return {"full": int(c[0]), "transform": int(c[1]), "material": int(c[2])}
 
     def set_option(self, option: int, value: int):
         if self.L.giCSetSceneOption(self.handle, option, value) != GI_C_OK:
@@ -486,7 +579,8 @@ class Scene:
             for h in self.meshes:
                 L.giCDestroyMesh(h)
             for h in self.materials:
-                L.giCDestroyMaterial(h)
+                if h:
+                    L.giCDestroyMaterial(h)
             if self.dome:
                 L.giCDestroyDomeLight(self.dome)
             for h in self.textures:

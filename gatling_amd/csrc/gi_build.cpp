@@ -95,6 +95,80 @@ inline void flattenTriangle(const InstanceRec& ir, bool usable, const GiCMesh* m
   if (!usable) t.v0[0] = std::numeric_limits<float>::quiet_NaN();
 }
 
+// The MaterialRec table of the scene's materials, in creation order (buildScene and updateMaterials: the one copy of this code)
+static void buildMaterialRecords(const GiCScene* s, std::vector<MaterialRec>& mats)
+{
+  mats.assign(s->materials.size(), MaterialRec{});
+  for (size_t i = 0; i < s->materials.size(); i++) {
+    mats[i].klass = s->materials[i]->desc.klass; mats[i].flags = s->materials[i]->desc.flags & ~(MAT_FLAG_TEXTURED | MAT_FLAG_OPACITY_TEX);
+    for (uint32_t slot = 0; slot < TEX_SLOT_COUNT; slot++) {
+      const GiCTextureBinding& b = s->materials[i]->tex[slot];
+      TexBindingRec& r = mats[i].tex[slot];
+      r = TexBindingRec{};
+      auto tit = b.texture ? std::find(s->textures.begin(), s->textures.end(), b.texture) : s->textures.end();
+      if (tit == s->textures.end()) {
+        if (!s->materials[i]->primvarInput[slot].empty()) {
+          r.mode = TEX_MODE_PRIMVAR; mats[i].flags |= MAT_FLAG_TEXTURED;
+          // Frontend.cpp:251-252: named scene data answered from the UBO
+          if (s->materials[i]->primvarInput[slot] == "CAMERA_POSITION") r.mode |= TEX_MODE_CAMERA_POSITION;
+          if (s->materials[i]->primvarInput[slot] == "FRAME") r.mode |= TEX_MODE_FRAME;
+        }
+        continue;
+      }
+      r.tex = (uint32_t)(tit - s->textures.begin()) + 1u;
+      r.mode = (uint32_t)b.wrapS | ((uint32_t)b.wrapT << 8) | (((uint32_t)b.channel & 3u) << 16);
+      memcpy(r.scale, b.scale, 16); memcpy(r.bias, b.bias, 16);
+      if (s->materials[i]->hasTexXf[slot]) { r.mode |= TEX_MODE_XFORM; memcpy(r.xf, s->materials[i]->texXf[slot], sizeof(r.xf)); }
+      mats[i].flags |= slot == TEX_OPACITY ? MAT_FLAG_OPACITY_TEX : MAT_FLAG_TEXTURED; // opacity is looked up by the any-hit test, not by k_shade
+    }
+    memcpy(mats[i].p, s->materials[i]->desc.p, sizeof(float) * MAT_PARAM_COUNT);
+    deriveMaterialConstants(mats[i]);
+  }
+}
+
+// Scene data one mesh's material reads (Gi.cpp:905-1019): instancer primvars first, mesh primvars override, by name.  Appends the mesh's MeshRec and its
+// primvar arrays (buildScene and updateMaterials: the one copy of this code)
+static void appendMeshSceneData(const GiCMesh* m, const GiCMaterial* mat, uint32_t vertexOffset, std::vector<MeshRec>& meshRecs, std::vector<float>& sceneData)
+{
+  MeshRec mr{}; mr.vertexOffset = vertexOffset;
+  for (uint32_t slot = 0; slot < TEX_SLOT_COUNT; slot++) {
+    const std::string& want = mat->primvarInput[slot];
+    if (want.empty()) continue;
+    const GiCPrimvar* pv = nullptr;
+    for (const GiCPrimvar& p : m->instancerPrimvars) if (p.name == want && !p.data.empty()) { pv = &p; break; }
+    for (const GiCPrimvar& p : m->primvars) if (p.name == want && !p.data.empty()) { pv = &p; break; }
+    if (!pv) continue; // SCENE_DATA_INVALID
+    const bool isInt = pv->type > GI_C_PRIMVAR_VEC4; // Int .. Int4 (Gi.h:76-79)
+    const uint32_t stride = (uint32_t)(isInt ? pv->type - GI_C_PRIMVAR_INT : pv->type) + 1u;
+    size_t entries = 1; // what a lookup can index: zero-padded so that short arrays read 0 like the oracle
+    if (pv->interpolation == GI_C_INTERP_VERTEX) entries = m->vertices.size();
+    else if (pv->interpolation == GI_C_INTERP_UNIFORM) entries = m->faces.size();
+    else if (pv->interpolation == GI_C_INTERP_INSTANCE) { int32_t mx = (int32_t)(m->instanceTransforms.size() / 16) - 1;
+        for (int32_t id : m->instanceIds) mx = std::max(mx, id); entries = (size_t)std::max(mx, 0) + 1; }
+    mr.sdOffset[slot] = (uint32_t)sceneData.size();
+    mr.sdInfo[slot] = 1u | ((stride - 1u) << 1) | ((uint32_t)pv->interpolation << 3) | (isInt ? SD_INFO_INT : 0u);
+    // (+ 2: a three-component lookup of a one- or two-component primvar reads up to two floats past its last entry -- the reference's stride arithmetic,
+    // mdl_interface.glsl:343-349, finds its neighbour in the packed buffer there; here, as in the oracle, zeros.  Found by tests/fuzz_parity.py)
+    const size_t need = std::max(entries * stride, pv->data.size()) + 2u;
+    sceneData.insert(sceneData.end(), pv->data.begin(), pv->data.end());
+    sceneData.resize(mr.sdOffset[slot] + need, 0.0f);
+  }
+  meshRecs.push_back(mr);
+}
+
+// TriRec::matFlags of a mesh bound to material `material` (record `mr`); adds the material to the scene's class masks and cutout flag, which the caller
+// has reset (buildScene and updateMaterials)
+static uint32_t meshMatFlags(GiCScene* s, const MaterialRec& mr, uint32_t material, const GiCMesh* m)
+{
+  const bool cutoutMat = mr.p[MP_CUTOUT] < 1.0f || (mr.flags & MAT_FLAG_OPACITY_TEX) != 0u;
+  if (cutoutMat) s->hasCutouts = true;
+  const uint32_t shadeClass = shadeClassOf(mr);
+  const uint32_t matFlags = material | (shadeClass << 24) | (cutoutMat ? (1u << 28) : 0u) | (((m->flipFacing ? 1u : 0u) | (m->doubleSided ? 2u : 0u)) << 30);
+  s->classMask |= 1u << (mr.klass & 0xfu); s->shadeClassMask |= 1u << shadeClass;
+  if (mr.flags & MAT_FLAG_TEXTURED) { s->classTextured |= 1u << (mr.klass & 0xfu); s->shadeClassTextured |= 1u << shadeClass; }
+  return matFlags;
+}
+
 // Two-level layout (SceneView::tlasNodes ...): built next to the flat BVH for instanced scenes that do not fit LDS.  The flat
 // arrays stay (k_shade reads the hit's TriRec, k_aov / giCTraceRays traverse them); the two-level ones are what k_trace_dyn2 walks,
 // and they are small: one BLAS per MESH instead of one subtree per instance, so traversal stays in the caches.
@@ -204,6 +278,30 @@ int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vec
   return GI_C_OK;
 }
 
+// Textures of one device: one device array per image + the TextureRec table.  An image the device already holds (GiCTexture::serial; texels never change
+// after giCCreateTexture) keeps its array, so a scene build or a material update sends only new images; arrays of textures that are gone are released.
+static int uploadTexturesTo(GiCScene* s, SceneDevice& D, hipStream_t st)
+{
+  std::vector<DeviceBuffer<float>*> old; old.swap(D.dTexels);
+  std::vector<uint64_t> oldSerial; oldSerial.swap(D.dTexelSerial);
+  std::vector<TextureRec> recs(s->textures.size());
+  int rc = GI_C_OK;
+  for (size_t i = 0; i < s->textures.size() && rc == GI_C_OK; i++) {
+    DeviceBuffer<float>* b = nullptr;
+    for (size_t k = 0; k < old.size(); k++) if (old[k] && oldSerial[k] == s->textures[i]->serial) { b = old[k]; old[k] = nullptr; break; }
+    const bool resident = b != nullptr;
+    if (!resident) b = new DeviceBuffer<float>();
+    D.dTexels.push_back(b); D.dTexelSerial.push_back(s->textures[i]->serial);
+    if (!resident && b->upload(s->textures[i]->rgba, st)) rc = GI_C_ERROR;
+    recs[i] = TextureRec{b->ptr, s->textures[i]->width, s->textures[i]->height};
+  }
+  // (the stream is drained first: a render that read the released arrays was synchronised by giCRender, an upload above may still be in flight)
+  if (rc == GI_C_OK && D.dTextures.upload(recs, st)) rc = GI_C_ERROR;
+  if (hipStreamSynchronize(st) != hipSuccess && rc == GI_C_OK) { setError("hipStreamSynchronize failed (texture upload)"); rc = GI_C_ERROR; } // `recs` goes out of scope
+  for (auto* b : old) if (b) { b->release(); delete b; }
+  return rc;
+}
+
 // ... and its upload into one device's memory (the primary's and every replica's: multi-device renders replicate the scene)
 int uploadSceneTo(GiCScene* s, SceneDevice& D, const SceneHost& H)
 {
@@ -219,19 +317,7 @@ int uploadSceneTo(GiCScene* s, SceneDevice& D, const SceneHost& H)
   if ((!H.deviceBuilt && D.dTriFaceId.upload(H.triFaceId, st)) || D.dTriShade.upload(H.triShade, st) || D.dTriGeomNormal.upload(H.triGeomNormal, st))
     return GI_C_ERROR;
   if (D.dMeshes.upload(H.meshRecs, st) || D.dSceneData.upload(H.sceneData, st)) return GI_C_ERROR;
-  { // textures: one device array per image + the TextureRec table
-    for (auto* b : D.dTexels) { b->release(); delete b; }
-    D.dTexels.clear();
-    std::vector<TextureRec> recs(s->textures.size());
-    for (size_t i = 0; i < s->textures.size(); i++) {
-      auto* b = new DeviceBuffer<float>();
-      D.dTexels.push_back(b);
-      if (b->upload(s->textures[i]->rgba, st)) return GI_C_ERROR;
-      recs[i] = TextureRec{b->ptr, s->textures[i]->width, s->textures[i]->height};
-    }
-    if (D.dTextures.upload(recs, st)) return GI_C_ERROR;
-    HIP_TRY(hipStreamSynchronize(st)); // `recs` goes out of scope
-  }
+  if (uploadTexturesTo(s, D, st) != GI_C_OK) return GI_C_ERROR;
   if (!H.deviceBuilt && (D.dNodes.upload(H.bvh.nodes, st) || D.dTris.upload(H.bvh.tris, st))) return GI_C_ERROR; // (device-built: the builder writes them)
   if (D.dInstances.upload(H.instances, st) || D.dVerts.upload(H.verts, st) || D.dMaterials.upload(H.mats, st)) return GI_C_ERROR;
   HIP_TRY(hipStreamSynchronize(st)); // host vectors may go out of scope
@@ -378,32 +464,8 @@ int buildScene(GiCScene* s)
   s->host.reset(); // (a failed build leaves no stale host copy behind)
   for (GiCMesh* m : s->meshes) { m->builtInstances = 0xffffffffu; m->xformDirty = false; m->instDirty.clear(); }
   std::vector<FVertex>& verts = H.verts; std::vector<InstanceRec>& instances = H.instances; std::vector<TriRec> tris; std::vector<int32_t> faceIdOf;
-  std::vector<MaterialRec>& mats = H.mats; mats.resize(s->materials.size());
-  for (size_t i = 0; i < s->materials.size(); i++) {
-    mats[i].klass = s->materials[i]->desc.klass; mats[i].flags = s->materials[i]->desc.flags & ~(MAT_FLAG_TEXTURED | MAT_FLAG_OPACITY_TEX);
-    for (uint32_t slot = 0; slot < TEX_SLOT_COUNT; slot++) {
-      const GiCTextureBinding& b = s->materials[i]->tex[slot];
-      TexBindingRec& r = mats[i].tex[slot];
-      r = TexBindingRec{};
-      auto tit = b.texture ? std::find(s->textures.begin(), s->textures.end(), b.texture) : s->textures.end();
-      if (tit == s->textures.end()) {
-        if (!s->materials[i]->primvarInput[slot].empty()) {
-          r.mode = TEX_MODE_PRIMVAR; mats[i].flags |= MAT_FLAG_TEXTURED;
-          // Frontend.cpp:251-252: named scene data answered from the UBO
-          if (s->materials[i]->primvarInput[slot] == "CAMERA_POSITION") r.mode |= TEX_MODE_CAMERA_POSITION;
-          if (s->materials[i]->primvarInput[slot] == "FRAME") r.mode |= TEX_MODE_FRAME;
-        }
-        continue;
-      }
-      r.tex = (uint32_t)(tit - s->textures.begin()) + 1u;
-      r.mode = (uint32_t)b.wrapS | ((uint32_t)b.wrapT << 8) | (((uint32_t)b.channel & 3u) << 16);
-      memcpy(r.scale, b.scale, 16); memcpy(r.bias, b.bias, 16);
-      if (s->materials[i]->hasTexXf[slot]) { r.mode |= TEX_MODE_XFORM; memcpy(r.xf, s->materials[i]->texXf[slot], sizeof(r.xf)); }
-      mats[i].flags |= slot == TEX_OPACITY ? MAT_FLAG_OPACITY_TEX : MAT_FLAG_TEXTURED; // opacity is looked up by the any-hit test, not by k_shade
-    }
-    memcpy(mats[i].p, s->materials[i]->desc.p, sizeof(float) * MAT_PARAM_COUNT);
-    deriveMaterialConstants(mats[i]);
-  }
+  std::vector<MaterialRec>& mats = H.mats;
+  buildMaterialRecords(s, mats);
   uint32_t meshIdx = 0;
   std::vector<MeshBuild>& meshBuilds = H.meshBuilds; // visible meshes in scene order (two-level layout, incremental updates)
   std::vector<MeshRec>& meshRecs = H.meshRecs; std::vector<float>& sceneData = H.sceneData;
@@ -415,39 +477,9 @@ int buildScene(GiCScene* s)
     if (mit == s->materials.end()) { fprintf(stderr, "[gatling_gi] invalid BLAS material for mesh %s\n", m->name.c_str()); continue; } // Gi.cpp:818-822
     const uint32_t material = (uint32_t)(mit - s->materials.begin());
     if (material > 0x00ffffffu) { setError("too many materials"); return GI_C_ERROR; }
-    const bool cutoutMat = mats[material].p[MP_CUTOUT] < 1.0f || (mats[material].flags & MAT_FLAG_OPACITY_TEX) != 0u;
-    if (cutoutMat) s->hasCutouts = true;
-    const uint32_t shadeClass = shadeClassOf(mats[material]);
-    const uint32_t matFlags = material | (shadeClass << 24) | (cutoutMat ? (1u << 28) : 0u) | (((m->flipFacing ? 1u : 0u) | (m->doubleSided ? 2u : 0u)) << 30);
-    s->classMask |= 1u << (mats[material].klass & 0xfu); s->shadeClassMask |= 1u << shadeClass;
-    if (mats[material].flags & MAT_FLAG_TEXTURED) { s->classTextured |= 1u << (mats[material].klass & 0xfu); s->shadeClassTextured |= 1u << shadeClass; }
+    const uint32_t matFlags = meshMatFlags(s, mats[material], material, m);
     const uint32_t vertexOffset = (uint32_t)verts.size();
-    { // scene data the mesh's material reads (Gi.cpp:905-1019): instancer primvars first, mesh primvars override, by name
-      MeshRec mr{}; mr.vertexOffset = vertexOffset;
-      for (uint32_t slot = 0; slot < TEX_SLOT_COUNT; slot++) {
-        const std::string& want = (*mit)->primvarInput[slot];
-        if (want.empty()) continue;
-        const GiCPrimvar* pv = nullptr;
-        for (const GiCPrimvar& p : m->instancerPrimvars) if (p.name == want && !p.data.empty()) { pv = &p; break; }
-        for (const GiCPrimvar& p : m->primvars) if (p.name == want && !p.data.empty()) { pv = &p; break; }
-        if (!pv) continue; // SCENE_DATA_INVALID
-        const bool isInt = pv->type > GI_C_PRIMVAR_VEC4; // Int .. Int4 (Gi.h:76-79)
-        const uint32_t stride = (uint32_t)(isInt ? pv->type - GI_C_PRIMVAR_INT : pv->type) + 1u;
-        size_t entries = 1; // what a lookup can index: zero-padded so that short arrays read 0 like the oracle
-        if (pv->interpolation == GI_C_INTERP_VERTEX) entries = m->vertices.size();
-        else if (pv->interpolation == GI_C_INTERP_UNIFORM) entries = m->faces.size();
-        else if (pv->interpolation == GI_C_INTERP_INSTANCE) { int32_t mx = (int32_t)(m->instanceTransforms.size() / 16) - 1;
-            for (int32_t id : m->instanceIds) mx = std::max(mx, id); entries = (size_t)std::max(mx, 0) + 1; }
-        mr.sdOffset[slot] = (uint32_t)sceneData.size();
-        mr.sdInfo[slot] = 1u | ((stride - 1u) << 1) | ((uint32_t)pv->interpolation << 3) | (isInt ? SD_INFO_INT : 0u);
-        // (+ 2: a three-component lookup of a one- or two-component primvar reads up to two floats past its last entry -- the reference's stride arithmetic,
-        // mdl_interface.glsl:343-349, finds its neighbour in the packed buffer there; here, as in the oracle, zeros.  Found by tests/fuzz_parity.py)
-        const size_t need = std::max(entries * stride, pv->data.size()) + 2u;
-        sceneData.insert(sceneData.end(), pv->data.begin(), pv->data.end());
-        sceneData.resize(mr.sdOffset[slot] + need, 0.0f);
-      }
-      meshRecs.push_back(mr);
-    }
+    appendMeshSceneData(m, *mit, vertexOffset, meshRecs, sceneData);
     for (const GiCVertex& vIn : m->vertices) { // Gi.cpp:848-861: quantise normal/tangent to octahedral unorm2x16, then decode once
       const GiCVertex v = usableShadingAttributes(vIn);
       FVertex fv; memcpy(fv.pos, v.pos, 12); fv.bsign = v.bitangentSign;
@@ -591,8 +623,9 @@ int buildScene(GiCScene* s)
 // over the subtree roots (buildTopBvh8: the roots are copied in as ordinary internal children) makes it one ordinary BVH8 again -- the traversal kernels, the
 // shading code and the triangle ids do not change, so images stay bit-identical to a full rebuild (traversal contract: results do not depend on the tree).
 // From then on moving an instance costs: its triangles re-transformed, its subtree rebuilt (a few thousand triangles), the top tree rebuilt (one item per
-// instance), and those ranges uploaded -- not a 10 M-triangle SAH build and a 0.7 GB upload.  Any other edit (geometry, materials, visibility, instance
-// counts) raises DIRTY_BVH and the next render rebuilds everything as one tree again.
+// instance), and those ranges uploaded -- not a 10 M-triangle SAH build and a 0.7 GB upload.  Material, assignment, texture and primvar edits have a path of
+// their own (updateMaterials below) that leaves the tree alone, partitioned or not.  Any other edit (geometry, visibility, instance counts and ids) raises
+// DIRTY_BVH and the next render rebuilds everything as one tree again.
 // ---------------------------------------------------------------------------------------------------------------
 void nodeBounds(const Node8& n, float box[6])
 {
@@ -756,22 +789,118 @@ int updateTransforms(GiCScene* s, bool& handled)
   return GI_C_OK;
 }
 
-// brings the device scene up to date with the host-side edits: incremental for transform-only edits, else a full build
+// ---------------------------------------------------------------------------------------------------------------
+// Incremental material updates.  An edit of a material, a material assignment, a texture binding or a primvar changes no vertex, box or triangle id: the
+// MaterialRec table, the texture table, the per-mesh scene data and ONE word per flattened triangle (TriRec::matFlags) change, and the scene flags derived
+// from them.  The small arrays are rebuilt by the functions buildScene uses and re-sent whole; the word is patched where it lives, in device memory
+// (gi_patch.hip k_patch_mat_flags) -- a device-built scene keeps no host copy of its triangles, and re-sending them would be the full upload again.
+// Covered: the flat layout in all its forms (host-built, device-built, partitioned) and the two-level layout (same flat triangles + InstTrav::matFlags, one
+// record per instance, re-sent).  Falls back to buildScene (handled = false, not an error): no host copy of the scene, fewer than 4096 triangles (as
+// updateTransforms), GATLING_OPTIONS=incremental=0, or the set of meshes in the scene changes -- a mesh that was left out for an invalid material gets a
+// valid one or the reverse (the scene-order ids of every later triangle shift).
+// ---------------------------------------------------------------------------------------------------------------
+int updateMaterials(GiCScene* s, bool& handled)
+{
+  handled = false;
+  if (!s->host || s->triCount < 4096u) return GI_C_OK; // small scenes rebuild in no time
+  if (!optionValue("incremental", 1)) return GI_C_OK;
+  SceneHost& H = *s->host;
+  const double t0 = nowMs();
+  { // the same meshes, in the same order, as the built scene holds?
+    size_t b = 0;
+    for (const GiCMesh* m : s->meshes) {
+      const bool inScene = m->visible && !m->faces.empty() && std::find(s->materials.begin(), s->materials.end(), m->material) != s->materials.end();
+      if (inScene != (m->builtInstances != 0xffffffffu)) return GI_C_OK;
+      if (!inScene) continue;
+      if (b >= H.meshBuilds.size() || H.meshBuilds[b].m != m || H.meshBuilds[b].instCount != m->builtInstances) return GI_C_OK;
+      b++;
+    }
+    if (b != H.meshBuilds.size() || H.meshRecs.size() != H.meshBuilds.size()) return GI_C_OK;
+  }
+  if (s->materials.size() > 0x01000000u) { setError("too many materials"); return GI_C_ERROR; }
+  // --- host: material records, scene data, every mesh's word, the scene's class masks
+  buildMaterialRecords(s, H.mats);
+  const bool hadCutouts = s->hasCutouts;
+  s->classMask = 0; s->hasCutouts = false; s->classTextured = 0; s->shadeClassMask = 0; s->shadeClassTextured = 0;
+  std::vector<MeshRec> meshRecs; std::vector<float> sceneData;
+  std::vector<uint32_t> wordOfMesh(H.meshBuilds.size(), 0u);
+  std::vector<uint8_t> changed(H.meshBuilds.size(), 0);
+  uint32_t meshesChanged = 0; uint64_t trisPatched = 0;
+  for (MeshBuild& mb : H.meshBuilds) {
+    const uint32_t material = (uint32_t)(std::find(s->materials.begin(), s->materials.end(), mb.m->material) - s->materials.begin());
+    const uint32_t word = meshMatFlags(s, H.mats[material], material, mb.m);
+    appendMeshSceneData(mb.m, mb.m->material, mb.vertexOffset, meshRecs, sceneData);
+    wordOfMesh[mb.meshIdx] = word;
+    if (word != mb.matFlags) { changed[mb.meshIdx] = 1; meshesChanged++; trisPatched += (uint64_t)mb.m->faces.size() * mb.instCount; mb.matFlags = word; }
+  }
+  H.meshRecs.swap(meshRecs); H.sceneData.swap(sceneData);
+  if (meshesChanged) {
+    // host copies of the triangles (host-built and partitioned trees, the two-level records): a later transform update uploads from them
+    for (TriRec& t : H.bvh.tris) { const uint32_t mesh = H.instances[t.instance].mesh; if (changed[mesh]) t.matFlags = wordOfMesh[mesh]; }
+    for (size_t i = 0; i < H.two.instTrav.size(); i++) H.two.instTrav[i].matFlags = wordOfMesh[H.instances[i].mesh];
+  }
+  if (s->hasCutouts != hadCutouts) { // the shadow walks' order was chosen for walks with / without the any-hit test: chosen anew
+    s->shadowOrder = -1; s->shadowOrderRays[0] = s->shadowOrderRays[1] = s->shadowOrderSteps[0] = s->shadowOrderSteps[1] = 0;
+  }
+  const double t1 = nowMs();
+  // --- every device of the scene, on its own stream: the small arrays, then the patch kernel
+  const uint32_t nDev = std::min<uint32_t>(sceneDeviceCount(s), (uint32_t)s->replicas.size() + 1u);
+  double textureMs = 0.0, patchMs = 0.0;
+  for (uint32_t d = 0; d < nDev; d++) {
+    SceneDevice& D = sceneDevice(s, d);
+    const DevCtx& ctx = g_ctx.devs[D.slot];
+    HIP_TRY(hipSetDevice(ctx.device));
+    hipStream_t st = ctx.stream;
+    const double ta = nowMs();
+    int rc = uploadTexturesTo(s, D, st);
+    const double tb = nowMs();
+    if (rc == GI_C_OK && (D.dMaterials.upload(H.mats, st) || D.dMeshes.upload(H.meshRecs, st) || D.dSceneData.upload(H.sceneData, st))) rc = GI_C_ERROR;
+    DeviceBuffer<uint32_t> dWords;
+    if (rc == GI_C_OK && meshesChanged) {
+      if (s->twoLevel && D.dInstTrav.upload(H.two.instTrav, st)) rc = GI_C_ERROR;
+      if (rc == GI_C_OK && D.dTris.count < s->triCount) { setError("internal: the device holds fewer triangles than the scene"); rc = GI_C_ERROR; }
+      if (rc == GI_C_OK && dWords.upload(wordOfMesh, st)) rc = GI_C_ERROR;
+      if (rc == GI_C_OK) launchPatchMatFlags(st, D.dTris.ptr, s->triCount, D.dInstances.ptr, (uint32_t)H.instances.size(), dWords.ptr, (uint32_t)wordOfMesh.size());
+    }
+    if (rc == GI_C_OK && (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) { setError("material update: device error"); rc = GI_C_ERROR; }
+    dWords.release();
+    if (rc != GI_C_OK) { (void)hipSetDevice(g_ctx.device); return GI_C_ERROR; }
+    textureMs += tb - ta; patchMs += nowMs() - tb;
+  }
+  HIP_TRY(hipSetDevice(g_ctx.device));
+  const double t2 = nowMs();
+  s->stats.bvhBuildMs = 0.0; s->stats.uploadMs = t2 - t0;
+  if (getenv("GATLING_BUILD_TIMING")) fprintf(stderr, "[gatling_gi] material update: %u mesh(es) with a new word of %zu, %llu triangle(s) patched, host %.2f ms, "
+                                              "device %.2f ms (texture table %.2f ms, other tables + patch kernel %.2f ms)\n", meshesChanged, H.meshBuilds.size(),
+                                              (unsigned long long)trisPatched, t1 - t0, t2 - t1, textureMs, patchMs);
+  handled = true;
+  return GI_C_OK;
+}
+
+// brings the device scene up to date with the host-side edits: incremental for material-only and transform-only edits (both may be due), else a full build
 int syncSceneGeometry(GiCScene* s)
 {
+  double materialMs = 0.0; // time of a material update that ran in front of a transform update: both go into the statistics
+  if ((s->dirty & DIRTY_MATERIALS) && !(s->dirty & DIRTY_BVH)) { // materials, assignments, textures, primvars: the small arrays + one word per triangle
+    bool handled = false;
+    s->generation++;
+    if (updateMaterials(s, handled) != GI_C_OK) { s->dirty |= DIRTY_BVH; return GI_C_ERROR; } // (half-updated arrays: the next render rebuilds)
+    if (handled) { s->dirty &= ~DIRTY_MATERIALS; s->updateCounts[2]++; materialMs = s->stats.uploadMs; } else s->dirty |= DIRTY_BVH;
+    s->dirty |= DIRTY_FRAMEBUFFER;
+  }
   if ((s->dirty & DIRTY_XFORM) && !(s->dirty & (DIRTY_BVH | DIRTY_MATERIALS))) { // only transforms changed: re-transform / re-braid those instances
     bool handled = false;
     s->generation++;
     if (updateTransforms(s, handled) != GI_C_OK) return GI_C_ERROR;
-    if (!handled) s->dirty |= DIRTY_BVH;
+    if (handled) { s->updateCounts[1]++; s->stats.uploadMs += materialMs; } else s->dirty |= DIRTY_BVH;
     s->dirty |= DIRTY_FRAMEBUFFER;
   }
   if (s->dirty & (DIRTY_BVH | DIRTY_MATERIALS)) {
     s->generation++;
     if (buildScene(s) != GI_C_OK) return GI_C_ERROR;
+    s->updateCounts[0]++;
     s->dirty &= ~(DIRTY_BVH | DIRTY_MATERIALS); s->dirty |= DIRTY_FRAMEBUFFER;
   }
   s->dirty &= ~DIRTY_XFORM;
   return GI_C_OK;
 }
-

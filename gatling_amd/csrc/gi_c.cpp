@@ -180,7 +180,7 @@ void SceneDevice::releaseAll()
   dNodes.release(); dTris.release(); dInstances.release(); dVerts.release(); dTriFaceId.release(); dTriShade.release(); dTriGeomNormal.release();
   dTlasNodes.release(); dBlasNodes.release(); dTlasItems.release(); dFlatOfOrig.release(); dBlasTris.release(); dInstTrav.release();
   for (auto* b : dTexels) { b->release(); delete b; }
-  dTexels.clear(); dTextures.release(); dMeshes.release(); dSceneData.release();
+  dTexels.clear(); dTexelSerial.clear(); dTextures.release(); dMeshes.release(); dSceneData.release();
   dMaterials.release(); dSphere.release(); dDistant.release(); dRect.release(); dDisk.release(); dRectFrames.release(); dDiskFrames.release();
   releasePathState(); scratchColor.release(); neeKey.release(); pathSegments.release(); accum.release();
   dCounters.release();

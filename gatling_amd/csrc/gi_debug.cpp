@@ -341,3 +341,74 @@ extern "C" int64_t giCDebugCheckSqrt(uint32_t first, uint64_t count)
   if (!ok) { setError("giCDebugCheckSqrt: device error"); return -1; }
   return (int64_t)h;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// giCDebugEditDirtyFlags / giCDebugSceneUpdateCounts: which edits take the incremental paths (host only)
+// ---------------------------------------------------------------------------------------------------------------
+// A scratch scene of one texture, two materials and one one-triangle mesh is made through the C ABI's own entry points; with `built` it is marked the way a
+// successful buildScene leaves it (a host copy, the mesh part of it, no dirty flag).  Then the one edit runs and the flags it raised are returned.  No device
+// is touched: the scene is never rendered.
+extern "C" int32_t giCDebugEditDirtyFlags(int32_t edit, int32_t built)
+{
+  std::unique_ptr<GiCScene> scene(new GiCScene());
+  GiCScene* s = scene.get();
+  const float texel[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+  GiCTextureDesc td{1u, 1u, texel};
+  GiCMaterialDesc md{}; md.klass = GI_C_MAT_USD_PREVIEW_SURFACE;
+  GiCVertex verts[3] = {}; verts[1].pos[0] = 1.0f; verts[2].pos[1] = 1.0f;
+  GiCFace face{}; face.v_i[0] = 0; face.v_i[1] = 1; face.v_i[2] = 2;
+  GiCMeshDesc meshDesc{}; meshDesc.faceCount = 1; meshDesc.faces = &face; meshDesc.vertexCount = 3; meshDesc.vertices = verts; meshDesc.name = "debug";
+  const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  GiCTexture* tex = giCCreateTexture(s, &td);
+  GiCMaterial* matA = giCCreateMaterial(s, "a", &md);
+  GiCMaterial* matB = giCCreateMaterial(s, "b", &md);
+  GiCMesh* mesh = giCCreateMesh(s, &meshDesc);
+  if (!tex || !matA || !matB || !mesh) return -1;
+  giCSetMeshInstanceTransforms(mesh, 1, identity);
+  giCSetMeshMaterial(mesh, matA);
+  if (built) { s->host.reset(new SceneHost()); mesh->builtInstances = 1; }
+  s->dirty = 0;
+  GiCMaterial* made = nullptr; GiCTexture* madeTex = nullptr; GiCMesh* madeMesh = nullptr;
+  GiCTextureBinding binding{}; binding.texture = tex; for (int i = 0; i < 4; i++) binding.scale[i] = 1.0f;
+  const float xf[6] = {1, 0, 0, 0, 1, 0};
+  const float one = 1.0f; const int32_t id = 7;
+  GiCPrimvarData pv{}; pv.name = "k"; pv.type = GI_C_PRIMVAR_FLOAT; pv.interpolation = GI_C_INTERP_CONSTANT; pv.data = &one; pv.dataSize = 4;
+  int32_t result = 0;
+  switch (edit) {
+    case 0: made = giCCreateMaterial(s, "c", &md); break;
+    case 1: giCDestroyMaterial(matB); matB = nullptr; break;
+    case 2: giCSetMeshMaterial(mesh, matB); break;
+    case 3: giCSetMaterialPrimvarInput(matA, GI_C_TEX_BASE_COLOR, "k"); break;
+    case 4: giCSetMaterialTexture(matA, GI_C_TEX_BASE_COLOR, &binding); break;
+    case 5: giCSetMaterialTextureTransform(matA, GI_C_TEX_BASE_COLOR, xf); break;
+    case 6: madeTex = giCCreateTexture(s, &td); break;
+    case 7: giCDestroyTexture(tex); tex = nullptr; break;
+    case 8: giCSetMeshPrimvars(mesh, 1, &pv); break;
+    case 9: giCSetMeshInstancerPrimvars(mesh, 1, &pv); break;
+    case 10: giCSetMeshTransform(mesh, identity); break;
+    case 11: giCSetMeshVisibility(mesh, 0); break;
+    case 12: giCSetMeshInstanceIds(mesh, 1, &id); break;
+    case 13: madeMesh = giCCreateMesh(s, &meshDesc); break;
+    case 14: giCDestroyMesh(mesh); mesh = nullptr; break;
+    case 15: giCSetMeshInstanceTransforms(mesh, 0, nullptr); break;
+    default: result = -1; break;
+  }
+  if (result == 0) result = (int32_t)s->dirty;
+  if (madeMesh) giCDestroyMesh(madeMesh);
+  if (mesh) giCDestroyMesh(mesh);
+  if (made) giCDestroyMaterial(made);
+  if (matA) giCDestroyMaterial(matA);
+  if (matB) giCDestroyMaterial(matB);
+  if (madeTex) giCDestroyTexture(madeTex);
+  if (tex) giCDestroyTexture(tex);
+  return result;
+}
+
+extern "C" int giCDebugSceneUpdateCounts(const GiCScene* scene, uint64_t* outCounts)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!s || !outCounts) { setError("giCDebugSceneUpdateCounts: bad arguments"); return GI_C_ERROR; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  for (int i = 0; i < 3; i++) outCounts[i] = s->updateCounts[i];
+  return GI_C_OK;
+}

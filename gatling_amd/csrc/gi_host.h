@@ -138,9 +138,12 @@ void deriveMaterialConstants(MaterialRec& m);
 // ---------------------------------------------------------------------------------------------------------------
 // DIRTY_XFORM: only transforms of meshes that are part of the built scene changed -- the incremental path (updateTransforms) handles it unless a full
 // rebuild is due anyway.  The reference keeps each mesh's BLAS and rebuilds the TLAS (Gi.cpp:1180-1202).
+// DIRTY_MATERIALS without DIRTY_BVH: materials, assignments, texture bindings or primvars of a built scene changed -- updateMaterials rebuilds the small
+// tables and patches TriRec::matFlags on the device; with DIRTY_BVH (or when that path declines) the scene is rebuilt.
 enum DirtyFlags : uint32_t { DIRTY_BVH = 1u, DIRTY_FRAMEBUFFER = 2u, DIRTY_LIGHTS = 4u, DIRTY_MATERIALS = 8u, DIRTY_ALL = 0xfu, DIRTY_XFORM = 16u };
 
-struct GiCTexture { GiCScene* scene; uint32_t width, height; std::vector<float> rgba; std::string cacheKey; uint32_t refs = 1; };
+struct GiCTexture { GiCScene* scene; uint32_t width, height; std::vector<float> rgba; std::string cacheKey; uint32_t refs = 1;
+    uint64_t serial = 0; /* unique per scene, never reused: names the image in a device's texel arrays (SceneDevice::dTexelSerial) */ };
 struct GiCPrimvar { std::string name; int32_t type, interpolation; std::vector<float> data; };
 struct GiCMaterial { GiCScene* scene; std::string name; GiCMaterialDesc desc; GiCTextureBinding tex[GI_C_TEX_SLOT_COUNT] = {};
     std::string primvarInput[GI_C_TEX_SLOT_COUNT];
@@ -231,6 +234,7 @@ struct SceneDevice {
   uint32_t slot = 0; // index into g_ctx.devs
   DeviceBuffer<MeshRec> dMeshes; DeviceBuffer<float> dSceneData;
   std::vector<DeviceBuffer<float>*> dTexels; DeviceBuffer<TextureRec> dTextures; // device copies (rebuilt with the materials)
+  std::vector<uint64_t> dTexelSerial; // GiCTexture::serial of the image dTexels[i] holds (gi_build.cpp uploadTexturesTo)
   DeviceBuffer<Node8> dNodes; DeviceBuffer<TriRec> dTris; DeviceBuffer<InstanceRec> dInstances;
   DeviceBuffer<FVertex> dVerts; DeviceBuffer<MaterialRec> dMaterials; DeviceBuffer<int32_t> dTriFaceId; DeviceBuffer<TriShade> dTriShade;
       DeviceBuffer<F4> dTriGeomNormal;
@@ -298,6 +302,7 @@ struct GiCScene : SceneDevice {
   std::vector<GiCMesh*> meshes;       // creation order (deterministic triangle ids; the reference uses an unordered_set)
   std::vector<GiCMaterial*> materials;
   std::vector<GiCTexture*> textures;  // creation order
+  uint64_t nextTextureSerial = 1;
   DenseStore<SphereLightRec, GiCSphereLight> sphereLights;
   DenseStore<DistantLightRec, GiCDistantLight> distantLights;
   DenseStore<RectLightRec, GiCRectLight> rectLights;
@@ -342,9 +347,10 @@ struct GiCScene : SceneDevice {
   // devices the previous giCRender used: progressive accumulation blends against each device's own buffer, so a change restarts it
   uint32_t lastRenderDevices = 0;
   int32_t optLookahead = 0; // GI_C_SCENE_OPTION_SAMPLE_LOOKAHEAD: calls a look-ahead window may hold; 0 = off
-  // contents of the device arrays: bumped by every scene build, transform update and light upload (materials, textures and primvars travel with the build) --
+  // contents of the device arrays: bumped by every scene build, transform update, material update and light upload --
   // a look-ahead window traced under another generation is not served from
   uint64_t generation = 0;
+  uint64_t updateCounts[3] = {0, 0, 0}; // syncSceneGeometry: full builds, incremental transform updates, incremental material updates (giCDebugSceneUpdateCounts)
 };
 
 
@@ -361,6 +367,8 @@ uint32_t sceneDeviceCount(const GiCScene* s);                // devices a render
 SceneDevice& sceneDevice(GiCScene* s, uint32_t slot);
 void nodeBounds(const Node8& n, float box[6]);               // dequantised bounds of a node's children (+ an ulp-scale pad)
 int syncSceneGeometry(GiCScene* s);                          // brings the device scene up to date with the host-side edits (incremental or full build)
+// dirty flags of a material-side edit: DIRTY_MATERIALS alone once the scene / the mesh is part of a built scene (the incremental path), else with DIRTY_BVH
+inline uint32_t materialEditFlags(bool built) { return DIRTY_MATERIALS | DIRTY_FRAMEBUFFER | (built ? 0u : (uint32_t)DIRTY_BVH); }
 // gi_render.cpp
 SceneView makeView(GiCScene* s, SceneDevice& D);
 SceneView makeView(GiCScene* s);

@@ -1,5 +1,5 @@
 // gi_kernels.h -- host-side launch interface of the stage kernels (gi_kernels.hip,
-// gi_trace.hip, gi_shade.hip, gi_aov.hip) and of the fused one (gi_path.hip).
+// gi_trace.hip, gi_shade.hip, gi_aov.hip, gi_patch.hip) and of the fused one (gi_path.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -46,6 +46,9 @@ int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool texture
 void launchAov(hipStream_t s, const FrameUniforms& U, const SceneView& sc, const AovTargets& A);
 void launchResolveNee(hipStream_t s, const FrameUniforms& U, const unsigned long long* key, F4* aov, uint32_t pixelCount);
 void launchZeroClosest(hipStream_t s, Counters* cnt, uint32_t par); // FLAG_TWO_STREAM: in front of every closest-hit launch
+// gi_patch.hip: rewrites TriRec::matFlags of the `triCount` device-resident triangles to wordOfMesh[instances[t.instance].mesh] where it differs
+void launchPatchMatFlags(hipStream_t s, TriRec* tris, uint32_t triCount, const InstanceRec* instances, uint32_t instanceCount, const uint32_t* wordOfMesh,
+    uint32_t meshCount);
 void launchSpin(hipStream_t s, unsigned long long ns);              // test hook: occupies a stream for ~ns nanoseconds
 void launchDebugBsdf(hipStream_t s, const MaterialRec* mat, uint32_t shadeClass, uint32_t count, const float* in, float* out);
 void launchDebugSqrt(hipStream_t s, uint32_t first, unsigned long long count, unsigned long long* mismatches); // gi_sqrt against sqrtf over bit patterns

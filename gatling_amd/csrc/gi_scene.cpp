@@ -42,7 +42,7 @@ GiCMaterial* giCCreateMaterial(GiCScene* scene, const char* name, const GiCMater
   // to the front ends, which set OpenPBR's defaults themselves: gtl_shim.cpp -- ADVICE r05)
   std::lock_guard<std::mutex> g(scene->mutex);
   scene->materials.push_back(m);
-  scene->dirty |= DIRTY_MATERIALS | DIRTY_BVH | DIRTY_FRAMEBUFFER;
+  scene->dirty |= materialEditFlags(scene->host != nullptr); // (material indices shift: the per-triangle word is patched, nothing is rebuilt)
   return m;
 }
 
@@ -54,7 +54,7 @@ void giCDestroyMaterial(GiCMaterial* mat)
     std::lock_guard<std::mutex> g(s->mutex);
     s->materials.erase(std::remove(s->materials.begin(), s->materials.end(), mat), s->materials.end());
     for (GiCMesh* m : s->meshes) if (m->material == mat) m->material = nullptr;
-    s->dirty |= DIRTY_MATERIALS | DIRTY_BVH | DIRTY_FRAMEBUFFER;
+    s->dirty |= materialEditFlags(s->host != nullptr); // (a mesh left without a material drops out of the scene: updateMaterials sees it and rebuilds)
   }
   delete mat;
 }
@@ -129,7 +129,9 @@ void giCSetMeshMaterial(GiCMesh* mesh, GiCMaterial* mat)
   if (!mesh) return;
   std::lock_guard<std::mutex> g(mesh->scene->mutex);
   mesh->material = mat;
-  mesh->scene->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER;
+  // a mesh of the built scene keeps its triangles: only their material word changes.  One that is not part of it (new, invisible, left out for an invalid
+  // material) may enter the scene now: rebuild
+  mesh->scene->dirty |= mesh->builtInstances != 0xffffffffu ? materialEditFlags(true) : (DIRTY_BVH | DIRTY_FRAMEBUFFER);
 }
 
 void giCSetMeshVisibility(GiCMesh* mesh, int32_t visible)
@@ -175,7 +177,8 @@ static int setPrimvarsImpl(GiCMesh* mesh, std::vector<GiCPrimvar>& dst, uint32_t
   }
   std::lock_guard<std::mutex> g(mesh->scene->mutex);
   dst = std::move(v);
-  mesh->scene->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER; // Gi.cpp:685-700
+  // Gi.cpp:685-700; primvars feed the per-mesh scene data, not the tree
+  mesh->scene->dirty |= mesh->builtInstances != 0xffffffffu ? materialEditFlags(true) : (DIRTY_BVH | DIRTY_FRAMEBUFFER);
   return GI_C_OK;
 }
 int giCSetMeshPrimvars(GiCMesh* mesh, uint32_t count, const GiCPrimvarData* pv) { return mesh
@@ -188,7 +191,7 @@ int giCSetMaterialPrimvarInput(GiCMaterial* mat, int32_t input, const char* name
       || input == GI_C_TEX_COAT_NORMAL) { setError("giCSetMaterialPrimvarInput: bad arguments"); return GI_C_ERROR; }
   std::lock_guard<std::mutex> g(mat->scene->mutex);
   mat->primvarInput[input] = name ? name : "";
-  mat->scene->dirty |= DIRTY_MATERIALS | DIRTY_BVH | DIRTY_FRAMEBUFFER;
+  mat->scene->dirty |= materialEditFlags(mat->scene->host != nullptr);
   return GI_C_OK;
 }
 

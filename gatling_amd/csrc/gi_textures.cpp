@@ -18,6 +18,7 @@ static GiCTexture* createTextureImpl(GiCScene* scene, const GiCTextureDesc* desc
   std::unique_ptr<GiCTexture> t(new GiCTexture{scene, desc->width, desc->height,
       std::vector<float>(desc->rgba, desc->rgba + (size_t)desc->width * desc->height * 4)});
   std::lock_guard<std::mutex> g(scene->mutex);
+  t->serial = scene->nextTextureSerial++;
   scene->textures.push_back(t.get());
   scene->dirty |= DIRTY_MATERIALS | DIRTY_FRAMEBUFFER;
   return t.release();
@@ -137,7 +138,7 @@ void giCDestroyTexture(GiCTexture* tex)
     if (--tex->refs != 0u) return; // shared file texture still in use
     s->textures.erase(std::remove(s->textures.begin(), s->textures.end(), tex), s->textures.end());
     for (GiCMaterial* m : s->materials) for (auto& b : m->tex) if (b.texture == tex) b.texture = nullptr;
-    s->dirty |= DIRTY_MATERIALS | DIRTY_BVH | DIRTY_FRAMEBUFFER;
+    s->dirty |= materialEditFlags(s->host != nullptr);
   }
   delete tex;
 }
@@ -151,7 +152,7 @@ int giCSetMaterialTexture(GiCMaterial* mat, int32_t input, const GiCTextureBindi
       return GI_C_ERROR; }
   std::lock_guard<std::mutex> g(mat->scene->mutex);
   if (binding) mat->tex[input] = *binding; else mat->tex[input] = GiCTextureBinding{};
-  mat->scene->dirty |= DIRTY_MATERIALS | DIRTY_BVH | DIRTY_FRAMEBUFFER;
+  mat->scene->dirty |= materialEditFlags(mat->scene->host != nullptr);
   return GI_C_OK;
 }
 
@@ -161,7 +162,7 @@ int giCSetMaterialTextureTransform(GiCMaterial* mat, int32_t input, const float*
   std::lock_guard<std::mutex> g(mat->scene->mutex);
   mat->hasTexXf[input] = xf != nullptr;
   if (xf) memcpy(mat->texXf[input], xf, sizeof(float) * 6);
-  mat->scene->dirty |= DIRTY_MATERIALS | DIRTY_BVH | DIRTY_FRAMEBUFFER;
+  mat->scene->dirty |= materialEditFlags(mat->scene->host != nullptr);
   return GI_C_OK;
 }
 

@@ -395,6 +395,14 @@ GiCMesh* giCCreateMesh(GiCScene* scene, const GiCMeshDesc* desc);
 void giCSetMeshTransform(GiCMesh* mesh, const float* mat4x4);
 void giCSetMeshInstanceTransforms(GiCMesh* mesh, uint32_t count, const float* transforms /* count x 16 */);
 void giCSetMeshInstanceIds(GiCMesh* mesh, uint32_t count, const int32_t* ids);
+/* [ext] Material-side edits of a scene that has been rendered do not rebuild it: giCCreateMaterial / giCDestroyMaterial, giCSetMeshMaterial on a mesh that is part
+ * of the scene, giCSetMaterialPrimvarInput, giCSetMaterialTexture / TextureTransform, giCCreateTexture / giCDestroyTexture and giCSetMesh(Instancer)Primvars
+ * change the material, texture and scene-data tables and one word per flattened triangle, which the next giCRender patches in device memory (flat and two-level
+ * layouts, host- or device-built, partitioned or not; GiCRenderStats.bvhBuildMs = 0, uploadMs = the update).  Measured on the
+ * 10.24 M-triangle interior (config C5): full build 2 235 + 919 ms, a colour-only replacement of one material 19.7 ms, re-assigning a 40 960-triangle mesh 17.1 ms.
+ * The next render rebuilds instead when the scene has fewer than 4096 triangles, when an edit changes WHICH meshes are in the scene (a mesh loses its material --
+ * NULL or destroyed -- or one that was left out gets a valid one), with GATLING_OPTIONS=incremental=0, and for every geometry-side edit (mesh creation /
+ * destruction, visibility, instance counts and ids). */
 void giCSetMeshMaterial(GiCMesh* mesh, GiCMaterial* mat);
 void giCSetMeshVisibility(GiCMesh* mesh, int32_t visible);
 void giCDestroyMesh(GiCMesh* mesh);
@@ -551,6 +559,17 @@ int giCDebugValidatePartitionedBvh(const float* triVerts, uint32_t triCount, uin
  * device builder made it; outDigest: a 64-bit hash of the node and triangle bytes.  Returns the number of violations, <0 on error. */
 int giCDebugValidateSceneBvh(const GiCScene* scene, uint32_t deviceIndex, uint32_t* outNodeCount, uint32_t* outMaxDepth, int32_t* outBuiltOnDevice,
                              uint64_t* outDigest);
+
+/* [ext] host-only: the dirty flags ONE edit raises on a scratch scene (one texture, two materials, one mesh; no device is touched), before the scene's first build
+ * (`built` = 0) or after it (`built` = 1).  Flags: 1 full rebuild, 2 framebuffer reset, 4 lights, 8 materials, 16 transforms; materials or transforms WITHOUT
+ * the rebuild bit take the incremental paths (see giCSetMeshMaterial).  `edit`: 0 giCCreateMaterial, 1 giCDestroyMaterial, 2 giCSetMeshMaterial,
+ * 3 giCSetMaterialPrimvarInput, 4 giCSetMaterialTexture, 5 giCSetMaterialTextureTransform, 6 giCCreateTexture, 7 giCDestroyTexture, 8 giCSetMeshPrimvars,
+ * 9 giCSetMeshInstancerPrimvars, 10 giCSetMeshTransform, 11 giCSetMeshVisibility, 12 giCSetMeshInstanceIds, 13 giCCreateMesh, 14 giCDestroyMesh,
+ * 15 giCSetMeshInstanceTransforms with another instance count.  <0 on error. */
+int32_t giCDebugEditDirtyFlags(int32_t edit, int32_t built);
+/* [ext] how often the scene's geometry was brought up to date by outCounts[0] a full build, [1] an incremental transform update, [2] an incremental material
+ * update, since the scene was created. */
+int giCDebugSceneUpdateCounts(const GiCScene* scene, uint64_t* outCounts /* 3 */);
 
 #ifdef __cplusplus
 }
