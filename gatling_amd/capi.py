@@ -23,6 +23,7 @@ AOV_COLOR = 0
 FORMAT_INT32, FORMAT_FLOAT32, FORMAT_FLOAT32_VEC4 = 0, 1, 2
 OPTION_COUNT_TRAVERSAL, OPTION_KERNEL_TIMERS, OPTION_POOL_SLOTS, OPTION_SAMPLE_BUFFER_MB, OPTION_TRACE_DYNAMIC, OPTION_TWO_LEVEL, OPTION_FUSED_PATH, OPTION_DEVICES = 1, 2, 3, 4, 5, 6, 7, 8
 OPTION_SAMPLE_LOOKAHEAD = 10  # N >= 2: a progressive call may trace the samples of up to N calls in one batch (include/gi_c.h); 0 / 1 = off (default)
+OPTION_VISIBILITY_UPDATES = 11  # 1: visibility edits of meshes of the built scene are applied to the resident scene instead of rebuilding it (include/gi_c.h); 0 = off (default)
 OPTION_BVH_BUILD = 9  # 0 = host BVH builder (default), 1 = device builder (flat-layout scenes of more than 128 triangles)
 
 
@@ -160,6 +161,7 @@ SYMBOLS = [
     ("giCDebugValidateSceneBvh", C.c_int, [_P, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     ("giCDebugTexRuntime", C.c_int, [_FP, _U, _U, _U, _U, _FP, _FP]),
     ("giCDebugEditDirtyFlags", C.c_int32, [_I, _I]), ("giCDebugSceneUpdateCounts", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("giCDebugSceneVisibilityUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]),
 ]
 
 _lib = None
@@ -424,7 +426,7 @@ class Scene:
         self._set_primvars(self.L.giCSetMeshInstancerPrimvars, self.meshes[mesh_index], list(primvars))
 
     def set_mesh_visibility(self, mesh_index: int, visible: bool):
-        """giSetMeshVisibility (Gi.h:216): a geometry-side edit, the next render rebuilds the scene."""
+        """giSetMeshVisibility (Gi.h:216): a geometry-side edit, the next render rebuilds the scene -- or, with OPTION_VISIBILITY_UPDATES, updates it in place."""
         self.desc.meshes[mesh_index].visible = bool(visible)
         self.L.giCSetMeshVisibility(self.meshes[mesh_index], int(bool(visible)))
 
@@ -434,6 +436,13 @@ class Scene:
         if self.L.giCDebugSceneUpdateCounts(self.handle, c) != GI_C_OK:
             raise GiError("giCDebugSceneUpdateCounts failed")
         return {"full": int(c[0]), "transform": int(c[1]), "material": int(c[2])}
+
+    def visibility_update_count(self) -> int:
+        """giCDebugSceneVisibilityUpdateCount: how often the scene was brought up to date by an incremental visibility update (not counted by update_counts)."""
+        n = C.c_uint64(0)
+        if self.L.giCDebugSceneVisibilityUpdateCount(self.handle, C.byref(n)) != GI_C_OK:
+            raise GiError("giCDebugSceneVisibilityUpdateCount failed")
+        return int(n.value)
 
     def set_option(self, option: int, value: int):
         if self.L.giCSetSceneOption(self.handle, option, value) != GI_C_OK:

@@ -462,7 +462,7 @@ int buildScene(GiCScene* s)
   std::unique_ptr<SceneHost> hostPtr(new SceneHost());
   SceneHost& H = *hostPtr;
   s->host.reset(); // (a failed build leaves no stale host copy behind)
-  for (GiCMesh* m : s->meshes) { m->builtInstances = 0xffffffffu; m->xformDirty = false; m->instDirty.clear(); }
+  for (GiCMesh* m : s->meshes) { m->builtInstances = 0xffffffffu; m->xformDirty = false; m->instDirty.clear(); m->visToggled = false; }
   std::vector<FVertex>& verts = H.verts; std::vector<InstanceRec>& instances = H.instances; std::vector<TriRec> tris; std::vector<int32_t> faceIdOf;
   std::vector<MaterialRec>& mats = H.mats;
   buildMaterialRecords(s, mats);
@@ -504,6 +504,7 @@ int buildScene(GiCScene* s)
     size_t instCount = m->instanceTransforms.size() / 16;
     m->builtInstances = (uint32_t)instCount;
     meshBuilds.push_back(MeshBuild{m, vertexOffset, matFlags, (uint32_t)instances.size(), (uint32_t)instCount, (uint32_t)tris.size(), meshIdx, meshFaceIdAov});
+    meshBuilds.back().idBase = meshBuilds.back().triFirst;
     for (size_t ii = 0; ii < instCount; ii++) { // Gi.cpp:1188-1202
       InstanceRec ir{};
       composeTransform(m->transform, &m->instanceTransforms[16 * ii], ir.o2w);
@@ -624,8 +625,9 @@ int buildScene(GiCScene* s)
 // shading code and the triangle ids do not change, so images stay bit-identical to a full rebuild (traversal contract: results do not depend on the tree).
 // From then on moving an instance costs: its triangles re-transformed, its subtree rebuilt (a few thousand triangles), the top tree rebuilt (one item per
 // instance), and those ranges uploaded -- not a 10 M-triangle SAH build and a 0.7 GB upload.  Material, assignment, texture and primvar edits have a path of
-// their own (updateMaterials below) that leaves the tree alone, partitioned or not.  Any other edit (geometry, visibility, instance counts and ids) raises
-// DIRTY_BVH and the next render rebuilds everything as one tree again.
+// their own (updateMaterials below) that leaves the tree alone, partitioned or not, and so have -- opt-in -- visibility edits (updateVisibility below: ids
+// renumbered in place; a partitioned tree leaves the parts of hidden meshes out of its top tree).  Any other edit (geometry, instance counts and ids, and
+// visibility without the option) raises DIRTY_BVH and the next render rebuilds everything as one tree again.
 // ---------------------------------------------------------------------------------------------------------------
 void nodeBounds(const Node8& n, float box[6])
 {
@@ -674,7 +676,9 @@ void placePart(SceneHost& H, InstPart& P, const PartBuild& B)
   for (uint32_t k = 0; k < P.nf; k++) {
     TriRec t = B.bvh.tris[k];
     H.triFaceId[P.triFirst + k] = mb.faceIdAov[t.prim];
-    t.origId += P.triFirst; // scene-order id: the instance's triangles are numbered in face order from triFirst, as in buildScene
+    // scene-order id: the instance's triangles are numbered in face order, as in buildScene -- from triFirst, or from where a fresh build of the visible
+    // meshes would start it once meshes in front of it are hidden (updateVisibility)
+    t.origId += mb.idBase + P.instInMesh * P.nf;
     H.bvh.tris[P.triFirst + k] = t;
   }
   H.instances[mb.instFirst + P.instInMesh] = B.inst;
@@ -698,7 +702,9 @@ int rebuildTop(GiCScene* s, SceneHost& H)
   std::vector<float> boxes(H.parts.size() * 6); std::vector<Node8> roots(H.parts.size());
   uint32_t subDepth = 0;
   for (size_t i = 0; i < H.parts.size(); i++) { memcpy(&boxes[6 * i], H.parts[i].box, 24); roots[i] = H.bvh.nodes[H.parts[i].nodeOff];
-      subDepth = std::max(subDepth, H.parts[i].depth); }
+      subDepth = std::max(subDepth, H.parts[i].depth);
+      // the parts of a hidden mesh (updateVisibility) keep their ranges and stay out of the top tree, like a part whose triangles are all inactive
+      if (H.meshBuilds[H.parts[i].meshBuild].hidden) for (int a = 0; a < 3; a++) { boxes[6 * i + a] = 3.0e38f; boxes[6 * i + 3 + a] = -3.0e38f; } }
   Bvh8 top;
   buildTopBvh8(boxes.data(), H.parts.size(), roots.data(), top);
   if (top.nodes.size() > H.topCap) { setError("internal: top tree larger than its reserved range"); return GI_C_ERROR; }
@@ -809,7 +815,9 @@ int updateMaterials(GiCScene* s, bool& handled)
   { // the same meshes, in the same order, as the built scene holds?
     size_t b = 0;
     for (const GiCMesh* m : s->meshes) {
-      const bool inScene = m->visible && !m->faces.empty() && std::find(s->materials.begin(), s->materials.end(), m->material) != s->materials.end();
+      // (a mesh hidden by updateVisibility is still part of the resident scene: its word is patched like any other)
+      const bool hiddenInScene = b < H.meshBuilds.size() && H.meshBuilds[b].m == m && H.meshBuilds[b].hidden;
+      const bool inScene = (m->visible || hiddenInScene) && !m->faces.empty() && std::find(s->materials.begin(), s->materials.end(), m->material) != s->materials.end();
       if (inScene != (m->builtInstances != 0xffffffffu)) return GI_C_OK;
       if (!inScene) continue;
       if (b >= H.meshBuilds.size() || H.meshBuilds[b].m != m || H.meshBuilds[b].instCount != m->builtInstances) return GI_C_OK;
@@ -828,7 +836,10 @@ int updateMaterials(GiCScene* s, bool& handled)
   uint32_t meshesChanged = 0; uint64_t trisPatched = 0;
   for (MeshBuild& mb : H.meshBuilds) {
     const uint32_t material = (uint32_t)(std::find(s->materials.begin(), s->materials.end(), mb.m->material) - s->materials.begin());
+    const uint32_t masks[4] = {s->classMask, s->classTextured, s->shadeClassMask, s->shadeClassTextured}; const bool cutouts = s->hasCutouts;
     const uint32_t word = meshMatFlags(s, H.mats[material], material, mb.m);
+    if (mb.hidden) { s->classMask = masks[0]; s->classTextured = masks[1]; s->shadeClassMask = masks[2]; s->shadeClassTextured = masks[3];
+        s->hasCutouts = cutouts; } // (a hidden mesh launches no kernel variant, as in a fresh build without it)
     appendMeshSceneData(mb.m, mb.m->material, mb.vertexOffset, meshRecs, sceneData);
     wordOfMesh[mb.meshIdx] = word;
     if (word != mb.matFlags) { changed[mb.meshIdx] = 1; meshesChanged++; trisPatched += (uint64_t)mb.m->faces.size() * mb.instCount; mb.matFlags = word; }
@@ -877,22 +888,149 @@ int updateMaterials(GiCScene* s, bool& handled)
   return GI_C_OK;
 }
 
-// brings the device scene up to date with the host-side edits: incremental for material-only and transform-only edits (both may be due), else a full build
+// ---------------------------------------------------------------------------------------------------------------
+// Incremental visibility updates (opt-in: GI_C_SCENE_OPTION_VISIBILITY_UPDATES / GATLING_OPTIONS=visibility_updates=1).  Hiding a mesh of the built scene
+// changes no tree, vertex or shading record.  Its triangles must stop being hit, and the triangles of the meshes behind it in scene order get the ids a
+// fresh build -- which leaves invisible meshes out (Gi.cpp:801-804) -- would give them: the cutout test hashes that id and the tie-break orders by it.  Both
+// are one pass over the resident triangle records (gi_patch.hip k_patch_visibility) driven by a table with one entry per flattened instance.
+//   flat layouts (host-built, device-built): the records of a hidden instance get zero edges, which no walk accepts, and are recomputed at the show.  The
+//       tree keeps the boxes of the hidden geometry until the next full build: walks still descend into them and reject the triangles.
+//   partitioned layout: the parts of a hidden mesh are left out of the top tree (rebuildTop) and their records are left alone; only ids are renumbered.
+// MeshBuild::hidden / idBase hold the state; updateTransforms and updateMaterials respect it, so a hide composes with a move and a material edit, before
+// the same render too.  Falls back to buildScene (handled = false, not an error): no host copy of the scene, GATLING_OPTIONS=incremental=0, the two-level
+// layout (SceneView::flatOfOrig is indexed by the ids this renumbers), a toggled mesh that is not part of the built scene (it was invisible or had no valid
+// material when the scene was built: it has no records on the device), fewer than 4096 visible flattened triangles after the edit (every mesh hidden
+// included).  The caller has established that nothing but visibility toggles asked for the rebuild.
+// ---------------------------------------------------------------------------------------------------------------
+static bool visibilityUpdatesWanted(const GiCScene* s)
+{
+  const long o = optionValue("visibility_updates", -1);
+  return o >= 0 ? o == 1 : s->optVisibilityUpdates == 1;
+}
+
+int updateVisibility(GiCScene* s, bool& handled)
+{
+  handled = false;
+  if (!s->host || s->twoLevel || !s->host->shadePacked) return GI_C_OK;
+  if (!optionValue("incremental", 1)) return GI_C_OK;
+  SceneHost& H = *s->host;
+  const double t0 = nowMs();
+  for (const GiCMesh* m : s->meshes) if (m->visToggled && m->builtInstances == 0xffffffffu) return GI_C_OK; // no records on the device: showing it rebuilds
+  // --- per instance: the id base a fresh build of the visible meshes gives it against the one the resident records hold, and what happens to its records
+  std::vector<VisPatch> patch(H.instances.size(), VisPatch{0, VIS_KEEP});
+  std::vector<uint32_t> newBase(H.meshBuilds.size(), 0u);
+  uint64_t visibleTris = 0; uint32_t hides = 0, shows = 0, renumbered = 0; bool launch = false;
+  for (const MeshBuild& mb : H.meshBuilds) {
+    if (mb.m->builtInstances != mb.instCount) return GI_C_OK; // (cannot happen: count changes ask for the rebuild)
+    const bool hide = !mb.m->visible;
+    // (the ids of a hidden mesh are never read: they stay what they are until it is shown)
+    newBase[mb.meshIdx] = hide ? mb.idBase : (uint32_t)visibleTris;
+    if (!hide) visibleTris += (uint64_t)mb.instCount * mb.m->faces.size();
+  }
+  if (visibleTris < 4096u) return GI_C_OK; // as updateTransforms / updateMaterials: small scenes rebuild in no time (and must stay LDS-resident)
+  for (const MeshBuild& mb : H.meshBuilds) {
+    const bool hide = !mb.m->visible;
+    const int32_t delta = (int32_t)(newBase[mb.meshIdx] - mb.idBase);
+    // a partitioned tree drops the parts from its top tree: their records stay whole
+    const uint32_t action = hide == mb.hidden || H.partitioned ? VIS_KEEP : (hide ? VIS_HIDE : VIS_SHOW);
+    if (hide != mb.hidden) { if (hide) hides++; else shows++; }
+    if (delta != 0) renumbered++;
+    if (delta != 0 || action != VIS_KEEP) { launch = true; for (uint32_t ii = 0; ii < mb.instCount; ii++) patch[mb.instFirst + ii] = VisPatch{delta, action}; }
+  }
+  // --- host: the triangles' host copies where they exist (host-built and partitioned trees; a later transform update uploads from them), the top tree of a
+  // partitioned scene, the class masks and the cutout flag over the visible meshes
+  if (launch && !H.bvh.tris.empty()) {
+    constexpr size_t CHUNK = 65536;
+    const size_t n = H.bvh.tris.size();
+    parallelOver((n + CHUNK - 1) / CHUNK, [&](size_t c) {
+      for (size_t i = c * CHUNK; i < std::min(n, (c + 1) * CHUNK); i++) {
+        TriRec& t = H.bvh.tris[i];
+        const VisPatch vp = patch[t.instance];
+        t.origId += (uint32_t)vp.idDelta;
+        if (vp.action == VIS_HIDE) for (int a = 0; a < 3; a++) { t.e1[a] = 0.0f; t.e2[a] = 0.0f; }
+        else if (vp.action == VIS_SHOW) {
+          const InstanceRec& ir = H.instances[t.instance];
+          TriRec whole; flattenTriangle(ir, true, H.meshBuilds[ir.mesh].m, t.prim, whole); // (meshBuilds[i].meshIdx == i)
+          memcpy(t.e1, whole.e1, 12); memcpy(t.e2, whole.e2, 12);
+        }
+      }
+    });
+  }
+  for (MeshBuild& mb : H.meshBuilds) { mb.hidden = !mb.m->visible; mb.idBase = newBase[mb.meshIdx]; }
+  const bool topChanged = H.partitioned && (hides || shows);
+  if (topChanged) {
+    if (rebuildTop(s, H) != GI_C_OK) return GI_C_ERROR;
+    setSceneBounds(s, H.bvh.nodes);
+  }
+  const bool hadCutouts = s->hasCutouts;
+  s->classMask = 0; s->hasCutouts = false; s->classTextured = 0; s->shadeClassMask = 0; s->shadeClassTextured = 0;
+  for (const MeshBuild& mb : H.meshBuilds) {
+    const uint32_t material = mb.matFlags & 0x00ffffffu; // (the table of the last sync; a material edit that is due as well runs behind this update)
+    if (!mb.hidden && material < H.mats.size()) (void)meshMatFlags(s, H.mats[material], material, mb.m);
+  }
+  if (s->hasCutouts != hadCutouts) { // the shadow walks' order was chosen for walks with / without the any-hit test: chosen anew
+    s->shadowOrder = -1; s->shadowOrderRays[0] = s->shadowOrderRays[1] = s->shadowOrderSteps[0] = s->shadowOrderSteps[1] = 0;
+  }
+  const double t1 = nowMs();
+  // --- every device of the scene, on its own stream: the table and the patch kernel, the top tree of a partitioned scene.  Nothing when no word changes
+  const uint32_t nDev = std::min<uint32_t>(sceneDeviceCount(s), (uint32_t)s->replicas.size() + 1u);
+  for (uint32_t d = 0; d < nDev && (launch || topChanged); d++) {
+    SceneDevice& D = sceneDevice(s, d);
+    const DevCtx& ctx = g_ctx.devs[D.slot];
+    HIP_TRY(hipSetDevice(ctx.device));
+    hipStream_t st = ctx.stream;
+    int rc = GI_C_OK;
+    DeviceBuffer<VisPatch> dPatch;
+    if (D.dTris.count < s->triCount || D.dInstances.count < H.instances.size() || D.dTriShade.count < H.triShade.size() || D.dNodes.count < H.topCap) {
+      setError("internal: the device holds less than the scene"); rc = GI_C_ERROR; }
+    if (rc == GI_C_OK && topChanged && hipMemcpyAsync(D.dNodes.ptr, H.bvh.nodes.data(), (size_t)H.topCap * sizeof(Node8), hipMemcpyHostToDevice, st)
+        != hipSuccess) { setError("visibility update: top tree upload failed"); rc = GI_C_ERROR; }
+    if (rc == GI_C_OK && launch) {
+      if (dPatch.upload(patch, st)) rc = GI_C_ERROR;
+      if (rc == GI_C_OK) launchPatchVisibility(st, D.dTris.ptr, s->triCount, D.dInstances.ptr, (uint32_t)H.instances.size(), dPatch.ptr, D.dTriShade.ptr,
+          (uint32_t)H.triShade.size());
+    }
+    if (rc == GI_C_OK && (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) { setError("visibility update: device error"); rc = GI_C_ERROR; }
+    dPatch.release();
+    if (rc != GI_C_OK) { (void)hipSetDevice(g_ctx.device); return GI_C_ERROR; }
+  }
+  HIP_TRY(hipSetDevice(g_ctx.device));
+  const double t2 = nowMs();
+  // (triangleCount / nodeCount keep describing what is resident on the device, hidden triangles included: include/gi_c.h)
+  s->stats.bvhBuildMs = 0.0; s->stats.uploadMs = t2 - t0;
+  if (getenv("GATLING_BUILD_TIMING")) fprintf(stderr, "[gatling_gi] visibility update: %u mesh(es) hidden, %u shown, %u renumbered of %zu, %llu visible "
+                                              "triangle(s) of %u resident, host %.2f ms, device %.2f ms\n", hides, shows, renumbered, H.meshBuilds.size(),
+                                              (unsigned long long)visibleTris, s->triCount, t1 - t0, t2 - t1);
+  handled = true;
+  return GI_C_OK;
+}
+
+// brings the device scene up to date with the host-side edits: incremental for visibility-only (opt-in), material-only and transform-only edits (all three
+// may be due, and run in this order), else a full build
 int syncSceneGeometry(GiCScene* s)
 {
-  double materialMs = 0.0; // time of a material update that ran in front of a transform update: both go into the statistics
+  double materialMs = 0.0; // time of the updates that ran in front of another one: all go into the statistics
+  // DIRTY_BVH raised by visibility toggles alone: the ids are renumbered and the toggled meshes' triangles hidden / shown in place
+  if ((s->dirty & DIRTY_BVH) && !s->rebuildDue && visibilityUpdatesWanted(s)) {
+    bool handled = false;
+    s->generation++;
+    if (updateVisibility(s, handled) != GI_C_OK) { s->rebuildDue = true; return GI_C_ERROR; } // (half-updated arrays: the next render rebuilds)
+    if (handled) { s->dirty &= ~DIRTY_BVH; s->visibilityUpdates++; materialMs = s->stats.uploadMs; }
+    s->dirty |= DIRTY_FRAMEBUFFER;
+  }
   if ((s->dirty & DIRTY_MATERIALS) && !(s->dirty & DIRTY_BVH)) { // materials, assignments, textures, primvars: the small arrays + one word per triangle
     bool handled = false;
     s->generation++;
-    if (updateMaterials(s, handled) != GI_C_OK) { s->dirty |= DIRTY_BVH; return GI_C_ERROR; } // (half-updated arrays: the next render rebuilds)
-    if (handled) { s->dirty &= ~DIRTY_MATERIALS; s->updateCounts[2]++; materialMs = s->stats.uploadMs; } else s->dirty |= DIRTY_BVH;
+    if (updateMaterials(s, handled) != GI_C_OK) { s->dirty |= DIRTY_BVH; s->rebuildDue = true; return GI_C_ERROR; } // (half-updated arrays: the next render rebuilds)
+    if (handled) { s->dirty &= ~DIRTY_MATERIALS; s->updateCounts[2]++; s->stats.uploadMs += materialMs; materialMs = s->stats.uploadMs; }
+    else { s->dirty |= DIRTY_BVH; s->rebuildDue = true; }
     s->dirty |= DIRTY_FRAMEBUFFER;
   }
   if ((s->dirty & DIRTY_XFORM) && !(s->dirty & (DIRTY_BVH | DIRTY_MATERIALS))) { // only transforms changed: re-transform / re-braid those instances
     bool handled = false;
     s->generation++;
-    if (updateTransforms(s, handled) != GI_C_OK) return GI_C_ERROR;
-    if (handled) { s->updateCounts[1]++; s->stats.uploadMs += materialMs; } else s->dirty |= DIRTY_BVH;
+    if (updateTransforms(s, handled) != GI_C_OK) { s->rebuildDue = true; return GI_C_ERROR; }
+    if (handled) { s->updateCounts[1]++; s->stats.uploadMs += materialMs; } else { s->dirty |= DIRTY_BVH; s->rebuildDue = true; }
     s->dirty |= DIRTY_FRAMEBUFFER;
   }
   if (s->dirty & (DIRTY_BVH | DIRTY_MATERIALS)) {
@@ -902,5 +1040,7 @@ int syncSceneGeometry(GiCScene* s)
     s->dirty &= ~(DIRTY_BVH | DIRTY_MATERIALS); s->dirty |= DIRTY_FRAMEBUFFER;
   }
   s->dirty &= ~DIRTY_XFORM;
+  s->rebuildDue = false;
+  for (GiCMesh* m : s->meshes) m->visToggled = false;
   return GI_C_OK;
 }

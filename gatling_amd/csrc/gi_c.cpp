@@ -329,16 +329,18 @@ int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value)
   if (option == GI_C_SCENE_OPTION_KERNEL_TIMERS) { scene->kernelTimers = value != 0; scene->kernelTimerStride = value > 0 ? (uint32_t)value : 1u;
       return GI_C_OK; }
   if (option == GI_C_SCENE_OPTION_POOL_SLOTS) { scene->optPoolSlots = value > 0 ? (uint64_t)value : 0; return GI_C_OK; }
-  if (option == GI_C_SCENE_OPTION_TWO_LEVEL) { scene->optTwoLevel = value < 0 ? -1 : (value ? 1 : 0); scene->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER;
+  if (option == GI_C_SCENE_OPTION_TWO_LEVEL) { scene->optTwoLevel = value < 0 ? -1 : (value ? 1 : 0); scene->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER; scene->rebuildDue = true;
       return GI_C_OK; }
   if (option == GI_C_SCENE_OPTION_TRACE_DYNAMIC) { scene->optTraceDyn = value < 0 ? -1 : (value > 64 ? 64 : value); return GI_C_OK; }
   if (option == GI_C_SCENE_OPTION_FUSED_PATH) { scene->optFusedPath = value < 0 ? -1 : (value > 2 ? -1 : value); return GI_C_OK; }
   if (option == GI_C_SCENE_OPTION_SAMPLE_BUFFER_MB) { scene->optSampleBufferMb = value > 0 ? (uint64_t)value : 0; return GI_C_OK; }
-  if (option == GI_C_SCENE_OPTION_BVH_BUILD) { scene->optBvhBuild = value == 1 ? 1 : 0; scene->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER; return GI_C_OK; }
-  if (option == GI_C_SCENE_OPTION_DEVICES) { scene->optDevices = value > 0 ? value : 0; scene->dirty |= DIRTY_BVH | DIRTY_LIGHTS | DIRTY_FRAMEBUFFER;
+  if (option == GI_C_SCENE_OPTION_BVH_BUILD) { scene->optBvhBuild = value == 1 ? 1 : 0; scene->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER; scene->rebuildDue = true; return GI_C_OK; }
+  if (option == GI_C_SCENE_OPTION_DEVICES) { scene->optDevices = value > 0 ? value : 0; scene->dirty |= DIRTY_BVH | DIRTY_LIGHTS | DIRTY_FRAMEBUFFER; scene->rebuildDue = true;
       /* replicas are made with the build; a NEW replica also needs the lights, which travel under DIRTY_LIGHTS only */ return GI_C_OK; }
   // (no dirty flag: a window in flight stays valid -- the option decides how FUTURE samples are traced, never what they are)
   if (option == GI_C_SCENE_OPTION_SAMPLE_LOOKAHEAD) { scene->optLookahead = value > 1 ? value : 0; return GI_C_OK; }
+  // (no dirty flag: the option decides how FUTURE visibility edits are applied)
+  if (option == GI_C_SCENE_OPTION_VISIBILITY_UPDATES) { scene->optVisibilityUpdates = value == 1 ? 1 : 0; return GI_C_OK; }
   setError("unknown scene option"); return GI_C_ERROR;
 }
 

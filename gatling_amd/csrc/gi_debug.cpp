@@ -412,3 +412,12 @@ extern "C" int giCDebugSceneUpdateCounts(const GiCScene* scene, uint64_t* outCou
   for (int i = 0; i < 3; i++) outCounts[i] = s->updateCounts[i];
   return GI_C_OK;
 }
+
+extern "C" int giCDebugSceneVisibilityUpdateCount(const GiCScene* scene, uint64_t* outCount)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!s || !outCount) { setError("giCDebugSceneVisibilityUpdateCount: bad arguments"); return GI_C_ERROR; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  *outCount = s->visibilityUpdates;
+  return GI_C_OK;
+}

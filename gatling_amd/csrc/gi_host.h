@@ -166,6 +166,7 @@ struct GiCMesh {
   bool xformDirty = false;  // transform / instance transforms changed since the last build or update ...
   std::vector<uint8_t> instDirty; // ... and which instances (empty: all of them)
   uint32_t builtInstances = 0xffffffffu; // instance count the built scene holds for this mesh (0xffffffff: not part of it)
+  bool visToggled = false;  // giCSetMeshVisibility was called since the last syncSceneGeometry
 };
 
 // swap-remove dense store (GgpuDenseDataStore, src/ggpu/impl/DenseDataStore.cpp:35-93): the arrays stay dense so
@@ -281,7 +282,10 @@ struct SceneDevice {
 struct TwoLevelHost { std::vector<Node8> tlasNodes, blasNodes; std::vector<uint32_t> tlasItems; std::vector<BlasTri> blasTris; std::vector<InstTrav> instTrav;
     };
 struct MeshBuild { const GiCMesh* m; uint32_t vertexOffset, matFlags, instFirst, instCount, triFirst; uint32_t meshIdx; std::vector<int32_t> faceIdAov;
-    uint32_t shadeBase = 0; };
+    uint32_t shadeBase = 0;
+    // incremental visibility updates (gi_build.cpp updateVisibility): the mesh is part of the resident scene but hidden; the scene-order id of its first
+    // triangle as the resident records hold it (triFirst until a mesh in front of it is hidden; triFirst stays the POSITION of a partitioned scene's ranges)
+    bool hidden = false; uint32_t idBase = 0; };
 // One flattened mesh instance of a PARTITIONED scene (after the first transform edit): its own subtree in its own node range, its triangles in its own
 // (scene-order) range, joined by a top tree over the subtree roots (bvh8.h buildTopBvh8).  Moving it rebuilds these ranges and the top tree only.
 struct InstPart { uint32_t meshBuild, instInMesh; uint32_t triFirst, nf; uint32_t nodeOff, nodeCount, nodeCap, depth; float box[6]; };
@@ -351,7 +355,13 @@ struct GiCScene : SceneDevice {
   // a look-ahead window traced under another generation is not served from
   uint64_t generation = 0;
   uint64_t updateCounts[3] = {0, 0, 0}; // syncSceneGeometry: full builds, incremental transform updates, incremental material updates (giCDebugSceneUpdateCounts)
+  int32_t optVisibilityUpdates = 0; // GI_C_SCENE_OPTION_VISIBILITY_UPDATES: 1 = visibility edits are applied to the resident scene (updateVisibility)
+  uint64_t visibilityUpdates = 0;   // syncSceneGeometry: incremental visibility updates (giCDebugSceneVisibilityUpdateCount)
+  // DIRTY_BVH was raised by something other than giCSetMeshVisibility since the last syncSceneGeometry (raiseRebuild): the rebuild is due whatever was toggled
+  bool rebuildDue = true;
 };
+// every geometry-side edit but a visibility toggle
+inline void raiseRebuild(GiCScene* s) { s->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER; s->rebuildDue = true; }
 
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -49,6 +49,13 @@ void launchZeroClosest(hipStream_t s, Counters* cnt, uint32_t par); // FLAG_TWO_
 // gi_patch.hip: rewrites TriRec::matFlags of the `triCount` device-resident triangles to wordOfMesh[instances[t.instance].mesh] where it differs
 void launchPatchMatFlags(hipStream_t s, TriRec* tris, uint32_t triCount, const InstanceRec* instances, uint32_t instanceCount, const uint32_t* wordOfMesh,
     uint32_t meshCount);
+// gi_patch.hip: a visibility edit applied to the device-resident triangles (gi_build.cpp updateVisibility).  One VisPatch per flattened instance: the change
+// of its triangles' scene-order ids, and whether its records are left alone, made unhittable (both edges zeroed) or given their edges back (recomputed from
+// the mesh triangle's shading record and the instance transform with the scene build's operations in its order)
+struct VisPatch { int32_t idDelta; uint32_t action; };
+constexpr uint32_t VIS_KEEP = 0u, VIS_HIDE = 1u, VIS_SHOW = 2u;
+void launchPatchVisibility(hipStream_t s, TriRec* tris, uint32_t triCount, const InstanceRec* instances, uint32_t instanceCount, const VisPatch* patchOfInstance,
+    const TriShade* triShade, uint32_t shadeCount);
 void launchSpin(hipStream_t s, unsigned long long ns);              // test hook: occupies a stream for ~ns nanoseconds
 void launchDebugBsdf(hipStream_t s, const MaterialRec* mat, uint32_t shadeClass, uint32_t count, const float* in, float* out);
 void launchDebugSqrt(hipStream_t s, uint32_t first, unsigned long long count, unsigned long long* mismatches); // gi_sqrt against sqrtf over bit patterns

@@ -35,6 +35,8 @@
 //   two_stream_delay     0         tests: 1 / 2 = hold the main / the second stream back 0.3 ms per iteration so that the other one runs ahead
 //   lookahead            -1        sample look-ahead of progressive low-spp calls: -1 = the scene option decides (GI_C_SCENE_OPTION_SAMPLE_LOOKAHEAD),
 //                                  0 / 1 = off, N >= 2 = a call may trace the samples of up to N calls in one batch (gi_render.cpp planLookahead)
+//   visibility_updates   -1        -1 = the scene option decides (GI_C_SCENE_OPTION_VISIBILITY_UPDATES), 0 / 1 = visibility edits rebuild the scene / are
+//                                  applied to the resident scene (gi_build.cpp updateVisibility)
 //   phase_stats          0         counting builds: print k_path's phase split / k_trace_dyn's lane accounting
 #pragma once
 

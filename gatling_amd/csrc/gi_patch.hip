@@ -1,5 +1,8 @@
-// gi_patch.hip -- k_patch_mat_flags: TriRec::matFlags rewritten in place after a material edit (gi_build.cpp updateMaterials).
+// gi_patch.hip -- edits applied in place to the device-resident triangle records:
+//   k_patch_mat_flags   TriRec::matFlags rewritten after a material edit (gi_build.cpp updateMaterials)
+//   k_patch_visibility  scene-order ids renumbered, records of hidden instances made unhittable / restored (gi_build.cpp updateVisibility; below)
 //
+// k_patch_mat_flags.
 // A material or assignment edit changes one word per flattened triangle -- material index | shade class << 24 | cutout << 28 | facing << 30 -- and nothing
 // else of the 64-byte record.  The triangles lie in whatever order their builder left them (leaf order of the host or the device builder, scene order inside
 // the ranges of a partitioned tree); order does not matter here: a triangle names its instance, the instance its mesh, and the mesh's new word comes from a
@@ -35,7 +38,52 @@ __global__ __launch_bounds__(kPatchBlock) void k_patch_mat_flags(TriRec* __restr
   if (word != im.y) tris[i].matFlags = word; // a plain vector store of the one dword
 }
 
+// k_patch_visibility.  Hiding or showing a mesh (opt-in: GI_C_SCENE_OPTION_VISIBILITY_UPDATES) changes two things in the records: the triangles of the meshes
+// behind it in scene order get the ids a fresh build would give them (the cutout hash and the tie-break read TriRec::origId), and -- on the flat layouts,
+// where one tree holds every instance -- the records of the mesh itself must stop being hit, and be hit again later.
+//   hide: e1 = e2 = 0.  tri_test (gi_traversal.h, the one intersection routine of every walk) then computes det = dot(0, cross(d, 0)): +-0 for a finite
+//         direction, NaN otherwise; `det != 0` fails for the zero, and with a NaN det u = NaN fails `u >= 0`.  No ray accepts the record.
+//   show: e1 and e2 are made again from the mesh triangle's object-space corners (TriShade::p, named by vi[0]) and the instance's o2w exactly as
+//         flattenTriangle makes them on the host -- xformPoint's ((a0 x + a1 y) + a2 z) + a3, then p1 - p0 and p2 - p0; the library is built without
+//         contraction, so these are the host's IEEE operations in the host's order and the record is bytewise what it was.  v0 is never touched (it carries
+//         the inactive marker of an unusable instance).
+// The host uploads one VisPatch per instance; a thread reads its record's instance word, then the entry, and stores only words that change: one dword for a renumbering, six for a
+// hide or a show.  No atomics; order does not matter.  Memory-bound like k_patch_mat_flags: triangle count x one 64-byte line read, lines written only for
+// instances whose entry is not (0, keep).  A partitioned tree leaves hidden parts out of its top tree instead, so there only ids are renumbered.
+__global__ __launch_bounds__(kPatchBlock) void k_patch_visibility(TriRec* __restrict__ tris, uint32_t triCount, const InstanceRec* __restrict__ instances,
+    uint32_t instanceCount, const VisPatch* __restrict__ patchOfInstance, const TriShade* __restrict__ triShade, uint32_t shadeCount)
+{
+  const uint32_t i = blockIdx.x * kPatchBlock + threadIdx.x;
+  if (i >= triCount) return;
+  TriRec& t = tris[i];
+  const uint32_t inst = t.instance;
+  if (inst >= instanceCount) return; // (cannot happen: the build numbers instances densely)
+  const VisPatch vp = patchOfInstance[inst];
+  if (vp.idDelta != 0) t.origId = t.origId + (uint32_t)vp.idDelta;
+  if (vp.action == VIS_HIDE) {
+    for (int a = 0; a < 3; a++) { t.e1[a] = 0.0f; t.e2[a] = 0.0f; }
+  } else if (vp.action == VIS_SHOW) {
+    const uint32_t rec = t.vi[0];
+    if (rec >= shadeCount) return; // (cannot happen: scenes beyond LDS name their shading record there)
+    const float* m = instances[inst].o2w;
+    float p[3][3];
+    for (int k = 0; k < 3; k++) {
+      const float x = triShade[rec].p[k][0], y = triShade[rec].p[k][1], z = triShade[rec].p[k][2];
+      for (int r = 0; r < 3; r++) p[k][r] = ((m[4 * r] * x + m[4 * r + 1] * y) + m[4 * r + 2] * z) + m[4 * r + 3];
+    }
+    for (int a = 0; a < 3; a++) { t.e1[a] = p[1][a] - p[0][a]; t.e2[a] = p[2][a] - p[0][a]; }
+  }
+}
+
 } // namespace
+
+void launchPatchVisibility(hipStream_t s, TriRec* tris, uint32_t triCount, const InstanceRec* instances, uint32_t instanceCount, const VisPatch* patchOfInstance,
+    const TriShade* triShade, uint32_t shadeCount)
+{
+  if (triCount == 0u) return;
+  hipLaunchKernelGGL(k_patch_visibility, dim3((triCount + kPatchBlock - 1u) / kPatchBlock), dim3(kPatchBlock), 0, s, tris, triCount, instances, instanceCount,
+      patchOfInstance, triShade, shadeCount);
+}
 
 void launchPatchMatFlags(hipStream_t s, TriRec* tris, uint32_t triCount, const InstanceRec* instances, uint32_t instanceCount, const uint32_t* wordOfMesh,
     uint32_t meshCount)

@@ -80,7 +80,7 @@ static GiCMesh* createMeshImpl(GiCScene* scene, const GiCMeshDesc* d)
   m->id = d->id; m->doubleSided = d->isDoubleSided != 0; m->flipFacing = d->isLeftHanded != 0; m->maxFaceId = d->maxFaceId;
   std::lock_guard<std::mutex> g(scene->mutex);
   scene->meshes.push_back(m.get());
-  scene->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER;
+  raiseRebuild(scene);
   return m.release();
 }
 
@@ -91,7 +91,7 @@ void giCSetMeshTransform(GiCMesh* mesh, const float* mat4x4)
   memcpy(mesh->transform, mat4x4, sizeof(float) * 16);
   // same triangles elsewhere: incremental update (every instance of the mesh moves)
   if (mesh->builtInstances != 0xffffffffu) { mesh->xformDirty = true; mesh->instDirty.clear(); mesh->scene->dirty |= DIRTY_XFORM | DIRTY_FRAMEBUFFER; }
-  else mesh->scene->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER;
+  else raiseRebuild(mesh->scene);
 }
 
 void giCSetMeshInstanceTransforms(GiCMesh* mesh, uint32_t count, const float* transforms)
@@ -109,7 +109,7 @@ void giCSetMeshInstanceTransforms(GiCMesh* mesh, uint32_t count, const float* tr
     }
     mesh->xformDirty = true; mesh->scene->dirty |= DIRTY_XFORM | DIRTY_FRAMEBUFFER;
   }
-  else mesh->scene->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER;
+  else raiseRebuild(mesh->scene);
   } catch (const std::exception& e) { setError(std::string("giCSetMeshInstanceTransforms: ") + e.what()); }
 }
 
@@ -120,7 +120,7 @@ void giCSetMeshInstanceIds(GiCMesh* mesh, uint32_t count, const int32_t* ids)
   std::vector<int32_t> copy(ids, ids + count);
   std::lock_guard<std::mutex> g(mesh->scene->mutex);
   mesh->instanceIds.swap(copy);
-  mesh->scene->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER;
+  raiseRebuild(mesh->scene);
   } catch (const std::exception& e) { setError(std::string("giCSetMeshInstanceIds: ") + e.what()); }
 }
 
@@ -131,7 +131,7 @@ void giCSetMeshMaterial(GiCMesh* mesh, GiCMaterial* mat)
   mesh->material = mat;
   // a mesh of the built scene keeps its triangles: only their material word changes.  One that is not part of it (new, invisible, left out for an invalid
   // material) may enter the scene now: rebuild
-  mesh->scene->dirty |= mesh->builtInstances != 0xffffffffu ? materialEditFlags(true) : (DIRTY_BVH | DIRTY_FRAMEBUFFER);
+  if (mesh->builtInstances != 0xffffffffu) mesh->scene->dirty |= materialEditFlags(true); else raiseRebuild(mesh->scene);
 }
 
 void giCSetMeshVisibility(GiCMesh* mesh, int32_t visible)
@@ -139,6 +139,9 @@ void giCSetMeshVisibility(GiCMesh* mesh, int32_t visible)
   if (!mesh) return;
   std::lock_guard<std::mutex> g(mesh->scene->mutex);
   mesh->visible = visible != 0;
+  // the same flags as any geometry-side edit; the scene notes which meshes were toggled, and syncSceneGeometry may answer with updateVisibility instead of
+  // the rebuild when nothing else asked for one (GI_C_SCENE_OPTION_VISIBILITY_UPDATES)
+  mesh->visToggled = true;
   mesh->scene->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER;
 }
 
@@ -149,7 +152,7 @@ void giCDestroyMesh(GiCMesh* mesh)
   {
     std::lock_guard<std::mutex> g(s->mutex);
     s->meshes.erase(std::remove(s->meshes.begin(), s->meshes.end(), mesh), s->meshes.end());
-    s->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER;
+    raiseRebuild(s);
   }
   delete mesh;
 }
@@ -178,7 +181,7 @@ static int setPrimvarsImpl(GiCMesh* mesh, std::vector<GiCPrimvar>& dst, uint32_t
   std::lock_guard<std::mutex> g(mesh->scene->mutex);
   dst = std::move(v);
   // Gi.cpp:685-700; primvars feed the per-mesh scene data, not the tree
-  mesh->scene->dirty |= mesh->builtInstances != 0xffffffffu ? materialEditFlags(true) : (DIRTY_BVH | DIRTY_FRAMEBUFFER);
+  if (mesh->builtInstances != 0xffffffffu) mesh->scene->dirty |= materialEditFlags(true); else raiseRebuild(mesh->scene);
   return GI_C_OK;
 }
 int giCSetMeshPrimvars(GiCMesh* mesh, uint32_t count, const GiCPrimvarData* pv) { return mesh

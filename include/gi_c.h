@@ -375,7 +375,8 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * 7: GI_C_P_COAT_ROTATION / GI_C_P_SPECULAR_ROTATION, slots that were reserved; 8: GI_C_SCENE_OPTION_BVH_BUILD, giCDebugValidateSceneBvh, bvhBuildMs counts
  * the device build when one ran).  A caller compares giCGetApiVersion() with the GI_C_API_VERSION it was built with.
  * Still 8 with GI_C_SCENE_OPTION_SAMPLE_LOOKAHEAD and giCGetLookaheadStats: no struct grew and no entry point changed meaning -- both are additions that a caller
- * built against an earlier header never sees.  A caller probes for them: giCSetSceneOption answers GI_C_ERROR for an option the library does not know. */
+ * built against an earlier header never sees.  A caller probes for them: giCSetSceneOption answers GI_C_ERROR for an option the library does not know.
+ * The same holds for GI_C_SCENE_OPTION_VISIBILITY_UPDATES and giCDebugSceneVisibilityUpdateCount. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -521,6 +522,15 @@ int giCGetRenderStats(const GiCScene* scene, GiCRenderStats* out);
  * rate and the K - 1 after it are short -- mean latency falls, per-call latency becomes uneven -- and the window holds pixels * K * spp * 16 bytes between
  * calls.  GATLING_OPTIONS=lookahead=N overrides it.  See giCGetLookaheadStats and the note below GiCRenderStats. */
 #define GI_C_SCENE_OPTION_SAMPLE_LOOKAHEAD 10
+/* [ext] Incremental visibility edits: value 1 = a giCSetMeshVisibility on a mesh of the built scene is applied to the device-resident scene by the next giCRender
+ * -- the triangles behind the mesh in scene order are renumbered as a fresh build would number them, the mesh's own triangles stop being hit (or are hit
+ * again) -- instead of rebuilding the scene; 0 = off (default): every visibility edit rebuilds, as in the reference (Gi.cpp:801-804).  The library falls
+ * back to the rebuild when anything but visibility edits asked for one, when a toggled mesh is not part of the built scene (it was invisible at the build),
+ * when fewer than 4096 visible flattened triangles remain, with GATLING_OPTIONS=incremental=0, and on the two-level layout.  After such an edit
+ * GiCRenderStats.triangleCount and nodeCount keep describing what is RESIDENT on the device (hidden triangles included), bvhBuildMs is 0 and uploadMs the
+ * time of the update.  Hidden geometry keeps its boxes in a flat tree until the next full build.  The image does not depend on the
+ * option.  GATLING_OPTIONS=visibility_updates=0|1 overrides it (hdGatling sets no scene options). */
+#define GI_C_SCENE_OPTION_VISIBILITY_UPDATES 11
 int giCGetLookaheadStats(const GiCScene* scene, GiCLookaheadStats* out);
 int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value);
 /* [ext] closest hit of one ray through the device traversal kernel (parity tests of the BVH8 path).
@@ -570,6 +580,9 @@ int32_t giCDebugEditDirtyFlags(int32_t edit, int32_t built);
 /* [ext] how often the scene's geometry was brought up to date by outCounts[0] a full build, [1] an incremental transform update, [2] an incremental material
  * update, since the scene was created. */
 int giCDebugSceneUpdateCounts(const GiCScene* scene, uint64_t* outCounts /* 3 */);
+/* [ext] how often the scene was brought up to date by an incremental visibility update (GI_C_SCENE_OPTION_VISIBILITY_UPDATES); such an update is not counted
+ * in giCDebugSceneUpdateCounts. */
+int giCDebugSceneVisibilityUpdateCount(const GiCScene* scene, uint64_t* outCount);
 
 #ifdef __cplusplus
 }
