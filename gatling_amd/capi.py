@@ -161,7 +161,7 @@ SYMBOLS = [
     ("giCDebugValidateSceneBvh", C.c_int, [_P, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),
     ("giCDebugTexRuntime", C.c_int, [_FP, _U, _U, _U, _U, _FP, _FP]),
     ("giCDebugEditDirtyFlags", C.c_int32, [_I, _I]), ("giCDebugSceneUpdateCounts", C.c_int, [_P, C.POINTER(C.c_uint64)]),
-    ("giCDebugSceneVisibilityUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("giCDebugSceneVisibilityUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugSceneClassState", C.c_int, [_P, C.POINTER(C.c_uint32)]),
 ]
 
 _lib = None
@@ -443,6 +443,13 @@ class Scene:
         if self.L.giCDebugSceneVisibilityUpdateCount(self.handle, C.byref(n)) != GI_C_OK:
             raise GiError("giCDebugSceneVisibilityUpdateCount failed")
         return int(n.value)
+
+    def class_state(self) -> dict:
+        """giCDebugSceneClassState: the class masks and the cutout flag the last scene sync derived (they pick a render's kernel variants)."""
+        c = (C.c_uint32 * 5)()
+        if self.L.giCDebugSceneClassState(self.handle, c) != GI_C_OK:
+            raise GiError("giCDebugSceneClassState failed")
+        return {"classMask": int(c[0]), "classTextured": int(c[1]), "shadeClassMask": int(c[2]), "shadeClassTextured": int(c[3]), "hasCutouts": bool(c[4])}
 
     def set_option(self, option: int, value: int):
         if self.L.giCSetSceneOption(self.handle, option, value) != GI_C_OK:

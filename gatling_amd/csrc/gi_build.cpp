@@ -2,6 +2,10 @@
 // (one of the translation units gi_c.cpp was split into in round 6; shared declarations: gi_host.h)
 #include "gi_host.h"
 #include "gi_bvh_build.h"
+constexpr uint32_t kIncrementalMinTris = 4096; // scenes with fewer triangles are not edited in place: they rebuild in no time (and must stay LDS-resident)
+// levels of a scene BVH: the deepest traversal variant keeps 16 stack entries in LDS and OVF_STACK = 40 in scratch; trav_node_pick does not bound-check the
+// spill.  The limit stays at 1 + 8 + 40 levels, the depth the 8-entry spilling variant of earlier versions could hold
+constexpr uint32_t kMaxBvhDepth = 1u + 8u + 40u;
 
 // ---------------------------------------------------------------------------------------------------------------
 // scene build: flatten instances into world space, pack vertex data, build + upload the BVH8
@@ -95,6 +99,31 @@ inline void flattenTriangle(const InstanceRec& ir, bool usable, const GiCMesh* m
   if (!usable) t.v0[0] = std::numeric_limits<float>::quiet_NaN();
 }
 
+// InstanceRec of instance `instInMesh` of mesh `m`, the scene's meshIdx-th (Gi.cpp:1188-1202)
+static InstanceRec makeInstanceRec(const GiCMesh* m, uint32_t meshIdx, size_t instInMesh)
+{
+  InstanceRec ir{};
+  composeTransform(m->transform, &m->instanceTransforms[16 * instInMesh], ir.o2w);
+  invert3x3(ir.o2w, ir.w2o);
+  ir.mesh = meshIdx; ir.instanceId = instInMesh < m->instanceIds.size() ? m->instanceIds[instInMesh] : (int32_t)instInMesh;
+  ir.pad = (uint32_t)m->id; // object id
+  return ir;
+}
+// The TriRecs of one flattened instance, out[f] for face f.  idBase: scene-order id of its first triangle; shadeBase: the mesh's first TriShade record where
+// vi[0] names the triangle's (scenes beyond LDS), else NOT_PACKED.  buildScene and buildPart: an edited scene and a fresh one hold the same bits through this.
+constexpr uint32_t NOT_PACKED = 0xffffffffu;
+static void flattenInstance(const InstanceRec& ir, uint32_t instIdx, const GiCMesh* m, uint32_t vertexOffset, uint32_t matFlags, uint32_t idBase, uint32_t shadeBase, TriRec* out)
+{
+  const bool usable = usableInstance(ir);
+  for (uint32_t f = 0; f < (uint32_t)m->faces.size(); f++) {
+    TriRec& t = out[f];
+    flattenTriangle(ir, usable, m, f, t);
+    for (int a = 0; a < 3; a++) t.vi[a] = vertexOffset + m->faces[f].v_i[a];
+    t.instance = instIdx; t.prim = f; t.origId = idBase + f; t.matFlags = matFlags;
+    if (shadeBase != NOT_PACKED) t.vi[0] = shadeBase + f;
+  }
+}
+
 // The MaterialRec table of the scene's materials, in creation order (buildScene and updateMaterials: the one copy of this code)
 static void buildMaterialRecords(const GiCScene* s, std::vector<MaterialRec>& mats)
 {
@@ -156,17 +185,32 @@ static void appendMeshSceneData(const GiCMesh* m, const GiCMaterial* mat, uint32
   meshRecs.push_back(mr);
 }
 
-// TriRec::matFlags of a mesh bound to material `material` (record `mr`); adds the material to the scene's class masks and cutout flag, which the caller
-// has reset (buildScene and updateMaterials)
-static uint32_t meshMatFlags(GiCScene* s, const MaterialRec& mr, uint32_t material, const GiCMesh* m)
+// TriRec::matFlags of a mesh bound to material `material` (record `mr`): material index | shade class << 24 | cutout << 28 | mesh flags << 30
+static uint32_t meshMatFlags(const MaterialRec& mr, uint32_t material, const GiCMesh* m)
 {
   const bool cutoutMat = mr.p[MP_CUTOUT] < 1.0f || (mr.flags & MAT_FLAG_OPACITY_TEX) != 0u;
-  if (cutoutMat) s->hasCutouts = true;
-  const uint32_t shadeClass = shadeClassOf(mr);
-  const uint32_t matFlags = material | (shadeClass << 24) | (cutoutMat ? (1u << 28) : 0u) | (((m->flipFacing ? 1u : 0u) | (m->doubleSided ? 2u : 0u)) << 30);
-  s->classMask |= 1u << (mr.klass & 0xfu); s->shadeClassMask |= 1u << shadeClass;
-  if (mr.flags & MAT_FLAG_TEXTURED) { s->classTextured |= 1u << (mr.klass & 0xfu); s->shadeClassTextured |= 1u << shadeClass; }
-  return matFlags;
+  return material | (shadeClassOf(mr) << 24) | (cutoutMat ? (1u << 28) : 0u) | (((m->flipFacing ? 1u : 0u) | (m->doubleSided ? 2u : 0u)) << 30);
+}
+
+// the shadow walks' order is chosen anew
+static void resetShadowOrder(GiCScene* s) { s->shadowOrder = -1; s->shadowOrderRays[0] = s->shadowOrderRays[1] = s->shadowOrderSteps[0] = s->shadowOrderSteps[1] = 0; }
+
+// The scene's class masks and cutout flag: which kernel variants a render launches and whether walks run the any-hit test.  The one place that writes them:
+// every build, and every update that changes a mesh's word or visibility, ends here.  Taken from the words of the meshes a fresh build would hold (a hidden mesh
+// launches no kernel variant) and the material table they index.  The shadow order was chosen for one tree and for walks with / without the any-hit test.
+static void deriveSceneClasses(GiCScene* s, const SceneHost& H, bool newTree)
+{
+  const bool hadCutouts = s->hasCutouts;
+  s->classMask = 0; s->classTextured = 0; s->shadeClassMask = 0; s->shadeClassTextured = 0; s->hasCutouts = false;
+  for (const MeshBuild& mb : H.meshBuilds) {
+    if (mb.hidden) continue;
+    const MaterialRec& mr = H.mats[mb.matFlags & 0x00ffffffu];
+    const uint32_t klassBit = 1u << (mr.klass & 0xfu), shadeBit = 1u << ((mb.matFlags >> 24) & 0xfu);
+    s->classMask |= klassBit; s->shadeClassMask |= shadeBit;
+    if (mr.flags & MAT_FLAG_TEXTURED) { s->classTextured |= klassBit; s->shadeClassTextured |= shadeBit; }
+    if (mb.matFlags & (1u << 28)) s->hasCutouts = true;
+  }
+  if (newTree || s->hasCutouts != hadCutouts) resetShadowOrder(s);
 }
 
 // Two-level layout (SceneView::tlasNodes ...): built next to the flat BVH for instanced scenes that do not fit LDS.  The flat
@@ -179,10 +223,7 @@ int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vec
   s->twoLevel = false;
   int want = s->optTwoLevel;
   want = (int)optionValue("two_level", want);
-  size_t uniqueTris = 0;
-  for (const MB& mb : meshBuilds) uniqueTris += mb.instCount ? mb.m->faces.size() : 0;
   const bool beyondLds = !sceneFitsLds(flatNodes, flatTris);
-  (void)uniqueTris;
   // Opt-in only. Measured (r01k): although its working set is tiny (C4: 1.5 MB of BLAS nodes + 2.6 MB of mesh triangles instead of 41 + 335 MB) the first
   // version is SLOWER than the flat layout -- C4 trace 185 -> 207 ms, C5 834 -> 1945 ms (29 instead of 20 nodes per ray: overlapping instance boxes, each visit
   // pays a ray transform, a BLAS root and a restore; candidates cost a rebuild). ... except where the flat traversal cannot address the scene: its
@@ -302,12 +343,9 @@ static int uploadTexturesTo(GiCScene* s, SceneDevice& D, hipStream_t st)
   return rc;
 }
 
-// ... and its upload into one device's memory (the primary's and every replica's: multi-device renders replicate the scene)
-int uploadSceneTo(GiCScene* s, SceneDevice& D, const SceneHost& H)
+// ... and its upload into one device's memory (the primary's and every replica's: multi-device renders replicate the scene); onSceneDevices made it current
+static int uploadSceneTo(GiCScene* s, SceneDevice& D, const SceneHost& H, hipStream_t st)
 {
-  const DevCtx& ctx = g_ctx.devs[D.slot];
-  HIP_TRY(hipSetDevice(ctx.device));
-  hipStream_t st = ctx.stream;
   if (s->twoLevel) {
     if (D.dTlasNodes.upload(H.two.tlasNodes, st) || D.dTlasItems.upload(H.two.tlasItems, st) || D.dBlasNodes.upload(H.two.blasNodes, st)
         || D.dBlasTris.upload(H.two.blasTris, st) ||
@@ -332,6 +370,32 @@ uint32_t sceneDeviceCount(const GiCScene* s)
   return std::max(n, 1u);
 }
 SceneDevice& sceneDevice(GiCScene* s, uint32_t slot) { return slot == 0u ? static_cast<SceneDevice&>(*s) : *s->replicas[slot - 1u]; }
+
+// one copy of the scene per device this scene renders on (a build); a new replica has no lights yet
+static void ensureReplicas(GiCScene* s)
+{
+  while (s->replicas.size() + 1u < sceneDeviceCount(s)) { s->replicas.emplace_back(new SceneDevice()); s->replicas.back()->slot = (uint32_t)s->replicas.size();
+      s->dirty |= DIRTY_LIGHTS; }
+}
+static uint32_t residentDeviceCount(const GiCScene* s) { return std::min<uint32_t>(sceneDeviceCount(s), (uint32_t)s->replicas.size() + 1u); } // (an update)
+
+// The frame of all per-device work: fn(SceneDevice&, hipStream_t) -> int runs for the scene's first nDev devices in turn, each made current, until one does
+// not answer GI_C_OK; that answer is returned.  The primary device is current again on every exit.
+template <class Fn> int onSceneDevices(GiCScene* s, uint32_t nDev, Fn&& fn)
+{
+  int rc = GI_C_OK;
+  auto makeCurrent = [&rc](int device) { if (hipSetDevice(device) != hipSuccess && rc == GI_C_OK) { setError("hipSetDevice failed"); rc = GI_C_ERROR; } };
+  for (uint32_t d = 0; d < nDev && rc == GI_C_OK; d++) {
+    SceneDevice& D = sceneDevice(s, d);
+    makeCurrent(g_ctx.devs[D.slot].device);
+    if (rc == GI_C_OK) rc = fn(D, g_ctx.devs[D.slot].stream);
+  }
+  makeCurrent(g_ctx.device);
+  return rc;
+}
+
+static int uploadTopTree(SceneDevice& D, const SceneHost& H, hipStream_t st) // the top tree of a partitioned scene: nodes [0, topCap)
+{ HIP_TRY(hipMemcpyAsync(D.dNodes.ptr, H.bvh.nodes.data(), (size_t)H.topCap * sizeof(Node8), hipMemcpyHostToDevice, st)); return GI_C_OK; }
 
 // The flat tree's root bounds for FLAG_BOUNDS_RETIRE: the dequantised child boxes of node 0 (which contain every triangle's padded box), padded once more by
 // 1e-5 of their magnitude and extent -- k_raygen's slab test adds its own per-ray rounding allowance on top.
@@ -378,11 +442,28 @@ static std::vector<uint32_t> buildShadeRecords(SceneHost& H)
   return shadeBaseOfMesh;
 }
 
+// What either builder leaves behind a tree that every device holds (H.bvh.maxDepth levels; `top`: its root node first): the scene's sizes, bounds and class
+// state, the statistics; the scene owns the host copy from here.
+static int finishBuild(GiCScene* s, std::unique_ptr<SceneHost>& hostPtr, uint32_t nodes, uint32_t tris, const std::vector<Node8>& top, double buildMs,
+    double uploadMs, const char* how)
+{
+  const uint32_t levels = hostPtr->bvh.maxDepth;
+  s->shadePacked = hostPtr->shadePacked; deriveSceneClasses(s, *hostPtr, true); // (a new tree)
+  // stack entries a walk can need: a pick at level L pushes the rest of level L-1's group (gi_traversal.h trav_node_pick), the root level pushes nothing
+  s->nodeCount = nodes; s->triCount = tris; s->bvhDepth = levels > 1u ? levels - 1u : 1u;
+  setSceneBounds(s, top);
+  s->stats.bvhBuildMs = buildMs; s->stats.uploadMs = uploadMs; s->stats.nodeCount = nodes; s->stats.triangleCount = tris;
+  if (getenv("GATLING_BUILD_TIMING")) fprintf(stderr, "[gatling_gi] scene%s: %u nodes, %u triangles, %u levels (traversal stack need %u)\n", how, nodes, tris,
+      levels, s->bvhDepth);
+  s->host = std::move(hostPtr);
+  return GI_C_OK;
+}
+
 // The device builder's side of buildScene (GI_C_SCENE_OPTION_BVH_BUILD; gi_bvh_build.hip): the flattened scene-order triangles and face ids are uploaded to
 // every device and each device builds its own tree over them (the builder is deterministic: the copies are identical).  Nothing of the tree is kept on the
 // host.  Returns GI_C_OK / GI_C_ERROR, or DEVICE_BUILD_FALLBACK when the host builder must take over (out of device memory, a tree deeper than the traversal
 // stack): not an error.
-constexpr int DEVICE_BUILD_FALLBACK = 1;
+constexpr int DEVICE_BUILD_FALLBACK = 2; // (neither GI_C_OK nor GI_C_ERROR)
 static int buildSceneOnDevice(GiCScene* s, std::unique_ptr<SceneHost>& hostPtr, std::vector<TriRec>& tris, const std::vector<int32_t>& faceIdOf, double t0)
 {
   SceneHost& H = *hostPtr;
@@ -406,54 +487,39 @@ static int buildSceneOnDevice(GiCScene* s, std::unique_ptr<SceneHost>& hostPtr, 
   H.deviceBuilt = true;
   const bool timing = getenv("GATLING_BUILD_TIMING") != nullptr;
   double uploadMs = nowMs() - t0 - buildMs;
-  const uint32_t nDev = sceneDeviceCount(s);
-  while (s->replicas.size() + 1u < nDev) { s->replicas.emplace_back(new SceneDevice()); s->replicas.back()->slot = (uint32_t)s->replicas.size();
-      s->dirty |= DIRTY_LIGHTS; }
+  ensureReplicas(s);
   DeviceBvhResult first;
-  for (uint32_t d = 0; d < nDev; d++) {
-    SceneDevice& D = sceneDevice(s, d);
+  const int rc = onSceneDevices(s, sceneDeviceCount(s), [&](SceneDevice& D, hipStream_t st) -> int {
     const double ta = nowMs();
-    if (uploadSceneTo(s, D, H) != GI_C_OK) { (void)hipSetDevice(g_ctx.device); return GI_C_ERROR; }
-    hipStream_t st = g_ctx.devs[D.slot].stream;
-    if (D.dTris.upload(tris, st) || D.dTriFaceId.upload(faceIdOf, st)) { (void)hipSetDevice(g_ctx.device); return GI_C_ERROR; }
+    if (uploadSceneTo(s, D, H, st) != GI_C_OK || D.dTris.upload(tris, st) || D.dTriFaceId.upload(faceIdOf, st)) return GI_C_ERROR;
     HIP_TRY(hipStreamSynchronize(st));
     const double tb = nowMs();
     DeviceBvhResult r;
-    const int rc = buildBvh8Device(st, D.dTris.ptr, D.dTriFaceId.ptr, n, 1u + 8u + 40u, r);
+    const int built = buildBvh8Device(st, D.dTris.ptr, D.dTriFaceId.ptr, n, kMaxBvhDepth, r);
     uploadMs += tb - ta; buildMs += nowMs() - tb;
-    if (rc == DEVICE_BVH_OUT_OF_MEMORY || rc == DEVICE_BVH_TOO_DEEP) {
-      if (timing || rc == DEVICE_BVH_TOO_DEEP) fprintf(stderr, "[gatling_gi] device BVH build on device %u: %s; the host builder takes over\n", d,
-          rc == DEVICE_BVH_TOO_DEEP ? "the tree is deeper than the traversal stack (49 levels)" : "out of device memory");
-      for (uint32_t k = 0; k <= d; k++) sceneDevice(s, k).dNodes.release(); // (no tree of the wrong shape left behind)
+    if (built == DEVICE_BVH_OUT_OF_MEMORY || built == DEVICE_BVH_TOO_DEEP) {
+      if (timing || built == DEVICE_BVH_TOO_DEEP) fprintf(stderr, "[gatling_gi] device BVH build on device %u: %s; the host builder takes over\n", D.slot,
+          built == DEVICE_BVH_TOO_DEEP ? "the tree is deeper than the traversal stack (49 levels)" : "out of device memory");
+      for (uint32_t k = 0; k <= D.slot; k++) sceneDevice(s, k).dNodes.release(); // (no tree of the wrong shape left behind)
       H.deviceBuilt = false; H.triShade.clear();
-      (void)hipSetDevice(g_ctx.device);
       return DEVICE_BUILD_FALLBACK;
     }
-    if (rc != DEVICE_BVH_OK) { setError(std::string("device BVH build failed: ") + r.error); (void)hipSetDevice(g_ctx.device); return GI_C_ERROR; }
+    if (built != DEVICE_BVH_OK) { setError(std::string("device BVH build failed: ") + r.error); return GI_C_ERROR; }
     D.dNodes.release(); D.dNodes.ptr = r.nodes; D.dNodes.count = r.nodeCount;
-    if (d == 0) first = r;
-    else if (r.nodeCount != first.nodeCount || r.maxDepth != first.maxDepth) { setError("internal: device BVH builds differ between devices");
-        (void)hipSetDevice(g_ctx.device); return GI_C_ERROR; }
+    if (D.slot == 0) first = r;
+    else if (r.nodeCount != first.nodeCount || r.maxDepth != first.maxDepth) { setError("internal: device BVH builds differ between devices"); return GI_C_ERROR; }
     if (timing) fprintf(stderr, "[gatling_gi] device bvh8 (device %u): boxes %.1f ms, sort %.1f ms, PLOC + collapse DP %.1f ms (%u passes; the DP is filled by "
-                                "the merge kernel), emission %.1f ms (%u levels, %u nodes, %u active of %u triangles)\n", d, r.ms[0], r.ms[1], r.ms[2],
+                                "the merge kernel), emission %.1f ms (%u levels, %u nodes, %u active of %u triangles)\n", D.slot, r.ms[0], r.ms[1], r.ms[2],
                         r.plocIterations, r.ms[3], r.maxDepth, r.nodeCount, r.activeTris, n);
-  }
-  HIP_TRY(hipSetDevice(g_ctx.device));
+    return GI_C_OK;
+  });
+  if (rc != GI_C_OK) return rc;
   if (first.activeTris != n - inactive) { setError("internal: device and host disagree on the inactive triangles"); return GI_C_ERROR; }
   s->stats.inactiveTriangleCount = inactive;
   if (inactive) warnInactive(H.meshBuilds, perMesh);
   H.bvh = Bvh8{}; H.bvh.maxDepth = first.maxDepth; H.bvh.activeTris = first.activeTris;
   H.triFaceId.clear(); H.flatOfOrig.clear();
-  s->shadePacked = true;
-  s->shadowOrder = -1; s->shadowOrderRays[0] = s->shadowOrderRays[1] = s->shadowOrderSteps[0] = s->shadowOrderSteps[1] = 0;
-  s->nodeCount = first.nodeCount; s->triCount = n; s->bvhDepth = first.maxDepth > 1u ? first.maxDepth - 1u : 1u;
-  setSceneBounds(s, std::vector<Node8>{first.root});
-  s->stats.bvhBuildMs = buildMs; s->stats.uploadMs = uploadMs;
-  s->stats.nodeCount = s->nodeCount; s->stats.triangleCount = s->triCount;
-  if (timing) fprintf(stderr, "[gatling_gi] scene (device build): %u nodes, %u triangles, %u levels (traversal stack need %u)\n", s->nodeCount, s->triCount,
-      first.maxDepth, s->bvhDepth);
-  s->host = std::move(hostPtr);
-  return GI_C_OK;
+  return finishBuild(s, hostPtr, first.nodeCount, n, std::vector<Node8>{first.root}, buildMs, uploadMs, " (device build)");
 }
 
 int buildScene(GiCScene* s)
@@ -464,12 +530,13 @@ int buildScene(GiCScene* s)
   s->host.reset(); // (a failed build leaves no stale host copy behind)
   for (GiCMesh* m : s->meshes) { m->builtInstances = 0xffffffffu; m->xformDirty = false; m->instDirty.clear(); m->visToggled = false; }
   std::vector<FVertex>& verts = H.verts; std::vector<InstanceRec>& instances = H.instances; std::vector<TriRec> tris; std::vector<int32_t> faceIdOf;
-  std::vector<MaterialRec>& mats = H.mats;
-  buildMaterialRecords(s, mats);
+  buildMaterialRecords(s, H.mats);
   uint32_t meshIdx = 0;
   std::vector<MeshBuild>& meshBuilds = H.meshBuilds; // visible meshes in scene order (two-level layout, incremental updates)
   std::vector<MeshRec>& meshRecs = H.meshRecs; std::vector<float>& sceneData = H.sceneData;
-  s->classMask = 0; s->hasCutouts = false; s->classTextured = 0; s->shadeClassMask = 0; s->shadeClassTextured = 0;
+  size_t upper = 0; // one allocation for the flattened triangles (an upper bound: a visible mesh may yet be left out)
+  for (const GiCMesh* m : s->meshes) if (m->visible) upper += m->faces.size() * (m->instanceTransforms.size() / 16);
+  tris.reserve(upper); faceIdOf.reserve(upper);
   for (GiCMesh* m : s->meshes) {
     if (!m->visible) continue; // Gi.cpp:801-804
     if (m->faces.empty()) continue;
@@ -477,7 +544,7 @@ int buildScene(GiCScene* s)
     if (mit == s->materials.end()) { fprintf(stderr, "[gatling_gi] invalid BLAS material for mesh %s\n", m->name.c_str()); continue; } // Gi.cpp:818-822
     const uint32_t material = (uint32_t)(mit - s->materials.begin());
     if (material > 0x00ffffffu) { setError("too many materials"); return GI_C_ERROR; }
-    const uint32_t matFlags = meshMatFlags(s, mats[material], material, m);
+    const uint32_t matFlags = meshMatFlags(H.mats[material], material, m);
     const uint32_t vertexOffset = (uint32_t)verts.size();
     appendMeshSceneData(m, *mit, vertexOffset, meshRecs, sceneData);
     for (const GiCVertex& vIn : m->vertices) { // Gi.cpp:848-861: quantise normal/tangent to octahedral unorm2x16, then decode once
@@ -505,23 +572,13 @@ int buildScene(GiCScene* s)
     m->builtInstances = (uint32_t)instCount;
     meshBuilds.push_back(MeshBuild{m, vertexOffset, matFlags, (uint32_t)instances.size(), (uint32_t)instCount, (uint32_t)tris.size(), meshIdx, meshFaceIdAov});
     meshBuilds.back().idBase = meshBuilds.back().triFirst;
-    for (size_t ii = 0; ii < instCount; ii++) { // Gi.cpp:1188-1202
-      InstanceRec ir{};
-      composeTransform(m->transform, &m->instanceTransforms[16 * ii], ir.o2w);
-      invert3x3(ir.o2w, ir.w2o);
-      ir.mesh = meshIdx; ir.instanceId = ii < m->instanceIds.size() ? m->instanceIds[ii] : (int32_t)ii;
-      ir.pad = (uint32_t)m->id; // object id
-      uint32_t instIdx = (uint32_t)instances.size();
-      instances.push_back(ir);
-      const bool usable = usableInstance(ir);
-      for (uint32_t f = 0; f < (uint32_t)m->faces.size(); f++) {
-        TriRec t;
-        flattenTriangle(ir, usable, m, f, t);
-        for (int a = 0; a < 3; a++) t.vi[a] = vertexOffset + m->faces[f].v_i[a];
-        t.instance = instIdx; t.prim = f; t.origId = (uint32_t)tris.size(); t.matFlags = matFlags;
-        tris.push_back(t);
-        faceIdOf.push_back(meshFaceIdAov[f]);
-      }
+    const size_t nf = m->faces.size(), first = tris.size();
+    tris.resize(first + instCount * nf);
+    for (size_t ii = 0; ii < instCount; ii++) {
+      const uint32_t instIdx = (uint32_t)instances.size(), idBase = (uint32_t)(first + ii * nf);
+      instances.push_back(makeInstanceRec(m, meshIdx, ii));
+      flattenInstance(instances.back(), instIdx, m, vertexOffset, matFlags, idBase, NOT_PACKED, &tris[idBase]); // (packed or not is known once the BVH is built)
+      faceIdOf.insert(faceIdOf.end(), meshFaceIdAov.begin(), meshFaceIdAov.end());
     }
     meshIdx++;
   }
@@ -550,9 +607,7 @@ int buildScene(GiCScene* s)
     for (size_t i = 0; i < bvh.tris.size(); i++) H.flatOfOrig[bvh.tris[i].origId] = (uint32_t)i;
   }
   double t1 = nowMs();
-  // the deepest traversal variant keeps 16 stack entries in LDS and OVF_STACK = 40 in scratch; trav_node_pick does not bound-check the spill.  The limit stays
-  // at 1 + 8 + 40 levels, the depth the 8-entry spilling variant of earlier versions could hold
-  if (bvh.maxDepth > 1u + 8u + 40u) { setError("scene BVH is deeper than the traversal stack (49 levels): degenerate geometry (long chains of nested splits)");
+  if (bvh.maxDepth > kMaxBvhDepth) { setError("scene BVH is deeper than the traversal stack (49 levels): degenerate geometry (long chains of nested splits)");
       return GI_C_ERROR; }
   if (bvh.tris.size() >= (1u << 26) && !s->twoLevel) {
     setError("scene has 2^26 or more triangles after instancing and no two-level layout (it is switched off, or its unique mesh triangles exceed 2^26 too): "
@@ -594,26 +649,9 @@ int buildScene(GiCScene* s)
       H.triGeomNormal[i] = F4{n[0], n[1], n[2], 0.0f};
     }
   }
-  s->shadePacked = H.shadePacked;
-  // a new tree: the shadow walks' order is chosen anew
-  s->shadowOrder = -1; s->shadowOrderRays[0] = s->shadowOrderRays[1] = s->shadowOrderSteps[0] = s->shadowOrderSteps[1] = 0;
-  // one copy of the scene per device this scene renders on
-  const uint32_t nDev = sceneDeviceCount(s);
-  // a new replica has no lights yet
-  while (s->replicas.size() + 1u < nDev) { s->replicas.emplace_back(new SceneDevice()); s->replicas.back()->slot = (uint32_t)s->replicas.size();
-      s->dirty |= DIRTY_LIGHTS; }
-  for (uint32_t d = 0; d < nDev; d++)
-    if (uploadSceneTo(s, sceneDevice(s, d), H) != GI_C_OK) { (void)hipSetDevice(g_ctx.device); return GI_C_ERROR; }
-  HIP_TRY(hipSetDevice(g_ctx.device));
-  // stack entries a walk can need: a pick at level L pushes the rest of level L-1's group (gi_traversal.h trav_node_pick), the root level pushes nothing
-  s->nodeCount = (uint32_t)bvh.nodes.size(); s->triCount = (uint32_t)bvh.tris.size(); s->bvhDepth = bvh.maxDepth > 1u ? bvh.maxDepth - 1u : 1u;
-  setSceneBounds(s, bvh.nodes);
-  s->stats.bvhBuildMs = t1 - t0; s->stats.uploadMs = nowMs() - t1;
-  s->stats.nodeCount = s->nodeCount; s->stats.triangleCount = s->triCount;
-  if (getenv("GATLING_BUILD_TIMING")) fprintf(stderr, "[gatling_gi] scene: %u nodes, %u triangles, %u levels (traversal stack need %u)\n", s->nodeCount,
-      s->triCount, bvh.maxDepth, s->bvhDepth);
-  s->host = std::move(hostPtr);
-  return GI_C_OK;
+  ensureReplicas(s);
+  if (onSceneDevices(s, sceneDeviceCount(s), [&](SceneDevice& D, hipStream_t st) { return uploadSceneTo(s, D, H, st); }) != GI_C_OK) return GI_C_ERROR;
+  return finishBuild(s, hostPtr, (uint32_t)bvh.nodes.size(), (uint32_t)bvh.tris.size(), bvh.nodes, t1 - t0, nowMs() - t1, "");
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -647,23 +685,10 @@ void nodeBounds(const Node8& n, float box[6])
 struct PartBuild { InstanceRec inst; Bvh8 bvh; };
 void buildPart(const MeshBuild& mb, uint32_t instInMesh, bool packed, PartBuild& out)
 {
-  const GiCMesh* m = mb.m;
-  InstanceRec ir{};
-  composeTransform(m->transform, &m->instanceTransforms[16 * (size_t)instInMesh], ir.o2w);
-  invert3x3(ir.o2w, ir.w2o);
-  ir.mesh = mb.meshIdx; ir.instanceId = instInMesh < m->instanceIds.size() ? m->instanceIds[instInMesh] : (int32_t)instInMesh;
-  ir.pad = (uint32_t)m->id;
-  out.inst = ir;
-  const uint32_t nf = (uint32_t)m->faces.size(), instIdx = mb.instFirst + instInMesh;
-  std::vector<TriRec> tris(nf);
-  const bool usable = usableInstance(ir);
-  for (uint32_t f = 0; f < nf; f++) { // as buildScene
-    TriRec& t = tris[f];
-    flattenTriangle(ir, usable, m, f, t);
-    for (int a = 0; a < 3; a++) t.vi[a] = mb.vertexOffset + m->faces[f].v_i[a];
-    t.instance = instIdx; t.prim = f; t.origId = f; t.matFlags = mb.matFlags;
-    if (packed) t.vi[0] = mb.shadeBase + f;
-  }
+  out.inst = makeInstanceRec(mb.m, mb.meshIdx, instInMesh);
+  std::vector<TriRec> tris(mb.m->faces.size());
+  // (ids from 0: placePart adds the instance's base)
+  flattenInstance(out.inst, mb.instFirst + instInMesh, mb.m, mb.vertexOffset, mb.matFlags, 0u, packed ? mb.shadeBase : NOT_PACKED, tris.data());
   buildBvh8(tris, out.bvh);
 }
 
@@ -711,18 +736,22 @@ int rebuildTop(GiCScene* s, SceneHost& H)
   std::copy(top.nodes.begin(), top.nodes.end(), H.bvh.nodes.begin());
   for (size_t i = top.nodes.size(); i < H.topCap; i++) memset(&H.bvh.nodes[i], 0, sizeof(Node8));
   H.bvh.maxDepth = top.maxDepth + (subDepth > 0u ? subDepth - 1u : 0u); // the copied roots are the subtrees' first level
-  if (H.bvh.maxDepth > 1u + 8u + 40u) { setError("scene BVH is deeper than the traversal stack (49 levels)"); return GI_C_ERROR; }
+  if (H.bvh.maxDepth > kMaxBvhDepth) { setError("scene BVH is deeper than the traversal stack (49 levels)"); return GI_C_ERROR; }
   s->bvhDepth = H.bvh.maxDepth > 1u ? H.bvh.maxDepth - 1u : 1u;
   return GI_C_OK;
 }
 
-// true: handled incrementally; false: the caller must run a full buildScene (not an error)
-int updateTransforms(GiCScene* s, bool& handled)
+struct UpdateCost { double buildMs = 0.0, uploadMs = 0.0; }; // what an update spent on host-side tree building, and on everything else (syncSceneGeometry)
+// The host copy of a scene that may be edited in place, or null: no host copy, or GATLING_OPTIONS=incremental=0.  (The floor of kIncrementalMinTris triangles
+// stays with each update: what it counts differs -- the resident triangles, or for a visibility edit the visible ones.)
+static SceneHost* incrementalHost(GiCScene* s) { return optionValue("incremental", 1) ? s->host.get() : nullptr; }
+
+// handled true: done incrementally; left false: the caller must run a full buildScene (not an error)
+static int updateTransforms(GiCScene* s, bool& handled, UpdateCost& cost)
 {
-  handled = false;
-  if (!s->host || s->twoLevel || s->triCount < 4096u) return GI_C_OK; // small scenes rebuild in no time (and must stay LDS-resident)
-  if (!optionValue("incremental", 1)) return GI_C_OK;
-  SceneHost& H = *s->host;
+  SceneHost* host = incrementalHost(s);
+  if (!host || s->twoLevel || s->triCount < kIncrementalMinTris) return GI_C_OK; // (the floor: resident triangles)
+  SceneHost& H = *host;
   for (const MeshBuild& mb : H.meshBuilds) if (mb.m->builtInstances != mb.instCount) return GI_C_OK; // (cannot happen: count changes raise DIRTY_BVH)
   const double t0 = nowMs();
   std::vector<uint32_t> dirtyParts;
@@ -765,16 +794,11 @@ int updateTransforms(GiCScene* s, bool& handled)
   for (GiCMesh* m : s->meshes) { m->xformDirty = false; m->instDirty.clear(); }
   const double t1 = nowMs();
   // --- upload: everything after the re-layout, else the moved parts' ranges, their InstanceRecs and the top region
-  const uint32_t nDev = std::min<uint32_t>(sceneDeviceCount(s), (uint32_t)s->replicas.size() + 1u);
   s->nodeCount = (uint32_t)H.bvh.nodes.size();
   setSceneBounds(s, H.bvh.nodes);
-  for (uint32_t d = 0; d < nDev; d++) {
-    SceneDevice& D = sceneDevice(s, d);
-    if (converted) { if (uploadSceneTo(s, D, H) != GI_C_OK) { (void)hipSetDevice(g_ctx.device); return GI_C_ERROR; } continue; }
-    const DevCtx& ctx = g_ctx.devs[d];
-    HIP_TRY(hipSetDevice(ctx.device));
-    hipStream_t st = ctx.stream;
-    HIP_TRY(hipMemcpyAsync(D.dNodes.ptr, H.bvh.nodes.data(), (size_t)H.topCap * sizeof(Node8), hipMemcpyHostToDevice, st));
+  if (onSceneDevices(s, residentDeviceCount(s), [&](SceneDevice& D, hipStream_t st) -> int {
+    if (converted) return uploadSceneTo(s, D, H, st);
+    if (uploadTopTree(D, H, st) != GI_C_OK) return GI_C_ERROR;
     for (uint32_t i : dirtyParts) {
       const InstPart& P = H.parts[i];
       const uint32_t instIdx = H.meshBuilds[P.meshBuild].instFirst + P.instInMesh;
@@ -784,13 +808,12 @@ int updateTransforms(GiCScene* s, bool& handled)
       HIP_TRY(hipMemcpyAsync(D.dInstances.ptr + instIdx, &H.instances[instIdx], sizeof(InstanceRec), hipMemcpyHostToDevice, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
-  }
-  HIP_TRY(hipSetDevice(g_ctx.device));
-  s->stats.bvhBuildMs = t1 - t0; s->stats.uploadMs = nowMs() - t1;
-  s->stats.nodeCount = s->nodeCount; s->stats.triangleCount = s->triCount;
+    return GI_C_OK;
+  }) != GI_C_OK) return GI_C_ERROR;
+  cost.buildMs = t1 - t0; cost.uploadMs = nowMs() - t1;
   if (getenv("GATLING_BUILD_TIMING")) fprintf(stderr, "[gatling_gi] transform update: %s, %zu part(s) rebuilt of %zu, host %.1f ms, upload %.1f ms\n",
                                               converted ? "scene re-laid out as per-instance subtrees" : "incremental", converted
-                                                  ? H.parts.size() : dirtyParts.size(), H.parts.size(), t1 - t0, nowMs() - t1);
+                                                  ? H.parts.size() : dirtyParts.size(), H.parts.size(), cost.buildMs, cost.uploadMs);
   handled = true;
   return GI_C_OK;
 }
@@ -801,16 +824,15 @@ int updateTransforms(GiCScene* s, bool& handled)
 // from them.  The small arrays are rebuilt by the functions buildScene uses and re-sent whole; the word is patched where it lives, in device memory
 // (gi_patch.hip k_patch_mat_flags) -- a device-built scene keeps no host copy of its triangles, and re-sending them would be the full upload again.
 // Covered: the flat layout in all its forms (host-built, device-built, partitioned) and the two-level layout (same flat triangles + InstTrav::matFlags, one
-// record per instance, re-sent).  Falls back to buildScene (handled = false, not an error): no host copy of the scene, fewer than 4096 triangles (as
-// updateTransforms), GATLING_OPTIONS=incremental=0, or the set of meshes in the scene changes -- a mesh that was left out for an invalid material gets a
+// record per instance, re-sent).  Falls back to buildScene (handled = false, not an error): no host copy of the scene, fewer than kIncrementalMinTris
+// triangles (as updateTransforms), GATLING_OPTIONS=incremental=0, or the set of meshes in the scene changes -- a mesh that was left out for an invalid material gets a
 // valid one or the reverse (the scene-order ids of every later triangle shift).
 // ---------------------------------------------------------------------------------------------------------------
-int updateMaterials(GiCScene* s, bool& handled)
+static int updateMaterials(GiCScene* s, bool& handled, UpdateCost& cost)
 {
-  handled = false;
-  if (!s->host || s->triCount < 4096u) return GI_C_OK; // small scenes rebuild in no time
-  if (!optionValue("incremental", 1)) return GI_C_OK;
-  SceneHost& H = *s->host;
+  SceneHost* host = incrementalHost(s);
+  if (!host || s->triCount < kIncrementalMinTris) return GI_C_OK; // (the floor: resident triangles)
+  SceneHost& H = *host;
   const double t0 = nowMs();
   { // the same meshes, in the same order, as the built scene holds?
     size_t b = 0;
@@ -828,18 +850,13 @@ int updateMaterials(GiCScene* s, bool& handled)
   if (s->materials.size() > 0x01000000u) { setError("too many materials"); return GI_C_ERROR; }
   // --- host: material records, scene data, every mesh's word, the scene's class masks
   buildMaterialRecords(s, H.mats);
-  const bool hadCutouts = s->hasCutouts;
-  s->classMask = 0; s->hasCutouts = false; s->classTextured = 0; s->shadeClassMask = 0; s->shadeClassTextured = 0;
   std::vector<MeshRec> meshRecs; std::vector<float> sceneData;
   std::vector<uint32_t> wordOfMesh(H.meshBuilds.size(), 0u);
   std::vector<uint8_t> changed(H.meshBuilds.size(), 0);
   uint32_t meshesChanged = 0; uint64_t trisPatched = 0;
   for (MeshBuild& mb : H.meshBuilds) {
     const uint32_t material = (uint32_t)(std::find(s->materials.begin(), s->materials.end(), mb.m->material) - s->materials.begin());
-    const uint32_t masks[4] = {s->classMask, s->classTextured, s->shadeClassMask, s->shadeClassTextured}; const bool cutouts = s->hasCutouts;
-    const uint32_t word = meshMatFlags(s, H.mats[material], material, mb.m);
-    if (mb.hidden) { s->classMask = masks[0]; s->classTextured = masks[1]; s->shadeClassMask = masks[2]; s->shadeClassTextured = masks[3];
-        s->hasCutouts = cutouts; } // (a hidden mesh launches no kernel variant, as in a fresh build without it)
+    const uint32_t word = meshMatFlags(H.mats[material], material, mb.m);
     appendMeshSceneData(mb.m, mb.m->material, mb.vertexOffset, meshRecs, sceneData);
     wordOfMesh[mb.meshIdx] = word;
     if (word != mb.matFlags) { changed[mb.meshIdx] = 1; meshesChanged++; trisPatched += (uint64_t)mb.m->faces.size() * mb.instCount; mb.matFlags = word; }
@@ -850,18 +867,11 @@ int updateMaterials(GiCScene* s, bool& handled)
     for (TriRec& t : H.bvh.tris) { const uint32_t mesh = H.instances[t.instance].mesh; if (changed[mesh]) t.matFlags = wordOfMesh[mesh]; }
     for (size_t i = 0; i < H.two.instTrav.size(); i++) H.two.instTrav[i].matFlags = wordOfMesh[H.instances[i].mesh];
   }
-  if (s->hasCutouts != hadCutouts) { // the shadow walks' order was chosen for walks with / without the any-hit test: chosen anew
-    s->shadowOrder = -1; s->shadowOrderRays[0] = s->shadowOrderRays[1] = s->shadowOrderSteps[0] = s->shadowOrderSteps[1] = 0;
-  }
+  deriveSceneClasses(s, H, false);
   const double t1 = nowMs();
   // --- every device of the scene, on its own stream: the small arrays, then the patch kernel
-  const uint32_t nDev = std::min<uint32_t>(sceneDeviceCount(s), (uint32_t)s->replicas.size() + 1u);
   double textureMs = 0.0, patchMs = 0.0;
-  for (uint32_t d = 0; d < nDev; d++) {
-    SceneDevice& D = sceneDevice(s, d);
-    const DevCtx& ctx = g_ctx.devs[D.slot];
-    HIP_TRY(hipSetDevice(ctx.device));
-    hipStream_t st = ctx.stream;
+  if (onSceneDevices(s, residentDeviceCount(s), [&](SceneDevice& D, hipStream_t st) -> int {
     const double ta = nowMs();
     int rc = uploadTexturesTo(s, D, st);
     const double tb = nowMs();
@@ -875,12 +885,11 @@ int updateMaterials(GiCScene* s, bool& handled)
     }
     if (rc == GI_C_OK && (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) { setError("material update: device error"); rc = GI_C_ERROR; }
     dWords.release();
-    if (rc != GI_C_OK) { (void)hipSetDevice(g_ctx.device); return GI_C_ERROR; }
     textureMs += tb - ta; patchMs += nowMs() - tb;
-  }
-  HIP_TRY(hipSetDevice(g_ctx.device));
+    return rc;
+  }) != GI_C_OK) return GI_C_ERROR;
   const double t2 = nowMs();
-  s->stats.bvhBuildMs = 0.0; s->stats.uploadMs = t2 - t0;
+  cost.uploadMs = t2 - t0; // (no tree was built: buildMs stays 0)
   if (getenv("GATLING_BUILD_TIMING")) fprintf(stderr, "[gatling_gi] material update: %u mesh(es) with a new word of %zu, %llu triangle(s) patched, host %.2f ms, "
                                               "device %.2f ms (texture table %.2f ms, other tables + patch kernel %.2f ms)\n", meshesChanged, H.meshBuilds.size(),
                                               (unsigned long long)trisPatched, t1 - t0, t2 - t1, textureMs, patchMs);
@@ -899,8 +908,8 @@ int updateMaterials(GiCScene* s, bool& handled)
 // MeshBuild::hidden / idBase hold the state; updateTransforms and updateMaterials respect it, so a hide composes with a move and a material edit, before
 // the same render too.  Falls back to buildScene (handled = false, not an error): no host copy of the scene, GATLING_OPTIONS=incremental=0, the two-level
 // layout (SceneView::flatOfOrig is indexed by the ids this renumbers), a toggled mesh that is not part of the built scene (it was invisible or had no valid
-// material when the scene was built: it has no records on the device), fewer than 4096 visible flattened triangles after the edit (every mesh hidden
-// included).  The caller has established that nothing but visibility toggles asked for the rebuild.
+// material when the scene was built: it has no records on the device), fewer than kIncrementalMinTris visible flattened triangles after the edit (every mesh
+// hidden included).  The caller has established that nothing but visibility toggles asked for the rebuild.
 // ---------------------------------------------------------------------------------------------------------------
 static bool visibilityUpdatesWanted(const GiCScene* s)
 {
@@ -908,12 +917,11 @@ static bool visibilityUpdatesWanted(const GiCScene* s)
   return o >= 0 ? o == 1 : s->optVisibilityUpdates == 1;
 }
 
-int updateVisibility(GiCScene* s, bool& handled)
+static int updateVisibility(GiCScene* s, bool& handled, UpdateCost& cost)
 {
-  handled = false;
-  if (!s->host || s->twoLevel || !s->host->shadePacked) return GI_C_OK;
-  if (!optionValue("incremental", 1)) return GI_C_OK;
-  SceneHost& H = *s->host;
+  SceneHost* host = incrementalHost(s);
+  if (!host || s->twoLevel || !host->shadePacked) return GI_C_OK;
+  SceneHost& H = *host;
   const double t0 = nowMs();
   for (const GiCMesh* m : s->meshes) if (m->visToggled && m->builtInstances == 0xffffffffu) return GI_C_OK; // no records on the device: showing it rebuilds
   // --- per instance: the id base a fresh build of the visible meshes gives it against the one the resident records hold, and what happens to its records
@@ -927,7 +935,7 @@ int updateVisibility(GiCScene* s, bool& handled)
     newBase[mb.meshIdx] = hide ? mb.idBase : (uint32_t)visibleTris;
     if (!hide) visibleTris += (uint64_t)mb.instCount * mb.m->faces.size();
   }
-  if (visibleTris < 4096u) return GI_C_OK; // as updateTransforms / updateMaterials: small scenes rebuild in no time (and must stay LDS-resident)
+  if (visibleTris < kIncrementalMinTris) return GI_C_OK; // (the floor: VISIBLE triangles, what a fresh build of the edited scene would hold)
   for (const MeshBuild& mb : H.meshBuilds) {
     const bool hide = !mb.m->visible;
     const int32_t delta = (int32_t)(newBase[mb.meshIdx] - mb.idBase);
@@ -962,29 +970,15 @@ int updateVisibility(GiCScene* s, bool& handled)
     if (rebuildTop(s, H) != GI_C_OK) return GI_C_ERROR;
     setSceneBounds(s, H.bvh.nodes);
   }
-  const bool hadCutouts = s->hasCutouts;
-  s->classMask = 0; s->hasCutouts = false; s->classTextured = 0; s->shadeClassMask = 0; s->shadeClassTextured = 0;
-  for (const MeshBuild& mb : H.meshBuilds) {
-    const uint32_t material = mb.matFlags & 0x00ffffffu; // (the table of the last sync; a material edit that is due as well runs behind this update)
-    if (!mb.hidden && material < H.mats.size()) (void)meshMatFlags(s, H.mats[material], material, mb.m);
-  }
-  if (s->hasCutouts != hadCutouts) { // the shadow walks' order was chosen for walks with / without the any-hit test: chosen anew
-    s->shadowOrder = -1; s->shadowOrderRays[0] = s->shadowOrderRays[1] = s->shadowOrderSteps[0] = s->shadowOrderSteps[1] = 0;
-  }
+  deriveSceneClasses(s, H, false); // (words and table of the last sync; a material edit that is due as well runs behind this update)
   const double t1 = nowMs();
   // --- every device of the scene, on its own stream: the table and the patch kernel, the top tree of a partitioned scene.  Nothing when no word changes
-  const uint32_t nDev = std::min<uint32_t>(sceneDeviceCount(s), (uint32_t)s->replicas.size() + 1u);
-  for (uint32_t d = 0; d < nDev && (launch || topChanged); d++) {
-    SceneDevice& D = sceneDevice(s, d);
-    const DevCtx& ctx = g_ctx.devs[D.slot];
-    HIP_TRY(hipSetDevice(ctx.device));
-    hipStream_t st = ctx.stream;
+  if (onSceneDevices(s, launch || topChanged ? residentDeviceCount(s) : 0u, [&](SceneDevice& D, hipStream_t st) -> int {
     int rc = GI_C_OK;
     DeviceBuffer<VisPatch> dPatch;
     if (D.dTris.count < s->triCount || D.dInstances.count < H.instances.size() || D.dTriShade.count < H.triShade.size() || D.dNodes.count < H.topCap) {
       setError("internal: the device holds less than the scene"); rc = GI_C_ERROR; }
-    if (rc == GI_C_OK && topChanged && hipMemcpyAsync(D.dNodes.ptr, H.bvh.nodes.data(), (size_t)H.topCap * sizeof(Node8), hipMemcpyHostToDevice, st)
-        != hipSuccess) { setError("visibility update: top tree upload failed"); rc = GI_C_ERROR; }
+    if (rc == GI_C_OK && topChanged && uploadTopTree(D, H, st) != GI_C_OK) { setError("visibility update: top tree upload failed"); rc = GI_C_ERROR; }
     if (rc == GI_C_OK && launch) {
       if (dPatch.upload(patch, st)) rc = GI_C_ERROR;
       if (rc == GI_C_OK) launchPatchVisibility(st, D.dTris.ptr, s->triCount, D.dInstances.ptr, (uint32_t)H.instances.size(), dPatch.ptr, D.dTriShade.ptr,
@@ -992,12 +986,10 @@ int updateVisibility(GiCScene* s, bool& handled)
     }
     if (rc == GI_C_OK && (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) { setError("visibility update: device error"); rc = GI_C_ERROR; }
     dPatch.release();
-    if (rc != GI_C_OK) { (void)hipSetDevice(g_ctx.device); return GI_C_ERROR; }
-  }
-  HIP_TRY(hipSetDevice(g_ctx.device));
+    return rc;
+  }) != GI_C_OK) return GI_C_ERROR;
   const double t2 = nowMs();
-  // (triangleCount / nodeCount keep describing what is resident on the device, hidden triangles included: include/gi_c.h)
-  s->stats.bvhBuildMs = 0.0; s->stats.uploadMs = t2 - t0;
+  cost.uploadMs = t2 - t0; // (no tree was built: buildMs stays 0; triangleCount / nodeCount keep describing what is resident, hidden triangles included)
   if (getenv("GATLING_BUILD_TIMING")) fprintf(stderr, "[gatling_gi] visibility update: %u mesh(es) hidden, %u shown, %u renumbered of %zu, %llu visible "
                                               "triangle(s) of %u resident, host %.2f ms, device %.2f ms\n", hides, shows, renumbered, H.meshBuilds.size(),
                                               (unsigned long long)visibleTris, s->triCount, t1 - t0, t2 - t1);
@@ -1005,42 +997,38 @@ int updateVisibility(GiCScene* s, bool& handled)
   return GI_C_OK;
 }
 
-// brings the device scene up to date with the host-side edits: incremental for visibility-only (opt-in), material-only and transform-only edits (all three
-// may be due, and run in this order), else a full build
+// brings the device scene up to date with the host-side edits: incremental for DIRTY_BVH raised by visibility toggles alone (opt-in: ids renumbered, the
+// toggled meshes' triangles hidden / shown in place), for material-side edits alone (the small arrays + one word per triangle) and for transform edits alone
+// (those instances re-transformed / re-braided) -- all three may be due, and run in this order -- else a full build
 int syncSceneGeometry(GiCScene* s)
 {
-  double materialMs = 0.0; // time of the updates that ran in front of another one: all go into the statistics
-  // DIRTY_BVH raised by visibility toggles alone: the ids are renumbered and the toggled meshes' triangles hidden / shown in place
-  if ((s->dirty & DIRTY_BVH) && !s->rebuildDue && visibilityUpdatesWanted(s)) {
-    bool handled = false;
-    s->generation++;
-    if (updateVisibility(s, handled) != GI_C_OK) { s->rebuildDue = true; return GI_C_ERROR; } // (half-updated arrays: the next render rebuilds)
-    if (handled) { s->dirty &= ~DIRTY_BVH; s->visibilityUpdates++; materialMs = s->stats.uploadMs; }
+  UpdateCost spent; bool updated = false; // what the updates that ran spent: all of them go into the statistics
+  // One update path: it runs when `due`, and either handles the edit (its dirty bits are cleared, it is counted), declines (not an error) or fails.  The paths
+  // differ in the dirty bits: a visibility update is due BECAUSE a rebuild is asked for, so it clears DIRTY_BVH and a decline has nothing to raise; a material
+  // or transform update that declines raises DIRTY_BVH (and rebuildDue) to get the full build below; DIRTY_XFORM is cleared at the end for every path.  An
+  // error leaves half-updated arrays: the next render rebuilds (rebuildDue; after a material update DIRTY_BVH as well, its own bit would try the update again).
+  auto run = [&](bool due, int (*update)(GiCScene*, bool&, UpdateCost&), uint32_t counter, uint32_t handledClears, uint32_t declineRaises, uint32_t errorRaises) -> int {
+    if (!due) return GI_C_OK;
+    bool handled = false; UpdateCost cost; s->generation++;
+    if (update(s, handled, cost) != GI_C_OK) { s->dirty |= errorRaises; s->rebuildDue = true; return GI_C_ERROR; }
+    if (handled) { s->dirty &= ~handledClears; s->updateCounts[counter]++; spent.buildMs += cost.buildMs; spent.uploadMs += cost.uploadMs; updated = true; }
+    else if (declineRaises) { s->dirty |= declineRaises; s->rebuildDue = true; }
     s->dirty |= DIRTY_FRAMEBUFFER;
-  }
-  if ((s->dirty & DIRTY_MATERIALS) && !(s->dirty & DIRTY_BVH)) { // materials, assignments, textures, primvars: the small arrays + one word per triangle
-    bool handled = false;
-    s->generation++;
-    if (updateMaterials(s, handled) != GI_C_OK) { s->dirty |= DIRTY_BVH; s->rebuildDue = true; return GI_C_ERROR; } // (half-updated arrays: the next render rebuilds)
-    if (handled) { s->dirty &= ~DIRTY_MATERIALS; s->updateCounts[2]++; s->stats.uploadMs += materialMs; materialMs = s->stats.uploadMs; }
-    else { s->dirty |= DIRTY_BVH; s->rebuildDue = true; }
-    s->dirty |= DIRTY_FRAMEBUFFER;
-  }
-  if ((s->dirty & DIRTY_XFORM) && !(s->dirty & (DIRTY_BVH | DIRTY_MATERIALS))) { // only transforms changed: re-transform / re-braid those instances
-    bool handled = false;
-    s->generation++;
-    if (updateTransforms(s, handled) != GI_C_OK) { s->rebuildDue = true; return GI_C_ERROR; }
-    if (handled) { s->updateCounts[1]++; s->stats.uploadMs += materialMs; } else { s->dirty |= DIRTY_BVH; s->rebuildDue = true; }
-    s->dirty |= DIRTY_FRAMEBUFFER;
-  }
+    return GI_C_OK;
+  };
+  int rc = run((s->dirty & DIRTY_BVH) && !s->rebuildDue && visibilityUpdatesWanted(s), updateVisibility, UPDATE_VISIBILITY, DIRTY_BVH, 0u, 0u);
+  if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_MATERIALS) && !(s->dirty & DIRTY_BVH), updateMaterials, UPDATE_MATERIAL, DIRTY_MATERIALS, DIRTY_BVH, DIRTY_BVH);
+  if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_XFORM) && !(s->dirty & (DIRTY_BVH | DIRTY_MATERIALS)), updateTransforms, UPDATE_TRANSFORM, 0u, DIRTY_BVH, 0u);
+  if (updated) { s->stats.bvhBuildMs = spent.buildMs; s->stats.uploadMs = spent.uploadMs; s->stats.nodeCount = s->nodeCount;
+      s->stats.triangleCount = s->triCount; } // (a full build below overrides all four)
+  if (rc != GI_C_OK) return rc;
   if (s->dirty & (DIRTY_BVH | DIRTY_MATERIALS)) {
     s->generation++;
     if (buildScene(s) != GI_C_OK) return GI_C_ERROR;
-    s->updateCounts[0]++;
+    s->updateCounts[UPDATE_FULL]++;
     s->dirty &= ~(DIRTY_BVH | DIRTY_MATERIALS); s->dirty |= DIRTY_FRAMEBUFFER;
   }
-  s->dirty &= ~DIRTY_XFORM;
-  s->rebuildDue = false;
+  s->dirty &= ~DIRTY_XFORM; s->rebuildDue = false;
   for (GiCMesh* m : s->meshes) m->visToggled = false;
   return GI_C_OK;
 }

@@ -409,7 +409,7 @@ extern "C" int giCDebugSceneUpdateCounts(const GiCScene* scene, uint64_t* outCou
   GiCScene* s = const_cast<GiCScene*>(scene);
   if (!s || !outCounts) { setError("giCDebugSceneUpdateCounts: bad arguments"); return GI_C_ERROR; }
   std::lock_guard<std::mutex> guard(s->mutex);
-  for (int i = 0; i < 3; i++) outCounts[i] = s->updateCounts[i];
+  outCounts[0] = s->updateCounts[UPDATE_FULL]; outCounts[1] = s->updateCounts[UPDATE_TRANSFORM]; outCounts[2] = s->updateCounts[UPDATE_MATERIAL];
   return GI_C_OK;
 }
 
@@ -418,6 +418,16 @@ extern "C" int giCDebugSceneVisibilityUpdateCount(const GiCScene* scene, uint64_
   GiCScene* s = const_cast<GiCScene*>(scene);
   if (!s || !outCount) { setError("giCDebugSceneVisibilityUpdateCount: bad arguments"); return GI_C_ERROR; }
   std::lock_guard<std::mutex> guard(s->mutex);
-  *outCount = s->visibilityUpdates;
+  *outCount = s->updateCounts[UPDATE_VISIBILITY];
+  return GI_C_OK;
+}
+
+// giCDebugSceneClassState: what picks a render's kernel variants (gi_build.cpp deriveSceneClasses), as the last scene sync left it.  Host only.
+extern "C" int giCDebugSceneClassState(const GiCScene* scene, uint32_t* out)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!s || !out) { setError("giCDebugSceneClassState: bad arguments"); return GI_C_ERROR; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  out[0] = s->classMask; out[1] = s->classTextured; out[2] = s->shadeClassMask; out[3] = s->shadeClassTextured; out[4] = s->hasCutouts ? 1u : 0u;
   return GI_C_OK;
 }

@@ -300,6 +300,7 @@ struct SceneHost {
   bool deviceBuilt = false;
 };
 
+enum : uint32_t { UPDATE_FULL = 0, UPDATE_TRANSFORM = 1, UPDATE_MATERIAL = 2, UPDATE_VISIBILITY = 3 }; // GiCScene::updateCounts
 struct GiCScene : SceneDevice {
   std::mutex mutex;
   uint32_t dirty = DIRTY_ALL;
@@ -354,9 +355,9 @@ struct GiCScene : SceneDevice {
   // contents of the device arrays: bumped by every scene build, transform update, material update and light upload --
   // a look-ahead window traced under another generation is not served from
   uint64_t generation = 0;
-  uint64_t updateCounts[3] = {0, 0, 0}; // syncSceneGeometry: full builds, incremental transform updates, incremental material updates (giCDebugSceneUpdateCounts)
+  // syncSceneGeometry, by UPDATE_*: full builds and incremental updates (giCDebugSceneUpdateCounts: the first three; giCDebugSceneVisibilityUpdateCount)
+  uint64_t updateCounts[4] = {0, 0, 0, 0};
   int32_t optVisibilityUpdates = 0; // GI_C_SCENE_OPTION_VISIBILITY_UPDATES: 1 = visibility edits are applied to the resident scene (updateVisibility)
-  uint64_t visibilityUpdates = 0;   // syncSceneGeometry: incremental visibility updates (giCDebugSceneVisibilityUpdateCount)
   // DIRTY_BVH was raised by something other than giCSetMeshVisibility since the last syncSceneGeometry (raiseRebuild): the rebuild is due whatever was toggled
   bool rebuildDue = true;
 };

@@ -376,7 +376,7 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * the device build when one ran).  A caller compares giCGetApiVersion() with the GI_C_API_VERSION it was built with.
  * Still 8 with GI_C_SCENE_OPTION_SAMPLE_LOOKAHEAD and giCGetLookaheadStats: no struct grew and no entry point changed meaning -- both are additions that a caller
  * built against an earlier header never sees.  A caller probes for them: giCSetSceneOption answers GI_C_ERROR for an option the library does not know.
- * The same holds for GI_C_SCENE_OPTION_VISIBILITY_UPDATES and giCDebugSceneVisibilityUpdateCount. */
+ * The same holds for GI_C_SCENE_OPTION_VISIBILITY_UPDATES, giCDebugSceneVisibilityUpdateCount and giCDebugSceneClassState. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -583,6 +583,10 @@ int giCDebugSceneUpdateCounts(const GiCScene* scene, uint64_t* outCounts /* 3 */
 /* [ext] how often the scene was brought up to date by an incremental visibility update (GI_C_SCENE_OPTION_VISIBILITY_UPDATES); such an update is not counted
  * in giCDebugSceneUpdateCounts. */
 int giCDebugSceneVisibilityUpdateCount(const GiCScene* scene, uint64_t* outCount);
+/* [ext] what the last scene sync derived from the visible meshes' materials, the state that picks a render's kernel variants: out[0] the material classes in
+ * use (one bit each), [1] those with a textured material, [2] and [3] the same per shade class, [4] 1 when some visible triangle has cutout opacity.  Host
+ * only: no device work. */
+int giCDebugSceneClassState(const GiCScene* scene, uint32_t* out /* 5 */);
 
 #ifdef __cplusplus
 }

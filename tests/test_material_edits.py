@@ -1,7 +1,8 @@
 """Incremental material updates (gi_build.cpp updateMaterials, gi_patch.hip k_patch_mat_flags): after an edit of a material, a material
 assignment, a texture binding or a primvar the next render rebuilds the material / texture / scene-data tables and patches one word per flattened triangle in
 device memory instead of rebuilding the scene.  The image and the AOVs must be bit-identical to a scene built from scratch from the edited description, and to
-the oracle's render of it.
+the oracle's render of it; the class masks and the cutout flag (gi_build.cpp deriveSceneClasses; Scene.class_state), which pick a render's kernel variants and
+cannot be seen in an image, must equal those of the scene built from scratch.
 
 CPU: which dirty flags every entry point raises before and after the first build (giCDebugEditDirtyFlags).
 GPU: an edit sequence on every layout (host-built, device-built, partitioned, two-level), the fallbacks, the look-ahead window, two device contexts, random
@@ -198,8 +199,10 @@ def _check(orc, sc, step, got):
     fresh = capi.Scene(copy.deepcopy(sc.desc))
     try:
         ref = fresh.render_aovs(RS, W, H, AOVS)
+        fresh_classes = fresh.class_state()
     finally:
         fresh.close()
+    assert sc.class_state() == fresh_classes, f"{step}: class state {sc.class_state()} differs from a scene built from scratch, {fresh_classes}"
     oimg, oaov = _oracle(orc, step, sc.desc)
     for k in ["color"] + AOVS:
         assert _bits_equal(got[k], ref[k]), f"{step}: {k} differs from a scene built from scratch"

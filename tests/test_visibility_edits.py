@@ -4,9 +4,12 @@ mesh, as a fresh build without it would number them, and makes the mesh's own tr
 (partitioned layout).  The image and the AOVs must be bit-identical to a scene built from scratch from the description with `visible` flipped, and to the
 oracle's render of it.  No tolerance anywhere.
 
-CPU: the header and the harness declare the option and the counter; the API version is unchanged.
+The class masks and the cutout flag (gi_build.cpp deriveSceneClasses; Scene.class_state) pick a render's kernel variants and cannot be seen in an image: after
+every step they must equal those of the scene built from scratch.
+
+CPU: the header and the harness declare the option, the counter and the class-state query; the API version is unchanged.
 GPU: an edit sequence on every layout (host-built, device-built, partitioned, two-level), the same sequence with the option off, the fallbacks, the cutout
-flag, the look-ahead window, two device contexts, random edit sequences against the oracle.
+flag, a material assigned to a hidden mesh, the look-ahead window, two device contexts, random edit sequences against the oracle.
 
 The scene is the look-development interior of tests/test_material_edits.py at its small size (6 412 flattened triangles: above the 4 096 floor of the
 incremental paths and beyond LDS).  Scene order there: mesh 1 (two instances, 640 triangles) lies in front of mesh 3, the only mesh bound to the cutout
@@ -52,6 +55,12 @@ def test_header_declares_the_option_and_the_counter_and_keeps_api_version_8():
 def test_harness_exposes_the_option_and_the_counter():
     assert capi.OPTION_VISIBILITY_UPDATES == 11
     assert callable(capi.Scene.set_mesh_visibility) and callable(capi.Scene.visibility_update_count)
+
+
+def test_header_and_harness_declare_the_class_state_query():
+    text = open(os.path.join(ROOT, "include", "gi_c.h")).read()
+    assert re.search(r"int\s+giCDebugSceneClassState\s*\(\s*const\s+GiCScene\s*\*", text)
+    assert hasattr(capi.load_library(), "giCDebugSceneClassState") and callable(capi.Scene.class_state)
 
 
 def test_visibility_setter_keeps_raising_the_rebuild_flag():
@@ -163,8 +172,10 @@ def _check(orc, sc, key, got):
     fresh = capi.Scene(copy.deepcopy(sc.desc))
     try:
         ref = fresh.render_aovs(RS, W, H, AOVS)
+        fresh_classes = fresh.class_state()
     finally:
         fresh.close()
+    assert sc.class_state() == fresh_classes, f"{key}: class state {sc.class_state()} differs from a scene built from scratch, {fresh_classes}"
     oimg, oaov = _oracle(orc, key, sc.desc)
     for k in ["color"] + AOVS:
         assert _bits_equal(got[k], ref[k]), f"{key}: {k} differs from a scene built from scratch"
@@ -343,6 +354,38 @@ def test_hiding_the_only_cutout_mesh_and_showing_it_again(gi, orc, layout):
         _check(orc, sc, "start", got)
         for k in got:
             assert _bits_equal(got[k], first[k])
+    finally:
+        sc.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("layout", ["host", "partitioned"])
+def test_material_assigned_to_a_hidden_mesh_counts_only_once_it_is_shown(gi, orc, layout):
+    """The cutout mesh is hidden and, before the same render, bound to a material of a class no visible mesh uses: neither the cutout flag nor that class's bit
+    may be set while it is hidden (a fresh build leaves the mesh out), and the class's bit appears with the show."""
+    sc = _make(layout)
+    try:
+        sc.render(RS, W, H)
+        if layout == "partitioned":
+            _partition(sc)
+        assert [i for i, m in enumerate(sc.desc.meshes) if m.material == DIFFUSE_MATERIAL] == [MOVED] and sc.desc.materials[DIFFUSE_MATERIAL].klass == MAT_DIFFUSE
+        sc.set_mesh_material(MOVED, 4)  # the only mesh of the diffuse class leaves it
+        got = sc.render_aovs(RS, W, H, AOVS)
+        _check(orc, sc, "diffuse-class-unused", got)
+        assert sc.class_state()["classMask"] & (1 << MAT_DIFFUSE) == 0 and sc.class_state()["hasCutouts"]
+        before, vis_before = sc.update_counts(), sc.visibility_update_count()
+        sc.set_mesh_visibility(CUT, False)
+        sc.set_mesh_material(CUT, DIFFUSE_MATERIAL)  # the cutout material is bound to no mesh, the diffuse one to a hidden mesh alone
+        got = sc.render_aovs(RS, W, H, AOVS)
+        assert sc.stats()["bvhBuildMs"] == 0.0 and sc.visibility_update_count() == vis_before + 1
+        assert sc.update_counts() == {"full": before["full"], "transform": before["transform"], "material": before["material"] + 1}
+        _check(orc, sc, "hidden-mesh-reassigned", got)
+        assert sc.class_state()["classMask"] & (1 << MAT_DIFFUSE) == 0 and not sc.class_state()["hasCutouts"]
+        sc.set_mesh_visibility(CUT, True)
+        got = sc.render_aovs(RS, W, H, AOVS)
+        assert sc.stats()["bvhBuildMs"] == 0.0 and sc.update_counts()["full"] == before["full"] and sc.visibility_update_count() == vis_before + 2
+        _check(orc, sc, "reassigned-mesh-shown", got)
+        assert sc.class_state()["classMask"] & (1 << MAT_DIFFUSE) and not sc.class_state()["hasCutouts"]
     finally:
         sc.close()
 
