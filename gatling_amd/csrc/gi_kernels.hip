@@ -61,30 +61,7 @@ __global__ void k_init(PathState st, QueueSet qs, Counters* cnt, uint32_t n, uin
 // term.  Entry i of the regen queue finishes its sample (if any) into the per-sample colour buffer and takes work item
 // w = workBase + i, decoded by work_item (gi_queues.h): by default consecutive entries get consecutive samples of one pixel, pixels in 8x8 blocks.
 // ------------------------------------------------------------------------------------------------
-// FLAG_BOUNDS_RETIRE: can the ray reach the scene at all?  A slab test against the root node's bounds (host: padded beyond the dequantised child boxes),
-// widened per ray by 30 x the rounding error of (plane - origin) * (1 / d) and decided only by comparisons that a NaN fails -- so it answers "misses" for no
-// ray whose walk could accept a triangle (every triangle lies inside its leaf box, every
-// leaf box inside the root's bounds; same contract as the node test).
-__device__ __forceinline__ bool ray_misses_bounds(const FrameUniforms& U, const V3& o, const V3& d, float tMin, float tMax)
-{
-  float tn = tMin, tf = tMax;
-  const float oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
-  bool out = false;
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    const float lo = U.sceneLo[a], hi = U.sceneHi[a];
-    const float pad = (fabsf(oo[a]) + fmax2(fabsf(lo), fabsf(hi))) * 4.0e-6f;
-    if (dd[a] == 0.0f) { out = out || (oo[a] < lo - pad) || (oo[a] > hi + pad); continue; }
-    const float inv = 1.0f / dd[a];
-    const float t0 = ((lo - pad) - oo[a]) * inv, t1 = ((hi + pad) - oo[a]) * inv;
-    float nearT = t0 < t1 ? t0 : t1, farT = t0 < t1 ? t1 : t0; // (the padded planes keep their order; a NaN leaves the interval alone below)
-    nearT -= fabsf(nearT) * 1.0e-5f; farT += fabsf(farT) * 1.0e-5f;
-    if (nearT > tn) tn = nearT;
-    if (farT < tf) tf = farT;
-  }
-  return out || tn > tf;
-}
-
+// (FLAG_BOUNDS_RETIRE: ray_misses_bounds and retire_fresh_miss are in gi_stages.h -- k_path uses the same test)
 // RAYGEN_ITEMS regen entries per thread and trip: the trip is otherwise two barriers and an atomic round trip around a chain of dependent loads (entry -> slot
 // -> finished sample), and the entries of one thread are independent of each other.
 // (1 -> 2: raygen stage -6 % on C3 / C4; 4: the same, r05x)

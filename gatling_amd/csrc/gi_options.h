@@ -15,7 +15,8 @@
 //   two_level            -1        -1 = automatic (from 2^26 flattened triangles), 0 / 1 = force the flat / the two-level layout
 //   work_order           1         1 = pixel-major work items, 0 = sample-major
 //   defer_slot           1         path slots are written where a path first hits
-//   bounds_retire        1         camera rays that cannot reach the scene's bounds retire in k_raygen
+//   bounds_retire        1         camera rays that cannot reach the scene's bounds retire where they are generated: in k_raygen (wavefront pipeline,
+//                                  deferred slots) and in k_path's ring preparation (fused kernel); 0 = every camera ray is traced
 //   fused                1         LDS-resident scenes run the fused persistent kernel
 //   pool_slots           0         pin the path pool (slots); 0 = the memory plan decides
 //   sample_buffer_mb     0         pin the per-sample buffer (MiB); 0 = the memory plan decides

@@ -15,6 +15,11 @@
 // oracle's; work items are claimed in chunks of consecutive ids (sample-major: adjacent pixels of one sample index), one atomic per
 // chunk on one cursor.
 //
+// Camera rays that cannot reach the scene's bounds (FLAG_BOUNDS_RETIRE, ray_misses_bounds in gi_stages.h: the test k_raygen applies) retire where they are
+// prepared: the lane stores the sample such a path ends with (0 + 1 x background, finished) and counts its one segment; only the other rays enter the ring.
+// A wave's 64 work items are adjacent pixels of a row, so in a frame wider than the scene whole trips of whole waves were such rays (C2: 62 % of them).
+// Renders that bind a path-following debug AOV (NEE, Bounces, ClockCycles) and counting builds trace every camera ray as before (gi_render.cpp scheduleFrame).
+//
 // Not handled here (the host falls back to the wavefront pipeline): medium stacks (mediumStackSize > 0), dome-light images,
 // scenes beyond LDS, trees deeper than 8 levels.
 
@@ -68,6 +73,9 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
   __shared__ uint32_t s_pre[TRACE_BLOCK / 64][PRE_FIELDS][128]; // ring of 128 prepared rays per wave
   GI_LDS uint32_t (*pre)[128] = (GI_LDS uint32_t (*)[128])&s_pre[threadIdx.x >> 6][0][0];
   uint32_t preHead = 0u, preTail = 0u; // wave-uniform ring positions (monotonic; slot = position & 127)
+  // FLAG_BOUNDS_RETIRE: a camera ray that cannot reach the scene's bounds (ray_misses_bounds, gi_stages.h) never enters the ring -- its sample is stored where the
+  // ray is prepared, so a wave whose 64 adjacent pixels all look past the scene spends no trip (ring round trip, root-node step, miss branch) on them
+  const bool boundsRetire = (U.flags & FLAG_BOUNDS_RETIRE) != 0u;
 
   unsigned long long pc[4] = {0ull, 0ull, 0ull, 0ull}, pl[4] = {0ull, 0ull, 0ull, 0ull}, trips = 0ull, tPrev = COUNT ? __builtin_readcyclecounter() : 0ull;
   auto phase = [&](int k,
@@ -88,17 +96,35 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
           chunkNext = b; chunkEnd = (U.workTotal - b) < chunk ? U.workTotal : b + chunk;
         }
         const uint32_t avail = chunkEnd - chunkNext, take = avail < 64u ? avail : 64u;
+        uint32_t nKept = 0u;
         if (lane < take) {
           const uint32_t w = chunkNext + lane;
           const uint32_t pl = w % U.pixelCount, sl = w / U.pixelCount;
           V3 o, d; float t0, t1; uint32_t r;
           // :195 (global pixel index: the RNG is tile independent)
           make_camera_ray(U, tile_to_image_pixel(U, pl), U.sampleOffset + U.batchFirstSample + sl, o, d, t0, t1, r);
-          const uint32_t slot = (preTail + lane) & 127u;
-          pre[0][slot] = f2u(o.x); pre[1][slot] = f2u(o.y); pre[2][slot] = f2u(o.z); pre[3][slot] = f2u(d.x); pre[4][slot] = f2u(d.y); pre[5][slot] = f2u(d.z);
-          pre[6][slot] = f2u(t0); pre[7][slot] = f2u(t1); pre[8][slot] = r; pre[9][slot] = w;
+          // (the bounds and the retired sample are wave-uniform; read through an empty asm they stay in scalar registers here -- left to itself the compiler
+          // hoists what it derives from them out of the trip loop, into a dozen vector registers that then stay live through the walk and the shading)
+          float lo[3] = {U.sceneLo[0], U.sceneLo[1], U.sceneLo[2]}, hi[3] = {U.sceneHi[0], U.sceneHi[1], U.sceneHi[2]};
+          asm volatile("" : "+s"(lo[0]), "+s"(lo[1]), "+s"(lo[2]), "+s"(hi[0]), "+s"(hi[1]), "+s"(hi[2]));
+          const bool keep = !(boundsRetire && ray_misses_box(lo, hi, o, d, t0, t1));
+          const unsigned long long kept = __ballot(keep); // (of the lanes below `take`) the rays that go on take consecutive ring slots: < 64 pending + <= 64 new
+          nKept = (uint32_t)__popcll(kept);
+          if (keep) {
+            const uint32_t slot = (preTail + (uint32_t)__popcll(kept & below)) & 127u;
+            pre[0][slot] = f2u(o.x); pre[1][slot] = f2u(o.y); pre[2][slot] = f2u(o.z); pre[3][slot] = f2u(d.x); pre[4][slot] = f2u(d.y); pre[5][slot] = f2u(d.z);
+            pre[6][slot] = f2u(t0); pre[7][slot] = f2u(t1); pre[8][slot] = r; pre[9][slot] = w;
+          } else { // the whole path is this one segment: its sample is the constant retire_fresh_miss stores (the miss branch + finish_sample below)
+            float bg[3] = {U.background[0], U.background[1], U.background[2]}, maxv = U.maxSampleValue;
+            asm volatile("" : "+s"(bg[0]), "+s"(bg[1]), "+s"(bg[2]), "+s"(maxv));
+            V3 c = v3(0.0f, 0.0f, 0.0f) + v3(1.0f, 1.0f, 1.0f) * v3(bg[0], bg[1], bg[2]);
+            const float mv = fmax2(c.x, fmax2(c.y, c.z));
+            if (mv > maxv) c = c * (maxv / mv);
+            st4(&sampleBuf[(size_t)sl * U.pixelCount + pl], fmax2(0.0f, c.x), fmax2(0.0f, c.y), fmax2(0.0f, c.z), 0.0f);
+            nSeg++;
+          }
         }
-        chunkNext += take; preTail += take;
+        chunkNext += take; preTail += (uint32_t)__builtin_amdgcn_readfirstlane((int)nKept); // (take >= 1: lane 0 was in)
       }
       __atomic_signal_fence(__ATOMIC_SEQ_CST);
       const uint32_t have = preTail - preHead, take = nIdle < have ? nIdle : have;

@@ -479,6 +479,14 @@ static Schedule scheduleFrame(Frame& f)
     U.flags |= FLAG_BOUNDS_RETIRE;
     for (int a = 0; a < 3; a++) { U.sceneLo[a] = s->bounds[a]; U.sceneHi[a] = s->bounds[3 + a]; }
   }
+  // ... and in the fused kernel: k_path applies the same test where it prepares camera rays for its ring, and stores the retired sample there (gi_path.hip).
+  // With work handed out sample-major a wave holds 64 adjacent pixels of a row, so where the frame is wider than the scene whole waves would otherwise spend
+  // whole trips on rays that miss (C2: 62 % of the camera rays). pathKernelSupports has excluded dome image, medium stack and two-level; the path-following
+  // debug AOVs keep today's route (the rule of defer_slot above), and so do counting builds.
+  if (fused && s->boundsValid && optionValue("bounds_retire", 1) != 0 && !s->countTraversal && !f.ps.neeKey && !f.ps.bouncesAov && !f.ps.pathSegments) {
+    U.flags |= FLAG_BOUNDS_RETIRE;
+    for (int a = 0; a < 3; a++) { U.sceneLo[a] = s->bounds[a]; U.sceneHi[a] = s->bounds[3 + a]; }
+  }
   Schedule sch;
   sch.dynRefill = traceDynRefill(s);
   // (GATLING_OPTIONS=shadow_order=0|1 pins it)

@@ -246,6 +246,34 @@ __device__ __forceinline__ void shade_segment(const FrameUniforms& U, const Scen
   io.sdir = sdir; io.nee = nee; io.ld = ld; io.rngShadow = rngShadow;
 }
 
+// FLAG_BOUNDS_RETIRE: can the ray reach the scene at all?  A slab test against the root node's bounds (host: padded beyond the dequantised child boxes),
+// widened per ray by 30 x the rounding error of (plane - origin) * (1 / d) and decided only by comparisons that a NaN fails -- so it answers "misses" for no
+// ray whose walk could accept a triangle (every triangle lies inside its leaf box, every
+// leaf box inside the root's bounds; same contract as the node test).
+__device__ __forceinline__ bool ray_misses_box(const float (&sceneLo)[3], const float (&sceneHi)[3], const V3& o, const V3& d, float tMin, float tMax)
+{
+  float tn = tMin, tf = tMax;
+  const float oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
+  bool out = false;
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const float lo = sceneLo[a], hi = sceneHi[a];
+    const float pad = (fabsf(oo[a]) + fmax2(fabsf(lo), fabsf(hi))) * 4.0e-6f;
+    if (dd[a] == 0.0f) { out = out || (oo[a] < lo - pad) || (oo[a] > hi + pad); continue; }
+    const float inv = 1.0f / dd[a];
+    const float t0 = ((lo - pad) - oo[a]) * inv, t1 = ((hi + pad) - oo[a]) * inv;
+    float nearT = t0 < t1 ? t0 : t1, farT = t0 < t1 ? t1 : t0; // (the padded planes keep their order; a NaN leaves the interval alone below)
+    nearT -= fabsf(nearT) * 1.0e-5f; farT += fabsf(farT) * 1.0e-5f;
+    if (nearT > tn) tn = nearT;
+    if (farT < tf) tf = farT;
+  }
+  return out || tn > tf;
+}
+__device__ __forceinline__ bool ray_misses_bounds(const FrameUniforms& U, const V3& o, const V3& d, float tMin, float tMax)
+{
+  return ray_misses_box(U.sceneLo, U.sceneHi, o, d, tMin, tMax);
+}
+
 // A new path's Slot (rp_main.rgen:274-276): throughput 1, bitfield 0, radiance 0, the rng state after the camera draws, its work item
 __device__ __forceinline__ void slot_begin_path(Slot* S, uint32_t rng, uint32_t pixelLocal, uint32_t sLocal)
 {
