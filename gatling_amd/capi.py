@@ -162,6 +162,7 @@ SYMBOLS = [
     ("giCDebugTexRuntime", C.c_int, [_FP, _U, _U, _U, _U, _FP, _FP]),
     ("giCDebugEditDirtyFlags", C.c_int32, [_I, _I]), ("giCDebugSceneUpdateCounts", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugSceneVisibilityUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugSceneClassState", C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    ("giCDebugMissRect", C.c_int, [_FP, C.POINTER(GiCCameraDesc), C.POINTER(GiCRenderSettings), _U, _U, C.POINTER(C.c_uint32)]),
 ]
 
 _lib = None
@@ -190,6 +191,17 @@ def _fp(values):
 
 class GiError(RuntimeError):
     pass
+
+
+def miss_rect(bounds, camera, rs: "RenderSettings", width: int, height: int):
+    """giCDebugMissRect: (x0, y0, x1, y1) -- the image rectangle outside which every camera ray of a pixel misses `bounds` (min xyz, max xyz); the whole
+    frame when nothing can be ruled out, (0, 0, 0, 0) when everything is.  Host only: needs neither a device nor giCInitialize."""
+    L = load_library()
+    out = (C.c_uint32 * 4)()
+    cam, st = _camera(camera), _settings(rs)
+    if L.giCDebugMissRect(_fp(bounds), C.byref(cam), C.byref(st), int(width), int(height), out) != GI_C_OK:
+        raise GiError("giCDebugMissRect failed: " + L.giCGetLastError().decode())
+    return tuple(int(v) for v in out)
 
 
 _initialized = False

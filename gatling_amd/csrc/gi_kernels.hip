@@ -189,7 +189,14 @@ __global__ __launch_bounds__(BLOCK) void k_accumulate(FrameUniforms U, const F4*
   if (p >= U.pixelCount) return;
   V3 pixelColor = v3(0.0f, 0.0f, 0.0f);
   if (!firstBatch) { const F4 a = ld4(&accum[p]); pixelColor = v3(a.x, a.y, a.z); }
-  if (U.flags & FLAG_PIXEL_MAJOR) { // the pixel's samples are one contiguous run: a thread streams its own lines, eight records (one 128-byte line) per round
+  // FLAG_MISS_RECT (fused frames): k_path wrote no records for a pixel outside the rectangle -- every sample of it is the retired camera ray's constant.  The
+  // same loop with the same expression as below, the constant in place of the loaded record, so the sum has the bits the records gave (no closed form: the
+  // additions round one by one); carry, blend and store are shared.
+  const uint32_t row = p / U.imageWidth, col = p - row * U.imageWidth;
+  if ((U.flags & FLAG_MISS_RECT) && (col < U.rectX0 || col >= U.rectX1 || row < U.rectTy0 || row >= U.rectTy1)) {
+    const V3 c = retired_miss_sample(U);
+    for (uint32_t s = 0; s < U.batchSamples; s++) pixelColor = pixelColor + c * U.invSpp;
+  } else if (U.flags & FLAG_PIXEL_MAJOR) { // the pixel's samples are one contiguous run: a thread streams its own lines, eight records (one 128-byte line) per round
     const F4* src = sampleBuf + (size_t)p * U.batchSamples;
     uint32_t s = 0;
     for (; s + 8u <= U.batchSamples; s += 8u) {

@@ -17,6 +17,8 @@
 //   defer_slot           1         path slots are written where a path first hits
 //   bounds_retire        1         camera rays that cannot reach the scene's bounds retire where they are generated: in k_raygen (wavefront pipeline,
 //                                  deferred slots) and in k_path's ring preparation (fused kernel); 0 = every camera ray is traced
+//   miss_rect            1         fused frames with bounds_retire: pixels whose every camera ray misses the scene's bounds (outside an image-space rectangle
+//                                  the host derives per render, gi_miss_rect.h) get no work items and no sample records; 0 = every pixel is enumerated
 //   fused                1         LDS-resident scenes run the fused persistent kernel
 //   pool_slots           0         pin the path pool (slots); 0 = the memory plan decides
 //   sample_buffer_mb     0         pin the per-sample buffer (MiB); 0 = the memory plan decides

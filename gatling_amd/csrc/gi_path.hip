@@ -19,6 +19,8 @@
 // prepared: the lane stores the sample such a path ends with (0 + 1 x background, finished) and counts its one segment; only the other rays enter the ring.
 // A wave's 64 work items are adjacent pixels of a row, so in a frame wider than the scene whole trips of whole waves were such rays (C2: 62 % of them).
 // Renders that bind a path-following debug AOV (NEE, Bounces, ClockCycles) and counting builds trace every camera ray as before (gi_render.cpp scheduleFrame).
+// Pixels whose EVERY camera ray misses (FLAG_MISS_RECT: outside the host's rectangle, gi_miss_rect.h) are not work items at all: the ids enumerate the pixels
+// of the active rectangle, the records of the others are never written, and k_accumulate sums their constant.
 //
 // Not handled here (the host falls back to the wavefront pipeline): medium stacks (mediumStackSize > 0), dome-light images,
 // scenes beyond LDS, trees deeper than 8 levels.
@@ -36,7 +38,7 @@
 
 namespace gi {
 
-constexpr uint32_t PRE_FIELDS = 10; // prepared camera ray: origin, direction, tMin, tMax, rng state, work item
+constexpr uint32_t PRE_FIELDS = 10; // prepared camera ray: origin, direction, tMin, tMax, rng state, record index of its sample
 constexpr uint32_t PATH_STACK_MAX = 8; // LDS traversal-stack entries per lane: 4 for trees of depth <= 4 (cornell), else 8 (the host checks bvhDepth <= 8)
 
 constexpr int PATH_WAVES = 4; // resident waves per SIMD the register allocation aims for (114 VGPRs without a hint; 3 cost 11 %, 5 spill 26 registers: r03)
@@ -82,7 +84,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
       unsigned long long lanes) { if (COUNT) { const unsigned long long t = __builtin_readcyclecounter(); pc[k] += t - tPrev; tPrev = t; pl[k] += lanes; } };
   for (;;) {
     __atomic_signal_fence(__ATOMIC_SEQ_CST); // (compiler only) the ring is exchanged between the lanes of this wave through LDS
-    // --- regeneration (rp_main.rgen:213-283): idle lanes take the next work items w = sample * P + pixel
+    // --- regeneration (rp_main.rgen:213-283): idle lanes take the next work items w = sample * A + (pixel of the active rectangle)
     unsigned long long idle = __ballot(!alive);
     const uint32_t nIdle = (uint32_t)__popcll(idle);
     if (nIdle) {
@@ -98,11 +100,17 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
         const uint32_t avail = chunkEnd - chunkNext, take = avail < 64u ? avail : 64u;
         uint32_t nKept = 0u;
         if (lane < take) {
+          // work item w = sample * activeCount + (pixel of the active rectangle, row-major): the whole tile, or with FLAG_MISS_RECT the part of it outside which every
+          // camera ray misses the bounds -- those pixels get no work and no record (k_accumulate sums their constant).  The sample's record keeps its place in
+          // the per-sample buffer, sample * pixelCount + tile pixel, and that index is what the ring carries.
           const uint32_t w = chunkNext + lane;
-          const uint32_t pl = w % U.pixelCount, sl = w / U.pixelCount;
+          const uint32_t sl = w / U.activeCount, a = w - sl * U.activeCount;
+          const uint32_t ar = a / U.activeWidth, row = U.rectTy0 + ar, px = U.rectX0 + (a - ar * U.activeWidth);
+          const uint32_t rec = sl * U.pixelCount + (row * U.imageWidth + px); // (< 2^32: the memory plan's clamp)
+          const uint32_t py = U.rowBegin + row * U.rowStride;
           V3 o, d; float t0, t1; uint32_t r;
           // :195 (global pixel index: the RNG is tile independent)
-          make_camera_ray(U, tile_to_image_pixel(U, pl), U.sampleOffset + U.batchFirstSample + sl, o, d, t0, t1, r);
+          make_camera_ray_at(U, px, py, py * U.imageWidth + px, U.sampleOffset + U.batchFirstSample + sl, o, d, t0, t1, r);
           // (the bounds and the retired sample are wave-uniform; read through an empty asm they stay in scalar registers here -- left to itself the compiler
           // hoists what it derives from them out of the trip loop, into a dozen vector registers that then stay live through the walk and the shading)
           float lo[3] = {U.sceneLo[0], U.sceneLo[1], U.sceneLo[2]}, hi[3] = {U.sceneHi[0], U.sceneHi[1], U.sceneHi[2]};
@@ -113,14 +121,14 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
           if (keep) {
             const uint32_t slot = (preTail + (uint32_t)__popcll(kept & below)) & 127u;
             pre[0][slot] = f2u(o.x); pre[1][slot] = f2u(o.y); pre[2][slot] = f2u(o.z); pre[3][slot] = f2u(d.x); pre[4][slot] = f2u(d.y); pre[5][slot] = f2u(d.z);
-            pre[6][slot] = f2u(t0); pre[7][slot] = f2u(t1); pre[8][slot] = r; pre[9][slot] = w;
+            pre[6][slot] = f2u(t0); pre[7][slot] = f2u(t1); pre[8][slot] = r; pre[9][slot] = rec;
           } else { // the whole path is this one segment: its sample is the constant retire_fresh_miss stores (the miss branch + finish_sample below)
             float bg[3] = {U.background[0], U.background[1], U.background[2]}, maxv = U.maxSampleValue;
             asm volatile("" : "+s"(bg[0]), "+s"(bg[1]), "+s"(bg[2]), "+s"(maxv));
             V3 c = v3(0.0f, 0.0f, 0.0f) + v3(1.0f, 1.0f, 1.0f) * v3(bg[0], bg[1], bg[2]);
             const float mv = fmax2(c.x, fmax2(c.y, c.z));
             if (mv > maxv) c = c * (maxv / mv);
-            st4(&sampleBuf[(size_t)sl * U.pixelCount + pl], fmax2(0.0f, c.x), fmax2(0.0f, c.y), fmax2(0.0f, c.z), 0.0f);
+            st4(&sampleBuf[rec], fmax2(0.0f, c.x), fmax2(0.0f, c.y), fmax2(0.0f, c.z), 0.0f);
             nSeg++;
           }
         }
@@ -133,8 +141,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
         const uint32_t slot = (preHead + rank) & 127u;
         ro = v3(u2f(pre[0][slot]), u2f(pre[1][slot]), u2f(pre[2][slot])); rdv = v3(u2f(pre[3][slot]), u2f(pre[4][slot]), u2f(pre[5][slot]));
         tMin = u2f(pre[6][slot]); tMax = u2f(pre[7][slot]); rng = pre[8][slot];
-        const uint32_t w = pre[9][slot];
-        pixelLocal = w % U.pixelCount; sLocal = w / U.pixelCount;
+        const uint32_t rec = pre[9][slot]; // the sample's record index
+        pixelLocal = rec % U.pixelCount; sLocal = rec / U.pixelCount;
         thr = v3(1.0f, 1.0f, 1.0f); rad = v3(0.0f, 0.0f, 0.0f); bitfield = 0u; // :274-276
         alive = true;
       }
@@ -262,6 +270,7 @@ static PathKernel pickPathKernel(uint32_t classMask, bool textured, bool nee, bo
 int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool textured, bool count, uint32_t chunk, const FrameUniforms& U, const SceneView& sc,
                const PathState& st, Counters* cnt, F4* sampleBuf)
 {
+  if (U.workTotal == 0u) return 0; // an empty active rectangle (FLAG_MISS_RECT, the camera looks away): no pixel needs a path
   const uint32_t ldsNodes = sc.nodeCount, ldsTris = sc.triCount;
   const uint32_t stack = sc.bvhDepth <= 4u ? 4u : 8u;
   const uint32_t bytes = stack * TRACE_BLOCK * (uint32_t)sizeof(uint2) + ldsNodes * 80u + ldsTris * 48u;

@@ -4,6 +4,7 @@
 // loop), finishPathAovs), runAovPass, readBackAndWait, the statistics
 // (one of the translation units gi_c.cpp was split into in round 6; shared declarations: gi_host.h)
 #include "gi_host.h"
+#include "gi_miss_rect.h"
 
 bool settingsEqual(const GiCRenderSettings& a, const GiCRenderSettings& b) { return memcmp(&a, &b, sizeof(a)) == 0; }
 
@@ -181,12 +182,9 @@ static hipError_t copyTileRows(GiCRenderBuffer* rb, size_t texel, const RenderJo
 
 // Uniforms (Gi.cpp:2373-2426; camera terms rp_main.rgen:199-212 evaluated once on the host).  The schedule adds its flags later (scheduleFrame /
 // scheduleBatch).
-static FrameUniforms makeUniforms(const GiCRenderParams& params, const RenderJob& job, const GiCScene* s)
+// (the camera terms alone: giCDebugMissRect needs them without a scene)
+static void cameraUniforms(const GiCCameraDesc& c, uint32_t width, uint32_t height, FrameUniforms& U)
 {
-  const GiCRenderSettings& rs = params.renderSettings;
-  const GiCCameraDesc& c = params.camera;
-  const uint32_t width = job.width, height = job.height;
-  FrameUniforms U{};
   auto norm3 = [](const float* v, float* o) {
     float inv = 1.0f / sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
     o[0] = v[0] * inv; o[1] = v[1] * inv; o[2] = v[2] * inv;
@@ -208,6 +206,18 @@ static FrameUniforms makeUniforms(const GiCRenderParams& params, const RenderJob
   U.focusDistance = c.focusDistance;
   uint32_t cr = packHalf2x16(c.clipStart, c.clipEnd);
   U.clipNear = f16ToF32((uint16_t)(cr & 0xffffu)); U.clipFar = f16ToF32((uint16_t)(cr >> 16));
+}
+static uint32_t samplingFlags(const GiCRenderSettings& rs)
+{
+  return (rs.jitteredSampling ? FLAG_JITTER : 0u) | (rs.filterImportanceSampling ? FLAG_FIS : 0u) | (rs.depthOfField ? FLAG_DOF : 0u);
+}
+static FrameUniforms makeUniforms(const GiCRenderParams& params, const RenderJob& job, const GiCScene* s)
+{
+  const GiCRenderSettings& rs = params.renderSettings;
+  const GiCCameraDesc& c = params.camera;
+  const uint32_t width = job.width, height = job.height;
+  FrameUniforms U{};
+  cameraUniforms(c, width, height, U);
   float cv[4]; memcpy(cv, job.clear, 16);
   for (int a = 0; a < 3; a++) { // fallback dome texel: glm::u8vec4(bg * 255) as RGBA8 unorm (Gi.cpp:2194-2199)
     int q = (int)(cv[a] * 255.0f); if (q < 0) q = 0; if (q > 255) q &= 255;
@@ -221,7 +231,7 @@ static FrameUniforms makeUniforms(const GiCRenderParams& params, const RenderJob
   U.mediumStackSize = rs.mediumStackSize; U.maxVolumeWalkLength = rs.maxVolumeWalkLength;
   U.maxBounces = std::min(rs.maxBounces, 0xfffu); U.rrBounceOffset = rs.rrBounceOffset & 0xffffu;
   U.imageWidth = width; U.imageHeight = height; U.rowBegin = job.rowBegin; U.rowStride = job.rowStride; U.pixelCount = (uint32_t)((size_t)job.tileRows * width);
-  U.flags = (rs.jitteredSampling ? FLAG_JITTER : 0u) | (rs.filterImportanceSampling ? FLAG_FIS : 0u) | (rs.depthOfField ? FLAG_DOF : 0u) |
+  U.flags = samplingFlags(rs) |
             (rs.clippingPlanes ? FLAG_CLIP : 0u) | (rs.nextEventEstimation ? FLAG_NEE : 0u) | (rs.progressiveAccumulation ? FLAG_PROGRESSIVE : 0u);
   U.sphereCount = s->lightCounts[0]; U.distantCount = s->lightCounts[1]; U.rectCount = s->lightCounts[2]; U.diskCount = s->lightCounts[3]; // (uploadLights)
   U.totalLightCount = U.sphereCount + U.distantCount + U.rectCount + U.diskCount;
@@ -437,6 +447,7 @@ struct Frame {
   double tStart = 0.0;
   uint32_t windowCalls = 0;     // sample look-ahead: >= 2 = the colour pass traces ONE batch of windowCalls * spp samples; this call folds the first spp
   bool served = false;          // ... or this call traced nothing: its samples came out of the window (serveFromWindow)
+  uint64_t skippedSegments = 0; // FLAG_MISS_RECT: samples of the pixels k_path was given no work for -- each is a path of one segment (fillStats)
 };
 
 // The PathState of the colour pass: the pool, and what the path-following AOVs bound to this render need beside it.
@@ -486,6 +497,23 @@ static Schedule scheduleFrame(Frame& f)
   if (fused && s->boundsValid && optionValue("bounds_retire", 1) != 0 && !s->countTraversal && !f.ps.neeKey && !f.ps.bouncesAov && !f.ps.pathSegments) {
     U.flags |= FLAG_BOUNDS_RETIRE;
     for (int a = 0; a < 3; a++) { U.sceneLo[a] = s->bounds[a]; U.sceneHi[a] = s->bounds[3 + a]; }
+  }
+  // The miss rectangle (gi_miss_rect.h): k_path still prepared the full-width camera ray of every one of those samples -- hash, two draws, the filter's log / sqrt
+  // / sincos, the normalise, the slab test's divisions, a 16-byte record -- and k_accumulate read the identical records back.  For a pixel whose every possible
+  // camera ray misses the bounds none of that reaches the image: such pixels get no work items (k_path enumerates the rectangle's pixels only) and no records
+  // (k_accumulate sums the constant in their place, same loop).  It rests on the per-ray retire (the pixels INSIDE the rectangle are still tested ray by ray),
+  // so it inherits every condition of FLAG_BOUNDS_RETIRE above.  A look-ahead window keeps the whole frame: later calls fold its records with k_fold_window,
+  // which reads every pixel's.  With max-bounces 0 no kernel traces anything (runZeroBounceBatch: every sample is black, not the background).
+  if (fused) {
+    U.rectX0 = 0u; U.rectX1 = U.imageWidth; U.rectTy0 = 0u; U.rectTy1 = f.job.tileRows;
+    if ((U.flags & FLAG_BOUNDS_RETIRE) && U.maxBounces > 0u && f.windowCalls < 2u && optionValue("miss_rect", 1) != 0) {
+      const MissRect r = computeMissRect(U.sceneLo, U.sceneHi, U, U.imageWidth, U.imageHeight);
+      uint32_t ty0, ty1; missRectTileRows(r, U.rowBegin, U.rowStride, f.job.tileRows, ty0, ty1);
+      if (r.empty() || ty1 <= ty0) { U.rectX0 = U.rectX1 = U.rectTy0 = U.rectTy1 = 0u; }
+      else { U.rectX0 = r.x0; U.rectX1 = r.x1; U.rectTy0 = ty0; U.rectTy1 = ty1; }
+    }
+    U.activeWidth = U.rectX1 - U.rectX0; U.activeCount = U.activeWidth * (U.rectTy1 - U.rectTy0);
+    if (U.activeCount < U.pixelCount) U.flags |= FLAG_MISS_RECT;
   }
   Schedule sch;
   sch.dynRefill = traceDynRefill(s);
@@ -743,8 +771,21 @@ static void fillStats(const Frame& f, double tEnd)
     return;
   }
   S.fusedPath = f.plan.fused ? 1u : 0u;
-  S.segments = c.segments; S.shadowRays = c.shadowRays; S.nodesVisited = c.nodesVisited; S.trisTested = c.trisTested;
+  S.segments = c.segments + f.skippedSegments; S.shadowRays = c.shadowRays; S.nodesVisited = c.nodesVisited; S.trisTested = c.trisTested;
   S.shadowNodesVisited = c.shadowNodesVisited; S.shadowTrisTested = c.shadowTrisTested;
+}
+
+// giCDebugMissRect: the rectangle scheduleFrame would give a whole-frame render of this camera over these bounds (before the rules that switch it off: options,
+// debug AOVs, look-ahead windows).  Host only: no device, no scene.  out = x0, y0, x1, y1; an empty rectangle is 0, 0, 0, 0.
+extern "C" int giCDebugMissRect(const float* bounds, const GiCCameraDesc* camera, const GiCRenderSettings* settings, uint32_t width, uint32_t height, uint32_t* out)
+{
+  if (!bounds || !camera || !settings || !out || width == 0u || height == 0u) { setError("giCDebugMissRect: bad arguments"); return GI_C_ERROR; }
+  FrameUniforms U{};
+  cameraUniforms(*camera, width, height, U);
+  U.flags = samplingFlags(*settings);
+  const MissRect r = computeMissRect(bounds, bounds + 3, U, width, height);
+  out[0] = r.x0; out[1] = r.y0; out[2] = r.x1; out[3] = r.y1;
+  return GI_C_OK;
 }
 
 // choose the shadow walks' order once both have been measured on enough rays of this scene: fewer node visits per ray wins
@@ -884,6 +925,10 @@ static int traceColour(Frame& f, const BoundAovs& aov, const LookaheadPlan& la)
     U.batchFirstSample = (uint32_t)(batch * batchSamples);
     U.batchSamples = (uint32_t)std::min<uint64_t>(batchSamples, samples - (uint64_t)batch * batchSamples);
     U.workTotal = (uint32_t)(pixels * U.batchSamples);
+    if (f.plan.fused && U.maxBounces > 0u) { // the fused kernel's work items are the active rectangle's pixels (scheduleFrame); a skipped sample is one segment
+      U.workTotal = (uint32_t)((uint64_t)U.activeCount * U.batchSamples);
+      f.skippedSegments += (uint64_t)(pixels - U.activeCount) * U.batchSamples;
+    }
     f.ps.neeSampleBase = U.batchFirstSample;
     const uint32_t poolNow = (uint32_t)std::min<uint64_t>(f.plan.slots, U.workTotal);
     U.poolSlots = poolNow;

@@ -8,10 +8,10 @@ namespace gi {
 
 // Camera ray of (pixel, sample): RNG init, pixel jitter / filter importance sampling, thin lens, clip range
 // (rp_main.rgen:215-288).  Returns the RNG state after the draws the reference makes here.
-__device__ __forceinline__ void make_camera_ray(const FrameUniforms& U, uint32_t pixelIndex, uint32_t sampleIndex, V3& origin, V3& dir, float& tMin,
-    float& tMax, uint32_t& rng)
+// (make_camera_ray_at: for a caller that already holds the pixel's column and row, pixelIndex = py * imageWidth + px)
+__device__ __forceinline__ void make_camera_ray_at(const FrameUniforms& U, uint32_t px, uint32_t py, uint32_t pixelIndex, uint32_t sampleIndex, V3& origin,
+    V3& dir, float& tMin, float& tMax, uint32_t& rng)
 {
-  const uint32_t px = pixelIndex % U.imageWidth, py = pixelIndex / U.imageWidth;
   rng = gi_hash_init(pixelIndex * (sampleIndex + 1u)); // :223, common.glsl:121-124
   float r0 = gi_next1f(rng), r1 = gi_next1f(rng);     // :224 (always drawn)
   float sox = 0.5f, soy = 0.5f;
@@ -39,6 +39,12 @@ __device__ __forceinline__ void make_camera_ray(const FrameUniforms& U, uint32_t
     float cosCone = fmax2(1e-5f, dot(dir, v3(U.camFwd)));
     tMin = U.clipNear / cosCone; tMax = U.clipFar / cosCone;
   }
+}
+
+__device__ __forceinline__ void make_camera_ray(const FrameUniforms& U, uint32_t pixelIndex, uint32_t sampleIndex, V3& origin, V3& dir, float& tMin,
+    float& tMax, uint32_t& rng)
+{
+  make_camera_ray_at(U, pixelIndex % U.imageWidth, pixelIndex / U.imageWidth, pixelIndex, sampleIndex, origin, dir, tMin, tMax, rng);
 }
 
 // Per-sample finish (rp_main.rgen:489-496): hue-preserving clamp on the max channel, then max(0); NaNs are not filtered.
@@ -272,6 +278,16 @@ __device__ __forceinline__ bool ray_misses_box(const float (&sceneLo)[3], const 
 __device__ __forceinline__ bool ray_misses_bounds(const FrameUniforms& U, const V3& o, const V3& d, float tMin, float tMax)
 {
   return ray_misses_box(U.sceneLo, U.sceneHi, o, d, tMin, tMax);
+}
+
+// The sample of a camera path that left the scene at once: radiance 0 + throughput 1 x background, then the per-sample finish (retire_fresh_miss below and
+// k_path's ring preparation store it per sample; k_accumulate sums it for the pixels FLAG_MISS_RECT leaves without records).  It depends on the frame alone.
+__device__ __forceinline__ V3 retired_miss_sample(const FrameUniforms& U)
+{
+  V3 rad = v3(0.0f, 0.0f, 0.0f) + v3(1.0f, 1.0f, 1.0f) * v3(U.background);
+  const float mv = fmax2(rad.x, fmax2(rad.y, rad.z));
+  if (mv > U.maxSampleValue) rad = rad * (U.maxSampleValue / mv);
+  return v3(fmax2(0.0f, rad.x), fmax2(0.0f, rad.y), fmax2(0.0f, rad.z));
 }
 
 // A new path's Slot (rp_main.rgen:274-276): throughput 1, bitfield 0, radiance 0, the rng state after the camera draws, its work item

@@ -175,6 +175,10 @@ struct FrameUniforms {
   uint32_t mediumStackSize, maxVolumeWalkLength; // GiRenderSettings (Gi.h:150-151); stack size 0 = inside/outside toggle only
   uint32_t rowStride, padStride;                 // the tile's rows are rowBegin + k * rowStride (multi-GPU row interleaving)
   float sceneLo[3], padLo, sceneHi[3], padHi;    // FLAG_BOUNDS_RETIRE: the root node's dequantised bounds, padded (host: sceneBoundsForRetire)
+  // Fused frames: the tile pixels k_path hands out work for -- columns [rectX0, rectX1) of the tile rows [rectTy0, rectTy1), activeWidth x (rectTy1 - rectTy0) =
+  // activeCount pixels; workTotal = activeCount * batchSamples.  The whole tile unless FLAG_MISS_RECT (gi_miss_rect.h): then every pixel outside is a certain miss.
+  uint32_t rectX0, rectX1, rectTy0, rectTy1;
+  uint32_t activeWidth, activeCount, padRect[2];
 };
 enum : uint32_t {
   FLAG_JITTER = 1u, FLAG_FIS = 2u, FLAG_DOF = 4u, FLAG_CLIP = 8u, FLAG_NEE = 16u, FLAG_PROGRESSIVE = 32u,
@@ -191,6 +195,9 @@ enum : uint32_t {
   // with FLAG_DEFER_SLOT on the k_trace_dyn path: a camera ray whose slab interval against the scene bounds is empty is never
   // queued -- k_raygen retires its sample (the arithmetic of retire_fresh_miss) and hands the slot straight to the next k_raygen
   FLAG_BOUNDS_RETIRE = 256u,
+  // fused frames: the pixels outside (rectX0 .. rectTy1) are certain misses -- k_path enumerates only the rectangle's pixels and never writes the others' records,
+  // k_accumulate sums the retired sample's constant for them instead of loading (gi_render.cpp scheduleFrame)
+  FLAG_MISS_RECT = 2048u,
 };
 
 // Device-side scene view handed to the kernels.
