@@ -23,6 +23,7 @@ AOV_COLOR = 0
 FORMAT_INT32, FORMAT_FLOAT32, FORMAT_FLOAT32_VEC4 = 0, 1, 2
 OPTION_COUNT_TRAVERSAL, OPTION_KERNEL_TIMERS, OPTION_POOL_SLOTS, OPTION_SAMPLE_BUFFER_MB, OPTION_TRACE_DYNAMIC, OPTION_TWO_LEVEL, OPTION_FUSED_PATH, OPTION_DEVICES = 1, 2, 3, 4, 5, 6, 7, 8
 OPTION_SAMPLE_LOOKAHEAD = 10  # N >= 2: a progressive call may trace the samples of up to N calls in one batch (include/gi_c.h); 0 / 1 = off (default)
+OPTION_VERTEX_UPDATES = 12  # 1: vertex edits (giCSetMeshVertices) of meshes of the built scene refit the resident BVH on the device instead of rebuilding the scene (include/gi_c.h); 0 = off (default)
 OPTION_VISIBILITY_UPDATES = 11  # 1: visibility edits of meshes of the built scene are applied to the resident scene instead of rebuilding it (include/gi_c.h); 0 = off (default)
 OPTION_BVH_BUILD = 9  # 0 = host BVH builder (default), 1 = device builder (flat-layout scenes of more than 128 triangles)
 
@@ -122,7 +123,7 @@ SYMBOLS = [
     ("giCCreateMaterial", _P, [_P, C.c_char_p, C.POINTER(GiCMaterialDesc)]), ("giCDestroyMaterial", None, [_P]),
     ("giCCreateMesh", _P, [_P, C.POINTER(GiCMeshDesc)]), ("giCSetMeshTransform", None, [_P, _FP]),
     ("giCSetMeshInstanceTransforms", None, [_P, _U, _FP]), ("giCSetMeshInstanceIds", None, [_P, _U, C.POINTER(C.c_int32)]),
-    ("giCSetMeshMaterial", None, [_P, _P]), ("giCSetMeshVisibility", None, [_P, _I]), ("giCDestroyMesh", None, [_P]),
+    ("giCSetMeshMaterial", None, [_P, _P]), ("giCSetMeshVisibility", None, [_P, _I]), ("giCSetMeshVertices", C.c_int, [_P, _U, _P]), ("giCDestroyMesh", None, [_P]),
     ("giCRender", C.c_int, [C.POINTER(GiCRenderParams)]),
     ("giCCreateScene", _P, []), ("giCDestroyScene", None, [_P]),
     ("giCCreateSphereLight", _P, [_P]), ("giCDestroySphereLight", None, [_P, _P]), ("giCSetSphereLightPosition", None, [_P, _FP]),
@@ -162,6 +163,8 @@ SYMBOLS = [
     ("giCDebugTexRuntime", C.c_int, [_FP, _U, _U, _U, _U, _FP, _FP]),
     ("giCDebugEditDirtyFlags", C.c_int32, [_I, _I]), ("giCDebugSceneUpdateCounts", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugSceneVisibilityUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugSceneClassState", C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    ("giCDebugSceneVertexUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugRefitBvh", C.c_int, [_FP, _FP, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("giCDebugSceneRefitCheck", C.c_int, [_P, _U, C.POINTER(C.c_uint32)]),
     ("giCDebugMissRect", C.c_int, [_FP, C.POINTER(GiCCameraDesc), C.POINTER(GiCRenderSettings), _U, _U, C.POINTER(C.c_uint32)]),
 ]
 
@@ -441,6 +444,30 @@ class Scene:
         """giSetMeshVisibility (Gi.h:216): a geometry-side edit, the next render rebuilds the scene -- or, with OPTION_VISIBILITY_UPDATES, updates it in place."""
         self.desc.meshes[mesh_index].visible = bool(visible)
         self.L.giCSetMeshVisibility(self.meshes[mesh_index], int(bool(visible)))
+
+    def set_mesh_vertices(self, mesh_index: int, vertices):
+        """giCSetMeshVertices: the mesh's vertex array replaced (same count; faces, ids, primvars, material and transforms stay).  A geometry-side edit: the
+        next render rebuilds the scene -- or, with OPTION_VERTEX_UPDATES, refits the resident BVH on the device.  A refused array leaves the mesh unchanged."""
+        from .scene import VERTEX_DTYPE
+        v = np.ascontiguousarray(vertices, VERTEX_DTYPE)
+        if self.L.giCSetMeshVertices(self.meshes[mesh_index], len(v), v.ctypes.data) != GI_C_OK:
+            raise GiError("giCSetMeshVertices failed: " + self.L.giCGetLastError().decode())
+        self.desc.meshes[mesh_index].vertices = v.copy()
+
+    def vertex_update_count(self) -> int:
+        """giCDebugSceneVertexUpdateCount: how often the scene was brought up to date by an incremental vertex update (not counted by update_counts)."""
+        n = C.c_uint64(0)
+        if self.L.giCDebugSceneVertexUpdateCount(self.handle, C.byref(n)) != GI_C_OK:
+            raise GiError("giCDebugSceneVertexUpdateCount failed")
+        return int(n.value)
+
+    def refit_check(self, device: int = 0) -> dict:
+        """giCDebugSceneRefitCheck: the resident tree against the host's refit of it.  Returns {"differing", "nodes"}."""
+        nodes = C.c_uint32(0)
+        v = self.L.giCDebugSceneRefitCheck(self.handle, device, C.byref(nodes))
+        if v < 0:
+            raise GiError("giCDebugSceneRefitCheck failed: " + self.L.giCGetLastError().decode())
+        return {"differing": v, "nodes": nodes.value}
 
     def update_counts(self) -> dict:
         """giCDebugSceneUpdateCounts: how often the scene was brought up to date by a full build / a transform update / a material update."""

@@ -234,14 +234,14 @@ inline int exponentFor(float extent)
 static void buildCore(const std::vector<TriRec>& trisIn, const float* boxes, size_t boxCount, Bvh8& out, std::vector<uint32_t>* order,
     const Node8* itemRoots = nullptr)
 {
-  out.nodes.clear(); out.tris.clear(); out.maxDepth = 0;
+  out.nodes.clear(); out.tris.clear(); out.maxDepth = 0; out.levelStart.clear();
   if (order) order->clear();
   const size_t itemCount = boxes ? boxCount : trisIn.size();
   out.activeTris = 0;
   auto emptyRoot = [&] {
     Node8 root; std::memset(&root, 0, sizeof(root));
     for (int a = 0; a < 3; a++) { root.e[a] = 127; for (int s = 0; s < 8; s++) { root.qlo[a][s] = 255; root.qhi[a][s] = 0; } }
-    out.nodes.push_back(root); out.maxDepth = 1;
+    out.nodes.push_back(root); out.maxDepth = 1; out.levelStart = {0u, 1u};
   };
   if (itemCount == 0) { emptyRoot(); return; }
   const bool timing = getenv("GATLING_BUILD_TIMING") != nullptr;
@@ -309,7 +309,7 @@ static void buildCore(const std::vector<TriRec>& trisIn, const float* boxes, siz
   out.nodes.resize(1);
   size_t triCount = 0;
   while (!level.empty()) {
-    out.maxDepth++;
+    out.maxDepth++; out.levelStart.push_back(level[0].n8);
     const size_t m = level.size();
     plans.resize(m);
     parallelFor(m, [&](size_t li) {
@@ -401,6 +401,7 @@ static void buildCore(const std::vector<TriRec>& trisIn, const float* boxes, siz
     triCount = triEnd;
     level.swap(next);
   }
+  out.levelStart.push_back((uint32_t)out.nodes.size());
   appendInactive();
   if (timing) fprintf(stderr, "[gatling_gi] bvh8: prepare %.0f ms, bvh2 %.0f ms, collapse+quantise %.0f ms (%zu items, %zu nodes)\n", tB - tA, tC - tB,
       now() - tC, itemCount, out.nodes.size());

@@ -14,6 +14,7 @@ struct Bvh8 {
   std::vector<Node8> nodes;   // breadth-first: the top of the tree comes first (LDS staging)
   std::vector<TriRec> tris;   // reordered so every node's leaf triangles are contiguous
   uint32_t maxDepth = 0;
+  std::vector<uint32_t> levelStart; // first node of every breadth-first level, then the node count: maxDepth + 1 entries (a refit walks the levels, gi_refit.hip)
   uint32_t activeTris = 0;    // items the tree references: tris[0, activeTris) (order[0, activeTris) in box mode); the rest are inactive, see below
 };
 

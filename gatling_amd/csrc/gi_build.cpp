@@ -2,6 +2,7 @@
 // (one of the translation units gi_c.cpp was split into in round 6; shared declarations: gi_host.h)
 #include "gi_host.h"
 #include "gi_bvh_build.h"
+#include "gi_refit.h"
 constexpr uint32_t kIncrementalMinTris = 4096; // scenes with fewer triangles are not edited in place: they rebuild in no time (and must stay LDS-resident)
 // levels of a scene BVH: the deepest traversal variant keeps 16 stack entries in LDS and OVF_STACK = 40 in scratch; trav_node_pick does not bound-check the
 // spill.  The limit stays at 1 + 8 + 40 levels, the depth the 8-entry spilling variant of earlier versions could hold
@@ -87,6 +88,32 @@ inline GiCVertex usableShadingAttributes(const GiCVertex& in)
   if (!std::isfinite(v.v)) v.v = 0.0f;
   if (!std::isfinite(v.bitangentSign)) v.bitangentSign = 1.0f;
   return v;
+}
+// The FVertex of one mesh vertex (Gi.cpp:848-861: normal and tangent quantised to octahedral unorm2x16, then decoded once) and the TriShade record of one mesh
+// face: buildScene, buildShadeRecords and updateVertices -- the one copy of this code
+static FVertex packVertex(const GiCVertex& vIn)
+{
+  const GiCVertex v = usableShadingAttributes(vIn);
+  FVertex fv; memcpy(fv.pos, v.pos, 12); fv.bsign = v.bitangentSign;
+  decodeDirection(encodeDirection(v.norm), fv.normal); decodeDirection(encodeDirection(v.tangent), fv.tangent);
+  fv.u = v.u; fv.v = v.v;
+  return fv;
+}
+static TriShade packTriShade(const GiCMesh* m, const GiCFace& f, uint32_t vertexOffset)
+{
+  TriShade q{};
+  for (int k = 0; k < 3; k++) {
+    const GiCVertex v = usableShadingAttributes(m->vertices[f.v_i[k]]);
+    // (Gi.cpp:848-861: quantised, then decoded once)
+    memcpy(q.p[k], v.pos, 12); decodeDirection(encodeDirection(v.norm), q.n[k]); decodeDirection(encodeDirection(v.tangent), q.t[k]);
+    q.uv[k][0] = v.u; q.uv[k][1] = v.v; q.bsign[k] = v.bitangentSign; q.vi[k] = vertexOffset + f.v_i[k];
+  }
+  return q;
+}
+bool usableVertexPositions(const GiCVertex* v, size_t count)
+{
+  for (size_t i = 0; i < count; i++) for (int a = 0; a < 3; a++) if (!usableCoordinate(v[i].pos[a])) return false;
+  return true;
 }
 // one flattened triangle (Gi.cpp:1188-1202 hands the instance transform to the TLAS; here it is applied); `usable` false: marked inactive for the builder
 inline void flattenTriangle(const InstanceRec& ir, bool usable, const GiCMesh* m, uint32_t f, TriRec& t)
@@ -428,16 +455,7 @@ static std::vector<uint32_t> buildShadeRecords(SceneHost& H)
   for (MeshBuild& mb : H.meshBuilds) {
     mb.shadeBase = (uint32_t)H.triShade.size(); shadeBaseOfMesh[mb.meshIdx] = mb.shadeBase;
     const GiCMesh* m = mb.m;
-    for (const GiCFace& f : m->faces) {
-      TriShade q{};
-      for (int k = 0; k < 3; k++) {
-        const GiCVertex v = usableShadingAttributes(m->vertices[f.v_i[k]]);
-        // (Gi.cpp:848-861: quantised, then decoded once)
-        memcpy(q.p[k], v.pos, 12); decodeDirection(encodeDirection(v.norm), q.n[k]); decodeDirection(encodeDirection(v.tangent), q.t[k]);
-        q.uv[k][0] = v.u; q.uv[k][1] = v.v; q.bsign[k] = v.bitangentSign; q.vi[k] = mb.vertexOffset + f.v_i[k];
-      }
-      H.triShade.push_back(q);
-    }
+    for (const GiCFace& f : m->faces) H.triShade.push_back(packTriShade(m, f, mb.vertexOffset));
   }
   return shadeBaseOfMesh;
 }
@@ -517,7 +535,7 @@ static int buildSceneOnDevice(GiCScene* s, std::unique_ptr<SceneHost>& hostPtr, 
   if (first.activeTris != n - inactive) { setError("internal: device and host disagree on the inactive triangles"); return GI_C_ERROR; }
   s->stats.inactiveTriangleCount = inactive;
   if (inactive) warnInactive(H.meshBuilds, perMesh);
-  H.bvh = Bvh8{}; H.bvh.maxDepth = first.maxDepth; H.bvh.activeTris = first.activeTris;
+  H.bvh = Bvh8{}; H.bvh.maxDepth = first.maxDepth; H.bvh.activeTris = first.activeTris; H.bvh.levelStart = first.levelStart;
   H.triFaceId.clear(); H.flatOfOrig.clear();
   return finishBuild(s, hostPtr, first.nodeCount, n, std::vector<Node8>{first.root}, buildMs, uploadMs, " (device build)");
 }
@@ -528,7 +546,7 @@ int buildScene(GiCScene* s)
   std::unique_ptr<SceneHost> hostPtr(new SceneHost());
   SceneHost& H = *hostPtr;
   s->host.reset(); // (a failed build leaves no stale host copy behind)
-  for (GiCMesh* m : s->meshes) { m->builtInstances = 0xffffffffu; m->xformDirty = false; m->instDirty.clear(); m->visToggled = false; }
+  for (GiCMesh* m : s->meshes) { m->builtInstances = 0xffffffffu; m->xformDirty = false; m->instDirty.clear(); m->visToggled = false; m->vertsEdited = false; }
   std::vector<FVertex>& verts = H.verts; std::vector<InstanceRec>& instances = H.instances; std::vector<TriRec> tris; std::vector<int32_t> faceIdOf;
   buildMaterialRecords(s, H.mats);
   uint32_t meshIdx = 0;
@@ -547,13 +565,7 @@ int buildScene(GiCScene* s)
     const uint32_t matFlags = meshMatFlags(H.mats[material], material, m);
     const uint32_t vertexOffset = (uint32_t)verts.size();
     appendMeshSceneData(m, *mit, vertexOffset, meshRecs, sceneData);
-    for (const GiCVertex& vIn : m->vertices) { // Gi.cpp:848-861: quantise normal/tangent to octahedral unorm2x16, then decode once
-      const GiCVertex v = usableShadingAttributes(vIn);
-      FVertex fv; memcpy(fv.pos, v.pos, 12); fv.bsign = v.bitangentSign;
-      decodeDirection(encodeDirection(v.norm), fv.normal); decodeDirection(encodeDirection(v.tangent), fv.tangent);
-      fv.u = v.u; fv.v = v.v;
-      verts.push_back(fv);
-    }
+    for (const GiCVertex& vIn : m->vertices) verts.push_back(packVertex(vIn));
     // FaceId AOV values, bug-compatible: face ids are stored with a 1/2/4-byte stride chosen from maxFaceId (Gi.cpp:878-885);
     // the shader fetches the 32-bit word prim / (4/stride), shifts it by (prim % (4/stride)) * 8 bits (sic) and masks it
     // with (stride*8 - 1) (rp_main.chit:231-240).  Evaluated once per primitive here.
@@ -696,7 +708,7 @@ void buildPart(const MeshBuild& mb, uint32_t instInMesh, bool packed, PartBuild&
 void placePart(SceneHost& H, InstPart& P, const PartBuild& B)
 {
   const MeshBuild& mb = H.meshBuilds[P.meshBuild];
-  P.nodeCount = (uint32_t)B.bvh.nodes.size(); P.depth = B.bvh.maxDepth;
+  P.nodeCount = (uint32_t)B.bvh.nodes.size(); P.depth = B.bvh.maxDepth; P.activeTris = B.bvh.activeTris; P.levelStart = B.bvh.levelStart;
   for (uint32_t i = 0; i < P.nodeCount; i++) { Node8 n = B.bvh.nodes[i]; n.childBase += P.nodeOff; n.triBase += P.triFirst; H.bvh.nodes[P.nodeOff + i] = n; }
   for (uint32_t k = 0; k < P.nf; k++) {
     TriRec t = B.bvh.tris[k];
@@ -766,7 +778,8 @@ static int updateTransforms(GiCScene* s, bool& handled, UpdateCost& cost)
           parts.push_back(P); }
     }
     if (parts.empty()) return GI_C_OK;
-    if (H.deviceBuilt) { H.bvh.tris.resize(s->triCount); H.triFaceId.resize(s->triCount); } // (a device-built tree has no host copy: placePart fills them)
+    // (a device-built tree has no host copy, and a vertex update dropped that of a host-built one: placePart fills them)
+    if (H.deviceBuilt || H.hostTreeDropped) { H.bvh.tris.resize(s->triCount); H.triFaceId.resize(s->triCount); H.hostTreeDropped = false; }
     std::vector<PartBuild> built(parts.size());
     parallelOver(parts.size(), [&](size_t i) { buildPart(H.meshBuilds[parts[i].meshBuild], parts[i].instInMesh, H.shadePacked, built[i]); });
     H.topCap = (uint32_t)parts.size() * 2u + 16u; // top nodes <= internal top nodes + one copied root per part
@@ -997,9 +1010,184 @@ static int updateVisibility(GiCScene* s, bool& handled, UpdateCost& cost)
   return GI_C_OK;
 }
 
-// brings the device scene up to date with the host-side edits: incremental for DIRTY_BVH raised by visibility toggles alone (opt-in: ids renumbered, the
+// ---------------------------------------------------------------------------------------------------------------
+// Incremental vertex updates (opt-in: GI_C_SCENE_OPTION_VERTEX_UPDATES / GATLING_OPTIONS=vertex_updates=1).  giCSetMeshVertices moved the points of meshes
+// of the built scene; topology, ids, materials and transforms stayed.  The tree keeps its shape and is REFITTED where it lives, in device memory
+// (gi_refit.hip): under the traversal contract a tree with the same topology and new conservative boxes gives the bits of a fresh build.
+//   host, per edited mesh: its range of H.verts and of H.triShade made again by the code buildScene runs (packVertex, packTriShade), sent to every device.
+//   device: k_refit_tris makes the flattened records of the edited instances again (TriShade::p, InstanceRec::o2w: flattenTriangle's operations);
+//       k_refit_level refits one level per launch, deepest first, over the refit units -- the whole tree (flat layouts, host- or device-built), or every
+//       part of an edited mesh (partitioned layout; the part roots are read back, rebuildTop + uploadTopTree run as after a transform edit).
+//   afterwards: the root is read back for the scene bounds (bounds retire and the miss rectangle read them).  The class state is untouched.
+// Host copies of the tree.  Flat host-built: dropped (H.hostTreeDropped) -- nodes, triangles and face ids would be stale, nothing reads them until the
+// re-layout of the first transform edit, which then makes them anew as it does for a device-built scene.  Partitioned: the triangles of the edited parts
+// are re-flattened on the host by the same code and the part roots are read back, so everything rebuildTop and later uploads read is current; the interior
+// nodes of a refitted part are stale on the host and are never read -- the only upload of a part's node range follows placePart, which rewrites the range.
+// Falls back to buildScene (handled = false, not an error): no host copy, GATLING_OPTIONS=incremental=0, the two-level layout, a scene within LDS, fewer
+// than kIncrementalMinTris resident triangles, an edited mesh without records on the device (invisible or without a valid material at the build) or hidden
+// by updateVisibility, a position that is not finite or beyond 1e18 in object or world space (a fresh build would leave the triangle out of the tree), a scene
+// or a part that had inactive triangles when it was built, out of device memory for the float boxes (32 bytes per node).  The caller has established that
+// nothing but vertex edits (and visibility toggles, which run behind this update) asked for the rebuild.
+// ---------------------------------------------------------------------------------------------------------------
+static bool vertexUpdatesWanted(const GiCScene* s)
+{
+  const long o = optionValue("vertex_updates", -1);
+  return o >= 0 ? o == 1 : s->optVertexUpdates == 1;
+}
+
+static int updateVertices(GiCScene* s, bool& handled, UpdateCost& cost)
+{
+  SceneHost* host = incrementalHost(s);
+  if (!host || s->twoLevel || !host->shadePacked || s->triCount < kIncrementalMinTris) return GI_C_OK; // (the floor: resident triangles)
+  SceneHost& H = *host;
+  if (s->stats.inactiveTriangleCount != 0u) return GI_C_OK;
+  if (!H.partitioned && (H.bvh.levelStart.size() < 2u || H.bvh.levelStart.back() != s->nodeCount)) return GI_C_OK;
+  const double t0 = nowMs();
+  // --- which meshes, and may they be refitted?
+  std::vector<uint32_t> edited; // indices into H.meshBuilds
+  for (const GiCMesh* m : s->meshes) {
+    if (!m->vertsEdited) continue;
+    uint32_t b = 0;
+    while (b < (uint32_t)H.meshBuilds.size() && H.meshBuilds[b].m != m) b++;
+    if (b == (uint32_t)H.meshBuilds.size()) return GI_C_OK; // no records on the device
+    const MeshBuild& mb = H.meshBuilds[b];
+    if (mb.hidden || m->builtInstances != mb.instCount) return GI_C_OK;
+    if ((size_t)mb.vertexOffset + m->vertices.size() > H.verts.size() || (size_t)mb.shadeBase + m->faces.size() > H.triShade.size()) return GI_C_OK;
+    if (!usableVertexPositions(m->vertices.data(), m->vertices.size())) return GI_C_OK;
+    edited.push_back(b);
+  }
+  if (edited.empty()) return GI_C_OK;
+  std::vector<uint32_t> editedOfInstance(H.instances.size(), 0u);
+  std::atomic<bool> worldOk{true};
+  for (uint32_t b : edited) {
+    const MeshBuild& mb = H.meshBuilds[b];
+    for (uint32_t ii = 0; ii < mb.instCount; ii++) { editedOfInstance[mb.instFirst + ii] = 1u; if (!usableInstance(H.instances[mb.instFirst + ii])) return GI_C_OK; }
+    // every flattened triangle must stay active, by the builders' own rule on the builders' own operands (prepareRange: v0, v0 + e1, v0 + e2)
+    const size_t nf = mb.m->faces.size();
+    parallelOver(mb.instCount, [&](size_t ii) {
+      const InstanceRec& ir = H.instances[mb.instFirst + ii];
+      for (size_t f = 0; f < nf; f++) {
+        TriRec t; flattenTriangle(ir, true, mb.m, (uint32_t)f, t);
+        float lo[3], hi[3];
+        if (!refit_tri_box(t.v0, t.e1, t.e2, lo, hi)) { worldOk = false; return; }
+      }
+    });
+  }
+  if (!worldOk) return GI_C_OK;
+  // --- refit units and their levels: thread ranges per level, deepest level first
+  struct Unit { uint32_t nodeOff; const std::vector<uint32_t>* levelStart; };
+  std::vector<Unit> units; std::vector<uint32_t> editedParts;
+  if (!H.partitioned) units.push_back(Unit{0u, &H.bvh.levelStart});
+  else {
+    std::vector<uint8_t> isEdited(H.meshBuilds.size(), 0);
+    for (uint32_t b : edited) isEdited[b] = 1;
+    for (uint32_t i = 0; i < (uint32_t)H.parts.size(); i++) {
+      const InstPart& P = H.parts[i];
+      if (!isEdited[P.meshBuild]) continue;
+      if (P.activeTris != P.nf || P.levelStart.size() < 2u || P.levelStart.back() != P.nodeCount || (size_t)P.nodeOff + P.nodeCount > H.bvh.nodes.size()) return GI_C_OK;
+      units.push_back(Unit{P.nodeOff, &P.levelStart}); editedParts.push_back(i);
+    }
+    if (units.empty()) return GI_C_OK;
+  }
+  size_t maxLevels = 0;
+  for (const Unit& u : units) maxLevels = std::max(maxLevels, u.levelStart->size() - 1u);
+  struct Level { uint32_t first, ranges, threads; };
+  std::vector<RefitRange> ranges; std::vector<Level> levels; // levels[0] = the deepest
+  for (size_t L = maxLevels; L-- > 0;) {
+    Level lv{(uint32_t)ranges.size(), 0u, 0u};
+    for (const Unit& u : units) {
+      if (L + 1u >= u.levelStart->size()) continue;
+      const uint32_t a = (*u.levelStart)[L], e = (*u.levelStart)[L + 1u];
+      if (e <= a || (size_t)u.nodeOff + e > s->nodeCount) return GI_C_OK; // (cannot happen: the levels of a tree inside the node array)
+      ranges.push_back(RefitRange{lv.threads, u.nodeOff + a}); lv.ranges++; lv.threads += e - a;
+    }
+    levels.push_back(lv);
+  }
+  // --- host: the edited meshes' vertex and shading records; the partitioned layout's host triangles
+  for (uint32_t b : edited) {
+    const MeshBuild& mb = H.meshBuilds[b];
+    for (size_t i = 0; i < mb.m->vertices.size(); i++) H.verts[mb.vertexOffset + i] = packVertex(mb.m->vertices[i]);
+    for (size_t f = 0; f < mb.m->faces.size(); f++) H.triShade[mb.shadeBase + f] = packTriShade(mb.m, mb.m->faces[f], mb.vertexOffset);
+  }
+  for (uint32_t i : editedParts) {
+    const InstPart& P = H.parts[i];
+    const MeshBuild& mb = H.meshBuilds[P.meshBuild];
+    const InstanceRec& ir = H.instances[mb.instFirst + P.instInMesh];
+    for (uint32_t k = 0; k < P.nf; k++) {
+      TriRec& t = H.bvh.tris[P.triFirst + k];
+      TriRec whole; flattenTriangle(ir, true, mb.m, t.prim, whole);
+      memcpy(t.v0, whole.v0, 12); memcpy(t.e1, whole.e1, 12); memcpy(t.e2, whole.e2, 12);
+    }
+  }
+  const double t1 = nowMs();
+  // --- every device of the scene, on its own stream.  Out of memory for the temporaries: the edit goes to buildScene (which sends everything anew)
+  bool outOfMemory = false; Node8 root{}; std::vector<Node8> partRoots(editedParts.size());
+  const uint32_t instanceCount = (uint32_t)H.instances.size(), shadeCount = (uint32_t)H.triShade.size();
+  const int rcDev = onSceneDevices(s, residentDeviceCount(s), [&](SceneDevice& D, hipStream_t st) -> int {
+    if (D.dTris.count < s->triCount || D.dNodes.count < s->nodeCount || D.dInstances.count < instanceCount || D.dTriShade.count < shadeCount ||
+        D.dVerts.count < H.verts.size()) { setError("internal: the device holds less than the scene"); return GI_C_ERROR; }
+    DeviceBuffer<float> dBoxes; DeviceBuffer<uint32_t> dEdited; DeviceBuffer<RefitRange> dRanges;
+    auto releaseAll = [&] { dBoxes.release(); dEdited.release(); dRanges.release(); };
+    const int a = dBoxes.alloc((size_t)s->nodeCount * 8u), b2 = a ? a : dEdited.alloc(editedOfInstance.size()), c = b2 ? b2 : dRanges.alloc(ranges.size());
+    if (c != GI_C_OK) { releaseAll(); if (c == GI_C_OUT_OF_MEMORY_INTERNAL) { outOfMemory = true; return DEVICE_BUILD_FALLBACK; } return GI_C_ERROR; }
+    int rc = GI_C_OK;
+    auto copy = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+      if (rc == GI_C_OK && bytes && hipMemcpyAsync(dst, src, bytes, kind, st) != hipSuccess) { setError("vertex update: copy failed"); rc = GI_C_ERROR; } };
+    for (uint32_t b : edited) {
+      const MeshBuild& mb = H.meshBuilds[b];
+      copy(D.dVerts.ptr + mb.vertexOffset, &H.verts[mb.vertexOffset], mb.m->vertices.size() * sizeof(FVertex), hipMemcpyHostToDevice);
+      copy(D.dTriShade.ptr + mb.shadeBase, &H.triShade[mb.shadeBase], mb.m->faces.size() * sizeof(TriShade), hipMemcpyHostToDevice);
+    }
+    copy(dEdited.ptr, editedOfInstance.data(), editedOfInstance.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    copy(dRanges.ptr, ranges.data(), ranges.size() * sizeof(RefitRange), hipMemcpyHostToDevice);
+    if (rc == GI_C_OK) {
+      launchRefitTris(st, D.dTris.ptr, s->triCount, D.dInstances.ptr, instanceCount, dEdited.ptr, D.dTriShade.ptr, shadeCount);
+      for (const Level& lv : levels) launchRefitLevel(st, D.dNodes.ptr, s->nodeCount, dBoxes.ptr, dRanges.ptr + lv.first, lv.ranges, lv.threads, D.dTris.ptr,
+          s->triCount, D.dInstances.ptr, instanceCount, D.dTriShade.ptr, shadeCount);
+      if (hipGetLastError() != hipSuccess) { setError("vertex update: launch failed"); rc = GI_C_ERROR; }
+    }
+    if (D.slot == 0u) { // (the refit is deterministic: every device holds the same bytes)
+      if (!H.partitioned) copy(&root, D.dNodes.ptr, sizeof(Node8), hipMemcpyDeviceToHost);
+      for (size_t k = 0; k < editedParts.size(); k++) copy(&partRoots[k], D.dNodes.ptr + H.parts[editedParts[k]].nodeOff, sizeof(Node8), hipMemcpyDeviceToHost);
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && rc == GI_C_OK) { setError("vertex update: device error"); rc = GI_C_ERROR; }
+    releaseAll(); // (before the render's memory plan reads free memory)
+    return rc;
+  });
+  if (rcDev == DEVICE_BUILD_FALLBACK && outOfMemory) {
+    if (getenv("GATLING_BUILD_TIMING")) fprintf(stderr, "[gatling_gi] vertex update: out of device memory for the refit's boxes; the scene is rebuilt\n");
+    return GI_C_OK;
+  }
+  if (rcDev != GI_C_OK) return GI_C_ERROR;
+  // --- the scene bounds; the top tree of a partitioned scene; the host copies
+  if (!H.partitioned) {
+    setSceneBounds(s, std::vector<Node8>{root});
+    if (!H.deviceBuilt && !H.hostTreeDropped) { // the host copies of a host-built tree are stale from here on: dropped
+      std::vector<Node8>().swap(H.bvh.nodes); std::vector<TriRec>().swap(H.bvh.tris); std::vector<int32_t>().swap(H.triFaceId);
+      H.hostTreeDropped = true;
+    }
+  } else {
+    for (size_t k = 0; k < editedParts.size(); k++) { InstPart& P = H.parts[editedParts[k]]; H.bvh.nodes[P.nodeOff] = partRoots[k]; nodeBounds(partRoots[k], P.box); }
+    if (rebuildTop(s, H) != GI_C_OK) return GI_C_ERROR;
+    setSceneBounds(s, H.bvh.nodes);
+    if (onSceneDevices(s, residentDeviceCount(s), [&](SceneDevice& D, hipStream_t st) -> int {
+      if (uploadTopTree(D, H, st) != GI_C_OK) return GI_C_ERROR;
+      HIP_TRY(hipStreamSynchronize(st));
+      return GI_C_OK;
+    }) != GI_C_OK) return GI_C_ERROR;
+  }
+  const double t2 = nowMs();
+  cost.uploadMs = t2 - t0; // (no tree was built: buildMs stays 0)
+  if (getenv("GATLING_BUILD_TIMING")) fprintf(stderr, "[gatling_gi] vertex update: %zu mesh(es), %zu refit unit(s), %zu level launch(es), host %.2f ms, device %.2f "
+                                              "ms\n", edited.size(), units.size(), levels.size(), t1 - t0, t2 - t1);
+  handled = true;
+  return GI_C_OK;
+}
+
+// brings the device scene up to date with the host-side edits: incremental for DIRTY_BVH raised by vertex edits alone (opt-in: the tree refitted on the
+// device), by visibility toggles alone (opt-in: ids renumbered, the
 // toggled meshes' triangles hidden / shown in place), for material-side edits alone (the small arrays + one word per triangle) and for transform edits alone
-// (those instances re-transformed / re-braided) -- all three may be due, and run in this order -- else a full build
+// (those instances re-transformed / re-braided) -- all four may be due, and run in this order -- else a full build
 int syncSceneGeometry(GiCScene* s)
 {
   UpdateCost spent; bool updated = false; // what the updates that ran spent: all of them go into the statistics
@@ -1016,7 +1204,14 @@ int syncSceneGeometry(GiCScene* s)
     s->dirty |= DIRTY_FRAMEBUFFER;
     return GI_C_OK;
   };
-  int rc = run((s->dirty & DIRTY_BVH) && !s->rebuildDue && visibilityUpdatesWanted(s), updateVisibility, UPDATE_VISIBILITY, DIRTY_BVH, 0u, 0u);
+  // DIRTY_BVH without rebuildDue: visibility toggles and vertex edits alone raised it.  Each kind needs its option, else the rebuild is due; a vertex update
+  // that declines makes it due as well (the visibility update behind it must not clear the flag).  With both kinds due the vertex update leaves DIRTY_BVH to
+  // the visibility update.
+  bool anyVis = false, anyVerts = false;
+  for (const GiCMesh* m : s->meshes) { anyVis = anyVis || m->visToggled; anyVerts = anyVerts || m->vertsEdited; }
+  if ((s->dirty & DIRTY_BVH) && anyVerts && (!vertexUpdatesWanted(s) || (anyVis && !visibilityUpdatesWanted(s)))) s->rebuildDue = true;
+  int rc = run((s->dirty & DIRTY_BVH) && !s->rebuildDue && anyVerts, updateVertices, UPDATE_VERTEX, anyVis ? 0u : (uint32_t)DIRTY_BVH, DIRTY_BVH, 0u);
+  if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_BVH) && !s->rebuildDue && visibilityUpdatesWanted(s), updateVisibility, UPDATE_VISIBILITY, DIRTY_BVH, 0u, 0u);
   if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_MATERIALS) && !(s->dirty & DIRTY_BVH), updateMaterials, UPDATE_MATERIAL, DIRTY_MATERIALS, DIRTY_BVH, DIRTY_BVH);
   if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_XFORM) && !(s->dirty & (DIRTY_BVH | DIRTY_MATERIALS)), updateTransforms, UPDATE_TRANSFORM, 0u, DIRTY_BVH, 0u);
   if (updated) { s->stats.bvhBuildMs = spent.buildMs; s->stats.uploadMs = spent.uploadMs; s->stats.nodeCount = s->nodeCount;
@@ -1029,6 +1224,6 @@ int syncSceneGeometry(GiCScene* s)
     s->dirty &= ~(DIRTY_BVH | DIRTY_MATERIALS); s->dirty |= DIRTY_FRAMEBUFFER;
   }
   s->dirty &= ~DIRTY_XFORM; s->rebuildDue = false;
-  for (GiCMesh* m : s->meshes) m->visToggled = false;
+  for (GiCMesh* m : s->meshes) { m->visToggled = false; m->vertsEdited = false; }
   return GI_C_OK;
 }

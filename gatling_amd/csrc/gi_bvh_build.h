@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <vector>
 
 #include "gi_types.h"
 
@@ -18,6 +19,7 @@ struct DeviceBvhResult {
   Node8 root{};             // node 0, read back for the scene bounds
   double ms[4] = {0, 0, 0, 0}; // boxes, sort, PLOC (+ the collapse DP it fills), emission (+ the inactive tail)
   uint32_t plocIterations = 0;
+  std::vector<uint32_t> levelStart; // first node of every breadth-first level, then nodeCount: maxDepth + 1 entries (Bvh8::levelStart)
   const char* error = "";
 };
 

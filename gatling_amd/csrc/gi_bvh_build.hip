@@ -475,13 +475,14 @@ int buildBvh8Device(hipStream_t st, TriRec* tris, int32_t* faceId, uint32_t n, u
     for (int a = 0; a < 3; a++) { root.e[a] = 127; for (int s = 0; s < 8; s++) { root.qlo[a][s] = 255; root.qhi[a][s] = 0; } }
     DB_TRY(hipMemcpyAsync(nodesTmp, &root, sizeof(root), hipMemcpyHostToDevice, st));
     DB_TRY(hipStreamSynchronize(st)); // (`root` leaves scope)
-    levels = 1;
+    levels = 1; out.levelStart.push_back(0u);
   } else {
     const Tree2 T{nLo, nHi, left, right, total, dp, A};
     DB_TRY(hipMemcpyAsync(lvA, &root2, 4, hipMemcpyHostToDevice, st));
     uint32_t levelStart = 0, m = 1;
     while (m > 0u) {
       if (++levels > maxLevels) return DEVICE_BVH_TOO_DEEP;
+      out.levelStart.push_back(levelStart);
       k_bvh_plan<<<blocksFor(m), kBlock, 0, st>>>(T, lvA, m, levels == 1u, plans, counts);
       DB_TRY(rocprim::inclusive_scan(scan2Tmp, scan2Bytes, counts, cincl, m, rocprim::plus<uint64_t>(), st));
       uint64_t sums = 0;
@@ -511,6 +512,7 @@ int buildBvh8Device(hipStream_t st, TriRec* tris, int32_t* faceId, uint32_t n, u
   }
   ar.release();
   const double t4 = nowMsDev();
+  out.levelStart.push_back(nodeCount);
   out.nodes = tree; out.nodeCount = nodeCount; out.maxDepth = levels; out.activeTris = A;
   out.ms[0] = t1 - t0; out.ms[1] = t2 - t1; out.ms[2] = t3 - t2; out.ms[3] = t4 - t3; out.plocIterations = plocIters;
   return DEVICE_BVH_OK;

@@ -341,6 +341,7 @@ int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value)
   if (option == GI_C_SCENE_OPTION_SAMPLE_LOOKAHEAD) { scene->optLookahead = value > 1 ? value : 0; return GI_C_OK; }
   // (no dirty flag: the option decides how FUTURE visibility edits are applied)
   if (option == GI_C_SCENE_OPTION_VISIBILITY_UPDATES) { scene->optVisibilityUpdates = value == 1 ? 1 : 0; return GI_C_OK; }
+  if (option == GI_C_SCENE_OPTION_VERTEX_UPDATES) { scene->optVertexUpdates = value == 1 ? 1 : 0; return GI_C_OK; } // (likewise: future vertex edits)
   setError("unknown scene option"); return GI_C_ERROR;
 }
 

@@ -1,6 +1,7 @@
 // gi_debug.cpp -- giCTraceRays and the debug / self-check entry points
 // (one of the translation units gi_c.cpp was split into in round 6; shared declarations: gi_host.h)
 #include "gi_host.h"
+#include "gi_refit.h"
 
 // ---------------------------------------------------------------------------------------------------------------
 // giCTraceRays: closest hits through the device traversal kernel (parity tests of the BVH8 path)
@@ -264,6 +265,77 @@ extern "C" int giCDebugValidateSceneBvh(const GiCScene* scene, uint32_t deviceIn
   return violations;
 }
 
+// giCDebugRefitBvh: the refit's arithmetic (gi_refit.h, what gi_refit.hip's kernels run) on the host -- a tree built over A, refitted to B, validated against B
+extern "C" int giCDebugRefitBvh(const float* triVertsA, const float* triVertsB, uint32_t triCount, uint32_t* outNodeCount, uint32_t* outMaxDepth)
+{
+  if (triCount && (!triVertsA || !triVertsB)) return -1;
+  std::vector<TriRec> tris(triCount);
+  for (uint32_t i = 0; i < triCount; i++) {
+    const float* p = triVertsA + 9 * (size_t)i;
+    for (int a = 0; a < 3; a++) { tris[i].v0[a] = p[a]; tris[i].e1[a] = p[3 + a] - p[a]; tris[i].e2[a] = p[6 + a] - p[a]; }
+    tris[i].instance = 0; tris[i].prim = i; tris[i].origId = i;
+  }
+  Bvh8 bvh; buildBvh8(tris, bvh);
+  const size_t nodesBefore = bvh.nodes.size();
+  for (TriRec& t : bvh.tris) { // the records where the builder left them; the id names the triangle
+    if (t.origId >= triCount) return -1;
+    const float* p = triVertsB + 9 * (size_t)t.origId;
+    for (int a = 0; a < 3; a++) { t.v0[a] = p[a]; t.e1[a] = p[3 + a] - p[a]; t.e2[a] = p[6 + a] - p[a]; }
+  }
+  std::vector<float> boxes(bvh.nodes.size() * 8u, 0.0f);
+  const RefitScene S{bvh.tris.data(), (uint32_t)bvh.tris.size(), nullptr, 0u, nullptr, 0u};
+  refitHost(bvh.nodes.data(), (uint32_t)bvh.nodes.size(), 0u, boxes.data(), S);
+  if (outNodeCount) *outNodeCount = (uint32_t)bvh.nodes.size();
+  if (outMaxDepth) *outMaxDepth = bvh.maxDepth;
+  if (bvh.nodes.size() != nodesBefore || bvh.levelStart.size() != (size_t)bvh.maxDepth + 1u || bvh.levelStart.back() != bvh.nodes.size()) return -1;
+  return validateTree(bvh.nodes, bvh.tris, triCount);
+}
+
+// giCDebugSceneRefitCheck: the resident nodes and triangles downloaded, the host refit run over a copy: a refit is a function of topology and triangles alone
+extern "C" int giCDebugSceneRefitCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t* outNodes)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!g_ctx.initialized || !s) { setError("giCDebugSceneRefitCheck: bad arguments"); return -1; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  if (!s->host) { setError("giCDebugSceneRefitCheck: the scene has not been built (render it once)"); return -1; }
+  if (deviceIndex > s->replicas.size() || deviceIndex >= sceneDeviceCount(s)) { setError("giCDebugSceneRefitCheck: no such device copy"); return -1; }
+  SceneDevice& D = sceneDevice(s, deviceIndex);
+  const SceneHost& H = *s->host;
+  const uint32_t nodeCount = s->nodeCount, triCount = s->triCount;
+  std::vector<Node8> nodes(nodeCount); std::vector<TriRec> tris(triCount);
+  if (hipSetDevice(g_ctx.devs[D.slot].device) != hipSuccess || D.dNodes.count < nodeCount || D.dTris.count < triCount ||
+      (nodeCount && hipMemcpy(nodes.data(), D.dNodes.ptr, (size_t)nodeCount * sizeof(Node8), hipMemcpyDeviceToHost) != hipSuccess) ||
+      (triCount && hipMemcpy(tris.data(), D.dTris.ptr, (size_t)triCount * sizeof(TriRec), hipMemcpyDeviceToHost) != hipSuccess)) {
+    (void)hipSetDevice(g_ctx.device); setError("giCDebugSceneRefitCheck: download failed"); return -1;
+  }
+  (void)hipSetDevice(g_ctx.device);
+  // Flat layouts: every node.  Partitioned layout: the live nodes of every part, [nodeOff, nodeOff + nodeCount) -- the top tree is built over padded part
+  // bounds, not refitted, and the reserve behind a part's nodes may hold what an earlier, larger subtree left there
+  std::vector<std::pair<uint32_t, uint32_t>> spans; // (first, count)
+  if (!H.partitioned) spans.emplace_back(0u, nodeCount);
+  else for (const InstPart& P : H.parts) {
+    if ((uint64_t)P.nodeOff + P.nodeCount > nodeCount) { setError("giCDebugSceneRefitCheck: a part lies outside the node array"); return -1; }
+    spans.emplace_back(P.nodeOff, P.nodeCount);
+  }
+  for (uint32_t i = 0; i < nodeCount; i++) { // refitHost walks by descending index: every internal child must lie behind its parent
+    const uint32_t internal = (uint32_t)__builtin_popcount(nodes[i].imask);
+    if (internal && ((uint64_t)nodes[i].childBase <= i || (uint64_t)nodes[i].childBase + internal > nodeCount)) { setError("giCDebugSceneRefitCheck: malformed tree"); return -1; }
+  }
+  std::vector<Node8> refitted(nodes);
+  std::vector<float> boxes((size_t)nodeCount * 8u, 0.0f);
+  // shading records only where the triangle records name them (scenes beyond LDS)
+  const RefitScene S{tris.data(), triCount, H.shadePacked ? H.instances.data() : nullptr, (uint32_t)H.instances.size(), H.shadePacked ? H.triShade.data() : nullptr,
+      (uint32_t)H.triShade.size()};
+  int differ = 0; uint32_t compared = 0;
+  for (const auto& sp : spans) { // (children before parents: descending index inside a tree)
+    for (uint32_t i = sp.first + sp.second; i-- > sp.first;) refit_node(refitted.data(), nodeCount, i, boxes.data(), S);
+    for (uint32_t i = sp.first; i < sp.first + sp.second; i++) if (memcmp(&refitted[i], &nodes[i], sizeof(Node8)) != 0) differ++;
+    compared += sp.second;
+  }
+  if (outNodes) *outNodes = compared;
+  return differ;
+}
+
 // giCDebugShadeClass: which k_shade variant an (untextured) material's hits are binned for -- host only
 extern "C" int giCDebugShadeClass(const GiCMaterialDesc* desc)
 {
@@ -391,6 +463,7 @@ extern "C" int32_t giCDebugEditDirtyFlags(int32_t edit, int32_t built)
     case 13: madeMesh = giCCreateMesh(s, &meshDesc); break;
     case 14: giCDestroyMesh(mesh); mesh = nullptr; break;
     case 15: giCSetMeshInstanceTransforms(mesh, 0, nullptr); break;
+    case 16: if (giCSetMeshVertices(mesh, 3, verts) != GI_C_OK) result = -1; break;
     default: result = -1; break;
   }
   if (result == 0) result = (int32_t)s->dirty;
@@ -419,6 +492,15 @@ extern "C" int giCDebugSceneVisibilityUpdateCount(const GiCScene* scene, uint64_
   if (!s || !outCount) { setError("giCDebugSceneVisibilityUpdateCount: bad arguments"); return GI_C_ERROR; }
   std::lock_guard<std::mutex> guard(s->mutex);
   *outCount = s->updateCounts[UPDATE_VISIBILITY];
+  return GI_C_OK;
+}
+
+extern "C" int giCDebugSceneVertexUpdateCount(const GiCScene* scene, uint64_t* outCount)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!s || !outCount) { setError("giCDebugSceneVertexUpdateCount: bad arguments"); return GI_C_ERROR; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  *outCount = s->updateCounts[UPDATE_VERTEX];
   return GI_C_OK;
 }
 

@@ -167,6 +167,7 @@ struct GiCMesh {
   std::vector<uint8_t> instDirty; // ... and which instances (empty: all of them)
   uint32_t builtInstances = 0xffffffffu; // instance count the built scene holds for this mesh (0xffffffff: not part of it)
   bool visToggled = false;  // giCSetMeshVisibility was called since the last syncSceneGeometry
+  bool vertsEdited = false; // giCSetMeshVertices was called since the last syncSceneGeometry
 };
 
 // swap-remove dense store (GgpuDenseDataStore, src/ggpu/impl/DenseDataStore.cpp:35-93): the arrays stay dense so
@@ -288,7 +289,10 @@ struct MeshBuild { const GiCMesh* m; uint32_t vertexOffset, matFlags, instFirst,
     bool hidden = false; uint32_t idBase = 0; };
 // One flattened mesh instance of a PARTITIONED scene (after the first transform edit): its own subtree in its own node range, its triangles in its own
 // (scene-order) range, joined by a top tree over the subtree roots (bvh8.h buildTopBvh8).  Moving it rebuilds these ranges and the top tree only.
-struct InstPart { uint32_t meshBuild, instInMesh; uint32_t triFirst, nf; uint32_t nodeOff, nodeCount, nodeCap, depth; float box[6]; };
+struct InstPart { uint32_t meshBuild, instInMesh; uint32_t triFirst, nf; uint32_t nodeOff, nodeCount, nodeCap, depth; float box[6];
+    // vertex updates (gi_build.cpp updateVertices): triangles the subtree holds (nf unless some were inactive when it was built), and the first node of every
+    // level of the subtree relative to nodeOff, then nodeCount (Bvh8::levelStart)
+    uint32_t activeTris = 0; std::vector<uint32_t> levelStart; };
 struct SceneHost {
   std::vector<FVertex> verts; std::vector<InstanceRec> instances; std::vector<MaterialRec> mats; std::vector<MeshRec> meshRecs; std::vector<float> sceneData;
   Bvh8 bvh; std::vector<int32_t> triFaceId; std::vector<uint32_t> flatOfOrig; TwoLevelHost two;
@@ -298,9 +302,12 @@ struct SceneHost {
   bool partitioned = false; std::vector<InstPart> parts; uint32_t topCap = 0; // partitioned layout: nodes [0, topCap) = top tree, then the parts' ranges
   // the device builder made the tree: it exists only in device memory (dNodes / dTris / dTriFaceId); `bvh` keeps its sizes (maxDepth, activeTris) alone
   bool deviceBuilt = false;
+  // a vertex update refitted a flat host-built tree in device memory: the host copies of its nodes, triangles and face ids were dropped (they would be
+  // stale), and the scene is treated as a device-built one is -- the re-layout of the first transform edit makes them anew
+  bool hostTreeDropped = false;
 };
 
-enum : uint32_t { UPDATE_FULL = 0, UPDATE_TRANSFORM = 1, UPDATE_MATERIAL = 2, UPDATE_VISIBILITY = 3 }; // GiCScene::updateCounts
+enum : uint32_t { UPDATE_FULL = 0, UPDATE_TRANSFORM = 1, UPDATE_MATERIAL = 2, UPDATE_VISIBILITY = 3, UPDATE_VERTEX = 4 }; // GiCScene::updateCounts
 struct GiCScene : SceneDevice {
   std::mutex mutex;
   uint32_t dirty = DIRTY_ALL;
@@ -355,13 +362,16 @@ struct GiCScene : SceneDevice {
   // contents of the device arrays: bumped by every scene build, transform update, material update and light upload --
   // a look-ahead window traced under another generation is not served from
   uint64_t generation = 0;
-  // syncSceneGeometry, by UPDATE_*: full builds and incremental updates (giCDebugSceneUpdateCounts: the first three; giCDebugSceneVisibilityUpdateCount)
-  uint64_t updateCounts[4] = {0, 0, 0, 0};
+  // syncSceneGeometry, by UPDATE_*: full builds and incremental updates (giCDebugSceneUpdateCounts: the first three; giCDebugSceneVisibilityUpdateCount,
+  // giCDebugSceneVertexUpdateCount)
+  uint64_t updateCounts[5] = {0, 0, 0, 0, 0};
   int32_t optVisibilityUpdates = 0; // GI_C_SCENE_OPTION_VISIBILITY_UPDATES: 1 = visibility edits are applied to the resident scene (updateVisibility)
-  // DIRTY_BVH was raised by something other than giCSetMeshVisibility since the last syncSceneGeometry (raiseRebuild): the rebuild is due whatever was toggled
+  int32_t optVertexUpdates = 0; // GI_C_SCENE_OPTION_VERTEX_UPDATES: 1 = vertex edits refit the resident tree (updateVertices)
+  // DIRTY_BVH was raised by something other than giCSetMeshVisibility / giCSetMeshVertices since the last syncSceneGeometry (raiseRebuild): the rebuild is due
+  // whatever was toggled or deformed
   bool rebuildDue = true;
 };
-// every geometry-side edit but a visibility toggle
+// every geometry-side edit but a visibility toggle and a vertex edit
 inline void raiseRebuild(GiCScene* s) { s->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER; s->rebuildDue = true; }
 
 
@@ -376,6 +386,7 @@ int uploadLights(GiCScene* s);
 uint32_t shadeClassOf(const MaterialRec& m);                 // shade class (k_shade variant) of a derived material record
 uint32_t sceneDeviceCount(const GiCScene* s);                // devices a render of this scene may use
 SceneDevice& sceneDevice(GiCScene* s, uint32_t slot);
+bool usableVertexPositions(const GiCVertex* v, size_t count);  // every position finite and within 1e18 (bvh8.h "Inactive items")
 void nodeBounds(const Node8& n, float box[6]);               // dequantised bounds of a node's children (+ an ulp-scale pad)
 int syncSceneGeometry(GiCScene* s);                          // brings the device scene up to date with the host-side edits (incremental or full build)
 // dirty flags of a material-side edit: DIRTY_MATERIALS alone once the scene / the mesh is part of a built scene (the incremental path), else with DIRTY_BVH

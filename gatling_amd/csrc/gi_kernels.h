@@ -1,5 +1,5 @@
 // gi_kernels.h -- host-side launch interface of the stage kernels (gi_kernels.hip,
-// gi_trace.hip, gi_shade.hip, gi_aov.hip, gi_patch.hip) and of the fused one (gi_path.hip).
+// gi_trace.hip, gi_shade.hip, gi_aov.hip, gi_patch.hip, gi_refit.hip) and of the fused one (gi_path.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -56,7 +56,16 @@ struct VisPatch { int32_t idDelta; uint32_t action; };
 constexpr uint32_t VIS_KEEP = 0u, VIS_HIDE = 1u, VIS_SHOW = 2u;
 void launchPatchVisibility(hipStream_t s, TriRec* tris, uint32_t triCount, const InstanceRec* instances, uint32_t instanceCount, const VisPatch* patchOfInstance,
     const TriShade* triShade, uint32_t shadeCount);
-void launchSpin(hipStream_t s, unsigned long long ns);              // test hook: occupies a stream for ~ns nanoseconds
+// gi_refit.hip: a vertex edit applied to the device-resident scene (gi_build.cpp updateVertices).  launchRefitTris makes the world-space corners of the records
+// of edited instances (editedOfInstance[t.instance] != 0) again from their shading records and instance transforms; launchRefitLevel refits one tree level:
+// thread i handles node ranges[r].nodeFirst + (i - ranges[r].threadBase) of the last range r with threadBase <= i, reading the float boxes (8 floats per
+// node) of the level below and writing its own
+struct RefitRange { uint32_t threadBase, nodeFirst; };
+void launchRefitTris(hipStream_t s, TriRec* tris, uint32_t triCount, const InstanceRec* instances, uint32_t instanceCount, const uint32_t* editedOfInstance,
+    const TriShade* triShade, uint32_t shadeCount);
+void launchRefitLevel(hipStream_t s, Node8* nodes, uint32_t nodeCount, float* boxes, const RefitRange* ranges, uint32_t rangeCount, uint32_t threads,
+    const TriRec* tris, uint32_t triCount, const InstanceRec* instances, uint32_t instanceCount, const TriShade* triShade, uint32_t shadeCount);
+void launchSpin(hipStream_t s, unsigned long long ns);             // test hook: occupies a stream for ~ns nanoseconds
 void launchDebugBsdf(hipStream_t s, const MaterialRec* mat, uint32_t shadeClass, uint32_t count, const float* in, float* out);
 void launchDebugSqrt(hipStream_t s, uint32_t first, unsigned long long count, unsigned long long* mismatches); // gi_sqrt against sqrtf over bit patterns
 void launchDebugTex(hipStream_t s, const float* texels, uint32_t w, uint32_t h, uint32_t d, uint32_t count, const float* queries, float* out);

@@ -40,6 +40,8 @@
 //                                  0 / 1 = off, N >= 2 = a call may trace the samples of up to N calls in one batch (gi_render.cpp planLookahead)
 //   visibility_updates   -1        -1 = the scene option decides (GI_C_SCENE_OPTION_VISIBILITY_UPDATES), 0 / 1 = visibility edits rebuild the scene / are
 //                                  applied to the resident scene (gi_build.cpp updateVisibility)
+//   vertex_updates       -1        -1 = the scene option decides (GI_C_SCENE_OPTION_VERTEX_UPDATES), 0 / 1 = vertex edits (giCSetMeshVertices) rebuild the
+//                                  scene / refit the resident tree on the device (gi_build.cpp updateVertices, gi_refit.hip)
 //   phase_stats          0         counting builds: print k_path's phase split / k_trace_dyn's lane accounting
 #pragma once
 

@@ -145,6 +145,25 @@ void giCSetMeshVisibility(GiCMesh* mesh, int32_t visible)
   mesh->scene->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER;
 }
 
+int giCSetMeshVertices(GiCMesh* mesh, uint32_t vertexCount, const GiCVertex* vertices)
+{
+  try { // (a copy of the caller's array: an allocation failure must not cross the C ABI)
+  if (!mesh || (vertexCount && !vertices)) { setError("giCSetMeshVertices: null argument"); return GI_C_ERROR; }
+  if ((size_t)vertexCount != mesh->vertices.size()) { // (the faces index the array: the topology stays)
+    setError("giCSetMeshVertices: mesh '" + mesh->name + "' has " + std::to_string(mesh->vertices.size()) + " vertices, not " + std::to_string(vertexCount));
+    return GI_C_ERROR;
+  }
+  std::vector<GiCVertex> copy(vertices, vertices + vertexCount); // copy outside the lock, swap inside
+  std::lock_guard<std::mutex> g(mesh->scene->mutex);
+  mesh->vertices.swap(copy);
+  // the flags a geometry edit always raised; the scene notes which meshes were deformed, and syncSceneGeometry may answer with updateVertices instead of the
+  // rebuild when nothing else asked for one (GI_C_SCENE_OPTION_VERTEX_UPDATES)
+  mesh->vertsEdited = true;
+  mesh->scene->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER;
+  return GI_C_OK;
+  } catch (const std::exception& e) { setError(std::string("giCSetMeshVertices: ") + e.what()); return GI_C_ERROR; }
+}
+
 void giCDestroyMesh(GiCMesh* mesh)
 {
   if (!mesh) return;

@@ -376,7 +376,8 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * the device build when one ran).  A caller compares giCGetApiVersion() with the GI_C_API_VERSION it was built with.
  * Still 8 with GI_C_SCENE_OPTION_SAMPLE_LOOKAHEAD and giCGetLookaheadStats: no struct grew and no entry point changed meaning -- both are additions that a caller
  * built against an earlier header never sees.  A caller probes for them: giCSetSceneOption answers GI_C_ERROR for an option the library does not know.
- * The same holds for GI_C_SCENE_OPTION_VISIBILITY_UPDATES, giCDebugSceneVisibilityUpdateCount, giCDebugSceneClassState and giCDebugMissRect. */
+ * The same holds for GI_C_SCENE_OPTION_VISIBILITY_UPDATES, giCDebugSceneVisibilityUpdateCount, giCDebugSceneClassState and giCDebugMissRect, and for
+ * giCSetMeshVertices, GI_C_SCENE_OPTION_VERTEX_UPDATES, giCDebugSceneVertexUpdateCount, giCDebugRefitBvh and giCDebugSceneRefitCheck. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -406,6 +407,11 @@ void giCSetMeshInstanceIds(GiCMesh* mesh, uint32_t count, const int32_t* ids);
  * destruction, visibility, instance counts and ids). */
 void giCSetMeshMaterial(GiCMesh* mesh, GiCMaterial* mat);
 void giCSetMeshVisibility(GiCMesh* mesh, int32_t visible);
+/* [ext] Replaces the mesh's vertex array (positions, normals, texture coordinates, tangents): the points of a mesh moved, its topology stayed -- a skinned
+ * character, a cloth cache, a sculpt stroke.  Faces, face ids, primvars, material and transforms stay.  `vertexCount` must equal the mesh's vertex count:
+ * otherwise GI_C_ERROR with a message, and the mesh is unchanged.  The reference has no such entry point (a points-only sync recreates the mesh there and
+ * pays one BLAS build).  The edit raises the flags of a geometry edit; what the next giCRender does with it is GI_C_SCENE_OPTION_VERTEX_UPDATES' business. */
+int giCSetMeshVertices(GiCMesh* mesh, uint32_t vertexCount, const GiCVertex* vertices);
 void giCDestroyMesh(GiCMesh* mesh);
 
 /* Gi.h:218 */
@@ -531,6 +537,17 @@ int giCGetRenderStats(const GiCScene* scene, GiCRenderStats* out);
  * time of the update.  Hidden geometry keeps its boxes in a flat tree until the next full build.  The image does not depend on the
  * option.  GATLING_OPTIONS=visibility_updates=0|1 overrides it (hdGatling sets no scene options). */
 #define GI_C_SCENE_OPTION_VISIBILITY_UPDATES 11
+/* [ext] Incremental vertex edits: value 1 = a giCSetMeshVertices on a mesh of the built scene is applied to the device-resident scene by the next giCRender --
+ * the mesh's vertex and shading records are re-sent, its flattened triangles are made again and the scene BVH is REFITTED in device memory (same topology,
+ * new conservative boxes; the partitioned layout refits the parts of the mesh and rebuilds its top tree) -- instead of rebuilding the scene; 0 = off
+ * (default): a vertex edit rebuilds.  The image does not depend on the option (traversal contract: results do not depend on the tree).  The library falls
+ * back to the rebuild when anything but vertex edits (and, with GI_C_SCENE_OPTION_VISIBILITY_UPDATES, visibility edits) asked for one, when an edited mesh is
+ * not part of the built scene or is hidden by the visibility path, when a new position is not finite or beyond 1e18 (in object or world space), when the
+ * scene had inactive triangles at its build, with fewer than 4096 resident triangles, with GATLING_OPTIONS=incremental=0, on the two-level layout and when
+ * the device cannot hold the temporaries (32 bytes per node).  After such an edit GiCRenderStats.bvhBuildMs is 0 and uploadMs the time of the update.  A
+ * refitted tree keeps the topology chosen for the OLD positions: large deformations make it slower to walk (never wrong); any full build resets that
+ * (DESIGN.md section 6).  GATLING_OPTIONS=vertex_updates=0|1 overrides the option (hdGatling sets no scene options). */
+#define GI_C_SCENE_OPTION_VERTEX_UPDATES 12
 int giCGetLookaheadStats(const GiCScene* scene, GiCLookaheadStats* out);
 int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value);
 /* [ext] closest hit of one ray through the device traversal kernel (parity tests of the BVH8 path).
@@ -563,6 +580,15 @@ int giCDebugValidateBvh(const float* triVerts, uint32_t triCount, uint32_t* outN
  * subtree each, joined by a top tree over the subtree roots.  Returns the violations of the assembled tree (0 = every triangle reachable and inside every
  * ancestor slot's box), <0 on error. */
 int giCDebugValidatePartitionedBvh(const float* triVerts, uint32_t triCount, uint32_t partCount, uint32_t* outNodeCount, uint32_t* outMaxDepth);
+/* [ext] host-only check of the BVH refit (gi_refit.h, the arithmetic the device kernels run): builds the tree over the `triCount` triangles of `triVertsA`
+ * (9 floats each), moves them to `triVertsB`, refits the tree -- same topology, new boxes -- and validates it against B as giCDebugValidateBvh does.  Returns
+ * the number of violations (0 = conservative), <0 on error; outNodeCount / outMaxDepth describe the tree, which a refit does not change. */
+int giCDebugRefitBvh(const float* triVertsA, const float* triVertsB, uint32_t triCount, uint32_t* outNodeCount, uint32_t* outMaxDepth);
+/* [ext] the nodes and triangles resident on device `deviceIndex` of a scene rendered at least once are downloaded and the host runs the refit over a copy of
+ * them.  A refit is a function of the topology and the triangles alone, so the host must reproduce the resident bytes: returns the number of nodes whose 80
+ * bytes differ (0 after a build as after a vertex update), <0 on error.  outNodes: nodes compared (partitioned layout: the parts' live nodes -- the top tree is
+ * built over padded part bounds, not refitted). */
+int giCDebugSceneRefitCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t* outNodes);
 /* [ext] the tree resident on device `deviceIndex` (0 = primary) of a scene rendered at least once, downloaded and checked: every active triangle reachable and
  * inside every ancestor slot's box; and (flat, unpartitioned layout) nodes breadth-first, internal children contiguous in slot order at childBase, leaf
  * triangles contiguous at triBase, every active id once in [0, activeTris), the inactive ones behind in id order; depth <= 49.  outBuiltOnDevice: 1 when the
@@ -575,7 +601,7 @@ int giCDebugValidateSceneBvh(const GiCScene* scene, uint32_t deviceIndex, uint32
  * the rebuild bit take the incremental paths (see giCSetMeshMaterial).  `edit`: 0 giCCreateMaterial, 1 giCDestroyMaterial, 2 giCSetMeshMaterial,
  * 3 giCSetMaterialPrimvarInput, 4 giCSetMaterialTexture, 5 giCSetMaterialTextureTransform, 6 giCCreateTexture, 7 giCDestroyTexture, 8 giCSetMeshPrimvars,
  * 9 giCSetMeshInstancerPrimvars, 10 giCSetMeshTransform, 11 giCSetMeshVisibility, 12 giCSetMeshInstanceIds, 13 giCCreateMesh, 14 giCDestroyMesh,
- * 15 giCSetMeshInstanceTransforms with another instance count.  <0 on error. */
+ * 15 giCSetMeshInstanceTransforms with another instance count, 16 giCSetMeshVertices.  <0 on error. */
 int32_t giCDebugEditDirtyFlags(int32_t edit, int32_t built);
 /* [ext] how often the scene's geometry was brought up to date by outCounts[0] a full build, [1] an incremental transform update, [2] an incremental material
  * update, since the scene was created. */
@@ -583,6 +609,9 @@ int giCDebugSceneUpdateCounts(const GiCScene* scene, uint64_t* outCounts /* 3 */
 /* [ext] how often the scene was brought up to date by an incremental visibility update (GI_C_SCENE_OPTION_VISIBILITY_UPDATES); such an update is not counted
  * in giCDebugSceneUpdateCounts. */
 int giCDebugSceneVisibilityUpdateCount(const GiCScene* scene, uint64_t* outCount);
+/* [ext] how often the scene was brought up to date by an incremental vertex update (GI_C_SCENE_OPTION_VERTEX_UPDATES); not counted in
+ * giCDebugSceneUpdateCounts either. */
+int giCDebugSceneVertexUpdateCount(const GiCScene* scene, uint64_t* outCount);
 /* [ext] what the last scene sync derived from the visible meshes' materials, the state that picks a render's kernel variants: out[0] the material classes in
  * use (one bit each), [1] those with a textured material, [2] and [3] the same per shade class, [4] 1 when some visible triangle has cutout opacity.  Host
  * only: no device work. */
