@@ -40,8 +40,9 @@ void launchShade(hipStream_t s, uint32_t blocks, uint32_t klass, bool textured /
 
 // Fused persistent path kernel (gi_path.hip) for LDS-resident scenes; launchPath returns the resident blocks per CU it launched with
 bool pathKernelSupports(const SceneView& sc);
-int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool textured, bool count, uint32_t chunk, const FrameUniforms& U, const SceneView& sc,
-               const PathState& st, Counters* cnt, F4* sampleBuf);
+int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool textured, bool count, uint32_t chunk, uint32_t walkCarry, const FrameUniforms& U,
+               const SceneView& sc, const PathState& st, Counters* cnt, F4* sampleBuf);
+constexpr long WALK_CARRY_DEFAULT = 8; // GATLING_OPTIONS=walk_carry (gi_options.h)
 
 void launchAov(hipStream_t s, const FrameUniforms& U, const SceneView& sc, const AovTargets& A);
 void launchResolveNee(hipStream_t s, const FrameUniforms& U, const unsigned long long* key, F4* aov, uint32_t pixelCount);

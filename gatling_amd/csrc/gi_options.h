@@ -19,6 +19,9 @@
 //                                  deferred slots) and in k_path's ring preparation (fused kernel); 0 = every camera ray is traced
 //   miss_rect            1         fused frames with bounds_retire: pixels whose every camera ray misses the scene's bounds (outside an image-space rectangle
 //                                  the host derives per render, gi_miss_rect.h) get no work items and no sample records; 0 = every pixel is enumerated
+//   walk_carry           8         fused frames without next-event estimation: the closest-hit loop of a k_path trip ends once at most this many lanes are
+//                                  still walking (and more entered); they go on walking in the next trip's loop (gi_path.hip).  0 = every loop runs until
+//                                  its last ray is done; 63 (tests) = carry whenever a lane has finished.  Counting builds run with 0
 //   fused                1         LDS-resident scenes run the fused persistent kernel
 //   pool_slots           0         pin the path pool (slots); 0 = the memory plan decides
 //   sample_buffer_mb     0         pin the per-sample buffer (MiB); 0 = the memory plan decides

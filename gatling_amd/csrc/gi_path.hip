@@ -45,8 +45,10 @@ constexpr int PATH_WAVES = 4; // resident waves per SIMD the register allocation
 template <uint32_t KLASS, bool TEXTURED, bool NEE, bool CUTOUT, bool COUNT, uint32_t PATH_STACK>
 __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PATH_WAVES, 8))) void k_path(FrameUniforms U, SceneView sc, PathState st,
     Counters* cnt, F4* __restrict__ sampleBuf,
-                                                      uint32_t ldsNodes, uint32_t ldsTris, uint32_t chunk)
+                                                      uint32_t ldsNodes, uint32_t ldsTris, uint32_t chunk, uint32_t walkCarry)
 {
+  // Walk carry (NEE off): see the closest-hit loop.  The NEE variants' shadow walk reuses R and WaveTri::best[lane], so they never carry.
+  constexpr bool CARRY = !NEE;
   extern __shared__ uint4 s_dyn[];
   uint2 (*s_stack)[TRACE_BLOCK] = reinterpret_cast<uint2 (*)[TRACE_BLOCK]>(s_dyn);
   uint4* s_nodes = s_dyn + (PATH_STACK * TRACE_BLOCK * sizeof(uint2)) / sizeof(uint4);
@@ -62,13 +64,13 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
   // the path this lane carries (rp_main_payload.glsl:20-33) and its next ray
   V3 thr = v3(0.0f, 0.0f, 0.0f), rad = thr, ro = thr, rdv = v3(0.0f, 0.0f, 1.0f);
   float tMin = 0.0f, tMax = 0.0f;
-  uint32_t bitfield = 0u, rng = 0u, pixelLocal = 0u, sLocal = 0u;
-  bool alive = false;
+  uint32_t bitfield = 0u, rng = 0u, rec = 0u; // rec: the record index of the lane's sample, sample * pixelCount + tile pixel -- the path's identity
+  bool alive = false, tAlive = false; // tAlive outlives a trip: a lane still walking when the closest-hit loop ends early is carried into the next one
   uint32_t chunkNext = 0u, chunkEnd = 0u; bool exhausted = false; // wave-uniform: the claimed work items not handed out yet
   uint32_t nSeg = 0u, nShadow = 0u;
   TraceCounters tc{0u, 0u}, tcs{0u, 0u};
   uint2 overflow[1];
-  RayTrav R;
+  RayTrav R; R.G = make_uint2(0u, 0u); R.sp = 0u;
   // Camera rays are generated 64 at a time, by ALL lanes, into a per-wave LDS ring (r03): a trip regenerates only the ~45 % of the lanes whose path just ended,
   // and make_camera_ray (hash, two draws, the Gaussian filter's log / sqrt / sincos, normalise) then ran at that lane utilisation on every trip.  Now the wave
   // prepares the next 64 work items' rays whenever fewer than 64 are pending (one full-width pass every ~2 trips) and idle lanes just pop them.
@@ -80,6 +82,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
   const bool boundsRetire = (U.flags & FLAG_BOUNDS_RETIRE) != 0u;
 
   unsigned long long pc[4] = {0ull, 0ull, 0ull, 0ull}, pl[4] = {0ull, 0ull, 0ull, 0ull}, trips = 0ull, tPrev = COUNT ? __builtin_readcyclecounter() : 0ull;
+  uint32_t whLanes[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}, whTrips[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}; // COUNT: lanes walking at step 0 .. 7+ of a trip's loop
   auto phase = [&](int k,
       unsigned long long lanes) { if (COUNT) { const unsigned long long t = __builtin_readcyclecounter(); pc[k] += t - tPrev; tPrev = t; pl[k] += lanes; } };
   for (;;) {
@@ -141,8 +144,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
         const uint32_t slot = (preHead + rank) & 127u;
         ro = v3(u2f(pre[0][slot]), u2f(pre[1][slot]), u2f(pre[2][slot])); rdv = v3(u2f(pre[3][slot]), u2f(pre[4][slot]), u2f(pre[5][slot]));
         tMin = u2f(pre[6][slot]); tMax = u2f(pre[7][slot]); rng = pre[8][slot];
-        const uint32_t rec = pre[9][slot]; // the sample's record index
-        pixelLocal = rec % U.pixelCount; sLocal = rec / U.pixelCount;
+        rec = pre[9][slot];
         thr = v3(1.0f, 1.0f, 1.0f); rad = v3(0.0f, 0.0f, 0.0f); bitfield = 0u; // :274-276
         alive = true;
       }
@@ -152,17 +154,42 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
     phase(0, nIdle); trips++;
 
     // --- closest hit (traceRayEXT, rp_main.rgen:381-393): all rays of the wave advance in steps, triangles are tested cooperatively
-    trav_init(R, ro, rdv, tMin, alive ? tMax : 0.0f);
-    wave_ray_begin(W, R.tBest);
-    bool tAlive = alive;
-    while (__ballot(tAlive)) {
-      if (wave_step<false, COUNT, PATH_STACK, false, true,
-          CUTOUT>(R, tAlive, W, sc, s_nodes, ldsNodes, s_tris, ldsTris, s_stack, overflow, tc, rng)) tAlive = false;
+    // Walk carry: the loop below runs until the SLOWEST of the wave's 64 incoherent rays is done, and its last steps pay the whole per-step cost (8-box node
+    // test, scan, ring append, a partial triangle batch, pop) for a handful of lanes.  So once at most walkCarry lanes are still walking -- and more than that
+    // entered, i.e. some lane has finished -- the loop ends; the stragglers skip this trip's shading and finish and go on walking in the NEXT trip's loop, beside
+    // the new rays.  Their walk state is per lane already: group and stack pointer in R, the stack column in LDS, the nearest hit in W.best / W.hit[lane]; ro, rdv
+    // and tMin stay put because a carried lane does nothing after the loop, and what trav_init derives from them is derived again.  Per-ray arithmetic, culling
+    // distance and the atomicMin key are what they were: the walk of a ray is the same sequence of steps, cut in two.  If no more than walkCarry lanes enter (the
+    // frame's tail) the loop runs to completion, so every trip retires at least one segment.  walkCarry = 0: every loop runs to completion.
+    {
+      const bool carried = CARRY && tAlive;
+      const uint2 G = R.G; const uint32_t sp = R.sp;
+      trav_init(R, ro, rdv, tMin, alive ? tMax : 0.0f);
+      if (carried) { R.G = G; R.sp = sp; R.tBest = u2f(wt_best_t(W, lane)); }
+      else wave_ray_begin(W, R.tBest);
     }
+    tAlive = alive;
+    if (CARRY) {
+      unsigned long long walking = __ballot(tAlive);
+      const uint32_t stop = (uint32_t)__popcll(walking) > walkCarry ? walkCarry : 0u;
+      uint32_t step = 0u;
+      while ((uint32_t)__popcll(walking) > stop) {
+        if (COUNT) { whLanes[step] += (uint32_t)__popcll(walking); whTrips[step]++; step = step < 7u ? step + 1u : 7u; }
+        if (wave_step<false, COUNT, PATH_STACK, false, true,
+            CUTOUT>(R, tAlive, W, sc, s_nodes, ldsNodes, s_tris, ldsTris, s_stack, overflow, tc, rng)) tAlive = false;
+        walking = __ballot(tAlive);
+      }
+    } else {
+      while (__ballot(tAlive)) {
+        if (wave_step<false, COUNT, PATH_STACK, false, true,
+            CUTOUT>(R, tAlive, W, sc, s_nodes, ldsNodes, s_tris, ldsTris, s_stack, overflow, tc, rng)) tAlive = false;
+      }
+    }
+    const bool walked = CARRY ? alive && !tAlive : alive; // this trip ended the lane's segment
     bool ended = false, missed = false;
     ShadeIO io; io.shadow = false; io.shadowFirst = false; io.cont = false;
-    phase(1, (unsigned long long)__popcll(__ballot(alive)));
-    if (alive) {
+    phase(1, (unsigned long long)__popcll(__ballot(walked)));
+    if (walked) {
       nSeg++;
       wave_ray_end(W, R);
       if (R.found) { // rp_main.chit + rp_main.rgen:397-480
@@ -171,17 +198,17 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
         shade_segment<KLASS, TEXTURED, false, NEE>(U, sc, nullptr, h, rd, io);
         thr = io.throughput; rad = io.radiance; bitfield = io.bitfield; rng = io.rng;
         // untraced shadow ray == "not shadowed" (rp_main.rgen:431-435)
-        if (NEE && st.neeKey && io.shadowFirst && !io.shadow) nee_aov_record_px(st, pixelLocal, sLocal, false);
+        if (NEE && st.neeKey && io.shadowFirst && !io.shadow) nee_aov_record_px(st, rec % U.pixelCount, rec / U.pixelCount, false);
         ended = !io.cont;
       } else { // rp_main.miss:68-86: uniform fallback dome == colour clear value; the loop's bounce++ still happens (rp_main.rgen:480)
         rad = rad + thr * v3(U.background);
-        if (st.neeKey && (bitfield & 0x00000fffu) == 0u) nee_aov_record_px(st, pixelLocal, sLocal, false);
+        if (st.neeKey && (bitfield & 0x00000fffu) == 0u) nee_aov_record_px(st, rec % U.pixelCount, rec / U.pixelCount, false);
         bitfield++;
         ended = true; missed = true;
       }
     }
     (void)missed;
-    phase(2, (unsigned long long)__popcll(__ballot(alive && R.found)));
+    phase(2, (unsigned long long)__popcll(__ballot(walked && R.found)));
 
     // --- shadow ray of this bounce (rp_main.rgen:397-429): origin = next ray origin, tMin 0.01, tMax = distance to the light sample
     if (NEE) {
@@ -197,25 +224,25 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
         if (traced) {
           nShadow++;
           if (!R.found) rad = rad + io.nee;
-          if (st.neeKey && io.shadowFirst) nee_aov_record_px(st, pixelLocal, sLocal, R.found);
+          if (st.neeKey && io.shadowFirst) nee_aov_record_px(st, rec % U.pixelCount, rec / U.pixelCount, R.found);
         }
       }
     }
 
     // --- next segment, or the per-sample finish (rp_main.rgen:483-496) -> per-sample colour buffer
-    if (alive) {
+    if (walked) {
       if (!ended) { ro = io.no; rdv = io.k2; tMin = 0.0f; tMax = io.tMaxNext; }
       else {
         const uint32_t bounces = bitfield & 0x00000fffu;
-        if (st.bouncesAov && U.batchFirstSample + sLocal == U.spp - 1u) { // Bounces AOV: the pixel's last sample (:483-486)
+        if (st.bouncesAov && U.batchFirstSample + rec / U.pixelCount == U.spp - 1u) { // Bounces AOV: the pixel's last sample (:483-486)
           const uint32_t maxB = U.maxBounces < 0x00000fffu ? U.maxBounces : 0x00000fffu;
           const V3 c = gi_colormap_inferno((float)bounces / (float)maxB);
-          F4* dst = &st.bouncesAov[tile_to_image_pixel(U, pixelLocal)];
+          F4* dst = &st.bouncesAov[tile_to_image_pixel(U, rec % U.pixelCount)];
           dst->x = c.x; dst->y = c.y; dst->z = c.z;
         }
-        if (st.pathSegments) atomicAdd(&st.pathSegments[pixelLocal], bounces); // ClockCycles proxy: integer sum, order-free
+        if (st.pathSegments) atomicAdd(&st.pathSegments[rec % U.pixelCount], bounces); // ClockCycles proxy: integer sum, order-free
         const V3 c = finish_sample(U, rad);
-        st4(&sampleBuf[(size_t)sLocal * U.pixelCount + pixelLocal], c.x, c.y, c.z, 0.0f);
+        st4(&sampleBuf[rec], c.x, c.y, c.z, 0.0f);
         alive = false;
       }
     }
@@ -224,7 +251,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
 
   if (COUNT
       && lane == 0u) { for (int k = 0; k < 4; k++) { atomicAdd(&cnt->phaseCycles[k], pc[k]); atomicAdd(&cnt->phaseLanes[k], pl[k]);
-      } atomicAdd(&cnt->phaseTrips, trips); }
+      } atomicAdd(&cnt->phaseTrips, trips);
+      for (int k = 0; k < 8; k++) { atomicAdd(&cnt->walkStepLanes[k], (unsigned long long)whLanes[k]); atomicAdd(&cnt->walkStepTrips[k], (unsigned long long)whTrips[k]); } }
   // statistics: one atomic per wave and counter
   unsigned long long a = nSeg, b = nShadow, c = tc.nodes, d = tc.tris, e = tcs.nodes, f = tcs.tris;
   for (int off = 32; off > 0; off >>= 1) {
@@ -251,7 +279,7 @@ bool pathKernelSupports(const SceneView& sc)
          && !sc.shadePacked;
 }
 
-using PathKernel = void (*)(FrameUniforms, SceneView, PathState, Counters*, F4*, uint32_t, uint32_t, uint32_t);
+using PathKernel = void (*)(FrameUniforms, SceneView, PathState, Counters*, F4*, uint32_t, uint32_t, uint32_t, uint32_t);
 // Hot variants: one material class, no textures, no cutouts, no counters (the C1 / C2 paths).  Everything else runs the general
 // variant (class read from the material record, textures and cutouts compiled in).
 template <uint32_t STACK>
@@ -267,8 +295,8 @@ static PathKernel pickPathKernel(uint32_t classMask, bool textured, bool nee, bo
   return nee ? k_path<KLASS_DYNAMIC, true, true, true, false, STACK> : k_path<KLASS_DYNAMIC, true, false, true, false, STACK>;
 }
 
-int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool textured, bool count, uint32_t chunk, const FrameUniforms& U, const SceneView& sc,
-               const PathState& st, Counters* cnt, F4* sampleBuf)
+int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool textured, bool count, uint32_t chunk, uint32_t walkCarry, const FrameUniforms& U,
+               const SceneView& sc, const PathState& st, Counters* cnt, F4* sampleBuf)
 {
   if (U.workTotal == 0u) return 0; // an empty active rectangle (FLAG_MISS_RECT, the camera looks away): no pixel needs a path
   const uint32_t ldsNodes = sc.nodeCount, ldsTris = sc.triCount;
@@ -294,7 +322,7 @@ int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool texture
   const uint64_t needed = (chunks + (TRACE_BLOCK / 64u) - 1u) / (TRACE_BLOCK / 64u);
   if (blocks > needed) blocks = needed;
   if (blocks == 0u) blocks = 1u;
-  hipLaunchKernelGGL(k, dim3((uint32_t)blocks), dim3(TRACE_BLOCK), bytes, s, U, sc, st, cnt, sampleBuf, ldsNodes, ldsTris, chunk);
+  hipLaunchKernelGGL(k, dim3((uint32_t)blocks), dim3(TRACE_BLOCK), bytes, s, U, sc, st, cnt, sampleBuf, ldsNodes, ldsTris, chunk, walkCarry);
   return perCu;
 }
 

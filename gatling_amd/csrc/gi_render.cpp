@@ -432,6 +432,7 @@ struct Schedule {
   bool twoStreamOk = false;     // batches whose work fits the pool may run their shadow launches on the second stream (scheduleFrame)
   long twoStreamDelay = 0;      // test hook: 1 | 2 holds the main | the second stream back
   uint32_t dynRefill = 8u;      // k_trace_dyn refill threshold
+  uint32_t walkCarry = 0u;      // k_path: the closest-hit loop of a trip ends once at most this many lanes are still walking (0: never early)
   int32_t shadowOrderNow = -1;  // visiting order of the shadow walks; -1: not chosen yet -- alternate, and count (chooseShadowOrder)
 };
 struct Frame {
@@ -516,6 +517,9 @@ static Schedule scheduleFrame(Frame& f)
     if (U.activeCount < U.pixelCount) U.flags |= FLAG_MISS_RECT;
   }
   Schedule sch;
+  // Walk carry of k_path (gi_path.hip): lanes still walking when at most this many are left go on in the next trip's loop.  Counting builds run every loop
+  // to its end, so that the phase counters (lanes per phase and trip) and the step histogram describe whole walks.
+  sch.walkCarry = s->countTraversal ? 0u : (uint32_t)std::min(std::max(optionValue("walk_carry", WALK_CARRY_DEFAULT), 0L), 63L);
   sch.dynRefill = traceDynRefill(s);
   // (GATLING_OPTIONS=shadow_order=0|1 pins it)
   sch.shadowOrderNow = optionSet("shadow_order") ? (int32_t)optionValue("shadow_order", -1) : s->shadowOrder.load();
@@ -579,8 +583,8 @@ static int runFusedBatch(Frame& f, uint32_t batch)
   chunk = (uint32_t)std::min<uint64_t>(chunk, std::max<uint64_t>(64u, ((uint64_t)U.workTotal / (waves * 16u)) & ~63ull));
   f.tm.beginIteration(true); // one launch per batch: timed whatever the stride
   f.tm.timed(f.st, StageTimers::TRACE, [&] {
-    launchPath(f.st, (uint32_t)f.ctx.cuCount, s->classMask, s->classTextured != 0u, s->countTraversal, chunk, U, f.view, f.ps, D.dCounters.ptr,
-               D.sampleBuf.ptr);
+    launchPath(f.st, (uint32_t)f.ctx.cuCount, s->classMask, s->classTextured != 0u, s->countTraversal, chunk, f.sch.walkCarry, U, f.view, f.ps,
+               D.dCounters.ptr, D.sampleBuf.ptr);
   });
   f.iters++; f.tm.totalIters++; f.traceLaunches++;
   accumulateBatch(f, batch);
@@ -819,6 +823,13 @@ static void printPhaseStats(const GiCScene* s, const Counters& c)
               100.0 * (double)c.phaseCycles[k] / tot, (double)c.phaseLanes[k] / (double)c.phaseTrips);
     }
     fprintf(stderr, "[gatling_gi] k_path trips %llu, %.0f cycles per trip and wave\n", (unsigned long long)c.phaseTrips, tot / (double)c.phaseTrips);
+    unsigned long long steps = 0ull;
+    for (int k = 0; k < 8; k++) steps += c.walkStepTrips[k];
+    for (int k = 0; k < 8 && c.walkStepTrips[k]; k++) {
+      fprintf(stderr, "[gatling_gi] k_path walk step %d%s reached by %5.1f %% of the trips (%4.1f %% of all wave steps), %5.2f of 64 lanes walking\n", k,
+              k == 7 ? "+" : " ", 100.0 * (double)c.walkStepTrips[k] / (double)c.phaseTrips, 100.0 * (double)c.walkStepTrips[k] / (double)steps,
+              (double)c.walkStepLanes[k] / (double)c.walkStepTrips[k]);
+    }
   }
   if (c.dynStats[0]) { // k_trace_dyn's lane accounting (closest-hit launches)
     const unsigned long long* d = c.dynStats; const double st = (double)d[0];

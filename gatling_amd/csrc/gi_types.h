@@ -343,6 +343,9 @@ struct Counters {
   // k_path, counting builds only (GI_C_SCENE_OPTION_COUNT_TRAVERSAL): shader-clock cycles per phase summed over waves, lanes doing useful work per phase summed
   // over trips, trips -- [0] regeneration, [1] closest-hit traversal, [2] shading, [3] shadow ray + finish (GATLING_OPTIONS=phase_stats=1 prints them)
   unsigned long long phaseCycles[4], phaseLanes[4], phaseTrips;
+  // ... and how full the closest-hit loop of a trip is, step by step: [k] = lanes still walking when step k of a trip's loop begins, summed over the trips
+  // that reach step k, and the number of those trips ([7]: step 7 and every later one).  What the walk carry (gi_path.hip) can save is read off this table.
+  unsigned long long walkStepLanes[8], walkStepTrips[8];
   // k_trace_dyn's closest-hit launches, counting builds only: [0] steps (loop trips of all waves), lanes per step that [1] hold a ray, [2] walk (run the node
   // test), [3] wait for the triangle ring (drained walk, pairs pending); [4] triangle
   // batches, [5] pairs in them, [6] steps in which some lane was refilled, [7] lanes refilled
