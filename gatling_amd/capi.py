@@ -165,6 +165,7 @@ SYMBOLS = [
     ("giCDebugSceneVisibilityUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugSceneClassState", C.c_int, [_P, C.POINTER(C.c_uint32)]),
     ("giCDebugSceneVertexUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugRefitBvh", C.c_int, [_FP, _FP, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("giCDebugSceneRefitCheck", C.c_int, [_P, _U, C.POINTER(C.c_uint32)]),
+    ("giCDebugPathWalkStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugMissRect", C.c_int, [_FP, C.POINTER(GiCCameraDesc), C.POINTER(GiCRenderSettings), _U, _U, C.POINTER(C.c_uint32)]),
 ]
 
@@ -489,6 +490,15 @@ class Scene:
         if self.L.giCDebugSceneClassState(self.handle, c) != GI_C_OK:
             raise GiError("giCDebugSceneClassState failed")
         return {"classMask": int(c[0]), "classTextured": int(c[1]), "shadeClassMask": int(c[2]), "shadeClassTextured": int(c[3]), "hasCutouts": bool(c[4])}
+
+    def path_walk_stats(self) -> dict:
+        """giCDebugPathWalkStats: the fused kernel's trips and walk-step tables of the last render (OPTION_COUNT_TRAVERSAL; all zero otherwise).  stepTrips[k] /
+        stepLanes[k]: trips whose closest-hit loop reached step k (7: that and every later step) and the lanes walking then; fewLaneSteps: steps begun with
+        fewer than 8 lanes walking."""
+        c = (C.c_uint64 * 18)()
+        if self.L.giCDebugPathWalkStats(self.handle, c) != GI_C_OK:
+            raise GiError("giCDebugPathWalkStats failed")
+        return {"phaseTrips": int(c[0]), "stepTrips": [int(v) for v in c[1:9]], "stepLanes": [int(v) for v in c[9:17]], "fewLaneSteps": int(c[17])}
 
     def set_option(self, option: int, value: int):
         if self.L.giCSetSceneOption(self.handle, option, value) != GI_C_OK:

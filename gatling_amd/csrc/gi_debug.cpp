@@ -504,6 +504,17 @@ extern "C" int giCDebugSceneVertexUpdateCount(const GiCScene* scene, uint64_t* o
   return GI_C_OK;
 }
 
+// giCDebugPathWalkStats: how the closest-hit loops of the fused kernel's trips ran in the last render of a counting build (Counters::phaseTrips, walkStepTrips,
+// walkStepLanes, walkFewLaneSteps of the primary device; gi_path.hip).  All zero after a render that did not run k_path with counters.
+extern "C" int giCDebugPathWalkStats(const GiCScene* scene, uint64_t* out)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!s || !out) { setError("giCDebugPathWalkStats: bad arguments"); return GI_C_ERROR; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  for (int k = 0; k < 18; k++) out[k] = s->pathWalkStats[k];
+  return GI_C_OK;
+}
+
 // giCDebugSceneClassState: what picks a render's kernel variants (gi_build.cpp deriveSceneClasses), as the last scene sync left it.  Host only.
 extern "C" int giCDebugSceneClassState(const GiCScene* scene, uint32_t* out)
 {

@@ -21,7 +21,8 @@
 //                                  the host derives per render, gi_miss_rect.h) get no work items and no sample records; 0 = every pixel is enumerated
 //   walk_carry           8         fused frames without next-event estimation: the closest-hit loop of a k_path trip ends once at most this many lanes are
 //                                  still walking (and more entered); they go on walking in the next trip's loop (gi_path.hip).  0 = every loop runs until
-//                                  its last ray is done; 63 (tests) = carry whenever a lane has finished.  Counting builds run with 0
+//                                  its last ray is done; 63 (tests) = carry whenever a lane has finished.  Counting builds run with 0 unless the key is set
+//                                  explicitly: then it reaches them too (giCDebugPathWalkStats shows what it did)
 //   fused                1         LDS-resident scenes run the fused persistent kernel
 //   pool_slots           0         pin the path pool (slots); 0 = the memory plan decides
 //   sample_buffer_mb     0         pin the per-sample buffer (MiB); 0 = the memory plan decides

@@ -83,6 +83,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
 
   unsigned long long pc[4] = {0ull, 0ull, 0ull, 0ull}, pl[4] = {0ull, 0ull, 0ull, 0ull}, trips = 0ull, tPrev = COUNT ? __builtin_readcyclecounter() : 0ull;
   uint32_t whLanes[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}, whTrips[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}; // COUNT: lanes walking at step 0 .. 7+ of a trip's loop
+  uint32_t whFew = 0u; // COUNT: steps that began with fewer than 8 lanes walking
   auto phase = [&](int k,
       unsigned long long lanes) { if (COUNT) { const unsigned long long t = __builtin_readcyclecounter(); pc[k] += t - tPrev; tPrev = t; pl[k] += lanes; } };
   for (;;) {
@@ -174,7 +175,11 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
       const uint32_t stop = (uint32_t)__popcll(walking) > walkCarry ? walkCarry : 0u;
       uint32_t step = 0u;
       while ((uint32_t)__popcll(walking) > stop) {
-        if (COUNT) { whLanes[step] += (uint32_t)__popcll(walking); whTrips[step]++; step = step < 7u ? step + 1u : 7u; }
+        if (COUNT) {
+          const uint32_t n = (uint32_t)__popcll(walking);
+          whLanes[step] += n; whTrips[step]++; step = step < 7u ? step + 1u : 7u;
+          if (n < 8u) whFew++;
+        }
         if (wave_step<false, COUNT, PATH_STACK, false, true,
             CUTOUT>(R, tAlive, W, sc, s_nodes, ldsNodes, s_tris, ldsTris, s_stack, overflow, tc, rng)) tAlive = false;
         walking = __ballot(tAlive);
@@ -252,7 +257,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
   if (COUNT
       && lane == 0u) { for (int k = 0; k < 4; k++) { atomicAdd(&cnt->phaseCycles[k], pc[k]); atomicAdd(&cnt->phaseLanes[k], pl[k]);
       } atomicAdd(&cnt->phaseTrips, trips);
-      for (int k = 0; k < 8; k++) { atomicAdd(&cnt->walkStepLanes[k], (unsigned long long)whLanes[k]); atomicAdd(&cnt->walkStepTrips[k], (unsigned long long)whTrips[k]); } }
+      for (int k = 0; k < 8; k++) { atomicAdd(&cnt->walkStepLanes[k], (unsigned long long)whLanes[k]); atomicAdd(&cnt->walkStepTrips[k], (unsigned long long)whTrips[k]); }
+      atomicAdd(&cnt->walkFewLaneSteps, (unsigned long long)whFew); }
   // statistics: one atomic per wave and counter
   unsigned long long a = nSeg, b = nShadow, c = tc.nodes, d = tc.tris, e = tcs.nodes, f = tcs.tris;
   for (int off = 32; off > 0; off >>= 1) {

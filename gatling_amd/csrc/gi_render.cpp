@@ -518,8 +518,9 @@ static Schedule scheduleFrame(Frame& f)
   }
   Schedule sch;
   // Walk carry of k_path (gi_path.hip): lanes still walking when at most this many are left go on in the next trip's loop.  Counting builds run every loop
-  // to its end, so that the phase counters (lanes per phase and trip) and the step histogram describe whole walks.
-  sch.walkCarry = s->countTraversal ? 0u : (uint32_t)std::min(std::max(optionValue("walk_carry", WALK_CARRY_DEFAULT), 0L), 63L);
+  // to its end by default, so that the phase counters (lanes per phase and trip) and the step histogram describe whole walks; an explicit walk_carry key
+  // reaches them too (the counters are then how a test sees that lanes were carried: giCDebugPathWalkStats).
+  sch.walkCarry = s->countTraversal && !optionSet("walk_carry") ? 0u : (uint32_t)std::min(std::max(optionValue("walk_carry", WALK_CARRY_DEFAULT), 0L), 63L);
   sch.dynRefill = traceDynRefill(s);
   // (GATLING_OPTIONS=shadow_order=0|1 pins it)
   sch.shadowOrderNow = optionSet("shadow_order") ? (int32_t)optionValue("shadow_order", -1) : s->shadowOrder.load();
@@ -769,6 +770,8 @@ static void fillStats(const Frame& f, double tEnd)
 {
   GiCRenderStats& S = f.D.stats; const Counters& c = *f.D.hCounters;
   S.renderMs = tEnd - f.tStart; S.samples = (uint64_t)f.pixels * f.rs.spp; S.iterations = f.iters; S.traceLaunches = f.traceLaunches;
+  uint64_t* W = f.D.pathWalkStats; // giCDebugPathWalkStats (all zero unless a counting build's k_path ran in this render)
+  for (int k = 0; k < 18; k++) W[k] = 0u;
   if (f.served) { // nothing was launched but the fold: the counters on the device are still those of the call that traced the window
     S.fusedPath = S.batches = S.poolSlots = 0u;
     S.segments = S.shadowRays = S.nodesVisited = S.trisTested = S.shadowNodesVisited = S.shadowTrisTested = 0u;
@@ -777,6 +780,8 @@ static void fillStats(const Frame& f, double tEnd)
   S.fusedPath = f.plan.fused ? 1u : 0u;
   S.segments = c.segments + f.skippedSegments; S.shadowRays = c.shadowRays; S.nodesVisited = c.nodesVisited; S.trisTested = c.trisTested;
   S.shadowNodesVisited = c.shadowNodesVisited; S.shadowTrisTested = c.shadowTrisTested;
+  W[0] = c.phaseTrips; W[17] = c.walkFewLaneSteps;
+  for (int k = 0; k < 8; k++) { W[1 + k] = c.walkStepTrips[k]; W[9 + k] = c.walkStepLanes[k]; }
 }
 
 // giCDebugMissRect: the rectangle scheduleFrame would give a whole-frame render of this camera over these bounds (before the rules that switch it off: options,

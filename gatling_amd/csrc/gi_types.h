@@ -350,6 +350,9 @@ struct Counters {
   // test), [3] wait for the triangle ring (drained walk, pairs pending); [4] triangle
   // batches, [5] pairs in them, [6] steps in which some lane was refilled, [7] lanes refilled
   unsigned long long dynStats[8];
+  // k_path, counting builds only: steps of the closest-hit loops that began with fewer than 8 lanes walking -- the steps the walk carry exists to avoid (with
+  // K >= 8 only a loop that no more than K lanes entered has any).  Last, so that every other counter keeps its offset.
+  unsigned long long walkFewLaneSteps;
 };
 
 } // namespace gi

@@ -376,7 +376,7 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * the device build when one ran).  A caller compares giCGetApiVersion() with the GI_C_API_VERSION it was built with.
  * Still 8 with GI_C_SCENE_OPTION_SAMPLE_LOOKAHEAD and giCGetLookaheadStats: no struct grew and no entry point changed meaning -- both are additions that a caller
  * built against an earlier header never sees.  A caller probes for them: giCSetSceneOption answers GI_C_ERROR for an option the library does not know.
- * The same holds for GI_C_SCENE_OPTION_VISIBILITY_UPDATES, giCDebugSceneVisibilityUpdateCount, giCDebugSceneClassState and giCDebugMissRect, and for
+ * The same holds for GI_C_SCENE_OPTION_VISIBILITY_UPDATES, giCDebugSceneVisibilityUpdateCount, giCDebugSceneClassState, giCDebugMissRect and giCDebugPathWalkStats, and for
  * giCSetMeshVertices, GI_C_SCENE_OPTION_VERTEX_UPDATES, giCDebugSceneVertexUpdateCount, giCDebugRefitBvh and giCDebugSceneRefitCheck. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
@@ -616,6 +616,11 @@ int giCDebugSceneVertexUpdateCount(const GiCScene* scene, uint64_t* outCount);
  * use (one bit each), [1] those with a textured material, [2] and [3] the same per shade class, [4] 1 when some visible triangle has cutout opacity.  Host
  * only: no device work. */
 int giCDebugSceneClassState(const GiCScene* scene, uint32_t* out /* 5 */);
+/* [ext] the fused path kernel's walk counters of the scene's last render, for renders with GI_C_SCENE_OPTION_COUNT_TRAVERSAL (all zero otherwise): out[0] trips
+ * of all waves, [1 + k] the trips whose closest-hit loop reached step k (k = 7: every step from the eighth on), [9 + k] the lanes walking when those steps
+ * began, [17] the steps that began with fewer than 8 lanes walking.  With $GATLING_OPTIONS walk_carry=K set explicitly a counting build carries walks as other
+ * builds do, and these numbers are how a test sees it: [17] falls and [0] rises against K = 0, while the image and the per-ray counters stay put. */
+int giCDebugPathWalkStats(const GiCScene* scene, uint64_t* out /* 18 */);
 /* [ext] the miss rectangle of a whole-frame render: out = x0, y0, x1, y1, image columns [x0, x1) and rows [y0, y1) outside which every camera ray the settings'
  * sampling can produce for a pixel misses `bounds` (min xyz, max xyz) -- the fused path kernel gives such pixels no work.  The whole frame when no pixel can be
  * ruled out (depth of field with a lens radius, the camera inside or beside the bounds); 0, 0, 0, 0 when every pixel is (the camera looks away).  Host only: no

@@ -729,6 +729,8 @@ def test_three_pipelines_for_lds_resident_scenes_agree(gi, orc):
     from gatling_amd.capi import OPTION_FUSED_PATH
     cases = [(cornell_box(), RenderSettings(spp=6, max_bounces=8), 96, 54), (cornell_box(MAT_DIFFUSE), RenderSettings(spp=3, max_bounces=4), 7, 5),
              (cornell_box(), RenderSettings(spp=1, max_bounces=3, rr_bounce_offset=0), 33, 1)]
+    from path_matrix_cases import scene
+    cases.append((scene("B"), RenderSettings(spp=3, max_bounces=6), 64, 36))  # mixed classes, a stochastic cutout, textured colour and opacity: the general variant
     for desc, rs, w, h in cases:
         ref, cnt = orc.render(desc, rs, w, h, threads=4)
         for mode in (0, 2, 1):
