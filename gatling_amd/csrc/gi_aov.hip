@@ -56,13 +56,7 @@ __device__ inline V3 bsdf_albedo(const MaterialRec* m, const ShState& st, V3 k1)
 template <uint32_t STACK, bool OVERFLOW, bool PACKED>
 __global__ __launch_bounds__(TRACE_BLOCK) void k_aov(FrameUniforms U, SceneView sc, AovTargets A, uint32_t ldsNodes, uint32_t ldsTris)
 {
-  extern __shared__ uint4 s_dyn[];
-  uint2 (*s_stack)[TRACE_BLOCK] = reinterpret_cast<uint2 (*)[TRACE_BLOCK]>(s_dyn);
-  uint4* s_nodes = s_dyn + (STACK * TRACE_BLOCK * sizeof(uint2)) / sizeof(uint4);
-  uint4* s_tris = s_nodes + ldsNodes * 5u;
-  for (uint32_t i = threadIdx.x; i < ldsNodes * 5u; i += TRACE_BLOCK) s_nodes[i] = reinterpret_cast<const uint4*>(sc.nodes)[i];
-  for (uint32_t i = threadIdx.x; i < ldsTris * 3u; i += TRACE_BLOCK) s_tris[i] = reinterpret_cast<const uint4*>(sc.tris)[(i / 3u) * 4u + (i % 3u)];
-  __syncthreads();
+  const StagedScene S = stage_scene<STACK>(sc, ldsNodes, ldsTris);
   const uint32_t p = blockIdx.x * TRACE_BLOCK + threadIdx.x;
   if (p >= U.pixelCount) return;
   const uint32_t pixelIndex = tile_to_image_pixel(U, p);
@@ -88,8 +82,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_aov(FrameUniforms U, SceneView 
     make_camera_ray(U, pixelIndex, U.sampleOffset + s, origin, dir, tMin, tMax, rng);
     float t, u, v; uint32_t tri;
     uint32_t matWord;
-    if (!traverse<false, false, STACK, OVERFLOW, false,
-        true>(sc, s_nodes, ldsNodes, s_tris, ldsTris, s_stack, origin, dir, tMin, tMax, t, u, v, tri, matWord, tc, rng)) continue;
+    if (!traverse<false, false, STACK, OVERFLOW, STAGED_SOME, true>(sc, S, origin, dir, tMin, tMax, t, u, v, tri, matWord, tc, rng)) continue;
     ShState ss;
     setup_shading_state<PACKED>(sc, tri, u, v, dir, ss);
     const uint4* tp = reinterpret_cast<const uint4*>(sc.tris) + (size_t)tri * 4u;
@@ -149,14 +142,14 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_aov(FrameUniforms U, SceneView 
 void launchAov(hipStream_t s, const FrameUniforms& U, const SceneView& sc, const AovTargets& A)
 {
   uint32_t ln, lt, bytes; traceLdsLayout(sc, ln, lt, bytes);
-  bytes = (sc.bvhDepth <= 8u ? 8u : 16u) * TRACE_BLOCK * (uint32_t)sizeof(uint2) + ln * 80u + lt * 48u; // k_aov has no 4-entry variant
+  bytes = traceLdsBytes(sc.bvhDepth <= 8u ? 8u : 16u, ln, lt); // k_aov has no 4-entry variant
   const uint32_t blocks = (U.pixelCount + TRACE_BLOCK - 1u) / TRACE_BLOCK;
-#define GI_LAUNCH_AOV(P) do { \
-  if (sc.bvhDepth <= 8u) hipLaunchKernelGGL((k_aov<8, false, P>), dim3(blocks), dim3(TRACE_BLOCK), bytes, s, U, sc, A, ln, lt); \
-  else if (sc.bvhDepth <= 16u) hipLaunchKernelGGL((k_aov<16, false, P>), dim3(blocks), dim3(TRACE_BLOCK), bytes, s, U, sc, A, ln, lt); \
-  else hipLaunchKernelGGL((k_aov<16, true, P>), dim3(blocks), dim3(TRACE_BLOCK), bytes, s, U, sc, A, ln, lt); } while (0)
-  if (sc.shadePacked) GI_LAUNCH_AOV(true); else GI_LAUNCH_AOV(false);
-#undef GI_LAUNCH_AOV
+  dispatchBools([&](auto packedC) {
+    constexpr bool PACKED = decltype(packedC)::value;
+    if (sc.bvhDepth <= 8u) hipLaunchKernelGGL((k_aov<8, false, PACKED>), dim3(blocks), dim3(TRACE_BLOCK), bytes, s, U, sc, A, ln, lt);
+    else if (sc.bvhDepth <= 16u) hipLaunchKernelGGL((k_aov<16, false, PACKED>), dim3(blocks), dim3(TRACE_BLOCK), bytes, s, U, sc, A, ln, lt);
+    else hipLaunchKernelGGL((k_aov<16, true, PACKED>), dim3(blocks), dim3(TRACE_BLOCK), bytes, s, U, sc, A, ln, lt);
+  }, sc.shadePacked != 0u);
 }
 
 } // namespace gi

@@ -2,11 +2,23 @@
 // gi_trace.hip, gi_shade.hip, gi_aov.hip, gi_patch.hip, gi_refit.hip) and of the fused one (gi_path.hip).
 #pragma once
 
+#include <type_traits>
 #include <hip/hip_runtime.h>
 
 #include "gi_types.h"
 
 namespace gi {
+
+// Launch selection: calls f with one std::bool_constant per bool, so that a generic lambda can name the kernel instantiation the run-time values pick
+// (constexpr bool X = decltype(xC)::value).  Every combination the lambda's body can be called with is instantiated.
+template <class F>
+auto dispatchBools(F&& f) { return f(); }
+template <class F, class... Bools>
+auto dispatchBools(F&& f, bool b, Bools... rest)
+{
+  return b ? dispatchBools([&](auto... cs) { return f(std::true_type{}, cs...); }, rest...)
+           : dispatchBools([&](auto... cs) { return f(std::false_type{}, cs...); }, rest...);
+}
 
 void launchInit(hipStream_t s, const PathState& st, const QueueSet& qs, Counters* cnt, uint32_t n, bool resetStats);
 // `par` = iteration parity: k_raygen reads REGEN[par] and appends TRACE[par]; k_trace reads TRACE[par] and appends HIT and
@@ -20,8 +32,12 @@ bool traceBlockSync(const SceneView& sc);
 // a tree of this many nodes and triangles is staged whole in LDS (gi_traversal.h LDS_NODES / LDS_TRIS); beyond it the host packs shading records, sizes a
 // larger path pool and may build the two-level layout
 bool sceneFitsLds(size_t nodeCount, size_t triCount);
-// LDS bytes one k_trace block needs for this scene (stack + staged nodes + staged triangles)
+// dynamic LDS bytes of a traversal block: `stackEntries` stack entries per lane + staged nodes + staged triangles (gi_traversal.h StagedScene)
+uint32_t traceLdsBytes(uint32_t stackEntries, uint32_t ldsNodes, uint32_t ldsTris);
+// resident blocks per CU that the 160 KiB of LDS allow a kernel with this much dynamic and static LDS (256 bytes per block of allocation slack)
+uint32_t blocksPerCuByLds(uint32_t dynamicBytes, uint32_t staticBytes);
 uint32_t traceStaticLdsBytes(); // static LDS of the traversal kernels on top of traceLdsLayout's dynamic bytes
+// what one k_trace block stages of this scene and the dynamic LDS bytes it needs for it
 void traceLdsLayout(const SceneView& sc, uint32_t& ldsNodes, uint32_t& ldsTris, uint32_t& bytes);
 void launchTrace(hipStream_t s, uint32_t blocks, bool anyHit, bool count, const SceneView& sc, const PathState& st, const QueueSet& qs, Counters* cnt,
                  uint32_t qIn, uint32_t qMiss, uint32_t dynRefill, uint32_t routeBlocks, const FrameUniforms& U, F4* sampleBuf);

@@ -44,20 +44,13 @@ constexpr uint32_t PATH_STACK_MAX = 8; // LDS traversal-stack entries per lane: 
 constexpr int PATH_WAVES = 4; // resident waves per SIMD the register allocation aims for (114 VGPRs without a hint; 3 cost 11 %, 5 spill 26 registers: r03)
 template <uint32_t KLASS, bool TEXTURED, bool NEE, bool CUTOUT, bool COUNT, uint32_t PATH_STACK>
 __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PATH_WAVES, 8))) void k_path(FrameUniforms U, SceneView sc, PathState st,
-    Counters* cnt, F4* __restrict__ sampleBuf,
-                                                      uint32_t ldsNodes, uint32_t ldsTris, uint32_t chunk, uint32_t walkCarry)
+    Counters* cnt, F4* __restrict__ sampleBuf, uint32_t ldsNodes, uint32_t ldsTris, uint32_t chunk, uint32_t walkCarry)
 {
   // Walk carry (NEE off): see the closest-hit loop.  The NEE variants' shadow walk reuses R and WaveTri::best[lane], so they never carry.
   constexpr bool CARRY = !NEE;
-  extern __shared__ uint4 s_dyn[];
-  uint2 (*s_stack)[TRACE_BLOCK] = reinterpret_cast<uint2 (*)[TRACE_BLOCK]>(s_dyn);
-  uint4* s_nodes = s_dyn + (PATH_STACK * TRACE_BLOCK * sizeof(uint2)) / sizeof(uint4);
-  uint4* s_tris = s_nodes + ldsNodes * 5u;
+  const StagedScene S = stage_scene<PATH_STACK>(sc, ldsNodes, ldsTris); // the only barrier: from here on the waves of a block are independent
   __shared__ WaveTri s_wave[TRACE_BLOCK / 64];
   WaveTri& W = s_wave[threadIdx.x >> 6];
-  for (uint32_t i = threadIdx.x; i < ldsNodes * 5u; i += TRACE_BLOCK) s_nodes[i] = reinterpret_cast<const uint4*>(sc.nodes)[i];
-  for (uint32_t i = threadIdx.x; i < ldsTris * 3u; i += TRACE_BLOCK) s_tris[i] = reinterpret_cast<const uint4*>(sc.tris)[(i / 3u) * 4u + (i % 3u)];
-  __syncthreads(); // the only barrier: from here on the waves of a block are independent
 
   const uint32_t lane = __lane_id();
   const unsigned long long below = (1ull << lane) - 1ull;
@@ -180,18 +173,16 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
           whLanes[step] += n; whTrips[step]++; step = step < 7u ? step + 1u : 7u;
           if (n < 8u) whFew++;
         }
-        if (wave_step<false, COUNT, PATH_STACK, false, true,
-            CUTOUT>(R, tAlive, W, sc, s_nodes, ldsNodes, s_tris, ldsTris, s_stack, overflow, tc, rng)) tAlive = false;
+        if (wave_step<false, COUNT, PATH_STACK, false, STAGED_ALL, CUTOUT>(R, tAlive, W, sc, S, overflow, tc, rng)) tAlive = false;
         walking = __ballot(tAlive);
       }
     } else {
       while (__ballot(tAlive)) {
-        if (wave_step<false, COUNT, PATH_STACK, false, true,
-            CUTOUT>(R, tAlive, W, sc, s_nodes, ldsNodes, s_tris, ldsTris, s_stack, overflow, tc, rng)) tAlive = false;
+        if (wave_step<false, COUNT, PATH_STACK, false, STAGED_ALL, CUTOUT>(R, tAlive, W, sc, S, overflow, tc, rng)) tAlive = false;
       }
     }
     const bool walked = CARRY ? alive && !tAlive : alive; // this trip ended the lane's segment
-    bool ended = false, missed = false;
+    bool ended = false;
     ShadeIO io; io.shadow = false; io.shadowFirst = false; io.cont = false;
     phase(1, (unsigned long long)__popcll(__ballot(walked)));
     if (walked) {
@@ -209,10 +200,9 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
         rad = rad + thr * v3(U.background);
         if (st.neeKey && (bitfield & 0x00000fffu) == 0u) nee_aov_record_px(st, rec % U.pixelCount, rec / U.pixelCount, false);
         bitfield++;
-        ended = true; missed = true;
+        ended = true;
       }
     }
-    (void)missed;
     phase(2, (unsigned long long)__popcll(__ballot(walked && R.found)));
 
     // --- shadow ray of this bounce (rp_main.rgen:397-429): origin = next ray origin, tMin 0.01, tMax = distance to the light sample
@@ -223,8 +213,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
         wave_ray_begin(W, R.tBest);
         const bool traced = sAlive;
         while (__ballot(sAlive)) {
-          if (wave_step<true, COUNT, PATH_STACK, false, true,
-              CUTOUT>(R, sAlive, W, sc, s_nodes, ldsNodes, s_tris, ldsTris, s_stack, overflow, tcs, io.rngShadow)) sAlive = false;
+          if (wave_step<true, COUNT, PATH_STACK, false, STAGED_ALL, CUTOUT>(R, sAlive, W, sc, S, overflow, tcs, io.rngShadow)) sAlive = false;
         }
         if (traced) {
           nShadow++;
@@ -291,14 +280,16 @@ using PathKernel = void (*)(FrameUniforms, SceneView, PathState, Counters*, F4*,
 template <uint32_t STACK>
 static PathKernel pickPathKernel(uint32_t classMask, bool textured, bool nee, bool cutout, bool count)
 {
-  const bool single = classMask == 1u || classMask == 2u || classMask == 4u;
-  if (single && !textured && !cutout && !count) {
-    if (classMask == 1u) return nee ? k_path<0u, false, true, false, false, STACK> : k_path<0u, false, false, false, false, STACK>;
-    if (classMask == 2u) return nee ? k_path<1u, false, true, false, false, STACK> : k_path<1u, false, false, false, false, STACK>;
-    return nee ? k_path<2u, false, true, false, false, STACK> : k_path<2u, false, false, false, false, STACK>;
-  }
-  if (count) return nee ? k_path<KLASS_DYNAMIC, true, true, true, true, STACK> : k_path<KLASS_DYNAMIC, true, false, true, true, STACK>;
-  return nee ? k_path<KLASS_DYNAMIC, true, true, true, false, STACK> : k_path<KLASS_DYNAMIC, true, false, true, false, STACK>;
+  const bool hot = (classMask == 1u || classMask == 2u || classMask == 4u) && !textured && !cutout && !count;
+  return dispatchBools([&](auto neeC) -> PathKernel {
+    constexpr bool NEE = decltype(neeC)::value;
+    if (hot) {
+      if (classMask == 1u) return k_path<0u, false, NEE, false, false, STACK>;
+      if (classMask == 2u) return k_path<1u, false, NEE, false, false, STACK>;
+      return k_path<2u, false, NEE, false, false, STACK>;
+    }
+    return dispatchBools([](auto countC) -> PathKernel { return k_path<KLASS_DYNAMIC, true, NEE, true, decltype(countC)::value, STACK>; }, count);
+  }, nee);
 }
 
 int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool textured, bool count, uint32_t chunk, uint32_t walkCarry, const FrameUniforms& U,
@@ -307,7 +298,7 @@ int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool texture
   if (U.workTotal == 0u) return 0; // an empty active rectangle (FLAG_MISS_RECT, the camera looks away): no pixel needs a path
   const uint32_t ldsNodes = sc.nodeCount, ldsTris = sc.triCount;
   const uint32_t stack = sc.bvhDepth <= 4u ? 4u : 8u;
-  const uint32_t bytes = stack * TRACE_BLOCK * (uint32_t)sizeof(uint2) + ldsNodes * 80u + ldsTris * 48u;
+  const uint32_t bytes = traceLdsBytes(stack, ldsNodes, ldsTris);
   const bool neeOn = (U.flags & FLAG_NEE) != 0u;
   PathKernel k = stack == 4u
       ? pickPathKernel<4u>(classMask, textured, neeOn, sc.hasCutouts != 0u, count) : pickPathKernel<8u>(classMask, textured, neeOn, sc.hasCutouts != 0u, count);
@@ -317,7 +308,7 @@ int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool texture
   hipFuncAttributes fa{};
   if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k)) == hipSuccess && fa.numRegs > 0) {
     const uint32_t regs = ((uint32_t)fa.numRegs + 7u) & ~7u, byRegs = 512u / regs;
-    const uint32_t byLds = (160u * 1024u) / (bytes + (uint32_t)fa.sharedSizeBytes + 256u);
+    const uint32_t byLds = blocksPerCuByLds(bytes, (uint32_t)fa.sharedSizeBytes);
     perCu = (int)(byRegs < byLds ? byRegs : byLds);
     if (perCu > 8) perCu = 8;
     if (perCu < 1) perCu = 1;

@@ -277,7 +277,7 @@ static uint32_t traceBlocksPerCu(const SceneView& v)
 {
   if (!traceBlockSync(v)) return 8u; // k_trace_dyn is persistent per wave: blocks beyond what is resident find the cursor exhausted
   uint32_t ln, lt, ldsBytes; traceLdsLayout(v, ln, lt, ldsBytes);
-  return std::max(1u, std::min<uint32_t>(6u, (160u * 1024u) / (ldsBytes + traceStaticLdsBytes() + 256u)));
+  return std::max(1u, std::min<uint32_t>(6u, blocksPerCuByLds(ldsBytes, traceStaticLdsBytes())));
 }
 static void sizeGrids(PathPlan& p, const PlanInputs& in)
 {

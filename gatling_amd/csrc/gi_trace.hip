@@ -1,7 +1,9 @@
-// gi_trace.hip -- the traversal kernels of the wavefront path tracer (gfx950): k_trace (block-synchronous, scenes staged whole in LDS), k_trace_dyn / k_trace_dyn2
-// (persistent waves with dynamic ray fetch for scenes that do not fit; results routed by gi_kernels.hip k_route).  They replace the two traceRayEXT calls of
+// gi_trace.hip -- the traversal kernels of the wavefront path tracer (gfx950): k_trace (one ray per lane and trip, scenes staged whole in LDS; its step is
+// gi_traversal.h wave_step), k_trace_dyn / k_trace_dyn2 (persistent waves with dynamic ray fetch for scenes that do not fit; trace_dyn_body below composes their
+// step from gi_traversal.h's node test, ring appends and triangle batch, or calls wave_step2; results routed by gi_kernels.hip k_route), and the launch
+// selection and LDS sizing all traversal launches share.  The kernels replace the two traceRayEXT calls of
 // the reference's ray generation shader (/root/reference/src/gi/shaders/rp_main.rgen:381-393, 412-424: closest hit and shadow test; hardware BVH traversal
-// there).  The walk itself is gi_traversal.h.  Built with -ffp-contract=off (arithmetic contract, gi_device_math.h); the box tests use explicit fmaf: they are
+// there).  Built with -ffp-contract=off (arithmetic contract, gi_device_math.h); the box tests use explicit fmaf: they are
 // conservative filters and never influence results.
 
 #include <type_traits>
@@ -17,16 +19,31 @@
 
 namespace gi {
 
+// End of a shadow ray (rp_main.rgen:425-435): an unoccluded one adds its light sample to the path's radiance
+static __device__ __forceinline__ void shadow_ray_finish(const PathState& st, const QueueSet& qs, uint32_t qIn, uint32_t rec, uint32_t slot, bool found)
+{
+  F4 nc = F4{0.0f, 0.0f, 0.0f, 0.0f}; // (neeContrib, 1 = emitted at bounce 0)
+  if (!found || st.neeKey) nc = ld4(&qs.c[qIn][rec]);
+  if (!found) {
+    Slot* S = &st.slots[slot];
+    F4 rr = ld4(&S->rad);
+    st4(&S->rad, rr.x + nc.x, rr.y + nc.y, rr.z + nc.z, rr.w);
+  }
+  if (st.neeKey && nc.w != 0.0f) nee_aov_record(st, slot, found);
+}
+// measurement builds only: one atomic pair per wave
+template <bool ANYHIT>
+static __device__ __forceinline__ void trace_counters_flush(Counters* cnt, const TraceCounters& tc)
+{
+  unsigned long long a = tc.nodes, b = tc.tris;
+  for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off); b += __shfl_down(b, off); }
+  if (__lane_id() == 0) { atomicAdd(ANYHIT ? &cnt->shadowNodesVisited : &cnt->nodesVisited, a); atomicAdd(ANYHIT ? &cnt->shadowTrisTested : &cnt->trisTested, b); }
+}
+
 template <bool ANYHIT, bool COUNT, uint32_t STACK, bool CUTOUT, bool DOME>
 __global__ __launch_bounds__(TRACE_BLOCK) void k_trace(SceneView sc, PathState st, QueueSet qs, Counters* cnt, uint32_t qIn, uint32_t qMiss, uint32_t ldsNodes,
-    uint32_t ldsTris,
-                                                       FrameUniforms U, F4* __restrict__ sampleBuf)
+                                                       uint32_t ldsTris, FrameUniforms U, F4* __restrict__ sampleBuf)
 {
-  // dynamic LDS, sized by the launch to what this scene actually stages: [stack | nodes | triangles]
-  extern __shared__ uint4 s_dyn[];
-  uint2 (*s_stack)[TRACE_BLOCK] = reinterpret_cast<uint2 (*)[TRACE_BLOCK]>(s_dyn);
-  uint4* s_nodes = s_dyn + (STACK * TRACE_BLOCK * sizeof(uint2)) / sizeof(uint4);
-  uint4* s_tris = s_nodes + ldsNodes * 5u;
   __shared__ AppendScratch<1 + MAT_CLASS_COUNT> sh;
   __shared__ WaveTri s_wave[TRACE_BLOCK / 64];
   WaveTri& W = s_wave[threadIdx.x >> 6];
@@ -34,9 +51,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace(SceneView sc, PathState s
   const uint32_t n = rd.pre[NSHARD];
   if (blockIdx.x == 0 && threadIdx.x == 0) { if (ANYHIT) cnt->shadowRays += n; else cnt->segments += n; } // single writer per launch
   if (blockIdx.x * TRACE_BLOCK >= n) return; // whole block idle (uniform)
-  for (uint32_t i = threadIdx.x; i < ldsNodes * 5u; i += TRACE_BLOCK) s_nodes[i] = reinterpret_cast<const uint4*>(sc.nodes)[i];
-  for (uint32_t i = threadIdx.x; i < ldsTris * 3u; i += TRACE_BLOCK) s_tris[i] = reinterpret_cast<const uint4*>(sc.tris)[(i / 3u) * 4u + (i % 3u)];
-  __syncthreads();
+  // dynamic LDS, sized by the launch to what this scene actually stages
+  const StagedScene S = stage_scene<STACK>(sc, ldsNodes, ldsTris);
 
   TraceCounters tc{0u, 0u};
   RayTrav R; trav_init(R, v3(0.0f, 0.0f, 0.0f), v3(0.0f, 0.0f, 1.0f), 0.0f, 0.0f);
@@ -63,23 +79,13 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace(SceneView sc, PathState s
       alive = true;
     }
     while (__ballot(alive)) {
-      if (wave_step<ANYHIT, COUNT, STACK, false, true,
-          CUTOUT>(R, alive, W, sc, s_nodes, ldsNodes, s_tris, ldsTris, s_stack, overflow, tc, rng)) alive = false;
+      if (wave_step<ANYHIT, COUNT, STACK, false, STAGED_ALL, CUTOUT>(R, alive, W, sc, S, overflow, tc, rng)) alive = false;
     }
     if (i < n) {
       wave_ray_end(W, R);
       if (!ANYHIT) {
         hit = R.found; miss = !hit; t = R.tBest; u = R.bestU; v = R.bestV; tri = R.bestTri; mat = R.bestMat;
-      } else {
-        F4 nc = F4{0.0f, 0.0f, 0.0f, 0.0f}; // (neeContrib, 1 = emitted at bounce 0)
-        if (!R.found || st.neeKey) nc = ld4(&qs.c[qIn][r]);
-        if (!R.found) {
-          Slot* S = &st.slots[slot];
-          F4 rr = ld4(&S->rad);
-          st4(&S->rad, rr.x + nc.x, rr.y + nc.y, rr.z + nc.z, rr.w);
-        }
-        if (st.neeKey && nc.w != 0.0f) nee_aov_record(st, slot, R.found);
-      }
+      } else shadow_ray_finish(st, qs, qIn, r, slot, R.found);
     }
     if (!ANYHIT) {
       // sort by outcome and material class: hits go to their class's shade queue as (slot, hit, direction) records, misses
@@ -116,12 +122,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace(SceneView sc, PathState s
       }
     }
   }
-  if (COUNT) { // measurement builds only: one atomic pair per wave
-    unsigned long long a = tc.nodes, b = tc.tris;
-    for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off); b += __shfl_down(b, off); }
-    if (__lane_id() == 0) { atomicAdd(ANYHIT ? &cnt->shadowNodesVisited : &cnt->nodesVisited, a);
-        atomicAdd(ANYHIT ? &cnt->shadowTrisTested : &cnt->trisTested, b); }
-  }
+  if (COUNT) trace_counters_flush<ANYHIT>(cnt, tc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -164,8 +165,7 @@ __device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin
 // launches 3 - 6 % of their traversal time when it is compiled into their loop (r05g).
 template <bool ANYHIT, bool COUNT, uint32_t STACK, bool OVERFLOW, bool CUTOUT, bool TWO, bool HELP, bool SLOT = false>
 __device__ __forceinline__ void trace_dyn_body(const SceneView& sc, const PathState& st, const QueueSet& qs, Counters* cnt, uint32_t qIn, uint32_t refill,
-    WaveTri& W,
-                                               uint32_t shardCount, uint32_t claim)
+                                               WaveTri& W, uint32_t shardCount, uint32_t claim)
 {
   // Shadow walks end at their first hit, so near-to-far order is not needed for the
   // result -- and which order finds an occluder sooner depends on the scene (C3's soup:
@@ -174,8 +174,7 @@ __device__ __forceinline__ void trace_dyn_body(const SceneView& sc, const PathSt
   // in slot order) and the kernel counts the walks' node visits for it to choose by.
   constexpr bool slotOrder = ANYHIT && !TWO && SLOT;
   uint32_t walkSteps = 0u;
-  extern __shared__ uint4 s_dyn[];
-  uint2 (*s_stack)[TRACE_BLOCK] = reinterpret_cast<uint2 (*)[TRACE_BLOCK]>(s_dyn);
+  const StagedScene S = stage_stack(); // nothing of the scene is staged
   const uint32_t lane = __lane_id();
   const uint32_t cap = qs.cap;
   PaddedCounter* cursors = cnt->cursor[ANYHIT ? 1 : 0];
@@ -284,7 +283,7 @@ __device__ __forceinline__ void trace_dyn_body(const SceneView& sc, const PathSt
         if (donor && dRank < nPairs) base++;
         if (thief) {
           R.o = o; R.d = d; R.idx = idx; R.idy = idy; R.idz = idz; R.tMin = tMin; R.tBest = tBest; R.octinv = octinv; rng = drng;
-          R.G = s_stack[dBase][(threadIdx.x & ~63u) + (uint32_t)from]; // (bottom entries live in LDS for every STACK / OVERFLOW variant)
+          R.G = S.stack[dBase][(threadIdx.x & ~63u) + (uint32_t)from]; // (bottom entries live in LDS for every STACK / OVERFLOW variant)
           R.sp = 0u; base = 0u; keyReg = dKey; helper = true;
           wt_helpers_add(W, key, 1u);
           alive = true; draining = false; lastEnd = ringHead;
@@ -292,7 +291,7 @@ __device__ __forceinline__ void trace_dyn_body(const SceneView& sc, const PathSt
       }
     }
     bool done = false;
-    if constexpr (TWO) done = wave_step2<ANYHIT, COUNT, CUTOUT>(R, alive, W, sc, s_stack, tc, rng);
+    if constexpr (TWO) done = wave_step2<ANYHIT, COUNT, CUTOUT>(R, alive, W, sc, S.stack, tc, rng);
     else {
       // The triangle ring is carried from step to step: a node step yields fewer pairs than a batch holds (C3: 23 per step, C4: 18), so flushing at the end of
       // every step ran the ~110-instruction batch at a third of its lanes.  A batch runs when 64 pairs are pending; the rest waits.  A ray whose walk has ended
@@ -300,13 +299,18 @@ __device__ __forceinline__ void trace_dyn_body(const SceneView& sc, const PathSt
       // the node phases until the ring has moved past its last pair (the ring is FIFO: `head` has reached `lastEnd`).  The ring is flushed below 64 pairs when
       // DYN_FLUSH_AT or more lanes are blocked like that, or when few lanes walk.  Results do not depend on any of this (the hit key under atomicMin does not
       // depend on when a pair is tested); only the culling distance a walking ray sees may lag by a step or two.
-      auto batch = [&](uint32_t n) { wave_tri_batch<COUNT, false, CUTOUT, true>(W, ringHead, n, R, rng, sc, nullptr, 0u, tc); ringHead += n;
-          if (COUNT) { ds[4]++; ds[5] += n; } };
+      auto batch = [&](uint32_t n) {
+        wave_tri_batch<COUNT, STAGED_NONE, CUTOUT, true>(W, ringHead, n, R, rng, sc, StagedScene{}, tc); // (STAGED_NONE: the batch reads no staged triangle)
+        ringHead += n;
+        if (COUNT) { ds[4]++; ds[5] += n; }
+      };
       const bool walking = alive && !draining;
-      if (COUNT) { ds[0]++; ds[1] += (unsigned long long)__popcll(__ballot(alive)); ds[2] += (unsigned long long)__popcll(__ballot(walking));
-          ds[3] += (unsigned long long)__popcll(__ballot(alive && draining)); }
+      if (COUNT) {
+        ds[0]++; ds[1] += (unsigned long long)__popcll(__ballot(alive)); ds[2] += (unsigned long long)__popcll(__ballot(walking));
+        ds[3] += (unsigned long long)__popcll(__ballot(alive && draining));
+      }
       uint2 Gt = make_uint2(0u, 0u);
-      if (walking) { Gt = trav_node<COUNT, STACK, OVERFLOW, false, !slotOrder>(R, sc, nullptr, 0u, s_stack, overflow, tc); if (ANYHIT && !TWO) walkSteps++; }
+      if (walking) { Gt = trav_node<COUNT, STACK, OVERFLOW, STAGED_NONE, !slotOrder>(R, sc, S, overflow, tc); if (ANYHIT && !TWO) walkSteps++; }
       // positions from a wave prefix sum over the per-lane pair counts, then every lane writes its own pairs
       const uint32_t cntL = (uint32_t)__popc(Gt.y);
       const uint32_t scan = wave_scan_inclusive(cntL);
@@ -340,7 +344,7 @@ __device__ __forceinline__ void trace_dyn_body(const SceneView& sc, const PathSt
         }
       }
       // the walk moves on before the ring is looked at (a closest-hit walk's pop does not depend on tBest)
-      if (!ANYHIT && walking && trav_pop<STACK, OVERFLOW>(R, s_stack, overflow, HELP ? base : 0u)) draining = true;
+      if (!ANYHIT && walking && trav_pop<STACK, OVERFLOW>(R, S.stack, overflow, HELP ? base : 0u)) draining = true;
       if (ringTail != ringHead) {
         const unsigned long long blocked = __ballot(alive && draining && (int)(ringHead - lastEnd) < 0);
         // (a wave with few walks left -- the tail of a launch, or all of a thin launch -- fills the ring slowly: waiting for 64 pairs there only delays the
@@ -352,7 +356,7 @@ __device__ __forceinline__ void trace_dyn_body(const SceneView& sc, const PathSt
       if (alive) {
         if (!ANYHIT) R.tBest = u2f(wt_best_t(W, key));
         // a shadow walk ends at the first hit
-        else if (!draining && (wt_best_id(W, key) != 0u || trav_pop<STACK, OVERFLOW>(R, s_stack, overflow, HELP ? base : 0u))) draining = true;
+        else if (!draining && (wt_best_id(W, key) != 0u || trav_pop<STACK, OVERFLOW>(R, S.stack, overflow, HELP ? base : 0u))) draining = true;
         done = draining && (int)(ringHead - lastEnd) >= 0;
       }
     }
@@ -372,15 +376,7 @@ __device__ __forceinline__ void trace_dyn_body(const SceneView& sc, const PathSt
             if (sc.mediumStackSize && word == MISS) { V3 wo = R.o; if constexpr (TWO) wo = R.wo; reinterpret_cast<float*>(&qs.b[qIn][rec])[3] = wo.z; }
           } else {
             const bool found = wt_best_id(W, lane) != 0u;
-            const uint32_t slot = qs.slot[qIn][rec];
-            F4 nc = F4{0.0f, 0.0f, 0.0f, 0.0f}; // (neeContrib, 1 = emitted at bounce 0)
-            if (!found || st.neeKey) nc = ld4(&qs.c[qIn][rec]);
-            if (!found) {
-              Slot* S = &st.slots[slot];
-              F4 rr = ld4(&S->rad);
-              st4(&S->rad, rr.x + nc.x, rr.y + nc.y, rr.z + nc.z, rr.w);
-            }
-            if (st.neeKey && nc.w != 0.0f) nee_aov_record(st, slot, found);
+            shadow_ray_finish(st, qs, qIn, rec, qs.slot[qIn][rec], found);
           }
         }
       }
@@ -391,10 +387,8 @@ __device__ __forceinline__ void trace_dyn_body(const SceneView& sc, const PathSt
     for (int off = 32; off > 0; off >>= 1) n += __shfl_down(n, off);
     if (lane == 0 && n) atomicAdd(&cnt->shadowOrderSteps[slotOrder ? 1 : 0][(blockIdx.x * (TRACE_BLOCK / 64u) + (threadIdx.x >> 6)) & 15u].v, n);
   }
-  if (COUNT) { // measurement builds only: one atomic pair per wave
-    unsigned long long a = tc.nodes, b = tc.tris;
-    for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off); b += __shfl_down(b, off); }
-    if (lane == 0) { atomicAdd(ANYHIT ? &cnt->shadowNodesVisited : &cnt->nodesVisited, a); atomicAdd(ANYHIT ? &cnt->shadowTrisTested : &cnt->trisTested, b); }
+  if (COUNT) {
+    trace_counters_flush<ANYHIT>(cnt, tc);
     if (!ANYHIT && !TWO && lane == 0) for (int k = 0; k < 8; k++) atomicAdd(&cnt->dynStats[k], ds[k]);
   }
 }
@@ -457,70 +451,57 @@ static bool sceneFitsLds(const SceneView& sc) { return sceneFitsLds(sc.nodeCount
 bool traceBlockSync(const SceneView& sc) { return sceneFitsLds(sc) && sc.bvhDepth <= 8u; }
 static uint32_t traceStackEntries(const SceneView& sc) { return (sc.bvhDepth <= 4u && sceneFitsLds(sc)) ? 4u : (sc.bvhDepth <= 8u ? 8u : 16u); }
 uint32_t traceStaticLdsBytes() { return (uint32_t)(sizeof(WaveTri) * (TRACE_BLOCK / 64) + sizeof(AppendScratch<1 + MAT_CLASS_COUNT>)); }
+uint32_t traceLdsBytes(uint32_t stackEntries, uint32_t ldsNodes, uint32_t ldsTris)
+{
+  return stackEntries * TRACE_BLOCK * (uint32_t)sizeof(uint2) + ldsNodes * LDS_NODE_BYTES + ldsTris * LDS_TRI_BYTES;
+}
+uint32_t blocksPerCuByLds(uint32_t dynamicBytes, uint32_t staticBytes) { return (160u * 1024u) / (dynamicBytes + staticBytes + 256u); }
 void traceLdsLayout(const SceneView& sc, uint32_t& ldsNodes, uint32_t& ldsTris, uint32_t& bytes)
 {
   ldsNodes = sc.nodeCount < LDS_NODES ? sc.nodeCount : LDS_NODES;
   ldsTris = sc.triCount <= LDS_TRIS ? sc.triCount : 0u;
-  bytes = traceStackEntries(sc) * TRACE_BLOCK * (uint32_t)sizeof(uint2) + ldsNodes * 80u + ldsTris * 48u;
+  bytes = traceLdsBytes(traceStackEntries(sc), ldsNodes, ldsTris);
   // (+ the kernels' static LDS: WaveTri per wave and the append scratch, see traceStaticLdsBytes)
-}
-template <bool ANYHIT, bool COUNT, bool CUTOUT>
-static void launchTraceVariant(hipStream_t s, uint32_t blocks, const SceneView& sc, const PathState& st, const QueueSet& qs, Counters* cnt, uint32_t qIn,
-    uint32_t qMiss,
-                               uint32_t dynRefill, uint32_t routeBlocks, const FrameUniforms& U, F4* sampleBuf)
-{
-  if (traceBlockSync(sc)) { // the whole scene is staged in LDS
-    uint32_t ln, lt, bytes; traceLdsLayout(sc, ln, lt, bytes);
-    const bool dome = !ANYHIT && (sc.domeTexture != 0u || sc.mediumStackSize != 0u); // misses need the slot: dome image lookup / scattering events
-#define GI_LAUNCH_TRACE(STACK) do { \
-      if (dome) \
-        hipLaunchKernelGGL((k_trace<ANYHIT, COUNT, STACK, CUTOUT, !ANYHIT>), dim3(blocks), dim3(TRACE_BLOCK), bytes, s, sc, st, qs, cnt, qIn, qMiss, ln, lt, U, \
-                           sampleBuf); \
-      else hipLaunchKernelGGL((k_trace<ANYHIT, COUNT, STACK, CUTOUT, false>), dim3(blocks), dim3(TRACE_BLOCK), bytes, s, sc, st, qs, cnt, qIn, qMiss, ln, lt, U, \
-          sampleBuf); } while (0)
-    if (sc.bvhDepth <= 4u) GI_LAUNCH_TRACE(4);
-    else GI_LAUNCH_TRACE(8);
-#undef GI_LAUNCH_TRACE
-    return;
-  }
-  // persistent waves with dynamic ray fetch, results routed by a streaming pass
-  const uint32_t refill = (dynRefill & 0xffu) | (ANYHIT ? (dynRefill & DYN_SLOT_ORDER) : 0u);
-  // 8 entries (16 KB per block), 12 (24 KB: 5 blocks per CU still fit next to the 8 KB of WaveTri) or 16 (32 KB: 4 blocks -- one wave per SIMD fewer); trees
-  // deeper than 16 levels spill the rest to scratch (persistent waves pay its set-up once)
-  const uint32_t stackBytes = (sc.bvhDepth <= 8u ? 8u : (sc.bvhDepth <= 12u ? 12u : 16u)) * TRACE_BLOCK * (uint32_t)sizeof(uint2);
-#define GI_LAUNCH_DYN(STACK, OVF) do { \
-    if (ANYHIT && (refill & DYN_SLOT_ORDER)) \
-      hipLaunchKernelGGL((k_trace_dyn<ANYHIT, COUNT, STACK, OVF, CUTOUT, ANYHIT>), dim3(blocks), dim3(TRACE_BLOCK), stackBytes, s, sc, st, qs, cnt, qIn, \
-                         refill); \
-    else hipLaunchKernelGGL((k_trace_dyn<ANYHIT, COUNT, STACK, OVF, CUTOUT, false>), dim3(blocks), dim3(TRACE_BLOCK), stackBytes, s, sc, st, qs, cnt, qIn, \
-        refill); } while (0)
-  if (sc.twoLevel) // instanced scene: TLAS + shared per-mesh BLASes
-    hipLaunchKernelGGL((k_trace_dyn2<ANYHIT, COUNT, CUTOUT>), dim3(blocks), dim3(TRACE_BLOCK), 16u * TRACE_BLOCK * (uint32_t)sizeof(uint2), s, sc, st, qs,
-        cnt, qIn, refill);
-  else if (sc.bvhDepth <= 8u) GI_LAUNCH_DYN(8, false);
-  else if (sc.bvhDepth <= 12u) GI_LAUNCH_DYN(12, false);
-  else if (sc.bvhDepth <= 16u) GI_LAUNCH_DYN(16, false);
-  else GI_LAUNCH_DYN(16, true);
-#undef GI_LAUNCH_DYN
-  if (!ANYHIT) launchRoute(s, routeBlocks, sc, st, qs, cnt, qIn, qMiss, U, sampleBuf);
-}
-template <bool ANYHIT, bool COUNT>
-static void launchTraceCutout(hipStream_t s, uint32_t blocks, const SceneView& sc, const PathState& st, const QueueSet& qs, Counters* cnt, uint32_t qIn,
-    uint32_t qMiss,
-                              uint32_t dynRefill, uint32_t routeBlocks, const FrameUniforms& U, F4* sampleBuf)
-{
-  if (sc.hasCutouts) launchTraceVariant<ANYHIT, COUNT, true>(s, blocks, sc, st, qs, cnt, qIn, qMiss, dynRefill, routeBlocks, U, sampleBuf);
-  else launchTraceVariant<ANYHIT, COUNT, false>(s, blocks, sc, st, qs, cnt, qIn, qMiss, dynRefill, routeBlocks, U, sampleBuf);
 }
 // U / sampleBuf: the frame's uniforms and per-sample colour buffer -- read only when the queue holds camera rays flagged TRACE_FRESH (FLAG_DEFER_SLOT)
 void launchTrace(hipStream_t s, uint32_t blocks, bool anyHit, bool count, const SceneView& sc, const PathState& st, const QueueSet& qs, Counters* cnt,
                  uint32_t qIn, uint32_t qMiss, uint32_t dynRefill, uint32_t routeBlocks, const FrameUniforms& U, F4* sampleBuf)
 {
   if ((dynRefill & 0xffu) > 64u) dynRefill = (dynRefill & ~0xffu) | 64u;
-  if (!anyHit) { if (count) launchTraceCutout<false, true>(s, blocks, sc, st, qs, cnt, qIn, qMiss, dynRefill, routeBlocks, U, sampleBuf);
-      else launchTraceCutout<false, false>(s, blocks, sc, st, qs, cnt, qIn, qMiss, dynRefill, routeBlocks, U, sampleBuf); }
-  else { if (count) launchTraceCutout<true, true>(s, blocks, sc, st, qs, cnt, qIn, qMiss, dynRefill, routeBlocks, U, sampleBuf);
-      else launchTraceCutout<true, false>(s, blocks, sc, st, qs, cnt, qIn, qMiss, dynRefill, routeBlocks, U, sampleBuf); }
+  dispatchBools([&](auto anyHitC, auto countC, auto cutoutC) {
+    constexpr bool ANYHIT = decltype(anyHitC)::value, COUNT = decltype(countC)::value, CUTOUT = decltype(cutoutC)::value;
+    if (traceBlockSync(sc)) { // the whole scene is staged in LDS
+      uint32_t ln, lt, bytes; traceLdsLayout(sc, ln, lt, bytes);
+      const bool dome = !ANYHIT && (sc.domeTexture != 0u || sc.mediumStackSize != 0u); // misses need the slot: dome image lookup / scattering events
+      dispatchBools([&](auto stack8C, auto domeC) {
+        constexpr uint32_t STACK = decltype(stack8C)::value ? 8u : 4u;
+        constexpr bool DOME = !ANYHIT && decltype(domeC)::value;
+        hipLaunchKernelGGL((k_trace<ANYHIT, COUNT, STACK, CUTOUT, DOME>), dim3(blocks), dim3(TRACE_BLOCK), bytes, s, sc, st, qs, cnt, qIn, qMiss, ln, lt, U,
+                           sampleBuf);
+      }, sc.bvhDepth > 4u, dome);
+      return;
+    }
+    // persistent waves with dynamic ray fetch, results routed by a streaming pass
+    const uint32_t refill = (dynRefill & 0xffu) | (ANYHIT ? (dynRefill & DYN_SLOT_ORDER) : 0u);
+    // 8 entries (16 KB per block), 12 (24 KB: 5 blocks per CU still fit next to the 8 KB of WaveTri) or 16 (32 KB: 4 blocks -- one wave per SIMD fewer); trees
+    // deeper than 16 levels spill the rest to scratch (persistent waves pay its set-up once)
+    auto dyn = [&](auto stackC, auto overflowC) {
+      constexpr uint32_t STACK = decltype(stackC)::value;
+      dispatchBools([&](auto slotC) {
+        constexpr bool SLOT = ANYHIT && decltype(slotC)::value;
+        hipLaunchKernelGGL((k_trace_dyn<ANYHIT, COUNT, STACK, decltype(overflowC)::value, CUTOUT, SLOT>), dim3(blocks), dim3(TRACE_BLOCK),
+                           traceLdsBytes(STACK, 0u, 0u), s, sc, st, qs, cnt, qIn, refill);
+      }, ANYHIT && (refill & DYN_SLOT_ORDER) != 0u);
+    };
+    using std::integral_constant;
+    if (sc.twoLevel) // instanced scene: TLAS + shared per-mesh BLASes
+      hipLaunchKernelGGL((k_trace_dyn2<ANYHIT, COUNT, CUTOUT>), dim3(blocks), dim3(TRACE_BLOCK), traceLdsBytes(16u, 0u, 0u), s, sc, st, qs, cnt, qIn, refill);
+    else if (sc.bvhDepth <= 8u) dyn(integral_constant<uint32_t, 8u>{}, std::false_type{});
+    else if (sc.bvhDepth <= 12u) dyn(integral_constant<uint32_t, 12u>{}, std::false_type{});
+    else if (sc.bvhDepth <= 16u) dyn(integral_constant<uint32_t, 16u>{}, std::false_type{});
+    else dyn(integral_constant<uint32_t, 16u>{}, std::true_type{});
+    if (!ANYHIT) launchRoute(s, routeBlocks, sc, st, qs, cnt, qIn, qMiss, U, sampleBuf);
+  }, anyHit, count, sc.hasCutouts != 0u);
 }
 
 } // namespace gi

@@ -1,5 +1,7 @@
-// gi_traversal.h -- software traversal of the 8-wide quantised BVH: per-lane traversal state and node test, the per-lane step
-// (k_aov), the wave-cooperative triangle stage and wave_step (k_trace, k_trace_dyn).  Included by gi_kernels.hip only.
+// gi_traversal.h -- software traversal of the 8-wide quantised BVH, shared by every kernel that walks it: per-lane traversal state and node test, the scene
+// staged in LDS (stage_scene), the per-lane step (k_aov: traverse), the wave's ring of (ray lane, triangle) pairs with its two append forms and the cooperative
+// triangle batch, wave_step (gi_trace.hip k_trace, gi_path.hip k_path) and the two-level walk wave_step2 (k_trace_dyn2).  gi_trace.hip's k_trace_dyn composes
+// its own step from the same pieces.  Included by gi_trace.hip, gi_path.hip, gi_aov.hip, gi_kernels.hip and gi_shade.hip.
 #pragma once
 
 #include "gi_queues.h"
@@ -8,7 +10,7 @@
 namespace gi {
 
 // ------------------------------------------------------------------------------------------------
-// k_trace: software traversal of the 8-wide quantised BVH, one ray per lane.
+// Software traversal of the 8-wide quantised BVH, one ray per lane.
 //   * persistent blocks stage the top of the tree (and, for small scenes, all triangles) into LDS once
 //   * per-lane traversal stack: 8 entries in LDS + scratch overflow
 //   * octant-ordered child visits (Ylitie et al. 2017), two-sided Moeller-Trumbore on 48-byte records
@@ -16,10 +18,41 @@ namespace gi {
 // ------------------------------------------------------------------------------------------------
 constexpr uint32_t LDS_NODES = 384;  // upper bound: 30 KiB   (the launch stages min(nodeCount, LDS_NODES) nodes)
 constexpr uint32_t LDS_TRIS = 128;   // upper bound: 6 KiB    (all triangles when the scene has <= LDS_TRIS, else none)
+constexpr uint32_t LDS_NODE_BYTES = 80; // a staged node: five 16-byte pieces
+constexpr uint32_t LDS_TRI_BYTES = 48;  // a staged triangle: the first three 16-byte pieces of its 64-byte record
 constexpr uint32_t OVF_STACK = 40;   // scratch overflow entries of the fallback variant (trees deeper than 16 levels)
 constexpr uint32_t TRACE_BLOCK = 256;
 
 struct TraceCounters { uint32_t nodes, tris; };
+
+// What a block keeps in its dynamic LDS, [stack | nodes | triangles]: the per-lane traversal stacks and the part of the scene staged beside them (the launch
+// sizes it: traceLdsBytes in gi_kernels.h).  A node below ldsNodes / a triangle below ldsTris is read from LDS, the others from global memory.
+struct StagedScene {
+  uint2 (*stack)[TRACE_BLOCK];
+  const uint4* nodes;
+  const uint4* tris;
+  uint32_t ldsNodes, ldsTris;
+};
+// what the walk's code is compiled for: nothing staged (every fetch goes to global memory), some of the scene (each fetch compares its index), all of it
+enum Staged : uint32_t { STAGED_NONE, STAGED_SOME, STAGED_ALL };
+// the stacks alone (k_trace_dyn: scenes beyond LDS)
+__device__ __forceinline__ StagedScene stage_stack()
+{
+  extern __shared__ uint4 s_dyn[];
+  return StagedScene{reinterpret_cast<uint2 (*)[TRACE_BLOCK]>(s_dyn), nullptr, nullptr, 0u, 0u};
+}
+// carves the dynamic LDS, copies the first ldsNodes nodes and ldsTris triangles of the scene into it and waits for the block (every thread of it calls this)
+template <uint32_t STACK>
+__device__ __forceinline__ StagedScene stage_scene(const SceneView& sc, uint32_t ldsNodes, uint32_t ldsTris)
+{
+  extern __shared__ uint4 s_dyn[];
+  uint4* s_nodes = s_dyn + (STACK * TRACE_BLOCK * sizeof(uint2)) / sizeof(uint4);
+  uint4* s_tris = s_nodes + ldsNodes * 5u;
+  for (uint32_t i = threadIdx.x; i < ldsNodes * 5u; i += TRACE_BLOCK) s_nodes[i] = reinterpret_cast<const uint4*>(sc.nodes)[i];
+  for (uint32_t i = threadIdx.x; i < ldsTris * 3u; i += TRACE_BLOCK) s_tris[i] = reinterpret_cast<const uint4*>(sc.tris)[(i / 3u) * 4u + (i % 3u)];
+  __syncthreads();
+  return StagedScene{reinterpret_cast<uint2 (*)[TRACE_BLOCK]>(s_dyn), s_nodes, s_tris, ldsNodes, ldsTris};
+}
 
 // STACK = per-lane stack entries kept in LDS.  The traversal pushes at most one entry per tree level, so the host
 // picks STACK >= tree depth (8 or 16) and the scratch overflow (OVERFLOW) is compiled in only for deeper trees:
@@ -44,9 +77,10 @@ struct RayTrav : RayWalk {
   bool found;
 };
 
-__device__ __forceinline__ void walk_init(RayWalk& R, V3 o, V3 d, float tMin, float tMax)
+// the ray a walk tests boxes with (k_trace_dyn2 sets it again whenever the walk enters or leaves an instance)
+__device__ __forceinline__ void walk_set_ray(RayWalk& R, V3 o, V3 d)
 {
-  R.o = o; R.d = d; R.tMin = tMin; R.tBest = tMax;
+  R.o = o; R.d = d;
   // reciprocal direction for the slab tests only (guard against 0: boxes are padded, a huge finite value is safe)
   const float gx = (fabsf(d.x) < 1e-30f) ? (d.x < 0.0f ? -1e-30f : 1e-30f) : d.x;
   const float gy = (fabsf(d.y) < 1e-30f) ? (d.y < 0.0f ? -1e-30f : 1e-30f) : d.y;
@@ -54,6 +88,11 @@ __device__ __forceinline__ void walk_init(RayWalk& R, V3 o, V3 d, float tMin, fl
   // v_rcp_f32 (1 ulp) instead of three IEEE divisions: the reciprocals only feed the box tests, whose far planes are widened by 1e-5
   R.idx = __builtin_amdgcn_rcpf(gx); R.idy = __builtin_amdgcn_rcpf(gy); R.idz = __builtin_amdgcn_rcpf(gz);
   R.octinv = ((d.x >= 0.0f ? 1u : 0u) | (d.y >= 0.0f ? 2u : 0u) | (d.z >= 0.0f ? 4u : 0u)) * 0x01010101u; // replicated into the 4 bytes (trav_node_test)
+}
+__device__ __forceinline__ void walk_init(RayWalk& R, V3 o, V3 d, float tMin, float tMax)
+{
+  R.tMin = tMin; R.tBest = tMax;
+  walk_set_ray(R, o, d);
   R.G = make_uint2(0u, 0x80000000u); // virtual group holding only the root
   R.sp = 0u;
 }
@@ -163,13 +202,13 @@ __device__ __forceinline__ void node_load(const SceneView& sc, uint32_t nodeIdx,
 }
 
 // The per-lane composition (each lane fetches its own node: from LDS when staged there, else from global memory)
-template <bool COUNT, uint32_t STACK, bool OVERFLOW, bool ALL_LDS, bool ORDERED = true>
-__device__ __forceinline__ uint2 trav_node(RayWalk& R, const SceneView& sc, const uint4* s_nodes, uint32_t ldsNodes,
-                                           uint2 (*s_stack)[TRACE_BLOCK], uint2 (&overflow)[OVERFLOW ? OVF_STACK : 1], TraceCounters& tc)
+template <bool COUNT, uint32_t STACK, bool OVERFLOW, Staged STAGED, bool ORDERED = true>
+__device__ __forceinline__ uint2 trav_node(RayWalk& R, const SceneView& sc, StagedScene S, uint2 (&overflow)[OVERFLOW ? OVF_STACK : 1],
+                                           TraceCounters& tc)
 {
-  const uint32_t nodeIdx = trav_node_pick<STACK, OVERFLOW, ORDERED>(R, s_stack, overflow);
+  const uint32_t nodeIdx = trav_node_pick<STACK, OVERFLOW, ORDERED>(R, S.stack, overflow);
   uint4 n0, n1, n2, n3, n4;
-  if (ALL_LDS || nodeIdx < ldsNodes) { const uint4* p = s_nodes + nodeIdx * 5u; n0 = p[0]; n1 = p[1]; n2 = p[2]; n3 = p[3]; n4 = p[4]; }
+  if (STAGED == STAGED_ALL || (STAGED == STAGED_SOME && nodeIdx < S.ldsNodes)) { const uint4* p = S.nodes + nodeIdx * 5u; n0 = p[0]; n1 = p[1]; n2 = p[2]; n3 = p[3]; n4 = p[4]; }
   else node_load(sc, nodeIdx, n0, n1, n2, n3, n4);
   if (COUNT) tc.nodes++;
   return trav_node_test<false, ORDERED>(R, n0, n1, n2, n3, n4);
@@ -205,13 +244,13 @@ __device__ __forceinline__ bool tri_test(V3 o, V3 d, float tMin, const uint4& a,
 }
 
 // Advances the ray by one group (node, then its leaf triangles one after the other, then pop); returns true when the
-// traversal is finished.  The per-lane form used by k_aov and the block-synchronous k_trace.
-template <bool ANYHIT, bool COUNT, uint32_t STACK, bool OVERFLOW, bool ALL_LDS, bool CUTOUT>
-__device__ __forceinline__ bool trav_step(RayTrav& R, const SceneView& sc, const uint4* s_nodes, uint32_t ldsNodes, const uint4* s_tris, uint32_t ldsTris,
-                                          uint2 (*s_stack)[TRACE_BLOCK], uint2 (&overflow)[OVERFLOW ? OVF_STACK : 1], TraceCounters& tc, uint32_t rng)
+// traversal is finished.  The per-lane form used by k_aov.
+template <bool ANYHIT, bool COUNT, uint32_t STACK, bool OVERFLOW, Staged STAGED, bool CUTOUT>
+__device__ __forceinline__ bool trav_step(RayTrav& R, const SceneView& sc, StagedScene S, uint2 (&overflow)[OVERFLOW ? OVF_STACK : 1], TraceCounters& tc,
+                                          uint32_t rng)
 {
   uint2 Gt;
-  if (R.G.y & 0xff000000u) Gt = trav_node<COUNT, STACK, OVERFLOW, ALL_LDS>(R, sc, s_nodes, ldsNodes, s_stack, overflow, tc);
+  if (R.G.y & 0xff000000u) Gt = trav_node<COUNT, STACK, OVERFLOW, STAGED>(R, sc, S, overflow, tc);
   else { Gt = R.G; R.G = make_uint2(0u, 0u); }
   // triangles of this node
   while (Gt.y) {
@@ -219,7 +258,7 @@ __device__ __forceinline__ bool trav_step(RayTrav& R, const SceneView& sc, const
     Gt.y &= Gt.y - 1u;
     const uint32_t triIdx = Gt.x + k;
     uint4 a, b, c;
-    if (ALL_LDS || triIdx < ldsTris) { const uint4* p = s_tris + triIdx * 3u; a = p[0]; b = p[1]; c = p[2]; }
+    if (STAGED == STAGED_ALL || (STAGED == STAGED_SOME && triIdx < S.ldsTris)) { const uint4* p = S.tris + triIdx * 3u; a = p[0]; b = p[1]; c = p[2]; }
     else { const uint4* p = reinterpret_cast<const uint4*>(sc.tris) + (size_t)triIdx * 4u; a = p[0]; b = p[1]; c = p[2]; }
     if (COUNT) tc.tris++;
     const uint32_t orig = c.y;
@@ -236,7 +275,7 @@ __device__ __forceinline__ bool trav_step(RayTrav& R, const SceneView& sc, const
       if (ANYHIT) { R.G.y = 0u; R.sp = 0u; break; }
     }
   }
-  return trav_pop<STACK, OVERFLOW>(R, s_stack, overflow);
+  return trav_pop<STACK, OVERFLOW>(R, S.stack, overflow);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -283,43 +322,60 @@ __device__ __forceinline__ uint32_t wt_helpers_add(WaveTri& W, uint32_t i, uint3
 __device__ __forceinline__ uint4 wt_hit_get(WaveTri& W, uint32_t i)
 { const gi_u4 v = *(volatile GI_LDS gi_u4*)&((GI_LDS WaveTri*)&W)->hit[i]; return make_uint4(v.x, v.y, v.z, v.w); }
 
-// 64 (ray lane, triangle) pairs of the ring, one per lane.  RESULT_RECORD (k_trace_dyn): the winner leaves the ray's finished result record in WaveTri::hit.
-template <bool COUNT, bool ALL_LDS, bool CUTOUT, bool RESULT_RECORD = false>
+// The ray of the lane that owns a pair, fetched from that lane's registers (executed by all lanes: wave-uniform control flow)
+template <bool CUTOUT>
+__device__ __forceinline__ void owner_ray(uint32_t rl, V3 ro, V3 rd, float rtMin, uint32_t rng, V3& o, V3& d, float& tMin, uint32_t& rrng)
+{
+  o = v3(__shfl(ro.x, (int)rl), __shfl(ro.y, (int)rl), __shfl(ro.z, (int)rl));
+  d = v3(__shfl(rd.x, (int)rl), __shfl(rd.y, (int)rl), __shfl(rd.z, (int)rl));
+  tMin = __shfl(rtMin, (int)rl);
+  rrng = CUTOUT ? (uint32_t)__shfl((int)rng, (int)rl) : 0u;
+}
+
+// What follows tri_test for a candidate of ray lane rl: the cutout decision, the hit key under atomicMin and the winner's hit record.  Of the triangle's third
+// 16-byte piece `c` it reads .y, the scene-order id, and .w, the material word; `flatTri` is the index of the triangle's TriRec (what the cutout lookup reads),
+// `recTri` what the record names it by.  RESULT_RECORD (k_trace_dyn, k_trace_dyn2): the winner leaves the ray's finished result record in WaveTri::hit.
+template <bool CUTOUT, bool RESULT_RECORD>
+__device__ __forceinline__ void wave_tri_accept(WaveTri& W, uint32_t rl, uint32_t rrng, const SceneView& sc, bool accept, float t, float u, float v,
+                                                const uint4& c, uint32_t flatTri, uint32_t recTri)
+{
+  if (CUTOUT && accept && (c.w & (1u << 28))) { // non-opaque material: stochastic cutout (ignoreIntersectionEXT, rp_main.ahit:57-60)
+    const float opacity = cutout_opacity_at(sc, c.w, flatTri, u, v);
+    accept = !(cutout_random(rrng, c.y) > opacity);
+  }
+  if (accept) {
+    const unsigned long long key = ((unsigned long long)f2u(t) << 32) | (unsigned long long)(c.y + 1u);
+    wt_best_min(W, rl, key);
+    if (wt_best_get(W, rl) == key) {
+      // the material class k_route sorts by rides in the top four bits
+      if (RESULT_RECORD) wt_hit_put3(W, rl, f2u(u), f2u(v), recTri | (((c.w >> 24) & 0xfu) << 28));
+      else wt_hit_put(W, rl, recTri, f2u(u), f2u(v), c.w);
+    }
+  }
+}
+
+// 64 (ray lane, triangle) pairs of the ring, one per lane.
+template <bool COUNT, Staged STAGED, bool CUTOUT, bool RESULT_RECORD = false>
 __device__ __forceinline__ void wave_tri_batch(WaveTri& W, uint32_t head, uint32_t cnt, const RayWalk& R, uint32_t rng, const SceneView& sc,
-                                               const uint4* s_tris, uint32_t ldsTris, TraceCounters& tc)
+                                               StagedScene S, TraceCounters& tc)
 {
   const uint32_t lane = __lane_id();
   const bool act = lane < cnt;
   const uint32_t e = act ? wt_queue_get(W, (head + lane) & 127u) : 0u;
   const uint32_t rl = e >> TRI_ID_BITS, triIdx = e & ((1u << TRI_ID_BITS) - 1u);
-  // the owning lane's ray (executed by all lanes: wave-uniform control flow)
-  const V3 o = v3(__shfl(R.o.x, (int)rl), __shfl(R.o.y, (int)rl), __shfl(R.o.z, (int)rl));
-  const V3 d = v3(__shfl(R.d.x, (int)rl), __shfl(R.d.y, (int)rl), __shfl(R.d.z, (int)rl));
-  const float tMin = __shfl(R.tMin, (int)rl);
-  const uint32_t rrng = CUTOUT ? (uint32_t)__shfl((int)rng, (int)rl) : 0u;
+  V3 o, d; float tMin; uint32_t rrng;
+  owner_ray<CUTOUT>(rl, R.o, R.d, R.tMin, rng, o, d, tMin, rrng);
   if (act) {
     uint4 a, b, c;
     // (the compiler loads c.x here and sinks the loads of c.y -- scene-order id -- and c.w -- material word -- into the accept branch; loading all 48 bytes
     // up front measured SLOWER in full launches, r03a: the vector-memory request path, not the dependent round trip, is what the batch waits for -- and no
     // faster in thin ones, r05i)
-    if (ALL_LDS || triIdx < ldsTris) { const uint4* p = s_tris + triIdx * 3u; a = p[0]; b = p[1]; c = p[2]; }
+    if (STAGED == STAGED_ALL || (STAGED == STAGED_SOME && triIdx < S.ldsTris)) { const uint4* p = S.tris + triIdx * 3u; a = p[0]; b = p[1]; c = p[2]; }
     else { const uint4* p = reinterpret_cast<const uint4*>(sc.tris) + (size_t)triIdx * 4u; a = p[0]; b = p[1]; c = p[2]; }
     if (COUNT) tc.tris++;
     float t, u, v;
-    bool accept = tri_test(o, d, tMin, a, b, c, t, u, v);
-    if (CUTOUT && accept && (c.w & (1u << 28))) { // non-opaque material: stochastic cutout (ignoreIntersectionEXT, rp_main.ahit:57-60)
-      const float opacity = cutout_opacity_at(sc, c.w, triIdx, u, v);
-      accept = !(cutout_random(rrng, c.y) > opacity);
-    }
-    if (accept) {
-      const unsigned long long key = ((unsigned long long)f2u(t) << 32) | (unsigned long long)(c.y + 1u);
-      wt_best_min(W, rl, key);
-      if (wt_best_get(W, rl) == key) {
-        // the material class k_route sorts by rides in the top four bits
-        if (RESULT_RECORD) wt_hit_put3(W, rl, f2u(u), f2u(v), triIdx | (((c.w >> 24) & 0xfu) << 28));
-        else wt_hit_put(W, rl, triIdx, f2u(u), f2u(v), c.w);
-      }
-    }
+    const bool inside = tri_test(o, d, tMin, a, b, c, t, u, v);
+    wave_tri_accept<CUTOUT, RESULT_RECORD>(W, rl, rrng, sc, inside, t, u, v, c, triIdx, triIdx);
   }
 }
 
@@ -336,16 +392,15 @@ __device__ __forceinline__ uint32_t wave_scan_inclusive(uint32_t v)
   return (uint32_t)scan;
 }
 
-// One step of all rays of a wave (k_trace: scenes staged in LDS): node phase per lane, then the cooperative triangle stage, then pop.  Wave-uniform
+// One step of all rays of a wave (k_trace, k_path: scenes staged in LDS): node phase per lane, then the cooperative triangle stage, then pop.  Wave-uniform
 // control flow; lanes without a ray (alive == false) only help testing triangles.  Returns true when this lane's ray is finished.
-template <bool ANYHIT, bool COUNT, uint32_t STACK, bool OVERFLOW, bool ALL_LDS, bool CUTOUT>
-__device__ __forceinline__ bool wave_step(RayTrav& R, bool alive, WaveTri& W, const SceneView& sc, const uint4* s_nodes, uint32_t ldsNodes,
-                                          const uint4* s_tris, uint32_t ldsTris, uint2 (*s_stack)[TRACE_BLOCK], uint2 (&overflow)[OVERFLOW ? OVF_STACK : 1],
-                                          TraceCounters& tc, uint32_t rng)
+template <bool ANYHIT, bool COUNT, uint32_t STACK, bool OVERFLOW, Staged STAGED, bool CUTOUT>
+__device__ __forceinline__ bool wave_step(RayTrav& R, bool alive, WaveTri& W, const SceneView& sc, StagedScene S,
+                                          uint2 (&overflow)[OVERFLOW ? OVF_STACK : 1], TraceCounters& tc, uint32_t rng)
 {
   const uint32_t lane = __lane_id();
   uint2 Gt = make_uint2(0u, 0u);
-  if (alive) Gt = trav_node<COUNT, STACK, OVERFLOW, ALL_LDS>(R, sc, s_nodes, ldsNodes, s_stack, overflow, tc);
+  if (alive) Gt = trav_node<COUNT, STACK, OVERFLOW, STAGED>(R, sc, S, overflow, tc);
   uint32_t head = 0u, tail = 0u; // wave-uniform
   { // positions from a wave prefix sum over the per-lane pair counts, then every lane writes its own pairs
     const uint32_t cntL = (uint32_t)__popc(Gt.y);
@@ -360,7 +415,7 @@ __device__ __forceinline__ bool wave_step(RayTrav& R, bool alive, WaveTri& W, co
         pos++;
       }
       tail = total;
-      while (tail - head >= 64u) { wave_tri_batch<COUNT, ALL_LDS, CUTOUT>(W, head, 64u, R, rng, sc, s_tris, ldsTris, tc); head += 64u; }
+      while (tail - head >= 64u) { wave_tri_batch<COUNT, STAGED, CUTOUT>(W, head, 64u, R, rng, sc, S, tc); head += 64u; }
     }
   }
   for (;;) { // (more pairs than the ring holds) one ballot round per triangle, a batch whenever 64 pairs are pending
@@ -372,15 +427,15 @@ __device__ __forceinline__ bool wave_step(RayTrav& R, bool alive, WaveTri& W, co
       wt_queue_put(W, (tail + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))) & 127u, (lane << TRI_ID_BITS) | (Gt.x + k));
     }
     tail += (uint32_t)__popcll(m);
-    if (tail - head >= 64u) { wave_tri_batch<COUNT, ALL_LDS, CUTOUT>(W, head, 64u, R, rng, sc, s_tris, ldsTris, tc); head += 64u; }
+    if (tail - head >= 64u) { wave_tri_batch<COUNT, STAGED, CUTOUT>(W, head, 64u, R, rng, sc, S, tc); head += 64u; }
   }
-  if (tail != head) wave_tri_batch<COUNT, ALL_LDS, CUTOUT>(W, head, tail - head, R, rng, sc, s_tris, ldsTris, tc);
+  if (tail != head) wave_tri_batch<COUNT, STAGED, CUTOUT>(W, head, tail - head, R, rng, sc, S, tc);
   bool done = false;
   if (alive) {
     const unsigned long long key = wt_best_get(W, lane);
     R.tBest = u2f((uint32_t)(key >> 32));
     R.found = (uint32_t)key != 0u;
-    done = (ANYHIT && R.found) ? true : trav_pop<STACK, OVERFLOW>(R, s_stack, overflow);
+    done = (ANYHIT && R.found) ? true : trav_pop<STACK, OVERFLOW>(R, S.stack, overflow);
   }
   return done;
 }
@@ -394,19 +449,16 @@ __device__ __forceinline__ void wave_ray_end(WaveTri& W, RayTrav& R)
   if (R.found) { const uint4 h = wt_hit_get(W, __lane_id()); R.bestTri = h.x; R.bestU = u2f(h.y); R.bestV = u2f(h.z); R.bestMat = h.w; }
 }
 
-template <bool ANYHIT, bool COUNT, uint32_t STACK, bool OVERFLOW, bool ALL_LDS, bool CUTOUT>
-__device__ __forceinline__ bool traverse(const SceneView& sc, const uint4* s_nodes, uint32_t ldsNodes, const uint4* s_tris, uint32_t ldsTris,
-                                         uint2 (*s_stack)[TRACE_BLOCK], V3 o, V3 d, float tMin, float tMax,
-                                         float& outT, float& outU, float& outV, uint32_t& outTri, uint32_t& outMat, TraceCounters& tc, uint32_t rng = 0u)
+template <bool ANYHIT, bool COUNT, uint32_t STACK, bool OVERFLOW, Staged STAGED, bool CUTOUT>
+__device__ __forceinline__ bool traverse(const SceneView& sc, StagedScene S, V3 o, V3 d, float tMin, float tMax, float& outT, float& outU, float& outV,
+                                         uint32_t& outTri, uint32_t& outMat, TraceCounters& tc, uint32_t rng = 0u)
 {
   RayTrav R; trav_init(R, o, d, tMin, tMax);
   uint2 overflow[OVERFLOW ? OVF_STACK : 1];
-  while (!trav_step<ANYHIT, COUNT, STACK, OVERFLOW, ALL_LDS, CUTOUT>(R, sc, s_nodes, ldsNodes, s_tris, ldsTris, s_stack, overflow, tc, rng)) {}
+  while (!trav_step<ANYHIT, COUNT, STACK, OVERFLOW, STAGED, CUTOUT>(R, sc, S, overflow, tc, rng)) {}
   outT = R.tBest; outU = R.bestU; outV = R.bestV; outTri = R.bestTri; outMat = R.bestMat;
   return R.found;
 }
-
-
 
 // ------------------------------------------------------------------------------------------------
 // Two-level traversal (k_trace_dyn2; SceneView::tlasNodes ...).  Instanced scenes flattened into one BVH are HBM-latency bound: 5 M
@@ -422,15 +474,6 @@ __device__ __forceinline__ bool traverse(const SceneView& sc, const uint4* s_nod
 constexpr uint32_t TLAS_ITEM_TAG = 0x80000000u, NO_INSTANCE = 0xffffffffu;
 struct RayTrav2 : RayWalk { V3 wo, wd; uint32_t inst, spBase; float slack; };
 
-__device__ __forceinline__ void trav2_set_ray(RayTrav2& R, V3 o, V3 d)
-{
-  R.o = o; R.d = d;
-  const float gx = (fabsf(d.x) < 1e-30f) ? (d.x < 0.0f ? -1e-30f : 1e-30f) : d.x;
-  const float gy = (fabsf(d.y) < 1e-30f) ? (d.y < 0.0f ? -1e-30f : 1e-30f) : d.y;
-  const float gz = (fabsf(d.z) < 1e-30f) ? (d.z < 0.0f ? -1e-30f : 1e-30f) : d.z;
-  R.idx = __builtin_amdgcn_rcpf(gx); R.idy = __builtin_amdgcn_rcpf(gy); R.idz = __builtin_amdgcn_rcpf(gz);
-  R.octinv = ((d.x >= 0.0f ? 1u : 0u) | (d.y >= 0.0f ? 2u : 0u) | (d.z >= 0.0f ? 4u : 0u)) * 0x01010101u;
-}
 __device__ __forceinline__ void trav2_init(RayTrav2& R, V3 o, V3 d, float tMin, float tMax)
 {
   walk_init(R, o, d, tMin, tMax);
@@ -450,13 +493,13 @@ __device__ __forceinline__ void trav2_enter(RayTrav2& R, const SceneView& sc, ui
   const float m0 = (fabsf(w[0] * rel.x) + fabsf(w[1] * rel.y)) + fabsf(w[2] * rel.z), m1 = (fabsf(w[3] * rel.x) + fabsf(w[4] * rel.y)) + fabsf(w[5] * rel.z),
               m2 = (fabsf(w[6] * rel.x) + fabsf(w[7] * rel.y)) + fabsf(w[8] * rel.z);
   R.slack = 4.0e-6f * ((m0 + m1) + (m2 + r6.x));
-  trav2_set_ray(R, o, d);
+  walk_set_ray(R, o, d);
   R.inst = inst; R.spBase = R.sp;
   R.G = make_uint2(f2u(r5.y), 0x80000000u); // virtual group holding only the BLAS root
 }
 __device__ __forceinline__ void trav2_leave(RayTrav2& R)
 {
-  trav2_set_ray(R, R.wo, R.wd);
+  walk_set_ray(R, R.wo, R.wd);
   R.inst = NO_INSTANCE; R.slack = 0.0f;
 }
 
@@ -469,11 +512,9 @@ __device__ __forceinline__ void wave_tri_batch2(WaveTri& W, uint32_t head, uint3
   const bool act = lane < cnt;
   const uint32_t e = act ? wt_queue_get(W, (head + lane) & 127u) : 0u;
   const uint32_t rl = e >> TRI_ID_BITS, bt = e & ((1u << TRI_ID_BITS) - 1u);
-  const V3 o = v3(__shfl(R.wo.x, (int)rl), __shfl(R.wo.y, (int)rl), __shfl(R.wo.z, (int)rl));
-  const V3 d = v3(__shfl(R.wd.x, (int)rl), __shfl(R.wd.y, (int)rl), __shfl(R.wd.z, (int)rl));
-  const float tMin = __shfl(R.tMin, (int)rl);
+  V3 o, d; float tMin; uint32_t rrng;
+  owner_ray<CUTOUT>(rl, R.wo, R.wd, R.tMin, rng, o, d, tMin, rrng);
   const uint32_t inst = (uint32_t)__shfl((int)R.inst, (int)rl);
-  const uint32_t rrng = CUTOUT ? (uint32_t)__shfl((int)rng, (int)rl) : 0u;
   if (act) {
     const float4* tp = reinterpret_cast<const float4*>(&sc.blasTris[bt]);   // one line: p0.xyz p1.x | p1.yz p2.xy | p2.z prim
     const float4 ta = tp[0], tb = tp[1], tq = tp[2];
@@ -495,17 +536,9 @@ __device__ __forceinline__ void wave_tri_batch2(WaveTri& W, uint32_t head, uint3
         c = make_uint4(f2u(e2.z), orig, inst, tv.z);
     if (COUNT) tc.tris++;
     float t, u, v;
-    bool accept = tri_test(o, d, tMin, a, b, c, t, u, v);
-    if (CUTOUT && accept && (c.w & (1u << 28))) {
-      const float opacity = cutout_opacity_at(sc, c.w, sc.flatOfOrig[orig], u, v);
-      accept = !(cutout_random(rrng, orig) > opacity);
-    }
-    if (accept) {
-      const unsigned long long key = ((unsigned long long)f2u(t) << 32) | (unsigned long long)(orig + 1u);
-      wt_best_min(W, rl, key);
-      // the result record, with the SCENE-ORDER id: the kernel maps it to the flat index
-      if (wt_best_get(W, rl) == key) wt_hit_put3(W, rl, f2u(u), f2u(v), orig | (((c.w >> 24) & 0xfu) << 28));
-    }
+    const bool inside = tri_test(o, d, tMin, a, b, c, t, u, v);
+    // the result record, with the SCENE-ORDER id: the kernel maps it to the flat index
+    wave_tri_accept<CUTOUT, true>(W, rl, rrng, sc, inside, t, u, v, c, CUTOUT ? sc.flatOfOrig[orig] : 0u, orig);
   }
 }
 
