@@ -25,6 +25,7 @@ OPTION_COUNT_TRAVERSAL, OPTION_KERNEL_TIMERS, OPTION_POOL_SLOTS, OPTION_SAMPLE_B
 OPTION_SAMPLE_LOOKAHEAD = 10  # N >= 2: a progressive call may trace the samples of up to N calls in one batch (include/gi_c.h); 0 / 1 = off (default)
 OPTION_VERTEX_UPDATES = 12  # 1: vertex edits (giCSetMeshVertices) of meshes of the built scene refit the resident BVH on the device instead of rebuilding the scene (include/gi_c.h); 0 = off (default)
 OPTION_VISIBILITY_UPDATES = 11  # 1: visibility edits of meshes of the built scene are applied to the resident scene instead of rebuilding it (include/gi_c.h); 0 = off (default)
+OPTION_TOPOLOGY_UPDATES = 13  # 1: meshes created and destroyed after the build are appended to / retired from the resident scene instead of rebuilding it (include/gi_c.h); 0 = off (default)
 OPTION_BVH_BUILD = 9  # 0 = host BVH builder (default), 1 = device builder (flat-layout scenes of more than 128 triangles)
 
 
@@ -165,6 +166,7 @@ SYMBOLS = [
     ("giCDebugSceneVisibilityUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugSceneClassState", C.c_int, [_P, C.POINTER(C.c_uint32)]),
     ("giCDebugSceneVertexUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugRefitBvh", C.c_int, [_FP, _FP, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("giCDebugSceneRefitCheck", C.c_int, [_P, _U, C.POINTER(C.c_uint32)]),
+    ("giCDebugSceneTopologyUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugPathWalkStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugMissRect", C.c_int, [_FP, C.POINTER(GiCCameraDesc), C.POINTER(GiCRenderSettings), _U, _U, C.POINTER(C.c_uint32)]),
 ]
@@ -285,34 +287,7 @@ class Scene:
             L.giCSetDomeLightRotation(self.dome, _fp(d.rotation)); L.giCSetDomeLightBaseEmission(self.dome, _fp(d.base_emission))
             L.giCSetDomeLightDiffuseSpecular(self.dome, d.diffuse, d.specular)
         for m in desc.meshes:
-            v = np.ascontiguousarray(m.vertices)
-            f = np.ascontiguousarray(m.faces, np.uint32)
-            fid = np.ascontiguousarray(m.face_ids, np.int32) if m.face_ids is not None else None
-            d = GiCMeshDesc(len(f), f.ctypes.data, fid.ctypes.data if fid is not None else None, m.id, int(m.double_sided),
-                            int(m.left_handed), m.name.encode(), int(m.max_face_id), len(v), v.ctypes.data)
-            h = L.giCCreateMesh(self.handle, C.byref(d))
-            if not h:
-                raise GiError("giCCreateMesh failed: " + L.giCGetLastError().decode())
-            L.giCSetMeshTransform(h, _fp(np.asarray(m.transform, np.float32).reshape(-1)))
-            it = np.ascontiguousarray(m.instance_transforms, np.float32).reshape(-1, 16)
-            L.giCSetMeshInstanceTransforms(h, len(it), it.ctypes.data_as(_FP))
-            if m.instance_ids is not None:
-                ids = np.ascontiguousarray(m.instance_ids, np.int32)
-                L.giCSetMeshInstanceIds(h, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int32)))
-            for attr, fn in (("primvars", L.giCSetMeshPrimvars), ("instancer_primvars", L.giCSetMeshInstancerPrimvars)):
-                pvs = getattr(m, attr, [])
-                if pvs:
-                    arr, keep = (GiCPrimvarData * len(pvs))(), []
-                    for k, pv in enumerate(pvs):
-                        d = np.ascontiguousarray(pv.data, np.int32 if int(pv.type) >= 4 else np.float32).reshape(-1)  # Int..Int4 (Gi.h:76-79)
-                        keep.append(d)
-                        arr[k] = GiCPrimvarData(pv.name.encode(), int(pv.type), int(pv.interpolation), d.ctypes.data, d.nbytes)
-                    if fn(h, len(pvs), arr) != GI_C_OK:  # copies the data
-                        raise GiError("giCSetMesh*Primvars failed: " + L.giCGetLastError().decode())
-            if m.material >= 0:
-                L.giCSetMeshMaterial(h, self.materials[m.material])
-            L.giCSetMeshVisibility(h, int(m.visible))
-            self.meshes.append(h)
+            self.meshes.append(self._mesh_handle(m))
         for l in desc.sphere_lights:
             h = L.giCCreateSphereLight(self.handle)
             L.giCSetSphereLightPosition(h, _fp(l.pos)); L.giCSetSphereLightBaseEmission(h, _fp(l.base_emission))
@@ -336,6 +311,58 @@ class Scene:
             L.giCSetDiskLightDiffuseSpecular(h, l.diffuse, l.specular)
             self.lights.append(("disk", h))
         self._buffers = {}
+
+    def _mesh_handle(self, m):
+        """giCCreateMesh and the setters hdGatling runs on every new mesh (mesh.cpp _CreateGiMeshes + Sync: transform, instance transforms, instance ids,
+        primvars, instancer primvars, material, visibility) for one MeshDesc."""
+        L = self.L
+        v = np.ascontiguousarray(m.vertices)
+        f = np.ascontiguousarray(m.faces, np.uint32)
+        fid = np.ascontiguousarray(m.face_ids, np.int32) if m.face_ids is not None else None
+        d = GiCMeshDesc(len(f), f.ctypes.data, fid.ctypes.data if fid is not None else None, m.id, int(m.double_sided),
+                        int(m.left_handed), m.name.encode(), int(m.max_face_id), len(v), v.ctypes.data)
+        h = L.giCCreateMesh(self.handle, C.byref(d))
+        if not h:
+            raise GiError("giCCreateMesh failed: " + L.giCGetLastError().decode())
+        L.giCSetMeshTransform(h, _fp(np.asarray(m.transform, np.float32).reshape(-1)))
+        it = np.ascontiguousarray(m.instance_transforms, np.float32).reshape(-1, 16)
+        L.giCSetMeshInstanceTransforms(h, len(it), it.ctypes.data_as(_FP))
+        if m.instance_ids is not None:
+            ids = np.ascontiguousarray(m.instance_ids, np.int32)
+            L.giCSetMeshInstanceIds(h, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int32)))
+        for attr, fn in (("primvars", L.giCSetMeshPrimvars), ("instancer_primvars", L.giCSetMeshInstancerPrimvars)):
+            pvs = getattr(m, attr, [])
+            if pvs:
+                arr, keep = (GiCPrimvarData * len(pvs))(), []
+                for k, pv in enumerate(pvs):
+                    d = np.ascontiguousarray(pv.data, np.int32 if int(pv.type) >= 4 else np.float32).reshape(-1)  # Int..Int4 (Gi.h:76-79)
+                    keep.append(d)
+                    arr[k] = GiCPrimvarData(pv.name.encode(), int(pv.type), int(pv.interpolation), d.ctypes.data, d.nbytes)
+                if fn(h, len(pvs), arr) != GI_C_OK:  # copies the data
+                    raise GiError("giCSetMesh*Primvars failed: " + L.giCGetLastError().decode())
+        if m.material >= 0:
+            L.giCSetMeshMaterial(h, self.materials[m.material])
+        L.giCSetMeshVisibility(h, int(m.visible))
+        return h
+
+    def create_mesh(self, mesh_desc) -> int:
+        """giCCreateMesh on a live scene with every setter hdGatling runs on a new mesh; the mesh is appended to desc.meshes.  Returns its index.  A topology
+        edit: the next render rebuilds the scene -- or, with OPTION_TOPOLOGY_UPDATES, appends the mesh to the resident scene."""
+        self.meshes.append(self._mesh_handle(mesh_desc))
+        self.desc.meshes.append(mesh_desc)
+        return len(self.meshes) - 1
+
+    def destroy_mesh(self, mesh_index: int):
+        """giCDestroyMesh on a live scene; the entry leaves desc.meshes too (later indices shift down), so desc stays the description a fresh build sees."""
+        self.L.giCDestroyMesh(self.meshes.pop(mesh_index))
+        del self.desc.meshes[mesh_index]
+
+    def topology_update_count(self) -> int:
+        """giCDebugSceneTopologyUpdateCount: how often the scene was brought up to date by an incremental topology update (not counted by update_counts)."""
+        n = C.c_uint64(0)
+        if self.L.giCDebugSceneTopologyUpdateCount(self.handle, C.byref(n)) != GI_C_OK:
+            raise GiError("giCDebugSceneTopologyUpdateCount failed")
+        return int(n.value)
 
     def set_mesh_transform(self, mesh_index: int, matrix):
         """giSetMeshTransform (Gi.h:213): a transform-only edit -- the next render updates the scene incrementally."""

@@ -219,6 +219,23 @@ static uint32_t meshMatFlags(const MaterialRec& mr, uint32_t material, const GiC
   return material | (shadeClassOf(mr) << 24) | (cutoutMat ? (1u << 28) : 0u) | (((m->flipFacing ? 1u : 0u) | (m->doubleSided ? 2u : 0u)) << 30);
 }
 
+// FaceId AOV values of a mesh's faces, bug-compatible: face ids are stored with a 1/2/4-byte stride chosen from maxFaceId (Gi.cpp:878-885); the shader fetches
+// the 32-bit word prim / (4/stride), shifts it by (prim % (4/stride)) * 8 bits (sic) and masks it with (stride*8 - 1) (rp_main.chit:231-240).  Evaluated once
+// per primitive here (buildScene and updateTopology: the one copy of this code)
+static std::vector<int32_t> faceIdAovOf(const GiCMesh* m)
+{
+  std::vector<int32_t> meshFaceIdAov(m->faces.size());
+  const int stride = m->maxFaceId <= 255u ? 1 : (m->maxFaceId <= 65535u ? 2 : 4), invStride = 4 / stride;
+  std::vector<uint8_t> packed(((size_t)m->faces.size() * stride + 3) / 4 * 4, 0);
+  for (size_t i = 0; i < m->faces.size(); i++) { int32_t fid = i < m->faceIds.size() ? m->faceIds[i] : 0; memcpy(&packed[i * stride], &fid, stride); }
+  for (size_t i = 0; i < m->faces.size(); i++) {
+    int32_t word; memcpy(&word, &packed[(i / (size_t)invStride) * 4], 4);
+    word >>= (int)((i % (size_t)invStride) * 8);
+    meshFaceIdAov[i] = word & (stride * 8 - 1);
+  }
+  return meshFaceIdAov;
+}
+
 // the shadow walks' order is chosen anew
 static void resetShadowOrder(GiCScene* s) { s->shadowOrder = -1; s->shadowOrderRays[0] = s->shadowOrderRays[1] = s->shadowOrderSteps[0] = s->shadowOrderSteps[1] = 0; }
 
@@ -546,6 +563,8 @@ int buildScene(GiCScene* s)
   std::unique_ptr<SceneHost> hostPtr(new SceneHost());
   SceneHost& H = *hostPtr;
   s->host.reset(); // (a failed build leaves no stale host copy behind)
+  for (GiCMesh* m : s->retiredMeshes) delete m; // (nothing refers to them any more: updateTopology kept them for the host copy that is gone)
+  s->retiredMeshes.clear();
   for (GiCMesh* m : s->meshes) { m->builtInstances = 0xffffffffu; m->xformDirty = false; m->instDirty.clear(); m->visToggled = false; m->vertsEdited = false; }
   std::vector<FVertex>& verts = H.verts; std::vector<InstanceRec>& instances = H.instances; std::vector<TriRec> tris; std::vector<int32_t> faceIdOf;
   buildMaterialRecords(s, H.mats);
@@ -566,20 +585,7 @@ int buildScene(GiCScene* s)
     const uint32_t vertexOffset = (uint32_t)verts.size();
     appendMeshSceneData(m, *mit, vertexOffset, meshRecs, sceneData);
     for (const GiCVertex& vIn : m->vertices) verts.push_back(packVertex(vIn));
-    // FaceId AOV values, bug-compatible: face ids are stored with a 1/2/4-byte stride chosen from maxFaceId (Gi.cpp:878-885);
-    // the shader fetches the 32-bit word prim / (4/stride), shifts it by (prim % (4/stride)) * 8 bits (sic) and masks it
-    // with (stride*8 - 1) (rp_main.chit:231-240).  Evaluated once per primitive here.
-    std::vector<int32_t> meshFaceIdAov(m->faces.size());
-    {
-      const int stride = m->maxFaceId <= 255u ? 1 : (m->maxFaceId <= 65535u ? 2 : 4), invStride = 4 / stride;
-      std::vector<uint8_t> packed(((size_t)m->faces.size() * stride + 3) / 4 * 4, 0);
-      for (size_t i = 0; i < m->faces.size(); i++) { int32_t fid = i < m->faceIds.size() ? m->faceIds[i] : 0; memcpy(&packed[i * stride], &fid, stride); }
-      for (size_t i = 0; i < m->faces.size(); i++) {
-        int32_t word; memcpy(&word, &packed[(i / (size_t)invStride) * 4], 4);
-        word >>= (int)((i % (size_t)invStride) * 8);
-        meshFaceIdAov[i] = word & (stride * 8 - 1);
-      }
-    }
+    const std::vector<int32_t> meshFaceIdAov = faceIdAovOf(m);
     size_t instCount = m->instanceTransforms.size() / 16;
     m->builtInstances = (uint32_t)instCount;
     meshBuilds.push_back(MeshBuild{m, vertexOffset, matFlags, (uint32_t)instances.size(), (uint32_t)instCount, (uint32_t)tris.size(), meshIdx, meshFaceIdAov});
@@ -676,8 +682,9 @@ int buildScene(GiCScene* s)
 // From then on moving an instance costs: its triangles re-transformed, its subtree rebuilt (a few thousand triangles), the top tree rebuilt (one item per
 // instance), and those ranges uploaded -- not a 10 M-triangle SAH build and a 0.7 GB upload.  Material, assignment, texture and primvar edits have a path of
 // their own (updateMaterials below) that leaves the tree alone, partitioned or not, and so have -- opt-in -- visibility edits (updateVisibility below: ids
-// renumbered in place; a partitioned tree leaves the parts of hidden meshes out of its top tree).  Any other edit (geometry, instance counts and ids, and
-// visibility without the option) raises DIRTY_BVH and the next render rebuilds everything as one tree again.
+// renumbered in place; a partitioned tree leaves the parts of hidden meshes out of its top tree), vertex edits (updateVertices: a refit) and mesh creations
+// and destructions (updateTopology: parts appended and retired).  Any other edit (instance counts and ids of a built mesh, and the opt-in kinds without their
+// option) raises DIRTY_BVH and the next render rebuilds everything as one tree again.
 // ---------------------------------------------------------------------------------------------------------------
 void nodeBounds(const Node8& n, float box[6])
 {
@@ -758,6 +765,36 @@ struct UpdateCost { double buildMs = 0.0, uploadMs = 0.0; }; // what an update s
 // stays with each update: what it counts differs -- the resident triangles, or for a visibility edit the visible ones.)
 static SceneHost* incrementalHost(GiCScene* s) { return optionValue("incremental", 1) ? s->host.get() : nullptr; }
 
+// The one-time re-layout of a flat scene (host-built, device-built or with its host tree dropped): every instance its own subtree + ranges (costs about one
+// full build, in parallel over the instances).  updateTransforms and updateTopology.  False: the scene has no instance, nothing was done; true: the host
+// copy is partitioned and host-built from here on, and the caller sends every array (uploadSceneTo).  With topology updates wanted the top range is twice
+// what the parts need: appended parts find room there.
+static bool relayoutPartitioned(GiCScene* s, SceneHost& H)
+{
+  std::vector<InstPart> parts;
+  for (uint32_t b = 0; b < (uint32_t)H.meshBuilds.size(); b++) {
+    const MeshBuild& mb = H.meshBuilds[b];
+    const uint32_t nf = (uint32_t)mb.m->faces.size();
+    for (uint32_t ii = 0; ii < mb.instCount; ii++) { InstPart P{}; P.meshBuild = b; P.instInMesh = ii; P.triFirst = mb.triFirst + ii * nf; P.nf = nf;
+        parts.push_back(P); }
+  }
+  if (parts.empty()) return false;
+  // (a device-built tree has no host copy, and a vertex update dropped that of a host-built one: placePart fills them)
+  if (H.deviceBuilt || H.hostTreeDropped) { H.bvh.tris.resize(s->triCount); H.triFaceId.resize(s->triCount); H.hostTreeDropped = false; }
+  std::vector<PartBuild> built(parts.size());
+  parallelOver(parts.size(), [&](size_t i) { buildPart(H.meshBuilds[parts[i].meshBuild], parts[i].instInMesh, H.shadePacked, built[i]); });
+  H.topCap = (uint32_t)parts.size() * 2u + 16u; // top nodes <= internal top nodes + one copied root per part
+  if (topologyUpdatesWanted(s)) H.topCap *= 2u;
+  uint32_t off = H.topCap;
+  for (size_t i = 0; i < parts.size(); i++) { const uint32_t n = (uint32_t)built[i].bvh.nodes.size(); parts[i].nodeOff = off;
+      parts[i].nodeCap = n + n / 4u + 8u; off += parts[i].nodeCap; }
+  H.bvh.nodes.assign(off, Node8{});
+  H.parts.swap(parts);
+  parallelOver(H.parts.size(), [&](size_t i) { placePart(H, H.parts[i], built[i]); });
+  H.partitioned = true; H.deviceBuilt = false; // host-built from here on
+  return true;
+}
+
 // handled true: done incrementally; left false: the caller must run a full buildScene (not an error)
 static int updateTransforms(GiCScene* s, bool& handled, UpdateCost& cost)
 {
@@ -769,27 +806,8 @@ static int updateTransforms(GiCScene* s, bool& handled, UpdateCost& cost)
   std::vector<uint32_t> dirtyParts;
   bool converted = false;
   if (!H.partitioned) {
-    // --- one-time re-layout: every instance its own subtree + ranges (costs about one full build, in parallel over the instances)
-    std::vector<InstPart> parts;
-    for (uint32_t b = 0; b < (uint32_t)H.meshBuilds.size(); b++) {
-      const MeshBuild& mb = H.meshBuilds[b];
-      const uint32_t nf = (uint32_t)mb.m->faces.size();
-      for (uint32_t ii = 0; ii < mb.instCount; ii++) { InstPart P{}; P.meshBuild = b; P.instInMesh = ii; P.triFirst = mb.triFirst + ii * nf; P.nf = nf;
-          parts.push_back(P); }
-    }
-    if (parts.empty()) return GI_C_OK;
-    // (a device-built tree has no host copy, and a vertex update dropped that of a host-built one: placePart fills them)
-    if (H.deviceBuilt || H.hostTreeDropped) { H.bvh.tris.resize(s->triCount); H.triFaceId.resize(s->triCount); H.hostTreeDropped = false; }
-    std::vector<PartBuild> built(parts.size());
-    parallelOver(parts.size(), [&](size_t i) { buildPart(H.meshBuilds[parts[i].meshBuild], parts[i].instInMesh, H.shadePacked, built[i]); });
-    H.topCap = (uint32_t)parts.size() * 2u + 16u; // top nodes <= internal top nodes + one copied root per part
-    uint32_t off = H.topCap;
-    for (size_t i = 0; i < parts.size(); i++) { const uint32_t n = (uint32_t)built[i].bvh.nodes.size(); parts[i].nodeOff = off;
-        parts[i].nodeCap = n + n / 4u + 8u; off += parts[i].nodeCap; }
-    H.bvh.nodes.assign(off, Node8{});
-    H.parts.swap(parts);
-    parallelOver(H.parts.size(), [&](size_t i) { placePart(H, H.parts[i], built[i]); });
-    H.partitioned = true; converted = true; H.deviceBuilt = false; // host-built from here on; the upload below sends every array
+    if (!relayoutPartitioned(s, H)) return GI_C_OK;
+    converted = true;
   } else {
     for (uint32_t i = 0; i < (uint32_t)H.parts.size(); i++) {
       const GiCMesh* m = H.meshBuilds[H.parts[i].meshBuild].m;
@@ -849,7 +867,10 @@ static int updateMaterials(GiCScene* s, bool& handled, UpdateCost& cost)
   const double t0 = nowMs();
   { // the same meshes, in the same order, as the built scene holds?
     size_t b = 0;
+    // (a retired mesh -- destroyed, its records still resident until the next build: updateTopology -- is no longer among s->meshes)
+    auto skipRetired = [&] { while (b < H.meshBuilds.size() && H.meshBuilds[b].m->retired) b++; };
     for (const GiCMesh* m : s->meshes) {
+      skipRetired();
       // (a mesh hidden by updateVisibility is still part of the resident scene: its word is patched like any other)
       const bool hiddenInScene = b < H.meshBuilds.size() && H.meshBuilds[b].m == m && H.meshBuilds[b].hidden;
       const bool inScene = (m->visible || hiddenInScene) && !m->faces.empty() && std::find(s->materials.begin(), s->materials.end(), m->material) != s->materials.end();
@@ -858,6 +879,7 @@ static int updateMaterials(GiCScene* s, bool& handled, UpdateCost& cost)
       if (b >= H.meshBuilds.size() || H.meshBuilds[b].m != m || H.meshBuilds[b].instCount != m->builtInstances) return GI_C_OK;
       b++;
     }
+    skipRetired();
     if (b != H.meshBuilds.size() || H.meshRecs.size() != H.meshBuilds.size()) return GI_C_OK;
   }
   if (s->materials.size() > 0x01000000u) { setError("too many materials"); return GI_C_ERROR; }
@@ -868,6 +890,8 @@ static int updateMaterials(GiCScene* s, bool& handled, UpdateCost& cost)
   std::vector<uint8_t> changed(H.meshBuilds.size(), 0);
   uint32_t meshesChanged = 0; uint64_t trisPatched = 0;
   for (MeshBuild& mb : H.meshBuilds) {
+    // a retired mesh is hidden for good and its material may be gone: it keeps its word (never read: no ray reaches its triangles) and an empty record
+    if (mb.m->retired) { meshRecs.push_back(MeshRec{}); wordOfMesh[mb.meshIdx] = mb.matFlags; continue; }
     const uint32_t material = (uint32_t)(std::find(s->materials.begin(), s->materials.end(), mb.m->material) - s->materials.begin());
     const uint32_t word = meshMatFlags(H.mats[material], material, mb.m);
     appendMeshSceneData(mb.m, mb.m->material, mb.vertexOffset, meshRecs, sceneData);
@@ -930,43 +954,43 @@ static bool visibilityUpdatesWanted(const GiCScene* s)
   return o >= 0 ? o == 1 : s->optVisibilityUpdates == 1;
 }
 
-static int updateVisibility(GiCScene* s, bool& handled, UpdateCost& cost)
+// What a new set of hidden meshes does to the resident records (updateVisibility; updateTopology retires meshes through it): per instance, the id base a fresh
+// build of the visible meshes gives it against the one the resident records hold, and what happens to its records.  hide(mb): the mesh is to be hidden.
+struct VisibilityPlan { std::vector<VisPatch> patch; std::vector<uint32_t> newBase; std::vector<uint8_t> hide; uint64_t visibleTris = 0;
+    uint32_t hides = 0, shows = 0, renumbered = 0; bool launch = false; };
+template <class Hide> static bool planVisibility(const SceneHost& H, Hide&& hideOf, VisibilityPlan& P)
 {
-  SceneHost* host = incrementalHost(s);
-  if (!host || s->twoLevel || !host->shadePacked) return GI_C_OK;
-  SceneHost& H = *host;
-  const double t0 = nowMs();
-  for (const GiCMesh* m : s->meshes) if (m->visToggled && m->builtInstances == 0xffffffffu) return GI_C_OK; // no records on the device: showing it rebuilds
-  // --- per instance: the id base a fresh build of the visible meshes gives it against the one the resident records hold, and what happens to its records
-  std::vector<VisPatch> patch(H.instances.size(), VisPatch{0, VIS_KEEP});
-  std::vector<uint32_t> newBase(H.meshBuilds.size(), 0u);
-  uint64_t visibleTris = 0; uint32_t hides = 0, shows = 0, renumbered = 0; bool launch = false;
+  P.patch.assign(H.instances.size(), VisPatch{0, VIS_KEEP}); P.newBase.assign(H.meshBuilds.size(), 0u); P.hide.assign(H.meshBuilds.size(), 0);
   for (const MeshBuild& mb : H.meshBuilds) {
-    if (mb.m->builtInstances != mb.instCount) return GI_C_OK; // (cannot happen: count changes ask for the rebuild)
-    const bool hide = !mb.m->visible;
+    if (mb.m->builtInstances != mb.instCount) return false;
+    const bool hide = hideOf(mb);
+    P.hide[mb.meshIdx] = hide ? 1 : 0;
     // (the ids of a hidden mesh are never read: they stay what they are until it is shown)
-    newBase[mb.meshIdx] = hide ? mb.idBase : (uint32_t)visibleTris;
-    if (!hide) visibleTris += (uint64_t)mb.instCount * mb.m->faces.size();
+    P.newBase[mb.meshIdx] = hide ? mb.idBase : (uint32_t)P.visibleTris;
+    if (!hide) P.visibleTris += (uint64_t)mb.instCount * mb.m->faces.size();
   }
-  if (visibleTris < kIncrementalMinTris) return GI_C_OK; // (the floor: VISIBLE triangles, what a fresh build of the edited scene would hold)
   for (const MeshBuild& mb : H.meshBuilds) {
-    const bool hide = !mb.m->visible;
-    const int32_t delta = (int32_t)(newBase[mb.meshIdx] - mb.idBase);
+    const bool hide = P.hide[mb.meshIdx] != 0;
+    const int32_t delta = (int32_t)(P.newBase[mb.meshIdx] - mb.idBase);
     // a partitioned tree drops the parts from its top tree: their records stay whole
     const uint32_t action = hide == mb.hidden || H.partitioned ? VIS_KEEP : (hide ? VIS_HIDE : VIS_SHOW);
-    if (hide != mb.hidden) { if (hide) hides++; else shows++; }
-    if (delta != 0) renumbered++;
-    if (delta != 0 || action != VIS_KEEP) { launch = true; for (uint32_t ii = 0; ii < mb.instCount; ii++) patch[mb.instFirst + ii] = VisPatch{delta, action}; }
+    if (hide != mb.hidden) { if (hide) P.hides++; else P.shows++; }
+    if (delta != 0) P.renumbered++;
+    if (delta != 0 || action != VIS_KEEP) { P.launch = true; for (uint32_t ii = 0; ii < mb.instCount; ii++) P.patch[mb.instFirst + ii] = VisPatch{delta, action}; }
   }
-  // --- host: the triangles' host copies where they exist (host-built and partitioned trees; a later transform update uploads from them), the top tree of a
-  // partitioned scene, the class masks and the cutout flag over the visible meshes
-  if (launch && !H.bvh.tris.empty()) {
+  return true;
+}
+// ... applied to the triangles' host copies where they exist (host-built and partitioned trees; a later transform update uploads from them) and to the state
+// the MeshBuilds keep; the device's records take the same table through k_patch_visibility
+static void applyVisibilityPlanOnHost(SceneHost& H, const VisibilityPlan& P)
+{
+  if (P.launch && !H.bvh.tris.empty()) {
     constexpr size_t CHUNK = 65536;
     const size_t n = H.bvh.tris.size();
     parallelOver((n + CHUNK - 1) / CHUNK, [&](size_t c) {
       for (size_t i = c * CHUNK; i < std::min(n, (c + 1) * CHUNK); i++) {
         TriRec& t = H.bvh.tris[i];
-        const VisPatch vp = patch[t.instance];
+        const VisPatch vp = P.patch[t.instance];
         t.origId += (uint32_t)vp.idDelta;
         if (vp.action == VIS_HIDE) for (int a = 0; a < 3; a++) { t.e1[a] = 0.0f; t.e2[a] = 0.0f; }
         else if (vp.action == VIS_SHOW) {
@@ -977,13 +1001,30 @@ static int updateVisibility(GiCScene* s, bool& handled, UpdateCost& cost)
       }
     });
   }
-  for (MeshBuild& mb : H.meshBuilds) { mb.hidden = !mb.m->visible; mb.idBase = newBase[mb.meshIdx]; }
+  for (MeshBuild& mb : H.meshBuilds) { mb.hidden = P.hide[mb.meshIdx] != 0; mb.idBase = P.newBase[mb.meshIdx]; }
+}
+
+static int updateVisibility(GiCScene* s, bool& handled, UpdateCost& cost)
+{
+  SceneHost* host = incrementalHost(s);
+  if (!host || s->twoLevel || !host->shadePacked) return GI_C_OK;
+  SceneHost& H = *host;
+  const double t0 = nowMs();
+  for (const GiCMesh* m : s->meshes) if (m->visToggled && m->builtInstances == 0xffffffffu) return GI_C_OK; // no records on the device: showing it rebuilds
+  VisibilityPlan plan;
+  if (!planVisibility(H, [](const MeshBuild& mb) { return !mb.m->visible; }, plan)) return GI_C_OK; // (cannot happen: count changes ask for the rebuild)
+  if (plan.visibleTris < kIncrementalMinTris) return GI_C_OK; // (the floor: VISIBLE triangles, what a fresh build of the edited scene would hold)
+  const std::vector<VisPatch>& patch = plan.patch;
+  const uint64_t visibleTris = plan.visibleTris; const uint32_t hides = plan.hides, shows = plan.shows, renumbered = plan.renumbered; const bool launch = plan.launch;
+  applyVisibilityPlanOnHost(H, plan);
   const bool topChanged = H.partitioned && (hides || shows);
   if (topChanged) {
     if (rebuildTop(s, H) != GI_C_OK) return GI_C_ERROR;
     setSceneBounds(s, H.bvh.nodes);
   }
-  deriveSceneClasses(s, H, false); // (words and table of the last sync; a material edit that is due as well runs behind this update)
+  // words and table of the last sync; a material edit that is due as well runs behind this update and derives the classes itself -- and must: an
+  // updateTopology in front of this update has then already replaced H.mats by the current table, which the resident words do not index yet
+  if (!(s->dirty & DIRTY_MATERIALS)) deriveSceneClasses(s, H, false);
   const double t1 = nowMs();
   // --- every device of the scene, on its own stream: the table and the patch kernel, the top tree of a partitioned scene.  Nothing when no word changes
   if (onSceneDevices(s, launch || topChanged ? residentDeviceCount(s) : 0u, [&](SceneDevice& D, hipStream_t st) -> int {
@@ -1184,6 +1225,295 @@ static int updateVertices(GiCScene* s, bool& handled, UpdateCost& cost)
   return GI_C_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Incremental topology updates (opt-in: GI_C_SCENE_OPTION_TOPOLOGY_UPDATES / GATLING_OPTIONS=topology_updates=1).  Meshes were created or destroyed (what
+// hdGatling does on every points, primvar or topology change of a prim: giDestroyMesh, giCreateMesh and every setter again, mesh.cpp:458-509); nothing else
+// asked for the rebuild.  The partitioned layout already gives every flattened instance its own subtree and ranges under a rebuilt top tree, so the SET of
+// parts may change as well:
+//   re-layout: a flat scene (host-built, device-built, host tree dropped) is first re-laid out as updateTransforms does (relayoutPartitioned) and sent whole.
+//   retire:    a destroyed mesh of the built scene was kept (GiCMesh::retired, GiCScene::retiredMeshes).  Its MeshBuild becomes hidden for good: its parts
+//              drop out of the top tree and the meshes behind it are renumbered -- updateVisibility's plan, host pass and k_patch_visibility.  Its records
+//              stay resident until the next buildScene, which frees the mesh too.
+//   append:    every mesh a fresh build would hold that has no MeshBuild gets one at the ends of the arrays (vertices, shading records, instances, triangles,
+//              face ids, one node range per instance with the usual reserve), made by the code buildScene runs.  Its parts are built by buildPart / placePart
+//              in parallel, or -- with the scene's device builder on (GI_C_SCENE_OPTION_BVH_BUILD / device_build) and at least device_parts_min faces -- where
+//              they live: buildBvh8Device over the part's own records, then k_place_part (gi_patch.hip).  The host copy of a device-built part holds its
+//              records in scene order and only the root of its subtree: the interior is stale on the host and never read, as after a vertex refit -- the
+//              only upload of a part's node range follows placePart, which rewrites it.
+//   device:    the arrays grow in place (DeviceBuffer::grow: contents kept, 25 % slack); only the appended ranges, the top tree, the mesh records and the
+//              scene data are sent.
+// The image is that of a fresh build: the only thing of the tree that reaches an image is the scene-order triangle id, and an appended mesh lies behind every
+// live built mesh, so its ids are the visible triangles in front of it.
+// Falls back to buildScene (handled = false, not an error): no host copy, GATLING_OPTIONS=incremental=0, the two-level layout, a scene within LDS, fewer
+// than kIncrementalMinTris visible triangles after the edit, an appended mesh with a position that is not finite or beyond 1e18 in object or world space (or
+// an unusable instance transform), a mesh to append in front of a live built mesh, the top tree outgrowing its range, 2^26 resident triangles, more retired
+// triangles than live ones (resident memory stays within twice the live scene, and the rebuild that compacts it is amortised), a flat scene that retires more
+// than it keeps of what was built (the re-layout would not pay), out of device memory.
+// ---------------------------------------------------------------------------------------------------------------
+bool topologyUpdatesWanted(const GiCScene* s)
+{
+  const long o = optionValue("topology_updates", -1);
+  return o >= 0 ? o == 1 : s->optTopologyUpdates == 1;
+}
+// faces from which an appended part is built on the device when the scene's device builder is on (GATLING_OPTIONS=device_parts_min).  Measured for ONE part
+// (tools/time_topology_edit.py): buildPart 0.57 / 1.2 / 2.4 / 5.0 / 11.3 ms at 1 / 2 / 4 / 8 / 16 Ki faces, the device route 2.1 / 2.3 /
+// 2.4 / 3.1 / 3.2 ms (a floor of ~2 ms of launches and stream synchronisations): they cross at 4 Ki.  Several parts are built in parallel by the host and
+// one after another on the device, so an edit of many mid-sized parts is faster on the host (C5, 8 parts of 5 120 faces: 5 ms against 21 ms)
+constexpr long kDevicePartsMinDefault = 4096;
+
+static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
+{
+  SceneHost* host = incrementalHost(s);
+  if (!host || s->twoLevel || !host->shadePacked) return GI_C_OK;
+  SceneHost& H = *host;
+  if (H.meshRecs.size() != H.meshBuilds.size()) return GI_C_OK;
+  for (const MeshBuild& mb : H.meshBuilds) if (mb.m->builtInstances != mb.instCount) return GI_C_OK; // (cannot happen: count changes ask for the rebuild)
+  const double t0 = nowMs();
+  // --- the meshes to append: what a fresh build would hold and the resident scene does not, all of them behind every live built mesh
+  struct NewMesh { GiCMesh* m; uint32_t material; };
+  std::vector<NewMesh> fresh;
+  uint64_t appendedTris = 0, appendedParts = 0;
+  for (GiCMesh* m : s->meshes) {
+    if (m->builtInstances != 0xffffffffu) { if (!fresh.empty()) return GI_C_OK; continue; }
+    if (!m->visible || m->faces.empty()) continue; // (as buildScene)
+    auto mit = std::find(s->materials.begin(), s->materials.end(), m->material);
+    if (mit == s->materials.end()) continue;
+    const uint32_t material = (uint32_t)(mit - s->materials.begin());
+    if (material > 0x00ffffffu) return GI_C_OK;
+    if (!usableVertexPositions(m->vertices.data(), m->vertices.size())) return GI_C_OK;
+    fresh.push_back(NewMesh{m, material});
+    const uint64_t instCount = m->instanceTransforms.size() / 16;
+    appendedTris += instCount * m->faces.size(); appendedParts += instCount;
+  }
+  // --- what the scene holds after the edit
+  uint64_t live = appendedTris, retired = 0, visible = appendedTris, partsNow = 0; uint32_t retiring = 0;
+  for (const MeshBuild& mb : H.meshBuilds) {
+    const uint64_t n = (uint64_t)mb.instCount * mb.m->faces.size();
+    partsNow += mb.instCount;
+    if (mb.m->retired) { retired += n; if (!mb.hidden) retiring++; } else { live += n; if (!mb.hidden) visible += n; }
+  }
+  if (visible < kIncrementalMinTris || retired > live || partsNow == 0u) return GI_C_OK;
+  // a flat scene that loses more than it keeps: the re-layout would spend its time on subtrees for what is leaving (measured on C3, one mesh resynced: 809 ms
+  // against the 580 ms of the build that follows anyway once the retired triangles outnumber the live ones)
+  if (!H.partitioned && retired > live - appendedTris) return GI_C_OK;
+  if ((uint64_t)s->triCount + appendedTris >= ((uint64_t)1 << 26)) return GI_C_OK;
+  const uint64_t topCap = H.partitioned ? H.topCap : (partsNow * 2u + 16u) * 2u; // (what relayoutPartitioned reserves)
+  if (appendedParts && (partsNow + appendedParts) * 2u + 16u > topCap) return GI_C_OK; // the top tree may outgrow its range
+  const uint32_t nDev = residentDeviceCount(s);
+  const bool timing = getenv("GATLING_BUILD_TIMING") != nullptr;
+  if (fresh.empty() && retiring == 0u) { // the edited meshes are not part of a fresh build either (invisible, no faces, no valid material)
+    for (GiCMesh* m : s->meshes) if (m->builtInstances == 0xffffffffu) { m->visToggled = false; m->vertsEdited = false; }
+    handled = true;
+    return GI_C_OK;
+  }
+  // --- a flat scene: re-laid out and sent whole first
+  bool converted = false;
+  if (!H.partitioned) {
+    if (!relayoutPartitioned(s, H)) return GI_C_OK;
+    converted = true;
+    s->nodeCount = (uint32_t)H.bvh.nodes.size();
+    if (onSceneDevices(s, nDev, [&](SceneDevice& D, hipStream_t st) { return uploadSceneTo(s, D, H, st); }) != GI_C_OK) return GI_C_ERROR;
+  }
+  if (H.bvh.tris.size() != s->triCount || H.triFaceId.size() != s->triCount) return GI_C_OK; // (cannot happen: a partitioned scene keeps its host triangles)
+  double buildMs = converted ? nowMs() - t0 : 0.0;
+  // --- retire: hidden for good, the meshes behind renumbered
+  VisibilityPlan plan;
+  if (!planVisibility(H, [](const MeshBuild& mb) { return mb.hidden || mb.m->retired; }, plan)) return GI_C_OK;
+  applyVisibilityPlanOnHost(H, plan);
+  const uint32_t oldTris = s->triCount, oldInstances = (uint32_t)H.instances.size();
+  // --- append, host side: the MeshBuilds and everything that does not depend on a tree
+  if (s->dirty & DIRTY_MATERIALS) buildMaterialRecords(s, H.mats); // the new meshes' words come from the current table; updateMaterials runs behind this update
+  const size_t vert0 = H.verts.size(), shade0 = H.triShade.size(), node0 = H.bvh.nodes.size(), part0 = H.parts.size();
+  uint64_t idBase = plan.visibleTris; // the visible triangles in front of the next appended mesh
+  for (const NewMesh& nm : fresh) {
+    GiCMesh* m = nm.m;
+    const uint32_t matFlags = meshMatFlags(H.mats[nm.material], nm.material, m);
+    const uint32_t vertexOffset = (uint32_t)H.verts.size(), meshIdx = (uint32_t)H.meshBuilds.size();
+    const uint32_t instCount = (uint32_t)(m->instanceTransforms.size() / 16), nf = (uint32_t)m->faces.size(), triFirst = (uint32_t)H.bvh.tris.size();
+    appendMeshSceneData(m, m->material, vertexOffset, H.meshRecs, H.sceneData);
+    for (const GiCVertex& vIn : m->vertices) H.verts.push_back(packVertex(vIn));
+    H.meshBuilds.push_back(MeshBuild{m, vertexOffset, matFlags, (uint32_t)H.instances.size(), instCount, triFirst, meshIdx, faceIdAovOf(m)});
+    H.meshBuilds.back().shadeBase = (uint32_t)H.triShade.size(); H.meshBuilds.back().idBase = (uint32_t)idBase;
+    for (const GiCFace& f : m->faces) H.triShade.push_back(packTriShade(m, f, vertexOffset));
+    // (25 % slack, as on the device: a std::vector would double 0.7 GB of triangles on the first append to C5 and copy them on every later doubling)
+    auto grown = [](auto& v, size_t n) { if (v.capacity() < n) v.reserve(n + n / 4u); v.resize(n); };
+    grown(H.instances, H.instances.size() + instCount); grown(H.bvh.tris, (size_t)triFirst + (size_t)instCount * nf); grown(H.triFaceId, H.bvh.tris.size());
+    for (uint32_t ii = 0; ii < instCount; ii++) { InstPart P{}; P.meshBuild = meshIdx; P.instInMesh = ii; P.triFirst = triFirst + ii * nf; P.nf = nf;
+        H.parts.push_back(P); }
+    idBase += (uint64_t)instCount * nf;
+  }
+  // --- the new parts: built on the host here, or flattened for the device builder
+  const long wantDevice = optionValue("device_build", -1);
+  const bool deviceParts = wantDevice < 0 ? s->optBvhBuild == 1 : wantDevice == 1;
+  const size_t devicePartsMin = (size_t)std::max(optionValue("device_parts_min", kDevicePartsMinDefault), 1L);
+  struct NewPart { bool onDevice = false, ok = true; PartBuild built; std::vector<TriRec> flat; DeviceBvhResult dev; };
+  std::vector<NewPart> newParts(H.parts.size() - part0);
+  const double tb0 = nowMs();
+  parallelOver(newParts.size(), [&](size_t k) {
+    NewPart& np = newParts[k];
+    const InstPart& P = H.parts[part0 + k];
+    const MeshBuild& mb = H.meshBuilds[P.meshBuild];
+    np.onDevice = deviceParts && P.nf >= devicePartsMin && P.nf > 128u; // (more than 128 faces: the size from which the scene's own device build runs)
+    if (!np.onDevice) { buildPart(mb, P.instInMesh, true, np.built); np.ok = np.built.bvh.activeTris == P.nf; return; }
+    // (ids from 0, as buildPart: k_place_part adds the instance's base)
+    np.built.inst = makeInstanceRec(mb.m, mb.meshIdx, P.instInMesh);
+    np.flat.resize(P.nf);
+    flattenInstance(np.built.inst, mb.instFirst + P.instInMesh, mb.m, mb.vertexOffset, mb.matFlags, 0u, mb.shadeBase, np.flat.data());
+    for (const TriRec& t : np.flat) // inactive by the builders' rule (bvh8.cpp prepareRange)
+      for (int a = 0; a < 3; a++) np.ok = np.ok && usableCoordinate(t.v0[a]) && usableCoordinate(t.v0[a] + t.e1[a]) && usableCoordinate(t.v0[a] + t.e2[a]);
+  });
+  for (const NewPart& np : newParts) if (!np.ok) return GI_C_OK; // a fresh build would leave triangles out of the tree
+  buildMs += nowMs() - tb0;
+  // --- devices, first pass: the arrays grown, what does not depend on node ranges sent, the retired meshes' patch, the device builder over its parts
+  std::vector<std::vector<Node8*>> partNodes(nDev, std::vector<Node8*>(newParts.size(), nullptr)); // the builder's blocks, per device
+  auto freePartNodes = [&] { for (auto& v : partNodes) for (Node8*& p : v) if (p) { (void)hipFree(p); p = nullptr; } };
+  bool outOfMemory = false; double deviceBuildMs = 0.0; uint32_t builtOnDevice = 0;
+  int rc = onSceneDevices(s, nDev, [&](SceneDevice& D, hipStream_t st) -> int {
+    if (D.slot >= nDev) { setError("internal: device slot out of range"); return GI_C_ERROR; }
+    if (D.dTris.count < oldTris || D.dInstances.count < oldInstances || D.dTriShade.count < shade0 || D.dVerts.count < vert0 || D.dTriFaceId.count < oldTris ||
+        D.dNodes.count < node0) { setError("internal: the device holds less than the scene"); return GI_C_ERROR; }
+    std::vector<void*> old; DeviceBuffer<VisPatch> dPatch;
+    int r = D.dVerts.grow(H.verts.size(), st, old);
+    if (r == GI_C_OK) r = D.dTriShade.grow(H.triShade.size(), st, old);
+    if (r == GI_C_OK) r = D.dInstances.grow(H.instances.size(), st, old);
+    if (r == GI_C_OK) r = D.dTris.grow(H.bvh.tris.size(), st, old);
+    if (r == GI_C_OK) r = D.dTriFaceId.grow(H.triFaceId.size(), st, old);
+    if (r == GI_C_OUT_OF_MEMORY_INTERNAL) { outOfMemory = true; r = DEVICE_BUILD_FALLBACK; }
+    auto copy = [&](void* dst, const void* src, size_t bytes) {
+      if (r == GI_C_OK && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) != hipSuccess) { setError("topology update: copy failed"); r = GI_C_ERROR; } };
+    copy(D.dVerts.ptr + vert0, H.verts.data() + vert0, (H.verts.size() - vert0) * sizeof(FVertex));
+    copy(D.dTriShade.ptr + shade0, H.triShade.data() + shade0, (H.triShade.size() - shade0) * sizeof(TriShade));
+    if (r == GI_C_OK && plan.launch) {
+      if (dPatch.upload(plan.patch, st)) r = GI_C_ERROR;
+      else launchPatchVisibility(st, D.dTris.ptr, oldTris, D.dInstances.ptr, oldInstances, dPatch.ptr, D.dTriShade.ptr, (uint32_t)H.triShade.size());
+    }
+    for (size_t k = 0; k < newParts.size() && r == GI_C_OK; k++) {
+      NewPart& np = newParts[k];
+      if (!np.onDevice) continue;
+      const InstPart& P = H.parts[part0 + k];
+      const MeshBuild& mb = H.meshBuilds[P.meshBuild];
+      if ((size_t)P.triFirst + P.nf > D.dTris.count || (size_t)P.triFirst + P.nf > D.dTriFaceId.count) { setError("internal: part outside the arrays"); r = GI_C_ERROR; break; }
+      copy(D.dTris.ptr + P.triFirst, np.flat.data(), (size_t)P.nf * sizeof(TriRec));
+      copy(D.dTriFaceId.ptr + P.triFirst, mb.faceIdAov.data(), (size_t)P.nf * sizeof(int32_t));
+      if (r != GI_C_OK) break;
+      const double ta = nowMs();
+      DeviceBvhResult res;
+      const int built = buildBvh8Device(st, D.dTris.ptr + P.triFirst, D.dTriFaceId.ptr + P.triFirst, P.nf, kMaxBvhDepth, res);
+      deviceBuildMs += nowMs() - ta;
+      if (built == DEVICE_BVH_OUT_OF_MEMORY || built == DEVICE_BVH_TOO_DEEP) {
+        // the first device decides for all: buildPart takes the part over (its records are sent anew); a later device that cannot follow gives the edit up
+        if (D.slot == 0u) { np.onDevice = false; continue; }
+        outOfMemory = true; r = DEVICE_BUILD_FALLBACK; break;
+      }
+      if (built != DEVICE_BVH_OK) { setError(std::string("device BVH build of an appended part failed: ") + res.error); r = GI_C_ERROR; break; }
+      partNodes[D.slot][k] = res.nodes;
+      if (res.activeTris != P.nf) { setError("internal: device and host disagree on the inactive triangles of an appended part"); r = GI_C_ERROR; break; }
+      if (D.slot == 0u) { np.dev = res; builtOnDevice++; }
+      else if (res.nodeCount != np.dev.nodeCount || res.maxDepth != np.dev.maxDepth) { setError("internal: device BVH builds differ between devices"); r = GI_C_ERROR; break; }
+    }
+    if (r == GI_C_OK && (hipGetLastError() != hipSuccess)) { setError("topology update: launch failed"); r = GI_C_ERROR; }
+    if (hipStreamSynchronize(st) != hipSuccess && r == GI_C_OK) { setError("topology update: device error"); r = GI_C_ERROR; }
+    dPatch.release();
+    for (void* p : old) (void)hipFree(p); // (the copies out of the old blocks are done)
+    return r;
+  });
+  if (rc != GI_C_OK) {
+    freePartNodes();
+    if (rc == DEVICE_BUILD_FALLBACK && outOfMemory) {
+      if (timing) fprintf(stderr, "[gatling_gi] topology update: out of device memory; the scene is rebuilt\n");
+      return GI_C_OK;
+    }
+    return GI_C_ERROR;
+  }
+  buildMs += deviceBuildMs;
+  // --- host: parts the device builder gave back, node ranges at the end of the node array, the parts placed, the top tree
+  const double tb1 = nowMs();
+  for (size_t k = 0; k < newParts.size(); k++) {
+    NewPart& np = newParts[k];
+    if (np.onDevice || !np.built.bvh.nodes.empty()) continue;
+    const InstPart& P = H.parts[part0 + k];
+    buildPart(H.meshBuilds[P.meshBuild], P.instInMesh, true, np.built);
+    if (np.built.bvh.activeTris != P.nf) { freePartNodes(); return GI_C_OK; }
+  }
+  buildMs += nowMs() - tb1;
+  size_t off = node0;
+  for (size_t k = 0; k < newParts.size(); k++) {
+    InstPart& P = H.parts[part0 + k];
+    const uint32_t n = newParts[k].onDevice ? newParts[k].dev.nodeCount : (uint32_t)newParts[k].built.bvh.nodes.size();
+    P.nodeOff = (uint32_t)off; P.nodeCap = n + n / 4u + 8u; off += P.nodeCap;
+  }
+  if (off * sizeof(Node8) >= ((size_t)1 << 32)) { freePartNodes(); return GI_C_OK; } // (the flat walk addresses nodes by 32-bit byte offset)
+  H.bvh.nodes.resize(off, Node8{});
+  parallelOver(newParts.size(), [&](size_t k) {
+    const NewPart& np = newParts[k];
+    InstPart& P = H.parts[part0 + k];
+    if (!np.onDevice) { placePart(H, P, np.built); return; }
+    // a device-built part: the root (rebased as k_place_part rebases it) for the top tree, the records in scene order with their final ids -- the order
+    // differs from the device's leaf order, and nothing uploads these records before a placePart has rewritten them
+    const MeshBuild& mb = H.meshBuilds[P.meshBuild];
+    P.nodeCount = np.dev.nodeCount; P.depth = np.dev.maxDepth; P.activeTris = np.dev.activeTris; P.levelStart = np.dev.levelStart;
+    Node8 root = np.dev.root; root.childBase += P.nodeOff; root.triBase += P.triFirst;
+    H.bvh.nodes[P.nodeOff] = root;
+    for (uint32_t f = 0; f < P.nf; f++) { TriRec t = np.flat[f]; t.origId += mb.idBase + P.instInMesh * P.nf; H.bvh.tris[P.triFirst + f] = t;
+        H.triFaceId[P.triFirst + f] = mb.faceIdAov[f]; }
+    H.instances[mb.instFirst + P.instInMesh] = np.built.inst;
+    nodeBounds(root, P.box);
+  });
+  if (rebuildTop(s, H) != GI_C_OK) { freePartNodes(); return GI_C_ERROR; }
+  setSceneBounds(s, H.bvh.nodes);
+  // (with a material edit due as well the resident words index the previous table: updateMaterials derives the classes behind this update)
+  if (!(s->dirty & DIRTY_MATERIALS)) deriveSceneClasses(s, H, false);
+  for (const NewMesh& nm : fresh) { nm.m->builtInstances = (uint32_t)(nm.m->instanceTransforms.size() / 16); nm.m->xformDirty = false; nm.m->instDirty.clear(); }
+  // (hdGatling calls the visibility setter on every new mesh; a mesh that stays out of the scene has nothing to toggle or refit)
+  for (const NewMesh& nm : fresh) { nm.m->visToggled = false; nm.m->vertsEdited = false; }
+  for (GiCMesh* m : s->meshes) if (m->builtInstances == 0xffffffffu) { m->visToggled = false; m->vertsEdited = false; }
+  s->triCount = (uint32_t)H.bvh.tris.size(); s->nodeCount = (uint32_t)H.bvh.nodes.size();
+  // --- devices, second pass: the node array grown, the new ranges, the device-built parts placed, the top tree, the small tables
+  rc = onSceneDevices(s, nDev, [&](SceneDevice& D, hipStream_t st) -> int {
+    std::vector<void*> old;
+    int r = D.dNodes.grow(H.bvh.nodes.size(), st, old);
+    if (r == GI_C_OUT_OF_MEMORY_INTERNAL) { outOfMemory = true; r = DEVICE_BUILD_FALLBACK; }
+    auto copy = [&](void* dst, const void* src, size_t bytes) {
+      if (r == GI_C_OK && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) != hipSuccess) { setError("topology update: copy failed"); r = GI_C_ERROR; } };
+    // (the whole new node range, reserves included: zeros where no node lives; k_place_part then writes the device-built parts over their ranges)
+    copy(D.dNodes.ptr + node0, H.bvh.nodes.data() + node0, (H.bvh.nodes.size() - node0) * sizeof(Node8));
+    copy(D.dInstances.ptr + oldInstances, H.instances.data() + oldInstances, (H.instances.size() - oldInstances) * sizeof(InstanceRec));
+    for (size_t k = 0; k < newParts.size() && r == GI_C_OK; k++) {
+      const InstPart& P = H.parts[part0 + k];
+      if ((size_t)P.nodeOff + P.nodeCount > D.dNodes.count || (size_t)P.triFirst + P.nf > D.dTris.count || (size_t)P.triFirst + P.nf > D.dTriFaceId.count) {
+        setError("internal: part outside the arrays"); r = GI_C_ERROR; break; }
+      if (newParts[k].onDevice) {
+        const MeshBuild& mb = H.meshBuilds[P.meshBuild];
+        launchPlacePart(st, partNodes[D.slot][k], P.nodeCount, D.dNodes.ptr, P.nodeOff, D.dTris.ptr, P.triFirst, P.nf, mb.idBase + P.instInMesh * P.nf);
+      } else {
+        copy(D.dTris.ptr + P.triFirst, &H.bvh.tris[P.triFirst], (size_t)P.nf * sizeof(TriRec));
+        copy(D.dTriFaceId.ptr + P.triFirst, &H.triFaceId[P.triFirst], (size_t)P.nf * sizeof(int32_t));
+      }
+    }
+    if (r == GI_C_OK && uploadTopTree(D, H, st) != GI_C_OK) r = GI_C_ERROR;
+    if (r == GI_C_OK && (D.dMeshes.upload(H.meshRecs, st) || D.dSceneData.upload(H.sceneData, st))) r = GI_C_ERROR;
+    if (r == GI_C_OK && hipGetLastError() != hipSuccess) { setError("topology update: launch failed"); r = GI_C_ERROR; }
+    if (hipStreamSynchronize(st) != hipSuccess && r == GI_C_OK) { setError("topology update: device error"); r = GI_C_ERROR; }
+    for (Node8*& p : partNodes[D.slot]) if (p) { (void)hipFree(p); p = nullptr; } // the builder's blocks
+    for (void* p : old) (void)hipFree(p);
+    return r;
+  });
+  freePartNodes();
+  if (rc == DEVICE_BUILD_FALLBACK && outOfMemory) {
+    if (timing) fprintf(stderr, "[gatling_gi] topology update: out of device memory; the scene is rebuilt\n");
+    return GI_C_OK;
+  }
+  if (rc != GI_C_OK) return GI_C_ERROR;
+  const double t2 = nowMs();
+  cost.buildMs = buildMs; cost.uploadMs = std::max(t2 - t0 - buildMs, 0.0);
+  if (timing) fprintf(stderr, "[gatling_gi] topology update:%s %u mesh(es) retired, %zu appended, %zu part(s) built, %u of them on the device (k_place_part), "
+                              "%llu live + %llu retired triangle(s), %u resident, builds %.2f ms, rest %.2f ms\n", converted
+                                  ? " scene re-laid out as per-instance subtrees," : "", retiring, fresh.size(), newParts.size(), builtOnDevice,
+                      (unsigned long long)live, (unsigned long long)retired, s->triCount, cost.buildMs, cost.uploadMs);
+  handled = true;
+  return GI_C_OK;
+}
+
 // brings the device scene up to date with the host-side edits: incremental for DIRTY_BVH raised by vertex edits alone (opt-in: the tree refitted on the
 // device), by visibility toggles alone (opt-in: ids renumbered, the
 // toggled meshes' triangles hidden / shown in place), for material-side edits alone (the small arrays + one word per triangle) and for transform edits alone
@@ -1207,10 +1537,17 @@ int syncSceneGeometry(GiCScene* s)
   // DIRTY_BVH without rebuildDue: visibility toggles and vertex edits alone raised it.  Each kind needs its option, else the rebuild is due; a vertex update
   // that declines makes it due as well (the visibility update behind it must not clear the flag).  With both kinds due the vertex update leaves DIRTY_BVH to
   // the visibility update.
+  // DIRTY_BVH with topologyDue: meshes were created or destroyed, or meshes outside the built scene edited.  Without the option that is the rebuild, in today's
+  // order of events.  With it updateTopology runs in front of every other path (the meshes it appends are part of the scene for them) and clears DIRTY_BVH
+  // unless toggles or vertex edits of other meshes are due as well; a decline makes the rebuild due.
+  if (s->topologyDue && !topologyUpdatesWanted(s)) s->rebuildDue = true;
+  const bool topologyRuns = (s->dirty & DIRTY_BVH) && !s->rebuildDue && s->topologyDue;
+  int rc = run(topologyRuns, updateTopology, UPDATE_TOPOLOGY, 0u, DIRTY_BVH, 0u);
   bool anyVis = false, anyVerts = false;
   for (const GiCMesh* m : s->meshes) { anyVis = anyVis || m->visToggled; anyVerts = anyVerts || m->vertsEdited; }
+  if (rc == GI_C_OK && topologyRuns && !s->rebuildDue && !anyVis && !anyVerts) s->dirty &= ~DIRTY_BVH;
   if ((s->dirty & DIRTY_BVH) && anyVerts && (!vertexUpdatesWanted(s) || (anyVis && !visibilityUpdatesWanted(s)))) s->rebuildDue = true;
-  int rc = run((s->dirty & DIRTY_BVH) && !s->rebuildDue && anyVerts, updateVertices, UPDATE_VERTEX, anyVis ? 0u : (uint32_t)DIRTY_BVH, DIRTY_BVH, 0u);
+  if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_BVH) && !s->rebuildDue && anyVerts, updateVertices, UPDATE_VERTEX, anyVis ? 0u : (uint32_t)DIRTY_BVH, DIRTY_BVH, 0u);
   if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_BVH) && !s->rebuildDue && visibilityUpdatesWanted(s), updateVisibility, UPDATE_VISIBILITY, DIRTY_BVH, 0u, 0u);
   if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_MATERIALS) && !(s->dirty & DIRTY_BVH), updateMaterials, UPDATE_MATERIAL, DIRTY_MATERIALS, DIRTY_BVH, DIRTY_BVH);
   if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_XFORM) && !(s->dirty & (DIRTY_BVH | DIRTY_MATERIALS)), updateTransforms, UPDATE_TRANSFORM, 0u, DIRTY_BVH, 0u);
@@ -1223,7 +1560,7 @@ int syncSceneGeometry(GiCScene* s)
     s->updateCounts[UPDATE_FULL]++;
     s->dirty &= ~(DIRTY_BVH | DIRTY_MATERIALS); s->dirty |= DIRTY_FRAMEBUFFER;
   }
-  s->dirty &= ~DIRTY_XFORM; s->rebuildDue = false;
+  s->dirty &= ~DIRTY_XFORM; s->rebuildDue = false; s->topologyDue = false;
   for (GiCMesh* m : s->meshes) { m->visToggled = false; m->vertsEdited = false; }
   return GI_C_OK;
 }

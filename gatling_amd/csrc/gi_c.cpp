@@ -342,6 +342,8 @@ int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value)
   // (no dirty flag: the option decides how FUTURE visibility edits are applied)
   if (option == GI_C_SCENE_OPTION_VISIBILITY_UPDATES) { scene->optVisibilityUpdates = value == 1 ? 1 : 0; return GI_C_OK; }
   if (option == GI_C_SCENE_OPTION_VERTEX_UPDATES) { scene->optVertexUpdates = value == 1 ? 1 : 0; return GI_C_OK; } // (likewise: future vertex edits)
+  // (likewise: future mesh creations and destructions)
+  if (option == GI_C_SCENE_OPTION_TOPOLOGY_UPDATES) { scene->optTopologyUpdates = value == 1 ? 1 : 0; return GI_C_OK; }
   setError("unknown scene option"); return GI_C_ERROR;
 }
 

@@ -83,7 +83,9 @@ static int giCTraceRaysImpl(GiCScene* s, uint32_t count, const float* origins, c
 // ---------------------------------------------------------------------------------------------------------------
 // giCDebugValidateBvh: host-only check of the builder's conservativeness contract
 // ---------------------------------------------------------------------------------------------------------------
-static int validateTree(const std::vector<Node8>& nodes, const std::vector<TriRec>& trisArr, uint32_t triCount)
+// `left`: per record, nonzero where the record belongs to a part that was left out of the top tree (a hidden or retired mesh of a partitioned scene): no leaf
+// may reference it, and its id -- stale, never read -- is not one of the `triCount` live ones
+static int validateTree(const std::vector<Node8>& nodes, const std::vector<TriRec>& trisArr, uint32_t triCount, const std::vector<uint8_t>* left = nullptr)
 {
   int violations = 0;
   std::vector<uint8_t> seen(triCount, 0);
@@ -117,7 +119,7 @@ static int validateTree(const std::vector<Node8>& nodes, const std::vector<TriRe
         if (cnt == 0u || off + cnt > 24u) { violations++; continue; }
         for (uint32_t k = 0; k < cnt; k++) {
           uint32_t ti = n.triBase + off + k;
-          if (ti >= trisArr.size()) { violations++; continue; }
+          if (ti >= trisArr.size() || (left && (*left)[ti])) { violations++; continue; }
           const TriRec& t = trisArr[ti];
           if (t.origId >= triCount || seen[t.origId]) { violations++; continue; }
           seen[t.origId] = 1;
@@ -133,7 +135,9 @@ static int validateTree(const std::vector<Node8>& nodes, const std::vector<TriRe
   }
   // every active triangle sits in exactly one leaf; an inactive one (bvh8.h: a vertex that is not finite or beyond 1e18) in none
   std::vector<uint8_t> inactive(triCount, 0);
-  for (const TriRec& t : trisArr) {
+  for (size_t i = 0; i < trisArr.size(); i++) {
+    const TriRec& t = trisArr[i];
+    if (left && (*left)[i]) continue;
     if (t.origId >= triCount) { violations++; continue; }
     for (int a = 0; a < 3; a++) {
       const float x0 = t.v0[a], x1 = t.v0[a] + t.e1[a], x2 = t.v0[a] + t.e2[a];
@@ -257,7 +261,19 @@ extern "C" int giCDebugValidateSceneBvh(const GiCScene* scene, uint32_t deviceIn
     for (uint32_t k = 0; k < activeTris; k++) { const uint32_t id = tris[k].origId; if (id >= triCount || seen[id]) violations++; else seen[id] = 1; }
     for (uint32_t k = activeTris; k < triCount; k++) if (tris[k].origId >= triCount || (k > activeTris && tris[k].origId <= tris[k - 1].origId)) violations++;
   }
-  if (violations == 0) violations = validateTree(nodes, tris, triCount); // (reachability + conservativeness; needs a well-formed tree)
+  // a partitioned scene leaves the parts of hidden and retired meshes out of its top tree (updateVisibility, updateTopology): their records stay resident,
+  // unreachable, and the live ids are those of a fresh build of the visible meshes
+  std::vector<uint8_t> left; uint32_t liveIds = triCount;
+  if (s->host->partitioned) {
+    left.assign(triCount, 0);
+    for (const InstPart& P : s->host->parts) {
+      if (!s->host->meshBuilds[P.meshBuild].hidden) continue;
+      if ((uint64_t)P.triFirst + P.nf > triCount) { violations++; continue; }
+      std::fill(left.begin() + P.triFirst, left.begin() + P.triFirst + P.nf, (uint8_t)1);
+      liveIds -= P.nf;
+    }
+  }
+  if (violations == 0) violations = validateTree(nodes, tris, liveIds, s->host->partitioned ? &left : nullptr); // (reachability + conservativeness; needs a well-formed tree)
   if (outNodeCount) *outNodeCount = nodeCount;
   if (outMaxDepth) *outMaxDepth = maxDepth;
   if (outBuiltOnDevice) *outBuiltOnDevice = s->host->deviceBuilt ? 1 : 0;
@@ -501,6 +517,15 @@ extern "C" int giCDebugSceneVertexUpdateCount(const GiCScene* scene, uint64_t* o
   if (!s || !outCount) { setError("giCDebugSceneVertexUpdateCount: bad arguments"); return GI_C_ERROR; }
   std::lock_guard<std::mutex> guard(s->mutex);
   *outCount = s->updateCounts[UPDATE_VERTEX];
+  return GI_C_OK;
+}
+
+extern "C" int giCDebugSceneTopologyUpdateCount(const GiCScene* scene, uint64_t* outCount)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!s || !outCount) { setError("giCDebugSceneTopologyUpdateCount: bad arguments"); return GI_C_ERROR; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  *outCount = s->updateCounts[UPDATE_TOPOLOGY];
   return GI_C_OK;
 }
 

@@ -119,6 +119,25 @@ struct DeviceBuffer {
     if (!v.empty()) HIP_TRY(hipMemcpyAsync(ptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
     return GI_C_OK;
   }
+  // Content-preserving grow (gi_build.cpp updateTopology): at least `n` elements, the first `count` kept.  A new block with 25 % slack, a device-to-device copy
+  // on `s`; the old block goes into `old` and is freed by the caller once the stream is synchronised (the copy reads it).  Same answers as alloc.
+  int grow(size_t n, hipStream_t s, std::vector<void*>& old)
+  {
+    if (n <= count && ptr) return GI_C_OK;
+    T* fresh = nullptr;
+    const size_t cap = n + n / 4u + 1u;
+    const hipError_t e = hipMalloc((void**)&fresh, cap * sizeof(T));
+    if (e != hipSuccess) {
+      if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); t_lastError = "hipMalloc: out of memory"; return GI_C_OUT_OF_MEMORY_INTERNAL; }
+      setError(std::string("hipMalloc: ") + hipGetErrorString(e)); return GI_C_ERROR;
+    }
+    if (ptr && count && hipMemcpyAsync(fresh, ptr, count * sizeof(T), hipMemcpyDeviceToDevice, s) != hipSuccess) {
+      (void)hipFree(fresh); setError("hipMemcpyAsync failed (device buffer grow)"); return GI_C_ERROR;
+    }
+    if (ptr) old.push_back(ptr);
+    ptr = fresh; count = cap;
+    return GI_C_OK;
+  }
   void release() { if (ptr) { (void)hipFree(ptr); ptr = nullptr; count = 0; } }
 };
 
@@ -168,6 +187,9 @@ struct GiCMesh {
   uint32_t builtInstances = 0xffffffffu; // instance count the built scene holds for this mesh (0xffffffff: not part of it)
   bool visToggled = false;  // giCSetMeshVisibility was called since the last syncSceneGeometry
   bool vertsEdited = false; // giCSetMeshVertices was called since the last syncSceneGeometry
+  // giCDestroyMesh on a mesh of the built scene with topology updates wanted: the mesh left GiCScene::meshes and is kept (GiCScene::retiredMeshes) until the
+  // next buildScene, because the resident scene still holds its records (MeshBuild::m).  Invisible for good
+  bool retired = false;
 };
 
 // swap-remove dense store (GgpuDenseDataStore, src/ggpu/impl/DenseDataStore.cpp:35-93): the arrays stay dense so
@@ -308,7 +330,7 @@ struct SceneHost {
   bool hostTreeDropped = false;
 };
 
-enum : uint32_t { UPDATE_FULL = 0, UPDATE_TRANSFORM = 1, UPDATE_MATERIAL = 2, UPDATE_VISIBILITY = 3, UPDATE_VERTEX = 4 }; // GiCScene::updateCounts
+enum : uint32_t { UPDATE_FULL = 0, UPDATE_TRANSFORM = 1, UPDATE_MATERIAL = 2, UPDATE_VISIBILITY = 3, UPDATE_VERTEX = 4, UPDATE_TOPOLOGY = 5 }; // GiCScene::updateCounts
 struct GiCScene : SceneDevice {
   std::mutex mutex;
   uint32_t dirty = DIRTY_ALL;
@@ -364,16 +386,24 @@ struct GiCScene : SceneDevice {
   // a look-ahead window traced under another generation is not served from
   uint64_t generation = 0;
   // syncSceneGeometry, by UPDATE_*: full builds and incremental updates (giCDebugSceneUpdateCounts: the first three; giCDebugSceneVisibilityUpdateCount,
-  // giCDebugSceneVertexUpdateCount)
-  uint64_t updateCounts[5] = {0, 0, 0, 0, 0};
+  // giCDebugSceneVertexUpdateCount, giCDebugSceneTopologyUpdateCount)
+  uint64_t updateCounts[6] = {0, 0, 0, 0, 0, 0};
   int32_t optVisibilityUpdates = 0; // GI_C_SCENE_OPTION_VISIBILITY_UPDATES: 1 = visibility edits are applied to the resident scene (updateVisibility)
   int32_t optVertexUpdates = 0; // GI_C_SCENE_OPTION_VERTEX_UPDATES: 1 = vertex edits refit the resident tree (updateVertices)
   // DIRTY_BVH was raised by something other than giCSetMeshVisibility / giCSetMeshVertices since the last syncSceneGeometry (raiseRebuild): the rebuild is due
   // whatever was toggled or deformed
   bool rebuildDue = true;
+  int32_t optTopologyUpdates = 0; // GI_C_SCENE_OPTION_TOPOLOGY_UPDATES: 1 = meshes are created and destroyed in the resident scene (updateTopology)
+  // DIRTY_BVH was raised by giCCreateMesh, giCDestroyMesh or a setter on a mesh that is not part of the built scene (raiseTopology): syncSceneGeometry may
+  // answer with updateTopology; without the option it turns this into rebuildDue
+  bool topologyDue = false;
+  std::vector<GiCMesh*> retiredMeshes; // destroyed meshes the resident scene still refers to (GiCMesh::retired): freed by buildScene and with the scene
+  ~GiCScene() { for (GiCMesh* m : retiredMeshes) delete m; }
 };
-// every geometry-side edit but a visibility toggle and a vertex edit
+// every geometry-side edit but a visibility toggle, a vertex edit and the topology edits below
 inline void raiseRebuild(GiCScene* s) { s->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER; s->rebuildDue = true; }
+// a mesh created or destroyed, or a setter on a mesh that is not part of the built scene: the same flags
+inline void raiseTopology(GiCScene* s) { s->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER; s->topologyDue = true; }
 
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -389,6 +419,7 @@ uint32_t sceneDeviceCount(const GiCScene* s);                // devices a render
 SceneDevice& sceneDevice(GiCScene* s, uint32_t slot);
 bool usableVertexPositions(const GiCVertex* v, size_t count);  // every position finite and within 1e18 (bvh8.h "Inactive items")
 void nodeBounds(const Node8& n, float box[6]);               // dequantised bounds of a node's children (+ an ulp-scale pad)
+bool topologyUpdatesWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_TOPOLOGY_UPDATES / GATLING_OPTIONS=topology_updates
 int syncSceneGeometry(GiCScene* s);                          // brings the device scene up to date with the host-side edits (incremental or full build)
 // dirty flags of a material-side edit: DIRTY_MATERIALS alone once the scene / the mesh is part of a built scene (the incremental path), else with DIRTY_BVH
 inline uint32_t materialEditFlags(bool built) { return DIRTY_MATERIALS | DIRTY_FRAMEBUFFER | (built ? 0u : (uint32_t)DIRTY_BVH); }

@@ -73,6 +73,11 @@ struct VisPatch { int32_t idDelta; uint32_t action; };
 constexpr uint32_t VIS_KEEP = 0u, VIS_HIDE = 1u, VIS_SHOW = 2u;
 void launchPatchVisibility(hipStream_t s, TriRec* tris, uint32_t triCount, const InstanceRec* instances, uint32_t instanceCount, const VisPatch* patchOfInstance,
     const TriShade* triShade, uint32_t shadeCount);
+// gi_patch.hip: a part the device builder made over the `nf` records at tris + triFirst (gi_build.cpp updateTopology) put where it lives: its `partNodes`
+// nodes copied from the builder's block to nodes + nodeOff with child and triangle bases made absolute, and `idAdd` added to the ids of its records (the
+// builder numbered them by position in the part).  The caller has checked both ranges against the arrays' sizes
+void launchPlacePart(hipStream_t s, const Node8* partNodes, uint32_t partNodeCount, Node8* nodes, uint32_t nodeOff, TriRec* tris, uint32_t triFirst, uint32_t nf,
+    uint32_t idAdd);
 // gi_refit.hip: a vertex edit applied to the device-resident scene (gi_build.cpp updateVertices).  launchRefitTris makes the world-space corners of the records
 // of edited instances (editedOfInstance[t.instance] != 0) again from their shading records and instance transforms; launchRefitLevel refits one tree level:
 // thread i handles node ranges[r].nodeFirst + (i - ranges[r].threadBase) of the last range r with threadBase <= i, reading the float boxes (8 floats per

@@ -46,6 +46,11 @@
 //                                  applied to the resident scene (gi_build.cpp updateVisibility)
 //   vertex_updates       -1        -1 = the scene option decides (GI_C_SCENE_OPTION_VERTEX_UPDATES), 0 / 1 = vertex edits (giCSetMeshVertices) rebuild the
 //                                  scene / refit the resident tree on the device (gi_build.cpp updateVertices, gi_refit.hip)
+//   topology_updates     -1        -1 = the scene option decides (GI_C_SCENE_OPTION_TOPOLOGY_UPDATES), 0 / 1 = mesh creations and destructions rebuild the
+//                                  scene / are applied to the resident scene (gi_build.cpp updateTopology)
+//   device_parts_min     4096      topology updates with the device builder on: an appended part of at least this many faces (and more than 128) is built
+//                                  on the device (buildBvh8Device + gi_patch.hip k_place_part), a smaller one by the host (buildPart).  The measured
+//                                  crossover for one part
 //   phase_stats          0         counting builds: print k_path's phase split / k_trace_dyn's lane accounting
 #pragma once
 

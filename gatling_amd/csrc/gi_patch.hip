@@ -1,6 +1,7 @@
 // gi_patch.hip -- edits applied in place to the device-resident triangle records:
 //   k_patch_mat_flags   TriRec::matFlags rewritten after a material edit (gi_build.cpp updateMaterials)
 //   k_patch_visibility  scene-order ids renumbered, records of hidden instances made unhittable / restored (gi_build.cpp updateVisibility; below)
+//   k_place_part        a device-built part of an appended mesh moved into the scene's node array, its ids made scene-order (gi_build.cpp updateTopology; below)
 //
 // k_patch_mat_flags.
 // A material or assignment edit changes one word per flattened triangle -- material index | shade class << 24 | cutout << 28 | facing << 30 -- and nothing
@@ -75,7 +76,34 @@ __global__ __launch_bounds__(kPatchBlock) void k_patch_visibility(TriRec* __rest
   }
 }
 
+// k_place_part.  A mesh appended to a partitioned scene (opt-in: GI_C_SCENE_OPTION_TOPOLOGY_UPDATES) whose parts the device builder made: buildBvh8Device ran
+// over the part's own records at tris + triFirst and left (a) a tree in a block of its own whose child and triangle bases count from 0, (b) the records in
+// leaf order with origId = position in the part.  Thread i < partNodeCount copies node i to nodes[nodeOff + i] with childBase += nodeOff and triBase +=
+// triFirst -- placePart's two additions on the host -- and thread i < nf adds idAdd (the instance's first scene-order id) to record i's id.  One grid over
+// max(partNodeCount, nf) threads: a tree has fewer nodes than triangles, so the node copy rides along with the id pass.  Plain vector loads and stores, no
+// atomics: every thread owns its node and its record.  Memory-bound and small: 80 bytes read + written per node, one 64-byte line touched per record.
+__global__ __launch_bounds__(kPatchBlock) void k_place_part(const Node8* __restrict__ partNodes, uint32_t partNodeCount, Node8* __restrict__ nodes, uint32_t nodeOff,
+    TriRec* __restrict__ tris, uint32_t triFirst, uint32_t nf, uint32_t idAdd)
+{
+  const uint32_t i = blockIdx.x * kPatchBlock + threadIdx.x;
+  if (i < partNodeCount) {
+    Node8 n = partNodes[i];
+    n.childBase += nodeOff; n.triBase += triFirst;
+    nodes[nodeOff + i] = n;
+  }
+  if (i < nf) tris[triFirst + i].origId += idAdd;
+}
+
 } // namespace
+
+void launchPlacePart(hipStream_t s, const Node8* partNodes, uint32_t partNodeCount, Node8* nodes, uint32_t nodeOff, TriRec* tris, uint32_t triFirst, uint32_t nf,
+    uint32_t idAdd)
+{
+  const uint32_t threads = partNodeCount > nf ? partNodeCount : nf;
+  if (threads == 0u) return;
+  hipLaunchKernelGGL(k_place_part, dim3((threads + kPatchBlock - 1u) / kPatchBlock), dim3(kPatchBlock), 0, s, partNodes, partNodeCount, nodes, nodeOff, tris,
+      triFirst, nf, idAdd);
+}
 
 void launchPatchVisibility(hipStream_t s, TriRec* tris, uint32_t triCount, const InstanceRec* instances, uint32_t instanceCount, const VisPatch* patchOfInstance,
     const TriShade* triShade, uint32_t shadeCount)

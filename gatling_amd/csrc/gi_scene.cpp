@@ -54,6 +54,7 @@ void giCDestroyMaterial(GiCMaterial* mat)
     std::lock_guard<std::mutex> g(s->mutex);
     s->materials.erase(std::remove(s->materials.begin(), s->materials.end(), mat), s->materials.end());
     for (GiCMesh* m : s->meshes) if (m->material == mat) m->material = nullptr;
+    for (GiCMesh* m : s->retiredMeshes) if (m->material == mat) m->material = nullptr;
     s->dirty |= materialEditFlags(s->host != nullptr); // (a mesh left without a material drops out of the scene: updateMaterials sees it and rebuilds)
   }
   delete mat;
@@ -80,7 +81,7 @@ static GiCMesh* createMeshImpl(GiCScene* scene, const GiCMeshDesc* d)
   m->id = d->id; m->doubleSided = d->isDoubleSided != 0; m->flipFacing = d->isLeftHanded != 0; m->maxFaceId = d->maxFaceId;
   std::lock_guard<std::mutex> g(scene->mutex);
   scene->meshes.push_back(m.get());
-  raiseRebuild(scene);
+  raiseTopology(scene); // (the flags of a rebuild; with GI_C_SCENE_OPTION_TOPOLOGY_UPDATES the mesh may be appended to the resident scene instead)
   return m.release();
 }
 
@@ -91,7 +92,7 @@ void giCSetMeshTransform(GiCMesh* mesh, const float* mat4x4)
   memcpy(mesh->transform, mat4x4, sizeof(float) * 16);
   // same triangles elsewhere: incremental update (every instance of the mesh moves)
   if (mesh->builtInstances != 0xffffffffu) { mesh->xformDirty = true; mesh->instDirty.clear(); mesh->scene->dirty |= DIRTY_XFORM | DIRTY_FRAMEBUFFER; }
-  else raiseRebuild(mesh->scene);
+  else raiseTopology(mesh->scene);
 }
 
 void giCSetMeshInstanceTransforms(GiCMesh* mesh, uint32_t count, const float* transforms)
@@ -109,7 +110,8 @@ void giCSetMeshInstanceTransforms(GiCMesh* mesh, uint32_t count, const float* tr
     }
     mesh->xformDirty = true; mesh->scene->dirty |= DIRTY_XFORM | DIRTY_FRAMEBUFFER;
   }
-  else raiseRebuild(mesh->scene);
+  else if (mesh->builtInstances == 0xffffffffu) raiseTopology(mesh->scene);
+  else raiseRebuild(mesh->scene); // (another instance count of a mesh of the built scene)
   } catch (const std::exception& e) { setError(std::string("giCSetMeshInstanceTransforms: ") + e.what()); }
 }
 
@@ -120,7 +122,7 @@ void giCSetMeshInstanceIds(GiCMesh* mesh, uint32_t count, const int32_t* ids)
   std::vector<int32_t> copy(ids, ids + count);
   std::lock_guard<std::mutex> g(mesh->scene->mutex);
   mesh->instanceIds.swap(copy);
-  raiseRebuild(mesh->scene);
+  if (mesh->builtInstances == 0xffffffffu) raiseTopology(mesh->scene); else raiseRebuild(mesh->scene);
   } catch (const std::exception& e) { setError(std::string("giCSetMeshInstanceIds: ") + e.what()); }
 }
 
@@ -131,7 +133,7 @@ void giCSetMeshMaterial(GiCMesh* mesh, GiCMaterial* mat)
   mesh->material = mat;
   // a mesh of the built scene keeps its triangles: only their material word changes.  One that is not part of it (new, invisible, left out for an invalid
   // material) may enter the scene now: rebuild
-  if (mesh->builtInstances != 0xffffffffu) mesh->scene->dirty |= materialEditFlags(true); else raiseRebuild(mesh->scene);
+  if (mesh->builtInstances != 0xffffffffu) mesh->scene->dirty |= materialEditFlags(true); else raiseTopology(mesh->scene);
 }
 
 void giCSetMeshVisibility(GiCMesh* mesh, int32_t visible)
@@ -171,7 +173,18 @@ void giCDestroyMesh(GiCMesh* mesh)
   {
     std::lock_guard<std::mutex> g(s->mutex);
     s->meshes.erase(std::remove(s->meshes.begin(), s->meshes.end(), mesh), s->meshes.end());
-    raiseRebuild(s);
+    const bool built = mesh->builtInstances != 0xffffffffu && s->host != nullptr;
+    if (built && topologyUpdatesWanted(s)) {
+      // retired: the resident scene keeps referring to it (MeshBuild::m) until updateTopology has taken its triangles out and the next buildScene frees it.
+      // For every loop over the built meshes it is a mesh hidden for good
+      mesh->visible = false; mesh->retired = true;
+      mesh->xformDirty = false; mesh->instDirty.clear(); // (a move of the same frame: its parts are unreachable, no transform update rebuilds them)
+      s->retiredMeshes.push_back(mesh);
+      raiseTopology(s);
+      return;
+    }
+    // (a mesh of the built scene deleted at once leaves MeshBuild::m dangling: only the rebuild may follow, whatever the option says by then)
+    if (built) raiseRebuild(s); else raiseTopology(s);
   }
   delete mesh;
 }
@@ -200,7 +213,7 @@ static int setPrimvarsImpl(GiCMesh* mesh, std::vector<GiCPrimvar>& dst, uint32_t
   std::lock_guard<std::mutex> g(mesh->scene->mutex);
   dst = std::move(v);
   // Gi.cpp:685-700; primvars feed the per-mesh scene data, not the tree
-  if (mesh->builtInstances != 0xffffffffu) mesh->scene->dirty |= materialEditFlags(true); else raiseRebuild(mesh->scene);
+  if (mesh->builtInstances != 0xffffffffu) mesh->scene->dirty |= materialEditFlags(true); else raiseTopology(mesh->scene);
   return GI_C_OK;
 }
 int giCSetMeshPrimvars(GiCMesh* mesh, uint32_t count, const GiCPrimvarData* pv) { return mesh

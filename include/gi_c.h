@@ -377,7 +377,8 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * Still 8 with GI_C_SCENE_OPTION_SAMPLE_LOOKAHEAD and giCGetLookaheadStats: no struct grew and no entry point changed meaning -- both are additions that a caller
  * built against an earlier header never sees.  A caller probes for them: giCSetSceneOption answers GI_C_ERROR for an option the library does not know.
  * The same holds for GI_C_SCENE_OPTION_VISIBILITY_UPDATES, giCDebugSceneVisibilityUpdateCount, giCDebugSceneClassState, giCDebugMissRect and giCDebugPathWalkStats, and for
- * giCSetMeshVertices, GI_C_SCENE_OPTION_VERTEX_UPDATES, giCDebugSceneVertexUpdateCount, giCDebugRefitBvh and giCDebugSceneRefitCheck. */
+ * giCSetMeshVertices, GI_C_SCENE_OPTION_VERTEX_UPDATES, giCDebugSceneVertexUpdateCount, giCDebugRefitBvh and giCDebugSceneRefitCheck, and for
+ * GI_C_SCENE_OPTION_TOPOLOGY_UPDATES and giCDebugSceneTopologyUpdateCount. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -548,6 +549,23 @@ int giCGetRenderStats(const GiCScene* scene, GiCRenderStats* out);
  * refitted tree keeps the topology chosen for the OLD positions: large deformations make it slower to walk (never wrong); any full build resets that
  * (DESIGN.md section 6).  GATLING_OPTIONS=vertex_updates=0|1 overrides the option (hdGatling sets no scene options). */
 #define GI_C_SCENE_OPTION_VERTEX_UPDATES 12
+/* [ext] Incremental topology edits: value 1 = meshes created (giCCreateMesh and the setters that follow it) and destroyed (giCDestroyMesh) since the last
+ * giCRender are applied to the device-resident scene -- a destroyed mesh of the built scene is taken out of the tree and the triangles behind it are
+ * renumbered as a fresh build would number them; a new mesh gets its records at the ends of the device arrays and one subtree per instance under a rebuilt top
+ * tree (built by the host, or on the device for parts of at least GATLING_OPTIONS=device_parts_min faces when GI_C_SCENE_OPTION_BVH_BUILD is 1) -- instead of
+ * rebuilding the scene; 0 = off (default): every creation and destruction rebuilds.  This is what hdGatling does for every points, primvar or topology change
+ * of a prim (destroy, create, every setter again).  With the option wanted giCDestroyMesh keeps a mesh of the built scene alive inside the library until the
+ * next full build; the handle is invalid for the caller all the same.  The image does not depend on the option.  The library falls back to the rebuild when
+ * anything else asked for one (instance counts or ids of a built mesh, scene options), with GATLING_OPTIONS=incremental=0, on the two-level layout, for a
+ * scene within LDS, when fewer than 4096 visible flattened triangles remain, when a new mesh has a position that is not finite or beyond 1e18 (in object or
+ * world space) or an unusable transform, when a new mesh lies in front of a mesh of the built scene in creation order (a mesh that was invisible or without a
+ * valid material at the build and is now shown), when the top tree outgrows the range reserved for it, at 2^26 resident triangles, when the retired
+ * triangles outnumber the live ones (resident memory stays within twice the live scene), when the first such edit of a scene destroys more of the built
+ * triangles than it leaves, and when device memory runs out.  After such an edit
+ * GiCRenderStats.triangleCount and nodeCount describe what is RESIDENT on the device (retired triangles and node reserves included), bvhBuildMs is the time
+ * spent building the new subtrees and uploadMs the rest.  The first such edit of a scene re-lays it out as per-instance subtrees (about one build).
+ * GATLING_OPTIONS=topology_updates=0|1 overrides the option (hdGatling sets no scene options).  DESIGN.md section 6. */
+#define GI_C_SCENE_OPTION_TOPOLOGY_UPDATES 13
 int giCGetLookaheadStats(const GiCScene* scene, GiCLookaheadStats* out);
 int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value);
 /* [ext] closest hit of one ray through the device traversal kernel (parity tests of the BVH8 path).
@@ -612,6 +630,9 @@ int giCDebugSceneVisibilityUpdateCount(const GiCScene* scene, uint64_t* outCount
 /* [ext] how often the scene was brought up to date by an incremental vertex update (GI_C_SCENE_OPTION_VERTEX_UPDATES); not counted in
  * giCDebugSceneUpdateCounts either. */
 int giCDebugSceneVertexUpdateCount(const GiCScene* scene, uint64_t* outCount);
+/* [ext] [debug] how often the scene was brought up to date by an incremental topology update (GI_C_SCENE_OPTION_TOPOLOGY_UPDATES); not counted in
+ * giCDebugSceneUpdateCounts either. */
+int giCDebugSceneTopologyUpdateCount(const GiCScene* scene, uint64_t* outCount);
 /* [ext] what the last scene sync derived from the visible meshes' materials, the state that picks a render's kernel variants: out[0] the material classes in
  * use (one bit each), [1] those with a textured material, [2] and [3] the same per shade class, [4] 1 when some visible triangle has cutout opacity.  Host
  * only: no device work. */
