@@ -26,6 +26,7 @@ OPTION_SAMPLE_LOOKAHEAD = 10  # N >= 2: a progressive call may trace the samples
 OPTION_VERTEX_UPDATES = 12  # 1: vertex edits (giCSetMeshVertices) of meshes of the built scene refit the resident BVH on the device instead of rebuilding the scene (include/gi_c.h); 0 = off (default)
 OPTION_VISIBILITY_UPDATES = 11  # 1: visibility edits of meshes of the built scene are applied to the resident scene instead of rebuilding it (include/gi_c.h); 0 = off (default)
 OPTION_TOPOLOGY_UPDATES = 13  # 1: meshes created and destroyed after the build are appended to / retired from the resident scene instead of rebuilding it (include/gi_c.h); 0 = off (default)
+OPTION_RESYNC_REFITS = 14  # 1 (with options 12 and 13): a destroyed and a created mesh with the same faces become a vertex refit of the resident records instead of a retire + append (include/gi_c.h); 0 = off (default)
 OPTION_BVH_BUILD = 9  # 0 = host BVH builder (default), 1 = device builder (flat-layout scenes of more than 128 triangles)
 
 
@@ -167,6 +168,8 @@ SYMBOLS = [
     ("giCDebugSceneVertexUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugRefitBvh", C.c_int, [_FP, _FP, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("giCDebugSceneRefitCheck", C.c_int, [_P, _U, C.POINTER(C.c_uint32)]),
     ("giCDebugSceneTopologyUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("giCDebugSceneResyncCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugGatherShade", C.c_int, [_P, _U, _P, _U]),
+    ("giCDebugSceneShadeCheck", C.c_int, [_P, _U, C.POINTER(C.c_uint32)]),
     ("giCDebugPathWalkStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugMissRect", C.c_int, [_FP, C.POINTER(GiCCameraDesc), C.POINTER(GiCRenderSettings), _U, _U, C.POINTER(C.c_uint32)]),
 ]
@@ -208,6 +211,19 @@ def miss_rect(bounds, camera, rs: "RenderSettings", width: int, height: int):
     if L.giCDebugMissRect(_fp(bounds), C.byref(cam), C.byref(st), int(width), int(height), out) != GI_C_OK:
         raise GiError("giCDebugMissRect failed: " + L.giCGetLastError().decode())
     return tuple(int(v) for v in out)
+
+
+def debug_gather_shade(vertices, faces) -> int:
+    """giCDebugGatherShade: the shading records a vertex update gathers from the packed vertex records against the ones the scene build packs, for the mesh
+    (`vertices`: VERTEX_DTYPE, `faces`: n x 3 indices).  Returns the number of differing records (0 is the contract).  Host only."""
+    from .scene import VERTEX_DTYPE
+    L = load_library()
+    v = np.ascontiguousarray(vertices, VERTEX_DTYPE)
+    f = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3)
+    n = L.giCDebugGatherShade(v.ctypes.data, len(v), f.ctypes.data, len(f))
+    if n < 0:
+        raise GiError("giCDebugGatherShade refused the mesh")
+    return int(n)
 
 
 _initialized = False
@@ -496,6 +512,22 @@ class Scene:
         if v < 0:
             raise GiError("giCDebugSceneRefitCheck failed: " + self.L.giCGetLastError().decode())
         return {"differing": v, "nodes": nodes.value}
+
+    def shade_check(self, device: int = 0) -> int:
+        """giCDebugSceneShadeCheck: the vertex and shading records resident on a device against the host's copies, whole arrays.  Returns the number of
+        differing records (0)."""
+        records = C.c_uint32(0)
+        v = self.L.giCDebugSceneShadeCheck(self.handle, device, C.byref(records))
+        if v < 0:
+            raise GiError("giCDebugSceneShadeCheck failed: " + self.L.giCGetLastError().decode())
+        return int(v)
+
+    def resync_count(self) -> int:
+        """giCDebugSceneResyncCount: meshes that adopted the resident records of the mesh they replaced (OPTION_RESYNC_REFITS) since the scene was created."""
+        n = C.c_uint64(0)
+        if self.L.giCDebugSceneResyncCount(self.handle, C.byref(n)) != GI_C_OK:
+            raise GiError("giCDebugSceneResyncCount failed")
+        return int(n.value)
 
     def update_counts(self) -> dict:
         """giCDebugSceneUpdateCounts: how often the scene was brought up to date by a full build / a transform update / a material update."""

@@ -3,6 +3,9 @@
 #include "gi_host.h"
 #include "gi_bvh_build.h"
 #include "gi_refit.h"
+#include "gi_pack.h"
+
+#include <unordered_map>
 constexpr uint32_t kIncrementalMinTris = 4096; // scenes with fewer triangles are not edited in place: they rebuild in no time (and must stay LDS-resident)
 // levels of a scene BVH: the deepest traversal variant keeps 16 stack entries in LDS and OVF_STACK = 40 in scratch; trav_node_pick does not bound-check the
 // spill.  The limit stays at 1 + 8 + 40 levels, the depth the 8-entry spilling variant of earlier versions could hold
@@ -76,39 +79,26 @@ inline bool usableInstance(const InstanceRec& ir)
   for (int i = 0; i < 9; i++) if (!std::isfinite(ir.w2o[i])) return false;
   return true;
 }
-// Shading attributes of a vertex as the scene build takes them: a normal or tangent with a non-finite component becomes +Z, a non-finite texture coordinate 0,
-// a non-finite bitangent sign +1 (the position is left alone: it decides whether the triangle is active). The reference uploads what it is given
-// (Gi.cpp:848-861) and a NaN attribute is a NaN pixel there; here hostile attributes cost the shading of the faces that use them, nothing else.
-inline GiCVertex usableShadingAttributes(const GiCVertex& in)
+// giCDebugGatherShade: packVertex + the gather a vertex update runs (gi_refit.h refit_gather_shade) against packTriShade, bytewise.  Host only.
+extern "C" int giCDebugGatherShade(const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount)
 {
-  GiCVertex v = in;
-  auto direction = [](float* d) { if (!std::isfinite(d[0]) || !std::isfinite(d[1]) || !std::isfinite(d[2])) { d[0] = 0.0f; d[1] = 0.0f; d[2] = 1.0f; } };
-  direction(v.norm); direction(v.tangent);
-  if (!std::isfinite(v.u)) v.u = 0.0f;
-  if (!std::isfinite(v.v)) v.v = 0.0f;
-  if (!std::isfinite(v.bitangentSign)) v.bitangentSign = 1.0f;
-  return v;
-}
-// The FVertex of one mesh vertex (Gi.cpp:848-861: normal and tangent quantised to octahedral unorm2x16, then decoded once) and the TriShade record of one mesh
-// face: buildScene, buildShadeRecords and updateVertices -- the one copy of this code
-static FVertex packVertex(const GiCVertex& vIn)
-{
-  const GiCVertex v = usableShadingAttributes(vIn);
-  FVertex fv; memcpy(fv.pos, v.pos, 12); fv.bsign = v.bitangentSign;
-  decodeDirection(encodeDirection(v.norm), fv.normal); decodeDirection(encodeDirection(v.tangent), fv.tangent);
-  fv.u = v.u; fv.v = v.v;
-  return fv;
-}
-static TriShade packTriShade(const GiCMesh* m, const GiCFace& f, uint32_t vertexOffset)
-{
-  TriShade q{};
-  for (int k = 0; k < 3; k++) {
-    const GiCVertex v = usableShadingAttributes(m->vertices[f.v_i[k]]);
-    // (Gi.cpp:848-861: quantised, then decoded once)
-    memcpy(q.p[k], v.pos, 12); decodeDirection(encodeDirection(v.norm), q.n[k]); decodeDirection(encodeDirection(v.tangent), q.t[k]);
-    q.uv[k][0] = v.u; q.uv[k][1] = v.v; q.bsign[k] = v.bitangentSign; q.vi[k] = vertexOffset + f.v_i[k];
-  }
-  return q;
+  if ((vertexCount && !vertices) || (faceCount && !faces)) return -1;
+  for (uint32_t f = 0; f < faceCount; f++) for (int k = 0; k < 3; k++) if (faces[f].v_i[k] >= vertexCount) return -1;
+  try {
+    constexpr uint32_t vertexOffset = 3u; // (as a mesh behind others in the scene's arrays: vi holds absolute indices)
+    std::vector<FVertex> verts(vertexOffset + (size_t)vertexCount, FVertex{});
+    for (uint32_t i = 0; i < vertexCount; i++) verts[vertexOffset + i] = packVertex(vertices[i]);
+    int differ = 0;
+    for (uint32_t f = 0; f < faceCount; f++) {
+      const TriShade packed = packTriShade(vertices, faces[f], vertexOffset);
+      TriShade gathered; memset(&gathered, 0xa5, sizeof(gathered)); // (every gathered word must be written)
+      for (int k = 0; k < 3; k++) gathered.vi[k] = packed.vi[k];
+      gathered.pad = packed.pad;
+      refit_gather_shade(verts.data(), (uint32_t)verts.size(), gathered);
+      if (memcmp(&gathered, &packed, sizeof(TriShade)) != 0) differ++;
+    }
+    return differ;
+  } catch (const std::exception&) { return -1; }
 }
 bool usableVertexPositions(const GiCVertex* v, size_t count)
 {
@@ -472,7 +462,7 @@ static std::vector<uint32_t> buildShadeRecords(SceneHost& H)
   for (MeshBuild& mb : H.meshBuilds) {
     mb.shadeBase = (uint32_t)H.triShade.size(); shadeBaseOfMesh[mb.meshIdx] = mb.shadeBase;
     const GiCMesh* m = mb.m;
-    for (const GiCFace& f : m->faces) H.triShade.push_back(packTriShade(m, f, mb.vertexOffset));
+    for (const GiCFace& f : m->faces) H.triShade.push_back(packTriShade(m->vertices.data(), f, mb.vertexOffset));
   }
   return shadeBaseOfMesh;
 }
@@ -865,7 +855,7 @@ static int updateMaterials(GiCScene* s, bool& handled, UpdateCost& cost)
   if (!host || s->triCount < kIncrementalMinTris) return GI_C_OK; // (the floor: resident triangles)
   SceneHost& H = *host;
   const double t0 = nowMs();
-  { // the same meshes, in the same order, as the built scene holds?
+  if (!H.reordered) { // the same meshes, in the same order, as the built scene holds?
     size_t b = 0;
     // (a retired mesh -- destroyed, its records still resident until the next build: updateTopology -- is no longer among s->meshes)
     auto skipRetired = [&] { while (b < H.meshBuilds.size() && H.meshBuilds[b].m->retired) b++; };
@@ -881,6 +871,20 @@ static int updateMaterials(GiCScene* s, bool& handled, UpdateCost& cost)
     }
     skipRetired();
     if (b != H.meshBuilds.size() || H.meshRecs.size() != H.meshBuilds.size()) return GI_C_OK;
+  } else { // a mesh adopted the records of the one it replaced (updateTopology adoptResyncs): the same meshes, each found by its handle
+    std::unordered_map<const GiCMesh*, size_t> buildOf;
+    size_t retired = 0, found = 0;
+    for (size_t b = 0; b < H.meshBuilds.size(); b++) { if (H.meshBuilds[b].m->retired) retired++; else buildOf[H.meshBuilds[b].m] = b; }
+    for (const GiCMesh* m : s->meshes) {
+      const auto it = buildOf.find(m);
+      const bool hiddenInScene = it != buildOf.end() && H.meshBuilds[it->second].hidden;
+      const bool inScene = (m->visible || hiddenInScene) && !m->faces.empty() && std::find(s->materials.begin(), s->materials.end(), m->material) != s->materials.end();
+      if (inScene != (m->builtInstances != 0xffffffffu)) return GI_C_OK;
+      if (!inScene) continue;
+      if (it == buildOf.end() || H.meshBuilds[it->second].instCount != m->builtInstances) return GI_C_OK;
+      found++;
+    }
+    if (found + retired != H.meshBuilds.size() || H.meshRecs.size() != H.meshBuilds.size()) return GI_C_OK;
   }
   if (s->materials.size() > 0x01000000u) { setError("too many materials"); return GI_C_ERROR; }
   // --- host: material records, scene data, every mesh's word, the scene's class masks
@@ -958,10 +962,26 @@ static bool visibilityUpdatesWanted(const GiCScene* s)
 // build of the visible meshes gives it against the one the resident records hold, and what happens to its records.  hide(mb): the mesh is to be hidden.
 struct VisibilityPlan { std::vector<VisPatch> patch; std::vector<uint32_t> newBase; std::vector<uint8_t> hide; uint64_t visibleTris = 0;
     uint32_t hides = 0, shows = 0, renumbered = 0; bool launch = false; };
-template <class Hide> static bool planVisibility(const SceneHost& H, Hide&& hideOf, VisibilityPlan& P)
+// The built meshes in the order a fresh build meets them: the position in GiCScene::meshes.  That is the order of H.meshBuilds until a mesh adopts the records
+// of the one it replaced (updateTopology, SceneHost::reordered): it sits where it was created, its records where the replaced mesh's sat.  Retired meshes
+// are no longer in the scene and come last (they are hidden: they take no ids).
+static std::vector<uint32_t> sceneOrder(const GiCScene* s, const SceneHost& H)
+{
+  std::vector<uint32_t> order(H.meshBuilds.size());
+  for (uint32_t b = 0; b < (uint32_t)order.size(); b++) order[b] = b;
+  if (!H.reordered) return order;
+  std::unordered_map<const GiCMesh*, size_t> at;
+  for (size_t i = 0; i < s->meshes.size(); i++) at[s->meshes[i]] = i;
+  std::vector<size_t> key(order.size());
+  for (size_t b = 0; b < key.size(); b++) { const auto it = at.find(H.meshBuilds[b].m); key[b] = it == at.end() ? (size_t)-1 : it->second; }
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+  return order;
+}
+template <class Hide> static bool planVisibility(const GiCScene* s, const SceneHost& H, Hide&& hideOf, VisibilityPlan& P)
 {
   P.patch.assign(H.instances.size(), VisPatch{0, VIS_KEEP}); P.newBase.assign(H.meshBuilds.size(), 0u); P.hide.assign(H.meshBuilds.size(), 0);
-  for (const MeshBuild& mb : H.meshBuilds) {
+  for (const uint32_t b : sceneOrder(s, H)) {
+    const MeshBuild& mb = H.meshBuilds[b];
     if (mb.m->builtInstances != mb.instCount) return false;
     const bool hide = hideOf(mb);
     P.hide[mb.meshIdx] = hide ? 1 : 0;
@@ -1012,7 +1032,7 @@ static int updateVisibility(GiCScene* s, bool& handled, UpdateCost& cost)
   const double t0 = nowMs();
   for (const GiCMesh* m : s->meshes) if (m->visToggled && m->builtInstances == 0xffffffffu) return GI_C_OK; // no records on the device: showing it rebuilds
   VisibilityPlan plan;
-  if (!planVisibility(H, [](const MeshBuild& mb) { return !mb.m->visible; }, plan)) return GI_C_OK; // (cannot happen: count changes ask for the rebuild)
+  if (!planVisibility(s, H, [](const MeshBuild& mb) { return !mb.m->visible; }, plan)) return GI_C_OK; // (cannot happen: count changes ask for the rebuild)
   if (plan.visibleTris < kIncrementalMinTris) return GI_C_OK; // (the floor: VISIBLE triangles, what a fresh build of the edited scene would hold)
   const std::vector<VisPatch>& patch = plan.patch;
   const uint64_t visibleTris = plan.visibleTris; const uint32_t hides = plan.hides, shows = plan.shows, renumbered = plan.renumbered; const bool launch = plan.launch;
@@ -1055,8 +1075,9 @@ static int updateVisibility(GiCScene* s, bool& handled, UpdateCost& cost)
 // Incremental vertex updates (opt-in: GI_C_SCENE_OPTION_VERTEX_UPDATES / GATLING_OPTIONS=vertex_updates=1).  giCSetMeshVertices moved the points of meshes
 // of the built scene; topology, ids, materials and transforms stayed.  The tree keeps its shape and is REFITTED where it lives, in device memory
 // (gi_refit.hip): under the traversal contract a tree with the same topology and new conservative boxes gives the bits of a fresh build.
-//   host, per edited mesh: its range of H.verts and of H.triShade made again by the code buildScene runs (packVertex, packTriShade), sent to every device.
-//   device: k_refit_tris makes the flattened records of the edited instances again (TriShade::p, InstanceRec::o2w: flattenTriangle's operations);
+//   host, per edited mesh: its range of H.verts made again by the code buildScene runs (packVertex) and sent to every device; its range of H.triShade
+//       gathered from it (gi_refit.h refit_gather_shade: bytewise what packTriShade makes) and NOT sent.
+//   device: k_gather_shade makes the mesh's shading records again from the vertex records just sent (the same gather); k_refit_tris makes the flattened records of the edited instances again (TriShade::p, InstanceRec::o2w: flattenTriangle's operations);
 //       k_refit_level refits one level per launch, deepest first, over the refit units -- the whole tree (flat layouts, host- or device-built), or every
 //       part of an edited mesh (partitioned layout; the part roots are read back, rebuildTop + uploadTopTree run as after a transform edit).
 //   afterwards: the root is read back for the scene bounds (bounds retire and the miss rectangle read them).  The class state is untouched.
@@ -1094,6 +1115,8 @@ static int updateVertices(GiCScene* s, bool& handled, UpdateCost& cost)
     const MeshBuild& mb = H.meshBuilds[b];
     if (mb.hidden || m->builtInstances != mb.instCount) return GI_C_OK;
     if ((size_t)mb.vertexOffset + m->vertices.size() > H.verts.size() || (size_t)mb.shadeBase + m->faces.size() > H.triShade.size()) return GI_C_OK;
+    // (the shading records are no longer sent: a range the gather kernel would refuse goes to the rebuild, never to stale records)
+    if (m->faces.size() > 0xffffffffu || !gatherShadeRangeOk((uint32_t)H.triShade.size(), mb.shadeBase, (uint32_t)m->faces.size())) return GI_C_OK;
     if (!usableVertexPositions(m->vertices.data(), m->vertices.size())) return GI_C_OK;
     edited.push_back(b);
   }
@@ -1145,10 +1168,15 @@ static int updateVertices(GiCScene* s, bool& handled, UpdateCost& cost)
     levels.push_back(lv);
   }
   // --- host: the edited meshes' vertex and shading records; the partitioned layout's host triangles
+  // (the shading records are a gather of the vertex records, gi_refit.h refit_gather_shade: the host copy by the function the device runs over its own)
   for (uint32_t b : edited) {
     const MeshBuild& mb = H.meshBuilds[b];
-    for (size_t i = 0; i < mb.m->vertices.size(); i++) H.verts[mb.vertexOffset + i] = packVertex(mb.m->vertices[i]);
-    for (size_t f = 0; f < mb.m->faces.size(); f++) H.triShade[mb.shadeBase + f] = packTriShade(mb.m, mb.m->faces[f], mb.vertexOffset);
+    constexpr size_t CHUNK = 4096;
+    const size_t nv = mb.m->vertices.size(), nf = mb.m->faces.size();
+    parallelOver((nv + CHUNK - 1) / CHUNK, [&](size_t c) {
+      for (size_t i = c * CHUNK; i < std::min(nv, (c + 1) * CHUNK); i++) H.verts[mb.vertexOffset + i] = packVertex(mb.m->vertices[i]); });
+    parallelOver((nf + CHUNK - 1) / CHUNK, [&](size_t c) {
+      for (size_t f = c * CHUNK; f < std::min(nf, (c + 1) * CHUNK); f++) refit_gather_shade(H.verts.data(), (uint32_t)H.verts.size(), H.triShade[mb.shadeBase + f]); });
   }
   for (uint32_t i : editedParts) {
     const InstPart& P = H.parts[i];
@@ -1177,7 +1205,12 @@ static int updateVertices(GiCScene* s, bool& handled, UpdateCost& cost)
     for (uint32_t b : edited) {
       const MeshBuild& mb = H.meshBuilds[b];
       copy(D.dVerts.ptr + mb.vertexOffset, &H.verts[mb.vertexOffset], mb.m->vertices.size() * sizeof(FVertex), hipMemcpyHostToDevice);
-      copy(D.dTriShade.ptr + mb.shadeBase, &H.triShade[mb.shadeBase], mb.m->faces.size() * sizeof(TriShade), hipMemcpyHostToDevice);
+    }
+    // (behind the vertex uploads on the same stream, in front of k_refit_tris, which reads TriShade::p)
+    if (rc == GI_C_OK) for (uint32_t b : edited) {
+      const MeshBuild& mb = H.meshBuilds[b];
+      if (!launchGatherShade(st, D.dTriShade.ptr, shadeCount, mb.shadeBase, (uint32_t)mb.m->faces.size(), D.dVerts.ptr, (uint32_t)H.verts.size())) {
+        setError("internal: shading records outside the array"); rc = GI_C_ERROR; break; } // (cannot happen: asked above)
     }
     copy(dEdited.ptr, editedOfInstance.data(), editedOfInstance.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
     copy(dRanges.ptr, ranges.data(), ranges.size() * sizeof(RefitRange), hipMemcpyHostToDevice);
@@ -1219,8 +1252,12 @@ static int updateVertices(GiCScene* s, bool& handled, UpdateCost& cost)
   }
   const double t2 = nowMs();
   cost.uploadMs = t2 - t0; // (no tree was built: buildMs stays 0)
-  if (getenv("GATLING_BUILD_TIMING")) fprintf(stderr, "[gatling_gi] vertex update: %zu mesh(es), %zu refit unit(s), %zu level launch(es), host %.2f ms, device %.2f "
-                                              "ms\n", edited.size(), units.size(), levels.size(), t1 - t0, t2 - t1);
+  if (getenv("GATLING_BUILD_TIMING")) {
+    size_t sent = editedOfInstance.size() * sizeof(uint32_t) + ranges.size() * sizeof(RefitRange), gathered = 0; // per device
+    for (uint32_t b : edited) { sent += H.meshBuilds[b].m->vertices.size() * sizeof(FVertex); gathered += H.meshBuilds[b].m->faces.size() * sizeof(TriShade); }
+    fprintf(stderr, "[gatling_gi] vertex update: %zu mesh(es), %zu refit unit(s), %zu level launch(es), host %.2f ms, device %.2f ms, %zu bytes sent per device, "
+                    "%zu bytes of shading records gathered there\n", edited.size(), units.size(), levels.size(), t1 - t0, t2 - t1, sent, gathered);
+  }
   handled = true;
   return GI_C_OK;
 }
@@ -1255,6 +1292,98 @@ bool topologyUpdatesWanted(const GiCScene* s)
   const long o = optionValue("topology_updates", -1);
   return o >= 0 ? o == 1 : s->optTopologyUpdates == 1;
 }
+// Resyncs (opt-in on top of topology and vertex updates: GI_C_SCENE_OPTION_RESYNC_REFITS / GATLING_OPTIONS=resync_refits=1).  The delegate answers a points or
+// primvar change of a prim with destroy + create of a mesh whose faces did not change: retire + append would leave N dead triangles behind per frame and
+// build a subtree whose topology the resident one already has.  adoptResyncs pairs each retiring mesh R (retired, its MeshBuild not hidden) with a fresh mesh
+// F (no records, visible, with faces and a valid material), both taken in creation order, the first partner that qualifies wins; F ADOPTS R's resident
+// records: the MeshBuild points at F, F counts as built, R is freed, nothing is retired or appended for the pair.  What differs between the two goes down the
+// paths that run behind updateTopology: vertices -> GiCMesh::vertsEdited (only if the bytes differ) -> updateVertices' refit; material assignment and primvars
+// -> DIRTY_MATERIALS -> updateMaterials; transforms -> xformDirty / instDirty -> updateTransforms.
+// A pair qualifies if faces (count and bytes), face ids, maxFaceId, vertex count, handedness, sidedness, id, instance count and instance ids are equal; if
+// updateVertices could refit R's records with F's points (not hidden; positions usable in object and world space; every part whole with its levels; no
+// inactive triangle at the scene's build); and if no fresh mesh that is not itself adopted precedes F in GiCScene::meshes (appended meshes lie behind every
+// built one).  Any other pair is retired and appended as before.
+// Scene order: F sits where it was created, its records where R's sat.  From the first adoption on (SceneHost::reordered) id bases are accumulated in the
+// order of GiCScene::meshes (sceneOrder, planVisibility), and the plan's idDelta renumbers F's triangles and those of every mesh that was behind R through
+// k_patch_visibility.  Storage -- instFirst, triFirst, shadeBase, vertexOffset, meshIdx, node ranges -- stays where it is.
+static bool resyncRefitsWanted(const GiCScene* s)
+{
+  if (!topologyUpdatesWanted(s) || !vertexUpdatesWanted(s)) return false;
+  const long o = optionValue("resync_refits", -1);
+  return o >= 0 ? o == 1 : s->optResyncRefits == 1;
+}
+// R's resident records fit F: everything the records, the tree's topology and the AOV tables were made from is equal
+static bool sameRecords(const GiCMesh* r, const GiCMesh* f)
+{
+  return r->faces.size() == f->faces.size() && memcmp(r->faces.data(), f->faces.data(), r->faces.size() * sizeof(GiCFace)) == 0 && r->faceIds == f->faceIds &&
+      r->maxFaceId == f->maxFaceId && r->vertices.size() == f->vertices.size() && r->flipFacing == f->flipFacing && r->doubleSided == f->doubleSided &&
+      r->id == f->id && r->instanceTransforms.size() == f->instanceTransforms.size() && r->instanceIds == f->instanceIds;
+}
+static bool samePrimvars(const std::vector<GiCPrimvar>& a, const std::vector<GiCPrimvar>& b)
+{
+  if (a.size() != b.size()) return false;
+  for (size_t i = 0; i < a.size(); i++) if (a[i].name != b[i].name || a[i].type != b[i].type || a[i].interpolation != b[i].interpolation ||
+      a[i].data.size() != b[i].data.size() || memcmp(a[i].data.data(), b[i].data.data(), a[i].data.size() * sizeof(float)) != 0) return false;
+  return true;
+}
+// updateVertices' preconditions for the MeshBuild `b` with F's points and transforms; the instance records F gives are left in `inst`
+// (The world-space pass is knowingly run twice in a sync that adopts: here with the transforms F brings, and again in updateVertices with the resident
+// ones, which are R's until updateTransforms has run -- the two differ whenever the resync moved the mesh, so neither result stands in for the other.  On
+// C5 this pass is part of the 1.7 ms a topology update that adopts a 40 960-triangle mesh takes.)
+static bool refitsWith(const GiCScene* s, const SceneHost& H, uint32_t b, const GiCMesh* f, std::vector<InstanceRec>& inst)
+{
+  const MeshBuild& mb = H.meshBuilds[b];
+  if (mb.hidden || s->stats.inactiveTriangleCount != 0u || !usableVertexPositions(f->vertices.data(), f->vertices.size())) return false;
+  if ((size_t)mb.vertexOffset + f->vertices.size() > H.verts.size() || (size_t)mb.shadeBase + f->faces.size() > H.triShade.size()) return false;
+  if (H.partitioned) for (const InstPart& P : H.parts)
+    if (P.meshBuild == b && (P.activeTris != P.nf || P.levelStart.size() < 2u || P.levelStart.back() != P.nodeCount)) return false;
+  inst.resize(mb.instCount);
+  for (uint32_t ii = 0; ii < mb.instCount; ii++) { inst[ii] = makeInstanceRec(f, mb.meshIdx, ii); if (!usableInstance(inst[ii])) return false; }
+  std::atomic<bool> worldOk{true};
+  const size_t nf = f->faces.size();
+  parallelOver(mb.instCount, [&](size_t ii) {
+    for (size_t k = 0; k < nf; k++) {
+      TriRec t; flattenTriangle(inst[ii], true, f, (uint32_t)k, t);
+      float lo[3], hi[3];
+      if (!refit_tri_box(t.v0, t.e1, t.e2, lo, hi)) { worldOk = false; return; }
+    }
+  });
+  return worldOk;
+}
+static uint32_t adoptResyncs(GiCScene* s, SceneHost& H)
+{
+  std::vector<uint32_t> retiring; // indices into H.meshBuilds, creation order
+  for (uint32_t b = 0; b < (uint32_t)H.meshBuilds.size(); b++) if (H.meshBuilds[b].m->retired && !H.meshBuilds[b].hidden) retiring.push_back(b);
+  uint32_t adopted = 0;
+  if (retiring.empty()) return 0u;
+  std::vector<InstanceRec> inst;
+  for (GiCMesh* f : s->meshes) {
+    if (f->builtInstances != 0xffffffffu || !f->visible || f->faces.empty()) continue; // (as updateTopology: not a fresh mesh)
+    if (std::find(s->materials.begin(), s->materials.end(), f->material) == s->materials.end()) continue;
+    size_t k = 0;
+    while (k < retiring.size() && !(sameRecords(H.meshBuilds[retiring[k]].m, f) && refitsWith(s, H, retiring[k], f, inst))) k++;
+    if (k == retiring.size()) break; // this mesh will be appended: every fresh mesh behind it lies behind an appended one
+    MeshBuild& mb = H.meshBuilds[retiring[k]];
+    GiCMesh* r = const_cast<GiCMesh*>(mb.m);
+    // what differs goes down the paths behind this update.  (An edit of R that was still due when it was destroyed: its vertices are not the resident ones;
+    // its material-side edits raised DIRTY_MATERIALS themselves; transforms are compared with the resident instance records.)
+    f->vertsEdited = r->vertsEdited || memcmp(r->vertices.data(), f->vertices.data(), f->vertices.size() * sizeof(GiCVertex)) != 0;
+    if (r->material != f->material || !samePrimvars(r->primvars, f->primvars) || !samePrimvars(r->instancerPrimvars, f->instancerPrimvars)) s->dirty |= DIRTY_MATERIALS;
+    f->xformDirty = false; f->instDirty.assign(mb.instCount, 0);
+    for (uint32_t ii = 0; ii < mb.instCount; ii++)
+      if (memcmp(inst[ii].o2w, H.instances[mb.instFirst + ii].o2w, sizeof(inst[ii].o2w)) != 0) { f->instDirty[ii] = 1; f->xformDirty = true; }
+    if (f->xformDirty) s->dirty |= DIRTY_XFORM; else f->instDirty.clear();
+    f->builtInstances = mb.instCount; f->visToggled = false;
+    mb.m = f;
+    s->retiredMeshes.erase(std::remove(s->retiredMeshes.begin(), s->retiredMeshes.end(), r), s->retiredMeshes.end());
+    delete r;
+    retiring.erase(retiring.begin() + (ptrdiff_t)k);
+    H.reordered = true; adopted++;
+    if (retiring.empty()) break;
+  }
+  return adopted;
+}
+
 // faces from which an appended part is built on the device when the scene's device builder is on (GATLING_OPTIONS=device_parts_min).  Measured for ONE part
 // (tools/time_topology_edit.py): buildPart 0.57 / 1.2 / 2.4 / 5.0 / 11.3 ms at 1 / 2 / 4 / 8 / 16 Ki faces, the device route 2.1 / 2.3 /
 // 2.4 / 3.1 / 3.2 ms (a floor of ~2 ms of launches and stream synchronisations): they cross at 4 Ki.  Several parts are built in parallel by the host and
@@ -1269,6 +1398,12 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
   if (H.meshRecs.size() != H.meshBuilds.size()) return GI_C_OK;
   for (const MeshBuild& mb : H.meshBuilds) if (mb.m->builtInstances != mb.instCount) return GI_C_OK; // (cannot happen: count changes ask for the rebuild)
   const double t0 = nowMs();
+  // --- resyncs: a retiring and a fresh mesh with the same faces become a vertex edit of the resident records
+  // adoptResyncs changes the scene at once -- MeshBuild::m repointed, R freed, F counted as built, dirty bits raised -- so EVERY decline behind this point must
+  // lead to the full build (it does: a decline raises DIRTY_BVH and rebuildDue, and buildScene makes all of that state anew from GiCScene::meshes).  Until
+  // updateVertices has run behind this update, H.verts / H.triShade still hold R's points while a re-layout below builds the parts from F's: F is marked
+  // vertsEdited whenever the bytes differ, and an updateVertices that declines rebuilds as well.
+  const uint32_t adopted = resyncRefitsWanted(s) ? adoptResyncs(s, H) : 0u;
   // --- the meshes to append: what a fresh build would hold and the resident scene does not, all of them behind every live built mesh
   struct NewMesh { GiCMesh* m; uint32_t material; };
   std::vector<NewMesh> fresh;
@@ -1301,7 +1436,7 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
   if (appendedParts && (partsNow + appendedParts) * 2u + 16u > topCap) return GI_C_OK; // the top tree may outgrow its range
   const uint32_t nDev = residentDeviceCount(s);
   const bool timing = getenv("GATLING_BUILD_TIMING") != nullptr;
-  if (fresh.empty() && retiring == 0u) { // the edited meshes are not part of a fresh build either (invisible, no faces, no valid material)
+  if (fresh.empty() && retiring == 0u && adopted == 0u) { // the edited meshes are not part of a fresh build either (invisible, no faces, no valid material)
     for (GiCMesh* m : s->meshes) if (m->builtInstances == 0xffffffffu) { m->visToggled = false; m->vertsEdited = false; }
     handled = true;
     return GI_C_OK;
@@ -1318,7 +1453,7 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
   double buildMs = converted ? nowMs() - t0 : 0.0;
   // --- retire: hidden for good, the meshes behind renumbered
   VisibilityPlan plan;
-  if (!planVisibility(H, [](const MeshBuild& mb) { return mb.hidden || mb.m->retired; }, plan)) return GI_C_OK;
+  if (!planVisibility(s, H, [](const MeshBuild& mb) { return mb.hidden || mb.m->retired; }, plan)) return GI_C_OK;
   applyVisibilityPlanOnHost(H, plan);
   const uint32_t oldTris = s->triCount, oldInstances = (uint32_t)H.instances.size();
   // --- append, host side: the MeshBuilds and everything that does not depend on a tree
@@ -1334,7 +1469,7 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
     for (const GiCVertex& vIn : m->vertices) H.verts.push_back(packVertex(vIn));
     H.meshBuilds.push_back(MeshBuild{m, vertexOffset, matFlags, (uint32_t)H.instances.size(), instCount, triFirst, meshIdx, faceIdAovOf(m)});
     H.meshBuilds.back().shadeBase = (uint32_t)H.triShade.size(); H.meshBuilds.back().idBase = (uint32_t)idBase;
-    for (const GiCFace& f : m->faces) H.triShade.push_back(packTriShade(m, f, vertexOffset));
+    for (const GiCFace& f : m->faces) H.triShade.push_back(packTriShade(m->vertices.data(), f, vertexOffset));
     // (25 % slack, as on the device: a std::vector would double 0.7 GB of triangles on the first append to C5 and copy them on every later doubling)
     auto grown = [](auto& v, size_t n) { if (v.capacity() < n) v.reserve(n + n / 4u); v.resize(n); };
     grown(H.instances, H.instances.size() + instCount); grown(H.bvh.tris, (size_t)triFirst + (size_t)instCount * nf); grown(H.triFaceId, H.bvh.tris.size());
@@ -1506,9 +1641,10 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
   if (rc != GI_C_OK) return GI_C_ERROR;
   const double t2 = nowMs();
   cost.buildMs = buildMs; cost.uploadMs = std::max(t2 - t0 - buildMs, 0.0);
-  if (timing) fprintf(stderr, "[gatling_gi] topology update:%s %u mesh(es) retired, %zu appended, %zu part(s) built, %u of them on the device (k_place_part), "
-                              "%llu live + %llu retired triangle(s), %u resident, builds %.2f ms, rest %.2f ms\n", converted
-                                  ? " scene re-laid out as per-instance subtrees," : "", retiring, fresh.size(), newParts.size(), builtOnDevice,
+  s->resyncCount += adopted;
+  if (timing) fprintf(stderr, "[gatling_gi] topology update:%s %u mesh(es) retired, %u adopted by their resync, %zu appended, %zu part(s) built, %u of them on the "
+                              "device (k_place_part), %llu live + %llu retired triangle(s), %u resident, builds %.2f ms, rest %.2f ms\n", converted
+                                  ? " scene re-laid out as per-instance subtrees," : "", retiring, adopted, fresh.size(), newParts.size(), builtOnDevice,
                       (unsigned long long)live, (unsigned long long)retired, s->triCount, cost.buildMs, cost.uploadMs);
   handled = true;
   return GI_C_OK;

@@ -39,34 +39,7 @@ float f16ToF32(uint16_t h)
 }
 uint32_t packHalf2x16(float a, float b) { return (uint32_t)f32ToF16(a) | ((uint32_t)f32ToF16(b) << 16); }
 
-// _EncodeDirection, Gi.cpp:287-300 (glm::packUnorm2x16 rounds)
-uint32_t encodeDirection(const float* vin)
-{
-  float x = vin[0], y = vin[1], z = vin[2];
-  float inv = 1.0f / sqrtf((x * x + y * y) + z * z);
-  x *= inv; y *= inv; z *= inv;
-  float s = fabsf(x) + fabsf(y) + fabsf(z);
-  x /= s; y /= s; z /= s;
-  float px = x >= 0.0f ? 1.0f : -1.0f, py = y >= 0.0f ? 1.0f : -1.0f, ex, ey;
-  if (z < 0.0f) { ex = (1.0f - fabsf(y)) * px; ey = (1.0f - fabsf(x)) * py; } else { ex = x; ey = y; }
-  ex = ex * 0.5f + 0.5f; ey = ey * 0.5f + 0.5f;
-  ex = std::min(std::max(ex, 0.0f), 1.0f); ey = std::min(std::max(ey, 0.0f), 1.0f);
-  return (uint32_t)nearbyintf(ex * 65535.0f) | ((uint32_t)nearbyintf(ey * 65535.0f) << 16);
-}
-
-// decode_direction (common.glsl:198-207) evaluated once per vertex on the host, operation for operation what
-// gi_decode_direction / the oracle execute (IEEE fp32, no contraction), so results stay bit-identical.
-void decodeDirection(uint32_t e, float out[3])
-{
-  float ex = (float)(e & 0xffffu) / 65535.0f, ey = (float)(e >> 16) / 65535.0f;
-  ex = ex * 2.0f - 1.0f; ey = ey * 2.0f - 1.0f;
-  float x = ex, y = ey, z = 1.0f - fabsf(ex) - fabsf(ey);
-  float t = (-z > 0.0f) ? -z : 0.0f;
-  x += (x >= 0.0f) ? -t : t;
-  y += (y >= 0.0f) ? -t : t;
-  float inv = 1.0f / sqrtf((x * x + y * y) + z * z);
-  out[0] = x * inv; out[1] = y * inv; out[2] = z * inv;
-}
+// (encodeDirection / decodeDirection: gi_pack.h)
 
 // Turbo colour map (A. Mikhailov's polynomial fit of Google's Turbo look-up table; the reference indexes the 256-entry table,
 // Gi.cpp:338-341).  Same association as the oracle's turbo_colormap.
@@ -344,6 +317,8 @@ int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value)
   if (option == GI_C_SCENE_OPTION_VERTEX_UPDATES) { scene->optVertexUpdates = value == 1 ? 1 : 0; return GI_C_OK; } // (likewise: future vertex edits)
   // (likewise: future mesh creations and destructions)
   if (option == GI_C_SCENE_OPTION_TOPOLOGY_UPDATES) { scene->optTopologyUpdates = value == 1 ? 1 : 0; return GI_C_OK; }
+  // (likewise: how future destroy + create pairs are applied; read only with options 12 and 13 wanted)
+  if (option == GI_C_SCENE_OPTION_RESYNC_REFITS) { scene->optResyncRefits = value == 1 ? 1 : 0; return GI_C_OK; }
   setError("unknown scene option"); return GI_C_ERROR;
 }
 

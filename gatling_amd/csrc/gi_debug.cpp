@@ -352,6 +352,31 @@ extern "C" int giCDebugSceneRefitCheck(const GiCScene* scene, uint32_t deviceInd
   return differ;
 }
 
+// giCDebugSceneShadeCheck: the resident vertex and shading records against the host's copies, whole arrays (a vertex update sends the former and gathers
+// the latter on the device: gi_refit.hip k_gather_shade)
+extern "C" int giCDebugSceneShadeCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t* outRecords)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!g_ctx.initialized || !s) { setError("giCDebugSceneShadeCheck: bad arguments"); return -1; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  if (!s->host) { setError("giCDebugSceneShadeCheck: the scene has not been built (render it once)"); return -1; }
+  if (deviceIndex > s->replicas.size() || deviceIndex >= sceneDeviceCount(s)) { setError("giCDebugSceneShadeCheck: no such device copy"); return -1; }
+  SceneDevice& D = sceneDevice(s, deviceIndex);
+  const SceneHost& H = *s->host;
+  std::vector<TriShade> shade(H.triShade.size()); std::vector<FVertex> verts(H.verts.size());
+  if (hipSetDevice(g_ctx.devs[D.slot].device) != hipSuccess || D.dTriShade.count < shade.size() || D.dVerts.count < verts.size() ||
+      (!shade.empty() && hipMemcpy(shade.data(), D.dTriShade.ptr, shade.size() * sizeof(TriShade), hipMemcpyDeviceToHost) != hipSuccess) ||
+      (!verts.empty() && hipMemcpy(verts.data(), D.dVerts.ptr, verts.size() * sizeof(FVertex), hipMemcpyDeviceToHost) != hipSuccess)) {
+    (void)hipSetDevice(g_ctx.device); setError("giCDebugSceneShadeCheck: download failed"); return -1;
+  }
+  (void)hipSetDevice(g_ctx.device);
+  int differ = 0;
+  for (size_t i = 0; i < shade.size(); i++) if (memcmp(&shade[i], &H.triShade[i], sizeof(TriShade)) != 0) differ++;
+  for (size_t i = 0; i < verts.size(); i++) if (memcmp(&verts[i], &H.verts[i], sizeof(FVertex)) != 0) differ++;
+  if (outRecords) *outRecords = (uint32_t)shade.size();
+  return differ;
+}
+
 // giCDebugShadeClass: which k_shade variant an (untextured) material's hits are binned for -- host only
 extern "C" int giCDebugShadeClass(const GiCMaterialDesc* desc)
 {
@@ -526,6 +551,15 @@ extern "C" int giCDebugSceneTopologyUpdateCount(const GiCScene* scene, uint64_t*
   if (!s || !outCount) { setError("giCDebugSceneTopologyUpdateCount: bad arguments"); return GI_C_ERROR; }
   std::lock_guard<std::mutex> guard(s->mutex);
   *outCount = s->updateCounts[UPDATE_TOPOLOGY];
+  return GI_C_OK;
+}
+
+extern "C" int giCDebugSceneResyncCount(const GiCScene* scene, uint64_t* outCount)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!s || !outCount) { setError("giCDebugSceneResyncCount: bad arguments"); return GI_C_ERROR; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  *outCount = s->resyncCount;
   return GI_C_OK;
 }
 

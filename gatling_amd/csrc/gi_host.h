@@ -37,6 +37,7 @@
 #include "gi_kernels.h"
 #include "gi_image.h"
 #include "gi_options.h"
+#include "gi_pack.h"
 #include "gi_types.h"
 
 using namespace gi;
@@ -146,8 +147,7 @@ struct DeviceBuffer {
 uint16_t f32ToF16(float f);
 float f16ToF32(uint16_t h);
 uint32_t packHalf2x16(float a, float b);
-uint32_t encodeDirection(const float* vin);
-void decodeDirection(uint32_t e, float out[3]);
+// (encodeDirection, decodeDirection, packVertex, packTriShade: gi_pack.h)
 void turboColormap(float x, float* rgb);
 float cutoutOpacity(const MaterialRec& m);
 void deriveMaterialConstants(MaterialRec& m);
@@ -328,6 +328,9 @@ struct SceneHost {
   // a vertex update refitted a flat host-built tree in device memory: the host copies of its nodes, triangles and face ids were dropped (they would be
   // stale), and the scene is treated as a device-built one is -- the re-layout of the first transform edit makes them anew
   bool hostTreeDropped = false;
+  // a mesh adopted the records of the one it replaced (updateTopology, GI_C_SCENE_OPTION_RESYNC_REFITS): the order of meshBuilds is no longer the scene's, and
+  // scene-order ids are accumulated over GiCScene::meshes (gi_build.cpp sceneOrder)
+  bool reordered = false;
 };
 
 enum : uint32_t { UPDATE_FULL = 0, UPDATE_TRANSFORM = 1, UPDATE_MATERIAL = 2, UPDATE_VISIBILITY = 3, UPDATE_VERTEX = 4, UPDATE_TOPOLOGY = 5 }; // GiCScene::updateCounts
@@ -397,6 +400,9 @@ struct GiCScene : SceneDevice {
   // DIRTY_BVH was raised by giCCreateMesh, giCDestroyMesh or a setter on a mesh that is not part of the built scene (raiseTopology): syncSceneGeometry may
   // answer with updateTopology; without the option it turns this into rebuildDue
   bool topologyDue = false;
+  // GI_C_SCENE_OPTION_RESYNC_REFITS: 1 = a destroyed mesh and a created one with the same faces become a vertex edit of the resident records (updateTopology
+  // adoptResyncs; read only with topology and vertex updates wanted); meshes adopted since the scene was created (giCDebugSceneResyncCount)
+  int32_t optResyncRefits = 0; uint64_t resyncCount = 0;
   std::vector<GiCMesh*> retiredMeshes; // destroyed meshes the resident scene still refers to (GiCMesh::retired): freed by buildScene and with the scene
   ~GiCScene() { for (GiCMesh* m : retiredMeshes) delete m; }
 };

@@ -81,10 +81,15 @@ void launchPlacePart(hipStream_t s, const Node8* partNodes, uint32_t partNodeCou
 // gi_refit.hip: a vertex edit applied to the device-resident scene (gi_build.cpp updateVertices).  launchRefitTris makes the world-space corners of the records
 // of edited instances (editedOfInstance[t.instance] != 0) again from their shading records and instance transforms; launchRefitLevel refits one tree level:
 // thread i handles node ranges[r].nodeFirst + (i - ranges[r].threadBase) of the last range r with threadBase <= i, reading the float boxes (8 floats per
-// node) of the level below and writing its own
+// node) of the level below and writing its own.  launchGatherShade makes the shading records [first, first + count) again from the vertex records they
+// name (TriShade::vi; gi_refit.h refit_gather_shade): it runs behind the vertex upload and in front of launchRefitTris.
+// gatherShadeRangeOk: the range lies inside the array and its nine threads per record fit a launch; launchGatherShade returns false, and launches nothing, where
+// it does not hold -- the records would stay stale, so updateVertices asks first and declines to the rebuild
 struct RefitRange { uint32_t threadBase, nodeFirst; };
 void launchRefitTris(hipStream_t s, TriRec* tris, uint32_t triCount, const InstanceRec* instances, uint32_t instanceCount, const uint32_t* editedOfInstance,
     const TriShade* triShade, uint32_t shadeCount);
+bool gatherShadeRangeOk(uint32_t shadeCount, uint32_t first, uint32_t count);
+bool launchGatherShade(hipStream_t s, TriShade* triShade, uint32_t shadeCount, uint32_t first, uint32_t count, const FVertex* verts, uint32_t vertCount);
 void launchRefitLevel(hipStream_t s, Node8* nodes, uint32_t nodeCount, float* boxes, const RefitRange* ranges, uint32_t rangeCount, uint32_t threads,
     const TriRec* tris, uint32_t triCount, const InstanceRec* instances, uint32_t instanceCount, const TriShade* triShade, uint32_t shadeCount);
 void launchSpin(hipStream_t s, unsigned long long ns);             // test hook: occupies a stream for ~ns nanoseconds

@@ -48,6 +48,9 @@
 //                                  scene / refit the resident tree on the device (gi_build.cpp updateVertices, gi_refit.hip)
 //   topology_updates     -1        -1 = the scene option decides (GI_C_SCENE_OPTION_TOPOLOGY_UPDATES), 0 / 1 = mesh creations and destructions rebuild the
 //                                  scene / are applied to the resident scene (gi_build.cpp updateTopology)
+//   resync_refits        -1        -1 = the scene option decides (GI_C_SCENE_OPTION_RESYNC_REFITS), 0 / 1 = a destroyed and a created mesh with the same
+//                                  faces are retired and appended / become a vertex refit of the resident records (gi_build.cpp adoptResyncs); read
+//                                  only with topology_updates and vertex_updates wanted
 //   device_parts_min     4096      topology updates with the device builder on: an appended part of at least this many faces (and more than 128) is built
 //                                  on the device (buildBvh8Device + gi_patch.hip k_place_part), a smaller one by the host (buildPart).  The measured
 //                                  crossover for one part

@@ -57,6 +57,31 @@ GI_REFIT_HD inline bool refit_tri_box(const float v0[3], const float e1[3], cons
   return true;
 }
 
+// gi_build.cpp packTriShade as a gather: the shading record of a mesh face is the FVertex records of its three corners (named by vi[k], absolute indices)
+// laid out per attribute.  packVertex and packTriShade run the same sanitising and the same encode / decode on the same inputs, so the gathered words are
+// bytewise packTriShade's (giCDebugGatherShade holds that).  Words 0..35 of the 40-word record are gathered -- p 0..8, n 9..17, t 18..26, uv 27..32, bsign
+// 33..35 --, vi and pad (36..39) are read, never written.  A record with a corner outside the vertex array is left as it is (cannot happen: giCCreateMesh
+// checks the faces).  Words are moved as integers: no float operation touches them.
+constexpr uint32_t kShadeGatherWords = 36u;
+GI_REFIT_HD inline bool refit_shade_corners_ok(const uint32_t vi[3], uint32_t vertCount) { return vi[0] < vertCount && vi[1] < vertCount && vi[2] < vertCount; }
+// word w < 36 of the record with corners vi (all three inside the array)
+GI_REFIT_HD inline uint32_t refit_shade_word(const FVertex* verts, const uint32_t vi[3], uint32_t w)
+{
+  uint32_t k, src; // corner, word of its FVertex (pos 0..2, bsign 3, normal 4..6, u 7, tangent 8..10, v 11)
+  if (w < 27u) { k = (w % 9u) / 3u; src = (w / 9u) * 4u + w % 3u; }
+  else if (w < 33u) { k = (w - 27u) >> 1; src = ((w - 27u) & 1u) ? 11u : 7u; }
+  else { k = w - 33u; src = 3u; }
+  uint32_t out;
+  __builtin_memcpy(&out, reinterpret_cast<const char*>(verts + vi[k]) + 4u * src, 4);
+  return out;
+}
+GI_REFIT_HD inline void refit_gather_shade(const FVertex* verts, uint32_t vertCount, TriShade& q)
+{
+  if (!refit_shade_corners_ok(q.vi, vertCount)) return;
+  char* words = reinterpret_cast<char*>(&q);
+  for (uint32_t w = 0; w < kShadeGatherWords; w++) { const uint32_t x = refit_shade_word(verts, q.vi, w); __builtin_memcpy(words + 4u * w, &x, 4); }
+}
+
 // What a refit reads beside the nodes.  `instances` / `triShade` may be null (a tree over bare triangles, giCDebugRefitBvh): they give a record whose edges
 // the incremental visibility path zeroed (gi_patch.hip k_patch_visibility, flat layouts) the box of the triangle it will be again when the mesh is shown.
 struct RefitScene {

@@ -378,7 +378,8 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * built against an earlier header never sees.  A caller probes for them: giCSetSceneOption answers GI_C_ERROR for an option the library does not know.
  * The same holds for GI_C_SCENE_OPTION_VISIBILITY_UPDATES, giCDebugSceneVisibilityUpdateCount, giCDebugSceneClassState, giCDebugMissRect and giCDebugPathWalkStats, and for
  * giCSetMeshVertices, GI_C_SCENE_OPTION_VERTEX_UPDATES, giCDebugSceneVertexUpdateCount, giCDebugRefitBvh and giCDebugSceneRefitCheck, and for
- * GI_C_SCENE_OPTION_TOPOLOGY_UPDATES and giCDebugSceneTopologyUpdateCount. */
+ * GI_C_SCENE_OPTION_TOPOLOGY_UPDATES and giCDebugSceneTopologyUpdateCount, and for GI_C_SCENE_OPTION_RESYNC_REFITS, giCDebugSceneResyncCount,
+ * giCDebugGatherShade and giCDebugSceneShadeCheck. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -566,6 +567,19 @@ int giCGetRenderStats(const GiCScene* scene, GiCRenderStats* out);
  * spent building the new subtrees and uploadMs the rest.  The first such edit of a scene re-lays it out as per-instance subtrees (about one build).
  * GATLING_OPTIONS=topology_updates=0|1 overrides the option (hdGatling sets no scene options).  DESIGN.md section 6. */
 #define GI_C_SCENE_OPTION_TOPOLOGY_UPDATES 13
+/* [ext] Resyncs as refits: value 1 = when GI_C_SCENE_OPTION_TOPOLOGY_UPDATES and GI_C_SCENE_OPTION_VERTEX_UPDATES are both wanted (the option is read only
+ * then), a mesh destroyed and a mesh created since the last giCRender whose faces are the same -- hdGatling's answer to a points or primvar change of a prim
+ * -- are recognised as ONE edited mesh: the new mesh ADOPTS the resident records of the destroyed one, nothing is retired and nothing is appended, and what
+ * differs goes down the existing paths: new points refit the resident subtree (only if the vertex bytes differ), another material or other primvars take the
+ * material update, other transforms the transform update; 0 = off (default): the pair is retired and appended.  A pair is adopted when the faces (count and
+ * bytes), face ids, maxFaceId, vertex count, isLeftHanded, isDoubleSided, id, instance count and instance ids are equal; when the vertex update could refit
+ * the destroyed mesh's records with the new points (it is not hidden by the visibility path, the positions are finite and within 1e18 in object and world
+ * space, no triangle of its subtrees or of the scene was inactive at the build); and when no new mesh that is not itself adopted was created before it.
+ * Meshes are paired in creation order, the first partner that qualifies wins.  Any other pair is retired and appended as without the option -- never
+ * rebuilt for that reason.  The adopting mesh keeps its place in creation order: its triangles and those of the meshes behind the destroyed one get the ids a
+ * fresh build gives them.  Resident triangle and node counts do not grow with such edits, so the rebuild that compacts retired triangles does not come due.
+ * The image does not depend on the option.  GATLING_OPTIONS=resync_refits=0|1 overrides it (hdGatling sets no scene options).  DESIGN.md section 6. */
+#define GI_C_SCENE_OPTION_RESYNC_REFITS 14
 int giCGetLookaheadStats(const GiCScene* scene, GiCLookaheadStats* out);
 int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value);
 /* [ext] closest hit of one ray through the device traversal kernel (parity tests of the BVH8 path).
@@ -633,6 +647,17 @@ int giCDebugSceneVertexUpdateCount(const GiCScene* scene, uint64_t* outCount);
 /* [ext] [debug] how often the scene was brought up to date by an incremental topology update (GI_C_SCENE_OPTION_TOPOLOGY_UPDATES); not counted in
  * giCDebugSceneUpdateCounts either. */
 int giCDebugSceneTopologyUpdateCount(const GiCScene* scene, uint64_t* outCount);
+/* [ext] [debug] how many meshes adopted the resident records of the mesh they replaced (GI_C_SCENE_OPTION_RESYNC_REFITS) since the scene was created.  An update
+ * that only adopts is counted as one topology update. */
+int giCDebugSceneResyncCount(const GiCScene* scene, uint64_t* outCount);
+/* [ext] [debug] host-only check that the shading records a vertex update GATHERS from the packed vertex records (gi_refit.h refit_gather_shade, the function the
+ * device kernel k_gather_shade runs) are the records the scene build packs: both made for the mesh (`vertices`, `faces`: 3 indices per face), compared
+ * bytewise.  Returns the number of records whose 160 bytes differ (0 is the contract), <0 on error (a null array, an index outside the vertices). */
+int giCDebugGatherShade(const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount);
+/* [ext] [debug] the vertex and shading records resident on device `deviceIndex` of a scene rendered at least once, downloaded and compared with the host's copies
+ * over the WHOLE arrays (a store outside an edited range is seen).  Returns the number of shading records whose 160 bytes differ plus the vertex records
+ * whose 48 bytes differ (0), <0 on error; outRecords: shading records compared (0 for a scene within LDS, which keeps none). */
+int giCDebugSceneShadeCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t* outRecords);
 /* [ext] what the last scene sync derived from the visible meshes' materials, the state that picks a render's kernel variants: out[0] the material classes in
  * use (one bit each), [1] those with a textured material, [2] and [3] the same per shade class, [4] 1 when some visible triangle has cutout opacity.  Host
  * only: no device work. */

@@ -9,6 +9,10 @@ soup (1 M triangles, one mesh), in one process: python tools/time_topology_edit.
      device_parts_min belongs.  The part is a random triangle soup appended to the small interior; `partMs` is GiCRenderStats.bvhBuildMs of the render that
      appended it (the part builds alone; best of three appends), `restMs` its uploadMs
 
+  5. --resync [--quick]: playback of the C5 clutter mesh -- 16 resyncs -- with topology and vertex updates on and GI_C_SCENE_OPTION_RESYNC_REFITS off and on:
+     the same library, one process per leg (`--resync-leg 0|1`), the legs alternating, two rounds.  Per leg: every frame's bvhBuildMs / uploadMs, the
+     16-frame total, resident triangles after the 16th and the counters; the library's timing lines (stderr) split each update into host and device time
+
 `sync` below is bvhBuildMs + uploadMs of the render that applied the edit; the library's own line (GATLING_BUILD_TIMING) goes to stderr.  --quick runs the
 scenes at test size and the sweep to 16 Ki.  Prints one line per measurement and a JSON summary last."""
 import copy
@@ -106,8 +110,53 @@ def sweep(result, sizes):
     result["partSweep"] = rows
 
 
+def resync_leg(on, quick, frames=16):
+    """One process, one setting of the option: the first resync (the re-layout) apart, then `frames` resyncs of the clutter mesh."""
+    capi.initialize(0)
+    c5 = interior_scene(clutter_instances=20, subdivisions=2, prototypes=3, material_count=4) if quick else interior_scene()
+    tris = lambda i: len(c5.meshes[i].faces) * len(c5.meshes[i].instance_transforms)
+    clutter = [i for i, m in enumerate(c5.meshes) if m.name.startswith("/Clutter")]
+    name = c5.meshes[min(clutter, key=lambda i: abs(tris(i) - 40960))].name
+    sc = capi.Scene(c5)
+    try:
+        sc.set_option(capi.OPTION_TOPOLOGY_UPDATES, 1); sc.set_option(capi.OPTION_VERTEX_UPDATES, 1); sc.set_option(capi.OPTION_RESYNC_REFITS, on)
+        sc.render(QUICK, 64, 36)
+        out = {"resyncRefits": on, "triangles": sc.desc.triangle_count(), "build": sync_ms(sc), "first-edit": resync(sc, name, 1)}
+        out["frames"] = [resync(sc, name, 2 + k) for k in range(frames)]
+        out["totalSyncMs"] = round(sum(f["sync"] for f in out["frames"]), 2)
+        out["totalRenderCallMs"] = round(sum(f["renderCallMs"] for f in out["frames"]), 2)
+        out["residentTriangles"] = sc.stats()["triangleCount"]
+        out["counts"] = dict(sc.update_counts(), topology=sc.topology_update_count(), vertex=sc.vertex_update_count(), resync=sc.resync_count())
+        for f in out["frames"]:
+            del f["counts"]
+    finally:
+        sc.close()
+    print("RESYNC_LEG " + json.dumps(out), flush=True)
+
+
+def resync_legs(quick):
+    import subprocess
+    legs = []
+    for on in (0, 1, 0, 1):  # alternating: drift of the machine falls on both
+        cmd = [sys.executable, os.path.abspath(__file__), "--resync-leg", str(on)] + (["--quick"] if quick else [])
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, GATLING_BUILD_TIMING="1"))
+        updates = [ln for ln in p.stderr.splitlines() if " update:" in ln]  # the library's host / device split of every update, whole
+        sys.stderr.write("\n".join(updates[-2 * 17:]) + "\n" if p.returncode == 0 else p.stderr[-6000:])
+        line = next((ln for ln in p.stdout.splitlines() if ln.startswith("RESYNC_LEG ")), None)
+        if p.returncode != 0 or line is None:
+            raise SystemExit(f"resync leg {on} failed ({p.returncode}): {p.stdout[-2000:]}")
+        legs.append(json.loads(line[len("RESYNC_LEG "):]))
+        print(f"resync_refits={on}: 16 frames {legs[-1]['totalSyncMs']} ms sync, {legs[-1]['totalRenderCallMs']} ms calls, resident {legs[-1]['residentTriangles']}, "
+              f"{legs[-1]['counts']}", flush=True)
+    print(json.dumps({"resyncLegs": legs}))
+
+
 def main():
     quick = "--quick" in sys.argv
+    if "--resync-leg" in sys.argv:
+        return resync_leg(int(sys.argv[sys.argv.index("--resync-leg") + 1]), quick)
+    if "--resync" in sys.argv:
+        return resync_legs(quick)
     capi.initialize(0)
     result = {"quick": quick}
     sweep(result, [1 << k for k in range(10, 15 if quick else 21)])

@@ -50,6 +50,11 @@ def edit(sc, mesh, seed):
     out = sync_ms(sc)
     out["renderCallMs"] = round((time.perf_counter() - t0) * 1e3, 2)
     out["vertexUpdates"] = sc.vertex_update_count()
+    # DERIVED from the mesh, not observed: what this library's update sends per device (the mesh's FVertex records) and what it gathers there instead of
+    # sending (the 160-byte shading records, gi_refit.hip); the library's own GATLING_BUILD_TIMING line reports the bytes it sent.  A library from before the
+    # device gather sent both
+    out["derivedVertexBytes"] = 48 * len(v)
+    out["derivedShadeBytes"] = 160 * len(sc.desc.meshes[mesh].faces)
     return out
 
 
