@@ -171,6 +171,8 @@ SYMBOLS = [
     ("giCDebugSceneResyncCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugGatherShade", C.c_int, [_P, _U, _P, _U]),
     ("giCDebugSceneShadeCheck", C.c_int, [_P, _U, C.POINTER(C.c_uint32)]),
     ("giCDebugPathWalkStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("giCDebugPathLobeStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("giCDebugPathLot", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("giCDebugMissRect", C.c_int, [_FP, C.POINTER(GiCCameraDesc), C.POINTER(GiCRenderSettings), _U, _U, C.POINTER(C.c_uint32)]),
 ]
 
@@ -558,6 +560,15 @@ class Scene:
         if self.L.giCDebugPathWalkStats(self.handle, c) != GI_C_OK:
             raise GiError("giCDebugPathWalkStats failed")
         return {"phaseTrips": int(c[0]), "stepTrips": [int(v) for v in c[1:9]], "stepLanes": [int(v) for v in c[9:17]], "fewLaneSteps": int(c[17])}
+
+    def path_lobe_stats(self) -> dict:
+        """giCDebugPathLobeStats: the fused kernel's glossy-lobe counters of the last render (OPTION_COUNT_TRAVERSAL; all zero otherwise) and, with
+        GATLING_OPTIONS lobe_park set explicitly, what the lobe parking did."""
+        c = (C.c_uint64 * 9)()
+        if self.L.giCDebugPathLobeStats(self.handle, c) != GI_C_OK:
+            raise GiError("giCDebugPathLobeStats failed")
+        keys = ("shaded", "glossy", "glossyTrips", "liteTrips", "fullTrips", "parked", "adopted", "reruns", "rerunHits")
+        return {k: int(v) for k, v in zip(keys, c)}
 
     def set_option(self, option: int, value: int):
         if self.L.giCSetSceneOption(self.handle, option, value) != GI_C_OK:

@@ -574,6 +574,26 @@ extern "C" int giCDebugPathWalkStats(const GiCScene* scene, uint64_t* out)
   return GI_C_OK;
 }
 
+// giCDebugPathLobeStats: the glossy-lobe counters of the fused kernel's shade phase and what its lobe parking did in the last render of a counting build
+// (Counters::lobeStats of the primary device; gi_path.hip).  All zero after a render that did not run k_path with counters.
+extern "C" int giCDebugPathLobeStats(const GiCScene* scene, uint64_t* out)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!s || !out) { setError("giCDebugPathLobeStats: bad arguments"); return GI_C_ERROR; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  for (int k = 0; k < 9; k++) out[k] = s->pathLobeStats[k];
+  return GI_C_OK;
+}
+
+// giCDebugPathLot: where k_path keeps parked hits for a tree of this depth (gi_kernels.h pathLotPlacement) and the dynamic LDS its launch asks for.  Host only.
+extern "C" int giCDebugPathLot(uint32_t bvhDepth, uint32_t nodeCount, uint32_t triCount, uint32_t* out)
+{
+  if (!out) { setError("giCDebugPathLot: bad arguments"); return GI_C_ERROR; }
+  const gi::PathLot lot = gi::pathLotPlacement(bvhDepth);
+  out[0] = lot.stack; out[1] = lot.row; out[2] = lot.capacity; out[3] = gi::traceLdsBytes(lot.stack, nodeCount, triCount);
+  return GI_C_OK;
+}
+
 // giCDebugSceneClassState: what picks a render's kernel variants (gi_build.cpp deriveSceneClasses), as the last scene sync left it.  Host only.
 extern "C" int giCDebugSceneClassState(const GiCScene* scene, uint32_t* out)
 {

@@ -56,9 +56,23 @@ void launchShade(hipStream_t s, uint32_t blocks, uint32_t klass, bool textured /
 
 // Fused persistent path kernel (gi_path.hip) for LDS-resident scenes; launchPath returns the resident blocks per CU it launched with
 bool pathKernelSupports(const SceneView& sc);
-int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool textured, bool count, uint32_t chunk, uint32_t walkCarry, const FrameUniforms& U,
-               const SceneView& sc, const PathState& st, Counters* cnt, F4* sampleBuf);
+// lobePark: k_path's class-1 variants without NEE park hits that drew a glossy lobe and shade them together once this many are parked (0: off); the general
+// variant takes it in counting builds only, every other variant ignores it
+int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool textured, bool count, uint32_t chunk, uint32_t walkCarry, uint32_t lobePark,
+               const FrameUniforms& U, const SceneView& sc, const PathState& st, Counters* cnt, F4* sampleBuf);
 constexpr long WALK_CARRY_DEFAULT = 8; // GATLING_OPTIONS=walk_carry (gi_options.h)
+constexpr long LOBE_PARK_DEFAULT = 8;  // GATLING_OPTIONS=lobe_park (gi_options.h)
+// Where k_path keeps its parked hits (the lot): in the rows of its per-lane traversal stack that no walk of the tree reaches.  A walk pushes at most bvhDepth
+// entries, so of the `stack` rows (4 for trees of depth <= 4, else 8) the rows from `row` = bvhDepth on are free; a row of a wave's 64 columns holds 8 records
+// of 16 dwords.  capacity 0: nothing is free, the parking is off for this tree.  The launch's LDS is traceLdsBytes(stack, ...) as ever: the lot adds nothing.
+// k_path clamps its threshold to the capacity (cornell, depth 1: 24 records; depth 2: 16; depth 3, 7: 8; depth 4, 8: none).
+struct PathLot { uint32_t stack, row, capacity; };
+inline PathLot pathLotPlacement(uint32_t bvhDepth)
+{
+  const uint32_t stack = bvhDepth <= 4u ? 4u : 8u;
+  const uint32_t row = bvhDepth < stack ? bvhDepth : stack;
+  return PathLot{stack, row, (stack - row) * 8u};
+}
 
 void launchAov(hipStream_t s, const FrameUniforms& U, const SceneView& sc, const AovTargets& A);
 void launchResolveNee(hipStream_t s, const FrameUniforms& U, const unsigned long long* key, F4* aov, uint32_t pixelCount);

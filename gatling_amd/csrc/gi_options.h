@@ -23,6 +23,11 @@
 //                                  still walking (and more entered); they go on walking in the next trip's loop (gi_path.hip).  0 = every loop runs until
 //                                  its last ray is done; 63 (tests) = carry whenever a lane has finished.  Counting builds run with 0 unless the key is set
 //                                  explicitly: then it reaches them too (giCDebugPathWalkStats shows what it did)
+//   lobe_park            8         fused frames without next-event estimation whose materials are all UsdPreviewSurface: a k_path wave sets hits that drew a
+//                                  glossy lobe aside and shades them together once this many are parked (gi_path.hip), clamped to what the free rows of
+//                                  the traversal stack hold (gi_kernels.h pathLotPlacement).  0 = every hit is shaded in the trip that found it; 1 (tests) =
+//                                  most eager; 64 (tests) = as late as the lot allows.  Counting builds run with 0 unless the key is set explicitly
+//                                  (giCDebugPathLobeStats shows what it did)
 //   fused                1         LDS-resident scenes run the fused persistent kernel
 //   pool_slots           0         pin the path pool (slots); 0 = the memory plan decides
 //   sample_buffer_mb     0         pin the per-sample buffer (MiB); 0 = the memory plan decides

@@ -22,10 +22,17 @@
 // Pixels whose EVERY camera ray misses (FLAG_MISS_RECT: outside the host's rectangle, gi_miss_rect.h) are not work items at all: the ids enumerate the pixels
 // of the active rectangle, the records of the others are never written, and k_accumulate sums their constant.
 //
+// Hits that drew a glossy lobe of a UsdPreviewSurface material are parked (the NEE-off class-1 variant; "Lobe parking" in the trip loop): most trips skip the
+// GGX block of the sample, the few hits that need it wait as 16-dword records in the traversal-stack rows the tree's walks never reach, and every few trips the
+// wave shades them together with that trip's own.  A path's sequence of draws and operations is unchanged -- only the trip in which it advances differs; carried
+// walker and free are exclusive lane states and only free lanes adopt; every trip retires a segment, adds to a bounded lot or takes from it; the kernel ends
+// with the lot empty; lobePark = 0 is the kernel without parking.
+//
 // Not handled here (the host falls back to the wavefront pipeline): medium stacks (mediumStackSize > 0), dome-light images,
 // scenes beyond LDS, trees deeper than 8 levels.
 
 #include <hip/hip_runtime.h>
+#include <cassert>
 
 #define GI_LEAN_SQRT 1 // gi_device_math.h gi_sqrt: the correctly rounded square root without the steps ordinary arguments do not need
 #include "gi_device_math.h"
@@ -44,10 +51,14 @@ constexpr uint32_t PATH_STACK_MAX = 8; // LDS traversal-stack entries per lane: 
 constexpr int PATH_WAVES = 4; // resident waves per SIMD the register allocation aims for (114 VGPRs without a hint; 3 cost 11 %, 5 spill 26 registers: r03)
 template <uint32_t KLASS, bool TEXTURED, bool NEE, bool CUTOUT, bool COUNT, uint32_t PATH_STACK>
 __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PATH_WAVES, 8))) void k_path(FrameUniforms U, SceneView sc, PathState st,
-    Counters* cnt, F4* __restrict__ sampleBuf, uint32_t ldsNodes, uint32_t ldsTris, uint32_t chunk, uint32_t walkCarry)
+    Counters* cnt, F4* __restrict__ sampleBuf, uint32_t ldsNodes, uint32_t ldsTris, uint32_t chunk, uint32_t walkCarry, uint32_t lobePark, uint32_t lotRow,
+    uint32_t lotCap)
 {
   // Walk carry (NEE off): see the closest-hit loop.  The NEE variants' shadow walk reuses R and WaveTri::best[lane], so they never carry.
   constexpr bool CARRY = !NEE;
+  // Lobe parking (NEE off, class 1 -- and the counting build, which is how tests see it): see "shade" below.  Every other variant is compiled without it.
+  constexpr bool PARK = !NEE && (KLASS == 1u || (KLASS == KLASS_DYNAMIC && COUNT));
+  constexpr bool DEFER = PARK || COUNT; // shade_segment's deferring form: PARK needs it; counting builds use it to count the glossy hits (lite never set)
   const StagedScene S = stage_scene<PATH_STACK>(sc, ldsNodes, ldsTris); // the only barrier: from here on the waves of a block are independent
   __shared__ WaveTri s_wave[TRACE_BLOCK / 64];
   WaveTri& W = s_wave[threadIdx.x >> 6];
@@ -77,6 +88,17 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
   unsigned long long pc[4] = {0ull, 0ull, 0ull, 0ull}, pl[4] = {0ull, 0ull, 0ull, 0ull}, trips = 0ull, tPrev = COUNT ? __builtin_readcyclecounter() : 0ull;
   uint32_t whLanes[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}, whTrips[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}; // COUNT: lanes walking at step 0 .. 7+ of a trip's loop
   uint32_t whFew = 0u; // COUNT: steps that began with fewer than 8 lanes walking
+  uint32_t lobeN[9] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}; // COUNT: Counters::lobeStats of this wave
+  // The lot: the parked hits of this wave, 16-dword records in the rows of the traversal stack that no walk of this tree reaches.  Record k lies in row
+  // lotRow + k / 8, in the 8 columns from k % 8 * 8 of the wave's 64 (a row of a wave: 64 columns x 8 bytes = 8 records).  The host passes the first free row
+  // and the capacity (launchPath: lotRow >= bvhDepth, the most entries a walk pushes); clamped here once more to what PATH_STACK rows hold.
+  const uint32_t lotFit = (PATH_STACK - (lotRow < PATH_STACK ? lotRow : PATH_STACK)) * 8u;
+  const uint32_t lotMax = PARK ? (lotCap < lotFit ? lotCap : lotFit) : 0u;
+  const uint32_t parkAt = PARK ? (lobePark < lotMax ? lobePark : lotMax) : 0u; // FULL once the lot holds this many (0: parking off, today's trips)
+  uint32_t lotCount = 0u; // wave-uniform
+  auto lot_record = [&](uint32_t k) __attribute__((always_inline)) {
+    return (volatile GI_LDS gi_u4*)(GI_LDS gi_u4*)&S.stack[lotRow + (k >> 3)][(threadIdx.x & ~63u) + ((k & 7u) << 3)];
+  };
   auto phase = [&](int k,
       unsigned long long lanes) { if (COUNT) { const unsigned long long t = __builtin_readcyclecounter(); pc[k] += t - tPrev; tPrev = t; pl[k] += lanes; } };
   for (;;) {
@@ -144,7 +166,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
       }
       preHead += take;
     }
-    if (!__ballot(alive)) break;
+    if (!__ballot(alive) && (!PARK || lotCount == 0u)) break; // (PARK: no work left, no ray pending, but parked hits: a trip without a walk shades them)
     phase(0, nIdle); trips++;
 
     // --- closest hit (traceRayEXT, rp_main.rgen:381-393): all rays of the wave advance in steps, triangles are tested cooperatively
@@ -184,18 +206,38 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
     const bool walked = CARRY ? alive && !tAlive : alive; // this trip ended the lane's segment
     bool ended = false;
     ShadeIO io; io.shadow = false; io.shadowFirst = false; io.cont = false;
+    if (DEFER) { io.lite = false; io.glossyLobe = false; io.deferred = false; }
     phase(1, (unsigned long long)__popcll(__ballot(walked)));
+    // PARK: the per-sample finish (below) as a function -- a lane about to adopt a parked hit finishes its sample ahead of the trip's end
+    auto finish_path = [&]() __attribute__((always_inline)) {
+      const uint32_t bounces = bitfield & 0x00000fffu;
+      if (st.bouncesAov && U.batchFirstSample + rec / U.pixelCount == U.spp - 1u) {
+        const uint32_t maxB = U.maxBounces < 0x00000fffu ? U.maxBounces : 0x00000fffu;
+        const V3 c = gi_colormap_inferno((float)bounces / (float)maxB);
+        F4* dst = &st.bouncesAov[tile_to_image_pixel(U, rec % U.pixelCount)];
+        dst->x = c.x; dst->y = c.y; dst->z = c.z;
+      }
+      if (st.pathSegments) atomicAdd(&st.pathSegments[rec % U.pixelCount], bounces);
+      const V3 c = finish_sample(U, rad);
+      st4(&sampleBuf[rec], c.x, c.y, c.z, 0.0f);
+      alive = false;
+    };
+    bool shaded = false; // PARK: this trip shaded a hit of the lane's path (not always the segment the lane walked)
+    uint32_t nEarly = 0u; // PARK (wave-uniform): samples finished ahead of the trip's end, by lanes about to adopt
     if (walked) {
       nSeg++;
       wave_ray_end(W, R);
       if (R.found) { // rp_main.chit + rp_main.rgen:397-480
-        io.throughput = thr; io.radiance = rad; io.bitfield = bitfield; io.rng = rng;
-        const F4 h = F4{R.tBest, R.bestU, R.bestV, u2f(R.bestTri)}, rd = F4{rdv.x, rdv.y, rdv.z, 0.0f};
-        shade_segment<KLASS, TEXTURED, false, NEE>(U, sc, nullptr, h, rd, io);
-        thr = io.throughput; rad = io.radiance; bitfield = io.bitfield; rng = io.rng;
-        // untraced shadow ray == "not shadowed" (rp_main.rgen:431-435)
-        if (NEE && st.neeKey && io.shadowFirst && !io.shadow) nee_aov_record_px(st, rec % U.pixelCount, rec / U.pixelCount, false);
-        ended = !io.cont;
+        if constexpr (!PARK) {
+          io.throughput = thr; io.radiance = rad; io.bitfield = bitfield; io.rng = rng;
+          const F4 h = F4{R.tBest, R.bestU, R.bestV, u2f(R.bestTri)}, rd = F4{rdv.x, rdv.y, rdv.z, 0.0f};
+          shade_segment<KLASS, TEXTURED, false, NEE, false, DEFER>(U, sc, nullptr, h, rd, io);
+          thr = io.throughput; rad = io.radiance; bitfield = io.bitfield; rng = io.rng;
+          // untraced shadow ray == "not shadowed" (rp_main.rgen:431-435)
+          if (NEE && st.neeKey && io.shadowFirst && !io.shadow) nee_aov_record_px(st, rec % U.pixelCount, rec / U.pixelCount, false);
+          ended = !io.cont;
+          shaded = true;
+        } // (PARK: below)
       } else { // rp_main.miss:68-86: uniform fallback dome == colour clear value; the loop's bounce++ still happens (rp_main.rgen:480)
         rad = rad + thr * v3(U.background);
         if (st.neeKey && (bitfield & 0x00000fffu) == 0u) nee_aov_record_px(st, rec % U.pixelCount, rec / U.pixelCount, false);
@@ -203,7 +245,83 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
         ended = true;
       }
     }
-    phase(2, (unsigned long long)__popcll(__ballot(walked && R.found)));
+    // Lobe parking.  A class-1 hit draws its lobe from x2, and the glossy ones (coat, specular: ggx_sample, two normalisations, eight more square roots, nine
+    // divisions -- a fifth of this kernel's VALU instructions) are few: on C2 3 .. 4 of a trip's ~40 hits, yet nearly every trip has one, so the wave issued
+    // that block on every trip for a twentieth of its lanes.  Now most trips are LITE: shade_segment leaves a hit that drew a glossy lobe untouched (`deferred`),
+    // the lane writes the hit's pre-shade state -- throughput, radiance, bitfield, rng, rec, ray direction, (t, u, v, triangle): 16 dwords -- to the lot by
+    // ballot rank and is free; the next trip's regeneration gives it a camera ray.  Once the lot holds parkAt records, or the wave is draining (no work left to
+    // claim, ring empty), the trip is FULL: the lanes whose segment missed finish their sample first, free lanes adopt the top records of the lot -- an adopting
+    // lane becomes that path, rec included -- and shade_segment runs with lite = false for the trip's own hits and the adopted ones together.
+    // Overflow rule: the lot never takes part of a trip's deferred hits.  If they do not all fit (a material whose hits nearly all go glossy: a metal), the
+    // trip's shade is run again on the spot as FULL for exactly those hits, beside whatever the lot holds; no lane keeps a hit across trips outside the lot.
+    // Invariants: a path's sequence of draws and operations is what it was -- shading from the parked state repeats the same arithmetic; only the trip in which
+    // the path advances differs, and nSeg counts a segment where its walk ends, not again at adoption.  Carried walker (alive, still walking) and free are
+    // exclusive lane states, and only free lanes adopt.  Every trip retires a segment, or adds to the lot (at most lotMax records), or -- FULL -- takes from
+    // it; the trip loop ends only with no lane alive AND the lot empty, so a launch hands nothing to the next.  parkAt = 0: every trip is FULL over an empty
+    // lot, which is the kernel without parking.
+    if constexpr (PARK) {
+      bool hit = walked && R.found; // the lane holds a hit to shade
+      // the shade of the hit in R for the path in the lane's registers; a deferred hit (io.lite) leaves everything as it was
+      auto shade_hit = [&]() __attribute__((always_inline)) {
+        io.throughput = thr; io.radiance = rad; io.bitfield = bitfield; io.rng = rng;
+        const F4 h = F4{R.tBest, R.bestU, R.bestV, u2f(R.bestTri)}, rd = F4{rdv.x, rdv.y, rdv.z, 0.0f};
+        shade_segment<KLASS, TEXTURED, false, NEE, false, DEFER>(U, sc, nullptr, h, rd, io);
+        if (io.deferred) return;
+        thr = io.throughput; rad = io.radiance; bitfield = io.bitfield; rng = io.rng;
+        ended = !io.cont;
+        shaded = true;
+        // (the next ray is taken here and not at the trip's end: a second pass of the shade would otherwise hold every out field of the first alive)
+        if (!ended) { ro = io.no; rdv = io.k2; tMin = 0.0f; tMax = io.tMaxNext; }
+      };
+      // (a trip without a hit of its own has nothing to set aside: FULL, so that a wave left with parked hits alone always takes from the lot)
+      bool lite = lotCount < parkAt && !(exhausted && preTail == preHead) && __ballot(hit) != 0ull;
+      if (COUNT && parkAt) lobeN[lite ? 3 : 4]++;
+      for (;;) {
+        if (!lite && lotCount) {
+          nEarly += (uint32_t)__popcll(__ballot(ended));
+          if (ended) { finish_path(); ended = false; }
+          const unsigned long long freeLanes = __ballot(!alive);
+          const uint32_t nFree = (uint32_t)__popcll(freeLanes), nAdopt = nFree < lotCount ? nFree : lotCount;
+          const uint32_t rank = (uint32_t)__popcll(freeLanes & below);
+          __atomic_signal_fence(__ATOMIC_SEQ_CST); // (compiler only) the records were written by other lanes of this wave
+          if (!alive && rank < nAdopt) {
+            volatile GI_LDS gi_u4* p = lot_record(lotCount - nAdopt + rank);
+            const gi_u4 a = p[0], b = p[1], c = p[2], d = p[3];
+            thr = v3(u2f(a.x), u2f(a.y), u2f(a.z)); bitfield = a.w; rad = v3(u2f(b.x), u2f(b.y), u2f(b.z)); rng = b.w;
+            rdv = v3(u2f(c.x), u2f(c.y), u2f(c.z)); rec = c.w; R.tBest = u2f(d.x); R.bestU = u2f(d.y); R.bestV = u2f(d.z); R.bestTri = d.w;
+            alive = true; hit = true;
+          }
+          lotCount -= nAdopt;
+          if (COUNT) lobeN[6] += nAdopt;
+        }
+        io.lite = lite;
+        if (hit) shade_hit();
+        const unsigned long long deferred = lite ? __ballot(hit && io.deferred) : 0ull;
+        if (!deferred) break;
+        const uint32_t nDeferred = (uint32_t)__popcll(deferred);
+        if (lotCount + nDeferred <= lotMax) {
+          if (hit && io.deferred) {
+            volatile GI_LDS gi_u4* p = lot_record(lotCount + (uint32_t)__popcll(deferred & below));
+            p[0] = gi_u4{f2u(thr.x), f2u(thr.y), f2u(thr.z), bitfield}; p[1] = gi_u4{f2u(rad.x), f2u(rad.y), f2u(rad.z), rng};
+            // (a deferring lane walked this trip: its hit is still in the wave's record, so (t, u, v, triangle) need not stay in registers through the shade)
+            const uint4 wh = wt_hit_get(W, lane);
+            p[2] = gi_u4{f2u(rdv.x), f2u(rdv.y), f2u(rdv.z), rec}; p[3] = gi_u4{wt_best_t(W, lane), wh.y, wh.z, wh.x};
+            alive = false;
+          }
+          __atomic_signal_fence(__ATOMIC_SEQ_CST);
+          lotCount += nDeferred;
+          if (COUNT) lobeN[5] += nDeferred;
+          break;
+        }
+        hit = hit && io.deferred; lite = false; // the overflow rule: this trip's deferred hits are shaded now
+        if (COUNT) { lobeN[7]++; lobeN[8] += nDeferred; }
+      }
+    }
+    if (COUNT) {
+      const unsigned long long glossy = __ballot(shaded && io.glossyLobe);
+      lobeN[0] += (uint32_t)__popcll(__ballot(shaded)); lobeN[1] += (uint32_t)__popcll(glossy); lobeN[2] += glossy ? 1u : 0u;
+    }
+    phase(2, (unsigned long long)__popcll(__ballot(PARK ? shaded : walked && R.found)));
 
     // --- shadow ray of this bounce (rp_main.rgen:397-429): origin = next ray origin, tMin 0.01, tMax = distance to the light sample
     if (NEE) {
@@ -224,7 +342,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
     }
 
     // --- next segment, or the per-sample finish (rp_main.rgen:483-496) -> per-sample colour buffer
-    if (walked) {
+    if constexpr (PARK) { if (ended) finish_path(); } // (a path that goes on took its next ray where it was shaded)
+    else if (walked) {
       if (!ended) { ro = io.no; rdv = io.k2; tMin = 0.0f; tMax = io.tMaxNext; }
       else {
         const uint32_t bounces = bitfield & 0x00000fffu;
@@ -240,14 +359,15 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
         alive = false;
       }
     }
-    phase(3, (unsigned long long)__popcll(__ballot(ended)));
+    phase(3, (unsigned long long)__popcll(__ballot(ended)) + nEarly);
   }
 
   if (COUNT
       && lane == 0u) { for (int k = 0; k < 4; k++) { atomicAdd(&cnt->phaseCycles[k], pc[k]); atomicAdd(&cnt->phaseLanes[k], pl[k]);
       } atomicAdd(&cnt->phaseTrips, trips);
       for (int k = 0; k < 8; k++) { atomicAdd(&cnt->walkStepLanes[k], (unsigned long long)whLanes[k]); atomicAdd(&cnt->walkStepTrips[k], (unsigned long long)whTrips[k]); }
-      atomicAdd(&cnt->walkFewLaneSteps, (unsigned long long)whFew); }
+      atomicAdd(&cnt->walkFewLaneSteps, (unsigned long long)whFew);
+      for (int k = 0; k < 9; k++) atomicAdd(&cnt->lobeStats[k], (unsigned long long)lobeN[k]); }
   // statistics: one atomic per wave and counter
   unsigned long long a = nSeg, b = nShadow, c = tc.nodes, d = tc.tris, e = tcs.nodes, f = tcs.tris;
   for (int off = 32; off > 0; off >>= 1) {
@@ -274,7 +394,7 @@ bool pathKernelSupports(const SceneView& sc)
          && !sc.shadePacked;
 }
 
-using PathKernel = void (*)(FrameUniforms, SceneView, PathState, Counters*, F4*, uint32_t, uint32_t, uint32_t, uint32_t);
+using PathKernel = void (*)(FrameUniforms, SceneView, PathState, Counters*, F4*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t);
 // Hot variants: one material class, no textures, no cutouts, no counters (the C1 / C2 paths).  Everything else runs the general
 // variant (class read from the material record, textures and cutouts compiled in).
 template <uint32_t STACK>
@@ -292,12 +412,14 @@ static PathKernel pickPathKernel(uint32_t classMask, bool textured, bool nee, bo
   }, nee);
 }
 
-int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool textured, bool count, uint32_t chunk, uint32_t walkCarry, const FrameUniforms& U,
-               const SceneView& sc, const PathState& st, Counters* cnt, F4* sampleBuf)
+int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool textured, bool count, uint32_t chunk, uint32_t walkCarry, uint32_t lobePark,
+               const FrameUniforms& U, const SceneView& sc, const PathState& st, Counters* cnt, F4* sampleBuf)
 {
   if (U.workTotal == 0u) return 0; // an empty active rectangle (FLAG_MISS_RECT, the camera looks away): no pixel needs a path
   const uint32_t ldsNodes = sc.nodeCount, ldsTris = sc.triCount;
-  const uint32_t stack = sc.bvhDepth <= 4u ? 4u : 8u;
+  const PathLot lot = pathLotPlacement(sc.bvhDepth); // the stack rows, and in them the home of k_path's parked hits: no LDS of its own
+  const uint32_t stack = lot.stack;
+  assert(sc.bvhDepth <= stack && lot.row >= sc.bvhDepth && lot.row + (lot.capacity + 7u) / 8u <= stack); // the walks own rows [0, bvhDepth), the lot the rest
   const uint32_t bytes = traceLdsBytes(stack, ldsNodes, ldsTris);
   const bool neeOn = (U.flags & FLAG_NEE) != 0u;
   PathKernel k = stack == 4u
@@ -319,7 +441,7 @@ int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool texture
   const uint64_t needed = (chunks + (TRACE_BLOCK / 64u) - 1u) / (TRACE_BLOCK / 64u);
   if (blocks > needed) blocks = needed;
   if (blocks == 0u) blocks = 1u;
-  hipLaunchKernelGGL(k, dim3((uint32_t)blocks), dim3(TRACE_BLOCK), bytes, s, U, sc, st, cnt, sampleBuf, ldsNodes, ldsTris, chunk, walkCarry);
+  hipLaunchKernelGGL(k, dim3((uint32_t)blocks), dim3(TRACE_BLOCK), bytes, s, U, sc, st, cnt, sampleBuf, ldsNodes, ldsTris, chunk, walkCarry, lobePark, lot.row, lot.capacity);
   return perCu;
 }
 

@@ -433,6 +433,7 @@ struct Schedule {
   long twoStreamDelay = 0;      // test hook: 1 | 2 holds the main | the second stream back
   uint32_t dynRefill = 8u;      // k_trace_dyn refill threshold
   uint32_t walkCarry = 0u;      // k_path: the closest-hit loop of a trip ends once at most this many lanes are still walking (0: never early)
+  uint32_t lobePark = 0u;       // k_path: hits that drew a glossy lobe are parked and shaded together once this many wait (0: shaded where they are)
   int32_t shadowOrderNow = -1;  // visiting order of the shadow walks; -1: not chosen yet -- alternate, and count (chooseShadowOrder)
 };
 struct Frame {
@@ -521,6 +522,9 @@ static Schedule scheduleFrame(Frame& f)
   // to its end by default, so that the phase counters (lanes per phase and trip) and the step histogram describe whole walks; an explicit walk_carry key
   // reaches them too (the counters are then how a test sees that lanes were carried: giCDebugPathWalkStats).
   sch.walkCarry = s->countTraversal && !optionSet("walk_carry") ? 0u : (uint32_t)std::min(std::max(optionValue("walk_carry", WALK_CARRY_DEFAULT), 0L), 63L);
+  // Lobe parking of k_path (gi_path.hip): the threshold at which a wave shades its parked glossy hits.  walk_carry's rule for counting builds: off unless the
+  // key is set, so that the phase tables keep describing plain trips (giCDebugPathLobeStats then shows what the parking did).
+  sch.lobePark = s->countTraversal && !optionSet("lobe_park") ? 0u : (uint32_t)std::min(std::max(optionValue("lobe_park", LOBE_PARK_DEFAULT), 0L), 64L);
   sch.dynRefill = traceDynRefill(s);
   // (GATLING_OPTIONS=shadow_order=0|1 pins it)
   sch.shadowOrderNow = optionSet("shadow_order") ? (int32_t)optionValue("shadow_order", -1) : s->shadowOrder.load();
@@ -584,7 +588,7 @@ static int runFusedBatch(Frame& f, uint32_t batch)
   chunk = (uint32_t)std::min<uint64_t>(chunk, std::max<uint64_t>(64u, ((uint64_t)U.workTotal / (waves * 16u)) & ~63ull));
   f.tm.beginIteration(true); // one launch per batch: timed whatever the stride
   f.tm.timed(f.st, StageTimers::TRACE, [&] {
-    launchPath(f.st, (uint32_t)f.ctx.cuCount, s->classMask, s->classTextured != 0u, s->countTraversal, chunk, f.sch.walkCarry, U, f.view, f.ps,
+    launchPath(f.st, (uint32_t)f.ctx.cuCount, s->classMask, s->classTextured != 0u, s->countTraversal, chunk, f.sch.walkCarry, f.sch.lobePark, U, f.view, f.ps,
                D.dCounters.ptr, D.sampleBuf.ptr);
   });
   f.iters++; f.tm.totalIters++; f.traceLaunches++;
@@ -772,6 +776,7 @@ static void fillStats(const Frame& f, double tEnd)
   S.renderMs = tEnd - f.tStart; S.samples = (uint64_t)f.pixels * f.rs.spp; S.iterations = f.iters; S.traceLaunches = f.traceLaunches;
   uint64_t* W = f.D.pathWalkStats; // giCDebugPathWalkStats (all zero unless a counting build's k_path ran in this render)
   for (int k = 0; k < 18; k++) W[k] = 0u;
+  for (int k = 0; k < 9; k++) f.D.pathLobeStats[k] = 0u; // giCDebugPathLobeStats, likewise
   if (f.served) { // nothing was launched but the fold: the counters on the device are still those of the call that traced the window
     S.fusedPath = S.batches = S.poolSlots = 0u;
     S.segments = S.shadowRays = S.nodesVisited = S.trisTested = S.shadowNodesVisited = S.shadowTrisTested = 0u;
@@ -781,6 +786,7 @@ static void fillStats(const Frame& f, double tEnd)
   S.segments = c.segments + f.skippedSegments; S.shadowRays = c.shadowRays; S.nodesVisited = c.nodesVisited; S.trisTested = c.trisTested;
   S.shadowNodesVisited = c.shadowNodesVisited; S.shadowTrisTested = c.shadowTrisTested;
   W[0] = c.phaseTrips; W[17] = c.walkFewLaneSteps;
+  for (int k = 0; k < 9; k++) f.D.pathLobeStats[k] = c.lobeStats[k];
   for (int k = 0; k < 8; k++) { W[1 + k] = c.walkStepTrips[k]; W[9 + k] = c.walkStepLanes[k]; }
 }
 

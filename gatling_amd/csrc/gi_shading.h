@@ -411,7 +411,9 @@ __device__ __forceinline__ UpsParams ups_params(const MaterialRec* m, const ShSt
   return u;
 }
 
-struct BsdfSample { V3 k2, overPdf; float pdf; uint32_t event; };
+struct BsdfSample { V3 k2, overPdf; float pdf; uint32_t event;
+  bool glossyLobe, deferred; // bsdf_sample<.., DEFER = true> alone sets them: the hit drew a glossy lobe of class 1 / and was left unsampled (`lite`)
+};
 struct BsdfEval { V3 diffuse, glossy; float pdf; };
 
 // ---- class 2: OpenPBR (lobe graph of src/gi/mtlx/open_pbr_surface.mtlx:99-635, closed forms of our own) ----
@@ -944,10 +946,14 @@ __device__ __forceinline__ V3 diffuse_class_color(const MaterialRec* m, const Sh
 }
 
 constexpr uint32_t KLASS_DYNAMIC = 0xffffffffu; // read the class from the material record (debug / AOV paths)
-template <uint32_t KLASS>
-__device__ inline void bsdf_sample(const MaterialRec* m, const ShState& st, V3 k1, float x0, float x1, float x2, BsdfSample& out)
+// DEFER (k_path's lobe parking, gi_path.hip): the deferring form of the class-1 sample.  It reports whether the hit drew a glossy lobe (coat or specular:
+// the GGX block below), and with the wave-uniform `lite` set such a hit leaves at once, marked `deferred` -- nothing else of `out` means anything then, and the
+// caller shades the hit again later from the same state, with lite = false.  DEFER = false is the function as it always was.
+template <uint32_t KLASS, bool DEFER = false>
+__device__ inline void bsdf_sample(const MaterialRec* m, const ShState& st, V3 k1, float x0, float x1, float x2, BsdfSample& out, bool lite = false)
 {
   out.event = EV_ABSORB; out.pdf = 0.0f; out.overPdf = v3(0.0f, 0.0f, 0.0f); out.k2 = v3(0.0f, 0.0f, 0.0f);
+  if (DEFER) { out.glossyLobe = false; out.deferred = false; }
   const uint32_t klass = (KLASS == KLASS_DYNAMIC) ? m->klass : KLASS;
   if (klass == 0u) {
     V3 l = gi_sample_hemisphere(x0, x1);
@@ -971,6 +977,7 @@ __device__ inline void bsdf_sample(const MaterialRec* m, const ShState& st, V3 k
       lobe = (z < ps) ? 1u : 2u;
     }
     if (lobe != 2u) {
+      if (DEFER) { out.glossyLobe = true; if (lite) { out.deferred = true; return; } }
       GgxOut g = ggx_sample(l1, lobe == 0u ? u.coatAlpha : u.alpha, x0, x1);
       V3 k2 = to_world(st, g.l2);
       if (!g.valid || !(dot(k2, st.geomNormal) > 0.0f)) return;

@@ -66,8 +66,13 @@ struct ShadeIO {
   bool cont, shadow, shadowFirst;                                    // out: path continues; a shadow ray is to be traced; this is bounce 0
   V3 no, k2; float tMaxNext;                                         // out: next ray
   V3 sdir, nee; float ld; uint32_t rngShadow;                        // out: shadow ray direction / distance, NEE contribution, rng copy (rp_main.rgen:399)
+  bool lite, glossyLobe, deferred;                                   // DEFER only -- in: wave-uniform, leave glossy class-1 hits unshaded; out: see below
 };
-template <uint32_t KLASS, bool TEXTURED, bool VOLUME, bool NEE, bool PACKED = false>
+// DEFER (k_path's lobe parking): the hit's class-1 sample runs in its deferring form (gi_shading.h bsdf_sample).  io.glossyLobe tells whether the hit drew a
+// glossy lobe; with io.lite set such a hit comes back `deferred` and the caller must take NOTHING from the call: throughput, radiance (the emission added above
+// the sample included), bitfield and rng are as they went in, no out field is written.  Shading the hit later from that state, lite = false, repeats the same
+// draws and the same arithmetic.  Without DEFER the three fields are never touched and the function is what it was.
+template <uint32_t KLASS, bool TEXTURED, bool VOLUME, bool NEE, bool PACKED = false, bool DEFER = false>
 __device__ __forceinline__ void shade_segment(const FrameUniforms& U, const SceneView& sc, float* M /* medium stack of the path (VOLUME) */, const F4& h,
     const F4& rd, ShadeIO& io)
 {
@@ -77,6 +82,7 @@ __device__ __forceinline__ void shade_segment(const FrameUniforms& U, const Scen
   bool cont = false, shadow = false, shadowFirst = false; uint32_t rngShadow = 0u;
   V3 no = v3(0.0f, 0.0f, 0.0f), k2 = no, sdir = no, nee = no; float ld = 0.0f, tMaxNext = GI_FLT_MAX;
   const uint32_t bounce = bitfield & 0x00000fffu;
+  if constexpr (DEFER) { io.glossyLobe = false; io.deferred = false; }
 
   const V3 rayDir = v3(rd.x, rd.y, rd.z);
   const uint32_t stackSize = VOLUME ? (U.mediumStackSize < MAX_MEDIUM_STACK ? U.mediumStackSize : MAX_MEDIUM_STACK) : 0u;
@@ -146,6 +152,10 @@ __device__ __forceinline__ void shade_segment(const FrameUniforms& U, const Scen
     baseCtx = opbr_base_ctx(mat, ss, -rayDir);
     bs.event = EV_ABSORB; bs.pdf = 0.0f; bs.overPdf = v3(0.0f, 0.0f, 0.0f); bs.k2 = v3(0.0f, 0.0f, 0.0f); // (bsdf_sample's initialisation)
     opbr_base_sample(mat, ss, -rayDir, x0, x1, x2, bs, &baseCtx);
+  } else if constexpr (DEFER) {
+    bsdf_sample<KLASS, true>(mat, ss, -rayDir, x0, x1, x2, bs, io.lite);
+    io.glossyLobe = bs.glossyLobe; io.deferred = bs.deferred;
+    if (bs.deferred) return;
   } else bsdf_sample<KLASS>(mat, ss, -rayDir, x0, x1, x2, bs);
   throughput = throughput * bs.overPdf;
   k2 = bs.k2;

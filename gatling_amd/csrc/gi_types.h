@@ -353,6 +353,11 @@ struct Counters {
   // k_path, counting builds only: steps of the closest-hit loops that began with fewer than 8 lanes walking -- the steps the walk carry exists to avoid (with
   // K >= 8 only a loop that no more than K lanes entered has any).  Last, so that every other counter keeps its offset.
   unsigned long long walkFewLaneSteps;
+  // k_path, counting builds only (giCDebugPathLobeStats): [0] hits shaded, [1] those that drew a glossy lobe of class 1 (coat or specular: the GGX block of
+  // bsdf_sample), [2] trips that shaded at least one such hit; and what the lobe parking (gi_path.hip) did -- [3] LITE trips, [4] FULL trips, [5] hits parked
+  // in the lot, [6] records adopted from it, [7] trips whose shade was run again as FULL on the spot (the lot could not take their glossy hits), [8] the hits
+  // shaded in those second passes.  [3] .. [8] stay zero while the parking is off.
+  unsigned long long lobeStats[9];
 };
 
 } // namespace gi

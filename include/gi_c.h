@@ -379,7 +379,7 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * The same holds for GI_C_SCENE_OPTION_VISIBILITY_UPDATES, giCDebugSceneVisibilityUpdateCount, giCDebugSceneClassState, giCDebugMissRect and giCDebugPathWalkStats, and for
  * giCSetMeshVertices, GI_C_SCENE_OPTION_VERTEX_UPDATES, giCDebugSceneVertexUpdateCount, giCDebugRefitBvh and giCDebugSceneRefitCheck, and for
  * GI_C_SCENE_OPTION_TOPOLOGY_UPDATES and giCDebugSceneTopologyUpdateCount, and for GI_C_SCENE_OPTION_RESYNC_REFITS, giCDebugSceneResyncCount,
- * giCDebugGatherShade and giCDebugSceneShadeCheck. */
+ * giCDebugGatherShade and giCDebugSceneShadeCheck, and for giCDebugPathLobeStats and giCDebugPathLot. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -667,6 +667,17 @@ int giCDebugSceneClassState(const GiCScene* scene, uint32_t* out /* 5 */);
  * began, [17] the steps that began with fewer than 8 lanes walking.  With $GATLING_OPTIONS walk_carry=K set explicitly a counting build carries walks as other
  * builds do, and these numbers are how a test sees it: [17] falls and [0] rises against K = 0, while the image and the per-ray counters stay put. */
 int giCDebugPathWalkStats(const GiCScene* scene, uint64_t* out /* 18 */);
+/* [ext] the fused path kernel's glossy-lobe counters of the scene's last render, for renders with GI_C_SCENE_OPTION_COUNT_TRAVERSAL (all zero otherwise): out[0]
+ * hits shaded, [1] those that drew a glossy lobe of a UsdPreviewSurface material (coat or specular), [2] trips of all waves that shaded at least one such hit.
+ * With $GATLING_OPTIONS lobe_park=N set explicitly a counting build parks such hits as other builds do, and the rest is how a test sees it: [3] LITE trips (glossy
+ * hits set aside), [4] FULL trips (parked and own glossy hits shaded together), [5] hits parked, [6] records adopted, [7] trips whose shade ran again as FULL
+ * on the spot because the lot could not take their glossy hits, [8] the hits shaded in those second passes.  [3] .. [8] are zero with lobe_park=0 or the key
+ * absent; image and per-ray counters are the same whatever N. */
+int giCDebugPathLobeStats(const GiCScene* scene, uint64_t* out /* 9 */);
+/* [ext] where the fused path kernel keeps parked hits for a BVH8 of `bvhDepth` levels below the root: out[0] traversal-stack rows per lane, [1] the first row
+ * no walk reaches, [2] the records that fit in the rows from there on (0: parking is off for such a tree), [3] the dynamic LDS bytes of a launch for a scene of
+ * nodeCount nodes and triCount triangles -- the rows and nothing else: parked hits add no LDS.  Host only: no device work, no scene. */
+int giCDebugPathLot(uint32_t bvhDepth, uint32_t nodeCount, uint32_t triCount, uint32_t* out /* 4 */);
 /* [ext] the miss rectangle of a whole-frame render: out = x0, y0, x1, y1, image columns [x0, x1) and rows [y0, y1) outside which every camera ray the settings'
  * sampling can produce for a pixel misses `bounds` (min xyz, max xyz) -- the fused path kernel gives such pixels no work.  The whole frame when no pixel can be
  * ruled out (depth of field with a lens radius, the camera inside or beside the bounds); 0, 0, 0, 0 when every pixel is (the camera looks away).  Host only: no
