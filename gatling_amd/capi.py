@@ -27,6 +27,7 @@ OPTION_VERTEX_UPDATES = 12  # 1: vertex edits (giCSetMeshVertices) of meshes of 
 OPTION_VISIBILITY_UPDATES = 11  # 1: visibility edits of meshes of the built scene are applied to the resident scene instead of rebuilding it (include/gi_c.h); 0 = off (default)
 OPTION_TOPOLOGY_UPDATES = 13  # 1: meshes created and destroyed after the build are appended to / retired from the resident scene instead of rebuilding it (include/gi_c.h); 0 = off (default)
 OPTION_RESYNC_REFITS = 14  # 1 (with options 12 and 13): a destroyed and a created mesh with the same faces become a vertex refit of the resident records instead of a retire + append (include/gi_c.h); 0 = off (default)
+OPTION_INSTANCE_UPDATES = 15  # 1 (with option 13): new instance ids or another instance count of a built mesh are applied to the resident scene instead of rebuilding it (include/gi_c.h); 0 = off (default)
 OPTION_BVH_BUILD = 9  # 0 = host BVH builder (default), 1 = device builder (flat-layout scenes of more than 128 triangles)
 
 
@@ -170,6 +171,7 @@ SYMBOLS = [
     ("giCDebugSceneTopologyUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugSceneResyncCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugGatherShade", C.c_int, [_P, _U, _P, _U]),
     ("giCDebugSceneShadeCheck", C.c_int, [_P, _U, C.POINTER(C.c_uint32)]),
+    ("giCDebugSceneInstanceUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugCloneInstance", C.c_int, [_P, _U, _P, _U, _I, _FP, _FP]),
     ("giCDebugPathWalkStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugPathLobeStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugPathLot", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
@@ -225,6 +227,21 @@ def debug_gather_shade(vertices, faces) -> int:
     n = L.giCDebugGatherShade(v.ctypes.data, len(v), f.ctypes.data, len(f))
     if n < 0:
         raise GiError("giCDebugGatherShade refused the mesh")
+    return int(n)
+
+
+def debug_clone_instance(vertices, faces, xform_a, xform_b, left_handed=False) -> int:
+    """giCDebugCloneInstance: the records of the mesh (`vertices`: VERTEX_DTYPE, `faces`: n x 3 indices) flattened under the instance transform `xform_a` and
+    cloned to `xform_b` (4 x 4, USD row vectors) by the function the device's clone kernel runs, against the scene build's records for `xform_b`.  Returns the
+    number of differing records (0 is the contract).  Host only."""
+    from .scene import VERTEX_DTYPE
+    L = load_library()
+    v = np.ascontiguousarray(vertices, VERTEX_DTYPE)
+    f = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3)
+    a, b = (np.ascontiguousarray(x, np.float32).reshape(16) for x in (xform_a, xform_b))
+    n = L.giCDebugCloneInstance(v.ctypes.data, len(v), f.ctypes.data, len(f), int(bool(left_handed)), a.ctypes.data_as(_FP), b.ctypes.data_as(_FP))
+    if n < 0:
+        raise GiError("giCDebugCloneInstance refused the mesh or a transform")
     return int(n)
 
 
@@ -393,6 +410,19 @@ class Scene:
         t = np.ascontiguousarray(transforms, np.float32).reshape(-1, 16)
         self.desc.meshes[mesh_index].instance_transforms = t.reshape(-1, 4, 4).copy()
         self.L.giCSetMeshInstanceTransforms(self.meshes[mesh_index], len(t), t.ctypes.data_as(_FP))
+
+    def set_mesh_instance_ids(self, mesh_index: int, ids):
+        """giSetMeshInstanceIds (Gi.h:215).  On a built mesh the next render rebuilds the scene -- or, with OPTION_INSTANCE_UPDATES, re-sends the instance records."""
+        a = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        self.desc.meshes[mesh_index].instance_ids = a.copy()
+        self.L.giCSetMeshInstanceIds(self.meshes[mesh_index], len(a), a.ctypes.data_as(C.POINTER(C.c_int32)))
+
+    def instance_update_counts(self) -> dict:
+        """giCDebugSceneInstanceUpdateCount: syncs that applied an instancer edit in place, instances appended, of those cloned on the device, instances retired."""
+        c = (C.c_uint64 * 4)()
+        if self.L.giCDebugSceneInstanceUpdateCount(self.handle, c) != GI_C_OK:
+            raise GiError("giCDebugSceneInstanceUpdateCount failed")
+        return {"syncs": int(c[0]), "appended": int(c[1]), "cloned": int(c[2]), "retired": int(c[3])}
 
     def _material_handle(self, m):
         """giCCreateMaterial + texture bindings + primvar inputs of one MaterialDesc (texture indices name self.textures)."""

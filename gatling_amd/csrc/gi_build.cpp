@@ -141,6 +141,35 @@ static void flattenInstance(const InstanceRec& ir, uint32_t instIdx, const GiCMe
   }
 }
 
+// giCDebugCloneInstance: the mesh flattened under instance transform A, every record cloned to instance transform B (gi_refit.h refit_clone_record, what
+// gi_patch.hip k_clone_parts runs) under another instance index and id base, against flattenInstance with B, bytewise.  Host only.
+extern "C" int giCDebugCloneInstance(const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, int32_t isLeftHanded,
+    const float* xformA, const float* xformB)
+{
+  if ((vertexCount && !vertices) || (faceCount && !faces) || !xformA || !xformB) return -1;
+  for (uint32_t f = 0; f < faceCount; f++) for (int k = 0; k < 3; k++) if (faces[f].v_i[k] >= vertexCount) return -1;
+  try {
+    GiCMesh m; m.scene = nullptr; m.flipFacing = isLeftHanded != 0; m.id = 11;
+    m.vertices.assign(vertices, vertices + vertexCount); m.faces.assign(faces, faces + faceCount);
+    m.instanceTransforms.assign(xformA, xformA + 16); m.instanceTransforms.insert(m.instanceTransforms.end(), xformB, xformB + 16);
+    constexpr uint32_t vertexOffset = 3u, shadeBase = 5u, meshIdx = 2u, instA = 4u, instB = 9u, idBaseA = 1000u, idBaseB = 77777u; // (as a mesh behind others)
+    const uint32_t matFlags = 6u | (m.flipFacing ? 1u << 30 : 0u);
+    const InstanceRec a = makeInstanceRec(&m, meshIdx, 0), b = makeInstanceRec(&m, meshIdx, 1);
+    if (!usableInstance(a) || !usableInstance(b)) return -1;
+    std::vector<TriShade> shade(shadeBase + (size_t)faceCount, TriShade{});
+    for (uint32_t f = 0; f < faceCount; f++) shade[shadeBase + f] = packTriShade(vertices, faces[f], vertexOffset);
+    std::vector<TriRec> recA(faceCount), recB(faceCount);
+    flattenInstance(a, instA, &m, vertexOffset, matFlags, idBaseA, shadeBase, recA.data());
+    flattenInstance(b, instB, &m, vertexOffset, matFlags, idBaseB, shadeBase, recB.data());
+    int differ = 0;
+    for (uint32_t f = 0; f < faceCount; f++) {
+      const TriRec cloned = refit_clone_record(recA[f], b.o2w, shade[recA[f].vi[0]].p, instB, idBaseB);
+      if (memcmp(&cloned, &recB[f], sizeof(TriRec)) != 0) differ++;
+    }
+    return differ;
+  } catch (const std::exception&) { return -1; }
+}
+
 // The MaterialRec table of the scene's materials, in creation order (buildScene and updateMaterials: the one copy of this code)
 static void buildMaterialRecords(const GiCScene* s, std::vector<MaterialRec>& mats)
 {
@@ -200,6 +229,19 @@ static void appendMeshSceneData(const GiCMesh* m, const GiCMaterial* mat, uint32
     sceneData.resize(mr.sdOffset[slot] + need, 0.0f);
   }
   meshRecs.push_back(mr);
+}
+
+// ... for every mesh of the built scene, in MeshBuild order (MeshRec i belongs to meshIdx i): a retired mesh -- destroyed, its records resident until the next
+// build, its material possibly gone -- keeps an empty record (updateMaterials and updateTopology: the one copy of this loop)
+static void appendBuiltMeshSceneData(const MeshBuild& mb, std::vector<MeshRec>& meshRecs, std::vector<float>& sceneData)
+{
+  if (mb.m->retired) meshRecs.push_back(MeshRec{}); else appendMeshSceneData(mb.m, mb.m->material, mb.vertexOffset, meshRecs, sceneData);
+}
+static void remakeSceneData(SceneHost& H)
+{
+  std::vector<MeshRec> meshRecs; std::vector<float> sceneData;
+  for (const MeshBuild& mb : H.meshBuilds) appendBuiltMeshSceneData(mb, meshRecs, sceneData);
+  H.meshRecs.swap(meshRecs); H.sceneData.swap(sceneData);
 }
 
 // TriRec::matFlags of a mesh bound to material `material` (record `mr`): material index | shade class << 24 | cutout << 28 | mesh flags << 30
@@ -305,7 +347,7 @@ int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vec
     // object-space magnitude the transformed ray's rounding error scales with inside this mesh (see wave_step2)
     const float extent = (std::fabs(mlo[0]) + std::fabs(mlo[1]) + std::fabs(mlo[2])) + (std::fabs(mhi[0]) + std::fabs(mhi[1]) + std::fabs(mhi[2]));
     for (uint32_t ii = 0; ii < mb.instCount; ii++) {
-      const uint32_t inst = mb.instFirst + ii;
+      const uint32_t inst = mb.inst[ii];
       InstTrav& tv = instTrav[inst];
       tv = InstTrav{};
       memcpy(tv.o2w, instances[inst].o2w, sizeof(tv.o2w)); memcpy(tv.w2o, instances[inst].w2o, sizeof(tv.w2o));
@@ -555,7 +597,8 @@ int buildScene(GiCScene* s)
   s->host.reset(); // (a failed build leaves no stale host copy behind)
   for (GiCMesh* m : s->retiredMeshes) delete m; // (nothing refers to them any more: updateTopology kept them for the host copy that is gone)
   s->retiredMeshes.clear();
-  for (GiCMesh* m : s->meshes) { m->builtInstances = 0xffffffffu; m->xformDirty = false; m->instDirty.clear(); m->visToggled = false; m->vertsEdited = false; }
+  for (GiCMesh* m : s->meshes) { m->builtInstances = 0xffffffffu; m->xformDirty = false; m->instDirty.clear(); m->visToggled = false; m->vertsEdited = false;
+      m->instEdited = false; }
   std::vector<FVertex>& verts = H.verts; std::vector<InstanceRec>& instances = H.instances; std::vector<TriRec> tris; std::vector<int32_t> faceIdOf;
   buildMaterialRecords(s, H.mats);
   uint32_t meshIdx = 0;
@@ -579,7 +622,7 @@ int buildScene(GiCScene* s)
     size_t instCount = m->instanceTransforms.size() / 16;
     m->builtInstances = (uint32_t)instCount;
     meshBuilds.push_back(MeshBuild{m, vertexOffset, matFlags, (uint32_t)instances.size(), (uint32_t)instCount, (uint32_t)tris.size(), meshIdx, meshFaceIdAov});
-    meshBuilds.back().idBase = meshBuilds.back().triFirst;
+    meshBuilds.back().idBase = meshBuilds.back().triFirst; meshBuilds.back().numberInstances();
     const size_t nf = m->faces.size(), first = tris.size();
     tris.resize(first + instCount * nf);
     for (size_t ii = 0; ii < instCount; ii++) {
@@ -673,8 +716,9 @@ int buildScene(GiCScene* s)
 // instance), and those ranges uploaded -- not a 10 M-triangle SAH build and a 0.7 GB upload.  Material, assignment, texture and primvar edits have a path of
 // their own (updateMaterials below) that leaves the tree alone, partitioned or not, and so have -- opt-in -- visibility edits (updateVisibility below: ids
 // renumbered in place; a partitioned tree leaves the parts of hidden meshes out of its top tree), vertex edits (updateVertices: a refit) and mesh creations
-// and destructions (updateTopology: parts appended and retired).  Any other edit (instance counts and ids of a built mesh, and the opt-in kinds without their
-// option) raises DIRTY_BVH and the next render rebuilds everything as one tree again.
+// and destructions (updateTopology: parts appended and retired) and instance counts and ids of a built mesh (updateTopology as well: instances appended,
+// cloned and retired).  Any other edit (a show of a mesh that was invisible at the build, and the opt-in kinds without their option) raises DIRTY_BVH and the
+// next render rebuilds everything as one tree again.
 // ---------------------------------------------------------------------------------------------------------------
 void nodeBounds(const Node8& n, float box[6])
 {
@@ -697,7 +741,7 @@ void buildPart(const MeshBuild& mb, uint32_t instInMesh, bool packed, PartBuild&
   out.inst = makeInstanceRec(mb.m, mb.meshIdx, instInMesh);
   std::vector<TriRec> tris(mb.m->faces.size());
   // (ids from 0: placePart adds the instance's base)
-  flattenInstance(out.inst, mb.instFirst + instInMesh, mb.m, mb.vertexOffset, mb.matFlags, 0u, packed ? mb.shadeBase : NOT_PACKED, tris.data());
+  flattenInstance(out.inst, mb.inst[instInMesh], mb.m, mb.vertexOffset, mb.matFlags, 0u, packed ? mb.shadeBase : NOT_PACKED, tris.data());
   buildBvh8(tris, out.bvh);
 }
 
@@ -715,7 +759,7 @@ void placePart(SceneHost& H, InstPart& P, const PartBuild& B)
     t.origId += mb.idBase + P.instInMesh * P.nf;
     H.bvh.tris[P.triFirst + k] = t;
   }
-  H.instances[mb.instFirst + P.instInMesh] = B.inst;
+  H.instances[mb.inst[P.instInMesh]] = B.inst;
   nodeBounds(H.bvh.nodes[P.nodeOff], P.box);
 }
 
@@ -737,8 +781,9 @@ int rebuildTop(GiCScene* s, SceneHost& H)
   uint32_t subDepth = 0;
   for (size_t i = 0; i < H.parts.size(); i++) { memcpy(&boxes[6 * i], H.parts[i].box, 24); roots[i] = H.bvh.nodes[H.parts[i].nodeOff];
       subDepth = std::max(subDepth, H.parts[i].depth);
-      // the parts of a hidden mesh (updateVisibility) keep their ranges and stay out of the top tree, like a part whose triangles are all inactive
-      if (H.meshBuilds[H.parts[i].meshBuild].hidden) for (int a = 0; a < 3; a++) { boxes[6 * i + a] = 3.0e38f; boxes[6 * i + 3 + a] = -3.0e38f; } }
+      // the parts of a hidden mesh (updateVisibility) and of a retired instance (updateTopology) keep their ranges and stay out of the top tree, like a part
+      // whose triangles are all inactive
+      if (H.meshBuilds[H.parts[i].meshBuild].hidden || H.parts[i].retired) for (int a = 0; a < 3; a++) { boxes[6 * i + a] = 3.0e38f; boxes[6 * i + 3 + a] = -3.0e38f; } }
   Bvh8 top;
   buildTopBvh8(boxes.data(), H.parts.size(), roots.data(), top);
   if (top.nodes.size() > H.topCap) { setError("internal: top tree larger than its reserved range"); return GI_C_ERROR; }
@@ -765,14 +810,15 @@ static bool relayoutPartitioned(GiCScene* s, SceneHost& H)
   for (uint32_t b = 0; b < (uint32_t)H.meshBuilds.size(); b++) {
     const MeshBuild& mb = H.meshBuilds[b];
     const uint32_t nf = (uint32_t)mb.m->faces.size();
-    for (uint32_t ii = 0; ii < mb.instCount; ii++) { InstPart P{}; P.meshBuild = b; P.instInMesh = ii; P.triFirst = mb.triFirst + ii * nf; P.nf = nf;
-        parts.push_back(P); }
+    // (the live instances: all of them, unless an instance update has just retired the last ones of a flat scene -- those keep a part without a subtree)
+    for (uint32_t ii = 0; ii < (uint32_t)mb.inst.size() + mb.retiredInst; ii++) { InstPart P{}; P.meshBuild = b; P.instInMesh = ii; P.triFirst = mb.triFirst + ii * nf;
+        P.nf = nf; P.retired = ii >= (uint32_t)mb.inst.size(); parts.push_back(P); }
   }
   if (parts.empty()) return false;
   // (a device-built tree has no host copy, and a vertex update dropped that of a host-built one: placePart fills them)
   if (H.deviceBuilt || H.hostTreeDropped) { H.bvh.tris.resize(s->triCount); H.triFaceId.resize(s->triCount); H.hostTreeDropped = false; }
   std::vector<PartBuild> built(parts.size());
-  parallelOver(parts.size(), [&](size_t i) { buildPart(H.meshBuilds[parts[i].meshBuild], parts[i].instInMesh, H.shadePacked, built[i]); });
+  parallelOver(parts.size(), [&](size_t i) { if (!parts[i].retired) buildPart(H.meshBuilds[parts[i].meshBuild], parts[i].instInMesh, H.shadePacked, built[i]); });
   H.topCap = (uint32_t)parts.size() * 2u + 16u; // top nodes <= internal top nodes + one copied root per part
   if (topologyUpdatesWanted(s)) H.topCap *= 2u;
   uint32_t off = H.topCap;
@@ -780,7 +826,14 @@ static bool relayoutPartitioned(GiCScene* s, SceneHost& H)
       parts[i].nodeCap = n + n / 4u + 8u; off += parts[i].nodeCap; }
   H.bvh.nodes.assign(off, Node8{});
   H.parts.swap(parts);
-  parallelOver(H.parts.size(), [&](size_t i) { placePart(H, H.parts[i], built[i]); });
+  parallelOver(H.parts.size(), [&](size_t i) {
+    InstPart& P = H.parts[i];
+    if (!P.retired) { placePart(H, P, built[i]); return; }
+    // no subtree: unhittable records that nothing refers to, an empty box (nodeOff names the first part's root, never read through this part)
+    for (uint32_t k = 0; k < P.nf; k++) { TriRec t{}; t.prim = k; H.bvh.tris[P.triFirst + k] = t; H.triFaceId[P.triFirst + k] = 0; }
+    P.nodeOff = H.topCap; P.nodeCount = 0; P.nodeCap = 0; P.depth = 0;
+    for (int a = 0; a < 3; a++) { P.box[a] = 3.0e38f; P.box[3 + a] = -3.0e38f; }
+  });
   H.partitioned = true; H.deviceBuilt = false; // host-built from here on
   return true;
 }
@@ -801,7 +854,7 @@ static int updateTransforms(GiCScene* s, bool& handled, UpdateCost& cost)
   } else {
     for (uint32_t i = 0; i < (uint32_t)H.parts.size(); i++) {
       const GiCMesh* m = H.meshBuilds[H.parts[i].meshBuild].m;
-      if (m->xformDirty && (m->instDirty.empty() || m->instDirty[H.parts[i].instInMesh])) dirtyParts.push_back(i);
+      if (m->xformDirty && !H.parts[i].retired && (m->instDirty.empty() || m->instDirty[H.parts[i].instInMesh])) dirtyParts.push_back(i);
     }
     std::vector<PartBuild> built(dirtyParts.size());
     parallelOver(dirtyParts.size(),
@@ -822,7 +875,7 @@ static int updateTransforms(GiCScene* s, bool& handled, UpdateCost& cost)
     if (uploadTopTree(D, H, st) != GI_C_OK) return GI_C_ERROR;
     for (uint32_t i : dirtyParts) {
       const InstPart& P = H.parts[i];
-      const uint32_t instIdx = H.meshBuilds[P.meshBuild].instFirst + P.instInMesh;
+      const uint32_t instIdx = H.meshBuilds[P.meshBuild].inst[P.instInMesh];
       HIP_TRY(hipMemcpyAsync(D.dNodes.ptr + P.nodeOff, &H.bvh.nodes[P.nodeOff], (size_t)P.nodeCount * sizeof(Node8), hipMemcpyHostToDevice, st));
       HIP_TRY(hipMemcpyAsync(D.dTris.ptr + P.triFirst, &H.bvh.tris[P.triFirst], (size_t)P.nf * sizeof(TriRec), hipMemcpyHostToDevice, st));
       HIP_TRY(hipMemcpyAsync(D.dTriFaceId.ptr + P.triFirst, &H.triFaceId[P.triFirst], (size_t)P.nf * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -895,10 +948,10 @@ static int updateMaterials(GiCScene* s, bool& handled, UpdateCost& cost)
   uint32_t meshesChanged = 0; uint64_t trisPatched = 0;
   for (MeshBuild& mb : H.meshBuilds) {
     // a retired mesh is hidden for good and its material may be gone: it keeps its word (never read: no ray reaches its triangles) and an empty record
-    if (mb.m->retired) { meshRecs.push_back(MeshRec{}); wordOfMesh[mb.meshIdx] = mb.matFlags; continue; }
+    appendBuiltMeshSceneData(mb, meshRecs, sceneData);
+    if (mb.m->retired) { wordOfMesh[mb.meshIdx] = mb.matFlags; continue; }
     const uint32_t material = (uint32_t)(std::find(s->materials.begin(), s->materials.end(), mb.m->material) - s->materials.begin());
     const uint32_t word = meshMatFlags(H.mats[material], material, mb.m);
-    appendMeshSceneData(mb.m, mb.m->material, mb.vertexOffset, meshRecs, sceneData);
     wordOfMesh[mb.meshIdx] = word;
     if (word != mb.matFlags) { changed[mb.meshIdx] = 1; meshesChanged++; trisPatched += (uint64_t)mb.m->faces.size() * mb.instCount; mb.matFlags = word; }
   }
@@ -996,7 +1049,7 @@ template <class Hide> static bool planVisibility(const GiCScene* s, const SceneH
     const uint32_t action = hide == mb.hidden || H.partitioned ? VIS_KEEP : (hide ? VIS_HIDE : VIS_SHOW);
     if (hide != mb.hidden) { if (hide) P.hides++; else P.shows++; }
     if (delta != 0) P.renumbered++;
-    if (delta != 0 || action != VIS_KEEP) { P.launch = true; for (uint32_t ii = 0; ii < mb.instCount; ii++) P.patch[mb.instFirst + ii] = VisPatch{delta, action}; }
+    if (delta != 0 || action != VIS_KEEP) { P.launch = true; for (const uint32_t rec : mb.inst) P.patch[rec] = VisPatch{delta, action}; }
   }
   return true;
 }
@@ -1097,6 +1150,28 @@ static bool vertexUpdatesWanted(const GiCScene* s)
   return o >= 0 ? o == 1 : s->optVertexUpdates == 1;
 }
 
+// The launches of a refit (updateVertices; the cloned parts of updateTopology): units = trees with their levels (Bvh8::levelStart, relative to nodeOff);
+// per level, deepest first (levels[0]), the thread ranges of launchRefitLevel -- one range per unit that has the level.  False: a level lies outside the
+// node array of `nodeCount` nodes (cannot happen)
+struct RefitUnit { uint32_t nodeOff; const std::vector<uint32_t>* levelStart; };
+struct RefitLevel { uint32_t first, ranges, threads; };
+static bool planRefitLevels(const std::vector<RefitUnit>& units, uint32_t nodeCount, std::vector<RefitRange>& ranges, std::vector<RefitLevel>& levels)
+{
+  size_t maxLevels = 0;
+  for (const RefitUnit& u : units) maxLevels = std::max(maxLevels, u.levelStart->size() - 1u);
+  for (size_t L = maxLevels; L-- > 0;) {
+    RefitLevel lv{(uint32_t)ranges.size(), 0u, 0u};
+    for (const RefitUnit& u : units) {
+      if (L + 1u >= u.levelStart->size()) continue;
+      const uint32_t a = (*u.levelStart)[L], e = (*u.levelStart)[L + 1u];
+      if (e <= a || (size_t)u.nodeOff + e > nodeCount) return false;
+      ranges.push_back(RefitRange{lv.threads, u.nodeOff + a}); lv.ranges++; lv.threads += e - a;
+    }
+    levels.push_back(lv);
+  }
+  return true;
+}
+
 static int updateVertices(GiCScene* s, bool& handled, UpdateCost& cost)
 {
   SceneHost* host = incrementalHost(s);
@@ -1125,11 +1200,11 @@ static int updateVertices(GiCScene* s, bool& handled, UpdateCost& cost)
   std::atomic<bool> worldOk{true};
   for (uint32_t b : edited) {
     const MeshBuild& mb = H.meshBuilds[b];
-    for (uint32_t ii = 0; ii < mb.instCount; ii++) { editedOfInstance[mb.instFirst + ii] = 1u; if (!usableInstance(H.instances[mb.instFirst + ii])) return GI_C_OK; }
+    for (uint32_t ii = 0; ii < mb.instCount; ii++) { editedOfInstance[mb.inst[ii]] = 1u; if (!usableInstance(H.instances[mb.inst[ii]])) return GI_C_OK; }
     // every flattened triangle must stay active, by the builders' own rule on the builders' own operands (prepareRange: v0, v0 + e1, v0 + e2)
     const size_t nf = mb.m->faces.size();
     parallelOver(mb.instCount, [&](size_t ii) {
-      const InstanceRec& ir = H.instances[mb.instFirst + ii];
+      const InstanceRec& ir = H.instances[mb.inst[ii]];
       for (size_t f = 0; f < nf; f++) {
         TriRec t; flattenTriangle(ir, true, mb.m, (uint32_t)f, t);
         float lo[3], hi[3];
@@ -1138,35 +1213,22 @@ static int updateVertices(GiCScene* s, bool& handled, UpdateCost& cost)
     });
   }
   if (!worldOk) return GI_C_OK;
-  // --- refit units and their levels: thread ranges per level, deepest level first
-  struct Unit { uint32_t nodeOff; const std::vector<uint32_t>* levelStart; };
-  std::vector<Unit> units; std::vector<uint32_t> editedParts;
-  if (!H.partitioned) units.push_back(Unit{0u, &H.bvh.levelStart});
+  // --- refit units and their levels
+  std::vector<RefitUnit> units; std::vector<uint32_t> editedParts;
+  if (!H.partitioned) units.push_back(RefitUnit{0u, &H.bvh.levelStart});
   else {
     std::vector<uint8_t> isEdited(H.meshBuilds.size(), 0);
     for (uint32_t b : edited) isEdited[b] = 1;
     for (uint32_t i = 0; i < (uint32_t)H.parts.size(); i++) {
       const InstPart& P = H.parts[i];
-      if (!isEdited[P.meshBuild]) continue;
+      if (!isEdited[P.meshBuild] || P.retired) continue; // (a retired instance's part is unreachable)
       if (P.activeTris != P.nf || P.levelStart.size() < 2u || P.levelStart.back() != P.nodeCount || (size_t)P.nodeOff + P.nodeCount > H.bvh.nodes.size()) return GI_C_OK;
-      units.push_back(Unit{P.nodeOff, &P.levelStart}); editedParts.push_back(i);
+      units.push_back(RefitUnit{P.nodeOff, &P.levelStart}); editedParts.push_back(i);
     }
     if (units.empty()) return GI_C_OK;
   }
-  size_t maxLevels = 0;
-  for (const Unit& u : units) maxLevels = std::max(maxLevels, u.levelStart->size() - 1u);
-  struct Level { uint32_t first, ranges, threads; };
-  std::vector<RefitRange> ranges; std::vector<Level> levels; // levels[0] = the deepest
-  for (size_t L = maxLevels; L-- > 0;) {
-    Level lv{(uint32_t)ranges.size(), 0u, 0u};
-    for (const Unit& u : units) {
-      if (L + 1u >= u.levelStart->size()) continue;
-      const uint32_t a = (*u.levelStart)[L], e = (*u.levelStart)[L + 1u];
-      if (e <= a || (size_t)u.nodeOff + e > s->nodeCount) return GI_C_OK; // (cannot happen: the levels of a tree inside the node array)
-      ranges.push_back(RefitRange{lv.threads, u.nodeOff + a}); lv.ranges++; lv.threads += e - a;
-    }
-    levels.push_back(lv);
-  }
+  std::vector<RefitRange> ranges; std::vector<RefitLevel> levels;
+  if (!planRefitLevels(units, s->nodeCount, ranges, levels)) return GI_C_OK; // (cannot happen: the levels of a tree inside the node array)
   // --- host: the edited meshes' vertex and shading records; the partitioned layout's host triangles
   // (the shading records are a gather of the vertex records, gi_refit.h refit_gather_shade: the host copy by the function the device runs over its own)
   for (uint32_t b : edited) {
@@ -1181,7 +1243,7 @@ static int updateVertices(GiCScene* s, bool& handled, UpdateCost& cost)
   for (uint32_t i : editedParts) {
     const InstPart& P = H.parts[i];
     const MeshBuild& mb = H.meshBuilds[P.meshBuild];
-    const InstanceRec& ir = H.instances[mb.instFirst + P.instInMesh];
+    const InstanceRec& ir = H.instances[mb.inst[P.instInMesh]];
     for (uint32_t k = 0; k < P.nf; k++) {
       TriRec& t = H.bvh.tris[P.triFirst + k];
       TriRec whole; flattenTriangle(ir, true, mb.m, t.prim, whole);
@@ -1216,7 +1278,7 @@ static int updateVertices(GiCScene* s, bool& handled, UpdateCost& cost)
     copy(dRanges.ptr, ranges.data(), ranges.size() * sizeof(RefitRange), hipMemcpyHostToDevice);
     if (rc == GI_C_OK) {
       launchRefitTris(st, D.dTris.ptr, s->triCount, D.dInstances.ptr, instanceCount, dEdited.ptr, D.dTriShade.ptr, shadeCount);
-      for (const Level& lv : levels) launchRefitLevel(st, D.dNodes.ptr, s->nodeCount, dBoxes.ptr, dRanges.ptr + lv.first, lv.ranges, lv.threads, D.dTris.ptr,
+      for (const RefitLevel& lv : levels) launchRefitLevel(st, D.dNodes.ptr, s->nodeCount, dBoxes.ptr, dRanges.ptr + lv.first, lv.ranges, lv.threads, D.dTris.ptr,
           s->triCount, D.dInstances.ptr, instanceCount, D.dTriShade.ptr, shadeCount);
       if (hipGetLastError() != hipSuccess) { setError("vertex update: launch failed"); rc = GI_C_ERROR; }
     }
@@ -1292,6 +1354,35 @@ bool topologyUpdatesWanted(const GiCScene* s)
   const long o = optionValue("topology_updates", -1);
   return o >= 0 ? o == 1 : s->optTopologyUpdates == 1;
 }
+// Instance updates (opt-in on top of topology updates: GI_C_SCENE_OPTION_INSTANCE_UPDATES / GATLING_OPTIONS=instance_updates=1).  The delegate answers every
+// DirtyInstancer / DirtyInstanceIndex sync of a prim with giSetMeshInstanceTransforms, giSetMeshInstancerPrimvars and giSetMeshInstanceIds (mesh.cpp:530-572):
+// an animated point instancer.  giCSetMeshInstanceIds, and giCSetMeshInstanceTransforms with another count, on a mesh of the built scene note the edit on the
+// mesh (GiCMesh::instEdited, GiCScene::instancesDue) and updateTopology applies it, in front of its other work and sharing it:
+//   ids:     InstanceRec::instanceId of the kept instances [0, min(old, new)) whose id changed is set and the records are re-sent; equal ids send nothing.
+//            Works on every layout updateTopology accepts: ids alone re-lay nothing out.
+//   moves:   a kept instance whose transform differs from the resident record is marked in GiCMesh::instDirty and DIRTY_XFORM is raised: updateTransforms
+//            rebuilds those parts behind this update, as after an adoption.
+//   shrink:  the instances [new, old) retire: InstPart::retired takes their parts out of the top tree for good, their records stay resident until the next
+//            build (MeshBuild::retiredInst: counted as retired triangles in the retired > live rule), the meshes behind are renumbered by the plan.
+//   grow:    the instances [old, new) are appended as the instances of a new mesh are: one InstanceRec, nf records and face ids at the ends of the arrays, one
+//            node range and one part each; ids are the mesh's id base + instance-in-mesh x nf + prim, the meshes behind shift by the plan's idDelta.  A new
+//            part is CLONED from a live sibling part of the mesh where one qualifies -- it was resident before this update, is whole with its levels
+//            (refitsWith's conditions on the part), the mesh is not hidden -- and GATLING_OPTIONS=instance_clone=1 asks for it (default off, see the
+//            measurement in DESIGN.md section 9): k_clone_parts (gi_patch.hip) copies the sibling's records and nodes in device memory, re-transformed, renumbered and rebased,
+//            k_refit_level gives the copied subtree its boxes, level by level over all clones together, and the part roots are read back for the top tree.
+//            The host keeps the records by the function the kernel runs (gi_refit.h refit_clone_record) and the root; the interior is stale on the host and
+//            never read, as after a vertex refit.  A cloned topology is a valid one: only scene-order ids reach an image and the refit is conservative.
+//            Otherwise the part is built by buildPart, or by the device builder from device_parts_min faces on.
+//   scene data: a mesh whose material reads primvars gets the MeshRec / scene-data tables made again (appendMeshSceneData sizes instance-interpolated
+//            entries from the count and the ids).
+// MeshBuild::inst names the InstanceRec of every live instance: after a grow they are no longer one run.  Declines (to buildScene, not an error): whatever
+// updateTopology declines for, a new count of 0, a mesh hidden by the visibility path, an unusable transform of a new instance.
+bool instanceUpdatesWanted(const GiCScene* s)
+{
+  if (!topologyUpdatesWanted(s)) return false;
+  const long o = optionValue("instance_updates", -1);
+  return o >= 0 ? o == 1 : s->optInstanceUpdates == 1;
+}
 // Resyncs (opt-in on top of topology and vertex updates: GI_C_SCENE_OPTION_RESYNC_REFITS / GATLING_OPTIONS=resync_refits=1).  The delegate answers a points or
 // primvar change of a prim with destroy + create of a mesh whose faces did not change: retire + append would leave N dead triangles behind per frame and
 // build a subtree whose topology the resident one already has.  adoptResyncs pairs each retiring mesh R (retired, its MeshBuild not hidden) with a fresh mesh
@@ -1336,7 +1427,7 @@ static bool refitsWith(const GiCScene* s, const SceneHost& H, uint32_t b, const 
   if (mb.hidden || s->stats.inactiveTriangleCount != 0u || !usableVertexPositions(f->vertices.data(), f->vertices.size())) return false;
   if ((size_t)mb.vertexOffset + f->vertices.size() > H.verts.size() || (size_t)mb.shadeBase + f->faces.size() > H.triShade.size()) return false;
   if (H.partitioned) for (const InstPart& P : H.parts)
-    if (P.meshBuild == b && (P.activeTris != P.nf || P.levelStart.size() < 2u || P.levelStart.back() != P.nodeCount)) return false;
+    if (P.meshBuild == b && !P.retired && (P.activeTris != P.nf || P.levelStart.size() < 2u || P.levelStart.back() != P.nodeCount)) return false;
   inst.resize(mb.instCount);
   for (uint32_t ii = 0; ii < mb.instCount; ii++) { inst[ii] = makeInstanceRec(f, mb.meshIdx, ii); if (!usableInstance(inst[ii])) return false; }
   std::atomic<bool> worldOk{true};
@@ -1371,7 +1462,7 @@ static uint32_t adoptResyncs(GiCScene* s, SceneHost& H)
     if (r->material != f->material || !samePrimvars(r->primvars, f->primvars) || !samePrimvars(r->instancerPrimvars, f->instancerPrimvars)) s->dirty |= DIRTY_MATERIALS;
     f->xformDirty = false; f->instDirty.assign(mb.instCount, 0);
     for (uint32_t ii = 0; ii < mb.instCount; ii++)
-      if (memcmp(inst[ii].o2w, H.instances[mb.instFirst + ii].o2w, sizeof(inst[ii].o2w)) != 0) { f->instDirty[ii] = 1; f->xformDirty = true; }
+      if (memcmp(inst[ii].o2w, H.instances[mb.inst[ii]].o2w, sizeof(inst[ii].o2w)) != 0) { f->instDirty[ii] = 1; f->xformDirty = true; }
     if (f->xformDirty) s->dirty |= DIRTY_XFORM; else f->instDirty.clear();
     f->builtInstances = mb.instCount; f->visToggled = false;
     mb.m = f;
@@ -1404,10 +1495,26 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
   // updateVertices has run behind this update, H.verts / H.triShade still hold R's points while a re-layout below builds the parts from F's: F is marked
   // vertsEdited whenever the bytes differ, and an updateVertices that declines rebuilds as well.
   const uint32_t adopted = resyncRefitsWanted(s) ? adoptResyncs(s, H) : 0u;
+  // --- instance edits of built meshes (the caller has established that the option is wanted): which, and what they add and retire
+  struct InstEdit { uint32_t b, oldCount, newCount; };
+  std::vector<InstEdit> instEdits;
+  uint64_t grownTris = 0, grownParts = 0, shrunkTris = 0, shrunkParts = 0; bool sceneDataStale = false;
+  for (uint32_t b = 0; b < (uint32_t)H.meshBuilds.size(); b++) {
+    const MeshBuild& mb = H.meshBuilds[b];
+    if (!mb.m->instEdited || mb.m->retired) continue;
+    const size_t newCount = mb.m->instanceTransforms.size() / 16;
+    if (newCount == 0u || newCount >= 0xffffffffu || mb.hidden) return GI_C_OK; // (a mesh without instances leaves the scene; a hidden one has ids to come back to)
+    instEdits.push_back(InstEdit{b, mb.instCount, (uint32_t)newCount});
+    const uint64_t nf = mb.m->faces.size();
+    if (newCount > mb.instCount) { grownParts += newCount - mb.instCount; grownTris += (newCount - mb.instCount) * nf; }
+    else { shrunkParts += mb.instCount - newCount; shrunkTris += (mb.instCount - newCount) * nf; }
+    if (mb.m->material) for (uint32_t slot = 0; slot < TEX_SLOT_COUNT; slot++) if (!mb.m->material->primvarInput[slot].empty()) sceneDataStale = true;
+  }
+  const bool countsChange = grownParts != 0u || shrunkParts != 0u;
   // --- the meshes to append: what a fresh build would hold and the resident scene does not, all of them behind every live built mesh
   struct NewMesh { GiCMesh* m; uint32_t material; };
   std::vector<NewMesh> fresh;
-  uint64_t appendedTris = 0, appendedParts = 0;
+  uint64_t appendedTris = grownTris, appendedParts = grownParts;
   for (GiCMesh* m : s->meshes) {
     if (m->builtInstances != 0xffffffffu) { if (!fresh.empty()) return GI_C_OK; continue; }
     if (!m->visible || m->faces.empty()) continue; // (as buildScene)
@@ -1423,10 +1530,11 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
   // --- what the scene holds after the edit
   uint64_t live = appendedTris, retired = 0, visible = appendedTris, partsNow = 0; uint32_t retiring = 0;
   for (const MeshBuild& mb : H.meshBuilds) {
-    const uint64_t n = (uint64_t)mb.instCount * mb.m->faces.size();
-    partsNow += mb.instCount;
-    if (mb.m->retired) { retired += n; if (!mb.hidden) retiring++; } else { live += n; if (!mb.hidden) visible += n; }
+    const uint64_t n = (uint64_t)mb.instCount * mb.m->faces.size(), gone = (uint64_t)mb.retiredInst * mb.m->faces.size(); // (gone: instances retired earlier)
+    partsNow += mb.instCount + mb.retiredInst;
+    if (mb.m->retired) { retired += n + gone; if (!mb.hidden) retiring++; } else { live += n; retired += gone; if (!mb.hidden) visible += n; }
   }
+  live -= shrunkTris; visible -= shrunkTris; retired += shrunkTris; // (the instances this update retires: of live, visible meshes)
   if (visible < kIncrementalMinTris || retired > live || partsNow == 0u) return GI_C_OK;
   // a flat scene that loses more than it keeps: the re-layout would spend its time on subtrees for what is leaving (measured on C3, one mesh resynced: 809 ms
   // against the 580 ms of the build that follows anyway once the retired triangles outnumber the live ones)
@@ -1436,8 +1544,47 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
   if (appendedParts && (partsNow + appendedParts) * 2u + 16u > topCap) return GI_C_OK; // the top tree may outgrow its range
   const uint32_t nDev = residentDeviceCount(s);
   const bool timing = getenv("GATLING_BUILD_TIMING") != nullptr;
-  if (fresh.empty() && retiring == 0u && adopted == 0u) { // the edited meshes are not part of a fresh build either (invisible, no faces, no valid material)
+  if (fresh.empty() && retiring == 0u && adopted == 0u && instEdits.empty()) { // the edited meshes are not part of a fresh build either (invisible, no faces, no valid material)
     for (GiCMesh* m : s->meshes) if (m->builtInstances == 0xffffffffu) { m->visToggled = false; m->vertsEdited = false; }
+    handled = true;
+    return GI_C_OK;
+  }
+  // --- instance edits, committed: from here on the MeshBuilds and the meshes hold the new counts (every decline behind this point leads to the full build, as
+  // after an adoption).  Ids and moves of the kept instances; the retired instances' parts; the records of appended instances follow the plan below
+  std::vector<uint32_t> idRecords; // InstanceRecs to re-send
+  uint32_t movedInstances = 0;
+  for (const InstEdit& e : instEdits) {
+    MeshBuild& mb = H.meshBuilds[e.b];
+    GiCMesh* m = const_cast<GiCMesh*>(mb.m);
+    const uint32_t kept = std::min(e.oldCount, e.newCount);
+    const bool all = m->xformDirty && m->instDirty.empty(); // (a giCSetMeshTransform is due as well: every part is rebuilt anyway)
+    if (!all) m->instDirty.resize(e.newCount, 0);
+    for (uint32_t ii = 0; ii < kept; ii++) {
+      InstanceRec& resident = H.instances[mb.inst[ii]];
+      const InstanceRec want = makeInstanceRec(m, mb.meshIdx, ii);
+      if (want.instanceId != resident.instanceId) { resident.instanceId = want.instanceId; idRecords.push_back(mb.inst[ii]); }
+      if (memcmp(want.o2w, resident.o2w, sizeof(want.o2w)) != 0) { movedInstances++; m->xformDirty = true; if (!all) m->instDirty[ii] = 1; }
+    }
+    if (m->xformDirty) s->dirty |= DIRTY_XFORM; else m->instDirty.clear();
+    if (H.partitioned) for (InstPart& P : H.parts) if (P.meshBuild == e.b && !P.retired && P.instInMesh >= e.newCount) P.retired = true;
+    if (e.newCount < e.oldCount) { mb.inst.resize(e.newCount); mb.retiredInst += e.oldCount - e.newCount; }
+    mb.instCount = e.newCount; m->builtInstances = e.newCount; m->instEdited = false;
+  }
+  // --- ids alone (and moves, which updateTransforms takes): nothing is laid out, appended or retired.  Every layout
+  if (fresh.empty() && retiring == 0u && adopted == 0u && !countsChange) {
+    if (sceneDataStale && !(s->dirty & DIRTY_MATERIALS)) remakeSceneData(H); // (with a material edit due updateMaterials makes the tables behind this update)
+    else sceneDataStale = false;
+    if (onSceneDevices(s, idRecords.empty() && !sceneDataStale ? 0u : nDev, [&](SceneDevice& D, hipStream_t st) -> int {
+      if (D.dInstances.count < H.instances.size()) { setError("internal: the device holds less than the scene"); return GI_C_ERROR; }
+      for (const uint32_t rec : idRecords) HIP_TRY(hipMemcpyAsync(D.dInstances.ptr + rec, &H.instances[rec], sizeof(InstanceRec), hipMemcpyHostToDevice, st));
+      if (sceneDataStale && (D.dMeshes.upload(H.meshRecs, st) || D.dSceneData.upload(H.sceneData, st))) return GI_C_ERROR;
+      HIP_TRY(hipStreamSynchronize(st));
+      return GI_C_OK;
+    }) != GI_C_OK) return GI_C_ERROR;
+    cost.uploadMs = nowMs() - t0;
+    if (timing) fprintf(stderr, "[gatling_gi] instance update: 0 instance(s) retired, 0 appended (0 cloned, 0 built), %zu instance record(s) re-sent for their ids, %u moved, "
+                                "0 node and record byte(s) sent for the new parts, builds 0.00 ms, rest %.2f ms\n", idRecords.size(), movedInstances, cost.uploadMs);
+    s->instanceCounts[0]++;
     handled = true;
     return GI_C_OK;
   }
@@ -1460,6 +1607,8 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
   if (s->dirty & DIRTY_MATERIALS) buildMaterialRecords(s, H.mats); // the new meshes' words come from the current table; updateMaterials runs behind this update
   const size_t vert0 = H.verts.size(), shade0 = H.triShade.size(), node0 = H.bvh.nodes.size(), part0 = H.parts.size();
   uint64_t idBase = plan.visibleTris; // the visible triangles in front of the next appended mesh
+  // (25 % slack, as on the device: a std::vector would double 0.7 GB of triangles on the first append to C5 and copy them on every later doubling)
+  auto grown = [](auto& v, size_t n) { if (v.capacity() < n) v.reserve(n + n / 4u); v.resize(n); };
   for (const NewMesh& nm : fresh) {
     GiCMesh* m = nm.m;
     const uint32_t matFlags = meshMatFlags(H.mats[nm.material], nm.material, m);
@@ -1470,30 +1619,72 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
     H.meshBuilds.push_back(MeshBuild{m, vertexOffset, matFlags, (uint32_t)H.instances.size(), instCount, triFirst, meshIdx, faceIdAovOf(m)});
     H.meshBuilds.back().shadeBase = (uint32_t)H.triShade.size(); H.meshBuilds.back().idBase = (uint32_t)idBase;
     for (const GiCFace& f : m->faces) H.triShade.push_back(packTriShade(m->vertices.data(), f, vertexOffset));
-    // (25 % slack, as on the device: a std::vector would double 0.7 GB of triangles on the first append to C5 and copy them on every later doubling)
-    auto grown = [](auto& v, size_t n) { if (v.capacity() < n) v.reserve(n + n / 4u); v.resize(n); };
     grown(H.instances, H.instances.size() + instCount); grown(H.bvh.tris, (size_t)triFirst + (size_t)instCount * nf); grown(H.triFaceId, H.bvh.tris.size());
     for (uint32_t ii = 0; ii < instCount; ii++) { InstPart P{}; P.meshBuild = meshIdx; P.instInMesh = ii; P.triFirst = triFirst + ii * nf; P.nf = nf;
         H.parts.push_back(P); }
     idBase += (uint64_t)instCount * nf;
+    H.meshBuilds.back().numberInstances();
   }
-  // --- the new parts: built on the host here, or flattened for the device builder
+  // --- append, instances of built meshes: one record, one triangle range and one part each; the part it may be cloned from
+  // (the sibling itself must be whole: inactive triangles elsewhere in the scene do not concern a clone, whose refit reads its own range alone)
+  // Opt-in (GATLING_OPTIONS=instance_clone=1): measured on C5, 64 clones cost 16 - 22 % of traceMs against a tree built from scratch
+  const bool cloneWanted = optionValue("instance_clone", 0) == 1;
+  std::vector<int64_t> siblingOfPart; // per new part: the resident part to clone, or -1
+  siblingOfPart.assign(H.parts.size() - part0, -1);
+  for (const InstEdit& e : instEdits) {
+    if (e.newCount <= e.oldCount) continue;
+    MeshBuild& mb = H.meshBuilds[e.b];
+    const uint32_t nf = (uint32_t)mb.m->faces.size();
+    int64_t sibling = -1;
+    if (cloneWanted) for (size_t i = 0; i < part0 && sibling < 0; i++) {
+      const InstPart& P = H.parts[i];
+      if (P.meshBuild == e.b && !P.retired && P.nf == nf && P.activeTris == P.nf && P.levelStart.size() >= 2u && P.levelStart.back() == P.nodeCount && P.nodeCount != 0u &&
+          (size_t)P.nodeOff + P.nodeCount <= node0 && (size_t)P.triFirst + P.nf <= oldTris) sibling = (int64_t)i;
+    }
+    for (uint32_t ii = e.oldCount; ii < e.newCount; ii++) {
+      mb.inst.push_back((uint32_t)H.instances.size());
+      grown(H.instances, H.instances.size() + 1u);
+      InstPart P{}; P.meshBuild = e.b; P.instInMesh = ii; P.triFirst = (uint32_t)H.bvh.tris.size(); P.nf = nf;
+      grown(H.bvh.tris, (size_t)P.triFirst + nf); grown(H.triFaceId, H.bvh.tris.size());
+      H.parts.push_back(P); siblingOfPart.push_back(sibling);
+    }
+  }
+  // the tables of a mesh whose material reads primvars are sized from its instance count and ids (with a material edit due updateMaterials makes them anew)
+  if (sceneDataStale && !(s->dirty & DIRTY_MATERIALS)) remakeSceneData(H);
+  // --- the new parts: built on the host here, flattened for the device builder, or cloned from a resident sibling
   const long wantDevice = optionValue("device_build", -1);
   const bool deviceParts = wantDevice < 0 ? s->optBvhBuild == 1 : wantDevice == 1;
   const size_t devicePartsMin = (size_t)std::max(optionValue("device_parts_min", kDevicePartsMinDefault), 1L);
-  struct NewPart { bool onDevice = false, ok = true; PartBuild built; std::vector<TriRec> flat; DeviceBvhResult dev; };
+  struct NewPart { bool onDevice = false, ok = true; int64_t sibling = -1; PartBuild built; std::vector<TriRec> flat; DeviceBvhResult dev; };
   std::vector<NewPart> newParts(H.parts.size() - part0);
   const double tb0 = nowMs();
   parallelOver(newParts.size(), [&](size_t k) {
     NewPart& np = newParts[k];
     const InstPart& P = H.parts[part0 + k];
     const MeshBuild& mb = H.meshBuilds[P.meshBuild];
+    np.sibling = siblingOfPart[k];
+    if (np.sibling >= 0) {
+      // a clone: the sibling's records (as the host holds them) under the new instance, by the function k_clone_parts runs over the device's; every triangle
+      // must be active by the builders' rule, as on the other routes
+      const InstPart& S = H.parts[(size_t)np.sibling];
+      np.built.inst = makeInstanceRec(mb.m, mb.meshIdx, P.instInMesh);
+      np.ok = usableInstance(np.built.inst);
+      np.flat.resize(P.nf);
+      for (uint32_t j = 0; j < P.nf && np.ok; j++) {
+        const TriRec& src = H.bvh.tris[S.triFirst + j];
+        if (src.vi[0] >= H.triShade.size()) { np.ok = false; break; }
+        np.flat[j] = refit_clone_record(src, np.built.inst.o2w, H.triShade[src.vi[0]].p, mb.inst[P.instInMesh], mb.idBase + P.instInMesh * P.nf);
+        float lo[3], hi[3];
+        np.ok = refit_tri_box(np.flat[j].v0, np.flat[j].e1, np.flat[j].e2, lo, hi);
+      }
+      return;
+    }
     np.onDevice = deviceParts && P.nf >= devicePartsMin && P.nf > 128u; // (more than 128 faces: the size from which the scene's own device build runs)
     if (!np.onDevice) { buildPart(mb, P.instInMesh, true, np.built); np.ok = np.built.bvh.activeTris == P.nf; return; }
     // (ids from 0, as buildPart: k_place_part adds the instance's base)
     np.built.inst = makeInstanceRec(mb.m, mb.meshIdx, P.instInMesh);
     np.flat.resize(P.nf);
-    flattenInstance(np.built.inst, mb.instFirst + P.instInMesh, mb.m, mb.vertexOffset, mb.matFlags, 0u, mb.shadeBase, np.flat.data());
+    flattenInstance(np.built.inst, mb.inst[P.instInMesh], mb.m, mb.vertexOffset, mb.matFlags, 0u, mb.shadeBase, np.flat.data());
     for (const TriRec& t : np.flat) // inactive by the builders' rule (bvh8.cpp prepareRange)
       for (int a = 0; a < 3; a++) np.ok = np.ok && usableCoordinate(t.v0[a]) && usableCoordinate(t.v0[a] + t.e1[a]) && usableCoordinate(t.v0[a] + t.e2[a]);
   });
@@ -1502,7 +1693,7 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
   // --- devices, first pass: the arrays grown, what does not depend on node ranges sent, the retired meshes' patch, the device builder over its parts
   std::vector<std::vector<Node8*>> partNodes(nDev, std::vector<Node8*>(newParts.size(), nullptr)); // the builder's blocks, per device
   auto freePartNodes = [&] { for (auto& v : partNodes) for (Node8*& p : v) if (p) { (void)hipFree(p); p = nullptr; } };
-  bool outOfMemory = false; double deviceBuildMs = 0.0; uint32_t builtOnDevice = 0;
+  bool outOfMemory = false; double deviceBuildMs = 0.0; uint32_t builtOnDevice = 0; size_t devicePartBytesSent = 0;
   int rc = onSceneDevices(s, nDev, [&](SceneDevice& D, hipStream_t st) -> int {
     if (D.slot >= nDev) { setError("internal: device slot out of range"); return GI_C_ERROR; }
     if (D.dTris.count < oldTris || D.dInstances.count < oldInstances || D.dTriShade.count < shade0 || D.dVerts.count < vert0 || D.dTriFaceId.count < oldTris ||
@@ -1518,6 +1709,7 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
       if (r == GI_C_OK && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) != hipSuccess) { setError("topology update: copy failed"); r = GI_C_ERROR; } };
     copy(D.dVerts.ptr + vert0, H.verts.data() + vert0, (H.verts.size() - vert0) * sizeof(FVertex));
     copy(D.dTriShade.ptr + shade0, H.triShade.data() + shade0, (H.triShade.size() - shade0) * sizeof(TriShade));
+    for (const uint32_t rec : idRecords) copy(D.dInstances.ptr + rec, &H.instances[rec], sizeof(InstanceRec)); // (instance ids of built meshes: rec < oldInstances)
     if (r == GI_C_OK && plan.launch) {
       if (dPatch.upload(plan.patch, st)) r = GI_C_ERROR;
       else launchPatchVisibility(st, D.dTris.ptr, oldTris, D.dInstances.ptr, oldInstances, dPatch.ptr, D.dTriShade.ptr, (uint32_t)H.triShade.size());
@@ -1530,6 +1722,7 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
       if ((size_t)P.triFirst + P.nf > D.dTris.count || (size_t)P.triFirst + P.nf > D.dTriFaceId.count) { setError("internal: part outside the arrays"); r = GI_C_ERROR; break; }
       copy(D.dTris.ptr + P.triFirst, np.flat.data(), (size_t)P.nf * sizeof(TriRec));
       copy(D.dTriFaceId.ptr + P.triFirst, mb.faceIdAov.data(), (size_t)P.nf * sizeof(int32_t));
+      if (D.slot == 0u) devicePartBytesSent += (size_t)P.nf * (sizeof(TriRec) + sizeof(int32_t));
       if (r != GI_C_OK) break;
       const double ta = nowMs();
       DeviceBvhResult res;
@@ -1565,7 +1758,7 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
   const double tb1 = nowMs();
   for (size_t k = 0; k < newParts.size(); k++) {
     NewPart& np = newParts[k];
-    if (np.onDevice || !np.built.bvh.nodes.empty()) continue;
+    if (np.onDevice || np.sibling >= 0 || !np.built.bvh.nodes.empty()) continue;
     const InstPart& P = H.parts[part0 + k];
     buildPart(H.meshBuilds[P.meshBuild], P.instInMesh, true, np.built);
     if (np.built.bvh.activeTris != P.nf) { freePartNodes(); return GI_C_OK; }
@@ -1574,7 +1767,8 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
   size_t off = node0;
   for (size_t k = 0; k < newParts.size(); k++) {
     InstPart& P = H.parts[part0 + k];
-    const uint32_t n = newParts[k].onDevice ? newParts[k].dev.nodeCount : (uint32_t)newParts[k].built.bvh.nodes.size();
+    const uint32_t n = newParts[k].sibling >= 0 ? H.parts[(size_t)newParts[k].sibling].nodeCount
+        : newParts[k].onDevice ? newParts[k].dev.nodeCount : (uint32_t)newParts[k].built.bvh.nodes.size();
     P.nodeOff = (uint32_t)off; P.nodeCap = n + n / 4u + 8u; off += P.nodeCap;
   }
   if (off * sizeof(Node8) >= ((size_t)1 << 32)) { freePartNodes(); return GI_C_OK; } // (the flat walk addresses nodes by 32-bit byte offset)
@@ -1582,6 +1776,15 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
   parallelOver(newParts.size(), [&](size_t k) {
     const NewPart& np = newParts[k];
     InstPart& P = H.parts[part0 + k];
+    if (np.sibling >= 0) {
+      // a clone: the sibling's shape; the records by the kernel's function, in the order the host holds the sibling's; the root and the box follow the
+      // device's refit below.  The interior is stale on the host and never read: the only upload of a part's node range follows placePart, which rewrites it
+      const InstPart& S = H.parts[(size_t)np.sibling];
+      P.nodeCount = S.nodeCount; P.depth = S.depth; P.activeTris = S.activeTris; P.levelStart = S.levelStart;
+      for (uint32_t j = 0; j < P.nf; j++) { H.bvh.tris[P.triFirst + j] = np.flat[j]; H.triFaceId[P.triFirst + j] = H.triFaceId[S.triFirst + j]; }
+      H.instances[H.meshBuilds[P.meshBuild].inst[P.instInMesh]] = np.built.inst;
+      return;
+    }
     if (!np.onDevice) { placePart(H, P, np.built); return; }
     // a device-built part: the root (rebased as k_place_part rebases it) for the top tree, the records in scene order with their final ids -- the order
     // differs from the device's leaf order, and nothing uploads these records before a placePart has rewritten them
@@ -1591,11 +1794,26 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
     H.bvh.nodes[P.nodeOff] = root;
     for (uint32_t f = 0; f < P.nf; f++) { TriRec t = np.flat[f]; t.origId += mb.idBase + P.instInMesh * P.nf; H.bvh.tris[P.triFirst + f] = t;
         H.triFaceId[P.triFirst + f] = mb.faceIdAov[f]; }
-    H.instances[mb.instFirst + P.instInMesh] = np.built.inst;
+    H.instances[mb.inst[P.instInMesh]] = np.built.inst;
     nodeBounds(root, P.box);
   });
-  if (rebuildTop(s, H) != GI_C_OK) { freePartNodes(); return GI_C_ERROR; }
-  setSceneBounds(s, H.bvh.nodes);
+  // the clones: one table entry each, and the levels of their refit (the sibling's), all clones together in one launch per level
+  std::vector<CloneEntry> cloneEntries; std::vector<uint32_t> cloneParts; std::vector<RefitUnit> cloneUnits; uint32_t cloneThreads = 0;
+  for (size_t k = 0; k < newParts.size(); k++) {
+    if (newParts[k].sibling < 0) continue;
+    const InstPart& P = H.parts[part0 + k]; const InstPart& S = H.parts[(size_t)newParts[k].sibling];
+    const MeshBuild& mb = H.meshBuilds[P.meshBuild];
+    cloneEntries.push_back(CloneEntry{cloneThreads, S.triFirst, P.triFirst, P.nf, S.nodeOff, P.nodeOff, P.nodeCount, mb.inst[P.instInMesh], mb.idBase + P.instInMesh * P.nf});
+    cloneThreads += cloneEntryThreads(P.nf, P.nodeCount);
+    cloneParts.push_back((uint32_t)(part0 + k)); cloneUnits.push_back(RefitUnit{P.nodeOff, &P.levelStart});
+  }
+  std::vector<RefitRange> cloneRanges; std::vector<RefitLevel> cloneLevels; std::vector<Node8> cloneRoots(cloneEntries.size());
+  if (!planRefitLevels(cloneUnits, (uint32_t)H.bvh.nodes.size(), cloneRanges, cloneLevels)) { freePartNodes(); return GI_C_OK; } // (cannot happen)
+  // (with clones the top tree waits for their roots: built and sent behind the second pass)
+  if (cloneEntries.empty()) {
+    if (rebuildTop(s, H) != GI_C_OK) { freePartNodes(); return GI_C_ERROR; }
+    setSceneBounds(s, H.bvh.nodes);
+  }
   // (with a material edit due as well the resident words index the previous table: updateMaterials derives the classes behind this update)
   if (!(s->dirty & DIRTY_MATERIALS)) deriveSceneClasses(s, H, false);
   for (const NewMesh& nm : fresh) { nm.m->builtInstances = (uint32_t)(nm.m->instanceTransforms.size() / 16); nm.m->xformDirty = false; nm.m->instDirty.clear(); }
@@ -1603,6 +1821,7 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
   for (const NewMesh& nm : fresh) { nm.m->visToggled = false; nm.m->vertsEdited = false; }
   for (GiCMesh* m : s->meshes) if (m->builtInstances == 0xffffffffu) { m->visToggled = false; m->vertsEdited = false; }
   s->triCount = (uint32_t)H.bvh.tris.size(); s->nodeCount = (uint32_t)H.bvh.nodes.size();
+  size_t partBytesSent = 0; // node, record and face-id bytes the host sent for the new parts, per device (a clone: none)
   // --- devices, second pass: the node array grown, the new ranges, the device-built parts placed, the top tree, the small tables
   rc = onSceneDevices(s, nDev, [&](SceneDevice& D, hipStream_t st) -> int {
     std::vector<void*> old;
@@ -1610,25 +1829,61 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
     if (r == GI_C_OUT_OF_MEMORY_INTERNAL) { outOfMemory = true; r = DEVICE_BUILD_FALLBACK; }
     auto copy = [&](void* dst, const void* src, size_t bytes) {
       if (r == GI_C_OK && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) != hipSuccess) { setError("topology update: copy failed"); r = GI_C_ERROR; } };
-    // (the whole new node range, reserves included: zeros where no node lives; k_place_part then writes the device-built parts over their ranges)
-    copy(D.dNodes.ptr + node0, H.bvh.nodes.data() + node0, (H.bvh.nodes.size() - node0) * sizeof(Node8));
+    // (every new node range whole, reserves included: zeros where no node lives; k_place_part then writes the device-built parts over their ranges.  The
+    // ranges tile [node0, end).  A CLONE gets nothing from the host per node or per triangle: its range is zeroed where it lives and k_clone_parts fills it)
+    if (r == GI_C_OK && D.dNodes.count < H.bvh.nodes.size()) { setError("internal: the device holds less than the scene"); r = GI_C_ERROR; }
     copy(D.dInstances.ptr + oldInstances, H.instances.data() + oldInstances, (H.instances.size() - oldInstances) * sizeof(InstanceRec));
     for (size_t k = 0; k < newParts.size() && r == GI_C_OK; k++) {
       const InstPart& P = H.parts[part0 + k];
-      if ((size_t)P.nodeOff + P.nodeCount > D.dNodes.count || (size_t)P.triFirst + P.nf > D.dTris.count || (size_t)P.triFirst + P.nf > D.dTriFaceId.count) {
+      if ((size_t)P.nodeOff + P.nodeCap > D.dNodes.count || P.nodeCount > P.nodeCap || (size_t)P.triFirst + P.nf > D.dTris.count || (size_t)P.triFirst + P.nf > D.dTriFaceId.count) {
         setError("internal: part outside the arrays"); r = GI_C_ERROR; break; }
+      if (newParts[k].sibling >= 0) {
+        if (hipMemsetAsync(D.dNodes.ptr + P.nodeOff, 0, (size_t)P.nodeCap * sizeof(Node8), st) != hipSuccess) { setError("topology update: memset failed"); r = GI_C_ERROR; }
+        continue;
+      }
+      copy(D.dNodes.ptr + P.nodeOff, &H.bvh.nodes[P.nodeOff], (size_t)P.nodeCap * sizeof(Node8));
+      if (D.slot == 0u) partBytesSent += (size_t)P.nodeCap * sizeof(Node8);
       if (newParts[k].onDevice) {
         const MeshBuild& mb = H.meshBuilds[P.meshBuild];
         launchPlacePart(st, partNodes[D.slot][k], P.nodeCount, D.dNodes.ptr, P.nodeOff, D.dTris.ptr, P.triFirst, P.nf, mb.idBase + P.instInMesh * P.nf);
       } else {
         copy(D.dTris.ptr + P.triFirst, &H.bvh.tris[P.triFirst], (size_t)P.nf * sizeof(TriRec));
         copy(D.dTriFaceId.ptr + P.triFirst, &H.triFaceId[P.triFirst], (size_t)P.nf * sizeof(int32_t));
+        if (D.slot == 0u) partBytesSent += (size_t)P.nf * (sizeof(TriRec) + sizeof(int32_t));
       }
     }
-    if (r == GI_C_OK && uploadTopTree(D, H, st) != GI_C_OK) r = GI_C_ERROR;
+    // the clones, behind the uploads of the new InstanceRecs and node ranges on the same stream: copied, refitted level by level, the roots read back
+    DeviceBuffer<CloneEntry> dClones; DeviceBuffer<RefitRange> dRanges; DeviceBuffer<float> dBoxes;
+    if (r == GI_C_OK && !cloneEntries.empty()) {
+      const uint32_t nodeCount = (uint32_t)H.bvh.nodes.size(), triCount = (uint32_t)H.bvh.tris.size(), instanceCount = (uint32_t)H.instances.size(),
+          shadeCount = (uint32_t)H.triShade.size();
+      for (const CloneEntry& c : cloneEntries) // both ranges of every clone inside what the device holds
+        if ((size_t)c.srcTri + c.nf > oldTris || (size_t)c.dstTri + c.nf > D.dTris.count || (size_t)c.dstTri + c.nf > D.dTriFaceId.count || (size_t)c.srcNode + c.nodeCount > node0 ||
+            (size_t)c.dstNode + c.nodeCount > D.dNodes.count || c.instance >= D.dInstances.count || c.dstTri < oldTris || c.dstNode < node0) {
+          setError("internal: clone outside the arrays"); r = GI_C_ERROR; break; }
+      if (r == GI_C_OK && (D.dNodes.count < nodeCount || D.dTris.count < triCount || D.dTriShade.count < shadeCount)) { setError("internal: the device holds less than the scene"); r = GI_C_ERROR; }
+      if (r == GI_C_OK) {
+        const int a = dBoxes.alloc((size_t)nodeCount * 8u), b = a ? a : dClones.alloc(cloneEntries.size()), c = b ? b : dRanges.alloc(cloneRanges.size());
+        if (c == GI_C_OUT_OF_MEMORY_INTERNAL) { outOfMemory = true; r = DEVICE_BUILD_FALLBACK; } else if (c != GI_C_OK) r = GI_C_ERROR;
+      }
+      copy(dClones.ptr, cloneEntries.data(), cloneEntries.size() * sizeof(CloneEntry));
+      copy(dRanges.ptr, cloneRanges.data(), cloneRanges.size() * sizeof(RefitRange));
+      if (r == GI_C_OK) {
+        launchCloneParts(st, dClones.ptr, (uint32_t)cloneEntries.size(), cloneThreads, D.dTris.ptr, triCount, D.dTriFaceId.ptr, D.dNodes.ptr, nodeCount, D.dInstances.ptr,
+            instanceCount, D.dTriShade.ptr, shadeCount);
+        for (const RefitLevel& lv : cloneLevels) launchRefitLevel(st, D.dNodes.ptr, nodeCount, dBoxes.ptr, dRanges.ptr + lv.first, lv.ranges, lv.threads, D.dTris.ptr,
+            triCount, D.dInstances.ptr, instanceCount, D.dTriShade.ptr, shadeCount);
+        if (D.slot == 0u) // (the clone and the refit are deterministic: every device holds the same bytes)
+          for (size_t k = 0; k < cloneEntries.size() && r == GI_C_OK; k++)
+            if (hipMemcpyAsync(&cloneRoots[k], D.dNodes.ptr + cloneEntries[k].dstNode, sizeof(Node8), hipMemcpyDeviceToHost, st) != hipSuccess) {
+              setError("topology update: copy failed"); r = GI_C_ERROR; }
+      }
+    }
+    if (r == GI_C_OK && cloneEntries.empty() && uploadTopTree(D, H, st) != GI_C_OK) r = GI_C_ERROR;
     if (r == GI_C_OK && (D.dMeshes.upload(H.meshRecs, st) || D.dSceneData.upload(H.sceneData, st))) r = GI_C_ERROR;
     if (r == GI_C_OK && hipGetLastError() != hipSuccess) { setError("topology update: launch failed"); r = GI_C_ERROR; }
     if (hipStreamSynchronize(st) != hipSuccess && r == GI_C_OK) { setError("topology update: device error"); r = GI_C_ERROR; }
+    dClones.release(); dRanges.release(); dBoxes.release(); // (before the render's memory plan reads free memory)
     for (Node8*& p : partNodes[D.slot]) if (p) { (void)hipFree(p); p = nullptr; } // the builder's blocks
     for (void* p : old) (void)hipFree(p);
     return r;
@@ -1639,12 +1894,29 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
     return GI_C_OK;
   }
   if (rc != GI_C_OK) return GI_C_ERROR;
+  if (!cloneEntries.empty()) { // the clones' roots and boxes as the device refitted them, then the top tree over all parts
+    for (size_t k = 0; k < cloneParts.size(); k++) { InstPart& P = H.parts[cloneParts[k]]; H.bvh.nodes[P.nodeOff] = cloneRoots[k]; nodeBounds(cloneRoots[k], P.box); }
+    if (rebuildTop(s, H) != GI_C_OK) return GI_C_ERROR;
+    setSceneBounds(s, H.bvh.nodes);
+    if (onSceneDevices(s, nDev, [&](SceneDevice& D, hipStream_t st) -> int {
+      if (uploadTopTree(D, H, st) != GI_C_OK) return GI_C_ERROR;
+      HIP_TRY(hipStreamSynchronize(st));
+      return GI_C_OK;
+    }) != GI_C_OK) return GI_C_ERROR;
+  }
   const double t2 = nowMs();
   cost.buildMs = buildMs; cost.uploadMs = std::max(t2 - t0 - buildMs, 0.0);
   s->resyncCount += adopted;
+  if (!instEdits.empty()) {
+    s->instanceCounts[0]++; s->instanceCounts[1] += grownParts; s->instanceCounts[2] += cloneEntries.size(); s->instanceCounts[3] += shrunkParts;
+    if (timing) fprintf(stderr, "[gatling_gi] instance update: %llu instance(s) retired, %llu appended (%zu cloned, %llu built), %zu instance record(s) re-sent for their ids, "
+                                "%u moved, %zu node and record byte(s) sent for the new parts, builds %.2f ms, rest %.2f ms\n", (unsigned long long)shrunkParts,
+                        (unsigned long long)grownParts, cloneEntries.size(), (unsigned long long)(grownParts - cloneEntries.size()), idRecords.size(), movedInstances,
+                        partBytesSent + devicePartBytesSent, cost.buildMs, cost.uploadMs);
+  }
   if (timing) fprintf(stderr, "[gatling_gi] topology update:%s %u mesh(es) retired, %u adopted by their resync, %zu appended, %zu part(s) built, %u of them on the "
                               "device (k_place_part), %llu live + %llu retired triangle(s), %u resident, builds %.2f ms, rest %.2f ms\n", converted
-                                  ? " scene re-laid out as per-instance subtrees," : "", retiring, adopted, fresh.size(), newParts.size(), builtOnDevice,
+                                  ? " scene re-laid out as per-instance subtrees," : "", retiring, adopted, fresh.size(), newParts.size() - cloneEntries.size(), builtOnDevice,
                       (unsigned long long)live, (unsigned long long)retired, s->triCount, cost.buildMs, cost.uploadMs);
   handled = true;
   return GI_C_OK;
@@ -1676,8 +1948,11 @@ int syncSceneGeometry(GiCScene* s)
   // DIRTY_BVH with topologyDue: meshes were created or destroyed, or meshes outside the built scene edited.  Without the option that is the rebuild, in today's
   // order of events.  With it updateTopology runs in front of every other path (the meshes it appends are part of the scene for them) and clears DIRTY_BVH
   // unless toggles or vertex edits of other meshes are due as well; a decline makes the rebuild due.
+  // DIRTY_BVH with instancesDue: instance ids or counts of built meshes changed (GiCMesh::instEdited).  The same shape: without
+  // GI_C_SCENE_OPTION_INSTANCE_UPDATES that is the rebuild; with it updateTopology applies them in front of its other work.
   if (s->topologyDue && !topologyUpdatesWanted(s)) s->rebuildDue = true;
-  const bool topologyRuns = (s->dirty & DIRTY_BVH) && !s->rebuildDue && s->topologyDue;
+  if (s->instancesDue && !instanceUpdatesWanted(s)) s->rebuildDue = true;
+  const bool topologyRuns = (s->dirty & DIRTY_BVH) && !s->rebuildDue && (s->topologyDue || s->instancesDue);
   int rc = run(topologyRuns, updateTopology, UPDATE_TOPOLOGY, 0u, DIRTY_BVH, 0u);
   bool anyVis = false, anyVerts = false;
   for (const GiCMesh* m : s->meshes) { anyVis = anyVis || m->visToggled; anyVerts = anyVerts || m->vertsEdited; }
@@ -1696,7 +1971,7 @@ int syncSceneGeometry(GiCScene* s)
     s->updateCounts[UPDATE_FULL]++;
     s->dirty &= ~(DIRTY_BVH | DIRTY_MATERIALS); s->dirty |= DIRTY_FRAMEBUFFER;
   }
-  s->dirty &= ~DIRTY_XFORM; s->rebuildDue = false; s->topologyDue = false;
-  for (GiCMesh* m : s->meshes) { m->visToggled = false; m->vertsEdited = false; }
+  s->dirty &= ~DIRTY_XFORM; s->rebuildDue = false; s->topologyDue = false; s->instancesDue = false;
+  for (GiCMesh* m : s->meshes) { m->visToggled = false; m->vertsEdited = false; m->instEdited = false; }
   return GI_C_OK;
 }

@@ -267,7 +267,7 @@ extern "C" int giCDebugValidateSceneBvh(const GiCScene* scene, uint32_t deviceIn
   if (s->host->partitioned) {
     left.assign(triCount, 0);
     for (const InstPart& P : s->host->parts) {
-      if (!s->host->meshBuilds[P.meshBuild].hidden) continue;
+      if (!s->host->meshBuilds[P.meshBuild].hidden && !P.retired) continue; // (a retired instance of a live mesh: gi_build.cpp updateTopology)
       if ((uint64_t)P.triFirst + P.nf > triCount) { violations++; continue; }
       std::fill(left.begin() + P.triFirst, left.begin() + P.triFirst + P.nf, (uint8_t)1);
       liveIds -= P.nf;
@@ -551,6 +551,15 @@ extern "C" int giCDebugSceneTopologyUpdateCount(const GiCScene* scene, uint64_t*
   if (!s || !outCount) { setError("giCDebugSceneTopologyUpdateCount: bad arguments"); return GI_C_ERROR; }
   std::lock_guard<std::mutex> guard(s->mutex);
   *outCount = s->updateCounts[UPDATE_TOPOLOGY];
+  return GI_C_OK;
+}
+
+extern "C" int giCDebugSceneInstanceUpdateCount(const GiCScene* scene, uint64_t* out)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!s || !out) { setError("giCDebugSceneInstanceUpdateCount: bad arguments"); return GI_C_ERROR; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  for (int k = 0; k < 4; k++) out[k] = s->instanceCounts[k];
   return GI_C_OK;
 }
 

@@ -187,6 +187,8 @@ struct GiCMesh {
   uint32_t builtInstances = 0xffffffffu; // instance count the built scene holds for this mesh (0xffffffff: not part of it)
   bool visToggled = false;  // giCSetMeshVisibility was called since the last syncSceneGeometry
   bool vertsEdited = false; // giCSetMeshVertices was called since the last syncSceneGeometry
+  // giCSetMeshInstanceIds, or giCSetMeshInstanceTransforms with another count, was called on this mesh of the built scene since the last syncSceneGeometry
+  bool instEdited = false;
   // giCDestroyMesh on a mesh of the built scene with topology updates wanted: the mesh left GiCScene::meshes and is kept (GiCScene::retiredMeshes) until the
   // next buildScene, because the resident scene still holds its records (MeshBuild::m).  Invisible for good
   bool retired = false;
@@ -308,6 +310,10 @@ struct TwoLevelHost { std::vector<Node8> tlasNodes, blasNodes; std::vector<uint3
     };
 struct MeshBuild { const GiCMesh* m; uint32_t vertexOffset, matFlags, instFirst, instCount, triFirst; uint32_t meshIdx; std::vector<int32_t> faceIdAov;
     uint32_t shadeBase = 0;
+    // the InstanceRec of every live instance, inst[instInMesh]: instFirst + instInMesh (and triangles at triFirst + instInMesh * faces) as the build leaves
+    // them; an instance update (gi_build.cpp updateTopology) appends records at the end of the array and retires others, which stay resident (retiredInst)
+    std::vector<uint32_t> inst; uint32_t retiredInst = 0;
+    void numberInstances() { inst.resize(instCount); for (uint32_t ii = 0; ii < instCount; ii++) inst[ii] = instFirst + ii; }
     // incremental visibility updates (gi_build.cpp updateVisibility): the mesh is part of the resident scene but hidden; the scene-order id of its first
     // triangle as the resident records hold it (triFirst until a mesh in front of it is hidden; triFirst stays the POSITION of a partitioned scene's ranges)
     bool hidden = false; uint32_t idBase = 0; };
@@ -316,7 +322,9 @@ struct MeshBuild { const GiCMesh* m; uint32_t vertexOffset, matFlags, instFirst,
 struct InstPart { uint32_t meshBuild, instInMesh; uint32_t triFirst, nf; uint32_t nodeOff, nodeCount, nodeCap, depth; float box[6];
     // vertex updates (gi_build.cpp updateVertices): triangles the subtree holds (nf unless some were inactive when it was built), and the first node of every
     // level of the subtree relative to nodeOff, then nodeCount (Bvh8::levelStart)
-    uint32_t activeTris = 0; std::vector<uint32_t> levelStart; };
+    uint32_t activeTris = 0; std::vector<uint32_t> levelStart;
+    // its instance was retired by an instance update: the ranges stay resident and out of the top tree, like those of a hidden mesh, for good
+    bool retired = false; };
 struct SceneHost {
   std::vector<FVertex> verts; std::vector<InstanceRec> instances; std::vector<MaterialRec> mats; std::vector<MeshRec> meshRecs; std::vector<float> sceneData;
   Bvh8 bvh; std::vector<int32_t> triFaceId; std::vector<uint32_t> flatOfOrig; TwoLevelHost two;
@@ -404,6 +412,12 @@ struct GiCScene : SceneDevice {
   // GI_C_SCENE_OPTION_RESYNC_REFITS: 1 = a destroyed mesh and a created one with the same faces become a vertex edit of the resident records (updateTopology
   // adoptResyncs; read only with topology and vertex updates wanted); meshes adopted since the scene was created (giCDebugSceneResyncCount)
   int32_t optResyncRefits = 0; uint64_t resyncCount = 0;
+  // GI_C_SCENE_OPTION_INSTANCE_UPDATES: 1 = instance ids and counts of built meshes are edited in the resident scene (updateTopology; read only with
+  // topology updates wanted); giCDebugSceneInstanceUpdateCount: syncs that applied such an edit, instances appended, of those cloned, instances retired
+  int32_t optInstanceUpdates = 0; uint64_t instanceCounts[4] = {0, 0, 0, 0};
+  // DIRTY_BVH was raised by giCSetMeshInstanceIds or a count change of giCSetMeshInstanceTransforms on a mesh of the built scene (raiseInstances):
+  // syncSceneGeometry lets updateTopology answer it; without the option it turns this into rebuildDue
+  bool instancesDue = false;
   std::vector<GiCMesh*> retiredMeshes; // destroyed meshes the resident scene still refers to (GiCMesh::retired): freed by buildScene and with the scene
   ~GiCScene() { for (GiCMesh* m : retiredMeshes) delete m; }
 };
@@ -411,6 +425,8 @@ struct GiCScene : SceneDevice {
 inline void raiseRebuild(GiCScene* s) { s->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER; s->rebuildDue = true; }
 // a mesh created or destroyed, or a setter on a mesh that is not part of the built scene: the same flags
 inline void raiseTopology(GiCScene* s) { s->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER; s->topologyDue = true; }
+// instance ids or the instance count of a mesh of the built scene changed: the same flags
+inline void raiseInstances(GiCMesh* m) { m->instEdited = true; m->scene->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER; m->scene->instancesDue = true; }
 
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -426,6 +442,7 @@ uint32_t sceneDeviceCount(const GiCScene* s);                // devices a render
 SceneDevice& sceneDevice(GiCScene* s, uint32_t slot);
 bool usableVertexPositions(const GiCVertex* v, size_t count);  // every position finite and within 1e18 (bvh8.h "Inactive items")
 void nodeBounds(const Node8& n, float box[6]);               // dequantised bounds of a node's children (+ an ulp-scale pad)
+bool instanceUpdatesWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_INSTANCE_UPDATES / GATLING_OPTIONS=instance_updates (with topology updates wanted)
 bool topologyUpdatesWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_TOPOLOGY_UPDATES / GATLING_OPTIONS=topology_updates
 int syncSceneGeometry(GiCScene* s);                          // brings the device scene up to date with the host-side edits (incremental or full build)
 // dirty flags of a material-side edit: DIRTY_MATERIALS alone once the scene / the mesh is part of a built scene (the incremental path), else with DIRTY_BVH

@@ -92,6 +92,15 @@ void launchPatchVisibility(hipStream_t s, TriRec* tris, uint32_t triCount, const
 // builder numbered them by position in the part).  The caller has checked both ranges against the arrays' sizes
 void launchPlacePart(hipStream_t s, const Node8* partNodes, uint32_t partNodeCount, Node8* nodes, uint32_t nodeOff, TriRec* tris, uint32_t triFirst, uint32_t nf,
     uint32_t idAdd);
+// gi_patch.hip: new instances of resident meshes made from live sibling instances (gi_build.cpp updateTopology, GI_C_SCENE_OPTION_INSTANCE_UPDATES).  One
+// CloneEntry per new instance: the sibling's `nf` records at srcTri and `nodeCount` nodes at srcNode are copied to dstTri / dstNode -- records re-transformed by
+// instances[instance].o2w and renumbered from idBase (gi_refit.h refit_clone_record), face ids copied, nodes with child and triangle bases moved by the
+// distance between the ranges.  threadBase: first thread of the entry (ascending from 0, a multiple of 64; max(nf, nodeCount) threads each).  The caller has
+// checked every range against the arrays' sizes and uploaded the new InstanceRecs; launchRefitLevel over the copied ranges follows
+struct CloneEntry { uint32_t threadBase, srcTri, dstTri, nf, srcNode, dstNode, nodeCount, instance, idBase; };
+inline uint32_t cloneEntryThreads(uint32_t nf, uint32_t nodeCount) { return ((nf > nodeCount ? nf : nodeCount) + 63u) & ~63u; }
+void launchCloneParts(hipStream_t s, const CloneEntry* entries, uint32_t entryCount, uint32_t threads, TriRec* tris, uint32_t triCount, int32_t* triFaceId,
+    Node8* nodes, uint32_t nodeCount, const InstanceRec* instances, uint32_t instanceCount, const TriShade* triShade, uint32_t shadeCount);
 // gi_refit.hip: a vertex edit applied to the device-resident scene (gi_build.cpp updateVertices).  launchRefitTris makes the world-space corners of the records
 // of edited instances (editedOfInstance[t.instance] != 0) again from their shading records and instance transforms; launchRefitLevel refits one tree level:
 // thread i handles node ranges[r].nodeFirst + (i - ranges[r].threadBase) of the last range r with threadBase <= i, reading the float boxes (8 floats per

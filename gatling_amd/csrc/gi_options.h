@@ -56,6 +56,11 @@
 //   resync_refits        -1        -1 = the scene option decides (GI_C_SCENE_OPTION_RESYNC_REFITS), 0 / 1 = a destroyed and a created mesh with the same
 //                                  faces are retired and appended / become a vertex refit of the resident records (gi_build.cpp adoptResyncs); read
 //                                  only with topology_updates and vertex_updates wanted
+//   instance_updates     -1        -1 = the scene option decides (GI_C_SCENE_OPTION_INSTANCE_UPDATES), 0 / 1 = new instance ids or another instance count
+//                                  of a built mesh rebuild the scene / are applied to the resident scene (gi_build.cpp updateTopology); read only with
+//                                  topology_updates wanted
+//   instance_clone       0         instance updates: 1 = an appended instance is made from a resident sibling on the device (gi_patch.hip k_clone_parts);
+//                                  0 = it is built as an appended mesh's part is (cheaper to walk: DESIGN.md section 9)
 //   device_parts_min     4096      topology updates with the device builder on: an appended part of at least this many faces (and more than 128) is built
 //                                  on the device (buildBvh8Device + gi_patch.hip k_place_part), a smaller one by the host (buildPart).  The measured
 //                                  crossover for one part

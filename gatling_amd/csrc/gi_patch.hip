@@ -2,6 +2,7 @@
 //   k_patch_mat_flags   TriRec::matFlags rewritten after a material edit (gi_build.cpp updateMaterials)
 //   k_patch_visibility  scene-order ids renumbered, records of hidden instances made unhittable / restored (gi_build.cpp updateVisibility; below)
 //   k_place_part        a device-built part of an appended mesh moved into the scene's node array, its ids made scene-order (gi_build.cpp updateTopology; below)
+//   k_clone_parts       new instances of resident meshes made from live sibling instances: records and subtrees copied and rebased (gi_build.cpp updateTopology; below)
 //
 // k_patch_mat_flags.
 // A material or assignment edit changes one word per flattened triangle -- material index | shade class << 24 | cutout << 28 | facing << 30 -- and nothing
@@ -19,6 +20,7 @@
 #include <cstddef>
 
 #include "gi_kernels.h"
+#include "gi_refit.h"
 
 namespace gi {
 namespace {
@@ -94,7 +96,58 @@ __global__ __launch_bounds__(kPatchBlock) void k_place_part(const Node8* __restr
   if (i < nf) tris[triFirst + i].origId += idAdd;
 }
 
+// k_clone_parts.  A mesh of a partitioned scene gets more instances (opt-in: GI_C_SCENE_OPTION_INSTANCE_UPDATES).  Everything a new instance needs but its
+// 96-byte InstanceRec is resident (the host sends that record and a zeroing of the node range, nothing per node or per triangle): the mesh's shading records, and a live sibling instance's part -- `nf` records in the order its builder left them and a
+// subtree over exactly those positions.  One launch makes all new instances of an update from a table with one CloneEntry each; a thread finds its entry by
+// bisection over threadBase (a multiple of 64: a wave never straddles two entries) and is thread j of it.
+//   j < nf:        the sibling's record srcTri + j is read whole (4 x 16 bytes), becomes the new instance's by refit_clone_record -- instance, id = idBase +
+//                  prim, v0 / e1 / e2 from TriShade::p of the record vi[0] names and the new instance's o2w with flattenTriangle's operations in its order (the
+//                  library is built without contraction: the bytes are a fresh build's) -- and is stored whole at dstTri + j; the face id rides along.
+//   j < nodeCount: the sibling's node srcNode + j is stored at dstNode + j with childBase and triBase moved by the distance between the ranges -- k_place_part's
+//                  two additions, as deltas.  Its boxes are the sibling's until k_refit_level has run over the new range (the host launches it next).
+// Plain vector loads and stores, no atomics: every thread owns its record and its node; source and destination ranges are disjoint (the destination lies
+// behind everything resident).  Lane j of a wave touches record j and node j of consecutive 64-byte and 80-byte records: a wave reads and writes 4 KiB of
+// records and 5 KiB of nodes as whole lines.  Memory-bound and small: per record 64 bytes read + 64 written, the 36 bytes of TriShade::p (one line of a
+// 160-byte record, shared with no neighbour) and 4 + 4 bytes of face id; per node 80 bytes read + 80 written.  o2w is read by every lane and stays in the caches.
+__global__ __launch_bounds__(kPatchBlock) void k_clone_parts(const CloneEntry* __restrict__ entries, uint32_t entryCount, uint32_t threads, TriRec* __restrict__ tris,
+    uint32_t triCount, int32_t* __restrict__ triFaceId, Node8* __restrict__ nodes, uint32_t nodeCount, const InstanceRec* __restrict__ instances,
+    uint32_t instanceCount, const TriShade* __restrict__ triShade, uint32_t shadeCount)
+{
+  const uint32_t i = blockIdx.x * kPatchBlock + threadIdx.x;
+  if (i >= threads || entryCount == 0u) return;
+  uint32_t lo = 0, hi = entryCount; // the last entry whose threadBase <= i (entries[0].threadBase == 0)
+  while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (entries[mid].threadBase <= i) lo = mid; else hi = mid; }
+  const CloneEntry c = entries[lo];
+  const uint32_t j = i - c.threadBase;
+  if (j < c.nf && c.srcTri + j < triCount && c.dstTri + j < triCount && c.instance < instanceCount) { // (the ranges cannot lie outside: the host checks them)
+    static_assert(sizeof(TriRec) == 64 && alignof(uint4) == 16, "a TriRec is four 16-byte pieces");
+    union { TriRec t; uint4 q[4]; } in, out;
+    const uint4* src = reinterpret_cast<const uint4*>(tris + c.srcTri + j);
+    for (int k = 0; k < 4; k++) in.q[k] = src[k];
+    const uint32_t rec = in.t.vi[0];
+    if (rec < shadeCount) { // (cannot fail: scenes beyond LDS name their shading record there)
+      out.t = refit_clone_record(in.t, instances[c.instance].o2w, triShade[rec].p, c.instance, c.idBase);
+      uint4* dst = reinterpret_cast<uint4*>(tris + c.dstTri + j);
+      for (int k = 0; k < 4; k++) dst[k] = out.q[k];
+      triFaceId[c.dstTri + j] = triFaceId[c.srcTri + j];
+    }
+  }
+  if (j < c.nodeCount && c.srcNode + j < nodeCount && c.dstNode + j < nodeCount) {
+    Node8 n = nodes[c.srcNode + j];
+    n.childBase += c.dstNode - c.srcNode; n.triBase += c.dstTri - c.srcTri;
+    nodes[c.dstNode + j] = n;
+  }
+}
+
 } // namespace
+
+void launchCloneParts(hipStream_t s, const CloneEntry* entries, uint32_t entryCount, uint32_t threads, TriRec* tris, uint32_t triCount, int32_t* triFaceId,
+    Node8* nodes, uint32_t nodeCount, const InstanceRec* instances, uint32_t instanceCount, const TriShade* triShade, uint32_t shadeCount)
+{
+  if (threads == 0u || entryCount == 0u) return;
+  hipLaunchKernelGGL(k_clone_parts, dim3((threads + kPatchBlock - 1u) / kPatchBlock), dim3(kPatchBlock), 0, s, entries, entryCount, threads, tris, triCount,
+      triFaceId, nodes, nodeCount, instances, instanceCount, triShade, shadeCount);
+}
 
 void launchPlacePart(hipStream_t s, const Node8* partNodes, uint32_t partNodeCount, Node8* nodes, uint32_t nodeOff, TriRec* tris, uint32_t triFirst, uint32_t nf,
     uint32_t idAdd)

@@ -42,6 +42,19 @@ GI_REFIT_HD inline void refit_flatten(const float* o2w, const float p[3][3], flo
   for (int a = 0; a < 3; a++) { v0[a] = q[0][a]; e1[a] = q[1][a] - q[0][a]; e2[a] = q[2][a] - q[0][a]; }
 }
 
+// An instance update (gi_build.cpp updateTopology, gi_patch.hip k_clone_parts) makes a new instance of a resident mesh from a live sibling instance: the
+// record `src` of the sibling becomes the record of instance `instance` (transform o2w) at the same position of its own range.  prim, matFlags and vi are
+// the mesh's and stay; the id is the new instance's base + prim (flattenInstance numbers an instance's triangles in face order); v0 / e1 / e2 are made from
+// the mesh triangle's object-space corners p (TriShade::p of the record vi[0] names) by flattenTriangle's operations in its order, so the 64 bytes are a fresh
+// build's.  The caller has established that the new instance is usable (no inactive marker to carry).
+GI_REFIT_HD inline TriRec refit_clone_record(const TriRec& src, const float* o2w, const float p[3][3], uint32_t instance, uint32_t idBase)
+{
+  TriRec t = src;
+  t.instance = instance; t.origId = idBase + src.prim;
+  refit_flatten(o2w, p, t.v0, t.e1, t.e2);
+  return t;
+}
+
 // bvh8.cpp prepareRange: the padded box of the triangle {v0, v0 + e1, v0 + e2}; false (and no box) for an inactive one
 GI_REFIT_HD inline bool refit_tri_box(const float v0[3], const float e1[3], const float e2[3], float lo[3], float hi[3])
 {

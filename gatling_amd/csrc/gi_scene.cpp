@@ -111,7 +111,7 @@ void giCSetMeshInstanceTransforms(GiCMesh* mesh, uint32_t count, const float* tr
     mesh->xformDirty = true; mesh->scene->dirty |= DIRTY_XFORM | DIRTY_FRAMEBUFFER;
   }
   else if (mesh->builtInstances == 0xffffffffu) raiseTopology(mesh->scene);
-  else raiseRebuild(mesh->scene); // (another instance count of a mesh of the built scene)
+  else raiseInstances(mesh); // (another instance count of a mesh of the built scene: which of the kept instances moved is found against the resident records)
   } catch (const std::exception& e) { setError(std::string("giCSetMeshInstanceTransforms: ") + e.what()); }
 }
 
@@ -122,7 +122,7 @@ void giCSetMeshInstanceIds(GiCMesh* mesh, uint32_t count, const int32_t* ids)
   std::vector<int32_t> copy(ids, ids + count);
   std::lock_guard<std::mutex> g(mesh->scene->mutex);
   mesh->instanceIds.swap(copy);
-  if (mesh->builtInstances == 0xffffffffu) raiseTopology(mesh->scene); else raiseRebuild(mesh->scene);
+  if (mesh->builtInstances == 0xffffffffu) raiseTopology(mesh->scene); else raiseInstances(mesh);
   } catch (const std::exception& e) { setError(std::string("giCSetMeshInstanceIds: ") + e.what()); }
 }
 

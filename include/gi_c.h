@@ -379,7 +379,8 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * The same holds for GI_C_SCENE_OPTION_VISIBILITY_UPDATES, giCDebugSceneVisibilityUpdateCount, giCDebugSceneClassState, giCDebugMissRect and giCDebugPathWalkStats, and for
  * giCSetMeshVertices, GI_C_SCENE_OPTION_VERTEX_UPDATES, giCDebugSceneVertexUpdateCount, giCDebugRefitBvh and giCDebugSceneRefitCheck, and for
  * GI_C_SCENE_OPTION_TOPOLOGY_UPDATES and giCDebugSceneTopologyUpdateCount, and for GI_C_SCENE_OPTION_RESYNC_REFITS, giCDebugSceneResyncCount,
- * giCDebugGatherShade and giCDebugSceneShadeCheck, and for giCDebugPathLobeStats and giCDebugPathLot. */
+ * giCDebugGatherShade and giCDebugSceneShadeCheck, and for giCDebugPathLobeStats and giCDebugPathLot, and for GI_C_SCENE_OPTION_INSTANCE_UPDATES,
+ * giCDebugSceneInstanceUpdateCount and giCDebugCloneInstance. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -580,6 +581,18 @@ int giCGetRenderStats(const GiCScene* scene, GiCRenderStats* out);
  * fresh build gives them.  Resident triangle and node counts do not grow with such edits, so the rebuild that compacts retired triangles does not come due.
  * The image does not depend on the option.  GATLING_OPTIONS=resync_refits=0|1 overrides it (hdGatling sets no scene options).  DESIGN.md section 6. */
 #define GI_C_SCENE_OPTION_RESYNC_REFITS 14
+/* [ext] Incremental instancer edits: value 1 = when GI_C_SCENE_OPTION_TOPOLOGY_UPDATES is wanted (the option is read only then), giCSetMeshInstanceIds and a
+ * giCSetMeshInstanceTransforms with another instance count on a mesh of the built scene -- what hdGatling sends for every DirtyInstancer / DirtyInstanceIndex
+ * sync of a prim -- are applied to the resident scene by the topology update instead of rebuilding it; 0 = off (default): they rebuild.  New ids alone re-send
+ * the mesh's instance records (equal ids send nothing).  A smaller count retires the instances behind the new count: their subtrees leave the top tree, their
+ * records stay resident until the next build and count as retired triangles.  A larger count appends one instance record, one triangle range and one subtree
+ * per new instance, built as the parts of a new mesh are; with GATLING_OPTIONS=instance_clone=1, where a live sibling instance of the mesh is resident with
+ * a whole subtree, the new one is made from it in device memory instead (records and nodes copied, re-transformed and refitted: a cheaper edit, a tree that
+ * costs more to walk).
+ * The triangles behind get the ids a fresh build gives them; kept instances whose transform changed go through the transform update.  The image does not
+ * depend on the option.  The scene is rebuilt instead for everything GI_C_SCENE_OPTION_TOPOLOGY_UPDATES rebuilds for, for a new count of 0 and for a mesh
+ * hidden by the visibility path.  GATLING_OPTIONS=instance_updates=0|1 overrides it (hdGatling sets no scene options).  DESIGN.md section 6. */
+#define GI_C_SCENE_OPTION_INSTANCE_UPDATES 15
 int giCGetLookaheadStats(const GiCScene* scene, GiCLookaheadStats* out);
 int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value);
 /* [ext] closest hit of one ray through the device traversal kernel (parity tests of the BVH8 path).
@@ -654,6 +667,16 @@ int giCDebugSceneResyncCount(const GiCScene* scene, uint64_t* outCount);
  * device kernel k_gather_shade runs) are the records the scene build packs: both made for the mesh (`vertices`, `faces`: 3 indices per face), compared
  * bytewise.  Returns the number of records whose 160 bytes differ (0 is the contract), <0 on error (a null array, an index outside the vertices). */
 int giCDebugGatherShade(const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount);
+/* [ext] [debug] what GI_C_SCENE_OPTION_INSTANCE_UPDATES did since the scene was created: out[0] scene syncs that applied an instancer edit in place, [1] instances
+ * appended, [2] of those, made from a resident sibling instance on the device (gi_patch.hip k_clone_parts), [3] instances retired.  Such a sync is counted as
+ * one topology update. */
+int giCDebugSceneInstanceUpdateCount(const GiCScene* scene, uint64_t* out /* 4 */);
+/* [ext] [debug] host-only check of the per-record arithmetic that makes a new instance from a resident sibling (gi_refit.h refit_clone_record, what k_clone_parts
+ * runs): the mesh is flattened under the instance transform `xformA` (16 floats, USD row vectors) with the scene build's code, every record is cloned to the
+ * instance transform `xformB` under another instance index and id base, and the result is compared bytewise with the scene build's records for `xformB`.
+ * Returns the number of records whose 64 bytes differ (0 is the contract), <0 on error (a null array, an index outside the vertices, an unusable transform). */
+int giCDebugCloneInstance(const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, int32_t isLeftHanded, const float* xformA,
+                          const float* xformB);
 /* [ext] [debug] the vertex and shading records resident on device `deviceIndex` of a scene rendered at least once, downloaded and compared with the host's copies
  * over the WHOLE arrays (a store outside an edited range is seen).  Returns the number of shading records whose 160 bytes differ plus the vertex records
  * whose 48 bytes differ (0), <0 on error; outRecords: shading records compared (0 for a scene within LDS, which keeps none). */
