@@ -20,9 +20,9 @@ HEADERS = ["gi_host.h", "gi_types.h", "gi_kernels.h", "gi_device_math.h", "gi_qu
 # -ffp-contract=off: arithmetic contract.  No fast-math: IEEE divide/sqrt are part of it.
 INCLUDE = os.path.join(_HERE, "..", "include")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-I", INCLUDE]
-# Kernel translation units: no SLP vectorisation.  The vectoriser packs pairs of independent fp32 operations into v_pk_mul / v_pk_add / v_pk_fma, which on
-# gfx950 issue at the rate of the scalar forms (tools/valu_calib.hip) but need their operands in aligned register pairs -- the packing costs v_mov's (k_trace_dyn:
-# 238 -> 161 static moves) and registers.  Measured (r03c): C2 7 034 -> 7 506 Msamples/s at spp 128, C3 / C4 unchanged.  Results are
+# Kernel translation units: no SLP vectorisation.  The vectoriser packs pairs of independent fp32 operations into v_pk_mul / v_pk_add / v_pk_fma.  On gfx950
+# v_pk_fma issues at the rate of the scalar form, v_pk_mul / v_pk_add at half of it (tools/valu_calib.hip; profiles/r16_valu_issue_calibration.txt), and all of
+# them need their operands in aligned register pairs -- the packing costs v_mov's (k_trace_dyn: 238 -> 161 static moves) and registers.  Measured (r03c): C2 7 034 -> 7 506 Msamples/s at spp 128, C3 / C4 unchanged.  Results are
 # bit-identical (packed and scalar fp32 operations round the same way); the hand-written packed fma of the box test stays.
 KERNEL_FLAGS = ["-fno-slp-vectorize"]
 

@@ -160,6 +160,7 @@ SYMBOLS = [
     ("giCDebugEvalBsdf", C.c_int, [C.POINTER(GiCMaterialDesc), _U, _FP, _FP]),
     ("giCDebugShadeClass", C.c_int, [C.POINTER(GiCMaterialDesc)]),
     ("giCDebugCheckSqrt", C.c_int64, [C.c_uint32, C.c_uint64]),
+    ("giCDebugCheckDiv", C.c_int64, [C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("giCDebugValidateBvh", C.c_int, [_FP, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("giCDebugValidatePartitionedBvh", C.c_int, [_FP, _U, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("giCDebugValidateSceneBvh", C.c_int, [_P, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]),

@@ -456,6 +456,28 @@ extern "C" int64_t giCDebugCheckSqrt(uint32_t first, uint64_t count)
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// giCDebugCheckDiv: the fused kernels' division (gi_device_math.h gi_div, V3 / float, normalize) against the compiler's correctly rounded `/` (gi_path.hip
+// k_debug_div has the modes).  Returns the number of items with a differing result, or -1 on error.
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" int64_t giCDebugCheckDiv(uint32_t mode, uint64_t count, uint32_t seed, const uint32_t* words)
+{
+  if (!g_ctx.initialized) { setError("giCDebugCheckDiv before giCInitialize"); return -1; }
+  const bool given = mode == 0u || mode == 2u;
+  if (mode > 4u || (given && (!words || count > (1ull << 28)))) { setError("giCDebugCheckDiv: bad arguments"); return -1; }
+  const size_t bytes = given ? (size_t)count * (mode == 0u ? 2u : 4u) * sizeof(uint32_t) : 0u;
+  unsigned long long* d = nullptr; unsigned long long h = 0ull; uint32_t* dw = nullptr;
+  if (hipMalloc(&d, sizeof(h)) != hipSuccess) { setError("giCDebugCheckDiv: hipMalloc failed"); return -1; }
+  bool ok = bytes == 0u || hipMalloc(&dw, bytes) == hipSuccess;
+  ok = ok && (bytes == 0u || hipMemcpyAsync(dw, words, bytes, hipMemcpyHostToDevice, g_ctx.stream) == hipSuccess);
+  ok = ok && hipMemsetAsync(d, 0, sizeof(h), g_ctx.stream) == hipSuccess;
+  if (ok) { launchDebugDiv(g_ctx.stream, mode, (unsigned long long)count, seed, dw, d); ok = hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, g_ctx.stream) == hipSuccess; }
+  ok = ok && hipStreamSynchronize(g_ctx.stream) == hipSuccess;
+  (void)hipFree(d); if (dw) (void)hipFree(dw);
+  if (!ok) { setError("giCDebugCheckDiv: device error"); return -1; }
+  return (int64_t)h;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // giCDebugEditDirtyFlags / giCDebugSceneUpdateCounts: which edits take the incremental paths (host only)
 // ---------------------------------------------------------------------------------------------------------------
 // A scratch scene of one texture, two materials and one one-triangle mesh is made through the C ABI's own entry points; with `built` it is marked the way a

@@ -15,6 +15,24 @@
 namespace gi {
 
 struct V3 { float x, y, z; };
+
+// Two forms of the arithmetic, same bits: the compiler's own square root and division ("ieee"), and the lean forms below ("lean": fewer instructions for ordinary
+// operands, everything else handed to the compiler's).  A translation unit asks for the lean forms by defining GI_LEAN_MATH before its first include of this
+// header: the fused kernels do (gi_path.hip), the stage kernels do not (see gi_sqrt / gi_div for the measurements).  Every device function of this header and
+// of gi_texture.h / gi_traversal.h / gi_shading.h / gi_stages.h lives in the inline namespace of its form -- gi::lean::normalize and gi::ieee::normalize are two
+// functions with two names, not two bodies of one inline function -- and code inside namespace gi names them without the qualifier.
+#if defined(GI_LEAN_MATH)
+#define GI_MATH_FORM lean
+#define GI_MATH_FORM_IS_LEAN true
+#else
+#define GI_MATH_FORM ieee
+#define GI_MATH_FORM_IS_LEAN false
+#endif
+#define GI_MATH_BEGIN inline namespace GI_MATH_FORM {
+#define GI_MATH_END }
+
+GI_MATH_BEGIN
+constexpr bool GI_MATH_IS_LEAN = GI_MATH_FORM_IS_LEAN;
 __device__ __forceinline__ V3 v3(float x, float y, float z) { return V3{x, y, z}; }
 __device__ __forceinline__ V3 v3(const float* p) { return V3{p[0], p[1], p[2]}; }
 __device__ __forceinline__ V3 operator+(V3 a, V3 b) { return V3{a.x + b.x, a.y + b.y, a.z + b.z}; }
@@ -22,7 +40,6 @@ __device__ __forceinline__ V3 operator-(V3 a, V3 b) { return V3{a.x - b.x, a.y -
 __device__ __forceinline__ V3 operator-(V3 a) { return V3{-a.x, -a.y, -a.z}; }
 __device__ __forceinline__ V3 operator*(V3 a, V3 b) { return V3{a.x * b.x, a.y * b.y, a.z * b.z}; }
 __device__ __forceinline__ V3 operator*(V3 a, float s) { return V3{a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ V3 operator/(V3 a, float s) { return V3{a.x / s, a.y / s, a.z / s}; }
 __device__ __forceinline__ float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 __device__ __forceinline__ V3 cross(V3 a, V3 b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 // Square root, correctly rounded like sqrtf (the oracle's), in fewer instructions for ordinary arguments.  The compiler expands sqrtf into 16 VALU instructions: scale
@@ -32,24 +49,97 @@ __device__ __forceinline__ V3 cross(V3 a, V3 b) { return V3{a.y * b.z - a.z * b.
 // Measured on one box, libraries alternating (profiles/r06zp_lean_sqrt_variants.txt): `k_path` 201.1 / 201.3 -> 199.8 / 199.6 ms per C2 launch at spp 1024 (it is
 // bound by its VALU issue rate and held 12 roots in 2 407 instructions); the shade stage C3 9.3 -> 9.15 ms but C5 26.9 -> 27.75 and C4 3.3 -> 3.5 (the second copy of
 // every root and its branch cost the UsdPreviewSurface kernel more than the five instructions save): the lean form is compiled into the fused kernels only.
+__device__ __forceinline__ float gi_sqrt_lean(float x) // x in [2^-95, +inf)
+{
+  float s = __builtin_amdgcn_sqrtf(x);
+  const float lo = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, s) - 1u), hi = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, s) + 1u);
+  const float rlo = __builtin_fmaf(-lo, s, x), rhi = __builtin_fmaf(-hi, s, x);
+  s = (rlo <= 0.0f) ? lo : s;
+  s = (rhi > 0.0f) ? hi : s;
+  return s;
+}
 __device__ __forceinline__ float gi_sqrt(float x)
 {
-#if !defined(GI_LEAN_SQRT)   // a translation unit asks for the lean form before it includes this header: the fused kernels do (gi_path.hip), the stage kernels do not
+  if (GI_MATH_IS_LEAN && __builtin_expect((__builtin_bit_cast(uint32_t, x) - 0x10000000u) < (0x7f800000u - 0x10000000u), 1)) return gi_sqrt_lean(x);
   return sqrtf(x);
-#else
-  if (__builtin_expect((__builtin_bit_cast(uint32_t, x) - 0x10000000u) < (0x7f800000u - 0x10000000u), 1)) {
-    float s = __builtin_amdgcn_sqrtf(x);
-    const float lo = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, s) - 1u), hi = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, s) + 1u);
-    const float rlo = __builtin_fmaf(-lo, s, x), rhi = __builtin_fmaf(-hi, s, x);
-    s = (rlo <= 0.0f) ? lo : s;
-    s = (rhi > 0.0f) ? hi : s;
-    return s;
+}
+// Division, correctly rounded like `/` (the oracle's), in fewer instructions for ordinary operands.  The compiler expands n / d into 11 VALU instructions:
+//     ds = v_div_scale(d, d, n); ns = v_div_scale(n, d, n) -> vcc; r = v_rcp(ds); e = fma(-ds, r, 1); r = fma(e, r, r); q = ns * r; e = fma(-ds, q, ns);
+//     q = fma(e, r, q); e = fma(-ds, q, ns); q = v_div_fmas(e, r, q); q = v_div_fixup(q, d, n)
+// By the gfx950 ISA's definitions, V_DIV_SCALE_F32 returns its first operand unchanged and clears vcc unless n or d is zero, d is a denormal, the exponents of n
+// and d differ by 96 or more, 1 / d or n / d is a denormal, or n's biased exponent is at most 23; V_DIV_FMAS_F32 with vcc clear is fma; V_DIV_FIXUP_F32 replaces
+// the quotient only for a NaN, infinite or zero operand, an exponent difference below -150 or a denominator exponent of 255, and otherwise gives it the sign of
+// n xor d, which a non-zero quotient of these operations already has.  With both biased exponents in [96, 160) -- 2^-31 <= |x| < 2^33, finite, normal, non-zero,
+// exponents at most 63 apart, 1 / d and n / d no smaller than 2^-65 -- none of those cases applies, and what is left, taken here literally, is the reciprocal,
+// its Newton step and five operations per quotient.  Any other operand pair (zeros -- 0 / d included: the residuals lose the sign of a -0 --, denormals,
+// infinities, NaN, far exponents) goes to `/`, for the whole wave: the test is one comparison of the wave's ballot, and ordinary operands never leave the lean
+// path.  Same bits by construction; tests/test_gpu_lean_division.py runs the exponent grid, random bit patterns and the specials through both.
+// A constant operand folds its half of the test away.  Measured on one box, four libraries round-robin (profiles/r16_packed_fp32.txt), ms per C2 step at spp 1024:
+// 161.8 with `/`; 161.0 with gi_div alone; 158.7 with normalize's 1 / sqrt under one test (gi_rsqrt); 158.0 with gi_rcp's shorter sequence.  The stage kernels keep
+// `/`, as they keep sqrtf: a second copy of every quotient behind a branch is what cost them the lean root's gain.
+__device__ __forceinline__ uint32_t gi_div_range(float x) { return (__builtin_bit_cast(uint32_t, x) << 1) - (96u << 24); } // below 64 << 24: biased exponent in [96, 160)
+__device__ __forceinline__ float gi_div_recip(float d) // r of the sequence above, shared by every quotient with this denominator
+{
+  const float r = __builtin_amdgcn_rcpf(d);
+  return __builtin_fmaf(__builtin_fmaf(-d, r, 1.0f), r, r);
+}
+__device__ __forceinline__ float gi_div_quotient(float n, float d, float r)
+{
+  float q = n * r;
+  q = __builtin_fmaf(__builtin_fmaf(-d, q, n), r, q);
+  return __builtin_fmaf(__builtin_fmaf(-d, q, n), r, q);
+}
+// WAVE: the whole wave takes one path (what the kernels use); !WAVE: each lane its own (tests reach the lean path of a pair whatever its neighbours hold)
+template <bool WAVE = true>
+__device__ __forceinline__ bool gi_div_is_lean(uint32_t ranges) // `|` of gi_div_range of every operand: 64 << 24 is 2^30, so in-range values stay below it together
+{
+  const bool ok = ranges < (64u << 24);
+  return GI_MATH_IS_LEAN && __builtin_expect(WAVE ? __builtin_amdgcn_ballot_w64(!ok) == 0ull : ok, 1);
+}
+template <bool WAVE = true>
+__device__ __forceinline__ float gi_div(float n, float d)
+{
+  if (gi_div_is_lean<WAVE>(gi_div_range(n) | gi_div_range(d))) return gi_div_quotient(n, d, gi_div_recip(d));
+  return n / d;
+}
+// three quotients by one denominator: its reciprocal and Newton step are computed once
+template <bool WAVE = true>
+__device__ __forceinline__ V3 gi_div3(V3 a, float s)
+{
+  if (gi_div_is_lean<WAVE>(gi_div_range(a.x) | gi_div_range(a.y) | gi_div_range(a.z) | gi_div_range(s))) {
+    const float r = gi_div_recip(s);
+    return V3{gi_div_quotient(a.x, s, r), gi_div_quotient(a.y, s, r), gi_div_quotient(a.z, s, r)};
   }
-  return sqrtf(x);
-#endif
+  return V3{a.x / s, a.y / s, a.z / s};
+}
+__device__ __forceinline__ V3 operator/(V3 a, float s) { return gi_div3(a, s); }
+// 1 / d.  With n = 1 the sequence above is r = v_rcp(d); r = fma(fma(-d, r, 1), r, r); q = r; q = fma(fma(-d, q, 1), r, q); q = fma(fma(-d, q, 1), r, q) -- and its last
+// correction never changes q: after the first one q is the correctly rounded reciprocal already.  That is not true by construction; it is true of v_rcp_f32 for
+// every d of the range, which is few enough to try them all (tests/test_gpu_lean_division.py runs all 2^32 bit patterns, as for the square root).  Five
+// instructions after the range test instead of eleven.
+__device__ __forceinline__ float gi_rcp_lean(float d)
+{
+  float r = __builtin_amdgcn_rcpf(d);
+  r = __builtin_fmaf(__builtin_fmaf(-d, r, 1.0f), r, r);
+  return __builtin_fmaf(__builtin_fmaf(-d, r, 1.0f), r, r);
+}
+template <bool WAVE = true>
+__device__ __forceinline__ float gi_rcp(float d)
+{
+  if (gi_div_is_lean<WAVE>(gi_div_range(d))) return gi_rcp_lean(d);
+  return 1.0f / d;
 }
 __device__ __forceinline__ float length(V3 a) { return gi_sqrt(dot(a, a)); }
-__device__ __forceinline__ V3 normalize(V3 a) { float inv = 1.0f / gi_sqrt(dot(a, a)); return a * inv; }
+// 1 / sqrt(d) under ONE range test: d in [2^-62, 2^66) -- biased exponent in [65, 193) -- is an argument of the lean square root, and its root, in [2^-31, 2^33), a
+// denominator of the lean reciprocal.  (One test instead of two is most of what the lean division gains the fused kernel: profiles/r16_packed_fp32.txt.)
+template <bool WAVE = true>
+__device__ __forceinline__ float gi_rsqrt(float d)
+{
+  const bool ok = (__builtin_bit_cast(uint32_t, d) - (65u << 23)) < (128u << 23); // (the sign bit stays in: a negative d fails the test)
+  if (GI_MATH_IS_LEAN && __builtin_expect(WAVE ? __builtin_amdgcn_ballot_w64(!ok) == 0ull : ok, 1)) return gi_rcp_lean(gi_sqrt_lean(d));
+  return 1.0f / gi_sqrt(d);
+}
+template <bool WAVE = true> __device__ __forceinline__ V3 normalize(V3 a) { float inv = gi_rsqrt<WAVE>(dot(a, a)); return a * inv; }
 __device__ __forceinline__ float fmax2(float a, float b) { return a > b ? a : b; }
 __device__ __forceinline__ float fmin2(float a, float b) { return a < b ? a : b; }
 __device__ __forceinline__ uint32_t f2u(float f) { return __float_as_uint(f); }
@@ -182,7 +272,7 @@ __device__ __forceinline__ float gi_next1f(uint32_t& state)
 __device__ __forceinline__ void gi_orthonormal_basis(V3 n, V3& b1, V3& b2)
 {
   float nsign = (n.z >= 0.0f) ? 1.0f : -1.0f;
-  float a = -1.0f / (nsign + n.z);
+  float a = gi_div(-1.0f, nsign + n.z);
   float b = n.x * n.y * a;
   b1 = v3(1.0f + nsign * n.x * n.x * a, nsign * b, -nsign * n.x);
   b2 = v3(b, nsign + n.y * n.y * a, -n.y);
@@ -278,4 +368,5 @@ __device__ __forceinline__ void gi_fis_gauss(float x0, float x1, float& ox, floa
   ox = c * r; oy = s * r;
 }
 
+GI_MATH_END
 } // namespace gi

@@ -118,6 +118,7 @@ void launchRefitLevel(hipStream_t s, Node8* nodes, uint32_t nodeCount, float* bo
 void launchSpin(hipStream_t s, unsigned long long ns);             // test hook: occupies a stream for ~ns nanoseconds
 void launchDebugBsdf(hipStream_t s, const MaterialRec* mat, uint32_t shadeClass, uint32_t count, const float* in, float* out);
 void launchDebugSqrt(hipStream_t s, uint32_t first, unsigned long long count, unsigned long long* mismatches); // gi_sqrt against sqrtf over bit patterns
+void launchDebugDiv(hipStream_t s, uint32_t mode, unsigned long long count, uint32_t seed, const uint32_t* words, unsigned long long* mismatches); // gi_div against `/`
 void launchDebugTex(hipStream_t s, const float* texels, uint32_t w, uint32_t h, uint32_t d, uint32_t count, const float* queries, float* out);
 
 } // namespace gi

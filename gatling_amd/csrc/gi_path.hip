@@ -34,7 +34,7 @@
 #include <hip/hip_runtime.h>
 #include <cassert>
 
-#define GI_LEAN_SQRT 1 // gi_device_math.h gi_sqrt: the correctly rounded square root without the steps ordinary arguments do not need
+#define GI_LEAN_MATH 1 // gi_device_math.h gi_sqrt / gi_div: the correctly rounded square root and division without the steps ordinary operands do not need
 #include "gi_device_math.h"
 #include "gi_kernels.h"
 #include "gi_types.h"
@@ -461,6 +461,57 @@ __global__ void k_debug_sqrt(uint32_t first, unsigned long long count, unsigned 
 void launchDebugSqrt(hipStream_t s, uint32_t first, unsigned long long count, unsigned long long* mismatches)
 {
   hipLaunchKernelGGL(k_debug_sqrt, dim3(4096), dim3(256), 0, s, first, count, mismatches);
+}
+
+// k_debug_div: the lean division (gi_device_math.h gi_div, the three-quotient V3 / float and normalize) against the compiler's `/`; counts the items for which any
+// result differs in a bit (NaN against NaN is equal whatever the payload).  Both forms of the range test run: the wave's (what the kernels execute -- one
+// out-of-range lane sends all 64 to `/`) and the lane's (so an in-range item is held to the lean sequence whatever its neighbours are).
+// Items: mode 0 -- `count` pairs (n, d) of `words`; mode 1 -- pairs drawn from a hash of (seed, index), every bit pattern equally likely; mode 2 -- `count` vectors
+// (x, y, z, s) of `words`: normalize(x, y, z) and (x, y, z) / s; mode 3 -- vectors from the hash: each component's exponent is uniform over all 256 in one item of
+// four and within +-24 of 1.0 in the others, and of the latter every eighth component is a zero or a denormal; mode 4 -- the reciprocal (gi_rcp) and the
+// reciprocal square root (gi_rsqrt) of the `count` bit patterns from `seed` on.  Modes 0 and 1 also hold gi_rcp of the denominator to 1 / d.
+__device__ __forceinline__ bool debug_same(float a, float b) { return f2u(a) == f2u(b) || (a != a && b != b); }
+__device__ __forceinline__ bool debug_same(V3 a, V3 b) { return debug_same(a.x, b.x) && debug_same(a.y, b.y) && debug_same(a.z, b.z); }
+__global__ void k_debug_div(uint32_t mode, unsigned long long count, uint32_t seed, const uint32_t* __restrict__ words, unsigned long long* mismatches)
+{
+  unsigned long long bad = 0ull;
+  for (unsigned long long i = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; i < count; i += (unsigned long long)gridDim.x * blockDim.x) {
+    uint32_t w[4];
+    if (mode == 4u) { w[0] = w[1] = w[2] = w[3] = 0u; }
+    else if (mode == 0u) { w[0] = words[2ull * i]; w[1] = words[2ull * i + 1ull]; w[2] = w[3] = 0u; }
+    else if (mode == 2u) { for (int k = 0; k < 4; k++) w[k] = words[4ull * i + k]; }
+    else {
+      for (uint32_t k = 0; k < 4u; k++) w[k] = gi_hash_init(gi_hash_init(seed + k) ^ (uint32_t)i) + gi_hash_init((uint32_t)(i >> 32) + 0x9e3779b9u * (k + 1u));
+      if (mode == 3u && (w[3] & 3u)) {
+        const uint32_t sel = gi_hash_init(w[0] ^ w[3]);
+        for (uint32_t k = 0; k < 4u; k++) {
+          const uint32_t e = 103u + ((w[k] >> 23) & 0xffu) % 49u;
+          w[k] = (w[k] & 0x807fffffu) | (e << 23);
+          const uint32_t c = (sel >> (8u * k)) & 0xffu;
+          if ((c & 7u) == 0u) w[k] &= (c & 8u) ? 0x80000000u : 0x807fffffu;
+        }
+      }
+    }
+    bool same;
+    if (mode == 4u) { // the reciprocal of the bit pattern seed + index (count = 2^32: every float)
+      const float d = u2f(seed + (uint32_t)i), q = 1.0f / d, rs = 1.0f / sqrtf(d);
+      same = debug_same(gi_rcp<true>(d), q) && debug_same(gi_rcp<false>(d), q) && debug_same(gi_rsqrt<true>(d), rs) && debug_same(gi_rsqrt<false>(d), rs);
+    } else if (mode < 2u) {
+      const float n = u2f(w[0]), d = u2f(w[1]), q = n / d, rq = 1.0f / d;
+      same = debug_same(gi_div<true>(n, d), q) && debug_same(gi_div<false>(n, d), q) && debug_same(gi_rcp<true>(d), rq) && debug_same(gi_rcp<false>(d), rq);
+    } else {
+      const V3 a = v3(u2f(w[0]), u2f(w[1]), u2f(w[2])); const float s = u2f(w[3]);
+      const V3 nrm = a * (1.0f / sqrtf(dot(a, a))), quo = V3{a.x / s, a.y / s, a.z / s};
+      same = debug_same(normalize<true>(a), nrm) && debug_same(normalize<false>(a), nrm) && debug_same(gi_div3<true>(a, s), quo) && debug_same(gi_div3<false>(a, s), quo);
+    }
+    if (!same) bad++;
+  }
+  if (bad) atomicAdd(mismatches, bad);
+}
+
+void launchDebugDiv(hipStream_t s, uint32_t mode, unsigned long long count, uint32_t seed, const uint32_t* words, unsigned long long* mismatches)
+{
+  hipLaunchKernelGGL(k_debug_div, dim3(4096), dim3(256), 0, s, mode, count, seed, words, mismatches);
 }
 
 } // namespace gi

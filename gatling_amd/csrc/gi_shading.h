@@ -7,6 +7,7 @@
 #include "gi_texture.h"
 
 namespace gi {
+GI_MATH_BEGIN // gi_device_math.h: the functions here inherit the form of the arithmetic they call
 
 // shadeRayPayloadGetMediumIdx / shadeRayPayloadIncrementWalk (rp_main_payload.glsl:60-90), literally (see the oracle's notes:
 // the increment lands in bit 0 of the bounce counter, the walk length never grows)
@@ -277,7 +278,7 @@ __device__ inline GgxOut ggx_sample(V3 l1, float alpha, float x0, float x1)
   GgxOut o; o.valid = false; o.pdf = 0.0f; o.g2OverG1 = 0.0f; o.kh = 0.0f; o.l2 = v3(0.0f, 0.0f, 0.0f);
   V3 vh = normalize(v3(alpha * l1.x, alpha * l1.y, l1.z));
   float lensq = vh.x * vh.x + vh.y * vh.y;
-  V3 T1 = lensq > 0.0f ? v3(-vh.y, vh.x, 0.0f) * (1.0f / gi_sqrt(lensq)) : v3(1.0f, 0.0f, 0.0f);
+  V3 T1 = lensq > 0.0f ? v3(-vh.y, vh.x, 0.0f) * gi_rsqrt(lensq) : v3(1.0f, 0.0f, 0.0f);
   V3 T2 = cross(vh, T1);
   float r = gi_sqrt(x0);
   float s, c; gi_sincos2pi(x1, &s, &c);
@@ -292,11 +293,11 @@ __device__ inline GgxOut ggx_sample(V3 l1, float alpha, float x0, float x1)
   float a2 = alpha * alpha;
   float nk1 = l1.z, nk2 = l2.z, nh2 = h.z * h.z;
   float dd = nh2 * (a2 - 1.0f) + 1.0f;
-  float D = a2 / (GI_PI * dd * dd);
+  float D = gi_div(a2, GI_PI * dd * dd);
   float L1 = ggx_lambda_term(a2, nk1), L2 = ggx_lambda_term(a2, nk2);
-  float G1 = 2.0f * nk1 / (nk1 + L1);
-  float G2 = 2.0f * nk1 * nk2 / (nk2 * L1 + nk1 * L2);
-  o.l2 = l2; o.kh = kh; o.pdf = G1 * D / (4.0f * nk1); o.g2OverG1 = G2 / G1; o.valid = true;
+  float G1 = gi_div(2.0f * nk1, nk1 + L1);
+  float G2 = gi_div(2.0f * nk1 * nk2, nk2 * L1 + nk1 * L2);
+  o.l2 = l2; o.kh = kh; o.pdf = gi_div(G1 * D, 4.0f * nk1); o.g2OverG1 = gi_div(G2, G1); o.valid = true;
   return o;
 }
 __device__ inline void ggx_eval(V3 l1, V3 l2, float alpha, float& fcos, float& pdf, float& kh)
@@ -308,12 +309,12 @@ __device__ inline void ggx_eval(V3 l1, V3 l2, float alpha, float& fcos, float& p
   float a2 = alpha * alpha;
   float nk1 = l1.z, nk2 = l2.z, nh2 = h.z * h.z;
   float dd = nh2 * (a2 - 1.0f) + 1.0f;
-  float D = a2 / (GI_PI * dd * dd);
+  float D = gi_div(a2, GI_PI * dd * dd);
   float L1 = ggx_lambda_term(a2, nk1), L2 = ggx_lambda_term(a2, nk2);
-  float G1 = 2.0f * nk1 / (nk1 + L1);
-  float G2 = 2.0f * nk1 * nk2 / (nk2 * L1 + nk1 * L2);
-  fcos = D * G2 / (4.0f * nk1);
-  pdf = G1 * D / (4.0f * nk1);
+  float G1 = gi_div(2.0f * nk1, nk1 + L1);
+  float G2 = gi_div(2.0f * nk1 * nk2, nk2 * L1 + nk1 * L2);
+  fcos = gi_div(D * G2, 4.0f * nk1);
+  pdf = gi_div(G1 * D, 4.0f * nk1);
 }
 
 // Anisotropic form, operation for operation the oracle's (oracle/gi_oracle.cpp "Anisotropic form"): used only when ax != ay, so isotropic materials keep the
@@ -330,7 +331,7 @@ __device__ inline GgxOut ggx_sample_xy(V3 l1, float ax, float ay, float x0, floa
   GgxOut o; o.valid = false; o.pdf = 0.0f; o.g2OverG1 = 0.0f; o.kh = 0.0f; o.l2 = v3(0.0f, 0.0f, 0.0f);
   V3 vh = normalize(v3(ax * l1.x, ay * l1.y, l1.z));
   float lensq = vh.x * vh.x + vh.y * vh.y;
-  V3 T1 = lensq > 0.0f ? v3(-vh.y, vh.x, 0.0f) * (1.0f / gi_sqrt(lensq)) : v3(1.0f, 0.0f, 0.0f);
+  V3 T1 = lensq > 0.0f ? v3(-vh.y, vh.x, 0.0f) * gi_rsqrt(lensq) : v3(1.0f, 0.0f, 0.0f);
   V3 T2 = cross(vh, T1);
   float r = gi_sqrt(x0);
   float s, c; gi_sincos2pi(x1, &s, &c);
@@ -345,9 +346,9 @@ __device__ inline GgxOut ggx_sample_xy(V3 l1, float ax, float ay, float x0, floa
   float nk1 = l1.z, nk2 = l2.z;
   float D = ggx_d_xy(ax, ay, h);
   float L1 = ggx_lambda_xy(ax, ay, l1), L2 = ggx_lambda_xy(ax, ay, l2);
-  float G1 = 2.0f * nk1 / (nk1 + L1);
-  float G2 = 2.0f * nk1 * nk2 / (nk2 * L1 + nk1 * L2);
-  o.l2 = l2; o.kh = kh; o.pdf = G1 * D / (4.0f * nk1); o.g2OverG1 = G2 / G1; o.valid = true;
+  float G1 = gi_div(2.0f * nk1, nk1 + L1);
+  float G2 = gi_div(2.0f * nk1 * nk2, nk2 * L1 + nk1 * L2);
+  o.l2 = l2; o.kh = kh; o.pdf = gi_div(G1 * D, 4.0f * nk1); o.g2OverG1 = gi_div(G2, G1); o.valid = true;
   return o;
 }
 __device__ inline void ggx_eval_xy(V3 l1, V3 l2, float ax, float ay, float& fcos, float& pdf, float& kh)
@@ -359,10 +360,10 @@ __device__ inline void ggx_eval_xy(V3 l1, V3 l2, float ax, float ay, float& fcos
   float nk1 = l1.z, nk2 = l2.z;
   float D = ggx_d_xy(ax, ay, h);
   float L1 = ggx_lambda_xy(ax, ay, l1), L2 = ggx_lambda_xy(ax, ay, l2);
-  float G1 = 2.0f * nk1 / (nk1 + L1);
-  float G2 = 2.0f * nk1 * nk2 / (nk2 * L1 + nk1 * L2);
-  fcos = D * G2 / (4.0f * nk1);
-  pdf = G1 * D / (4.0f * nk1);
+  float G1 = gi_div(2.0f * nk1, nk1 + L1);
+  float G2 = gi_div(2.0f * nk1 * nk2, nk2 * L1 + nk1 * L2);
+  fcos = gi_div(D * G2, 4.0f * nk1);
+  pdf = gi_div(G1 * D, 4.0f * nk1);
 }
 // open_pbr_anisotropy (open_pbr_surface.mtlx:133-136, 552-555): alpha_t = r^2 sqrt(2 / (1 + (1 - a)^2)), alpha_b = (1 - a) alpha_t
 __device__ __forceinline__ void opbr_anisotropy(float alpha, float a, float& ax, float& ay)
@@ -959,7 +960,7 @@ __device__ inline void bsdf_sample(const MaterialRec* m, const ShState& st, V3 k
     V3 l = gi_sample_hemisphere(x0, x1);
     V3 k2 = to_world(st, l);
     if (!(l.z > 0.0f) || !(dot(k2, st.geomNormal) > 0.0f)) return;
-    out.k2 = k2; out.pdf = l.z / GI_PI; out.overPdf = diffuse_class_color(m, st); out.event = EV_DIFFUSE | EV_REFLECTION;
+    out.k2 = k2; out.pdf = gi_div(l.z, GI_PI); out.overPdf = diffuse_class_color(m, st); out.event = EV_DIFFUSE | EV_REFLECTION;
     return;
   }
   if (klass == 1u) {
@@ -971,7 +972,7 @@ __device__ inline void bsdf_sample(const MaterialRec* m, const ShState& st, V3 k
     V3 Fs = v3(0.0f, 0.0f, 0.0f); float ps = 0.0f;
     uint32_t lobe = 0u; // 0 coat, 1 specular, 2 diffuse (one ggx_sample for both glossy lobes, see opbr_sample)
     if (!(z < Fc)) {
-      z = (z - Fc) / (1.0f - Fc);
+      z = gi_div(z - Fc, 1.0f - Fc);
       Fs = schlick3(u.F0, nk1);
       ps = fmax2(Fs.x, fmax2(Fs.y, Fs.z));
       lobe = (z < ps) ? 1u : 2u;
@@ -984,19 +985,19 @@ __device__ inline void bsdf_sample(const MaterialRec* m, const ShState& st, V3 k
       out.k2 = k2; out.event = EV_GLOSSY | EV_REFLECTION;
       if (lobe == 0u) {
         float Fh = u.coat * (0.04f + 0.96f * schlick_w(g.kh));
-        float w = (Fh / Fc) * g.g2OverG1;
+        float w = gi_div(Fh, Fc) * g.g2OverG1;
         out.pdf = Fc * g.pdf; out.overPdf = v3(w, w, w);
       } else {
         V3 Fh = schlick3(u.F0, g.kh);
-        out.pdf = (1.0f - Fc) * ps * g.pdf; out.overPdf = Fh * (g.g2OverG1 / ps);
+        out.pdf = (1.0f - Fc) * ps * g.pdf; out.overPdf = Fh * gi_div(g.g2OverG1, ps);
       }
       return;
     }
     V3 l = gi_sample_hemisphere(x0, x1);
     V3 k2 = to_world(st, l);
     if (!(l.z > 0.0f) || !(dot(k2, st.geomNormal) > 0.0f)) return;
-    out.k2 = k2; out.pdf = (1.0f - Fc) * (1.0f - ps) * (l.z / GI_PI);
-    out.overPdf = (u.albedo * (v3(1.0f, 1.0f, 1.0f) - Fs)) * (1.0f / (1.0f - ps));
+    out.k2 = k2; out.pdf = (1.0f - Fc) * (1.0f - ps) * gi_div(l.z, GI_PI);
+    out.overPdf = (u.albedo * (v3(1.0f, 1.0f, 1.0f) - Fs)) * gi_rcp(1.0f - ps);
     out.event = EV_DIFFUSE | EV_REFLECTION;
     return;
   }
@@ -1108,4 +1109,5 @@ __device__ inline void sample_light(const SceneView& sc, const FrameUniforms& U,
 }
 
 
+GI_MATH_END
 } // namespace gi

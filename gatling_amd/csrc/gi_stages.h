@@ -5,6 +5,7 @@
 #include "gi_shading.h"
 
 namespace gi {
+GI_MATH_BEGIN // gi_device_math.h: the functions here inherit the form of the arithmetic they call
 
 // Camera ray of (pixel, sample): RNG init, pixel jitter / filter importance sampling, thin lens, clip range
 // (rp_main.rgen:215-288).  Returns the RNG state after the draws the reference makes here.
@@ -276,7 +277,7 @@ __device__ __forceinline__ bool ray_misses_box(const float (&sceneLo)[3], const 
     const float lo = sceneLo[a], hi = sceneHi[a];
     const float pad = (fabsf(oo[a]) + fmax2(fabsf(lo), fabsf(hi))) * 4.0e-6f;
     if (dd[a] == 0.0f) { out = out || (oo[a] < lo - pad) || (oo[a] > hi + pad); continue; }
-    const float inv = 1.0f / dd[a];
+    const float inv = gi_rcp(dd[a]);
     const float t0 = ((lo - pad) - oo[a]) * inv, t1 = ((hi + pad) - oo[a]) * inv;
     float nearT = t0 < t1 ? t0 : t1, farT = t0 < t1 ? t1 : t0; // (the padded planes keep their order; a NaN leaves the interval alone below)
     nearT -= fabsf(nearT) * 1.0e-5f; farT += fabsf(farT) * 1.0e-5f;
@@ -327,4 +328,5 @@ __device__ __forceinline__ void begin_fresh_path(const FrameUniforms& U, const P
 }
 // (a first segment that HIT is begun by k_shade, which gathers the ray record and the FreshRec beside it and completes the Slot in one go)
 
+GI_MATH_END
 } // namespace gi

@@ -5,6 +5,7 @@
 #include "gi_queues.h"
 
 namespace gi {
+GI_MATH_BEGIN // gi_device_math.h: the functions here inherit the form of the arithmetic they call
 
 // ------------------------------------------------------------------------------------------------
 // Texture runtime (mdl_interface.glsl:8-38 apply_wrap_and_crop, :127-145 tex_lookup_float4_2d) over a software sampler:
@@ -142,4 +143,5 @@ __device__ inline float cutout_opacity_at(const SceneView& sc, uint32_t matWord,
   return cutout_rule(m->klass, raw, m->p[15]); // p[15] = opacityThreshold
 }
 
+GI_MATH_END
 } // namespace gi

@@ -8,6 +8,7 @@
 #include "gi_texture.h"
 
 namespace gi {
+GI_MATH_BEGIN // gi_device_math.h: the functions here inherit the form of the arithmetic they call
 
 // ------------------------------------------------------------------------------------------------
 // Software traversal of the 8-wide quantised BVH, one ray per lane.
@@ -234,7 +235,7 @@ __device__ __forceinline__ bool tri_test(V3 o, V3 d, float tMin, const uint4& a,
   const V3 v0 = v3(u2f(a.x), u2f(a.y), u2f(a.z)), e1 = v3(u2f(a.w), u2f(b.x), u2f(b.y)), e2 = v3(u2f(b.z), u2f(b.w), u2f(c.x));
   const V3 pv = cross(d, e2);
   const float det = dot(e1, pv);
-  const float inv = 1.0f / det;
+  const float inv = gi_rcp(det);
   const V3 tv = o - v0;
   u = dot(tv, pv) * inv;
   const V3 qv = cross(tv, e1);
@@ -597,4 +598,5 @@ __device__ __forceinline__ bool wave_step2(RayTrav2& R, bool alive, WaveTri& W, 
   return done;
 }
 
+GI_MATH_END
 } // namespace gi

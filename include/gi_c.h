@@ -615,6 +615,13 @@ int giCDebugShadeClass(const GiCMaterialDesc* desc);
 /* [ext] device self check: the kernels' square root (the compiler's correctly rounded expansion without the steps that ordinary arguments do not need) against sqrtf
  * for the `count` float bit patterns from `first` on; count = 2^32 covers every float.  Returns the number of arguments whose results differ (0), -1 on error. */
 int64_t giCDebugCheckSqrt(uint32_t first, uint64_t count);
+/* [ext] device self check: the fused kernels' division (the compiler's correctly rounded expansion without the steps that ordinary operands do not need; one
+ * reciprocal for the three quotients of a vector by a scalar) against `/`.  mode 0: `count` pairs (numerator, denominator) of float bit patterns in `words`;
+ * mode 1: `count` pairs drawn on the device from `seed`, every bit pattern equally likely (`words` unused); mode 2: `count` items (x, y, z, s) in `words`, checking
+ * normalize(x, y, z) and (x, y, z) / s; mode 3: such items drawn on the device from `seed`, with zero and denormal components among ordinary ones; mode 4: the
+ * reciprocal (1 / d in one correction step less) and 1 / sqrt(d) of the `count` bit patterns from `seed` on, count = 2^32 covers every float.  Modes 0 and 1 check 1 / d as well.
+ * Returns the number of items with a result that differs in a bit (NaN equals NaN), -1 on error. */
+int64_t giCDebugCheckDiv(uint32_t mode, uint64_t count, uint32_t seed, const uint32_t* words);
 /* [ext] device-side hook for the MDL renderer runtime's remaining texture entry points (mdl_interface.glsl:45-65, 86-105, 167-221), which only MDL-generated code
  * calls: `rgba` = width x height x depth RGBA float texels (slice by slice; depth 1 = a 2-D image); per query 8 floats (kind, valid, c0, c1, c2, wrapU, wrapV, wrapW)
  * with kind 0 tex_texel_float4_2d(c0, c1), 1 tex_resolution_2d, 2 tex_lookup_float4_3d(c0, c1, c2; wraps), 3 tex_texel_float4_3d(c0, c1, c2); valid 0 = the invalid

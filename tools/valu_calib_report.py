@@ -3,6 +3,7 @@
 profiles/valu_issue_calibration.{txt,json}.  bench.py reads `cycles_per_wave64_valu` from the json (VALU_CYCLES_PER_INST).
 
   python tools/valu_calib_report.py <valu_calib stdout> [<pmc results.db>] [--tag r03]
+  python tools/valu_calib_report.py <stdout of `valu_calib --packed`> --tag r16 --rows-only     (adds `rows_r16` to the json; the ceilings bench.py reads stay)
 """
 import argparse
 import json
@@ -42,16 +43,26 @@ def main():
     ap.add_argument("pmc_db", nargs="?")
     ap.add_argument("--pmc-log", help="stdout of the --pmc run (names the rows of pmc_db in launch order)")
     ap.add_argument("--tag", default="r03")
+    ap.add_argument("--rows-only", action="store_true", help="a partial run (valu_calib --packed): write the table and add the rows to the json as rows_<tag>, leave everything else in it alone")
     a = ap.parse_args()
     dev, rows = parse(a.log)
     if not rows:
         raise SystemExit("no VALU_CALIB lines in " + a.log)
     lines = [f"# VALU issue-rate calibration ({a.tag}; tools/valu_calib.hip) on {dev.get('name', '?')} ({dev.get('cus', '?')} CUs)",
              "# cycles/instr/SIMD = median wave cycles (s_memtime) / (waves per SIMD x instructions per wave): clock independent",
-             f"{'instruction':38s} {'waves/SIMD':>10s} {'cyc/instr/SIMD':>15s} {'instr/SIMD/ns (wall)':>21s} {'implied GHz':>12s} {'max waves per HW key':>21s}"]
+             f"{'instruction':62s} {'waves/SIMD':>10s} {'cyc/instr/SIMD':>15s} {'instr/SIMD/ns (wall)':>21s} {'implied GHz':>12s} {'max waves per HW key':>21s}"]
     for r in rows:
-        lines.append(f"{r['op']:38s} {int(r['waves_per_simd']):10d} {r['cycles_per_instr_per_simd']:15.4f} {r['wall_instr_per_simd_per_ns']:21.5f} "
+        lines.append(f"{r['op']:62s} {int(r['waves_per_simd']):10d} {r['cycles_per_instr_per_simd']:15.4f} {r['wall_instr_per_simd_per_ns']:21.5f} "
                      f"{r['implied_clock_GHz_at_that_rate']:12.4f} {int(r['max_waves_sharing_hw_key']):21d}")
+    if a.rows_only:
+        path = os.path.join(ROOT, "profiles", "valu_issue_calibration.json")
+        j = json.load(open(path))
+        j["rows_" + a.tag] = rows
+        j["source_" + a.tag] = f"profiles/{a.tag}_valu_issue_calibration.txt"
+        json.dump(j, open(path, "w"), indent=1)
+        open(os.path.join(ROOT, "profiles", f"{a.tag}_valu_issue_calibration.txt"), "w").write("\n".join(lines) + "\n")
+        print("\n".join(lines))
+        return
     # the constant: plain fp32 VALU at 8 waves/SIMD (issue-saturated)
     sat = {r["op"]: r["cycles_per_instr_per_simd"] for r in rows if int(r["waves_per_simd"]) == 8}
     rate = {r["op"]: r["wall_instr_per_simd_per_ns"] for r in rows if int(r["waves_per_simd"]) == 8}
@@ -71,7 +82,7 @@ def main():
         timed = prow[1::2]  # every timed launch follows its warm-up launch
         lines.append("")
         lines.append("# rocprofv3 --pmc of `valu_calib --pmc` (timed launches): what the SQ counters report for a known instruction count")
-        lines.append(f"{'instruction':38s} {'waves/SIMD':>10s} {'SQ_INSTS_VALU':>16s} {'expected':>16s} {'SQ_ACTIVE_INST_VALU':>20s} {'ACTIVE/INSTS':>13s} {'SQ_BUSY_CYCLES':>16s} {'SQ_WAVE_CYCLES':>16s}")
+        lines.append(f"{'instruction':62s} {'waves/SIMD':>10s} {'SQ_INSTS_VALU':>16s} {'expected':>16s} {'SQ_ACTIVE_INST_VALU':>20s} {'ACTIVE/INSTS':>13s} {'SQ_BUSY_CYCLES':>16s} {'SQ_WAVE_CYCLES':>16s}")
         pm = []
         for i, p in enumerate(timed):
             op, w = names[i] if names and i < len(names) else ("?", 0)
