@@ -28,6 +28,7 @@ OPTION_VISIBILITY_UPDATES = 11  # 1: visibility edits of meshes of the built sce
 OPTION_TOPOLOGY_UPDATES = 13  # 1: meshes created and destroyed after the build are appended to / retired from the resident scene instead of rebuilding it (include/gi_c.h); 0 = off (default)
 OPTION_RESYNC_REFITS = 14  # 1 (with options 12 and 13): a destroyed and a created mesh with the same faces become a vertex refit of the resident records instead of a retire + append (include/gi_c.h); 0 = off (default)
 OPTION_INSTANCE_UPDATES = 15  # 1 (with option 13): new instance ids or another instance count of a built mesh are applied to the resident scene instead of rebuilding it (include/gi_c.h); 0 = off (default)
+OPTION_TLAS_UPDATES = 16  # 1: transform edits of a built two-level scene (OPTION_TWO_LEVEL) are applied to the resident scene -- moved instances' records, a new TLAS, a refit of the flat tree -- instead of rebuilding it (include/gi_c.h); 0 = off (default)
 OPTION_BVH_BUILD = 9  # 0 = host BVH builder (default), 1 = device builder (flat-layout scenes of more than 128 triangles)
 
 
@@ -173,6 +174,8 @@ SYMBOLS = [
     ("giCDebugSceneResyncCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugGatherShade", C.c_int, [_P, _U, _P, _U]),
     ("giCDebugSceneShadeCheck", C.c_int, [_P, _U, C.POINTER(C.c_uint32)]),
     ("giCDebugSceneInstanceUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugCloneInstance", C.c_int, [_P, _U, _P, _U, _I, _FP, _FP]),
+    ("giCDebugSceneTlasUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugSceneTlasCheck", C.c_int, [_P, _U, C.POINTER(C.c_uint32)]),
+    ("giCDebugInstanceBounds", C.c_int, [_P, _U, _P, _U, _FP, _U, _FP, C.POINTER(C.c_uint32)]),
     ("giCDebugPathWalkStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugPathLobeStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugPathLot", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
@@ -244,6 +247,33 @@ def debug_clone_instance(vertices, faces, xform_a, xform_b, left_handed=False) -
     if n < 0:
         raise GiError("giCDebugCloneInstance refused the mesh or a transform")
     return int(n)
+
+
+def debug_instance_bounds(vertices, faces, xforms):
+    """giCDebugInstanceBounds: the device kernels that make the world boxes of moved instances of a two-level scene (k_inst_bounds / k_inst_finish) over the
+    mesh (`vertices`: VERTEX_DTYPE, `faces`: n x 3 indices) under each of `xforms` (k x 4 x 4, USD row vectors), against the host form of the same arithmetic.
+    Returns (differing, boxes, status): the number of (box, status) pairs that differ bytewise (0 is the contract), the device's padded boxes (k x 6: min xyz,
+    max xyz) and status words (k; 0 = usable).  Needs an initialised device."""
+    from .scene import VERTEX_DTYPE
+    L = load_library()
+    v = np.ascontiguousarray(vertices, VERTEX_DTYPE)
+    f = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3)
+    x = np.ascontiguousarray(xforms, np.float32).reshape(-1, 16)
+    boxes = np.zeros((len(x), 6), np.float32)
+    status = np.zeros(len(x), np.uint32)
+    n = L.giCDebugInstanceBounds(v.ctypes.data, len(v), f.ctypes.data, len(f), x.ctypes.data_as(_FP), len(x), boxes.ctypes.data_as(_FP),
+                                 status.ctypes.data_as(C.POINTER(C.c_uint32)))
+    if n < 0:
+        raise GiError("giCDebugInstanceBounds failed: " + L.giCGetLastError().decode())
+    return int(n), boxes, status
+
+
+class TlasCheck(int):
+    """Scene.tlas_check's answer: the number of differing records as an int, with what the hook reports beside it."""
+    two_level = 0
+    instances = 0
+    tlas_nodes = 0
+    tlas_depth = 0
 
 
 _initialized = False
@@ -399,6 +429,25 @@ class Scene:
         if self.L.giCDebugSceneTopologyUpdateCount(self.handle, C.byref(n)) != GI_C_OK:
             raise GiError("giCDebugSceneTopologyUpdateCount failed")
         return int(n.value)
+
+    def tlas_update_count(self) -> int:
+        """giCDebugSceneTlasUpdateCount: how often the scene was brought up to date by a transform update of the two-level layout (OPTION_TLAS_UPDATES; not
+        counted by update_counts)."""
+        n = C.c_uint64(0)
+        if self.L.giCDebugSceneTlasUpdateCount(self.handle, C.byref(n)) != GI_C_OK:
+            raise GiError("giCDebugSceneTlasUpdateCount failed")
+        return int(n.value)
+
+    def tlas_check(self, device: int = 0) -> "TlasCheck":
+        """giCDebugSceneTlasCheck: the two-level arrays resident on a device against the arrays the scene build's code makes anew from the current meshes.
+        Returns the number of differing records (0) as a TlasCheck: .two_level (1 when the layout is in use), .instances, .tlas_nodes, .tlas_depth."""
+        out = (C.c_uint32 * 4)()
+        v = self.L.giCDebugSceneTlasCheck(self.handle, device, out)
+        if v < 0:
+            raise GiError("giCDebugSceneTlasCheck failed: " + self.L.giCGetLastError().decode())
+        r = TlasCheck(v)
+        r.two_level, r.instances, r.tlas_nodes, r.tlas_depth = int(out[0]), int(out[1]), int(out[2]), int(out[3])
+        return r
 
     def set_mesh_transform(self, mesh_index: int, matrix):
         """giSetMeshTransform (Gi.h:213): a transform-only edit -- the next render updates the scene incrementally."""

@@ -3,6 +3,7 @@
 #include "gi_host.h"
 #include "gi_bvh_build.h"
 #include "gi_refit.h"
+#include "gi_tlas.h"
 #include "gi_pack.h"
 
 #include <unordered_map>
@@ -312,11 +313,9 @@ int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vec
   if (want <= 0 || instances.empty() || !beyondLds) return GI_C_OK;
   std::vector<Node8> blasNodes; std::vector<BlasTri> blasTris; std::vector<InstTrav> instTrav(instances.size());
   uint32_t blasDepth = 0;
-  std::vector<float> instBoxes(instances.size() * 6);
-  auto padBox = [](float* lo, float* hi) { // as bvh8.cpp pads triangle boxes: 2^-20 relative, covers the rounding of the exact test's inputs
-    for (int a = 0; a < 3; a++) { const float mag = std::max(std::fabs(lo[a]), std::fabs(hi[a])) + (hi[a] - lo[a]);
-        const float pad = mag * 9.5367431640625e-7f + 1.0e-30f; lo[a] -= pad; hi[a] += pad; }
-  };
+  std::vector<float> instBoxes(instances.size() * 6); std::vector<uint32_t> meshBlasTri(meshBuilds.size(), 0u);
+  // (gi_tlas.h: the point transform, the pad, the status rule and the InstTrav record are shared with the transform update in place and its kernels)
+  auto padBox = [](float* lo, float* hi) { tlas_pad_box(lo, hi); };
   for (const MB& mb : meshBuilds) {
     if (mb.instCount == 0) continue;
     const GiCMesh* m = mb.m;
@@ -335,6 +334,7 @@ int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vec
     Bvh8 b; std::vector<uint32_t> order;
     buildBvh8Boxes(boxes.data(), nf, b, order);
     const uint32_t nodeBase = (uint32_t)blasNodes.size(), triBase = (uint32_t)blasTris.size();
+    if (mb.meshIdx < meshBlasTri.size()) meshBlasTri[mb.meshIdx] = triBase;
     for (Node8 n : b.nodes) { n.childBase += nodeBase; n.triBase += triBase; blasNodes.push_back(n); }
     for (uint32_t f : order) {
       BlasTri bt{};
@@ -348,30 +348,23 @@ int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vec
     const float extent = (std::fabs(mlo[0]) + std::fabs(mlo[1]) + std::fabs(mlo[2])) + (std::fabs(mhi[0]) + std::fabs(mhi[1]) + std::fabs(mhi[2]));
     for (uint32_t ii = 0; ii < mb.instCount; ii++) {
       const uint32_t inst = mb.inst[ii];
-      InstTrav& tv = instTrav[inst];
-      tv = InstTrav{};
-      memcpy(tv.o2w, instances[inst].o2w, sizeof(tv.o2w)); memcpy(tv.w2o, instances[inst].w2o, sizeof(tv.w2o));
-      tv.blasRoot = nodeBase; tv.triBase = mb.triFirst + ii * (uint32_t)nf; tv.matFlags = mb.matFlags; tv.slack = extent;
-      float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+      instTrav[inst] = tlasMakeInstTrav(instances[inst], nodeBase, mb.triFirst + ii * (uint32_t)nf, mb.matFlags, extent);
       // inactive triangles (bvh8.h): a face with an unusable OBJECT-space vertex is left out of the BLAS by the builder and out of this box; an unusable
       // instance keeps the inverted box (the builder leaves it out of the TLAS). A usable face whose WORLD-space vertex is unusable is inactive in the flat
       // tree but would be walked here: such scenes keep the flat layout
+      TlasBounds wb; tlas_bounds_init(wb);
       if (usableInstance(instances[inst]))
-        for (size_t f = 0; f < nf; f++) {
-          bool objectOk = true, worldOk = true; float q[3][3];
-          for (int k = 0; k < 3; k++) {
-            const float* o = m->vertices[m->faces[f].v_i[k]].pos;
-            xformPoint(instances[inst].o2w, o, q[k]);
-            for (int a = 0; a < 3; a++) { objectOk = objectOk && usableCoordinate(o[a]); worldOk = worldOk && usableCoordinate(q[k][a]); }
-          }
-          if (!objectOk) continue;
-          if (!worldOk) {
-            if (want > 0) fprintf(stderr,
-                "[gatling_gi] two-level layout not used: an instance carries triangles that leave the usable coordinate range in world space\n");
-            return GI_C_OK;
-          }
-          for (int k = 0; k < 3; k++) for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], q[k][a]); hi[a] = std::max(hi[a], q[k][a]); }
+        for (size_t f = 0; f < nf && !(wb.status & TLAS_STATUS_WORLD); f++) {
+          float p[3][3];
+          for (int k = 0; k < 3; k++) memcpy(p[k], m->vertices[m->faces[f].v_i[k]].pos, 12);
+          tlas_bounds_add_tri(instances[inst].o2w, p, wb, false);
         }
+      if (wb.status & TLAS_STATUS_WORLD) {
+        if (want > 0) fprintf(stderr,
+            "[gatling_gi] two-level layout not used: an instance carries triangles that leave the usable coordinate range in world space\n");
+        return GI_C_OK;
+      }
+      float* lo = wb.lo; float* hi = wb.hi;
       padBox(lo, hi);
       for (int a = 0; a < 3; a++) { instBoxes[6 * inst + a] = lo[a]; instBoxes[6 * inst + 3 + a] = hi[a]; }
     }
@@ -392,6 +385,7 @@ int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vec
       "[gatling_gi] two-level: TLAS %zu nodes over %zu instances, %zu BLAS nodes, %zu mesh triangles (flat: %zu nodes, %zu triangles)\n",
                                               tlas.nodes.size(), instances.size(), blasNodes.size(), blasTris.size(), flatNodes, flatTris);
   out.tlasNodes.swap(tlas.nodes); out.tlasItems.swap(tlasItems); out.blasNodes.swap(blasNodes); out.blasTris.swap(blasTris); out.instTrav.swap(instTrav);
+  out.instBoxes.swap(instBoxes); out.meshBlasTri.swap(meshBlasTri); out.tlasDepth = tlas.maxDepth; out.blasDepth = blasDepth;
   return GI_C_OK;
 }
 
@@ -838,10 +832,19 @@ static bool relayoutPartitioned(GiCScene* s, SceneHost& H)
   return true;
 }
 
+// GI_C_SCENE_OPTION_TLAS_UPDATES / GATLING_OPTIONS=tlas_updates: transform edits of a two-level scene are applied in place (updateTransformsTwoLevel below)
+bool tlasUpdatesWanted(const GiCScene* s)
+{
+  const long o = optionValue("tlas_updates", -1);
+  return o >= 0 ? o == 1 : s->optTlasUpdates == 1;
+}
+static int updateTransformsTwoLevel(GiCScene* s, SceneHost& H, bool& handled, UpdateCost& cost);
+
 // handled true: done incrementally; left false: the caller must run a full buildScene (not an error)
 static int updateTransforms(GiCScene* s, bool& handled, UpdateCost& cost)
 {
   SceneHost* host = incrementalHost(s);
+  if (host && s->twoLevel && tlasUpdatesWanted(s)) return updateTransformsTwoLevel(s, *host, handled, cost);
   if (!host || s->twoLevel || s->triCount < kIncrementalMinTris) return GI_C_OK; // (the floor: resident triangles)
   SceneHost& H = *host;
   for (const MeshBuild& mb : H.meshBuilds) if (mb.m->builtInstances != mb.instCount) return GI_C_OK; // (cannot happen: count changes raise DIRTY_BVH)
@@ -1922,6 +1925,264 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
   return GI_C_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Transform updates on the two-level layout (opt-in: GI_C_SCENE_OPTION_TLAS_UPDATES / GATLING_OPTIONS=tlas_updates=1).  Instances of a built two-level scene
+// moved (giCSetMeshTransform, giCSetMeshInstanceTransforms with the same count); nothing else asked for a rebuild.  Moving an instance is the edit a TLAS is
+// for: every BLAS stays, and
+//   device, primary, scratch only: the padded world box and the status of every moved instance, from the mesh's resident BLAS triangles under the new
+//       transform (gi_tlas.hip k_inst_bounds / k_inst_finish; gi_tlas.h is buildTwoLevel's arithmetic).  28 bytes per moved instance are read back.
+//   host: the decision (below), then the TLAS built again over ALL instance boxes by the builder buildTwoLevel uses -- N boxes, not triangles.
+//   every device: the moved instances' InstanceRec and InstTrav records in runs, the TLAS nodes and items, and -- the flat tree stays (k_shade reads its
+//       records, k_aov and giCTraceRays walk it) -- k_refit_tris over the flat records of the moved instances and k_refit_level over the whole flat tree,
+//       deepest level first: what updateVertices does for an unpartitioned tree.  The flat root is read back for the scene bounds.
+//   host copies: H.instances and H.two are brought up to date; the flat host tree is dropped as after a vertex refit (H.hostTreeDropped).
+// The arrays k_trace_dyn2 walks are then bytewise a fresh build's (giCDebugSceneTlasCheck); the flat tree has the build's topology and conservative boxes, and
+// the image is a fresh build's under the traversal contract.
+// Declines (handled = false, not an error; the resident scene is untouched but where noted): no host copy or GATLING_OPTIONS=incremental=0 (the caller),
+// fewer than kIncrementalMinTris resident triangles, a scene built with inactive triangles, a flat tree without its level table (device-built), a moved
+// instance that is unusable (usableInstance) or whose status is set (gi_tlas.h: a corner unusable in object or world space, a flattened triangle the
+// builders would leave out), a TLAS too deep for the layout's stack (2 x TLAS depth + BLAS depth + 1 > 16: a fresh build would leave the two-level layout),
+// out of device memory for the scratch or the refit's boxes (a later device of several: the earlier ones are committed, and buildScene sends everything anew).
+// ---------------------------------------------------------------------------------------------------------------
+static int updateTransformsTwoLevel(GiCScene* s, SceneHost& H, bool& handled, UpdateCost& cost)
+{
+  TwoLevelHost& T = H.two;
+  const uint32_t instanceCount = (uint32_t)H.instances.size(), shadeCount = (uint32_t)H.triShade.size();
+  if (s->triCount < kIncrementalMinTris || !H.shadePacked || s->stats.inactiveTriangleCount != 0u) return GI_C_OK; // (the floor: resident triangles)
+  if (H.deviceBuilt || H.partitioned || H.bvh.levelStart.size() < 2u || H.bvh.levelStart.back() != s->nodeCount) return GI_C_OK;
+  if (T.instTrav.size() != instanceCount || T.instBoxes.size() != 6u * (size_t)instanceCount || T.meshBlasTri.size() != H.meshBuilds.size()) return GI_C_OK; // (cannot happen)
+  const bool timing = getenv("GATLING_BUILD_TIMING") != nullptr;
+  const double t0 = nowMs();
+  // --- the moved instances: their records and one bounds job each
+  std::vector<InstBoundsJob> jobs; std::vector<InstanceRec> moved;
+  uint32_t chunksPerJob = 0;
+  for (const MeshBuild& mb : H.meshBuilds) {
+    if (mb.m->builtInstances != mb.instCount) return GI_C_OK; // (cannot happen: count changes raise DIRTY_BVH)
+    if (!mb.m->xformDirty) continue;
+    const size_t nf = mb.m->faces.size();
+    const uint32_t first = T.meshBlasTri[mb.meshIdx];
+    if (mb.hidden || mb.m->retired || nf >= ((size_t)1 << 26) || (size_t)first + nf > T.blasTris.size()) return GI_C_OK; // (cannot happen on this layout)
+    for (uint32_t ii = 0; ii < mb.instCount; ii++) {
+      if (!mb.m->instDirty.empty() && !(ii < mb.m->instDirty.size() && mb.m->instDirty[ii])) continue;
+      const InstanceRec ir = makeInstanceRec(mb.m, mb.meshIdx, ii);
+      if (!usableInstance(ir)) return GI_C_OK;
+      InstBoundsJob j{}; memcpy(j.o2w, ir.o2w, sizeof(j.o2w)); j.firstTri = first; j.faceCount = (uint32_t)nf; j.instance = mb.inst[ii];
+      if (j.instance >= instanceCount) return GI_C_OK; // (cannot happen)
+      jobs.push_back(j); moved.push_back(ir);
+      chunksPerJob = std::max(chunksPerJob, instBoundsChunks(j.faceCount));
+    }
+  }
+  const uint32_t jobCount = (uint32_t)jobs.size();
+  if (jobCount == 0u) { // the setters were called with the transforms the scene holds
+    for (GiCMesh* m : s->meshes) { m->xformDirty = false; m->instDirty.clear(); }
+    handled = true;
+    return GI_C_OK;
+  }
+  if ((uint64_t)jobCount * chunksPerJob >= (1ull << 31)) return GI_C_OK; // (more workgroups than a launch takes)
+  // --- primary device, scratch only: padded boxes and statuses
+  std::vector<uint32_t> result((size_t)jobCount * 7u);
+  bool outOfMemory = false;
+  int rcDev = onSceneDevices(s, 1u, [&](SceneDevice& D, hipStream_t st) -> int {
+    if (D.dBlasTris.count < T.blasTris.size()) { setError("internal: the device holds less than the scene"); return GI_C_ERROR; }
+    DeviceBuffer<InstBoundsJob> dJobs; DeviceBuffer<float> dPartials; DeviceBuffer<uint32_t> dOut;
+    auto releaseAll = [&] { dJobs.release(); dPartials.release(); dOut.release(); };
+    const int a = dJobs.alloc(jobCount), b = a ? a : dPartials.alloc((size_t)jobCount * chunksPerJob * 8u), c = b ? b : dOut.alloc(result.size());
+    if (c != GI_C_OK) { releaseAll(); if (c == GI_C_OUT_OF_MEMORY_INTERNAL) { outOfMemory = true; return DEVICE_BUILD_FALLBACK; } return GI_C_ERROR; }
+    int rc = GI_C_OK;
+    if (hipMemcpyAsync(dJobs.ptr, jobs.data(), jobs.size() * sizeof(InstBoundsJob), hipMemcpyHostToDevice, st) != hipSuccess) rc = GI_C_ERROR;
+    if (rc == GI_C_OK && !launchInstBounds(st, dJobs.ptr, jobCount, chunksPerJob, D.dBlasTris.ptr, (uint32_t)T.blasTris.size(), dPartials.ptr, dOut.ptr)) rc = GI_C_ERROR; // (asked above)
+    if (rc == GI_C_OK && (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(result.data(), dOut.ptr, result.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess)) rc = GI_C_ERROR;
+    if (hipStreamSynchronize(st) != hipSuccess) rc = GI_C_ERROR;
+    if (rc != GI_C_OK) setError("transform update (two-level): instance bounds failed on the device");
+    releaseAll();
+    return rc;
+  });
+  if (rcDev == DEVICE_BUILD_FALLBACK && outOfMemory) return GI_C_OK;
+  if (rcDev != GI_C_OK) return GI_C_ERROR;
+  // --- the decision: every moved instance usable; the TLAS over all boxes within the stack rule
+  for (uint32_t k = 0; k < jobCount; k++)
+    if (result[7u * k + 6u] != 0u) {
+      if (timing) fprintf(stderr, "[gatling_gi] transform update (two-level): instance %u is not usable where it moved (status %u); the scene is rebuilt\n",
+                          jobs[k].instance, result[7u * k + 6u]);
+      return GI_C_OK;
+    }
+  std::vector<float> boxes(T.instBoxes);
+  for (uint32_t k = 0; k < jobCount; k++) memcpy(&boxes[6u * (size_t)jobs[k].instance], &result[7u * (size_t)k], 24);
+  const double t1 = nowMs();
+  Bvh8 tlas; std::vector<uint32_t> tlasItems;
+  buildBvh8Boxes(boxes.data(), instanceCount, tlas, tlasItems);
+  const double t2 = nowMs();
+  if (2u * tlas.maxDepth + T.blasDepth + 1u > 16u) {
+    if (timing) fprintf(stderr, "[gatling_gi] transform update (two-level): the new TLAS is too deep for the 16-entry stack; the scene is rebuilt\n");
+    return GI_C_OK;
+  }
+  // --- the new records, the flat refit's plan
+  std::vector<InstanceRec> instances(H.instances); std::vector<InstTrav> instTrav(T.instTrav);
+  std::vector<uint32_t> editedOfInstance(instanceCount, 0u);
+  for (uint32_t k = 0; k < jobCount; k++) {
+    const uint32_t i = jobs[k].instance;
+    const InstTrav& was = T.instTrav[i]; // (the mesh's constants: a transform changes none; matFlags is the last material update's)
+    instances[i] = moved[k]; instTrav[i] = tlasMakeInstTrav(moved[k], was.blasRoot, was.triBase, was.matFlags, was.slack);
+    editedOfInstance[i] = 1u;
+  }
+  std::vector<std::pair<uint32_t, uint32_t>> runs; // (first, count) of consecutive moved instances
+  for (uint32_t i = 0; i < instanceCount; i++)
+    if (editedOfInstance[i]) { if (!runs.empty() && runs.back().first + runs.back().second == i) runs.back().second++; else runs.emplace_back(i, 1u); }
+  std::vector<RefitUnit> units{RefitUnit{0u, &H.bvh.levelStart}};
+  std::vector<RefitRange> ranges; std::vector<RefitLevel> levels;
+  if (!planRefitLevels(units, s->nodeCount, ranges, levels)) return GI_C_OK; // (cannot happen: the levels of a tree inside the node array)
+  // --- every device of the scene, on its own stream.  The temporaries are allocated before anything resident changes
+  Node8 root{}; size_t bytesSent = 0;
+  rcDev = onSceneDevices(s, residentDeviceCount(s), [&](SceneDevice& D, hipStream_t st) -> int {
+    if (D.dTris.count < s->triCount || D.dNodes.count < s->nodeCount || D.dInstances.count < instanceCount || D.dInstTrav.count < instanceCount ||
+        D.dTriShade.count < shadeCount) { setError("internal: the device holds less than the scene"); return GI_C_ERROR; }
+    DeviceBuffer<float> dBoxes; DeviceBuffer<uint32_t> dEdited; DeviceBuffer<RefitRange> dRanges;
+    auto releaseAll = [&] { dBoxes.release(); dEdited.release(); dRanges.release(); };
+    const int a = dBoxes.alloc((size_t)s->nodeCount * 8u), b = a ? a : dEdited.alloc(editedOfInstance.size()), c = b ? b : dRanges.alloc(ranges.size());
+    if (c != GI_C_OK) { releaseAll(); if (c == GI_C_OUT_OF_MEMORY_INTERNAL) { outOfMemory = true; return DEVICE_BUILD_FALLBACK; } return GI_C_ERROR; }
+    int rc = GI_C_OK;
+    auto copy = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+      if (rc == GI_C_OK && bytes && hipMemcpyAsync(dst, src, bytes, kind, st) != hipSuccess) { setError("transform update (two-level): copy failed"); rc = GI_C_ERROR; } };
+    for (const auto& r : runs) {
+      copy(D.dInstances.ptr + r.first, &instances[r.first], (size_t)r.second * sizeof(InstanceRec), hipMemcpyHostToDevice);
+      copy(D.dInstTrav.ptr + r.first, &instTrav[r.first], (size_t)r.second * sizeof(InstTrav), hipMemcpyHostToDevice);
+    }
+    if (rc == GI_C_OK && (D.dTlasNodes.upload(tlas.nodes, st) || D.dTlasItems.upload(tlasItems, st))) rc = GI_C_ERROR;
+    copy(dEdited.ptr, editedOfInstance.data(), editedOfInstance.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    copy(dRanges.ptr, ranges.data(), ranges.size() * sizeof(RefitRange), hipMemcpyHostToDevice);
+    if (rc == GI_C_OK) {
+      launchRefitTris(st, D.dTris.ptr, s->triCount, D.dInstances.ptr, instanceCount, dEdited.ptr, D.dTriShade.ptr, shadeCount);
+      for (const RefitLevel& lv : levels) launchRefitLevel(st, D.dNodes.ptr, s->nodeCount, dBoxes.ptr, dRanges.ptr + lv.first, lv.ranges, lv.threads, D.dTris.ptr,
+          s->triCount, D.dInstances.ptr, instanceCount, D.dTriShade.ptr, shadeCount);
+      if (hipGetLastError() != hipSuccess) { setError("transform update (two-level): launch failed"); rc = GI_C_ERROR; }
+    }
+    if (D.slot == 0u) copy(&root, D.dNodes.ptr, sizeof(Node8), hipMemcpyDeviceToHost); // (the refit is deterministic: every device holds the same bytes)
+    if (hipStreamSynchronize(st) != hipSuccess && rc == GI_C_OK) { setError("transform update (two-level): device error"); rc = GI_C_ERROR; }
+    releaseAll(); // (before the render's memory plan reads free memory)
+    return rc;
+  });
+  if (rcDev == DEVICE_BUILD_FALLBACK && outOfMemory) {
+    if (timing) fprintf(stderr, "[gatling_gi] transform update (two-level): out of device memory for the refit's boxes; the scene is rebuilt\n");
+    return GI_C_OK;
+  }
+  if (rcDev != GI_C_OK) return GI_C_ERROR;
+  // --- the host copies
+  bytesSent = (size_t)jobCount * (sizeof(InstBoundsJob) + sizeof(InstanceRec) + sizeof(InstTrav)) + tlas.nodes.size() * sizeof(Node8) + tlasItems.size() * sizeof(uint32_t) +
+      editedOfInstance.size() * sizeof(uint32_t) + ranges.size() * sizeof(RefitRange);
+  const size_t tlasNodeCount = tlas.nodes.size();
+  H.instances.swap(instances); T.instTrav.swap(instTrav); T.instBoxes.swap(boxes); T.tlasNodes.swap(tlas.nodes); T.tlasItems.swap(tlasItems); T.tlasDepth = tlas.maxDepth;
+  setSceneBounds(s, std::vector<Node8>{root});
+  if (!H.hostTreeDropped) { // the host copies of the flat tree are stale from here on: dropped, as after a vertex refit
+    std::vector<Node8>().swap(H.bvh.nodes); std::vector<TriRec>().swap(H.bvh.tris); std::vector<int32_t>().swap(H.triFaceId);
+    H.hostTreeDropped = true;
+  }
+  for (GiCMesh* m : s->meshes) { m->xformDirty = false; m->instDirty.clear(); }
+  const double t3 = nowMs();
+  cost.buildMs = t2 - t1; cost.uploadMs = std::max(t3 - t0 - cost.buildMs, 0.0);
+  if (timing) fprintf(stderr, "[gatling_gi] transform update (two-level): %u instance(s) moved of %u, TLAS %zu node(s) in %u level(s), %zu level launch(es) over the flat "
+                              "tree, host TLAS build %.2f ms, bounds kernels + read-back %.2f ms, commit %.2f ms, %zu bytes sent per device\n", jobCount,
+                      instanceCount, tlasNodeCount, T.tlasDepth, levels.size(), t2 - t1, t1 - t0, t3 - t2, bytesSent);
+  handled = true;
+  return GI_C_OK;
+}
+
+// giCDebugSceneTlasCheck: the two-level arrays resident on a device against the arrays buildTwoLevel makes anew from the scene's current meshes, bytewise
+extern "C" int giCDebugSceneTlasCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t* out)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!g_ctx.initialized || !s || !out) { setError("giCDebugSceneTlasCheck: bad arguments"); return -1; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  if (!s->host) { setError("giCDebugSceneTlasCheck: the scene has not been built (render it once)"); return -1; }
+  if (deviceIndex > s->replicas.size() || deviceIndex >= sceneDeviceCount(s)) { setError("giCDebugSceneTlasCheck: no such device copy"); return -1; }
+  const SceneHost& H = *s->host;
+  out[0] = s->twoLevel ? 1u : 0u; out[1] = (uint32_t)H.instances.size(); out[2] = (uint32_t)H.two.tlasNodes.size(); out[3] = H.two.tlasDepth;
+  if (!s->twoLevel) { out[2] = out[3] = 0u; return 0; }
+  try {
+    std::vector<InstanceRec> instances(H.instances.size());
+    for (const MeshBuild& mb : H.meshBuilds) {
+      if (mb.m->instanceTransforms.size() != (size_t)mb.instCount * 16u) { setError("giCDebugSceneTlasCheck: a mesh's instance count is not the built one (render first)"); return -1; }
+      for (uint32_t ii = 0; ii < mb.instCount; ii++) instances[mb.inst[ii]] = makeInstanceRec(mb.m, mb.meshIdx, ii);
+    }
+    TwoLevelHost fresh;
+    const int rc = buildTwoLevel(s, H.meshBuilds, instances, s->triCount, s->nodeCount, fresh);
+    const bool stillTwoLevel = s->twoLevel;
+    s->twoLevel = true; // (buildTwoLevel answers through it: the resident scene is what it was)
+    if (rc != GI_C_OK || !stillTwoLevel) { setError("giCDebugSceneTlasCheck: a fresh build of the current meshes would not use the two-level layout"); return -1; }
+    SceneDevice& D = sceneDevice(s, deviceIndex);
+    std::vector<Node8> tlasNodes(fresh.tlasNodes.size()), blasNodes(fresh.blasNodes.size()); std::vector<uint32_t> tlasItems(fresh.tlasItems.size());
+    std::vector<BlasTri> blasTris(fresh.blasTris.size()); std::vector<InstTrav> instTrav(fresh.instTrav.size());
+    int differ = 0;
+    // (a resident array shorter than the fresh one: every missing record differs; the TLAS buffers may be longer -- they keep their block when the tree shrinks)
+    auto fetch = [&](auto& host, const auto& dev) -> bool {
+      using R = typename std::remove_reference<decltype(host)>::type::value_type;
+      const size_t n = std::min(host.size(), dev.ptr ? dev.count : (size_t)0);
+      differ += (int)(host.size() - n);
+      host.resize(n);
+      return n == 0u || hipMemcpy(host.data(), dev.ptr, n * sizeof(R), hipMemcpyDeviceToHost) == hipSuccess;
+    };
+    bool ok = hipSetDevice(g_ctx.devs[D.slot].device) == hipSuccess;
+    ok = ok && fetch(tlasNodes, D.dTlasNodes) && fetch(tlasItems, D.dTlasItems) && fetch(instTrav, D.dInstTrav) && fetch(blasNodes, D.dBlasNodes) && fetch(blasTris, D.dBlasTris);
+    (void)hipSetDevice(g_ctx.device);
+    if (!ok) { setError("giCDebugSceneTlasCheck: download failed"); return -1; }
+    if (H.two.tlasNodes.size() != fresh.tlasNodes.size()) differ++; // (the host copy the next update starts from)
+    auto compare = [&](const auto& got, const auto& want) {
+      using R = typename std::remove_reference<decltype(got)>::type::value_type;
+      for (size_t i = 0; i < got.size(); i++) if (memcmp(&got[i], &want[i], sizeof(R)) != 0) differ++;
+    };
+    compare(tlasNodes, fresh.tlasNodes); compare(tlasItems, fresh.tlasItems); compare(instTrav, fresh.instTrav); compare(blasNodes, fresh.blasNodes);
+    compare(blasTris, fresh.blasTris);
+    out[2] = (uint32_t)fresh.tlasNodes.size(); out[3] = fresh.tlasDepth;
+    return differ;
+  } catch (const std::exception& e) { s->twoLevel = true; setError(std::string("giCDebugSceneTlasCheck: ") + e.what()); return -1; }
+}
+
+// giCDebugInstanceBounds: k_inst_bounds + k_inst_finish over one mesh under `xformCount` instance transforms against the host form of the same arithmetic
+// (gi_tlas.h tlasInstanceBoundsHost), bytewise
+extern "C" int giCDebugInstanceBounds(const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, const float* xforms16,
+    uint32_t xformCount, float* outBoxes6, uint32_t* outStatus)
+{
+  if (!g_ctx.initialized) { setError("giCDebugInstanceBounds before giCInitialize"); return -1; }
+  if ((vertexCount && !vertices) || (faceCount && !faces) || (xformCount && !xforms16) || faceCount >= (1u << 26)) { setError("giCDebugInstanceBounds: bad arguments"); return -1; }
+  for (uint32_t f = 0; f < faceCount; f++) for (int k = 0; k < 3; k++) if (faces[f].v_i[k] >= vertexCount) { setError("giCDebugInstanceBounds: a face index outside the vertices"); return -1; }
+  if (xformCount == 0u) return 0;
+  try {
+    std::vector<BlasTri> tris(faceCount);
+    for (uint32_t f = 0; f < faceCount; f++) {
+      BlasTri bt{};
+      memcpy(bt.p0, vertices[faces[f].v_i[0]].pos, 12); memcpy(bt.p1, vertices[faces[f].v_i[1]].pos, 12); memcpy(bt.p2, vertices[faces[f].v_i[2]].pos, 12);
+      bt.prim = f; tris[f] = bt;
+    }
+    GiCMesh m; m.scene = nullptr; m.id = 0;
+    m.instanceTransforms.assign(xforms16, xforms16 + (size_t)xformCount * 16u);
+    std::vector<InstBoundsJob> jobs(xformCount);
+    for (uint32_t i = 0; i < xformCount; i++) {
+      const InstanceRec ir = makeInstanceRec(&m, 0u, i);
+      jobs[i] = InstBoundsJob{}; memcpy(jobs[i].o2w, ir.o2w, sizeof(ir.o2w)); jobs[i].firstTri = 0u; jobs[i].faceCount = faceCount; jobs[i].instance = i;
+    }
+    const uint32_t chunksPerJob = std::max(instBoundsChunks(faceCount), 1u);
+    std::vector<uint32_t> result((size_t)xformCount * 7u, 0xa5a5a5a5u);
+    DeviceBuffer<InstBoundsJob> dJobs; DeviceBuffer<BlasTri> dTris; DeviceBuffer<float> dPartials; DeviceBuffer<uint32_t> dOut;
+    hipStream_t st = g_ctx.stream;
+    bool ok = hipSetDevice(g_ctx.device) == hipSuccess && dJobs.upload(jobs, st) == GI_C_OK && dTris.upload(tris, st) == GI_C_OK &&
+        dPartials.alloc((size_t)xformCount * chunksPerJob * 8u) == GI_C_OK && dOut.upload(result, st) == GI_C_OK;
+    ok = ok && launchInstBounds(st, dJobs.ptr, xformCount, chunksPerJob, dTris.ptr, faceCount, dPartials.ptr, dOut.ptr) && hipGetLastError() == hipSuccess;
+    ok = ok && hipMemcpyAsync(result.data(), dOut.ptr, result.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess;
+    ok = hipStreamSynchronize(st) == hipSuccess && ok;
+    dJobs.release(); dTris.release(); dPartials.release(); dOut.release();
+    if (!ok) { setError("giCDebugInstanceBounds: device error"); return -1; }
+    int differ = 0;
+    for (uint32_t i = 0; i < xformCount; i++) {
+      float box[6];
+      const uint32_t status = tlasInstanceBoundsHost(jobs[i].o2w, tris.data(), tris.size(), box);
+      if (memcmp(box, &result[7u * (size_t)i], 24) != 0 || status != result[7u * (size_t)i + 6u]) differ++;
+      if (outBoxes6) memcpy(outBoxes6 + 6u * (size_t)i, &result[7u * (size_t)i], 24);
+      if (outStatus) outStatus[i] = result[7u * (size_t)i + 6u];
+    }
+    return differ;
+  } catch (const std::exception& e) { setError(std::string("giCDebugInstanceBounds: ") + e.what()); return -1; }
+}
+
 // brings the device scene up to date with the host-side edits: incremental for DIRTY_BVH raised by vertex edits alone (opt-in: the tree refitted on the
 // device), by visibility toggles alone (opt-in: ids renumbered, the
 // toggled meshes' triangles hidden / shown in place), for material-side edits alone (the small arrays + one word per triangle) and for transform edits alone
@@ -1961,7 +2222,9 @@ int syncSceneGeometry(GiCScene* s)
   if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_BVH) && !s->rebuildDue && anyVerts, updateVertices, UPDATE_VERTEX, anyVis ? 0u : (uint32_t)DIRTY_BVH, DIRTY_BVH, 0u);
   if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_BVH) && !s->rebuildDue && visibilityUpdatesWanted(s), updateVisibility, UPDATE_VISIBILITY, DIRTY_BVH, 0u, 0u);
   if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_MATERIALS) && !(s->dirty & DIRTY_BVH), updateMaterials, UPDATE_MATERIAL, DIRTY_MATERIALS, DIRTY_BVH, DIRTY_BVH);
-  if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_XFORM) && !(s->dirty & (DIRTY_BVH | DIRTY_MATERIALS)), updateTransforms, UPDATE_TRANSFORM, 0u, DIRTY_BVH, 0u);
+  // (a transform update of the two-level layout has a counter of its own: giCDebugSceneUpdateCounts keeps counting what it counted)
+  const uint32_t transformCounter = s->twoLevel && tlasUpdatesWanted(s) && incrementalHost(s) ? (uint32_t)UPDATE_TLAS : (uint32_t)UPDATE_TRANSFORM;
+  if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_XFORM) && !(s->dirty & (DIRTY_BVH | DIRTY_MATERIALS)), updateTransforms, transformCounter, 0u, DIRTY_BVH, 0u);
   if (updated) { s->stats.bvhBuildMs = spent.buildMs; s->stats.uploadMs = spent.uploadMs; s->stats.nodeCount = s->nodeCount;
       s->stats.triangleCount = s->triCount; } // (a full build below overrides all four)
   if (rc != GI_C_OK) return rc;

@@ -320,6 +320,7 @@ int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value)
   // (likewise: how future destroy + create pairs are applied; read only with options 12 and 13 wanted)
   if (option == GI_C_SCENE_OPTION_RESYNC_REFITS) { scene->optResyncRefits = value == 1 ? 1 : 0; return GI_C_OK; }
   if (option == GI_C_SCENE_OPTION_INSTANCE_UPDATES) { scene->optInstanceUpdates = value == 1 ? 1 : 0; return GI_C_OK; }
+  if (option == GI_C_SCENE_OPTION_TLAS_UPDATES) { scene->optTlasUpdates = value == 1 ? 1 : 0; return GI_C_OK; }
   setError("unknown scene option"); return GI_C_ERROR;
 }
 

@@ -576,6 +576,15 @@ extern "C" int giCDebugSceneTopologyUpdateCount(const GiCScene* scene, uint64_t*
   return GI_C_OK;
 }
 
+extern "C" int giCDebugSceneTlasUpdateCount(const GiCScene* scene, uint64_t* outCount)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!s || !outCount) { setError("giCDebugSceneTlasUpdateCount: bad arguments"); return GI_C_ERROR; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  *outCount = s->updateCounts[UPDATE_TLAS];
+  return GI_C_OK;
+}
+
 extern "C" int giCDebugSceneInstanceUpdateCount(const GiCScene* scene, uint64_t* out)
 {
   GiCScene* s = const_cast<GiCScene*>(scene);

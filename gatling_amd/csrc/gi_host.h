@@ -307,7 +307,9 @@ struct SceneDevice {
 
 // The scene as host arrays (built once per scene change, kept for incremental transform updates) ...
 struct TwoLevelHost { std::vector<Node8> tlasNodes, blasNodes; std::vector<uint32_t> tlasItems; std::vector<BlasTri> blasTris; std::vector<InstTrav> instTrav;
-    };
+    // transform updates in place (gi_build.cpp updateTransformsTwoLevel): the padded world box of every instance (6 floats each: what the TLAS is built
+    // over), the first BLAS triangle of every mesh by meshIdx, and the depths the layout's stack rule reads
+    std::vector<float> instBoxes; std::vector<uint32_t> meshBlasTri; uint32_t tlasDepth = 0, blasDepth = 0; };
 struct MeshBuild { const GiCMesh* m; uint32_t vertexOffset, matFlags, instFirst, instCount, triFirst; uint32_t meshIdx; std::vector<int32_t> faceIdAov;
     uint32_t shadeBase = 0;
     // the InstanceRec of every live instance, inst[instInMesh]: instFirst + instInMesh (and triangles at triFirst + instInMesh * faces) as the build leaves
@@ -342,7 +344,7 @@ struct SceneHost {
   bool reordered = false;
 };
 
-enum : uint32_t { UPDATE_FULL = 0, UPDATE_TRANSFORM = 1, UPDATE_MATERIAL = 2, UPDATE_VISIBILITY = 3, UPDATE_VERTEX = 4, UPDATE_TOPOLOGY = 5 }; // GiCScene::updateCounts
+enum : uint32_t { UPDATE_FULL = 0, UPDATE_TRANSFORM = 1, UPDATE_MATERIAL = 2, UPDATE_VISIBILITY = 3, UPDATE_VERTEX = 4, UPDATE_TOPOLOGY = 5, UPDATE_TLAS = 6 }; // GiCScene::updateCounts
 struct GiCScene : SceneDevice {
   std::mutex mutex;
   uint32_t dirty = DIRTY_ALL;
@@ -398,8 +400,8 @@ struct GiCScene : SceneDevice {
   // a look-ahead window traced under another generation is not served from
   uint64_t generation = 0;
   // syncSceneGeometry, by UPDATE_*: full builds and incremental updates (giCDebugSceneUpdateCounts: the first three; giCDebugSceneVisibilityUpdateCount,
-  // giCDebugSceneVertexUpdateCount, giCDebugSceneTopologyUpdateCount)
-  uint64_t updateCounts[6] = {0, 0, 0, 0, 0, 0};
+  // giCDebugSceneVertexUpdateCount, giCDebugSceneTopologyUpdateCount, giCDebugSceneTlasUpdateCount)
+  uint64_t updateCounts[7] = {0, 0, 0, 0, 0, 0, 0};
   int32_t optVisibilityUpdates = 0; // GI_C_SCENE_OPTION_VISIBILITY_UPDATES: 1 = visibility edits are applied to the resident scene (updateVisibility)
   int32_t optVertexUpdates = 0; // GI_C_SCENE_OPTION_VERTEX_UPDATES: 1 = vertex edits refit the resident tree (updateVertices)
   // DIRTY_BVH was raised by something other than giCSetMeshVisibility / giCSetMeshVertices since the last syncSceneGeometry (raiseRebuild): the rebuild is due
@@ -418,6 +420,8 @@ struct GiCScene : SceneDevice {
   // DIRTY_BVH was raised by giCSetMeshInstanceIds or a count change of giCSetMeshInstanceTransforms on a mesh of the built scene (raiseInstances):
   // syncSceneGeometry lets updateTopology answer it; without the option it turns this into rebuildDue
   bool instancesDue = false;
+  // GI_C_SCENE_OPTION_TLAS_UPDATES: 1 = transform edits of a two-level scene are applied to the resident scene (updateTransformsTwoLevel)
+  int32_t optTlasUpdates = 0;
   std::vector<GiCMesh*> retiredMeshes; // destroyed meshes the resident scene still refers to (GiCMesh::retired): freed by buildScene and with the scene
   ~GiCScene() { for (GiCMesh* m : retiredMeshes) delete m; }
 };
@@ -443,6 +447,7 @@ SceneDevice& sceneDevice(GiCScene* s, uint32_t slot);
 bool usableVertexPositions(const GiCVertex* v, size_t count);  // every position finite and within 1e18 (bvh8.h "Inactive items")
 void nodeBounds(const Node8& n, float box[6]);               // dequantised bounds of a node's children (+ an ulp-scale pad)
 bool instanceUpdatesWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_INSTANCE_UPDATES / GATLING_OPTIONS=instance_updates (with topology updates wanted)
+bool tlasUpdatesWanted(const GiCScene* s);                   // GI_C_SCENE_OPTION_TLAS_UPDATES / GATLING_OPTIONS=tlas_updates
 bool topologyUpdatesWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_TOPOLOGY_UPDATES / GATLING_OPTIONS=topology_updates
 int syncSceneGeometry(GiCScene* s);                          // brings the device scene up to date with the host-side edits (incremental or full build)
 // dirty flags of a material-side edit: DIRTY_MATERIALS alone once the scene / the mesh is part of a built scene (the incremental path), else with DIRTY_BVH

@@ -1,5 +1,5 @@
 // gi_kernels.h -- host-side launch interface of the stage kernels (gi_kernels.hip,
-// gi_trace.hip, gi_shade.hip, gi_aov.hip, gi_patch.hip, gi_refit.hip) and of the fused one (gi_path.hip).
+// gi_trace.hip, gi_shade.hip, gi_aov.hip, gi_patch.hip, gi_refit.hip, gi_tlas.hip) and of the fused one (gi_path.hip).
 #pragma once
 
 #include <type_traits>
@@ -115,6 +115,16 @@ bool gatherShadeRangeOk(uint32_t shadeCount, uint32_t first, uint32_t count);
 bool launchGatherShade(hipStream_t s, TriShade* triShade, uint32_t shadeCount, uint32_t first, uint32_t count, const FVertex* verts, uint32_t vertCount);
 void launchRefitLevel(hipStream_t s, Node8* nodes, uint32_t nodeCount, float* boxes, const RefitRange* ranges, uint32_t rangeCount, uint32_t threads,
     const TriRec* tris, uint32_t triCount, const InstanceRec* instances, uint32_t instanceCount, const TriShade* triShade, uint32_t shadeCount);
+// gi_tlas.hip: the padded world boxes of moved instances of a two-level scene (gi_build.cpp updateTransformsTwoLevel, GI_C_SCENE_OPTION_TLAS_UPDATES).  One
+// 64-byte job per instance: its new o2w, its mesh's BLAS triangles [firstTri, firstTri + faceCount) and its instance index (carried for the host).
+// launchInstBounds runs k_inst_bounds over jobCount x chunksPerJob workgroups (chunksPerJob = instBoundsChunks of the longest job; `partials`: 8 floats per
+// workgroup) and k_inst_finish behind it, which writes 7 words per job to `out`: the padded box (lo xyz, hi xyz) and the status (gi_tlas.h TLAS_STATUS_*,
+// 0 = usable).  Scratch only.  False, and nothing launched: the grid would not fit a launch.
+struct InstBoundsJob { float o2w[12]; uint32_t firstTri, faceCount, instance, pad; };
+constexpr uint32_t kInstBoundsChunk = 4096u;
+uint32_t instBoundsChunks(uint32_t faceCount);
+bool launchInstBounds(hipStream_t s, const InstBoundsJob* jobs, uint32_t jobCount, uint32_t chunksPerJob, const BlasTri* blasTris, uint32_t blasTriCount,
+    float* partials, uint32_t* out);
 void launchSpin(hipStream_t s, unsigned long long ns);             // test hook: occupies a stream for ~ns nanoseconds
 void launchDebugBsdf(hipStream_t s, const MaterialRec* mat, uint32_t shadeClass, uint32_t count, const float* in, float* out);
 void launchDebugSqrt(hipStream_t s, uint32_t first, unsigned long long count, unsigned long long* mismatches); // gi_sqrt against sqrtf over bit patterns

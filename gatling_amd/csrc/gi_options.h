@@ -64,6 +64,8 @@
 //   device_parts_min     4096      topology updates with the device builder on: an appended part of at least this many faces (and more than 128) is built
 //                                  on the device (buildBvh8Device + gi_patch.hip k_place_part), a smaller one by the host (buildPart).  The measured
 //                                  crossover for one part
+//   tlas_updates         -1        -1 = the scene option decides (GI_C_SCENE_OPTION_TLAS_UPDATES), 0 / 1 = transform edits of a two-level scene rebuild it /
+//                                  are applied to the resident scene (gi_build.cpp updateTransformsTwoLevel)
 //   phase_stats          0         counting builds: print k_path's phase split / k_trace_dyn's lane accounting
 #pragma once
 

@@ -380,7 +380,8 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * giCSetMeshVertices, GI_C_SCENE_OPTION_VERTEX_UPDATES, giCDebugSceneVertexUpdateCount, giCDebugRefitBvh and giCDebugSceneRefitCheck, and for
  * GI_C_SCENE_OPTION_TOPOLOGY_UPDATES and giCDebugSceneTopologyUpdateCount, and for GI_C_SCENE_OPTION_RESYNC_REFITS, giCDebugSceneResyncCount,
  * giCDebugGatherShade and giCDebugSceneShadeCheck, and for giCDebugPathLobeStats and giCDebugPathLot, and for GI_C_SCENE_OPTION_INSTANCE_UPDATES,
- * giCDebugSceneInstanceUpdateCount and giCDebugCloneInstance. */
+ * giCDebugSceneInstanceUpdateCount and giCDebugCloneInstance, and for GI_C_SCENE_OPTION_TLAS_UPDATES, giCDebugSceneTlasUpdateCount, giCDebugSceneTlasCheck
+ * and giCDebugInstanceBounds. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -593,6 +594,18 @@ int giCGetRenderStats(const GiCScene* scene, GiCRenderStats* out);
  * depend on the option.  The scene is rebuilt instead for everything GI_C_SCENE_OPTION_TOPOLOGY_UPDATES rebuilds for, for a new count of 0 and for a mesh
  * hidden by the visibility path.  GATLING_OPTIONS=instance_updates=0|1 overrides it (hdGatling sets no scene options).  DESIGN.md section 6. */
 #define GI_C_SCENE_OPTION_INSTANCE_UPDATES 15
+/* [ext] Incremental transform edits on the two-level layout (GI_C_SCENE_OPTION_TWO_LEVEL, or chosen automatically from 2^26 flattened triangles): value 1 = a
+ * giCSetMeshTransform, or a giCSetMeshInstanceTransforms with an unchanged instance count, on a mesh of a built two-level scene is applied to the resident
+ * scene by the next giCRender when nothing else asks for a rebuild: the moved instances' records are re-sent, their world boxes are made on the device from
+ * the mesh's BLAS triangles, the TLAS is built again on the host over the instance boxes and re-sent, and the flat tree that AOVs and giCTraceRays walk is
+ * refitted in device memory; every BLAS stays.  0 = off (default): such an edit rebuilds the scene, as before.  The image does not depend on the option.
+ * The scene is rebuilt instead when: there is no host copy of the scene or GATLING_OPTIONS=incremental=0; fewer than 4 096 triangles are resident; the
+ * scene was built with inactive triangles; the flat tree has no level table (it was built on the device); a moved instance's transform is not finite or
+ * not invertible, or carries a corner of its mesh beyond 1e18 (or to a non-finite value) in object or world space; the new TLAS would be too deep for the
+ * layout's 16-entry stack (a fresh build would leave the two-level layout); the device has no memory for the refit's boxes (32 bytes per node).  A material
+ * edit due in the same render is applied first, by the material update.  GATLING_OPTIONS=tlas_updates=0|1 overrides the option (hdGatling sets no scene
+ * options).  DESIGN.md section 6. */
+#define GI_C_SCENE_OPTION_TLAS_UPDATES 16
 int giCGetLookaheadStats(const GiCScene* scene, GiCLookaheadStats* out);
 int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value);
 /* [ext] closest hit of one ray through the device traversal kernel (parity tests of the BVH8 path).
@@ -688,6 +701,21 @@ int giCDebugCloneInstance(const GiCVertex* vertices, uint32_t vertexCount, const
  * over the WHOLE arrays (a store outside an edited range is seen).  Returns the number of shading records whose 160 bytes differ plus the vertex records
  * whose 48 bytes differ (0), <0 on error; outRecords: shading records compared (0 for a scene within LDS, which keeps none). */
 int giCDebugSceneShadeCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t* outRecords);
+/* [ext] [debug] how often the scene was brought up to date by a transform update of the two-level layout (GI_C_SCENE_OPTION_TLAS_UPDATES); not counted in
+ * giCDebugSceneUpdateCounts either. */
+int giCDebugSceneTlasUpdateCount(const GiCScene* scene, uint64_t* outCount);
+/* [ext] [debug] the two-level arrays resident on device `deviceIndex` of a scene rendered at least once -- TLAS nodes, TLAS items, per-instance traversal
+ * records, BLAS nodes, BLAS triangles -- downloaded and compared with the arrays the scene build's own code makes anew from the scene's current meshes.
+ * Returns the number of records that differ bytewise (0 after a build as after every update in place), <0 on error.  out[0]: 1 when the two-level layout is
+ * in use (0: nothing was compared), [1] instances, [2] TLAS nodes, [3] TLAS depth. */
+int giCDebugSceneTlasCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t* out /* 4 */);
+/* [ext] [debug] device check of the kernels that make the world boxes of moved instances (gi_tlas.hip k_inst_bounds / k_inst_finish): the mesh (`vertices`,
+ * `faces`: 3 indices per face) under each of the `xformCount` instance transforms (16 floats each, USD row vectors).  outBoxes6 (6 floats per transform: min
+ * xyz, max xyz, padded) and outStatus (one word per transform, 0 = usable; bits: 1 a corner unusable in object space, 2 in world space, 4 a flattened
+ * triangle the builders would leave out) receive the device's results; either may be null.  Returns the number of (box, status) pairs that differ bytewise
+ * from the host form of the same arithmetic (0 is the contract), <0 on error (no device, a null array, an index outside the vertices). */
+int giCDebugInstanceBounds(const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, const float* xforms16, uint32_t xformCount,
+                           float* outBoxes6, uint32_t* outStatus);
 /* [ext] what the last scene sync derived from the visible meshes' materials, the state that picks a render's kernel variants: out[0] the material classes in
  * use (one bit each), [1] those with a textured material, [2] and [3] the same per shade class, [4] 1 when some visible triangle has cutout opacity.  Host
  * only: no device work. */
