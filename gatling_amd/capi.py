@@ -29,6 +29,7 @@ OPTION_TOPOLOGY_UPDATES = 13  # 1: meshes created and destroyed after the build 
 OPTION_RESYNC_REFITS = 14  # 1 (with options 12 and 13): a destroyed and a created mesh with the same faces become a vertex refit of the resident records instead of a retire + append (include/gi_c.h); 0 = off (default)
 OPTION_INSTANCE_UPDATES = 15  # 1 (with option 13): new instance ids or another instance count of a built mesh are applied to the resident scene instead of rebuilding it (include/gi_c.h); 0 = off (default)
 OPTION_TLAS_UPDATES = 16  # 1: transform edits of a built two-level scene (OPTION_TWO_LEVEL) are applied to the resident scene -- moved instances' records, a new TLAS, a refit of the flat tree -- instead of rebuilding it (include/gi_c.h); 0 = off (default)
+OPTION_BLAS_UPDATES = 17  # 1: vertex edits of a built two-level scene are applied to the resident scene -- the mesh's BLAS refitted on the device, a new TLAS, a refit of the flat tree -- instead of rebuilding it; read only with OPTION_VERTEX_UPDATES wanted (include/gi_c.h); 0 = off (default)
 OPTION_BVH_BUILD = 9  # 0 = host BVH builder (default), 1 = device builder (flat-layout scenes of more than 128 triangles)
 
 
@@ -176,6 +177,9 @@ SYMBOLS = [
     ("giCDebugSceneInstanceUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugCloneInstance", C.c_int, [_P, _U, _P, _U, _I, _FP, _FP]),
     ("giCDebugSceneTlasUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugSceneTlasCheck", C.c_int, [_P, _U, C.POINTER(C.c_uint32)]),
     ("giCDebugInstanceBounds", C.c_int, [_P, _U, _P, _U, _FP, _U, _FP, C.POINTER(C.c_uint32)]),
+    ("giCDebugSceneBlasUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugSceneBlasCheck", C.c_int, [_P, _U, C.POINTER(C.c_uint32)]),
+    ("giCDebugBlasRefit", C.c_int, [_P, _P, _U, _P, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("giCDebugBlasRefitHost", C.c_int, [_P, _P, _U, _P, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("giCDebugPathWalkStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugPathLobeStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugPathLot", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
@@ -266,6 +270,35 @@ def debug_instance_bounds(vertices, faces, xforms):
     if n < 0:
         raise GiError("giCDebugInstanceBounds failed: " + L.giCGetLastError().decode())
     return int(n), boxes, status
+
+
+def debug_blas_refit(vertices_a, vertices_b, faces, host_only=False):
+    """giCDebugBlasRefit: one BLAS of the two-level layout is built over the mesh with points `vertices_a` (VERTEX_DTYPE; `faces`: n x 3 indices) and brought
+    to `vertices_b` by the device kernels (k_blas_tris / k_blas_refit_level) and by the host form of the same arithmetic.  Returns (differing, nodes,
+    violations): the node and record bytes that differ between device and host -- with the same positions in both, plus those that differ from the build's
+    -- (0 is the contract), the BLAS's node count, and the violations of the conservative check (0).  host_only: giCDebugBlasRefitHost, the host form alone
+    (no device; `differing` then counts topology bytes that left the build's, or with the same positions every byte that did)."""
+    from .scene import VERTEX_DTYPE
+    L = load_library()
+    a = np.ascontiguousarray(vertices_a, VERTEX_DTYPE)
+    b = np.ascontiguousarray(vertices_b, VERTEX_DTYPE)
+    if len(a) != len(b):
+        raise ValueError("debug_blas_refit: both point sets must have one entry per vertex")
+    f = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3)
+    nodes, violations = C.c_uint32(0), C.c_uint32(0)
+    fn = L.giCDebugBlasRefitHost if host_only else L.giCDebugBlasRefit
+    n = fn(a.ctypes.data, b.ctypes.data, len(a), f.ctypes.data, len(f), C.byref(nodes), C.byref(violations))
+    if n < 0:
+        raise GiError("giCDebugBlasRefit failed: " + L.giCGetLastError().decode())
+    return int(n), int(nodes.value), int(violations.value)
+
+
+class BlasCheck(int):
+    """Scene.blas_check's answer: differences plus conservative violations as an int, with what the hook reports beside it."""
+    two_level = 0
+    blas_nodes = 0
+    violations = 0
+    blas_tris = 0
 
 
 class TlasCheck(int):
@@ -437,6 +470,26 @@ class Scene:
         if self.L.giCDebugSceneTlasUpdateCount(self.handle, C.byref(n)) != GI_C_OK:
             raise GiError("giCDebugSceneTlasUpdateCount failed")
         return int(n.value)
+
+    def blas_update_count(self) -> int:
+        """giCDebugSceneBlasUpdateCount: how often the scene was brought up to date by a vertex update of the two-level layout (OPTION_BLAS_UPDATES; counted
+        neither in update_counts() nor in vertex_update_count())."""
+        n = C.c_uint64(0)
+        if self.L.giCDebugSceneBlasUpdateCount(self.handle, C.byref(n)) != GI_C_OK:
+            raise GiError("giCDebugSceneBlasUpdateCount failed")
+        return int(n.value)
+
+    def blas_check(self, device: int = 0) -> "BlasCheck":
+        """giCDebugSceneBlasCheck: the two-level arrays resident on a device against the current meshes after vertex updates in place -- BLAS triangles, BLAS
+        nodes against the host form of the refit, TLAS, items and per-instance records against a fresh build.  Returns differences + conservative violations
+        (0) as a BlasCheck: .two_level (1 when the layout is in use), .blas_nodes, .violations (the conservative check alone), .blas_tris."""
+        out = (C.c_uint32 * 4)()
+        v = self.L.giCDebugSceneBlasCheck(self.handle, device, out)
+        if v < 0:
+            raise GiError("giCDebugSceneBlasCheck failed: " + self.L.giCGetLastError().decode())
+        r = BlasCheck(v)
+        r.two_level, r.blas_nodes, r.violations, r.blas_tris = int(out[0]), int(out[1]), int(out[2]), int(out[3])
+        return r
 
     def tlas_check(self, device: int = 0) -> "TlasCheck":
         """giCDebugSceneTlasCheck: the two-level arrays resident on a device against the arrays the scene build's code makes anew from the current meshes.

@@ -4,6 +4,7 @@
 #include "gi_bvh_build.h"
 #include "gi_refit.h"
 #include "gi_tlas.h"
+#include "gi_blas.h"
 #include "gi_pack.h"
 
 #include <unordered_map>
@@ -293,6 +294,32 @@ static void deriveSceneClasses(GiCScene* s, const SceneHost& H, bool newTree)
 // Two-level layout (SceneView::tlasNodes ...): built next to the flat BVH for instanced scenes that do not fit LDS.  The flat
 // arrays stay (k_shade reads the hit's TriRec, k_aov / giCTraceRays traverse them); the two-level ones are what k_trace_dyn2 walks,
 // and they are small: one BLAS per MESH instead of one subtree per instance, so traversal stays in the caches.
+// The BLAS of one mesh (buildTwoLevel; giCDebugBlasRefit): a tree over the padded object-space boxes of its faces.  A face with an unusable corner keeps an
+// inverted box: the builder leaves it out, and it does not widen mlo / mhi, the union of the usable faces' boxes
+static void buildMeshBlas(const GiCVertex* vertices, const GiCFace* faces, size_t nf, Bvh8& b, std::vector<uint32_t>& order, float mlo[3], float mhi[3])
+{
+  std::vector<float> boxes(nf * 6);
+  for (int a = 0; a < 3; a++) { mlo[a] = 3.0e38f; mhi[a] = -3.0e38f; }
+  for (size_t f = 0; f < nf; f++) {
+    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+    bool faceOk = true; // (an unusable face keeps an inverted box: the builder leaves it out, and it must not widen the mesh magnitude below)
+    for (int k = 0; k < 3; k++) { const float* p = vertices[faces[f].v_i[k]].pos;
+        for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], p[a]); hi[a] = std::max(hi[a], p[a]); faceOk = faceOk && usableCoordinate(p[a]); } }
+    if (faceOk) tlas_pad_box(lo, hi); else for (int a = 0; a < 3; a++) { lo[a] = 3.0e38f; hi[a] = -3.0e38f; }
+    for (int a = 0; a < 3; a++) { boxes[6 * f + a] = lo[a]; boxes[6 * f + 3 + a] = hi[a]; }
+    if (faceOk) for (int a = 0; a < 3; a++) { mlo[a] = std::min(mlo[a], lo[a]); mhi[a] = std::max(mhi[a], hi[a]); }
+  }
+  buildBvh8Boxes(boxes.data(), nf, b, order);
+}
+// ... and its record of face f, as the builder's order places it
+static BlasTri makeBlasTri(const GiCVertex* vertices, const GiCFace* faces, uint32_t f)
+{
+  BlasTri bt{};
+  memcpy(bt.p0, vertices[faces[f].v_i[0]].pos, 12); memcpy(bt.p1, vertices[faces[f].v_i[1]].pos, 12); memcpy(bt.p2, vertices[faces[f].v_i[2]].pos, 12);
+  bt.prim = f;
+  return bt;
+}
+
 template <class MB>
 int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vector<InstanceRec>& instances, size_t flatTris, size_t flatNodes,
     TwoLevelHost& out)
@@ -313,36 +340,21 @@ int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vec
   if (want <= 0 || instances.empty() || !beyondLds) return GI_C_OK;
   std::vector<Node8> blasNodes; std::vector<BlasTri> blasTris; std::vector<InstTrav> instTrav(instances.size());
   uint32_t blasDepth = 0;
-  std::vector<float> instBoxes(instances.size() * 6); std::vector<uint32_t> meshBlasTri(meshBuilds.size(), 0u);
+  std::vector<float> instBoxes(instances.size() * 6); std::vector<uint32_t> meshBlasTri(meshBuilds.size(), 0u), meshBlasNode(meshBuilds.size(), 0u);
+  std::vector<std::vector<uint32_t>> meshBlasLevels(meshBuilds.size());
   // (gi_tlas.h: the point transform, the pad, the status rule and the InstTrav record are shared with the transform update in place and its kernels)
   auto padBox = [](float* lo, float* hi) { tlas_pad_box(lo, hi); };
   for (const MB& mb : meshBuilds) {
     if (mb.instCount == 0) continue;
     const GiCMesh* m = mb.m;
     const size_t nf = m->faces.size();
-    std::vector<float> boxes(nf * 6);
-    float mlo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, mhi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-    for (size_t f = 0; f < nf; f++) {
-      float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-      bool faceOk = true; // (an unusable face keeps an inverted box: the builder leaves it out, and it must not widen the mesh magnitude below)
-      for (int k = 0; k < 3; k++) { const float* p = m->vertices[m->faces[f].v_i[k]].pos;
-          for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], p[a]); hi[a] = std::max(hi[a], p[a]); faceOk = faceOk && usableCoordinate(p[a]); } }
-      if (faceOk) padBox(lo, hi); else for (int a = 0; a < 3; a++) { lo[a] = 3.0e38f; hi[a] = -3.0e38f; }
-      for (int a = 0; a < 3; a++) { boxes[6 * f + a] = lo[a]; boxes[6 * f + 3 + a] = hi[a]; }
-      if (faceOk) for (int a = 0; a < 3; a++) { mlo[a] = std::min(mlo[a], lo[a]); mhi[a] = std::max(mhi[a], hi[a]); }
-    }
+    float mlo[3], mhi[3];
     Bvh8 b; std::vector<uint32_t> order;
-    buildBvh8Boxes(boxes.data(), nf, b, order);
+    buildMeshBlas(m->vertices.data(), m->faces.data(), nf, b, order, mlo, mhi);
     const uint32_t nodeBase = (uint32_t)blasNodes.size(), triBase = (uint32_t)blasTris.size();
-    if (mb.meshIdx < meshBlasTri.size()) meshBlasTri[mb.meshIdx] = triBase;
+    if (mb.meshIdx < meshBlasTri.size()) { meshBlasTri[mb.meshIdx] = triBase; meshBlasNode[mb.meshIdx] = nodeBase; meshBlasLevels[mb.meshIdx] = b.levelStart; }
     for (Node8 n : b.nodes) { n.childBase += nodeBase; n.triBase += triBase; blasNodes.push_back(n); }
-    for (uint32_t f : order) {
-      BlasTri bt{};
-      memcpy(bt.p0, m->vertices[m->faces[f].v_i[0]].pos, 12); memcpy(bt.p1, m->vertices[m->faces[f].v_i[1]].pos, 12);
-          memcpy(bt.p2, m->vertices[m->faces[f].v_i[2]].pos, 12);
-      bt.prim = f;
-      blasTris.push_back(bt);
-    }
+    for (uint32_t f : order) blasTris.push_back(makeBlasTri(m->vertices.data(), m->faces.data(), f));
     blasDepth = std::max(blasDepth, b.maxDepth);
     // object-space magnitude the transformed ray's rounding error scales with inside this mesh (see wave_step2)
     const float extent = (std::fabs(mlo[0]) + std::fabs(mlo[1]) + std::fabs(mlo[2])) + (std::fabs(mhi[0]) + std::fabs(mhi[1]) + std::fabs(mhi[2]));
@@ -386,6 +398,7 @@ int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vec
                                               tlas.nodes.size(), instances.size(), blasNodes.size(), blasTris.size(), flatNodes, flatTris);
   out.tlasNodes.swap(tlas.nodes); out.tlasItems.swap(tlasItems); out.blasNodes.swap(blasNodes); out.blasTris.swap(blasTris); out.instTrav.swap(instTrav);
   out.instBoxes.swap(instBoxes); out.meshBlasTri.swap(meshBlasTri); out.tlasDepth = tlas.maxDepth; out.blasDepth = blasDepth;
+  out.meshBlasNode.swap(meshBlasNode); out.meshBlasLevels.swap(meshBlasLevels);
   return GI_C_OK;
 }
 
@@ -1175,9 +1188,18 @@ static bool planRefitLevels(const std::vector<RefitUnit>& units, uint32_t nodeCo
   return true;
 }
 
+// GI_C_SCENE_OPTION_BLAS_UPDATES / GATLING_OPTIONS=blas_updates: vertex edits of a two-level scene are applied in place (updateVerticesTwoLevel below)
+bool blasUpdatesWanted(const GiCScene* s)
+{
+  const long o = optionValue("blas_updates", -1);
+  return o >= 0 ? o == 1 : s->optBlasUpdates == 1;
+}
+static int updateVerticesTwoLevel(GiCScene* s, SceneHost& H, bool& handled, UpdateCost& cost);
+
 static int updateVertices(GiCScene* s, bool& handled, UpdateCost& cost)
 {
   SceneHost* host = incrementalHost(s);
+  if (host && s->twoLevel && blasUpdatesWanted(s)) return updateVerticesTwoLevel(s, *host, handled, cost);
   if (!host || s->twoLevel || !host->shadePacked || s->triCount < kIncrementalMinTris) return GI_C_OK; // (the floor: resident triangles)
   SceneHost& H = *host;
   if (s->stats.inactiveTriangleCount != 0u) return GI_C_OK;
@@ -1944,9 +1966,125 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
 // builders would leave out), a TLAS too deep for the layout's stack (2 x TLAS depth + BLAS depth + 1 > 16: a fresh build would leave the two-level layout),
 // out of device memory for the scratch or the refit's boxes (a later device of several: the earlier ones are committed, and buildScene sends everything anew).
 // ---------------------------------------------------------------------------------------------------------------
+// What the updates in place of the two-level layout share behind their bounds jobs (updateTransformsTwoLevel, updateVerticesTwoLevel): the padded world
+// boxes and statuses of the jobs' instances from the primary device, the TLAS over all boxes with the decision, the plan of the flat tree's refit, the
+// per-device commit and the host copies.
+struct TwoLevelEdit {
+  std::vector<float> boxes; Bvh8 tlas; std::vector<uint32_t> tlasItems; // all instance boxes with the jobs' new ones; the TLAS over them
+  std::vector<uint32_t> editedOfInstance; std::vector<std::pair<uint32_t, uint32_t>> runs; // the jobs' instances: one word each; (first, count) of consecutive ones
+  std::vector<RefitRange> ranges; std::vector<RefitLevel> levels; // the flat tree's refit
+  double tlasMs = 0.0;
+};
+struct FlatRefitScratch {
+  DeviceBuffer<float> boxes; DeviceBuffer<uint32_t> edited; DeviceBuffer<RefitRange> ranges;
+  int alloc(uint32_t nodeCount, const TwoLevelEdit& E)
+  { const int a = boxes.alloc((size_t)nodeCount * 8u), b = a ? a : edited.alloc(E.editedOfInstance.size()); return b ? b : ranges.alloc(E.ranges.size()); }
+  void release() { boxes.release(); edited.release(); ranges.release(); }
+};
+
+// primary device, scratch only: padded boxes and statuses, 7 words per job.  scratchTris: the BLAS triangles the jobs name (a vertex edit: the edited meshes'
+// records with their new points, which are not resident yet), or null for the resident ones
+static int instanceBoundsOnPrimary(GiCScene* s, const std::vector<InstBoundsJob>& jobs, uint32_t chunksPerJob, const std::vector<BlasTri>* scratchTris,
+    std::vector<uint32_t>& result, bool& outOfMemory, const char* what)
+{
+  const uint32_t jobCount = (uint32_t)jobs.size();
+  result.assign((size_t)jobCount * 7u, 0u);
+  return onSceneDevices(s, 1u, [&](SceneDevice& D, hipStream_t st) -> int {
+    const size_t triCount = scratchTris ? scratchTris->size() : s->host->two.blasTris.size();
+    if (!scratchTris && D.dBlasTris.count < triCount) { setError("internal: the device holds less than the scene"); return GI_C_ERROR; }
+    DeviceBuffer<InstBoundsJob> dJobs; DeviceBuffer<float> dPartials; DeviceBuffer<uint32_t> dOut; DeviceBuffer<BlasTri> dScratch;
+    auto releaseAll = [&] { dJobs.release(); dPartials.release(); dOut.release(); dScratch.release(); };
+    const int a = dJobs.alloc(jobCount), b = a ? a : dPartials.alloc((size_t)jobCount * chunksPerJob * 8u), c0 = b ? b : dOut.alloc(result.size());
+    const int c = c0 ? c0 : (scratchTris && !scratchTris->empty() ? dScratch.alloc(scratchTris->size()) : GI_C_OK);
+    if (c != GI_C_OK) { releaseAll(); if (c == GI_C_OUT_OF_MEMORY_INTERNAL) { outOfMemory = true; return DEVICE_BUILD_FALLBACK; } return GI_C_ERROR; }
+    int rc = GI_C_OK;
+    if (hipMemcpyAsync(dJobs.ptr, jobs.data(), jobs.size() * sizeof(InstBoundsJob), hipMemcpyHostToDevice, st) != hipSuccess) rc = GI_C_ERROR;
+    if (rc == GI_C_OK && dScratch.ptr && hipMemcpyAsync(dScratch.ptr, scratchTris->data(), scratchTris->size() * sizeof(BlasTri), hipMemcpyHostToDevice, st) != hipSuccess)
+      rc = GI_C_ERROR;
+    const BlasTri* tris = scratchTris ? dScratch.ptr : D.dBlasTris.ptr;
+    if (rc == GI_C_OK && !launchInstBounds(st, dJobs.ptr, jobCount, chunksPerJob, tris, (uint32_t)triCount, dPartials.ptr, dOut.ptr)) rc = GI_C_ERROR; // (asked by the caller)
+    if (rc == GI_C_OK && (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(result.data(), dOut.ptr, result.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess)) rc = GI_C_ERROR;
+    if (hipStreamSynchronize(st) != hipSuccess) rc = GI_C_ERROR;
+    if (rc != GI_C_OK) setError(std::string(what) + ": instance bounds failed on the device");
+    releaseAll();
+    return rc;
+  });
+}
+
+// boxes -> TLAS -> decision -> the flat refit's plan.  False: the edit declines (every job's instance must be usable; the TLAS over all boxes must stay
+// within the stack rule)
+static bool planTwoLevelEdit(const GiCScene* s, const SceneHost& H, const std::vector<InstBoundsJob>& jobs, const std::vector<uint32_t>& result, const char* what,
+    bool timing, TwoLevelEdit& E)
+{
+  const TwoLevelHost& T = H.two;
+  const uint32_t jobCount = (uint32_t)jobs.size(), instanceCount = (uint32_t)H.instances.size();
+  for (uint32_t k = 0; k < jobCount; k++)
+    if (result[7u * k + 6u] != 0u) {
+      if (timing) fprintf(stderr, "[gatling_gi] %s: instance %u is not usable after the edit (status %u); the scene is rebuilt\n", what, jobs[k].instance,
+                          result[7u * k + 6u]);
+      return false;
+    }
+  E.boxes = T.instBoxes;
+  for (uint32_t k = 0; k < jobCount; k++) memcpy(&E.boxes[6u * (size_t)jobs[k].instance], &result[7u * (size_t)k], 24);
+  const double t1 = nowMs();
+  buildBvh8Boxes(E.boxes.data(), instanceCount, E.tlas, E.tlasItems);
+  E.tlasMs = nowMs() - t1;
+  if (2u * E.tlas.maxDepth + T.blasDepth + 1u > 16u) {
+    if (timing) fprintf(stderr, "[gatling_gi] %s: the new TLAS is too deep for the 16-entry stack; the scene is rebuilt\n", what);
+    return false;
+  }
+  E.editedOfInstance.assign(instanceCount, 0u);
+  for (uint32_t k = 0; k < jobCount; k++) E.editedOfInstance[jobs[k].instance] = 1u;
+  for (uint32_t i = 0; i < instanceCount; i++)
+    if (E.editedOfInstance[i]) { if (!E.runs.empty() && E.runs.back().first + E.runs.back().second == i) E.runs.back().second++; else E.runs.emplace_back(i, 1u); }
+  std::vector<RefitUnit> units{RefitUnit{0u, &H.bvh.levelStart}};
+  return planRefitLevels(units, s->nodeCount, E.ranges, E.levels); // (false cannot happen: the levels of a tree inside the node array)
+}
+
+// one device, behind whatever the edit itself sent on `st`: the instances' records in runs (`instances` may be null: a vertex edit changes none), the TLAS,
+// k_refit_tris over the flat records of the edited instances and k_refit_level over the whole flat tree; the primary reads the flat root back.  Not
+// synchronised: the caller drains the stream and releases `scratch`
+static int commitTwoLevelEdit(GiCScene* s, const SceneHost& H, SceneDevice& D, hipStream_t st, const TwoLevelEdit& E, const std::vector<InstanceRec>* instances,
+    const std::vector<InstTrav>& instTrav, FlatRefitScratch& scratch, Node8& root, const char* what)
+{
+  const uint32_t instanceCount = (uint32_t)H.instances.size(), shadeCount = (uint32_t)H.triShade.size();
+  int rc = GI_C_OK;
+  auto copy = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    if (rc == GI_C_OK && bytes && hipMemcpyAsync(dst, src, bytes, kind, st) != hipSuccess) { setError(std::string(what) + ": copy failed"); rc = GI_C_ERROR; } };
+  for (const auto& r : E.runs) {
+    if (instances) copy(D.dInstances.ptr + r.first, &(*instances)[r.first], (size_t)r.second * sizeof(InstanceRec), hipMemcpyHostToDevice);
+    copy(D.dInstTrav.ptr + r.first, &instTrav[r.first], (size_t)r.second * sizeof(InstTrav), hipMemcpyHostToDevice);
+  }
+  if (rc == GI_C_OK && (D.dTlasNodes.upload(E.tlas.nodes, st) || D.dTlasItems.upload(E.tlasItems, st))) rc = GI_C_ERROR;
+  copy(scratch.edited.ptr, E.editedOfInstance.data(), E.editedOfInstance.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+  copy(scratch.ranges.ptr, E.ranges.data(), E.ranges.size() * sizeof(RefitRange), hipMemcpyHostToDevice);
+  if (rc == GI_C_OK) {
+    launchRefitTris(st, D.dTris.ptr, s->triCount, D.dInstances.ptr, instanceCount, scratch.edited.ptr, D.dTriShade.ptr, shadeCount);
+    for (const RefitLevel& lv : E.levels) launchRefitLevel(st, D.dNodes.ptr, s->nodeCount, scratch.boxes.ptr, scratch.ranges.ptr + lv.first, lv.ranges, lv.threads,
+        D.dTris.ptr, s->triCount, D.dInstances.ptr, instanceCount, D.dTriShade.ptr, shadeCount);
+    if (hipGetLastError() != hipSuccess) { setError(std::string(what) + ": launch failed"); rc = GI_C_ERROR; }
+  }
+  if (D.slot == 0u) copy(&root, D.dNodes.ptr, sizeof(Node8), hipMemcpyDeviceToHost); // (the refit is deterministic: every device holds the same bytes)
+  return rc;
+}
+
+// the host copies behind a committed edit: the two-level arrays, the scene bounds; the flat host tree is dropped as after a vertex refit
+static void finishTwoLevelEdit(GiCScene* s, SceneHost& H, TwoLevelEdit& E, std::vector<InstTrav>& instTrav, const Node8& root)
+{
+  TwoLevelHost& T = H.two;
+  T.instTrav.swap(instTrav); T.instBoxes.swap(E.boxes); T.tlasNodes.swap(E.tlas.nodes); T.tlasItems.swap(E.tlasItems); T.tlasDepth = E.tlas.maxDepth;
+  setSceneBounds(s, std::vector<Node8>{root});
+  if (!H.hostTreeDropped) {
+    std::vector<Node8>().swap(H.bvh.nodes); std::vector<TriRec>().swap(H.bvh.tris); std::vector<int32_t>().swap(H.triFaceId);
+    H.hostTreeDropped = true;
+  }
+}
+
 static int updateTransformsTwoLevel(GiCScene* s, SceneHost& H, bool& handled, UpdateCost& cost)
 {
   TwoLevelHost& T = H.two;
+  const char* const what = "transform update (two-level)";
   const uint32_t instanceCount = (uint32_t)H.instances.size(), shadeCount = (uint32_t)H.triShade.size();
   if (s->triCount < kIncrementalMinTris || !H.shadePacked || s->stats.inactiveTriangleCount != 0u) return GI_C_OK; // (the floor: resident triangles)
   if (H.deviceBuilt || H.partitioned || H.bvh.levelStart.size() < 2u || H.bvh.levelStart.back() != s->nodeCount) return GI_C_OK;
@@ -1980,86 +2118,34 @@ static int updateTransformsTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Up
   }
   if ((uint64_t)jobCount * chunksPerJob >= (1ull << 31)) return GI_C_OK; // (more workgroups than a launch takes)
   // --- primary device, scratch only: padded boxes and statuses
-  std::vector<uint32_t> result((size_t)jobCount * 7u);
+  std::vector<uint32_t> result;
   bool outOfMemory = false;
-  int rcDev = onSceneDevices(s, 1u, [&](SceneDevice& D, hipStream_t st) -> int {
-    if (D.dBlasTris.count < T.blasTris.size()) { setError("internal: the device holds less than the scene"); return GI_C_ERROR; }
-    DeviceBuffer<InstBoundsJob> dJobs; DeviceBuffer<float> dPartials; DeviceBuffer<uint32_t> dOut;
-    auto releaseAll = [&] { dJobs.release(); dPartials.release(); dOut.release(); };
-    const int a = dJobs.alloc(jobCount), b = a ? a : dPartials.alloc((size_t)jobCount * chunksPerJob * 8u), c = b ? b : dOut.alloc(result.size());
-    if (c != GI_C_OK) { releaseAll(); if (c == GI_C_OUT_OF_MEMORY_INTERNAL) { outOfMemory = true; return DEVICE_BUILD_FALLBACK; } return GI_C_ERROR; }
-    int rc = GI_C_OK;
-    if (hipMemcpyAsync(dJobs.ptr, jobs.data(), jobs.size() * sizeof(InstBoundsJob), hipMemcpyHostToDevice, st) != hipSuccess) rc = GI_C_ERROR;
-    if (rc == GI_C_OK && !launchInstBounds(st, dJobs.ptr, jobCount, chunksPerJob, D.dBlasTris.ptr, (uint32_t)T.blasTris.size(), dPartials.ptr, dOut.ptr)) rc = GI_C_ERROR; // (asked above)
-    if (rc == GI_C_OK && (hipGetLastError() != hipSuccess ||
-        hipMemcpyAsync(result.data(), dOut.ptr, result.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess)) rc = GI_C_ERROR;
-    if (hipStreamSynchronize(st) != hipSuccess) rc = GI_C_ERROR;
-    if (rc != GI_C_OK) setError("transform update (two-level): instance bounds failed on the device");
-    releaseAll();
-    return rc;
-  });
+  int rcDev = instanceBoundsOnPrimary(s, jobs, chunksPerJob, nullptr, result, outOfMemory, what);
   if (rcDev == DEVICE_BUILD_FALLBACK && outOfMemory) return GI_C_OK;
   if (rcDev != GI_C_OK) return GI_C_ERROR;
-  // --- the decision: every moved instance usable; the TLAS over all boxes within the stack rule
-  for (uint32_t k = 0; k < jobCount; k++)
-    if (result[7u * k + 6u] != 0u) {
-      if (timing) fprintf(stderr, "[gatling_gi] transform update (two-level): instance %u is not usable where it moved (status %u); the scene is rebuilt\n",
-                          jobs[k].instance, result[7u * k + 6u]);
-      return GI_C_OK;
-    }
-  std::vector<float> boxes(T.instBoxes);
-  for (uint32_t k = 0; k < jobCount; k++) memcpy(&boxes[6u * (size_t)jobs[k].instance], &result[7u * (size_t)k], 24);
+  // --- the decision: every moved instance usable; the TLAS over all boxes within the stack rule; the flat refit's plan
   const double t1 = nowMs();
-  Bvh8 tlas; std::vector<uint32_t> tlasItems;
-  buildBvh8Boxes(boxes.data(), instanceCount, tlas, tlasItems);
+  TwoLevelEdit E;
+  if (!planTwoLevelEdit(s, H, jobs, result, what, timing, E)) return GI_C_OK;
   const double t2 = nowMs();
-  if (2u * tlas.maxDepth + T.blasDepth + 1u > 16u) {
-    if (timing) fprintf(stderr, "[gatling_gi] transform update (two-level): the new TLAS is too deep for the 16-entry stack; the scene is rebuilt\n");
-    return GI_C_OK;
-  }
-  // --- the new records, the flat refit's plan
+  // --- the new records
   std::vector<InstanceRec> instances(H.instances); std::vector<InstTrav> instTrav(T.instTrav);
-  std::vector<uint32_t> editedOfInstance(instanceCount, 0u);
   for (uint32_t k = 0; k < jobCount; k++) {
     const uint32_t i = jobs[k].instance;
     const InstTrav& was = T.instTrav[i]; // (the mesh's constants: a transform changes none; matFlags is the last material update's)
     instances[i] = moved[k]; instTrav[i] = tlasMakeInstTrav(moved[k], was.blasRoot, was.triBase, was.matFlags, was.slack);
-    editedOfInstance[i] = 1u;
   }
-  std::vector<std::pair<uint32_t, uint32_t>> runs; // (first, count) of consecutive moved instances
-  for (uint32_t i = 0; i < instanceCount; i++)
-    if (editedOfInstance[i]) { if (!runs.empty() && runs.back().first + runs.back().second == i) runs.back().second++; else runs.emplace_back(i, 1u); }
-  std::vector<RefitUnit> units{RefitUnit{0u, &H.bvh.levelStart}};
-  std::vector<RefitRange> ranges; std::vector<RefitLevel> levels;
-  if (!planRefitLevels(units, s->nodeCount, ranges, levels)) return GI_C_OK; // (cannot happen: the levels of a tree inside the node array)
   // --- every device of the scene, on its own stream.  The temporaries are allocated before anything resident changes
   Node8 root{}; size_t bytesSent = 0;
   rcDev = onSceneDevices(s, residentDeviceCount(s), [&](SceneDevice& D, hipStream_t st) -> int {
     if (D.dTris.count < s->triCount || D.dNodes.count < s->nodeCount || D.dInstances.count < instanceCount || D.dInstTrav.count < instanceCount ||
         D.dTriShade.count < shadeCount) { setError("internal: the device holds less than the scene"); return GI_C_ERROR; }
-    DeviceBuffer<float> dBoxes; DeviceBuffer<uint32_t> dEdited; DeviceBuffer<RefitRange> dRanges;
-    auto releaseAll = [&] { dBoxes.release(); dEdited.release(); dRanges.release(); };
-    const int a = dBoxes.alloc((size_t)s->nodeCount * 8u), b = a ? a : dEdited.alloc(editedOfInstance.size()), c = b ? b : dRanges.alloc(ranges.size());
-    if (c != GI_C_OK) { releaseAll(); if (c == GI_C_OUT_OF_MEMORY_INTERNAL) { outOfMemory = true; return DEVICE_BUILD_FALLBACK; } return GI_C_ERROR; }
-    int rc = GI_C_OK;
-    auto copy = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
-      if (rc == GI_C_OK && bytes && hipMemcpyAsync(dst, src, bytes, kind, st) != hipSuccess) { setError("transform update (two-level): copy failed"); rc = GI_C_ERROR; } };
-    for (const auto& r : runs) {
-      copy(D.dInstances.ptr + r.first, &instances[r.first], (size_t)r.second * sizeof(InstanceRec), hipMemcpyHostToDevice);
-      copy(D.dInstTrav.ptr + r.first, &instTrav[r.first], (size_t)r.second * sizeof(InstTrav), hipMemcpyHostToDevice);
-    }
-    if (rc == GI_C_OK && (D.dTlasNodes.upload(tlas.nodes, st) || D.dTlasItems.upload(tlasItems, st))) rc = GI_C_ERROR;
-    copy(dEdited.ptr, editedOfInstance.data(), editedOfInstance.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    copy(dRanges.ptr, ranges.data(), ranges.size() * sizeof(RefitRange), hipMemcpyHostToDevice);
-    if (rc == GI_C_OK) {
-      launchRefitTris(st, D.dTris.ptr, s->triCount, D.dInstances.ptr, instanceCount, dEdited.ptr, D.dTriShade.ptr, shadeCount);
-      for (const RefitLevel& lv : levels) launchRefitLevel(st, D.dNodes.ptr, s->nodeCount, dBoxes.ptr, dRanges.ptr + lv.first, lv.ranges, lv.threads, D.dTris.ptr,
-          s->triCount, D.dInstances.ptr, instanceCount, D.dTriShade.ptr, shadeCount);
-      if (hipGetLastError() != hipSuccess) { setError("transform update (two-level): launch failed"); rc = GI_C_ERROR; }
-    }
-    if (D.slot == 0u) copy(&root, D.dNodes.ptr, sizeof(Node8), hipMemcpyDeviceToHost); // (the refit is deterministic: every device holds the same bytes)
+    FlatRefitScratch scratch;
+    const int c = scratch.alloc(s->nodeCount, E);
+    if (c != GI_C_OK) { scratch.release(); if (c == GI_C_OUT_OF_MEMORY_INTERNAL) { outOfMemory = true; return DEVICE_BUILD_FALLBACK; } return GI_C_ERROR; }
+    int rc = commitTwoLevelEdit(s, H, D, st, E, &instances, instTrav, scratch, root, what);
     if (hipStreamSynchronize(st) != hipSuccess && rc == GI_C_OK) { setError("transform update (two-level): device error"); rc = GI_C_ERROR; }
-    releaseAll(); // (before the render's memory plan reads free memory)
+    scratch.release(); // (before the render's memory plan reads free memory)
     return rc;
   });
   if (rcDev == DEVICE_BUILD_FALLBACK && outOfMemory) {
@@ -2068,21 +2154,203 @@ static int updateTransformsTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Up
   }
   if (rcDev != GI_C_OK) return GI_C_ERROR;
   // --- the host copies
-  bytesSent = (size_t)jobCount * (sizeof(InstBoundsJob) + sizeof(InstanceRec) + sizeof(InstTrav)) + tlas.nodes.size() * sizeof(Node8) + tlasItems.size() * sizeof(uint32_t) +
-      editedOfInstance.size() * sizeof(uint32_t) + ranges.size() * sizeof(RefitRange);
-  const size_t tlasNodeCount = tlas.nodes.size();
-  H.instances.swap(instances); T.instTrav.swap(instTrav); T.instBoxes.swap(boxes); T.tlasNodes.swap(tlas.nodes); T.tlasItems.swap(tlasItems); T.tlasDepth = tlas.maxDepth;
-  setSceneBounds(s, std::vector<Node8>{root});
-  if (!H.hostTreeDropped) { // the host copies of the flat tree are stale from here on: dropped, as after a vertex refit
-    std::vector<Node8>().swap(H.bvh.nodes); std::vector<TriRec>().swap(H.bvh.tris); std::vector<int32_t>().swap(H.triFaceId);
-    H.hostTreeDropped = true;
-  }
+  bytesSent = (size_t)jobCount * (sizeof(InstBoundsJob) + sizeof(InstanceRec) + sizeof(InstTrav)) + E.tlas.nodes.size() * sizeof(Node8) + E.tlasItems.size() * sizeof(uint32_t) +
+      E.editedOfInstance.size() * sizeof(uint32_t) + E.ranges.size() * sizeof(RefitRange);
+  const size_t tlasNodeCount = E.tlas.nodes.size(), levelLaunches = E.levels.size();
+  H.instances.swap(instances);
+  finishTwoLevelEdit(s, H, E, instTrav, root);
   for (GiCMesh* m : s->meshes) { m->xformDirty = false; m->instDirty.clear(); }
   const double t3 = nowMs();
-  cost.buildMs = t2 - t1; cost.uploadMs = std::max(t3 - t0 - cost.buildMs, 0.0);
+  cost.buildMs = E.tlasMs; cost.uploadMs = std::max(t3 - t0 - cost.buildMs, 0.0);
   if (timing) fprintf(stderr, "[gatling_gi] transform update (two-level): %u instance(s) moved of %u, TLAS %zu node(s) in %u level(s), %zu level launch(es) over the flat "
                               "tree, host TLAS build %.2f ms, bounds kernels + read-back %.2f ms, commit %.2f ms, %zu bytes sent per device\n", jobCount,
-                      instanceCount, tlasNodeCount, T.tlasDepth, levels.size(), t2 - t1, t1 - t0, t3 - t2, bytesSent);
+                      instanceCount, tlasNodeCount, T.tlasDepth, levelLaunches, E.tlasMs, t1 - t0, t3 - t2, bytesSent);
+  handled = true;
+  return GI_C_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Vertex updates on the two-level layout (opt-in: GI_C_SCENE_OPTION_BLAS_UPDATES / GATLING_OPTIONS=blas_updates=1, read with vertex updates wanted).  The
+// points of meshes of a built two-level scene moved (giCSetMeshVertices); nothing else asked for a rebuild.  One BLAS is shared by all instances of a mesh,
+// so the edit touches nf triangles, not nf x instances; and the walk tests the world-space triangle it rebuilds from BlasTri + InstTrav against the
+// world-space ray, so hits do not depend on the BLAS's shape: a BLAS with the build's topology and new conservative boxes gives a fresh build's bits.
+//   host: the edited meshes' BlasTri records with their new points, in the builder's order (a copy by prim).
+//   device, primary, scratch only: those records are sent to a scratch block and k_inst_bounds / k_inst_finish make the padded world box and the status of
+//       EVERY instance of every edited mesh from them (the resident records still hold the old points: every decision is made before the first resident
+//       write).  28 bytes per instance are read back.
+//   host: the decision -- a set status (OBJECT / WORLD / TRIBOX: the rule a fresh build and the flat refit apply) declines --, the TLAS built again over all
+//       instance boxes, the depth rule (the BLAS depth cannot change).
+//   every device: the edited meshes' FVertex ranges; k_gather_shade; k_blas_tris; k_blas_refit_level level by level over all edited BLASes (gi_blas.hip);
+//       the primary reads the refitted BLAS roots' float boxes back (32 bytes per mesh): the union of the padded face boxes, buildTwoLevel's mlo / mhi up to
+//       the sign of a zero, from which InstTrav::slack is formed with buildTwoLevel's expression; then the instances' InstTrav records with the new slack,
+//       the TLAS, and k_refit_tris + k_refit_level over the whole flat tree (commitTwoLevelEdit: what a transform update of this layout runs).
+//   host copies: H.verts, H.triShade, T.blasTris, T.instTrav, T.instBoxes and the TLAS are brought up to date; the flat host tree is dropped; T.blasNodes keeps
+//       the build's topology and stale planes (gi_host.h).
+// A refitted BLAS degrades like a refitted flat tree until the next full build.
+// Declines (handled = false, not an error; the resident scene is untouched but where noted): what updateVertices and updateTransformsTwoLevel decline for --
+// no host copy or incremental=0 (the caller), fewer than kIncrementalMinTris resident triangles, no packed shading records, a scene built with inactive
+// triangles, a flat tree that is device-built, partitioned or without its level table, an edited mesh that is not built, hidden, without faces or with
+// another instance count, an unusable position, an unusable instance, a set status, the depth rule --, a visibility toggle due in the same sync (it rebuilds
+// on this layout), out of device memory (a later device of several: the earlier ones are committed, and buildScene sends everything anew).
+// ---------------------------------------------------------------------------------------------------------------
+static int updateVerticesTwoLevel(GiCScene* s, SceneHost& H, bool& handled, UpdateCost& cost)
+{
+  TwoLevelHost& T = H.two;
+  const char* const what = "vertex update (two-level)";
+  const uint32_t instanceCount = (uint32_t)H.instances.size(), shadeCount = (uint32_t)H.triShade.size();
+  const uint32_t blasNodeCount = (uint32_t)T.blasNodes.size(), blasTriCount = (uint32_t)T.blasTris.size();
+  if (s->triCount < kIncrementalMinTris || !H.shadePacked || s->stats.inactiveTriangleCount != 0u) return GI_C_OK; // (the floor: resident triangles)
+  if (H.deviceBuilt || H.partitioned || H.bvh.levelStart.size() < 2u || H.bvh.levelStart.back() != s->nodeCount) return GI_C_OK;
+  if (T.instTrav.size() != instanceCount || T.instBoxes.size() != 6u * (size_t)instanceCount || T.meshBlasTri.size() != H.meshBuilds.size() ||
+      T.meshBlasNode.size() != H.meshBuilds.size() || T.meshBlasLevels.size() != H.meshBuilds.size()) return GI_C_OK; // (cannot happen)
+  const bool timing = getenv("GATLING_BUILD_TIMING") != nullptr;
+  const double t0 = nowMs();
+  // --- which meshes, and may their BLASes be refitted?
+  struct Edited { uint32_t build, firstTri, nodeBase, scratchFirst, nf; };
+  std::vector<Edited> edited;
+  uint32_t scratchCount = 0;
+  for (const GiCMesh* m : s->meshes) {
+    if (m->visToggled) return GI_C_OK; // (the visibility update declines on this layout: the scene is rebuilt anyway)
+    if (!m->vertsEdited) continue;
+    uint32_t b = 0;
+    while (b < (uint32_t)H.meshBuilds.size() && H.meshBuilds[b].m != m) b++;
+    if (b == (uint32_t)H.meshBuilds.size()) return GI_C_OK; // no records on the device
+    const MeshBuild& mb = H.meshBuilds[b];
+    const size_t nf = m->faces.size();
+    if (mb.hidden || m->retired || mb.instCount == 0u || m->builtInstances != mb.instCount || mb.meshIdx >= T.meshBlasTri.size()) return GI_C_OK;
+    if ((size_t)mb.vertexOffset + m->vertices.size() > H.verts.size() || nf == 0u || nf >= ((size_t)1 << 26)) return GI_C_OK;
+    if (!gatherShadeRangeOk(shadeCount, mb.shadeBase, (uint32_t)nf)) return GI_C_OK; // (a range the kernels would refuse goes to the rebuild, never to stale records)
+    const uint32_t first = T.meshBlasTri[mb.meshIdx], nodeBase = T.meshBlasNode[mb.meshIdx];
+    const std::vector<uint32_t>& lv = T.meshBlasLevels[mb.meshIdx];
+    if (!blasTrisRangeOk(blasTriCount, first, (uint32_t)nf, shadeCount, mb.shadeBase)) return GI_C_OK;
+    if (lv.size() < 2u || lv[0] != 0u || (size_t)nodeBase + lv.back() > blasNodeCount) return GI_C_OK; // (cannot happen: the build kept them)
+    if (!usableVertexPositions(m->vertices.data(), m->vertices.size())) return GI_C_OK;
+    for (uint32_t ii = 0; ii < mb.instCount; ii++) if (mb.inst[ii] >= instanceCount || !usableInstance(H.instances[mb.inst[ii]])) return GI_C_OK;
+    edited.push_back(Edited{b, first, nodeBase, scratchCount, (uint32_t)nf});
+    scratchCount += (uint32_t)nf;
+    if (scratchCount >= (1u << 26)) return GI_C_OK;
+  }
+  if (edited.empty()) return GI_C_OK;
+  // --- the BLAS records with their new points (the builder's order: a copy by prim), one bounds job per instance, the BLAS refit's plan
+  std::vector<BlasTri> scratchTris(scratchCount);
+  std::vector<InstBoundsJob> jobs; uint32_t chunksPerJob = 0;
+  std::vector<RefitUnit> units;
+  for (const Edited& e : edited) {
+    const MeshBuild& mb = H.meshBuilds[e.build];
+    const GiCMesh* m = mb.m;
+    std::atomic<bool> primOk{true};
+    constexpr size_t CHUNK = 4096;
+    parallelOver(((size_t)e.nf + CHUNK - 1) / CHUNK, [&](size_t c) {
+      for (size_t i = c * CHUNK; i < std::min((size_t)e.nf, (c + 1) * CHUNK); i++) {
+        BlasTri bt = T.blasTris[e.firstTri + i];
+        if (bt.prim >= e.nf) { primOk = false; return; } // (cannot happen)
+        const GiCFace& f = m->faces[bt.prim];
+        memcpy(bt.p0, m->vertices[f.v_i[0]].pos, 12); memcpy(bt.p1, m->vertices[f.v_i[1]].pos, 12); memcpy(bt.p2, m->vertices[f.v_i[2]].pos, 12);
+        scratchTris[e.scratchFirst + i] = bt;
+      }
+    });
+    if (!primOk) return GI_C_OK;
+    for (uint32_t ii = 0; ii < mb.instCount; ii++) {
+      InstBoundsJob j{}; memcpy(j.o2w, H.instances[mb.inst[ii]].o2w, sizeof(j.o2w)); j.firstTri = e.scratchFirst; j.faceCount = e.nf; j.instance = mb.inst[ii];
+      jobs.push_back(j);
+    }
+    chunksPerJob = std::max(chunksPerJob, instBoundsChunks(e.nf));
+    units.push_back(RefitUnit{e.nodeBase, &T.meshBlasLevels[mb.meshIdx]});
+  }
+  const uint32_t jobCount = (uint32_t)jobs.size();
+  if ((uint64_t)jobCount * chunksPerJob >= (1ull << 31)) return GI_C_OK; // (more workgroups than a launch takes)
+  std::vector<RefitRange> blasRanges; std::vector<RefitLevel> blasLevels;
+  if (!planRefitLevels(units, blasNodeCount, blasRanges, blasLevels)) return GI_C_OK; // (cannot happen: the levels of BLASes inside the node array)
+  // --- primary device, scratch only: padded boxes and statuses of every instance of every edited mesh
+  std::vector<uint32_t> result;
+  bool outOfMemory = false;
+  const double tA = nowMs();
+  int rcDev = instanceBoundsOnPrimary(s, jobs, chunksPerJob, &scratchTris, result, outOfMemory, what);
+  if (rcDev == DEVICE_BUILD_FALLBACK && outOfMemory) return GI_C_OK;
+  if (rcDev != GI_C_OK) return GI_C_ERROR;
+  // --- the decision; from here on nothing declines but out of device memory
+  const double t1 = nowMs();
+  TwoLevelEdit E;
+  if (!planTwoLevelEdit(s, H, jobs, result, what, timing, E)) return GI_C_OK;
+  const double tP = nowMs();
+  // --- host: the edited meshes' vertex and shading records, as updateVertices makes them
+  for (const Edited& e : edited) {
+    const MeshBuild& mb = H.meshBuilds[e.build];
+    constexpr size_t CHUNK = 4096;
+    const size_t nv = mb.m->vertices.size(), nf = e.nf;
+    parallelOver((nv + CHUNK - 1) / CHUNK, [&](size_t c) {
+      for (size_t i = c * CHUNK; i < std::min(nv, (c + 1) * CHUNK); i++) H.verts[mb.vertexOffset + i] = packVertex(mb.m->vertices[i]); });
+    parallelOver((nf + CHUNK - 1) / CHUNK, [&](size_t c) {
+      for (size_t f = c * CHUNK; f < std::min(nf, (c + 1) * CHUNK); f++) refit_gather_shade(H.verts.data(), (uint32_t)H.verts.size(), H.triShade[mb.shadeBase + f]); });
+  }
+  const double t2 = nowMs();
+  // --- every device of the scene, on its own stream.  The temporaries are allocated before anything resident changes
+  Node8 root{}; std::vector<InstTrav> instTrav(T.instTrav); std::vector<float> rootBoxes(8u * edited.size(), 0.0f);
+  rcDev = onSceneDevices(s, residentDeviceCount(s), [&](SceneDevice& D, hipStream_t st) -> int {
+    if (D.dTris.count < s->triCount || D.dNodes.count < s->nodeCount || D.dInstances.count < instanceCount || D.dInstTrav.count < instanceCount ||
+        D.dTriShade.count < shadeCount || D.dVerts.count < H.verts.size() || D.dBlasTris.count < blasTriCount || D.dBlasNodes.count < blasNodeCount) {
+      setError("internal: the device holds less than the scene"); return GI_C_ERROR; }
+    FlatRefitScratch scratch; DeviceBuffer<float> dBlasBoxes; DeviceBuffer<RefitRange> dBlasRanges;
+    auto releaseAll = [&] { scratch.release(); dBlasBoxes.release(); dBlasRanges.release(); };
+    const int a = scratch.alloc(s->nodeCount, E), b = a ? a : dBlasBoxes.alloc((size_t)blasNodeCount * 8u), c = b ? b : dBlasRanges.alloc(blasRanges.size());
+    if (c != GI_C_OK) { releaseAll(); if (c == GI_C_OUT_OF_MEMORY_INTERNAL) { outOfMemory = true; return DEVICE_BUILD_FALLBACK; } return GI_C_ERROR; }
+    int rc = GI_C_OK;
+    auto copy = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+      if (rc == GI_C_OK && bytes && hipMemcpyAsync(dst, src, bytes, kind, st) != hipSuccess) { setError("vertex update (two-level): copy failed"); rc = GI_C_ERROR; } };
+    for (const Edited& e : edited) {
+      const MeshBuild& mb = H.meshBuilds[e.build];
+      copy(D.dVerts.ptr + mb.vertexOffset, &H.verts[mb.vertexOffset], mb.m->vertices.size() * sizeof(FVertex), hipMemcpyHostToDevice);
+    }
+    copy(dBlasRanges.ptr, blasRanges.data(), blasRanges.size() * sizeof(RefitRange), hipMemcpyHostToDevice);
+    // (behind the vertex uploads on the same stream: the shading records, then the BLAS records that read TriShade::p, then the BLAS levels)
+    if (rc == GI_C_OK) for (const Edited& e : edited) {
+      const MeshBuild& mb = H.meshBuilds[e.build];
+      if (!launchGatherShade(st, D.dTriShade.ptr, shadeCount, mb.shadeBase, e.nf, D.dVerts.ptr, (uint32_t)H.verts.size()) ||
+          !launchBlasTris(st, D.dBlasTris.ptr, blasTriCount, e.firstTri, e.nf, D.dTriShade.ptr, shadeCount, mb.shadeBase)) {
+        setError("internal: an edited mesh's records outside their arrays"); rc = GI_C_ERROR; break; } // (cannot happen: asked above)
+    }
+    if (rc == GI_C_OK) {
+      for (const RefitLevel& lv : blasLevels) launchBlasRefitLevel(st, D.dBlasNodes.ptr, blasNodeCount, dBlasBoxes.ptr, dBlasRanges.ptr + lv.first, lv.ranges,
+          lv.threads, D.dBlasTris.ptr, blasTriCount);
+      if (hipGetLastError() != hipSuccess) { setError("vertex update (two-level): launch failed"); rc = GI_C_ERROR; }
+    }
+    if (D.slot == 0u) { // (the refit is deterministic: every device holds the same bytes) the BLAS roots' float boxes -> the meshes' object-space magnitude
+      for (size_t k = 0; k < edited.size(); k++) copy(&rootBoxes[8u * k], dBlasBoxes.ptr + 8u * (size_t)edited[k].nodeBase, 32u, hipMemcpyDeviceToHost);
+      if (rc == GI_C_OK && hipStreamSynchronize(st) != hipSuccess) { setError("vertex update (two-level): device error"); rc = GI_C_ERROR; }
+      if (rc == GI_C_OK) for (size_t k = 0; k < edited.size(); k++) {
+        const float* lo = &rootBoxes[8u * k]; const float* hi = lo + 4;
+        const float extent = (std::fabs(lo[0]) + std::fabs(lo[1]) + std::fabs(lo[2])) + (std::fabs(hi[0]) + std::fabs(hi[1]) + std::fabs(hi[2])); // (buildTwoLevel's)
+        const MeshBuild& mb = H.meshBuilds[edited[k].build];
+        for (uint32_t ii = 0; ii < mb.instCount; ii++) instTrav[mb.inst[ii]].slack = extent; // (the matrices, blasRoot, triBase and matFlags stay)
+      }
+    }
+    if (rc == GI_C_OK) rc = commitTwoLevelEdit(s, H, D, st, E, nullptr, instTrav, scratch, root, what);
+    if (hipStreamSynchronize(st) != hipSuccess && rc == GI_C_OK) { setError("vertex update (two-level): device error"); rc = GI_C_ERROR; }
+    releaseAll(); // (before the render's memory plan reads free memory)
+    return rc;
+  });
+  if (rcDev == DEVICE_BUILD_FALLBACK && outOfMemory) {
+    if (timing) fprintf(stderr, "[gatling_gi] vertex update (two-level): out of device memory for the refits' boxes; the scene is rebuilt\n");
+    return GI_C_OK;
+  }
+  if (rcDev != GI_C_OK) return GI_C_ERROR;
+  // --- the host copies
+  size_t bytesSent = scratchTris.size() * sizeof(BlasTri) /* the primary alone */ + (size_t)jobCount * (sizeof(InstBoundsJob) + sizeof(InstTrav)) +
+      E.tlas.nodes.size() * sizeof(Node8) + E.tlasItems.size() * sizeof(uint32_t) + E.editedOfInstance.size() * sizeof(uint32_t) +
+      (E.ranges.size() + blasRanges.size()) * sizeof(RefitRange);
+  for (const Edited& e : edited) {
+    bytesSent += H.meshBuilds[e.build].m->vertices.size() * sizeof(FVertex);
+    std::copy(scratchTris.begin() + e.scratchFirst, scratchTris.begin() + e.scratchFirst + e.nf, T.blasTris.begin() + e.firstTri);
+  }
+  const size_t tlasNodeCount = E.tlas.nodes.size(), flatLaunches = E.levels.size();
+  finishTwoLevelEdit(s, H, E, instTrav, root);
+  const double t3 = nowMs();
+  cost.buildMs = E.tlasMs; cost.uploadMs = std::max(t3 - t0 - cost.buildMs, 0.0);
+  if (timing) fprintf(stderr, "[gatling_gi] vertex update (two-level): %zu mesh(es), %zu BLAS level launch(es), %u instance(s) re-bounded of %u, TLAS %zu node(s), "
+                              "%zu level launch(es) over the flat tree, host %.2f ms (records + plans %.2f, TLAS build %.2f, vertex packing %.2f), device %.2f ms "
+                              "(bounds kernels + read-back %.2f, refits + commit %.2f), %zu bytes sent to the primary device\n", edited.size(), blasLevels.size(),
+                      jobCount, instanceCount, tlasNodeCount, flatLaunches, (tA - t0) + (t2 - t1), (tA - t0) + (tP - t1 - E.tlasMs), E.tlasMs, t2 - tP, (t1 - tA) + (t3 - t2),
+                      t1 - tA, t3 - t2, bytesSent);
   handled = true;
   return GI_C_OK;
 }
@@ -2183,6 +2451,152 @@ extern "C" int giCDebugInstanceBounds(const GiCVertex* vertices, uint32_t vertex
   } catch (const std::exception& e) { setError(std::string("giCDebugInstanceBounds: ") + e.what()); return -1; }
 }
 
+// giCDebugSceneBlasCheck: the two-level arrays resident on a device after vertex updates in place, against the scene's current meshes (include/gi_c.h has
+// the five parts).  The BLAS nodes are compared with the HOST form of the refit over the host's topology copy and the current points; the TLAS, its items
+// and the InstTrav records with a fresh buildTwoLevel, whose instance boxes do not depend on a BLAS's shape.
+extern "C" int giCDebugSceneBlasCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t* out)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!g_ctx.initialized || !s || !out) { setError("giCDebugSceneBlasCheck: bad arguments"); return -1; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  if (!s->host) { setError("giCDebugSceneBlasCheck: the scene has not been built (render it once)"); return -1; }
+  if (deviceIndex > s->replicas.size() || deviceIndex >= sceneDeviceCount(s)) { setError("giCDebugSceneBlasCheck: no such device copy"); return -1; }
+  const SceneHost& H = *s->host; const TwoLevelHost& T = H.two;
+  out[0] = s->twoLevel ? 1u : 0u; out[1] = out[2] = out[3] = 0u;
+  if (!s->twoLevel) return 0;
+  try {
+    std::vector<InstanceRec> instances(H.instances.size());
+    for (const MeshBuild& mb : H.meshBuilds) {
+      if (mb.m->instanceTransforms.size() != (size_t)mb.instCount * 16u) { setError("giCDebugSceneBlasCheck: a mesh's instance count is not the built one (render first)"); return -1; }
+      for (uint32_t ii = 0; ii < mb.instCount; ii++) instances[mb.inst[ii]] = makeInstanceRec(mb.m, mb.meshIdx, ii);
+    }
+    TwoLevelHost fresh;
+    const int rc = buildTwoLevel(s, H.meshBuilds, instances, s->triCount, s->nodeCount, fresh);
+    const bool stillTwoLevel = s->twoLevel;
+    s->twoLevel = true; // (buildTwoLevel answers through it: the resident scene is what it was)
+    if (rc != GI_C_OK || !stillTwoLevel) { setError("giCDebugSceneBlasCheck: a fresh build of the current meshes would not use the two-level layout"); return -1; }
+    if (T.meshBlasTri.size() != H.meshBuilds.size() || T.meshBlasNode.size() != H.meshBuilds.size() || T.meshBlasLevels.size() != H.meshBuilds.size() ||
+        fresh.instTrav.size() != T.instTrav.size() || fresh.blasTris.size() != T.blasTris.size()) { setError("giCDebugSceneBlasCheck: the host copy is not the built scene's"); return -1; }
+    SceneDevice& D = sceneDevice(s, deviceIndex);
+    std::vector<Node8> tlasNodes(fresh.tlasNodes.size()), blasNodes(T.blasNodes.size()); std::vector<uint32_t> tlasItems(fresh.tlasItems.size());
+    std::vector<BlasTri> blasTris(T.blasTris.size()); std::vector<InstTrav> instTrav(fresh.instTrav.size());
+    int differ = 0;
+    auto fetch = [&](auto& host, const auto& dev) -> bool { // (a resident array shorter than expected: every missing record differs)
+      using R = typename std::remove_reference<decltype(host)>::type::value_type;
+      const size_t n = std::min(host.size(), dev.ptr ? dev.count : (size_t)0);
+      differ += (int)(host.size() - n);
+      host.resize(n);
+      return n == 0u || hipMemcpy(host.data(), dev.ptr, n * sizeof(R), hipMemcpyDeviceToHost) == hipSuccess;
+    };
+    bool ok = hipSetDevice(g_ctx.devs[D.slot].device) == hipSuccess;
+    ok = ok && fetch(tlasNodes, D.dTlasNodes) && fetch(tlasItems, D.dTlasItems) && fetch(instTrav, D.dInstTrav) && fetch(blasNodes, D.dBlasNodes) && fetch(blasTris, D.dBlasTris);
+    (void)hipSetDevice(g_ctx.device);
+    if (!ok) { setError("giCDebugSceneBlasCheck: download failed"); return -1; }
+    if (blasNodes.size() != T.blasNodes.size() || blasTris.size() != T.blasTris.size()) return differ; // (nothing further can be compared)
+    // (a) the records: the build's prim at its place, the current corners; and the expected arrays of (b)
+    std::vector<BlasTri> wantTris(T.blasTris); std::vector<Node8> wantNodes(T.blasNodes);
+    std::vector<float> boxes(8u * wantNodes.size(), 0.0f), under(6u * wantNodes.size(), 0.0f);
+    uint32_t violations = 0;
+    for (const MeshBuild& mb : H.meshBuilds) {
+      if (mb.instCount == 0u) continue;
+      const GiCMesh* m = mb.m;
+      const uint32_t first = T.meshBlasTri[mb.meshIdx], nodeBase = T.meshBlasNode[mb.meshIdx], nf = (uint32_t)m->faces.size();
+      const std::vector<uint32_t>& lv = T.meshBlasLevels[mb.meshIdx];
+      if ((size_t)first + nf > wantTris.size() || lv.size() < 2u || (size_t)nodeBase + lv.back() > wantNodes.size()) { differ++; continue; }
+      for (uint32_t i = 0; i < nf; i++) {
+        const uint32_t prim = T.blasTris[first + i].prim;
+        if (prim >= nf) { differ++; continue; }
+        wantTris[first + i] = makeBlasTri(m->vertices.data(), m->faces.data(), prim);
+        if (memcmp(&blasTris[first + i], &wantTris[first + i], sizeof(BlasTri)) != 0) differ++;
+      }
+      // (b) the host form of the refit over the host's topology copy; (c) the conservative check of what is resident
+      blasRefitHost(wantNodes.data(), (uint32_t)wantNodes.size(), nodeBase, lv.back(), boxes.data(), wantTris.data(), (uint32_t)wantTris.size());
+      for (uint32_t i = 0; i < lv.back(); i++) if (memcmp(&blasNodes[nodeBase + i], &wantNodes[nodeBase + i], sizeof(Node8)) != 0) differ++;
+      std::vector<uint8_t> seen(nf, 0);
+      violations += blasConservativeViolations(blasNodes.data(), (uint32_t)blasNodes.size(), nodeBase, lv.back(), blasTris.data(), (uint32_t)blasTris.size(), first, nf,
+          under.data(), seen.data());
+      // (e) the fresh records with the resident BLAS's root
+      for (uint32_t ii = 0; ii < mb.instCount; ii++) if (mb.inst[ii] < fresh.instTrav.size()) fresh.instTrav[mb.inst[ii]].blasRoot = nodeBase;
+    }
+    // (d), (e)
+    if (T.tlasNodes.size() != fresh.tlasNodes.size()) differ++; // (the host copy the next update starts from)
+    auto compare = [&](const auto& got, const auto& want) {
+      using R = typename std::remove_reference<decltype(got)>::type::value_type;
+      for (size_t i = 0; i < got.size(); i++) if (memcmp(&got[i], &want[i], sizeof(R)) != 0) differ++;
+    };
+    compare(tlasNodes, fresh.tlasNodes); compare(tlasItems, fresh.tlasItems); compare(instTrav, fresh.instTrav);
+    for (size_t i = 0; i < instTrav.size(); i++) if (memcmp(&T.instTrav[i], &fresh.instTrav[i], sizeof(InstTrav)) != 0) differ++; // (the host copy)
+    out[1] = (uint32_t)blasNodes.size(); out[2] = violations; out[3] = (uint32_t)blasTris.size();
+    return differ + (int)violations;
+  } catch (const std::exception& e) { s->twoLevel = true; setError(std::string("giCDebugSceneBlasCheck: ") + e.what()); return -1; }
+}
+
+// giCDebugBlasRefit / giCDebugBlasRefitHost: one BLAS built over points a, refitted to points b by the host form (gi_blas.h) and -- onDevice -- by k_blas_tris +
+// k_blas_refit_level, compared bytewise
+static int debugBlasRefit(const char* name, bool onDevice, const GiCVertex* a, const GiCVertex* b, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount,
+    uint32_t* outNodes, uint32_t* outViolations)
+{
+  if (onDevice && !g_ctx.initialized) { setError(std::string(name) + " before giCInitialize"); return -1; }
+  if (!a || !b || !faces || vertexCount == 0u || faceCount == 0u || faceCount >= (1u << 26)) { setError(std::string(name) + ": bad arguments"); return -1; }
+  for (uint32_t f = 0; f < faceCount; f++) for (int k = 0; k < 3; k++) if (faces[f].v_i[k] >= vertexCount) { setError(std::string(name) + ": a face index outside the vertices"); return -1; }
+  try {
+    bool same = true;
+    for (uint32_t i = 0; i < vertexCount && same; i++) same = memcmp(a[i].pos, b[i].pos, 12) == 0;
+    Bvh8 built; std::vector<uint32_t> order; float mlo[3], mhi[3];
+    buildMeshBlas(a, faces, faceCount, built, order, mlo, mhi);
+    std::vector<BlasTri> builtTris; builtTris.reserve(faceCount);
+    for (uint32_t f : order) builtTris.push_back(makeBlasTri(a, faces, f));
+    const uint32_t nodeCount = (uint32_t)built.nodes.size();
+    if (builtTris.size() != faceCount || built.levelStart.size() < 2u || built.levelStart.back() != nodeCount) { setError(std::string(name) + ": the builder's tree has no level table"); return -1; }
+    std::vector<TriShade> shade(faceCount); // (the corners alone: what the refit reads of a shading record)
+    for (uint32_t f = 0; f < faceCount; f++) { TriShade q{}; for (int k = 0; k < 3; k++) memcpy(q.p[k], b[faces[f].v_i[k]].pos, 12); shade[f] = q; }
+    // --- the host form
+    std::vector<Node8> hostNodes(built.nodes); std::vector<BlasTri> hostTris(builtTris); std::vector<float> boxes(8u * (size_t)nodeCount, 0.0f);
+    int differ = 0;
+    for (uint32_t i = 0; i < faceCount; i++) if (!blas_tri_from_shade(hostTris[i], shade.data(), faceCount, 0u, faceCount)) differ += (int)sizeof(BlasTri);
+    blasRefitHost(hostNodes.data(), nodeCount, 0u, nodeCount, boxes.data(), hostTris.data(), faceCount);
+    std::vector<Node8> nodes(hostNodes); std::vector<BlasTri> tris(hostTris); // what is checked below: the host's result, or the device's
+    if (onDevice) {
+      std::vector<RefitUnit> units{RefitUnit{0u, &built.levelStart}};
+      std::vector<RefitRange> ranges; std::vector<RefitLevel> levels;
+      if (!planRefitLevels(units, nodeCount, ranges, levels)) { setError(std::string(name) + ": the level table lies outside the tree"); return -1; }
+      DeviceBuffer<Node8> dNodes; DeviceBuffer<BlasTri> dTris; DeviceBuffer<TriShade> dShade; DeviceBuffer<float> dBoxes; DeviceBuffer<RefitRange> dRanges;
+      hipStream_t st = g_ctx.stream;
+      bool ok = hipSetDevice(g_ctx.device) == hipSuccess && dNodes.upload(built.nodes, st) == GI_C_OK && dTris.upload(builtTris, st) == GI_C_OK &&
+          dShade.upload(shade, st) == GI_C_OK && dBoxes.alloc(8u * (size_t)nodeCount) == GI_C_OK && dRanges.upload(ranges, st) == GI_C_OK;
+      ok = ok && launchBlasTris(st, dTris.ptr, faceCount, 0u, faceCount, dShade.ptr, faceCount, 0u);
+      if (ok) for (const RefitLevel& lv : levels) launchBlasRefitLevel(st, dNodes.ptr, nodeCount, dBoxes.ptr, dRanges.ptr + lv.first, lv.ranges, lv.threads, dTris.ptr, faceCount);
+      ok = ok && hipGetLastError() == hipSuccess;
+      ok = ok && hipMemcpyAsync(nodes.data(), dNodes.ptr, nodes.size() * sizeof(Node8), hipMemcpyDeviceToHost, st) == hipSuccess &&
+          hipMemcpyAsync(tris.data(), dTris.ptr, tris.size() * sizeof(BlasTri), hipMemcpyDeviceToHost, st) == hipSuccess;
+      ok = hipStreamSynchronize(st) == hipSuccess && ok;
+      dNodes.release(); dTris.release(); dShade.release(); dBoxes.release(); dRanges.release();
+      if (!ok) { setError(std::string(name) + ": device error"); return -1; }
+    }
+    auto bytesDiffering = [](const void* x, const void* y, size_t n) { int d = 0; for (size_t i = 0; i < n; i++) d += ((const uint8_t*)x)[i] != ((const uint8_t*)y)[i]; return d; };
+    if (onDevice) differ += bytesDiffering(nodes.data(), hostNodes.data(), nodes.size() * sizeof(Node8)) + bytesDiffering(tris.data(), hostTris.data(), tris.size() * sizeof(BlasTri));
+    if (same) differ += bytesDiffering(nodes.data(), built.nodes.data(), nodes.size() * sizeof(Node8)) + bytesDiffering(tris.data(), builtTris.data(), tris.size() * sizeof(BlasTri));
+    else { // the topology is the build's
+      for (uint32_t i = 0; i < nodeCount; i++) {
+        const Node8& x = nodes[i]; const Node8& y = built.nodes[i];
+        differ += (x.imask != y.imask) + bytesDiffering(x.meta, y.meta, 8) + bytesDiffering(&x.childBase, &y.childBase, 4) + bytesDiffering(&x.triBase, &y.triBase, 4);
+      }
+      for (uint32_t i = 0; i < faceCount; i++) differ += bytesDiffering(&tris[i].prim, &builtTris[i].prim, 4);
+    }
+    std::vector<float> under(6u * (size_t)nodeCount, 0.0f); std::vector<uint8_t> seen(faceCount, 0);
+    const uint32_t violations = blasConservativeViolations(nodes.data(), nodeCount, 0u, nodeCount, tris.data(), faceCount, 0u, faceCount, under.data(), seen.data());
+    if (outNodes) *outNodes = nodeCount;
+    if (outViolations) *outViolations = violations;
+    return differ;
+  } catch (const std::exception& e) { setError(std::string(name) + ": " + e.what()); return -1; }
+}
+extern "C" int giCDebugBlasRefit(const GiCVertex* a, const GiCVertex* b, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, uint32_t* outNodes,
+    uint32_t* outViolations)
+{ return debugBlasRefit("giCDebugBlasRefit", true, a, b, vertexCount, faces, faceCount, outNodes, outViolations); }
+extern "C" int giCDebugBlasRefitHost(const GiCVertex* a, const GiCVertex* b, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, uint32_t* outNodes,
+    uint32_t* outViolations)
+{ return debugBlasRefit("giCDebugBlasRefitHost", false, a, b, vertexCount, faces, faceCount, outNodes, outViolations); }
+
 // brings the device scene up to date with the host-side edits: incremental for DIRTY_BVH raised by vertex edits alone (opt-in: the tree refitted on the
 // device), by visibility toggles alone (opt-in: ids renumbered, the
 // toggled meshes' triangles hidden / shown in place), for material-side edits alone (the small arrays + one word per triangle) and for transform edits alone
@@ -2219,7 +2633,9 @@ int syncSceneGeometry(GiCScene* s)
   for (const GiCMesh* m : s->meshes) { anyVis = anyVis || m->visToggled; anyVerts = anyVerts || m->vertsEdited; }
   if (rc == GI_C_OK && topologyRuns && !s->rebuildDue && !anyVis && !anyVerts) s->dirty &= ~DIRTY_BVH;
   if ((s->dirty & DIRTY_BVH) && anyVerts && (!vertexUpdatesWanted(s) || (anyVis && !visibilityUpdatesWanted(s)))) s->rebuildDue = true;
-  if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_BVH) && !s->rebuildDue && anyVerts, updateVertices, UPDATE_VERTEX, anyVis ? 0u : (uint32_t)DIRTY_BVH, DIRTY_BVH, 0u);
+  // (a vertex update of the two-level layout has a counter of its own as well: giCDebugSceneVertexUpdateCount keeps counting what it counted)
+  const uint32_t vertexCounter = s->twoLevel && blasUpdatesWanted(s) && incrementalHost(s) ? (uint32_t)UPDATE_BLAS : (uint32_t)UPDATE_VERTEX;
+  if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_BVH) && !s->rebuildDue && anyVerts, updateVertices, vertexCounter, anyVis ? 0u : (uint32_t)DIRTY_BVH, DIRTY_BVH, 0u);
   if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_BVH) && !s->rebuildDue && visibilityUpdatesWanted(s), updateVisibility, UPDATE_VISIBILITY, DIRTY_BVH, 0u, 0u);
   if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_MATERIALS) && !(s->dirty & DIRTY_BVH), updateMaterials, UPDATE_MATERIAL, DIRTY_MATERIALS, DIRTY_BVH, DIRTY_BVH);
   // (a transform update of the two-level layout has a counter of its own: giCDebugSceneUpdateCounts keeps counting what it counted)

@@ -321,6 +321,7 @@ int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value)
   if (option == GI_C_SCENE_OPTION_RESYNC_REFITS) { scene->optResyncRefits = value == 1 ? 1 : 0; return GI_C_OK; }
   if (option == GI_C_SCENE_OPTION_INSTANCE_UPDATES) { scene->optInstanceUpdates = value == 1 ? 1 : 0; return GI_C_OK; }
   if (option == GI_C_SCENE_OPTION_TLAS_UPDATES) { scene->optTlasUpdates = value == 1 ? 1 : 0; return GI_C_OK; }
+  if (option == GI_C_SCENE_OPTION_BLAS_UPDATES) { scene->optBlasUpdates = value == 1 ? 1 : 0; return GI_C_OK; } // (read only with option 12 wanted)
   setError("unknown scene option"); return GI_C_ERROR;
 }
 

@@ -309,7 +309,12 @@ struct SceneDevice {
 struct TwoLevelHost { std::vector<Node8> tlasNodes, blasNodes; std::vector<uint32_t> tlasItems; std::vector<BlasTri> blasTris; std::vector<InstTrav> instTrav;
     // transform updates in place (gi_build.cpp updateTransformsTwoLevel): the padded world box of every instance (6 floats each: what the TLAS is built
     // over), the first BLAS triangle of every mesh by meshIdx, and the depths the layout's stack rule reads
-    std::vector<float> instBoxes; std::vector<uint32_t> meshBlasTri; uint32_t tlasDepth = 0, blasDepth = 0; };
+    std::vector<float> instBoxes; std::vector<uint32_t> meshBlasTri; uint32_t tlasDepth = 0, blasDepth = 0;
+    // vertex updates in place (gi_build.cpp updateVerticesTwoLevel): the first BLAS node of every mesh by meshIdx and the first node of every level of its
+    // BLAS relative to that, then the BLAS's node count (Bvh8::levelStart; empty for a mesh without instances).  After such an update blasNodes keeps the
+    // build's TOPOLOGY (imask, meta, childBase, triBase) while its planes (p, e, qlo, qhi) go stale: nothing reads them before the next buildScene -- the
+    // device refits its own copy, and giCDebugSceneBlasCheck runs the host refit over a copy of the topology
+    std::vector<uint32_t> meshBlasNode; std::vector<std::vector<uint32_t>> meshBlasLevels; };
 struct MeshBuild { const GiCMesh* m; uint32_t vertexOffset, matFlags, instFirst, instCount, triFirst; uint32_t meshIdx; std::vector<int32_t> faceIdAov;
     uint32_t shadeBase = 0;
     // the InstanceRec of every live instance, inst[instInMesh]: instFirst + instInMesh (and triangles at triFirst + instInMesh * faces) as the build leaves
@@ -344,7 +349,7 @@ struct SceneHost {
   bool reordered = false;
 };
 
-enum : uint32_t { UPDATE_FULL = 0, UPDATE_TRANSFORM = 1, UPDATE_MATERIAL = 2, UPDATE_VISIBILITY = 3, UPDATE_VERTEX = 4, UPDATE_TOPOLOGY = 5, UPDATE_TLAS = 6 }; // GiCScene::updateCounts
+enum : uint32_t { UPDATE_FULL = 0, UPDATE_TRANSFORM = 1, UPDATE_MATERIAL = 2, UPDATE_VISIBILITY = 3, UPDATE_VERTEX = 4, UPDATE_TOPOLOGY = 5, UPDATE_TLAS = 6, UPDATE_BLAS = 7 }; // GiCScene::updateCounts
 struct GiCScene : SceneDevice {
   std::mutex mutex;
   uint32_t dirty = DIRTY_ALL;
@@ -400,8 +405,8 @@ struct GiCScene : SceneDevice {
   // a look-ahead window traced under another generation is not served from
   uint64_t generation = 0;
   // syncSceneGeometry, by UPDATE_*: full builds and incremental updates (giCDebugSceneUpdateCounts: the first three; giCDebugSceneVisibilityUpdateCount,
-  // giCDebugSceneVertexUpdateCount, giCDebugSceneTopologyUpdateCount, giCDebugSceneTlasUpdateCount)
-  uint64_t updateCounts[7] = {0, 0, 0, 0, 0, 0, 0};
+  // giCDebugSceneVertexUpdateCount, giCDebugSceneTopologyUpdateCount, giCDebugSceneTlasUpdateCount, giCDebugSceneBlasUpdateCount)
+  uint64_t updateCounts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   int32_t optVisibilityUpdates = 0; // GI_C_SCENE_OPTION_VISIBILITY_UPDATES: 1 = visibility edits are applied to the resident scene (updateVisibility)
   int32_t optVertexUpdates = 0; // GI_C_SCENE_OPTION_VERTEX_UPDATES: 1 = vertex edits refit the resident tree (updateVertices)
   // DIRTY_BVH was raised by something other than giCSetMeshVisibility / giCSetMeshVertices since the last syncSceneGeometry (raiseRebuild): the rebuild is due
@@ -422,6 +427,9 @@ struct GiCScene : SceneDevice {
   bool instancesDue = false;
   // GI_C_SCENE_OPTION_TLAS_UPDATES: 1 = transform edits of a two-level scene are applied to the resident scene (updateTransformsTwoLevel)
   int32_t optTlasUpdates = 0;
+  // GI_C_SCENE_OPTION_BLAS_UPDATES: 1 = vertex edits of a two-level scene are applied to the resident scene (updateVerticesTwoLevel; read only with vertex
+  // updates wanted)
+  int32_t optBlasUpdates = 0;
   std::vector<GiCMesh*> retiredMeshes; // destroyed meshes the resident scene still refers to (GiCMesh::retired): freed by buildScene and with the scene
   ~GiCScene() { for (GiCMesh* m : retiredMeshes) delete m; }
 };
@@ -448,6 +456,7 @@ bool usableVertexPositions(const GiCVertex* v, size_t count);  // every position
 void nodeBounds(const Node8& n, float box[6]);               // dequantised bounds of a node's children (+ an ulp-scale pad)
 bool instanceUpdatesWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_INSTANCE_UPDATES / GATLING_OPTIONS=instance_updates (with topology updates wanted)
 bool tlasUpdatesWanted(const GiCScene* s);                   // GI_C_SCENE_OPTION_TLAS_UPDATES / GATLING_OPTIONS=tlas_updates
+bool blasUpdatesWanted(const GiCScene* s);                   // GI_C_SCENE_OPTION_BLAS_UPDATES / GATLING_OPTIONS=blas_updates
 bool topologyUpdatesWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_TOPOLOGY_UPDATES / GATLING_OPTIONS=topology_updates
 int syncSceneGeometry(GiCScene* s);                          // brings the device scene up to date with the host-side edits (incremental or full build)
 // dirty flags of a material-side edit: DIRTY_MATERIALS alone once the scene / the mesh is part of a built scene (the incremental path), else with DIRTY_BVH

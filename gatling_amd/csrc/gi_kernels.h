@@ -125,7 +125,17 @@ constexpr uint32_t kInstBoundsChunk = 4096u;
 uint32_t instBoundsChunks(uint32_t faceCount);
 bool launchInstBounds(hipStream_t s, const InstBoundsJob* jobs, uint32_t jobCount, uint32_t chunksPerJob, const BlasTri* blasTris, uint32_t blasTriCount,
     float* partials, uint32_t* out);
-void launchSpin(hipStream_t s, unsigned long long ns);             // test hook: occupies a stream for ~ns nanoseconds
+// gi_blas.hip: a vertex edit applied to the resident BLAS of a two-level scene (gi_build.cpp updateVerticesTwoLevel, GI_C_SCENE_OPTION_BLAS_UPDATES).
+// launchBlasTris gives the BLAS triangles [first, first + count) of one mesh -- count = its face count -- the object-space corners of the faces they name
+// (BlasTri::prim) from the shading records shadeBase + prim, behind launchGatherShade on the same stream; blasTrisRangeOk: both ranges lie inside their
+// arrays and the threads fit a launch -- launchBlasTris returns false, and launches nothing, where it does not hold.  launchBlasRefitLevel refits one level
+// of the edited BLASes (launchRefitLevel's ranges and thread mapping; `boxes`: 8 floats per node of the whole BLAS node array), deepest level first
+bool blasTrisRangeOk(uint32_t blasTriCount, uint32_t first, uint32_t count, uint32_t shadeCount, uint32_t shadeBase);
+bool launchBlasTris(hipStream_t s, BlasTri* blasTris, uint32_t blasTriCount, uint32_t first, uint32_t count, const TriShade* triShade, uint32_t shadeCount,
+    uint32_t shadeBase);
+void launchBlasRefitLevel(hipStream_t s, Node8* nodes, uint32_t nodeCount, float* boxes, const RefitRange* ranges, uint32_t rangeCount, uint32_t threads,
+    const BlasTri* blasTris, uint32_t blasTriCount);
+void launchSpin(hipStream_t s, unsigned long long ns);           // test hook: occupies a stream for ~ns nanoseconds
 void launchDebugBsdf(hipStream_t s, const MaterialRec* mat, uint32_t shadeClass, uint32_t count, const float* in, float* out);
 void launchDebugSqrt(hipStream_t s, uint32_t first, unsigned long long count, unsigned long long* mismatches); // gi_sqrt against sqrtf over bit patterns
 void launchDebugDiv(hipStream_t s, uint32_t mode, unsigned long long count, uint32_t seed, const uint32_t* words, unsigned long long* mismatches); // gi_div against `/`

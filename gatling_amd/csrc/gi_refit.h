@@ -123,7 +123,10 @@ GI_REFIT_HD inline bool refit_record_box(const RefitScene& S, uint32_t ti, float
 // box minimum, e = exponent_for(extent), qlo / qhi rounded outwards and fixed up against the fp32 planes the traversal evaluates.  Empty slots keep 255 / 0;
 // imask, meta, childBase and triBase are not touched.  A node without an occupied slot (the empty root, a reserved slot of a partitioned range) is left as
 // it is and gets an inverted box.
-GI_REFIT_HD inline void refit_node(Node8* nodes, uint32_t nodeCount, uint32_t ni, float* boxes, const RefitScene& S)
+// `leaf(ti, lo, hi)` is the leaf-box provider: the padded box of the item a leaf slot names, false where it contributes nothing.  The flat tree's is
+// refit_record_box over the resident records (RefitSceneLeaf, refit_node below); a BLAS of the two-level layout has its own (gi_blas.h).
+template <class Leaf>
+GI_REFIT_HD inline void refit_node_with(Node8* nodes, uint32_t nodeCount, uint32_t ni, float* boxes, const Leaf& leaf)
 {
   Node8 n = nodes[ni];
   float slo[8][3], shi[8][3]; uint32_t occupied = 0, rel = 0;
@@ -140,7 +143,7 @@ GI_REFIT_HD inline void refit_node(Node8* nodes, uint32_t nodeCount, uint32_t ni
       const uint32_t unary = meta >> 5, off = meta & 31u, cnt = unary == 1u ? 1u : unary == 3u ? 2u : unary == 7u ? 3u : 0u;
       for (uint32_t k = 0; k < cnt; k++) {
         float tl[3], th[3];
-        if (!refit_record_box(S, n.triBase + off + k, tl, th)) continue;
+        if (!leaf(n.triBase + off + k, tl, th)) continue;
         for (int a = 0; a < 3; a++) { lo[a] = refit_min(lo[a], tl[a]); hi[a] = refit_max(hi[a], th[a]); }
       }
     }
@@ -165,6 +168,14 @@ GI_REFIT_HD inline void refit_node(Node8* nodes, uint32_t nodeCount, uint32_t ni
     }
   }
   nodes[ni] = n;
+}
+struct RefitSceneLeaf {
+  const RefitScene& S;
+  GI_REFIT_HD bool operator()(uint32_t ti, float lo[3], float hi[3]) const { return refit_record_box(S, ti, lo, hi); }
+};
+GI_REFIT_HD inline void refit_node(Node8* nodes, uint32_t nodeCount, uint32_t ni, float* boxes, const RefitScene& S)
+{
+  refit_node_with(nodes, nodeCount, ni, boxes, RefitSceneLeaf{S});
 }
 
 // The whole refit on the host: every node from `firstNode` on, children before parents (both builders and the partitioned layout place children behind

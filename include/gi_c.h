@@ -381,7 +381,8 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * GI_C_SCENE_OPTION_TOPOLOGY_UPDATES and giCDebugSceneTopologyUpdateCount, and for GI_C_SCENE_OPTION_RESYNC_REFITS, giCDebugSceneResyncCount,
  * giCDebugGatherShade and giCDebugSceneShadeCheck, and for giCDebugPathLobeStats and giCDebugPathLot, and for GI_C_SCENE_OPTION_INSTANCE_UPDATES,
  * giCDebugSceneInstanceUpdateCount and giCDebugCloneInstance, and for GI_C_SCENE_OPTION_TLAS_UPDATES, giCDebugSceneTlasUpdateCount, giCDebugSceneTlasCheck
- * and giCDebugInstanceBounds. */
+ * and giCDebugInstanceBounds, and for GI_C_SCENE_OPTION_BLAS_UPDATES, giCDebugSceneBlasUpdateCount, giCDebugSceneBlasCheck, giCDebugBlasRefit and
+ * giCDebugBlasRefitHost. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -606,6 +607,19 @@ int giCGetRenderStats(const GiCScene* scene, GiCRenderStats* out);
  * edit due in the same render is applied first, by the material update.  GATLING_OPTIONS=tlas_updates=0|1 overrides the option (hdGatling sets no scene
  * options).  DESIGN.md section 6. */
 #define GI_C_SCENE_OPTION_TLAS_UPDATES 16
+/* [ext] Incremental vertex edits on the two-level layout; read only when vertex updates are wanted (GI_C_SCENE_OPTION_VERTEX_UPDATES, or
+ * GATLING_OPTIONS=vertex_updates=1): value 1 = a giCSetMeshVertices on a mesh of a built two-level scene is applied to the resident scene by the next
+ * giCRender when nothing else asks for a rebuild: the mesh's vertex records are re-sent, its shading records and BLAS triangles are made again on the device,
+ * its BLAS -- one per mesh, shared by all its instances -- keeps its topology and is refitted level by level in device memory, the world boxes of the mesh's
+ * instances are made on the device, the TLAS is built again on the host over the instance boxes and re-sent, and the flat tree that AOVs and giCTraceRays
+ * walk is refitted as well.  0 = off (default): such an edit rebuilds the scene, as before.  The image does not depend on the option; a refitted BLAS costs
+ * more to walk the further its mesh deformed, until the next full build.  The scene is rebuilt instead when: there is no host copy of the scene or
+ * GATLING_OPTIONS=incremental=0; fewer than 4 096 triangles are resident; the scene was built with inactive triangles; the flat tree has no level table (it
+ * was built on the device); an edited mesh is not part of the built scene, is hidden or has another instance count; a new position is not finite or beyond
+ * 1e18, or an instance of the mesh carries one beyond 1e18 in world space or has a transform that is not finite or not invertible; the new TLAS would be too
+ * deep for the layout's 16-entry stack; the device has no memory for the refits' boxes (32 bytes per node).  A visibility toggle due in the same render
+ * rebuilds on this layout.  GATLING_OPTIONS=blas_updates=0|1 overrides the option (hdGatling sets no scene options).  DESIGN.md section 6. */
+#define GI_C_SCENE_OPTION_BLAS_UPDATES 17
 int giCGetLookaheadStats(const GiCScene* scene, GiCLookaheadStats* out);
 int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value);
 /* [ext] closest hit of one ray through the device traversal kernel (parity tests of the BVH8 path).
@@ -716,6 +730,31 @@ int giCDebugSceneTlasCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t
  * from the host form of the same arithmetic (0 is the contract), <0 on error (no device, a null array, an index outside the vertices). */
 int giCDebugInstanceBounds(const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, const float* xforms16, uint32_t xformCount,
                            float* outBoxes6, uint32_t* outStatus);
+/* [ext] [debug] how often the scene was brought up to date by a vertex update of the two-level layout (GI_C_SCENE_OPTION_BLAS_UPDATES); counted neither in
+ * giCDebugSceneUpdateCounts nor in giCDebugSceneVertexUpdateCount. */
+int giCDebugSceneBlasUpdateCount(const GiCScene* scene, uint64_t* outCount);
+/* [ext] [debug] the two-level arrays resident on device `deviceIndex` of a scene rendered at least once, checked against the scene's current meshes after
+ * vertex updates in place.  Counted as differences: (a) a resident BLAS triangle that does not carry the build's `prim` at its place or, bytewise, the
+ * current corners of that face; (b) a resident BLAS node whose 80 bytes differ from the host form of the BLAS refit (gi_blas.h, children before parents) run
+ * over the host's copy of the build's topology and the current points; (d) a resident TLAS node or item that differs bytewise from a fresh build's over the
+ * current meshes (instance boxes do not depend on a BLAS's shape); (e) a resident per-instance traversal record that differs from the fresh one with its
+ * BLAS root replaced by the resident BLAS's.  (c), reported separately: out[2] counts the violations of the conservative check -- every node's dequantised
+ * slot box contains the padded boxes of all faces below it, every usable face is named by exactly one leaf slot.  Returns the number of differences plus those violations (0), <0
+ * on error.  out[0]: 1 when the two-level layout is in use (0: nothing was compared), [1] BLAS nodes compared, [2] conservative violations, [3] BLAS
+ * triangles compared. */
+int giCDebugSceneBlasCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t* out /* 4 */);
+/* [ext] [debug] device check of the BLAS refit kernels (gi_blas.hip k_blas_tris / k_blas_refit_level): one BLAS is built on the host over the mesh with
+ * points `a` (`faces`: 3 indices per face) as the scene build does, uploaded, and brought to points `b` by the kernels; the host form of the same arithmetic
+ * (gi_blas.h) does the same.  Returns the number of node and triangle-record bytes that differ between device and host (0 is the contract) -- with a == b
+ * (the same array, or the same positions) plus the bytes that differ from the build's --, <0 on error (no device, a null array, an index outside the
+ * vertices).  outNodes: nodes of the BLAS; outViolations: violations of the conservative check over the device's result. */
+int giCDebugBlasRefit(const GiCVertex* a, const GiCVertex* b, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, uint32_t* outNodes,
+                      uint32_t* outViolations);
+/* [ext] [debug] the host-only sibling: the host form of the BLAS refit alone, no device use.  Returns the number of bytes by which the refitted topology
+ * (imask, meta, childBase, triBase of every node; prim of every record) differs from the build's -- with the same positions in a and b, the number of node
+ * and record bytes that differ from the build's at all -- (0), <0 on error.  outNodes / outViolations as above. */
+int giCDebugBlasRefitHost(const GiCVertex* a, const GiCVertex* b, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, uint32_t* outNodes,
+                          uint32_t* outViolations);
 /* [ext] what the last scene sync derived from the visible meshes' materials, the state that picks a render's kernel variants: out[0] the material classes in
  * use (one bit each), [1] those with a textured material, [2] and [3] the same per shade class, [4] 1 when some visible triangle has cutout opacity.  Host
  * only: no device work. */
