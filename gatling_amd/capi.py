@@ -30,6 +30,7 @@ OPTION_RESYNC_REFITS = 14  # 1 (with options 12 and 13): a destroyed and a creat
 OPTION_INSTANCE_UPDATES = 15  # 1 (with option 13): new instance ids or another instance count of a built mesh are applied to the resident scene instead of rebuilding it (include/gi_c.h); 0 = off (default)
 OPTION_TLAS_UPDATES = 16  # 1: transform edits of a built two-level scene (OPTION_TWO_LEVEL) are applied to the resident scene -- moved instances' records, a new TLAS, a refit of the flat tree -- instead of rebuilding it (include/gi_c.h); 0 = off (default)
 OPTION_BLAS_UPDATES = 17  # 1: vertex edits of a built two-level scene are applied to the resident scene -- the mesh's BLAS refitted on the device, a new TLAS, a refit of the flat tree -- instead of rebuilding it; read only with OPTION_VERTEX_UPDATES wanted (include/gi_c.h); 0 = off (default)
+OPTION_TLAS_VISIBILITY = 18  # 1: visibility edits of a built two-level scene are applied to the resident scene -- ids, the id table and the instances' id bases renumbered on the device, a new TLAS over the visible instances -- instead of rebuilding it; read only with OPTION_VISIBILITY_UPDATES wanted (include/gi_c.h); 0 = off (default)
 OPTION_BVH_BUILD = 9  # 0 = host BVH builder (default), 1 = device builder (flat-layout scenes of more than 128 triangles)
 
 
@@ -180,6 +181,8 @@ SYMBOLS = [
     ("giCDebugSceneBlasUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugSceneBlasCheck", C.c_int, [_P, _U, C.POINTER(C.c_uint32)]),
     ("giCDebugBlasRefit", C.c_int, [_P, _P, _U, _P, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("giCDebugBlasRefitHost", C.c_int, [_P, _P, _U, _P, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("giCDebugSceneTlasVisibilityUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugSceneFlatIdCheck", C.c_int, [_P, _U, C.POINTER(C.c_uint32)]),
+    ("giCDebugPatchVisibilityTwoLevel", C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _U, _U, C.POINTER(C.c_uint32)]),
     ("giCDebugPathWalkStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugPathLobeStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugPathLot", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
@@ -291,6 +294,34 @@ def debug_blas_refit(vertices_a, vertices_b, faces, host_only=False):
     if n < 0:
         raise GiError("giCDebugBlasRefit failed: " + L.giCGetLastError().decode())
     return int(n), int(nodes.value), int(violations.value)
+
+
+def debug_patch_visibility_two_level(face_counts, hidden_before, hidden_after, seed=1):
+    """giCDebugPatchVisibilityTwoLevel: the device kernels of a visibility update of the two-level layout (k_patch_visibility2 / k_patch_inst_trav) over
+    synthetic records -- one instance per entry in scene order with `face_counts[i]` triangles, hidden before / after the edit where the flags say so, laid
+    out in a shuffled flat order drawn from `seed` -- against the host form of the same code, and the host form against a fresh numbering.  Returns
+    (differing, triangles): the words of TriRec::origId, the id table and InstTrav::triBase that differ, plus the host form's violations (0 is the contract),
+    and the resident triangles.  Needs an initialised device."""
+    L = load_library()
+    n = np.ascontiguousarray(face_counts, np.uint32)
+    hb = np.ascontiguousarray(hidden_before, np.uint8)
+    ha = np.ascontiguousarray(hidden_after, np.uint8)
+    if not (len(n) == len(hb) == len(ha)):
+        raise ValueError("debug_patch_visibility_two_level: one entry per instance in all three arrays")
+    tris = C.c_uint32(0)
+    v = L.giCDebugPatchVisibilityTwoLevel(n.ctypes.data_as(C.POINTER(C.c_uint32)), hb.ctypes.data_as(C.POINTER(C.c_uint8)), ha.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                          len(n), int(seed), C.byref(tris))
+    if v < 0:
+        raise GiError("giCDebugPatchVisibilityTwoLevel failed: " + L.giCGetLastError().decode())
+    return int(v), int(tris.value)
+
+
+class FlatIdCheck(int):
+    """Scene.flat_id_check's answer: the number of violations as an int, with what the hook reports beside it."""
+    visible_tris = 0
+    resident_tris = 0
+    hidden_instances = 0
+    two_level = 0
 
 
 class BlasCheck(int):
@@ -478,6 +509,26 @@ class Scene:
         if self.L.giCDebugSceneBlasUpdateCount(self.handle, C.byref(n)) != GI_C_OK:
             raise GiError("giCDebugSceneBlasUpdateCount failed")
         return int(n.value)
+
+    def tlas_visibility_update_count(self) -> int:
+        """giCDebugSceneTlasVisibilityUpdateCount: how often the scene was brought up to date by a visibility update of the two-level layout
+        (OPTION_TLAS_VISIBILITY; counted neither in update_counts() nor in visibility_update_count())."""
+        n = C.c_uint64(0)
+        if self.L.giCDebugSceneTlasVisibilityUpdateCount(self.handle, C.byref(n)) != GI_C_OK:
+            raise GiError("giCDebugSceneTlasVisibilityUpdateCount failed")
+        return int(n.value)
+
+    def flat_id_check(self, device: int = 0) -> "FlatIdCheck":
+        """giCDebugSceneFlatIdCheck: the flat records, the id table and the per-instance records resident on a device -- the ids of visible records are a
+        permutation of [0, visible), the table names each at its id, triBase + prim is the id, hidden records have zero edges.  Returns the violations (0) as a
+        FlatIdCheck: .visible_tris, .resident_tris, .hidden_instances, .two_level (1 when the layout is in use; 0: nothing was compared)."""
+        out = (C.c_uint32 * 4)()
+        v = self.L.giCDebugSceneFlatIdCheck(self.handle, device, out)
+        if v < 0:
+            raise GiError("giCDebugSceneFlatIdCheck failed: " + self.L.giCGetLastError().decode())
+        r = FlatIdCheck(v)
+        r.visible_tris, r.resident_tris, r.hidden_instances, r.two_level = int(out[0]), int(out[1]), int(out[2]), int(out[3])
+        return r
 
     def blas_check(self, device: int = 0) -> "BlasCheck":
         """giCDebugSceneBlasCheck: the two-level arrays resident on a device against the current meshes after vertex updates in place -- BLAS triangles, BLAS

@@ -6,7 +6,9 @@
 #include "gi_tlas.h"
 #include "gi_blas.h"
 #include "gi_pack.h"
+#include "gi_vispatch.h"
 
+#include <random>
 #include <unordered_map>
 constexpr uint32_t kIncrementalMinTris = 4096; // scenes with fewer triangles are not edited in place: they rebuild in no time (and must stay LDS-resident)
 // levels of a scene BVH: the deepest traversal variant keeps 16 stack entries in LDS and OVF_STACK = 40 in scratch; trav_node_pick does not bound-check the
@@ -320,6 +322,15 @@ static BlasTri makeBlasTri(const GiCVertex* vertices, const GiCFace* faces, uint
   return bt;
 }
 
+// one byte per flattened instance: 1 where its mesh is hidden (MeshBuild::hidden: visibility updates in place)
+template <class MB>
+static std::vector<uint8_t> hiddenOfInstances(const std::vector<MB>& meshBuilds, size_t instanceCount)
+{
+  std::vector<uint8_t> hidden(instanceCount, 0);
+  for (const MB& mb : meshBuilds) if (mb.hidden) for (const uint32_t inst : mb.inst) if (inst < instanceCount) hidden[inst] = 1;
+  return hidden;
+}
+
 template <class MB>
 int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vector<InstanceRec>& instances, size_t flatTris, size_t flatNodes,
     TwoLevelHost& out)
@@ -360,7 +371,9 @@ int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vec
     const float extent = (std::fabs(mlo[0]) + std::fabs(mlo[1]) + std::fabs(mlo[2])) + (std::fabs(mhi[0]) + std::fabs(mhi[1]) + std::fabs(mhi[2]));
     for (uint32_t ii = 0; ii < mb.instCount; ii++) {
       const uint32_t inst = mb.inst[ii];
-      instTrav[inst] = tlasMakeInstTrav(instances[inst], nodeBase, mb.triFirst + ii * (uint32_t)nf, mb.matFlags, extent);
+      // (idBase is triFirst at a build; after visibility updates in place -- updateVisibilityTwoLevel, which giCDebugSceneTlasCheck holds to this function --
+      // it is the id a fresh build of the visible meshes gives the mesh's first triangle, and a hidden mesh keeps the one it had)
+      instTrav[inst] = tlasMakeInstTrav(instances[inst], nodeBase, mb.idBase + ii * (uint32_t)nf, mb.matFlags, extent);
       // inactive triangles (bvh8.h): a face with an unusable OBJECT-space vertex is left out of the BLAS by the builder and out of this box; an unusable
       // instance keeps the inverted box (the builder leaves it out of the TLAS). A usable face whose WORLD-space vertex is unusable is inactive in the flat
       // tree but would be walked here: such scenes keep the flat layout
@@ -382,7 +395,16 @@ int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vec
     }
   }
   Bvh8 tlas; std::vector<uint32_t> tlasItems;
-  buildBvh8Boxes(instBoxes.data(), instances.size(), tlas, tlasItems);
+  { // the hidden rule (never at a build: buildScene leaves invisible meshes out; giCDebugSceneTlasCheck / giCDebugSceneBlasCheck over a resident scene whose
+    // meshes updateVisibilityTwoLevel hid): the TLAS does not name the instances of a hidden mesh; `instBoxes` keeps their true boxes
+    std::vector<uint8_t> hidden = hiddenOfInstances(meshBuilds, instances.size());
+    if (std::find(hidden.begin(), hidden.end(), (uint8_t)1) == hidden.end()) buildBvh8Boxes(instBoxes.data(), instances.size(), tlas, tlasItems);
+    else {
+      std::vector<float> masked(instBoxes);
+      tlasMaskHiddenBoxes(masked.data(), hidden.data(), instances.size());
+      buildBvh8Boxes(masked.data(), instances.size(), tlas, tlasItems);
+    }
+  }
   // per-lane stack: a TLAS level can leave a node group and an instance group behind, a BLAS level a node group
   if (blasTris.size() >= ((size_t)1 << 26)) {
     if (want > 0) fprintf(stderr, "[gatling_gi] two-level layout not used: 2^26 or more unique mesh triangles\n");
@@ -1017,7 +1039,7 @@ static int updateMaterials(GiCScene* s, bool& handled, UpdateCost& cost)
 //   partitioned layout: the parts of a hidden mesh are left out of the top tree (rebuildTop) and their records are left alone; only ids are renumbered.
 // MeshBuild::hidden / idBase hold the state; updateTransforms and updateMaterials respect it, so a hide composes with a move and a material edit, before
 // the same render too.  Falls back to buildScene (handled = false, not an error): no host copy of the scene, GATLING_OPTIONS=incremental=0, the two-level
-// layout (SceneView::flatOfOrig is indexed by the ids this renumbers), a toggled mesh that is not part of the built scene (it was invisible or had no valid
+// layout without GI_C_SCENE_OPTION_TLAS_VISIBILITY (SceneView::flatOfOrig is indexed by the ids this renumbers: updateVisibilityTwoLevel below), a toggled mesh that is not part of the built scene (it was invisible or had no valid
 // material when the scene was built: it has no records on the device), fewer than kIncrementalMinTris visible flattened triangles after the edit (every mesh
 // hidden included).  The caller has established that nothing but visibility toggles asked for the rebuild.
 // ---------------------------------------------------------------------------------------------------------------
@@ -1093,9 +1115,18 @@ static void applyVisibilityPlanOnHost(SceneHost& H, const VisibilityPlan& P)
   for (MeshBuild& mb : H.meshBuilds) { mb.hidden = P.hide[mb.meshIdx] != 0; mb.idBase = P.newBase[mb.meshIdx]; }
 }
 
+// GI_C_SCENE_OPTION_TLAS_VISIBILITY / GATLING_OPTIONS=tlas_visibility: visibility edits of a two-level scene are applied in place (updateVisibilityTwoLevel below)
+bool tlasVisibilityWanted(const GiCScene* s)
+{
+  const long o = optionValue("tlas_visibility", -1);
+  return o >= 0 ? o == 1 : s->optTlasVisibility == 1;
+}
+static int updateVisibilityTwoLevel(GiCScene* s, SceneHost& H, bool& handled, UpdateCost& cost);
+
 static int updateVisibility(GiCScene* s, bool& handled, UpdateCost& cost)
 {
   SceneHost* host = incrementalHost(s);
+  if (host && s->twoLevel && host->shadePacked && tlasVisibilityWanted(s)) return updateVisibilityTwoLevel(s, *host, handled, cost);
   if (!host || s->twoLevel || !host->shadePacked) return GI_C_OK;
   SceneHost& H = *host;
   const double t0 = nowMs();
@@ -1136,6 +1167,104 @@ static int updateVisibility(GiCScene* s, bool& handled, UpdateCost& cost)
   if (getenv("GATLING_BUILD_TIMING")) fprintf(stderr, "[gatling_gi] visibility update: %u mesh(es) hidden, %u shown, %u renumbered of %zu, %llu visible "
                                               "triangle(s) of %u resident, host %.2f ms, device %.2f ms\n", hides, shows, renumbered, H.meshBuilds.size(),
                                               (unsigned long long)visibleTris, s->triCount, t1 - t0, t2 - t1);
+  handled = true;
+  return GI_C_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Visibility updates on the two-level layout (opt-in: GI_C_SCENE_OPTION_TLAS_VISIBILITY / GATLING_OPTIONS=tlas_visibility=1, read with visibility updates
+// wanted).  Hiding a mesh of a built two-level scene changes no BLAS, vertex, shading record or instance box.  What changes:
+//   the scene-order ids behind the hidden mesh become a fresh build's -- TriRec::origId of the flat records (k_shade, k_aov and the tie-break read them) and
+//       InstTrav::triBase (k_trace_dyn2 forms triBase + prim, hashes it for cutouts and orders ties by it);
+//   SceneView::flatOfOrig, the table that turns such an id into a flat record, changes with them;
+//   the TLAS no longer names the hidden instances.
+// The flat tree of a two-level scene is unpartitioned and takes the flat layouts' treatment: zero edges at a hide, edges recomputed at a show, the boxes stay.
+//   host: planVisibility's table with VIS_HIDDEN_AFTER set for the instances of hidden meshes; the TLAS built over a copy of T.instBoxes in which those
+//       instances carry the inverted box (the builder leaves them out); the depth rule.  T.instBoxes keeps the true boxes: a show needs no bounds kernel.
+//   every device, on its own stream: the table, k_patch_visibility2 over the flat records and the id table, k_patch_inst_trav over the instances' records
+//       (gi_patch.hip; gi_vispatch.h has the per-item forms), the TLAS nodes and items.  Nothing is read back; the scene bounds stay the flat root's
+//       (conservative, as after a flat hide).
+//   host copies: MeshBuild::hidden / idBase, H.bvh.tris where still held, T.instTrav's triBase, the TLAS; H.flatOfOrig is made again from the host records
+//       or, where an update in place dropped them (H.hostTreeDropped), dropped with them -- only a build's upload reads it.
+// Every decision comes before the first resident write.  Declines (handled = false, not an error): what updateVisibility declines for but the layout, a scene
+// built with inactive triangles, the depth rule (a fresh build would leave the two-level layout), missing T.instTrav / T.instBoxes, the option off (the caller).
+// While a mesh is hidden, updateTransformsTwoLevel and updateVerticesTwoLevel keep its instances out of the TLAS they build (planTwoLevelEdit) and decline an
+// edit OF the hidden mesh.
+// ---------------------------------------------------------------------------------------------------------------
+static int updateVisibilityTwoLevel(GiCScene* s, SceneHost& H, bool& handled, UpdateCost& cost)
+{
+  TwoLevelHost& T = H.two;
+  const uint32_t instanceCount = (uint32_t)H.instances.size();
+  const bool timing = getenv("GATLING_BUILD_TIMING") != nullptr;
+  const double t0 = nowMs();
+  for (const GiCMesh* m : s->meshes) if (m->visToggled && m->builtInstances == 0xffffffffu) return GI_C_OK; // no records on the device: showing it rebuilds
+  if (s->stats.inactiveTriangleCount != 0u || H.partitioned || H.deviceBuilt) return GI_C_OK;
+  if (T.instTrav.size() != instanceCount || T.instBoxes.size() != 6u * (size_t)instanceCount) return GI_C_OK; // (cannot happen)
+  VisibilityPlan plan;
+  if (!planVisibility(s, H, [](const MeshBuild& mb) { return !mb.m->visible; }, plan)) return GI_C_OK; // (cannot happen: count changes ask for the rebuild)
+  if (plan.visibleTris < kIncrementalMinTris) return GI_C_OK; // (the floor: VISIBLE triangles, what a fresh build of the edited scene would hold)
+  const uint64_t visibleTris = plan.visibleTris; const uint32_t hides = plan.hides, shows = plan.shows, renumbered = plan.renumbered; const bool launch = plan.launch;
+  // --- the TLAS over the boxes of the instances that stay visible.  Nothing changes (a hidden mesh hidden again): nothing is built
+  std::vector<uint8_t> hiddenAfter(instanceCount, 0);
+  for (const MeshBuild& mb : H.meshBuilds) if (plan.hide[mb.meshIdx]) for (const uint32_t inst : mb.inst) if (inst < instanceCount) hiddenAfter[inst] = 1;
+  Bvh8 tlas; std::vector<uint32_t> tlasItems; double tlasMs = 0.0;
+  if (launch) {
+    std::vector<float> masked(T.instBoxes);
+    tlasMaskHiddenBoxes(masked.data(), hiddenAfter.data(), instanceCount);
+    const double ta = nowMs();
+    buildBvh8Boxes(masked.data(), instanceCount, tlas, tlasItems);
+    tlasMs = nowMs() - ta;
+    if (2u * tlas.maxDepth + T.blasDepth + 1u > 16u) {
+      if (timing) fprintf(stderr, "[gatling_gi] visibility update (two-level): the new TLAS is too deep for the 16-entry stack; the scene is rebuilt\n");
+      return GI_C_OK;
+    }
+  }
+  // --- decided.  The host copies: the records where they are still held, the MeshBuilds' state; then the table's extra bit for the kernel
+  applyVisibilityPlanOnHost(H, plan);
+  for (uint32_t i = 0; i < instanceCount; i++) if (hiddenAfter[i]) plan.patch[i].action |= VIS_HIDDEN_AFTER;
+  const std::vector<VisPatch>& patch = plan.patch;
+  if (launch) {
+    patchInstTravHost(T.instTrav.data(), instanceCount, patch.data());
+    if (!H.bvh.tris.empty() && H.flatOfOrig.size() == H.bvh.tris.size()) {
+      constexpr size_t CHUNK = 65536;
+      const size_t n = H.bvh.tris.size();
+      parallelOver((n + CHUNK - 1) / CHUNK, [&](size_t c) { // (one writer per word: the visible ids are a permutation)
+        for (size_t i = c * CHUNK; i < std::min(n, (c + 1) * CHUNK); i++) {
+          const TriRec& t = H.bvh.tris[i];
+          if (!hiddenAfter[t.instance] && t.origId < n) H.flatOfOrig[t.origId] = (uint32_t)i;
+        }
+      });
+    } else std::vector<uint32_t>().swap(H.flatOfOrig); // (stale with the dropped host records; nothing reads it before the next build makes it anew)
+  }
+  if (!(s->dirty & DIRTY_MATERIALS)) deriveSceneClasses(s, H, false); // (as updateVisibility: a material edit due as well runs behind and derives them itself)
+  const double t1 = nowMs();
+  // --- every device of the scene, on its own stream
+  const size_t bytesSent = launch ? patch.size() * sizeof(VisPatch) + tlas.nodes.size() * sizeof(Node8) + tlasItems.size() * sizeof(uint32_t) : 0u;
+  if (onSceneDevices(s, launch ? residentDeviceCount(s) : 0u, [&](SceneDevice& D, hipStream_t st) -> int {
+    int rc = GI_C_OK;
+    DeviceBuffer<VisPatch> dPatch;
+    if (D.dTris.count < s->triCount || D.dInstances.count < instanceCount || D.dTriShade.count < H.triShade.size() || D.dInstTrav.count < instanceCount ||
+        D.dFlatOfOrig.count < s->triCount) { setError("internal: the device holds less than the scene"); rc = GI_C_ERROR; }
+    if (rc == GI_C_OK && dPatch.upload(patch, st)) rc = GI_C_ERROR;
+    if (rc == GI_C_OK) {
+      launchPatchVisibility2(st, D.dTris.ptr, s->triCount, D.dInstances.ptr, instanceCount, dPatch.ptr, D.dTriShade.ptr, (uint32_t)H.triShade.size(),
+          D.dFlatOfOrig.ptr, s->triCount);
+      if (renumbered) launchPatchInstTrav(st, D.dInstTrav.ptr, instanceCount, dPatch.ptr);
+      if (hipGetLastError() != hipSuccess) rc = GI_C_ERROR;
+    }
+    if (rc == GI_C_OK && (D.dTlasNodes.upload(tlas.nodes, st) || D.dTlasItems.upload(tlasItems, st))) rc = GI_C_ERROR;
+    if (hipStreamSynchronize(st) != hipSuccess) rc = GI_C_ERROR;
+    if (rc != GI_C_OK) setError("visibility update (two-level): device error");
+    dPatch.release();
+    return rc;
+  }) != GI_C_OK) return GI_C_ERROR;
+  const size_t tlasNodeCount = launch ? tlas.nodes.size() : T.tlasNodes.size();
+  if (launch) { T.tlasNodes.swap(tlas.nodes); T.tlasItems.swap(tlasItems); T.tlasDepth = tlas.maxDepth; }
+  const double t2 = nowMs();
+  cost.uploadMs = t2 - t0; // (no scene tree was built: buildMs stays 0, the TLAS build over the instance boxes is part of the update's cost here)
+  if (timing) fprintf(stderr, "[gatling_gi] visibility update (two-level): %u mesh(es) hidden, %u shown, %u renumbered of %zu, %llu visible triangle(s) of %u "
+                              "resident, TLAS %zu node(s), host TLAS build %.2f ms, host rest %.2f ms, device %.2f ms, %zu bytes sent per device\n", hides, shows,
+                      renumbered, H.meshBuilds.size(), (unsigned long long)visibleTris, s->triCount, tlasNodeCount, tlasMs, (t1 - t0) - tlasMs, t2 - t1, bytesSent);
   handled = true;
   return GI_C_OK;
 }
@@ -2028,7 +2157,15 @@ static bool planTwoLevelEdit(const GiCScene* s, const SceneHost& H, const std::v
   E.boxes = T.instBoxes;
   for (uint32_t k = 0; k < jobCount; k++) memcpy(&E.boxes[6u * (size_t)jobs[k].instance], &result[7u * (size_t)k], 24);
   const double t1 = nowMs();
-  buildBvh8Boxes(E.boxes.data(), instanceCount, E.tlas, E.tlasItems);
+  { // the instances of meshes updateVisibilityTwoLevel hid stay out of the TLAS (E.boxes, the host copy behind the edit, keeps their true boxes)
+    const std::vector<uint8_t> hidden = hiddenOfInstances(H.meshBuilds, instanceCount);
+    if (std::find(hidden.begin(), hidden.end(), (uint8_t)1) == hidden.end()) buildBvh8Boxes(E.boxes.data(), instanceCount, E.tlas, E.tlasItems);
+    else {
+      std::vector<float> masked(E.boxes);
+      tlasMaskHiddenBoxes(masked.data(), hidden.data(), instanceCount);
+      buildBvh8Boxes(masked.data(), instanceCount, E.tlas, E.tlasItems);
+    }
+  }
   E.tlasMs = nowMs() - t1;
   if (2u * E.tlas.maxDepth + T.blasDepth + 1u > 16u) {
     if (timing) fprintf(stderr, "[gatling_gi] %s: the new TLAS is too deep for the 16-entry stack; the scene is rebuilt\n", what);
@@ -2099,7 +2236,9 @@ static int updateTransformsTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Up
     if (!mb.m->xformDirty) continue;
     const size_t nf = mb.m->faces.size();
     const uint32_t first = T.meshBlasTri[mb.meshIdx];
-    if (mb.hidden || mb.m->retired || nf >= ((size_t)1 << 26) || (size_t)first + nf > T.blasTris.size()) return GI_C_OK; // (cannot happen on this layout)
+    // a moved mesh that updateVisibilityTwoLevel hid declines to the rebuild: k_refit_tris would give its flat records their edges back.  (The rest cannot
+    // happen on this layout.)
+    if (mb.hidden || mb.m->retired || nf >= ((size_t)1 << 26) || (size_t)first + nf > T.blasTris.size()) return GI_C_OK;
     for (uint32_t ii = 0; ii < mb.instCount; ii++) {
       if (!mb.m->instDirty.empty() && !(ii < mb.m->instDirty.size() && mb.m->instDirty[ii])) continue;
       const InstanceRec ir = makeInstanceRec(mb.m, mb.meshIdx, ii);
@@ -2210,13 +2349,14 @@ static int updateVerticesTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Upda
   std::vector<Edited> edited;
   uint32_t scratchCount = 0;
   for (const GiCMesh* m : s->meshes) {
-    if (m->visToggled) return GI_C_OK; // (the visibility update declines on this layout: the scene is rebuilt anyway)
+    if (m->visToggled) return GI_C_OK; // (a vertex edit together with a toggle in one sync keeps rebuilding on this layout)
     if (!m->vertsEdited) continue;
     uint32_t b = 0;
     while (b < (uint32_t)H.meshBuilds.size() && H.meshBuilds[b].m != m) b++;
     if (b == (uint32_t)H.meshBuilds.size()) return GI_C_OK; // no records on the device
     const MeshBuild& mb = H.meshBuilds[b];
     const size_t nf = m->faces.size();
+    // (an edited mesh that updateVisibilityTwoLevel hid declines to the rebuild: k_refit_tris would give its flat records their edges back)
     if (mb.hidden || m->retired || mb.instCount == 0u || m->builtInstances != mb.instCount || mb.meshIdx >= T.meshBlasTri.size()) return GI_C_OK;
     if ((size_t)mb.vertexOffset + m->vertices.size() > H.verts.size() || nf == 0u || nf >= ((size_t)1 << 26)) return GI_C_OK;
     if (!gatherShadeRangeOk(shadeCount, mb.shadeBase, (uint32_t)nf)) return GI_C_OK; // (a range the kernels would refuse goes to the rebuild, never to stale records)
@@ -2403,6 +2543,143 @@ extern "C" int giCDebugSceneTlasCheck(const GiCScene* scene, uint32_t deviceInde
     out[2] = (uint32_t)fresh.tlasNodes.size(); out[3] = fresh.tlasDepth;
     return differ;
   } catch (const std::exception& e) { s->twoLevel = true; setError(std::string("giCDebugSceneTlasCheck: ") + e.what()); return -1; }
+}
+
+// giCDebugSceneFlatIdCheck: the flat records, the id table and the InstTrav records resident on a device against the rules a visibility update in place of the
+// two-level layout must keep (gi_vispatch.h flatIdViolations)
+extern "C" int giCDebugSceneFlatIdCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t* out)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!g_ctx.initialized || !s || !out) { setError("giCDebugSceneFlatIdCheck: bad arguments"); return -1; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  if (!s->host) { setError("giCDebugSceneFlatIdCheck: the scene has not been built (render it once)"); return -1; }
+  if (deviceIndex > s->replicas.size() || deviceIndex >= sceneDeviceCount(s)) { setError("giCDebugSceneFlatIdCheck: no such device copy"); return -1; }
+  const SceneHost& H = *s->host;
+  const uint32_t instanceCount = (uint32_t)H.instances.size();
+  out[0] = 0u; out[1] = s->triCount; out[2] = 0u; out[3] = s->twoLevel ? 1u : 0u;
+  if (!s->twoLevel) return 0;
+  try {
+    const std::vector<uint8_t> hidden = hiddenOfInstances(H.meshBuilds, instanceCount);
+    for (const uint8_t h : hidden) out[2] += h;
+    SceneDevice& D = sceneDevice(s, deviceIndex);
+    if (D.dTris.count < s->triCount || D.dFlatOfOrig.count < s->triCount || D.dInstTrav.count < instanceCount) { setError("giCDebugSceneFlatIdCheck: the device holds less than the scene"); return -1; }
+    std::vector<TriRec> tris(s->triCount); std::vector<uint32_t> flat(s->triCount); std::vector<InstTrav> instTrav(instanceCount);
+    bool ok = hipSetDevice(g_ctx.devs[D.slot].device) == hipSuccess;
+    ok = ok && (tris.empty() || hipMemcpy(tris.data(), D.dTris.ptr, tris.size() * sizeof(TriRec), hipMemcpyDeviceToHost) == hipSuccess);
+    ok = ok && (flat.empty() || hipMemcpy(flat.data(), D.dFlatOfOrig.ptr, flat.size() * sizeof(uint32_t), hipMemcpyDeviceToHost) == hipSuccess);
+    ok = ok && (instTrav.empty() || hipMemcpy(instTrav.data(), D.dInstTrav.ptr, instTrav.size() * sizeof(InstTrav), hipMemcpyDeviceToHost) == hipSuccess);
+    (void)hipSetDevice(g_ctx.device);
+    if (!ok) { setError("giCDebugSceneFlatIdCheck: download failed"); return -1; }
+    std::vector<uint8_t> seen(tris.size(), 0);
+    uint32_t bad = flatIdViolations(tris.data(), (uint32_t)tris.size(), flat.data(), (uint32_t)flat.size(), instTrav.data(), hidden.data(), instanceCount, seen.data(), out[0]);
+    // (the host copies the next update starts from: the instances' id bases, and the records and the table where they are still held)
+    for (uint32_t i = 0; i < instanceCount && i < (uint32_t)H.two.instTrav.size(); i++) if (H.two.instTrav[i].triBase != instTrav[i].triBase) bad++;
+    if (H.bvh.tris.size() == tris.size() && H.flatOfOrig.size() == flat.size())
+      for (size_t i = 0; i < tris.size(); i++) {
+        if (memcmp(&H.bvh.tris[i], &tris[i], sizeof(TriRec)) != 0) bad++;
+        if (tris[i].instance < instanceCount && !hidden[tris[i].instance] && tris[i].origId < flat.size() && H.flatOfOrig[tris[i].origId] != flat[tris[i].origId]) bad++;
+      }
+    return (int)bad;
+  } catch (const std::exception& e) { setError(std::string("giCDebugSceneFlatIdCheck: ") + e.what()); return -1; }
+}
+
+// giCDebugPatchVisibilityTwoLevel: k_patch_visibility2 + k_patch_inst_trav over synthetic records against the host form of the same code (gi_vispatch.h), and
+// the host form against the numbering a fresh build of the instances visible after the edit gives
+extern "C" int giCDebugPatchVisibilityTwoLevel(const uint32_t* faceCounts, const uint8_t* hiddenBefore, const uint8_t* hiddenAfter, uint32_t instanceCount,
+    uint32_t seed, uint32_t* outTris)
+{
+  if (!g_ctx.initialized) { setError("giCDebugPatchVisibilityTwoLevel before giCInitialize"); return -1; }
+  if (!faceCounts || !hiddenBefore || !hiddenAfter || instanceCount == 0u) { setError("giCDebugPatchVisibilityTwoLevel: bad arguments"); return -1; }
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < instanceCount; i++) total += faceCounts[i];
+  if (total == 0u || total >= (1ull << 26)) { setError("giCDebugPatchVisibilityTwoLevel: no triangles, or 2^26 and more"); return -1; }
+  try {
+    const uint32_t n = (uint32_t)total;
+    std::mt19937 rng(seed);
+    std::uniform_real_distribution<float> coord(-2.0f, 2.0f);
+    // --- the scene: a pool of shading records (their corners alone), one instance record each, id bases before and after as planVisibility forms them --
+    // a hidden instance keeps the base it had; before the edit that is the build's (all visible): it overlaps the ids of what lies behind it
+    constexpr uint32_t kPool = 97u;
+    std::vector<TriShade> shade(kPool);
+    for (TriShade& q : shade) { q = TriShade{}; for (int k = 0; k < 3; k++) for (int a = 0; a < 3; a++) q.p[k][a] = coord(rng); }
+    std::vector<InstanceRec> instances(instanceCount); std::vector<InstTrav> instTrav(instanceCount); std::vector<VisPatch> patch(instanceCount);
+    std::vector<uint32_t> baseBefore(instanceCount), first(instanceCount);
+    uint32_t built = 0, before = 0, after = 0;
+    for (uint32_t i = 0; i < instanceCount; i++) {
+      InstanceRec ir{}; const float o2w[12] = {1.0f + 0.01f * (float)(i % 7u), 0.1f, 0.0f, coord(rng), 0.0f, 0.9f, 0.2f, coord(rng), -0.1f, 0.0f, 1.1f, coord(rng)};
+      memcpy(ir.o2w, o2w, sizeof(o2w)); ir.mesh = i; instances[i] = ir;
+      first[i] = built;
+      baseBefore[i] = hiddenBefore[i] ? built : before;
+      const uint32_t baseAfter = hiddenAfter[i] ? baseBefore[i] : after;
+      const bool hb = hiddenBefore[i] != 0, ha = hiddenAfter[i] != 0;
+      patch[i] = VisPatch{(int32_t)(baseAfter - baseBefore[i]), (hb == ha ? VIS_KEEP : (ha ? VIS_HIDE : VIS_SHOW)) | (ha ? VIS_HIDDEN_AFTER : 0u)};
+      InstTrav tv{}; memcpy(tv.o2w, o2w, sizeof(o2w)); tv.blasRoot = i; tv.triBase = baseBefore[i]; tv.matFlags = 0x01000000u | i; tv.slack = 1.0f; instTrav[i] = tv;
+      built += faceCounts[i]; if (!hb) before += faceCounts[i]; if (!ha) after += faceCounts[i];
+    }
+    // --- the records in a shuffled flat order; the table as the build and the edits before leave it: visible records named, every other word stale
+    std::vector<uint32_t> place(n);
+    for (uint32_t i = 0; i < n; i++) place[i] = i;
+    std::shuffle(place.begin(), place.end(), rng);
+    std::vector<TriRec> tris(n); std::vector<uint32_t> flat(n, 0xdeadbeefu); std::vector<uint8_t> hiddenA(instanceCount);
+    for (uint32_t i = 0; i < instanceCount; i++) {
+      hiddenA[i] = hiddenAfter[i] ? 1 : 0;
+      for (uint32_t f = 0; f < faceCounts[i]; f++) {
+        TriRec t{}; t.instance = i; t.prim = f; t.origId = baseBefore[i] + f; t.matFlags = instTrav[i].matFlags; t.vi[0] = (first[i] + f) % kPool;
+        refit_flatten(instances[i].o2w, shade[t.vi[0]].p, t.v0, t.e1, t.e2);
+        if (hiddenBefore[i]) for (int a = 0; a < 3; a++) { t.e1[a] = 0.0f; t.e2[a] = 0.0f; }
+        const uint32_t at = place[first[i] + f];
+        tris[at] = t;
+        if (!hiddenBefore[i]) flat[t.origId] = at;
+      }
+    }
+    // --- the device
+    std::vector<TriRec> devTris(n); std::vector<uint32_t> devFlat(n); std::vector<InstTrav> devTrav(instanceCount);
+    DeviceBuffer<TriRec> dTris; DeviceBuffer<InstanceRec> dInstances; DeviceBuffer<VisPatch> dPatch; DeviceBuffer<TriShade> dShade; DeviceBuffer<uint32_t> dFlat;
+    DeviceBuffer<InstTrav> dTrav;
+    hipStream_t st = g_ctx.stream;
+    bool ok = hipSetDevice(g_ctx.device) == hipSuccess && dTris.upload(tris, st) == GI_C_OK && dInstances.upload(instances, st) == GI_C_OK &&
+        dPatch.upload(patch, st) == GI_C_OK && dShade.upload(shade, st) == GI_C_OK && dFlat.upload(flat, st) == GI_C_OK && dTrav.upload(instTrav, st) == GI_C_OK;
+    if (ok) {
+      launchPatchVisibility2(st, dTris.ptr, n, dInstances.ptr, instanceCount, dPatch.ptr, dShade.ptr, kPool, dFlat.ptr, n);
+      launchPatchInstTrav(st, dTrav.ptr, instanceCount, dPatch.ptr);
+      ok = hipGetLastError() == hipSuccess;
+    }
+    ok = ok && hipMemcpyAsync(devTris.data(), dTris.ptr, (size_t)n * sizeof(TriRec), hipMemcpyDeviceToHost, st) == hipSuccess &&
+        hipMemcpyAsync(devFlat.data(), dFlat.ptr, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+        hipMemcpyAsync(devTrav.data(), dTrav.ptr, (size_t)instanceCount * sizeof(InstTrav), hipMemcpyDeviceToHost, st) == hipSuccess;
+    ok = hipStreamSynchronize(st) == hipSuccess && ok;
+    dTris.release(); dInstances.release(); dPatch.release(); dShade.release(); dFlat.release(); dTrav.release();
+    if (!ok) { setError("giCDebugPatchVisibilityTwoLevel: device error"); return -1; }
+    // --- the host form, and the words that differ
+    patchVisibilityTwoLevelHost(tris.data(), n, instances.data(), instanceCount, patch.data(), shade.data(), kPool, flat.data(), n);
+    patchInstTravHost(instTrav.data(), instanceCount, patch.data());
+    int differ = 0;
+    for (uint32_t i = 0; i < n; i++) {
+      differ += devTris[i].origId != tris[i].origId;
+      differ += devFlat[i] != flat[i];
+      for (int a = 0; a < 3; a++) differ += (memcmp(&devTris[i].e1[a], &tris[i].e1[a], 4) != 0) + (memcmp(&devTris[i].e2[a], &tris[i].e2[a], 4) != 0);
+      TriRec a = devTris[i], b = tris[i]; // (every other word of the record stays)
+      a.origId = b.origId = 0u; memset(a.e1, 0, 24); memset(b.e1, 0, 24);
+      differ += memcmp(&a, &b, sizeof(TriRec)) != 0;
+    }
+    for (uint32_t i = 0; i < instanceCount; i++) {
+      differ += devTrav[i].triBase != instTrav[i].triBase;
+      InstTrav a = devTrav[i], b = instTrav[i]; a.triBase = b.triBase = 0u;
+      differ += memcmp(&a, &b, sizeof(InstTrav)) != 0;
+    }
+    // --- the host form against a fresh numbering of the instances visible after the edit
+    std::vector<uint8_t> seen(n, 0); uint32_t visible = 0;
+    uint32_t bad = flatIdViolations(tris.data(), n, flat.data(), n, instTrav.data(), hiddenA.data(), instanceCount, seen.data(), visible);
+    if (visible != after) bad++;
+    for (uint32_t i = 0; i < n; i++) {
+      const TriRec& t = tris[i];
+      if (hiddenA[t.instance]) continue;
+      TriRec w{}; refit_flatten(instances[t.instance].o2w, shade[t.vi[0]].p, w.v0, w.e1, w.e2);
+      if (memcmp(w.v0, t.v0, 36) != 0) bad++; // (v0, e1, e2: the record is whole again)
+    }
+    if (outTris) *outTris = n;
+    return differ + (int)bad;
+  } catch (const std::exception& e) { setError(std::string("giCDebugPatchVisibilityTwoLevel: ") + e.what()); return -1; }
 }
 
 // giCDebugInstanceBounds: k_inst_bounds + k_inst_finish over one mesh under `xformCount` instance transforms against the host form of the same arithmetic
@@ -2636,7 +2913,9 @@ int syncSceneGeometry(GiCScene* s)
   // (a vertex update of the two-level layout has a counter of its own as well: giCDebugSceneVertexUpdateCount keeps counting what it counted)
   const uint32_t vertexCounter = s->twoLevel && blasUpdatesWanted(s) && incrementalHost(s) ? (uint32_t)UPDATE_BLAS : (uint32_t)UPDATE_VERTEX;
   if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_BVH) && !s->rebuildDue && anyVerts, updateVertices, vertexCounter, anyVis ? 0u : (uint32_t)DIRTY_BVH, DIRTY_BVH, 0u);
-  if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_BVH) && !s->rebuildDue && visibilityUpdatesWanted(s), updateVisibility, UPDATE_VISIBILITY, DIRTY_BVH, 0u, 0u);
+  // (a visibility update of the two-level layout has a counter of its own as well: giCDebugSceneVisibilityUpdateCount keeps counting what it counted)
+  const uint32_t visibilityCounter = s->twoLevel && tlasVisibilityWanted(s) && incrementalHost(s) ? (uint32_t)UPDATE_TLAS_VISIBILITY : (uint32_t)UPDATE_VISIBILITY;
+  if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_BVH) && !s->rebuildDue && visibilityUpdatesWanted(s), updateVisibility, visibilityCounter, DIRTY_BVH, 0u, 0u);
   if (rc == GI_C_OK) rc = run((s->dirty & DIRTY_MATERIALS) && !(s->dirty & DIRTY_BVH), updateMaterials, UPDATE_MATERIAL, DIRTY_MATERIALS, DIRTY_BVH, DIRTY_BVH);
   // (a transform update of the two-level layout has a counter of its own: giCDebugSceneUpdateCounts keeps counting what it counted)
   const uint32_t transformCounter = s->twoLevel && tlasUpdatesWanted(s) && incrementalHost(s) ? (uint32_t)UPDATE_TLAS : (uint32_t)UPDATE_TRANSFORM;

@@ -322,6 +322,7 @@ int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value)
   if (option == GI_C_SCENE_OPTION_INSTANCE_UPDATES) { scene->optInstanceUpdates = value == 1 ? 1 : 0; return GI_C_OK; }
   if (option == GI_C_SCENE_OPTION_TLAS_UPDATES) { scene->optTlasUpdates = value == 1 ? 1 : 0; return GI_C_OK; }
   if (option == GI_C_SCENE_OPTION_BLAS_UPDATES) { scene->optBlasUpdates = value == 1 ? 1 : 0; return GI_C_OK; } // (read only with option 12 wanted)
+  if (option == GI_C_SCENE_OPTION_TLAS_VISIBILITY) { scene->optTlasVisibility = value == 1 ? 1 : 0; return GI_C_OK; } // (read only with option 11 wanted)
   setError("unknown scene option"); return GI_C_ERROR;
 }
 

@@ -349,7 +349,7 @@ struct SceneHost {
   bool reordered = false;
 };
 
-enum : uint32_t { UPDATE_FULL = 0, UPDATE_TRANSFORM = 1, UPDATE_MATERIAL = 2, UPDATE_VISIBILITY = 3, UPDATE_VERTEX = 4, UPDATE_TOPOLOGY = 5, UPDATE_TLAS = 6, UPDATE_BLAS = 7 }; // GiCScene::updateCounts
+enum : uint32_t { UPDATE_FULL = 0, UPDATE_TRANSFORM = 1, UPDATE_MATERIAL = 2, UPDATE_VISIBILITY = 3, UPDATE_VERTEX = 4, UPDATE_TOPOLOGY = 5, UPDATE_TLAS = 6, UPDATE_BLAS = 7, UPDATE_TLAS_VISIBILITY = 8 }; // GiCScene::updateCounts
 struct GiCScene : SceneDevice {
   std::mutex mutex;
   uint32_t dirty = DIRTY_ALL;
@@ -405,8 +405,8 @@ struct GiCScene : SceneDevice {
   // a look-ahead window traced under another generation is not served from
   uint64_t generation = 0;
   // syncSceneGeometry, by UPDATE_*: full builds and incremental updates (giCDebugSceneUpdateCounts: the first three; giCDebugSceneVisibilityUpdateCount,
-  // giCDebugSceneVertexUpdateCount, giCDebugSceneTopologyUpdateCount, giCDebugSceneTlasUpdateCount, giCDebugSceneBlasUpdateCount)
-  uint64_t updateCounts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // giCDebugSceneVertexUpdateCount, giCDebugSceneTopologyUpdateCount, giCDebugSceneTlasUpdateCount, giCDebugSceneBlasUpdateCount, giCDebugSceneTlasVisibilityUpdateCount)
+  uint64_t updateCounts[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   int32_t optVisibilityUpdates = 0; // GI_C_SCENE_OPTION_VISIBILITY_UPDATES: 1 = visibility edits are applied to the resident scene (updateVisibility)
   int32_t optVertexUpdates = 0; // GI_C_SCENE_OPTION_VERTEX_UPDATES: 1 = vertex edits refit the resident tree (updateVertices)
   // DIRTY_BVH was raised by something other than giCSetMeshVisibility / giCSetMeshVertices since the last syncSceneGeometry (raiseRebuild): the rebuild is due
@@ -430,6 +430,9 @@ struct GiCScene : SceneDevice {
   // GI_C_SCENE_OPTION_BLAS_UPDATES: 1 = vertex edits of a two-level scene are applied to the resident scene (updateVerticesTwoLevel; read only with vertex
   // updates wanted)
   int32_t optBlasUpdates = 0;
+  // GI_C_SCENE_OPTION_TLAS_VISIBILITY: 1 = visibility edits of a two-level scene are applied to the resident scene (updateVisibilityTwoLevel; read only with
+  // visibility updates wanted)
+  int32_t optTlasVisibility = 0;
   std::vector<GiCMesh*> retiredMeshes; // destroyed meshes the resident scene still refers to (GiCMesh::retired): freed by buildScene and with the scene
   ~GiCScene() { for (GiCMesh* m : retiredMeshes) delete m; }
 };
@@ -457,6 +460,7 @@ void nodeBounds(const Node8& n, float box[6]);               // dequantised boun
 bool instanceUpdatesWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_INSTANCE_UPDATES / GATLING_OPTIONS=instance_updates (with topology updates wanted)
 bool tlasUpdatesWanted(const GiCScene* s);                   // GI_C_SCENE_OPTION_TLAS_UPDATES / GATLING_OPTIONS=tlas_updates
 bool blasUpdatesWanted(const GiCScene* s);                   // GI_C_SCENE_OPTION_BLAS_UPDATES / GATLING_OPTIONS=blas_updates
+bool tlasVisibilityWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_TLAS_VISIBILITY / GATLING_OPTIONS=tlas_visibility (with visibility updates wanted)
 bool topologyUpdatesWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_TOPOLOGY_UPDATES / GATLING_OPTIONS=topology_updates
 int syncSceneGeometry(GiCScene* s);                          // brings the device scene up to date with the host-side edits (incremental or full build)
 // dirty flags of a material-side edit: DIRTY_MATERIALS alone once the scene / the mesh is part of a built scene (the incremental path), else with DIRTY_BVH

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gi_types.h"
+#include "gi_vispatch.h"
 
 namespace gi {
 
@@ -82,11 +83,16 @@ void launchPatchMatFlags(hipStream_t s, TriRec* tris, uint32_t triCount, const I
     uint32_t meshCount);
 // gi_patch.hip: a visibility edit applied to the device-resident triangles (gi_build.cpp updateVisibility).  One VisPatch per flattened instance: the change
 // of its triangles' scene-order ids, and whether its records are left alone, made unhittable (both edges zeroed) or given their edges back (recomputed from
-// the mesh triangle's shading record and the instance transform with the scene build's operations in its order)
-struct VisPatch { int32_t idDelta; uint32_t action; };
-constexpr uint32_t VIS_KEEP = 0u, VIS_HIDE = 1u, VIS_SHOW = 2u;
+// the mesh triangle's shading record and the instance transform with the scene build's operations in its order) -- gi_vispatch.h has the record
 void launchPatchVisibility(hipStream_t s, TriRec* tris, uint32_t triCount, const InstanceRec* instances, uint32_t instanceCount, const VisPatch* patchOfInstance,
     const TriShade* triShade, uint32_t shadeCount);
+// gi_patch.hip: a visibility edit applied to a resident two-level scene (gi_build.cpp updateVisibilityTwoLevel, GI_C_SCENE_OPTION_TLAS_VISIBILITY).
+// launchPatchVisibility2 is launchPatchVisibility over the flat records plus, in the same pass, flatOfOrig[new id] = i for every record whose instance is
+// visible after the edit (VisPatch::action carries VIS_HIDDEN_AFTER for the others; `flatCount`: words of the table); launchPatchInstTrav moves
+// InstTrav::triBase of every instance by its idDelta (gi_vispatch.h has both per-item forms)
+void launchPatchVisibility2(hipStream_t s, TriRec* tris, uint32_t triCount, const InstanceRec* instances, uint32_t instanceCount, const VisPatch* patchOfInstance,
+    const TriShade* triShade, uint32_t shadeCount, uint32_t* flatOfOrig, uint32_t flatCount);
+void launchPatchInstTrav(hipStream_t s, InstTrav* instTrav, uint32_t instanceCount, const VisPatch* patchOfInstance);
 // gi_patch.hip: a part the device builder made over the `nf` records at tris + triFirst (gi_build.cpp updateTopology) put where it lives: its `partNodes`
 // nodes copied from the builder's block to nodes + nodeOff with child and triangle bases made absolute, and `idAdd` added to the ids of its records (the
 // builder numbered them by position in the part).  The caller has checked both ranges against the arrays' sizes

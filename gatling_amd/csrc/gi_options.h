@@ -68,6 +68,8 @@
 //                                  are applied to the resident scene (gi_build.cpp updateTransformsTwoLevel)
 //   blas_updates         -1        -1 = the scene option decides (GI_C_SCENE_OPTION_BLAS_UPDATES), 0 / 1 = vertex edits of a two-level scene rebuild it / are
 //                                  applied to the resident scene (gi_build.cpp updateVerticesTwoLevel); read only with vertex_updates wanted
+//   tlas_visibility      -1        -1 = the scene option decides (GI_C_SCENE_OPTION_TLAS_VISIBILITY), 0 / 1 = visibility edits of a two-level scene rebuild it
+//                                  / are applied to the resident scene (gi_build.cpp updateVisibilityTwoLevel); read only with visibility_updates wanted
 //   phase_stats          0         counting builds: print k_path's phase split / k_trace_dyn's lane accounting
 #pragma once
 

@@ -1,6 +1,8 @@
 // gi_patch.hip -- edits applied in place to the device-resident triangle records:
 //   k_patch_mat_flags   TriRec::matFlags rewritten after a material edit (gi_build.cpp updateMaterials)
 //   k_patch_visibility  scene-order ids renumbered, records of hidden instances made unhittable / restored (gi_build.cpp updateVisibility; below)
+//   k_patch_visibility2 the same on a two-level scene, with the id -> record table made again in the pass (gi_build.cpp updateVisibilityTwoLevel; below)
+//   k_patch_inst_trav   InstTrav::triBase of renumbered instances of a two-level scene (the same edit; below)
 //   k_place_part        a device-built part of an appended mesh moved into the scene's node array, its ids made scene-order (gi_build.cpp updateTopology; below)
 //   k_clone_parts       new instances of resident meshes made from live sibling instances: records and subtrees copied and rebased (gi_build.cpp updateTopology; below)
 //
@@ -76,6 +78,33 @@ __global__ __launch_bounds__(kPatchBlock) void k_patch_visibility(TriRec* __rest
     }
     for (int a = 0; a < 3; a++) { t.e1[a] = p[1][a] - p[0][a]; t.e2[a] = p[2][a] - p[0][a]; }
   }
+}
+
+// k_patch_visibility2 / k_patch_inst_trav.  The same edit on a resident TWO-LEVEL scene (opt-in: GI_C_SCENE_OPTION_TLAS_VISIBILITY; gi_build.cpp
+// updateVisibilityTwoLevel).  The flat records take k_patch_visibility's treatment (k_aov walks the flat tree, k_shade reads its records); in the same pass
+// every record whose instance is visible AFTER the edit, and whose id or visibility changed, stores its own index at its NEW id in flatOfOrig -- the table
+// k_trace_dyn2 turns a scene-order id (InstTrav::triBase + BlasTri::prim) into a flat record index with.  Records of hidden instances never store there:
+// their stale ids overlap the ids the meshes behind them just received, and that overlap is the one way this pass can go wrong.  The visible ids are a
+// permutation of [0, visibleTris), so every word has one writer: no atomics, any order; entries at and beyond visibleTris are never read and stay stale.
+// The per-record form is gi_vispatch.h vis2_patch_record, which the host runs too (giCDebugPatchVisibilityTwoLevel compares the words).
+// Memory: the pass reads one 64-byte line per resident triangle (origId, instance, vi[0] share it) and stores one dword into it per renumbered record, six
+// more per hidden / shown record, and one SCATTERED dword into flatOfOrig per renumbered or shown visible record: records lie in leaf order, ids in scene
+// order, so a wave's 64 stores touch up to 64 lines of the table.  The table and the VisPatch entries are read by nobody else in the pass.
+// k_patch_inst_trav: one thread per instance, InstTrav::triBase += idDelta where it is not zero -- one dword of the 128-byte record; matFlags stays.
+__global__ __launch_bounds__(kPatchBlock) void k_patch_visibility2(TriRec* __restrict__ tris, uint32_t triCount, const InstanceRec* __restrict__ instances,
+    uint32_t instanceCount, const VisPatch* __restrict__ patchOfInstance, const TriShade* __restrict__ triShade, uint32_t shadeCount,
+    uint32_t* __restrict__ flatOfOrig, uint32_t flatCount)
+{
+  const uint32_t i = blockIdx.x * kPatchBlock + threadIdx.x;
+  if (i >= triCount) return;
+  vis2_patch_record(tris, i, instances, instanceCount, patchOfInstance, triShade, shadeCount, flatOfOrig, flatCount);
+}
+
+__global__ __launch_bounds__(kPatchBlock) void k_patch_inst_trav(InstTrav* __restrict__ instTrav, uint32_t instanceCount, const VisPatch* __restrict__ patchOfInstance)
+{
+  const uint32_t i = blockIdx.x * kPatchBlock + threadIdx.x;
+  if (i >= instanceCount) return;
+  vis2_patch_inst_trav(instTrav, i, patchOfInstance);
 }
 
 // k_place_part.  A mesh appended to a partitioned scene (opt-in: GI_C_SCENE_OPTION_TOPOLOGY_UPDATES) whose parts the device builder made: buildBvh8Device ran
@@ -164,6 +193,20 @@ void launchPatchVisibility(hipStream_t s, TriRec* tris, uint32_t triCount, const
   if (triCount == 0u) return;
   hipLaunchKernelGGL(k_patch_visibility, dim3((triCount + kPatchBlock - 1u) / kPatchBlock), dim3(kPatchBlock), 0, s, tris, triCount, instances, instanceCount,
       patchOfInstance, triShade, shadeCount);
+}
+
+void launchPatchVisibility2(hipStream_t s, TriRec* tris, uint32_t triCount, const InstanceRec* instances, uint32_t instanceCount, const VisPatch* patchOfInstance,
+    const TriShade* triShade, uint32_t shadeCount, uint32_t* flatOfOrig, uint32_t flatCount)
+{
+  if (triCount == 0u) return;
+  hipLaunchKernelGGL(k_patch_visibility2, dim3((triCount + kPatchBlock - 1u) / kPatchBlock), dim3(kPatchBlock), 0, s, tris, triCount, instances, instanceCount,
+      patchOfInstance, triShade, shadeCount, flatOfOrig, flatCount);
+}
+
+void launchPatchInstTrav(hipStream_t s, InstTrav* instTrav, uint32_t instanceCount, const VisPatch* patchOfInstance)
+{
+  if (instanceCount == 0u) return;
+  hipLaunchKernelGGL(k_patch_inst_trav, dim3((instanceCount + kPatchBlock - 1u) / kPatchBlock), dim3(kPatchBlock), 0, s, instTrav, instanceCount, patchOfInstance);
 }
 
 void launchPatchMatFlags(hipStream_t s, TriRec* tris, uint32_t triCount, const InstanceRec* instances, uint32_t instanceCount, const uint32_t* wordOfMesh,

@@ -382,7 +382,8 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * giCDebugGatherShade and giCDebugSceneShadeCheck, and for giCDebugPathLobeStats and giCDebugPathLot, and for GI_C_SCENE_OPTION_INSTANCE_UPDATES,
  * giCDebugSceneInstanceUpdateCount and giCDebugCloneInstance, and for GI_C_SCENE_OPTION_TLAS_UPDATES, giCDebugSceneTlasUpdateCount, giCDebugSceneTlasCheck
  * and giCDebugInstanceBounds, and for GI_C_SCENE_OPTION_BLAS_UPDATES, giCDebugSceneBlasUpdateCount, giCDebugSceneBlasCheck, giCDebugBlasRefit and
- * giCDebugBlasRefitHost. */
+ * giCDebugBlasRefitHost, and for GI_C_SCENE_OPTION_TLAS_VISIBILITY, giCDebugSceneTlasVisibilityUpdateCount, giCDebugSceneFlatIdCheck and
+ * giCDebugPatchVisibilityTwoLevel. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -620,6 +621,20 @@ int giCGetRenderStats(const GiCScene* scene, GiCRenderStats* out);
  * deep for the layout's 16-entry stack; the device has no memory for the refits' boxes (32 bytes per node).  A visibility toggle due in the same render
  * rebuilds on this layout.  GATLING_OPTIONS=blas_updates=0|1 overrides the option (hdGatling sets no scene options).  DESIGN.md section 6. */
 #define GI_C_SCENE_OPTION_BLAS_UPDATES 17
+/* [ext] Incremental visibility edits on the two-level layout; read only when visibility updates are wanted (GI_C_SCENE_OPTION_VISIBILITY_UPDATES, or
+ * GATLING_OPTIONS=visibility_updates=1): value 1 = a giCSetMeshVisibility on a mesh of a built two-level scene is applied to the resident scene by the next
+ * giCRender when nothing but visibility toggles asks for a rebuild: no BLAS, vertex, shading record or instance box changes; the scene-order ids of the
+ * meshes behind a hidden one become a fresh build's in the flat records and in the per-instance traversal records, the table from such an id to its flat
+ * record is made again in the same device pass, the flat records of a hidden mesh get zero edges (recomputed at the show), and the TLAS is built again on
+ * the host over the boxes of the visible instances and re-sent.  0 = off (default): such an edit rebuilds the scene, as before.  The image does not depend
+ * on the option; the flat tree that AOVs and giCTraceRays walk keeps the boxes of hidden geometry until the next full build.  The scene is rebuilt instead
+ * when: there is no host copy of the scene or GATLING_OPTIONS=incremental=0; a toggled mesh has no records on the device (it was invisible or without a
+ * valid material at the build); fewer than 4 096 triangles stay visible; the scene was built with inactive triangles; the new TLAS would be too deep for the
+ * layout's 16-entry stack.  While a mesh is hidden, a transform or vertex edit OF THAT MESH rebuilds the scene (options 16 and 17 decline); edits of visible
+ * meshes keep their paths and leave the hidden instances out of the TLAS.  A material edit due in the same render runs behind the visibility update, a
+ * transform edit behind both; a vertex edit together with a toggle in one render rebuilds.  GATLING_OPTIONS=tlas_visibility=0|1 overrides the option
+ * (hdGatling sets no scene options).  DESIGN.md section 6. */
+#define GI_C_SCENE_OPTION_TLAS_VISIBILITY 18
 int giCGetLookaheadStats(const GiCScene* scene, GiCLookaheadStats* out);
 int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value);
 /* [ext] closest hit of one ray through the device traversal kernel (parity tests of the BVH8 path).
@@ -755,6 +770,24 @@ int giCDebugBlasRefit(const GiCVertex* a, const GiCVertex* b, uint32_t vertexCou
  * and record bytes that differ from the build's at all -- (0), <0 on error.  outNodes / outViolations as above. */
 int giCDebugBlasRefitHost(const GiCVertex* a, const GiCVertex* b, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, uint32_t* outNodes,
                           uint32_t* outViolations);
+/* [ext] [debug] how often the scene was brought up to date by a visibility update of the two-level layout (GI_C_SCENE_OPTION_TLAS_VISIBILITY); counted neither
+ * in giCDebugSceneUpdateCounts nor in giCDebugSceneVisibilityUpdateCount. */
+int giCDebugSceneTlasVisibilityUpdateCount(const GiCScene* scene, uint64_t* outCount);
+/* [ext] [debug] the flat triangle records, the id table (scene-order id -> flat record) and the per-instance traversal records resident on device
+ * `deviceIndex` of a scene rendered at least once, downloaded and checked.  Returns the number of violations of: the ids of the records of visible instances
+ * are a permutation of [0, visible triangles); the table names each of them at its id; its instance's triBase + prim is its id; records of hidden instances
+ * have zero edges (0), <0 on error.  out[0]: visible triangles, [1] resident triangles, [2] hidden instances, [3] 1 when the two-level layout is in use (0:
+ * nothing was compared). */
+int giCDebugSceneFlatIdCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t* out /* 4 */);
+/* [ext] [debug] device check of the kernels of a visibility update of the two-level layout (gi_patch.hip k_patch_visibility2 / k_patch_inst_trav).  The
+ * caller describes `instanceCount` instances in scene order: faceCounts[i] triangles each, hiddenBefore[i] / hiddenAfter[i] != 0 where the instance is hidden
+ * before / after the edit.  The hook makes synthetic flat records of all of them in a shuffled order drawn from `seed`, the state a build and the edits
+ * before leave (ids over the instances visible before, zero edges and stale ids in the hidden ones, a table with stale words), applies the edit by both
+ * kernels and by the host form of the same code (gi_vispatch.h), and checks the host form against the numbering a fresh build of the instances visible
+ * after gives.  Returns the number of words of TriRec::origId, the table and InstTrav::triBase (and of the records' edges) that differ between device and
+ * host form, plus the host form's violations of that numbering (0 is the contract), <0 on error.  outTris: resident triangles. */
+int giCDebugPatchVisibilityTwoLevel(const uint32_t* faceCounts, const uint8_t* hiddenBefore, const uint8_t* hiddenAfter, uint32_t instanceCount, uint32_t seed,
+                                    uint32_t* outTris);
 /* [ext] what the last scene sync derived from the visible meshes' materials, the state that picks a render's kernel variants: out[0] the material classes in
  * use (one bit each), [1] those with a textured material, [2] and [3] the same per shade class, [4] 1 when some visible triangle has cutout opacity.  Host
  * only: no device work. */
