@@ -31,6 +31,7 @@ OPTION_INSTANCE_UPDATES = 15  # 1 (with option 13): new instance ids or another 
 OPTION_TLAS_UPDATES = 16  # 1: transform edits of a built two-level scene (OPTION_TWO_LEVEL) are applied to the resident scene -- moved instances' records, a new TLAS, a refit of the flat tree -- instead of rebuilding it (include/gi_c.h); 0 = off (default)
 OPTION_BLAS_UPDATES = 17  # 1: vertex edits of a built two-level scene are applied to the resident scene -- the mesh's BLAS refitted on the device, a new TLAS, a refit of the flat tree -- instead of rebuilding it; read only with OPTION_VERTEX_UPDATES wanted (include/gi_c.h); 0 = off (default)
 OPTION_TLAS_VISIBILITY = 18  # 1: visibility edits of a built two-level scene are applied to the resident scene -- ids, the id table and the instances' id bases renumbered on the device, a new TLAS over the visible instances -- instead of rebuilding it; read only with OPTION_VISIBILITY_UPDATES wanted (include/gi_c.h); 0 = off (default)
+OPTION_TLAS_ONLY = 19  # 1: a scene that takes the two-level layout (OPTION_TWO_LEVEL 1, or 2^26 flattened triangles) is built without the flat BVH8 -- the flat records stay in scene order, the non-colour AOVs walk the TLAS (k_aov2), the scene bounds come from the instance boxes and the edits in place of options 16 - 18 run without the flat refit; read at the scene build only (include/gi_c.h); 0 = off (default)
 OPTION_BVH_BUILD = 9  # 0 = host BVH builder (default), 1 = device builder (flat-layout scenes of more than 128 triangles)
 
 
@@ -182,6 +183,7 @@ SYMBOLS = [
     ("giCDebugBlasRefit", C.c_int, [_P, _P, _U, _P, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("giCDebugBlasRefitHost", C.c_int, [_P, _P, _U, _P, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("giCDebugSceneTlasVisibilityUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugSceneFlatIdCheck", C.c_int, [_P, _U, C.POINTER(C.c_uint32)]),
+    ("giCDebugSceneFlatTreeState", C.c_int, [_P, _U, C.POINTER(C.c_uint64)]),
     ("giCDebugPatchVisibilityTwoLevel", C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _U, _U, C.POINTER(C.c_uint32)]),
     ("giCDebugPathWalkStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugPathLobeStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
@@ -529,6 +531,14 @@ class Scene:
         r = FlatIdCheck(v)
         r.visible_tris, r.resident_tris, r.hidden_instances, r.two_level = int(out[0]), int(out[1]), int(out[2]), int(out[3])
         return r
+
+    def flat_tree_state(self, device: int = 0) -> dict:
+        """giCDebugSceneFlatTreeState: what a scene rendered at least once holds of the flat tree (OPTION_TLAS_ONLY).  Returns {"two_level", "treeless" (1: built
+        without the flat tree), "resident_nodes" (flat nodes on `device`), "host_node_bytes"}."""
+        out = (C.c_uint64 * 4)()
+        if self.L.giCDebugSceneFlatTreeState(self.handle, device, out) != GI_C_OK:
+            raise GiError("giCDebugSceneFlatTreeState failed: " + self.L.giCGetLastError().decode())
+        return {"two_level": int(out[0]), "treeless": int(out[1]), "resident_nodes": int(out[2]), "host_node_bytes": int(out[3])}
 
     def blas_check(self, device: int = 0) -> "BlasCheck":
         """giCDebugSceneBlasCheck: the two-level arrays resident on a device against the current meshes after vertex updates in place -- BLAS triangles, BLAS

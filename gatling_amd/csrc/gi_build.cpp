@@ -295,7 +295,8 @@ static void deriveSceneClasses(GiCScene* s, const SceneHost& H, bool newTree)
 
 // Two-level layout (SceneView::tlasNodes ...): built next to the flat BVH for instanced scenes that do not fit LDS.  The flat
 // arrays stay (k_shade reads the hit's TriRec, k_aov / giCTraceRays traverse them); the two-level ones are what k_trace_dyn2 walks,
-// and they are small: one BLAS per MESH instead of one subtree per instance, so traversal stays in the caches.
+// and they are small: one BLAS per MESH instead of one subtree per instance, so traversal stays in the caches.  (With GI_C_SCENE_OPTION_TLAS_ONLY the flat
+// NODES are not built at all -- buildSceneTreeless below: the flat records stay, in scene order, and k_aov2 walks these arrays for the AOVs as well.)
 // The BLAS of one mesh (buildTwoLevel; giCDebugBlasRefit): a tree over the padded object-space boxes of its faces.  A face with an unusable corner keeps an
 // inverted box: the builder leaves it out, and it does not widen mlo / mhi, the union of the usable faces' boxes
 static void buildMeshBlas(const GiCVertex* vertices, const GiCFace* faces, size_t nf, Bvh8& b, std::vector<uint32_t>& order, float mlo[3], float mhi[3])
@@ -331,6 +332,8 @@ static std::vector<uint8_t> hiddenOfInstances(const std::vector<MB>& meshBuilds,
   return hidden;
 }
 
+// flatNodes == 0: the caller has no flat tree (buildScene's route for GI_C_SCENE_OPTION_TLAS_ONLY, and the checks of a scene built that way).  "Beyond LDS" is
+// then what sceneFitsLds answers for the triangles alone -- more than LDS_TRIS of them --, and the automatic rule on node bytes is not consulted.
 template <class MB>
 int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vector<InstanceRec>& instances, size_t flatTris, size_t flatNodes,
     TwoLevelHost& out)
@@ -415,9 +418,13 @@ int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vec
     return GI_C_OK;
   }
   s->twoLevel = true;
-  if (getenv("GATLING_BUILD_TIMING")) fprintf(stderr,
+  if (getenv("GATLING_BUILD_TIMING")) {
+    if (flatNodes) fprintf(stderr,
       "[gatling_gi] two-level: TLAS %zu nodes over %zu instances, %zu BLAS nodes, %zu mesh triangles (flat: %zu nodes, %zu triangles)\n",
                                               tlas.nodes.size(), instances.size(), blasNodes.size(), blasTris.size(), flatNodes, flatTris);
+    else fprintf(stderr, "[gatling_gi] two-level: TLAS %zu nodes over %zu instances, %zu BLAS nodes, %zu mesh triangles (no flat tree was built; %zu flat "
+                         "records in scene order)\n", tlas.nodes.size(), instances.size(), blasNodes.size(), blasTris.size(), flatTris);
+  }
   out.tlasNodes.swap(tlas.nodes); out.tlasItems.swap(tlasItems); out.blasNodes.swap(blasNodes); out.blasTris.swap(blasTris); out.instTrav.swap(instTrav);
   out.instBoxes.swap(instBoxes); out.meshBlasTri.swap(meshBlasTri); out.tlasDepth = tlas.maxDepth; out.blasDepth = blasDepth;
   out.meshBlasNode.swap(meshBlasNode); out.meshBlasLevels.swap(meshBlasLevels);
@@ -461,7 +468,8 @@ static int uploadSceneTo(GiCScene* s, SceneDevice& D, const SceneHost& H, hipStr
     return GI_C_ERROR;
   if (D.dMeshes.upload(H.meshRecs, st) || D.dSceneData.upload(H.sceneData, st)) return GI_C_ERROR;
   if (uploadTexturesTo(s, D, st) != GI_C_OK) return GI_C_ERROR;
-  if (!H.deviceBuilt && (D.dNodes.upload(H.bvh.nodes, st) || D.dTris.upload(H.bvh.tris, st))) return GI_C_ERROR; // (device-built: the builder writes them)
+  if (H.treeless) { D.dNodes.release(); if (D.dTris.upload(H.bvh.tris, st)) return GI_C_ERROR; } // (no flat tree: no device holds flat nodes)
+  else if (!H.deviceBuilt && (D.dNodes.upload(H.bvh.nodes, st) || D.dTris.upload(H.bvh.tris, st))) return GI_C_ERROR; // (device-built: the builder writes them)
   if (D.dInstances.upload(H.instances, st) || D.dVerts.upload(H.verts, st) || D.dMaterials.upload(H.mats, st)) return GI_C_ERROR;
   HIP_TRY(hipStreamSynchronize(st)); // host vectors may go out of scope
   return GI_C_OK;
@@ -517,6 +525,33 @@ static void setSceneBounds(GiCScene* s, const std::vector<Node8>& nodes)
   s->boundsValid = true;
 }
 
+// ... and of a two-level scene without the flat tree (SceneHost::treeless), at its build and after every edit in place: the union of the padded world boxes of
+// the instances the TLAS names (gi_tlas.h tlas_scene_bounds), under the same pad and the same validity rule
+static void setSceneBoundsFromInstances(GiCScene* s, const SceneHost& H)
+{
+  const size_t n = H.instances.size();
+  s->boundsValid = false;
+  if (H.two.instBoxes.size() != 6u * n) return; // (cannot happen)
+  const std::vector<uint8_t> hidden = hiddenOfInstances(H.meshBuilds, n);
+  float b[6]; bool valid = false;
+  tlas_scene_bounds(H.two.instBoxes.data(), hidden.data(), n, b, valid);
+  if (valid) memcpy(s->bounds, b, sizeof(b));
+  s->boundsValid = valid;
+}
+
+// inactive triangles among scene-order records by bvh8.cpp's rule (prepareRange); perMesh[meshIdx] = the mesh's count
+static uint32_t countInactive(const std::vector<TriRec>& tris, const SceneHost& H, std::vector<uint32_t>& perMesh)
+{
+  uint32_t inactive = 0;
+  perMesh.assign(H.meshBuilds.size(), 0u);
+  for (const TriRec& t : tris) {
+    bool ok = true;
+    for (int a = 0; a < 3; a++) ok = ok && usableCoordinate(t.v0[a]) && usableCoordinate(t.v0[a] + t.e1[a]) && usableCoordinate(t.v0[a] + t.e2[a]);
+    if (!ok) { inactive++; perMesh[H.instances[t.instance].mesh]++; }
+  }
+  return inactive;
+}
+
 // one line per mesh with inactive triangles (bvh8.h "Inactive items"); perMesh[meshIdx] = its inactive count
 static void warnInactive(const std::vector<MeshBuild>& meshBuilds, const std::vector<uint32_t>& perMesh)
 {
@@ -565,13 +600,8 @@ static int buildSceneOnDevice(GiCScene* s, std::unique_ptr<SceneHost>& hostPtr, 
   SceneHost& H = *hostPtr;
   const uint32_t n = (uint32_t)tris.size();
   // inactive triangles by bvh8.cpp's rule (prepareRange), counted here as well: the statistic and the per-mesh warnings are the host path's
-  uint32_t inactive = 0;
-  std::vector<uint32_t> perMesh(H.meshBuilds.size(), 0u);
-  for (const TriRec& t : tris) {
-    bool ok = true;
-    for (int a = 0; a < 3; a++) ok = ok && usableCoordinate(t.v0[a]) && usableCoordinate(t.v0[a] + t.e1[a]) && usableCoordinate(t.v0[a] + t.e2[a]);
-    if (!ok) { inactive++; perMesh[H.instances[t.instance].mesh]++; }
-  }
+  std::vector<uint32_t> perMesh;
+  const uint32_t inactive = countInactive(tris, H, perMesh);
   s->twoLevel = false;
   // (bvhBuildMs / uploadMs split as on the host path: flattening and the build, then the shading records and the uploads)
   double buildMs = nowMs() - t0;
@@ -616,6 +646,52 @@ static int buildSceneOnDevice(GiCScene* s, std::unique_ptr<SceneHost>& hostPtr, 
   H.bvh = Bvh8{}; H.bvh.maxDepth = first.maxDepth; H.bvh.activeTris = first.activeTris; H.bvh.levelStart = first.levelStart;
   H.triFaceId.clear(); H.flatOfOrig.clear();
   return finishBuild(s, hostPtr, first.nodeCount, n, std::vector<Node8>{first.root}, buildMs, uploadMs, " (device build)");
+}
+
+// GI_C_SCENE_OPTION_TLAS_ONLY / GATLING_OPTIONS=tlas_only: a scene that wants the two-level layout is built without the flat tree (buildSceneTreeless below)
+bool tlasOnlyWanted(const GiCScene* s)
+{
+  const long o = optionValue("tlas_only", -1);
+  return o >= 0 ? o == 1 : s->optTlasOnly == 1;
+}
+// is the two-level layout wanted for a scene of `flatTris` flattened triangles, before any flat tree exists?  buildTwoLevel's rules but the one on node bytes,
+// which needs that tree
+static bool twoLevelWantedWithoutTree(const GiCScene* s, size_t flatTris)
+{
+  const long want = optionValue("two_level", s->optTwoLevel);
+  return want > 0 || (want < 0 && flatTris >= ((size_t)1 << 26));
+}
+
+// buildScene's route for two-level scenes without the flat tree (GI_C_SCENE_OPTION_TLAS_ONLY): the TLAS and the BLASes are built over the meshes, the flat
+// RECORDS are the flattening loop's, in scene order (origId == index: flatOfOrig is the identity, the face ids are faceIdOf), and no flat node is built, sent
+// or kept.  The caller has established: the option and the layout are wanted, more than LDS_TRIS triangles, none of them inactive.  DEVICE_BUILD_FALLBACK:
+// buildTwoLevel declined (it has said why) and nothing was changed -- buildScene goes on as without the option.
+static int buildSceneTreeless(GiCScene* s, std::unique_ptr<SceneHost>& hostPtr, std::vector<TriRec>& tris, std::vector<int32_t>& faceIdOf, double t0)
+{
+  SceneHost& H = *hostPtr;
+  if (buildTwoLevel(s, H.meshBuilds, H.instances, tris.size(), 0u, H.two) != GI_C_OK) return GI_C_ERROR;
+  if (!s->twoLevel) { H.two = TwoLevelHost{}; return DEVICE_BUILD_FALLBACK; }
+  if (tris.size() >= (1u << 28)) {
+    setError("scene has 2^28 or more triangles after instancing: the hit record packs (triangle, material class) into 32 bits");
+    return GI_C_ERROR;
+  }
+  const uint32_t n = (uint32_t)tris.size();
+  s->stats.inactiveTriangleCount = 0u;
+  H.treeless = true;
+  H.bvh = Bvh8{}; H.bvh.maxDepth = 1u; H.bvh.activeTris = n;
+  H.flatOfOrig.resize(n);
+  for (uint32_t i = 0; i < n; i++) H.flatOfOrig[i] = i;
+  const double t1 = nowMs();
+  // beyond LDS by construction: shading records, and TriRec::vi[0] names the triangle's record
+  H.shadePacked = true; H.triShade.clear(); H.triGeomNormal.clear();
+  const std::vector<uint32_t> shadeBaseOfMesh = buildShadeRecords(H);
+  for (TriRec& t : tris) t.vi[0] = shadeBaseOfMesh[H.instances[t.instance].mesh] + t.prim;
+  H.bvh.tris.swap(tris); H.triFaceId.swap(faceIdOf);
+  ensureReplicas(s);
+  if (onSceneDevices(s, sceneDeviceCount(s), [&](SceneDevice& D, hipStream_t st) { return uploadSceneTo(s, D, H, st); }) != GI_C_OK) return GI_C_ERROR;
+  const int rc = finishBuild(s, hostPtr, 0u, n, std::vector<Node8>{}, t1 - t0, nowMs() - t1, " (two-level, no flat tree)");
+  setSceneBoundsFromInstances(s, *s->host);
+  return rc;
 }
 
 int buildScene(GiCScene* s)
@@ -669,6 +745,15 @@ int buildScene(GiCScene* s)
         && tris.size() * sizeof(Node8) < ((size_t)1 << 32);
     if (device) {
       const int rc = buildSceneOnDevice(s, hostPtr, tris, faceIdOf, t0);
+      if (rc != DEVICE_BUILD_FALLBACK) return rc;
+    }
+  }
+  // two-level scenes without the flat tree (GI_C_SCENE_OPTION_TLAS_ONLY / tlas_only): read only when the layout is wanted, for scenes beyond LDS (more than
+  // LDS_TRIS triangles; a smaller scene could be LDS-resident) without inactive triangles.  A decline of buildTwoLevel falls through to the flat build
+  if (tlasOnlyWanted(s) && twoLevelWantedWithoutTree(s, tris.size()) && !instances.empty() && !sceneFitsLds(0u, tris.size())) {
+    std::vector<uint32_t> perMesh;
+    if (countInactive(tris, H, perMesh) == 0u) {
+      const int rc = buildSceneTreeless(s, hostPtr, tris, faceIdOf, t0);
       if (rc != DEVICE_BUILD_FALLBACK) return rc;
     }
   }
@@ -1183,7 +1268,8 @@ static int updateVisibility(GiCScene* s, bool& handled, UpdateCost& cost)
 //       instances carry the inverted box (the builder leaves them out); the depth rule.  T.instBoxes keeps the true boxes: a show needs no bounds kernel.
 //   every device, on its own stream: the table, k_patch_visibility2 over the flat records and the id table, k_patch_inst_trav over the instances' records
 //       (gi_patch.hip; gi_vispatch.h has the per-item forms), the TLAS nodes and items.  Nothing is read back; the scene bounds stay the flat root's
-//       (conservative, as after a flat hide).
+//       (conservative, as after a flat hide) -- on a scene without the flat tree (SceneHost::treeless) they are made again from the boxes of the instances
+//       that are visible after the edit (setSceneBoundsFromInstances): another edit in place may have narrowed them to the visible ones in between.
 //   host copies: MeshBuild::hidden / idBase, H.bvh.tris where still held, T.instTrav's triBase, the TLAS; H.flatOfOrig is made again from the host records
 //       or, where an update in place dropped them (H.hostTreeDropped), dropped with them -- only a build's upload reads it.
 // Every decision comes before the first resident write.  Declines (handled = false, not an error): what updateVisibility declines for but the layout, a scene
@@ -1260,6 +1346,8 @@ static int updateVisibilityTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Up
   }) != GI_C_OK) return GI_C_ERROR;
   const size_t tlasNodeCount = launch ? tlas.nodes.size() : T.tlasNodes.size();
   if (launch) { T.tlasNodes.swap(tlas.nodes); T.tlasItems.swap(tlasItems); T.tlasDepth = tlas.maxDepth; }
+  // (without the flat tree the bounds are the visible instances' boxes: a show must widen them again where an edit in between narrowed them)
+  if (launch && H.treeless) setSceneBoundsFromInstances(s, H);
   const double t2 = nowMs();
   cost.uploadMs = t2 - t0; // (no scene tree was built: buildMs stays 0, the TLAS build over the instance boxes is part of the update's cost here)
   if (timing) fprintf(stderr, "[gatling_gi] visibility update (two-level): %u mesh(es) hidden, %u shown, %u renumbered of %zu, %llu visible triangle(s) of %u "
@@ -2097,7 +2185,9 @@ static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
 // ---------------------------------------------------------------------------------------------------------------
 // What the updates in place of the two-level layout share behind their bounds jobs (updateTransformsTwoLevel, updateVerticesTwoLevel): the padded world
 // boxes and statuses of the jobs' instances from the primary device, the TLAS over all boxes with the decision, the plan of the flat tree's refit, the
-// per-device commit and the host copies.
+// per-device commit and the host copies.  On a scene built without the flat tree (SceneHost::treeless, GI_C_SCENE_OPTION_TLAS_ONLY) there is no refit to plan,
+// allocate for or launch and no root to read back: k_refit_tris alone keeps the flat records a fresh build's bytes, and the scene bounds are made again from
+// the instance boxes (setSceneBoundsFromInstances).
 struct TwoLevelEdit {
   std::vector<float> boxes; Bvh8 tlas; std::vector<uint32_t> tlasItems; // all instance boxes with the jobs' new ones; the TLAS over them
   std::vector<uint32_t> editedOfInstance; std::vector<std::pair<uint32_t, uint32_t>> runs; // the jobs' instances: one word each; (first, count) of consecutive ones
@@ -2106,8 +2196,12 @@ struct TwoLevelEdit {
 };
 struct FlatRefitScratch {
   DeviceBuffer<float> boxes; DeviceBuffer<uint32_t> edited; DeviceBuffer<RefitRange> ranges;
+  // (a scene without the flat tree -- nodeCount 0 -- has no level to refit: k_refit_tris's table alone)
   int alloc(uint32_t nodeCount, const TwoLevelEdit& E)
-  { const int a = boxes.alloc((size_t)nodeCount * 8u), b = a ? a : edited.alloc(E.editedOfInstance.size()); return b ? b : ranges.alloc(E.ranges.size()); }
+  {
+    if (nodeCount == 0u) return edited.alloc(E.editedOfInstance.size());
+    const int a = boxes.alloc((size_t)nodeCount * 8u), b = a ? a : edited.alloc(E.editedOfInstance.size()); return b ? b : ranges.alloc(E.ranges.size());
+  }
   void release() { boxes.release(); edited.release(); ranges.release(); }
 };
 
@@ -2175,6 +2269,7 @@ static bool planTwoLevelEdit(const GiCScene* s, const SceneHost& H, const std::v
   for (uint32_t k = 0; k < jobCount; k++) E.editedOfInstance[jobs[k].instance] = 1u;
   for (uint32_t i = 0; i < instanceCount; i++)
     if (E.editedOfInstance[i]) { if (!E.runs.empty() && E.runs.back().first + E.runs.back().second == i) E.runs.back().second++; else E.runs.emplace_back(i, 1u); }
+  if (H.treeless) return true; // (no flat tree: nothing to refit)
   std::vector<RefitUnit> units{RefitUnit{0u, &H.bvh.levelStart}};
   return planRefitLevels(units, s->nodeCount, E.ranges, E.levels); // (false cannot happen: the levels of a tree inside the node array)
 }
@@ -2195,14 +2290,15 @@ static int commitTwoLevelEdit(GiCScene* s, const SceneHost& H, SceneDevice& D, h
   }
   if (rc == GI_C_OK && (D.dTlasNodes.upload(E.tlas.nodes, st) || D.dTlasItems.upload(E.tlasItems, st))) rc = GI_C_ERROR;
   copy(scratch.edited.ptr, E.editedOfInstance.data(), E.editedOfInstance.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-  copy(scratch.ranges.ptr, E.ranges.data(), E.ranges.size() * sizeof(RefitRange), hipMemcpyHostToDevice);
+  if (!H.treeless) copy(scratch.ranges.ptr, E.ranges.data(), E.ranges.size() * sizeof(RefitRange), hipMemcpyHostToDevice);
   if (rc == GI_C_OK) {
+    // (the flat records stay a fresh build's bytes on every scene; the levels and the root belong to the flat tree: a scene without it has neither)
     launchRefitTris(st, D.dTris.ptr, s->triCount, D.dInstances.ptr, instanceCount, scratch.edited.ptr, D.dTriShade.ptr, shadeCount);
-    for (const RefitLevel& lv : E.levels) launchRefitLevel(st, D.dNodes.ptr, s->nodeCount, scratch.boxes.ptr, scratch.ranges.ptr + lv.first, lv.ranges, lv.threads,
+    if (!H.treeless) for (const RefitLevel& lv : E.levels) launchRefitLevel(st, D.dNodes.ptr, s->nodeCount, scratch.boxes.ptr, scratch.ranges.ptr + lv.first, lv.ranges, lv.threads,
         D.dTris.ptr, s->triCount, D.dInstances.ptr, instanceCount, D.dTriShade.ptr, shadeCount);
     if (hipGetLastError() != hipSuccess) { setError(std::string(what) + ": launch failed"); rc = GI_C_ERROR; }
   }
-  if (D.slot == 0u) copy(&root, D.dNodes.ptr, sizeof(Node8), hipMemcpyDeviceToHost); // (the refit is deterministic: every device holds the same bytes)
+  if (D.slot == 0u && !H.treeless) copy(&root, D.dNodes.ptr, sizeof(Node8), hipMemcpyDeviceToHost); // (the refit is deterministic: every device holds the same bytes)
   return rc;
 }
 
@@ -2211,7 +2307,8 @@ static void finishTwoLevelEdit(GiCScene* s, SceneHost& H, TwoLevelEdit& E, std::
 {
   TwoLevelHost& T = H.two;
   T.instTrav.swap(instTrav); T.instBoxes.swap(E.boxes); T.tlasNodes.swap(E.tlas.nodes); T.tlasItems.swap(E.tlasItems); T.tlasDepth = E.tlas.maxDepth;
-  setSceneBounds(s, std::vector<Node8>{root});
+  if (H.treeless) setSceneBoundsFromInstances(s, H); // (the boxes just swapped in; hidden instances stay out, as out of the TLAS)
+  else setSceneBounds(s, std::vector<Node8>{root});
   if (!H.hostTreeDropped) {
     std::vector<Node8>().swap(H.bvh.nodes); std::vector<TriRec>().swap(H.bvh.tris); std::vector<int32_t>().swap(H.triFaceId);
     H.hostTreeDropped = true;
@@ -2224,7 +2321,7 @@ static int updateTransformsTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Up
   const char* const what = "transform update (two-level)";
   const uint32_t instanceCount = (uint32_t)H.instances.size(), shadeCount = (uint32_t)H.triShade.size();
   if (s->triCount < kIncrementalMinTris || !H.shadePacked || s->stats.inactiveTriangleCount != 0u) return GI_C_OK; // (the floor: resident triangles)
-  if (H.deviceBuilt || H.partitioned || H.bvh.levelStart.size() < 2u || H.bvh.levelStart.back() != s->nodeCount) return GI_C_OK;
+  if (H.deviceBuilt || H.partitioned || (!H.treeless && (H.bvh.levelStart.size() < 2u || H.bvh.levelStart.back() != s->nodeCount))) return GI_C_OK;
   if (T.instTrav.size() != instanceCount || T.instBoxes.size() != 6u * (size_t)instanceCount || T.meshBlasTri.size() != H.meshBuilds.size()) return GI_C_OK; // (cannot happen)
   const bool timing = getenv("GATLING_BUILD_TIMING") != nullptr;
   const double t0 = nowMs();
@@ -2339,7 +2436,7 @@ static int updateVerticesTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Upda
   const uint32_t instanceCount = (uint32_t)H.instances.size(), shadeCount = (uint32_t)H.triShade.size();
   const uint32_t blasNodeCount = (uint32_t)T.blasNodes.size(), blasTriCount = (uint32_t)T.blasTris.size();
   if (s->triCount < kIncrementalMinTris || !H.shadePacked || s->stats.inactiveTriangleCount != 0u) return GI_C_OK; // (the floor: resident triangles)
-  if (H.deviceBuilt || H.partitioned || H.bvh.levelStart.size() < 2u || H.bvh.levelStart.back() != s->nodeCount) return GI_C_OK;
+  if (H.deviceBuilt || H.partitioned || (!H.treeless && (H.bvh.levelStart.size() < 2u || H.bvh.levelStart.back() != s->nodeCount))) return GI_C_OK;
   if (T.instTrav.size() != instanceCount || T.instBoxes.size() != 6u * (size_t)instanceCount || T.meshBlasTri.size() != H.meshBuilds.size() ||
       T.meshBlasNode.size() != H.meshBuilds.size() || T.meshBlasLevels.size() != H.meshBuilds.size()) return GI_C_OK; // (cannot happen)
   const bool timing = getenv("GATLING_BUILD_TIMING") != nullptr;

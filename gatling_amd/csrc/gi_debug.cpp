@@ -204,6 +204,9 @@ extern "C" int giCDebugValidateSceneBvh(const GiCScene* scene, uint32_t deviceIn
   std::lock_guard<std::mutex> guard(s->mutex);
   if (!s->host) { setError("giCDebugValidateSceneBvh: the scene has not been built (render it once)"); return -1; }
   if (deviceIndex > s->replicas.size() || deviceIndex >= sceneDeviceCount(s)) { setError("giCDebugValidateSceneBvh: no such device copy"); return -1; }
+  // (a result here would be made up: there is no tree to download, check or hash -- giCDebugSceneTlasCheck and giCDebugSceneBlasCheck hold what the scene walks)
+  if (s->host->treeless) { setError("giCDebugValidateSceneBvh: the scene was built without the flat tree (GI_C_SCENE_OPTION_TLAS_ONLY): there is no flat BVH to "
+                                    "validate"); return -1; }
   SceneDevice& D = sceneDevice(s, deviceIndex);
   const uint32_t nodeCount = s->nodeCount, triCount = s->triCount;
   std::vector<Node8> nodes(nodeCount); std::vector<TriRec> tris(triCount);
@@ -279,6 +282,21 @@ extern "C" int giCDebugValidateSceneBvh(const GiCScene* scene, uint32_t deviceIn
   if (outBuiltOnDevice) *outBuiltOnDevice = s->host->deviceBuilt ? 1 : 0;
   if (outDigest) *outDigest = h;
   return violations;
+}
+
+// giCDebugSceneFlatTreeState: what a built scene holds of the flat tree (GI_C_SCENE_OPTION_TLAS_ONLY)
+extern "C" int giCDebugSceneFlatTreeState(const GiCScene* scene, uint32_t deviceIndex, uint64_t out[4])
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!g_ctx.initialized || !s || !out) { setError("giCDebugSceneFlatTreeState: bad arguments"); return GI_C_ERROR; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  if (!s->host) { setError("giCDebugSceneFlatTreeState: the scene has not been built (render it once)"); return GI_C_ERROR; }
+  if (deviceIndex > s->replicas.size() || deviceIndex >= sceneDeviceCount(s)) { setError("giCDebugSceneFlatTreeState: no such device copy"); return GI_C_ERROR; }
+  const SceneDevice& D = sceneDevice(s, deviceIndex);
+  out[0] = s->twoLevel ? 1u : 0u; out[1] = s->host->treeless ? 1u : 0u;
+  out[2] = D.dNodes.ptr ? (uint64_t)D.dNodes.count : 0u;
+  out[3] = (uint64_t)s->host->bvh.nodes.size() * sizeof(Node8);
+  return GI_C_OK;
 }
 
 // giCDebugRefitBvh: the refit's arithmetic (gi_refit.h, what gi_refit.hip's kernels run) on the host -- a tree built over A, refitted to B, validated against B

@@ -347,6 +347,10 @@ struct SceneHost {
   // a mesh adopted the records of the one it replaced (updateTopology, GI_C_SCENE_OPTION_RESYNC_REFITS): the order of meshBuilds is no longer the scene's, and
   // scene-order ids are accumulated over GiCScene::meshes (gi_build.cpp sceneOrder)
   bool reordered = false;
+  // a two-level scene built without the flat tree (GI_C_SCENE_OPTION_TLAS_ONLY): bvh.nodes / levelStart are empty and no device holds flat nodes
+  // (GiCScene::nodeCount is 0); bvh.tris are the flat records in scene order (origId == index, flatOfOrig the identity); the scene bounds come from the
+  // instance boxes (gi_tlas.h tlas_scene_bounds); k_aov2 makes the AOVs
+  bool treeless = false;
 };
 
 enum : uint32_t { UPDATE_FULL = 0, UPDATE_TRANSFORM = 1, UPDATE_MATERIAL = 2, UPDATE_VISIBILITY = 3, UPDATE_VERTEX = 4, UPDATE_TOPOLOGY = 5, UPDATE_TLAS = 6, UPDATE_BLAS = 7, UPDATE_TLAS_VISIBILITY = 8 }; // GiCScene::updateCounts
@@ -373,7 +377,9 @@ struct GiCScene : SceneDevice {
   float oldDomeEmission[3] = {0, 0, 0};
   // the scene as built (the same on every device)
   uint32_t nodeCount = 0, triCount = 0, bvhDepth = 0;
-  float bounds[6] = {0, 0, 0, 0, 0, 0}; bool boundsValid = false; // the flat tree's root bounds (nodeBounds + a relative pad), for FLAG_BOUNDS_RETIRE
+  // the flat tree's root bounds (nodeBounds + a relative pad) -- on a scene without the flat tree the union of the instance boxes under the same pad
+  // (gi_tlas.h tlas_scene_bounds) --, for FLAG_BOUNDS_RETIRE
+  float bounds[6] = {0, 0, 0, 0, 0, 0}; bool boundsValid = false;
   int optBvhBuild = 0; // GI_C_SCENE_OPTION_BVH_BUILD: 1 = the device builder for flat-layout scenes beyond LDS (gi_bvh_build.hip)
   bool twoLevel = false; int optTwoLevel = -1; // 1: build and use the two-level layout (scenes beyond LDS); otherwise the flat one
   bool hasCutouts = false;
@@ -433,6 +439,9 @@ struct GiCScene : SceneDevice {
   // GI_C_SCENE_OPTION_TLAS_VISIBILITY: 1 = visibility edits of a two-level scene are applied to the resident scene (updateVisibilityTwoLevel; read only with
   // visibility updates wanted)
   int32_t optTlasVisibility = 0;
+  // GI_C_SCENE_OPTION_TLAS_ONLY: 1 = a scene that takes the two-level layout is built without the flat tree (buildScene; SceneHost::treeless); read at the
+  // build only, and only with the two-level layout wanted
+  int32_t optTlasOnly = 0;
   std::vector<GiCMesh*> retiredMeshes; // destroyed meshes the resident scene still refers to (GiCMesh::retired): freed by buildScene and with the scene
   ~GiCScene() { for (GiCMesh* m : retiredMeshes) delete m; }
 };
@@ -460,6 +469,7 @@ void nodeBounds(const Node8& n, float box[6]);               // dequantised boun
 bool instanceUpdatesWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_INSTANCE_UPDATES / GATLING_OPTIONS=instance_updates (with topology updates wanted)
 bool tlasUpdatesWanted(const GiCScene* s);                   // GI_C_SCENE_OPTION_TLAS_UPDATES / GATLING_OPTIONS=tlas_updates
 bool blasUpdatesWanted(const GiCScene* s);                   // GI_C_SCENE_OPTION_BLAS_UPDATES / GATLING_OPTIONS=blas_updates
+bool tlasOnlyWanted(const GiCScene* s);                      // GI_C_SCENE_OPTION_TLAS_ONLY / GATLING_OPTIONS=tlas_only (read at the build, with the two-level layout wanted)
 bool tlasVisibilityWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_TLAS_VISIBILITY / GATLING_OPTIONS=tlas_visibility (with visibility updates wanted)
 bool topologyUpdatesWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_TOPOLOGY_UPDATES / GATLING_OPTIONS=topology_updates
 int syncSceneGeometry(GiCScene* s);                          // brings the device scene up to date with the host-side edits (incremental or full build)

@@ -76,6 +76,8 @@ inline PathLot pathLotPlacement(uint32_t bvhDepth)
 }
 
 void launchAov(hipStream_t s, const FrameUniforms& U, const SceneView& sc, const AovTargets& A);
+// gi_aov2.hip: the same AOVs for a two-level scene without the flat tree (sc.twoLevel, sc.nodeCount == 0); launchAov picks it
+void launchAov2(hipStream_t s, const FrameUniforms& U, const SceneView& sc, const AovTargets& A);
 void launchResolveNee(hipStream_t s, const FrameUniforms& U, const unsigned long long* key, F4* aov, uint32_t pixelCount);
 void launchZeroClosest(hipStream_t s, Counters* cnt, uint32_t par); // FLAG_TWO_STREAM: in front of every closest-hit launch
 // gi_patch.hip: rewrites TriRec::matFlags of the `triCount` device-resident triangles to wordOfMesh[instances[t.instance].mesh] where it differs

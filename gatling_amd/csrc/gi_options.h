@@ -70,6 +70,9 @@
 //                                  applied to the resident scene (gi_build.cpp updateVerticesTwoLevel); read only with vertex_updates wanted
 //   tlas_visibility      -1        -1 = the scene option decides (GI_C_SCENE_OPTION_TLAS_VISIBILITY), 0 / 1 = visibility edits of a two-level scene rebuild it
 //                                  / are applied to the resident scene (gi_build.cpp updateVisibilityTwoLevel); read only with visibility_updates wanted
+//   tlas_only            -1        -1 = the scene option decides (GI_C_SCENE_OPTION_TLAS_ONLY), 0 / 1 = a scene that wants the two-level layout builds the flat
+//                                  tree beside it / builds, sends and keeps no flat tree (gi_build.cpp buildScene; AOVs walk the TLAS: gi_aov2.hip); read at
+//                                  the scene build, and only with the two-level layout wanted
 //   phase_stats          0         counting builds: print k_path's phase split / k_trace_dyn's lane accounting
 #pragma once
 

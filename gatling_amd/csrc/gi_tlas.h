@@ -96,4 +96,34 @@ inline InstTrav tlasMakeInstTrav(const InstanceRec& ir, uint32_t blasRoot, uint3
   return tv;
 }
 
+// The bounds of a two-level scene without the flat tree (GI_C_SCENE_OPTION_TLAS_ONLY; gi_build.cpp): the union of the padded world boxes of the instances
+// the TLAS names -- not hidden (`hidden` may be null: none is), not inverted (the box an unusable instance keeps; the builder leaves it out) -- run through the
+// pad the flat root's bounds get (gi_build.cpp setSceneBounds: 1e-5 of magnitude and extent, plus 1e-30).  Every box contains every world-space corner of
+// its instance, so k_raygen's bounds retire stays conservative.  valid = false, as there: no box in the union, or a side that is not finite -- a box with
+// such a side makes the whole answer invalid (a built scene holds none: buildTwoLevel declines for them), never a smaller union.
+inline void tlas_scene_bounds(const float* instBoxes, const uint8_t* hidden, size_t n, float out[6], bool& valid)
+{
+  float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+  valid = false;
+  for (int a = 0; a < 6; a++) out[a] = 0.0f;
+  bool any = false;
+  for (size_t i = 0; i < n; i++) {
+    if (hidden && hidden[i]) continue;
+    const float* b = instBoxes + 6u * i;
+    bool finite = true, inverted = false;
+    for (int a = 0; a < 3; a++) { finite = finite && std::isfinite(b[a]) && std::isfinite(b[3 + a]); inverted = inverted || !(b[a] <= b[3 + a]); }
+    if (!finite) return;
+    if (inverted) continue;
+    for (int a = 0; a < 3; a++) { lo[a] = refit_min(lo[a], b[a]); hi[a] = refit_max(hi[a], b[3 + a]); }
+    any = true;
+  }
+  if (!any) return;
+  for (int a = 0; a < 3; a++) {
+    const float pad = (std::fabs(lo[a]) + std::fabs(hi[a]) + (hi[a] - lo[a])) * 1.0e-5f + 1.0e-30f;
+    out[a] = lo[a] - pad; out[3 + a] = hi[a] + pad;
+    if (!std::isfinite(out[a]) || !std::isfinite(out[3 + a])) return;
+  }
+  valid = true;
+}
+
 } // namespace gi

@@ -383,7 +383,7 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * giCDebugSceneInstanceUpdateCount and giCDebugCloneInstance, and for GI_C_SCENE_OPTION_TLAS_UPDATES, giCDebugSceneTlasUpdateCount, giCDebugSceneTlasCheck
  * and giCDebugInstanceBounds, and for GI_C_SCENE_OPTION_BLAS_UPDATES, giCDebugSceneBlasUpdateCount, giCDebugSceneBlasCheck, giCDebugBlasRefit and
  * giCDebugBlasRefitHost, and for GI_C_SCENE_OPTION_TLAS_VISIBILITY, giCDebugSceneTlasVisibilityUpdateCount, giCDebugSceneFlatIdCheck and
- * giCDebugPatchVisibilityTwoLevel. */
+ * giCDebugPatchVisibilityTwoLevel, and for GI_C_SCENE_OPTION_TLAS_ONLY and giCDebugSceneFlatTreeState. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -635,6 +635,16 @@ int giCGetRenderStats(const GiCScene* scene, GiCRenderStats* out);
  * transform edit behind both; a vertex edit together with a toggle in one render rebuilds.  GATLING_OPTIONS=tlas_visibility=0|1 overrides the option
  * (hdGatling sets no scene options).  DESIGN.md section 6. */
 #define GI_C_SCENE_OPTION_TLAS_VISIBILITY 18
+/* [ext] Two-level scenes without the flat tree; read at the scene build, and only when the two-level layout is wanted (GI_C_SCENE_OPTION_TWO_LEVEL 1,
+ * GATLING_OPTIONS=two_level=1, or 2^26 and more flattened triangles): value 1 = the flat BVH8 over all flattened triangles is neither built nor sent nor
+ * kept -- the TLAS and the per-mesh BLASes are the scene's only trees.  The flat RECORDS stay, in scene order (the shading kernels read them); the non-colour
+ * AOVs find their primary hits with a two-level walk (k_aov2), the scene bounds are the union of the instance boxes, and the edits in place of options 16,
+ * 17 and 18 run without their flat refit.  0 = off (default): the flat tree is built beside the two-level arrays, as before.  The image does not depend on
+ * the option.  The flat tree is built as before when: the scene has 128 triangles or fewer, or one inactive triangle (a vertex that is not finite or beyond
+ * 1e18 after instancing), or the two-level layout declines (trees too deep for its 16-entry stack, 2^26 unique mesh triangles).  On a scene without the flat
+ * tree GiCRenderStats.nodeCount is 0 and giCDebugValidateSceneBvh answers with an error.  GATLING_OPTIONS=tlas_only=0|1 overrides the option (hdGatling
+ * sets no scene options).  DESIGN.md section 6. */
+#define GI_C_SCENE_OPTION_TLAS_ONLY 19
 int giCGetLookaheadStats(const GiCScene* scene, GiCLookaheadStats* out);
 int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value);
 /* [ext] closest hit of one ray through the device traversal kernel (parity tests of the BVH8 path).
@@ -773,6 +783,10 @@ int giCDebugBlasRefitHost(const GiCVertex* a, const GiCVertex* b, uint32_t verte
 /* [ext] [debug] how often the scene was brought up to date by a visibility update of the two-level layout (GI_C_SCENE_OPTION_TLAS_VISIBILITY); counted neither
  * in giCDebugSceneUpdateCounts nor in giCDebugSceneVisibilityUpdateCount. */
 int giCDebugSceneTlasVisibilityUpdateCount(const GiCScene* scene, uint64_t* outCount);
+/* [ext] [debug] what a built scene holds of the flat tree (GI_C_SCENE_OPTION_TLAS_ONLY): out[0] = 1 for the two-level layout, out[1] = 1 when the scene was built
+ * without the flat tree, out[2] = flat nodes resident on device copy `device`, out[3] = bytes of flat nodes the host copy holds.  GI_C_OK, or GI_C_ERROR for a
+ * scene that has not been built or a device copy that does not exist. */
+int giCDebugSceneFlatTreeState(const GiCScene* scene, uint32_t device, uint64_t out[4]);
 /* [ext] [debug] the flat triangle records, the id table (scene-order id -> flat record) and the per-instance traversal records resident on device
  * `deviceIndex` of a scene rendered at least once, downloaded and checked.  Returns the number of violations of: the ids of the records of visible instances
  * are a permutation of [0, visible triangles); the table names each of them at its id; its instance's triBase + prim is its id; records of hidden instances
