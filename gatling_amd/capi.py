@@ -32,6 +32,7 @@ OPTION_TLAS_UPDATES = 16  # 1: transform edits of a built two-level scene (OPTIO
 OPTION_BLAS_UPDATES = 17  # 1: vertex edits of a built two-level scene are applied to the resident scene -- the mesh's BLAS refitted on the device, a new TLAS, a refit of the flat tree -- instead of rebuilding it; read only with OPTION_VERTEX_UPDATES wanted (include/gi_c.h); 0 = off (default)
 OPTION_TLAS_VISIBILITY = 18  # 1: visibility edits of a built two-level scene are applied to the resident scene -- ids, the id table and the instances' id bases renumbered on the device, a new TLAS over the visible instances -- instead of rebuilding it; read only with OPTION_VISIBILITY_UPDATES wanted (include/gi_c.h); 0 = off (default)
 OPTION_TLAS_ONLY = 19  # 1: a scene that takes the two-level layout (OPTION_TWO_LEVEL 1, or 2^26 flattened triangles) is built without the flat BVH8 -- the flat records stay in scene order, the non-colour AOVs walk the TLAS (k_aov2), the scene bounds come from the instance boxes and the edits in place of options 16 - 18 run without the flat refit; read at the scene build only (include/gi_c.h); 0 = off (default)
+OPTION_TLAS_TOPOLOGY = 20  # 1: mesh creations and destructions on a built two-level scene without the flat tree (OPTION_TLAS_ONLY) are applied to the resident scene -- a destroyed mesh retired as a hidden one, a created mesh appended: one BLAS from the host, its shading records, BLAS triangles, flat records, face ids and id-table words made on the device (gi_append.hip) -- instead of rebuilding it; read only with OPTION_TOPOLOGY_UPDATES wanted (include/gi_c.h); 0 = off (default)
 OPTION_BVH_BUILD = 9  # 0 = host BVH builder (default), 1 = device builder (flat-layout scenes of more than 128 triangles)
 
 
@@ -184,6 +185,9 @@ SYMBOLS = [
     ("giCDebugBlasRefitHost", C.c_int, [_P, _P, _U, _P, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("giCDebugSceneTlasVisibilityUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugSceneFlatIdCheck", C.c_int, [_P, _U, C.POINTER(C.c_uint32)]),
     ("giCDebugSceneFlatTreeState", C.c_int, [_P, _U, C.POINTER(C.c_uint64)]),
+    ("giCDebugSceneTlasTopologyUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("giCDebugAppendRecords", C.c_int, [_P, _U, _P, _U, _P, _U, _U, _FP, _U, _U, _U, _U, _U]),
+    ("giCDebugAppendRecordsHost", C.c_int, [_P, _U, _P, _U, _P, _U, _U, _FP, _U, _U, _U, _U, _U]),
     ("giCDebugPatchVisibilityTwoLevel", C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _U, _U, C.POINTER(C.c_uint32)]),
     ("giCDebugPathWalkStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugPathLobeStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
@@ -296,6 +300,29 @@ def debug_blas_refit(vertices_a, vertices_b, faces, host_only=False):
     if n < 0:
         raise GiError("giCDebugBlasRefit failed: " + L.giCGetLastError().decode())
     return int(n), int(nodes.value), int(violations.value)
+
+
+def debug_append_records(vertices, faces, xforms, face_ids=None, max_face_id=0, flip_facing=False, double_sided=False, vertex_offset=0, shade_base=0, id_base=0,
+                         mat_flags=0, host_only=False) -> int:
+    """giCDebugAppendRecords: the device kernels that make an appended mesh's records on a two-level scene without the flat tree (k_append_shade_index,
+    k_gather_shade, k_append_blas_tris, k_append_records) over the mesh (`vertices`: VERTEX_DTYPE, `faces`: n x 3 indices, `face_ids`: n or None) under each of
+    `xforms` (k x 4 x 4, USD row vectors), laid out behind `vertex_offset` vertex records, `shade_base` shading records and the scene-order id `id_base`, against
+    the scene build's own host code.  Returns the number of differing bytes (0 is the contract).  host_only: giCDebugAppendRecordsHost, the host forms of the
+    same kernels (gi_append.h) against the same references (no device)."""
+    from .scene import VERTEX_DTYPE
+    L = load_library()
+    v = np.ascontiguousarray(vertices, VERTEX_DTYPE)
+    f = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3)
+    x = np.ascontiguousarray(xforms, np.float32).reshape(-1, 16)
+    ids = None if face_ids is None else np.ascontiguousarray(face_ids, np.int32).reshape(-1)
+    if ids is not None and len(ids) != len(f):
+        raise ValueError("debug_append_records: one face id per face")
+    fn = L.giCDebugAppendRecordsHost if host_only else L.giCDebugAppendRecords
+    n = fn(v.ctypes.data, len(v), f.ctypes.data, len(f), None if ids is None else ids.ctypes.data, int(max_face_id), (1 if flip_facing else 0) | (2 if double_sided else 0),
+           x.ctypes.data_as(_FP), len(x), int(vertex_offset), int(shade_base), int(id_base), int(mat_flags))
+    if n < 0:
+        raise GiError("giCDebugAppendRecords failed: " + L.giCGetLastError().decode())
+    return int(n)
 
 
 def debug_patch_visibility_two_level(face_counts, hidden_before, hidden_after, seed=1):
@@ -518,6 +545,14 @@ class Scene:
         n = C.c_uint64(0)
         if self.L.giCDebugSceneTlasVisibilityUpdateCount(self.handle, C.byref(n)) != GI_C_OK:
             raise GiError("giCDebugSceneTlasVisibilityUpdateCount failed")
+        return int(n.value)
+
+    def tlas_topology_update_count(self) -> int:
+        """giCDebugSceneTlasTopologyUpdateCount: how often the scene was brought up to date by a topology update of the two-level layout
+        (OPTION_TLAS_TOPOLOGY; counted neither in update_counts() nor in topology_update_count())."""
+        n = C.c_uint64(0)
+        if self.L.giCDebugSceneTlasTopologyUpdateCount(self.handle, C.byref(n)) != GI_C_OK:
+            raise GiError("giCDebugSceneTlasTopologyUpdateCount failed")
         return int(n.value)
 
     def flat_id_check(self, device: int = 0) -> "FlatIdCheck":

@@ -7,6 +7,7 @@
 #include "gi_blas.h"
 #include "gi_pack.h"
 #include "gi_vispatch.h"
+#include "gi_append.h"
 
 #include <random>
 #include <unordered_map>
@@ -1723,9 +1724,25 @@ static uint32_t adoptResyncs(GiCScene* s, SceneHost& H)
 // one after another on the device, so an edit of many mid-sized parts is faster on the host (C5, 8 parts of 5 120 faces: 5 ms against 21 ms)
 constexpr long kDevicePartsMinDefault = 4096;
 
+// GI_C_SCENE_OPTION_TLAS_TOPOLOGY / GATLING_OPTIONS=tlas_topology: mesh creations and destructions on a two-level scene without the flat tree are applied in
+// place (updateTopologyTwoLevel below); read only with topology updates wanted
+bool tlasTopologyWanted(const GiCScene* s)
+{
+  if (!topologyUpdatesWanted(s)) return false;
+  const long o = optionValue("tlas_topology", -1);
+  return o >= 0 ? o == 1 : s->optTlasTopology == 1;
+}
+static int updateTopologyTwoLevel(GiCScene* s, SceneHost& H, bool& handled, UpdateCost& cost);
+
 static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
 {
   SceneHost* host = incrementalHost(s);
+  if (s->twoLevel && tlasTopologyWanted(s)) {
+    if (host && host->treeless && host->shadePacked) return updateTopologyTwoLevel(s, *host, handled, cost);
+    if (getenv("GATLING_BUILD_TIMING")) fprintf(stderr, "[gatling_gi] topology update (two-level): %s; the scene is rebuilt\n",
+        host ? "the scene keeps its flat tree (built without GI_C_SCENE_OPTION_TLAS_ONLY)" : "no host copy of the scene, or GATLING_OPTIONS=incremental=0");
+    return GI_C_OK;
+  }
   if (!host || s->twoLevel || !host->shadePacked) return GI_C_OK;
   SceneHost& H = *host;
   if (H.meshRecs.size() != H.meshBuilds.size()) return GI_C_OK;
@@ -2592,7 +2609,338 @@ static int updateVerticesTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Upda
   return GI_C_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Topology updates on the two-level layout (opt-in: GI_C_SCENE_OPTION_TLAS_TOPOLOGY / GATLING_OPTIONS=tlas_topology=1, read with topology updates wanted, on a
+// scene built without the flat tree: SceneHost::treeless).  Meshes were created or destroyed; nothing else asked for the rebuild.  With no flat tree to grow,
+//   retire:  a destroyed mesh of the built scene (GiCMesh::retired) becomes hidden for good through updateVisibilityTwoLevel's machinery -- planVisibility
+//            with the predicate hidden || retired, k_patch_visibility2 and k_patch_inst_trav over the resident records, its instances masked out of the TLAS.
+//            Its BLAS nodes and triangles, flat records and shading records stay resident as retired ranges until the next buildScene, which frees the mesh.
+//   append:  every mesh a fresh build would hold that has no MeshBuild, all of them behind every built one, goes to the ends of the arrays.  The host makes
+//            and sends what the mesh has per vertex, per face and per instance: FVertex records (packVertex), the faces, the AOV face ids (faceIdAovOf), the
+//            InstanceRecs (makeInstanceRec), the InstTrav records (tlasMakeInstTrav, triBase = the plan's id base), its ONE BLAS (buildMeshBlas, as
+//            buildTwoLevel runs it, rebased onto the ends of the BLAS arrays) with the builder's face order, the MeshRec / scene-data tables.  The instances'
+//            world boxes and statuses come from k_inst_bounds / k_inst_finish over the new BLAS triangles in scratch memory (instanceBoundsOnPrimary) before
+//            anything resident changes; the TLAS is built again by buildBvh8Boxes over all boxes, hidden and retired instances masked.
+//   device:  the arrays grow in place (DeviceBuffer::grow); gi_append.hip makes everything per face and per flattened triangle where it lives --
+//            k_append_shade_index, k_gather_shade, k_append_blas_tris, k_append_records: shading records, BLAS triangles, the flat TriRecs, their face-id
+//            words and their words of the id table.  Nothing per flattened triangle crosses the link.
+//   host copies: the MeshBuilds, H.verts, H.triShade, H.instances, the tables, H.two with meshBlasTri / meshBlasNode / meshBlasLevels (a later BLAS refit
+//            finds the mesh); the flat records, face ids and id table where the host still holds them (gi_append.h appendRecordsHost, the kernels' form) --
+//            where an edit in place dropped them they stay dropped.
+// Every decision comes before the first resident write.  Declines (handled = false, not an error, one line under GATLING_BUILD_TIMING): the option off, a
+// scene with a flat tree, no host copy or incremental=0 (updateTopology); an instance-count or instance-id edit of a built mesh due; a scene built with
+// inactive triangles; fewer than kIncrementalMinTris visible triangles after the edit; more retired than live triangles; a new mesh in front of a built one;
+// an unusable vertex position; an unusable instance transform; a set status (triangles that leave the usable range in world space); a material index above
+// 2^24; 2^26 unique BLAS triangles or 2^28 flat records; a TLAS too deep (2 x TLAS depth + BLAS depth + 1 > 16, the new BLAS included); out of device
+// memory (a later device of several: the earlier ones are committed, and buildScene sends everything anew).
+// ---------------------------------------------------------------------------------------------------------------
+static int updateTopologyTwoLevel(GiCScene* s, SceneHost& H, bool& handled, UpdateCost& cost)
+{
+  TwoLevelHost& T = H.two;
+  const char* const what = "topology update (two-level)";
+  const bool timing = getenv("GATLING_BUILD_TIMING") != nullptr;
+  auto decline = [&](const char* why) { if (timing) fprintf(stderr, "[gatling_gi] %s: %s; the scene is rebuilt\n", what, why); return GI_C_OK; };
+  const uint32_t oldInstances = (uint32_t)H.instances.size(), oldTris = s->triCount, shade0 = (uint32_t)H.triShade.size(), vert0 = (uint32_t)H.verts.size();
+  const uint32_t blasNode0 = (uint32_t)T.blasNodes.size(), blasTri0 = (uint32_t)T.blasTris.size(), mesh0 = (uint32_t)H.meshBuilds.size();
+  if (s->stats.inactiveTriangleCount != 0u) return decline("the scene was built with inactive triangles");
+  if (H.deviceBuilt || H.partitioned || !H.treeless || !H.shadePacked || H.reordered) return decline("the scene is not a two-level scene without the flat tree");
+  if (T.instTrav.size() != oldInstances || T.instBoxes.size() != 6u * (size_t)oldInstances || T.meshBlasTri.size() != mesh0 || T.meshBlasNode.size() != mesh0 ||
+      T.meshBlasLevels.size() != mesh0 || H.meshRecs.size() != mesh0) return decline("the host copy is not the built scene's"); // (cannot happen)
+  for (const MeshBuild& mb : H.meshBuilds) if (mb.m->builtInstances != mb.instCount) return decline("a built mesh with another instance count"); // (cannot happen)
+  if (s->instancesDue) return decline("an instance-count or instance-id edit of a built mesh is due");
+  const double t0 = nowMs();
+  // --- the meshes to append: updateTopology's selection loop -- what a fresh build would hold and the resident scene does not, all behind every built mesh
+  struct NewMesh { GiCMesh* m; uint32_t material, matFlags, vertexOffset, shadeBase, instFirst, instCount, nf, triFirst, idBase, blasNode, blasTri, faceFirst; float extent;
+      Bvh8 blas; std::vector<uint32_t> order; std::vector<int32_t> faceIdAov; };
+  std::vector<NewMesh> fresh;
+  uint64_t appendedTris = 0, appendedFaces = 0, appendedInstances = 0, appendedVerts = 0;
+  for (GiCMesh* m : s->meshes) {
+    if (m->builtInstances != 0xffffffffu) { if (!fresh.empty()) return decline("a new mesh lies in front of a built one"); continue; }
+    if (!m->visible || m->faces.empty()) continue; // (as buildScene)
+    auto mit = std::find(s->materials.begin(), s->materials.end(), m->material);
+    if (mit == s->materials.end()) continue;
+    const uint32_t material = (uint32_t)(mit - s->materials.begin());
+    if (material > 0x00ffffffu) return decline("a material index above 2^24");
+    if (!usableVertexPositions(m->vertices.data(), m->vertices.size())) return decline("a new mesh has a vertex position that is not usable");
+    const uint64_t instCount = m->instanceTransforms.size() / 16;
+    if (instCount == 0u) continue; // (no instance: a fresh build holds a MeshBuild without records; the next build takes it up)
+    NewMesh nm{}; nm.m = m; nm.material = material; nm.instCount = (uint32_t)instCount; nm.nf = (uint32_t)m->faces.size();
+    fresh.push_back(std::move(nm));
+    appendedTris += instCount * m->faces.size(); appendedFaces += m->faces.size(); appendedInstances += instCount; appendedVerts += m->vertices.size();
+  }
+  // --- what the scene holds after the edit
+  uint64_t live = appendedTris, retired = 0, visible = appendedTris; uint32_t retiring = 0;
+  for (const MeshBuild& mb : H.meshBuilds) {
+    const uint64_t n = (uint64_t)mb.instCount * mb.m->faces.size();
+    if (mb.m->retired) { retired += n; if (!mb.hidden) retiring++; } else { live += n; if (!mb.hidden) visible += n; }
+  }
+  if (visible < kIncrementalMinTris) return decline("fewer than 4096 visible triangles after the edit");
+  if (retired > live) return decline("retired triangles outnumber live ones");
+  if ((uint64_t)oldTris + appendedTris >= ((uint64_t)1 << 28)) return decline("2^28 or more flat records after the append");
+  if ((uint64_t)blasTri0 + appendedFaces >= ((uint64_t)1 << 26)) return decline("2^26 or more unique BLAS triangles after the append");
+  if ((uint64_t)oldInstances + appendedInstances >= 0xffffffffull || (uint64_t)vert0 + appendedVerts >= 0xffffffffull) return decline("the arrays outgrow 32-bit indices");
+  if (fresh.empty() && retiring == 0u) { // the edited meshes are not part of a fresh build either (invisible, no faces, no instance, no valid material)
+    for (GiCMesh* m : s->meshes) if (m->builtInstances == 0xffffffffu) { m->visToggled = false; m->vertsEdited = false; }
+    handled = true;
+    return GI_C_OK;
+  }
+  // --- retire: the plan (nothing resident is touched yet)
+  VisibilityPlan plan;
+  if (!planVisibility(s, H, [](const MeshBuild& mb) { return mb.hidden || mb.m->retired; }, plan)) return decline("a built mesh with another instance count");
+  // --- append, planned: the new meshes' words come from the current material table (updateMaterials runs behind this update when an edit is due)
+  std::vector<MaterialRec> mats;
+  const bool matsRemade = (s->dirty & DIRTY_MATERIALS) != 0u;
+  if (matsRemade) buildMaterialRecords(s, mats);
+  const std::vector<MaterialRec>& matTable = matsRemade ? mats : H.mats;
+  const uint32_t newInstances = oldInstances + (uint32_t)appendedInstances, newTris = oldTris + (uint32_t)appendedTris;
+  std::vector<FVertex> newVerts; newVerts.reserve(appendedVerts);
+  std::vector<InstanceRec> newInst; newInst.reserve(appendedInstances);
+  std::vector<uint32_t> faces3, orderAll; std::vector<int32_t> faceIdAll; // the per-face temporaries of all new meshes, one upload each
+  faces3.reserve(3u * appendedFaces); orderAll.reserve(appendedFaces); faceIdAll.reserve(appendedFaces);
+  std::vector<MeshRec> meshRecs(H.meshRecs); std::vector<float> sceneData(H.sceneData);
+  {
+    uint64_t idBase = plan.visibleTris; uint32_t vertexOffset = vert0, shadeBase = shade0, instFirst = oldInstances, triFirst = oldTris, faceFirst = 0;
+    for (NewMesh& nm : fresh) {
+      GiCMesh* m = nm.m;
+      if (nm.material >= matTable.size()) return decline("a new mesh's material is not in the material table"); // (cannot happen: creating a material raises DIRTY_MATERIALS)
+      nm.matFlags = meshMatFlags(matTable[nm.material], nm.material, m);
+      nm.vertexOffset = vertexOffset; nm.shadeBase = shadeBase; nm.instFirst = instFirst; nm.triFirst = triFirst; nm.idBase = (uint32_t)idBase; nm.faceFirst = faceFirst;
+      appendMeshSceneData(m, m->material, vertexOffset, meshRecs, sceneData);
+      for (const GiCVertex& vIn : m->vertices) newVerts.push_back(packVertex(vIn));
+      for (const GiCFace& f : m->faces) { faces3.push_back(f.v_i[0]); faces3.push_back(f.v_i[1]); faces3.push_back(f.v_i[2]); }
+      nm.faceIdAov = faceIdAovOf(m);
+      faceIdAll.insert(faceIdAll.end(), nm.faceIdAov.begin(), nm.faceIdAov.end());
+      for (uint32_t ii = 0; ii < nm.instCount; ii++) {
+        newInst.push_back(makeInstanceRec(m, mesh0 + (uint32_t)(&nm - fresh.data()), ii));
+        if (!usableInstance(newInst.back())) return decline("a new instance has a transform that is not usable");
+      }
+      vertexOffset += (uint32_t)m->vertices.size(); shadeBase += nm.nf; instFirst += nm.instCount; triFirst += nm.instCount * nm.nf; faceFirst += nm.nf;
+      idBase += (uint64_t)nm.instCount * nm.nf;
+    }
+  }
+  // --- the new BLASes, by the host builder exactly as buildTwoLevel runs it; their records in the builder's order (the bounds kernels read them from scratch)
+  const double tb0 = nowMs();
+  std::vector<uint8_t> blasOk(fresh.size(), 1);
+  parallelOver(fresh.size(), [&](size_t k) {
+    NewMesh& nm = fresh[k];
+    float mlo[3], mhi[3];
+    buildMeshBlas(nm.m->vertices.data(), nm.m->faces.data(), nm.nf, nm.blas, nm.order, mlo, mhi);
+    nm.extent = (std::fabs(mlo[0]) + std::fabs(mlo[1]) + std::fabs(mlo[2])) + (std::fabs(mhi[0]) + std::fabs(mhi[1]) + std::fabs(mhi[2])); // (buildTwoLevel's)
+    blasOk[k] = nm.order.size() == nm.nf && !nm.blas.nodes.empty() && nm.blas.levelStart.size() >= 2u && nm.blas.levelStart.back() == nm.blas.nodes.size();
+    for (const uint32_t f : nm.order) if (f >= nm.nf) blasOk[k] = 0;
+  });
+  const double blasMs = nowMs() - tb0;
+  for (const uint8_t ok : blasOk) if (!ok) return decline("a new mesh's BLAS has no level table"); // (cannot happen)
+  std::vector<Node8> newBlasNodes; std::vector<BlasTri> newBlasTris; newBlasTris.reserve(appendedFaces);
+  std::vector<InstTrav> newTrav; newTrav.reserve(appendedInstances);
+  std::vector<InstBoundsJob> jobs; jobs.reserve(appendedInstances);
+  uint32_t blasDepth = T.blasDepth, chunksPerJob = 0;
+  for (NewMesh& nm : fresh) {
+    nm.blasNode = blasNode0 + (uint32_t)newBlasNodes.size(); nm.blasTri = blasTri0 + (uint32_t)newBlasTris.size();
+    const uint32_t scratchFirst = (uint32_t)newBlasTris.size();
+    for (Node8 n : nm.blas.nodes) { n.childBase += nm.blasNode; n.triBase += nm.blasTri; newBlasNodes.push_back(n); }
+    for (const uint32_t f : nm.order) { newBlasTris.push_back(makeBlasTri(nm.m->vertices.data(), nm.m->faces.data(), f)); orderAll.push_back(f); }
+    blasDepth = std::max(blasDepth, nm.blas.maxDepth);
+    for (uint32_t ii = 0; ii < nm.instCount; ii++) {
+      const InstanceRec& ir = newInst[nm.instFirst - oldInstances + ii];
+      newTrav.push_back(tlasMakeInstTrav(ir, nm.blasNode, nm.idBase + ii * nm.nf, nm.matFlags, nm.extent));
+      InstBoundsJob j{}; memcpy(j.o2w, ir.o2w, sizeof(j.o2w)); j.firstTri = scratchFirst; j.faceCount = nm.nf; j.instance = nm.instFirst + ii;
+      jobs.push_back(j);
+    }
+    chunksPerJob = std::max(chunksPerJob, instBoundsChunks(nm.nf));
+  }
+  if ((uint64_t)jobs.size() * chunksPerJob >= (1ull << 31)) return decline("more bounds workgroups than a launch takes");
+  // --- primary device, scratch only: padded world boxes and statuses of the new instances
+  std::vector<uint32_t> result;
+  bool outOfMemory = false;
+  const double tA = nowMs();
+  if (!jobs.empty()) {
+    const int rcB = instanceBoundsOnPrimary(s, jobs, chunksPerJob, &newBlasTris, result, outOfMemory, what);
+    if (rcB == DEVICE_BUILD_FALLBACK && outOfMemory) return decline("out of device memory");
+    if (rcB != GI_C_OK) return GI_C_ERROR;
+  }
+  const double boundsMs = nowMs() - tA;
+  for (size_t k = 0; k < jobs.size(); k++)
+    if (result[7u * k + 6u] != 0u) return decline("a new instance carries triangles that leave the usable coordinate range in world space");
+  // --- the TLAS over all boxes, hidden and retired instances masked; the depth rule with the new BLASes
+  std::vector<float> boxes(T.instBoxes); boxes.resize(6u * (size_t)newInstances);
+  for (size_t k = 0; k < jobs.size(); k++) memcpy(&boxes[6u * (size_t)jobs[k].instance], &result[7u * k], 24);
+  std::vector<uint8_t> hiddenAfter(newInstances, 0);
+  for (const MeshBuild& mb : H.meshBuilds) if (plan.hide[mb.meshIdx]) for (const uint32_t inst : mb.inst) if (inst < oldInstances) hiddenAfter[inst] = 1;
+  Bvh8 tlas; std::vector<uint32_t> tlasItems;
+  const double tt0 = nowMs();
+  {
+    std::vector<float> masked(boxes);
+    tlasMaskHiddenBoxes(masked.data(), hiddenAfter.data(), newInstances);
+    buildBvh8Boxes(masked.data(), newInstances, tlas, tlasItems);
+  }
+  const double tlasMs = nowMs() - tt0;
+  if (2u * tlas.maxDepth + blasDepth + 1u > 16u) return decline("the new TLAS is too deep for the 16-entry stack");
+  // --- decided.  The host copies of the retire: the records where they are still held, the MeshBuilds' state; then the table's extra bit for the kernel
+  const bool hostRecords = !H.hostTreeDropped && H.bvh.tris.size() == oldTris && H.triFaceId.size() == oldTris && H.flatOfOrig.size() == oldTris;
+  applyVisibilityPlanOnHost(H, plan);
+  for (uint32_t i = 0; i < oldInstances; i++) if (hiddenAfter[i]) plan.patch[i].action |= VIS_HIDDEN_AFTER;
+  const std::vector<VisPatch>& patch = plan.patch;
+  const uint32_t newShade = shade0 + (uint32_t)appendedFaces, newVertCount = vert0 + (uint32_t)appendedVerts;
+  const uint32_t newBlasNodeCount = blasNode0 + (uint32_t)newBlasNodes.size(), newBlasTriCount = blasTri0 + (uint32_t)newBlasTris.size();
+  const double t1 = nowMs();
+  // --- every device of the scene, on its own stream: the arrays grown and the temporaries allocated before anything resident changes
+  double appendKernelMs = 0.0;
+  const size_t bytesSent = (plan.launch ? patch.size() * sizeof(VisPatch) : 0u) + newVerts.size() * sizeof(FVertex) + newInst.size() * (sizeof(InstanceRec) + sizeof(InstTrav)) +
+      newBlasNodes.size() * sizeof(Node8) + faces3.size() * 4u + orderAll.size() * 4u + faceIdAll.size() * 4u + tlas.nodes.size() * sizeof(Node8) + tlasItems.size() * 4u +
+      meshRecs.size() * sizeof(MeshRec) + sceneData.size() * sizeof(float);
+  const int rcDev = onSceneDevices(s, residentDeviceCount(s), [&](SceneDevice& D, hipStream_t st) -> int {
+    if (D.dTris.count < oldTris || D.dTriFaceId.count < oldTris || D.dFlatOfOrig.count < oldTris || D.dInstances.count < oldInstances || D.dInstTrav.count < oldInstances ||
+        D.dTriShade.count < shade0 || D.dVerts.count < vert0 || D.dBlasNodes.count < blasNode0 || D.dBlasTris.count < blasTri0) {
+      setError("internal: the device holds less than the scene"); return GI_C_ERROR; }
+    std::vector<void*> old;
+    DeviceBuffer<VisPatch> dPatch; DeviceBuffer<uint32_t> dFaces, dOrder; DeviceBuffer<int32_t> dFaceIds;
+    auto releaseAll = [&] { dPatch.release(); dFaces.release(); dOrder.release(); dFaceIds.release(); for (void* p : old) (void)hipFree(p); old.clear(); };
+    int r = plan.launch ? dPatch.alloc(patch.size()) : GI_C_OK;
+    if (r == GI_C_OK && !fresh.empty()) { r = dFaces.alloc(faces3.size()); if (r == GI_C_OK) r = dOrder.alloc(orderAll.size()); if (r == GI_C_OK) r = dFaceIds.alloc(faceIdAll.size()); }
+    if (r == GI_C_OK) r = D.dVerts.grow(newVertCount, st, old);
+    if (r == GI_C_OK) r = D.dTriShade.grow(newShade, st, old);
+    if (r == GI_C_OK) r = D.dInstances.grow(newInstances, st, old);
+    if (r == GI_C_OK) r = D.dInstTrav.grow(newInstances, st, old);
+    if (r == GI_C_OK) r = D.dBlasNodes.grow(newBlasNodeCount, st, old);
+    if (r == GI_C_OK) r = D.dBlasTris.grow(newBlasTriCount, st, old);
+    if (r == GI_C_OK) r = D.dTris.grow(newTris, st, old);
+    if (r == GI_C_OK) r = D.dTriFaceId.grow(newTris, st, old);
+    if (r == GI_C_OK) r = D.dFlatOfOrig.grow(newTris, st, old);
+    if (r != GI_C_OK) { // (the copies out of the old blocks must finish before they are freed)
+      (void)hipStreamSynchronize(st); releaseAll();
+      if (r == GI_C_OUT_OF_MEMORY_INTERNAL) { outOfMemory = true; return DEVICE_BUILD_FALLBACK; }
+      return GI_C_ERROR;
+    }
+    auto copy = [&](void* dst, const void* src, size_t bytes) {
+      if (r == GI_C_OK && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) != hipSuccess) { setError("topology update (two-level): copy failed"); r = GI_C_ERROR; } };
+    // the retire: ids, the id table and the instances' id bases, over what was resident before the append
+    if (plan.launch) {
+      copy(dPatch.ptr, patch.data(), patch.size() * sizeof(VisPatch));
+      if (r == GI_C_OK) {
+        launchPatchVisibility2(st, D.dTris.ptr, oldTris, D.dInstances.ptr, oldInstances, dPatch.ptr, D.dTriShade.ptr, shade0, D.dFlatOfOrig.ptr, newTris);
+        if (plan.renumbered) launchPatchInstTrav(st, D.dInstTrav.ptr, oldInstances, dPatch.ptr);
+      }
+    }
+    // the append: what the host made per vertex, per face and per instance ...
+    copy(D.dVerts.ptr + vert0, newVerts.data(), newVerts.size() * sizeof(FVertex));
+    copy(D.dInstances.ptr + oldInstances, newInst.data(), newInst.size() * sizeof(InstanceRec));
+    copy(D.dInstTrav.ptr + oldInstances, newTrav.data(), newTrav.size() * sizeof(InstTrav));
+    copy(D.dBlasNodes.ptr + blasNode0, newBlasNodes.data(), newBlasNodes.size() * sizeof(Node8));
+    copy(dFaces.ptr, faces3.data(), faces3.size() * 4u); copy(dOrder.ptr, orderAll.data(), orderAll.size() * 4u); copy(dFaceIds.ptr, faceIdAll.data(), faceIdAll.size() * 4u);
+    if (r == GI_C_OK && (D.dTlasNodes.upload(tlas.nodes, st) || D.dTlasItems.upload(tlasItems, st) || D.dMeshes.upload(meshRecs, st) || D.dSceneData.upload(sceneData, st))) r = GI_C_ERROR;
+    // ... and everything per face and per flattened triangle, made where it lives (gi_append.hip), behind those copies on the same stream
+    double tk = 0.0;
+    if (r == GI_C_OK && timing && D.slot == 0u) { if (hipStreamSynchronize(st) != hipSuccess) r = GI_C_ERROR; tk = nowMs(); }
+    for (const NewMesh& nm : fresh) {
+      if (r != GI_C_OK) break;
+      AppendMesh M{}; M.triFirst = nm.triFirst; M.faceCount = nm.nf; M.instFirst = nm.instFirst; M.instCount = nm.instCount; M.shadeBase = nm.shadeBase; M.idBase = nm.idBase;
+      M.matFlags = nm.matFlags; M.triCount = newTris; M.instanceCount = newInstances; M.shadeCount = newShade; M.flatCount = newTris;
+      if (!launchAppendShadeIndex(st, D.dTriShade.ptr, newShade, nm.shadeBase, dFaces.ptr + 3u * (size_t)nm.faceFirst, nm.nf, nm.vertexOffset) ||
+          !launchGatherShade(st, D.dTriShade.ptr, newShade, nm.shadeBase, nm.nf, D.dVerts.ptr, newVertCount) ||
+          !launchAppendBlasTris(st, D.dBlasTris.ptr, newBlasTriCount, nm.blasTri, dOrder.ptr + nm.faceFirst, nm.nf, D.dTriShade.ptr, newShade, nm.shadeBase) ||
+          !launchAppendRecords(st, M, D.dTris.ptr, D.dTriFaceId.ptr, D.dFlatOfOrig.ptr, D.dInstances.ptr, D.dTriShade.ptr, dFaceIds.ptr + nm.faceFirst)) {
+        setError("internal: an appended mesh's records outside their arrays"); r = GI_C_ERROR; } // (cannot happen: the arrays were grown to hold them)
+    }
+    if (r == GI_C_OK && hipGetLastError() != hipSuccess) { setError("topology update (two-level): launch failed"); r = GI_C_ERROR; }
+    if (hipStreamSynchronize(st) != hipSuccess && r == GI_C_OK) { setError("topology update (two-level): device error"); r = GI_C_ERROR; }
+    if (timing && D.slot == 0u && r == GI_C_OK) appendKernelMs = nowMs() - tk;
+    releaseAll(); // (before the render's memory plan reads free memory)
+    return r;
+  });
+  if (rcDev == DEVICE_BUILD_FALLBACK && outOfMemory) return decline("out of device memory");
+  if (rcDev != GI_C_OK) return GI_C_ERROR;
+  const double t2 = nowMs();
+  // --- the host copies behind the committed edit: the retire ...
+  if (plan.launch) {
+    patchInstTravHost(T.instTrav.data(), oldInstances, patch.data());
+    if (hostRecords) {
+      constexpr size_t CHUNK = 65536;
+      const size_t n = oldTris;
+      parallelOver((n + CHUNK - 1) / CHUNK, [&](size_t c) { // (one writer per word: the visible ids are a permutation)
+        for (size_t i = c * CHUNK; i < std::min(n, (c + 1) * CHUNK); i++) {
+          const TriRec& t = H.bvh.tris[i];
+          if (t.instance < oldInstances && !hiddenAfter[t.instance] && t.origId < n) H.flatOfOrig[t.origId] = (uint32_t)i;
+        }
+      });
+    } else std::vector<uint32_t>().swap(H.flatOfOrig); // (stale with the dropped host records; nothing reads it before the next build makes it anew)
+  }
+  // ... and the append
+  H.verts.insert(H.verts.end(), newVerts.begin(), newVerts.end());
+  H.instances.insert(H.instances.end(), newInst.begin(), newInst.end());
+  H.meshRecs.swap(meshRecs); H.sceneData.swap(sceneData);
+  if (matsRemade) H.mats.swap(mats);
+  T.blasNodes.insert(T.blasNodes.end(), newBlasNodes.begin(), newBlasNodes.end()); T.blasTris.insert(T.blasTris.end(), newBlasTris.begin(), newBlasTris.end());
+  T.instTrav.insert(T.instTrav.end(), newTrav.begin(), newTrav.end());
+  T.instBoxes.swap(boxes); T.tlasNodes.swap(tlas.nodes); T.tlasItems.swap(tlasItems); T.tlasDepth = tlas.maxDepth; T.blasDepth = blasDepth;
+  // (25 % slack, as on the device and as updateTopology grows its host arrays: a std::vector would double 4.3 GB of records on the first append to a
+  // 67.7 M-triangle scene and copy them on every later doubling)
+  auto grown = [](auto& v, size_t n) { if (v.capacity() < n) v.reserve(n + n / 4u); v.resize(n); };
+  if (hostRecords) { grown(H.bvh.tris, newTris); grown(H.triFaceId, newTris); grown(H.flatOfOrig, newTris); }
+  else { // dropped by an edit in place before: they stay dropped, and the id table -- one word per resident record -- goes with them
+    std::vector<uint32_t>().swap(H.flatOfOrig);
+    if (!H.hostTreeDropped) { std::vector<TriRec>().swap(H.bvh.tris); std::vector<int32_t>().swap(H.triFaceId); H.hostTreeDropped = true; } // (cannot happen)
+  }
+  for (NewMesh& nm : fresh) {
+    GiCMesh* m = nm.m;
+    const uint32_t meshIdx = (uint32_t)H.meshBuilds.size();
+    for (const GiCFace& f : m->faces) H.triShade.push_back(packTriShade(m->vertices.data(), f, nm.vertexOffset));
+    H.meshBuilds.push_back(MeshBuild{m, nm.vertexOffset, nm.matFlags, nm.instFirst, nm.instCount, nm.triFirst, meshIdx, nm.faceIdAov});
+    H.meshBuilds.back().shadeBase = nm.shadeBase; H.meshBuilds.back().idBase = nm.idBase; H.meshBuilds.back().numberInstances();
+    T.meshBlasTri.push_back(nm.blasTri); T.meshBlasNode.push_back(nm.blasNode); T.meshBlasLevels.push_back(nm.blas.levelStart);
+    if (hostRecords) { // the flat records, face ids and id-table words by the kernels' own form
+      AppendMesh M{}; M.triFirst = nm.triFirst; M.faceCount = nm.nf; M.instFirst = nm.instFirst; M.instCount = nm.instCount; M.shadeBase = nm.shadeBase; M.idBase = nm.idBase;
+      M.matFlags = nm.matFlags; M.triCount = newTris; M.instanceCount = newInstances; M.shadeCount = (uint32_t)H.triShade.size(); M.flatCount = newTris;
+      constexpr uint32_t CHUNK = 65536;
+      const uint32_t items = nm.nf * nm.instCount;
+      parallelOver(((size_t)items + CHUNK - 1) / CHUNK, [&](size_t c) {
+        appendRecordsHost(M, (uint32_t)c * CHUNK, std::min(items, ((uint32_t)c + 1u) * CHUNK), H.bvh.tris.data(), H.triFaceId.data(), H.flatOfOrig.data(), H.instances.data(),
+            H.triShade.data(), nm.faceIdAov.data());
+      });
+    }
+    m->builtInstances = nm.instCount; m->xformDirty = false; m->instDirty.clear();
+  }
+  // (hdGatling calls the visibility setter on every new mesh; a mesh that stays out of the scene has nothing to toggle or refit)
+  for (const NewMesh& nm : fresh) { nm.m->visToggled = false; nm.m->vertsEdited = false; }
+  for (GiCMesh* m : s->meshes) if (m->builtInstances == 0xffffffffu) { m->visToggled = false; m->vertsEdited = false; }
+  s->triCount = newTris; H.bvh.activeTris = newTris;
+  // (with a material edit due as well the resident words index the previous table: updateMaterials derives the classes behind this update)
+  if (!(s->dirty & DIRTY_MATERIALS)) deriveSceneClasses(s, H, false);
+  setSceneBoundsFromInstances(s, H);
+  const double t3 = nowMs();
+  cost.buildMs = tlasMs + blasMs; cost.uploadMs = std::max(t3 - t0 - cost.buildMs, 0.0);
+  if (timing) fprintf(stderr, "[gatling_gi] topology update (two-level): %u mesh(es) retired, %zu appended (%llu face(s), %llu instance(s), %llu flat record(s) made on the "
+                              "device), %llu live + %llu retired triangle(s), %u resident, TLAS %zu node(s), host TLAS build %.2f ms, host BLAS build %.2f ms, host rest "
+                              "%.2f ms, device %.2f ms (bounds kernels + read-back %.2f, commit %.2f of which append kernels %.3f), %zu bytes sent per device\n",
+                      retiring, fresh.size(), (unsigned long long)appendedFaces, (unsigned long long)appendedInstances, (unsigned long long)appendedTris,
+                      (unsigned long long)live, (unsigned long long)retired, s->triCount, T.tlasNodes.size(), tlasMs, blasMs,
+                      std::max((t1 - t0) - tlasMs - blasMs - boundsMs + (t3 - t2), 0.0), boundsMs + (t2 - t1), boundsMs, t2 - t1, appendKernelMs, bytesSent);
+  handled = true;
+  return GI_C_OK;
+}
+
+// What the checks of a resident two-level scene ignore once updateTopologyTwoLevel has retired meshes: one byte per BLAS node, per BLAS triangle and per
+// instance, 1 inside the ranges of a retired mesh (destroyed: its records stay resident until the next build and nothing reaches them -- its instances are
+// out of the TLAS).  `layout`: first BLAS node / triangle and levels by meshIdx, of arrays laid out in storage order.  Empty masks: no mesh is retired
+struct RetiredRanges { std::vector<uint8_t> node, tri, inst; };
+static RetiredRanges retiredRangesOf(const SceneHost& H, const TwoLevelHost& layout, size_t nodeCount, size_t triCount)
+{
+  RetiredRanges R;
+  for (const MeshBuild& mb : H.meshBuilds) {
+    if (!mb.m->retired || mb.instCount == 0u) continue;
+    if (R.inst.empty()) { R.node.assign(nodeCount, 0); R.tri.assign(triCount, 0); R.inst.assign(H.instances.size(), 0); }
+    if (mb.meshIdx >= layout.meshBlasNode.size() || mb.meshIdx >= layout.meshBlasTri.size() || mb.meshIdx >= layout.meshBlasLevels.size()) continue;
+    const std::vector<uint32_t>& lv = layout.meshBlasLevels[mb.meshIdx];
+    const size_t n0 = layout.meshBlasNode[mb.meshIdx], t0 = layout.meshBlasTri[mb.meshIdx], nn = lv.empty() ? 0u : lv.back(), nf = mb.m->faces.size();
+    for (size_t i = n0; i < std::min(n0 + nn, nodeCount); i++) R.node[i] = 1;
+    for (size_t i = t0; i < std::min(t0 + nf, triCount); i++) R.tri[i] = 1;
+    for (const uint32_t inst : mb.inst) if (inst < R.inst.size()) R.inst[inst] = 1;
+  }
+  return R;
+}
+
 // giCDebugSceneTlasCheck: the two-level arrays resident on a device against the arrays buildTwoLevel makes anew from the scene's current meshes, bytewise
+// (storage order: retired meshes and appended ones included, as updateTopologyTwoLevel leaves them; the ranges and records of a retired mesh are ignored)
 extern "C" int giCDebugSceneTlasCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t* out)
 {
   GiCScene* s = const_cast<GiCScene*>(scene);
@@ -2631,12 +2979,16 @@ extern "C" int giCDebugSceneTlasCheck(const GiCScene* scene, uint32_t deviceInde
     (void)hipSetDevice(g_ctx.device);
     if (!ok) { setError("giCDebugSceneTlasCheck: download failed"); return -1; }
     if (H.two.tlasNodes.size() != fresh.tlasNodes.size()) differ++; // (the host copy the next update starts from)
-    auto compare = [&](const auto& got, const auto& want) {
+    // (a retired mesh is a hidden one whose ranges are ignored: the fresh arrays hold it in storage order, so every live and appended mesh's BLAS range is
+    // compared where it lies; the TLAS, which names no instance of it, and the live instances' records are compared whole)
+    const RetiredRanges ignored = retiredRangesOf(H, fresh, fresh.blasNodes.size(), fresh.blasTris.size());
+    const std::vector<uint8_t> none;
+    auto compare = [&](const auto& got, const auto& want, const std::vector<uint8_t>& skip) {
       using R = typename std::remove_reference<decltype(got)>::type::value_type;
-      for (size_t i = 0; i < got.size(); i++) if (memcmp(&got[i], &want[i], sizeof(R)) != 0) differ++;
+      for (size_t i = 0; i < got.size(); i++) if (!(i < skip.size() && skip[i]) && memcmp(&got[i], &want[i], sizeof(R)) != 0) differ++;
     };
-    compare(tlasNodes, fresh.tlasNodes); compare(tlasItems, fresh.tlasItems); compare(instTrav, fresh.instTrav); compare(blasNodes, fresh.blasNodes);
-    compare(blasTris, fresh.blasTris);
+    compare(tlasNodes, fresh.tlasNodes, none); compare(tlasItems, fresh.tlasItems, none); compare(instTrav, fresh.instTrav, ignored.inst);
+    compare(blasNodes, fresh.blasNodes, ignored.node); compare(blasTris, fresh.blasTris, ignored.tri);
     out[2] = (uint32_t)fresh.tlasNodes.size(); out[3] = fresh.tlasDepth;
     return differ;
   } catch (const std::exception& e) { s->twoLevel = true; setError(std::string("giCDebugSceneTlasCheck: ") + e.what()); return -1; }
@@ -2871,8 +3223,9 @@ extern "C" int giCDebugSceneBlasCheck(const GiCScene* scene, uint32_t deviceInde
     std::vector<BlasTri> wantTris(T.blasTris); std::vector<Node8> wantNodes(T.blasNodes);
     std::vector<float> boxes(8u * wantNodes.size(), 0.0f), under(6u * wantNodes.size(), 0.0f);
     uint32_t violations = 0;
+    const RetiredRanges ignored = retiredRangesOf(H, T, T.blasNodes.size(), T.blasTris.size());
     for (const MeshBuild& mb : H.meshBuilds) {
-      if (mb.instCount == 0u) continue;
+      if (mb.instCount == 0u || mb.m->retired) continue; // (a retired mesh -- updateTopologyTwoLevel -- is hidden for good: its ranges are ignored)
       const GiCMesh* m = mb.m;
       const uint32_t first = T.meshBlasTri[mb.meshIdx], nodeBase = T.meshBlasNode[mb.meshIdx], nf = (uint32_t)m->faces.size();
       const std::vector<uint32_t>& lv = T.meshBlasLevels[mb.meshIdx];
@@ -2894,12 +3247,14 @@ extern "C" int giCDebugSceneBlasCheck(const GiCScene* scene, uint32_t deviceInde
     }
     // (d), (e)
     if (T.tlasNodes.size() != fresh.tlasNodes.size()) differ++; // (the host copy the next update starts from)
-    auto compare = [&](const auto& got, const auto& want) {
+    const std::vector<uint8_t> none;
+    auto compare = [&](const auto& got, const auto& want, const std::vector<uint8_t>& skip) {
       using R = typename std::remove_reference<decltype(got)>::type::value_type;
-      for (size_t i = 0; i < got.size(); i++) if (memcmp(&got[i], &want[i], sizeof(R)) != 0) differ++;
+      for (size_t i = 0; i < got.size(); i++) if (!(i < skip.size() && skip[i]) && memcmp(&got[i], &want[i], sizeof(R)) != 0) differ++;
     };
-    compare(tlasNodes, fresh.tlasNodes); compare(tlasItems, fresh.tlasItems); compare(instTrav, fresh.instTrav);
-    for (size_t i = 0; i < instTrav.size(); i++) if (memcmp(&T.instTrav[i], &fresh.instTrav[i], sizeof(InstTrav)) != 0) differ++; // (the host copy)
+    compare(tlasNodes, fresh.tlasNodes, none); compare(tlasItems, fresh.tlasItems, none); compare(instTrav, fresh.instTrav, ignored.inst);
+    for (size_t i = 0; i < instTrav.size(); i++) // (the host copy)
+      if (!(i < ignored.inst.size() && ignored.inst[i]) && memcmp(&T.instTrav[i], &fresh.instTrav[i], sizeof(InstTrav)) != 0) differ++;
     out[1] = (uint32_t)blasNodes.size(); out[2] = violations; out[3] = (uint32_t)blasTris.size();
     return differ + (int)violations;
   } catch (const std::exception& e) { s->twoLevel = true; setError(std::string("giCDebugSceneBlasCheck: ") + e.what()); return -1; }
@@ -2971,6 +3326,94 @@ extern "C" int giCDebugBlasRefitHost(const GiCVertex* a, const GiCVertex* b, uin
     uint32_t* outViolations)
 { return debugBlasRefit("giCDebugBlasRefitHost", false, a, b, vertexCount, faces, faceCount, outNodes, outViolations); }
 
+// giCDebugAppendRecords / giCDebugAppendRecordsHost: one mesh appended behind `vertexOffset` vertex records, `shadeBase` shading records, a few BLAS and flat
+// records and the scene-order id `idBase` -- its shading records, BLAS records, flat records, face-id words and id-table words made by the host forms of
+// gi_append.h and, onDevice, by k_append_shade_index + k_gather_shade + k_append_blas_tris + k_append_records on scratch arrays, against the scene build's own
+// code (packTriShade, makeBlasTri in buildMeshBlas's order, flattenInstance as buildSceneTreeless leaves its records, faceIdAovOf, flatOfOrig[id] = position).
+// Every array starts as 0xa5 bytes on both sides: a store outside the mesh's ranges is seen.  Returns the bytes that differ
+static int debugAppendRecords(const char* name, bool onDevice, const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount,
+    const int32_t* faceIds, uint32_t maxFaceId, uint32_t flags, const float* xforms16, uint32_t xformCount, uint32_t vertexOffset, uint32_t shadeBase, uint32_t idBase,
+    uint32_t matFlags)
+{
+  if (onDevice && !g_ctx.initialized) { setError(std::string(name) + " before giCInitialize"); return -1; }
+  if (!vertices || !faces || !xforms16 || vertexCount == 0u || faceCount == 0u || xformCount == 0u || (uint64_t)faceCount * xformCount >= (1ull << 24) ||
+      vertexOffset >= (1u << 20) || shadeBase >= (1u << 20) || idBase >= (1u << 24)) { setError(std::string(name) + ": bad arguments"); return -1; }
+  for (uint32_t f = 0; f < faceCount; f++) for (int k = 0; k < 3; k++) if (faces[f].v_i[k] >= vertexCount) { setError(std::string(name) + ": a face index outside the vertices"); return -1; }
+  try {
+    GiCMesh m; m.scene = nullptr; m.id = 11; m.flipFacing = (flags & 1u) != 0u; m.doubleSided = (flags & 2u) != 0u; m.maxFaceId = maxFaceId;
+    m.vertices.assign(vertices, vertices + vertexCount); m.faces.assign(faces, faces + faceCount);
+    if (faceIds) m.faceIds.assign(faceIds, faceIds + faceCount);
+    m.instanceTransforms.assign(xforms16, xforms16 + (size_t)xformCount * 16u);
+    constexpr uint32_t meshIdx = 2u, instFirst = 5u, triFirst = 7u, blasFirst = 3u; // (as a mesh behind others in every array)
+    const uint32_t items = faceCount * xformCount, triCount = triFirst + items, instanceCount = instFirst + xformCount, shadeCount = shadeBase + faceCount;
+    const uint32_t vertCount = vertexOffset + vertexCount, blasCount = blasFirst + faceCount, flatCount = idBase + items;
+    std::vector<InstanceRec> instances(instanceCount, InstanceRec{});
+    for (uint32_t i = 0; i < xformCount; i++) { instances[instFirst + i] = makeInstanceRec(&m, meshIdx, i);
+        if (!usableInstance(instances[instFirst + i])) { setError(std::string(name) + ": an instance transform is not usable"); return -1; } }
+    std::vector<FVertex> verts(vertCount, FVertex{});
+    for (uint32_t i = 0; i < vertexCount; i++) verts[vertexOffset + i] = packVertex(vertices[i]);
+    std::vector<uint32_t> faces3(3u * (size_t)faceCount);
+    for (uint32_t f = 0; f < faceCount; f++) for (int k = 0; k < 3; k++) faces3[3u * (size_t)f + k] = faces[f].v_i[k];
+    Bvh8 blas; std::vector<uint32_t> order; float mlo[3], mhi[3];
+    buildMeshBlas(vertices, faces, faceCount, blas, order, mlo, mhi);
+    if (order.size() != faceCount) { setError(std::string(name) + ": the builder left faces out (an unusable position)"); return -1; }
+    const std::vector<int32_t> faceIdAov = faceIdAovOf(&m);
+    // --- the scene build's forms over arrays of 0xa5 bytes
+    auto filled = [](auto& v, size_t n) { v.resize(n); if (n) memset(static_cast<void*>(v.data()), 0xa5, n * sizeof(v[0])); };
+    std::vector<TriShade> wantShade, gotShade; std::vector<BlasTri> wantBlas, gotBlas; std::vector<TriRec> wantTris, gotTris; std::vector<int32_t> wantFaceId, gotFaceId;
+    std::vector<uint32_t> wantFlat, gotFlat;
+    filled(wantShade, shadeCount); filled(gotShade, shadeCount); filled(wantBlas, blasCount); filled(gotBlas, blasCount); filled(wantTris, triCount); filled(gotTris, triCount);
+    filled(wantFaceId, triCount); filled(gotFaceId, triCount); filled(wantFlat, flatCount); filled(gotFlat, flatCount);
+    for (uint32_t f = 0; f < faceCount; f++) wantShade[shadeBase + f] = packTriShade(vertices, faces[f], vertexOffset);
+    for (uint32_t i = 0; i < faceCount; i++) wantBlas[blasFirst + i] = makeBlasTri(vertices, faces, order[i]);
+    for (uint32_t i = 0; i < xformCount; i++) {
+      const uint32_t at = triFirst + i * faceCount, base = idBase + i * faceCount;
+      flattenInstance(instances[instFirst + i], instFirst + i, &m, vertexOffset, matFlags, base, shadeBase, &wantTris[at]);
+      for (uint32_t f = 0; f < faceCount; f++) { wantFaceId[at + f] = faceIdAov[f]; wantFlat[base + f] = at + f; }
+    }
+    AppendMesh M{}; M.triFirst = triFirst; M.faceCount = faceCount; M.instFirst = instFirst; M.instCount = xformCount; M.shadeBase = shadeBase; M.idBase = idBase;
+    M.matFlags = matFlags; M.triCount = triCount; M.instanceCount = instanceCount; M.shadeCount = shadeCount; M.flatCount = flatCount;
+    if (!appendMeshRangesOk(M)) { setError(std::string(name) + ": internal: ranges"); return -1; }
+    if (!onDevice) {
+      appendShadeIndexHost(gotShade.data(), shadeCount, shadeBase, faces3.data(), faceCount, vertexOffset);
+      for (uint32_t f = 0; f < faceCount; f++) refit_gather_shade(verts.data(), vertCount, gotShade[shadeBase + f]);
+      appendBlasTrisHost(gotBlas.data(), blasCount, blasFirst, order.data(), faceCount, gotShade.data(), shadeCount, shadeBase);
+      appendRecordsHost(M, 0u, items, gotTris.data(), gotFaceId.data(), gotFlat.data(), instances.data(), gotShade.data(), faceIdAov.data());
+    } else {
+      DeviceBuffer<TriShade> dShade; DeviceBuffer<BlasTri> dBlas; DeviceBuffer<TriRec> dTris; DeviceBuffer<int32_t> dFaceId, dFaceIdOfFace; DeviceBuffer<uint32_t> dFlat, dFaces, dOrder;
+      DeviceBuffer<InstanceRec> dInstances; DeviceBuffer<FVertex> dVerts;
+      hipStream_t st = g_ctx.stream;
+      bool ok = hipSetDevice(g_ctx.device) == hipSuccess && dShade.upload(gotShade, st) == GI_C_OK && dBlas.upload(gotBlas, st) == GI_C_OK && dTris.upload(gotTris, st) == GI_C_OK &&
+          dFaceId.upload(gotFaceId, st) == GI_C_OK && dFlat.upload(gotFlat, st) == GI_C_OK && dFaces.upload(faces3, st) == GI_C_OK && dOrder.upload(order, st) == GI_C_OK &&
+          dFaceIdOfFace.upload(faceIdAov, st) == GI_C_OK && dInstances.upload(instances, st) == GI_C_OK && dVerts.upload(verts, st) == GI_C_OK;
+      ok = ok && launchAppendShadeIndex(st, dShade.ptr, shadeCount, shadeBase, dFaces.ptr, faceCount, vertexOffset) &&
+          launchGatherShade(st, dShade.ptr, shadeCount, shadeBase, faceCount, dVerts.ptr, vertCount) &&
+          launchAppendBlasTris(st, dBlas.ptr, blasCount, blasFirst, dOrder.ptr, faceCount, dShade.ptr, shadeCount, shadeBase) &&
+          launchAppendRecords(st, M, dTris.ptr, dFaceId.ptr, dFlat.ptr, dInstances.ptr, dShade.ptr, dFaceIdOfFace.ptr);
+      ok = ok && hipGetLastError() == hipSuccess;
+      ok = ok && hipMemcpyAsync(gotShade.data(), dShade.ptr, gotShade.size() * sizeof(TriShade), hipMemcpyDeviceToHost, st) == hipSuccess &&
+          hipMemcpyAsync(gotBlas.data(), dBlas.ptr, gotBlas.size() * sizeof(BlasTri), hipMemcpyDeviceToHost, st) == hipSuccess &&
+          hipMemcpyAsync(gotTris.data(), dTris.ptr, gotTris.size() * sizeof(TriRec), hipMemcpyDeviceToHost, st) == hipSuccess &&
+          hipMemcpyAsync(gotFaceId.data(), dFaceId.ptr, gotFaceId.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+          hipMemcpyAsync(gotFlat.data(), dFlat.ptr, gotFlat.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess;
+      ok = hipStreamSynchronize(st) == hipSuccess && ok;
+      dShade.release(); dBlas.release(); dTris.release(); dFaceId.release(); dFaceIdOfFace.release(); dFlat.release(); dFaces.release(); dOrder.release();
+      dInstances.release(); dVerts.release();
+      if (!ok) { setError(std::string(name) + ": device error"); return -1; }
+    }
+    auto bytesDiffering = [](const void* x, const void* y, size_t n) { int d = 0; for (size_t i = 0; i < n; i++) d += ((const uint8_t*)x)[i] != ((const uint8_t*)y)[i]; return d; };
+    return bytesDiffering(gotShade.data(), wantShade.data(), gotShade.size() * sizeof(TriShade)) + bytesDiffering(gotBlas.data(), wantBlas.data(), gotBlas.size() * sizeof(BlasTri)) +
+        bytesDiffering(gotTris.data(), wantTris.data(), gotTris.size() * sizeof(TriRec)) + bytesDiffering(gotFaceId.data(), wantFaceId.data(), gotFaceId.size() * sizeof(int32_t)) +
+        bytesDiffering(gotFlat.data(), wantFlat.data(), gotFlat.size() * sizeof(uint32_t));
+  } catch (const std::exception& e) { setError(std::string(name) + ": " + e.what()); return -1; }
+}
+extern "C" int giCDebugAppendRecords(const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, const int32_t* faceIds, uint32_t maxFaceId,
+    uint32_t flags, const float* xforms16, uint32_t xformCount, uint32_t vertexOffset, uint32_t shadeBase, uint32_t idBase, uint32_t matFlags)
+{ return debugAppendRecords("giCDebugAppendRecords", true, vertices, vertexCount, faces, faceCount, faceIds, maxFaceId, flags, xforms16, xformCount, vertexOffset, shadeBase, idBase, matFlags); }
+extern "C" int giCDebugAppendRecordsHost(const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, const int32_t* faceIds, uint32_t maxFaceId,
+    uint32_t flags, const float* xforms16, uint32_t xformCount, uint32_t vertexOffset, uint32_t shadeBase, uint32_t idBase, uint32_t matFlags)
+{ return debugAppendRecords("giCDebugAppendRecordsHost", false, vertices, vertexCount, faces, faceCount, faceIds, maxFaceId, flags, xforms16, xformCount, vertexOffset, shadeBase, idBase, matFlags); }
+
 // brings the device scene up to date with the host-side edits: incremental for DIRTY_BVH raised by vertex edits alone (opt-in: the tree refitted on the
 // device), by visibility toggles alone (opt-in: ids renumbered, the
 // toggled meshes' triangles hidden / shown in place), for material-side edits alone (the small arrays + one word per triangle) and for transform edits alone
@@ -3002,7 +3445,9 @@ int syncSceneGeometry(GiCScene* s)
   if (s->topologyDue && !topologyUpdatesWanted(s)) s->rebuildDue = true;
   if (s->instancesDue && !instanceUpdatesWanted(s)) s->rebuildDue = true;
   const bool topologyRuns = (s->dirty & DIRTY_BVH) && !s->rebuildDue && (s->topologyDue || s->instancesDue);
-  int rc = run(topologyRuns, updateTopology, UPDATE_TOPOLOGY, 0u, DIRTY_BVH, 0u);
+  // (a topology update of the two-level layout has a counter of its own: giCDebugSceneTopologyUpdateCount keeps counting what it counted)
+  const uint32_t topologyCounter = s->twoLevel && tlasTopologyWanted(s) && incrementalHost(s) ? (uint32_t)UPDATE_TLAS_TOPOLOGY : (uint32_t)UPDATE_TOPOLOGY;
+  int rc = run(topologyRuns, updateTopology, topologyCounter, 0u, DIRTY_BVH, 0u);
   bool anyVis = false, anyVerts = false;
   for (const GiCMesh* m : s->meshes) { anyVis = anyVis || m->visToggled; anyVerts = anyVerts || m->vertsEdited; }
   if (rc == GI_C_OK && topologyRuns && !s->rebuildDue && !anyVis && !anyVerts) s->dirty &= ~DIRTY_BVH;

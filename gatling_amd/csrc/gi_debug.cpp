@@ -621,6 +621,15 @@ extern "C" int giCDebugSceneTlasVisibilityUpdateCount(const GiCScene* scene, uin
   return GI_C_OK;
 }
 
+extern "C" int giCDebugSceneTlasTopologyUpdateCount(const GiCScene* scene, uint64_t* outCount)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!s || !outCount) { setError("giCDebugSceneTlasTopologyUpdateCount: bad arguments"); return GI_C_ERROR; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  *outCount = s->updateCounts[UPDATE_TLAS_TOPOLOGY];
+  return GI_C_OK;
+}
+
 extern "C" int giCDebugSceneInstanceUpdateCount(const GiCScene* scene, uint64_t* out)
 {
   GiCScene* s = const_cast<GiCScene*>(scene);

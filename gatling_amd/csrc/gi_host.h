@@ -353,7 +353,7 @@ struct SceneHost {
   bool treeless = false;
 };
 
-enum : uint32_t { UPDATE_FULL = 0, UPDATE_TRANSFORM = 1, UPDATE_MATERIAL = 2, UPDATE_VISIBILITY = 3, UPDATE_VERTEX = 4, UPDATE_TOPOLOGY = 5, UPDATE_TLAS = 6, UPDATE_BLAS = 7, UPDATE_TLAS_VISIBILITY = 8 }; // GiCScene::updateCounts
+enum : uint32_t { UPDATE_FULL = 0, UPDATE_TRANSFORM = 1, UPDATE_MATERIAL = 2, UPDATE_VISIBILITY = 3, UPDATE_VERTEX = 4, UPDATE_TOPOLOGY = 5, UPDATE_TLAS = 6, UPDATE_BLAS = 7, UPDATE_TLAS_VISIBILITY = 8, UPDATE_TLAS_TOPOLOGY = 9 }; // GiCScene::updateCounts
 struct GiCScene : SceneDevice {
   std::mutex mutex;
   uint32_t dirty = DIRTY_ALL;
@@ -411,8 +411,9 @@ struct GiCScene : SceneDevice {
   // a look-ahead window traced under another generation is not served from
   uint64_t generation = 0;
   // syncSceneGeometry, by UPDATE_*: full builds and incremental updates (giCDebugSceneUpdateCounts: the first three; giCDebugSceneVisibilityUpdateCount,
-  // giCDebugSceneVertexUpdateCount, giCDebugSceneTopologyUpdateCount, giCDebugSceneTlasUpdateCount, giCDebugSceneBlasUpdateCount, giCDebugSceneTlasVisibilityUpdateCount)
-  uint64_t updateCounts[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  // giCDebugSceneVertexUpdateCount, giCDebugSceneTopologyUpdateCount, giCDebugSceneTlasUpdateCount, giCDebugSceneBlasUpdateCount, giCDebugSceneTlasVisibilityUpdateCount,
+  // giCDebugSceneTlasTopologyUpdateCount)
+  uint64_t updateCounts[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   int32_t optVisibilityUpdates = 0; // GI_C_SCENE_OPTION_VISIBILITY_UPDATES: 1 = visibility edits are applied to the resident scene (updateVisibility)
   int32_t optVertexUpdates = 0; // GI_C_SCENE_OPTION_VERTEX_UPDATES: 1 = vertex edits refit the resident tree (updateVertices)
   // DIRTY_BVH was raised by something other than giCSetMeshVisibility / giCSetMeshVertices since the last syncSceneGeometry (raiseRebuild): the rebuild is due
@@ -442,6 +443,9 @@ struct GiCScene : SceneDevice {
   // GI_C_SCENE_OPTION_TLAS_ONLY: 1 = a scene that takes the two-level layout is built without the flat tree (buildScene; SceneHost::treeless); read at the
   // build only, and only with the two-level layout wanted
   int32_t optTlasOnly = 0;
+  // GI_C_SCENE_OPTION_TLAS_TOPOLOGY: 1 = meshes are created and destroyed in a resident two-level scene that was built without the flat tree
+  // (updateTopologyTwoLevel; read only with topology updates wanted)
+  int32_t optTlasTopology = 0;
   std::vector<GiCMesh*> retiredMeshes; // destroyed meshes the resident scene still refers to (GiCMesh::retired): freed by buildScene and with the scene
   ~GiCScene() { for (GiCMesh* m : retiredMeshes) delete m; }
 };
@@ -472,6 +476,7 @@ bool blasUpdatesWanted(const GiCScene* s);                   // GI_C_SCENE_OPTIO
 bool tlasOnlyWanted(const GiCScene* s);                      // GI_C_SCENE_OPTION_TLAS_ONLY / GATLING_OPTIONS=tlas_only (read at the build, with the two-level layout wanted)
 bool tlasVisibilityWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_TLAS_VISIBILITY / GATLING_OPTIONS=tlas_visibility (with visibility updates wanted)
 bool topologyUpdatesWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_TOPOLOGY_UPDATES / GATLING_OPTIONS=topology_updates
+bool tlasTopologyWanted(const GiCScene* s);                  // GI_C_SCENE_OPTION_TLAS_TOPOLOGY / GATLING_OPTIONS=tlas_topology (with topology updates wanted)
 int syncSceneGeometry(GiCScene* s);                          // brings the device scene up to date with the host-side edits (incremental or full build)
 // dirty flags of a material-side edit: DIRTY_MATERIALS alone once the scene / the mesh is part of a built scene (the incremental path), else with DIRTY_BVH
 inline uint32_t materialEditFlags(bool built) { return DIRTY_MATERIALS | DIRTY_FRAMEBUFFER | (built ? 0u : (uint32_t)DIRTY_BVH); }

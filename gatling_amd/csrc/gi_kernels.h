@@ -143,6 +143,18 @@ bool launchBlasTris(hipStream_t s, BlasTri* blasTris, uint32_t blasTriCount, uin
     uint32_t shadeBase);
 void launchBlasRefitLevel(hipStream_t s, Node8* nodes, uint32_t nodeCount, float* boxes, const RefitRange* ranges, uint32_t rangeCount, uint32_t threads,
     const BlasTri* blasTris, uint32_t blasTriCount);
+// gi_append.hip: a mesh appended to a resident two-level scene without the flat tree (gi_build.cpp updateTopologyTwoLevel, GI_C_SCENE_OPTION_TLAS_TOPOLOGY;
+// gi_append.h has every per-item form and AppendMesh).  On one stream, in this order: launchAppendShadeIndex writes TriShade::vi / pad of the mesh's faces
+// (`faces3`: three indices per face, relative to the mesh), launchGatherShade fills the rest of those records from the vertex records, then
+// launchAppendBlasTris writes the mesh's whole BlasTri records in the builder's `order` and launchAppendRecords the flat records, face-id words and id-table
+// words of all its instances.  Each returns false, and launches nothing, where a range lies outside its array or the threads do not fit a launch
+struct AppendMesh;
+bool launchAppendShadeIndex(hipStream_t s, TriShade* triShade, uint32_t shadeCount, uint32_t shadeBase, const uint32_t* faces3, uint32_t faceCount,
+    uint32_t vertexOffset);
+bool launchAppendBlasTris(hipStream_t s, BlasTri* blasTris, uint32_t blasTriCount, uint32_t first, const uint32_t* order, uint32_t faceCount,
+    const TriShade* triShade, uint32_t shadeCount, uint32_t shadeBase);
+bool launchAppendRecords(hipStream_t s, const AppendMesh& M, TriRec* tris, int32_t* triFaceId, uint32_t* flatOfOrig, const InstanceRec* instances,
+    const TriShade* triShade, const int32_t* faceIdOfFace);
 void launchSpin(hipStream_t s, unsigned long long ns);           // test hook: occupies a stream for ~ns nanoseconds
 void launchDebugBsdf(hipStream_t s, const MaterialRec* mat, uint32_t shadeClass, uint32_t count, const float* in, float* out);
 void launchDebugSqrt(hipStream_t s, uint32_t first, unsigned long long count, unsigned long long* mismatches); // gi_sqrt against sqrtf over bit patterns

@@ -73,6 +73,9 @@
 //   tlas_only            -1        -1 = the scene option decides (GI_C_SCENE_OPTION_TLAS_ONLY), 0 / 1 = a scene that wants the two-level layout builds the flat
 //                                  tree beside it / builds, sends and keeps no flat tree (gi_build.cpp buildScene; AOVs walk the TLAS: gi_aov2.hip); read at
 //                                  the scene build, and only with the two-level layout wanted
+//   tlas_topology        -1        -1 = the scene option decides (GI_C_SCENE_OPTION_TLAS_TOPOLOGY), 0 / 1 = mesh creations and destructions on a two-level
+//                                  scene built without the flat tree rebuild it / are applied to the resident scene (gi_build.cpp updateTopologyTwoLevel; the
+//                                  per-triangle records are made on the device: gi_append.hip); read only with topology_updates wanted
 //   phase_stats          0         counting builds: print k_path's phase split / k_trace_dyn's lane accounting
 #pragma once
 

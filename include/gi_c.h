@@ -383,7 +383,8 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * giCDebugSceneInstanceUpdateCount and giCDebugCloneInstance, and for GI_C_SCENE_OPTION_TLAS_UPDATES, giCDebugSceneTlasUpdateCount, giCDebugSceneTlasCheck
  * and giCDebugInstanceBounds, and for GI_C_SCENE_OPTION_BLAS_UPDATES, giCDebugSceneBlasUpdateCount, giCDebugSceneBlasCheck, giCDebugBlasRefit and
  * giCDebugBlasRefitHost, and for GI_C_SCENE_OPTION_TLAS_VISIBILITY, giCDebugSceneTlasVisibilityUpdateCount, giCDebugSceneFlatIdCheck and
- * giCDebugPatchVisibilityTwoLevel, and for GI_C_SCENE_OPTION_TLAS_ONLY and giCDebugSceneFlatTreeState. */
+ * giCDebugPatchVisibilityTwoLevel, and for GI_C_SCENE_OPTION_TLAS_ONLY and giCDebugSceneFlatTreeState, and for GI_C_SCENE_OPTION_TLAS_TOPOLOGY,
+ * giCDebugSceneTlasTopologyUpdateCount, giCDebugAppendRecords and giCDebugAppendRecordsHost. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -645,6 +646,21 @@ int giCGetRenderStats(const GiCScene* scene, GiCRenderStats* out);
  * tree GiCRenderStats.nodeCount is 0 and giCDebugValidateSceneBvh answers with an error.  GATLING_OPTIONS=tlas_only=0|1 overrides the option (hdGatling
  * sets no scene options).  DESIGN.md section 6. */
 #define GI_C_SCENE_OPTION_TLAS_ONLY 19
+/* [ext] Mesh creations and destructions on a two-level scene built without the flat tree (GI_C_SCENE_OPTION_TLAS_ONLY); read only with
+ * GI_C_SCENE_OPTION_TOPOLOGY_UPDATES wanted (value 1 or GATLING_OPTIONS=topology_updates=1): value 1 = a giCDestroyMesh / giCCreateMesh of such a scene is
+ * applied to the resident scene by the next giCRender when nothing else asks for a rebuild.  A destroyed mesh is retired as a visibility update hides one
+ * (option 18's device pass renumbers the ids behind it; its instances leave the TLAS; its BLAS, flat records and shading records stay resident until the
+ * next full build).  A created mesh is appended behind every built one: the host sends its vertex records, faces, face ids and instance records, builds its
+ * one BLAS and the TLAS over one box more per instance; its shading records, BLAS triangles, flat records, face-id words and id-table words are made on
+ * the device (gi_append.hip), so nothing per flattened triangle crosses the link.  0 = off (default): such an edit rebuilds the scene, as before.  The image
+ * does not depend on the option.  The scene is rebuilt instead when: it keeps a flat tree (option 19 off, or declined at the build); there is no host copy or
+ * GATLING_OPTIONS=incremental=0; fewer than 4 096 triangles stay visible; retired triangles outnumber live ones; a new mesh lies in front of a built one in
+ * creation order; a new mesh has a vertex position that is not finite or beyond 1e18, an instance transform that is not finite or singular, or triangles
+ * that leave the usable range in world space; the scene was built with inactive triangles; 2^26 unique BLAS triangles or 2^28 flat records would be
+ * reached; the new TLAS would be too deep for the layout's 16-entry stack; a material index beyond 2^24; out of device memory; an instance count or id
+ * edit of a built mesh is due (option 15 has no two-level form).  Material, transform, vertex and visibility edits due in the same render take the paths of
+ * options 16 - 18 behind this update.  GATLING_OPTIONS=tlas_topology=0|1 overrides the option (hdGatling sets no scene options).  DESIGN.md section 6. */
+#define GI_C_SCENE_OPTION_TLAS_TOPOLOGY 20
 int giCGetLookaheadStats(const GiCScene* scene, GiCLookaheadStats* out);
 int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value);
 /* [ext] closest hit of one ray through the device traversal kernel (parity tests of the BVH8 path).
@@ -745,7 +761,9 @@ int giCDebugSceneShadeCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_
 int giCDebugSceneTlasUpdateCount(const GiCScene* scene, uint64_t* outCount);
 /* [ext] [debug] the two-level arrays resident on device `deviceIndex` of a scene rendered at least once -- TLAS nodes, TLAS items, per-instance traversal
  * records, BLAS nodes, BLAS triangles -- downloaded and compared with the arrays the scene build's own code makes anew from the scene's current meshes.
- * Returns the number of records that differ bytewise (0 after a build as after every update in place), <0 on error.  out[0]: 1 when the two-level layout is
+ * Returns the number of records that differ bytewise (0 after a build as after every update in place), <0 on error.  After topology updates in place
+ * (GI_C_SCENE_OPTION_TLAS_TOPOLOGY) the arrays are made anew over the meshes in storage order, appended ones at the end: every BLAS range is compared where it
+ * lies; a retired (destroyed) mesh is a hidden one -- out of the TLAS -- and its BLAS ranges and traversal records are ignored.  out[0]: 1 when the two-level layout is
  * in use (0: nothing was compared), [1] instances, [2] TLAS nodes, [3] TLAS depth. */
 int giCDebugSceneTlasCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t* out /* 4 */);
 /* [ext] [debug] device check of the kernels that make the world boxes of moved instances (gi_tlas.hip k_inst_bounds / k_inst_finish): the mesh (`vertices`,
@@ -764,7 +782,8 @@ int giCDebugSceneBlasUpdateCount(const GiCScene* scene, uint64_t* outCount);
  * over the host's copy of the build's topology and the current points; (d) a resident TLAS node or item that differs bytewise from a fresh build's over the
  * current meshes (instance boxes do not depend on a BLAS's shape); (e) a resident per-instance traversal record that differs from the fresh one with its
  * BLAS root replaced by the resident BLAS's.  (c), reported separately: out[2] counts the violations of the conservative check -- every node's dequantised
- * slot box contains the padded boxes of all faces below it, every usable face is named by exactly one leaf slot.  Returns the number of differences plus those violations (0), <0
+ * slot box contains the padded boxes of all faces below it, every usable face is named by exactly one leaf slot.  A mesh retired by a topology update in place
+ * (GI_C_SCENE_OPTION_TLAS_TOPOLOGY) is skipped: its ranges and records are ignored, as a hidden mesh it is out of the TLAS.  Returns the number of differences plus those violations (0), <0
  * on error.  out[0]: 1 when the two-level layout is in use (0: nothing was compared), [1] BLAS nodes compared, [2] conservative violations, [3] BLAS
  * triangles compared. */
 int giCDebugSceneBlasCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t* out /* 4 */);
@@ -783,6 +802,22 @@ int giCDebugBlasRefitHost(const GiCVertex* a, const GiCVertex* b, uint32_t verte
 /* [ext] [debug] how often the scene was brought up to date by a visibility update of the two-level layout (GI_C_SCENE_OPTION_TLAS_VISIBILITY); counted neither
  * in giCDebugSceneUpdateCounts nor in giCDebugSceneVisibilityUpdateCount. */
 int giCDebugSceneTlasVisibilityUpdateCount(const GiCScene* scene, uint64_t* outCount);
+/* [ext] [debug] how often the scene was brought up to date by a topology update of the two-level layout (GI_C_SCENE_OPTION_TLAS_TOPOLOGY); counted neither in
+ * giCDebugSceneUpdateCounts nor in giCDebugSceneTopologyUpdateCount. */
+int giCDebugSceneTlasTopologyUpdateCount(const GiCScene* scene, uint64_t* outCount);
+/* [ext] [debug] device check of the kernels that make an appended mesh's records (gi_append.hip k_append_shade_index, k_append_blas_tris, k_append_records,
+ * with gi_refit.hip k_gather_shade between them): the mesh (`vertices`, `faces`: 3 indices per face, `faceIds`: faceCount entries or NULL, `maxFaceId`,
+ * `flags`: bit 0 flip-facing, bit 1 double-sided) under `xformCount` instance transforms (16 floats each, USD row vectors), laid out behind `vertexOffset`
+ * vertex records, `shadeBase` shading records and the scene-order id `idBase`, with the word `matFlags`.  The kernels run on scratch arrays; returns the number
+ * of BYTES of the shading records, BLAS records (in the host builder's order), flat records, face-id words and id-table words that differ from the scene
+ * build's own host forms (flattenInstance, packTriShade, makeBlasTri, faceIdAovOf, id == position in the table) (0 is the contract), <0 on error (no device,
+ * a null array, an index outside the vertices, an unusable transform).  giCDebugAppendRecordsHost: the host forms of the same kernels (gi_append.h) against
+ * the same references; no device use. */
+int giCDebugAppendRecords(const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, const int32_t* faceIds, uint32_t maxFaceId,
+                          uint32_t flags, const float* xforms16, uint32_t xformCount, uint32_t vertexOffset, uint32_t shadeBase, uint32_t idBase, uint32_t matFlags);
+int giCDebugAppendRecordsHost(const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, const int32_t* faceIds, uint32_t maxFaceId,
+                              uint32_t flags, const float* xforms16, uint32_t xformCount, uint32_t vertexOffset, uint32_t shadeBase, uint32_t idBase,
+                              uint32_t matFlags);
 /* [ext] [debug] what a built scene holds of the flat tree (GI_C_SCENE_OPTION_TLAS_ONLY): out[0] = 1 for the two-level layout, out[1] = 1 when the scene was built
  * without the flat tree, out[2] = flat nodes resident on device copy `device`, out[3] = bytes of flat nodes the host copy holds.  GI_C_OK, or GI_C_ERROR for a
  * scene that has not been built or a device copy that does not exist. */
@@ -790,7 +825,7 @@ int giCDebugSceneFlatTreeState(const GiCScene* scene, uint32_t device, uint64_t 
 /* [ext] [debug] the flat triangle records, the id table (scene-order id -> flat record) and the per-instance traversal records resident on device
  * `deviceIndex` of a scene rendered at least once, downloaded and checked.  Returns the number of violations of: the ids of the records of visible instances
  * are a permutation of [0, visible triangles); the table names each of them at its id; its instance's triBase + prim is its id; records of hidden instances
- * have zero edges (0), <0 on error.  out[0]: visible triangles, [1] resident triangles, [2] hidden instances, [3] 1 when the two-level layout is in use (0:
+ * have zero edges (0), <0 on error.  A mesh retired by a topology update in place counts as a hidden one: its ids are skipped.  out[0]: visible triangles, [1] resident triangles, [2] hidden instances, [3] 1 when the two-level layout is in use (0:
  * nothing was compared). */
 int giCDebugSceneFlatIdCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t* out /* 4 */);
 /* [ext] [debug] device check of the kernels of a visibility update of the two-level layout (gi_patch.hip k_patch_visibility2 / k_patch_inst_trav).  The
