@@ -33,6 +33,7 @@ OPTION_BLAS_UPDATES = 17  # 1: vertex edits of a built two-level scene are appli
 OPTION_TLAS_VISIBILITY = 18  # 1: visibility edits of a built two-level scene are applied to the resident scene -- ids, the id table and the instances' id bases renumbered on the device, a new TLAS over the visible instances -- instead of rebuilding it; read only with OPTION_VISIBILITY_UPDATES wanted (include/gi_c.h); 0 = off (default)
 OPTION_TLAS_ONLY = 19  # 1: a scene that takes the two-level layout (OPTION_TWO_LEVEL 1, or 2^26 flattened triangles) is built without the flat BVH8 -- the flat records stay in scene order, the non-colour AOVs walk the TLAS (k_aov2), the scene bounds come from the instance boxes and the edits in place of options 16 - 18 run without the flat refit; read at the scene build only (include/gi_c.h); 0 = off (default)
 OPTION_TLAS_TOPOLOGY = 20  # 1: mesh creations and destructions on a built two-level scene without the flat tree (OPTION_TLAS_ONLY) are applied to the resident scene -- a destroyed mesh retired as a hidden one, a created mesh appended: one BLAS from the host, its shading records, BLAS triangles, flat records, face ids and id-table words made on the device (gi_append.hip) -- instead of rebuilding it; read only with OPTION_TOPOLOGY_UPDATES wanted (include/gi_c.h); 0 = off (default)
+OPTION_TLAS_INSTANCES = 21  # 1: instance-id and instance-count edits of built meshes on a built two-level scene without the flat tree (OPTION_TLAS_ONLY) are applied to the resident scene -- retired instances hidden and their storage slots reused by later grows of the same mesh, new instances' flat records made on the device in one launch (gi_instances.hip) -- instead of rebuilding it; read only with OPTION_TOPOLOGY_UPDATES, OPTION_INSTANCE_UPDATES and OPTION_TLAS_TOPOLOGY wanted (include/gi_c.h); 0 = off (default)
 OPTION_BVH_BUILD = 9  # 0 = host BVH builder (default), 1 = device builder (flat-layout scenes of more than 128 triangles)
 
 
@@ -188,6 +189,9 @@ SYMBOLS = [
     ("giCDebugSceneTlasTopologyUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugAppendRecords", C.c_int, [_P, _U, _P, _U, _P, _U, _U, _FP, _U, _U, _U, _U, _U]),
     ("giCDebugAppendRecordsHost", C.c_int, [_P, _U, _P, _U, _P, _U, _U, _FP, _U, _U, _U, _U, _U]),
+    ("giCDebugInstanceRecords", C.c_int, [_P, _U, _P, _U]),
+    ("giCDebugInstanceRecordsHost", C.c_int, [_P, _U, _P, _U]),
+    ("giCDebugSceneTlasInstanceUpdateStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugPatchVisibilityTwoLevel", C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _U, _U, C.POINTER(C.c_uint32)]),
     ("giCDebugPathWalkStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugPathLobeStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
@@ -322,6 +326,52 @@ def debug_append_records(vertices, faces, xforms, face_ids=None, max_face_id=0, 
            x.ctypes.data_as(_FP), len(x), int(vertex_offset), int(shade_base), int(id_base), int(mat_flags))
     if n < 0:
         raise GiError("giCDebugAppendRecords failed: " + L.giCGetLastError().decode())
+    return int(n)
+
+
+class _DebugInstanceMesh(C.Structure):
+    _fields_ = [("vertices", C.c_void_p), ("faces", C.c_void_p), ("faceIds", C.c_void_p), ("vertexCount", C.c_uint32), ("faceCount", C.c_uint32),
+                ("maxFaceId", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class _DebugInstanceJob(C.Structure):
+    _fields_ = [("mesh", C.c_uint32), ("instanceSlot", C.c_uint32), ("recordSlot", C.c_uint32), ("idBase", C.c_uint32), ("transform", C.c_float * 16)]
+
+
+def debug_instance_records(meshes, jobs, host_only=False) -> int:
+    """giCDebugInstanceRecords: the device kernel that makes the flat records, face-id words and id-table words of new instances of built meshes on a two-level
+    scene without the flat tree (k_instance_records, one launch for all jobs) against the scene build's own host code.  `meshes`: dicts with "vertices"
+    (VERTEX_DTYPE), "faces" (n x 3) and optionally "face_ids" (n), "max_face_id", "flip_facing", "double_sided"; `jobs`: dicts with "mesh" (index), "xform"
+    (4 x 4, USD row vectors), "instance_slot", "record_slot" (first flat record) and "id_base" -- slots in any order, with gaps.  Returns the number of differing
+    bytes over the whole scratch arrays (0 is the contract).  host_only: giCDebugInstanceRecordsHost, the host form of the kernel (gi_instances.h) against the
+    same references (no device)."""
+    from .scene import VERTEX_DTYPE
+    L = load_library()
+    keep = []
+    ms = (_DebugInstanceMesh * max(len(meshes), 1))()
+    for k, m in enumerate(meshes):
+        v = None if m.get("vertices") is None else np.ascontiguousarray(m["vertices"], VERTEX_DTYPE)
+        f = None if m.get("faces") is None else np.ascontiguousarray(m["faces"], np.uint32).reshape(-1, 3)
+        ids = None if m.get("face_ids") is None else np.ascontiguousarray(m["face_ids"], np.int32).reshape(-1)
+        if ids is not None and f is not None and len(ids) != len(f):
+            raise ValueError("debug_instance_records: one face id per face")
+        keep += [v, f, ids]
+        ms[k].vertices = None if v is None else v.ctypes.data
+        ms[k].faces = None if f is None else f.ctypes.data
+        ms[k].faceIds = None if ids is None else ids.ctypes.data
+        ms[k].vertexCount = 0 if v is None else len(v)
+        ms[k].faceCount = 0 if f is None else len(f)
+        ms[k].maxFaceId = int(m.get("max_face_id", 0))
+        ms[k].flags = (1 if m.get("flip_facing") else 0) | (2 if m.get("double_sided") else 0)
+    js = (_DebugInstanceJob * max(len(jobs), 1))()
+    for k, j in enumerate(jobs):
+        js[k].mesh, js[k].instanceSlot, js[k].recordSlot, js[k].idBase = int(j["mesh"]), int(j["instance_slot"]), int(j["record_slot"]), int(j["id_base"])
+        js[k].transform = (C.c_float * 16)(*np.ascontiguousarray(j["xform"], np.float32).reshape(16).tolist())
+    fn = L.giCDebugInstanceRecordsHost if host_only else L.giCDebugInstanceRecords
+    n = fn(C.addressof(ms) if len(meshes) else None, len(meshes), C.addressof(js) if len(jobs) else None, len(jobs))
+    del keep
+    if n < 0:
+        raise GiError("giCDebugInstanceRecords failed: " + L.giCGetLastError().decode())
     return int(n)
 
 
@@ -554,6 +604,15 @@ class Scene:
         if self.L.giCDebugSceneTlasTopologyUpdateCount(self.handle, C.byref(n)) != GI_C_OK:
             raise GiError("giCDebugSceneTlasTopologyUpdateCount failed")
         return int(n.value)
+
+    def tlas_instance_update_stats(self) -> dict:
+        """giCDebugSceneTlasInstanceUpdateStats: instancer edits applied in place on the two-level layout (OPTION_TLAS_INSTANCES).  Returns {"syncs",
+        "appended", "reused" (of the appended instances, how many went into the storage slots retired ones left), "retired"}.  Such a sync counts once in
+        tlas_topology_update_count(), and neither in update_counts() nor in instance_update_count()."""
+        out = (C.c_uint64 * 4)()
+        if self.L.giCDebugSceneTlasInstanceUpdateStats(self.handle, out) != GI_C_OK:
+            raise GiError("giCDebugSceneTlasInstanceUpdateStats failed")
+        return {"syncs": int(out[0]), "appended": int(out[1]), "reused": int(out[2]), "retired": int(out[3])}
 
     def flat_id_check(self, device: int = 0) -> "FlatIdCheck":
         """giCDebugSceneFlatIdCheck: the flat records, the id table and the per-instance records resident on a device -- the ids of visible records are a

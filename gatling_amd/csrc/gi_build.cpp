@@ -8,6 +8,7 @@
 #include "gi_pack.h"
 #include "gi_vispatch.h"
 #include "gi_append.h"
+#include "gi_instances.h"
 
 #include <random>
 #include <unordered_map>
@@ -324,12 +325,19 @@ static BlasTri makeBlasTri(const GiCVertex* vertices, const GiCFace* faces, uint
   return bt;
 }
 
+// ... and where the slot is free (MeshBuild::freeSlots: an instancer edit in place of the two-level layout retired its instance)
+template <class MB>
+static void markFreeSlots(const std::vector<MB>& meshBuilds, std::vector<uint8_t>& hidden)
+{
+  for (const MB& mb : meshBuilds) for (const auto& fs : mb.freeSlots) if (fs.inst < hidden.size()) hidden[fs.inst] = 1;
+}
 // one byte per flattened instance: 1 where its mesh is hidden (MeshBuild::hidden: visibility updates in place)
 template <class MB>
 static std::vector<uint8_t> hiddenOfInstances(const std::vector<MB>& meshBuilds, size_t instanceCount)
 {
   std::vector<uint8_t> hidden(instanceCount, 0);
   for (const MB& mb : meshBuilds) if (mb.hidden) for (const uint32_t inst : mb.inst) if (inst < instanceCount) hidden[inst] = 1;
+  markFreeSlots(meshBuilds, hidden); // (the slots of retired instances: hidden until a grow of their mesh takes them, updateInstancesTwoLevel)
   return hidden;
 }
 
@@ -1294,6 +1302,7 @@ static int updateVisibilityTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Up
   // --- the TLAS over the boxes of the instances that stay visible.  Nothing changes (a hidden mesh hidden again): nothing is built
   std::vector<uint8_t> hiddenAfter(instanceCount, 0);
   for (const MeshBuild& mb : H.meshBuilds) if (plan.hide[mb.meshIdx]) for (const uint32_t inst : mb.inst) if (inst < instanceCount) hiddenAfter[inst] = 1;
+  markFreeSlots(H.meshBuilds, hiddenAfter);
   Bvh8 tlas; std::vector<uint32_t> tlasItems; double tlasMs = 0.0;
   if (launch) {
     std::vector<float> masked(T.instBoxes);
@@ -2610,6 +2619,332 @@ static int updateVerticesTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Upda
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Instancer edits on the two-level layout (opt-in: GI_C_SCENE_OPTION_TLAS_INSTANCES / GATLING_OPTIONS=tlas_instances=1, read with topology, instance and
+// two-level topology updates wanted, on a scene built without the flat tree).  Instance ids or counts of built meshes changed (GiCMesh::instEdited): the
+// delegate's answer to every DirtyInstancer / DirtyInstanceIndex sync.  The BLAS of a built mesh is resident and shared by its instances, so one more
+// instance costs one InstanceRec, one InstTrav, one box in the TLAS and nf flat records.  updateTopologyTwoLevel runs this in front of its other work, with
+// the semantics instance updates have on the flat layouts (above instanceUpdatesWanted):
+//   ids:     InstanceRec::instanceId of the kept instances whose id changed is set and those records are re-sent; equal ids send nothing.
+//   moves:   a kept instance whose transform differs from the resident record is marked in GiCMesh::instDirty and DIRTY_XFORM is raised:
+//            updateTransformsTwoLevel applies it behind this update.  Without GI_C_SCENE_OPTION_TLAS_UPDATES wanted a sync with a move declines.
+//   shrink:  the instances [new, old) retire as the instances of a hidden mesh do -- VIS_HIDE | VIS_HIDDEN_AFTER in their VisPatch: both edges zeroed, no
+//            id-table word; masked out of the TLAS --, the kept instances of the meshes behind are renumbered by the plan (idDelta; k_patch_visibility2 and
+//            k_patch_inst_trav), and their SLOTS -- InstanceRec / InstTrav index and nf flat records -- go on the mesh's free list (MeshBuild::freeSlots).
+//            They count as retired triangles in updateTopologyTwoLevel's retired > live rule until they are reused.
+//   grow:    the instances [old, new) take free slots of the SAME mesh first, lowest index first -- never one retired in this very sync --, then the ends of
+//            the arrays (DeviceBuffer::grow).  Per new instance the host makes and sends the InstanceRec, the InstTrav (blasRoot and slack of a live sibling,
+//            triBase = the mesh's new id base + instance-in-mesh x nf) and one 32-byte job; per mesh that grows the per-FACE faceIdAov table once.  The world
+//            boxes and statuses come from k_inst_bounds / k_inst_finish over the RESIDENT BLAS triangles (instanceBoundsOnPrimary, scratch outputs only)
+//            before anything resident changes; a set status declines.  The TLAS is built again over all boxes, hidden and free slots masked, and held to
+//            the 16-entry stack rule.  k_instance_records (gi_instances.hip) makes the flat records, face-id words and id-table words of all new instances of
+//            all meshes in ONE launch: an instancer that goes up and down reuses its slots instead of leaving a retired range behind per frame.
+//   scene data: a mesh whose material reads primvars gets the MeshRec / scene-data tables made again (with a material edit due updateMaterials makes them).
+// MeshBuild::inst / instTri name the InstanceRec and the first flat record of every live instance: a mesh's records are no longer one run.  The paths of
+// options 16 - 18 and 20 address records through TriRec::instance and MeshBuild::inst alone; everything that masks hidden instances masks free slots too
+// (hiddenOfInstances, markFreeSlots, retiredRangesOf).  Host copies: H.instances, T.instTrav, T.instBoxes and the TLAS are brought up to date; the flat
+// records, face ids and id table where the host still holds them are written by the kernels' own host forms (vis2_patch_record, instanceRecordsHost), and stay
+// dropped where an edit in place dropped them.
+// Every decision comes before the first resident write.  Declines (applied = false, not an error, one line under GATLING_BUILD_TIMING; the caller rebuilds):
+// what updateTopologyTwoLevel declines for on the scene as it is, a new count of 0, a mesh hidden by the visibility path, a built mesh without an instance
+// (it has no BLAS), an unusable transform of a new instance, a move without option 16, a set status, the depth rule, 2^28 flat records, fewer than
+// kIncrementalMinTris visible triangles, more retired than live triangles, out of device memory.
+// ---------------------------------------------------------------------------------------------------------------
+bool tlasInstancesWanted(const GiCScene* s)
+{
+  if (!instanceUpdatesWanted(s) || !tlasTopologyWanted(s)) return false;
+  const long o = optionValue("tlas_instances", -1);
+  return o >= 0 ? o == 1 : s->optTlasInstances == 1;
+}
+
+static int updateInstancesTwoLevel(GiCScene* s, SceneHost& H, bool& applied, UpdateCost& cost)
+{
+  TwoLevelHost& T = H.two;
+  const char* const what = "instance update (two-level)";
+  const bool timing = getenv("GATLING_BUILD_TIMING") != nullptr;
+  auto decline = [&](const char* why) { if (timing) fprintf(stderr, "[gatling_gi] %s: %s; the scene is rebuilt\n", what, why); return GI_C_OK; };
+  const uint32_t oldInstances = (uint32_t)H.instances.size(), oldTris = s->triCount, shadeCount = (uint32_t)H.triShade.size(), meshCount = (uint32_t)H.meshBuilds.size();
+  if (s->stats.inactiveTriangleCount != 0u) return decline("the scene was built with inactive triangles");
+  if (H.deviceBuilt || H.partitioned || !H.treeless || !H.shadePacked || H.reordered) return decline("the scene is not a two-level scene without the flat tree");
+  if (T.instTrav.size() != oldInstances || T.instBoxes.size() != 6u * (size_t)oldInstances || T.meshBlasTri.size() != meshCount || H.meshRecs.size() != meshCount)
+    return decline("the host copy is not the built scene's"); // (cannot happen)
+  for (const MeshBuild& mb : H.meshBuilds)
+    if (mb.m->builtInstances != mb.instCount || mb.inst.size() != mb.instCount || mb.instTri.size() != mb.instCount || mb.meshIdx != (uint32_t)(&mb - H.meshBuilds.data()))
+      return decline("a built mesh with another instance count"); // (cannot happen)
+  const double t0 = nowMs();
+  // --- the edits: which meshes, what they add and retire; ids and moves of the kept instances (planned: nothing is written yet)
+  struct InstEdit { uint32_t b, oldCount, newCount, reuse; };
+  struct IdEdit { uint32_t rec; int32_t id; };
+  struct Move { uint32_t b, ii; };
+  std::vector<InstEdit> edits; std::vector<IdEdit> idEdits; std::vector<Move> moves;
+  std::vector<uint32_t> newCountOf(meshCount);
+  uint64_t grownInst = 0, shrunkInst = 0, reusedInst = 0, grownTris = 0, shrunkTris = 0, reusedTris = 0; bool sceneDataStale = false;
+  for (uint32_t b = 0; b < meshCount; b++) {
+    const MeshBuild& mb = H.meshBuilds[b];
+    newCountOf[b] = mb.instCount;
+    if (!mb.m->instEdited || mb.m->retired) continue;
+    const size_t newCount = mb.m->instanceTransforms.size() / 16;
+    const uint64_t nf = mb.m->faces.size();
+    if (newCount == 0u) return decline("a new count of 0");
+    if (newCount >= 0xffffffffu || nf == 0u || nf >= ((uint64_t)1 << 26)) return decline("an instance count or face count beyond the layout's"); // (cannot happen)
+    if (mb.hidden) return decline("an instancer edit of a mesh hidden by the visibility path");
+    if (mb.instCount == 0u) return decline("a built mesh without an instance has no BLAS");
+    InstEdit e{b, mb.instCount, (uint32_t)newCount, 0u};
+    if (e.newCount > e.oldCount) {
+      e.reuse = (uint32_t)std::min<size_t>(e.newCount - e.oldCount, mb.freeSlots.size());
+      grownInst += e.newCount - e.oldCount; grownTris += (e.newCount - e.oldCount) * nf; reusedInst += e.reuse; reusedTris += e.reuse * nf;
+    } else { shrunkInst += e.oldCount - e.newCount; shrunkTris += (e.oldCount - e.newCount) * nf; }
+    newCountOf[b] = e.newCount;
+    edits.push_back(e);
+    if (mb.m->material) for (uint32_t slot = 0; slot < TEX_SLOT_COUNT; slot++) if (!mb.m->material->primvarInput[slot].empty()) sceneDataStale = true;
+    const uint32_t kept = std::min(e.oldCount, e.newCount);
+    for (uint32_t ii = 0; ii < kept; ii++) {
+      if (mb.inst[ii] >= oldInstances) return decline("the host copy is not the built scene's"); // (cannot happen)
+      const InstanceRec& resident = H.instances[mb.inst[ii]];
+      const InstanceRec want = makeInstanceRec(mb.m, mb.meshIdx, ii);
+      if (want.instanceId != resident.instanceId) idEdits.push_back(IdEdit{mb.inst[ii], want.instanceId});
+      if (memcmp(want.o2w, resident.o2w, sizeof(want.o2w)) != 0) moves.push_back(Move{b, ii});
+    }
+  }
+  if (edits.empty()) { applied = true; return GI_C_OK; } // (the edited meshes are retired: updateTopologyTwoLevel takes them out)
+  if (!moves.empty() && !tlasUpdatesWanted(s)) return decline("a kept instance moved and transform updates of the two-level layout are not wanted");
+  const bool countsChange = grownInst != 0u || shrunkInst != 0u;
+  const uint64_t appendedInst = grownInst - reusedInst, appendedTris = grownTris - reusedTris;
+  // --- what the scene holds after the edit
+  {
+    uint64_t live = 0, retired = 0, visible = 0;
+    for (const MeshBuild& mb : H.meshBuilds) {
+      const uint64_t n = (uint64_t)mb.instCount * mb.m->faces.size(), gone = (uint64_t)mb.retiredInst * mb.m->faces.size();
+      if (mb.m->retired) retired += n + gone; else { live += n; retired += gone; if (!mb.hidden) visible += n; }
+    }
+    live += grownTris; live -= shrunkTris; visible += grownTris; visible -= shrunkTris; retired += shrunkTris; retired -= reusedTris;
+    if (visible < kIncrementalMinTris) return decline("fewer than 4096 visible triangles after the edit");
+    if (retired > live) return decline("retired triangles outnumber live ones");
+  }
+  if ((uint64_t)oldTris + appendedTris >= ((uint64_t)1 << 28)) return decline("2^28 or more flat records after the append");
+  if ((uint64_t)oldInstances + appendedInst >= 0xffffffffull) return decline("the arrays outgrow 32-bit indices");
+  const uint32_t newInstances = oldInstances + (uint32_t)appendedInst, newTris = oldTris + (uint32_t)appendedTris;
+  // --- the ids after the edit, in the order a fresh build meets the meshes (a hidden mesh keeps the ids it has; a mesh destroyed in this very sync is still
+  // part of the scene here: updateTopologyTwoLevel retires it behind this update) ...
+  std::vector<uint32_t> newBase(meshCount, 0u);
+  uint64_t visibleTris = 0;
+  for (const MeshBuild& mb : H.meshBuilds) {
+    newBase[mb.meshIdx] = mb.hidden ? mb.idBase : (uint32_t)visibleTris;
+    if (!mb.hidden) visibleTris += (uint64_t)newCountOf[mb.meshIdx] * mb.m->faces.size();
+  }
+  if (visibleTris > newTris) return decline("the host copy is not the built scene's"); // (cannot happen: the id table has one word per resident record)
+  // ... and the table of the device pass over what is resident: kept instances move with their mesh, retiring ones are hidden for good
+  std::vector<VisPatch> patch(oldInstances, VisPatch{0, VIS_KEEP});
+  std::vector<uint8_t> hiddenAfter(newInstances, 0);
+  bool launchPatch = false, renumbered = false;
+  for (const MeshBuild& mb : H.meshBuilds) {
+    const int32_t delta = (int32_t)(newBase[mb.meshIdx] - mb.idBase);
+    const uint32_t kept = std::min(mb.instCount, newCountOf[mb.meshIdx]);
+    if (mb.hidden) for (const uint32_t inst : mb.inst) hiddenAfter[inst] = 1;
+    if (delta != 0) { launchPatch = renumbered = true; for (uint32_t ii = 0; ii < kept; ii++) patch[mb.inst[ii]].idDelta = delta; }
+    for (uint32_t ii = kept; ii < mb.instCount; ii++) { patch[mb.inst[ii]] = VisPatch{0, VIS_HIDE}; hiddenAfter[mb.inst[ii]] = 1; launchPatch = true; }
+  }
+  // --- the new instances: their slots, records and jobs
+  struct NewInst { uint32_t b, ii, slot, tri; InstanceRec rec; };
+  std::vector<NewInst> fresh; fresh.reserve(grownInst);
+  std::vector<InstanceJob> jobs; jobs.reserve(grownInst);
+  std::vector<InstBoundsJob> boundsJobs; boundsJobs.reserve(grownInst);
+  std::vector<int32_t> faceIdAll;
+  uint32_t chunksPerJob = 0;
+  {
+    uint32_t nextInst = oldInstances, nextTri = oldTris;
+    for (const InstEdit& e : edits) {
+      if (e.newCount <= e.oldCount) continue;
+      const MeshBuild& mb = H.meshBuilds[e.b];
+      const uint32_t nf = (uint32_t)mb.m->faces.size(), blasFirst = T.meshBlasTri[mb.meshIdx];
+      if (mb.faceIdAov.size() != nf || (size_t)blasFirst + nf > T.blasTris.size()) return decline("the host copy is not the built scene's"); // (cannot happen)
+      const uint32_t faceIdFirst = (uint32_t)faceIdAll.size();
+      faceIdAll.insert(faceIdAll.end(), mb.faceIdAov.begin(), mb.faceIdAov.end());
+      for (uint32_t ii = e.oldCount; ii < e.newCount; ii++) {
+        NewInst ni{}; ni.b = e.b; ni.ii = ii;
+        const uint32_t k = ii - e.oldCount;
+        if (k < e.reuse) { ni.slot = mb.freeSlots[k].inst; ni.tri = mb.freeSlots[k].tri; }
+        else { ni.slot = nextInst++; ni.tri = nextTri; nextTri += nf; }
+        ni.rec = makeInstanceRec(mb.m, mb.meshIdx, ii);
+        if (!usableInstance(ni.rec)) return decline("a new instance has a transform that is not usable");
+        if (ni.slot >= newInstances || (uint64_t)ni.tri + nf > newTris) return decline("the host copy is not the built scene's"); // (cannot happen)
+        InstanceJob j{}; j.instance = ni.slot; j.triFirst = ni.tri; j.idBase = newBase[mb.meshIdx] + ii * nf; j.shadeBase = mb.shadeBase; j.faceCount = nf; j.matFlags = mb.matFlags;
+        j.faceIdFirst = faceIdFirst;
+        InstBoundsJob bj{}; memcpy(bj.o2w, ni.rec.o2w, sizeof(bj.o2w)); bj.firstTri = blasFirst; bj.faceCount = nf; bj.instance = ni.slot;
+        fresh.push_back(ni); jobs.push_back(j); boundsJobs.push_back(bj);
+        hiddenAfter[ni.slot] = 0;
+      }
+      chunksPerJob = std::max(chunksPerJob, instBoundsChunks(nf));
+    }
+  }
+  // (the free slots that stay free; those of this sync's retiring instances were marked above)
+  for (uint32_t b = 0; b < meshCount; b++) {
+    const MeshBuild& mb = H.meshBuilds[b];
+    uint32_t taken = 0;
+    for (const InstEdit& e : edits) if (e.b == b) taken = e.reuse;
+    for (size_t k = taken; k < mb.freeSlots.size(); k++) hiddenAfter[mb.freeSlots[k].inst] = 1;
+  }
+  InstanceJobSizes Z{}; Z.jobCount = (uint32_t)jobs.size(); Z.triCount = newTris; Z.instanceCount = newInstances; Z.shadeCount = shadeCount; Z.flatCount = newTris;
+  Z.faceIdCount = (uint32_t)faceIdAll.size(); Z.wgCount = instanceJobsNumber(jobs.data(), Z.jobCount);
+  if (!jobs.empty() && (Z.wgCount == 0u || !instanceJobsOk(jobs.data(), Z))) return decline("a new instance's records outside their arrays"); // (cannot happen)
+  if ((uint64_t)boundsJobs.size() * chunksPerJob >= (1ull << 31)) return decline("more bounds workgroups than a launch takes");
+  // --- primary device, scratch only: padded world boxes and statuses of the new instances over the resident BLAS triangles
+  std::vector<uint32_t> result;
+  bool outOfMemory = false;
+  const double tA = nowMs();
+  if (!boundsJobs.empty()) {
+    const int rcB = instanceBoundsOnPrimary(s, boundsJobs, chunksPerJob, nullptr, result, outOfMemory, what);
+    if (rcB == DEVICE_BUILD_FALLBACK && outOfMemory) return decline("out of device memory");
+    if (rcB != GI_C_OK) return GI_C_ERROR;
+  }
+  const double boundsMs = nowMs() - tA;
+  for (size_t k = 0; k < boundsJobs.size(); k++)
+    if (result[7u * k + 6u] != 0u) return decline("a new instance carries triangles that leave the usable coordinate range in world space");
+  // --- the TLAS over all boxes, hidden instances and free slots masked; the depth rule (the BLASes do not change)
+  std::vector<float> boxes; Bvh8 tlas; std::vector<uint32_t> tlasItems; double tlasMs = 0.0;
+  if (countsChange) {
+    boxes = T.instBoxes; boxes.resize(6u * (size_t)newInstances, 0.0f);
+    for (size_t k = 0; k < boundsJobs.size(); k++) memcpy(&boxes[6u * (size_t)boundsJobs[k].instance], &result[7u * k], 24);
+    std::vector<float> masked(boxes);
+    tlasMaskHiddenBoxes(masked.data(), hiddenAfter.data(), newInstances);
+    const double tt0 = nowMs();
+    buildBvh8Boxes(masked.data(), newInstances, tlas, tlasItems);
+    tlasMs = nowMs() - tt0;
+    if (2u * tlas.maxDepth + T.blasDepth + 1u > 16u) return decline("the new TLAS is too deep for the 16-entry stack");
+  }
+  // --- the records after the edit, staged: ids, the renumbered id bases, the new instances
+  std::vector<InstanceRec> instances(H.instances); instances.resize(newInstances, InstanceRec{});
+  std::vector<InstTrav> instTrav(T.instTrav); instTrav.resize(newInstances, InstTrav{});
+  for (const IdEdit& e : idEdits) instances[e.rec].instanceId = e.id;
+  if (renumbered) patchInstTravHost(instTrav.data(), oldInstances, patch.data());
+  for (const NewInst& ni : fresh) {
+    const MeshBuild& mb = H.meshBuilds[ni.b];
+    const InstTrav& sibling = T.instTrav[mb.inst[0]]; // (the mesh's constants: its resident BLAS, the slack of its current points, the last material update's word)
+    instances[ni.slot] = ni.rec;
+    instTrav[ni.slot] = tlasMakeInstTrav(ni.rec, sibling.blasRoot, newBase[mb.meshIdx] + ni.ii * (uint32_t)mb.m->faces.size(), sibling.matFlags, sibling.slack);
+  }
+  for (uint32_t i = 0; i < oldInstances; i++) if (hiddenAfter[i]) patch[i].action |= VIS_HIDDEN_AFTER;
+  // the tables of a mesh whose material reads primvars are sized from its instance count and ids (with a material edit due updateMaterials makes them anew)
+  std::vector<MeshRec> meshRecs; std::vector<float> sceneData;
+  if (sceneDataStale && !(s->dirty & DIRTY_MATERIALS)) for (const MeshBuild& mb : H.meshBuilds) appendBuiltMeshSceneData(mb, meshRecs, sceneData);
+  else sceneDataStale = false;
+  const double t1 = nowMs();
+  // --- every device of the scene, on its own stream: the arrays grown and the temporaries allocated before anything resident changes
+  double recordsKernelMs = 0.0;
+  const size_t bytesSent = (launchPatch ? patch.size() * sizeof(VisPatch) : 0u) + idEdits.size() * sizeof(InstanceRec) +
+      fresh.size() * (sizeof(InstanceRec) + sizeof(InstTrav) + sizeof(InstanceJob)) + faceIdAll.size() * 4u + tlas.nodes.size() * sizeof(Node8) + tlasItems.size() * 4u +
+      meshRecs.size() * sizeof(MeshRec) + sceneData.size() * sizeof(float);
+  const bool anythingToSend = countsChange || !idEdits.empty() || sceneDataStale;
+  const int rcDev = onSceneDevices(s, anythingToSend ? residentDeviceCount(s) : 0u, [&](SceneDevice& D, hipStream_t st) -> int {
+    if (D.dTris.count < oldTris || D.dTriFaceId.count < oldTris || D.dFlatOfOrig.count < oldTris || D.dInstances.count < oldInstances || D.dInstTrav.count < oldInstances ||
+        D.dTriShade.count < shadeCount) { setError("internal: the device holds less than the scene"); return GI_C_ERROR; }
+    std::vector<void*> old;
+    DeviceBuffer<VisPatch> dPatch; DeviceBuffer<InstanceJob> dJobs; DeviceBuffer<int32_t> dFaceIds;
+    auto releaseAll = [&] { dPatch.release(); dJobs.release(); dFaceIds.release(); for (void* p : old) (void)hipFree(p); old.clear(); };
+    int r = launchPatch ? dPatch.alloc(patch.size()) : GI_C_OK;
+    if (r == GI_C_OK && !jobs.empty()) { r = dJobs.alloc(jobs.size()); if (r == GI_C_OK) r = dFaceIds.alloc(faceIdAll.size()); }
+    if (r == GI_C_OK) r = D.dInstances.grow(newInstances, st, old);
+    if (r == GI_C_OK) r = D.dInstTrav.grow(newInstances, st, old);
+    if (r == GI_C_OK) r = D.dTris.grow(newTris, st, old);
+    if (r == GI_C_OK) r = D.dTriFaceId.grow(newTris, st, old);
+    if (r == GI_C_OK) r = D.dFlatOfOrig.grow(newTris, st, old);
+    if (r != GI_C_OK) { // (the copies out of the old blocks must finish before they are freed)
+      (void)hipStreamSynchronize(st); releaseAll();
+      if (r == GI_C_OUT_OF_MEMORY_INTERNAL) { outOfMemory = true; return DEVICE_BUILD_FALLBACK; }
+      return GI_C_ERROR;
+    }
+    auto copy = [&](void* dst, const void* src, size_t bytes) {
+      if (r == GI_C_OK && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) != hipSuccess) { setError("instance update (two-level): copy failed"); r = GI_C_ERROR; } };
+    // the retire and the renumbering: ids, edges, the id table and the instances' id bases, over what was resident before
+    if (launchPatch) {
+      copy(dPatch.ptr, patch.data(), patch.size() * sizeof(VisPatch));
+      if (r == GI_C_OK) {
+        launchPatchVisibility2(st, D.dTris.ptr, oldTris, D.dInstances.ptr, oldInstances, dPatch.ptr, D.dTriShade.ptr, shadeCount, D.dFlatOfOrig.ptr, newTris);
+        if (renumbered) launchPatchInstTrav(st, D.dInstTrav.ptr, oldInstances, dPatch.ptr);
+      }
+    }
+    // what the host made per instance and per face ...
+    for (const IdEdit& e : idEdits) copy(D.dInstances.ptr + e.rec, &instances[e.rec], sizeof(InstanceRec));
+    for (const NewInst& ni : fresh) { copy(D.dInstances.ptr + ni.slot, &instances[ni.slot], sizeof(InstanceRec)); copy(D.dInstTrav.ptr + ni.slot, &instTrav[ni.slot], sizeof(InstTrav)); }
+    copy(dJobs.ptr, jobs.data(), jobs.size() * sizeof(InstanceJob)); copy(dFaceIds.ptr, faceIdAll.data(), faceIdAll.size() * 4u);
+    if (r == GI_C_OK && countsChange && (D.dTlasNodes.upload(tlas.nodes, st) || D.dTlasItems.upload(tlasItems, st))) r = GI_C_ERROR;
+    if (r == GI_C_OK && sceneDataStale && (D.dMeshes.upload(meshRecs, st) || D.dSceneData.upload(sceneData, st))) r = GI_C_ERROR;
+    // ... and everything per flattened triangle of all new instances, made where it lives in one launch (gi_instances.hip), behind those copies on the stream
+    double tk = 0.0;
+    if (r == GI_C_OK && timing && D.slot == 0u) { if (hipStreamSynchronize(st) != hipSuccess) r = GI_C_ERROR; tk = nowMs(); }
+    if (r == GI_C_OK && !jobs.empty() &&
+        !launchInstanceRecords(st, jobs.data(), dJobs.ptr, Z, D.dTris.ptr, D.dTriFaceId.ptr, D.dFlatOfOrig.ptr, D.dInstances.ptr, D.dTriShade.ptr, dFaceIds.ptr)) {
+      setError("internal: a new instance's records outside their arrays"); r = GI_C_ERROR; } // (cannot happen: asked above)
+    if (r == GI_C_OK && hipGetLastError() != hipSuccess) { setError("instance update (two-level): launch failed"); r = GI_C_ERROR; }
+    if (hipStreamSynchronize(st) != hipSuccess && r == GI_C_OK) { setError("instance update (two-level): device error"); r = GI_C_ERROR; }
+    if (timing && D.slot == 0u && r == GI_C_OK) recordsKernelMs = nowMs() - tk;
+    releaseAll(); // (before the render's memory plan reads free memory)
+    return r;
+  });
+  if (rcDev == DEVICE_BUILD_FALLBACK && outOfMemory) return decline("out of device memory");
+  if (rcDev != GI_C_OK) return GI_C_ERROR;
+  const double t2 = nowMs();
+  // --- the host copies behind the committed edit: the flat records, face ids and id table where they are still held, by the kernels' own host forms
+  const bool hostRecords = !H.hostTreeDropped && H.bvh.tris.size() == oldTris && H.triFaceId.size() == oldTris && H.flatOfOrig.size() == oldTris;
+  if (countsChange) {
+    if (hostRecords) {
+      auto grown = [](auto& v, size_t n) { if (v.capacity() < n) v.reserve(n + n / 4u); v.resize(n); }; // (25 % slack, as updateTopologyTwoLevel)
+      grown(H.bvh.tris, newTris); grown(H.triFaceId, newTris); grown(H.flatOfOrig, newTris);
+      if (launchPatch) {
+        constexpr size_t CHUNK = 65536;
+        parallelOver(((size_t)oldTris + CHUNK - 1) / CHUNK, [&](size_t c) { // (one writer per word: the visible ids are a permutation)
+          for (size_t i = c * CHUNK; i < std::min((size_t)oldTris, (c + 1) * CHUNK); i++)
+            vis2_patch_record(H.bvh.tris.data(), (uint32_t)i, H.instances.data(), oldInstances, patch.data(), H.triShade.data(), shadeCount, H.flatOfOrig.data(), newTris);
+        });
+      }
+      constexpr uint32_t WGS = 1024;
+      parallelOver(((size_t)Z.wgCount + WGS - 1) / WGS, [&](size_t c) {
+        instanceRecordsHost(jobs.data(), Z, (uint32_t)c * WGS, std::min(Z.wgCount, ((uint32_t)c + 1u) * WGS), H.bvh.tris.data(), H.triFaceId.data(), H.flatOfOrig.data(),
+            instances.data(), H.triShade.data(), faceIdAll.data());
+      });
+    } else { // dropped by an edit in place before: they stay dropped, and the id table -- one word per resident record -- goes with them
+      std::vector<uint32_t>().swap(H.flatOfOrig);
+      if (!H.hostTreeDropped) { std::vector<TriRec>().swap(H.bvh.tris); std::vector<int32_t>().swap(H.triFaceId); H.hostTreeDropped = true; } // (cannot happen)
+    }
+  }
+  H.instances.swap(instances); T.instTrav.swap(instTrav);
+  if (countsChange) { T.instBoxes.swap(boxes); T.tlasNodes.swap(tlas.nodes); T.tlasItems.swap(tlasItems); T.tlasDepth = tlas.maxDepth; }
+  if (sceneDataStale) { H.meshRecs.swap(meshRecs); H.sceneData.swap(sceneData); }
+  // --- the MeshBuilds and the meshes: counts, slots, id bases; the moves go to updateTransformsTwoLevel
+  for (MeshBuild& mb : H.meshBuilds) mb.idBase = newBase[mb.meshIdx];
+  size_t nextFresh = 0;
+  for (const InstEdit& e : edits) {
+    MeshBuild& mb = H.meshBuilds[e.b];
+    GiCMesh* m = const_cast<GiCMesh*>(mb.m);
+    if (e.newCount < e.oldCount) {
+      for (uint32_t ii = e.newCount; ii < e.oldCount; ii++) mb.freeSlots.push_back(MeshBuild::FreeSlot{mb.inst[ii], mb.instTri[ii]});
+      std::sort(mb.freeSlots.begin(), mb.freeSlots.end(), [](const MeshBuild::FreeSlot& a, const MeshBuild::FreeSlot& c) { return a.inst < c.inst; });
+      mb.inst.resize(e.newCount); mb.instTri.resize(e.newCount);
+    } else if (e.newCount > e.oldCount) {
+      mb.freeSlots.erase(mb.freeSlots.begin(), mb.freeSlots.begin() + e.reuse);
+      for (uint32_t ii = e.oldCount; ii < e.newCount; ii++, nextFresh++) { mb.inst.push_back(fresh[nextFresh].slot); mb.instTri.push_back(fresh[nextFresh].tri); }
+    }
+    mb.retiredInst = (uint32_t)mb.freeSlots.size();
+    mb.instCount = e.newCount; m->builtInstances = e.newCount; m->instEdited = false;
+    const bool all = m->xformDirty && m->instDirty.empty(); // (a giCSetMeshTransform is due as well: every instance is re-bounded anyway)
+    if (!all) m->instDirty.resize(e.newCount, 0);
+    for (const Move& mv : moves) if (mv.b == e.b) { m->xformDirty = true; if (!all) m->instDirty[mv.ii] = 1; }
+    if (m->xformDirty) s->dirty |= DIRTY_XFORM; else m->instDirty.clear();
+  }
+  if (countsChange) { s->triCount = newTris; H.bvh.activeTris = newTris; setSceneBoundsFromInstances(s, H); }
+  const double t3 = nowMs();
+  cost.buildMs += tlasMs; cost.uploadMs += std::max(t3 - t0 - tlasMs, 0.0);
+  s->tlasInstanceCounts[0]++; s->tlasInstanceCounts[1] += grownInst; s->tlasInstanceCounts[2] += reusedInst; s->tlasInstanceCounts[3] += shrunkInst;
+  if (timing) fprintf(stderr, "[gatling_gi] instance update (two-level): %llu instance(s) retired, %llu appended (%llu into reused slots, %llu flat record(s) made on the "
+                              "device by %u workgroup(s) of one launch), %zu instance record(s) re-sent for their ids, %zu moved, %u resident triangle(s), %u instance "
+                              "slot(s), TLAS %zu node(s), host TLAS build %.2f ms, host rest %.2f ms, device %.2f ms (bounds kernels + read-back %.2f, commit %.2f of "
+                              "which the records kernel %.3f), %zu bytes sent per device\n", (unsigned long long)shrunkInst, (unsigned long long)grownInst,
+                      (unsigned long long)reusedInst, (unsigned long long)grownTris, Z.wgCount, idEdits.size(), moves.size(), s->triCount, newInstances, T.tlasNodes.size(),
+                      tlasMs, std::max((t1 - t0) - tlasMs - boundsMs + (t3 - t2), 0.0), boundsMs + (t2 - t1), boundsMs, t2 - t1, recordsKernelMs, bytesSent);
+  applied = true;
+  return GI_C_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Topology updates on the two-level layout (opt-in: GI_C_SCENE_OPTION_TLAS_TOPOLOGY / GATLING_OPTIONS=tlas_topology=1, read with topology updates wanted, on a
 // scene built without the flat tree: SceneHost::treeless).  Meshes were created or destroyed; nothing else asked for the rebuild.  With no flat tree to grow,
 //   retire:  a destroyed mesh of the built scene (GiCMesh::retired) becomes hidden for good through updateVisibilityTwoLevel's machinery -- planVisibility
@@ -2640,6 +2975,15 @@ static int updateTopologyTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Upda
   const char* const what = "topology update (two-level)";
   const bool timing = getenv("GATLING_BUILD_TIMING") != nullptr;
   auto decline = [&](const char* why) { if (timing) fprintf(stderr, "[gatling_gi] %s: %s; the scene is rebuilt\n", what, why); return GI_C_OK; };
+  // --- instancer edits of built meshes come first (GI_C_SCENE_OPTION_TLAS_INSTANCES: updateInstancesTwoLevel above): committed whole, or declined with nothing
+  // resident touched.  The meshes created and destroyed in the same sync are then applied to the scene it leaves; a decline below rebuilds, as ever
+  if (s->instancesDue) {
+    if (!tlasInstancesWanted(s)) return decline("an instance-count or instance-id edit of a built mesh is due");
+    bool applied = false;
+    if (updateInstancesTwoLevel(s, H, applied, cost) != GI_C_OK) return GI_C_ERROR;
+    if (!applied) return GI_C_OK;
+  }
+  const UpdateCost instancerCost = cost;
   const uint32_t oldInstances = (uint32_t)H.instances.size(), oldTris = s->triCount, shade0 = (uint32_t)H.triShade.size(), vert0 = (uint32_t)H.verts.size();
   const uint32_t blasNode0 = (uint32_t)T.blasNodes.size(), blasTri0 = (uint32_t)T.blasTris.size(), mesh0 = (uint32_t)H.meshBuilds.size();
   if (s->stats.inactiveTriangleCount != 0u) return decline("the scene was built with inactive triangles");
@@ -2647,7 +2991,6 @@ static int updateTopologyTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Upda
   if (T.instTrav.size() != oldInstances || T.instBoxes.size() != 6u * (size_t)oldInstances || T.meshBlasTri.size() != mesh0 || T.meshBlasNode.size() != mesh0 ||
       T.meshBlasLevels.size() != mesh0 || H.meshRecs.size() != mesh0) return decline("the host copy is not the built scene's"); // (cannot happen)
   for (const MeshBuild& mb : H.meshBuilds) if (mb.m->builtInstances != mb.instCount) return decline("a built mesh with another instance count"); // (cannot happen)
-  if (s->instancesDue) return decline("an instance-count or instance-id edit of a built mesh is due");
   const double t0 = nowMs();
   // --- the meshes to append: updateTopology's selection loop -- what a fresh build would hold and the resident scene does not, all behind every built mesh
   struct NewMesh { GiCMesh* m; uint32_t material, matFlags, vertexOffset, shadeBase, instFirst, instCount, nf, triFirst, idBase, blasNode, blasTri, faceFirst; float extent;
@@ -2671,8 +3014,8 @@ static int updateTopologyTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Upda
   // --- what the scene holds after the edit
   uint64_t live = appendedTris, retired = 0, visible = appendedTris; uint32_t retiring = 0;
   for (const MeshBuild& mb : H.meshBuilds) {
-    const uint64_t n = (uint64_t)mb.instCount * mb.m->faces.size();
-    if (mb.m->retired) { retired += n; if (!mb.hidden) retiring++; } else { live += n; if (!mb.hidden) visible += n; }
+    const uint64_t n = (uint64_t)mb.instCount * mb.m->faces.size(), gone = (uint64_t)mb.retiredInst * mb.m->faces.size(); // (gone: the free slots of retired instances)
+    if (mb.m->retired) { retired += n + gone; if (!mb.hidden) retiring++; } else { live += n; retired += gone; if (!mb.hidden) visible += n; }
   }
   if (visible < kIncrementalMinTris) return decline("fewer than 4096 visible triangles after the edit");
   if (retired > live) return decline("retired triangles outnumber live ones");
@@ -2767,6 +3110,7 @@ static int updateTopologyTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Upda
   for (size_t k = 0; k < jobs.size(); k++) memcpy(&boxes[6u * (size_t)jobs[k].instance], &result[7u * k], 24);
   std::vector<uint8_t> hiddenAfter(newInstances, 0);
   for (const MeshBuild& mb : H.meshBuilds) if (plan.hide[mb.meshIdx]) for (const uint32_t inst : mb.inst) if (inst < oldInstances) hiddenAfter[inst] = 1;
+  markFreeSlots(H.meshBuilds, hiddenAfter);
   Bvh8 tlas; std::vector<uint32_t> tlasItems;
   const double tt0 = nowMs();
   {
@@ -2908,7 +3252,7 @@ static int updateTopologyTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Upda
   if (!(s->dirty & DIRTY_MATERIALS)) deriveSceneClasses(s, H, false);
   setSceneBoundsFromInstances(s, H);
   const double t3 = nowMs();
-  cost.buildMs = tlasMs + blasMs; cost.uploadMs = std::max(t3 - t0 - cost.buildMs, 0.0);
+  cost.buildMs = instancerCost.buildMs + tlasMs + blasMs; cost.uploadMs = instancerCost.uploadMs + std::max(t3 - t0 - tlasMs - blasMs, 0.0);
   if (timing) fprintf(stderr, "[gatling_gi] topology update (two-level): %u mesh(es) retired, %zu appended (%llu face(s), %llu instance(s), %llu flat record(s) made on the "
                               "device), %llu live + %llu retired triangle(s), %u resident, TLAS %zu node(s), host TLAS build %.2f ms, host BLAS build %.2f ms, host rest "
                               "%.2f ms, device %.2f ms (bounds kernels + read-back %.2f, commit %.2f of which append kernels %.3f), %zu bytes sent per device\n",
@@ -2926,9 +3270,12 @@ struct RetiredRanges { std::vector<uint8_t> node, tri, inst; };
 static RetiredRanges retiredRangesOf(const SceneHost& H, const TwoLevelHost& layout, size_t nodeCount, size_t triCount)
 {
   RetiredRanges R;
+  auto begin = [&] { if (R.inst.empty()) { R.node.assign(nodeCount, 0); R.tri.assign(triCount, 0); R.inst.assign(H.instances.size(), 0); } };
+  // (the slots retired instances of a live mesh left, updateInstancesTwoLevel: their traversal records are stale until a grow takes them)
+  for (const MeshBuild& mb : H.meshBuilds) for (const MeshBuild::FreeSlot& fs : mb.freeSlots) { begin(); if (fs.inst < R.inst.size()) R.inst[fs.inst] = 1; }
   for (const MeshBuild& mb : H.meshBuilds) {
     if (!mb.m->retired || mb.instCount == 0u) continue;
-    if (R.inst.empty()) { R.node.assign(nodeCount, 0); R.tri.assign(triCount, 0); R.inst.assign(H.instances.size(), 0); }
+    begin();
     if (mb.meshIdx >= layout.meshBlasNode.size() || mb.meshIdx >= layout.meshBlasTri.size() || mb.meshIdx >= layout.meshBlasLevels.size()) continue;
     const std::vector<uint32_t>& lv = layout.meshBlasLevels[mb.meshIdx];
     const size_t n0 = layout.meshBlasNode[mb.meshIdx], t0 = layout.meshBlasTri[mb.meshIdx], nn = lv.empty() ? 0u : lv.back(), nf = mb.m->faces.size();
@@ -3413,6 +3760,112 @@ extern "C" int giCDebugAppendRecords(const GiCVertex* vertices, uint32_t vertexC
 extern "C" int giCDebugAppendRecordsHost(const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, const int32_t* faceIds, uint32_t maxFaceId,
     uint32_t flags, const float* xforms16, uint32_t xformCount, uint32_t vertexOffset, uint32_t shadeBase, uint32_t idBase, uint32_t matFlags)
 { return debugAppendRecords("giCDebugAppendRecordsHost", false, vertices, vertexCount, faces, faceCount, faceIds, maxFaceId, flags, xforms16, xformCount, vertexOffset, shadeBase, idBase, matFlags); }
+
+// giCDebugInstanceRecords / giCDebugInstanceRecordsHost: new instances of several meshes at arbitrary storage slots -- their flat records, face-id words and
+// id-table words made by k_instance_records in ONE launch (onDevice) or by its host form (gi_instances.h) on scratch arrays, against the scene build's own
+// code (flattenInstance as buildSceneTreeless leaves its records, faceIdAovOf, flatOfOrig[id] = position).  Every array starts as 0xa5 bytes on both sides: a
+// store outside the jobs' ranges is seen.  Returns the bytes that differ
+static int debugInstanceRecords(const char* name, bool onDevice, const GiCDebugInstanceMesh* meshes, uint32_t meshCount, const GiCDebugInstanceJob* jobsIn, uint32_t jobCount)
+{
+  if (onDevice && !g_ctx.initialized) { setError(std::string(name) + " before giCInitialize"); return -1; }
+  if (!meshes || !jobsIn || meshCount == 0u || jobCount == 0u || meshCount > (1u << 16) || jobCount > (1u << 20)) { setError(std::string(name) + ": bad arguments"); return -1; }
+  uint64_t faceTotal = 0;
+  for (uint32_t k = 0; k < meshCount; k++) {
+    const GiCDebugInstanceMesh& dm = meshes[k];
+    if (!dm.vertices || !dm.faces || dm.vertexCount == 0u || dm.faceCount == 0u || dm.faceCount >= (1u << 22) || dm.vertexCount >= (1u << 24)) { setError(std::string(name) + ": bad arguments"); return -1; }
+    for (uint32_t f = 0; f < dm.faceCount; f++) for (int c = 0; c < 3; c++) if (dm.faces[f].v_i[c] >= dm.vertexCount) { setError(std::string(name) + ": a face index outside the vertices"); return -1; }
+    faceTotal += dm.faceCount;
+  }
+  if (faceTotal >= (1u << 24)) { setError(std::string(name) + ": bad arguments"); return -1; }
+  try {
+    // --- the meshes, one behind the other in the per-face arrays, as meshes behind others in every array
+    struct Mesh { GiCMesh m; uint32_t vertexOffset, shadeBase, faceIdFirst, matFlags; std::vector<int32_t> faceIdAov; };
+    std::vector<Mesh> built(meshCount);
+    uint32_t vertexOffset = 3u, shadeCount = 5u, faceIdCount = 2u;
+    for (uint32_t k = 0; k < meshCount; k++) {
+      const GiCDebugInstanceMesh& dm = meshes[k];
+      Mesh& B = built[k];
+      B.m.scene = nullptr; B.m.id = 11 + (int32_t)k; B.m.flipFacing = (dm.flags & 1u) != 0u; B.m.doubleSided = (dm.flags & 2u) != 0u; B.m.maxFaceId = dm.maxFaceId;
+      B.m.vertices.assign(dm.vertices, dm.vertices + dm.vertexCount); B.m.faces.assign(dm.faces, dm.faces + dm.faceCount);
+      if (dm.faceIds) B.m.faceIds.assign(dm.faceIds, dm.faceIds + dm.faceCount);
+      B.vertexOffset = vertexOffset; B.shadeBase = shadeCount; B.faceIdFirst = faceIdCount; B.matFlags = (6u + k) | ((dm.flags & 3u) << 30);
+      B.faceIdAov = faceIdAovOf(&B.m);
+      vertexOffset += dm.vertexCount; shadeCount += dm.faceCount; faceIdCount += dm.faceCount;
+    }
+    // --- the jobs: ranges inside sane sizes, usable transforms, no slot named twice and no two ranges overlapping
+    uint32_t triCount = 0, flatCount = 0, instanceCount = 0;
+    for (uint32_t k = 0; k < jobCount; k++) {
+      const GiCDebugInstanceJob& dj = jobsIn[k];
+      if (dj.mesh >= meshCount || dj.instanceSlot >= (1u << 20) || dj.recordSlot >= (1u << 24) || dj.idBase >= (1u << 24)) { setError(std::string(name) + ": bad arguments"); return -1; }
+      const uint32_t nf = meshes[dj.mesh].faceCount;
+      triCount = std::max(triCount, dj.recordSlot + nf); flatCount = std::max(flatCount, dj.idBase + nf); instanceCount = std::max(instanceCount, dj.instanceSlot + 1u);
+    }
+    triCount += 5u; flatCount += 3u; instanceCount += 2u; // (untouched words behind the last range)
+    {
+      std::vector<uint8_t> recUsed(triCount, 0), idUsed(flatCount, 0), instUsed(instanceCount, 0);
+      for (uint32_t k = 0; k < jobCount; k++) {
+        const GiCDebugInstanceJob& dj = jobsIn[k];
+        const uint32_t nf = meshes[dj.mesh].faceCount;
+        bool overlap = instUsed[dj.instanceSlot] != 0; instUsed[dj.instanceSlot] = 1;
+        for (uint32_t f = 0; f < nf; f++) { overlap = overlap || recUsed[dj.recordSlot + f] || idUsed[dj.idBase + f]; recUsed[dj.recordSlot + f] = 1; idUsed[dj.idBase + f] = 1; }
+        if (overlap) { setError(std::string(name) + ": overlapping slots"); return -1; }
+      }
+    }
+    std::vector<InstanceRec> instances(instanceCount, InstanceRec{});
+    std::vector<InstanceJob> jobs(jobCount);
+    for (uint32_t k = 0; k < jobCount; k++) {
+      const GiCDebugInstanceJob& dj = jobsIn[k];
+      Mesh& B = built[dj.mesh];
+      B.m.instanceTransforms.assign(dj.transform, dj.transform + 16);
+      instances[dj.instanceSlot] = makeInstanceRec(&B.m, dj.mesh, 0);
+      instances[dj.instanceSlot].instanceId = (int32_t)k;
+      if (!usableInstance(instances[dj.instanceSlot])) { setError(std::string(name) + ": an instance transform is not usable"); return -1; }
+      InstanceJob& j = jobs[k];
+      j.instance = dj.instanceSlot; j.triFirst = dj.recordSlot; j.idBase = dj.idBase; j.shadeBase = B.shadeBase; j.faceCount = meshes[dj.mesh].faceCount; j.matFlags = B.matFlags;
+      j.faceIdFirst = B.faceIdFirst; j.wgFirst = 0u;
+    }
+    InstanceJobSizes Z{}; Z.jobCount = jobCount; Z.triCount = triCount; Z.instanceCount = instanceCount; Z.shadeCount = shadeCount; Z.flatCount = flatCount;
+    Z.faceIdCount = faceIdCount; Z.wgCount = instanceJobsNumber(jobs.data(), jobCount);
+    if (Z.wgCount == 0u || !instanceJobsOk(jobs.data(), Z)) { setError(std::string(name) + ": internal: ranges"); return -1; }
+    // --- the scene build's forms over arrays of 0xa5 bytes
+    auto filled = [](auto& v, size_t n) { v.resize(n); if (n) memset(static_cast<void*>(v.data()), 0xa5, n * sizeof(v[0])); };
+    std::vector<TriShade> shade(shadeCount, TriShade{}); std::vector<int32_t> faceIdTable(faceIdCount, 0);
+    for (const Mesh& B : built) for (uint32_t f = 0; f < (uint32_t)B.m.faces.size(); f++) {
+      shade[B.shadeBase + f] = packTriShade(B.m.vertices.data(), B.m.faces[f], B.vertexOffset); faceIdTable[B.faceIdFirst + f] = B.faceIdAov[f]; }
+    std::vector<TriRec> wantTris, gotTris; std::vector<int32_t> wantFaceId, gotFaceId; std::vector<uint32_t> wantFlat, gotFlat;
+    filled(wantTris, triCount); filled(gotTris, triCount); filled(wantFaceId, triCount); filled(gotFaceId, triCount); filled(wantFlat, flatCount); filled(gotFlat, flatCount);
+    for (uint32_t k = 0; k < jobCount; k++) {
+      const InstanceJob& j = jobs[k];
+      const Mesh& B = built[jobsIn[k].mesh];
+      flattenInstance(instances[j.instance], j.instance, &B.m, B.vertexOffset, B.matFlags, j.idBase, B.shadeBase, &wantTris[j.triFirst]);
+      for (uint32_t f = 0; f < j.faceCount; f++) { wantFaceId[j.triFirst + f] = B.faceIdAov[f]; wantFlat[j.idBase + f] = j.triFirst + f; }
+    }
+    if (!onDevice) {
+      instanceRecordsHost(jobs.data(), Z, 0u, Z.wgCount, gotTris.data(), gotFaceId.data(), gotFlat.data(), instances.data(), shade.data(), faceIdTable.data());
+    } else {
+      DeviceBuffer<TriShade> dShade; DeviceBuffer<TriRec> dTris; DeviceBuffer<int32_t> dFaceId, dFaceIdTable; DeviceBuffer<uint32_t> dFlat; DeviceBuffer<InstanceRec> dInstances;
+      DeviceBuffer<InstanceJob> dJobs;
+      hipStream_t st = g_ctx.stream;
+      bool ok = hipSetDevice(g_ctx.device) == hipSuccess && dShade.upload(shade, st) == GI_C_OK && dTris.upload(gotTris, st) == GI_C_OK && dFaceId.upload(gotFaceId, st) == GI_C_OK &&
+          dFlat.upload(gotFlat, st) == GI_C_OK && dFaceIdTable.upload(faceIdTable, st) == GI_C_OK && dInstances.upload(instances, st) == GI_C_OK && dJobs.upload(jobs, st) == GI_C_OK;
+      ok = ok && launchInstanceRecords(st, jobs.data(), dJobs.ptr, Z, dTris.ptr, dFaceId.ptr, dFlat.ptr, dInstances.ptr, dShade.ptr, dFaceIdTable.ptr);
+      ok = ok && hipGetLastError() == hipSuccess;
+      ok = ok && hipMemcpyAsync(gotTris.data(), dTris.ptr, gotTris.size() * sizeof(TriRec), hipMemcpyDeviceToHost, st) == hipSuccess &&
+          hipMemcpyAsync(gotFaceId.data(), dFaceId.ptr, gotFaceId.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st) == hipSuccess &&
+          hipMemcpyAsync(gotFlat.data(), dFlat.ptr, gotFlat.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st) == hipSuccess;
+      ok = hipStreamSynchronize(st) == hipSuccess && ok;
+      dShade.release(); dTris.release(); dFaceId.release(); dFaceIdTable.release(); dFlat.release(); dInstances.release(); dJobs.release();
+      if (!ok) { setError(std::string(name) + ": device error"); return -1; }
+    }
+    auto bytesDiffering = [](const void* x, const void* y, size_t n) { int d = 0; for (size_t i = 0; i < n; i++) d += ((const uint8_t*)x)[i] != ((const uint8_t*)y)[i]; return d; };
+    return bytesDiffering(gotTris.data(), wantTris.data(), gotTris.size() * sizeof(TriRec)) + bytesDiffering(gotFaceId.data(), wantFaceId.data(), gotFaceId.size() * sizeof(int32_t)) +
+        bytesDiffering(gotFlat.data(), wantFlat.data(), gotFlat.size() * sizeof(uint32_t));
+  } catch (const std::exception& e) { setError(std::string(name) + ": " + e.what()); return -1; }
+}
+extern "C" int giCDebugInstanceRecords(const GiCDebugInstanceMesh* meshes, uint32_t meshCount, const GiCDebugInstanceJob* jobs, uint32_t jobCount)
+{ return debugInstanceRecords("giCDebugInstanceRecords", true, meshes, meshCount, jobs, jobCount); }
+extern "C" int giCDebugInstanceRecordsHost(const GiCDebugInstanceMesh* meshes, uint32_t meshCount, const GiCDebugInstanceJob* jobs, uint32_t jobCount)
+{ return debugInstanceRecords("giCDebugInstanceRecordsHost", false, meshes, meshCount, jobs, jobCount); }
 
 // brings the device scene up to date with the host-side edits: incremental for DIRTY_BVH raised by vertex edits alone (opt-in: the tree refitted on the
 // device), by visibility toggles alone (opt-in: ids renumbered, the

@@ -324,6 +324,7 @@ int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value)
   if (option == GI_C_SCENE_OPTION_BLAS_UPDATES) { scene->optBlasUpdates = value == 1 ? 1 : 0; return GI_C_OK; } // (read only with option 12 wanted)
   if (option == GI_C_SCENE_OPTION_TLAS_VISIBILITY) { scene->optTlasVisibility = value == 1 ? 1 : 0; return GI_C_OK; } // (read only with option 11 wanted)
   // (read at the scene build, with the two-level layout wanted: the next build decides)
+  if (option == GI_C_SCENE_OPTION_TLAS_INSTANCES) { scene->optTlasInstances = value == 1 ? 1 : 0; return GI_C_OK; } // (read only with options 13, 15 and 20 wanted, on a scene built with option 19)
   if (option == GI_C_SCENE_OPTION_TLAS_TOPOLOGY) { scene->optTlasTopology = value == 1 ? 1 : 0; return GI_C_OK; } // (read only with option 13 wanted, on a scene built with option 19)
   if (option == GI_C_SCENE_OPTION_TLAS_ONLY) { scene->optTlasOnly = value == 1 ? 1 : 0; scene->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER; scene->rebuildDue = true; return GI_C_OK; }
   setError("unknown scene option"); return GI_C_ERROR;

@@ -630,6 +630,15 @@ extern "C" int giCDebugSceneTlasTopologyUpdateCount(const GiCScene* scene, uint6
   return GI_C_OK;
 }
 
+extern "C" int giCDebugSceneTlasInstanceUpdateStats(const GiCScene* scene, uint64_t* out)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!s || !out) { setError("giCDebugSceneTlasInstanceUpdateStats: bad arguments"); return GI_C_ERROR; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  for (int i = 0; i < 4; i++) out[i] = s->tlasInstanceCounts[i];
+  return GI_C_OK;
+}
+
 extern "C" int giCDebugSceneInstanceUpdateCount(const GiCScene* scene, uint64_t* out)
 {
   GiCScene* s = const_cast<GiCScene*>(scene);

@@ -320,7 +320,14 @@ struct MeshBuild { const GiCMesh* m; uint32_t vertexOffset, matFlags, instFirst,
     // the InstanceRec of every live instance, inst[instInMesh]: instFirst + instInMesh (and triangles at triFirst + instInMesh * faces) as the build leaves
     // them; an instance update (gi_build.cpp updateTopology) appends records at the end of the array and retires others, which stay resident (retiredInst)
     std::vector<uint32_t> inst; uint32_t retiredInst = 0;
-    void numberInstances() { inst.resize(instCount); for (uint32_t ii = 0; ii < instCount; ii++) inst[ii] = instFirst + ii; }
+    // a two-level scene without the flat tree under instancer edits in place (gi_build.cpp updateInstancesTwoLevel): the first flat record of every live
+    // instance, instTri[instInMesh] -- a mesh's records are no longer one run once an instance sits in a reused slot --, and the slots its retired instances
+    // left (InstanceRec / InstTrav index and first flat record, ascending by index; retiredInst counts them): out of the TLAS, edges zero, no id-table word,
+    // as the instances of a hidden mesh, until a later grow of the SAME mesh takes them
+    struct FreeSlot { uint32_t inst, tri; };
+    std::vector<uint32_t> instTri; std::vector<FreeSlot> freeSlots;
+    void numberInstances() { inst.resize(instCount); instTri.resize(instCount);
+        for (uint32_t ii = 0; ii < instCount; ii++) { inst[ii] = instFirst + ii; instTri[ii] = triFirst + ii * (uint32_t)m->faces.size(); } }
     // incremental visibility updates (gi_build.cpp updateVisibility): the mesh is part of the resident scene but hidden; the scene-order id of its first
     // triangle as the resident records hold it (triFirst until a mesh in front of it is hidden; triFirst stays the POSITION of a partitioned scene's ranges)
     bool hidden = false; uint32_t idBase = 0; };
@@ -446,6 +453,10 @@ struct GiCScene : SceneDevice {
   // GI_C_SCENE_OPTION_TLAS_TOPOLOGY: 1 = meshes are created and destroyed in a resident two-level scene that was built without the flat tree
   // (updateTopologyTwoLevel; read only with topology updates wanted)
   int32_t optTlasTopology = 0;
+  // GI_C_SCENE_OPTION_TLAS_INSTANCES: 1 = instance ids and counts of built meshes are edited in a resident two-level scene that was built without the flat
+  // tree (updateInstancesTwoLevel; read only with topology, instance and two-level topology updates wanted); giCDebugSceneTlasInstanceUpdateStats: syncs
+  // that applied such an edit, instances appended, of those into reused slots, instances retired
+  int32_t optTlasInstances = 0; uint64_t tlasInstanceCounts[4] = {0, 0, 0, 0};
   std::vector<GiCMesh*> retiredMeshes; // destroyed meshes the resident scene still refers to (GiCMesh::retired): freed by buildScene and with the scene
   ~GiCScene() { for (GiCMesh* m : retiredMeshes) delete m; }
 };
@@ -477,6 +488,7 @@ bool tlasOnlyWanted(const GiCScene* s);                      // GI_C_SCENE_OPTIO
 bool tlasVisibilityWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_TLAS_VISIBILITY / GATLING_OPTIONS=tlas_visibility (with visibility updates wanted)
 bool topologyUpdatesWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_TOPOLOGY_UPDATES / GATLING_OPTIONS=topology_updates
 bool tlasTopologyWanted(const GiCScene* s);                  // GI_C_SCENE_OPTION_TLAS_TOPOLOGY / GATLING_OPTIONS=tlas_topology (with topology updates wanted)
+bool tlasInstancesWanted(const GiCScene* s);                 // GI_C_SCENE_OPTION_TLAS_INSTANCES / GATLING_OPTIONS=tlas_instances (with options 13, 15 and 20 wanted)
 int syncSceneGeometry(GiCScene* s);                          // brings the device scene up to date with the host-side edits (incremental or full build)
 // dirty flags of a material-side edit: DIRTY_MATERIALS alone once the scene / the mesh is part of a built scene (the incremental path), else with DIRTY_BVH
 inline uint32_t materialEditFlags(bool built) { return DIRTY_MATERIALS | DIRTY_FRAMEBUFFER | (built ? 0u : (uint32_t)DIRTY_BVH); }

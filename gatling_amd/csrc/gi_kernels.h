@@ -155,6 +155,13 @@ bool launchAppendBlasTris(hipStream_t s, BlasTri* blasTris, uint32_t blasTriCoun
     const TriShade* triShade, uint32_t shadeCount, uint32_t shadeBase);
 bool launchAppendRecords(hipStream_t s, const AppendMesh& M, TriRec* tris, int32_t* triFaceId, uint32_t* flatOfOrig, const InstanceRec* instances,
     const TriShade* triShade, const int32_t* faceIdOfFace);
+// gi_instances.hip: the flat records, face-id words and id-table words of all new instances of built meshes of one sync, in one launch (gi_build.cpp
+// updateInstancesTwoLevel, GI_C_SCENE_OPTION_TLAS_INSTANCES; gi_instances.h has every per-item form, InstanceJob and InstanceJobSizes).  `hostJobs`: the table
+// `deviceJobs` holds, for the range check (instanceJobsOk): false, and nothing launched, for a job outside its arrays, 2^28 or more items, or a workgroup
+// prefix that is not the job sizes'.  The caller keeps the jobs' ranges disjoint
+struct InstanceJob; struct InstanceJobSizes;
+bool launchInstanceRecords(hipStream_t s, const InstanceJob* hostJobs, const InstanceJob* deviceJobs, const InstanceJobSizes& Z, TriRec* tris, int32_t* triFaceId,
+    uint32_t* flatOfOrig, const InstanceRec* instances, const TriShade* triShade, const int32_t* faceIdTable);
 void launchSpin(hipStream_t s, unsigned long long ns);           // test hook: occupies a stream for ~ns nanoseconds
 void launchDebugBsdf(hipStream_t s, const MaterialRec* mat, uint32_t shadeClass, uint32_t count, const float* in, float* out);
 void launchDebugSqrt(hipStream_t s, uint32_t first, unsigned long long count, unsigned long long* mismatches); // gi_sqrt against sqrtf over bit patterns

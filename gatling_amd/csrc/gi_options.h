@@ -76,6 +76,10 @@
 //   tlas_topology        -1        -1 = the scene option decides (GI_C_SCENE_OPTION_TLAS_TOPOLOGY), 0 / 1 = mesh creations and destructions on a two-level
 //                                  scene built without the flat tree rebuild it / are applied to the resident scene (gi_build.cpp updateTopologyTwoLevel; the
 //                                  per-triangle records are made on the device: gi_append.hip); read only with topology_updates wanted
+//   tlas_instances       -1        -1 = the scene option decides (GI_C_SCENE_OPTION_TLAS_INSTANCES), 0 / 1 = instance-count and instance-id edits of built
+//                                  meshes on a two-level scene built without the flat tree rebuild it / are applied to the resident scene (gi_build.cpp
+//                                  updateInstancesTwoLevel; the flat records of all new instances are made on the device in one launch: gi_instances.hip);
+//                                  read only with topology_updates, instance_updates and tlas_topology wanted
 //   phase_stats          0         counting builds: print k_path's phase split / k_trace_dyn's lane accounting
 #pragma once
 

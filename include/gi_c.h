@@ -384,7 +384,8 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * and giCDebugInstanceBounds, and for GI_C_SCENE_OPTION_BLAS_UPDATES, giCDebugSceneBlasUpdateCount, giCDebugSceneBlasCheck, giCDebugBlasRefit and
  * giCDebugBlasRefitHost, and for GI_C_SCENE_OPTION_TLAS_VISIBILITY, giCDebugSceneTlasVisibilityUpdateCount, giCDebugSceneFlatIdCheck and
  * giCDebugPatchVisibilityTwoLevel, and for GI_C_SCENE_OPTION_TLAS_ONLY and giCDebugSceneFlatTreeState, and for GI_C_SCENE_OPTION_TLAS_TOPOLOGY,
- * giCDebugSceneTlasTopologyUpdateCount, giCDebugAppendRecords and giCDebugAppendRecordsHost. */
+ * giCDebugSceneTlasTopologyUpdateCount, giCDebugAppendRecords and giCDebugAppendRecordsHost, and for GI_C_SCENE_OPTION_TLAS_INSTANCES,
+ * giCDebugSceneTlasInstanceUpdateStats, giCDebugInstanceRecords and giCDebugInstanceRecordsHost. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -658,9 +659,21 @@ int giCGetRenderStats(const GiCScene* scene, GiCRenderStats* out);
  * creation order; a new mesh has a vertex position that is not finite or beyond 1e18, an instance transform that is not finite or singular, or triangles
  * that leave the usable range in world space; the scene was built with inactive triangles; 2^26 unique BLAS triangles or 2^28 flat records would be
  * reached; the new TLAS would be too deep for the layout's 16-entry stack; a material index beyond 2^24; out of device memory; an instance count or id
- * edit of a built mesh is due (option 15 has no two-level form).  Material, transform, vertex and visibility edits due in the same render take the paths of
+ * edit of a built mesh is due and option 21 is not wanted.  Material, transform, vertex and visibility edits due in the same render take the paths of
  * options 16 - 18 behind this update.  GATLING_OPTIONS=tlas_topology=0|1 overrides the option (hdGatling sets no scene options).  DESIGN.md section 6. */
 #define GI_C_SCENE_OPTION_TLAS_TOPOLOGY 20
+/* [ext] Instancer edits -- giCSetMeshInstanceIds, giCSetMeshInstanceTransforms with another count -- on a mesh of a built two-level scene without the flat
+ * tree; read only with options 13 (topology updates), 15 (instance updates) and 20 (two-level topology) wanted, on a scene built with option 19: value 1 =
+ * the edit is applied to the resident scene by the next giCRender, with option 15's semantics.  Ids of kept instances are set in their records; a kept
+ * instance that moved goes down option 16's path behind this update (without option 16 the scene is rebuilt); the instances [new, old) of a mesh that shrinks
+ * retire -- out of the TLAS, their flat records made unhittable, the meshes behind renumbered by option 18's device pass -- and leave their storage slots on a
+ * free list of the mesh; the instances [old, new) of a mesh that grows take free slots of the same mesh first, lowest first, then the ends of the arrays:
+ * the host sends one instance record, one traversal record and one 32-byte job per new instance and builds the TLAS over all boxes; the flat records,
+ * face-id words and id-table words of all new instances of all meshes are made on the device in one launch (gi_instances.hip).  The mesh's BLAS is shared and
+ * not touched.  0 = off (default): such an edit rebuilds the scene, as before.  The image does not depend on the option.  The scene is rebuilt instead for
+ * whatever option 20 declines for, a new count of 0, a mesh hidden by the visibility path, an unusable transform of a new instance, a move without option 16,
+ * out of device memory.  GATLING_OPTIONS=tlas_instances=0|1 overrides the option (hdGatling sets no scene options).  DESIGN.md section 6. */
+#define GI_C_SCENE_OPTION_TLAS_INSTANCES 21
 int giCGetLookaheadStats(const GiCScene* scene, GiCLookaheadStats* out);
 int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value);
 /* [ext] closest hit of one ray through the device traversal kernel (parity tests of the BVH8 path).
@@ -763,7 +776,8 @@ int giCDebugSceneTlasUpdateCount(const GiCScene* scene, uint64_t* outCount);
  * records, BLAS nodes, BLAS triangles -- downloaded and compared with the arrays the scene build's own code makes anew from the scene's current meshes.
  * Returns the number of records that differ bytewise (0 after a build as after every update in place), <0 on error.  After topology updates in place
  * (GI_C_SCENE_OPTION_TLAS_TOPOLOGY) the arrays are made anew over the meshes in storage order, appended ones at the end: every BLAS range is compared where it
- * lies; a retired (destroyed) mesh is a hidden one -- out of the TLAS -- and its BLAS ranges and traversal records are ignored.  out[0]: 1 when the two-level layout is
+ * lies; a retired (destroyed) mesh is a hidden one -- out of the TLAS -- and its BLAS ranges and traversal records are ignored; so is the storage slot a
+ * retired instance left (GI_C_SCENE_OPTION_TLAS_INSTANCES) until a grow of its mesh takes it: the arrays are made over the live instances where they lie.  out[0]: 1 when the two-level layout is
  * in use (0: nothing was compared), [1] instances, [2] TLAS nodes, [3] TLAS depth. */
 int giCDebugSceneTlasCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t* out /* 4 */);
 /* [ext] [debug] device check of the kernels that make the world boxes of moved instances (gi_tlas.hip k_inst_bounds / k_inst_finish): the mesh (`vertices`,
@@ -783,7 +797,8 @@ int giCDebugSceneBlasUpdateCount(const GiCScene* scene, uint64_t* outCount);
  * current meshes (instance boxes do not depend on a BLAS's shape); (e) a resident per-instance traversal record that differs from the fresh one with its
  * BLAS root replaced by the resident BLAS's.  (c), reported separately: out[2] counts the violations of the conservative check -- every node's dequantised
  * slot box contains the padded boxes of all faces below it, every usable face is named by exactly one leaf slot.  A mesh retired by a topology update in place
- * (GI_C_SCENE_OPTION_TLAS_TOPOLOGY) is skipped: its ranges and records are ignored, as a hidden mesh it is out of the TLAS.  Returns the number of differences plus those violations (0), <0
+ * (GI_C_SCENE_OPTION_TLAS_TOPOLOGY) is skipped: its ranges and records are ignored, as a hidden mesh it is out of the TLAS; the traversal record of a storage slot a
+ * retired instance left (GI_C_SCENE_OPTION_TLAS_INSTANCES) is ignored likewise.  Returns the number of differences plus those violations (0), <0
  * on error.  out[0]: 1 when the two-level layout is in use (0: nothing was compared), [1] BLAS nodes compared, [2] conservative violations, [3] BLAS
  * triangles compared. */
 int giCDebugSceneBlasCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t* out /* 4 */);
@@ -818,6 +833,22 @@ int giCDebugAppendRecords(const GiCVertex* vertices, uint32_t vertexCount, const
 int giCDebugAppendRecordsHost(const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, const int32_t* faceIds, uint32_t maxFaceId,
                               uint32_t flags, const float* xforms16, uint32_t xformCount, uint32_t vertexOffset, uint32_t shadeBase, uint32_t idBase,
                               uint32_t matFlags);
+/* [ext] [debug] device check of the kernel that makes the flat records of new instances of built meshes (gi_instances.hip k_instance_records): `meshCount`
+ * meshes (`flags`: bit 0 flip-facing, bit 1 double-sided; `faceIds`: faceCount entries or NULL) and `jobCount` new instances, each of mesh `mesh` under
+ * `transform` (16 floats, USD row vectors), with the instance record `instanceSlot`, the flat records [recordSlot, recordSlot + the mesh's faces) and the
+ * scene-order ids from `idBase` on -- slots in any order, with gaps.  ONE launch runs over scratch arrays pre-filled with a pattern; returns the number of
+ * BYTES of the flat records, face-id words and id-table words that differ from the scene build's own host forms (flattenInstance, faceIdAovOf, id ==
+ * position in the table), words outside every job's range included (0 is the contract), <0 on error (no device, a null array, an index outside the
+ * vertices, an unusable transform, overlapping slots).  giCDebugInstanceRecordsHost: the host form of the same kernel (gi_instances.h) against the same
+ * references; no device use. */
+typedef struct GiCDebugInstanceMesh { const GiCVertex* vertices; const GiCFace* faces; const int32_t* faceIds; uint32_t vertexCount, faceCount, maxFaceId, flags; } GiCDebugInstanceMesh;
+typedef struct GiCDebugInstanceJob { uint32_t mesh, instanceSlot, recordSlot, idBase; float transform[16]; } GiCDebugInstanceJob;
+int giCDebugInstanceRecords(const GiCDebugInstanceMesh* meshes, uint32_t meshCount, const GiCDebugInstanceJob* jobs, uint32_t jobCount);
+int giCDebugInstanceRecordsHost(const GiCDebugInstanceMesh* meshes, uint32_t meshCount, const GiCDebugInstanceJob* jobs, uint32_t jobCount);
+/* [ext] [debug] instancer edits applied in place on the two-level layout (GI_C_SCENE_OPTION_TLAS_INSTANCES): out[0] = syncs applied, out[1] = instances
+ * appended, out[2] = of those, how many went into reused storage slots, out[3] = instances retired.  Such a sync counts once in
+ * giCDebugSceneTlasTopologyUpdateCount, and neither in giCDebugSceneUpdateCounts nor in giCDebugSceneInstanceUpdateCount. */
+int giCDebugSceneTlasInstanceUpdateStats(const GiCScene* scene, uint64_t out[4]);
 /* [ext] [debug] what a built scene holds of the flat tree (GI_C_SCENE_OPTION_TLAS_ONLY): out[0] = 1 for the two-level layout, out[1] = 1 when the scene was built
  * without the flat tree, out[2] = flat nodes resident on device copy `device`, out[3] = bytes of flat nodes the host copy holds.  GI_C_OK, or GI_C_ERROR for a
  * scene that has not been built or a device copy that does not exist. */
@@ -825,7 +856,8 @@ int giCDebugSceneFlatTreeState(const GiCScene* scene, uint32_t device, uint64_t 
 /* [ext] [debug] the flat triangle records, the id table (scene-order id -> flat record) and the per-instance traversal records resident on device
  * `deviceIndex` of a scene rendered at least once, downloaded and checked.  Returns the number of violations of: the ids of the records of visible instances
  * are a permutation of [0, visible triangles); the table names each of them at its id; its instance's triBase + prim is its id; records of hidden instances
- * have zero edges (0), <0 on error.  A mesh retired by a topology update in place counts as a hidden one: its ids are skipped.  out[0]: visible triangles, [1] resident triangles, [2] hidden instances, [3] 1 when the two-level layout is in use (0:
+ * have zero edges (0), <0 on error.  A mesh retired by a topology update in place counts as a hidden one: its ids are skipped; so does the storage
+ * slot a retired instance left (GI_C_SCENE_OPTION_TLAS_INSTANCES) until a grow of its mesh takes it.  out[0]: visible triangles, [1] resident triangles, [2] hidden instances, [3] 1 when the two-level layout is in use (0:
  * nothing was compared). */
 int giCDebugSceneFlatIdCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t* out /* 4 */);
 /* [ext] [debug] device check of the kernels of a visibility update of the two-level layout (gi_patch.hip k_patch_visibility2 / k_patch_inst_trav).  The
