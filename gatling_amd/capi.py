@@ -195,6 +195,7 @@ SYMBOLS = [
     ("giCDebugPatchVisibilityTwoLevel", C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _U, _U, C.POINTER(C.c_uint32)]),
     ("giCDebugPathWalkStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugPathLobeStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("giCDebugPathRingStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugPathLot", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("giCDebugMissRect", C.c_int, [_FP, C.POINTER(GiCCameraDesc), C.POINTER(GiCRenderSettings), _U, _U, C.POINTER(C.c_uint32)]),
 ]
@@ -856,6 +857,15 @@ class Scene:
         if self.L.giCDebugPathLobeStats(self.handle, c) != GI_C_OK:
             raise GiError("giCDebugPathLobeStats failed")
         keys = ("shaded", "glossy", "glossyTrips", "liteTrips", "fullTrips", "parked", "adopted", "reruns", "rerunHits")
+        return {k: int(v) for k, v in zip(keys, c)}
+
+    def path_ring_stats(self) -> dict:
+        """giCDebugPathRingStats: the triangle-ring counters of the fused kernel's closest-hit loops in the last render (OPTION_COUNT_TRAVERSAL; all zero
+        otherwise).  With GATLING_OPTIONS ring_carry=1 set explicitly the ring is carried across the steps of a trip and flushed once at the loop's end."""
+        c = (C.c_uint64 * 5)()
+        if self.L.giCDebugPathRingStats(self.handle, c) != GI_C_OK:
+            raise GiError("giCDebugPathRingStats failed")
+        keys = ("batches", "pairs", "partialBatches", "flushes", "ballotSteps")
         return {k: int(v) for k, v in zip(keys, c)}
 
     def set_option(self, option: int, value: int):

@@ -679,6 +679,17 @@ extern "C" int giCDebugPathLobeStats(const GiCScene* scene, uint64_t* out)
   return GI_C_OK;
 }
 
+// giCDebugPathRingStats: what the triangle ring of the fused kernel's closest-hit loops did in the last render of a counting build (Counters::ringStats of the
+// primary device; gi_path.hip).  All zero after a render that did not run k_path with counters.
+extern "C" int giCDebugPathRingStats(const GiCScene* scene, uint64_t* out)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!s || !out) { setError("giCDebugPathRingStats: bad arguments"); return GI_C_ERROR; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  for (int k = 0; k < 5; k++) out[k] = s->pathRingStats[k];
+  return GI_C_OK;
+}
+
 // giCDebugPathLot: where k_path keeps parked hits for a tree of this depth (gi_kernels.h pathLotPlacement) and the dynamic LDS its launch asks for.  Host only.
 extern "C" int giCDebugPathLot(uint32_t bvhDepth, uint32_t nodeCount, uint32_t triCount, uint32_t* out)
 {

@@ -292,6 +292,7 @@ struct SceneDevice {
   GiCRenderStats stats{};
   uint64_t pathWalkStats[18] = {}; // giCDebugPathWalkStats: k_path's trips and walk-step tables of the last render (counting builds; fillStats)
   uint64_t pathLobeStats[9] = {};  // giCDebugPathLobeStats: Counters::lobeStats of the last render (counting builds; fillStats)
+  uint64_t pathRingStats[5] = {};  // giCDebugPathRingStats: Counters::ringStats of the last render (counting builds; fillStats)
   std::vector<hipEvent_t> eventPool;
   // the resizable path state (what the memory plan of a render sizes: slots, media, sampleBuf, the queues) -- the ONE list of these buffers
   template <typename Fn> void forEachPathBuffer(Fn&& fn)

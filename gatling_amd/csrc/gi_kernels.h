@@ -59,10 +59,12 @@ void launchShade(hipStream_t s, uint32_t blocks, uint32_t klass, bool textured /
 bool pathKernelSupports(const SceneView& sc);
 // lobePark: k_path's class-1 variants without NEE park hits that drew a glossy lobe and shade them together once this many are parked (0: off); the general
 // variant takes it in counting builds only, every other variant ignores it
+// ringCarry: the variants without NEE carry the triangle ring across the steps of a trip's closest-hit loop and flush it once (0: every step empties it)
 int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool textured, bool count, uint32_t chunk, uint32_t walkCarry, uint32_t lobePark,
-               const FrameUniforms& U, const SceneView& sc, const PathState& st, Counters* cnt, F4* sampleBuf);
+               uint32_t ringCarry, const FrameUniforms& U, const SceneView& sc, const PathState& st, Counters* cnt, F4* sampleBuf);
 constexpr long WALK_CARRY_DEFAULT = 8; // GATLING_OPTIONS=walk_carry (gi_options.h)
 constexpr long LOBE_PARK_DEFAULT = 8;  // GATLING_OPTIONS=lobe_park (gi_options.h)
+constexpr long RING_CARRY_DEFAULT = 1; // GATLING_OPTIONS=ring_carry (gi_options.h)
 // Where k_path keeps its parked hits (the lot): in the rows of its per-lane traversal stack that no walk of the tree reaches.  A walk pushes at most bvhDepth
 // entries, so of the `stack` rows (4 for trees of depth <= 4, else 8) the rows from `row` = bvhDepth on are free; a row of a wave's 64 columns holds 8 records
 // of 16 dwords.  capacity 0: nothing is free, the parking is off for this tree.  The launch's LDS is traceLdsBytes(stack, ...) as ever: the lot adds nothing.

@@ -53,6 +53,7 @@ __global__ void k_init(PathState st, QueueSet qs, Counters* cnt, uint32_t n, uin
                       for (int k = 0; k < 4; k++) { cnt->phaseCycles[k] = 0; cnt->phaseLanes[k] = 0; } cnt->phaseTrips = 0;
                       for (int k = 0; k < 8; k++) { cnt->walkStepLanes[k] = 0; cnt->walkStepTrips[k] = 0; } cnt->walkFewLaneSteps = 0;
                       for (int k = 0; k < 9; k++) cnt->lobeStats[k] = 0;
+                      for (int k = 0; k < 5; k++) cnt->ringStats[k] = 0;
                           for (int k = 0; k < 8; k++) cnt->dynStats[k] = 0; }
   }
   for (; i < n; i += gridDim.x * blockDim.x) qs.slot[Q_REGEN_A][(i / per) * qs.cap + (i % per)] = i | REGEN_FRESH; // the slots themselves stay untouched

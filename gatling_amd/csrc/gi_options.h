@@ -28,6 +28,11 @@
 //                                  the traversal stack hold (gi_kernels.h pathLotPlacement).  0 = every hit is shaded in the trip that found it; 1 (tests) =
 //                                  most eager; 64 (tests) = as late as the lot allows.  Counting builds run with 0 unless the key is set explicitly
 //                                  (giCDebugPathLobeStats shows what it did)
+//   ring_carry           1         fused frames without next-event estimation: the ring of (ray, triangle) pairs of a k_path wave is carried across the steps
+//                                  of a trip's closest-hit loop -- a triangle batch runs when 64 pairs are pending, and one flush at the loop's end tests the
+//                                  rest (gi_path.hip).  0 = every step ends with a batch over whatever is pending.  Counting builds run with 0 unless the
+//                                  key is set explicitly: a lagging culling distance moves their node and triangle counts (giCDebugPathRingStats shows
+//                                  the batches either way)
 //   fused                1         LDS-resident scenes run the fused persistent kernel
 //   pool_slots           0         pin the path pool (slots); 0 = the memory plan decides
 //   sample_buffer_mb     0         pin the per-sample buffer (MiB); 0 = the memory plan decides

@@ -28,6 +28,10 @@
 // walker and free are exclusive lane states and only free lanes adopt; every trip retires a segment, adds to a bounded lot or takes from it; the kernel ends
 // with the lot empty; lobePark = 0 is the kernel without parking.
 //
+// The (ray, triangle) pairs a step leaves over after its full batches wait for the next step of the trip (the NEE-off variants; "Ring carry" in the trip loop):
+// a triangle batch runs whenever 64 pairs are pending and one flush in the loop's last step tests the rest, instead of a partial batch at the end of every
+// step.  Hit keys do not depend on when a pair is tested; ringCarry = 0 flushes in every step.
+//
 // Not handled here (the host falls back to the wavefront pipeline): medium stacks (mediumStackSize > 0), dome-light images,
 // scenes beyond LDS, trees deeper than 8 levels.
 
@@ -52,7 +56,7 @@ constexpr int PATH_WAVES = 4; // resident waves per SIMD the register allocation
 template <uint32_t KLASS, bool TEXTURED, bool NEE, bool CUTOUT, bool COUNT, uint32_t PATH_STACK>
 __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PATH_WAVES, 8))) void k_path(FrameUniforms U, SceneView sc, PathState st,
     Counters* cnt, F4* __restrict__ sampleBuf, uint32_t ldsNodes, uint32_t ldsTris, uint32_t chunk, uint32_t walkCarry, uint32_t lobePark, uint32_t lotRow,
-    uint32_t lotCap)
+    uint32_t lotCap, uint32_t ringCarry)
 {
   // Walk carry (NEE off): see the closest-hit loop.  The NEE variants' shadow walk reuses R and WaveTri::best[lane], so they never carry.
   constexpr bool CARRY = !NEE;
@@ -89,6 +93,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
   uint32_t whLanes[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}, whTrips[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}; // COUNT: lanes walking at step 0 .. 7+ of a trip's loop
   uint32_t whFew = 0u; // COUNT: steps that began with fewer than 8 lanes walking
   uint32_t lobeN[9] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}; // COUNT: Counters::lobeStats of this wave
+  RingStats ringN{0u, 0u, 0u, 0u, 0u}; // COUNT: Counters::ringStats of this wave
   // The lot: the parked hits of this wave, 16-dword records in the rows of the traversal stack that no walk of this tree reaches.  Record k lies in row
   // lotRow + k / 8, in the 8 columns from k % 8 * 8 of the wave's 64 (a row of a wave: 64 columns x 8 bytes = 8 records).  The host passes the first free row
   // and the capacity (launchPath: lotRow >= bvhDepth, the most entries a walk pushes); clamped here once more to what PATH_STACK rows hold.
@@ -177,6 +182,14 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
     // and tMin stay put because a carried lane does nothing after the loop, and what trav_init derives from them is derived again.  Per-ray arithmetic, culling
     // distance and the atomicMin key are what they were: the walk of a ray is the same sequence of steps, cut in two.  If no more than walkCarry lanes enter (the
     // frame's tail) the loop runs to completion, so every trip retires at least one segment.  walkCarry = 0: every loop runs to completion.
+    // Ring carry (NEE off): a step yields fewer (ray, triangle) pairs than a batch holds -- a trip's two to three steps make ~180 pairs, three batches' worth
+    // -- and wave_step ends every step with a batch over whatever is pending, so a trip paid a partial batch per step on top of the full ones.  With ringCarry
+    // the pending pairs live across the steps of this loop (wave_step_ring, gi_traversal.h): a batch runs whenever 64 are pending, and ONE flush in the loop's
+    // last step -- the loop run to completion or ended early by the walk carry -- tests the rest.  Every lane of the trip reads its key at the end of every
+    // step, so a lane whose walk ended in an early step has its final hit after that flush; it keeps R.o / R.d / tMin / rng untouched until then, which is
+    // what its pending pairs read.  Nothing is pending at a trip boundary, so carried walks, adoption from the lot and regeneration see nothing of it.  Hit
+    // keys do not depend on when a pair is tested: images and `segments` are the same; a walk may cull with a distance one step old, so nodes visited and
+    // triangles tested can only grow.  ringCarry = 0: every step ends with that flush (the kernel before the carry).
     {
       const bool carried = CARRY && tAlive;
       const uint2 G = R.G; const uint32_t sp = R.sp;
@@ -189,14 +202,25 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
       unsigned long long walking = __ballot(tAlive);
       const uint32_t stop = (uint32_t)__popcll(walking) > walkCarry ? walkCarry : 0u;
       uint32_t step = 0u;
-      while ((uint32_t)__popcll(walking) > stop) {
+      uint32_t pend = 0u; // wave-uniform: pairs waiting in the queue (none when a trip's loop begins, none when it has ended)
+      if ((uint32_t)__popcll(walking) > stop) for (;;) {
         if (COUNT) {
           const uint32_t n = (uint32_t)__popcll(walking);
           whLanes[step] += n; whTrips[step]++; step = step < 7u ? step + 1u : 7u;
           if (n < 8u) whFew++;
         }
-        if (wave_step<false, COUNT, PATH_STACK, false, STAGED_ALL, CUTOUT>(R, tAlive, W, sc, S, overflow, tc, rng)) tAlive = false;
+        if (wave_step_ring<COUNT, PATH_STACK, STAGED_ALL, CUTOUT>(R, tAlive, W, sc, S, overflow, tc, rng, pend, ringN)) tAlive = false;
         walking = __ballot(tAlive);
+        const bool last = (uint32_t)__popcll(walking) <= stop;
+        if ((last || ringCarry == 0u) && pend != 0u) { // the one flush of the trip (ringCarry = 0: of every step)
+          if (COUNT && ringCarry != 0u) ringN.flushes++;
+          wave_ring_batch<COUNT, STAGED_ALL, CUTOUT>(W, pend, pend, R, rng, sc, S, tc, ringN);
+        }
+        // every lane of the trip picks up what the batches have found: a walking lane its culling distance, a lane whose walk has ended -- in this step or
+        // an earlier one -- its hit, which is final after the flush of the last step
+        __atomic_signal_fence(__ATOMIC_SEQ_CST);
+        if (alive) wave_ring_refresh(R, W);
+        if (last) break;
       }
     } else {
       while (__ballot(tAlive)) {
@@ -367,7 +391,10 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
       } atomicAdd(&cnt->phaseTrips, trips);
       for (int k = 0; k < 8; k++) { atomicAdd(&cnt->walkStepLanes[k], (unsigned long long)whLanes[k]); atomicAdd(&cnt->walkStepTrips[k], (unsigned long long)whTrips[k]); }
       atomicAdd(&cnt->walkFewLaneSteps, (unsigned long long)whFew);
-      for (int k = 0; k < 9; k++) atomicAdd(&cnt->lobeStats[k], (unsigned long long)lobeN[k]); }
+      for (int k = 0; k < 9; k++) atomicAdd(&cnt->lobeStats[k], (unsigned long long)lobeN[k]);
+      if (CARRY) { atomicAdd(&cnt->ringStats[0], (unsigned long long)ringN.batches); atomicAdd(&cnt->ringStats[1], (unsigned long long)ringN.pairs);
+        atomicAdd(&cnt->ringStats[2], (unsigned long long)ringN.partial); atomicAdd(&cnt->ringStats[3], (unsigned long long)ringN.flushes);
+        atomicAdd(&cnt->ringStats[4], (unsigned long long)ringN.ballotSteps); } }
   // statistics: one atomic per wave and counter
   unsigned long long a = nSeg, b = nShadow, c = tc.nodes, d = tc.tris, e = tcs.nodes, f = tcs.tris;
   for (int off = 32; off > 0; off >>= 1) {
@@ -394,7 +421,7 @@ bool pathKernelSupports(const SceneView& sc)
          && !sc.shadePacked;
 }
 
-using PathKernel = void (*)(FrameUniforms, SceneView, PathState, Counters*, F4*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t);
+using PathKernel = void (*)(FrameUniforms, SceneView, PathState, Counters*, F4*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t);
 // Hot variants: one material class, no textures, no cutouts, no counters (the C1 / C2 paths).  Everything else runs the general
 // variant (class read from the material record, textures and cutouts compiled in).
 template <uint32_t STACK>
@@ -413,7 +440,7 @@ static PathKernel pickPathKernel(uint32_t classMask, bool textured, bool nee, bo
 }
 
 int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool textured, bool count, uint32_t chunk, uint32_t walkCarry, uint32_t lobePark,
-               const FrameUniforms& U, const SceneView& sc, const PathState& st, Counters* cnt, F4* sampleBuf)
+               uint32_t ringCarry, const FrameUniforms& U, const SceneView& sc, const PathState& st, Counters* cnt, F4* sampleBuf)
 {
   if (U.workTotal == 0u) return 0; // an empty active rectangle (FLAG_MISS_RECT, the camera looks away): no pixel needs a path
   const uint32_t ldsNodes = sc.nodeCount, ldsTris = sc.triCount;
@@ -441,7 +468,7 @@ int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool texture
   const uint64_t needed = (chunks + (TRACE_BLOCK / 64u) - 1u) / (TRACE_BLOCK / 64u);
   if (blocks > needed) blocks = needed;
   if (blocks == 0u) blocks = 1u;
-  hipLaunchKernelGGL(k, dim3((uint32_t)blocks), dim3(TRACE_BLOCK), bytes, s, U, sc, st, cnt, sampleBuf, ldsNodes, ldsTris, chunk, walkCarry, lobePark, lot.row, lot.capacity);
+  hipLaunchKernelGGL(k, dim3((uint32_t)blocks), dim3(TRACE_BLOCK), bytes, s, U, sc, st, cnt, sampleBuf, ldsNodes, ldsTris, chunk, walkCarry, lobePark, lot.row, lot.capacity, ringCarry);
   return perCu;
 }
 

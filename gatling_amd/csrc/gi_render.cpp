@@ -434,6 +434,7 @@ struct Schedule {
   uint32_t dynRefill = 8u;      // k_trace_dyn refill threshold
   uint32_t walkCarry = 0u;      // k_path: the closest-hit loop of a trip ends once at most this many lanes are still walking (0: never early)
   uint32_t lobePark = 0u;       // k_path: hits that drew a glossy lobe are parked and shaded together once this many wait (0: shaded where they are)
+  uint32_t ringCarry = 0u;      // k_path: the triangle ring is carried across the steps of a trip's closest-hit loop (0: every step empties it)
   int32_t shadowOrderNow = -1;  // visiting order of the shadow walks; -1: not chosen yet -- alternate, and count (chooseShadowOrder)
 };
 struct Frame {
@@ -525,6 +526,9 @@ static Schedule scheduleFrame(Frame& f)
   // Lobe parking of k_path (gi_path.hip): the threshold at which a wave shades its parked glossy hits.  walk_carry's rule for counting builds: off unless the
   // key is set, so that the phase tables keep describing plain trips (giCDebugPathLobeStats then shows what the parking did).
   sch.lobePark = s->countTraversal && !optionSet("lobe_park") ? 0u : (uint32_t)std::min(std::max(optionValue("lobe_park", LOBE_PARK_DEFAULT), 0L), 64L);
+  // Ring carry of k_path (gi_path.hip): pending (ray, triangle) pairs wait for a full batch across the steps of a trip.  A walk then culls with a distance
+  // that may lag by a step, so a counting build's nodesVisited / trisTested move with it: the same rule again, off there unless the key is set.
+  sch.ringCarry = s->countTraversal && !optionSet("ring_carry") ? 0u : (optionValue("ring_carry", RING_CARRY_DEFAULT) != 0 ? 1u : 0u);
   sch.dynRefill = traceDynRefill(s);
   // (GATLING_OPTIONS=shadow_order=0|1 pins it)
   sch.shadowOrderNow = optionSet("shadow_order") ? (int32_t)optionValue("shadow_order", -1) : s->shadowOrder.load();
@@ -588,7 +592,7 @@ static int runFusedBatch(Frame& f, uint32_t batch)
   chunk = (uint32_t)std::min<uint64_t>(chunk, std::max<uint64_t>(64u, ((uint64_t)U.workTotal / (waves * 16u)) & ~63ull));
   f.tm.beginIteration(true); // one launch per batch: timed whatever the stride
   f.tm.timed(f.st, StageTimers::TRACE, [&] {
-    launchPath(f.st, (uint32_t)f.ctx.cuCount, s->classMask, s->classTextured != 0u, s->countTraversal, chunk, f.sch.walkCarry, f.sch.lobePark, U, f.view, f.ps,
+    launchPath(f.st, (uint32_t)f.ctx.cuCount, s->classMask, s->classTextured != 0u, s->countTraversal, chunk, f.sch.walkCarry, f.sch.lobePark, f.sch.ringCarry, U, f.view, f.ps,
                D.dCounters.ptr, D.sampleBuf.ptr);
   });
   f.iters++; f.tm.totalIters++; f.traceLaunches++;
@@ -777,6 +781,7 @@ static void fillStats(const Frame& f, double tEnd)
   uint64_t* W = f.D.pathWalkStats; // giCDebugPathWalkStats (all zero unless a counting build's k_path ran in this render)
   for (int k = 0; k < 18; k++) W[k] = 0u;
   for (int k = 0; k < 9; k++) f.D.pathLobeStats[k] = 0u; // giCDebugPathLobeStats, likewise
+  for (int k = 0; k < 5; k++) f.D.pathRingStats[k] = 0u; // giCDebugPathRingStats, likewise
   if (f.served) { // nothing was launched but the fold: the counters on the device are still those of the call that traced the window
     S.fusedPath = S.batches = S.poolSlots = 0u;
     S.segments = S.shadowRays = S.nodesVisited = S.trisTested = S.shadowNodesVisited = S.shadowTrisTested = 0u;
@@ -787,6 +792,7 @@ static void fillStats(const Frame& f, double tEnd)
   S.shadowNodesVisited = c.shadowNodesVisited; S.shadowTrisTested = c.shadowTrisTested;
   W[0] = c.phaseTrips; W[17] = c.walkFewLaneSteps;
   for (int k = 0; k < 9; k++) f.D.pathLobeStats[k] = c.lobeStats[k];
+  for (int k = 0; k < 5; k++) f.D.pathRingStats[k] = c.ringStats[k];
   for (int k = 0; k < 8; k++) { W[1 + k] = c.walkStepTrips[k]; W[9 + k] = c.walkStepLanes[k]; }
 }
 

@@ -1,6 +1,6 @@
 // gi_traversal.h -- software traversal of the 8-wide quantised BVH, shared by every kernel that walks it: per-lane traversal state and node test, the scene
 // staged in LDS (stage_scene), the per-lane step (k_aov: traverse), the wave's ring of (ray lane, triangle) pairs with its two append forms and the cooperative
-// triangle batch, wave_step (gi_trace.hip k_trace, gi_path.hip k_path) and the two-level walk wave_step2 (k_trace_dyn2).  gi_trace.hip's k_trace_dyn composes
+// triangle batch, wave_step (gi_trace.hip k_trace, gi_path.hip k_path), wave_step_ring (k_path without NEE: pending pairs carried across steps) and the two-level walk wave_step2 (k_trace_dyn2).  gi_trace.hip's k_trace_dyn composes
 // its own step from the same pieces.  Included by gi_trace.hip, gi_path.hip, gi_aov.hip, gi_kernels.hip and gi_shade.hip.
 #pragma once
 
@@ -355,14 +355,14 @@ __device__ __forceinline__ void wave_tri_accept(WaveTri& W, uint32_t rl, uint32_
   }
 }
 
-// 64 (ray lane, triangle) pairs of the ring, one per lane.
-template <bool COUNT, Staged STAGED, bool CUTOUT, bool RESULT_RECORD = false>
+// 64 (ray lane, triangle) pairs of the ring, one per lane.  // LINEAR: the entries head .. head + cnt - 1 do not wrap (wave_step_ring)
+template <bool COUNT, Staged STAGED, bool CUTOUT, bool RESULT_RECORD = false, bool LINEAR = false>
 __device__ __forceinline__ void wave_tri_batch(WaveTri& W, uint32_t head, uint32_t cnt, const RayWalk& R, uint32_t rng, const SceneView& sc,
                                                StagedScene S, TraceCounters& tc)
 {
   const uint32_t lane = __lane_id();
   const bool act = lane < cnt;
-  const uint32_t e = act ? wt_queue_get(W, (head + lane) & 127u) : 0u;
+  const uint32_t e = act ? wt_queue_get(W, LINEAR ? head + lane : (head + lane) & 127u) : 0u;
   const uint32_t rl = e >> TRI_ID_BITS, triIdx = e & ((1u << TRI_ID_BITS) - 1u);
   V3 o, d; float tMin; uint32_t rrng;
   owner_ray<CUTOUT>(rl, R.o, R.d, R.tMin, rng, o, d, tMin, rrng);
@@ -439,6 +439,72 @@ __device__ __forceinline__ bool wave_step(RayTrav& R, bool alive, WaveTri& W, co
     done = (ANYHIT && R.found) ? true : trav_pop<STACK, OVERFLOW>(R, S.stack, overflow);
   }
   return done;
+}
+
+// wave_step with the pending pairs carried from step to step (k_path's closest-hit loop, NEE off; k_trace_dyn composes its own form, a FIFO with draining
+// lanes).  wave_step empties the ring at the end of every step, so every step that produced pairs ends with a partial batch -- the whole ~110-instruction batch
+// for a handful of pairs.  Here the caller keeps `pend` (wave-uniform, < 64 between steps), the number of pairs waiting in queue[0 .. pend): a step appends its
+// pairs behind them -- by prefix sum when pending + new fit the 128 entries, else by ballot rounds -- and a batch takes the LAST 64 entries whenever 64 are
+// pending; the rest waits for the next step.  Taking batches from the top keeps the pending pairs at the bottom of the queue: no position ever wraps, so the
+// append loop is wave_step's, instruction for instruction (a ring's `& 127` per entry written cost more than the batches saved, profiles/r22_ring_carry.txt);
+// the order in which pairs are tested decides nothing (the key under atomicMin).  The caller flushes what is pending when its loop ends (wave_ring_batch) and
+// the lanes then read their key (wave_ring_refresh).  Nothing a pending pair needs changes meanwhile: its owner lane keeps R.o, R.d, R.tMin and rng until that
+// flush.  A walking lane culls with the distance the batches that did run have found, so it may visit a node or test a triangle that an emptied queue would
+// have culled -- never fewer.
+struct RingStats { uint32_t batches, pairs, partial, flushes, ballotSteps; }; // COUNT: Counters::ringStats of one wave
+// a batch over the top n (<= 64) pending pairs
+template <bool COUNT, Staged STAGED, bool CUTOUT>
+__device__ __forceinline__ void wave_ring_batch(WaveTri& W, uint32_t& pend, uint32_t n, const RayWalk& R, uint32_t rng, const SceneView& sc, StagedScene S,
+                                                TraceCounters& tc, RingStats& rs)
+{
+  pend -= n;
+  wave_tri_batch<COUNT, STAGED, CUTOUT, false, true>(W, pend, n, R, rng, sc, S, tc);
+  if (COUNT) { rs.batches++; rs.pairs += n; if (n < 64u) rs.partial++; }
+}
+// node phase, append, the full batches, pop; returns true when this lane's walk has ended (its R.tBest / R.found: wave_ring_refresh, after the flush)
+template <bool COUNT, uint32_t STACK, Staged STAGED, bool CUTOUT>
+__device__ __forceinline__ bool wave_step_ring(RayTrav& R, bool alive, WaveTri& W, const SceneView& sc, StagedScene S, uint2 (&overflow)[1], TraceCounters& tc,
+                                               uint32_t rng, uint32_t& pend, RingStats& rs)
+{
+  const uint32_t lane = __lane_id();
+  uint2 Gt = make_uint2(0u, 0u);
+  if (alive) Gt = trav_node<COUNT, STACK, false, STAGED>(R, sc, S, overflow, tc);
+  const uint32_t cntL = (uint32_t)__popc(Gt.y);
+  const uint32_t scan = wave_scan_inclusive(cntL);
+  const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)scan, 63);
+  if (pend + total <= 128u) { // positions from the prefix sum, behind the pending pairs
+    uint32_t pos = pend + scan - cntL;
+    while (Gt.y) {
+      const uint32_t k = (uint32_t)__ffs((int)Gt.y) - 1u;
+      Gt.y &= Gt.y - 1u;
+      wt_queue_put(W, pos, (lane << TRI_ID_BITS) | (Gt.x + k));
+      pos++;
+    }
+    pend += total;
+    while (pend >= 64u) wave_ring_batch<COUNT, STAGED, CUTOUT>(W, pend, 64u, R, rng, sc, S, tc, rs);
+  } else { // (more pairs than the queue has room for) one ballot round per triangle; a batch as soon as 64 pairs are pending (<= 63 + 64 <= the 128 entries)
+    if (COUNT) rs.ballotSteps++;
+    for (;;) {
+      const unsigned long long m = __ballot(Gt.y != 0u);
+      if (!m) break;
+      if (Gt.y) {
+        const uint32_t k = (uint32_t)__ffs((int)Gt.y) - 1u;
+        Gt.y &= Gt.y - 1u;
+        wt_queue_put(W, pend + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)), (lane << TRI_ID_BITS) | (Gt.x + k));
+      }
+      pend += (uint32_t)__popcll(m);
+      if (pend >= 64u) wave_ring_batch<COUNT, STAGED, CUTOUT>(W, pend, 64u, R, rng, sc, S, tc, rs);
+    }
+  }
+  pend = (uint32_t)__builtin_amdgcn_readfirstlane((int)pend); // a scalar register across the steps
+  return alive ? trav_pop<STACK, false>(R, S.stack, overflow) : false; // (a closest-hit pop does not depend on tBest)
+}
+// what the batches that ran have found for this lane's ray
+__device__ __forceinline__ void wave_ring_refresh(RayTrav& R, WaveTri& W)
+{
+  const unsigned long long key = wt_best_get(W, __lane_id());
+  R.tBest = u2f((uint32_t)(key >> 32));
+  R.found = (uint32_t)key != 0u;
 }
 
 // start of a ray in the cooperative scheme (after trav_init)

@@ -358,6 +358,9 @@ struct Counters {
   // in the lot, [6] records adopted from it, [7] trips whose shade was run again as FULL on the spot (the lot could not take their glossy hits), [8] the hits
   // shaded in those second passes.  [3] .. [8] stay zero while the parking is off.
   unsigned long long lobeStats[9];
+  // k_path, counting builds only (giCDebugPathRingStats): the triangle ring of the closest-hit loops -- [0] batches, [1] (ray, triangle) pairs tested in them,
+  // [2] batches of fewer than 64 pairs, [3] end-of-loop flushes (ring carry on: gi_path.hip), [4] steps whose pairs were appended by ballot rounds
+  unsigned long long ringStats[5];
 };
 
 } // namespace gi

@@ -379,7 +379,7 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * The same holds for GI_C_SCENE_OPTION_VISIBILITY_UPDATES, giCDebugSceneVisibilityUpdateCount, giCDebugSceneClassState, giCDebugMissRect and giCDebugPathWalkStats, and for
  * giCSetMeshVertices, GI_C_SCENE_OPTION_VERTEX_UPDATES, giCDebugSceneVertexUpdateCount, giCDebugRefitBvh and giCDebugSceneRefitCheck, and for
  * GI_C_SCENE_OPTION_TOPOLOGY_UPDATES and giCDebugSceneTopologyUpdateCount, and for GI_C_SCENE_OPTION_RESYNC_REFITS, giCDebugSceneResyncCount,
- * giCDebugGatherShade and giCDebugSceneShadeCheck, and for giCDebugPathLobeStats and giCDebugPathLot, and for GI_C_SCENE_OPTION_INSTANCE_UPDATES,
+ * giCDebugGatherShade and giCDebugSceneShadeCheck, and for giCDebugPathLobeStats, giCDebugPathRingStats and giCDebugPathLot, and for GI_C_SCENE_OPTION_INSTANCE_UPDATES,
  * giCDebugSceneInstanceUpdateCount and giCDebugCloneInstance, and for GI_C_SCENE_OPTION_TLAS_UPDATES, giCDebugSceneTlasUpdateCount, giCDebugSceneTlasCheck
  * and giCDebugInstanceBounds, and for GI_C_SCENE_OPTION_BLAS_UPDATES, giCDebugSceneBlasUpdateCount, giCDebugSceneBlasCheck, giCDebugBlasRefit and
  * giCDebugBlasRefitHost, and for GI_C_SCENE_OPTION_TLAS_VISIBILITY, giCDebugSceneTlasVisibilityUpdateCount, giCDebugSceneFlatIdCheck and
@@ -885,6 +885,12 @@ int giCDebugPathWalkStats(const GiCScene* scene, uint64_t* out /* 18 */);
  * on the spot because the lot could not take their glossy hits, [8] the hits shaded in those second passes.  [3] .. [8] are zero with lobe_park=0 or the key
  * absent; image and per-ray counters are the same whatever N. */
 int giCDebugPathLobeStats(const GiCScene* scene, uint64_t* out /* 9 */);
+/* [ext] the fused path kernel's triangle-ring counters of the scene's last render, for renders with GI_C_SCENE_OPTION_COUNT_TRAVERSAL (all zero otherwise):
+ * out[0] triangle batches of the closest-hit loops, [1] the (ray, triangle) pairs tested in them, [2] the batches that held fewer than 64 pairs, [3] end-of-loop
+ * flushes (a loop that ended with pairs pending), [4] steps whose pairs were appended by ballot rounds because the ring had no room for them at once.  With
+ * $GATLING_OPTIONS ring_carry=1 set explicitly a counting build carries the ring across the steps of a trip as other builds do: partial batches then happen in
+ * flushes only, at most one per trip.  With ring_carry=0 or the key absent every step ends with the ring empty and [3] is zero; the image is the same. */
+int giCDebugPathRingStats(const GiCScene* scene, uint64_t* out /* 5 */);
 /* [ext] where the fused path kernel keeps parked hits for a BVH8 of `bvhDepth` levels below the root: out[0] traversal-stack rows per lane, [1] the first row
  * no walk reaches, [2] the records that fit in the rows from there on (0: parking is off for such a tree), [3] the dynamic LDS bytes of a launch for a scene of
  * nodeCount nodes and triCount triangles -- the rows and nothing else: parked hits add no LDS.  Host only: no device work, no scene. */
