@@ -197,6 +197,8 @@ SYMBOLS = [
     ("giCDebugPathLobeStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugPathRingStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugPathLot", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("giCDebugTraversalStackHigh", C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    ("giCDebugBvhStackReach", C.c_int, [_FP, _U, _FP, _FP, _U, C.POINTER(C.c_uint32)]),
     ("giCDebugMissRect", C.c_int, [_FP, C.POINTER(GiCCameraDesc), C.POINTER(GiCRenderSettings), _U, _U, C.POINTER(C.c_uint32)]),
 ]
 
@@ -237,6 +239,23 @@ def miss_rect(bounds, camera, rs: "RenderSettings", width: int, height: int):
     if L.giCDebugMissRect(_fp(bounds), C.byref(cam), C.byref(st), int(width), int(height), out) != GI_C_OK:
         raise GiError("giCDebugMissRect failed: " + L.giCGetLastError().decode())
     return tuple(int(v) for v in out)
+
+
+def bvh_stack_reach(tri_verts, origins, dirs):
+    """giCDebugBvhStackReach: (levels, nodes, reach) of the host builder's BVH8 over `tri_verts` (n x 3 x 3 world-space triangles in scene order) -- reach[i] is
+    the most stack entries the traversal kernels' ordered walk holds for ray i.  The walk tests boxes only and culls nothing, so reach is an UPPER BOUND on
+    what a device walk of the ray holds (exact for a ray that hits no triangle): it is for designing scenes and for pinning them against builder changes; that
+    a render did fill a stack is shown by the device counter (Scene.traversal_stack_high).  Host only: needs neither a device nor giCInitialize."""
+    import numpy as np
+    L = load_library()
+    v = np.ascontiguousarray(tri_verts, np.float32).reshape(-1, 9)
+    o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    assert o.shape == d.shape
+    out = np.zeros(2 + len(o), np.uint32)
+    if L.giCDebugBvhStackReach(v.ctypes.data_as(_FP), len(v), o.ctypes.data_as(_FP), d.ctypes.data_as(_FP), len(o), out.ctypes.data_as(C.POINTER(C.c_uint32))) != 0:
+        raise GiError("giCDebugBvhStackReach failed")
+    return int(out[0]), int(out[1]), out[2:].copy()
 
 
 def debug_gather_shade(vertices, faces) -> int:
@@ -867,6 +886,15 @@ class Scene:
             raise GiError("giCDebugPathRingStats failed")
         keys = ("batches", "pairs", "partialBatches", "flushes", "ballotSteps")
         return {k: int(v) for k, v in zip(keys, c)}
+
+    def traversal_stack_high(self) -> dict:
+        """giCDebugTraversalStackHigh: the most traversal-stack entries a closest-hit walk (`closest`) and a shadow walk (`shadow`) held in the last render
+        (OPTION_COUNT_TRAVERSAL; all zero otherwise), the stack `rows` of the kernel variant that ran and the scratch-`spill` entries used at most (both derived on the host from the dispatch rule, not
+        counted).  The primary device's walks only."""
+        c = (C.c_uint32 * 4)()
+        if self.L.giCDebugTraversalStackHigh(self.handle, c) != GI_C_OK:
+            raise GiError("giCDebugTraversalStackHigh failed")
+        return {k: int(v) for k, v in zip(("closest", "shadow", "rows", "spill"), c)}
 
     def set_option(self, option: int, value: int):
         if self.L.giCSetSceneOption(self.handle, option, value) != GI_C_OK:

@@ -163,6 +163,68 @@ extern "C" int giCDebugValidateBvh(const float* triVerts, uint32_t triCount, uin
   return validateTree(bvh.nodes, bvh.tris, triCount);
 }
 
+// giCDebugBvhStackReach: the ordered walk of gi_traversal.h (trav_node_pick / trav_pop: a node's hit internal children in octant-flipped slot order, highest
+// bit first, the rest pushed) over the host-built tree, boxes only -- how many stack entries a ray's walk holds at most.  Nothing is culled: no triangle is
+// tested, so the distance never shrinks and every internal child whose box the ray meets counts; the box test is the device's with a wider margin (a box the
+// device accepts by rounding is accepted here).  The result is therefore an UPPER bound on what a device walk of that ray holds, and exact for a ray that hits
+// no triangle.  Host only.
+extern "C" int giCDebugBvhStackReach(const float* triVerts, uint32_t triCount, const float* origins, const float* dirs, uint32_t rayCount, uint32_t* out)
+{
+  if (!out || (triCount && !triVerts) || (rayCount && (!origins || !dirs))) return -1;
+  std::vector<TriRec> tris(triCount);
+  for (uint32_t i = 0; i < triCount; i++) {
+    const float* p = triVerts + 9 * (size_t)i;
+    for (int a = 0; a < 3; a++) { tris[i].v0[a] = p[a]; tris[i].e1[a] = p[3 + a] - p[a]; tris[i].e2[a] = p[6 + a] - p[a]; }
+    tris[i].instance = 0; tris[i].prim = i; tris[i].origId = i;
+  }
+  Bvh8 bvh; buildBvh8(tris, bvh);
+  const std::vector<Node8>& nodes = bvh.nodes;
+  out[0] = bvh.maxDepth; out[1] = (uint32_t)nodes.size();
+  std::vector<std::pair<uint32_t, uint32_t>> stack; // (first child, unvisited hit internal children in bits 24-31 | the node's internal-child mask)
+  for (uint32_t r = 0; r < rayCount; r++) {
+    double o[3], inv[3]; uint32_t oct = 0u;
+    for (int a = 0; a < 3; a++) {
+      o[a] = origins[3 * (size_t)r + a];
+      const float d = dirs[3 * (size_t)r + a];
+      inv[a] = 1.0 / (std::fabs(d) < 1e-30f ? (d < 0.0f ? -1e-30 : 1e-30) : (double)d); // (walk_set_ray's guard)
+      if (d >= 0.0f) oct |= 1u << a;
+    }
+    stack.clear();
+    uint32_t high = 0u;
+    std::pair<uint32_t, uint32_t> G(0u, 0x80000000u); // virtual group holding only the root
+    for (;;) {
+      if (G.second & 0xff000000u) {
+        const uint32_t bit = 31u - (uint32_t)__builtin_clz(G.second & 0xff000000u);
+        G.second &= ~(1u << bit);
+        if (G.second & 0xff000000u) { stack.push_back(G); high = std::max(high, (uint32_t)stack.size()); }
+        const uint32_t slot = (bit - 24u) ^ oct;
+        const uint32_t nodeIdx = G.first + (uint32_t)__builtin_popcount((G.second & 0xffu) & ((1u << slot) - 1u));
+        if (nodeIdx >= nodes.size()) return -1;
+        const Node8& n = nodes[nodeIdx];
+        uint32_t hit = 0u;
+        for (uint32_t s = 0; s < 8u; s++) {
+          if (!((n.imask >> s) & 1u)) continue;
+          double tn = 0.0, tf = 3.0e38;
+          for (int a = 0; a < 3; a++) {
+            const uint32_t eb = (uint32_t)n.e[a] << 23; float scale; memcpy(&scale, &eb, 4);
+            const double t0 = (((double)n.p[a] + (double)n.qlo[a][s] * (double)scale) - o[a]) * inv[a];
+            const double t1 = (((double)n.p[a] + (double)n.qhi[a][s] * (double)scale) - o[a]) * inv[a];
+            tn = std::max(tn, std::min(t0, t1)); tf = std::min(tf, std::max(t0, t1));
+          }
+          if (tn * (1.0 - 1.0e-4) <= tf * (1.0 + 1.0e-4)) hit |= 1u << (24u + (s ^ oct));
+        }
+        G = std::make_pair(n.childBase, hit | (uint32_t)n.imask);
+      }
+      if (!(G.second & 0xff000000u)) {
+        if (stack.empty()) break;
+        G = stack.back(); stack.pop_back();
+      }
+    }
+    out[2 + (size_t)r] = high;
+  }
+  return 0;
+}
+
 // The same check for the PARTITIONED layout of incremental updates: the triangles are cut into `partCount` consecutive ranges, every range gets its own
 // subtree in its own node range, and a top tree over the subtree roots (buildTopBvh8) joins them.  Returns the violations of the assembled tree.
 extern "C" int giCDebugValidatePartitionedBvh(const float* triVerts, uint32_t triCount, uint32_t partCount, uint32_t* outNodeCount, uint32_t* outMaxDepth)
@@ -687,6 +749,18 @@ extern "C" int giCDebugPathRingStats(const GiCScene* scene, uint64_t* out)
   if (!s || !out) { setError("giCDebugPathRingStats: bad arguments"); return GI_C_ERROR; }
   std::lock_guard<std::mutex> guard(s->mutex);
   for (int k = 0; k < 5; k++) out[k] = s->pathRingStats[k];
+  return GI_C_OK;
+}
+
+// giCDebugTraversalStackHigh: how full the per-lane traversal stack got in the last render of a counting build (Counters::stackHigh of the primary device, raised
+// by the COUNT instantiations of k_path, k_trace and k_trace_dyn: gi_traversal.h trav_node), the rows of the variant that ran and the spill entries used.  All
+// zero after a render that did not count.
+extern "C" int giCDebugTraversalStackHigh(const GiCScene* scene, uint32_t* out)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!s || !out) { setError("giCDebugTraversalStackHigh: bad arguments"); return GI_C_ERROR; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  for (int k = 0; k < 4; k++) out[k] = s->traversalStackHigh[k];
   return GI_C_OK;
 }
 

@@ -293,6 +293,9 @@ struct SceneDevice {
   uint64_t pathWalkStats[18] = {}; // giCDebugPathWalkStats: k_path's trips and walk-step tables of the last render (counting builds; fillStats)
   uint64_t pathLobeStats[9] = {};  // giCDebugPathLobeStats: Counters::lobeStats of the last render (counting builds; fillStats)
   uint64_t pathRingStats[5] = {};  // giCDebugPathRingStats: Counters::ringStats of the last render (counting builds; fillStats)
+  // giCDebugTraversalStackHigh: Counters::stackHigh of the last render, the stack rows of the traversal variant it ran and the scratch-spill entries its
+  // walks used at most (counting builds; fillStats)
+  uint32_t traversalStackHigh[4] = {};
   std::vector<hipEvent_t> eventPool;
   // the resizable path state (what the memory plan of a render sizes: slots, media, sampleBuf, the queues) -- the ONE list of these buffers
   template <typename Fn> void forEachPathBuffer(Fn&& fn)

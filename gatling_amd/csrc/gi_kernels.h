@@ -40,6 +40,9 @@ uint32_t blocksPerCuByLds(uint32_t dynamicBytes, uint32_t staticBytes);
 uint32_t traceStaticLdsBytes(); // static LDS of the traversal kernels on top of traceLdsLayout's dynamic bytes
 // what one k_trace block stages of this scene and the dynamic LDS bytes it needs for it
 void traceLdsLayout(const SceneView& sc, uint32_t& ldsNodes, uint32_t& ldsTris, uint32_t& bytes);
+// the per-lane stack rows of the traversal kernel launchTrace picks for this scene (k_trace: 4 or 8; k_trace_dyn: 8, 12 or 16; k_trace_dyn2: 16) and whether
+// that variant spills entries beyond its rows to scratch (gi_traversal.h OVF_STACK)
+uint32_t traceStackRows(const SceneView& sc, bool& spills);
 void launchTrace(hipStream_t s, uint32_t blocks, bool anyHit, bool count, const SceneView& sc, const PathState& st, const QueueSet& qs, Counters* cnt,
                  uint32_t qIn, uint32_t qMiss, uint32_t dynRefill, uint32_t routeBlocks, const FrameUniforms& U, F4* sampleBuf);
 void launchRoute(hipStream_t s, uint32_t blocks, const SceneView& sc, const PathState& st, const QueueSet& qs, Counters* cnt, uint32_t qIn, uint32_t qMiss,

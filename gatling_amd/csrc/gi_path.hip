@@ -76,7 +76,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
   bool alive = false, tAlive = false; // tAlive outlives a trip: a lane still walking when the closest-hit loop ends early is carried into the next one
   uint32_t chunkNext = 0u, chunkEnd = 0u; bool exhausted = false; // wave-uniform: the claimed work items not handed out yet
   uint32_t nSeg = 0u, nShadow = 0u;
-  TraceCounters tc{0u, 0u}, tcs{0u, 0u};
+  WalkCounters<COUNT> tc{}, tcs{};
   uint2 overflow[1];
   RayTrav R; R.G = make_uint2(0u, 0u); R.sp = 0u;
   // Camera rays are generated 64 at a time, by ALL lanes, into a per-wave LDS ring (r03): a trip regenerates only the ~45 % of the lanes whose path just ended,
@@ -406,6 +406,14 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
     if (NEE) atomicAdd(&cnt->shadowRays, b);
     if (COUNT) { atomicAdd(&cnt->nodesVisited, c); atomicAdd(&cnt->trisTested, d); atomicAdd(&cnt->shadowNodesVisited, e); atomicAdd(&cnt->shadowTrisTested, f);
         }
+  }
+  if constexpr (COUNT) { // Counters::stackHigh: the fullest stack of any lane's walks
+    uint32_t hc = tc.high, hs = tcs.high;
+    for (int off = 32; off > 0; off >>= 1) {
+      const uint32_t oc = (uint32_t)__shfl_down((int)hc, off), os = (uint32_t)__shfl_down((int)hs, off);
+      hc = oc > hc ? oc : hc; hs = os > hs ? os : hs;
+    }
+    if (lane == 0u) { atomicMax(&cnt->stackHigh[0], hc); if (NEE) atomicMax(&cnt->stackHigh[1], hs); }
   }
 }
 

@@ -445,6 +445,7 @@ struct Frame {
   FrameUniforms U{}; SceneView view{};
   PathPlan plan; PathState ps{}; QueueSet qs{}; Schedule sch;
   F4* colorOut = nullptr;
+  bool stackHighCounted = false; // this render zeroed Counters::stackHigh and ran walks that raise it (traceColour)
   uint32_t numBatches = 0;
   uint32_t iters = 0, traceLaunches = 0; // GiCRenderStats::iterations / traceLaunches
   double tStart = 0.0;
@@ -782,6 +783,7 @@ static void fillStats(const Frame& f, double tEnd)
   for (int k = 0; k < 18; k++) W[k] = 0u;
   for (int k = 0; k < 9; k++) f.D.pathLobeStats[k] = 0u; // giCDebugPathLobeStats, likewise
   for (int k = 0; k < 5; k++) f.D.pathRingStats[k] = 0u; // giCDebugPathRingStats, likewise
+  for (int k = 0; k < 4; k++) f.D.traversalStackHigh[k] = 0u; // giCDebugTraversalStackHigh, likewise
   if (f.served) { // nothing was launched but the fold: the counters on the device are still those of the call that traced the window
     S.fusedPath = S.batches = S.poolSlots = 0u;
     S.segments = S.shadowRays = S.nodesVisited = S.trisTested = S.shadowNodesVisited = S.shadowTrisTested = 0u;
@@ -793,6 +795,13 @@ static void fillStats(const Frame& f, double tEnd)
   W[0] = c.phaseTrips; W[17] = c.walkFewLaneSteps;
   for (int k = 0; k < 9; k++) f.D.pathLobeStats[k] = c.lobeStats[k];
   for (int k = 0; k < 5; k++) f.D.pathRingStats[k] = c.ringStats[k];
+  if (f.stackHighCounted) {
+    bool spills = false;
+    const uint32_t rows = f.plan.fused ? pathLotPlacement(f.view.bvhDepth).stack : traceStackRows(f.view, spills);
+    const uint32_t high = std::max(c.stackHigh[0], c.stackHigh[1]);
+    uint32_t* H = f.D.traversalStackHigh;
+    H[0] = c.stackHigh[0]; H[1] = c.stackHigh[1]; H[2] = rows; H[3] = spills && high > rows ? high - rows : 0u;
+  }
   for (int k = 0; k < 8; k++) { W[1 + k] = c.walkStepTrips[k]; W[9 + k] = c.walkStepLanes[k]; }
 }
 
@@ -961,6 +970,10 @@ static int traceColour(Frame& f, const BoundAovs& aov, const LookaheadPlan& la)
     const uint32_t poolNow = (uint32_t)std::min<uint64_t>(f.plan.slots, U.workTotal);
     U.poolSlots = poolNow;
     launchInit(st, f.ps, f.qs, D.dCounters.ptr, f.plan.fused ? 0u : poolNow, batch == 0);
+    if (batch == 0 && s->countTraversal) { // (Counters::stackHigh is not k_init's to zero: that kernel is shared with the builds that do not count)
+      HIP_TRY(hipMemsetAsync(D.dCounters.ptr->stackHigh, 0, sizeof(Counters::stackHigh), st));
+      f.stackHighCounted = U.maxBounces != 0u;
+    }
     const int rc = U.maxBounces == 0u ? runZeroBounceBatch(f, batch) : f.plan.fused ? runFusedBatch(f, batch) : runWavefrontBatch(f, batch, poolNow);
     if (rc != GI_C_OK) return rc;
   }

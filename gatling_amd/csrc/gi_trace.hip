@@ -39,6 +39,14 @@ static __device__ __forceinline__ void trace_counters_flush(Counters* cnt, const
   for (int off = 32; off > 0; off >>= 1) { a += __shfl_down(a, off); b += __shfl_down(b, off); }
   if (__lane_id() == 0) { atomicAdd(ANYHIT ? &cnt->shadowNodesVisited : &cnt->nodesVisited, a); atomicAdd(ANYHIT ? &cnt->shadowTrisTested : &cnt->trisTested, b); }
 }
+// ... and the fullest stack of any lane's walks (Counters::stackHigh)
+template <bool ANYHIT>
+static __device__ __forceinline__ void trace_high_flush(Counters* cnt, const TraceCountersHigh& tc)
+{
+  uint32_t h = tc.high;
+  for (int off = 32; off > 0; off >>= 1) { const uint32_t o = (uint32_t)__shfl_down((int)h, off); h = o > h ? o : h; }
+  if (__lane_id() == 0) atomicMax(&cnt->stackHigh[ANYHIT ? 1 : 0], h);
+}
 
 template <bool ANYHIT, bool COUNT, uint32_t STACK, bool CUTOUT, bool DOME>
 __global__ __launch_bounds__(TRACE_BLOCK) void k_trace(SceneView sc, PathState st, QueueSet qs, Counters* cnt, uint32_t qIn, uint32_t qMiss, uint32_t ldsNodes,
@@ -54,7 +62,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace(SceneView sc, PathState s
   // dynamic LDS, sized by the launch to what this scene actually stages
   const StagedScene S = stage_scene<STACK>(sc, ldsNodes, ldsTris);
 
-  TraceCounters tc{0u, 0u};
+  WalkCounters<COUNT> tc{};
   RayTrav R; trav_init(R, v3(0.0f, 0.0f, 0.0f), v3(0.0f, 0.0f, 1.0f), 0.0f, 0.0f);
   uint2 overflow[1];
   const uint32_t stride = gridDim.x * TRACE_BLOCK;
@@ -123,6 +131,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace(SceneView sc, PathState s
     }
   }
   if (COUNT) trace_counters_flush<ANYHIT>(cnt, tc);
+  if constexpr (COUNT) trace_high_flush<ANYHIT>(cnt, tc);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -178,7 +187,7 @@ __device__ __forceinline__ void trace_dyn_body(const SceneView& sc, const PathSt
   const uint32_t lane = __lane_id();
   const uint32_t cap = qs.cap;
   PaddedCounter* cursors = cnt->cursor[ANYHIT ? 1 : 0];
-  TraceCounters tc{0u, 0u};
+  WalkCounters<COUNT> tc{};
   typename DynRay<TWO>::type R;
   auto ray_init = [&](V3 o, V3 d, float tMin, float tMax) { if constexpr (TWO) trav2_init(R, o, d, tMin, tMax); else walk_init(R, o, d, tMin, tMax); };
   ray_init(v3(0.0f, 0.0f, 0.0f), v3(0.0f, 0.0f, 1.0f), 0.0f, 0.0f);
@@ -391,6 +400,7 @@ __device__ __forceinline__ void trace_dyn_body(const SceneView& sc, const PathSt
     trace_counters_flush<ANYHIT>(cnt, tc);
     if (!ANYHIT && !TWO && lane == 0) for (int k = 0; k < 8; k++) atomicAdd(&cnt->dynStats[k], ds[k]);
   }
+  if constexpr (COUNT && !TWO) trace_high_flush<ANYHIT>(cnt, tc); // (wave_step2 keeps no such count)
 }
 
 #undef key
@@ -463,6 +473,17 @@ void traceLdsLayout(const SceneView& sc, uint32_t& ldsNodes, uint32_t& ldsTris, 
   bytes = traceLdsBytes(traceStackEntries(sc), ldsNodes, ldsTris);
   // (+ the kernels' static LDS: WaveTri per wave and the append scratch, see traceStaticLdsBytes)
 }
+// the rule launchTrace dispatches by (and what giCDebugTraversalStackHigh reports as the rows of the variant that ran)
+uint32_t traceStackRows(const SceneView& sc, bool& spills)
+{
+  spills = false;
+  if (traceBlockSync(sc)) return traceStackEntries(sc); // k_trace
+  if (sc.twoLevel) return 16u;                          // k_trace_dyn2
+  if (sc.bvhDepth <= 8u) return 8u;
+  if (sc.bvhDepth <= 12u) return 12u;
+  spills = sc.bvhDepth > 16u; // trees deeper than 16 levels spill the rest to scratch
+  return 16u;
+}
 // U / sampleBuf: the frame's uniforms and per-sample colour buffer -- read only when the queue holds camera rays flagged TRACE_FRESH (FLAG_DEFER_SLOT)
 void launchTrace(hipStream_t s, uint32_t blocks, bool anyHit, bool count, const SceneView& sc, const PathState& st, const QueueSet& qs, Counters* cnt,
                  uint32_t qIn, uint32_t qMiss, uint32_t dynRefill, uint32_t routeBlocks, const FrameUniforms& U, F4* sampleBuf)
@@ -494,11 +515,12 @@ void launchTrace(hipStream_t s, uint32_t blocks, bool anyHit, bool count, const 
       }, ANYHIT && (refill & DYN_SLOT_ORDER) != 0u);
     };
     using std::integral_constant;
+    bool spills; const uint32_t rows = traceStackRows(sc, spills);
     if (sc.twoLevel) // instanced scene: TLAS + shared per-mesh BLASes
       hipLaunchKernelGGL((k_trace_dyn2<ANYHIT, COUNT, CUTOUT>), dim3(blocks), dim3(TRACE_BLOCK), traceLdsBytes(16u, 0u, 0u), s, sc, st, qs, cnt, qIn, refill);
-    else if (sc.bvhDepth <= 8u) dyn(integral_constant<uint32_t, 8u>{}, std::false_type{});
-    else if (sc.bvhDepth <= 12u) dyn(integral_constant<uint32_t, 12u>{}, std::false_type{});
-    else if (sc.bvhDepth <= 16u) dyn(integral_constant<uint32_t, 16u>{}, std::false_type{});
+    else if (rows == 8u) dyn(integral_constant<uint32_t, 8u>{}, std::false_type{});
+    else if (rows == 12u) dyn(integral_constant<uint32_t, 12u>{}, std::false_type{});
+    else if (!spills) dyn(integral_constant<uint32_t, 16u>{}, std::false_type{});
     else dyn(integral_constant<uint32_t, 16u>{}, std::true_type{});
     if (!ANYHIT) launchRoute(s, routeBlocks, sc, st, qs, cnt, qIn, qMiss, U, sampleBuf);
   }, anyHit, count, sc.hasCutouts != 0u);

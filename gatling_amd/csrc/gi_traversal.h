@@ -25,6 +25,13 @@ constexpr uint32_t OVF_STACK = 40;   // scratch overflow entries of the fallback
 constexpr uint32_t TRACE_BLOCK = 256;
 
 struct TraceCounters { uint32_t nodes, tris; };
+// What a COUNT instantiation keeps per lane: `high`, the most stack entries a walk of the lane held -- R.sp after a push (Counters::stackHigh).  A type of its
+// own, and not a third field of TraceCounters: a field no instruction reads still moved the register allocation of the kernels that do not count.  The kernels
+// declare WalkCounters<COUNT> and the walk functions take it; the triangle batches see its TraceCounters part.
+struct TraceCountersHigh : TraceCounters { uint32_t high; };
+template <bool COUNT> struct WalkCountersOf { using type = TraceCounters; };
+template <> struct WalkCountersOf<true> { using type = TraceCountersHigh; };
+template <bool COUNT> using WalkCounters = typename WalkCountersOf<COUNT>::type;
 
 // What a block keeps in its dynamic LDS, [stack | nodes | triangles]: the per-lane traversal stacks and the part of the scene staged beside them (the launch
 // sizes it: traceLdsBytes in gi_kernels.h).  A node below ldsNodes / a triangle below ldsTris is read from LDS, the others from global memory.
@@ -205,13 +212,14 @@ __device__ __forceinline__ void node_load(const SceneView& sc, uint32_t nodeIdx,
 // The per-lane composition (each lane fetches its own node: from LDS when staged there, else from global memory)
 template <bool COUNT, uint32_t STACK, bool OVERFLOW, Staged STAGED, bool ORDERED = true>
 __device__ __forceinline__ uint2 trav_node(RayWalk& R, const SceneView& sc, StagedScene S, uint2 (&overflow)[OVERFLOW ? OVF_STACK : 1],
-                                           TraceCounters& tc)
+                                           WalkCounters<COUNT>& tc)
 {
   const uint32_t nodeIdx = trav_node_pick<STACK, OVERFLOW, ORDERED>(R, S.stack, overflow);
   uint4 n0, n1, n2, n3, n4;
   if (STAGED == STAGED_ALL || (STAGED == STAGED_SOME && nodeIdx < S.ldsNodes)) { const uint4* p = S.nodes + nodeIdx * 5u; n0 = p[0]; n1 = p[1]; n2 = p[2]; n3 = p[3]; n4 = p[4]; }
   else node_load(sc, nodeIdx, n0, n1, n2, n3, n4);
   if (COUNT) tc.nodes++;
+  if constexpr (COUNT) tc.high = R.sp > tc.high ? R.sp : tc.high;
   return trav_node_test<false, ORDERED>(R, n0, n1, n2, n3, n4);
 }
 
@@ -247,7 +255,7 @@ __device__ __forceinline__ bool tri_test(V3 o, V3 d, float tMin, const uint4& a,
 // Advances the ray by one group (node, then its leaf triangles one after the other, then pop); returns true when the
 // traversal is finished.  The per-lane form used by k_aov.
 template <bool ANYHIT, bool COUNT, uint32_t STACK, bool OVERFLOW, Staged STAGED, bool CUTOUT>
-__device__ __forceinline__ bool trav_step(RayTrav& R, const SceneView& sc, StagedScene S, uint2 (&overflow)[OVERFLOW ? OVF_STACK : 1], TraceCounters& tc,
+__device__ __forceinline__ bool trav_step(RayTrav& R, const SceneView& sc, StagedScene S, uint2 (&overflow)[OVERFLOW ? OVF_STACK : 1], WalkCounters<COUNT>& tc,
                                           uint32_t rng)
 {
   uint2 Gt;
@@ -397,7 +405,7 @@ __device__ __forceinline__ uint32_t wave_scan_inclusive(uint32_t v)
 // control flow; lanes without a ray (alive == false) only help testing triangles.  Returns true when this lane's ray is finished.
 template <bool ANYHIT, bool COUNT, uint32_t STACK, bool OVERFLOW, Staged STAGED, bool CUTOUT>
 __device__ __forceinline__ bool wave_step(RayTrav& R, bool alive, WaveTri& W, const SceneView& sc, StagedScene S,
-                                          uint2 (&overflow)[OVERFLOW ? OVF_STACK : 1], TraceCounters& tc, uint32_t rng)
+                                          uint2 (&overflow)[OVERFLOW ? OVF_STACK : 1], WalkCounters<COUNT>& tc, uint32_t rng)
 {
   const uint32_t lane = __lane_id();
   uint2 Gt = make_uint2(0u, 0u);
@@ -463,7 +471,7 @@ __device__ __forceinline__ void wave_ring_batch(WaveTri& W, uint32_t& pend, uint
 }
 // node phase, append, the full batches, pop; returns true when this lane's walk has ended (its R.tBest / R.found: wave_ring_refresh, after the flush)
 template <bool COUNT, uint32_t STACK, Staged STAGED, bool CUTOUT>
-__device__ __forceinline__ bool wave_step_ring(RayTrav& R, bool alive, WaveTri& W, const SceneView& sc, StagedScene S, uint2 (&overflow)[1], TraceCounters& tc,
+__device__ __forceinline__ bool wave_step_ring(RayTrav& R, bool alive, WaveTri& W, const SceneView& sc, StagedScene S, uint2 (&overflow)[1], WalkCounters<COUNT>& tc,
                                                uint32_t rng, uint32_t& pend, RingStats& rs)
 {
   const uint32_t lane = __lane_id();
@@ -518,7 +526,7 @@ __device__ __forceinline__ void wave_ray_end(WaveTri& W, RayTrav& R)
 
 template <bool ANYHIT, bool COUNT, uint32_t STACK, bool OVERFLOW, Staged STAGED, bool CUTOUT>
 __device__ __forceinline__ bool traverse(const SceneView& sc, StagedScene S, V3 o, V3 d, float tMin, float tMax, float& outT, float& outU, float& outV,
-                                         uint32_t& outTri, uint32_t& outMat, TraceCounters& tc, uint32_t rng = 0u)
+                                         uint32_t& outTri, uint32_t& outMat, WalkCounters<COUNT>& tc, uint32_t rng = 0u)
 {
   RayTrav R; trav_init(R, o, d, tMin, tMax);
   uint2 overflow[OVERFLOW ? OVF_STACK : 1];

@@ -361,6 +361,10 @@ struct Counters {
   // k_path, counting builds only (giCDebugPathRingStats): the triangle ring of the closest-hit loops -- [0] batches, [1] (ray, triangle) pairs tested in them,
   // [2] batches of fewer than 64 pairs, [3] end-of-loop flushes (ring carry on: gi_path.hip), [4] steps whose pairs were appended by ballot rounds
   unsigned long long ringStats[5];
+  // k_path, k_trace, k_trace_dyn, counting builds only (giCDebugTraversalStackHigh): the most traversal-stack entries a walk held -- the stack pointer after a
+  // push, maximum over every walk of the render -- [0] closest-hit walks, [1] shadow walks.  The host zeroes it before a counting render's first batch (k_init
+  // is not touched: it is shared with the builds that do not count).  Last, so that every other counter keeps its offset.
+  uint32_t stackHigh[2];
 };
 
 } // namespace gi

@@ -385,7 +385,7 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * giCDebugBlasRefitHost, and for GI_C_SCENE_OPTION_TLAS_VISIBILITY, giCDebugSceneTlasVisibilityUpdateCount, giCDebugSceneFlatIdCheck and
  * giCDebugPatchVisibilityTwoLevel, and for GI_C_SCENE_OPTION_TLAS_ONLY and giCDebugSceneFlatTreeState, and for GI_C_SCENE_OPTION_TLAS_TOPOLOGY,
  * giCDebugSceneTlasTopologyUpdateCount, giCDebugAppendRecords and giCDebugAppendRecordsHost, and for GI_C_SCENE_OPTION_TLAS_INSTANCES,
- * giCDebugSceneTlasInstanceUpdateStats, giCDebugInstanceRecords and giCDebugInstanceRecordsHost. */
+ * giCDebugSceneTlasInstanceUpdateStats, giCDebugInstanceRecords and giCDebugInstanceRecordsHost, and for giCDebugTraversalStackHigh and giCDebugBvhStackReach. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -709,6 +709,12 @@ int64_t giCDebugCheckDiv(uint32_t mode, uint64_t count, uint32_t seed, const uin
  * texture; per result 4 floats. */
 int giCDebugTexRuntime(const float* rgba, uint32_t width, uint32_t height, uint32_t depth, uint32_t count, const float* queries, float* out);
 int giCDebugValidateBvh(const float* triVerts, uint32_t triCount, uint32_t* outNodeCount, uint32_t* outMaxDepth);
+/* [ext] host-only walk for designing test scenes: builds the BVH8 over the `triCount` triangles of `triVerts` (9 floats each) as giCDebugValidateBvh does and runs
+ * the traversal kernels' ordered walk (a node's hit internal children in octant-flipped slot order, nearest first, the rest pushed) for `rayCount` rays
+ * (origins / dirs: 3 floats each), boxes only.  out[0] = levels of the tree, out[1] = nodes, out[2 + i] = the most stack entries the walk of ray i holds.
+ * Nothing is culled -- no triangle is tested, every internal child whose box the ray meets counts --, so out[2 + i] is an UPPER BOUND on what a device walk of
+ * that ray holds (exact for a ray that hits no triangle); the proof that a render filled a stack is giCDebugTraversalStackHigh.  Returns 0, <0 on error. */
+int giCDebugBvhStackReach(const float* triVerts, uint32_t triCount, const float* origins, const float* dirs, uint32_t rayCount, uint32_t* out /* 2 + rayCount */);
 /* [ext] the same host-only check for the partitioned layout incremental transform updates use: `partCount` consecutive triangle ranges, one
  * subtree each, joined by a top tree over the subtree roots.  Returns the violations of the assembled tree (0 = every triangle reachable and inside every
  * ancestor slot's box), <0 on error. */
@@ -891,6 +897,15 @@ int giCDebugPathLobeStats(const GiCScene* scene, uint64_t* out /* 9 */);
  * $GATLING_OPTIONS ring_carry=1 set explicitly a counting build carries the ring across the steps of a trip as other builds do: partial batches then happen in
  * flushes only, at most one per trip.  With ring_carry=0 or the key absent every step ends with the ring empty and [3] is zero; the image is the same. */
 int giCDebugPathRingStats(const GiCScene* scene, uint64_t* out /* 5 */);
+/* [ext] how full the per-lane traversal stack got in the scene's last render, for renders with GI_C_SCENE_OPTION_COUNT_TRAVERSAL (all zero otherwise): out[0] the
+ * most entries a closest-hit walk held -- the stack pointer after a push, maximum over every walk of the render --, [1] the same for the shadow walks, [2] the
+ * stack rows of the traversal variant that ran (the fused path kernel and the LDS-resident trace kernel: 4 or 8; the persistent trace kernel: 8, 12 or 16),
+ * [3] the entries that went to the scratch spill at most (trees deeper than 16 levels; else 0).  A walk pushes at most one entry per tree level below the
+ * root, so [0] and [1] never exceed that depth.  Only [0] and [1] are counted on the device; [2] and [3] are DERIVED on the host from the rule the launch
+ * dispatches by and from [0] / [1], not reported by the kernel that ran.  The primary device's walks only: on a scene spread over several devices the
+ * other devices' shares are not in the maximum.  Counted by the fused path kernel and the two flat trace kernels; the two-level walk and the AOV kernel have no
+ * such counter ([0] and [1] stay 0 for a two-level scene). */
+int giCDebugTraversalStackHigh(const GiCScene* scene, uint32_t* out /* 4 */);
 /* [ext] where the fused path kernel keeps parked hits for a BVH8 of `bvhDepth` levels below the root: out[0] traversal-stack rows per lane, [1] the first row
  * no walk reaches, [2] the records that fit in the rows from there on (0: parking is off for such a tree), [3] the dynamic LDS bytes of a launch for a scene of
  * nodeCount nodes and triCount triangles -- the rows and nothing else: parked hits add no LDS.  Host only: no device work, no scene. */

@@ -6,7 +6,8 @@ Scenes (all LDS-resident):
   B             cornell with the three classes mixed, a stochastic cutout (opacity 0.4) on the white material and a textured colour + textured opacity on the red
                 wall: the general variant, 4-entry stack
   C / C1        the telescope of tests/test_gpu_path_walk_carry.py (100 triangles, ratio 1.1, a tree of 7 levels) as two meshes, every other triangle with a
-                cutout material: the general variant, 8-entry stack.  C1 is C through the camera of the 33 x 1 frame (a slice along the telescope's axis)
+                cutout material: the general variant, 8-entry stack -- how full is not counted here (the host walk of test_deep_trees_parity's ray bundle over this tree
+                holds 2 entries, tests/test_stack_fill_host.py; the stack is filled in tests/test_gpu_stack_fill.py).  C1 is C through the camera of the 33 x 1 frame (a slice along the telescope's axis)
   D / D1        a cluster of 6 quads (12 triangles) right of the view axis.  D at 32 x 18: a miss rectangle 2 .. 20 columns wide.  D1 at 1 x 36: activeWidth == 1.
                 Twelve triangles fit one BVH8 node, so every walk there is ONE step and no lane can be carried; D2 / D3 are the same cluster and cameras with
                 14 quads (28 triangles, a root with three child nodes) for the cases that claim carried lanes under a narrow rectangle.
@@ -25,7 +26,7 @@ Axes (a Case's fields, in order):
 
 The table covers every pair of axis values at least once per kernel family (test_path_matrix_inputs.py checks that and prints the coverage), holds one "many trips"
 case (96 x 54, spp 8) per kernel variant the scenes select (A1 .. A3, B, C with NEE off and on: ten of the twenty instantiations; no scene here is one class
-over a tree deeper than four levels, so the six hot stack-8 instantiations have no case, and the counting ones run in the carry proofs), and the combinations
+over a tree deeper than four levels, so the six hot stack-8 instantiations have no case here -- tests/test_gpu_stack_fill.py runs them --, and the counting ones run in the carry proofs), and the combinations
 marked NAMED.
 
 work_order is INERT in the fused kernel: gi_render.cpp reads it for the wavefront pipeline only, k_path always hands work out sample-major.  The axis is here

@@ -939,7 +939,8 @@ def _telescope(n, ratio):
 @pytest.mark.parametrize("n,ratio", [(100, 1.1), (120, 1.2), (400, 1.03), (2000, 1.006), (400, 1.2)])
 def test_deep_trees_parity(gi, orc, n, ratio):
     """Trees deeper than BASELINE's scenes give (host-side depth 7 / 13 / 11 / 12 / 39): 100 triangles run the fused kernels with the 8-entry
-    stack nearly full, 120 triangles an LDS-resident tree too deep for them and for k_trace (k_trace_dyn + k_route, 12 entries), 400 and 2000
+    stack (of which the ray bundle below holds 2 entries by the host walk, an upper bound; the render's rays are not walked: a deep tree is not a full stack -- tests/test_stack_fill_host.py has the host walk's
+    figures for all five cases, 2 / 2 / 8 / 8 / 7 entries, and tests/test_gpu_stack_fill.py the scenes that do fill each stack), 120 triangles an LDS-resident tree too deep for them and for k_trace (k_trace_dyn + k_route, 12 entries), 400 and 2000
     the 16-entry stack, the last case the deepest
     tree the builder produces here (16 entries + overflow) -- images with shadow rays, and random rays, against the oracle.
     The 120-triangle case and the last one are compared by image only: their triangles shrink to 3e-10 and 1e-32 at the origin, and a ray that passes within float resolution of

@@ -77,7 +77,8 @@ def _telescope(n, ratio):
 
 
 def test_tree_deeper_than_four_levels(gi, orc, monkeypatch):
-    """The 8-entry-stack instantiation: a carried lane's stack column holds up to seven entries across the trip boundary.  64x36, spp 4."""
+    """The 8-entry-stack instantiation: a carried lane's stack column holds its entries across the trip boundary.  How many is not counted here: the host walk of
+    test_deep_trees_parity's ray bundle, another ray family over this tree, holds 2 at most (tests/test_stack_fill_host.py), the tree's depth allows six; tests/test_gpu_stack_fill.py carries walks with the stack full.  64x36, spp 4."""
     _check(gi, orc, monkeypatch, _telescope(100, 1.1), RenderSettings(spp=4, max_bounces=4, progressive_accumulation=False), 64, 36, "telescope 64x36 spp 4")
 
 
