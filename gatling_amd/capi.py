@@ -34,6 +34,7 @@ OPTION_TLAS_VISIBILITY = 18  # 1: visibility edits of a built two-level scene ar
 OPTION_TLAS_ONLY = 19  # 1: a scene that takes the two-level layout (OPTION_TWO_LEVEL 1, or 2^26 flattened triangles) is built without the flat BVH8 -- the flat records stay in scene order, the non-colour AOVs walk the TLAS (k_aov2), the scene bounds come from the instance boxes and the edits in place of options 16 - 18 run without the flat refit; read at the scene build only (include/gi_c.h); 0 = off (default)
 OPTION_TLAS_TOPOLOGY = 20  # 1: mesh creations and destructions on a built two-level scene without the flat tree (OPTION_TLAS_ONLY) are applied to the resident scene -- a destroyed mesh retired as a hidden one, a created mesh appended: one BLAS from the host, its shading records, BLAS triangles, flat records, face ids and id-table words made on the device (gi_append.hip) -- instead of rebuilding it; read only with OPTION_TOPOLOGY_UPDATES wanted (include/gi_c.h); 0 = off (default)
 OPTION_TLAS_INSTANCES = 21  # 1: instance-id and instance-count edits of built meshes on a built two-level scene without the flat tree (OPTION_TLAS_ONLY) are applied to the resident scene -- retired instances hidden and their storage slots reused by later grows of the same mesh, new instances' flat records made on the device in one launch (gi_instances.hip) -- instead of rebuilding it; read only with OPTION_TOPOLOGY_UPDATES, OPTION_INSTANCE_UPDATES and OPTION_TLAS_TOPOLOGY wanted (include/gi_c.h); 0 = off (default)
+OPTION_TLAS_DEVICE_BUILD = 22  # 1: the edits in place of a two-level scene (options 16 - 18, 20, 21) build their TLAS on the primary device (gi_tlas_build.hip: Morton sort, PLOC, depth-bounded cost-optimal collapse) instead of with the host builder, which remains the fallback; read only where such an edit is applied (include/gi_c.h); 0 = off (default)
 OPTION_BVH_BUILD = 9  # 0 = host BVH builder (default), 1 = device builder (flat-layout scenes of more than 128 triangles)
 
 
@@ -192,6 +193,9 @@ SYMBOLS = [
     ("giCDebugInstanceRecords", C.c_int, [_P, _U, _P, _U]),
     ("giCDebugInstanceRecordsHost", C.c_int, [_P, _U, _P, _U]),
     ("giCDebugSceneTlasInstanceUpdateStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("giCDebugBuildTlasHost", C.c_int, [_FP, _U, _U, _U, C.POINTER(C.c_double)]),
+    ("giCDebugBuildTlas", C.c_int, [_FP, _U, _U, _U, C.POINTER(C.c_double)]),
+    ("giCDebugSceneTlasBuildStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugPatchVisibilityTwoLevel", C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _U, _U, C.POINTER(C.c_uint32)]),
     ("giCDebugPathWalkStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugPathLobeStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
@@ -284,6 +288,26 @@ def debug_clone_instance(vertices, faces, xform_a, xform_b, left_handed=False) -
     if n < 0:
         raise GiError("giCDebugCloneInstance refused the mesh or a transform")
     return int(n)
+
+
+TLAS_BUILD_TOO_DEEP = -2  # GI_C_TLAS_BUILD_TOO_DEEP
+
+
+def debug_build_tlas(boxes, depth_budget=7, radius=16, host_only=False) -> dict:
+    """giCDebugBuildTlasHost (`host_only`: no device is used) / giCDebugBuildTlas: the TLAS builder of edits in place (OPTION_TLAS_DEVICE_BUILD) over `boxes`
+    (n x 6: min xyz, max xyz) with at most `depth_budget` levels and PLOC radius `radius`.  Returns {"violations": broken rules of the tree -- plus, for the
+    device builder, node and item records that differ bytewise from the host form's -- (0 is the contract), or TLAS_BUILD_TOO_DEEP; "nodes", "depth",
+    "passes", "cost" and "host_cost" (the SAH model cost of this tree and of the host builder's over the same boxes, by one function), "host_waits",
+    "host_depth", "active"}."""
+    L = load_library()
+    b = np.ascontiguousarray(boxes, np.float32).reshape(-1, 6)
+    out = (C.c_double * 8)()
+    fn = L.giCDebugBuildTlasHost if host_only else L.giCDebugBuildTlas
+    v = fn(b.ctypes.data_as(_FP), len(b), int(depth_budget), int(radius), out)
+    if v < 0 and v != TLAS_BUILD_TOO_DEEP:
+        raise GiError("giCDebugBuildTlas failed: " + L.giCGetLastError().decode())
+    return {"violations": int(v), "nodes": int(out[0]), "depth": int(out[1]), "passes": int(out[2]), "cost": float(out[3]), "host_cost": float(out[4]),
+            "host_waits": int(out[5]), "host_depth": int(out[6]), "active": int(out[7])}
 
 
 def debug_instance_bounds(vertices, faces, xforms):
@@ -633,6 +657,17 @@ class Scene:
         if self.L.giCDebugSceneTlasInstanceUpdateStats(self.handle, out) != GI_C_OK:
             raise GiError("giCDebugSceneTlasInstanceUpdateStats failed")
         return {"syncs": int(out[0]), "appended": int(out[1]), "reused": int(out[2]), "retired": int(out[3])}
+
+    def tlas_build_stats(self) -> dict:
+        """giCDebugSceneTlasBuildStats: the TLAS builds of edits in place under OPTION_TLAS_DEVICE_BUILD.  Returns {"device_builds", "too_deep", "out_of_memory",
+        "error", "under_min" (the four fallbacks to the host builder), "stage_us" (upload + boxes + sort, PLOC, emission, read-back of the last device build),
+        "passes", "host_waits", "depth", "nodes", "allocations", "resident_device_built", "budget"}.  All zero with the option off."""
+        out = (C.c_uint64 * 16)()
+        if self.L.giCDebugSceneTlasBuildStats(self.handle, out) != GI_C_OK:
+            raise GiError("giCDebugSceneTlasBuildStats failed")
+        return {"device_builds": int(out[0]), "too_deep": int(out[1]), "out_of_memory": int(out[2]), "error": int(out[3]), "under_min": int(out[4]),
+                "stage_us": [int(out[5 + k]) for k in range(4)], "passes": int(out[9]), "host_waits": int(out[10]), "depth": int(out[11]), "nodes": int(out[12]),
+                "allocations": int(out[13]), "resident_device_built": int(out[14]), "budget": int(out[15])}
 
     def flat_id_check(self, device: int = 0) -> "FlatIdCheck":
         """giCDebugSceneFlatIdCheck: the flat records, the id table and the per-instance records resident on a device -- the ids of visible records are a

@@ -436,6 +436,7 @@ int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vec
   }
   out.tlasNodes.swap(tlas.nodes); out.tlasItems.swap(tlasItems); out.blasNodes.swap(blasNodes); out.blasTris.swap(blasTris); out.instTrav.swap(instTrav);
   out.instBoxes.swap(instBoxes); out.meshBlasTri.swap(meshBlasTri); out.tlasDepth = tlas.maxDepth; out.blasDepth = blasDepth;
+  out.tlasDeviceBuilt = false; out.tlasBuildBudget = 0u; // (a build's TLAS is the host builder's)
   out.meshBlasNode.swap(meshBlasNode); out.meshBlasLevels.swap(meshBlasLevels);
   return GI_C_OK;
 }
@@ -1286,6 +1287,9 @@ static int updateVisibility(GiCScene* s, bool& handled, UpdateCost& cost)
 // While a mesh is hidden, updateTransformsTwoLevel and updateVerticesTwoLevel keep its instances out of the TLAS they build (planTwoLevelEdit) and decline an
 // edit OF the hidden mesh.
 // ---------------------------------------------------------------------------------------------------------------
+struct TlasMade { bool device = false; uint32_t budget = 0; }; // which builder made an edit's TLAS, and the device builder's depth budget
+static TlasMade buildEditTlas(GiCScene* s, uint32_t blasDepth, const float* masked, size_t count, Bvh8& tlas, std::vector<uint32_t>& items);
+static void noteTlasMade(TwoLevelHost& T, const TlasMade& made);
 static int updateVisibilityTwoLevel(GiCScene* s, SceneHost& H, bool& handled, UpdateCost& cost)
 {
   TwoLevelHost& T = H.two;
@@ -1303,12 +1307,12 @@ static int updateVisibilityTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Up
   std::vector<uint8_t> hiddenAfter(instanceCount, 0);
   for (const MeshBuild& mb : H.meshBuilds) if (plan.hide[mb.meshIdx]) for (const uint32_t inst : mb.inst) if (inst < instanceCount) hiddenAfter[inst] = 1;
   markFreeSlots(H.meshBuilds, hiddenAfter);
-  Bvh8 tlas; std::vector<uint32_t> tlasItems; double tlasMs = 0.0;
+  Bvh8 tlas; std::vector<uint32_t> tlasItems; double tlasMs = 0.0; TlasMade tlasMade;
   if (launch) {
     std::vector<float> masked(T.instBoxes);
     tlasMaskHiddenBoxes(masked.data(), hiddenAfter.data(), instanceCount);
     const double ta = nowMs();
-    buildBvh8Boxes(masked.data(), instanceCount, tlas, tlasItems);
+    tlasMade = buildEditTlas(s, T.blasDepth, masked.data(), instanceCount, tlas, tlasItems);
     tlasMs = nowMs() - ta;
     if (2u * tlas.maxDepth + T.blasDepth + 1u > 16u) {
       if (timing) fprintf(stderr, "[gatling_gi] visibility update (two-level): the new TLAS is too deep for the 16-entry stack; the scene is rebuilt\n");
@@ -1355,7 +1359,7 @@ static int updateVisibilityTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Up
     return rc;
   }) != GI_C_OK) return GI_C_ERROR;
   const size_t tlasNodeCount = launch ? tlas.nodes.size() : T.tlasNodes.size();
-  if (launch) { T.tlasNodes.swap(tlas.nodes); T.tlasItems.swap(tlasItems); T.tlasDepth = tlas.maxDepth; }
+  if (launch) { T.tlasNodes.swap(tlas.nodes); T.tlasItems.swap(tlasItems); T.tlasDepth = tlas.maxDepth; noteTlasMade(T, tlasMade); }
   // (without the flat tree the bounds are the visible instances' boxes: a show must widen them again where an edit in between narrowed them)
   if (launch && H.treeless) setSceneBoundsFromInstances(s, H);
   const double t2 = nowMs();
@@ -2218,7 +2222,7 @@ struct TwoLevelEdit {
   std::vector<float> boxes; Bvh8 tlas; std::vector<uint32_t> tlasItems; // all instance boxes with the jobs' new ones; the TLAS over them
   std::vector<uint32_t> editedOfInstance; std::vector<std::pair<uint32_t, uint32_t>> runs; // the jobs' instances: one word each; (first, count) of consecutive ones
   std::vector<RefitRange> ranges; std::vector<RefitLevel> levels; // the flat tree's refit
-  double tlasMs = 0.0;
+  double tlasMs = 0.0; TlasMade tlasMade;
 };
 struct FlatRefitScratch {
   DeviceBuffer<float> boxes; DeviceBuffer<uint32_t> edited; DeviceBuffer<RefitRange> ranges;
@@ -2261,6 +2265,49 @@ static int instanceBoundsOnPrimary(GiCScene* s, const std::vector<InstBoundsJob>
   });
 }
 
+// The TLAS of an edit in place over `masked` (the instance boxes, hidden / retired / free-slot instances masked): the ONE place the update paths of the
+// two-level layout build it.  With GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD wanted the primary device builds it (gi_tlas_build.hip) under the depth budget the
+// stack rule leaves beside BLASes of depth `blasDepth`, and the nodes and items are read back -- the caller decides and sends them to every device as it does
+// a host-built TLAS, so a decline leaves the scene untouched.  Under tlas_device_min instances, on a tree that does not fit the budget, out of memory or on an
+// error status the host builder runs instead (counted in GiCScene::tlasBuildStats): the edit never fails because of the option.
+static void noteTlasMade(TwoLevelHost& T, const TlasMade& made) { T.tlasDeviceBuilt = made.device; T.tlasBuildBudget = made.budget; } // (with the committed host copies)
+static TlasMade buildEditTlas(GiCScene* s, uint32_t blasDepth, const float* masked, size_t count, Bvh8& tlas, std::vector<uint32_t>& items)
+{
+  TlasMade made;
+  if (tlasDeviceBuildWanted(s)) {
+    uint64_t* stats = s->tlasBuildStats;
+    uint32_t budget = std::min(tlasDepthBudget(blasDepth), kTlasMaxBudget);
+    if (optionSet("tlas_depth_budget")) budget = std::min(budget, (uint32_t)std::max(optionValue("tlas_depth_budget", 0), 0L));
+    if ((long)count < optionValue("tlas_device_min", TLAS_DEVICE_MIN_DEFAULT)) stats[4]++;
+    else if (count > kTlasMaxItems) stats[3]++;
+    else {
+      const uint32_t radius = (uint32_t)std::min(std::max(optionValue("ploc_radius", 16), 1L), 256L);
+      TlasBuildInfo info; int rc = TLAS_BUILD_ERROR;
+      std::vector<Node8> nodes;
+      (void)onSceneDevices(s, 1u, [&](SceneDevice& D, hipStream_t st) -> int {
+        rc = buildTlasDevice(D.tlasWorkspace, st, masked, (uint32_t)count, budget, radius, nodes, items, info);
+        return GI_C_OK;
+      });
+      if (rc == TLAS_BUILD_OK) {
+        tlas = Bvh8{}; tlas.nodes.swap(nodes); tlas.maxDepth = info.maxDepth; tlas.activeTris = info.active;
+        stats[0]++;
+        for (int k = 0; k < 4; k++) stats[5 + k] = (uint64_t)(info.ms[k] * 1000.0f);
+        stats[9] = info.passes; stats[10] = info.hostWaits; stats[11] = info.maxDepth; stats[12] = info.nodeCount;
+        made.device = true; made.budget = budget;
+        if (getenv("GATLING_BUILD_TIMING")) fprintf(stderr, "[gatling_gi] device TLAS build: %zu boxes, %u node(s), depth %u of %u, %u PLOC pass(es), %u host wait(s); upload + "
+            "boxes + sort %.3f ms, PLOC %.3f ms, emission %.3f ms, read-back %.3f ms\n", count, info.nodeCount, info.maxDepth, budget, info.passes, info.hostWaits,
+            info.ms[0], info.ms[1], info.ms[2], info.ms[3]);
+        return made;
+      }
+      stats[rc == TLAS_BUILD_TOO_DEEP ? 1 : rc == TLAS_BUILD_OUT_OF_MEMORY ? 2 : 3]++;
+      if (getenv("GATLING_BUILD_TIMING")) fprintf(stderr, "[gatling_gi] device TLAS build: %s; the host builder runs\n", rc == TLAS_BUILD_TOO_DEEP ?
+          "the tree does not fit the depth budget" : rc == TLAS_BUILD_OUT_OF_MEMORY ? "out of device memory" : info.error);
+    }
+  }
+  buildBvh8Boxes(masked, count, tlas, items);
+  return made;
+}
+
 // boxes -> TLAS -> decision -> the flat refit's plan.  False: the edit declines (every job's instance must be usable; the TLAS over all boxes must stay
 // within the stack rule)
 static bool planTwoLevelEdit(const GiCScene* s, const SceneHost& H, const std::vector<InstBoundsJob>& jobs, const std::vector<uint32_t>& result, const char* what,
@@ -2279,11 +2326,12 @@ static bool planTwoLevelEdit(const GiCScene* s, const SceneHost& H, const std::v
   const double t1 = nowMs();
   { // the instances of meshes updateVisibilityTwoLevel hid stay out of the TLAS (E.boxes, the host copy behind the edit, keeps their true boxes)
     const std::vector<uint8_t> hidden = hiddenOfInstances(H.meshBuilds, instanceCount);
-    if (std::find(hidden.begin(), hidden.end(), (uint8_t)1) == hidden.end()) buildBvh8Boxes(E.boxes.data(), instanceCount, E.tlas, E.tlasItems);
+    GiCScene* scene = const_cast<GiCScene*>(s); // (the device builder's workspace and counters)
+    if (std::find(hidden.begin(), hidden.end(), (uint8_t)1) == hidden.end()) E.tlasMade = buildEditTlas(scene, T.blasDepth, E.boxes.data(), instanceCount, E.tlas, E.tlasItems);
     else {
       std::vector<float> masked(E.boxes);
       tlasMaskHiddenBoxes(masked.data(), hidden.data(), instanceCount);
-      buildBvh8Boxes(masked.data(), instanceCount, E.tlas, E.tlasItems);
+      E.tlasMade = buildEditTlas(scene, T.blasDepth, masked.data(), instanceCount, E.tlas, E.tlasItems);
     }
   }
   E.tlasMs = nowMs() - t1;
@@ -2332,7 +2380,7 @@ static int commitTwoLevelEdit(GiCScene* s, const SceneHost& H, SceneDevice& D, h
 static void finishTwoLevelEdit(GiCScene* s, SceneHost& H, TwoLevelEdit& E, std::vector<InstTrav>& instTrav, const Node8& root)
 {
   TwoLevelHost& T = H.two;
-  T.instTrav.swap(instTrav); T.instBoxes.swap(E.boxes); T.tlasNodes.swap(E.tlas.nodes); T.tlasItems.swap(E.tlasItems); T.tlasDepth = E.tlas.maxDepth;
+  T.instTrav.swap(instTrav); T.instBoxes.swap(E.boxes); T.tlasNodes.swap(E.tlas.nodes); T.tlasItems.swap(E.tlasItems); T.tlasDepth = E.tlas.maxDepth; noteTlasMade(T, E.tlasMade);
   if (H.treeless) setSceneBoundsFromInstances(s, H); // (the boxes just swapped in; hidden instances stay out, as out of the TLAS)
   else setSceneBounds(s, std::vector<Node8>{root});
   if (!H.hostTreeDropped) {
@@ -2649,6 +2697,12 @@ static int updateVerticesTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Upda
 // (it has no BLAS), an unusable transform of a new instance, a move without option 16, a set status, the depth rule, 2^28 flat records, fewer than
 // kIncrementalMinTris visible triangles, more retired than live triangles, out of device memory.
 // ---------------------------------------------------------------------------------------------------------------
+bool tlasDeviceBuildWanted(const GiCScene* s)
+{
+  const long o = optionValue("tlas_device_build", -1);
+  return o >= 0 ? o == 1 : s->optTlasDeviceBuild == 1;
+}
+
 bool tlasInstancesWanted(const GiCScene* s)
 {
   if (!instanceUpdatesWanted(s) || !tlasTopologyWanted(s)) return false;
@@ -2800,14 +2854,14 @@ static int updateInstancesTwoLevel(GiCScene* s, SceneHost& H, bool& applied, Upd
   for (size_t k = 0; k < boundsJobs.size(); k++)
     if (result[7u * k + 6u] != 0u) return decline("a new instance carries triangles that leave the usable coordinate range in world space");
   // --- the TLAS over all boxes, hidden instances and free slots masked; the depth rule (the BLASes do not change)
-  std::vector<float> boxes; Bvh8 tlas; std::vector<uint32_t> tlasItems; double tlasMs = 0.0;
+  std::vector<float> boxes; Bvh8 tlas; std::vector<uint32_t> tlasItems; double tlasMs = 0.0; TlasMade tlasMade;
   if (countsChange) {
     boxes = T.instBoxes; boxes.resize(6u * (size_t)newInstances, 0.0f);
     for (size_t k = 0; k < boundsJobs.size(); k++) memcpy(&boxes[6u * (size_t)boundsJobs[k].instance], &result[7u * k], 24);
     std::vector<float> masked(boxes);
     tlasMaskHiddenBoxes(masked.data(), hiddenAfter.data(), newInstances);
     const double tt0 = nowMs();
-    buildBvh8Boxes(masked.data(), newInstances, tlas, tlasItems);
+    tlasMade = buildEditTlas(s, T.blasDepth, masked.data(), newInstances, tlas, tlasItems);
     tlasMs = nowMs() - tt0;
     if (2u * tlas.maxDepth + T.blasDepth + 1u > 16u) return decline("the new TLAS is too deep for the 16-entry stack");
   }
@@ -2907,7 +2961,7 @@ static int updateInstancesTwoLevel(GiCScene* s, SceneHost& H, bool& applied, Upd
     }
   }
   H.instances.swap(instances); T.instTrav.swap(instTrav);
-  if (countsChange) { T.instBoxes.swap(boxes); T.tlasNodes.swap(tlas.nodes); T.tlasItems.swap(tlasItems); T.tlasDepth = tlas.maxDepth; }
+  if (countsChange) { T.instBoxes.swap(boxes); T.tlasNodes.swap(tlas.nodes); T.tlasItems.swap(tlasItems); T.tlasDepth = tlas.maxDepth; noteTlasMade(T, tlasMade); }
   if (sceneDataStale) { H.meshRecs.swap(meshRecs); H.sceneData.swap(sceneData); }
   // --- the MeshBuilds and the meshes: counts, slots, id bases; the moves go to updateTransformsTwoLevel
   for (MeshBuild& mb : H.meshBuilds) mb.idBase = newBase[mb.meshIdx];
@@ -3111,12 +3165,12 @@ static int updateTopologyTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Upda
   std::vector<uint8_t> hiddenAfter(newInstances, 0);
   for (const MeshBuild& mb : H.meshBuilds) if (plan.hide[mb.meshIdx]) for (const uint32_t inst : mb.inst) if (inst < oldInstances) hiddenAfter[inst] = 1;
   markFreeSlots(H.meshBuilds, hiddenAfter);
-  Bvh8 tlas; std::vector<uint32_t> tlasItems;
+  Bvh8 tlas; std::vector<uint32_t> tlasItems; TlasMade tlasMade;
   const double tt0 = nowMs();
   {
     std::vector<float> masked(boxes);
     tlasMaskHiddenBoxes(masked.data(), hiddenAfter.data(), newInstances);
-    buildBvh8Boxes(masked.data(), newInstances, tlas, tlasItems);
+    tlasMade = buildEditTlas(s, blasDepth, masked.data(), newInstances, tlas, tlasItems);
   }
   const double tlasMs = nowMs() - tt0;
   if (2u * tlas.maxDepth + blasDepth + 1u > 16u) return decline("the new TLAS is too deep for the 16-entry stack");
@@ -3216,7 +3270,7 @@ static int updateTopologyTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Upda
   if (matsRemade) H.mats.swap(mats);
   T.blasNodes.insert(T.blasNodes.end(), newBlasNodes.begin(), newBlasNodes.end()); T.blasTris.insert(T.blasTris.end(), newBlasTris.begin(), newBlasTris.end());
   T.instTrav.insert(T.instTrav.end(), newTrav.begin(), newTrav.end());
-  T.instBoxes.swap(boxes); T.tlasNodes.swap(tlas.nodes); T.tlasItems.swap(tlasItems); T.tlasDepth = tlas.maxDepth; T.blasDepth = blasDepth;
+  T.instBoxes.swap(boxes); T.tlasNodes.swap(tlas.nodes); T.tlasItems.swap(tlasItems); T.tlasDepth = tlas.maxDepth; T.blasDepth = blasDepth; noteTlasMade(T, tlasMade);
   // (25 % slack, as on the device and as updateTopology grows its host arrays: a std::vector would double 4.3 GB of records on the first append to a
   // 67.7 M-triangle scene and copy them on every later doubling)
   auto grown = [](auto& v, size_t n) { if (v.capacity() < n) v.reserve(n + n / 4u); v.resize(n); };
@@ -3286,6 +3340,22 @@ static RetiredRanges retiredRangesOf(const SceneHost& H, const TwoLevelHost& lay
   return R;
 }
 
+// "What the scene's own code makes anew" where the device builder made the resident TLAS (GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD; TwoLevelHost::tlasDeviceBuilt):
+// the comparison TLAS of giCDebugSceneTlasCheck / giCDebugSceneBlasCheck is then the host form of that builder over the same masked boxes under the same depth
+// budget, in place of buildTwoLevel's.  Nothing changes otherwise.
+static bool freshTlasOfResidentBuilder(const SceneHost& H, size_t instanceCount, TwoLevelHost& fresh)
+{
+  if (!H.two.tlasDeviceBuilt) return true;
+  std::vector<float> masked(fresh.instBoxes);
+  const std::vector<uint8_t> hidden = hiddenOfInstances(H.meshBuilds, instanceCount);
+  tlasMaskHiddenBoxes(masked.data(), hidden.data(), instanceCount);
+  TlasBuildInfo info;
+  const uint32_t radius = (uint32_t)std::min(std::max(optionValue("ploc_radius", 16), 1L), 256L);
+  if (masked.size() != 6u * instanceCount || buildTlasHost(masked.data(), instanceCount, H.two.tlasBuildBudget, radius, fresh.tlasNodes, fresh.tlasItems, info) != TLAS_BUILD_OK) return false;
+  fresh.tlasDepth = info.maxDepth;
+  return true;
+}
+
 // giCDebugSceneTlasCheck: the two-level arrays resident on a device against the arrays buildTwoLevel makes anew from the scene's current meshes, bytewise
 // (storage order: retired meshes and appended ones included, as updateTopologyTwoLevel leaves them; the ranges and records of a retired mesh are ignored)
 extern "C" int giCDebugSceneTlasCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t* out)
@@ -3309,6 +3379,7 @@ extern "C" int giCDebugSceneTlasCheck(const GiCScene* scene, uint32_t deviceInde
     const bool stillTwoLevel = s->twoLevel;
     s->twoLevel = true; // (buildTwoLevel answers through it: the resident scene is what it was)
     if (rc != GI_C_OK || !stillTwoLevel) { setError("giCDebugSceneTlasCheck: a fresh build of the current meshes would not use the two-level layout"); return -1; }
+    if (!freshTlasOfResidentBuilder(H, instances.size(), fresh)) { setError("giCDebugSceneTlasCheck: the host form of the device TLAS builder failed"); return -1; }
     SceneDevice& D = sceneDevice(s, deviceIndex);
     std::vector<Node8> tlasNodes(fresh.tlasNodes.size()), blasNodes(fresh.blasNodes.size()); std::vector<uint32_t> tlasItems(fresh.tlasItems.size());
     std::vector<BlasTri> blasTris(fresh.blasTris.size()); std::vector<InstTrav> instTrav(fresh.instTrav.size());
@@ -3548,6 +3619,7 @@ extern "C" int giCDebugSceneBlasCheck(const GiCScene* scene, uint32_t deviceInde
     const bool stillTwoLevel = s->twoLevel;
     s->twoLevel = true; // (buildTwoLevel answers through it: the resident scene is what it was)
     if (rc != GI_C_OK || !stillTwoLevel) { setError("giCDebugSceneBlasCheck: a fresh build of the current meshes would not use the two-level layout"); return -1; }
+    if (!freshTlasOfResidentBuilder(H, instances.size(), fresh)) { setError("giCDebugSceneBlasCheck: the host form of the device TLAS builder failed"); return -1; }
     if (T.meshBlasTri.size() != H.meshBuilds.size() || T.meshBlasNode.size() != H.meshBuilds.size() || T.meshBlasLevels.size() != H.meshBuilds.size() ||
         fresh.instTrav.size() != T.instTrav.size() || fresh.blasTris.size() != T.blasTris.size()) { setError("giCDebugSceneBlasCheck: the host copy is not the built scene's"); return -1; }
     SceneDevice& D = sceneDevice(s, deviceIndex);

@@ -24,27 +24,15 @@
 
 #include "gi_bvh_build.h"
 #include "gi_options.h"
+#define GI_BVH_STAGE_KERNELS
+#include "gi_bvh_stages.h" // the arithmetic and the stage kernels shared with gi_tlas_build.hip
 
 namespace gi {
 namespace {
 
-constexpr uint32_t kBlock = 256;
-constexpr uint32_t kMaxLeaf = 3;   // bvh8.cpp kMaxLeaf: 3-bit unary triangle count in Node8::meta
-constexpr float kCPrim = 0.5f;     // bvh8.cpp cPrim of the flat tree
+constexpr uint32_t kBlock = kStageBlock;
+constexpr uint32_t kMaxLeaf = kBvhMaxLeaf;
 
-// bvh8.cpp struct Dp (44 bytes per BVH2 node)
-struct Dp { float c[7]; uint8_t eff[7]; uint8_t split[7]; uint8_t leaf; };
-// one node's emission plan (bvh8.cpp Plan): children (BVH2 ids), slot of each, leaf mask, node box
-struct Plan { uint32_t ch[8]; int8_t childInSlot[8]; float lo[3], hi[3]; uint8_t leafMask, n, pad[2]; };
-
-__device__ inline float box_area(const float4& lo, const float4& hi)
-{
-  const float dx = hi.x - lo.x, dy = hi.y - lo.y, dz = hi.z - lo.z;
-  if (dx < 0.0f) return 0.0f;
-  return 2.0f * (dx * dy + dy * dz + dz * dx);
-}
-__device__ inline float4 min4(const float4& a, const float4& b) { return make_float4(fminf(a.x, b.x), fminf(a.y, b.y), fminf(a.z, b.z), 0.0f); }
-__device__ inline float4 max4(const float4& a, const float4& b) { return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), 0.0f); }
 __device__ inline bool usable(float x) { return fabsf(x) <= 1.0e18f; } // bvh8.cpp Builder::usable (false for NaN)
 
 // ---- 1. boxes -----------------------------------------------------------------------------------------------------------------------------------------
@@ -76,91 +64,10 @@ __global__ __launch_bounds__(kBlock) void k_bvh_boxes(const TriRec* __restrict__
     }
     triLo[i] = bl; triHi[i] = bh;
   }
-  sLo[threadIdx.x] = cLo; sHi[threadIdx.x] = cHi; sAlive[threadIdx.x] = alive;
-  __syncthreads();
-  for (uint32_t s = kBlock / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) { sLo[threadIdx.x] = min4(sLo[threadIdx.x], sLo[threadIdx.x + s]); sHi[threadIdx.x] = max4(sHi[threadIdx.x], sHi[threadIdx.x + s]);
-        sAlive[threadIdx.x] += sAlive[threadIdx.x + s]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { blockLo[blockIdx.x] = sLo[0]; blockHi[blockIdx.x] = sHi[0]; blockAlive[blockIdx.x] = sAlive[0]; }
+  stage_block_bounds(cLo, cHi, alive, sLo, sHi, sAlive, blockLo, blockHi, blockAlive);
 }
 
-// one block: the centroid bounds and the active count out of the per-block partials (min / max / integer sums: the order does not matter)
-__global__ __launch_bounds__(kBlock) void k_bvh_bounds(const float4* __restrict__ blockLo, const float4* __restrict__ blockHi,
-    const uint32_t* __restrict__ blockAlive, uint32_t blocks, float4* __restrict__ bounds, uint32_t* __restrict__ alive)
-{
-  __shared__ float4 sLo[kBlock], sHi[kBlock]; __shared__ uint32_t sAlive[kBlock];
-  float4 lo = make_float4(3.0e38f, 3.0e38f, 3.0e38f, 0.0f), hi = make_float4(-3.0e38f, -3.0e38f, -3.0e38f, 0.0f); uint32_t cnt = 0;
-  for (uint32_t b = threadIdx.x; b < blocks; b += kBlock) { lo = min4(lo, blockLo[b]); hi = max4(hi, blockHi[b]); cnt += blockAlive[b]; }
-  sLo[threadIdx.x] = lo; sHi[threadIdx.x] = hi; sAlive[threadIdx.x] = cnt;
-  __syncthreads();
-  for (uint32_t s = kBlock / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) { sLo[threadIdx.x] = min4(sLo[threadIdx.x], sLo[threadIdx.x + s]); sHi[threadIdx.x] = max4(sHi[threadIdx.x], sHi[threadIdx.x + s]);
-        sAlive[threadIdx.x] += sAlive[threadIdx.x + s]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { bounds[0] = sLo[0]; bounds[1] = sHi[0]; *alive = sAlive[0]; }
-}
-
-// ---- 2. Morton codes ----------------------------------------------------------------------------------------------------------------------------------
-__device__ inline uint64_t spread21(uint32_t x)
-{
-  uint64_t v = x & 0x1fffffu;
-  v = (v | v << 32) & 0x1f00000000ffffull;
-  v = (v | v << 16) & 0x1f0000ff0000ffull;
-  v = (v | v << 8) & 0x100f00f00f00f00full;
-  v = (v | v << 4) & 0x10c30c30c30c30c3ull;
-  v = (v | v << 2) & 0x1249249249249249ull;
-  return v;
-}
-__global__ __launch_bounds__(kBlock) void k_bvh_morton(const float4* __restrict__ triLo, const float4* __restrict__ triHi, uint32_t n,
-    const float4* __restrict__ bounds, uint64_t* __restrict__ keys, uint32_t* __restrict__ ids)
-{
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  ids[i] = i;
-  const float4 lo = triLo[i], hi = triHi[i];
-  if (!(lo.x <= hi.x)) { keys[i] = ~0ull; return; } // inactive: sorted behind every active triangle, in id order (the sort is stable)
-  const float4 bl = bounds[0], bh = bounds[1];
-  const float c[3] = {0.5f * (lo.x + hi.x), 0.5f * (lo.y + hi.y), 0.5f * (lo.z + hi.z)};
-  const float l[3] = {bl.x, bl.y, bl.z}, h[3] = {bh.x, bh.y, bh.z};
-  uint64_t code = 0;
-  for (int a = 0; a < 3; a++) {
-    const float ext = h[a] - l[a];
-    float u = ext > 0.0f ? (c[a] - l[a]) / ext : 0.0f;
-    u = fminf(fmaxf(u, 0.0f), 1.0f);
-    const uint32_t q = (uint32_t)fminf(u * 2097152.0f, 2097151.0f);
-    code |= spread21(q) << (2 - a);
-  }
-  keys[i] = code;
-}
-
-// ---- 3. PLOC + 4. collapse DP -------------------------------------------------------------------------------------------------------------------------
-__device__ inline void dp_leaf(Dp& d, float area)
-{
-  for (int i = 0; i < 7; i++) { d.c[i] = area * kCPrim; d.eff[i] = 1; d.split[i] = 0; }
-  d.leaf = 1;
-}
-// bvh8.cpp Builder::dpNode for an internal node
-__device__ inline void dp_internal(Dp& d, const Dp& L, const Dp& R, float area, uint32_t total)
-{
-  float dist[9];
-  for (int j = 2; j <= 8; j++) {
-    float best = 3.0e38f; int bk = 1;
-    for (int k = max(1, j - 7); k <= min(7, j - 1); k++) { const float c = L.c[k - 1] + R.c[j - k - 1]; if (c < best) { best = c; bk = k; } }
-    dist[j] = best; d.split[j - 2] = (uint8_t)bk;
-  }
-  const float cLeaf = total <= kMaxLeaf ? area * kCPrim * (float)total : 3.0e38f;
-  const float cInt = area + dist[8];
-  d.leaf = (total <= kMaxLeaf && cLeaf <= cInt) ? 1 : 0;
-  d.c[0] = d.leaf ? cLeaf : cInt; d.eff[0] = 1;
-  for (int i = 2; i <= 7; i++) {
-    if (dist[i] < d.c[i - 2]) { d.c[i - 1] = dist[i]; d.eff[i - 1] = (uint8_t)i; }
-    else { d.c[i - 1] = d.c[i - 2]; d.eff[i - 1] = d.eff[i - 2]; }
-  }
-}
-
+// ---- 3. PLOC + 4. collapse DP (gi_bvh_stages.h) ---------------------------------------------------------------------------------------------------------
 // BVH2 leaves 0 .. A-1: the sorted active triangles
 __global__ __launch_bounds__(kBlock) void k_bvh_leaves(const uint32_t* __restrict__ sortedIds, uint32_t A, const float4* __restrict__ triLo,
     const float4* __restrict__ triHi, float4* __restrict__ nLo, float4* __restrict__ nHi, uint32_t* __restrict__ total, Dp* __restrict__ dp,
@@ -171,18 +78,9 @@ __global__ __launch_bounds__(kBlock) void k_bvh_leaves(const uint32_t* __restric
   const uint32_t id = sortedIds[k];
   const float4 lo = triLo[id], hi = triHi[id];
   nLo[k] = lo; nHi[k] = hi; total[k] = 1u; clusters[k] = k;
-  Dp d; dp_leaf(d, box_area(lo, hi)); dp[k] = d;
+  Dp d; bvh_dp_leaf(d, box_area(lo, hi)); dp[k] = d;
 }
 
-// Tie-break of equal distances: a hash of the PAIR, then the partner's position.  (distance, pairHash, lower, upper) orders all pairs totally and the same
-// way seen from either end, so the smallest pair in the list is always mutual (progress); the hash keeps runs of equal boxes (coincident centroids) from
-// merging one pair per pass.
-__device__ inline uint32_t pair_hash(uint32_t a, uint32_t b)
-{
-  uint32_t h = a * 0x9e3779b1u ^ (b + 0x7f4a7c15u) * 0x85ebca77u;
-  h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
-  return h;
-}
 __global__ __launch_bounds__(kBlock) void k_ploc_nn(const uint32_t* __restrict__ clusters, uint32_t m, uint32_t radius, const float4* __restrict__ nLo,
     const float4* __restrict__ nHi, uint32_t* __restrict__ nn)
 {
@@ -196,8 +94,7 @@ __global__ __launch_bounds__(kBlock) void k_ploc_nn(const uint32_t* __restrict__
     if (j == i) continue;
     const uint32_t cj = clusters[j];
     const float d = box_area(min4(lo, nLo[cj]), max4(hi, nHi[cj]));
-    const uint32_t h = pair_hash(min(i, j), max(i, j));
-    if (d < bestD || (d == bestD && (h < bestH || (h == bestH && j < best)))) { bestD = d; bestH = h; best = j; }
+    bvh_nn_consider(i, j, d, bestD, bestH, best);
   }
   nn[i] = best;
 }
@@ -208,7 +105,7 @@ __global__ __launch_bounds__(kBlock) void k_ploc_flags(const uint32_t* __restric
   if (i >= m) return;
   const uint32_t j = nn[i];
   const bool mutual = j < m && nn[j] == i;
-  flags[i] = ((uint64_t)(mutual && i < j) << 32) | (uint64_t)!(mutual && i > j);
+  flags[i] = bvh_ploc_flags(i, j, mutual);
 }
 __global__ __launch_bounds__(kBlock) void k_ploc_merge(const uint32_t* __restrict__ clusters, uint32_t m, const uint32_t* __restrict__ nn,
     const uint64_t* __restrict__ flags, const uint64_t* __restrict__ incl, uint32_t nodeBase, float4* __restrict__ nLo, float4* __restrict__ nHi,
@@ -226,30 +123,12 @@ __global__ __launch_bounds__(kBlock) void k_ploc_merge(const uint32_t* __restric
   const uint32_t t = total[a] + total[b];
   nLo[node] = lo; nHi[node] = hi; left[node] = a; right[node] = b; total[node] = t;
   const Dp L = dp[a], R = dp[b];
-  Dp d; dp_internal(d, L, R, box_area(lo, hi), t); dp[node] = d;
+  Dp d; bvh_dp_internal(d, L, R, box_area(lo, hi), t); dp[node] = d;
   next[keepAt] = node;
 }
 
 // ---- 5. emission --------------------------------------------------------------------------------------------------------------------------------------
 struct Tree2 { const float4* lo; const float4* hi; const uint32_t* left; const uint32_t* right; const uint32_t* total; const Dp* dp; uint32_t A; };
-
-// bvh8.cpp gatherOptimal: the child list of the 8-wide node rooted at BVH2 node `root`
-__device__ inline int gather_optimal(const Tree2& T, uint32_t root, uint32_t* ch, bool* chLeaf)
-{
-  int n = 0;
-  uint32_t tn[32]; int8_t ts[32]; bool te[32]; int tp = 0;
-  tn[tp] = root; ts[tp] = 8; te[tp] = true; tp++;
-  while (tp > 0) {
-    tp--; const uint32_t n2 = tn[tp]; const int slots = ts[tp]; const bool expand = te[tp];
-    const Dp& d = T.dp[n2];
-    int j = slots;
-    if (!expand) { j = d.eff[slots - 1]; if (j == 1) { ch[n] = n2; chLeaf[n] = d.leaf != 0; n++; continue; } }
-    const int k = d.split[j - 2];
-    tn[tp] = T.right[n2]; ts[tp] = (int8_t)(j - k); te[tp] = false; tp++;
-    tn[tp] = T.left[n2]; ts[tp] = (int8_t)k; te[tp] = false; tp++;
-  }
-  return n;
-}
 
 __global__ __launch_bounds__(kBlock) void k_bvh_plan(Tree2 T, const uint32_t* __restrict__ level, uint32_t m, bool rootLevel, Plan* __restrict__ plans,
     uint64_t* __restrict__ counts)
@@ -259,28 +138,18 @@ __global__ __launch_bounds__(kBlock) void k_bvh_plan(Tree2 T, const uint32_t* __
   const uint32_t n2 = level[li];
   uint32_t ch[8]; bool chLeaf[8]; int n = 0;
   if (n2 < T.A || (rootLevel && T.total[n2] <= kMaxLeaf)) { ch[0] = n2; chLeaf[0] = true; n = 1; } // a root that is itself a leaf (bvh8.cpp: level 0 only)
-  else n = gather_optimal(T, n2, ch, chLeaf);
+  else n = bvh_gather_optimal(T.left, T.right, n2, [&](uint32_t x, bool) -> const Dp& { return T.dp[x]; }, ch, chLeaf);
   // node box + slot assignment (greedy max of the centroid projection on the slot's octant direction)
   float4 nbLo = make_float4(3.0e38f, 3.0e38f, 3.0e38f, 0.0f), nbHi = make_float4(-3.0e38f, -3.0e38f, -3.0e38f, 0.0f);
   for (int i = 0; i < n; i++) { nbLo = min4(nbLo, T.lo[ch[i]]); nbHi = max4(nbHi, T.hi[ch[i]]); }
   const float center[3] = {0.5f * (nbLo.x + nbHi.x), 0.5f * (nbLo.y + nbHi.y), 0.5f * (nbLo.z + nbHi.z)};
-  float cost[8][8];
+  float clo[8][3], chi[8][3];
   for (int i = 0; i < n; i++) {
     const float4 bl = T.lo[ch[i]], bh = T.hi[ch[i]];
-    const float d[3] = {0.5f * (bl.x + bh.x) - center[0], 0.5f * (bl.y + bh.y) - center[1], 0.5f * (bl.z + bh.z) - center[2]};
-    for (int s = 0; s < 8; s++) cost[i][s] = ((s & 1) ? d[0] : -d[0]) + ((s & 2) ? d[1] : -d[1]) + ((s & 4) ? d[2] : -d[2]);
+    clo[i][0] = bl.x; clo[i][1] = bl.y; clo[i][2] = bl.z; chi[i][0] = bh.x; chi[i][1] = bh.y; chi[i][2] = bh.z;
   }
-  int slotOf[8]; bool slotUsed[8] = {false, false, false, false, false, false, false, false};
-  bool childDone[8] = {false, false, false, false, false, false, false, false};
-  for (int k = 0; k < n; k++) {
-    int bi = -1, bs = -1; float bc = -3.0e38f;
-    for (int i = 0; i < n; i++) if (!childDone[i]) for (int s = 0; s < 8; s++) if (!slotUsed[s] && cost[i][s] > bc) { bc = cost[i][s]; bi = i; bs = s; }
-    if (bi < 0) { // (non-finite costs: first free child, first free slot)
-      for (int i = 0; i < n && bi < 0; i++) if (!childDone[i]) bi = i;
-      for (int s = 0; s < 8 && bs < 0; s++) if (!slotUsed[s]) bs = s;
-    }
-    slotOf[bi] = bs; slotUsed[bs] = true; childDone[bi] = true;
-  }
+  int slotOf[8];
+  bvh_assign_slots(n, clo, chi, center, slotOf);
   Plan P;
   for (int s = 0; s < 8; s++) { P.childInSlot[s] = -1; P.ch[s] = 0; }
   uint32_t internal = 0, trisHere = 0; P.leafMask = 0; P.n = (uint8_t)n; P.pad[0] = P.pad[1] = 0;
@@ -291,17 +160,6 @@ __global__ __launch_bounds__(kBlock) void k_bvh_plan(Tree2 T, const uint32_t* __
   }
   plans[li] = P;
   counts[li] = ((uint64_t)internal << 32) | trisHere;
-}
-
-// bvh8.cpp exponentFor: smallest e with 255 * 2^e >= extent
-__device__ inline int exponent_for(float extent)
-{
-  if (!(extent > 0.0f)) return -126;
-  int e; const float m = frexpf(extent / 255.0f, &e);
-  if (m == 0.5f) e -= 1;
-  e = min(max(e, -126), 127);
-  while (255.0f * ldexpf(1.0f, e) < extent && e < 127) e++;
-  return e;
 }
 
 __global__ __launch_bounds__(kBlock) void k_bvh_write(Tree2 T, const uint32_t* __restrict__ level, uint32_t m, uint32_t levelStart,
@@ -315,35 +173,21 @@ __global__ __launch_bounds__(kBlock) void k_bvh_write(Tree2 T, const uint32_t* _
   const uint64_t ex = incl[li] - counts[li];
   const uint32_t childBase = nodeEnd + (uint32_t)(ex >> 32), triBase = triStart + (uint32_t)(ex & 0xffffffffull);
   Node8 node; memset(&node, 0, sizeof(node));
-  int exA[3]; float scale[3];
-  for (int a = 0; a < 3; a++) { node.p[a] = P.lo[a]; exA[a] = exponent_for(P.hi[a] - P.lo[a]); node.e[a] = (uint8_t)(exA[a] + 127);
-      scale[a] = ldexpf(1.0f, exA[a]); }
+  float scale[3];
+  bvh_node_frame(node, P, scale);
   node.childBase = childBase; node.triBase = triBase;
   uint32_t triOffset = 0, childIdx = childBase;
   for (int s = 0; s < 8; s++) {
     const int i = P.childInSlot[s];
-    if (i < 0) { for (int a = 0; a < 3; a++) { node.qlo[a][s] = 255; node.qhi[a][s] = 0; } continue; }
+    if (i < 0) { bvh_empty_slot(node, s); continue; }
     const uint32_t c = P.ch[i];
     const float4 cl4 = T.lo[c], ch4 = T.hi[c];
     const float clo[3] = {cl4.x, cl4.y, cl4.z}, chi[3] = {ch4.x, ch4.y, ch4.z};
-    for (int a = 0; a < 3; a++) { // outward rounding, then bvh8.cpp's fix-up loops against the fp32 planes the traversal evaluates
-      int lo = (int)floor(((double)clo[a] - (double)node.p[a]) / (double)scale[a]);
-      int hi = (int)ceil(((double)chi[a] - (double)node.p[a]) / (double)scale[a]);
-      lo = min(max(lo, 0), 255); hi = min(max(hi, 0), 255);
-      while (lo > 0 && node.p[a] + (float)lo * scale[a] > clo[a]) lo--;
-      while (hi < 255 && node.p[a] + (float)hi * scale[a] < chi[a]) hi++;
-      node.qlo[a][s] = (uint8_t)lo; node.qhi[a][s] = (uint8_t)hi;
-    }
+    bvh_quantise_slot(node, s, clo, chi, scale);
     if (P.leafMask & (1u << i)) { // leaf slot: unary count in the high 3 bits, triangle offset in the low 5; the BVH2 leaves below, left to right
-      uint32_t leaves[kMaxLeaf]; uint32_t cnt = 0;
-      uint32_t stack[2 * kMaxLeaf]; int sp = 0; stack[sp++] = c;
-      while (sp > 0 && cnt < kMaxLeaf) {
-        const uint32_t x = stack[--sp];
-        if (x < T.A) { leaves[cnt++] = x; continue; }
-        if (sp + 2 > (int)(2 * kMaxLeaf)) break; // (cannot happen: a leaf slot holds at most three BVH2 leaves)
-        stack[sp++] = T.right[x]; stack[sp++] = T.left[x];
-      }
-      node.meta[s] = (uint8_t)((((1u << cnt) - 1u) << 5) | triOffset);
+      uint32_t leaves[kMaxLeaf];
+      const uint32_t cnt = bvh_leaves_below(T.left, T.right, T.A, c, leaves);
+      node.meta[s] = bvh_leaf_meta(cnt, triOffset);
       for (uint32_t k = 0; k < cnt; k++) {
         const uint32_t ref = sortedIds[leaves[k]], dst = triBase + triOffset + k;
         TriRec t = inTris[ref]; t.origId = ref; outTris[dst] = t; outFace[dst] = inFace[ref];
@@ -351,7 +195,7 @@ __global__ __launch_bounds__(kBlock) void k_bvh_write(Tree2 T, const uint32_t* _
       triOffset += cnt;
     } else {
       node.imask |= (uint8_t)(1u << s);
-      node.meta[s] = (uint8_t)((1u << 5) | (24u + (uint32_t)s));
+      node.meta[s] = bvh_internal_meta(s);
       nextLevel[childIdx - nodeEnd] = c;
       childIdx++;
     }
@@ -471,8 +315,7 @@ int buildBvh8Device(hipStream_t st, TriRec* tris, int32_t* faceId, uint32_t n, u
   void* scan2Tmp = ar.get<uint8_t>(scan2Bytes); DB_ALLOC_CHECK();
   uint32_t nodeCount = 1, triCount = 0, levels = 0;
   if (A == 0u) { // bvh8.cpp emptyRoot: a single empty node
-    Node8 root; memset(&root, 0, sizeof(root));
-    for (int a = 0; a < 3; a++) { root.e[a] = 127; for (int s = 0; s < 8; s++) { root.qlo[a][s] = 255; root.qhi[a][s] = 0; } }
+    Node8 root; bvh_empty_root(root);
     DB_TRY(hipMemcpyAsync(nodesTmp, &root, sizeof(root), hipMemcpyHostToDevice, st));
     DB_TRY(hipStreamSynchronize(st)); // (`root` leaves scope)
     levels = 1; out.levelStart.push_back(0u);

@@ -151,6 +151,7 @@ void deriveMaterialConstants(MaterialRec& m)
 void SceneDevice::releaseAll()
 {
   dNodes.release(); dTris.release(); dInstances.release(); dVerts.release(); dTriFaceId.release(); dTriShade.release(); dTriGeomNormal.release();
+  tlasWorkspace.release();
   dTlasNodes.release(); dBlasNodes.release(); dTlasItems.release(); dFlatOfOrig.release(); dBlasTris.release(); dInstTrav.release();
   for (auto* b : dTexels) { b->release(); delete b; }
   dTexels.clear(); dTexelSerial.clear(); dTextures.release(); dMeshes.release(); dSceneData.release();
@@ -326,6 +327,7 @@ int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value)
   // (read at the scene build, with the two-level layout wanted: the next build decides)
   if (option == GI_C_SCENE_OPTION_TLAS_INSTANCES) { scene->optTlasInstances = value == 1 ? 1 : 0; return GI_C_OK; } // (read only with options 13, 15 and 20 wanted, on a scene built with option 19)
   if (option == GI_C_SCENE_OPTION_TLAS_TOPOLOGY) { scene->optTlasTopology = value == 1 ? 1 : 0; return GI_C_OK; } // (read only with option 13 wanted, on a scene built with option 19)
+  if (option == GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD) { scene->optTlasDeviceBuild = value == 1 ? 1 : 0; return GI_C_OK; } // (read only where options 16 - 18, 20, 21 apply an edit in place)
   if (option == GI_C_SCENE_OPTION_TLAS_ONLY) { scene->optTlasOnly = value == 1 ? 1 : 0; scene->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER; scene->rebuildDue = true; return GI_C_OK; }
   setError("unknown scene option"); return GI_C_ERROR;
 }

@@ -2,6 +2,9 @@
 // (one of the translation units gi_c.cpp was split into in round 6; shared declarations: gi_host.h)
 #include "gi_host.h"
 #include "gi_refit.h"
+#include "gi_tlas_build.h"
+#include "gi_bvh_stages.h"
+#include "bvh8.h"
 
 // ---------------------------------------------------------------------------------------------------------------
 // giCTraceRays: closest hits through the device traversal kernel (parity tests of the BVH8 path)
@@ -780,5 +783,153 @@ extern "C" int giCDebugSceneClassState(const GiCScene* scene, uint32_t* out)
   if (!s || !out) { setError("giCDebugSceneClassState: bad arguments"); return GI_C_ERROR; }
   std::lock_guard<std::mutex> guard(s->mutex);
   out[0] = s->classMask; out[1] = s->classTextured; out[2] = s->shadeClassMask; out[3] = s->shadeClassTextured; out[4] = s->hasCutouts ? 1u : 0u;
+  return GI_C_OK;
+}
+
+// ---- the TLAS builders of an edit (gi_tlas_build.h): giCDebugBuildTlasHost / giCDebugBuildTlas ---------------------------------------------------------------
+namespace {
+
+// the dequantised box of slot s: the fp32 planes the traversal evaluates
+void tlasSlotBox(const Node8& nd, int s, float box[6])
+{
+  for (int a = 0; a < 3; a++) {
+    const float scale = ldexpf(1.0f, (int)nd.e[a] - 127);
+    box[a] = nd.p[a] + (float)nd.qlo[a][s] * scale; box[3 + a] = nd.p[a] + (float)nd.qhi[a][s] * scale;
+  }
+}
+bool tlasSlotUsed(const Node8& nd, int s) { return nd.meta[s] != 0; }
+
+// the SAH model cost of a tree over its dequantised slot boxes: root area + per internal slot its area + per leaf slot cPrim * items * its area
+double tlasModelCost(const std::vector<Node8>& nodes)
+{
+  if (nodes.empty()) return 0.0;
+  double cost = 0.0;
+  float root[6] = {3.0e38f, 3.0e38f, 3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f}; bool any = false;
+  for (size_t i = 0; i < nodes.size(); i++) {
+    const Node8& nd = nodes[i];
+    for (int s = 0; s < 8; s++) {
+      if (!tlasSlotUsed(nd, s)) continue;
+      float b[6]; tlasSlotBox(nd, s, b);
+      if (i == 0) { any = true; for (int a = 0; a < 3; a++) { root[a] = std::min(root[a], b[a]); root[3 + a] = std::max(root[3 + a], b[3 + a]); } }
+      const double area = (double)tlas_box_area(b);
+      if (nd.imask & (1u << s)) cost += area;
+      else { uint32_t cnt = 0; for (uint32_t u = nd.meta[s] >> 5; u; u >>= 1) cnt += u & 1u; cost += area * (double)kBvhCPrim * (double)cnt; }
+    }
+  }
+  if (any) cost += (double)tlas_box_area(root);
+  return cost;
+}
+
+// the rules of giCDebugBuildTlasHost; `depth` is the builder's answer
+int tlasViolations(const float* boxes6, uint32_t n, const std::vector<Node8>& nodes, const std::vector<uint32_t>& items, uint32_t depth, uint32_t budget)
+{
+  int bad = 0;
+  std::vector<uint32_t> inactive; uint32_t A = 0;
+  for (uint32_t i = 0; i < n; i++) { if (tlas_box_active(boxes6 + 6u * (size_t)i)) A++; else inactive.push_back(i); }
+  if (items.size() != n) return 1 + (int)n;
+  std::vector<uint32_t> seen(n, 0u);
+  for (uint32_t k = 0; k < A; k++) { const uint32_t id = items[k]; if (id >= n || !tlas_box_active(boxes6 + 6u * (size_t)id)) bad++; else seen[id]++; }
+  for (uint32_t i = 0; i < n; i++) if (tlas_box_active(boxes6 + 6u * (size_t)i) && seen[i] != 1u) bad++;
+  for (uint32_t k = A; k < n; k++) if (items[k] != inactive[k - A]) bad++;
+  if (nodes.empty()) return bad + 1;
+  if (depth > budget || depth == 0u) bad++;
+  // breadth-first walk: the next internal child must be the next node; every item inside every ancestor slot
+  struct Anc { float box[6]; };
+  std::vector<std::vector<Anc>> chain(nodes.size()); std::vector<uint32_t> levelOf(nodes.size(), 0u);
+  uint32_t nextNode = 1, itemsNamed = 0, maxLevel = 1; std::vector<uint32_t> named(n, 0u);
+  levelOf[0] = 1;
+  for (uint32_t i = 0; i < nodes.size(); i++) {
+    const Node8& nd = nodes[i];
+    if (i >= nextNode) { bad++; break; } // (a node nothing names)
+    maxLevel = std::max(maxLevel, levelOf[i]);
+    uint32_t child = nd.childBase;
+    for (int s = 0; s < 8; s++) {
+      if (!tlasSlotUsed(nd, s)) { if (nd.imask & (1u << s)) bad++; continue; }
+      Anc me; tlasSlotBox(nd, s, me.box);
+      if (nd.imask & (1u << s)) {
+        if (child != nextNode || child >= nodes.size()) { bad++; child++; continue; }
+        chain[child] = chain[i]; chain[child].push_back(me); levelOf[child] = levelOf[i] + 1u;
+        child++; nextNode++;
+        continue;
+      }
+      uint32_t cnt = 0; for (uint32_t u = nd.meta[s] >> 5; u; u >>= 1) cnt += u & 1u;
+      const uint32_t first = nd.triBase + (nd.meta[s] & 31u);
+      if (cnt == 0u || cnt > kBvhMaxLeaf || (size_t)first + cnt > A) { bad++; continue; }
+      for (uint32_t k = 0; k < cnt; k++) {
+        const uint32_t id = items[first + k];
+        if (id >= n) { bad++; continue; }
+        named[id]++; itemsNamed++;
+        const float* b = boxes6 + 6u * (size_t)id;
+        auto inside = [&](const float* o) { for (int a = 0; a < 3; a++) if (!(o[a] <= b[a] && b[3 + a] <= o[3 + a])) return false; return true; };
+        if (!inside(me.box)) bad++;
+        for (const Anc& an : chain[i]) if (!inside(an.box)) bad++;
+      }
+    }
+  }
+  if (nextNode != nodes.size()) bad++;
+  if (itemsNamed != A) bad++;
+  for (uint32_t i = 0; i < n; i++) if (tlas_box_active(boxes6 + 6u * (size_t)i) && named[i] != 1u) bad++;
+  if (maxLevel != depth && A != 0u) bad++;
+  return bad;
+}
+
+void tlasFillOut(const float* boxes6, uint32_t count, const std::vector<Node8>& nodes, const TlasBuildInfo& info, double* out)
+{
+  Bvh8 ref; std::vector<uint32_t> order;
+  buildBvh8Boxes(boxes6, count, ref, order);
+  out[0] = (double)info.nodeCount; out[1] = (double)info.maxDepth; out[2] = (double)info.passes; out[3] = tlasModelCost(nodes); out[4] = tlasModelCost(ref.nodes);
+  out[5] = (double)info.hostWaits; out[6] = (double)ref.maxDepth; out[7] = (double)info.active;
+}
+
+} // namespace
+
+extern "C" int giCDebugBuildTlasHost(const float* boxes6, uint32_t count, uint32_t depthBudget, uint32_t radius, double* out)
+{
+  if ((count && !boxes6) || !out) { setError("giCDebugBuildTlasHost: bad arguments"); return -1; }
+  try {
+    for (int k = 0; k < 8; k++) out[k] = 0.0;
+    std::vector<Node8> nodes; std::vector<uint32_t> items; TlasBuildInfo info;
+    const int rc = buildTlasHost(boxes6, count, depthBudget, radius, nodes, items, info);
+    if (rc == TLAS_BUILD_TOO_DEEP) return GI_C_TLAS_BUILD_TOO_DEEP;
+    if (rc != TLAS_BUILD_OK) { setError(std::string("giCDebugBuildTlasHost: ") + info.error); return -1; }
+    tlasFillOut(boxes6, count, nodes, info, out);
+    return tlasViolations(boxes6, count, nodes, items, info.maxDepth, std::min(depthBudget, kTlasMaxBudget));
+  } catch (const std::exception& e) { setError(std::string("giCDebugBuildTlasHost: ") + e.what()); return -1; }
+}
+
+extern "C" int giCDebugBuildTlas(const float* boxes6, uint32_t count, uint32_t depthBudget, uint32_t radius, double* out)
+{
+  if (!g_ctx.initialized || (count && !boxes6) || !out) { setError("giCDebugBuildTlas: bad arguments"); return -1; }
+  try {
+    for (int k = 0; k < 8; k++) out[k] = 0.0;
+    std::vector<Node8> nodes, hostNodes; std::vector<uint32_t> items, hostItems; TlasBuildInfo info, hostInfo;
+    TlasBuildWorkspace ws;
+    const int rc = buildTlasDevice(ws, g_ctx.stream, boxes6, count, depthBudget, radius, nodes, items, info);
+    ws.release();
+    const int hostRc = buildTlasHost(boxes6, count, depthBudget, radius, hostNodes, hostItems, hostInfo);
+    out[5] = (double)info.hostWaits;
+    if (rc == TLAS_BUILD_TOO_DEEP) { if (hostRc != TLAS_BUILD_TOO_DEEP) { setError("giCDebugBuildTlas: too deep on the device alone"); return -1; } return GI_C_TLAS_BUILD_TOO_DEEP; }
+    if (rc != TLAS_BUILD_OK) { setError(std::string("giCDebugBuildTlas: ") + info.error); return -1; }
+    if (hostRc != TLAS_BUILD_OK) { setError("giCDebugBuildTlas: the host form failed where the device did not"); return -1; }
+    tlasFillOut(boxes6, count, nodes, info, out);
+    int differ = tlasViolations(boxes6, count, nodes, items, info.maxDepth, std::min(depthBudget, kTlasMaxBudget));
+    if (nodes.size() != hostNodes.size()) differ += 1 + (int)std::max(nodes.size(), hostNodes.size()) - (int)std::min(nodes.size(), hostNodes.size());
+    for (size_t i = 0; i < std::min(nodes.size(), hostNodes.size()); i++) if (memcmp(&nodes[i], &hostNodes[i], sizeof(Node8)) != 0) differ++;
+    if (items.size() != hostItems.size()) differ++;
+    for (size_t i = 0; i < std::min(items.size(), hostItems.size()); i++) if (items[i] != hostItems[i]) differ++;
+    if (info.maxDepth != hostInfo.maxDepth || info.passes != hostInfo.passes || info.active != hostInfo.active) differ++;
+    return differ;
+  } catch (const std::exception& e) { setError(std::string("giCDebugBuildTlas: ") + e.what()); return -1; }
+}
+
+extern "C" int giCDebugSceneTlasBuildStats(const GiCScene* scene, uint64_t* out)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!s || !out) { setError("giCDebugSceneTlasBuildStats: bad arguments"); return GI_C_ERROR; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  for (int k = 0; k < 16; k++) out[k] = s->tlasBuildStats[k];
+  out[13] = s->tlasWorkspace.allocations;
+  out[14] = s->host && s->host->two.tlasDeviceBuilt ? 1u : 0u;
+  out[15] = s->host && s->host->two.tlasDeviceBuilt ? s->host->two.tlasBuildBudget : 0u;
   return GI_C_OK;
 }

@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "bvh8.h"
+#include "gi_tlas_build.h"
 #include "gi_kernels.h"
 #include "gi_image.h"
 #include "gi_options.h"
@@ -267,6 +268,7 @@ struct SceneDevice {
   DeviceBuffer<SphereLightRec> dSphere; DeviceBuffer<DistantLightRec> dDistant; DeviceBuffer<RectLightRec> dRect; DeviceBuffer<DiskLightRec> dDisk;
   DeviceBuffer<LightFrame> dRectFrames, dDiskFrames; // decoded tangents + normal per rect / disk light (uploadLights)
   DeviceBuffer<Node8> dTlasNodes, dBlasNodes; DeviceBuffer<uint32_t> dTlasItems, dFlatOfOrig; DeviceBuffer<BlasTri> dBlasTris; DeviceBuffer<InstTrav> dInstTrav;
+  TlasBuildWorkspace tlasWorkspace; // the device TLAS builder's slab (primary device only; GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD): grows geometrically, released with the scene
   // path state
   DeviceBuffer<Slot> slots;
   DeviceBuffer<float> media; // per-slot medium stack + walkSegmentPdf (mediumStackSize > 0)
@@ -318,7 +320,10 @@ struct TwoLevelHost { std::vector<Node8> tlasNodes, blasNodes; std::vector<uint3
     // BLAS relative to that, then the BLAS's node count (Bvh8::levelStart; empty for a mesh without instances).  After such an update blasNodes keeps the
     // build's TOPOLOGY (imask, meta, childBase, triBase) while its planes (p, e, qlo, qhi) go stale: nothing reads them before the next buildScene -- the
     // device refits its own copy, and giCDebugSceneBlasCheck runs the host refit over a copy of the topology
-    std::vector<uint32_t> meshBlasNode; std::vector<std::vector<uint32_t>> meshBlasLevels; };
+    std::vector<uint32_t> meshBlasNode; std::vector<std::vector<uint32_t>> meshBlasLevels;
+    // GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD: the device builder (gi_tlas_build.hip) made the resident TLAS, under this depth budget -- an edit in place sets both,
+    // a scene build clears them; giCDebugSceneTlasCheck makes its comparison TLAS with the same builder
+    bool tlasDeviceBuilt = false; uint32_t tlasBuildBudget = 0; };
 struct MeshBuild { const GiCMesh* m; uint32_t vertexOffset, matFlags, instFirst, instCount, triFirst; uint32_t meshIdx; std::vector<int32_t> faceIdAov;
     uint32_t shadeBase = 0;
     // the InstanceRec of every live instance, inst[instInMesh]: instFirst + instInMesh (and triangles at triFirst + instInMesh * faces) as the build leaves
@@ -461,6 +466,9 @@ struct GiCScene : SceneDevice {
   // tree (updateInstancesTwoLevel; read only with topology, instance and two-level topology updates wanted); giCDebugSceneTlasInstanceUpdateStats: syncs
   // that applied such an edit, instances appended, of those into reused slots, instances retired
   int32_t optTlasInstances = 0; uint64_t tlasInstanceCounts[4] = {0, 0, 0, 0};
+  // GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD: 1 = the edits in place of a two-level scene build their TLAS on the primary device (gi_build.cpp buildEditTlas);
+  // giCDebugSceneTlasBuildStats: device builds, fallbacks (too deep, memory, error, under tlas_device_min), the last device build's figures
+  int32_t optTlasDeviceBuild = 0; uint64_t tlasBuildStats[16] = {};
   std::vector<GiCMesh*> retiredMeshes; // destroyed meshes the resident scene still refers to (GiCMesh::retired): freed by buildScene and with the scene
   ~GiCScene() { for (GiCMesh* m : retiredMeshes) delete m; }
 };
@@ -492,6 +500,7 @@ bool tlasOnlyWanted(const GiCScene* s);                      // GI_C_SCENE_OPTIO
 bool tlasVisibilityWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_TLAS_VISIBILITY / GATLING_OPTIONS=tlas_visibility (with visibility updates wanted)
 bool topologyUpdatesWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_TOPOLOGY_UPDATES / GATLING_OPTIONS=topology_updates
 bool tlasTopologyWanted(const GiCScene* s);                  // GI_C_SCENE_OPTION_TLAS_TOPOLOGY / GATLING_OPTIONS=tlas_topology (with topology updates wanted)
+bool tlasDeviceBuildWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD / GATLING_OPTIONS=tlas_device_build (read where options 16 - 18, 20, 21 apply an edit)
 bool tlasInstancesWanted(const GiCScene* s);                 // GI_C_SCENE_OPTION_TLAS_INSTANCES / GATLING_OPTIONS=tlas_instances (with options 13, 15 and 20 wanted)
 int syncSceneGeometry(GiCScene* s);                          // brings the device scene up to date with the host-side edits (incremental or full build)
 // dirty flags of a material-side edit: DIRTY_MATERIALS alone once the scene / the mesh is part of a built scene (the incremental path), else with DIRTY_BVH

@@ -85,6 +85,11 @@
 //                                  meshes on a two-level scene built without the flat tree rebuild it / are applied to the resident scene (gi_build.cpp
 //                                  updateInstancesTwoLevel; the flat records of all new instances are made on the device in one launch: gi_instances.hip);
 //                                  read only with topology_updates, instance_updates and tlas_topology wanted
+//   tlas_device_build    -1        -1 = the scene option decides (GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD), 0 / 1 = the edits in place of a two-level scene build
+//                                  their TLAS with the host builder / on the primary device (gi_tlas_build.hip; gi_build.cpp buildEditTlas); read only
+//                                  where tlas_updates, blas_updates, tlas_visibility, tlas_topology or tlas_instances applies an edit
+//   tlas_device_min      TLAS_DEVICE_MIN_DEFAULT   with tlas_device_build: scenes of fewer instances keep the host builder (the crossover)
+//   tlas_depth_budget    -         with tlas_device_build: lowers the device builder's depth budget below the stack rule's (tests)
 //   phase_stats          0         counting builds: print k_path's phase split / k_trace_dyn's lane accounting
 #pragma once
 
@@ -92,6 +97,11 @@
 #include <cstring>
 
 namespace gi {
+
+// instances below which an edit's TLAS stays with the host builder although GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD is on (GATLING_OPTIONS=tlas_device_min): the
+// measured crossover of a steady transform edit (tools/time_tlas_device_build.py --crossover, profiles/r23_tlas_device_build.txt: the host builder wins at
+// 4 096 instances, 1.39 against 2.48 ms, the device builder from 8 281 on, 2.74 against 3.27 ms)
+constexpr long TLAS_DEVICE_MIN_DEFAULT = 8192;
 
 // value of `key` in $GATLING_OPTIONS, or `def`.  Read at every call (tests change the variable between renders of one process).
 inline long optionValue(const char* key, long def)

@@ -385,7 +385,8 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * giCDebugBlasRefitHost, and for GI_C_SCENE_OPTION_TLAS_VISIBILITY, giCDebugSceneTlasVisibilityUpdateCount, giCDebugSceneFlatIdCheck and
  * giCDebugPatchVisibilityTwoLevel, and for GI_C_SCENE_OPTION_TLAS_ONLY and giCDebugSceneFlatTreeState, and for GI_C_SCENE_OPTION_TLAS_TOPOLOGY,
  * giCDebugSceneTlasTopologyUpdateCount, giCDebugAppendRecords and giCDebugAppendRecordsHost, and for GI_C_SCENE_OPTION_TLAS_INSTANCES,
- * giCDebugSceneTlasInstanceUpdateStats, giCDebugInstanceRecords and giCDebugInstanceRecordsHost, and for giCDebugTraversalStackHigh and giCDebugBvhStackReach. */
+ * giCDebugSceneTlasInstanceUpdateStats, giCDebugInstanceRecords and giCDebugInstanceRecordsHost, and for giCDebugTraversalStackHigh and giCDebugBvhStackReach,
+ * and for GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD, giCDebugBuildTlasHost, giCDebugBuildTlas and giCDebugSceneTlasBuildStats. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -674,6 +675,15 @@ int giCGetRenderStats(const GiCScene* scene, GiCRenderStats* out);
  * whatever option 20 declines for, a new count of 0, a mesh hidden by the visibility path, an unusable transform of a new instance, a move without option 16,
  * out of device memory.  GATLING_OPTIONS=tlas_instances=0|1 overrides the option (hdGatling sets no scene options).  DESIGN.md section 6. */
 #define GI_C_SCENE_OPTION_TLAS_INSTANCES 21
+/* [ext] Where the TLAS of an edit in place is built; read only where one of options 16, 17, 18, 20 or 21 applies an edit to a resident two-level scene: value
+ * 1 = the TLAS over the instance boxes is built on the primary device (gi_tlas_build.hip: Morton sort, PLOC, a cost-optimal 8-wide collapse whose depth is
+ * bounded by the layout's 16-entry stack, D = floor((15 - BLAS depth) / 2) levels) instead of by the host's binned-SAH builder; nodes and items are read back
+ * and sent to every device as a host-built TLAS is.  0 = off (default): every launch, flag, counter and resident byte is what it is without the option.  The
+ * image does not depend on the option (the traversal contract).  The host builder is used instead -- the edit never fails because of the option -- when the
+ * scene has fewer instances than GATLING_OPTIONS=tlas_device_min (default in gi_options.h), when the tree does not fit D levels, out of device memory, or
+ * on an error status; giCDebugSceneTlasBuildStats counts each.  The scene build itself keeps the host builder.  GATLING_OPTIONS=tlas_device_build=0|1
+ * overrides the option (hdGatling sets no scene options); tlas_depth_budget=N lowers D for the device builder (tests).  DESIGN.md section 6. */
+#define GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD 22
 int giCGetLookaheadStats(const GiCScene* scene, GiCLookaheadStats* out);
 int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value);
 /* [ext] closest hit of one ray through the device traversal kernel (parity tests of the BVH8 path).
@@ -786,6 +796,27 @@ int giCDebugSceneTlasUpdateCount(const GiCScene* scene, uint64_t* outCount);
  * retired instance left (GI_C_SCENE_OPTION_TLAS_INSTANCES) until a grow of its mesh takes it: the arrays are made over the live instances where they lie.  out[0]: 1 when the two-level layout is
  * in use (0: nothing was compared), [1] instances, [2] TLAS nodes, [3] TLAS depth. */
 int giCDebugSceneTlasCheck(const GiCScene* scene, uint32_t deviceIndex, uint32_t* out /* 4 */);
+/* (With GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD the check keeps its meaning, "what the scene's own code makes anew": the comparison TLAS is made by the builder
+ * that made the resident one -- after an edit whose TLAS the device built, the host form of that builder (giCDebugBuildTlasHost's) over the same masked boxes
+ * under the same depth budget -- so it still answers 0; the BLAS and traversal-record parts are unchanged, and so is everything with the option off.) */
+/* [ext] [debug] the host form of the device TLAS builder (gi_tlas_build_host.cpp; no device is used): a TLAS over `count` boxes (6 floats each: min xyz, max
+ * xyz; taken as they are) with at most `depthBudget` levels (clamped to 7) and PLOC radius `radius`, validated: every active item exactly once in items[0,
+ * active), the inactive ones (an inverted box, a non-finite side, a magnitude beyond 1e18) behind in input order; nodes breadth-first, internal children
+ * contiguous at childBase in slot order; every item box inside every ancestor slot's dequantised box; depth <= budget.  Returns the number of violations
+ * (0), GI_C_TLAS_BUILD_TOO_DEEP when the tree cannot fit the budget, -1 on error.  out[0] nodes, [1] depth, [2] PLOC passes, [3] the tree's SAH model cost
+ * (root area + per internal slot its area + per leaf slot 0.5 * items * its area, over the dequantised slot boxes), [4] the same function over
+ * buildBvh8Boxes's tree of the same boxes, [5] host waits (0 here), [6] buildBvh8Boxes's depth, [7] active items. */
+#define GI_C_TLAS_BUILD_TOO_DEEP (-2)
+int giCDebugBuildTlasHost(const float* boxes6, uint32_t count, uint32_t depthBudget, uint32_t radius, double* out /* 8 */);
+/* [ext] [debug] the device builder (gi_tlas_build.hip) on the same arguments: the same validation plus the node and item records that differ bytewise from the
+ * host form's (0 is the contract); GI_C_TLAS_BUILD_TOO_DEEP exactly where the host form answers it.  out as above, [5] = waits of the host on the device
+ * inside the build (bounded whatever `count`: gi_tlas_build.h kTlasMaxHostWaits). */
+int giCDebugBuildTlas(const float* boxes6, uint32_t count, uint32_t depthBudget, uint32_t radius, double* out /* 8 */);
+/* [ext] [debug] GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD on this scene: out[0] TLAS builds on the device, fallbacks to the host builder: [1] too deep, [2] out of
+ * memory, [3] error status, [4] fewer instances than tlas_device_min; of the last device build: [5] - [8] stage times in microseconds (upload + boxes + sort,
+ * PLOC, emission, read-back), [9] PLOC passes, [10] host waits, [11] depth, [12] nodes, [13] workspace allocations since the scene was created, [14] 1 when
+ * the resident TLAS was made by the device builder, [15] the depth budget of that build.  All zero with the option off. */
+int giCDebugSceneTlasBuildStats(const GiCScene* scene, uint64_t out[16]);
 /* [ext] [debug] device check of the kernels that make the world boxes of moved instances (gi_tlas.hip k_inst_bounds / k_inst_finish): the mesh (`vertices`,
  * `faces`: 3 indices per face) under each of the `xformCount` instance transforms (16 floats each, USD row vectors).  outBoxes6 (6 floats per transform: min
  * xyz, max xyz, padded) and outStatus (one word per transform, 0 = usable; bits: 1 a corner unusable in object space, 2 in world space, 4 a flattened
