@@ -174,6 +174,7 @@ SYMBOLS = [
     ("giCDebugTexRuntime", C.c_int, [_FP, _U, _U, _U, _U, _FP, _FP]),
     ("giCDebugEditDirtyFlags", C.c_int32, [_I, _I]), ("giCDebugSceneUpdateCounts", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugSceneVisibilityUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugSceneClassState", C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    ("giCDebugSceneUpsPlain", C.c_int, [_P, C.POINTER(C.c_uint32)]), ("giCDebugUpsTraits", C.c_int, [C.POINTER(GiCMaterialDesc), _U, C.c_int, C.POINTER(C.c_uint32)]),
     ("giCDebugSceneVertexUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugRefitBvh", C.c_int, [_FP, _FP, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("giCDebugSceneRefitCheck", C.c_int, [_P, _U, C.POINTER(C.c_uint32)]),
     ("giCDebugSceneTopologyUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]),
@@ -895,6 +896,14 @@ class Scene:
             raise GiError("giCDebugSceneClassState failed")
         return {"classMask": int(c[0]), "classTextured": int(c[1]), "shadeClassMask": int(c[2]), "shadeClassTextured": int(c[3]), "hasCutouts": bool(c[4])}
 
+    def ups_plain(self) -> dict:
+        """giCDebugSceneUpsPlain: `traits` -- what the UsdPreviewSurface materials of the visible meshes have in common (UPS_NOCOAT) as the last scene
+        sync derived it -- and `launched`, the traits the fused kernel of the last render was compiled for (0: the general kernel, or none)."""
+        c = (C.c_uint32 * 2)()
+        if self.L.giCDebugSceneUpsPlain(self.handle, c) != GI_C_OK:
+            raise GiError("giCDebugSceneUpsPlain failed")
+        return {"traits": int(c[0]), "launched": int(c[1])}
+
     def path_walk_stats(self) -> dict:
         """giCDebugPathWalkStats: the fused kernel's trips and walk-step tables of the last render (OPTION_COUNT_TRAVERSAL; all zero otherwise).  stepTrips[k] /
         stepLanes[k]: trips whose closest-hit loop reached step k (7: that and every later step) and the lanes walking then; fewLaneSteps: steps begun with
@@ -1090,6 +1099,22 @@ def shade_class(material) -> int:
     """giCDebugShadeClass: the k_shade variant (shade class) of an untextured material; host only."""
     md = GiCMaterialDesc(material.klass, 0, (C.c_float * P_COUNT)(*np.asarray(material.params, np.float32)))
     return int(load_library().giCDebugShadeClass(C.byref(md)))
+
+
+UPS_NOCOAT = 1  # gi_types.h: the trait of a scene's UsdPreviewSurface materials (Scene.ups_plain)
+
+
+def ups_traits(records, derive: bool = True) -> int:
+    """giCDebugUpsTraits: the traits of a material table alone; host only.  `records`: (klass, flags, params[64]) triples -- with `derive` the parameters are a
+    material description's, without it a derived record's, word for word (so float32 arrays keep the bits they were given)."""
+    descs = (GiCMaterialDesc * max(len(records), 1))()
+    for d, (klass, flags, params) in zip(descs, records):
+        d.klass, d.flags = klass, flags
+        C.memmove(d.p, np.ascontiguousarray(params, np.float32).ctypes.data, 4 * P_COUNT)
+    out = C.c_uint32(0)
+    if load_library().giCDebugUpsTraits(descs, len(records), 1 if derive else 0, C.byref(out)) != GI_C_OK:
+        raise GiError("giCDebugUpsTraits failed")
+    return int(out.value)
 
 
 def bsdf_debug(material, items, device: int = 0):

@@ -75,6 +75,16 @@ uint32_t shadeClassOf(const MaterialRec& m)
   return SHADE_CLASS_OPBR_BASE;
 }
 
+// Traits of one derived UsdPreviewSurface record (gi_types.h UPS_*), for the fused kernel's plain class-1 variant.  The variant drops the `coat * x` products,
+// which is the same arithmetic only for the exact word of +0.0f: -0.0f would make the coat Fresnel -0 (and 1 - Fc, z - Fc other operations), a NaN stays a NaN.
+// A textured record has no trait: the class then runs the textured kernel, whose ups_params recomputes the constants from the hit's texture values.
+uint32_t upsTraitsOf(const MaterialRec& m)
+{
+  if (m.klass != GI_C_MAT_USD_PREVIEW_SURFACE || (m.flags & MAT_FLAG_TEXTURED)) return 0u;
+  uint32_t coat; memcpy(&coat, &m.p[MP_COAT], 4);
+  return coat == 0u ? UPS_NOCOAT : 0u;
+}
+
 // Hostile geometry (bvh8.h "Inactive items").  A coordinate the build works with: finite, at most 1e18 in magnitude.
 inline bool usableCoordinate(float x) { return std::fabs(x) <= 1.0e18f; } // (false for NaN)
 // An instance the flattening can use: every entry of its affine finite and its 3x3 invertible with an inverse that is finite in fp32 (w2o transforms normals
@@ -284,6 +294,7 @@ static void deriveSceneClasses(GiCScene* s, const SceneHost& H, bool newTree)
 {
   const bool hadCutouts = s->hasCutouts;
   s->classMask = 0; s->classTextured = 0; s->shadeClassMask = 0; s->shadeClassTextured = 0; s->hasCutouts = false;
+  uint32_t ups = UPS_NOCOAT; // what the class-1 materials in use have in common
   for (const MeshBuild& mb : H.meshBuilds) {
     if (mb.hidden) continue;
     const MaterialRec& mr = H.mats[mb.matFlags & 0x00ffffffu];
@@ -291,7 +302,9 @@ static void deriveSceneClasses(GiCScene* s, const SceneHost& H, bool newTree)
     s->classMask |= klassBit; s->shadeClassMask |= shadeBit;
     if (mr.flags & MAT_FLAG_TEXTURED) { s->classTextured |= klassBit; s->shadeClassTextured |= shadeBit; }
     if (mb.matFlags & (1u << 28)) s->hasCutouts = true;
+    if (mr.klass == GI_C_MAT_USD_PREVIEW_SURFACE) ups &= upsTraitsOf(mr);
   }
+  s->upsTraits = (s->classMask & 2u) ? ups : 0u;
   if (newTree || s->hasCutouts != hadCutouts) resetShadowOrder(s);
 }
 

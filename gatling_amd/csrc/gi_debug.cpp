@@ -786,6 +786,34 @@ extern "C" int giCDebugSceneClassState(const GiCScene* scene, uint32_t* out)
   return GI_C_OK;
 }
 
+// giCDebugSceneUpsPlain: the traits of the scene's class-1 materials (gi_build.cpp deriveSceneClasses) as the last scene sync left them, and the traits the
+// last render's fused launch was compiled for.  Host only.
+extern "C" int giCDebugSceneUpsPlain(const GiCScene* scene, uint32_t* out)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!s || !out) { setError("giCDebugSceneUpsPlain: bad arguments"); return GI_C_ERROR; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  out[0] = s->upsTraits; out[1] = s->upsPlainLaunched;
+  return GI_C_OK;
+}
+
+// giCDebugUpsTraits: the same rule on a material table alone -- what a scene whose visible meshes use exactly these materials would report.  `derive`: the
+// descriptions are a caller's, and their constants are derived as a build derives them; 0: they are derived records already (MaterialRec::p word for word).
+// A description's flags are taken as they are (MAT_FLAG_TEXTURED: a record with a bound input).  Host only: no scene.
+extern "C" int giCDebugUpsTraits(const GiCMaterialDesc* descs, uint32_t count, int derive, uint32_t* out)
+{
+  if (!out || (count && !descs)) { setError("giCDebugUpsTraits: bad arguments"); return GI_C_ERROR; }
+  uint32_t ups = UPS_NOCOAT; bool any = false;
+  for (uint32_t i = 0; i < count; i++) {
+    MaterialRec m{}; m.klass = descs[i].klass; m.flags = descs[i].flags; memcpy(m.p, descs[i].p, sizeof(m.p));
+    if (derive) deriveMaterialConstants(m);
+    if (m.klass != GI_C_MAT_USD_PREVIEW_SURFACE) continue;
+    any = true; ups &= upsTraitsOf(m);
+  }
+  *out = any ? ups : 0u;
+  return GI_C_OK;
+}
+
 // ---- the TLAS builders of an edit (gi_tlas_build.h): giCDebugBuildTlasHost / giCDebugBuildTlas ---------------------------------------------------------------
 namespace {
 

@@ -404,6 +404,9 @@ struct GiCScene : SceneDevice {
   uint32_t classTextured = 0; // classes with at least one textured material in use (k_shade<class, TEXTURED>)
   // the same per SHADE class (gi_types.h: the HIT queues of the wavefront pipeline; classMask / classTextured pick the fused kernels)
   uint32_t shadeClassMask = 0, shadeClassTextured = 0;
+  // what every class-1 material in use has in common (gi_types.h UPS_NOCOAT; 0 when the class is textured or absent): the fused kernel's plain
+  // UsdPreviewSurface variant.  upsPlainLaunched: the traits the last render's k_path launch was compiled for (0: the general text, or no fused launch)
+  uint32_t upsTraits = 0, upsPlainLaunched = 0;
   std::unique_ptr<SceneHost> host; // the scene as host arrays, kept for incremental transform updates
   std::vector<std::unique_ptr<SceneDevice>> replicas; // devices 1 .. N-1 (created with the first build when the library runs on several devices)
   // options + stats
@@ -489,6 +492,7 @@ extern "C++" bool loadImage(const char* path, bool srgbToLinear, bool keepHdr, u
 int uploadLights(GiCScene* s);
 // gi_build.cpp
 uint32_t shadeClassOf(const MaterialRec& m);                 // shade class (k_shade variant) of a derived material record
+uint32_t upsTraitsOf(const MaterialRec& m);                  // UPS_* traits of one derived class-1 record (the scene's: their intersection, deriveSceneClasses)
 uint32_t sceneDeviceCount(const GiCScene* s);                // devices a render of this scene may use
 SceneDevice& sceneDevice(GiCScene* s, uint32_t slot);
 bool usableVertexPositions(const GiCVertex* v, size_t count);  // every position finite and within 1e18 (bvh8.h "Inactive items")

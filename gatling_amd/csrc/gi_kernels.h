@@ -63,8 +63,15 @@ bool pathKernelSupports(const SceneView& sc);
 // lobePark: k_path's class-1 variants without NEE park hits that drew a glossy lobe and shade them together once this many are parked (0: off); the general
 // variant takes it in counting builds only, every other variant ignores it
 // ringCarry: the variants without NEE carry the triangle ring across the steps of a trip's closest-hit loop and flush it once (0: every step empties it)
+// upsTraits: what the scene's class-1 materials have in common (gi_types.h UPS_*; 0: nothing, or the switch is off).  pathUpsVariant is the rule: the traits the
+// kernel launchPath picks is compiled for -- the hot class-1 kernel without NEE takes them, every other one is the general text (0)
 int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool textured, bool count, uint32_t chunk, uint32_t walkCarry, uint32_t lobePark,
-               uint32_t ringCarry, const FrameUniforms& U, const SceneView& sc, const PathState& st, Counters* cnt, F4* sampleBuf);
+               uint32_t ringCarry, uint32_t upsTraits, const FrameUniforms& U, const SceneView& sc, const PathState& st, Counters* cnt, F4* sampleBuf);
+inline uint32_t pathUpsVariant(uint32_t classMask, bool textured, bool nee, bool cutout, bool count, uint32_t upsTraits)
+{
+  return (classMask == 2u && !textured && !cutout && !count && !nee) ? upsTraits : 0u;
+}
+constexpr long UPS_PLAIN_DEFAULT = 1;  // GATLING_OPTIONS=ups_plain (gi_options.h)
 constexpr long WALK_CARRY_DEFAULT = 8; // GATLING_OPTIONS=walk_carry (gi_options.h)
 constexpr long LOBE_PARK_DEFAULT = 8;  // GATLING_OPTIONS=lobe_park (gi_options.h)
 constexpr long RING_CARRY_DEFAULT = 1; // GATLING_OPTIONS=ring_carry (gi_options.h)

@@ -33,6 +33,10 @@
 //                                  rest (gi_path.hip).  0 = every step ends with a batch over whatever is pending.  Counting builds run with 0 unless the
 //                                  key is set explicitly: a lagging culling distance moves their node and triangle counts (giCDebugPathRingStats shows
 //                                  the batches either way)
+//   ups_plain            1         fused frames without next-event estimation whose materials are all untextured UsdPreviewSurface: k_path runs the variant
+//                                  compiled for what those materials have in common -- no coat (clearcoat +0 in every one) -- which leaves out the
+//                                  operations that are exact identities then (gi_shading.h bsdf_sample; the traits: gi_build.cpp
+//                                  deriveSceneClasses, giCDebugSceneUpsPlain).  0 = the general class-1 kernel.  Counting builds never run the variant
 //   fused                1         LDS-resident scenes run the fused persistent kernel
 //   pool_slots           0         pin the path pool (slots); 0 = the memory plan decides
 //   sample_buffer_mb     0         pin the per-sample buffer (MiB); 0 = the memory plan decides

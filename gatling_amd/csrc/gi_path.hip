@@ -32,6 +32,10 @@
 // a triangle batch runs whenever 64 pairs are pending and one flush in the loop's last step tests the rest, instead of a partial batch at the end of every
 // step.  Hit keys do not depend on when a pair is tested; ringCarry = 0 flushes in every step.
 //
+// A scene whose class-1 materials are all untextured and have no coat (UPS_NOCOAT, gi_types.h; the host derives it: gi_build.cpp deriveSceneClasses) runs the
+// instantiation whose class-1 sample leaves the coat lobe out (the NEE-off class-1 variant; UPS, the last template argument; gi_shading.h ups_plain_sample): the
+// operations dropped are exact identities when coat is the word of +0, so the bits are the same.  UPS = 0 is the kernel as it was; ups_plain=0 selects it.
+//
 // Not handled here (the host falls back to the wavefront pipeline): medium stacks (mediumStackSize > 0), dome-light images,
 // scenes beyond LDS, trees deeper than 8 levels.
 
@@ -53,7 +57,7 @@ constexpr uint32_t PRE_FIELDS = 10; // prepared camera ray: origin, direction, t
 constexpr uint32_t PATH_STACK_MAX = 8; // LDS traversal-stack entries per lane: 4 for trees of depth <= 4 (cornell), else 8 (the host checks bvhDepth <= 8)
 
 constexpr int PATH_WAVES = 4; // resident waves per SIMD the register allocation aims for (114 VGPRs without a hint; 3 cost 11 %, 5 spill 26 registers: r03)
-template <uint32_t KLASS, bool TEXTURED, bool NEE, bool CUTOUT, bool COUNT, uint32_t PATH_STACK>
+template <uint32_t KLASS, bool TEXTURED, bool NEE, bool CUTOUT, bool COUNT, uint32_t PATH_STACK, uint32_t UPS = 0u>
 __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PATH_WAVES, 8))) void k_path(FrameUniforms U, SceneView sc, PathState st,
     Counters* cnt, F4* __restrict__ sampleBuf, uint32_t ldsNodes, uint32_t ldsTris, uint32_t chunk, uint32_t walkCarry, uint32_t lobePark, uint32_t lotRow,
     uint32_t lotCap, uint32_t ringCarry)
@@ -255,7 +259,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
         if constexpr (!PARK) {
           io.throughput = thr; io.radiance = rad; io.bitfield = bitfield; io.rng = rng;
           const F4 h = F4{R.tBest, R.bestU, R.bestV, u2f(R.bestTri)}, rd = F4{rdv.x, rdv.y, rdv.z, 0.0f};
-          shade_segment<KLASS, TEXTURED, false, NEE, false, DEFER>(U, sc, nullptr, h, rd, io);
+          shade_segment<KLASS, TEXTURED, false, NEE, false, DEFER, UPS>(U, sc, nullptr, h, rd, io);
           thr = io.throughput; rad = io.radiance; bitfield = io.bitfield; rng = io.rng;
           // untraced shadow ray == "not shadowed" (rp_main.rgen:431-435)
           if (NEE && st.neeKey && io.shadowFirst && !io.shadow) nee_aov_record_px(st, rec % U.pixelCount, rec / U.pixelCount, false);
@@ -289,7 +293,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
       auto shade_hit = [&]() __attribute__((always_inline)) {
         io.throughput = thr; io.radiance = rad; io.bitfield = bitfield; io.rng = rng;
         const F4 h = F4{R.tBest, R.bestU, R.bestV, u2f(R.bestTri)}, rd = F4{rdv.x, rdv.y, rdv.z, 0.0f};
-        shade_segment<KLASS, TEXTURED, false, NEE, false, DEFER>(U, sc, nullptr, h, rd, io);
+        shade_segment<KLASS, TEXTURED, false, NEE, false, DEFER, UPS>(U, sc, nullptr, h, rd, io);
         if (io.deferred) return;
         thr = io.throughput; rad = io.radiance; bitfield = io.bitfield; rng = io.rng;
         ended = !io.cont;
@@ -433,13 +437,17 @@ using PathKernel = void (*)(FrameUniforms, SceneView, PathState, Counters*, F4*,
 // Hot variants: one material class, no textures, no cutouts, no counters (the C1 / C2 paths).  Everything else runs the general
 // variant (class read from the material record, textures and cutouts compiled in).
 template <uint32_t STACK>
-static PathKernel pickPathKernel(uint32_t classMask, bool textured, bool nee, bool cutout, bool count)
+static PathKernel pickPathKernel(uint32_t classMask, bool textured, bool nee, bool cutout, bool count, uint32_t upsTraits)
 {
   const bool hot = (classMask == 1u || classMask == 2u || classMask == 4u) && !textured && !cutout && !count;
+  const uint32_t ups = pathUpsVariant(classMask, textured, nee, cutout, count, upsTraits);
   return dispatchBools([&](auto neeC) -> PathKernel {
     constexpr bool NEE = decltype(neeC)::value;
     if (hot) {
       if (classMask == 1u) return k_path<0u, false, NEE, false, false, STACK>;
+      if constexpr (!NEE) { // the plain UsdPreviewSurface variant (gi_shading.h ups_plain_sample)
+        if (ups == UPS_NOCOAT) return k_path<1u, false, false, false, false, STACK, UPS_NOCOAT>;
+      }
       if (classMask == 2u) return k_path<1u, false, NEE, false, false, STACK>;
       return k_path<2u, false, NEE, false, false, STACK>;
     }
@@ -448,7 +456,7 @@ static PathKernel pickPathKernel(uint32_t classMask, bool textured, bool nee, bo
 }
 
 int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool textured, bool count, uint32_t chunk, uint32_t walkCarry, uint32_t lobePark,
-               uint32_t ringCarry, const FrameUniforms& U, const SceneView& sc, const PathState& st, Counters* cnt, F4* sampleBuf)
+               uint32_t ringCarry, uint32_t upsTraits, const FrameUniforms& U, const SceneView& sc, const PathState& st, Counters* cnt, F4* sampleBuf)
 {
   if (U.workTotal == 0u) return 0; // an empty active rectangle (FLAG_MISS_RECT, the camera looks away): no pixel needs a path
   const uint32_t ldsNodes = sc.nodeCount, ldsTris = sc.triCount;
@@ -458,7 +466,8 @@ int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool texture
   const uint32_t bytes = traceLdsBytes(stack, ldsNodes, ldsTris);
   const bool neeOn = (U.flags & FLAG_NEE) != 0u;
   PathKernel k = stack == 4u
-      ? pickPathKernel<4u>(classMask, textured, neeOn, sc.hasCutouts != 0u, count) : pickPathKernel<8u>(classMask, textured, neeOn, sc.hasCutouts != 0u, count);
+      ? pickPathKernel<4u>(classMask, textured, neeOn, sc.hasCutouts != 0u, count, upsTraits)
+      : pickPathKernel<8u>(classMask, textured, neeOn, sc.hasCutouts != 0u, count, upsTraits);
   // Resident blocks per CU (4 waves per block = 1 wave per SIMD and block): the smaller of what the 160 KiB of LDS and the 512-entry
   // register file of a SIMD hold.  (hipOccupancyMaxActiveBlocksPerMultiprocessor answered 3 for a 35 KiB block: it does not know gfx950's LDS size.)
   int perCu = 2;

@@ -435,6 +435,7 @@ struct Schedule {
   uint32_t walkCarry = 0u;      // k_path: the closest-hit loop of a trip ends once at most this many lanes are still walking (0: never early)
   uint32_t lobePark = 0u;       // k_path: hits that drew a glossy lobe are parked and shaded together once this many wait (0: shaded where they are)
   uint32_t ringCarry = 0u;      // k_path: the triangle ring is carried across the steps of a trip's closest-hit loop (0: every step empties it)
+  uint32_t upsTraits = 0u;      // k_path: the traits of the scene's class-1 materials its plain variant may be compiled for (0: the general kernel)
   int32_t shadowOrderNow = -1;  // visiting order of the shadow walks; -1: not chosen yet -- alternate, and count (chooseShadowOrder)
 };
 struct Frame {
@@ -530,6 +531,10 @@ static Schedule scheduleFrame(Frame& f)
   // Ring carry of k_path (gi_path.hip): pending (ray, triangle) pairs wait for a full batch across the steps of a trip.  A walk then culls with a distance
   // that may lag by a step, so a counting build's nodesVisited / trisTested move with it: the same rule again, off there unless the key is set.
   sch.ringCarry = s->countTraversal && !optionSet("ring_carry") ? 0u : (optionValue("ring_carry", RING_CARRY_DEFAULT) != 0 ? 1u : 0u);
+  // The plain UsdPreviewSurface variant of k_path (gi_path.hip): the scene's traits (deriveSceneClasses) unless switched off.  Which kernels take them is
+  // launchPath's rule (pathUpsVariant); counting builds run the general kernel, whose counters the tests read.
+  f.s->upsPlainLaunched = 0u; // giCDebugSceneUpsPlain: until a fused batch of this render launches (runFusedBatch)
+  sch.upsTraits = !s->countTraversal && optionValue("ups_plain", UPS_PLAIN_DEFAULT) != 0 ? s->upsTraits : 0u;
   sch.dynRefill = traceDynRefill(s);
   // (GATLING_OPTIONS=shadow_order=0|1 pins it)
   sch.shadowOrderNow = optionSet("shadow_order") ? (int32_t)optionValue("shadow_order", -1) : s->shadowOrder.load();
@@ -584,7 +589,7 @@ static void accumulateBatch(Frame& f, uint32_t batch)
 // LDS-resident scenes: one launch of the fused persistent kernel k_path runs the batch's paths from camera ray to retirement
 static int runFusedBatch(Frame& f, uint32_t batch)
 {
-  const GiCScene* s = f.s; SceneDevice& D = f.D; const FrameUniforms& U = f.U;
+  GiCScene* s = f.s; SceneDevice& D = f.D; const FrameUniforms& U = f.U;
   // work items are claimed in chunks of consecutive ids; small frames get small chunks so that every resident wave finds work
   uint32_t chunk = 2048u;
   const uint64_t waves = (uint64_t)f.ctx.cuCount * 16u;
@@ -593,9 +598,11 @@ static int runFusedBatch(Frame& f, uint32_t batch)
   chunk = (uint32_t)std::min<uint64_t>(chunk, std::max<uint64_t>(64u, ((uint64_t)U.workTotal / (waves * 16u)) & ~63ull));
   f.tm.beginIteration(true); // one launch per batch: timed whatever the stride
   f.tm.timed(f.st, StageTimers::TRACE, [&] {
-    launchPath(f.st, (uint32_t)f.ctx.cuCount, s->classMask, s->classTextured != 0u, s->countTraversal, chunk, f.sch.walkCarry, f.sch.lobePark, f.sch.ringCarry, U, f.view, f.ps,
-               D.dCounters.ptr, D.sampleBuf.ptr);
+    launchPath(f.st, (uint32_t)f.ctx.cuCount, s->classMask, s->classTextured != 0u, s->countTraversal, chunk, f.sch.walkCarry, f.sch.lobePark, f.sch.ringCarry,
+               f.sch.upsTraits, U, f.view, f.ps, D.dCounters.ptr, D.sampleBuf.ptr);
   });
+  // (every device of the render launches the same variant: one value, whoever writes it)
+  s->upsPlainLaunched = pathUpsVariant(s->classMask, s->classTextured != 0u, (U.flags & FLAG_NEE) != 0u, f.view.hasCutouts != 0u, s->countTraversal, f.sch.upsTraits);
   f.iters++; f.tm.totalIters++; f.traceLaunches++;
   accumulateBatch(f, batch);
   return GI_C_OK;

@@ -946,15 +946,53 @@ __device__ __forceinline__ V3 diffuse_class_color(const MaterialRec* m, const Sh
   return (st.texMask & (1u << TEX_BASE_COLOR)) ? st.texBaseColor : v3(m->p[0], m->p[1], m->p[2]);
 }
 
+// The class-1 sample of bsdf_sample below for a scene whose UsdPreviewSurface materials are all untextured and have no coat (UPS_NOCOAT, gi_types.h; derived by
+// the host, gi_build.cpp deriveSceneClasses): the same statements with the operations left out that are exact identities then, so a hit shades to the same bits
+// through either form (tests/test_gpu_path_ups_plain.py holds both to the oracle).  coat is the word of +0.0f.  nk1 >= 1e-4 is never NaN (fmax2(a, b) is
+// a > b ? a : b) and schlick_w clamps to [0, 1], so 0.04 + 0.96 w is finite and positive and Fc = (+0) x that = +0 at every hit.  Then !(z < Fc) holds for every
+// z in [0, 1); z - 0 = z, 1 - 0 = 1 and the correctly rounded z / 1 is z (one lean division and its wave-wide range test, a branch, gone); (1 - Fc) X = 1 X = X;
+// lobe 0, the coat's, is unreachable, and with it the choice of alpha and the coat's weight in the GGX block.  coat and coatAlpha are not loaded.
+// bsdf_evaluate<1> (next-event estimation) keeps its text: dropping Fch x fc there turns (+0) + X into X, which differs for X = -0, and needs fc finite --
+// both provable only under more conditions than this one.
+template <bool DEFER>
+__device__ __forceinline__ void ups_plain_sample(const MaterialRec* m, const ShState& st, V3 k1, float x0, float x1, float x2, BsdfSample& out, bool lite)
+{
+  const V3 albedo = v3(m->p[MP_ALBEDO], m->p[MP_ALBEDO + 1], m->p[MP_ALBEDO + 2]), F0 = v3(m->p[MP_F0], m->p[MP_F0 + 1], m->p[MP_F0 + 2]);
+  const float alpha = m->p[MP_ALPHA];
+  V3 l1 = to_local(st, k1);
+  float nk1 = fmax2(l1.z, 1e-4f); l1.z = nk1;
+  const V3 Fs = schlick3(F0, nk1);
+  const float ps = fmax2(Fs.x, fmax2(Fs.y, Fs.z));
+  if (x2 < ps) { // the specular lobe
+    if (DEFER) { out.glossyLobe = true; if (lite) { out.deferred = true; return; } }
+    GgxOut g = ggx_sample(l1, alpha, x0, x1);
+    V3 k2 = to_world(st, g.l2);
+    if (!g.valid || !(dot(k2, st.geomNormal) > 0.0f)) return;
+    out.k2 = k2; out.event = EV_GLOSSY | EV_REFLECTION;
+    V3 Fh = schlick3(F0, g.kh);
+    out.pdf = ps * g.pdf; out.overPdf = Fh * gi_div(g.g2OverG1, ps);
+    return;
+  }
+  V3 l = gi_sample_hemisphere(x0, x1);
+  V3 k2 = to_world(st, l);
+  if (!(l.z > 0.0f) || !(dot(k2, st.geomNormal) > 0.0f)) return;
+  out.k2 = k2; out.pdf = (1.0f - ps) * gi_div(l.z, GI_PI);
+  out.overPdf = (albedo * (v3(1.0f, 1.0f, 1.0f) - Fs)) * gi_rcp(1.0f - ps);
+  out.event = EV_DIFFUSE | EV_REFLECTION;
+}
+
 constexpr uint32_t KLASS_DYNAMIC = 0xffffffffu; // read the class from the material record (debug / AOV paths)
 // DEFER (k_path's lobe parking, gi_path.hip): the deferring form of the class-1 sample.  It reports whether the hit drew a glossy lobe (coat or specular:
 // the GGX block below), and with the wave-uniform `lite` set such a hit leaves at once, marked `deferred` -- nothing else of `out` means anything then, and the
 // caller shades the hit again later from the same state, with lite = false.  DEFER = false is the function as it always was.
-template <uint32_t KLASS, bool DEFER = false>
+// UPS (class 1 only; k_path's plain variant): what the scene's materials share (UPS_NOCOAT) -- the class-1 sample is ups_plain_sample above.  0: today's text.
+template <uint32_t KLASS, bool DEFER = false, uint32_t UPS = 0u>
 __device__ inline void bsdf_sample(const MaterialRec* m, const ShState& st, V3 k1, float x0, float x1, float x2, BsdfSample& out, bool lite = false)
 {
+  static_assert(UPS == 0u || (KLASS == 1u && UPS == UPS_NOCOAT), "the traits are those of UsdPreviewSurface materials");
   out.event = EV_ABSORB; out.pdf = 0.0f; out.overPdf = v3(0.0f, 0.0f, 0.0f); out.k2 = v3(0.0f, 0.0f, 0.0f);
   if (DEFER) { out.glossyLobe = false; out.deferred = false; }
+  if constexpr (UPS != 0u) { ups_plain_sample<DEFER>(m, st, k1, x0, x1, x2, out, lite); return; }
   const uint32_t klass = (KLASS == KLASS_DYNAMIC) ? m->klass : KLASS;
   if (klass == 0u) {
     V3 l = gi_sample_hemisphere(x0, x1);

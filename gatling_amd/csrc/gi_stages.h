@@ -73,12 +73,14 @@ struct ShadeIO {
 // glossy lobe; with io.lite set such a hit comes back `deferred` and the caller must take NOTHING from the call: throughput, radiance (the emission added above
 // the sample included), bitfield and rng are as they went in, no out field is written.  Shading the hit later from that state, lite = false, repeats the same
 // draws and the same arithmetic.  Without DEFER the three fields are never touched and the function is what it was.
-template <uint32_t KLASS, bool TEXTURED, bool VOLUME, bool NEE, bool PACKED = false, bool DEFER = false>
+// UPS (k_path's plain UsdPreviewSurface variant): the traits the class-1 sample is compiled for (gi_shading.h ups_plain_sample); 0: the function as it was.
+template <uint32_t KLASS, bool TEXTURED, bool VOLUME, bool NEE, bool PACKED = false, bool DEFER = false, uint32_t UPS = 0u>
 __device__ __forceinline__ void shade_segment(const FrameUniforms& U, const SceneView& sc, float* M /* medium stack of the path (VOLUME) */, const F4& h,
     const F4& rd, ShadeIO& io)
 {
   static_assert(KLASS != SHADE_CLASS_OPBR_BASE || (!TEXTURED && !VOLUME),
       "the BASE variant exists for untextured materials in renders without a medium stack (launchShade sends the others through the full kernel)");
+  static_assert(UPS == 0u || (KLASS == 1u && !TEXTURED && !NEE), "the plain variant: untextured UsdPreviewSurface, sample only (bsdf_evaluate keeps its text)");
   V3 throughput = io.throughput, radiance = io.radiance; uint32_t bitfield = io.bitfield, rng = io.rng;
   bool cont = false, shadow = false, shadowFirst = false; uint32_t rngShadow = 0u;
   V3 no = v3(0.0f, 0.0f, 0.0f), k2 = no, sdir = no, nee = no; float ld = 0.0f, tMaxNext = GI_FLT_MAX;
@@ -154,10 +156,10 @@ __device__ __forceinline__ void shade_segment(const FrameUniforms& U, const Scen
     bs.event = EV_ABSORB; bs.pdf = 0.0f; bs.overPdf = v3(0.0f, 0.0f, 0.0f); bs.k2 = v3(0.0f, 0.0f, 0.0f); // (bsdf_sample's initialisation)
     opbr_base_sample(mat, ss, -rayDir, x0, x1, x2, bs, &baseCtx);
   } else if constexpr (DEFER) {
-    bsdf_sample<KLASS, true>(mat, ss, -rayDir, x0, x1, x2, bs, io.lite);
+    bsdf_sample<KLASS, true, UPS>(mat, ss, -rayDir, x0, x1, x2, bs, io.lite);
     io.glossyLobe = bs.glossyLobe; io.deferred = bs.deferred;
     if (bs.deferred) return;
-  } else bsdf_sample<KLASS>(mat, ss, -rayDir, x0, x1, x2, bs);
+  } else bsdf_sample<KLASS, false, UPS>(mat, ss, -rayDir, x0, x1, x2, bs);
   throughput = throughput * bs.overPdf;
   k2 = bs.k2;
   const bool isTransmission = (bs.event & EV_TRANSMISSION) != 0u;

@@ -97,6 +97,10 @@ constexpr uint32_t MP_FEATURES = 54, MATF_THIN_WALLED = 1u, MATF_FUZZ = 2u, MATF
                    MATF_SPEC_ROTATION = 64u;
 enum : uint32_t { MP_ALBEDO = 32, MP_F0 = 35, MP_ALPHA = 38, MP_COAT = 39, MP_COAT_ALPHA = 40, MP_COAT_F0 = 41, MP_ETA = 42, MP_SIGMA_A = 43,
     MP_CUTOUT = 46 /* mdl_cutout_opacity, 1 = opaque */ };
+// Trait of a scene's untextured class-1 (UsdPreviewSurface) materials, a compile-time mask of the fused kernel's class-1 sample (gi_shading.h bsdf_sample):
+// NOCOAT -- MP_COAT is the word of +0.0f in every one (clearcoat 0, the schema's default).  Derived by the host: gi_build.cpp upsTraitsOf / deriveSceneClasses.
+// (A second trait, equal F0 channels, was measured and not kept: DESIGN.md section 9.)
+constexpr uint32_t UPS_NOCOAT = 1u;
 // Textured material inputs (UsdUVTexture semantics: value = texel * scale + bias at the hit's st).  Replaces the MDL
 // renderer runtime's tex_lookup_* path (mdl_interface.glsl:127-145) for the inputs the closed-form materials expose.
 enum : uint32_t { TEX_BASE_COLOR = 0, TEX_EMISSION = 1, TEX_ROUGHNESS = 2, TEX_METALLIC = 3, TEX_NORMAL = 4,

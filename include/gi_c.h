@@ -386,7 +386,8 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * giCDebugPatchVisibilityTwoLevel, and for GI_C_SCENE_OPTION_TLAS_ONLY and giCDebugSceneFlatTreeState, and for GI_C_SCENE_OPTION_TLAS_TOPOLOGY,
  * giCDebugSceneTlasTopologyUpdateCount, giCDebugAppendRecords and giCDebugAppendRecordsHost, and for GI_C_SCENE_OPTION_TLAS_INSTANCES,
  * giCDebugSceneTlasInstanceUpdateStats, giCDebugInstanceRecords and giCDebugInstanceRecordsHost, and for giCDebugTraversalStackHigh and giCDebugBvhStackReach,
- * and for GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD, giCDebugBuildTlasHost, giCDebugBuildTlas and giCDebugSceneTlasBuildStats. */
+ * and for GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD, giCDebugBuildTlasHost, giCDebugBuildTlas and giCDebugSceneTlasBuildStats, and for giCDebugSceneUpsPlain and
+ * giCDebugUpsTraits. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -910,6 +911,15 @@ int giCDebugPatchVisibilityTwoLevel(const uint32_t* faceCounts, const uint8_t* h
  * use (one bit each), [1] those with a textured material, [2] and [3] the same per shade class, [4] 1 when some visible triangle has cutout opacity.  Host
  * only: no device work. */
 int giCDebugSceneClassState(const GiCScene* scene, uint32_t* out /* 5 */);
+/* [ext] the plain UsdPreviewSurface variant of the fused path kernel: out[0] what every UsdPreviewSurface material of the visible meshes has in common, as the
+ * last scene sync derived it -- bit 0: clearcoat is the word of +0.0f in every one; 0 when one of them binds a texture or a primvar, or the scene has none --
+ * and out[1] the traits the fused kernel of the scene's last render was
+ * compiled for (0: the general kernel ran -- $GATLING_OPTIONS ups_plain=0, next-event estimation, other classes in use, a counting build --, or no fused
+ * kernel).  Host only: no device work. */
+int giCDebugSceneUpsPlain(const GiCScene* scene, uint32_t* out /* 2 */);
+/* [ext] out[0] of giCDebugSceneUpsPlain for a scene whose visible meshes would use exactly the `count` materials of `descs`.  derive != 0: the descriptions are
+ * what giCCreateMaterial takes; 0: `p` holds derived records word for word.  `flags` bit 31 marks a material with a bound input.  Host only: no scene. */
+int giCDebugUpsTraits(const GiCMaterialDesc* descs, uint32_t count, int derive, uint32_t* out /* 1 */);
 /* [ext] the fused path kernel's walk counters of the scene's last render, for renders with GI_C_SCENE_OPTION_COUNT_TRAVERSAL (all zero otherwise): out[0] trips
  * of all waves, [1 + k] the trips whose closest-hit loop reached step k (k = 7: every step from the eighth on), [9 + k] the lanes walking when those steps
  * began, [17] the steps that began with fewer than 8 lanes walking.  With $GATLING_OPTIONS walk_carry=K set explicitly a counting build carries walks as other
