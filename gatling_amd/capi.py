@@ -196,6 +196,9 @@ SYMBOLS = [
     ("giCDebugSceneTlasInstanceUpdateStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugBuildTlasHost", C.c_int, [_FP, _U, _U, _U, C.POINTER(C.c_double)]),
     ("giCDebugBuildTlas", C.c_int, [_FP, _U, _U, _U, C.POINTER(C.c_double)]),
+    ("giCDebugBuildBlasHost", C.c_int, [_P, _U, _P, _U, _U, _U, C.POINTER(C.c_double)]),
+    ("giCDebugBuildBlas", C.c_int, [_P, _U, _P, _U, _U, _U, C.POINTER(C.c_double)]),
+    ("giCDebugSceneBlasBuildStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugSceneTlasBuildStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugPatchVisibilityTwoLevel", C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _U, _U, C.POINTER(C.c_uint32)]),
     ("giCDebugPathWalkStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
@@ -291,6 +294,7 @@ def debug_clone_instance(vertices, faces, xform_a, xform_b, left_handed=False) -
     return int(n)
 
 
+OPTION_BLAS_DEVICE_BUILD = 23  # 1: the BLAS of a mesh of blas_device_min .. blas_device_max faces of a two-level scene is built on the primary device (gi_blas_build.hip: face boxes from the uploaded points, then the device TLAS builder's stages under a deeper budget) instead of with the host builder, which remains the fallback; read at the scene build and where option 20 applies a mesh create (include/gi_c.h); 0 = off (default)
 TLAS_BUILD_TOO_DEEP = -2  # GI_C_TLAS_BUILD_TOO_DEEP
 
 
@@ -309,6 +313,29 @@ def debug_build_tlas(boxes, depth_budget=7, radius=16, host_only=False) -> dict:
         raise GiError("giCDebugBuildTlas failed: " + L.giCGetLastError().decode())
     return {"violations": int(v), "nodes": int(out[0]), "depth": int(out[1]), "passes": int(out[2]), "cost": float(out[3]), "host_cost": float(out[4]),
             "host_waits": int(out[5]), "host_depth": int(out[6]), "active": int(out[7])}
+
+
+def debug_build_blas(vertices, faces, depth_budget=12, radius=16, host_only=False) -> dict:
+    """giCDebugBuildBlasHost (`host_only`: no device is used) / giCDebugBuildBlas: the BLAS builder of OPTION_BLAS_DEVICE_BUILD over one mesh (`vertices`:
+    VERTEX_DTYPE, `faces`: n x 3 indices) with at most `depth_budget` levels and PLOC radius `radius`.  Returns {"violations": broken rules of the tree -- plus,
+    for the device builder, the node / order / mlo / mhi bytes that differ from the host form's -- (0 is the contract), or TLAS_BUILD_TOO_DEEP; "nodes",
+    "depth", "passes", "cost" and "host_cost" (the SAH model cost of this tree and of the host builder's), "host_waits", "host_depth", "active",
+    "conservative" (blasConservativeViolations), "rules" (depth within the budget, every usable face named once, unusable faces behind in input order,
+    children behind parents), "levels" (level table), "bounds_bytes" (mlo / mhi against the host builder's), "tlas_records" (records that differ from the TLAS
+    builder's host form over the same boxes; compared for depth_budget <= 7), "refit_bytes" (node bytes a refit over the unchanged points changes), "budget",
+    "differing_bytes" (device against host form)}."""
+    from .scene import VERTEX_DTYPE
+    L = load_library()
+    v = np.ascontiguousarray(vertices, VERTEX_DTYPE)
+    f = np.ascontiguousarray(faces, np.uint32).reshape(-1, 3)
+    out = (C.c_double * 16)()
+    fn = L.giCDebugBuildBlasHost if host_only else L.giCDebugBuildBlas
+    r = fn(v.ctypes.data, len(v), f.ctypes.data, len(f), int(depth_budget), int(radius), out)
+    if r < 0 and r != TLAS_BUILD_TOO_DEEP:
+        raise GiError("giCDebugBuildBlas failed: " + L.giCGetLastError().decode())
+    return {"violations": int(r), "nodes": int(out[0]), "depth": int(out[1]), "passes": int(out[2]), "cost": float(out[3]), "host_cost": float(out[4]),
+            "host_waits": int(out[5]), "host_depth": int(out[6]), "active": int(out[7]), "conservative": int(out[8]), "rules": int(out[9]), "levels": int(out[10]),
+            "bounds_bytes": int(out[11]), "tlas_records": int(out[12]), "refit_bytes": int(out[13]), "budget": int(out[14]), "differing_bytes": int(out[15])}
 
 
 def debug_instance_bounds(vertices, faces, xforms):
@@ -669,6 +696,17 @@ class Scene:
         return {"device_builds": int(out[0]), "too_deep": int(out[1]), "out_of_memory": int(out[2]), "error": int(out[3]), "under_min": int(out[4]),
                 "stage_us": [int(out[5 + k]) for k in range(4)], "passes": int(out[9]), "host_waits": int(out[10]), "depth": int(out[11]), "nodes": int(out[12]),
                 "allocations": int(out[13]), "resident_device_built": int(out[14]), "budget": int(out[15])}
+
+    def blas_build_stats(self) -> dict:
+        """giCDebugSceneBlasBuildStats: the BLAS builds of this scene under OPTION_BLAS_DEVICE_BUILD.  Returns {"device_builds", "under_min", "over_max", "too_deep",
+        "out_of_memory", "error" (the five fallbacks to the host builder), "stage_us" (upload + face boxes + sort, PLOC, emission, read-back of the last device
+        build), "passes", "host_waits", "depth", "nodes", "budget", "resident_device_built" (meshes of the resident scene)}.  All zero with the option off."""
+        out = (C.c_uint64 * 16)()
+        if self.L.giCDebugSceneBlasBuildStats(self.handle, out) != GI_C_OK:
+            raise GiError("giCDebugSceneBlasBuildStats failed")
+        return {"device_builds": int(out[0]), "under_min": int(out[1]), "over_max": int(out[2]), "too_deep": int(out[3]), "out_of_memory": int(out[4]),
+                "error": int(out[5]), "stage_us": [int(out[6 + k]) for k in range(4)], "passes": int(out[10]), "host_waits": int(out[11]), "depth": int(out[12]),
+                "nodes": int(out[13]), "budget": int(out[14]), "resident_device_built": int(out[15])}
 
     def flat_id_check(self, device: int = 0) -> "FlatIdCheck":
         """giCDebugSceneFlatIdCheck: the flat records, the id table and the per-instance records resident on a device -- the ids of visible records are a

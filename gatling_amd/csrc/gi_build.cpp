@@ -5,6 +5,7 @@
 #include "gi_refit.h"
 #include "gi_tlas.h"
 #include "gi_blas.h"
+#include "gi_blas_build.h"
 #include "gi_pack.h"
 #include "gi_vispatch.h"
 #include "gi_append.h"
@@ -314,7 +315,7 @@ static void deriveSceneClasses(GiCScene* s, const SceneHost& H, bool newTree)
 // NODES are not built at all -- buildSceneTreeless below: the flat records stay, in scene order, and k_aov2 walks these arrays for the AOVs as well.)
 // The BLAS of one mesh (buildTwoLevel; giCDebugBlasRefit): a tree over the padded object-space boxes of its faces.  A face with an unusable corner keeps an
 // inverted box: the builder leaves it out, and it does not widen mlo / mhi, the union of the usable faces' boxes
-static void buildMeshBlas(const GiCVertex* vertices, const GiCFace* faces, size_t nf, Bvh8& b, std::vector<uint32_t>& order, float mlo[3], float mhi[3])
+void buildMeshBlas(const GiCVertex* vertices, const GiCFace* faces, size_t nf, Bvh8& b, std::vector<uint32_t>& order, float mlo[3], float mhi[3])
 {
   std::vector<float> boxes(nf * 6);
   for (int a = 0; a < 3; a++) { mlo[a] = 3.0e38f; mhi[a] = -3.0e38f; }
@@ -330,13 +331,19 @@ static void buildMeshBlas(const GiCVertex* vertices, const GiCFace* faces, size_
   buildBvh8Boxes(boxes.data(), nf, b, order);
 }
 // ... and its record of face f, as the builder's order places it
-static BlasTri makeBlasTri(const GiCVertex* vertices, const GiCFace* faces, uint32_t f)
+BlasTri makeBlasTri(const GiCVertex* vertices, const GiCFace* faces, uint32_t f)
 {
   BlasTri bt{};
   memcpy(bt.p0, vertices[faces[f].v_i[0]].pos, 12); memcpy(bt.p1, vertices[faces[f].v_i[1]].pos, 12); memcpy(bt.p2, vertices[faces[f].v_i[2]].pos, 12);
   bt.prim = f;
   return bt;
 }
+
+// The BLAS of one mesh that will sit under a TLAS of depth `tlasDepth` (defined behind onSceneDevices): the ONE place the scene's code chooses the builder.
+// Returns the depth budget of a device build, 0 where the host builder made the tree
+static uint32_t makeMeshBlas(GiCScene* s, bool deviceWanted, uint32_t tlasDepth, const GiCMesh* m, Bvh8& b, std::vector<uint32_t>& order, float mlo[3], float mhi[3]);
+// ... made anew by the builder that made the resident one (the checks): the host form under `budget`, or the host builder where budget is 0
+static bool remakeMeshBlas(uint32_t budget, const GiCMesh* m, Bvh8& b, std::vector<uint32_t>& order, float mlo[3], float mhi[3]);
 
 // ... and where the slot is free (MeshBuild::freeSlots: an instancer edit in place of the two-level layout retired its instance)
 template <class MB>
@@ -356,9 +363,12 @@ static std::vector<uint8_t> hiddenOfInstances(const std::vector<MB>& meshBuilds,
 
 // flatNodes == 0: the caller has no flat tree (buildScene's route for GI_C_SCENE_OPTION_TLAS_ONLY, and the checks of a scene built that way).  "Beyond LDS" is
 // then what sceneFitsLds answers for the triangles alone -- more than LDS_TRIS of them --, and the automatic rule on node bytes is not consulted.
+// sceneBuild: the call is buildScene's -- with GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD wanted makeMeshBlas may take a mesh's BLAS to the device, under the budget the
+// TLAS of this same build leaves (instance boxes do not depend on a BLAS's shape, so the TLAS is built first).  Otherwise (the checks of a resident scene) every
+// BLAS is made anew by the builder that made the resident one (TwoLevelHost::meshBlasBudget).
 template <class MB>
 int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vector<InstanceRec>& instances, size_t flatTris, size_t flatNodes,
-    TwoLevelHost& out)
+    TwoLevelHost& out, bool sceneBuild = false)
 {
   s->twoLevel = false;
   int want = s->optTwoLevel;
@@ -378,27 +388,17 @@ int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vec
   uint32_t blasDepth = 0;
   std::vector<float> instBoxes(instances.size() * 6); std::vector<uint32_t> meshBlasTri(meshBuilds.size(), 0u), meshBlasNode(meshBuilds.size(), 0u);
   std::vector<std::vector<uint32_t>> meshBlasLevels(meshBuilds.size());
+  std::vector<uint32_t> meshBlasBudget(meshBuilds.size(), 0u);
+  const std::vector<uint32_t>* residentBudget = !sceneBuild && s->host ? &s->host->two.meshBlasBudget : nullptr;
   // (gi_tlas.h: the point transform, the pad, the status rule and the InstTrav record are shared with the transform update in place and its kernels)
   auto padBox = [](float* lo, float* hi) { tlas_pad_box(lo, hi); };
+  // the instances' world boxes first: they read the meshes' points, never a BLAS
   for (const MB& mb : meshBuilds) {
     if (mb.instCount == 0) continue;
     const GiCMesh* m = mb.m;
     const size_t nf = m->faces.size();
-    float mlo[3], mhi[3];
-    Bvh8 b; std::vector<uint32_t> order;
-    buildMeshBlas(m->vertices.data(), m->faces.data(), nf, b, order, mlo, mhi);
-    const uint32_t nodeBase = (uint32_t)blasNodes.size(), triBase = (uint32_t)blasTris.size();
-    if (mb.meshIdx < meshBlasTri.size()) { meshBlasTri[mb.meshIdx] = triBase; meshBlasNode[mb.meshIdx] = nodeBase; meshBlasLevels[mb.meshIdx] = b.levelStart; }
-    for (Node8 n : b.nodes) { n.childBase += nodeBase; n.triBase += triBase; blasNodes.push_back(n); }
-    for (uint32_t f : order) blasTris.push_back(makeBlasTri(m->vertices.data(), m->faces.data(), f));
-    blasDepth = std::max(blasDepth, b.maxDepth);
-    // object-space magnitude the transformed ray's rounding error scales with inside this mesh (see wave_step2)
-    const float extent = (std::fabs(mlo[0]) + std::fabs(mlo[1]) + std::fabs(mlo[2])) + (std::fabs(mhi[0]) + std::fabs(mhi[1]) + std::fabs(mhi[2]));
     for (uint32_t ii = 0; ii < mb.instCount; ii++) {
       const uint32_t inst = mb.inst[ii];
-      // (idBase is triFirst at a build; after visibility updates in place -- updateVisibilityTwoLevel, which giCDebugSceneTlasCheck holds to this function --
-      // it is the id a fresh build of the visible meshes gives the mesh's first triangle, and a hidden mesh keeps the one it had)
-      instTrav[inst] = tlasMakeInstTrav(instances[inst], nodeBase, mb.idBase + ii * (uint32_t)nf, mb.matFlags, extent);
       // inactive triangles (bvh8.h): a face with an unusable OBJECT-space vertex is left out of the BLAS by the builder and out of this box; an unusable
       // instance keeps the inverted box (the builder leaves it out of the TLAS). A usable face whose WORLD-space vertex is unusable is inactive in the flat
       // tree but would be walked here: such scenes keep the flat layout
@@ -430,6 +430,33 @@ int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vec
       buildBvh8Boxes(masked.data(), instances.size(), tlas, tlasItems);
     }
   }
+  // the BLASes, under the TLAS they will sit under
+  const bool blasOnDevice = sceneBuild && blasDeviceBuildWanted(s);
+  for (const MB& mb : meshBuilds) {
+    if (mb.instCount == 0) continue;
+    const GiCMesh* m = mb.m;
+    const size_t nf = m->faces.size();
+    float mlo[3], mhi[3];
+    Bvh8 b; std::vector<uint32_t> order;
+    uint32_t budget = 0u;
+    if (sceneBuild) budget = makeMeshBlas(s, blasOnDevice, tlas.maxDepth, m, b, order, mlo, mhi);
+    else {
+      budget = residentBudget && mb.meshIdx < residentBudget->size() ? (*residentBudget)[mb.meshIdx] : 0u;
+      if (!remakeMeshBlas(budget, m, b, order, mlo, mhi)) { setError("the host form of the device BLAS builder failed on a mesh the device built"); return GI_C_ERROR; }
+    }
+    const uint32_t nodeBase = (uint32_t)blasNodes.size(), triBase = (uint32_t)blasTris.size();
+    if (mb.meshIdx < meshBlasTri.size()) { meshBlasTri[mb.meshIdx] = triBase; meshBlasNode[mb.meshIdx] = nodeBase; meshBlasLevels[mb.meshIdx] = b.levelStart;
+        meshBlasBudget[mb.meshIdx] = budget; }
+    for (Node8 n : b.nodes) { n.childBase += nodeBase; n.triBase += triBase; blasNodes.push_back(n); }
+    for (uint32_t f : order) blasTris.push_back(makeBlasTri(m->vertices.data(), m->faces.data(), f));
+    blasDepth = std::max(blasDepth, b.maxDepth);
+    // object-space magnitude the transformed ray's rounding error scales with inside this mesh (see wave_step2)
+    const float extent = (std::fabs(mlo[0]) + std::fabs(mlo[1]) + std::fabs(mlo[2])) + (std::fabs(mhi[0]) + std::fabs(mhi[1]) + std::fabs(mhi[2]));
+    // (idBase is triFirst at a build; after visibility updates in place -- updateVisibilityTwoLevel, which giCDebugSceneTlasCheck holds to this function --
+    // it is the id a fresh build of the visible meshes gives the mesh's first triangle, and a hidden mesh keeps the one it had)
+    for (uint32_t ii = 0; ii < mb.instCount; ii++)
+      instTrav[mb.inst[ii]] = tlasMakeInstTrav(instances[mb.inst[ii]], nodeBase, mb.idBase + ii * (uint32_t)nf, mb.matFlags, extent);
+  }
   // per-lane stack: a TLAS level can leave a node group and an instance group behind, a BLAS level a node group
   if (blasTris.size() >= ((size_t)1 << 26)) {
     if (want > 0) fprintf(stderr, "[gatling_gi] two-level layout not used: 2^26 or more unique mesh triangles\n");
@@ -450,7 +477,7 @@ int buildTwoLevel(GiCScene* s, const std::vector<MB>& meshBuilds, const std::vec
   out.tlasNodes.swap(tlas.nodes); out.tlasItems.swap(tlasItems); out.blasNodes.swap(blasNodes); out.blasTris.swap(blasTris); out.instTrav.swap(instTrav);
   out.instBoxes.swap(instBoxes); out.meshBlasTri.swap(meshBlasTri); out.tlasDepth = tlas.maxDepth; out.blasDepth = blasDepth;
   out.tlasDeviceBuilt = false; out.tlasBuildBudget = 0u; // (a build's TLAS is the host builder's)
-  out.meshBlasNode.swap(meshBlasNode); out.meshBlasLevels.swap(meshBlasLevels);
+  out.meshBlasNode.swap(meshBlasNode); out.meshBlasLevels.swap(meshBlasLevels); out.meshBlasBudget.swap(meshBlasBudget);
   return GI_C_OK;
 }
 
@@ -528,6 +555,70 @@ template <class Fn> int onSceneDevices(GiCScene* s, uint32_t nDev, Fn&& fn)
   }
   makeCurrent(g_ctx.device);
   return rc;
+}
+
+// GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD / GATLING_OPTIONS=blas_device_build
+bool blasDeviceBuildWanted(const GiCScene* s)
+{
+  const long o = optionValue("blas_device_build", -1);
+  return o >= 0 ? o == 1 : s->optBlasDeviceBuild == 1;
+}
+// 0: a mesh of nf faces is the device builder's; 1: under blas_device_min; 2: over blas_device_max (the indices of the fallback counters in blasBuildStats)
+static int blasDeviceRange(size_t nf)
+{
+  const long lo = optionValue("blas_device_min", BLAS_DEVICE_MIN_DEFAULT), hi = std::min(optionValue("blas_device_max", BLAS_DEVICE_MAX_DEFAULT), (long)kBlasMaxItems);
+  return (long)nf < lo ? 1 : (long)nf > hi ? 2 : 0;
+}
+// With the option wanted a mesh of blas_device_min .. blas_device_max faces gets its BLAS from the primary device (gi_blas_build.hip; the scene's slab) under
+// B = min(kBlasMaxBudget, 15 - 2 * tlasDepth); the nodes and the order are read back, and the caller goes on as behind the host builder.  Outside the range,
+// on a tree that does not fit the budget, out of memory or on an error status the host builder runs instead (counted in GiCScene::blasBuildStats): a build
+// never fails because of the option, and the render is the same.
+static uint32_t makeMeshBlas(GiCScene* s, bool deviceWanted, uint32_t tlasDepth, const GiCMesh* m, Bvh8& b, std::vector<uint32_t>& order, float mlo[3], float mhi[3])
+{
+  const size_t nf = m->faces.size();
+  if (deviceWanted) {
+    uint64_t* stats = s->blasBuildStats;
+    const bool timing = getenv("GATLING_BUILD_TIMING") != nullptr;
+    uint32_t budget = blasDepthBudget(tlasDepth);
+    if (optionSet("blas_depth_budget")) budget = std::min(budget, (uint32_t)std::max(optionValue("blas_depth_budget", 0), 0L));
+    const int range = blasDeviceRange(nf);
+    const double t0 = nowMs();
+    if (range != 0) {
+      stats[range]++;
+      buildMeshBlas(m->vertices.data(), m->faces.data(), nf, b, order, mlo, mhi);
+      if (timing) fprintf(stderr, "[gatling_gi] BLAS of %zu faces: the host builder (%s), %.3f ms\n", nf, range == 1 ? "under blas_device_min" : "over blas_device_max",
+          nowMs() - t0);
+      return 0u;
+    } else {
+      const uint32_t radius = (uint32_t)std::min(std::max(optionValue("ploc_radius", 16), 1L), 256L);
+      BlasBuildInfo info; int rc = budget == 0u ? TLAS_BUILD_TOO_DEEP : TLAS_BUILD_ERROR;
+      if (budget != 0u) (void)onSceneDevices(s, 1u, [&](SceneDevice& D, hipStream_t st) -> int {
+        rc = buildBlasDevice(D.tlasWorkspace, st, m->vertices.data(), m->vertices.size(), m->faces.data(), nf, budget, radius, b, order, mlo, mhi, info);
+        return GI_C_OK;
+      });
+      if (rc == TLAS_BUILD_OK) {
+        stats[0]++;
+        for (int k = 0; k < 4; k++) stats[6 + k] = (uint64_t)(info.ms[k] * 1000.0f);
+        stats[10] = info.passes; stats[11] = info.hostWaits; stats[12] = info.maxDepth; stats[13] = info.nodeCount; stats[14] = budget;
+        if (timing) fprintf(stderr, "[gatling_gi] BLAS of %zu faces: the device builder, %.3f ms, %u node(s), depth %u of %u, %u PLOC pass(es), %u host wait(s); upload + "
+            "boxes + sort %.3f ms, PLOC %.3f ms, emission %.3f ms, read-back %.3f ms\n", nf, nowMs() - t0, info.nodeCount, info.maxDepth, budget, info.passes,
+            info.hostWaits, info.ms[0], info.ms[1], info.ms[2], info.ms[3]);
+        return budget;
+      }
+      stats[rc == TLAS_BUILD_TOO_DEEP ? 3 : rc == TLAS_BUILD_OUT_OF_MEMORY ? 4 : 5]++;
+      if (timing) fprintf(stderr, "[gatling_gi] BLAS of %zu faces: the host builder (device build after %.3f ms: %s)\n", nf, nowMs() - t0, rc == TLAS_BUILD_TOO_DEEP ?
+          "the tree does not fit the depth budget" : rc == TLAS_BUILD_OUT_OF_MEMORY ? "out of device memory" : info.error);
+    }
+  }
+  buildMeshBlas(m->vertices.data(), m->faces.data(), nf, b, order, mlo, mhi);
+  return 0u;
+}
+static bool remakeMeshBlas(uint32_t budget, const GiCMesh* m, Bvh8& b, std::vector<uint32_t>& order, float mlo[3], float mhi[3])
+{
+  if (budget == 0u) { buildMeshBlas(m->vertices.data(), m->faces.data(), m->faces.size(), b, order, mlo, mhi); return true; }
+  const uint32_t radius = (uint32_t)std::min(std::max(optionValue("ploc_radius", 16), 1L), 256L);
+  BlasBuildInfo info;
+  return buildBlasHost(m->vertices.data(), m->vertices.size(), m->faces.data(), m->faces.size(), budget, radius, b, order, mlo, mhi, info) == TLAS_BUILD_OK;
 }
 
 static int uploadTopTree(SceneDevice& D, const SceneHost& H, hipStream_t st) // the top tree of a partitioned scene: nodes [0, topCap)
@@ -692,7 +783,7 @@ static bool twoLevelWantedWithoutTree(const GiCScene* s, size_t flatTris)
 static int buildSceneTreeless(GiCScene* s, std::unique_ptr<SceneHost>& hostPtr, std::vector<TriRec>& tris, std::vector<int32_t>& faceIdOf, double t0)
 {
   SceneHost& H = *hostPtr;
-  if (buildTwoLevel(s, H.meshBuilds, H.instances, tris.size(), 0u, H.two) != GI_C_OK) return GI_C_ERROR;
+  if (buildTwoLevel(s, H.meshBuilds, H.instances, tris.size(), 0u, H.two, true) != GI_C_OK) return GI_C_ERROR;
   if (!s->twoLevel) { H.two = TwoLevelHost{}; return DEVICE_BUILD_FALLBACK; }
   if (tris.size() >= (1u << 28)) {
     setError("scene has 2^28 or more triangles after instancing: the hit record packs (triangle, material class) into 32 bits");
@@ -789,7 +880,7 @@ int buildScene(GiCScene* s)
     for (size_t i = bvh.activeTris; i < bvh.tris.size(); i++) perMesh[instances[bvh.tris[i].instance].mesh]++;
     warnInactive(meshBuilds, perMesh);
   }
-  if (buildTwoLevel(s, meshBuilds, instances, bvh.tris.size(), bvh.nodes.size(), H.two) != GI_C_OK) return GI_C_ERROR;
+  if (buildTwoLevel(s, meshBuilds, instances, bvh.tris.size(), bvh.nodes.size(), H.two, true) != GI_C_OK) return GI_C_ERROR;
   if (s->twoLevel) {
     H.flatOfOrig.resize(bvh.tris.size());
     for (size_t i = 0; i < bvh.tris.size(); i++) H.flatOfOrig[bvh.tris[i].origId] = (uint32_t)i;
@@ -3061,7 +3152,7 @@ static int updateTopologyTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Upda
   const double t0 = nowMs();
   // --- the meshes to append: updateTopology's selection loop -- what a fresh build would hold and the resident scene does not, all behind every built mesh
   struct NewMesh { GiCMesh* m; uint32_t material, matFlags, vertexOffset, shadeBase, instFirst, instCount, nf, triFirst, idBase, blasNode, blasTri, faceFirst; float extent;
-      Bvh8 blas; std::vector<uint32_t> order; std::vector<int32_t> faceIdAov; };
+      Bvh8 blas; std::vector<uint32_t> order; std::vector<int32_t> faceIdAov; uint32_t blasBudget = 0; };
   std::vector<NewMesh> fresh;
   uint64_t appendedTris = 0, appendedFaces = 0, appendedInstances = 0, appendedVerts = 0;
   for (GiCMesh* m : s->meshes) {
@@ -3128,13 +3219,31 @@ static int updateTopologyTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Upda
       idBase += (uint64_t)nm.instCount * nm.nf;
     }
   }
-  // --- the new BLASes, by the host builder exactly as buildTwoLevel runs it; their records in the builder's order (the bounds kernels read them from scratch)
+  // --- the new BLASes, by the host builder exactly as buildTwoLevel runs it; their records in the builder's order (the bounds kernels read them from scratch).
+  // With GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD wanted the meshes within blas_device_min .. blas_device_max go through makeMeshBlas first, one after the other on
+  // the build stream with the scene's one slab, under the budget the resident TLAS's depth leaves; the others stay with the host builder, in parallel
   const double tb0 = nowMs();
-  std::vector<uint8_t> blasOk(fresh.size(), 1);
+  std::vector<uint8_t> blasOk(fresh.size(), 1), blasMade(fresh.size(), 0);
+  std::vector<float> blasExtent(fresh.size(), 0.0f);
+  if (blasDeviceBuildWanted(s))
+    for (size_t k = 0; k < fresh.size(); k++) {
+      NewMesh& nm = fresh[k];
+      const int range = blasDeviceRange(nm.nf);
+      if (range != 0) {
+        s->blasBuildStats[range]++;
+        if (timing) fprintf(stderr, "[gatling_gi] BLAS of %u faces: the host builder (%s)\n", nm.nf, range == 1 ? "under blas_device_min" : "over blas_device_max");
+        continue;
+      }
+      float mlo[3], mhi[3];
+      nm.blasBudget = makeMeshBlas(s, true, T.tlasDepth, nm.m, nm.blas, nm.order, mlo, mhi);
+      blasExtent[k] = (std::fabs(mlo[0]) + std::fabs(mlo[1]) + std::fabs(mlo[2])) + (std::fabs(mhi[0]) + std::fabs(mhi[1]) + std::fabs(mhi[2]));
+      blasMade[k] = 1;
+    }
   parallelOver(fresh.size(), [&](size_t k) {
     NewMesh& nm = fresh[k];
     float mlo[3], mhi[3];
-    buildMeshBlas(nm.m->vertices.data(), nm.m->faces.data(), nm.nf, nm.blas, nm.order, mlo, mhi);
+    if (!blasMade[k]) buildMeshBlas(nm.m->vertices.data(), nm.m->faces.data(), nm.nf, nm.blas, nm.order, mlo, mhi);
+    if (blasMade[k]) nm.extent = blasExtent[k]; else
     nm.extent = (std::fabs(mlo[0]) + std::fabs(mlo[1]) + std::fabs(mlo[2])) + (std::fabs(mhi[0]) + std::fabs(mhi[1]) + std::fabs(mhi[2])); // (buildTwoLevel's)
     blasOk[k] = nm.order.size() == nm.nf && !nm.blas.nodes.empty() && nm.blas.levelStart.size() >= 2u && nm.blas.levelStart.back() == nm.blas.nodes.size();
     for (const uint32_t f : nm.order) if (f >= nm.nf) blasOk[k] = 0;
@@ -3299,6 +3408,7 @@ static int updateTopologyTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Upda
     H.meshBuilds.push_back(MeshBuild{m, nm.vertexOffset, nm.matFlags, nm.instFirst, nm.instCount, nm.triFirst, meshIdx, nm.faceIdAov});
     H.meshBuilds.back().shadeBase = nm.shadeBase; H.meshBuilds.back().idBase = nm.idBase; H.meshBuilds.back().numberInstances();
     T.meshBlasTri.push_back(nm.blasTri); T.meshBlasNode.push_back(nm.blasNode); T.meshBlasLevels.push_back(nm.blas.levelStart);
+    T.meshBlasBudget.resize(T.meshBlasNode.size() - 1u, 0u); T.meshBlasBudget.push_back(nm.blasBudget);
     if (hostRecords) { // the flat records, face ids and id-table words by the kernels' own form
       AppendMesh M{}; M.triFirst = nm.triFirst; M.faceCount = nm.nf; M.instFirst = nm.instFirst; M.instCount = nm.instCount; M.shadeBase = nm.shadeBase; M.idBase = nm.idBase;
       M.matFlags = nm.matFlags; M.triCount = newTris; M.instanceCount = newInstances; M.shadeCount = (uint32_t)H.triShade.size(); M.flatCount = newTris;

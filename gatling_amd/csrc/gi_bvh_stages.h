@@ -310,6 +310,17 @@ __device__ inline float box_area(const float4& lo, const float4& hi)
 __device__ inline float4 min4(const float4& a, const float4& b) { return make_float4(fminf(a.x, b.x), fminf(a.y, b.y), fminf(a.z, b.z), 0.0f); }
 __device__ inline float4 max4(const float4& a, const float4& b) { return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), 0.0f); }
 
+// one item's padded box b (6 floats) as the box builders' stages take it: the float4 pair k_bvh_morton reads (inverted where the tree leaves the item out),
+// the item's share of the centroid bounds, whether it is active
+__device__ inline void stage_item_box(const float b[6], float4& bl, float4& bh, float4& cLo, float4& cHi, uint32_t& alive)
+{
+  bl = make_float4(3.0e38f, 3.0e38f, 3.0e38f, 0.0f); bh = make_float4(-3.0e38f, -3.0e38f, -3.0e38f, 0.0f);
+  if (tlas_box_active(b)) {
+    bl = make_float4(b[0], b[1], b[2], 0.0f); bh = make_float4(b[3], b[4], b[5], 0.0f);
+    cLo = make_float4(0.5f * (b[0] + b[3]), 0.5f * (b[1] + b[4]), 0.5f * (b[2] + b[5]), 0.0f); cHi = cLo; alive = 1;
+  }
+}
+
 // the block's share of the centroid bounds and of the active count (every thread calls it; thread 0 writes the block's partials)
 __device__ inline void stage_block_bounds(float4 cLo, float4 cHi, uint32_t alive, float4* sLo, float4* sHi, uint32_t* sAlive, float4* __restrict__ blockLo,
     float4* __restrict__ blockHi, uint32_t* __restrict__ blockAlive)
@@ -342,7 +353,8 @@ __global__ __launch_bounds__(kStageBlock) void k_bvh_bounds(const float4* __rest
 }
 
 // 63-bit Morton codes of the box centroids (an inverted box: all ones, sorted behind every active item, in id order since the sort is stable)
-__global__ __launch_bounds__(kStageBlock) void k_bvh_morton(const float4* __restrict__ triLo, const float4* __restrict__ triHi, uint32_t n,
+// (a source of boxes -- gi_blas_build.hip -- includes the stage kernels for the bounds alone)
+[[maybe_unused]] __global__ __launch_bounds__(kStageBlock) void k_bvh_morton(const float4* __restrict__ triLo, const float4* __restrict__ triHi, uint32_t n,
     const float4* __restrict__ bounds, uint64_t* __restrict__ keys, uint32_t* __restrict__ ids)
 {
   const uint32_t i = blockIdx.x * kStageBlock + threadIdx.x;

@@ -3,6 +3,8 @@
 #include "gi_host.h"
 #include "gi_refit.h"
 #include "gi_tlas_build.h"
+#include "gi_blas.h"
+#include "gi_blas_build.h"
 #include "gi_bvh_stages.h"
 #include "bvh8.h"
 
@@ -959,5 +961,139 @@ extern "C" int giCDebugSceneTlasBuildStats(const GiCScene* scene, uint64_t* out)
   out[13] = s->tlasWorkspace.allocations;
   out[14] = s->host && s->host->two.tlasDeviceBuilt ? 1u : 0u;
   out[15] = s->host && s->host->two.tlasDeviceBuilt ? s->host->two.tlasBuildBudget : 0u;
+  return GI_C_OK;
+}
+
+// ---- the BLAS builders of GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD (gi_blas_build.h): giCDebugBuildBlasHost / giCDebugBuildBlas / giCDebugSceneBlasBuildStats -------
+namespace {
+
+int bytesDiffering(const void* x, const void* y, size_t n) { int d = 0; for (size_t i = 0; i < n; i++) d += ((const uint8_t*)x)[i] != ((const uint8_t*)y)[i]; return d; }
+
+// the rules of giCDebugBuildBlasHost over one tree (the host form's or the device's); fills out[0 .. 14] and returns the violations
+int blasBuildChecks(const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t nf, uint32_t budget, uint32_t radius, const Bvh8& b,
+    const std::vector<uint32_t>& order, const float mlo[3], const float mhi[3], const BlasBuildInfo& info, double* out)
+{
+  const uint32_t nodeCount = (uint32_t)b.nodes.size();
+  std::vector<float> boxes6(6u * (size_t)nf);
+  for (uint32_t f = 0; f < nf; f++) {
+    float p[3][3], lo[3], hi[3];
+    for (int k = 0; k < 3; k++) memcpy(p[k], vertices[faces[f].v_i[k]].pos, 12);
+    if (!blas_face_box(p, lo, hi)) for (int a = 0; a < 3; a++) { lo[a] = 3.0e38f; hi[a] = -3.0e38f; }
+    for (int a = 0; a < 3; a++) { boxes6[6u * (size_t)f + a] = lo[a]; boxes6[6u * (size_t)f + 3 + a] = hi[a]; }
+  }
+  Bvh8 ref; std::vector<uint32_t> refOrder; float rlo[3], rhi[3];
+  buildMeshBlas(vertices, faces, nf, ref, refOrder, rlo, rhi);
+  out[0] = (double)info.nodeCount; out[1] = (double)info.maxDepth; out[2] = (double)info.passes; out[3] = tlasModelCost(b.nodes); out[4] = tlasModelCost(ref.nodes);
+  out[5] = (double)info.hostWaits; out[6] = (double)ref.maxDepth; out[7] = (double)info.active; out[14] = (double)std::min(budget, kBlasMaxBudget);
+  // [8] the conservative check of gi_blas.h over the mesh's records in the builder's order
+  int conservative = 1;
+  if (order.size() == nf && nodeCount != 0u) {
+    bool inRange = true; for (const uint32_t f : order) if (f >= nf) inRange = false;
+    if (inRange) {
+      std::vector<BlasTri> tris; tris.reserve(nf);
+      for (const uint32_t f : order) tris.push_back(makeBlasTri(vertices, faces, f));
+      std::vector<float> under(6u * (size_t)nodeCount, 0.0f); std::vector<uint8_t> seen(std::max(nf, 1u), 0);
+      conservative = (int)blasConservativeViolations(b.nodes.data(), nodeCount, 0u, nodeCount, tris.data(), nf, 0u, nf, under.data(), seen.data());
+      // [13] a refit over the unchanged points writes the build's bytes
+      std::vector<Node8> refitted(b.nodes); std::vector<float> scratch(8u * (size_t)nodeCount, 0.0f);
+      blasRefitHost(refitted.data(), nodeCount, 0u, nodeCount, scratch.data(), tris.data(), nf);
+      out[13] = (double)bytesDiffering(refitted.data(), b.nodes.data(), (size_t)nodeCount * sizeof(Node8));
+    }
+  }
+  out[8] = (double)conservative;
+  // [9] the builder's contract over the boxes
+  out[9] = (double)tlasViolations(boxes6.data(), nf, b.nodes, order, b.maxDepth, std::min(budget, kBlasMaxBudget));
+  // [10] the level table: maxDepth + 1 entries from 0 to the node count, every internal child one level below its parent
+  int levelBad = 0;
+  const std::vector<uint32_t>& ls = b.levelStart;
+  if (ls.size() != (size_t)b.maxDepth + 1u || ls.empty() || ls.front() != 0u || ls.back() != nodeCount || b.maxDepth != info.maxDepth) levelBad++;
+  else {
+    for (size_t l = 0; l + 1u < ls.size(); l++) if (!(ls[l] < ls[l + 1u])) levelBad++;
+    for (size_t l = 0; l + 1u < ls.size() && !levelBad; l++)
+      for (uint32_t i = ls[l]; i < ls[l + 1u]; i++) {
+        uint32_t rel = 0;
+        for (int s = 0; s < 8; s++) if ((b.nodes[i].imask >> s) & 1u) {
+          const uint32_t c = b.nodes[i].childBase + rel++;
+          if (l + 2u >= ls.size() || c < ls[l + 1u] || c >= ls[l + 2u]) levelBad++;
+        }
+      }
+  }
+  out[10] = (double)levelBad;
+  // [11] mlo / mhi against the host builder's
+  out[11] = (double)(bytesDiffering(mlo, rlo, 12) + bytesDiffering(mhi, rhi, 12));
+  // [12] the generalisation did not move the TLAS builder: the same boxes under a TLAS budget give the same records
+  out[12] = 0.0;
+  if (budget <= kTlasMaxBudget && nf <= kTlasMaxItems) {
+    std::vector<Node8> tn; std::vector<uint32_t> ti; TlasBuildInfo tinfo;
+    int differ = 0;
+    if (buildTlasHost(boxes6.data(), nf, budget, radius, tn, ti, tinfo) != TLAS_BUILD_OK) differ = 1;
+    else {
+      if (tn.size() != b.nodes.size() || ti.size() != order.size()) differ++;
+      for (size_t i = 0; i < std::min(tn.size(), b.nodes.size()); i++) if (memcmp(&tn[i], &b.nodes[i], sizeof(Node8)) != 0) differ++;
+      for (size_t i = 0; i < std::min(ti.size(), order.size()); i++) if (ti[i] != order[i]) differ++;
+    }
+    out[12] = (double)differ;
+  }
+  return (int)out[8] + (int)out[9] + (int)out[10] + (int)out[11] + (int)out[13] + (out[12] > 0.0 ? 1 : 0);
+}
+
+bool blasDebugArgsOk(const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, const double* out)
+{
+  return out && (vertices || vertexCount == 0u) && (faces || faceCount == 0u);
+}
+
+} // namespace
+
+extern "C" int giCDebugBuildBlasHost(const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, uint32_t depthBudget, uint32_t radius,
+    double* out)
+{
+  if (!blasDebugArgsOk(vertices, vertexCount, faces, faceCount, out)) { setError("giCDebugBuildBlasHost: bad arguments"); return -1; }
+  try {
+    for (int k = 0; k < 16; k++) out[k] = 0.0;
+    Bvh8 b; std::vector<uint32_t> order; float mlo[3], mhi[3]; BlasBuildInfo info;
+    const int rc = buildBlasHost(vertices, vertexCount, faces, faceCount, depthBudget, radius, b, order, mlo, mhi, info);
+    if (rc == TLAS_BUILD_TOO_DEEP) return GI_C_TLAS_BUILD_TOO_DEEP;
+    if (rc != TLAS_BUILD_OK) { setError(std::string("giCDebugBuildBlasHost: ") + info.error); return -1; }
+    return blasBuildChecks(vertices, vertexCount, faces, faceCount, depthBudget, radius, b, order, mlo, mhi, info, out);
+  } catch (const std::exception& e) { setError(std::string("giCDebugBuildBlasHost: ") + e.what()); return -1; }
+}
+
+extern "C" int giCDebugBuildBlas(const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, uint32_t depthBudget, uint32_t radius,
+    double* out)
+{
+  if (!g_ctx.initialized || !blasDebugArgsOk(vertices, vertexCount, faces, faceCount, out)) { setError("giCDebugBuildBlas: bad arguments"); return -1; }
+  try {
+    for (int k = 0; k < 16; k++) out[k] = 0.0;
+    Bvh8 b, hb; std::vector<uint32_t> order, horder; float mlo[3], mhi[3], hlo[3], hhi[3]; BlasBuildInfo info, hinfo;
+    TlasBuildWorkspace ws;
+    const int rc = buildBlasDevice(ws, g_ctx.stream, vertices, vertexCount, faces, faceCount, depthBudget, radius, b, order, mlo, mhi, info);
+    ws.release();
+    const int hostRc = buildBlasHost(vertices, vertexCount, faces, faceCount, depthBudget, radius, hb, horder, hlo, hhi, hinfo);
+    out[5] = (double)info.hostWaits;
+    if (rc == TLAS_BUILD_TOO_DEEP) { if (hostRc != TLAS_BUILD_TOO_DEEP) { setError("giCDebugBuildBlas: too deep on the device alone"); return -1; } return GI_C_TLAS_BUILD_TOO_DEEP; }
+    if (rc != TLAS_BUILD_OK) { setError(std::string("giCDebugBuildBlas: ") + info.error); return -1; }
+    if (hostRc != TLAS_BUILD_OK) { setError("giCDebugBuildBlas: the host form failed where the device did not"); return -1; }
+    const int violations = blasBuildChecks(vertices, vertexCount, faces, faceCount, depthBudget, radius, b, order, mlo, mhi, info, out);
+    int differ = 0;
+    if (b.nodes.size() != hb.nodes.size()) differ += (int)sizeof(Node8) * (int)(std::max(b.nodes.size(), hb.nodes.size()) - std::min(b.nodes.size(), hb.nodes.size()));
+    differ += bytesDiffering(b.nodes.data(), hb.nodes.data(), std::min(b.nodes.size(), hb.nodes.size()) * sizeof(Node8));
+    if (order.size() != horder.size()) differ += 4;
+    differ += bytesDiffering(order.data(), horder.data(), std::min(order.size(), horder.size()) * sizeof(uint32_t));
+    differ += bytesDiffering(mlo, hlo, 12) + bytesDiffering(mhi, hhi, 12);
+    if (b.levelStart != hb.levelStart || b.maxDepth != hb.maxDepth || info.passes != hinfo.passes || info.active != hinfo.active) differ++;
+    out[15] = (double)differ;
+    return differ + violations;
+  } catch (const std::exception& e) { setError(std::string("giCDebugBuildBlas: ") + e.what()); return -1; }
+}
+
+extern "C" int giCDebugSceneBlasBuildStats(const GiCScene* scene, uint64_t* out)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!s || !out) { setError("giCDebugSceneBlasBuildStats: bad arguments"); return GI_C_ERROR; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  for (int k = 0; k < 16; k++) out[k] = s->blasBuildStats[k];
+  uint64_t deviceBuilt = 0;
+  if (s->host) for (const uint32_t budget : s->host->two.meshBlasBudget) deviceBuilt += budget != 0u;
+  out[15] = deviceBuilt;
   return GI_C_OK;
 }

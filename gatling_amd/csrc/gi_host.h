@@ -323,7 +323,11 @@ struct TwoLevelHost { std::vector<Node8> tlasNodes, blasNodes; std::vector<uint3
     std::vector<uint32_t> meshBlasNode; std::vector<std::vector<uint32_t>> meshBlasLevels;
     // GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD: the device builder (gi_tlas_build.hip) made the resident TLAS, under this depth budget -- an edit in place sets both,
     // a scene build clears them; giCDebugSceneTlasCheck makes its comparison TLAS with the same builder
-    bool tlasDeviceBuilt = false; uint32_t tlasBuildBudget = 0; };
+    bool tlasDeviceBuilt = false; uint32_t tlasBuildBudget = 0;
+    // GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD: by meshIdx, the depth budget under which the device builder (gi_blas_build.hip) made the mesh's resident BLAS; 0 (or no
+    // entry): the host builder made it.  Whatever makes a BLAS anew for comparison (buildTwoLevel under giCDebugSceneTlasCheck / giCDebugSceneBlasCheck) runs
+    // the host form of the builder that made the resident one, under this budget
+    std::vector<uint32_t> meshBlasBudget; };
 struct MeshBuild { const GiCMesh* m; uint32_t vertexOffset, matFlags, instFirst, instCount, triFirst; uint32_t meshIdx; std::vector<int32_t> faceIdAov;
     uint32_t shadeBase = 0;
     // the InstanceRec of every live instance, inst[instInMesh]: instFirst + instInMesh (and triangles at triFirst + instInMesh * faces) as the build leaves
@@ -472,6 +476,10 @@ struct GiCScene : SceneDevice {
   // GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD: 1 = the edits in place of a two-level scene build their TLAS on the primary device (gi_build.cpp buildEditTlas);
   // giCDebugSceneTlasBuildStats: device builds, fallbacks (too deep, memory, error, under tlas_device_min), the last device build's figures
   int32_t optTlasDeviceBuild = 0; uint64_t tlasBuildStats[16] = {};
+  // GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD: 1 = the BLAS of a mesh of blas_device_min .. blas_device_max faces is built on the primary device (gi_build.cpp
+  // makeMeshBlas: the scene build's buildTwoLevel and updateTopologyTwoLevel); giCDebugSceneBlasBuildStats: device builds, fallbacks (under the minimum, over
+  // the maximum, too deep, memory, error), the last device build's figures
+  int32_t optBlasDeviceBuild = 0; uint64_t blasBuildStats[16] = {};
   std::vector<GiCMesh*> retiredMeshes; // destroyed meshes the resident scene still refers to (GiCMesh::retired): freed by buildScene and with the scene
   ~GiCScene() { for (GiCMesh* m : retiredMeshes) delete m; }
 };
@@ -505,6 +513,10 @@ bool tlasVisibilityWanted(const GiCScene* s);               // GI_C_SCENE_OPTION
 bool topologyUpdatesWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_TOPOLOGY_UPDATES / GATLING_OPTIONS=topology_updates
 bool tlasTopologyWanted(const GiCScene* s);                  // GI_C_SCENE_OPTION_TLAS_TOPOLOGY / GATLING_OPTIONS=tlas_topology (with topology updates wanted)
 bool tlasDeviceBuildWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD / GATLING_OPTIONS=tlas_device_build (read where options 16 - 18, 20, 21 apply an edit)
+bool blasDeviceBuildWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD / GATLING_OPTIONS=blas_device_build (read where a BLAS is built)
+// the host builder's BLAS of one mesh: padded face boxes, buildBvh8Boxes; mlo / mhi: the union of the usable faces' boxes
+void buildMeshBlas(const GiCVertex* vertices, const GiCFace* faces, size_t nf, Bvh8& b, std::vector<uint32_t>& order, float mlo[3], float mhi[3]);
+BlasTri makeBlasTri(const GiCVertex* vertices, const GiCFace* faces, uint32_t f); // its record of face f
 bool tlasInstancesWanted(const GiCScene* s);                 // GI_C_SCENE_OPTION_TLAS_INSTANCES / GATLING_OPTIONS=tlas_instances (with options 13, 15 and 20 wanted)
 int syncSceneGeometry(GiCScene* s);                          // brings the device scene up to date with the host-side edits (incremental or full build)
 // dirty flags of a material-side edit: DIRTY_MATERIALS alone once the scene / the mesh is part of a built scene (the incremental path), else with DIRTY_BVH

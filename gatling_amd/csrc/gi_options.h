@@ -94,6 +94,12 @@
 //                                  where tlas_updates, blas_updates, tlas_visibility, tlas_topology or tlas_instances applies an edit
 //   tlas_device_min      TLAS_DEVICE_MIN_DEFAULT   with tlas_device_build: scenes of fewer instances keep the host builder (the crossover)
 //   tlas_depth_budget    -         with tlas_device_build: lowers the device builder's depth budget below the stack rule's (tests)
+//   blas_device_build    -1        -1 = the scene option decides (GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD), 0 / 1 = the BLAS of a mesh of a two-level scene is built
+//                                  by the host builder / on the primary device (gi_blas_build.hip; gi_build.cpp makeMeshBlas); read where a BLAS is built:
+//                                  at the scene build (buildTwoLevel) and where tlas_topology applies a mesh create (updateTopologyTwoLevel)
+//   blas_device_min      BLAS_DEVICE_MIN_DEFAULT   with blas_device_build: meshes of fewer faces keep the host builder (the crossover)
+//   blas_device_max      BLAS_DEVICE_MAX_DEFAULT   with blas_device_build: meshes of more faces keep the host builder (the slab: about 1.5 KB per face)
+//   blas_depth_budget    -         with blas_device_build: lowers the device builder's depth budget below the stack rule's (tests)
 //   phase_stats          0         counting builds: print k_path's phase split / k_trace_dyn's lane accounting
 #pragma once
 
@@ -106,6 +112,13 @@ namespace gi {
 // measured crossover of a steady transform edit (tools/time_tlas_device_build.py --crossover, profiles/r23_tlas_device_build.txt: the host builder wins at
 // 4 096 instances, 1.39 against 2.48 ms, the device builder from 8 281 on, 2.74 against 3.27 ms)
 constexpr long TLAS_DEVICE_MIN_DEFAULT = 8192;
+
+// faces below which a mesh's BLAS stays with the host builder although GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD is on (GATLING_OPTIONS=blas_device_min): the
+// measured crossover of one BLAS at a scene build (tools/time_blas_device_build.py --crossover, profiles/r25_blas_device_build.txt: the host builder wins at
+// 5 120 faces, 2.69 against 3.38 ms, the device builder from 20 480 on, 3.89 against 11.71 ms)
+constexpr long BLAS_DEVICE_MIN_DEFAULT = 20480;
+// ... and above which it does (GATLING_OPTIONS=blas_device_max): the builder's slab takes about 1.5 KB per face at depth budget 12
+constexpr long BLAS_DEVICE_MAX_DEFAULT = 1L << 20;
 
 // value of `key` in $GATLING_OPTIONS, or `def`.  Read at every call (tests change the variable between renders of one process).
 inline long optionValue(const char* key, long def)

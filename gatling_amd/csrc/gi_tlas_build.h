@@ -8,6 +8,10 @@
 // Stages: centroid bounds -> 63-bit Morton codes -> stable sort -> PLOC (radius positions either side, the (distance, pair hash, position) tie-break) ->
 // the DEPTH-BOUNDED cost-optimal collapse (gi_bvh_stages.h bvh_dp_internal_bounded: cPrim 0.5, at most 3 items per leaf slot) -> level-wise emission.  The
 // tree has at most `budget` levels by construction; a root that does not fit answers TLAS_BUILD_TOO_DEEP.
+//
+// The stages are a box-tree builder of their own (buildBoxTreeDevice / buildBoxTreeHost below): where the boxes come from, the item limit and the largest
+// budget are parameters of a build.  The TLAS builder is that builder over uploaded boxes under kTlasBuildLimits; the BLAS builder of gi_blas_build.h is the
+// same one over face boxes made on the device, under limits of its own.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -30,8 +34,15 @@ constexpr uint32_t kTlasMaxBatches = 16;      // batches before the build gives 
 // emission, one for the nodes and items.
 constexpr uint32_t kTlasMaxHostWaits = kTlasMaxBatches + 2u;
 
+// What a build is sized for: the most items it takes and the deepest budget it honours.  The TLAS of an edit has the two constants above; the BLAS of a mesh
+// (gi_blas_build.h) runs the same stages under its own.
+struct BoxBuildLimits { uint32_t maxItems, maxBudget; };
+constexpr BoxBuildLimits kTlasBuildLimits{kTlasMaxItems, kTlasMaxBudget};
+constexpr uint32_t kBoxBuildMaxLevels = 16;   // levels any build of these stages may emit (the 16-entry traversal stack bounds every budget)
+
 struct TlasBuildInfo {
   uint32_t nodeCount = 0, maxDepth = 0, active = 0, passes = 0, hostWaits = 0;
+  uint32_t levelStart[kBoxBuildMaxLevels + 1] = {}; // first node of every breadth-first level, then the node count: maxDepth + 1 entries (Bvh8::levelStart)
   float ms[4] = {0, 0, 0, 0}; // device: upload + boxes + sort, PLOC (+ the DP it fills), emission, read-back
   const char* error = "";
 };
@@ -40,6 +51,8 @@ struct TlasBuildInfo {
 inline uint32_t tlasDepthBudget(uint32_t blasDepth) { return blasDepth >= 15u ? 0u : (15u - blasDepth) / 2u; }
 
 // the host form: plain C++ over gi_bvh_stages.h, one thread
+int buildBoxTreeHost(const float* boxes6, size_t n, uint32_t budget, uint32_t radius, const BoxBuildLimits& limits, std::vector<Node8>& nodes,
+    std::vector<uint32_t>& items, TlasBuildInfo& info);
 int buildTlasHost(const float* boxes6, size_t n, uint32_t budget, uint32_t radius, std::vector<Node8>& nodes, std::vector<uint32_t>& items, TlasBuildInfo& info);
 
 // What a scene keeps on its primary device for these builds: one slab, carved anew by every build, that grows geometrically and is released with the scene
@@ -54,5 +67,17 @@ struct TlasBuildWorkspace {
 // it sends a host-built TLAS).  The bytes are buildTlasHost's.
 int buildTlasDevice(TlasBuildWorkspace& ws, hipStream_t st, const float* boxes6, uint32_t n, uint32_t budget, uint32_t radius, std::vector<Node8>& nodes,
     std::vector<uint32_t>& items, TlasBuildInfo& info);
+
+// The stages behind buildTlasDevice for any source of boxes.  `fill` enqueues on the stream what leaves the n padded boxes (6 floats each; an item the tree
+// leaves out: the inverted box), their float4 pairs and every workgroup's centroid bounds and active count (gi_bvh_stages.h stage_item_box,
+// stage_block_bounds; one workgroup per kStageBlock items) in the places BoxStage names.  `extraBytes` of the slab are the source's own (BoxStage::extra,
+// 256-byte aligned): a source allocates nothing.  Behind the emission `backBytes` bytes at extra + backOffset are read back to backHost with the nodes and items.
+struct BoxStage { float* boxes6; float4 *lo4, *hi4, *blockLo, *blockHi; uint32_t* blockAlive; void* extra; };
+struct BoxSource {
+  hipError_t (*fill)(void* ctx, const BoxStage& stage, uint32_t n, hipStream_t st) = nullptr; void* ctx = nullptr;
+  size_t extraBytes = 0, backOffset = 0, backBytes = 0; void* backHost = nullptr;
+};
+int buildBoxTreeDevice(TlasBuildWorkspace& ws, hipStream_t st, const BoxSource& source, uint32_t n, uint32_t budget, uint32_t radius, const BoxBuildLimits& limits,
+    std::vector<Node8>& nodes, std::vector<uint32_t>& items, TlasBuildInfo& info);
 
 } // namespace gi

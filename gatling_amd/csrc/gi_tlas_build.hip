@@ -12,6 +12,9 @@
 //   bounded loops    a pass merges at least one pair (the smallest pair is mutual); a pass without a merge sets the error status, and every kernel behind it
 //                    returns at once
 //
+// One builder, two sources: buildBoxTreeDevice runs these stages for any BoxSource (gi_tlas_build.h) under the limits of the call -- buildTlasDevice with the
+// caller's boxes under kTlasBuildLimits, gi_blas_build.hip with a mesh's face boxes under kBlasBuildLimits.  Indices and offsets are written for 2^22 items.
+//
 // Determinism: every position comes from a scan, the sort is stable, ties are broken by index: the bytes are a function of the input, and they are the host
 // form's (gi_tlas_build_host.cpp; giCDebugBuildTlas holds that).
 #include <cstring> // (before rocprim: its texture iterator calls memset in host code)
@@ -42,6 +45,7 @@ struct State {
   uint32_t root2;
   uint32_t levelM, levelStart, levelParity, levels, nodeCount, itemCount;
   uint32_t pad[3];
+  uint32_t levelStartOf[kBoxBuildMaxLevels + 1]; // first node of every emitted level, then the node count (Bvh8::levelStart)
 };
 
 struct Tree { float* box; uint32_t* left; uint32_t* right; uint32_t* total; Dp* dp; uint32_t layers; };
@@ -56,11 +60,8 @@ __global__ __launch_bounds__(kBlock) void k_tlas_boxes(const float* __restrict__
   uint32_t alive = 0;
   if (i < n) {
     float b[6]; for (int a = 0; a < 6; a++) b[a] = boxes6[6u * (size_t)i + a];
-    float4 bl = make_float4(3.0e38f, 3.0e38f, 3.0e38f, 0.0f), bh = make_float4(-3.0e38f, -3.0e38f, -3.0e38f, 0.0f);
-    if (tlas_box_active(b)) {
-      bl = make_float4(b[0], b[1], b[2], 0.0f); bh = make_float4(b[3], b[4], b[5], 0.0f);
-      cLo = make_float4(0.5f * (b[0] + b[3]), 0.5f * (b[1] + b[4]), 0.5f * (b[2] + b[5]), 0.0f); cHi = cLo; alive = 1;
-    }
+    float4 bl, bh;
+    stage_item_box(b, bl, bh, cLo, cHi, alive);
     lo4[i] = bl; hi4[i] = bh;
   }
   stage_block_bounds(cLo, cHi, alive, sLo, sHi, sAlive, blockLo, blockHi, blockAlive);
@@ -233,7 +234,7 @@ __global__ __launch_bounds__(kTailThreads) void k_tlas_tail(const uint32_t* __re
 __global__ void k_tlas_emit_init(uint32_t* __restrict__ lvA, Node8* __restrict__ nodes, State* __restrict__ S)
 {
   S->levelM = 0u; S->levelStart = 0u; S->levelParity = 0u; S->levels = 0u; S->nodeCount = 0u; S->itemCount = 0u;
-  if (S->A == 0u) { Node8 root; bvh_empty_root(root); nodes[0] = root; S->levels = 1u; S->nodeCount = 1u; return; }
+  if (S->A == 0u) { Node8 root; bvh_empty_root(root); nodes[0] = root; S->levels = 1u; S->nodeCount = 1u; S->levelStartOf[0] = 0u; S->levelStartOf[1] = 1u; return; }
   if (S->status != TLAS_BUILD_OK) return;
   if (S->m > 1u) { S->status = TLAS_BUILD_ERROR; return; } // (the tail did not run: cannot happen)
   lvA[0] = S->root2; S->levelM = 1u; S->nodeCount = 1u;
@@ -278,6 +279,7 @@ __global__ void k_tlas_level(const uint64_t* __restrict__ incl, uint32_t cap, ui
   const uint64_t sums = incl[cap - 1u];
   const uint32_t internal = (uint32_t)(sums >> 32), itemsHere = (uint32_t)(sums & 0xffffffffull), nodeEnd = S->levelStart + m;
   if (nodeEnd + internal > cap || S->itemCount + itemsHere > S->A) { S->status = TLAS_BUILD_ERROR; return; }
+  if (S->levels < kBoxBuildMaxLevels) { S->levelStartOf[S->levels] = S->levelStart; S->levelStartOf[S->levels + 1u] = nodeEnd; } // (the last level has no internal child)
   S->levelStart = nodeEnd; S->levelM = internal; S->itemCount += itemsHere; S->nodeCount = nodeEnd + internal; S->levels += 1u; S->levelParity ^= 1u;
 }
 // inactive items behind the active ones, in input order (the stable sort left them there); thread 0 closes the build
@@ -300,9 +302,9 @@ struct Carver {
 struct Layout {
   float* boxes6; float4 *lo4, *hi4, *blockLo, *blockHi, *bounds; uint32_t* blockAlive; uint64_t *keys, *keys2; uint32_t *ids, *sortedIds;
   Tree T; uint32_t *clA, *clB, *nn; uint64_t *flags, *incl; Node8* nodes; uint32_t *items, *lvA, *lvB; Plan* plans; uint64_t *counts, *cincl; State* S;
-  void *sortTmp, *scanTmp, *scan2Tmp; size_t bytes;
+  void *sortTmp, *scanTmp, *scan2Tmp, *extra; size_t bytes;
 };
-Layout carve(void* mem, uint32_t n, uint32_t layers, size_t sortBytes, size_t scanBytes, size_t scan2Bytes)
+Layout carve(void* mem, uint32_t n, uint32_t layers, size_t sortBytes, size_t scanBytes, size_t scan2Bytes, size_t extraBytes)
 {
   Carver c{(uint8_t*)mem}; Layout L{};
   const size_t nb = std::max(blocksFor(n), 1u), nodes2 = 2u * (size_t)std::max(n, 1u), cap = (size_t)n + 1u;
@@ -315,6 +317,7 @@ Layout carve(void* mem, uint32_t n, uint32_t layers, size_t sortBytes, size_t sc
   L.nodes = c.get<Node8>(cap); L.items = c.get<uint32_t>(n); L.lvA = c.get<uint32_t>(cap); L.lvB = c.get<uint32_t>(cap);
   L.plans = c.get<Plan>(cap); L.counts = c.get<uint64_t>(cap); L.cincl = c.get<uint64_t>(cap); L.S = c.get<State>(1);
   L.sortTmp = c.get<uint8_t>(sortBytes); L.scanTmp = c.get<uint8_t>(scanBytes); L.scan2Tmp = c.get<uint8_t>(scan2Bytes);
+  L.extra = extraBytes ? c.get<uint8_t>(extraBytes) : nullptr; // (a source without arrays of its own leaves the slab's size what it was)
   L.bytes = c.at + 256u;
   return L;
 }
@@ -328,12 +331,34 @@ void TlasBuildWorkspace::release()
   for (hipEvent_t& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
 }
 
+namespace {
+// the TLAS's source: the caller's boxes, uploaded as they are
+struct HostBoxes { const float* boxes6; };
+hipError_t fillFromHostBoxes(void* ctx, const BoxStage& stage, uint32_t n, hipStream_t st)
+{
+  const hipError_t e = hipMemcpyAsync(stage.boxes6, static_cast<const HostBoxes*>(ctx)->boxes6, (size_t)n * 24u, hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return e;
+  k_tlas_boxes<<<blocksFor(n), kBlock, 0, st>>>(stage.boxes6, n, stage.lo4, stage.hi4, stage.blockLo, stage.blockHi, stage.blockAlive);
+  return hipSuccess;
+}
+} // namespace
+
 int buildTlasDevice(TlasBuildWorkspace& ws, hipStream_t st, const float* boxes6, uint32_t n, uint32_t budget, uint32_t radius, std::vector<Node8>& nodes,
     std::vector<uint32_t>& items, TlasBuildInfo& info)
 {
+  HostBoxes host{boxes6};
+  BoxSource source; source.fill = fillFromHostBoxes; source.ctx = &host;
+  return buildBoxTreeDevice(ws, st, source, n, budget, radius, kTlasBuildLimits, nodes, items, info);
+}
+
+int buildBoxTreeDevice(TlasBuildWorkspace& ws, hipStream_t st, const BoxSource& source, uint32_t n, uint32_t budget, uint32_t radius, const BoxBuildLimits& limits,
+    std::vector<Node8>& nodes, std::vector<uint32_t>& items, TlasBuildInfo& info)
+{
   info = TlasBuildInfo{}; nodes.clear(); items.clear();
-  if (n > kTlasMaxItems) { info.error = "more items than the builder is sized for"; return TLAS_BUILD_ERROR; }
-  budget = std::min(budget, kTlasMaxBudget); radius = std::min(std::max(radius, 1u), 256u);
+  if (n > limits.maxItems || n > 0x7fffffffu || !source.fill) { info.error = "more items than the builder is sized for"; return TLAS_BUILD_ERROR; }
+  if (source.backBytes && (!source.backHost || source.backOffset > source.extraBytes || source.backBytes > source.extraBytes - source.backOffset)) {
+    info.error = "the source's read-back lies outside its share of the slab"; return TLAS_BUILD_ERROR; }
+  budget = std::min(std::min(budget, limits.maxBudget), kBoxBuildMaxLevels); radius = std::min(std::max(radius, 1u), 256u);
   if (budget == 0u) return TLAS_BUILD_TOO_DEEP;
   const uint32_t layers = budget + 1u, cap = n + 1u;
 #define TB_TRY(expr) do { const hipError_t _e = (expr); if (_e != hipSuccess) { (void)hipGetLastError(); info.error = #expr; \
@@ -345,7 +370,7 @@ int buildTlasDevice(TlasBuildWorkspace& ws, hipStream_t st, const float* boxes6,
     TB_TRY(rocprim::inclusive_scan(nullptr, scanBytes, (uint64_t*)nullptr, (uint64_t*)nullptr, n, rocprim::plus<uint64_t>(), st));
   }
   TB_TRY(rocprim::inclusive_scan(nullptr, scan2Bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, cap, rocprim::plus<uint64_t>(), st));
-  const size_t need = carve(nullptr, n, layers, sortBytes, scanBytes, scan2Bytes).bytes;
+  const size_t need = carve(nullptr, n, layers, sortBytes, scanBytes, scan2Bytes, source.extraBytes).bytes;
   if (need > ws.bytes) {
     TB_TRY(hipStreamSynchronize(st)); // (nothing of an earlier build is in flight: builds end with a wait; a foreign stream's work is the caller's)
     const size_t want = std::max(need, 2u * ws.bytes);
@@ -358,15 +383,15 @@ int buildTlasDevice(TlasBuildWorkspace& ws, hipStream_t st, const float* boxes6,
     ws.allocations++;
   }
   for (hipEvent_t& e : ws.ev) if (!e) TB_TRY(hipEventCreate(&e));
-  const Layout L = carve(ws.mem, n, layers, sortBytes, scanBytes, scan2Bytes);
+  const Layout L = carve(ws.mem, n, layers, sortBytes, scanBytes, scan2Bytes, source.extraBytes);
   const uint32_t nb = std::max(blocksFor(n), 1u);
   uint32_t waits = 0;
   // ---- 1. boxes and bounds, 2. codes and sort
   TB_TRY(hipEventRecord(ws.ev[0], st));
   TB_TRY(hipMemsetAsync(L.S, 0, sizeof(State), st));
   if (n) {
-    TB_TRY(hipMemcpyAsync(L.boxes6, boxes6, (size_t)n * 24u, hipMemcpyHostToDevice, st));
-    k_tlas_boxes<<<nb, kBlock, 0, st>>>(L.boxes6, n, L.lo4, L.hi4, L.blockLo, L.blockHi, L.blockAlive);
+    const BoxStage stage{L.boxes6, L.lo4, L.hi4, L.blockLo, L.blockHi, L.blockAlive, L.extra};
+    TB_TRY(source.fill(source.ctx, stage, n, st));
   }
   k_bvh_bounds<<<1, kBlock, 0, st>>>(L.blockLo, L.blockHi, L.blockAlive, n ? nb : 0u, L.bounds, &L.S->A);
   if (n) {
@@ -419,9 +444,11 @@ int buildTlasDevice(TlasBuildWorkspace& ws, hipStream_t st, const float* boxes6,
   nodes.resize(S.nodeCount); items.resize(n);
   TB_TRY(hipMemcpyAsync(nodes.data(), L.nodes, (size_t)S.nodeCount * sizeof(Node8), hipMemcpyDeviceToHost, st));
   if (n) TB_TRY(hipMemcpyAsync(items.data(), L.items, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  if (n && source.backBytes) TB_TRY(hipMemcpyAsync(source.backHost, (const uint8_t*)L.extra + source.backOffset, source.backBytes, hipMemcpyDeviceToHost, st));
   TB_TRY(hipEventRecord(ws.ev[4], st));
   TB_TRY(hipStreamSynchronize(st)); waits++;
   info.hostWaits = waits; info.nodeCount = S.nodeCount; info.maxDepth = S.levels;
+  for (uint32_t lv = 0; lv <= S.levels && lv <= kBoxBuildMaxLevels; lv++) info.levelStart[lv] = S.levelStartOf[lv];
   for (int k = 0; k < 4; k++) { float ms = 0.0f; if (hipEventElapsedTime(&ms, ws.ev[k], ws.ev[k + 1]) == hipSuccess) info.ms[k] = ms; else (void)hipGetLastError(); }
   return TLAS_BUILD_OK;
 #undef TB_TRY

@@ -10,9 +10,15 @@ namespace gi {
 
 int buildTlasHost(const float* boxes6, size_t n, uint32_t budget, uint32_t radius, std::vector<Node8>& nodes, std::vector<uint32_t>& items, TlasBuildInfo& info)
 {
+  return buildBoxTreeHost(boxes6, n, budget, radius, kTlasBuildLimits, nodes, items, info);
+}
+
+int buildBoxTreeHost(const float* boxes6, size_t n, uint32_t budget, uint32_t radius, const BoxBuildLimits& limits, std::vector<Node8>& nodes,
+    std::vector<uint32_t>& items, TlasBuildInfo& info)
+{
   info = TlasBuildInfo{}; nodes.clear(); items.clear();
-  if (n > kTlasMaxItems) { info.error = "more items than the builder is sized for"; return TLAS_BUILD_ERROR; }
-  budget = std::min(budget, kTlasMaxBudget); radius = std::min(std::max(radius, 1u), 256u);
+  if (n > limits.maxItems) { info.error = "more items than the builder is sized for"; return TLAS_BUILD_ERROR; }
+  budget = std::min(std::min(budget, limits.maxBudget), kBoxBuildMaxLevels); radius = std::min(std::max(radius, 1u), 256u);
   if (budget == 0u) return TLAS_BUILD_TOO_DEEP;
   const uint32_t layers = budget + 1u;
   // ---- 1. active items, centroid bounds
@@ -36,7 +42,7 @@ int buildTlasHost(const float* boxes6, size_t n, uint32_t budget, uint32_t radiu
   std::stable_sort(sorted.begin(), sorted.end(), [&](uint32_t a, uint32_t b) { return keys[a] < keys[b]; });
   if (A == 0u) {
     Node8 root; bvh_empty_root(root); nodes.push_back(root); items = sorted;
-    info.nodeCount = 1; info.maxDepth = 1;
+    info.nodeCount = 1; info.maxDepth = 1; info.levelStart[0] = 0u; info.levelStart[1] = 1u;
     return TLAS_BUILD_OK;
   }
   // ---- 3. PLOC, 4. the depth-bounded DP inside the merge
@@ -96,12 +102,13 @@ int buildTlasHost(const float* boxes6, size_t n, uint32_t budget, uint32_t radiu
       tlas_write_node(T, plans[li], childBase, itemBase, nodeEnd, sorted.data(), nodes[(size_t)levelStart + li], items.data(), next.data());
       childBase += (uint32_t)(counts[li] >> 32); itemBase += (uint32_t)(counts[li] & 0xffffffffull);
     }
+    info.levelStart[levels] = levelStart;
     levelStart = nodeEnd; itemCount += itemsHere; levels++;
     level.swap(next);
   }
   if (itemCount != A) { info.error = "emission lost items"; return TLAS_BUILD_ERROR; }
   for (size_t k = A; k < n; k++) items[k] = sorted[k];
-  info.nodeCount = (uint32_t)nodes.size(); info.maxDepth = levels;
+  info.nodeCount = (uint32_t)nodes.size(); info.maxDepth = levels; info.levelStart[levels] = (uint32_t)nodes.size();
   return TLAS_BUILD_OK;
 }
 

@@ -387,7 +387,7 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * giCDebugSceneTlasTopologyUpdateCount, giCDebugAppendRecords and giCDebugAppendRecordsHost, and for GI_C_SCENE_OPTION_TLAS_INSTANCES,
  * giCDebugSceneTlasInstanceUpdateStats, giCDebugInstanceRecords and giCDebugInstanceRecordsHost, and for giCDebugTraversalStackHigh and giCDebugBvhStackReach,
  * and for GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD, giCDebugBuildTlasHost, giCDebugBuildTlas and giCDebugSceneTlasBuildStats, and for giCDebugSceneUpsPlain and
- * giCDebugUpsTraits. */
+ * giCDebugUpsTraits, and for GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD, giCDebugBuildBlasHost, giCDebugBuildBlas and giCDebugSceneBlasBuildStats. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -685,6 +685,17 @@ int giCGetRenderStats(const GiCScene* scene, GiCRenderStats* out);
  * on an error status; giCDebugSceneTlasBuildStats counts each.  The scene build itself keeps the host builder.  GATLING_OPTIONS=tlas_device_build=0|1
  * overrides the option (hdGatling sets no scene options); tlas_depth_budget=N lowers D for the device builder (tests).  DESIGN.md section 6. */
 #define GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD 22
+/* [ext] Where the BLAS of a mesh of a two-level scene is built; read where one is built: at the scene build, and where option 20 applies a mesh create to a
+ * resident scene.  Value 1 = a mesh of at least GATLING_OPTIONS=blas_device_min and at most blas_device_max faces (defaults in gi_options.h) gets its BLAS
+ * from the primary device (gi_blas_build.hip: padded face boxes from the uploaded points, then the stages of the device TLAS builder -- Morton sort, PLOC, a
+ * cost-optimal 8-wide collapse whose depth is bounded by the layout's 16-entry stack, B = min(12, 15 - 2 * TLAS depth) levels) instead of from the host's
+ * binned-SAH builder; nodes and face order are read back, and from there the host does what it does behind its own builder.  0 = off (default): every launch,
+ * flag, counter and resident byte is what it is without the option.  The image does not depend on the option (the traversal contract).  The host builder is
+ * used instead -- a build never fails because of the option -- for a mesh outside the face range, when the tree does not fit B levels, out of device memory,
+ * or on an error status; giCDebugSceneBlasBuildStats counts each.  Vertex, visibility and instancer edits and option 22 compose unchanged on top of a
+ * device-built BLAS.  GATLING_OPTIONS=blas_device_build=0|1 overrides the option (hdGatling sets no scene options); blas_depth_budget=N lowers B (tests).
+ * DESIGN.md section 6. */
+#define GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD 23
 int giCGetLookaheadStats(const GiCScene* scene, GiCLookaheadStats* out);
 int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value);
 /* [ext] closest hit of one ray through the device traversal kernel (parity tests of the BVH8 path).
@@ -818,6 +829,28 @@ int giCDebugBuildTlas(const float* boxes6, uint32_t count, uint32_t depthBudget,
  * PLOC, emission, read-back), [9] PLOC passes, [10] host waits, [11] depth, [12] nodes, [13] workspace allocations since the scene was created, [14] 1 when
  * the resident TLAS was made by the device builder, [15] the depth budget of that build.  All zero with the option off. */
 int giCDebugSceneTlasBuildStats(const GiCScene* scene, uint64_t out[16]);
+/* [ext] [debug] the host form of the BLAS builder of GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD (gi_blas_build_host.cpp) over one mesh, `depthBudget` levels at most (the
+ * builder's own bound is 12), PLOC search radius `radius`.  Host only.  Returns the number of violated rules (0 is the contract: out[8] + out[9] + out[10] +
+ * out[11] + out[13], + 1 where out[12] > 0), GI_C_TLAS_BUILD_TOO_DEEP when the tree cannot fit the budget, -1 on error (a face index outside the vertices is
+ * one).  out[0] nodes, [1] depth, [2] PLOC passes, [3] the tree's SAH model cost (as giCDebugBuildTlasHost), [4] the same function over the host builder's
+ * tree (buildMeshBlas), [5] host waits (0 here), [6] the host builder's depth, [7] active faces, [8] blasConservativeViolations of the tree over the mesh's
+ * records, [9] rule violations of the tree over the padded face boxes (depth within the budget, every usable face named once, unusable faces behind in input
+ * order, children behind parents breadth-first, every face inside every ancestor slot), [10] inconsistencies of the level table, [11] bytes of mlo / mhi that
+ * differ from buildMeshBlas's, [12] with depthBudget <= 7: node and item records that differ from the TLAS builder's host form over the same boxes (else 0),
+ * [13] node bytes a BLAS refit over the unchanged points changes (gi_blas.h blasRefitHost), [14] the depth budget the build ran under. */
+int giCDebugBuildBlasHost(const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, uint32_t depthBudget, uint32_t radius,
+                          double* out /* 16 */);
+/* [ext] [debug] the device builder (gi_blas_build.hip) on the same arguments: the number of node / order / mlo / mhi BYTES that differ from the host form's plus
+ * the violated rules above, counted on the device's bytes (0 is the contract); GI_C_TLAS_BUILD_TOO_DEEP exactly where the host form answers it (when both say
+ * so).  out as above, [5] = waits of the host on the device inside the build (bounded whatever faceCount: gi_tlas_build.h kTlasMaxHostWaits), [15] = the
+ * differing bytes alone. */
+int giCDebugBuildBlas(const GiCVertex* vertices, uint32_t vertexCount, const GiCFace* faces, uint32_t faceCount, uint32_t depthBudget, uint32_t radius,
+                      double* out /* 16 */);
+/* [ext] [debug] GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD on this scene: out[0] BLAS builds on the device, fallbacks to the host builder: [1] fewer faces than
+ * blas_device_min, [2] more than blas_device_max, [3] too deep, [4] out of memory, [5] error status; of the last device build: [6] - [9] stage times in
+ * microseconds (upload + face boxes + sort, PLOC, emission, read-back), [10] PLOC passes, [11] host waits, [12] depth, [13] nodes, [14] its depth budget;
+ * [15] meshes of the resident scene whose BLAS the device built.  All zero with the option off. */
+int giCDebugSceneBlasBuildStats(const GiCScene* scene, uint64_t out[16]);
 /* [ext] [debug] device check of the kernels that make the world boxes of moved instances (gi_tlas.hip k_inst_bounds / k_inst_finish): the mesh (`vertices`,
  * `faces`: 3 indices per face) under each of the `xformCount` instance transforms (16 floats each, USD row vectors).  outBoxes6 (6 floats per transform: min
  * xyz, max xyz, padded) and outStatus (one word per transform, 0 = usable; bits: 1 a corner unusable in object space, 2 in world space, 4 a flattened
