@@ -194,6 +194,9 @@ SYMBOLS = [
     ("giCDebugInstanceRecords", C.c_int, [_P, _U, _P, _U]),
     ("giCDebugInstanceRecordsHost", C.c_int, [_P, _U, _P, _U]),
     ("giCDebugSceneTlasInstanceUpdateStats", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("giCDebugSceneCompactionCount", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("giCDebugCompactRanges", C.c_int, [_U, _P, _U, _P, _U, C.POINTER(C.c_uint32)]),
+    ("giCDebugCompactRangesHost", C.c_int, [_U, _P, _U, _P, _U, C.POINTER(C.c_uint32)]),
     ("giCDebugBuildTlasHost", C.c_int, [_FP, _U, _U, _U, C.POINTER(C.c_double)]),
     ("giCDebugBuildTlas", C.c_int, [_FP, _U, _U, _U, C.POINTER(C.c_double)]),
     ("giCDebugBuildBlasHost", C.c_int, [_P, _U, _P, _U, _U, _U, C.POINTER(C.c_double)]),
@@ -295,6 +298,7 @@ def debug_clone_instance(vertices, faces, xform_a, xform_b, left_handed=False) -
 
 
 OPTION_BLAS_DEVICE_BUILD = 23  # 1: the BLAS of a mesh of blas_device_min .. blas_device_max faces of a two-level scene is built on the primary device (gi_blas_build.hip: face boxes from the uploaded points, then the device TLAS builder's stages under a deeper budget) instead of with the host builder, which remains the fallback; read at the scene build and where option 20 applies a mesh create (include/gi_c.h); 0 = off (default)
+OPTION_TLAS_COMPACTION = 24  # 1: before a topology or instancer edit in place of a two-level scene without the flat tree declines because retired triangles outnumber live ones (retired x 100 > live x GATLING_OPTIONS=tlas_compact_percent, default 100), the ranges earlier edits retired are compacted on the device (gi_compact.hip: one launch per array kind into new allocations, indices rebased, the TLAS rebuilt) and the edit goes on; read only where option 20 or 21 applies an edit (include/gi_c.h); 0 = off (default)
 TLAS_BUILD_TOO_DEEP = -2  # GI_C_TLAS_BUILD_TOO_DEEP
 
 
@@ -445,6 +449,41 @@ def debug_instance_records(meshes, jobs, host_only=False) -> int:
     if n < 0:
         raise GiError("giCDebugInstanceRecords failed: " + L.giCGetLastError().decode())
     return int(n)
+
+
+class _DebugCompactRange(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("live", C.c_uint32), ("delta", C.c_uint32 * 3), ("hidden", C.c_uint32)]
+
+
+# the array kinds of a compaction (gi_compact.h) and the bytes of one record of each
+COMPACT_VERTS, COMPACT_BLAS_TRIS, COMPACT_WORDS, COMPACT_SHADE, COMPACT_BLAS_NODES, COMPACT_INSTANCES, COMPACT_INST_TRAV, COMPACT_TRIS = range(8)
+COMPACT_RECORD_BYTES = {COMPACT_VERTS: 48, COMPACT_BLAS_TRIS: 64, COMPACT_WORDS: 4, COMPACT_SHADE: 160, COMPACT_BLAS_NODES: 80, COMPACT_INSTANCES: 96, COMPACT_INST_TRAV: 128,
+                        COMPACT_TRIS: 64}
+
+
+def debug_compact_ranges(kind, records, ranges, host_only=False):
+    """giCDebugCompactRanges: the device kernel that compacts one array kind of a two-level scene (k_compact_ranges, one launch for all ranges) against a
+    straightforward restatement -- filter, then rebase.  `kind`: COMPACT_*; `records`: an array whose bytes are the records (COMPACT_RECORD_BYTES[kind] each);
+    `ranges`: consecutive ranges that cover them, dicts with "count", "live" and, for a live one, optionally "delta" (up to three words, by kind:
+    gi_compact.h) and "hidden" (kind COMPACT_TRIS: its records do not write the id table).  Returns (differing bytes -- 0 is the contract --, info) with
+    info = {"wave_items", "block_items" (whole items a wave / a workgroup holds under the mapping as built), "live", "workgroups"}.  host_only:
+    giCDebugCompactRangesHost, the host form of the kernel (gi_compact.h) against the same restatement (no device)."""
+    L = load_library()
+    raw = np.ascontiguousarray(records).view(np.uint8).reshape(-1)
+    size = COMPACT_RECORD_BYTES[int(kind)]
+    if len(raw) % size:
+        raise ValueError("debug_compact_ranges: the records are not whole")
+    rs = (_DebugCompactRange * max(len(ranges), 1))()
+    for k, r in enumerate(ranges):
+        d = [int(x) & 0xffffffff for x in r.get("delta", ())] + [0, 0, 0]
+        rs[k].count, rs[k].live, rs[k].hidden = int(r["count"]), 1 if r["live"] else 0, 1 if r.get("hidden") else 0
+        rs[k].delta = (C.c_uint32 * 3)(*d[:3])
+    info = (C.c_uint32 * 4)()
+    fn = L.giCDebugCompactRangesHost if host_only else L.giCDebugCompactRanges
+    n = fn(int(kind), raw.ctypes.data if len(raw) else None, len(raw) // size, C.addressof(rs) if len(ranges) else None, len(ranges), info)
+    if n < 0:
+        raise GiError("giCDebugCompactRanges failed: " + L.giCGetLastError().decode())
+    return int(n), {"wave_items": int(info[0]), "block_items": int(info[1]), "live": int(info[2]), "workgroups": int(info[3])}
 
 
 def debug_patch_visibility_two_level(face_counts, hidden_before, hidden_after, seed=1):
@@ -685,6 +724,18 @@ class Scene:
         if self.L.giCDebugSceneTlasInstanceUpdateStats(self.handle, out) != GI_C_OK:
             raise GiError("giCDebugSceneTlasInstanceUpdateStats failed")
         return {"syncs": int(out[0]), "appended": int(out[1]), "reused": int(out[2]), "retired": int(out[3])}
+
+    def compaction_stats(self) -> dict:
+        """giCDebugSceneCompactionCount: compactions of the retired ranges of this scene (OPTION_TLAS_COMPACTION).  Returns {"applied", "records_moved",
+        "bytes_released" (on the primary device), "declined"}.  A compaction is part of the sync that triggers it: it has no entry in update_counts()."""
+        out = (C.c_uint64 * 4)()
+        if self.L.giCDebugSceneCompactionCount(self.handle, out) != GI_C_OK:
+            raise GiError("giCDebugSceneCompactionCount failed")
+        return {"applied": int(out[0]), "records_moved": int(out[1]), "bytes_released": int(out[2]), "declined": int(out[3])}
+
+    def compaction_count(self) -> int:
+        """Compactions applied to this scene (compaction_stats()["applied"])."""
+        return self.compaction_stats()["applied"]
 
     def tlas_build_stats(self) -> dict:
         """giCDebugSceneTlasBuildStats: the TLAS builds of edits in place under OPTION_TLAS_DEVICE_BUILD.  Returns {"device_builds", "too_deep", "out_of_memory",

@@ -10,6 +10,7 @@
 #include "gi_vispatch.h"
 #include "gi_append.h"
 #include "gi_instances.h"
+#include "gi_compact.h"
 
 #include <random>
 #include <unordered_map>
@@ -1849,7 +1850,7 @@ bool tlasTopologyWanted(const GiCScene* s)
   const long o = optionValue("tlas_topology", -1);
   return o >= 0 ? o == 1 : s->optTlasTopology == 1;
 }
-static int updateTopologyTwoLevel(GiCScene* s, SceneHost& H, bool& handled, UpdateCost& cost);
+static int updateTopologyTwoLevel(GiCScene* s, SceneHost& H, bool& handled, UpdateCost& cost, bool afterCompaction = false);
 
 static int updateTopology(GiCScene* s, bool& handled, UpdateCost& cost)
 {
@@ -2814,7 +2815,311 @@ bool tlasInstancesWanted(const GiCScene* s)
   return o >= 0 ? o == 1 : s->optTlasInstances == 1;
 }
 
-static int updateInstancesTwoLevel(GiCScene* s, SceneHost& H, bool& applied, UpdateCost& cost)
+// ---------------------------------------------------------------------------------------------------------------
+// Compaction of the retired ranges of a two-level scene without the flat tree (opt-in: GI_C_SCENE_OPTION_TLAS_COMPACTION / GATLING_OPTIONS=tlas_compaction=1;
+// read where updateTopologyTwoLevel or updateInstancesTwoLevel is about to apply an edit and retired x 100 > live x tlas_compact_percent holds on the planned
+// after-edit counts: compactBeforeEdit below).  Those edits retire by hiding: the vertex, shading, BLAS, instance and flat records of a destroyed mesh and
+// the slots of retired instances stay resident, and once they outnumber the live records the edit declines and the scene is rebuilt.  Here they leave:
+//   dropped: every MeshBuild retired by an EARLIER sync (m->retired && hidden) with all its ranges; every free instance slot with its flat records.
+//   kept:    live meshes, meshes hidden by the visibility path, meshes the current sync retires (still visible resident records: the edit that follows
+//            retires them as ever).  Storage order is preserved; nothing is sorted back into scene order, and scene-order ids do not change.
+//   device:  one range table per array kind (gi_compact.h CompactTable: runs of kept items with equal deltas are one range) and ONE launch per kind
+//            (gi_compact.hip) into NEW allocations sized as DeviceBuffer::grow sizes them, which are swapped in behind the launches -- FVertex, BlasTri and
+//            face-id words moved; TriShade::vi, Node8::childBase / triBase, InstanceRec::mesh, InstTrav::blasRoot, TriRec::instance / vi rebased; the new
+//            id table written by the flat records' own lanes.  The new blocks of EVERY device are allocated before the first resident change: out of
+//            memory declines with nothing touched.  The old blocks are freed before the render's memory plan reads free memory.  Host waits: one stream
+//            synchronisation per device whatever the scene size (two on the primary under GATLING_BUILD_TIMING), plus those of the device TLAS builder
+//            where GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD is wanted.
+//   host:    the MeshBuilds renumbered (meshIdx == index again; inst / instTri renamed, free lists emptied, vertexOffset / shadeBase / instFirst / triFirst
+//            moved), H.verts, H.triShade, H.instances, the BLAS arrays, the traversal records and -- where still held -- the flat records, face ids and id
+//            table WHERE THEY LIE through the kernel's per-piece form (a stable compaction moves towards the front: ranges that stay are not touched); the
+//            instance boxes; MeshRec and the scene-data tables made again (appendBuiltMeshSceneData); the TLAS by
+//            buildEditTlas over the compacted boxes, hidden instances masked; blasDepth over the kept meshes; retired GiCMeshes nothing names any more freed.
+// Declines (compacted = false, not an error, counted, one line under GATLING_BUILD_TIMING; the scene is untouched and the caller goes on as without the
+// option): whatever updateTopologyTwoLevel declines for on the scene as it is; a count that does not add up; a TLAS too deep; out of device memory.
+// With nothing to drop the call is a no-op and is not counted.
+// ---------------------------------------------------------------------------------------------------------------
+bool tlasCompactionWanted(const GiCScene* s)
+{
+  const long o = optionValue("tlas_compaction", -1);
+  return o >= 0 ? o == 1 : s->optTlasCompaction == 1;
+}
+
+static int compactTwoLevel(GiCScene* s, SceneHost& H, bool& compacted, UpdateCost& cost)
+{
+  compacted = false;
+  TwoLevelHost& T = H.two;
+  const bool timing = getenv("GATLING_BUILD_TIMING") != nullptr;
+  auto decline = [&](const char* why) { s->compactionStats[3]++; if (timing) fprintf(stderr, "[gatling_gi] compaction (two-level): %s; nothing is moved\n", why); return GI_C_OK; };
+  const char* const mismatch = "a count of the host copy does not add up";
+  const uint32_t oldInstances = (uint32_t)H.instances.size(), oldTris = s->triCount, oldShade = (uint32_t)H.triShade.size(), oldVerts = (uint32_t)H.verts.size();
+  const uint32_t oldBlasNodes = (uint32_t)T.blasNodes.size(), oldBlasTris = (uint32_t)T.blasTris.size(), oldMeshes = (uint32_t)H.meshBuilds.size();
+  // --- what leaves: nothing, and this is not a compaction
+  std::vector<uint8_t> keep(oldMeshes, 1); std::vector<uint32_t> newMeshIdx(oldMeshes, 0xffffffffu);
+  uint32_t keptMeshes = 0; uint64_t droppedTris = 0;
+  for (uint32_t b = 0; b < oldMeshes; b++) {
+    const MeshBuild& mb = H.meshBuilds[b];
+    const uint64_t nf = mb.m->faces.size();
+    keep[b] = !(mb.m->retired && mb.hidden);
+    if (keep[b]) { newMeshIdx[b] = keptMeshes++; droppedTris += mb.freeSlots.size() * nf; } else droppedTris += (mb.instCount + mb.freeSlots.size()) * nf;
+  }
+  if (keptMeshes == oldMeshes && droppedTris == 0u) return GI_C_OK;
+  // --- the scene as updateTopologyTwoLevel wants it
+  if (s->stats.inactiveTriangleCount != 0u) return decline("the scene was built with inactive triangles");
+  if (H.deviceBuilt || H.partitioned || !H.treeless || !H.shadePacked || H.reordered) return decline("the scene is not a two-level scene without the flat tree");
+  if (T.instTrav.size() != oldInstances || T.instBoxes.size() != 6u * (size_t)oldInstances || T.meshBlasTri.size() != oldMeshes || T.meshBlasNode.size() != oldMeshes ||
+      T.meshBlasLevels.size() != oldMeshes || H.meshRecs.size() != oldMeshes) return decline("the host copy is not the built scene's"); // (cannot happen)
+  for (const MeshBuild& mb : H.meshBuilds)
+    if (mb.inst.size() != mb.instCount || mb.instTri.size() != mb.instCount || mb.meshIdx != (uint32_t)(&mb - H.meshBuilds.data())) return decline(mismatch); // (cannot happen)
+  const double t0 = nowMs();
+  // --- the per-mesh arrays, in storage order: every range must lie where the ranges before it end
+  CompactTable tVerts(COMPACT_VERTS), tShade(COMPACT_SHADE), tNodes(COMPACT_BLAS_NODES), tBlasTris(COMPACT_BLAS_TRIS), tInst(COMPACT_INSTANCES), tTrav(COMPACT_INST_TRAV),
+      tTris(COMPACT_TRIS), tWords(COMPACT_WORDS);
+  struct Place { uint32_t vertexOffset = 0, shadeBase = 0, blasNode = 0, blasTri = 0; };
+  std::vector<Place> place(oldMeshes);
+  uint32_t blasDepth = 0;
+  {
+    uint64_t vAt = 0, sAt = 0, nAt = 0, bAt = 0;
+    for (uint32_t b = 0; b < oldMeshes; b++) {
+      const MeshBuild& mb = H.meshBuilds[b];
+      const std::vector<uint32_t>& lv = T.meshBlasLevels[b];
+      const uint64_t nv = mb.m->vertices.size(), nf = mb.m->faces.size(), nn = lv.empty() ? 0u : lv.back();
+      if (mb.vertexOffset != vAt || mb.shadeBase != sAt || vAt + nv > oldVerts || sAt + nf > oldShade) return decline(mismatch);
+      if (lv.empty() ? mb.instCount != 0u : (lv.size() < 2u || T.meshBlasNode[b] != nAt || T.meshBlasTri[b] != bAt || nAt + nn > oldBlasNodes || bAt + nf > oldBlasTris)) return decline(mismatch);
+      if (keep[b]) {
+        Place& P = place[b];
+        P.vertexOffset = tVerts.Z.dstCount; P.shadeBase = tShade.Z.dstCount; P.blasNode = tNodes.Z.dstCount; P.blasTri = tBlasTris.Z.dstCount;
+        tVerts.add((uint32_t)vAt, (uint32_t)nv);
+        tShade.add((uint32_t)sAt, (uint32_t)nf, P.vertexOffset - (uint32_t)vAt);
+        if (!lv.empty()) {
+          tNodes.add((uint32_t)nAt, (uint32_t)nn, P.blasNode - (uint32_t)nAt, P.blasTri - (uint32_t)bAt);
+          tBlasTris.add((uint32_t)bAt, (uint32_t)nf);
+          blasDepth = std::max(blasDepth, (uint32_t)lv.size() - 1u); // (Bvh8::levelStart: maxDepth + 1 entries)
+        }
+      }
+      vAt += nv; sAt += nf; if (!lv.empty()) { nAt += nn; bAt += nf; }
+    }
+    if (vAt != oldVerts || sAt != oldShade || nAt != oldBlasNodes || bAt != oldBlasTris) return decline(mismatch);
+  }
+  // --- the instance slots: every slot is a live instance's or a free one, once; the kept ones keep their order
+  constexpr uint32_t NONE = 0xffffffffu;
+  std::vector<uint32_t> slotMesh(oldInstances, NONE), newSlot(oldInstances, NONE), newTriOfSlot(oldInstances, NONE);
+  {
+    std::vector<uint8_t> seen(oldInstances, 0); uint64_t slots = 0;
+    auto take = [&](uint32_t slot) { if (slot >= oldInstances || seen[slot]) return false; seen[slot] = 1; slots++; return true; };
+    for (uint32_t b = 0; b < oldMeshes; b++) {
+      const MeshBuild& mb = H.meshBuilds[b];
+      for (const uint32_t slot : mb.inst) { if (!take(slot)) return decline(mismatch); if (keep[b]) slotMesh[slot] = b; }
+      for (const MeshBuild::FreeSlot& fs : mb.freeSlots) if (!take(fs.inst)) return decline(mismatch);
+    }
+    if (slots != oldInstances) return decline(mismatch);
+  }
+  for (uint32_t slot = 0; slot < oldInstances; slot++) {
+    const uint32_t b = slotMesh[slot];
+    if (b == NONE) continue;
+    if (H.instances[slot].mesh != b) return decline(mismatch); // (cannot happen)
+    newSlot[slot] = tInst.Z.dstCount;
+    tInst.add(slot, 1u, newMeshIdx[b] - b);
+    tTrav.add(slot, 1u, place[b].blasNode - T.meshBlasNode[b]);
+  }
+  // --- the flat records: one run per kept instance, in the order they lie; with the runs of what leaves they cover the array
+  struct Run { uint32_t src, nf, slot, b; };
+  std::vector<Run> runs;
+  {
+    uint64_t covered = 0;
+    for (uint32_t b = 0; b < oldMeshes; b++) {
+      const MeshBuild& mb = H.meshBuilds[b];
+      const uint64_t nf = mb.m->faces.size();
+      if (nf >= ((uint64_t)1 << 26)) return decline(mismatch); // (cannot happen)
+      covered += (mb.instCount + mb.freeSlots.size()) * nf;
+      if (keep[b]) for (uint32_t ii = 0; ii < mb.instCount; ii++) runs.push_back(Run{mb.instTri[ii], (uint32_t)nf, mb.inst[ii], b});
+    }
+    if (covered != oldTris) return decline(mismatch);
+    std::sort(runs.begin(), runs.end(), [](const Run& a, const Run& c) { return a.src < c.src; });
+    uint64_t end = 0;
+    for (const Run& r : runs) {
+      if (r.src < end || (uint64_t)r.src + r.nf > oldTris) return decline(mismatch);
+      end = (uint64_t)r.src + r.nf;
+      const MeshBuild& mb = H.meshBuilds[r.b];
+      newTriOfSlot[r.slot] = tTris.Z.dstCount;
+      tTris.add(r.src, r.nf, newSlot[r.slot] - r.slot, place[r.b].shadeBase - mb.shadeBase, place[r.b].vertexOffset - mb.vertexOffset, mb.hidden ? COMPACT_RANGE_HIDDEN : 0u);
+      tWords.add(r.src, r.nf);
+    }
+  }
+  const uint32_t newInstances = tInst.Z.dstCount, newTris = tTris.Z.dstCount;
+  if (newInstances == 0u || newTris == 0u) return decline("nothing would stay");
+  if (!tVerts.finish(oldVerts, 0u) || !tShade.finish(oldShade, 0u) || !tNodes.finish(oldBlasNodes, 0u) || !tBlasTris.finish(oldBlasTris, 0u) || !tInst.finish(oldInstances, 0u) ||
+      !tTrav.finish(oldInstances, 0u) || !tTris.finish(oldTris, newTris) || !tWords.finish(oldTris, 0u)) return decline("a range table does not pass its check"); // (cannot happen)
+  CompactTable* const tables[8] = {&tVerts, &tShade, &tNodes, &tBlasTris, &tInst, &tTrav, &tTris, &tWords};
+  uint64_t movedRecords = 0; size_t rangeCount = 0;
+  for (const CompactTable* t : tables) { movedRecords += t->Z.dstCount; rangeCount += t->ranges.size(); }
+  // --- the MeshBuilds after the compaction (staged), and the tables that are made from them
+  std::vector<MeshBuild> meshBuilds; meshBuilds.reserve(keptMeshes);
+  std::vector<uint32_t> meshBlasTri, meshBlasNode, meshBlasBudget; std::vector<std::vector<uint32_t>> meshBlasLevels;
+  {
+    std::vector<uint32_t> keptSlotsBelow(oldInstances + 1u, 0u); // for a mesh without an instance: where its (empty) runs would lie
+    for (uint32_t slot = 0; slot < oldInstances; slot++) keptSlotsBelow[slot + 1u] = keptSlotsBelow[slot] + (newSlot[slot] != NONE ? 1u : 0u);
+    for (uint32_t b = 0; b < oldMeshes; b++) {
+      if (!keep[b]) continue;
+      MeshBuild nb = H.meshBuilds[b];
+      nb.meshIdx = newMeshIdx[b]; nb.vertexOffset = place[b].vertexOffset; nb.shadeBase = place[b].shadeBase;
+      for (uint32_t ii = 0; ii < nb.instCount; ii++) { const uint32_t slot = nb.inst[ii]; nb.inst[ii] = newSlot[slot]; nb.instTri[ii] = newTriOfSlot[slot]; }
+      nb.freeSlots.clear(); nb.retiredInst = 0u;
+      if (nb.instCount != 0u) { nb.instFirst = nb.inst[0]; nb.triFirst = nb.instTri[0]; }
+      else {
+        nb.instFirst = keptSlotsBelow[std::min(nb.instFirst, oldInstances)];
+        const auto it = std::lower_bound(runs.begin(), runs.end(), nb.triFirst, [](const Run& r, uint32_t x) { return r.src < x; });
+        nb.triFirst = it == runs.end() ? newTris : newTriOfSlot[it->slot];
+      }
+      meshBuilds.push_back(std::move(nb));
+      meshBlasTri.push_back(place[b].blasTri); meshBlasNode.push_back(place[b].blasNode); meshBlasLevels.push_back(T.meshBlasLevels[b]);
+      meshBlasBudget.push_back(b < T.meshBlasBudget.size() ? T.meshBlasBudget[b] : 0u);
+    }
+  }
+  std::vector<MeshRec> meshRecs; std::vector<float> sceneData;
+  for (const MeshBuild& mb : meshBuilds) appendBuiltMeshSceneData(mb, meshRecs, sceneData);
+  // --- the TLAS over the compacted boxes, hidden instances masked; the depth rule with the BLASes that stay
+  std::vector<float> boxes(6u * (size_t)newInstances);
+  std::vector<uint8_t> hiddenAfter(newInstances, 0);
+  for (uint32_t slot = 0; slot < oldInstances; slot++)
+    if (newSlot[slot] != NONE) { memcpy(&boxes[6u * (size_t)newSlot[slot]], &T.instBoxes[6u * (size_t)slot], 24); hiddenAfter[newSlot[slot]] = H.meshBuilds[slotMesh[slot]].hidden ? 1 : 0; }
+  Bvh8 tlas; std::vector<uint32_t> tlasItems; TlasMade tlasMade;
+  const double tt0 = nowMs();
+  {
+    std::vector<float> masked(boxes);
+    tlasMaskHiddenBoxes(masked.data(), hiddenAfter.data(), newInstances);
+    tlasMade = buildEditTlas(s, blasDepth, masked.data(), newInstances, tlas, tlasItems);
+  }
+  const double tlasMs = nowMs() - tt0;
+  if (2u * tlas.maxDepth + blasDepth + 1u > 16u) return decline("the TLAS over the compacted boxes is too deep for the 16-entry stack");
+  // --- every device of the scene: ALL new blocks first, sized as a growth to the kept count would size them
+  struct Fresh { DeviceBuffer<FVertex> verts; DeviceBuffer<TriShade> shade; DeviceBuffer<Node8> blasNodes; DeviceBuffer<BlasTri> blasTris; DeviceBuffer<InstanceRec> instances;
+      DeviceBuffer<InstTrav> instTrav; DeviceBuffer<TriRec> tris; DeviceBuffer<int32_t> faceIds; DeviceBuffer<uint32_t> flat; DeviceBuffer<CompactRange> ranges;
+      void release() { verts.release(); shade.release(); blasNodes.release(); blasTris.release(); instances.release(); instTrav.release(); tris.release(); faceIds.release();
+          flat.release(); ranges.release(); }
+      size_t bytes() const { return verts.bytes() + shade.bytes() + blasNodes.bytes() + blasTris.bytes() + instances.bytes() + instTrav.bytes() + tris.bytes() + faceIds.bytes() + flat.bytes(); } };
+  std::vector<CompactRange> allRanges; size_t rangeFirst[8];
+  for (int k = 0; k < 8; k++) { rangeFirst[k] = allRanges.size(); allRanges.insert(allRanges.end(), tables[k]->ranges.begin(), tables[k]->ranges.end()); }
+  const uint32_t nDev = residentDeviceCount(s);
+  std::vector<Fresh> fresh(nDev);
+  auto slack = [](size_t n) { return n + n / 4u + 1u; }; // (DeviceBuffer::grow's)
+  bool outOfMemory = false;
+  const double t1 = nowMs();
+  int rcDev = onSceneDevices(s, nDev, [&](SceneDevice& D, hipStream_t) -> int {
+    if (D.dTris.count < oldTris || D.dTriFaceId.count < oldTris || D.dFlatOfOrig.count < oldTris || D.dInstances.count < oldInstances || D.dInstTrav.count < oldInstances ||
+        D.dTriShade.count < oldShade || D.dVerts.count < oldVerts || D.dBlasNodes.count < oldBlasNodes || D.dBlasTris.count < oldBlasTris) {
+      setError("internal: the device holds less than the scene"); return GI_C_ERROR; }
+    Fresh& F = fresh[D.slot]; // (SceneDevice::slot is its index among the scene's devices)
+    int r = F.ranges.alloc(allRanges.size());
+    if (r == GI_C_OK) r = F.verts.alloc(slack(tVerts.Z.dstCount));
+    if (r == GI_C_OK) r = F.shade.alloc(slack(tShade.Z.dstCount));
+    if (r == GI_C_OK) r = F.blasNodes.alloc(slack(tNodes.Z.dstCount));
+    if (r == GI_C_OK) r = F.blasTris.alloc(slack(tBlasTris.Z.dstCount));
+    if (r == GI_C_OK) r = F.instances.alloc(slack(newInstances));
+    if (r == GI_C_OK) r = F.instTrav.alloc(slack(newInstances));
+    if (r == GI_C_OK) r = F.tris.alloc(slack(newTris));
+    if (r == GI_C_OK) r = F.faceIds.alloc(slack(newTris));
+    if (r == GI_C_OK) r = F.flat.alloc(slack(newTris));
+    if (r == GI_C_OUT_OF_MEMORY_INTERNAL) { outOfMemory = true; return DEVICE_BUILD_FALLBACK; }
+    return r;
+  });
+  if (rcDev != GI_C_OK) { // (nothing resident was touched on any device)
+    (void)onSceneDevices(s, nDev, [&](SceneDevice& D, hipStream_t) -> int { fresh[D.slot].release(); return GI_C_OK; });
+    if (rcDev == DEVICE_BUILD_FALLBACK && outOfMemory) return decline("out of device memory");
+    return GI_C_ERROR;
+  }
+  // --- decided.  One launch per array kind behind the tables' copy, the small arrays the host made, one wait, the swap
+  double deviceMs = 0.0; uint64_t releasedBytes = 0, oldBytes = 0, newBytes = 0; // (of the primary device: both sets of blocks are resident until the swap)
+  rcDev = onSceneDevices(s, nDev, [&](SceneDevice& D, hipStream_t st) -> int {
+    Fresh& F = fresh[D.slot];
+    int r = GI_C_OK;
+    if (hipMemcpyAsync(F.ranges.ptr, allRanges.data(), allRanges.size() * sizeof(CompactRange), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemsetAsync(F.flat.ptr, 0, F.flat.count * sizeof(uint32_t), st) != hipSuccess) { setError("compaction (two-level): copy failed"); r = GI_C_ERROR; }
+    double tk = 0.0;
+    if (r == GI_C_OK && timing && D.slot == 0u) { if (hipStreamSynchronize(st) != hipSuccess) r = GI_C_ERROR; tk = nowMs(); }
+    const void* const src[8] = {D.dVerts.ptr, D.dTriShade.ptr, D.dBlasNodes.ptr, D.dBlasTris.ptr, D.dInstances.ptr, D.dInstTrav.ptr, D.dTris.ptr, D.dTriFaceId.ptr};
+    void* const dst[8] = {F.verts.ptr, F.shade.ptr, F.blasNodes.ptr, F.blasTris.ptr, F.instances.ptr, F.instTrav.ptr, F.tris.ptr, F.faceIds.ptr};
+    for (int k = 0; k < 8 && r == GI_C_OK; k++)
+      if (!launchCompactRanges(st, tables[k]->ranges.data(), F.ranges.ptr + rangeFirst[k], tables[k]->Z, src[k], dst[k], tables[k]->Z.kind == COMPACT_TRIS ? F.flat.ptr : nullptr)) {
+        setError("internal: a compaction range outside its array"); r = GI_C_ERROR; } // (cannot happen: the tables passed their check)
+    if (r == GI_C_OK && hipGetLastError() != hipSuccess) { setError("compaction (two-level): launch failed"); r = GI_C_ERROR; }
+    if (r == GI_C_OK && (D.dTlasNodes.upload(tlas.nodes, st) || D.dTlasItems.upload(tlasItems, st) || D.dMeshes.upload(meshRecs, st) || D.dSceneData.upload(sceneData, st))) r = GI_C_ERROR;
+    if (hipStreamSynchronize(st) != hipSuccess && r == GI_C_OK) { setError("compaction (two-level): device error"); r = GI_C_ERROR; }
+    if (timing && D.slot == 0u && r == GI_C_OK) deviceMs = nowMs() - tk;
+    if (r == GI_C_OK) { // the swap: the scene owns the new blocks, `F` the old ones
+      const size_t before = D.dVerts.bytes() + D.dTriShade.bytes() + D.dBlasNodes.bytes() + D.dBlasTris.bytes() + D.dInstances.bytes() + D.dInstTrav.bytes() + D.dTris.bytes() +
+          D.dTriFaceId.bytes() + D.dFlatOfOrig.bytes(), after = F.bytes();
+      if (D.slot == 0u) { oldBytes = before; newBytes = after; if (before > after) releasedBytes = before - after; }
+      std::swap(D.dVerts, F.verts); std::swap(D.dTriShade, F.shade); std::swap(D.dBlasNodes, F.blasNodes); std::swap(D.dBlasTris, F.blasTris); std::swap(D.dInstances, F.instances);
+      std::swap(D.dInstTrav, F.instTrav); std::swap(D.dTris, F.tris); std::swap(D.dTriFaceId, F.faceIds); std::swap(D.dFlatOfOrig, F.flat);
+    }
+    F.release(); // (the old blocks, or after an error the new ones; before the render's memory plan reads free memory)
+    return r;
+  });
+  if (rcDev != GI_C_OK) { // (a device is half done: the error path of the sync rebuilds the scene)
+    (void)onSceneDevices(s, nDev, [&](SceneDevice& D, hipStream_t) -> int { fresh[D.slot].release(); return GI_C_OK; });
+    return GI_C_ERROR;
+  }
+  const double t2 = nowMs();
+  // --- the host copies behind the committed compaction, where they lie (gi_compact.h compactRangesInPlaceHost: the kernel's per-piece form, ranges that stay
+  // where they are untouched); the arrays keep their capacity
+  const bool hostRecords = !H.hostTreeDropped && H.bvh.tris.size() == oldTris && H.triFaceId.size() == oldTris && H.flatOfOrig.size() == oldTris;
+  {
+    struct HostMove { const CompactTable* t; void* data; uint32_t* table; };
+    std::vector<HostMove> moves = {{&tVerts, H.verts.data(), nullptr}, {&tShade, H.triShade.data(), nullptr}, {&tNodes, T.blasNodes.data(), nullptr},
+        {&tBlasTris, T.blasTris.data(), nullptr}, {&tInst, H.instances.data(), nullptr}, {&tTrav, T.instTrav.data(), nullptr}};
+    if (hostRecords) { moves.push_back({&tTris, H.bvh.tris.data(), H.flatOfOrig.data()}); moves.push_back({&tWords, H.triFaceId.data(), nullptr}); }
+    parallelOver(moves.size(), [&](size_t k) { compactRangesInPlaceHost(moves[k].t->ranges.data(), moves[k].t->Z, moves[k].data, moves[k].table); }); // (one thread per array)
+    H.verts.resize(tVerts.Z.dstCount); H.triShade.resize(tShade.Z.dstCount); T.blasNodes.resize(tNodes.Z.dstCount); T.blasTris.resize(tBlasTris.Z.dstCount);
+    H.instances.resize(newInstances); T.instTrav.resize(newInstances);
+  }
+  if (hostRecords) { H.bvh.tris.resize(newTris); H.triFaceId.resize(newTris); H.flatOfOrig.resize(newTris); }
+  else { // dropped by an edit in place before: they stay dropped, and the id table goes with them
+    std::vector<uint32_t>().swap(H.flatOfOrig);
+    if (!H.hostTreeDropped) { std::vector<TriRec>().swap(H.bvh.tris); std::vector<int32_t>().swap(H.triFaceId); H.hostTreeDropped = true; } // (cannot happen)
+  }
+  H.meshBuilds.swap(meshBuilds); H.meshRecs.swap(meshRecs); H.sceneData.swap(sceneData);
+  T.meshBlasTri.swap(meshBlasTri); T.meshBlasNode.swap(meshBlasNode); T.meshBlasLevels.swap(meshBlasLevels); T.meshBlasBudget.swap(meshBlasBudget);
+  T.instBoxes.swap(boxes); T.tlasNodes.swap(tlas.nodes); T.tlasItems.swap(tlasItems); T.tlasDepth = tlas.maxDepth; T.blasDepth = blasDepth; noteTlasMade(T, tlasMade);
+  { // the destroyed meshes nothing refers to any more
+    std::vector<GiCMesh*> still;
+    for (GiCMesh* m : s->retiredMeshes) {
+      bool named = false;
+      for (const MeshBuild& mb : H.meshBuilds) if (mb.m == m) { named = true; break; }
+      if (named) still.push_back(m); else delete m;
+    }
+    s->retiredMeshes.swap(still);
+  }
+  s->triCount = newTris; H.bvh.activeTris = newTris;
+  if (!(s->dirty & DIRTY_MATERIALS)) deriveSceneClasses(s, H, false); // (with a material edit due updateMaterials derives the classes behind the edit)
+  setSceneBoundsFromInstances(s, H);
+  const double t3 = nowMs();
+  cost.buildMs += tlasMs; cost.uploadMs += std::max(t3 - t0 - tlasMs, 0.0);
+  s->compactionStats[0]++; s->compactionStats[1] += movedRecords; s->compactionStats[2] += releasedBytes;
+  if (timing) fprintf(stderr, "[gatling_gi] compaction (two-level): %zu range(s) of 8 array kinds, %llu record(s) moved (%u of %u flat record(s), %u of %u instance(s), %u of %u "
+                              "mesh(es) stay), %llu byte(s) freed on the primary device (%llu old + %llu new resident during the swap), host %.2f ms (of which TLAS build %.2f), device %.2f ms "
+                              "(launches + wait %.3f)\n",
+                      rangeCount, (unsigned long long)movedRecords, newTris, oldTris, newInstances, oldInstances, keptMeshes, oldMeshes, (unsigned long long)releasedBytes,
+                      (unsigned long long)oldBytes, (unsigned long long)newBytes, (t1 - t0) + (t3 - t2), tlasMs, t2 - t1, deviceMs);
+  compacted = true;
+  return GI_C_OK;
+}
+
+// The trigger, where an edit in place has planned its after-edit counts and is about to test "retired triangles outnumber live ones": with the option wanted
+// and retired x 100 > live x tlas_compact_percent the resident scene is compacted.  True: it was -- every index the caller has planned with is stale, and it
+// starts over on the compacted scene (where it does not ask again).  rc: GI_C_ERROR on a device error
+static bool compactBeforeEdit(GiCScene* s, SceneHost& H, uint64_t retired, uint64_t live, UpdateCost& cost, int& rc)
+{
+  rc = GI_C_OK;
+  if (!tlasCompactionWanted(s)) return false;
+  const uint64_t percent = (uint64_t)std::max(optionValue("tlas_compact_percent", 100), 0L);
+  if (!(retired * 100u > live * percent)) return false;
+  bool compacted = false;
+  rc = compactTwoLevel(s, H, compacted, cost);
+  return rc == GI_C_OK && compacted;
+}
+
+static int updateInstancesTwoLevel(GiCScene* s, SceneHost& H, bool& applied, UpdateCost& cost, bool mayCompact = true)
 {
   TwoLevelHost& T = H.two;
   const char* const what = "instance update (two-level)";
@@ -2876,6 +3181,11 @@ static int updateInstancesTwoLevel(GiCScene* s, SceneHost& H, bool& applied, Upd
     }
     live += grownTris; live -= shrunkTris; visible += grownTris; visible -= shrunkTris; retired += shrunkTris; retired -= reusedTris;
     if (visible < kIncrementalMinTris) return decline("fewer than 4096 visible triangles after the edit");
+    if (mayCompact) { // (GI_C_SCENE_OPTION_TLAS_COMPACTION: the plan above names slots and meshes of the scene as it was -- it is made again)
+      int rc = GI_C_OK;
+      if (compactBeforeEdit(s, H, retired, live, cost, rc)) return updateInstancesTwoLevel(s, H, applied, cost, false);
+      if (rc != GI_C_OK) return GI_C_ERROR;
+    }
     if (retired > live) return decline("retired triangles outnumber live ones");
   }
   if ((uint64_t)oldTris + appendedTris >= ((uint64_t)1 << 28)) return decline("2^28 or more flat records after the append");
@@ -3127,7 +3437,7 @@ static int updateInstancesTwoLevel(GiCScene* s, SceneHost& H, bool& applied, Upd
 // 2^24; 2^26 unique BLAS triangles or 2^28 flat records; a TLAS too deep (2 x TLAS depth + BLAS depth + 1 > 16, the new BLAS included); out of device
 // memory (a later device of several: the earlier ones are committed, and buildScene sends everything anew).
 // ---------------------------------------------------------------------------------------------------------------
-static int updateTopologyTwoLevel(GiCScene* s, SceneHost& H, bool& handled, UpdateCost& cost)
+static int updateTopologyTwoLevel(GiCScene* s, SceneHost& H, bool& handled, UpdateCost& cost, bool afterCompaction)
 {
   TwoLevelHost& T = H.two;
   const char* const what = "topology update (two-level)";
@@ -3135,7 +3445,8 @@ static int updateTopologyTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Upda
   auto decline = [&](const char* why) { if (timing) fprintf(stderr, "[gatling_gi] %s: %s; the scene is rebuilt\n", what, why); return GI_C_OK; };
   // --- instancer edits of built meshes come first (GI_C_SCENE_OPTION_TLAS_INSTANCES: updateInstancesTwoLevel above): committed whole, or declined with nothing
   // resident touched.  The meshes created and destroyed in the same sync are then applied to the scene it leaves; a decline below rebuilds, as ever
-  if (s->instancesDue) {
+  // (afterCompaction: the call started over behind a compaction of its own -- the instancer edits are applied, and it does not ask for another)
+  if (s->instancesDue && !afterCompaction) {
     if (!tlasInstancesWanted(s)) return decline("an instance-count or instance-id edit of a built mesh is due");
     bool applied = false;
     if (updateInstancesTwoLevel(s, H, applied, cost) != GI_C_OK) return GI_C_ERROR;
@@ -3176,6 +3487,13 @@ static int updateTopologyTwoLevel(GiCScene* s, SceneHost& H, bool& handled, Upda
     if (mb.m->retired) { retired += n + gone; if (!mb.hidden) retiring++; } else { live += n; retired += gone; if (!mb.hidden) visible += n; }
   }
   if (visible < kIncrementalMinTris) return decline("fewer than 4096 visible triangles after the edit");
+  // (GI_C_SCENE_OPTION_TLAS_COMPACTION, where this stage has an edit of its own to apply -- a sync of instancer edits alone asked above, before it retired its
+  // slots: the counts and bases above are those of the scene as it was, and they are taken again)
+  if (!afterCompaction && (!fresh.empty() || retiring != 0u)) {
+    int rc = GI_C_OK;
+    if (compactBeforeEdit(s, H, retired, live, cost, rc)) return updateTopologyTwoLevel(s, H, handled, cost, true);
+    if (rc != GI_C_OK) return GI_C_ERROR;
+  }
   if (retired > live) return decline("retired triangles outnumber live ones");
   if ((uint64_t)oldTris + appendedTris >= ((uint64_t)1 << 28)) return decline("2^28 or more flat records after the append");
   if ((uint64_t)blasTri0 + appendedFaces >= ((uint64_t)1 << 26)) return decline("2^26 or more unique BLAS triangles after the append");

@@ -328,6 +328,7 @@ int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value)
   if (option == GI_C_SCENE_OPTION_TLAS_INSTANCES) { scene->optTlasInstances = value == 1 ? 1 : 0; return GI_C_OK; } // (read only with options 13, 15 and 20 wanted, on a scene built with option 19)
   if (option == GI_C_SCENE_OPTION_TLAS_TOPOLOGY) { scene->optTlasTopology = value == 1 ? 1 : 0; return GI_C_OK; } // (read only with option 13 wanted, on a scene built with option 19)
   if (option == GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD) { scene->optTlasDeviceBuild = value == 1 ? 1 : 0; return GI_C_OK; } // (read only where options 16 - 18, 20, 21 apply an edit in place)
+  if (option == GI_C_SCENE_OPTION_TLAS_COMPACTION) { scene->optTlasCompaction = value == 1 ? 1 : 0; return GI_C_OK; } // (read only where option 20 or 21 is about to apply an edit)
   if (option == GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD) { scene->optBlasDeviceBuild = value == 1 ? 1 : 0; return GI_C_OK; } // (read where a BLAS is built: the next build or mesh create decides)
   if (option == GI_C_SCENE_OPTION_TLAS_ONLY) { scene->optTlasOnly = value == 1 ? 1 : 0; scene->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER; scene->rebuildDue = true; return GI_C_OK; }
   setError("unknown scene option"); return GI_C_ERROR;

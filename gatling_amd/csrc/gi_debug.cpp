@@ -6,6 +6,7 @@
 #include "gi_blas.h"
 #include "gi_blas_build.h"
 #include "gi_bvh_stages.h"
+#include "gi_compact.h"
 #include "bvh8.h"
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -705,6 +706,120 @@ extern "C" int giCDebugSceneTlasInstanceUpdateStats(const GiCScene* scene, uint6
   for (int i = 0; i < 4; i++) out[i] = s->tlasInstanceCounts[i];
   return GI_C_OK;
 }
+
+extern "C" int giCDebugSceneCompactionCount(const GiCScene* scene, uint64_t* out)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!s || !out) { setError("giCDebugSceneCompactionCount: bad arguments"); return GI_C_ERROR; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  for (int i = 0; i < 4; i++) out[i] = s->compactionStats[i];
+  return GI_C_OK;
+}
+
+// giCDebugCompactRanges / giCDebugCompactRangesHost: k_compact_ranges (onDevice) or its host form (gi_compact.h) over the caller's records and live / dead
+// ranges, against a restatement written without the header's per-piece forms: the live ranges' records filtered in order, then the fields that hold indices
+// rebased one by one through the record types, the id table written at the ids of the flat records that are not hidden.  Scratch arrays start as 0xa5 bytes
+template <class Rec, class Rebase>
+static void compactRestated(const void* records, const GiCDebugCompactRange* ranges, uint32_t rangeCount, std::vector<uint8_t>& want, Rebase&& rebase)
+{
+  const Rec* in = static_cast<const Rec*>(records);
+  std::vector<Rec> live; std::vector<uint32_t> rangeOf;
+  uint32_t at = 0;
+  for (uint32_t k = 0; k < rangeCount; at += ranges[k].count, k++)
+    if (ranges[k].live) for (uint32_t i = 0; i < ranges[k].count; i++) { live.push_back(in[at + i]); rangeOf.push_back(k); } // filter ...
+  for (size_t i = 0; i < live.size(); i++) rebase(live[i], ranges[rangeOf[i]], (uint32_t)i);                            // ... then rebase
+  want.resize(live.size() * sizeof(Rec));
+  if (!live.empty()) memcpy(want.data(), live.data(), want.size());
+}
+static int debugCompactRanges(const char* name, bool onDevice, uint32_t kind, const void* records, uint32_t recordCount, const GiCDebugCompactRange* rangesIn,
+    uint32_t rangeCount, uint32_t* outInfo)
+{
+  if (onDevice && !g_ctx.initialized) { setError(std::string(name) + " before giCInitialize"); return -1; }
+  const uint32_t P = compact_pieces(kind);
+  if (P == 0u || (recordCount && !records) || (rangeCount && !rangesIn)) { setError(std::string(name) + ": bad arguments"); return -1; }
+  try {
+    const size_t recBytes = (size_t)P * compact_piece_bytes(kind);
+    uint64_t covered = 0, liveCount = 0;
+    for (uint32_t k = 0; k < rangeCount; k++) { covered += rangesIn[k].count; if (rangesIn[k].live) liveCount += rangesIn[k].count; }
+    if (covered != recordCount || liveCount >= (1ull << 28)) { setError(std::string(name) + ": the ranges do not cover the records"); return -1; }
+    const uint32_t live = (uint32_t)liveCount, tableCount = kind == COMPACT_TRIS ? live : 0u;
+    // --- the restatement
+    std::vector<uint8_t> want; std::vector<uint32_t> wantTable(tableCount, 0xa5a5a5a5u);
+    switch (kind) {
+      case COMPACT_VERTS: compactRestated<FVertex>(records, rangesIn, rangeCount, want, [](FVertex&, const GiCDebugCompactRange&, uint32_t) {}); break;
+      case COMPACT_BLAS_TRIS: compactRestated<BlasTri>(records, rangesIn, rangeCount, want, [](BlasTri&, const GiCDebugCompactRange&, uint32_t) {}); break;
+      case COMPACT_WORDS: compactRestated<int32_t>(records, rangesIn, rangeCount, want, [](int32_t&, const GiCDebugCompactRange&, uint32_t) {}); break;
+      case COMPACT_SHADE: compactRestated<TriShade>(records, rangesIn, rangeCount, want, [](TriShade& q, const GiCDebugCompactRange& r, uint32_t) {
+          for (int k = 0; k < 3; k++) q.vi[k] += r.delta[0]; }); break;
+      case COMPACT_BLAS_NODES: compactRestated<Node8>(records, rangesIn, rangeCount, want, [](Node8& n, const GiCDebugCompactRange& r, uint32_t) {
+          n.childBase += r.delta[0]; n.triBase += r.delta[1]; }); break;
+      case COMPACT_INSTANCES: compactRestated<InstanceRec>(records, rangesIn, rangeCount, want, [](InstanceRec& ir, const GiCDebugCompactRange& r, uint32_t) { ir.mesh += r.delta[0]; }); break;
+      case COMPACT_INST_TRAV: compactRestated<InstTrav>(records, rangesIn, rangeCount, want, [](InstTrav& tv, const GiCDebugCompactRange& r, uint32_t) { tv.blasRoot += r.delta[0]; }); break;
+      default: compactRestated<TriRec>(records, rangesIn, rangeCount, want, [&](TriRec& t, const GiCDebugCompactRange& r, uint32_t at) {
+          t.instance += r.delta[0]; t.vi[0] += r.delta[1]; t.vi[1] += r.delta[2]; t.vi[2] += r.delta[2];
+          if (!r.hidden && t.origId < tableCount) wantTable[t.origId] = at; }); break;
+    }
+    // --- the table of the live ranges, as gi_build.cpp compactTwoLevel makes it (one entry per live range: empty ones keep theirs; nothing is joined)
+    std::vector<CompactRange> ranges;
+    CompactSizes Z{}; Z.kind = kind; Z.srcCount = recordCount; Z.dstCount = live; Z.tableCount = tableCount;
+    uint32_t src = 0, dst = 0;
+    for (uint32_t k = 0; k < rangeCount; src += rangesIn[k].count, k++) {
+      if (!rangesIn[k].live) continue;
+      ranges.push_back(CompactRange{src, dst, rangesIn[k].count, 0u, {rangesIn[k].delta[0], rangesIn[k].delta[1], rangesIn[k].delta[2]}, rangesIn[k].hidden ? COMPACT_RANGE_HIDDEN : 0u});
+      dst += rangesIn[k].count;
+    }
+    Z.rangeCount = (uint32_t)ranges.size(); Z.wgCount = compactRangesNumber(kind, ranges.data(), Z.rangeCount);
+    if (Z.wgCount == 0xffffffffu || !compactRangesOk(ranges.data(), Z)) { setError(std::string(name) + ": the range table does not pass its check"); return -1; }
+    if (outInfo) { outInfo[0] = compact_items_per_wave(kind); outInfo[1] = compact_items_per_block(kind); outInfo[2] = live; outInfo[3] = Z.wgCount; }
+    // --- the kernel or its host form, into arrays of the exact size
+    std::vector<uint8_t> got((size_t)live * recBytes, 0xa5); std::vector<uint32_t> gotTable(tableCount, 0xa5a5a5a5u);
+    int inPlaceDiffer = 0;
+    if (!onDevice) {
+      // (16-byte aligned pieces: the records as the type they are)
+      std::vector<F4> srcAligned(((size_t)recordCount * recBytes + 15u) / 16u + 1u), dstAligned(((size_t)live * recBytes + 15u) / 16u + 1u);
+      if (recordCount) memcpy(srcAligned.data(), records, (size_t)recordCount * recBytes);
+      memset(static_cast<void*>(dstAligned.data()), 0xa5, dstAligned.size() * sizeof(F4));
+      const uint32_t half = Z.wgCount / 2u; // (in two halves, as the host's thread pool splits the workgroups, and past the end)
+      compactRangesHost(ranges.data(), Z, half, Z.wgCount, srcAligned.data(), dstAligned.data(), gotTable.data());
+      compactRangesHost(ranges.data(), Z, 0u, half, srcAligned.data(), dstAligned.data(), gotTable.data());
+      compactRangesHost(ranges.data(), Z, Z.wgCount, Z.wgCount + 3u, srcAligned.data(), dstAligned.data(), gotTable.data());
+      if (!got.empty()) memcpy(got.data(), dstAligned.data(), got.size());
+      // the host's own form (gi_build.cpp compactTwoLevel): the array compacted where it lies, the table the OLD one -- every visible record named at its old
+      // position -- whose first words become the new one; its differing bytes are counted with the others
+      std::vector<uint32_t> oldTable(tableCount, 0xa5a5a5a5u);
+      if (kind == COMPACT_TRIS) {
+        uint32_t at = 0;
+        for (uint32_t k = 0; k < rangeCount; k++) for (uint32_t i = 0; i < rangesIn[k].count; i++, at++)
+          if (rangesIn[k].live && !rangesIn[k].hidden) { TriRec t; memcpy(&t, reinterpret_cast<const char*>(srcAligned.data()) + (size_t)at * recBytes, sizeof(t)); if (t.origId < tableCount) oldTable[t.origId] = at; }
+      }
+      compactRangesInPlaceHost(ranges.data(), Z, srcAligned.data(), oldTable.data());
+      for (size_t i = 0; i < got.size(); i++) inPlaceDiffer += reinterpret_cast<const uint8_t*>(srcAligned.data())[i] != want[i];
+      for (uint32_t i = 0; i < tableCount; i++) inPlaceDiffer += 4 * (oldTable[i] != wantTable[i]);
+    } else {
+      DeviceBuffer<uint8_t> dSrc, dDst; DeviceBuffer<uint32_t> dTable; DeviceBuffer<CompactRange> dRanges;
+      hipStream_t st = g_ctx.stream;
+      bool ok = hipSetDevice(g_ctx.device) == hipSuccess && dSrc.alloc((size_t)recordCount * recBytes) == GI_C_OK && dDst.alloc(got.size()) == GI_C_OK &&
+          dTable.alloc(tableCount) == GI_C_OK && dRanges.upload(ranges, st) == GI_C_OK;
+      ok = ok && (recordCount == 0u || hipMemcpyAsync(dSrc.ptr, records, (size_t)recordCount * recBytes, hipMemcpyHostToDevice, st) == hipSuccess) &&
+          (got.empty() || hipMemcpyAsync(dDst.ptr, got.data(), got.size(), hipMemcpyHostToDevice, st) == hipSuccess) &&
+          (tableCount == 0u || hipMemcpyAsync(dTable.ptr, gotTable.data(), (size_t)tableCount * 4u, hipMemcpyHostToDevice, st) == hipSuccess);
+      ok = ok && launchCompactRanges(st, ranges.data(), dRanges.ptr, Z, dSrc.ptr, dDst.ptr, tableCount ? dTable.ptr : nullptr) && hipGetLastError() == hipSuccess;
+      ok = ok && (got.empty() || hipMemcpyAsync(got.data(), dDst.ptr, got.size(), hipMemcpyDeviceToHost, st) == hipSuccess) &&
+          (tableCount == 0u || hipMemcpyAsync(gotTable.data(), dTable.ptr, (size_t)tableCount * 4u, hipMemcpyDeviceToHost, st) == hipSuccess);
+      ok = hipStreamSynchronize(st) == hipSuccess && ok;
+      dSrc.release(); dDst.release(); dTable.release(); dRanges.release();
+      if (!ok) { setError(std::string(name) + ": device error"); return -1; }
+    }
+    int differ = inPlaceDiffer;
+    for (size_t i = 0; i < got.size(); i++) differ += got[i] != want[i];
+    for (uint32_t i = 0; i < tableCount; i++) for (int b = 0; b < 4; b++) differ += ((gotTable[i] >> (8 * b)) & 0xffu) != ((wantTable[i] >> (8 * b)) & 0xffu);
+    return differ;
+  } catch (const std::exception& e) { setError(std::string(name) + ": " + e.what()); return -1; }
+}
+extern "C" int giCDebugCompactRanges(uint32_t kind, const void* records, uint32_t recordCount, const GiCDebugCompactRange* ranges, uint32_t rangeCount, uint32_t* outInfo)
+{ return debugCompactRanges("giCDebugCompactRanges", true, kind, records, recordCount, ranges, rangeCount, outInfo); }
+extern "C" int giCDebugCompactRangesHost(uint32_t kind, const void* records, uint32_t recordCount, const GiCDebugCompactRange* ranges, uint32_t rangeCount, uint32_t* outInfo)
+{ return debugCompactRanges("giCDebugCompactRangesHost", false, kind, records, recordCount, ranges, rangeCount, outInfo); }
 
 extern "C" int giCDebugSceneInstanceUpdateCount(const GiCScene* scene, uint64_t* out)
 {

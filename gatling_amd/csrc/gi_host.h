@@ -480,6 +480,10 @@ struct GiCScene : SceneDevice {
   // makeMeshBlas: the scene build's buildTwoLevel and updateTopologyTwoLevel); giCDebugSceneBlasBuildStats: device builds, fallbacks (under the minimum, over
   // the maximum, too deep, memory, error), the last device build's figures
   int32_t optBlasDeviceBuild = 0; uint64_t blasBuildStats[16] = {};
+  // GI_C_SCENE_OPTION_TLAS_COMPACTION: 1 = the ranges options 20 and 21 retired are compacted on the device when they outgrow tlas_compact_percent (gi_build.cpp
+  // compactTwoLevel: read only where updateTopologyTwoLevel / updateInstancesTwoLevel is about to apply an edit); giCDebugSceneCompactionCount: compactions
+  // applied, records moved, bytes released on the primary device, compactions that declined
+  int32_t optTlasCompaction = 0; uint64_t compactionStats[4] = {0, 0, 0, 0};
   std::vector<GiCMesh*> retiredMeshes; // destroyed meshes the resident scene still refers to (GiCMesh::retired): freed by buildScene and with the scene
   ~GiCScene() { for (GiCMesh* m : retiredMeshes) delete m; }
 };
@@ -517,6 +521,7 @@ bool blasDeviceBuildWanted(const GiCScene* s);               // GI_C_SCENE_OPTIO
 // the host builder's BLAS of one mesh: padded face boxes, buildBvh8Boxes; mlo / mhi: the union of the usable faces' boxes
 void buildMeshBlas(const GiCVertex* vertices, const GiCFace* faces, size_t nf, Bvh8& b, std::vector<uint32_t>& order, float mlo[3], float mhi[3]);
 BlasTri makeBlasTri(const GiCVertex* vertices, const GiCFace* faces, uint32_t f); // its record of face f
+bool tlasCompactionWanted(const GiCScene* s);                // GI_C_SCENE_OPTION_TLAS_COMPACTION / GATLING_OPTIONS=tlas_compaction (read where options 20 and 21 apply an edit)
 bool tlasInstancesWanted(const GiCScene* s);                 // GI_C_SCENE_OPTION_TLAS_INSTANCES / GATLING_OPTIONS=tlas_instances (with options 13, 15 and 20 wanted)
 int syncSceneGeometry(GiCScene* s);                          // brings the device scene up to date with the host-side edits (incremental or full build)
 // dirty flags of a material-side edit: DIRTY_MATERIALS alone once the scene / the mesh is part of a built scene (the incremental path), else with DIRTY_BVH

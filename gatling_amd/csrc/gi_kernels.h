@@ -174,6 +174,13 @@ bool launchAppendRecords(hipStream_t s, const AppendMesh& M, TriRec* tris, int32
 struct InstanceJob; struct InstanceJobSizes;
 bool launchInstanceRecords(hipStream_t s, const InstanceJob* hostJobs, const InstanceJob* deviceJobs, const InstanceJobSizes& Z, TriRec* tris, int32_t* triFaceId,
     uint32_t* flatOfOrig, const InstanceRec* instances, const TriShade* triShade, const int32_t* faceIdTable);
+// gi_compact.hip: the live ranges of ONE array kind of a resident two-level scene moved to the front of a new allocation, their indices rebased, in one launch
+// (gi_build.cpp compactTwoLevel, GI_C_SCENE_OPTION_TLAS_COMPACTION; gi_compact.h has every per-item form, CompactRange and CompactSizes).  `hostRanges`: the
+// table `deviceRanges` holds, for the range check (compactRangesOk): false, and nothing launched, for a range outside the old array, destinations that do not
+// ascend without gaps to Z.dstCount, a prefix that is not the range sizes', or src == dst.  `table`: the new id table (COMPACT_TRIS), else null
+struct CompactRange; struct CompactSizes;
+bool launchCompactRanges(hipStream_t s, const CompactRange* hostRanges, const CompactRange* deviceRanges, const CompactSizes& Z, const void* src, void* dst,
+    uint32_t* table);
 void launchSpin(hipStream_t s, unsigned long long ns);           // test hook: occupies a stream for ~ns nanoseconds
 void launchDebugBsdf(hipStream_t s, const MaterialRec* mat, uint32_t shadeClass, uint32_t count, const float* in, float* out);
 void launchDebugSqrt(hipStream_t s, uint32_t first, unsigned long long count, unsigned long long* mismatches); // gi_sqrt against sqrtf over bit patterns

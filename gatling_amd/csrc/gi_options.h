@@ -100,6 +100,13 @@
 //   blas_device_min      BLAS_DEVICE_MIN_DEFAULT   with blas_device_build: meshes of fewer faces keep the host builder (the crossover)
 //   blas_device_max      BLAS_DEVICE_MAX_DEFAULT   with blas_device_build: meshes of more faces keep the host builder (the slab: about 1.5 KB per face)
 //   blas_depth_budget    -         with blas_device_build: lowers the device builder's depth budget below the stack rule's (tests)
+//   tlas_compaction      -1        -1 = the scene option decides (GI_C_SCENE_OPTION_TLAS_COMPACTION), 0 / 1 = the retired ranges topology and instancer edits in
+//                                  place leave on a two-level scene without the flat tree stay until the scene is rebuilt / are compacted on the device
+//                                  when they outgrow tlas_compact_percent (gi_compact.hip; gi_build.cpp compactTwoLevel); read only where tlas_topology or
+//                                  tlas_instances is about to apply an edit
+//   tlas_compact_percent 100       with tlas_compaction: the resident scene is compacted before an edit in place when retired x 100 > live x P on the planned
+//                                  after-edit triangle counts; 100 is the point at which the edit declines and the scene is rebuilt without the option, 0
+//                                  compacts whenever anything is retired (tests)
 //   phase_stats          0         counting builds: print k_path's phase split / k_trace_dyn's lane accounting
 #pragma once
 

@@ -387,7 +387,8 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * giCDebugSceneTlasTopologyUpdateCount, giCDebugAppendRecords and giCDebugAppendRecordsHost, and for GI_C_SCENE_OPTION_TLAS_INSTANCES,
  * giCDebugSceneTlasInstanceUpdateStats, giCDebugInstanceRecords and giCDebugInstanceRecordsHost, and for giCDebugTraversalStackHigh and giCDebugBvhStackReach,
  * and for GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD, giCDebugBuildTlasHost, giCDebugBuildTlas and giCDebugSceneTlasBuildStats, and for giCDebugSceneUpsPlain and
- * giCDebugUpsTraits, and for GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD, giCDebugBuildBlasHost, giCDebugBuildBlas and giCDebugSceneBlasBuildStats. */
+ * giCDebugUpsTraits, and for GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD, giCDebugBuildBlasHost, giCDebugBuildBlas and giCDebugSceneBlasBuildStats, and for
+ * GI_C_SCENE_OPTION_TLAS_COMPACTION, giCDebugSceneCompactionCount, giCDebugCompactRanges and giCDebugCompactRangesHost. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -696,6 +697,18 @@ int giCGetRenderStats(const GiCScene* scene, GiCRenderStats* out);
  * device-built BLAS.  GATLING_OPTIONS=blas_device_build=0|1 overrides the option (hdGatling sets no scene options); blas_depth_budget=N lowers B (tests).
  * DESIGN.md section 6. */
 #define GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD 23
+/* [ext] What becomes of the ranges options 20 and 21 retire -- the records of destroyed meshes, the storage slots of retired instances --; read only where
+ * one of those options is about to apply an edit to a resident two-level scene without the flat tree.  Value 1 = before such an edit declines because
+ * retired triangles outnumber live ones, the sync evaluates retired x 100 > live x P on the planned after-edit counts (P = GATLING_OPTIONS=
+ * tlas_compact_percent, default 100: the point of that decline); where it holds and something retired by an EARLIER sync is resident, the scene is compacted
+ * on the device first (gi_compact.hip): every mesh retired earlier and every free instance slot leaves every array, the live records move to the front of new
+ * allocations in storage order with their indices rebased, the mesh records and scene-data tables are made again, the TLAS is built over the compacted
+ * boxes.  The rule is then evaluated on the compacted scene and the edit goes on as without the option.  Live meshes, meshes hidden by option 18 and the
+ * meshes the very same sync retires stay.  0 = off (default): every launch, flag, counter, statistic and resident byte is what it is without the option.  The
+ * image does not depend on the option.  A compaction declines, leaving the scene untouched, for whatever option 20 declines for on the scene as it is, out of
+ * device memory (new blocks are allocated on every device before anything resident changes), a TLAS over the compacted boxes that is too deep, or a count
+ * that does not add up.  GATLING_OPTIONS=tlas_compaction=0|1 overrides the option (hdGatling sets no scene options).  DESIGN.md section 6. */
+#define GI_C_SCENE_OPTION_TLAS_COMPACTION 24
 int giCGetLookaheadStats(const GiCScene* scene, GiCLookaheadStats* out);
 int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value);
 /* [ext] closest hit of one ray through the device traversal kernel (parity tests of the BVH8 path).
@@ -920,6 +933,23 @@ int giCDebugInstanceRecordsHost(const GiCDebugInstanceMesh* meshes, uint32_t mes
  * appended, out[2] = of those, how many went into reused storage slots, out[3] = instances retired.  Such a sync counts once in
  * giCDebugSceneTlasTopologyUpdateCount, and neither in giCDebugSceneUpdateCounts nor in giCDebugSceneInstanceUpdateCount. */
 int giCDebugSceneTlasInstanceUpdateStats(const GiCScene* scene, uint64_t out[4]);
+/* [ext] [debug] compactions of the retired ranges of this scene (GI_C_SCENE_OPTION_TLAS_COMPACTION): out[0] = compactions applied, out[1] = records moved
+ * (items of all eight array kinds), out[2] = bytes of device memory released on the primary device (old blocks minus new ones), out[3] = compactions that
+ * were due and declined.  A compaction is part of the sync that triggers it and has no entry in giCDebugSceneUpdateCounts. */
+int giCDebugSceneCompactionCount(const GiCScene* scene, uint64_t out[4]);
+/* [ext] [debug] device check of the kernel that compacts one array kind (gi_compact.hip k_compact_ranges).  `kind`: 0 FVertex, 1 BlasTri, 2 face-id words,
+ * 3 TriShade, 4 Node8, 5 InstanceRec, 6 InstTrav, 7 TriRec; `records`: recordCount records of that kind; `ranges`: consecutive ranges that cover them in
+ * order (their counts add up to recordCount; a count may be 0), each live or dead, a live one with the deltas its records' indices move by (by kind:
+ * gi_compact.h) and, for kind 7, `hidden` != 0 where its records must not write the id table.  ONE launch moves all live ranges to the front of a scratch
+ * array pre-filled with a pattern; for kind 7 an id table of one word per live record is pre-filled likewise.  Returns the number of BYTES of the new array
+ * and the table that differ from a straightforward restatement -- the records of the live ranges filtered in order, then their fields rebased one by one, the
+ * table written at the ids of the records that are not hidden -- (0 is the contract), <0 on error (no device, a null array, counts that do not add up, an
+ * unknown kind).  outInfo: [0] whole items a wave holds under the mapping as built, [1] a workgroup, [2] live records, [3] workgroups launched.
+ * giCDebugCompactRangesHost: the host form of the same kernel (gi_compact.h) against the same restatement, and with it the form the host compacts its own
+ * arrays with, in place (compactRangesInPlaceHost; its table starts as the old one, which names every visible record at its old position); no device use. */
+typedef struct GiCDebugCompactRange { uint32_t count, live, delta[3], hidden; } GiCDebugCompactRange;
+int giCDebugCompactRanges(uint32_t kind, const void* records, uint32_t recordCount, const GiCDebugCompactRange* ranges, uint32_t rangeCount, uint32_t outInfo[4]);
+int giCDebugCompactRangesHost(uint32_t kind, const void* records, uint32_t recordCount, const GiCDebugCompactRange* ranges, uint32_t rangeCount, uint32_t outInfo[4]);
 /* [ext] [debug] what a built scene holds of the flat tree (GI_C_SCENE_OPTION_TLAS_ONLY): out[0] = 1 for the two-level layout, out[1] = 1 when the scene was built
  * without the flat tree, out[2] = flat nodes resident on device copy `device`, out[3] = bytes of flat nodes the host copy holds.  GI_C_OK, or GI_C_ERROR for a
  * scene that has not been built or a device copy that does not exist. */
