@@ -87,6 +87,23 @@ class GiCLookaheadStats(C.Structure):
                 ("windowsTraced", C.c_uint64), ("callsServed", C.c_uint64), ("windowsDiscarded", C.c_uint64), ("samplesUnused", C.c_uint64)]
 
 
+# giCDenoise (include/gi_c.h): where the inputs come from
+DENOISE_SOURCE_AUTO, DENOISE_SOURCE_HOST, DENOISE_SOURCE_HOST_FORM = 0, 1, 2
+# (GiCDenoiseStats.deviceInputs / sentInputs are bit masks: 1 colour, 2 normal, 4 depth, 8 albedo)
+
+
+class GiCDenoiseParams(C.Structure):
+    _fields_ = [("color", C.c_void_p), ("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("output", C.c_void_p),
+                ("iterations", C.c_uint32), ("normalSquarings", C.c_uint32), ("sigmaColor", C.c_float), ("sigmaDepth", C.c_float),
+                ("backgroundDepth", C.c_float), ("albedoFloor", C.c_float), ("source", C.c_int32)]
+
+
+class GiCDenoiseStats(C.Structure):
+    _fields_ = [("source", C.c_int32), ("deviceInputs", C.c_uint32), ("sentInputs", C.c_uint32), ("iterations", C.c_uint32),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("bytesSent", C.c_uint64), ("prepareMs", C.c_double), ("passMs", C.c_double * 6),
+                ("copyMs", C.c_double), ("sendMs", C.c_double), ("totalMs", C.c_double)]
+
+
 # every symbol include/gi_c.h declares: (name, restype, argtypes)
 _P, _F, _U, _I = C.c_void_p, C.c_float, C.c_uint32, C.c_int32
 _FP = C.POINTER(C.c_float)
@@ -161,6 +178,9 @@ SYMBOLS = [
     ("giCSetMaterialPrimvarInput", C.c_int, [_P, _I, C.c_char_p]),
     ("giCCreateRenderBuffer", _P, [_U, _U, _I]), ("giCDestroyRenderBuffer", None, [_P]), ("giCGetRenderBufferMem", _P, [_P]),
     ("giCGetRenderBufferDeviceMem", _P, [_P]), ("giCSetRenderBufferDeviceOnly", None, [_P, _I]),
+    ("giCCreateHostRenderBuffer", _P, [_U, _U, _I]),
+    ("giCDenoiseDefaults", None, [C.POINTER(GiCDenoiseParams)]), ("giCDenoise", C.c_int, [C.POINTER(GiCDenoiseParams)]),
+    ("giCGetDenoiseStats", C.c_int, [C.POINTER(GiCDenoiseStats)]),
     ("giCGetRenderStats", C.c_int, [_P, C.POINTER(GiCRenderStats)]), ("giCSetSceneOption", C.c_int, [_P, _I, _I]),
     ("giCGetLookaheadStats", C.c_int, [_P, C.POINTER(GiCLookaheadStats)]),
     ("giCTraceRays", C.c_int, [_P, _U, _FP, _FP, _F, _F, _FP, C.POINTER(C.c_int32)]),
@@ -239,6 +259,64 @@ def _fp(values):
 
 class GiError(RuntimeError):
     pass
+
+
+def denoise_params(**params) -> GiCDenoiseParams:
+    """giCDenoiseDefaults with the named fields replaced: iterations, normalSquarings, sigmaColor, sigmaDepth, backgroundDepth, albedoFloor, source."""
+    p = GiCDenoiseParams()
+    load_library().giCDenoiseDefaults(C.byref(p))
+    for k, v in params.items():
+        if k not in ("iterations", "normalSquarings", "sigmaColor", "sigmaDepth", "backgroundDepth", "albedoFloor", "source"):
+            raise TypeError(f"denoise: unknown parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def denoise_stats() -> dict:
+    """giCGetDenoiseStats: the last giCDenoise of the process -- the source it used, which inputs were read from their device copies and which were sent,
+    the bytes sent, and the times of the prepare launch, every pass and the copy back (device events; the host form: host clock)."""
+    s = GiCDenoiseStats()
+    if load_library().giCGetDenoiseStats(C.byref(s)) != GI_C_OK:
+        raise GiError("giCGetDenoiseStats failed")
+    out = {name: getattr(s, name) for name, _ in GiCDenoiseStats._fields_ if name != "passMs"}
+    out["passMs"] = [float(v) for v in s.passMs][:s.iterations]
+    return out
+
+
+def denoise(color, normal, depth, albedo=None, host_form=False, **params):
+    """giCDenoise over arrays: color / normal / albedo float32 [h, w, 4], depth float32 [h, w]; returns the filtered image [h, w, 4].  ``host_form=True``
+    runs the host form over host render buffers (no device, no giCInitialize); otherwise the arrays are sent to the device
+    (GI_C_DENOISE_SOURCE_HOST: the library must be initialised) and the kernels of gi_denoise.hip run.  The keyword parameters are giCDenoiseParams' fields."""
+    L = load_library()
+    color = np.ascontiguousarray(color, np.float32)
+    h, w = color.shape[:2]
+    arrays = {"color": color, "normal": np.ascontiguousarray(normal, np.float32), "depth": np.ascontiguousarray(depth, np.float32)}
+    if albedo is not None:
+        arrays["albedo"] = np.ascontiguousarray(albedo, np.float32)
+    create = L.giCCreateHostRenderBuffer if host_form else L.giCCreateRenderBuffer
+    bufs = {}
+    try:
+        for name, a in list(arrays.items()) + [("output", None)]:
+            fmt = FORMAT_FLOAT32 if name == "depth" else FORMAT_FLOAT32_VEC4
+            if a is not None and a.shape != ((h, w) if name == "depth" else (h, w, 4)):
+                raise ValueError(f"denoise: {name} has shape {a.shape}")
+            rb = create(w, h, fmt)
+            if not rb:
+                raise GiError("render buffer creation failed: " + L.giCGetLastError().decode())
+            bufs[name] = rb
+            if a is not None and a.nbytes:
+                C.memmove(L.giCGetRenderBufferMem(rb), a.ctypes.data, a.nbytes)
+        p = denoise_params(source=DENOISE_SOURCE_HOST_FORM if host_form else DENOISE_SOURCE_HOST, **params)
+        p.color, p.normal, p.depth, p.albedo, p.output = bufs["color"], bufs["normal"], bufs["depth"], bufs.get("albedo"), bufs["output"]
+        if L.giCDenoise(C.byref(p)) != GI_C_OK:
+            raise GiError("giCDenoise failed: " + L.giCGetLastError().decode())
+        out = np.empty((h, w, 4), np.float32)
+        if out.nbytes:
+            C.memmove(out.ctypes.data, L.giCGetRenderBufferMem(bufs["output"]), out.nbytes)
+        return out
+    finally:
+        for rb in bufs.values():
+            L.giCDestroyRenderBuffer(rb)
 
 
 def miss_rect(bounds, camera, rs: "RenderSettings", width: int, height: int):
@@ -1109,8 +1187,10 @@ class Scene:
         p.aovBindings = C.cast(arr, C.POINTER(GiCAovBinding)); p.aovBindingCount = len(bufs)
         p.camera = _camera(self.desc.camera); p.domeLight = self.dome; p.renderSettings = _settings(settings); p.scene = self.handle
         p.rowBegin, p.rowEnd, p.rowStride = r0, r1, row_stride
+        self._last_aovs = None
         if L.giCRender(C.byref(p)) != GI_C_OK:
             raise GiError("giCRender failed: " + L.giCGetLastError().decode())
+        self._last_aovs = (width, height, {name: rb for name, (rb, fmt, raw, aid) in bufs.items()})
         out = {}
         for name, (rb, fmt, raw, aid) in bufs.items():
             mem = L.giCGetRenderBufferMem(rb)
@@ -1122,6 +1202,34 @@ class Scene:
                 a = np.ctypeslib.as_array(C.cast(mem, C.POINTER(C.c_int32)), shape=(height, width))
             out[name] = a[r0:r1:row_stride].copy()
         return out
+
+    def denoise_last(self, device_only=False, **params):
+        """giCDenoise on the buffers of the last render_aovs, which must have bound the colour, "normal" and "depth" (clear value = backgroundDepth, 1.0 by
+        default); "albedo" is used when it was bound.  source defaults to GI_C_DENOISE_SOURCE_AUTO: the device copies where that render was a whole frame on
+        the primary device.  Returns the filtered image float32 [h, w, 4] (None with ``device_only``); the output buffer is the scene's own, kept per size."""
+        if not getattr(self, "_last_aovs", None):
+            raise GiError("denoise_last: no render_aovs call to take the buffers from")
+        width, height, bufs = self._last_aovs
+        for name in ("color", "normal", "depth"):
+            if name not in bufs:
+                raise GiError(f"denoise_last: the last render_aovs did not bind {name!r}")
+        L = self.L
+        key = ("denoised", width, height)
+        if key not in self._buffers:
+            rb = L.giCCreateRenderBuffer(width, height, FORMAT_FLOAT32_VEC4)
+            if not rb:
+                raise GiError("giCCreateRenderBuffer failed: " + L.giCGetLastError().decode())
+            self._buffers[key] = rb
+        out_rb = self._buffers[key]
+        L.giCSetRenderBufferDeviceOnly(out_rb, int(device_only))
+        p = denoise_params(**params)
+        p.color, p.normal, p.depth, p.albedo, p.output = bufs["color"], bufs["normal"], bufs["depth"], bufs.get("albedo"), out_rb
+        if L.giCDenoise(C.byref(p)) != GI_C_OK:
+            raise GiError("giCDenoise failed: " + L.giCGetLastError().decode())
+        if device_only:
+            return None
+        mem = L.giCGetRenderBufferMem(out_rb)
+        return np.ctypeslib.as_array(C.cast(mem, C.POINTER(C.c_float)), shape=(height, width, 4)).copy()
 
     def device_pointer(self, width, height) -> int:
         return int(self.L.giCGetRenderBufferDeviceMem(self.color_buffer(width, height)))

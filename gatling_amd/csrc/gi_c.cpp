@@ -248,6 +248,9 @@ void giCTerminate(void)
   if (!g_ctx.initialized) return;
   for (auto& w : g_ctx.workers) if (w) w->shutdown();
   g_ctx.workers.clear();
+  (void)hipSetDevice(g_ctx.device);
+  (void)hipStreamSynchronize(g_ctx.stream);
+  releaseDenoiseScratch();
   for (DevCtx& c : g_ctx.devs) {
     (void)hipSetDevice(c.device);
     (void)hipStreamSynchronize(c.stream);
@@ -268,6 +271,7 @@ GiCRenderBuffer* giCCreateRenderBuffer(uint32_t width, uint32_t height, int32_t 
   if (!g_ctx.initialized) { setError("giCCreateRenderBuffer before giCInitialize"); return nullptr; }
   uint32_t stride = (format == GI_C_FORMAT_FLOAT32_VEC4) ? 16u : 4u;
   auto* rb = new GiCRenderBuffer{width, height, stride, (size_t)width * height * stride};
+  rb->format = format;
   size_t bytes = rb->size ? rb->size : 16;
   if (hipMalloc(&rb->deviceMem, bytes) != hipSuccess || hipHostMalloc(&rb->hostMem, bytes, hipHostMallocDefault) != hipSuccess) {
     setError("failed to allocate render buffer");
@@ -278,9 +282,22 @@ GiCRenderBuffer* giCCreateRenderBuffer(uint32_t width, uint32_t height, int32_t 
   memset(rb->hostMem, 0, bytes);
   return rb;
 }
+// [ext] host memory alone (giCDenoise's host form and its sent inputs): no HIP call
+GiCRenderBuffer* giCCreateHostRenderBuffer(uint32_t width, uint32_t height, int32_t format)
+{
+  const uint32_t stride = (format == GI_C_FORMAT_FLOAT32_VEC4) ? 16u : 4u;
+  auto* rb = new GiCRenderBuffer{width, height, stride, (size_t)width * height * stride};
+  rb->format = format;
+  rb->hostOnly = true;
+  rb->hostMem = aligned_alloc(64, ((rb->size ? rb->size : 16) + 63u) & ~(size_t)63u);
+  if (!rb->hostMem) { setError("failed to allocate render buffer"); delete rb; return nullptr; }
+  memset(rb->hostMem, 0, rb->size ? rb->size : 16);
+  return rb;
+}
 void giCDestroyRenderBuffer(GiCRenderBuffer* rb)
 {
   if (!rb) return;
+  if (rb->hostOnly) { free(rb->hostMem); delete rb; return; }
   std::lock_guard<std::mutex> g(g_ctx.resourceMutex);
   (void)hipStreamSynchronize(g_ctx.stream);
   if (rb->deviceMem) (void)hipFree(rb->deviceMem);

@@ -1,4 +1,4 @@
-// gi_host.h -- shared declarations of the host side (gi_c.cpp, gi_scene.cpp, gi_textures.cpp, gi_lights.cpp, gi_build.cpp, gi_render.cpp, gi_debug.cpp): host
+// gi_host.h -- shared declarations of the host side (gi_c.cpp, gi_scene.cpp, gi_textures.cpp, gi_lights.cpp, gi_build.cpp, gi_render.cpp, gi_debug.cpp, gi_denoise_host.cpp): host
 // side of the MI355X-native gi core: scene containers, dirty flags, host packing, BVH build,
 // uploads, the wavefront bounce loop, render buffers.  Implements include/gi_c.h.
 //
@@ -229,7 +229,14 @@ struct GiCRenderBuffer {
   bool scratch = false; // internal stand-in that lives in the rendering device's own scratch memory (no replicas)
   std::vector<void*> replicaMem; // [slot - 1]: the same buffer on the other devices (multi-device renders), allocated on first use
   void* stageMem = nullptr; // pinned, rb->size: where the row shares of devices WITHOUT peer access to the primary pass through (allocated on first use)
+  // the last giCRender that bound the buffer rendered the WHOLE frame on the primary device alone: deviceMem holds what hostMem holds (or would, deviceOnly).
+  // giCRender sets it; row shares, multi-device renders and failed renders clear it (giCDenoise GI_C_DENOISE_SOURCE_AUTO reads such a copy in place)
+  bool wholeFrame = false;
+  bool hostOnly = false; // giCCreateHostRenderBuffer: hostMem is plain host memory, there is no deviceMem
+  int32_t format = GI_C_FORMAT_FLOAT32_VEC4; // GiCRenderBufferFormat it was created with (stride alone does not tell Int32 from Float32)
 };
+// gi_denoise_host.cpp: the library's denoiser scratch on the primary device (giCTerminate frees it)
+void releaseDenoiseScratch();
 
 // Sample look-ahead (GI_C_SCENE_OPTION_SAMPLE_LOOKAHEAD; gi_render.cpp planLookahead / serveFromWindow): the window one device holds in its per-sample buffer --
 // the samples [firstOffset, firstOffset + calls * spp) of every pixel of its rows, traced as ONE batch by the window's first call -- and what it was traced

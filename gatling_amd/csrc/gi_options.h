@@ -107,6 +107,9 @@
 //   tlas_compact_percent 100       with tlas_compaction: the resident scene is compacted before an edit in place when retired x 100 > live x P on the planned
 //                                  after-edit triangle counts; 100 is the point at which the edit declines and the scene is rebuilt without the option, 0
 //                                  compacts whenever anything is retired (tests)
+//   denoise_form         0         giCDenoise: where k_denoise_pass takes its taps from (gi_denoise.hip; every form stores the same bytes): 0 = an LDS tile with
+//                                  a 2 x step halo at steps 1 and 2, direct 16-byte loads above (the measured choice); 1 = direct loads at
+//                                  every step; 2 = the tile at steps 1, 2 and 4
 //   phase_stats          0         counting builds: print k_path's phase split / k_trace_dyn's lane accounting
 #pragma once
 

@@ -1118,6 +1118,7 @@ static int giCRenderImpl(const GiCRenderParams* params)
   const GiCAovBinding* colorBinding = nullptr;
   for (uint32_t i = 0; i < params->aovBindingCount; i++) {
     if (!params->aovBindings[i].renderBuffer) { setError("giCRender: AOV binding without render buffer"); return GI_C_ERROR; }
+    if (params->aovBindings[i].renderBuffer->hostOnly) { setError("giCRender: a host render buffer (giCCreateHostRenderBuffer) cannot be rendered into"); return GI_C_ERROR; }
     if (params->aovBindings[i].aovId == GI_C_AOV_COLOR) colorBinding = &params->aovBindings[i];
   }
   if (params->aovBindingCount == 0) { setError("giCRender: no AOV bindings"); return GI_C_ERROR; }
@@ -1215,6 +1216,14 @@ static int giCRenderImpl(const GiCRenderParams* params)
     rc = renderOnDevice(s, *s, job);
   } else {
     rc = renderOnDevices(s, nDev, job);
+  }
+  // whose device copy on the primary device is the whole frame now (GiCRenderBuffer::wholeFrame; giCDenoise reads such a copy in place): the colour AOV and
+  // the AOVs the AOV kernels make, after a render of every row on the primary device alone
+  for (uint32_t i = 0; i < params->aovBindingCount; i++) {
+    const GiCAovBinding& b = params->aovBindings[i];
+    const bool pathAov = b.aovId == GI_C_AOV_NEE || b.aovId == GI_C_AOV_BOUNCES || b.aovId == GI_C_AOV_CLOCK_CYCLES || b.aovId < 0 || b.aovId >= GI_C_AOV_COUNT;
+    b.renderBuffer->wholeFrame = rc == GI_C_OK && nDev == 1u && rowStride == 1u && rowBegin == 0u && rowEnd == height && !pathAov &&
+        b.renderBuffer->width == width && b.renderBuffer->height == height;
   }
   if (rc != GI_C_OK) return rc;
   s->sampleOffset += rs.spp; // Gi.cpp:2515

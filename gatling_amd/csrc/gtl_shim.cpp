@@ -746,4 +746,18 @@ namespace gtl
   { auto* b = giCCreateRenderBuffer(w, h, int(f)); return b ? new GiRenderBuffer{b} : nullptr; }
   void giDestroyRenderBuffer(GiRenderBuffer* b) { if (!b) return; giCDestroyRenderBuffer(b->h); delete b; }
   void* giGetRenderBufferMem(GiRenderBuffer* b) { return b ? giCGetRenderBufferMem(b->h) : nullptr; }
+
+  // [ext] -> giCDenoise over the wrapped handles
+  GiStatus gtlDenoise(const GtlDenoiseParams& p)
+  {
+    GiCDenoiseParams c;
+    giCDenoiseDefaults(&c);
+    c.color = p.color ? p.color->h : nullptr; c.albedo = p.albedo ? p.albedo->h : nullptr; c.normal = p.normal ? p.normal->h : nullptr;
+    c.depth = p.depth ? p.depth->h : nullptr; c.output = p.output ? p.output->h : nullptr;
+    c.iterations = p.iterations; c.normalSquarings = p.normalSquarings; c.sigmaColor = p.sigmaColor; c.sigmaDepth = p.sigmaDepth;
+    c.backgroundDepth = p.backgroundDepth; c.albedoFloor = p.albedoFloor; c.source = p.source;
+    if (giCDenoise(&c) == GI_C_OK) return GiStatus::Ok;
+    fprintf(stderr, "[gatling_gi] gtlDenoise: %s\n", giCGetLastError());
+    return GiStatus::Error;
+  }
 }

@@ -388,7 +388,8 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * giCDebugSceneTlasInstanceUpdateStats, giCDebugInstanceRecords and giCDebugInstanceRecordsHost, and for giCDebugTraversalStackHigh and giCDebugBvhStackReach,
  * and for GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD, giCDebugBuildTlasHost, giCDebugBuildTlas and giCDebugSceneTlasBuildStats, and for giCDebugSceneUpsPlain and
  * giCDebugUpsTraits, and for GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD, giCDebugBuildBlasHost, giCDebugBuildBlas and giCDebugSceneBlasBuildStats, and for
- * GI_C_SCENE_OPTION_TLAS_COMPACTION, giCDebugSceneCompactionCount, giCDebugCompactRanges and giCDebugCompactRangesHost. */
+ * GI_C_SCENE_OPTION_TLAS_COMPACTION, giCDebugSceneCompactionCount, giCDebugCompactRanges and giCDebugCompactRangesHost, and for giCCreateHostRenderBuffer,
+ * giCDenoiseDefaults, giCDenoise and giCGetDenoiseStats. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -502,6 +503,62 @@ void* giCGetRenderBufferMem(GiCRenderBuffer* renderBuffer);
 void* giCGetRenderBufferDeviceMem(GiCRenderBuffer* renderBuffer);
 /* [ext] when nonzero, giCRender leaves results on the device only (no D2H copy); default 0 = reference behaviour */
 void giCSetRenderBufferDeviceOnly(GiCRenderBuffer* renderBuffer, int32_t deviceOnly);
+/* [ext] a render buffer that is host memory alone: no device copy, no HIP call, usable without giCInitialize.  It serves giCDenoise with
+ * GI_C_DENOISE_SOURCE_HOST_FORM (every buffer) and as an INPUT of the other sources (sent from its memory); giCRender refuses it.  Destroyed with
+ * giCDestroyRenderBuffer; giCGetRenderBufferDeviceMem answers NULL. */
+GiCRenderBuffer* giCCreateHostRenderBuffer(uint32_t width, uint32_t height, int32_t format /* GiCRenderBufferFormat */);
+
+/* [ext] Denoiser of the colour AOV: an edge-stopping a-trous wavelet filter guided by the normal, depth and (optionally) albedo AOVs the library already
+ * renders -- what a viewport shows during the first seconds after an edit is a 1 - 16 spp image.  The filter is this library's own: nothing in the reference
+ * pins it.  It is specified in DESIGN.md section 6 "Denoiser" and gi_denoise.h: `iterations` Jacobi passes of a 5 x 5 B3-spline kernel at steps 1, 2, 4 ...,
+ * over colour / max(albedo, albedoFloor), with rational weights 1 / (1 + d^2) on depth (scale sigmaDepth; the depth AOV is log-depth) and on colour (scale
+ * sigmaColor, halved every pass) and max(n_p . n_q, 0) squared `normalSquarings` times on the normals.  Pixels whose depth is `backgroundDepth` (exact
+ * compare: bind the depth AOV with that clear value) or not finite, or whose colour or normal is not finite, are UNGUIDED: they come out bytewise as they
+ * went in and contribute to no other pixel.  Alpha is passed through.  Only + - x / and a maximum on fp32 in one association: the device kernels
+ * (gi_denoise.hip), the host form and tests/denoise_ref.py agree bit for bit.
+ *
+ * color / normal / albedo / output are Float32Vec4 buffers, depth a Float32 one, all of one size (sides at most 65535); albedo may be NULL.  Inputs are
+ * never written -- giCRender's progressive accumulation reads the previous colour back from the colour buffer's device copy -- so `output` must be a buffer
+ * of its own: aliasing an input is refused.
+ *   GI_C_DENOISE_SOURCE_AUTO       an input is read from its DEVICE COPY when the last giCRender that bound it rendered the whole frame on the primary device
+ *                                  alone; otherwise (a row share, a multi-device render, never rendered) it is sent from its host memory, and if it is
+ *                                  deviceOnly the call is refused.
+ *   GI_C_DENOISE_SOURCE_HOST       every input is sent from its host memory (tests feed synthetic guides).
+ *   GI_C_DENOISE_SOURCE_HOST_FORM  the host form runs on the calling thread and touches no device; works without giCInitialize.  The result goes to `output`'s
+ *                                  host memory alone.
+ * AUTO and HOST launch on the primary device's stream without a host wait between passes, write `output`'s device copy, and copy it to `output`'s host memory
+ * unless `output` is deviceOnly; they return when that is done.  Scratch (three Float32Vec4 planes, and a staging plane per sent input) belongs to the library,
+ * is reused while the size does not change and freed by giCTerminate.
+ * Refused with GI_C_ERROR and a giCGetLastError message: a NULL params or required buffer, sizes that differ, a wrong format, aliasing, iterations outside
+ * 1 .. 6, normalSquarings above 6, a sigma or floor that is not finite or not positive, a non-finite backgroundDepth, an unknown source.
+ * NOT concurrent with a giCRender that binds any of the buffers, nor with another giCDenoise on one of them (calls are serialised inside the library). */
+#define GI_C_DENOISE_SOURCE_AUTO 0
+#define GI_C_DENOISE_SOURCE_HOST 1
+#define GI_C_DENOISE_SOURCE_HOST_FORM 2
+typedef struct GiCDenoiseParams {
+  GiCRenderBuffer *color, *albedo /* may be NULL */, *normal, *depth, *output;
+  uint32_t iterations, normalSquarings;
+  float sigmaColor, sigmaDepth, backgroundDepth, albedoFloor;
+  int32_t source;   /* GI_C_DENOISE_SOURCE_* */
+} GiCDenoiseParams;
+/* of the last giCDenoise that ran in this process (a refused call leaves them alone) */
+typedef struct GiCDenoiseStats {
+  int32_t source;          /* what the call did: AUTO = every input read from its device copy, HOST = at least one input sent, HOST_FORM */
+  uint32_t deviceInputs;   /* bit mask of the inputs read from their device copy: 1 colour, 2 normal, 4 depth, 8 albedo ...              */
+  uint32_t sentInputs;     /* ... and of those sent from host memory                                                                     */
+  uint32_t iterations;
+  uint32_t width, height;
+  uint64_t bytesSent;      /* host-to-device bytes of the sent inputs                                                                    */
+  double prepareMs;        /* device events: k_denoise_prepare (HOST_FORM: host clock) ...                                               */
+  double passMs[6];        /* ... each k_denoise_pass ...                                                                                */
+  double copyMs;           /* ... and the copy of the output to host memory (0 for a deviceOnly output)                                  */
+  double sendMs;           /* the host-to-device copies of the sent inputs                                                               */
+  double totalMs;          /* host clock around the whole call                                                                           */
+} GiCDenoiseStats;
+void giCDenoiseDefaults(GiCDenoiseParams* params); /* iterations 5, normalSquarings 4, sigmaColor 2, sigmaDepth 0.02, backgroundDepth 1, albedoFloor 1e-3, AUTO; buffers NULL */
+int giCDenoise(const GiCDenoiseParams* params);
+int giCGetDenoiseStats(GiCDenoiseStats* out);
+
 /* [ext] statistics of the last giCRender on this scene; countTraversal != 0 in giCSetSceneOption enables
  * node/triangle counters (slower; measurement runs only). */
 int giCGetRenderStats(const GiCScene* scene, GiCRenderStats* out);

@@ -144,4 +144,18 @@ namespace gtl
   GiRenderBuffer* giCreateRenderBuffer(uint32_t width, uint32_t height, GiRenderBufferFormat format);
   void giDestroyRenderBuffer(GiRenderBuffer*);
   void* giGetRenderBufferMem(GiRenderBuffer*);
+
+  // ---- [ext] denoiser of the colour AOV (-> giCDenoise, include/gi_c.h; the filter is this library's own, nothing in the reference pins it): an a-trous filter
+  // guided by the Normal, Depth and (optional) Albedo AOVs of the same giRender.  `output` is a buffer of its own -- the colour buffer is never written, the
+  // next progressive giRender blends against it.  source: 0 = read the buffers where the last giRender left them on the device, 1 = send their host memory,
+  // 2 = run on the host.  Not concurrent with a giRender that binds one of the buffers.  INTEGRATION.md has the lines a render delegate adds.
+  struct GtlDenoiseParams
+  {
+    GiRenderBuffer* color = nullptr; GiRenderBuffer* albedo = nullptr /* may stay null */; GiRenderBuffer* normal = nullptr; GiRenderBuffer* depth = nullptr;
+    GiRenderBuffer* output = nullptr;
+    uint32_t iterations = 5, normalSquarings = 4;
+    float sigmaColor = 2.0f, sigmaDepth = 0.02f, backgroundDepth = 1.0f /* the Depth binding's clear value */, albedoFloor = 1.0e-3f;
+    int32_t source = 0;
+  };
+  GiStatus gtlDenoise(const GtlDenoiseParams&);
 }

@@ -8,6 +8,10 @@
  *   tools/gi_render scene.gscn out.pfm [--image-width W] [--image-height H] [--spp N] [--max-bounces B] [--rr-bounce-offset K]
  *                   [--next-event-estimation 0|1] [--medium-stack-size K] [--max-sample-value X] [--rows begin:end[:stride]]
  *                   [--device D] [--stats]
+ *                   [--denoise out.pfm [--denoise-iterations I] [--denoise-normal-squarings K] [--denoise-sigma-color S] [--denoise-sigma-depth S]
+ *                    [--denoise-albedo-floor F] [--denoise-no-albedo 1]]
+ *                   --denoise binds the normal, depth (clear value 1.0) and albedo AOVs (clear 0) beside the colour, runs giCDenoise (the library's own
+ *                   a-trous filter: include/gi_c.h) on the device copies and writes the filtered image beside the unfiltered one (whole frames only)
  *   tools/gi_render scene.gscn --info        parses the file and prints its inventory; needs no GPU
  *
  * Output by extension: .pfm (RGB float, bottom row first -- the buffer's own order), .raw (RGBA float32, bottom row first),
@@ -104,7 +108,10 @@ int main(int argc, char** argv)
     fs.clear[0] = fs.clear[1] = fs.clear[2] = fs.clear[3] = 1.0f;
   }
   uint32_t rowBegin = 0, rowEnd = 0, rowStride = 1;
-  int device = 0, stats = 0;
+  int device = 0, stats = 0, denoiseNoAlbedo = 0;
+  const char* denoisePath = NULL;
+  GiCDenoiseParams dn;
+  giCDenoiseDefaults(&dn);
   for (int i = 3; i < argc; i++) {
     const char* a = argv[i];
     const char* v = i + 1 < argc ? argv[i + 1] : NULL;
@@ -122,6 +129,13 @@ int main(int argc, char** argv)
     else if (!strcmp(a, "--medium-stack-size")) fs.rs.mediumStackSize = (uint32_t)atoi(v);
     else if (!strcmp(a, "--depth-of-field")) fs.rs.depthOfField = atoi(v);
     else if (!strcmp(a, "--device")) device = atoi(v);
+    else if (!strcmp(a, "--denoise")) denoisePath = v;
+    else if (!strcmp(a, "--denoise-iterations")) dn.iterations = (uint32_t)atoi(v);
+    else if (!strcmp(a, "--denoise-normal-squarings")) dn.normalSquarings = (uint32_t)atoi(v);
+    else if (!strcmp(a, "--denoise-sigma-color")) dn.sigmaColor = (float)atof(v);
+    else if (!strcmp(a, "--denoise-sigma-depth")) dn.sigmaDepth = (float)atof(v);
+    else if (!strcmp(a, "--denoise-albedo-floor")) dn.albedoFloor = (float)atof(v);
+    else if (!strcmp(a, "--denoise-no-albedo")) denoiseNoAlbedo = atoi(v);
     else if (!strcmp(a, "--rows")) { if (sscanf(v, "%u:%u:%u", &rowBegin, &rowEnd, &rowStride) < 2) return fail("--rows wants begin:end[:stride]"); }
     else { fprintf(stderr, "gi_render: unknown option %s\n", a); return 2; }
   }
@@ -302,14 +316,30 @@ int main(int argc, char** argv)
   /* one giCRender call; the colour AOV arrives in the render buffer's host memory (Gi.cpp:2492-2502) */
   GiCRenderBuffer* rb = giCCreateRenderBuffer(fs.width, fs.height, GI_C_FORMAT_FLOAT32_VEC4);
   if (!rb) { fprintf(stderr, "gi_render: giCCreateRenderBuffer: %s\n", giCGetLastError()); return 1; }
-  GiCAovBinding binding;
-  memset(&binding, 0, sizeof binding);
-  binding.aovId = GI_C_AOV_COLOR;
-  memcpy(binding.clearValue, fs.clear, 16);
-  binding.renderBuffer = rb;
+  GiCAovBinding bindings[4];
+  memset(bindings, 0, sizeof bindings);
+  bindings[0].aovId = GI_C_AOV_COLOR;
+  memcpy(bindings[0].clearValue, fs.clear, 16);
+  bindings[0].renderBuffer = rb;
+  uint32_t nBindings = 1;
+  GiCRenderBuffer* guides[4] = {NULL, NULL, NULL, NULL}; /* normal, depth, albedo, the filtered image */
+  if (denoisePath) { /* the guides of giCDenoise: depth cleared to backgroundDepth (1.0), normal and albedo to 0 */
+    static const int32_t ids[3] = {GI_C_AOV_NORMAL, GI_C_AOV_DEPTH, GI_C_AOV_ALBEDO};
+    const float one = dn.backgroundDepth;
+    for (int g = 0; g < 4; g++) {
+      if (g == 2 && denoiseNoAlbedo) continue;
+      guides[g] = giCCreateRenderBuffer(fs.width, fs.height, g == 1 ? GI_C_FORMAT_FLOAT32 : GI_C_FORMAT_FLOAT32_VEC4);
+      if (!guides[g]) { fprintf(stderr, "gi_render: giCCreateRenderBuffer: %s\n", giCGetLastError()); return 1; }
+      if (g == 3) break;
+      bindings[nBindings].aovId = ids[g];
+      if (g == 1) memcpy(bindings[nBindings].clearValue, &one, 4);
+      bindings[nBindings].renderBuffer = guides[g];
+      nBindings++;
+    }
+  }
   GiCRenderParams p;
   memset(&p, 0, sizeof p);
-  p.aovBindings = &binding; p.aovBindingCount = 1; p.camera = cam; p.domeLight = dome; p.renderSettings = fs.rs; p.scene = scene;
+  p.aovBindings = bindings; p.aovBindingCount = nBindings; p.camera = cam; p.domeLight = dome; p.renderSettings = fs.rs; p.scene = scene;
   p.rowBegin = rowBegin; p.rowEnd = rowEnd ? rowEnd : fs.height; p.rowStride = rowStride ? rowStride : 1;
   if (giCRender(&p) != GI_C_OK) { fprintf(stderr, "gi_render: giCRender: %s\n", giCGetLastError()); return 1; }
   if (stats) {
@@ -319,9 +349,24 @@ int main(int argc, char** argv)
              st.bvhBuildMs, st.uploadMs, (double)st.samples / (st.renderMs * 1e3), (unsigned long long)st.samples, (unsigned long long)st.segments,
              st.nodeCount, st.triangleCount);
   }
-  const int rc = write_image(argv[2], (const float*)giCGetRenderBufferMem(rb), fs.width, fs.height);
+  int rc = write_image(argv[2], (const float*)giCGetRenderBufferMem(rb), fs.width, fs.height);
+  if (denoisePath) {
+    dn.color = rb; dn.normal = guides[0]; dn.depth = guides[1]; dn.albedo = guides[2]; dn.output = guides[3];
+    if (giCDenoise(&dn) != GI_C_OK) { fprintf(stderr, "gi_render: giCDenoise: %s\n", giCGetLastError()); return 1; }
+    if (stats) {
+      GiCDenoiseStats ds;
+      if (giCGetDenoiseStats(&ds) == GI_C_OK) {
+        double passes = 0.0;
+        for (uint32_t i = 0; i < ds.iterations; i++) passes += ds.passMs[i];
+        printf("denoise %.3f ms (inputs from device copies: mask %u, sent: mask %u, %llu bytes; prepare %.3f ms, %u passes %.3f ms, copy %.3f ms)\n", ds.totalMs,
+               ds.deviceInputs, ds.sentInputs, (unsigned long long)ds.bytesSent, ds.prepareMs, ds.iterations, passes, ds.copyMs);
+      }
+    }
+    if (!rc) rc = write_image(denoisePath, (const float*)giCGetRenderBufferMem(guides[3]), fs.width, fs.height);
+  }
 
   giCDestroyRenderBuffer(rb);
+  for (int g = 0; g < 4; g++) if (guides[g]) giCDestroyRenderBuffer(guides[g]);
   for (uint32_t m = 0; m < nMesh; m++) giCDestroyMesh(meshes[m]);
   for (uint32_t m = 0; m < nMat; m++) giCDestroyMaterial(materials[m]);
   if (dome) giCDestroyDomeLight(dome);
