@@ -195,6 +195,8 @@ SYMBOLS = [
     ("giCDebugEditDirtyFlags", C.c_int32, [_I, _I]), ("giCDebugSceneUpdateCounts", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("giCDebugSceneVisibilityUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugSceneClassState", C.c_int, [_P, C.POINTER(C.c_uint32)]),
     ("giCDebugSceneUpsPlain", C.c_int, [_P, C.POINTER(C.c_uint32)]), ("giCDebugUpsTraits", C.c_int, [C.POINTER(GiCMaterialDesc), _U, C.c_int, C.POINTER(C.c_uint32)]),
+    ("giCDebugSceneLeafLift", C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    ("giCDebugLeafLift", C.c_int, [_FP, _U, C.c_int32, _P, _U, _U, _P, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]),
     ("giCDebugSceneVertexUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugRefitBvh", C.c_int, [_FP, _FP, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("giCDebugSceneRefitCheck", C.c_int, [_P, _U, C.POINTER(C.c_uint32)]),
     ("giCDebugSceneTopologyUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]),
@@ -330,6 +332,26 @@ def miss_rect(bounds, camera, rs: "RenderSettings", width: int, height: int):
     return tuple(int(v) for v in out)
 
 
+def leaf_lift(tri_verts, mode: int = 1, tree_nodes=None, tree_depth: int = 0) -> dict:
+    """giCDebugLeafLift: the leaf lift of small flat trees (leaf_lift.cpp) on the host.  Without `tree_nodes`: the host builder's BVH8 over `tri_verts` (n x 3 x 3
+    triangles in scene order), then the pass as `mode` says -- 0: not run, 1: run, -1: as a scene build would (GATLING_OPTIONS leaf_lift, the LDS limits).  With
+    `tree_nodes` (bytes or a uint8 array of 80-byte nodes, breadth-first, `tree_depth` levels): that tree over the triangles in ITS leaf order.  Returns
+    {"violations", "nodes" (uint8, n x 80), "order" (ids in leaf order), "depth", "lifted", "active", "cost_before", "cost_after"}.  Host only."""
+    import numpy as np
+    L = load_library()
+    v = np.ascontiguousarray(tri_verts, np.float32).reshape(-1, 9)
+    given = None if tree_nodes is None else np.ascontiguousarray(np.frombuffer(bytes(tree_nodes), np.uint8)).reshape(-1, 80)
+    cap = max(len(v), 1) + 1 if given is None else len(given)
+    nodes = np.zeros((cap, 80), np.uint8); order = np.zeros(max(len(v), 1), np.uint32); info = np.zeros(4, np.uint32); cost = np.zeros(2, np.float64)
+    rc = L.giCDebugLeafLift(v.ctypes.data_as(_FP), len(v), mode, None if given is None else given.ctypes.data_as(_P), 0 if given is None else len(given), tree_depth,
+                            nodes.ctypes.data_as(_P), cap, order.ctypes.data_as(C.POINTER(C.c_uint32)), info.ctypes.data_as(C.POINTER(C.c_uint32)),
+                            cost.ctypes.data_as(C.POINTER(C.c_double)))
+    if rc < 0:
+        raise GiError(f"giCDebugLeafLift failed ({rc})")
+    return {"violations": rc, "nodes": nodes[:int(info[0])].copy(), "order": order[:len(v)].copy(), "depth": int(info[1]), "lifted": int(info[2]),
+            "active": int(info[3]), "cost_before": float(cost[0]), "cost_after": float(cost[1])}
+
+
 def bvh_stack_reach(tri_verts, origins, dirs):
     """giCDebugBvhStackReach: (levels, nodes, reach) of the host builder's BVH8 over `tri_verts` (n x 3 x 3 world-space triangles in scene order) -- reach[i] is
     the most stack entries the traversal kernels' ordered walk holds for ray i.  The walk tests boxes only and culls nothing, so reach is an UPPER BOUND on
@@ -377,6 +399,7 @@ def debug_clone_instance(vertices, faces, xform_a, xform_b, left_handed=False) -
 
 OPTION_BLAS_DEVICE_BUILD = 23  # 1: the BLAS of a mesh of blas_device_min .. blas_device_max faces of a two-level scene is built on the primary device (gi_blas_build.hip: face boxes from the uploaded points, then the device TLAS builder's stages under a deeper budget) instead of with the host builder, which remains the fallback; read at the scene build and where option 20 applies a mesh create (include/gi_c.h); 0 = off (default)
 OPTION_TLAS_COMPACTION = 24  # 1: before a topology or instancer edit in place of a two-level scene without the flat tree declines because retired triangles outnumber live ones (retired x 100 > live x GATLING_OPTIONS=tlas_compact_percent, default 100), the ranges earlier edits retired are compacted on the device (gi_compact.hip: one launch per array kind into new allocations, indices rebased, the TLAS rebuilt) and the edit goes on; read only where option 20 or 21 applies an edit (include/gi_c.h); 0 = off (default)
+OPTION_LEAF_LIFT = 25  # -1 / 1: the flat tree of a scene the fused kernel walks out of LDS (LDS-resident, not two-level, a root and one level below it) goes through the leaf lift (leaf_lift.cpp) at the scene build; 0: the builder's tree, byte for byte (include/gi_c.h); default on; GATLING_OPTIONS=leaf_lift overrides it
 TLAS_BUILD_TOO_DEEP = -2  # GI_C_TLAS_BUILD_TOO_DEEP
 
 
@@ -1070,6 +1093,14 @@ class Scene:
         if self.L.giCDebugSceneUpsPlain(self.handle, c) != GI_C_OK:
             raise GiError("giCDebugSceneUpsPlain failed")
         return {"traits": int(c[0]), "launched": int(c[1])}
+
+    def leaf_lift(self) -> dict:
+        """giCDebugSceneLeafLift: `lifted` -- the leaf slots the last scene build moved into free slots of the root (OPTION_LEAF_LIFT; 0: switched off, a scene
+        outside the pass, or nothing to gain) -- and `depth`, the levels of the host-built flat tree."""
+        c = (C.c_uint32 * 2)()
+        if self.L.giCDebugSceneLeafLift(self.handle, c) != GI_C_OK:
+            raise GiError("giCDebugSceneLeafLift failed")
+        return {"lifted": int(c[0]), "depth": int(c[1])}
 
     def path_walk_stats(self) -> dict:
         """giCDebugPathWalkStats: the fused kernel's trips and walk-step tables of the last render (OPTION_COUNT_TRAVERSAL; all zero otherwise).  stepTrips[k] /

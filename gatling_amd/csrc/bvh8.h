@@ -28,6 +28,16 @@ struct Bvh8 {
 // single empty root so traversal code needs no special case.
 void buildBvh8(const std::vector<TriRec>& tris, Bvh8& out);
 
+// A pass over a finished tree of buildBvh8 (leaf_lift.cpp): while the builder's cost model -- area x (1 | cPrim x references), summed over the dequantised
+// slot boxes -- strictly decreases, one leaf slot of an internal child moves into a free slot of the child's parent, the best move first.  Internal topology,
+// quantisation frames and origId do not change; `tris` is laid out again (node order, slot order within a node).  Returns the leaf slots moved; 0: `bvh` is
+// untouched, byte for byte.  Trees deeper than kLeafLiftMaxDepth levels are left alone: the pass is for trees the fused kernel walks out of LDS, where a
+// second node visit is a wave-wide step (scene sync decides which trees see it: gi_build.cpp buildScene).
+constexpr uint32_t kLeafLiftMaxDepth = 2;
+uint32_t liftLeafSlots(Bvh8& bvh);
+// the model cost the pass minimises, over all occupied slots of `nodes`
+double bvh8ModelCost(const std::vector<Node8>& nodes);
+
 // The same tree over caller-supplied, already padded boxes (6 floats per item: min xyz, max xyz): the TLAS over instance bounds and
 // the per-mesh BLAS of the two-level layout.  `order[k]` is the item a leaf slot's k-th reference (Node8::triBase + offset) names.
 void buildBvh8Boxes(const float* boxes, size_t count, Bvh8& out, std::vector<uint32_t>& order);

@@ -769,6 +769,12 @@ bool tlasOnlyWanted(const GiCScene* s)
   const long o = optionValue("tlas_only", -1);
   return o >= 0 ? o == 1 : s->optTlasOnly == 1;
 }
+// GI_C_SCENE_OPTION_LEAF_LIFT / GATLING_OPTIONS=leaf_lift: the flat tree of a small scene goes through liftLeafSlots (buildScene below; default on)
+bool leafLiftWanted(const GiCScene* s)
+{
+  const long o = optionValue("leaf_lift", -1);
+  return o >= 0 ? o == 1 : (s->optLeafLift < 0 ? LEAF_LIFT_DEFAULT != 0 : s->optLeafLift == 1);
+}
 // is the two-level layout wanted for a scene of `flatTris` flattened triangles, before any flat tree exists?  buildTwoLevel's rules but the one on node bytes,
 // which needs that tree
 static bool twoLevelWantedWithoutTree(const GiCScene* s, size_t flatTris)
@@ -815,6 +821,7 @@ int buildScene(GiCScene* s)
   std::unique_ptr<SceneHost> hostPtr(new SceneHost());
   SceneHost& H = *hostPtr;
   s->host.reset(); // (a failed build leaves no stale host copy behind)
+  s->liftedLeafSlots = 0u; // (giCDebugSceneLeafLift: what this build's tree got; only the host-built flat tree below is offered to the pass)
   for (GiCMesh* m : s->retiredMeshes) delete m; // (nothing refers to them any more: updateTopology kept them for the host copy that is gone)
   s->retiredMeshes.clear();
   for (GiCMesh* m : s->meshes) { m->builtInstances = 0xffffffffu; m->xformDirty = false; m->instDirty.clear(); m->visToggled = false; m->vertsEdited = false;
@@ -882,6 +889,11 @@ int buildScene(GiCScene* s)
     warnInactive(meshBuilds, perMesh);
   }
   if (buildTwoLevel(s, meshBuilds, instances, bvh.tris.size(), bvh.nodes.size(), H.two, true) != GI_C_OK) return GI_C_ERROR;
+  // Leaf lift (leaf_lift.cpp; GI_C_SCENE_OPTION_LEAF_LIFT / GATLING_OPTIONS=leaf_lift, default on): the flat tree of a scene the fused kernel walks out of LDS
+  // -- LDS-resident, not two-level, a root and one level below it -- hands leaf slots that stretch a child's box to free slots of the root.  Before anything
+  // is derived from the triangle order (flatOfOrig, triFaceId, triGeomNormal below).  Scenes this small rebuild on every geometry edit (kIncrementalMinTris),
+  // so the pass reruns with them and no edit in place ever meets a lifted tree.
+  if (leafLiftWanted(s) && !s->twoLevel && sceneFitsLds(bvh.nodes.size(), bvh.tris.size())) s->liftedLeafSlots = liftLeafSlots(bvh);
   if (s->twoLevel) {
     H.flatOfOrig.resize(bvh.tris.size());
     for (size_t i = 0; i < bvh.tris.size(); i++) H.flatOfOrig[bvh.tris[i].origId] = (uint32_t)i;

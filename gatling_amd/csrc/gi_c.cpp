@@ -348,6 +348,8 @@ int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value)
   if (option == GI_C_SCENE_OPTION_TLAS_COMPACTION) { scene->optTlasCompaction = value == 1 ? 1 : 0; return GI_C_OK; } // (read only where option 20 or 21 is about to apply an edit)
   if (option == GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD) { scene->optBlasDeviceBuild = value == 1 ? 1 : 0; return GI_C_OK; } // (read where a BLAS is built: the next build or mesh create decides)
   if (option == GI_C_SCENE_OPTION_TLAS_ONLY) { scene->optTlasOnly = value == 1 ? 1 : 0; scene->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER; scene->rebuildDue = true; return GI_C_OK; }
+  // (read at the scene build: the next build decides)
+  if (option == GI_C_SCENE_OPTION_LEAF_LIFT) { scene->optLeafLift = value < 0 ? -1 : (value ? 1 : 0); scene->dirty |= DIRTY_BVH | DIRTY_FRAMEBUFFER; scene->rebuildDue = true; return GI_C_OK; }
   setError("unknown scene option"); return GI_C_ERROR;
 }
 

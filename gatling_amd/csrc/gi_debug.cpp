@@ -169,6 +169,59 @@ extern "C" int giCDebugValidateBvh(const float* triVerts, uint32_t triCount, uin
   return validateTree(bvh.nodes, bvh.tris, triCount);
 }
 
+// giCDebugLeafLift / giCDebugSceneLeafLift: the leaf lift of small flat trees (leaf_lift.cpp; gi_build.cpp buildScene).  Host only.
+extern "C" int giCDebugLeafLift(const float* triVerts, uint32_t triCount, int32_t mode, const void* treeNodes, uint32_t treeNodeCount, uint32_t treeDepth,
+    void* outNodes, uint32_t nodeCap, uint32_t* outOrder, uint32_t* outInfo, double* outCost)
+{
+  if ((triCount && (!triVerts || !outOrder)) || !outNodes || !outInfo || !outCost || (treeNodes && treeNodeCount == 0u)) return -1;
+  std::vector<TriRec> tris(triCount);
+  for (uint32_t i = 0; i < triCount; i++) {
+    const float* p = triVerts + 9 * (size_t)i;
+    for (int a = 0; a < 3; a++) { tris[i].v0[a] = p[a]; tris[i].e1[a] = p[3 + a] - p[a]; tris[i].e2[a] = p[6 + a] - p[a]; }
+    tris[i].instance = 0; tris[i].prim = i; tris[i].origId = i;
+  }
+  Bvh8 bvh;
+  if (treeNodes) { // a tree of the caller's making: every triangle is taken as referenced, the level table is derived from the child indices
+    bvh.nodes.resize(treeNodeCount); memcpy(bvh.nodes.data(), treeNodes, (size_t)treeNodeCount * sizeof(Node8));
+    bvh.tris = tris; bvh.activeTris = triCount; bvh.maxDepth = treeDepth;
+    std::vector<uint32_t> depth(treeNodeCount, 0u); depth[0] = 1u;
+    for (uint32_t i = 0; i < treeNodeCount; i++) {
+      const uint32_t internal = (uint32_t)__builtin_popcount(bvh.nodes[i].imask);
+      for (uint32_t k = 0; k < internal; k++) {
+        const uint64_t c = (uint64_t)bvh.nodes[i].childBase + k;
+        if (c <= i || c >= treeNodeCount || depth[i] == 0u) return -1;
+        depth[c] = depth[i] + 1u;
+      }
+    }
+    for (uint32_t i = 0; i < treeNodeCount; i++) if (depth[i] == 0u || depth[i] > treeDepth || (i && depth[i] < depth[i - 1u])) return -1;
+    for (uint32_t i = 0; i < treeNodeCount; i++) if (i == 0u || depth[i] != depth[i - 1u]) bvh.levelStart.push_back(i);
+    bvh.levelStart.push_back(treeNodeCount);
+  } else buildBvh8(tris, bvh);
+  outCost[0] = bvh8ModelCost(bvh.nodes);
+  const std::vector<uint32_t> levels = bvh.levelStart;
+  uint32_t lifted = 0u;
+  // -1: the scene build's rule but the layout (no scene here: a flat tree by construction)
+  const bool run = mode == 1 || (mode < 0 && optionValue("leaf_lift", LEAF_LIFT_DEFAULT) != 0 && sceneFitsLds(bvh.nodes.size(), bvh.tris.size()));
+  if (run) lifted = liftLeafSlots(bvh);
+  outCost[1] = bvh8ModelCost(bvh.nodes);
+  if (bvh.nodes.size() > nodeCap) return -2;
+  if (bvh.levelStart != levels || bvh.tris.size() != triCount) return -3; // (the pass leaves the level table and the record count alone)
+  memcpy(outNodes, bvh.nodes.data(), bvh.nodes.size() * sizeof(Node8));
+  for (uint32_t i = 0; i < triCount; i++) outOrder[i] = bvh.tris[i].origId;
+  outInfo[0] = (uint32_t)bvh.nodes.size(); outInfo[1] = bvh.maxDepth; outInfo[2] = lifted; outInfo[3] = bvh.activeTris;
+  return validateTree(bvh.nodes, bvh.tris, triCount);
+}
+
+extern "C" int giCDebugSceneLeafLift(const GiCScene* scene, uint32_t* out)
+{
+  GiCScene* s = const_cast<GiCScene*>(scene);
+  if (!s || !out) { setError("giCDebugSceneLeafLift: bad arguments"); return GI_C_ERROR; }
+  std::lock_guard<std::mutex> guard(s->mutex);
+  out[0] = s->liftedLeafSlots;
+  out[1] = s->host && !s->host->treeless ? s->host->bvh.maxDepth : 0u;
+  return GI_C_OK;
+}
+
 // giCDebugBvhStackReach: the ordered walk of gi_traversal.h (trav_node_pick / trav_pop: a node's hit internal children in octant-flipped slot order, highest
 // bit first, the rest pushed) over the host-built tree, boxes only -- how many stack entries a ray's walk holds at most.  Nothing is culled: no triangle is
 // tested, so the distance never shrinks and every internal child whose box the ray meets counts; the box test is the device's with a wider margin (a box the

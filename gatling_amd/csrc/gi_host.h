@@ -491,6 +491,9 @@ struct GiCScene : SceneDevice {
   // compactTwoLevel: read only where updateTopologyTwoLevel / updateInstancesTwoLevel is about to apply an edit); giCDebugSceneCompactionCount: compactions
   // applied, records moved, bytes released on the primary device, compactions that declined
   int32_t optTlasCompaction = 0; uint64_t compactionStats[4] = {0, 0, 0, 0};
+  // GI_C_SCENE_OPTION_LEAF_LIFT: -1 = the default (LEAF_LIFT_DEFAULT, gi_kernels.h), 0 / 1 = the flat tree of a small scene stays the builder's / goes through
+  // liftLeafSlots (leaf_lift.cpp; gi_build.cpp buildScene); giCDebugSceneLeafLift: the leaf slots the last scene build moved
+  int32_t optLeafLift = -1; uint32_t liftedLeafSlots = 0;
   std::vector<GiCMesh*> retiredMeshes; // destroyed meshes the resident scene still refers to (GiCMesh::retired): freed by buildScene and with the scene
   ~GiCScene() { for (GiCMesh* m : retiredMeshes) delete m; }
 };
@@ -519,7 +522,8 @@ void nodeBounds(const Node8& n, float box[6]);               // dequantised boun
 bool instanceUpdatesWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_INSTANCE_UPDATES / GATLING_OPTIONS=instance_updates (with topology updates wanted)
 bool tlasUpdatesWanted(const GiCScene* s);                   // GI_C_SCENE_OPTION_TLAS_UPDATES / GATLING_OPTIONS=tlas_updates
 bool blasUpdatesWanted(const GiCScene* s);                   // GI_C_SCENE_OPTION_BLAS_UPDATES / GATLING_OPTIONS=blas_updates
-bool tlasOnlyWanted(const GiCScene* s);                      // GI_C_SCENE_OPTION_TLAS_ONLY / GATLING_OPTIONS=tlas_only (read at the build, with the two-level layout wanted)
+bool leafLiftWanted(const GiCScene* s);                      // GI_C_SCENE_OPTION_LEAF_LIFT / GATLING_OPTIONS=leaf_lift (read at the scene build)
+bool tlasOnlyWanted(const GiCScene* s);                   // GI_C_SCENE_OPTION_TLAS_ONLY / GATLING_OPTIONS=tlas_only (read at the build, with the two-level layout wanted)
 bool tlasVisibilityWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_TLAS_VISIBILITY / GATLING_OPTIONS=tlas_visibility (with visibility updates wanted)
 bool topologyUpdatesWanted(const GiCScene* s);               // GI_C_SCENE_OPTION_TOPOLOGY_UPDATES / GATLING_OPTIONS=topology_updates
 bool tlasTopologyWanted(const GiCScene* s);                  // GI_C_SCENE_OPTION_TLAS_TOPOLOGY / GATLING_OPTIONS=tlas_topology (with topology updates wanted)

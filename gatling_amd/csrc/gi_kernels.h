@@ -75,6 +75,7 @@ constexpr long UPS_PLAIN_DEFAULT = 1;  // GATLING_OPTIONS=ups_plain (gi_options.
 constexpr long WALK_CARRY_DEFAULT = 8; // GATLING_OPTIONS=walk_carry (gi_options.h)
 constexpr long LOBE_PARK_DEFAULT = 8;  // GATLING_OPTIONS=lobe_park (gi_options.h)
 constexpr long RING_CARRY_DEFAULT = 1; // GATLING_OPTIONS=ring_carry (gi_options.h)
+constexpr long LEAF_LIFT_DEFAULT = 1;  // GATLING_OPTIONS=leaf_lift (gi_options.h; read at the scene build: gi_build.cpp leafLiftWanted)
 // Where k_path keeps its parked hits (the lot): in the rows of its per-lane traversal stack that no walk of the tree reaches.  A walk pushes at most bvhDepth
 // entries, so of the `stack` rows (4 for trees of depth <= 4, else 8) the rows from `row` = bvhDepth on are free; a row of a wave's 64 columns holds 8 records
 // of 16 dwords.  capacity 0: nothing is free, the parking is off for this tree.  The launch's LDS is traceLdsBytes(stack, ...) as ever: the lot adds nothing.

@@ -37,6 +37,10 @@
 //                                  compiled for what those materials have in common -- no coat (clearcoat +0 in every one) -- which leaves out the
 //                                  operations that are exact identities then (gi_shading.h bsdf_sample; the traits: gi_build.cpp
 //                                  deriveSceneClasses, giCDebugSceneUpsPlain).  0 = the general class-1 kernel.  Counting builds never run the variant
+//   leaf_lift            1         scene build: the flat tree of a scene the fused kernel walks out of LDS (LDS-resident, not two-level, a root and one level
+//                                  below it) goes through liftLeafSlots (leaf_lift.cpp): leaf slots that stretch a child's box move into free slots of the
+//                                  root while the builder's cost model strictly decreases.  0 = the builder's tree, byte for byte.  Overrides
+//                                  GI_C_SCENE_OPTION_LEAF_LIFT; read at the scene build (giCDebugSceneLeafLift shows what it did)
 //   fused                1         LDS-resident scenes run the fused persistent kernel
 //   pool_slots           0         pin the path pool (slots); 0 = the memory plan decides
 //   sample_buffer_mb     0         pin the per-sample buffer (MiB); 0 = the memory plan decides

@@ -1,4 +1,6 @@
-// gi_path.hip -- k_path: the fused persistent path kernel for scenes whose whole BVH lives in LDS (cornell: 5 nodes, 46 triangles).
+// gi_path.hip -- k_path: the fused persistent path kernel for scenes whose whole BVH lives in LDS (cornell: 4 nodes -- a root and three children --, 46
+// triangles).  The tree it walks is the host builder's after the leaf lift (leaf_lift.cpp; gi_build.cpp buildScene): for a tree of two levels every second
+// node visit is a wave-wide step of the closest-hit loop below, so scene sync moves leaf slots that stretch a child's box into free slots of the root.
 //
 // The wavefront pipeline (gi_kernels.hip) streams every path through HBM once per stage and bounce: ray record out, hit record in,
 // 64-byte slot gathered and scattered -- on config C2 1.6 TB per frame for a scene of 2.6 KB.  When the scene is LDS-resident none

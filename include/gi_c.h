@@ -389,7 +389,7 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * and for GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD, giCDebugBuildTlasHost, giCDebugBuildTlas and giCDebugSceneTlasBuildStats, and for giCDebugSceneUpsPlain and
  * giCDebugUpsTraits, and for GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD, giCDebugBuildBlasHost, giCDebugBuildBlas and giCDebugSceneBlasBuildStats, and for
  * GI_C_SCENE_OPTION_TLAS_COMPACTION, giCDebugSceneCompactionCount, giCDebugCompactRanges and giCDebugCompactRangesHost, and for giCCreateHostRenderBuffer,
- * giCDenoiseDefaults, giCDenoise and giCGetDenoiseStats. */
+ * giCDenoiseDefaults, giCDenoise and giCGetDenoiseStats, and for GI_C_SCENE_OPTION_LEAF_LIFT, giCDebugSceneLeafLift and giCDebugLeafLift. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -766,6 +766,14 @@ int giCGetRenderStats(const GiCScene* scene, GiCRenderStats* out);
  * device memory (new blocks are allocated on every device before anything resident changes), a TLAS over the compacted boxes that is too deep, or a count
  * that does not add up.  GATLING_OPTIONS=tlas_compaction=0|1 overrides the option (hdGatling sets no scene options).  DESIGN.md section 6. */
 #define GI_C_SCENE_OPTION_TLAS_COMPACTION 24
+/* [ext] Leaf lift; read at the scene build.  The flat tree of a scene the fused kernel walks out of LDS -- LDS-resident, not two-level, a root and one level
+ * below it -- is handed to a pass (leaf_lift.cpp liftLeafSlots) that moves leaf slots of an internal child into free slots of the root while the builder's
+ * cost model, evaluated over the dequantised slot boxes, strictly decreases: a leaf the top-down split left in a subtree it stretches is tested one level up,
+ * and the child's box shrinks to the rest.  Internal topology and triangle ids are untouched; the image does not depend on the option (the traversal
+ * contract).  -1 = the default (on), 0 = the builder's tree, byte for byte, 1 = on.  Setting it rebuilds the scene at the next render.
+ * GATLING_OPTIONS=leaf_lift=0|1 overrides the option (hdGatling sets no scene options).  giCDebugSceneLeafLift reports what the last build moved.
+ * DESIGN.md sections 1 and 6. */
+#define GI_C_SCENE_OPTION_LEAF_LIFT 25
 int giCGetLookaheadStats(const GiCScene* scene, GiCLookaheadStats* out);
 int giCSetSceneOption(GiCScene* scene, int32_t option, int32_t value);
 /* [ext] closest hit of one ray through the device traversal kernel (parity tests of the BVH8 path).
@@ -1040,6 +1048,18 @@ int giCDebugSceneUpsPlain(const GiCScene* scene, uint32_t* out /* 2 */);
 /* [ext] out[0] of giCDebugSceneUpsPlain for a scene whose visible meshes would use exactly the `count` materials of `descs`.  derive != 0: the descriptions are
  * what giCCreateMaterial takes; 0: `p` holds derived records word for word.  `flags` bit 31 marks a material with a bound input.  Host only: no scene. */
 int giCDebugUpsTraits(const GiCMaterialDesc* descs, uint32_t count, int derive, uint32_t* out /* 1 */);
+/* [ext] leaf lift (GI_C_SCENE_OPTION_LEAF_LIFT): out[0] the leaf slots the scene's last build moved into free slots of their parent's parent node (0: the
+ * option or $GATLING_OPTIONS leaf_lift=0, a scene outside the pass -- beyond LDS, two-level, deeper than a root and one level, device-built --, or a tree the
+ * model finds nothing to gain on), out[1] the levels of the flat tree (1: a root alone).  Host only: no device work. */
+int giCDebugSceneLeafLift(const GiCScene* scene, uint32_t* out /* 2 */);
+/* [ext] host-only: the pass itself.  treeNodes == NULL: the host builder's tree over `triCount` triangles (9 floats each: v0, v1, v2; ids = positions), then
+ * the pass as `mode` says -- 0: not run, 1: run, -1: as a scene build would ($GATLING_OPTIONS leaf_lift, default on, and the LDS limits).  treeNodes != NULL:
+ * `treeNodeCount` 80-byte nodes of a tree of `treeDepth` levels, breadth-first, over the triangles in THAT tree's leaf order (ids = positions), and the pass
+ * run over it as `mode` says.  outNodes: room for `nodeCap` nodes (an error when the tree has more); outOrder: `triCount` ids, the leaf order of the result;
+ * outInfo[0] nodes, [1] levels, [2] leaf slots moved, [3] triangles the tree references; outCost[0] / [1]: the model cost before / after the pass.
+ * Returns the violations of the result's conservativeness contract as giCDebugValidateBvh counts them (0 = none), <0 on error. */
+int giCDebugLeafLift(const float* triVerts, uint32_t triCount, int32_t mode, const void* treeNodes, uint32_t treeNodeCount, uint32_t treeDepth,
+                     void* outNodes, uint32_t nodeCap, uint32_t* outOrder, uint32_t* outInfo /* 4 */, double* outCost /* 2 */);
 /* [ext] the fused path kernel's walk counters of the scene's last render, for renders with GI_C_SCENE_OPTION_COUNT_TRAVERSAL (all zero otherwise): out[0] trips
  * of all waves, [1 + k] the trips whose closest-hit loop reached step k (k = 7: every step from the eighth on), [9 + k] the lanes walking when those steps
  * began, [17] the steps that began with fewer than 8 lanes walking.  With $GATLING_OPTIONS walk_carry=K set explicitly a counting build carries walks as other
