@@ -20,6 +20,7 @@ if os.environ.get("GATLING_GI_LIB"):  # experiments: a variant build of the same
 
 GI_C_OK = 0
 AOV_COLOR = 0
+AOV_EXT_MOMENTS = 0x100  # GI_C_AOV_EXT_MOMENTS: a binding id outside the GiCAovId enum (include/gi_c.h)
 FORMAT_INT32, FORMAT_FLOAT32, FORMAT_FLOAT32_VEC4 = 0, 1, 2
 OPTION_COUNT_TRAVERSAL, OPTION_KERNEL_TIMERS, OPTION_POOL_SLOTS, OPTION_SAMPLE_BUFFER_MB, OPTION_TRACE_DYNAMIC, OPTION_TWO_LEVEL, OPTION_FUSED_PATH, OPTION_DEVICES = 1, 2, 3, 4, 5, 6, 7, 8
 OPTION_SAMPLE_LOOKAHEAD = 10  # N >= 2: a progressive call may trace the samples of up to N calls in one batch (include/gi_c.h); 0 / 1 = off (default)
@@ -96,6 +97,10 @@ class GiCDenoiseParams(C.Structure):
     _fields_ = [("color", C.c_void_p), ("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("output", C.c_void_p),
                 ("iterations", C.c_uint32), ("normalSquarings", C.c_uint32), ("sigmaColor", C.c_float), ("sigmaDepth", C.c_float),
                 ("backgroundDepth", C.c_float), ("albedoFloor", C.c_float), ("source", C.c_int32)]
+
+
+class GiCDenoiseVarianceParams(C.Structure):
+    _fields_ = [("base", GiCDenoiseParams), ("moments", C.c_void_p), ("sigmaVariance", C.c_float), ("varianceFloor", C.c_float), ("minSamples", C.c_uint32)]
 
 
 class GiCDenoiseStats(C.Structure):
@@ -179,6 +184,7 @@ SYMBOLS = [
     ("giCCreateRenderBuffer", _P, [_U, _U, _I]), ("giCDestroyRenderBuffer", None, [_P]), ("giCGetRenderBufferMem", _P, [_P]),
     ("giCGetRenderBufferDeviceMem", _P, [_P]), ("giCSetRenderBufferDeviceOnly", None, [_P, _I]),
     ("giCCreateHostRenderBuffer", _P, [_U, _U, _I]),
+    ("giCDenoiseVarianceDefaults", None, [C.POINTER(GiCDenoiseVarianceParams)]), ("giCDenoiseVariance", C.c_int, [C.POINTER(GiCDenoiseVarianceParams)]),
     ("giCDenoiseDefaults", None, [C.POINTER(GiCDenoiseParams)]), ("giCDenoise", C.c_int, [C.POINTER(GiCDenoiseParams)]),
     ("giCGetDenoiseStats", C.c_int, [C.POINTER(GiCDenoiseStats)]),
     ("giCGetRenderStats", C.c_int, [_P, C.POINTER(GiCRenderStats)]), ("giCSetSceneOption", C.c_int, [_P, _I, _I]),
@@ -232,6 +238,8 @@ SYMBOLS = [
     ("giCDebugPathLot", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     ("giCDebugTraversalStackHigh", C.c_int, [_P, C.POINTER(C.c_uint32)]),
     ("giCDebugBvhStackReach", C.c_int, [_FP, _U, _FP, _FP, _U, C.POINTER(C.c_uint32)]),
+    ("giCDebugSampleMoments", C.c_int, [_P, _FP, _FP, C.POINTER(C.c_uint32), _FP, _FP]),
+    ("giCDebugSampleMomentsHost", C.c_int, [_P, _FP, _FP, C.POINTER(C.c_uint32), _FP, _FP]),
     ("giCDebugMissRect", C.c_int, [_FP, C.POINTER(GiCCameraDesc), C.POINTER(GiCRenderSettings), _U, _U, C.POINTER(C.c_uint32)]),
 ]
 
@@ -285,7 +293,27 @@ def denoise_stats() -> dict:
     return out
 
 
-def denoise(color, normal, depth, albedo=None, host_form=False, **params):
+VARIANCE_PARAMS = ("sigmaVariance", "varianceFloor", "minSamples")
+
+
+def denoise_variance_params(**params) -> GiCDenoiseVarianceParams:
+    """giCDenoiseVarianceDefaults with the named fields replaced: giCDenoiseParams' fields (into ``base``) and sigmaVariance, varianceFloor, minSamples."""
+    p = GiCDenoiseVarianceParams()
+    load_library().giCDenoiseVarianceDefaults(C.byref(p))
+    p.base = denoise_params(**{k: v for k, v in params.items() if k not in VARIANCE_PARAMS})
+    for k in VARIANCE_PARAMS:
+        if k in params:
+            setattr(p, k, params[k])
+    return p
+
+
+def denoise_variance(color, normal, depth, moments, albedo=None, host_form=False, **params):
+    """giCDenoiseVariance over arrays: as ``denoise`` with ``moments`` float32 [h, w, 4] = (S1, S2, n, 0) (the "moments" AOV); the keyword parameters are
+    giCDenoiseParams' fields and sigmaVariance, varianceFloor, minSamples."""
+    return denoise(color, normal, depth, albedo, host_form, _moments=moments, **params)
+
+
+def denoise(color, normal, depth, albedo=None, host_form=False, _moments=None, **params):
     """giCDenoise over arrays: color / normal / albedo float32 [h, w, 4], depth float32 [h, w]; returns the filtered image [h, w, 4].  ``host_form=True``
     runs the host form over host render buffers (no device, no giCInitialize); otherwise the arrays are sent to the device
     (GI_C_DENOISE_SOURCE_HOST: the library must be initialised) and the kernels of gi_denoise.hip run.  The keyword parameters are giCDenoiseParams' fields."""
@@ -295,6 +323,8 @@ def denoise(color, normal, depth, albedo=None, host_form=False, **params):
     arrays = {"color": color, "normal": np.ascontiguousarray(normal, np.float32), "depth": np.ascontiguousarray(depth, np.float32)}
     if albedo is not None:
         arrays["albedo"] = np.ascontiguousarray(albedo, np.float32)
+    if _moments is not None:
+        arrays["moments"] = np.ascontiguousarray(_moments, np.float32)
     create = L.giCCreateHostRenderBuffer if host_form else L.giCCreateRenderBuffer
     bufs = {}
     try:
@@ -308,9 +338,15 @@ def denoise(color, normal, depth, albedo=None, host_form=False, **params):
             bufs[name] = rb
             if a is not None and a.nbytes:
                 C.memmove(L.giCGetRenderBufferMem(rb), a.ctypes.data, a.nbytes)
-        p = denoise_params(source=DENOISE_SOURCE_HOST_FORM if host_form else DENOISE_SOURCE_HOST, **params)
+        source = DENOISE_SOURCE_HOST_FORM if host_form else DENOISE_SOURCE_HOST
+        vp = denoise_variance_params(source=source, **params) if _moments is not None else None
+        p = vp.base if vp is not None else denoise_params(source=source, **params)
         p.color, p.normal, p.depth, p.albedo, p.output = bufs["color"], bufs["normal"], bufs["depth"], bufs.get("albedo"), bufs["output"]
-        if L.giCDenoise(C.byref(p)) != GI_C_OK:
+        if vp is not None:
+            vp.moments = bufs["moments"]
+            if L.giCDenoiseVariance(C.byref(vp)) != GI_C_OK:
+                raise GiError("giCDenoiseVariance failed: " + L.giCGetLastError().decode())
+        elif L.giCDenoise(C.byref(p)) != GI_C_OK:
             raise GiError("giCDenoise failed: " + L.giCGetLastError().decode())
         out = np.empty((h, w, 4), np.float32)
         if out.nbytes:
@@ -319,6 +355,28 @@ def denoise(color, normal, depth, albedo=None, host_form=False, **params):
     finally:
         for rb in bufs.values():
             L.giCDestroyRenderBuffer(rb)
+
+
+def debug_sample_moments(samples, pixel_major, width, rows, first=0, count=None, prev=None, rect=None, miss_rgb=None, host_only=False):
+    """giCDebugSampleMoments: the kernel of the moments AOV (k_moments) over a synthetic per-sample buffer.  ``samples``: float32 [pixels, S, 4] with
+    ``pixel_major`` else [S, pixels, 4], pixels = width * rows; the samples [first, first + count) of every pixel are folded (count defaults to the rest),
+    from ``prev`` ([pixels, 4]) or from zero.  ``rect`` = (x0, y0, x1, y1): pixels outside it have no records, each sample of theirs is ``miss_rgb``.
+    Returns M float32 [pixels, 4] = (S1, S2, n, 0).  host_only: giCDebugSampleMomentsHost, the host form of the same per-pixel code (no device)."""
+    L = load_library()
+    samples = np.ascontiguousarray(samples, np.float32)
+    pixels = int(width) * int(rows)
+    S = samples.shape[1] if pixel_major else samples.shape[0]
+    assert samples.shape == ((pixels, S, 4) if pixel_major else (S, pixels, 4)), samples.shape
+    d = (C.c_uint32 * 6)(int(width), int(rows), S, int(first), int(S - first if count is None else count), int(bool(pixel_major)))
+    ptr = lambda a: None if a is None else a.ctypes.data_as(_FP)
+    prev_a = None if prev is None else np.ascontiguousarray(prev, np.float32).reshape(pixels, 4)
+    rect_a = None if rect is None else (C.c_uint32 * 4)(*[int(v) for v in rect])
+    miss_a = None if miss_rgb is None else np.ascontiguousarray(miss_rgb, np.float32)
+    out = np.empty((pixels, 4), np.float32)
+    fn = L.giCDebugSampleMomentsHost if host_only else L.giCDebugSampleMoments
+    if fn(d, ptr(samples), ptr(prev_a), rect_a, ptr(miss_a), ptr(out)) != GI_C_OK:
+        raise GiError("giCDebugSampleMoments failed: " + L.giCGetLastError().decode())
+    return out
 
 
 def miss_rect(bounds, camera, rs: "RenderSettings", width: int, height: int):
@@ -1184,7 +1242,9 @@ class Scene:
             "texcoords": (4, FORMAT_FLOAT32_VEC4), "bounces": (5, FORMAT_FLOAT32_VEC4), "clockCycles": (6, FORMAT_FLOAT32_VEC4), "opacity": (7, FORMAT_FLOAT32_VEC4),
             "tangents": (8, FORMAT_FLOAT32_VEC4), "bitangents": (9, FORMAT_FLOAT32_VEC4), "thinWalled": (10, FORMAT_FLOAT32_VEC4),
             "objectId": (11, FORMAT_INT32), "depth": (12, FORMAT_FLOAT32), "faceId": (13, FORMAT_INT32), "instanceId": (14, FORMAT_INT32),
-            "doubleSided": (15, FORMAT_FLOAT32_VEC4), "albedo": (16, FORMAT_FLOAT32_VEC4)}
+            "doubleSided": (15, FORMAT_FLOAT32_VEC4), "albedo": (16, FORMAT_FLOAT32_VEC4),
+            # GI_C_AOV_EXT_MOMENTS: per pixel (S1, S2, n, 0) over the luminance of the accumulation's samples; the clear value is not used
+            "moments": (AOV_EXT_MOMENTS, FORMAT_FLOAT32_VEC4)}
 
     def render_aovs(self, settings: RenderSettings, width: int, height: int, names, clear_values=None, with_color=True, rows=None, row_stride=1):
         """One giCRender call with the colour AOV (optional) plus the named non-colour AOVs bound (Gi.h:36-56, 161-166).
@@ -1234,14 +1294,22 @@ class Scene:
             out[name] = a[r0:r1:row_stride].copy()
         return out
 
-    def denoise_last(self, device_only=False, **params):
+    def aov_host_array(self, name: str, width: int, height: int):
+        """The whole host copy of the buffer render_aovs keeps for `name` at this size, every row of it (render_aovs returns the rendered rows alone)."""
+        rb = self._buffers[("aov", name, width, height)]
+        fmt = self.AOVS[name][1]
+        ctype, shape = (C.c_float, (height, width, 4)) if fmt == FORMAT_FLOAT32_VEC4 else ((C.c_float if fmt == FORMAT_FLOAT32 else C.c_int32), (height, width))
+        return np.ctypeslib.as_array(C.cast(self.L.giCGetRenderBufferMem(rb), C.POINTER(ctype)), shape=shape).copy()
+
+    def denoise_last(self, device_only=False, variance=False, **params):
         """giCDenoise on the buffers of the last render_aovs, which must have bound the colour, "normal" and "depth" (clear value = backgroundDepth, 1.0 by
         default); "albedo" is used when it was bound.  source defaults to GI_C_DENOISE_SOURCE_AUTO: the device copies where that render was a whole frame on
-        the primary device.  Returns the filtered image float32 [h, w, 4] (None with ``device_only``); the output buffer is the scene's own, kept per size."""
+        the primary device.  Returns the filtered image float32 [h, w, 4] (None with ``device_only``); the output buffer is the scene's own, kept per size.
+        ``variance=True``: giCDenoiseVariance with the "moments" buffer that render bound (the parameters then take sigmaVariance, varianceFloor, minSamples)."""
         if not getattr(self, "_last_aovs", None):
             raise GiError("denoise_last: no render_aovs call to take the buffers from")
         width, height, bufs = self._last_aovs
-        for name in ("color", "normal", "depth"):
+        for name in ("color", "normal", "depth") + (("moments",) if variance else ()):
             if name not in bufs:
                 raise GiError(f"denoise_last: the last render_aovs did not bind {name!r}")
         L = self.L
@@ -1253,9 +1321,14 @@ class Scene:
             self._buffers[key] = rb
         out_rb = self._buffers[key]
         L.giCSetRenderBufferDeviceOnly(out_rb, int(device_only))
-        p = denoise_params(**params)
+        vp = denoise_variance_params(**params) if variance else None
+        p = vp.base if variance else denoise_params(**params)
         p.color, p.normal, p.depth, p.albedo, p.output = bufs["color"], bufs["normal"], bufs["depth"], bufs.get("albedo"), out_rb
-        if L.giCDenoise(C.byref(p)) != GI_C_OK:
+        if variance:
+            vp.moments = bufs["moments"]
+            if L.giCDenoiseVariance(C.byref(vp)) != GI_C_OK:
+                raise GiError("giCDenoiseVariance failed: " + L.giCGetLastError().decode())
+        elif L.giCDenoise(C.byref(p)) != GI_C_OK:
             raise GiError("giCDenoise failed: " + L.giCGetLastError().decode())
         if device_only:
             return None

@@ -7,6 +7,7 @@
 #include "gi_blas_build.h"
 #include "gi_bvh_stages.h"
 #include "gi_compact.h"
+#include "gi_moments.h"
 #include "bvh8.h"
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1265,3 +1266,59 @@ extern "C" int giCDebugSceneBlasBuildStats(const GiCScene* scene, uint64_t* out)
   out[15] = deviceBuilt;
   return GI_C_OK;
 }
+
+// giCDebugSampleMoments / giCDebugSampleMomentsHost: k_moments (onDevice) or its host form (gi_moments.h) over the caller's per-sample buffer.  The tile is the
+// whole image; the miss constant reaches the kernel the way a render's does, through retired_miss_sample(U): the background IS the constant and nothing clamps
+static int debugSampleMoments(const char* name, bool onDevice, const GiCDebugMomentsDesc* d, const float* samples, const float* prevM, const uint32_t* rect,
+    const float* missRgb, float* outM)
+{
+  auto refuse = [&](const char* what) { setError(std::string(name) + ": " + what); return GI_C_ERROR; };
+  if (onDevice && !g_ctx.initialized) return refuse("called before giCInitialize");
+  if (!d || !samples || !outM) return refuse("a required argument is NULL");
+  if (d->width == 0u || d->rows == 0u || d->bufferSamples == 0u || d->count == 0u) return refuse("an empty tile, buffer or slice");
+  if ((uint64_t)d->first + d->count > d->bufferSamples) return refuse("the slice does not lie inside the buffer");
+  const uint64_t pixels64 = (uint64_t)d->width * d->rows;
+  if (d->width > 65535u || d->rows > 65535u || pixels64 * d->bufferSamples > 0xffffffffull) return refuse("more than 2^32 - 1 records, or a side above 65535");
+  if (rect) {
+    if (!missRgb) return refuse("a miss rectangle without its constant");
+    if (rect[0] > rect[2] || rect[1] > rect[3] || rect[2] > d->width || rect[3] > d->rows) return refuse("the miss rectangle does not lie inside the image");
+    for (int a = 0; a < 3; a++) if (!(missRgb[a] >= 0.0f) || std::signbit(missRgb[a]) || !std::isfinite(missRgb[a])) return refuse("the miss constant must be finite and not negative");
+  }
+  try {
+    const uint32_t pixels = (uint32_t)pixels64;
+    const size_t records = (size_t)pixels * d->bufferSamples;
+    MomentsFold F{};
+    F.pixelCount = pixels; F.imageWidth = d->width; F.rowBegin = 0u; F.rowStride = 1u;
+    F.bufferSamples = d->bufferSamples; F.first = d->first; F.count = d->count; F.pixelMajor = d->pixelMajor ? 1u : 0u; F.continues = prevM ? 1u : 0u;
+    if (rect) { F.missRect = 1u; F.rectX0 = rect[0]; F.rectTy0 = rect[1]; F.rectX1 = rect[2]; F.rectTy1 = rect[3]; for (int a = 0; a < 3; a++) F.missSample[a] = missRgb[a]; }
+    if (!onDevice) {
+      std::vector<F4> buf(records), M(pixels);
+      memcpy(static_cast<void*>(buf.data()), samples, records * sizeof(F4));
+      if (prevM) memcpy(static_cast<void*>(M.data()), prevM, (size_t)pixels * sizeof(F4));
+      else memset(static_cast<void*>(M.data()), 0xa5, (size_t)pixels * sizeof(F4)); // (a fold from zero must not look at it)
+      momentsHost(F, buf.data(), M.data());
+      memcpy(outM, M.data(), (size_t)pixels * sizeof(F4));
+      return GI_C_OK;
+    }
+    FrameUniforms U{};
+    U.pixelCount = pixels; U.imageWidth = d->width; U.imageHeight = d->rows; U.rowBegin = 0u; U.rowStride = 1u;
+    U.maxSampleValue = INFINITY;
+    if (rect) { U.flags |= FLAG_MISS_RECT; U.rectX0 = rect[0]; U.rectTy0 = rect[1]; U.rectX1 = rect[2]; U.rectTy1 = rect[3]; for (int a = 0; a < 3; a++) U.background[a] = missRgb[a]; }
+    DeviceBuffer<F4> dBuf, dM;
+    hipStream_t st = g_ctx.stream;
+    std::vector<uint8_t> fill((size_t)pixels * sizeof(F4), 0xa5);
+    bool ok = hipSetDevice(g_ctx.device) == hipSuccess && dBuf.alloc(records) == GI_C_OK && dM.alloc(pixels) == GI_C_OK;
+    ok = ok && hipMemcpyAsync(dBuf.ptr, samples, records * sizeof(F4), hipMemcpyHostToDevice, st) == hipSuccess &&
+        hipMemcpyAsync(dM.ptr, prevM ? static_cast<const void*>(prevM) : static_cast<const void*>(fill.data()), (size_t)pixels * sizeof(F4), hipMemcpyHostToDevice, st) == hipSuccess;
+    if (ok) { launchMoments(st, U, dBuf.ptr, dM.ptr, d->bufferSamples, d->first, d->count, d->pixelMajor != 0u, prevM != nullptr); ok = hipGetLastError() == hipSuccess; }
+    ok = ok && hipMemcpyAsync(outM, dM.ptr, (size_t)pixels * sizeof(F4), hipMemcpyDeviceToHost, st) == hipSuccess;
+    ok = hipStreamSynchronize(st) == hipSuccess && ok;
+    dBuf.release(); dM.release();
+    if (!ok) return refuse("device error");
+    return GI_C_OK;
+  } catch (const std::exception& e) { setError(std::string(name) + ": " + e.what()); return GI_C_ERROR; }
+}
+extern "C" int giCDebugSampleMoments(const GiCDebugMomentsDesc* desc, const float* samples, const float* prevM, const uint32_t* rect, const float* missRgb, float* outM)
+{ return debugSampleMoments("giCDebugSampleMoments", true, desc, samples, prevM, rect, missRgb, outM); }
+extern "C" int giCDebugSampleMomentsHost(const GiCDebugMomentsDesc* desc, const float* samples, const float* prevM, const uint32_t* rect, const float* missRgb, float* outM)
+{ return debugSampleMoments("giCDebugSampleMomentsHost", false, desc, samples, prevM, rect, missRgb, outM); }

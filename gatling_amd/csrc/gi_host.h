@@ -234,6 +234,10 @@ struct GiCRenderBuffer {
   bool wholeFrame = false;
   bool hostOnly = false; // giCCreateHostRenderBuffer: hostMem is plain host memory, there is no deviceMem
   int32_t format = GI_C_FORMAT_FLOAT32_VEC4; // GiCRenderBufferFormat it was created with (stride alone does not tell Int32 from Float32)
+  // GI_C_AOV_EXT_MOMENTS: the accumulation whose moments the buffer holds -- its epoch (GiCScene::accumEpoch: a process-wide number drawn anew whenever a
+  // scene's sample offset restarts at 0, never 0 itself) and the sample offset the last successful giCRender that bound the buffer left that scene at.  A
+  // progressive call of the SAME accumulation at exactly that offset continues the moments; any other starts them from zero (gi_moments.h)
+  uint64_t momentsEpoch = 0, momentsNext = 0;
 };
 // gi_denoise_host.cpp: the library's denoiser scratch on the primary device (giCTerminate frees it)
 void releaseDenoiseScratch();
@@ -395,6 +399,7 @@ struct GiCScene : SceneDevice {
   // sphere / distant / rect / disk lights the device arrays hold (uploadLights: the stores' records minus the unusable ones)
   uint32_t lightCounts[4] = {0, 0, 0, 0};
   uint32_t sampleOffset = 0;
+  uint64_t accumEpoch = 0; // which accumulation sampleOffset counts: nextAccumEpoch() wherever sampleOffset restarts at 0 (giCRender); 0 = none yet
   bool haveOldParams = false;
   GiCCameraDesc oldCamera{};
   GiCRenderSettings oldSettings{};

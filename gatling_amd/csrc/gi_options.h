@@ -113,7 +113,8 @@
 //                                  compacts whenever anything is retired (tests)
 //   denoise_form         0         giCDenoise: where k_denoise_pass takes its taps from (gi_denoise.hip; every form stores the same bytes): 0 = an LDS tile with
 //                                  a 2 x step halo at steps 1 and 2, direct 16-byte loads above (the measured choice); 1 = direct loads at
-//                                  every step; 2 = the tile at steps 1, 2 and 4
+//                                  every step; 2 = the tile at steps 1, 2 and 4.  giCDenoiseVariance reads it the same way (gi_denoise_var.hip) and knows
+//                                  3 = form 0 with the 3 x 3 variance average of the direct-load steps written by a launch of its own (giCDenoise: as 0)
 //   phase_stats          0         counting builds: print k_path's phase split / k_trace_dyn's lane accounting
 #pragma once
 

@@ -5,6 +5,7 @@
 // (one of the translation units gi_c.cpp was split into in round 6; shared declarations: gi_host.h)
 #include "gi_host.h"
 #include "gi_miss_rect.h"
+#include "gi_moments.h"
 
 bool settingsEqual(const GiCRenderSettings& a, const GiCRenderSettings& b) { return memcmp(&a, &b, sizeof(a)) == 0; }
 
@@ -103,7 +104,8 @@ extern "C" int giCRender(const GiCRenderParams* params)
 // One device's part of a render: the rows rowBegin, rowBegin + rowStride, ... < rowEnd of the frame, on device D.slot with D's copy of the scene.  Called
 // under the scene mutex, after the dirty handling; with several devices, once per device from its own host thread (the bounce loop polls the queue sizes).
 struct RenderJob { const GiCRenderParams* params; const GiCAovBinding* colorBinding; uint32_t width, height, rowBegin, rowEnd, rowStride, tileRows;
-    uint8_t clear[GI_C_MAX_AOV_COMP_SIZE]; bool readback; };
+    uint8_t clear[GI_C_MAX_AOV_COMP_SIZE]; bool readback;
+    bool momentsContinue = false; }; // GI_C_AOV_EXT_MOMENTS: the bound buffer holds the moments of the call before this one (giCRenderImpl)
 
 static void* rbMem(GiCRenderBuffer* rb, uint32_t slot) { return (slot == 0u || rb->scratch) ? rb->deviceMem : rb->replicaMem[slot - 1u]; }
 
@@ -116,6 +118,7 @@ struct BoundAovs {
   AovTargets targets{};                          // what k_aov writes ...
   std::vector<GiCRenderBuffer*> produced;        // ... and the buffers behind it
   GiCRenderBuffer* nee = nullptr; GiCRenderBuffer* bounces = nullptr; GiCRenderBuffer* clock = nullptr; // the path-following AOVs
+  GiCRenderBuffer* moments = nullptr;            // GI_C_AOV_EXT_MOMENTS: filled beside every batch's accumulation (gi_moments.hip)
   GiCRenderBuffer* color = nullptr;              // the colour AOV's buffer, or `scratchColor` when only path-following AOVs need the colour pass
   GiCRenderBuffer scratchColor{};
 };
@@ -128,6 +131,12 @@ static int bindAovs(SceneDevice& D, const RenderJob& job, hipStream_t st, BoundA
     if (b.aovId == GI_C_AOV_COLOR) continue;
     GiCRenderBuffer* rb = b.renderBuffer;
     if (rb->width != job.width || rb->height != job.height) { setError("giCRender: AOV buffers must share one size"); return GI_C_ERROR; }
+    if (b.aovId == GI_C_AOV_EXT_MOMENTS) { // outside the enum: neither k_aov's nor a path-following AOV; no clear value
+      if (rb->stride != 16 || rb->format != GI_C_FORMAT_FLOAT32_VEC4) { setError("giCRender: the moments AOV needs a Float32Vec4 buffer"); return GI_C_ERROR; }
+      if (A.moments) { setError("giCRender: the moments AOV is bound twice"); return GI_C_ERROR; }
+      A.moments = rb;
+      continue;
+    }
     if (b.aovId < 0 || b.aovId >= GI_C_AOV_COUNT) { setError("giCRender: bad AOV id"); return GI_C_ERROR; }
     AovTargets& T = A.targets;
     memcpy(T.clear[b.aovId], b.clearValue, 16);
@@ -158,7 +167,7 @@ static int bindAovs(SceneDevice& D, const RenderJob& job, hipStream_t st, BoundA
     }
   }
   A.color = job.colorBinding ? job.colorBinding->renderBuffer : nullptr;
-  if (!A.color && (A.nee || A.bounces || A.clock)) { // the path-following debug AOVs need the colour pass: render it into a scratch buffer
+  if (!A.color && (A.nee || A.bounces || A.clock || A.moments)) { // the path-following debug AOVs need the colour pass: render it into a scratch buffer
     const size_t n = (size_t)job.width * job.height;
     if (D.scratchColor.alloc(n)) return GI_C_ERROR;
     GiCRenderBuffer& c = A.scratchColor;
@@ -446,6 +455,7 @@ struct Frame {
   FrameUniforms U{}; SceneView view{};
   PathPlan plan; PathState ps{}; QueueSet qs{}; Schedule sch;
   F4* colorOut = nullptr;
+  GiCRenderBuffer* moments = nullptr; // GI_C_AOV_EXT_MOMENTS bound: k_moments runs beside every fold of this render
   bool stackHighCounted = false; // this render zeroed Counters::stackHigh and ran walks that raise it (traceColour)
   uint32_t numBatches = 0;
   uint32_t iters = 0, traceLaunches = 0; // GiCRenderStats::iterations / traceLaunches
@@ -579,6 +589,9 @@ static bool scheduleBatch(Frame& f, uint64_t rounds)
 // --- the three kinds of batch.  renderOnDevice has set the batch's uniforms and launched k_init; each ends in the batch's accumulation.
 static void accumulateBatch(Frame& f, uint32_t batch)
 {
+  // the moments AOV: the same records, before the next batch overwrites them (a window: this call's share, its first spp; later batches continue the first's)
+  if (f.moments) launchMoments(f.st, f.U, f.D.sampleBuf.ptr, reinterpret_cast<F4*>(rbMem(f.moments, f.D.slot)), f.U.batchSamples, 0u,
+                               f.windowCalls >= 2u ? f.U.spp : f.U.batchSamples, (f.U.flags & FLAG_PIXEL_MAJOR) != 0u, batch > 0u || f.job.momentsContinue);
   if (f.windowCalls >= 2u) { // a look-ahead window (one batch): this call's samples are its first spp
     launchFoldWindow(f.st, f.U, f.D.sampleBuf.ptr, f.colorOut, f.U.batchSamples, 0u, (f.U.flags & FLAG_PIXEL_MAJOR) != 0u);
     return;
@@ -777,6 +790,7 @@ static int readBackAndWait(Frame& f, GiCRenderBuffer* colorRb)
   SceneDevice& D = f.D;
   HIP_TRY(hipMemcpyAsync(D.hCounters, D.dCounters.ptr, sizeof(Counters), hipMemcpyDeviceToHost, f.st));
   if (colorRb && !colorRb->deviceOnly && f.job.readback) HIP_TRY(copyTileRows(colorRb, 16, f.job, D.slot, f.st));
+  if (f.moments && !f.moments->deviceOnly && f.job.readback) HIP_TRY(copyTileRows(f.moments, 16, f.job, D.slot, f.st));
   HIP_TRY(hipStreamSynchronize(f.st));
   HIP_TRY(hipGetLastError());
   return GI_C_OK;
@@ -932,6 +946,11 @@ static int serveFromWindow(Frame& f, const BoundAovs& A)
   f.colorOut = reinterpret_cast<F4*>(rbMem(A.color, D.slot));
   launchFoldWindow(f.st, f.U, D.sampleBuf.ptr, f.colorOut, (uint32_t)windowSamples, (uint32_t)first, L.pixelMajor != 0u);
   if (hipGetLastError() != hipSuccess) { setError("k_fold_window launch failed"); return GI_C_ERROR; }
+  if (f.moments) { // the moments ride along with the window: the same slice
+    launchMoments(f.st, f.U, D.sampleBuf.ptr, reinterpret_cast<F4*>(rbMem(f.moments, D.slot)), (uint32_t)windowSamples, (uint32_t)first, f.rs.spp,
+                  L.pixelMajor != 0u, f.job.momentsContinue);
+    if (hipGetLastError() != hipSuccess) { setError("k_moments launch failed"); return GI_C_ERROR; }
+  }
   L.served++; L.callsServed++; L.traced = 0u;
   return GI_C_OK;
 }
@@ -1010,6 +1029,7 @@ static int renderOnDevice(GiCScene* s, SceneDevice& D, const RenderJob& job)
   Frame f{s, D, ctx, job, rs, st, pixels, StageTimers(s, D)};
   f.U = makeUniforms(*job.params, job, s);
   f.tStart = nowMs();
+  f.moments = aov.color ? aov.moments : nullptr;
   f.view = makeFrameView(s, D, *job.params, f.U);
   if (ensurePathState(&D, 1, 1, 1) != GI_C_OK) return GI_C_ERROR; // counters / pinned mirror exist even for AOV-only renders
   LookaheadPlan la;
@@ -1198,16 +1218,24 @@ static int giCRenderImpl(const GiCRenderParams* params)
   if (s->lastRenderDevices != nDev) s->dirty |= DIRTY_FRAMEBUFFER;
   s->lastRenderDevices = nDev;
   if (s->dirty & DIRTY_FRAMEBUFFER) { s->sampleOffset = 0; s->dirty &= ~DIRTY_FRAMEBUFFER; }
+  // a new accumulation: its own number, process-wide (a scene allocated where a destroyed one lay never repeats one), so that what a buffer holds of an
+  // earlier accumulation -- the moments AOV -- is never continued by this one, whatever the sample offsets happen to be
+  if (s->sampleOffset == 0u) { static std::atomic<uint64_t> nextAccumEpoch{1}; s->accumEpoch = nextAccumEpoch.fetch_add(1); }
 
 
   RenderJob job{params, colorBinding, width, height, rowBegin, rowEnd, rowStride, tileRows, {0}, true};
   memcpy(job.clear, clear, sizeof(job.clear));
+  // the moments AOV continues what its buffer holds only if that is the moments of THIS accumulation's samples [0, sampleOffset) (gi_moments.h)
+  GiCRenderBuffer* momentsRb = nullptr;
+  for (uint32_t i = 0; i < params->aovBindingCount; i++) if (params->aovBindings[i].aovId == GI_C_AOV_EXT_MOMENTS) momentsRb = params->aovBindings[i].renderBuffer;
+  job.momentsContinue = momentsRb && rs.progressiveAccumulation && s->sampleOffset > 0 && momentsRb->momentsEpoch == s->accumEpoch &&
+      momentsRb->momentsNext == (uint64_t)s->sampleOffset;
   // AOVs the colour pass fills along whole paths (NEE, Bounces, ClockCycles) and unknown ids start from their clear value: host copy filled once, here
   for (uint32_t i = 0; i < params->aovBindingCount; i++) {
     const GiCAovBinding& b = params->aovBindings[i];
     GiCRenderBuffer* rb = b.renderBuffer;
     const bool pathAov = b.aovId == GI_C_AOV_NEE || b.aovId == GI_C_AOV_BOUNCES || b.aovId == GI_C_AOV_CLOCK_CYCLES || b.aovId < 0 || b.aovId >= GI_C_AOV_COUNT;
-    if (b.aovId == GI_C_AOV_COLOR || !pathAov) continue;
+    if (b.aovId == GI_C_AOV_COLOR || !pathAov || b.aovId == GI_C_AOV_EXT_MOMENTS) continue; // (the moments have no clear value: rows outside the share stay)
     const size_t n = (size_t)rb->width * rb->height;
     for (size_t k = 0; k < n; k++) memcpy((uint8_t*)rb->hostMem + k * rb->stride, b.clearValue, rb->stride);
   }
@@ -1221,10 +1249,12 @@ static int giCRenderImpl(const GiCRenderParams* params)
   // the AOVs the AOV kernels make, after a render of every row on the primary device alone
   for (uint32_t i = 0; i < params->aovBindingCount; i++) {
     const GiCAovBinding& b = params->aovBindings[i];
-    const bool pathAov = b.aovId == GI_C_AOV_NEE || b.aovId == GI_C_AOV_BOUNCES || b.aovId == GI_C_AOV_CLOCK_CYCLES || b.aovId < 0 || b.aovId >= GI_C_AOV_COUNT;
+    const bool pathAov = b.aovId != GI_C_AOV_EXT_MOMENTS &&
+        (b.aovId == GI_C_AOV_NEE || b.aovId == GI_C_AOV_BOUNCES || b.aovId == GI_C_AOV_CLOCK_CYCLES || b.aovId < 0 || b.aovId >= GI_C_AOV_COUNT);
     b.renderBuffer->wholeFrame = rc == GI_C_OK && nDev == 1u && rowStride == 1u && rowBegin == 0u && rowEnd == height && !pathAov &&
         b.renderBuffer->width == width && b.renderBuffer->height == height;
   }
+  if (momentsRb) { momentsRb->momentsEpoch = rc == GI_C_OK ? s->accumEpoch : 0u; momentsRb->momentsNext = (uint64_t)s->sampleOffset + rs.spp; }
   if (rc != GI_C_OK) return rc;
   s->sampleOffset += rs.spp; // Gi.cpp:2515
   return GI_C_OK;

@@ -747,8 +747,8 @@ namespace gtl
   void giDestroyRenderBuffer(GiRenderBuffer* b) { if (!b) return; giCDestroyRenderBuffer(b->h); delete b; }
   void* giGetRenderBufferMem(GiRenderBuffer* b) { return b ? giCGetRenderBufferMem(b->h) : nullptr; }
 
-  // [ext] -> giCDenoise over the wrapped handles
-  GiStatus gtlDenoise(const GtlDenoiseParams& p)
+  // [ext] -> giCDenoise / giCDenoiseVariance over the wrapped handles
+  static GiCDenoiseParams denoiseParams(const GtlDenoiseParams& p)
   {
     GiCDenoiseParams c;
     giCDenoiseDefaults(&c);
@@ -756,8 +756,23 @@ namespace gtl
     c.depth = p.depth ? p.depth->h : nullptr; c.output = p.output ? p.output->h : nullptr;
     c.iterations = p.iterations; c.normalSquarings = p.normalSquarings; c.sigmaColor = p.sigmaColor; c.sigmaDepth = p.sigmaDepth;
     c.backgroundDepth = p.backgroundDepth; c.albedoFloor = p.albedoFloor; c.source = p.source;
+    return c;
+  }
+  GiStatus gtlDenoise(const GtlDenoiseParams& p)
+  {
+    const GiCDenoiseParams c = denoiseParams(p);
     if (giCDenoise(&c) == GI_C_OK) return GiStatus::Ok;
     fprintf(stderr, "[gatling_gi] gtlDenoise: %s\n", giCGetLastError());
+    return GiStatus::Error;
+  }
+  GiStatus gtlDenoiseVariance(const GtlDenoiseVarianceParams& p)
+  {
+    GiCDenoiseVarianceParams c;
+    giCDenoiseVarianceDefaults(&c);
+    c.base = denoiseParams(p.base);
+    c.moments = p.moments ? p.moments->h : nullptr; c.sigmaVariance = p.sigmaVariance; c.varianceFloor = p.varianceFloor; c.minSamples = p.minSamples;
+    if (giCDenoiseVariance(&c) == GI_C_OK) return GiStatus::Ok;
+    fprintf(stderr, "[gatling_gi] gtlDenoiseVariance: %s\n", giCGetLastError());
     return GiStatus::Error;
   }
 }

@@ -44,6 +44,20 @@ typedef enum GiCAovId {
   GI_C_AOV_COUNT
 } GiCAovId;
 
+/* [ext] Sample moments: an id a GiCAovBinding takes beside the GiCAovId values.  It lies OUTSIDE the enum: GI_C_AOV_COUNT stays 17 and the enum keeps mirroring
+ * Gi.h.  The buffer is Float32Vec4 and holds, per pixel, M = (S1, S2, n, 0) over the samples the colour AOV's running accumulation holds:
+ *   L = (0.2126 r + 0.7152 g) + 0.0722 b of a path sample as the colour pass retires it (after the clamp to maxSampleValue), no fused multiply-add;
+ *   S1 = sum of L, S2 = sum of (L L), n = sum of 1.0f, the samples added one by one in sample order, from zero (gi_moments.h).
+ * M depends on the samples alone: N progressive calls of spp 1, one call of spp N, a call cut into batches (GI_C_SCENE_OPTION_SAMPLE_BUFFER_MB), look-ahead
+ * windows (the moments ride along: the binding does not switch look-ahead off) and a row share give the same bytes for the rows they render; rows outside a
+ * call's share are not written.  The binding's clear value is not used.  Whatever resets the colour's accumulation (a camera or settings change, an edit,
+ * progressiveAccumulation off) restarts M at that call.  A buffer first bound at a sample offset > 0 -- or bound again after a call that did not bind it --
+ * starts from zero at that call: its n then counts fewer samples than the colour holds.  A binding without a colour binding renders the colour pass into
+ * scratch memory, as the path-following AOVs do.  Multi-device renders: every device accumulates its rows in its own copy and the shares are gathered into
+ * the primary's buffer exactly as the colour AOV's are.  Without the binding giCRender launches what it launched before: the kernel (gi_moments.hip
+ * k_moments, one thread per pixel, beside each batch's accumulation) runs for renders that bind it alone. */
+#define GI_C_AOV_EXT_MOMENTS 0x100
+
 /* Gi.h:70-75 */
 typedef enum GiCRenderBufferFormat { GI_C_FORMAT_INT32 = 0, GI_C_FORMAT_FLOAT32 = 1, GI_C_FORMAT_FLOAT32_VEC4 = 2 } GiCRenderBufferFormat;
 
@@ -389,7 +403,8 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * and for GI_C_SCENE_OPTION_TLAS_DEVICE_BUILD, giCDebugBuildTlasHost, giCDebugBuildTlas and giCDebugSceneTlasBuildStats, and for giCDebugSceneUpsPlain and
  * giCDebugUpsTraits, and for GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD, giCDebugBuildBlasHost, giCDebugBuildBlas and giCDebugSceneBlasBuildStats, and for
  * GI_C_SCENE_OPTION_TLAS_COMPACTION, giCDebugSceneCompactionCount, giCDebugCompactRanges and giCDebugCompactRangesHost, and for giCCreateHostRenderBuffer,
- * giCDenoiseDefaults, giCDenoise and giCGetDenoiseStats, and for GI_C_SCENE_OPTION_LEAF_LIFT, giCDebugSceneLeafLift and giCDebugLeafLift. */
+ * giCDenoiseDefaults, giCDenoise and giCGetDenoiseStats, and for GI_C_SCENE_OPTION_LEAF_LIFT, giCDebugSceneLeafLift and giCDebugLeafLift, and for
+ * GI_C_AOV_EXT_MOMENTS, giCDebugSampleMoments, giCDebugSampleMomentsHost, giCDenoiseVarianceDefaults and giCDenoiseVariance. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -544,7 +559,7 @@ typedef struct GiCDenoiseParams {
 /* of the last giCDenoise that ran in this process (a refused call leaves them alone) */
 typedef struct GiCDenoiseStats {
   int32_t source;          /* what the call did: AUTO = every input read from its device copy, HOST = at least one input sent, HOST_FORM */
-  uint32_t deviceInputs;   /* bit mask of the inputs read from their device copy: 1 colour, 2 normal, 4 depth, 8 albedo ...              */
+  uint32_t deviceInputs;   /* bit mask of the inputs read from their device copy: 1 colour, 2 normal, 4 depth, 8 albedo, 16 moments ...  */
   uint32_t sentInputs;     /* ... and of those sent from host memory                                                                     */
   uint32_t iterations;
   uint32_t width, height;
@@ -558,6 +573,26 @@ typedef struct GiCDenoiseStats {
 void giCDenoiseDefaults(GiCDenoiseParams* params); /* iterations 5, normalSquarings 4, sigmaColor 2, sigmaDepth 0.02, backgroundDepth 1, albedoFloor 1e-3, AUTO; buffers NULL */
 int giCDenoise(const GiCDenoiseParams* params);
 int giCGetDenoiseStats(GiCDenoiseStats* out);
+
+/* [ext] The variance-guided denoiser: giCDenoise with the colour weight's fixed sigma replaced, per pixel, by the variance of the pixel's mean, taken from a
+ * sample-moments buffer (GI_C_AOV_EXT_MOMENTS) rendered beside the colour -- loose where a pixel is noisy, tight where it has converged, whatever the sample
+ * count.  Specified in DESIGN.md section 6 "Denoiser" and gi_denoise.h: per pixel with n = M.z >= minSamples and finite sums, v = max(S2 / n - (S1 / n)^2, 0) /
+ * (n - 1) / lum(max(albedo, albedoFloor))^2; per pass a guided pixel whose v is known weighs a tap's colour by 1 / (1 + dl^2 / (sigmaVariance^2 (vt +
+ * varianceFloor))), dl the difference of the two luminances and vt the 3 x 3 {1/4, 1/2, 1/4}^2 average of v around the pixel, and v travels with the colour
+ * (v' = sum w^2 v / (sum w)^2).  A pixel with fewer than minSamples samples, sums that are not finite or a v above 1e30 uses giCDenoise's weight with
+ * base.sigmaColor.  Everything else -- the guides, the unguided pixels, the three sources, the scratch (two 8-byte planes more, allocated by the first call of
+ * this entry), "inputs are never written", the refusals, giCGetDenoiseStats (prepareMs covers both prepare kernels; deviceInputs / sentInputs bit 16: the
+ * moments) -- is giCDenoise's, and the same operator set in one association: the device kernels (gi_denoise_var.hip), the host form and
+ * tests/denoise_var_ref.py agree bit for bit.  Refused in addition: a NULL moments buffer (giCDenoise is the fixed filter), one of another format or size or
+ * that is the output, minSamples below 2, a sigmaVariance or varianceFloor that is not finite and positive. */
+typedef struct GiCDenoiseVarianceParams {
+  GiCDenoiseParams base;
+  GiCRenderBuffer* moments;
+  float sigmaVariance, varianceFloor;
+  uint32_t minSamples;
+} GiCDenoiseVarianceParams;
+void giCDenoiseVarianceDefaults(GiCDenoiseVarianceParams* params); /* base: giCDenoiseDefaults; sigmaVariance 4, varianceFloor 1e-6, minSamples 2; moments NULL */
+int giCDenoiseVariance(const GiCDenoiseVarianceParams* params);
 
 /* [ext] statistics of the last giCRender on this scene; countTraversal != 0 in giCSetSceneOption enables
  * node/triangle counters (slower; measurement runs only). */
@@ -1097,6 +1132,20 @@ int giCDebugPathLot(uint32_t bvhDepth, uint32_t nodeCount, uint32_t triCount, ui
  * device work, no scene. */
 int giCDebugMissRect(const float* bounds /* 6 */, const GiCCameraDesc* camera, const GiCRenderSettings* settings, uint32_t width, uint32_t height,
                      uint32_t* out /* 4 */);
+/* [ext] [debug] the kernel of the sample-moments AOV (GI_C_AOV_EXT_MOMENTS; gi_moments.hip k_moments) over a synthetic per-sample buffer: a tile of
+ * width x rows pixels (the whole image), `bufferSamples` Float32Vec4 records per pixel in `samples` -- [pixel][bufferSamples] with pixelMajor != 0, else
+ * [bufferSamples][pixel] -- of which the samples [first, first + count) of every pixel are folded (first + count <= bufferSamples; a look-ahead window's slice
+ * has first > 0).  prevM != NULL: width x rows records the fold continues from; NULL: from zero.  rect != NULL: x0, y0, x1, y1 -- a pixel outside columns
+ * [x0, x1) and rows [y0, y1) has no records: each of its `count` samples is the constant missRgb (three finite values >= 0).  outM: width x rows records
+ * (S1, S2, n, 0).  GI_C_OK, or GI_C_ERROR with a message (no device, a NULL or empty argument, a slice outside the buffer, more than 2^32 - 1 records, a
+ * rectangle outside the image).  giCDebugSampleMomentsHost: the host form of the same per-pixel code (gi_moments.h); no device, works without giCInitialize. */
+typedef struct GiCDebugMomentsDesc {
+  uint32_t width, rows, bufferSamples, first, count, pixelMajor;
+} GiCDebugMomentsDesc;
+int giCDebugSampleMoments(const GiCDebugMomentsDesc* desc, const float* samples, const float* prevM, const uint32_t* rect /* 4 */, const float* missRgb /* 3 */,
+                          float* outM);
+int giCDebugSampleMomentsHost(const GiCDebugMomentsDesc* desc, const float* samples, const float* prevM, const uint32_t* rect /* 4 */,
+                              const float* missRgb /* 3 */, float* outM);
 
 #ifdef __cplusplus
 }

@@ -158,4 +158,17 @@ namespace gtl
     int32_t source = 0;
   };
   GiStatus gtlDenoise(const GtlDenoiseParams&);
+
+  // ---- [ext] the variance-guided denoiser (-> giCDenoiseVariance, include/gi_c.h): gtlDenoise with the colour weight taken, per pixel, from the variance of
+  // the pixel's mean.  `moments` is a Float32Vec4 buffer bound in the same giRender calls as the colour with the AOV id kGtlAovMoments (it lies outside the
+  // GiAovId enum, which keeps mirroring the reference's: cast it); it holds (sum L, sum L L, sample count, 0) of the accumulation's samples.
+  constexpr int kGtlAovMoments = 0x100; // == GI_C_AOV_EXT_MOMENTS
+  struct GtlDenoiseVarianceParams
+  {
+    GtlDenoiseParams base;
+    GiRenderBuffer* moments = nullptr;
+    float sigmaVariance = 4.0f, varianceFloor = 1.0e-6f;
+    uint32_t minSamples = 2;
+  };
+  GiStatus gtlDenoiseVariance(const GtlDenoiseVarianceParams&);
 }

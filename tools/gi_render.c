@@ -12,6 +12,9 @@
  *                    [--denoise-albedo-floor F] [--denoise-no-albedo 1]]
  *                   --denoise binds the normal, depth (clear value 1.0) and albedo AOVs (clear 0) beside the colour, runs giCDenoise (the library's own
  *                   a-trous filter: include/gi_c.h) on the device copies and writes the filtered image beside the unfiltered one (whole frames only)
+ *                   [--denoise-variance out.pfm [--denoise-sigma-variance S] [--denoise-variance-floor F] [--denoise-min-samples N]]
+ *                   --denoise-variance binds the same guides and the sample-moments buffer (GI_C_AOV_EXT_MOMENTS) itself and runs giCDenoiseVariance, the
+ *                   variance-guided form of the filter; it takes the --denoise-* parameters too, and both outputs may be asked for in one run
  *   tools/gi_render scene.gscn --info        parses the file and prints its inventory; needs no GPU
  *
  * Output by extension: .pfm (RGB float, bottom row first -- the buffer's own order), .raw (RGBA float32, bottom row first),
@@ -110,8 +113,11 @@ int main(int argc, char** argv)
   uint32_t rowBegin = 0, rowEnd = 0, rowStride = 1;
   int device = 0, stats = 0, denoiseNoAlbedo = 0;
   const char* denoisePath = NULL;
+  const char* denoiseVarPath = NULL;
   GiCDenoiseParams dn;
   giCDenoiseDefaults(&dn);
+  GiCDenoiseVarianceParams dv;
+  giCDenoiseVarianceDefaults(&dv);
   for (int i = 3; i < argc; i++) {
     const char* a = argv[i];
     const char* v = i + 1 < argc ? argv[i + 1] : NULL;
@@ -136,6 +142,10 @@ int main(int argc, char** argv)
     else if (!strcmp(a, "--denoise-sigma-depth")) dn.sigmaDepth = (float)atof(v);
     else if (!strcmp(a, "--denoise-albedo-floor")) dn.albedoFloor = (float)atof(v);
     else if (!strcmp(a, "--denoise-no-albedo")) denoiseNoAlbedo = atoi(v);
+    else if (!strcmp(a, "--denoise-variance")) denoiseVarPath = v;
+    else if (!strcmp(a, "--denoise-sigma-variance")) dv.sigmaVariance = (float)atof(v);
+    else if (!strcmp(a, "--denoise-variance-floor")) dv.varianceFloor = (float)atof(v);
+    else if (!strcmp(a, "--denoise-min-samples")) dv.minSamples = (uint32_t)atoi(v);
     else if (!strcmp(a, "--rows")) { if (sscanf(v, "%u:%u:%u", &rowBegin, &rowEnd, &rowStride) < 2) return fail("--rows wants begin:end[:stride]"); }
     else { fprintf(stderr, "gi_render: unknown option %s\n", a); return 2; }
   }
@@ -316,18 +326,20 @@ int main(int argc, char** argv)
   /* one giCRender call; the colour AOV arrives in the render buffer's host memory (Gi.cpp:2492-2502) */
   GiCRenderBuffer* rb = giCCreateRenderBuffer(fs.width, fs.height, GI_C_FORMAT_FLOAT32_VEC4);
   if (!rb) { fprintf(stderr, "gi_render: giCCreateRenderBuffer: %s\n", giCGetLastError()); return 1; }
-  GiCAovBinding bindings[4];
+  GiCAovBinding bindings[5];
   memset(bindings, 0, sizeof bindings);
   bindings[0].aovId = GI_C_AOV_COLOR;
   memcpy(bindings[0].clearValue, fs.clear, 16);
   bindings[0].renderBuffer = rb;
   uint32_t nBindings = 1;
   GiCRenderBuffer* guides[4] = {NULL, NULL, NULL, NULL}; /* normal, depth, albedo, the filtered image */
-  if (denoisePath) { /* the guides of giCDenoise: depth cleared to backgroundDepth (1.0), normal and albedo to 0 */
+  GiCRenderBuffer* momentsRb = NULL; GiCRenderBuffer* varOut = NULL; /* --denoise-variance: the sample moments, the filtered image */
+  if (denoisePath || denoiseVarPath) { /* the guides of giCDenoise: depth cleared to backgroundDepth (1.0), normal and albedo to 0 */
     static const int32_t ids[3] = {GI_C_AOV_NORMAL, GI_C_AOV_DEPTH, GI_C_AOV_ALBEDO};
     const float one = dn.backgroundDepth;
     for (int g = 0; g < 4; g++) {
       if (g == 2 && denoiseNoAlbedo) continue;
+      if (g == 3 && !denoisePath) break; /* (--denoise-variance alone: its output is a buffer of its own) */
       guides[g] = giCCreateRenderBuffer(fs.width, fs.height, g == 1 ? GI_C_FORMAT_FLOAT32 : GI_C_FORMAT_FLOAT32_VEC4);
       if (!guides[g]) { fprintf(stderr, "gi_render: giCCreateRenderBuffer: %s\n", giCGetLastError()); return 1; }
       if (g == 3) break;
@@ -336,6 +348,14 @@ int main(int argc, char** argv)
       bindings[nBindings].renderBuffer = guides[g];
       nBindings++;
     }
+  }
+  if (denoiseVarPath) {
+    momentsRb = giCCreateRenderBuffer(fs.width, fs.height, GI_C_FORMAT_FLOAT32_VEC4);
+    varOut = giCCreateRenderBuffer(fs.width, fs.height, GI_C_FORMAT_FLOAT32_VEC4);
+    if (!momentsRb || !varOut) { fprintf(stderr, "gi_render: giCCreateRenderBuffer: %s\n", giCGetLastError()); return 1; }
+    bindings[nBindings].aovId = GI_C_AOV_EXT_MOMENTS;
+    bindings[nBindings].renderBuffer = momentsRb;
+    nBindings++;
   }
   GiCRenderParams p;
   memset(&p, 0, sizeof p);
@@ -364,9 +384,26 @@ int main(int argc, char** argv)
     }
     if (!rc) rc = write_image(denoisePath, (const float*)giCGetRenderBufferMem(guides[3]), fs.width, fs.height);
   }
+  if (denoiseVarPath) {
+    dv.base = dn;
+    dv.base.color = rb; dv.base.normal = guides[0]; dv.base.depth = guides[1]; dv.base.albedo = guides[2]; dv.base.output = varOut; dv.moments = momentsRb;
+    if (giCDenoiseVariance(&dv) != GI_C_OK) { fprintf(stderr, "gi_render: giCDenoiseVariance: %s\n", giCGetLastError()); return 1; }
+    if (stats) {
+      GiCDenoiseStats ds;
+      if (giCGetDenoiseStats(&ds) == GI_C_OK) {
+        double passes = 0.0;
+        for (uint32_t i = 0; i < ds.iterations; i++) passes += ds.passMs[i];
+        printf("denoise-variance %.3f ms (inputs from device copies: mask %u, sent: mask %u, %llu bytes; prepare %.3f ms, %u passes %.3f ms, copy %.3f ms)\n",
+               ds.totalMs, ds.deviceInputs, ds.sentInputs, (unsigned long long)ds.bytesSent, ds.prepareMs, ds.iterations, passes, ds.copyMs);
+      }
+    }
+    if (!rc) rc = write_image(denoiseVarPath, (const float*)giCGetRenderBufferMem(varOut), fs.width, fs.height);
+  }
 
   giCDestroyRenderBuffer(rb);
   for (int g = 0; g < 4; g++) if (guides[g]) giCDestroyRenderBuffer(guides[g]);
+  if (momentsRb) giCDestroyRenderBuffer(momentsRb);
+  if (varOut) giCDestroyRenderBuffer(varOut);
   for (uint32_t m = 0; m < nMesh; m++) giCDestroyMesh(meshes[m]);
   for (uint32_t m = 0; m < nMat; m++) giCDestroyMaterial(materials[m]);
   if (dome) giCDestroyDomeLight(dome);
