@@ -14,7 +14,7 @@ LIB = os.path.join(_HERE, "libgatling_gi.so")
 # the host side of the C ABI (gi_c.cpp until round 6): built with -fvisibility=hidden, the API keeps default visibility through gi_host.h
 HOST_SOURCES = ["gi_c.cpp", "gi_scene.cpp", "gi_textures.cpp", "gi_lights.cpp", "gi_build.cpp", "gi_render.cpp", "gi_debug.cpp", "gi_denoise_host.cpp"]
 SOURCES = HOST_SOURCES + ["gi_image.cpp", "bvh8.cpp", "leaf_lift.cpp", "gi_kernels.hip", "gi_trace.hip", "gi_shade.hip", "gi_aov.hip", "gi_aov2.hip", "gi_path.hip", "gi_bvh_build.hip", "gi_patch.hip", "gi_refit.hip", "gi_tlas.hip", "gi_blas.hip", "gi_append.hip", "gi_instances.hip", "gi_compact.hip", "gi_tlas_build.hip", "gi_tlas_build_host.cpp", "gi_blas_build.hip", "gi_blas_build_host.cpp", "gi_denoise.hip", "gi_moments.hip", "gi_denoise_var.hip", "gtl_shim.cpp"]
-HEADERS = ["gi_host.h", "gi_types.h", "gi_kernels.h", "gi_device_math.h", "gi_queues.h", "gi_traversal.h", "gi_texture.h", "gi_shading.h", "gi_stages.h", "gi_image.h", "gi_options.h", "gi_miss_rect.h", "bvh8.h", "gi_bvh_build.h", "gi_refit.h", "gi_tlas.h", "gi_blas.h", "gi_pack.h", "gi_vispatch.h", "gi_aov_body.h", "gi_append.h", "gi_instances.h", "gi_compact.h", "gi_bvh_stages.h", "gi_tlas_build.h", "gi_blas_build.h", "gi_denoise.h", "gi_moments.h",
+HEADERS = ["gi_host.h", "gi_types.h", "gi_kernels.h", "gi_device_math.h", "gi_queues.h", "gi_traversal.h", "gi_texture.h", "gi_shading.h", "gi_stages.h", "gi_image.h", "gi_options.h", "gi_miss_rect.h", "bvh8.h", "gi_bvh_build.h", "gi_refit.h", "gi_tlas.h", "gi_blas.h", "gi_pack.h", "gi_vispatch.h", "gi_aov_body.h", "gi_append.h", "gi_instances.h", "gi_compact.h", "gi_bvh_stages.h", "gi_tlas_build.h", "gi_blas_build.h", "gi_denoise.h", "gi_moments.h", "gi_node_cook.h",
            os.path.join("..", "..", "include", "gi_c.h"), os.path.join("..", "..", "include", "gtl", "gi", "Gi.h"),
            os.path.join("..", "..", "include", "gtl", "gb", "ParamTypes.h")]
 # -ffp-contract=off: arithmetic contract.  No fast-math: IEEE divide/sqrt are part of it.

@@ -202,6 +202,9 @@ SYMBOLS = [
     ("giCDebugSceneVisibilityUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugSceneClassState", C.c_int, [_P, C.POINTER(C.c_uint32)]),
     ("giCDebugSceneUpsPlain", C.c_int, [_P, C.POINTER(C.c_uint32)]), ("giCDebugUpsTraits", C.c_int, [C.POINTER(GiCMaterialDesc), _U, C.c_int, C.POINTER(C.c_uint32)]),
     ("giCDebugSceneLeafLift", C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    ("giCDebugSceneNodeCook", C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    ("giCDebugNodeCook", C.c_int, [_P, _U, C.c_int32, _P, _U, C.POINTER(C.c_uint32)]),
+    ("giCDebugCheckNodeCook", C.c_int64, [_P, _U, _FP, C.c_uint64]),
     ("giCDebugLeafLift", C.c_int, [_FP, _U, C.c_int32, _P, _U, _U, _P, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_double)]),
     ("giCDebugSceneVertexUpdateCount", C.c_int, [_P, C.POINTER(C.c_uint64)]), ("giCDebugRefitBvh", C.c_int, [_FP, _FP, _U, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("giCDebugSceneRefitCheck", C.c_int, [_P, _U, C.POINTER(C.c_uint32)]),
@@ -408,6 +411,36 @@ def leaf_lift(tri_verts, mode: int = 1, tree_nodes=None, tree_depth: int = 0) ->
         raise GiError(f"giCDebugLeafLift failed ({rc})")
     return {"violations": rc, "nodes": nodes[:int(info[0])].copy(), "order": order[:len(v)].copy(), "depth": int(info[1]), "lifted": int(info[2]),
             "active": int(info[3]), "cost_before": float(cost[0]), "cost_after": float(cost[1])}
+
+
+def node_cook(nodes, oct_blocks: int = -1) -> dict:
+    """giCDebugNodeCook: the cooked image of `nodes` (bytes or a uint8 array of 80-byte nodes) as a block of the fused kernel stages it.  Returns {"records"
+    (uint32, n x 28), "oct" (uint32, blocks x 8 octants x 8 children), "stride", "oct_block_bytes"}; `oct_blocks` < 0: the blocks a tree of n nodes can need,
+    n - 1.  Host only."""
+    import numpy as np
+    L = load_library()
+    given = np.ascontiguousarray(np.frombuffer(bytes(nodes), np.uint8)).reshape(-1, 80)
+    n = len(given)
+    blocks = max(n - 1, 0) if oct_blocks < 0 else int(oct_blocks)
+    image = np.zeros(n * 28 + blocks * 64, np.uint32); info = np.zeros(3, np.uint32)
+    if L.giCDebugNodeCook(given.ctypes.data_as(_P), n, int(oct_blocks), image.ctypes.data_as(_P), image.nbytes, info.ctypes.data_as(C.POINTER(C.c_uint32))) != GI_C_OK:
+        raise GiError("giCDebugNodeCook failed: " + L.giCGetLastError().decode())
+    assert int(info[0]) == image.nbytes and int(info[1]) == 112 and int(info[2]) == 256
+    return {"records": image[:n * 28].reshape(n, 28).copy(), "oct": image[n * 28:].reshape(blocks, 8, 8).copy(), "stride": int(info[1]),
+            "oct_block_bytes": int(info[2])}
+
+
+def check_node_cook(nodes, rays) -> int:
+    """giCDebugCheckNodeCook: on the device, the cooked node test against the plain one for the pairs (node i % n, ray i); `nodes`: 1 .. 64 nodes of 80 bytes,
+    `rays`: m x 8 floats (origin, direction, tMin, tBest).  Returns the pairs whose hit groups differ in a bit."""
+    import numpy as np
+    L = load_library()
+    given = np.ascontiguousarray(np.frombuffer(bytes(nodes), np.uint8)).reshape(-1, 80)
+    r = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+    bad = L.giCDebugCheckNodeCook(given.ctypes.data_as(_P), len(given), r.ctypes.data_as(_FP), len(r))
+    if bad < 0:
+        raise GiError("giCDebugCheckNodeCook failed: " + L.giCGetLastError().decode())
+    return int(bad)
 
 
 def bvh_stack_reach(tri_verts, origins, dirs):
@@ -1151,6 +1184,14 @@ class Scene:
         if self.L.giCDebugSceneUpsPlain(self.handle, c) != GI_C_OK:
             raise GiError("giCDebugSceneUpsPlain failed")
         return {"traits": int(c[0]), "launched": int(c[1])}
+
+    def node_cook(self) -> bool:
+        """giCDebugSceneNodeCook: whether the fused kernel of the last render staged its nodes cooked (GATLING_OPTIONS node_cook; False: the kernel that
+        decodes the meta bytes ran, or no fused kernel)."""
+        c = (C.c_uint32 * 1)()
+        if self.L.giCDebugSceneNodeCook(self.handle, c) != GI_C_OK:
+            raise GiError("giCDebugSceneNodeCook failed")
+        return bool(c[0])
 
     def leaf_lift(self) -> dict:
         """giCDebugSceneLeafLift: `lifted` -- the leaf slots the last scene build moved into free slots of the root (OPTION_LEAF_LIFT; 0: switched off, a scene

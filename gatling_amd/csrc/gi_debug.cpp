@@ -8,6 +8,7 @@
 #include "gi_bvh_stages.h"
 #include "gi_compact.h"
 #include "gi_moments.h"
+#include "gi_node_cook.h"
 #include "bvh8.h"
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -614,6 +615,57 @@ extern "C" int64_t giCDebugCheckDiv(uint32_t mode, uint64_t count, uint32_t seed
   ok = ok && hipStreamSynchronize(g_ctx.stream) == hipSuccess;
   (void)hipFree(d); if (dw) (void)hipFree(dw);
   if (!ok) { setError("giCDebugCheckDiv: device error"); return -1; }
+  return (int64_t)h;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Cooked nodes (gi_node_cook.h; k_path's COOK variants): giCDebugSceneNodeCook -- whether the last fused launch ran one (gi_render.cpp runFusedBatch);
+// giCDebugNodeCook -- the cooked image of given nodes, made by the function the kernel stages with (host only); giCDebugCheckNodeCook -- the cooked node test
+// against trav_node_test on the device (gi_path.hip k_debug_node_cook).
+// ---------------------------------------------------------------------------------------------------------------
+extern "C" int giCDebugSceneNodeCook(const GiCScene* scene, uint32_t* out)
+{
+  const GiCScene* s = scene;
+  if (!s || !out) { setError("giCDebugSceneNodeCook: bad arguments"); return GI_C_ERROR; }
+  out[0] = s->nodeCookLaunched;
+  return GI_C_OK;
+}
+
+extern "C" int giCDebugNodeCook(const void* nodes, uint32_t nodeCount, int32_t octBlocks, void* outImage, uint32_t imageCap, uint32_t* outInfo)
+{
+  if (!nodes || !outImage || !outInfo || nodeCount == 0u || nodeCount > (1u << 16)) { setError("giCDebugNodeCook: bad arguments"); return GI_C_ERROR; }
+  const uint32_t blocks = octBlocks < 0 ? gi::cook_oct_blocks_max(nodeCount) : (uint32_t)octBlocks;
+  if (blocks > (1u << 16)) { setError("giCDebugNodeCook: bad arguments"); return GI_C_ERROR; }
+  const uint32_t bytes = nodeCount * gi::COOK_NODE_BYTES + blocks * gi::COOK_OCT_DWORDS * 4u;
+  if (imageCap < bytes) { setError("giCDebugNodeCook: the image needs more room"); return GI_C_ERROR; }
+  std::vector<gi::Node8> in(nodeCount);
+  memcpy(in.data(), nodes, (size_t)nodeCount * sizeof(gi::Node8));
+  std::vector<uint32_t> image(bytes / 4u, 0u);
+  for (uint32_t i = 0; i < nodeCount; i++) gi::cook_place(in.data(), i, nodeCount, blocks, image.data());
+  memcpy(outImage, image.data(), bytes);
+  outInfo[0] = bytes; outInfo[1] = gi::COOK_NODE_BYTES; outInfo[2] = gi::COOK_OCT_DWORDS * 4u;
+  return GI_C_OK;
+}
+
+extern "C" int64_t giCDebugCheckNodeCook(const void* nodes, uint32_t nodeCount, const float* rays, uint64_t count)
+{
+  if (!g_ctx.initialized) { setError("giCDebugCheckNodeCook before giCInitialize"); return -1; }
+  if (!nodes || !rays || nodeCount == 0u || nodeCount > 64u || count == 0u || count > (1ull << 26)) { setError("giCDebugCheckNodeCook: bad arguments"); return -1; }
+  const size_t nodeBytes = (size_t)nodeCount * sizeof(gi::Node8), rayBytes = (size_t)count * 8u * sizeof(float);
+  unsigned long long* d = nullptr; unsigned long long h = 0ull; gi::Node8* dn = nullptr; float* dr = nullptr;
+  bool ok = hipMalloc(&d, sizeof(h)) == hipSuccess && hipMalloc(&dn, nodeBytes) == hipSuccess && hipMalloc(&dr, rayBytes) == hipSuccess;
+  ok = ok && hipMemcpyAsync(dn, nodes, nodeBytes, hipMemcpyHostToDevice, g_ctx.stream) == hipSuccess;
+  ok = ok && hipMemcpyAsync(dr, rays, rayBytes, hipMemcpyHostToDevice, g_ctx.stream) == hipSuccess;
+  ok = ok && hipMemsetAsync(d, 0, sizeof(h), g_ctx.stream) == hipSuccess;
+  if (ok) {
+    ok = launchDebugNodeCook(g_ctx.stream, dn, nodeCount, dr, (unsigned long long)count, d) == 0;
+    ok = ok && hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, g_ctx.stream) == hipSuccess;
+  }
+  ok = hipStreamSynchronize(g_ctx.stream) == hipSuccess && ok;
+  if (d) (void)hipFree(d);
+  if (dn) (void)hipFree(dn);
+  if (dr) (void)hipFree(dr);
+  if (!ok) { setError("giCDebugCheckNodeCook: device error"); return -1; }
   return (int64_t)h;
 }
 

@@ -423,6 +423,7 @@ struct GiCScene : SceneDevice {
   // what every class-1 material in use has in common (gi_types.h UPS_NOCOAT; 0 when the class is textured or absent): the fused kernel's plain
   // UsdPreviewSurface variant.  upsPlainLaunched: the traits the last render's k_path launch was compiled for (0: the general text, or no fused launch)
   uint32_t upsTraits = 0, upsPlainLaunched = 0;
+  uint32_t nodeCookLaunched = 0; // giCDebugSceneNodeCook: 1 when the last render's k_path launch staged cooked nodes (gi_node_cook.h; launchPath's rule)
   std::unique_ptr<SceneHost> host; // the scene as host arrays, kept for incremental transform updates
   std::vector<std::unique_ptr<SceneDevice>> replicas; // devices 1 .. N-1 (created with the first build when the library runs on several devices)
   // options + stats

@@ -65,8 +65,20 @@ bool pathKernelSupports(const SceneView& sc);
 // ringCarry: the variants without NEE carry the triangle ring across the steps of a trip's closest-hit loop and flush it once (0: every step empties it)
 // upsTraits: what the scene's class-1 materials have in common (gi_types.h UPS_*; 0: nothing, or the switch is off).  pathUpsVariant is the rule: the traits the
 // kernel launchPath picks is compiled for -- the hot class-1 kernel without NEE takes them, every other one is the general text (0)
+// nodeCook: the kernels pathCookVariant names run their COOK instantiation -- the nodes staged in the cooked form of gi_node_cook.h, the node test reading
+// each child's hit-mask word from a table and only the occupied slots -- when the cooked image leaves blocksPerCuByLds what it is with the raw one (0: never).
+// *cooked (may be null): whether the launch ran one
 int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool textured, bool count, uint32_t chunk, uint32_t walkCarry, uint32_t lobePark,
-               uint32_t ringCarry, uint32_t upsTraits, const FrameUniforms& U, const SceneView& sc, const PathState& st, Counters* cnt, F4* sampleBuf);
+               uint32_t ringCarry, uint32_t upsTraits, uint32_t nodeCook, const FrameUniforms& U, const SceneView& sc, const PathState& st, Counters* cnt,
+               F4* sampleBuf, uint32_t* cooked);
+// the kernels that have a COOK instantiation: the hot variants of class 0 and class 1 (the latter with or without UPS_NOCOAT) without NEE
+inline bool pathCookVariant(uint32_t classMask, bool textured, bool nee, bool cutout, bool count)
+{
+  return (classMask == 1u || classMask == 2u) && !textured && !cutout && !count && !nee;
+}
+// traceLdsBytes with the nodes in their cooked form (gi_node_cook.h cook_image_bytes)
+uint32_t pathCookedLdsBytes(uint32_t stackEntries, uint32_t ldsNodes, uint32_t ldsTris);
+constexpr long NODE_COOK_DEFAULT = 1;  // GATLING_OPTIONS=node_cook (gi_options.h)
 inline uint32_t pathUpsVariant(uint32_t classMask, bool textured, bool nee, bool cutout, bool count, uint32_t upsTraits)
 {
   return (classMask == 2u && !textured && !cutout && !count && !nee) ? upsTraits : 0u;
@@ -186,6 +198,8 @@ void launchSpin(hipStream_t s, unsigned long long ns);           // test hook: o
 void launchDebugBsdf(hipStream_t s, const MaterialRec* mat, uint32_t shadeClass, uint32_t count, const float* in, float* out);
 void launchDebugSqrt(hipStream_t s, uint32_t first, unsigned long long count, unsigned long long* mismatches); // gi_sqrt against sqrtf over bit patterns
 void launchDebugDiv(hipStream_t s, uint32_t mode, unsigned long long count, uint32_t seed, const uint32_t* words, unsigned long long* mismatches); // gi_div against `/`
+// trav_node_test against trav_node_test_cooked on `count` (node i % nodeCount, ray i) pairs (gi_path.hip k_debug_node_cook); -1: more nodes than a block cooks
+int launchDebugNodeCook(hipStream_t s, const Node8* nodes, uint32_t nodeCount, const float* rays, unsigned long long count, unsigned long long* mismatches);
 void launchDebugTex(hipStream_t s, const float* texels, uint32_t w, uint32_t h, uint32_t d, uint32_t count, const float* queries, float* out);
 
 } // namespace gi

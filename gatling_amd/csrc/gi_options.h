@@ -41,6 +41,11 @@
 //                                  below it) goes through liftLeafSlots (leaf_lift.cpp): leaf slots that stretch a child's box move into free slots of the
 //                                  root while the builder's cost model strictly decreases.  0 = the builder's tree, byte for byte.  Overrides
 //                                  GI_C_SCENE_OPTION_LEAF_LIFT; read at the scene build (giCDebugSceneLeafLift shows what it did)
+//   node_cook            1         fused frames without next-event estimation whose materials are all of one class, 0 or 1, and untextured: k_path runs the
+//                                  variant that stages its nodes cooked (gi_node_cook.h) -- the word each child adds to the hit mask comes from a per-octant
+//                                  table made once per block instead of a decode per visit, and the child loop covers the occupied slots only -- provided
+//                                  the larger node image costs no resident block (gi_path.hip launchPath).  0 = the kernel that decodes the meta bytes.
+//                                  Counting builds never run the variant (giCDebugSceneNodeCook shows which one ran)
 //   fused                1         LDS-resident scenes run the fused persistent kernel
 //   pool_slots           0         pin the path pool (slots); 0 = the memory plan decides
 //   sample_buffer_mb     0         pin the per-sample buffer (MiB); 0 = the memory plan decides

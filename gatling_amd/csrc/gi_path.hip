@@ -38,6 +38,11 @@
 // instantiation whose class-1 sample leaves the coat lobe out (the NEE-off class-1 variant; UPS, the last template argument; gi_shading.h ups_plain_sample): the
 // operations dropped are exact identities when coat is the word of +0, so the bits are the same.  UPS = 0 is the kernel as it was; ups_plain=0 selects it.
 //
+// The hot variants of classes 0 and 1 without NEE have a COOK instantiation (the last template argument; launchPath picks it, GATLING_OPTIONS=node_cook=0 does
+// not): the block stages its nodes in the cooked form of gi_node_cook.h -- made from sc.nodes by its own threads before the barrier, nothing of it in HBM -- and
+// the node test reads the word each child adds to the hit mask from a per-octant table instead of decoding the meta bytes on every visit, over the occupied
+// slots only (gi_traversal.h trav_node_test_cooked).  The box arithmetic is untouched: hit masks, walks, images and `segments` are the same.
+//
 // Not handled here (the host falls back to the wavefront pipeline): medium stacks (mediumStackSize > 0), dome-light images,
 // scenes beyond LDS, trees deeper than 8 levels.
 
@@ -59,7 +64,7 @@ constexpr uint32_t PRE_FIELDS = 10; // prepared camera ray: origin, direction, t
 constexpr uint32_t PATH_STACK_MAX = 8; // LDS traversal-stack entries per lane: 4 for trees of depth <= 4 (cornell), else 8 (the host checks bvhDepth <= 8)
 
 constexpr int PATH_WAVES = 4; // resident waves per SIMD the register allocation aims for (114 VGPRs without a hint; 3 cost 11 %, 5 spill 26 registers: r03)
-template <uint32_t KLASS, bool TEXTURED, bool NEE, bool CUTOUT, bool COUNT, uint32_t PATH_STACK, uint32_t UPS = 0u>
+template <uint32_t KLASS, bool TEXTURED, bool NEE, bool CUTOUT, bool COUNT, uint32_t PATH_STACK, uint32_t UPS = 0u, bool COOK = false>
 __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PATH_WAVES, 8))) void k_path(FrameUniforms U, SceneView sc, PathState st,
     Counters* cnt, F4* __restrict__ sampleBuf, uint32_t ldsNodes, uint32_t ldsTris, uint32_t chunk, uint32_t walkCarry, uint32_t lobePark, uint32_t lotRow,
     uint32_t lotCap, uint32_t ringCarry)
@@ -69,7 +74,9 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
   // Lobe parking (NEE off, class 1 -- and the counting build, which is how tests see it): see "shade" below.  Every other variant is compiled without it.
   constexpr bool PARK = !NEE && (KLASS == 1u || (KLASS == KLASS_DYNAMIC && COUNT));
   constexpr bool DEFER = PARK || COUNT; // shade_segment's deferring form: PARK needs it; counting builds use it to count the glossy hits (lite never set)
-  const StagedScene S = stage_scene<PATH_STACK>(sc, ldsNodes, ldsTris); // the only barrier: from here on the waves of a block are independent
+  static_assert(!COOK || (!NEE && !COUNT), "cooked nodes: the hot variants without NEE (wave_step_ring)");
+  // the only barrier: from here on the waves of a block are independent
+  const StagedScene S = COOK ? stage_scene_cooked<PATH_STACK>(sc, ldsNodes, ldsTris) : stage_scene<PATH_STACK>(sc, ldsNodes, ldsTris);
   __shared__ WaveTri s_wave[TRACE_BLOCK / 64];
   WaveTri& W = s_wave[threadIdx.x >> 6];
 
@@ -215,7 +222,7 @@ __global__ __launch_bounds__(TRACE_BLOCK) __attribute__((amdgpu_waves_per_eu(PAT
           whLanes[step] += n; whTrips[step]++; step = step < 7u ? step + 1u : 7u;
           if (n < 8u) whFew++;
         }
-        if (wave_step_ring<COUNT, PATH_STACK, STAGED_ALL, CUTOUT>(R, tAlive, W, sc, S, overflow, tc, rng, pend, ringN)) tAlive = false;
+        if (wave_step_ring<COUNT, PATH_STACK, STAGED_ALL, CUTOUT, COOK>(R, tAlive, W, sc, S, overflow, tc, rng, pend, ringN)) tAlive = false;
         walking = __ballot(tAlive);
         const bool last = (uint32_t)__popcll(walking) <= stop;
         if ((last || ringCarry == 0u) && pend != 0u) { // the one flush of the trip (ringCarry = 0: of every step)
@@ -435,14 +442,26 @@ bool pathKernelSupports(const SceneView& sc)
          && !sc.shadePacked;
 }
 
+uint32_t pathCookedLdsBytes(uint32_t stackEntries, uint32_t ldsNodes, uint32_t ldsTris)
+{
+  return stackEntries * TRACE_BLOCK * (uint32_t)sizeof(uint2) + cook_image_bytes(ldsNodes) + ldsTris * LDS_TRI_BYTES;
+}
+
 using PathKernel = void (*)(FrameUniforms, SceneView, PathState, Counters*, F4*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t);
 // Hot variants: one material class, no textures, no cutouts, no counters (the C1 / C2 paths).  Everything else runs the general
 // variant (class read from the material record, textures and cutouts compiled in).
+// cook: the COOK instantiation of the kernel the other arguments pick, or nullptr where there is none (pathCookVariant)
 template <uint32_t STACK>
-static PathKernel pickPathKernel(uint32_t classMask, bool textured, bool nee, bool cutout, bool count, uint32_t upsTraits)
+static PathKernel pickPathKernel(uint32_t classMask, bool textured, bool nee, bool cutout, bool count, uint32_t upsTraits, bool cook = false)
 {
   const bool hot = (classMask == 1u || classMask == 2u || classMask == 4u) && !textured && !cutout && !count;
   const uint32_t ups = pathUpsVariant(classMask, textured, nee, cutout, count, upsTraits);
+  if (cook) {
+    if (!pathCookVariant(classMask, textured, nee, cutout, count)) return nullptr;
+    if (classMask == 1u) return k_path<0u, false, false, false, false, STACK, 0u, true>;
+    if (ups == UPS_NOCOAT) return k_path<1u, false, false, false, false, STACK, UPS_NOCOAT, true>;
+    return k_path<1u, false, false, false, false, STACK, 0u, true>;
+  }
   return dispatchBools([&](auto neeC) -> PathKernel {
     constexpr bool NEE = decltype(neeC)::value;
     if (hot) {
@@ -458,18 +477,36 @@ static PathKernel pickPathKernel(uint32_t classMask, bool textured, bool nee, bo
 }
 
 int launchPath(hipStream_t s, uint32_t cuCount, uint32_t classMask, bool textured, bool count, uint32_t chunk, uint32_t walkCarry, uint32_t lobePark,
-               uint32_t ringCarry, uint32_t upsTraits, const FrameUniforms& U, const SceneView& sc, const PathState& st, Counters* cnt, F4* sampleBuf)
+               uint32_t ringCarry, uint32_t upsTraits, uint32_t nodeCook, const FrameUniforms& U, const SceneView& sc, const PathState& st, Counters* cnt,
+               F4* sampleBuf, uint32_t* cooked)
 {
+  if (cooked) *cooked = 0u;
   if (U.workTotal == 0u) return 0; // an empty active rectangle (FLAG_MISS_RECT, the camera looks away): no pixel needs a path
   const uint32_t ldsNodes = sc.nodeCount, ldsTris = sc.triCount;
   const PathLot lot = pathLotPlacement(sc.bvhDepth); // the stack rows, and in them the home of k_path's parked hits: no LDS of its own
   const uint32_t stack = lot.stack;
   assert(sc.bvhDepth <= stack && lot.row >= sc.bvhDepth && lot.row + (lot.capacity + 7u) / 8u <= stack); // the walks own rows [0, bvhDepth), the lot the rest
-  const uint32_t bytes = traceLdsBytes(stack, ldsNodes, ldsTris);
+  uint32_t bytes = traceLdsBytes(stack, ldsNodes, ldsTris);
   const bool neeOn = (U.flags & FLAG_NEE) != 0u;
   PathKernel k = stack == 4u
       ? pickPathKernel<4u>(classMask, textured, neeOn, sc.hasCutouts != 0u, count, upsTraits)
       : pickPathKernel<8u>(classMask, textured, neeOn, sc.hasCutouts != 0u, count, upsTraits);
+  // Cooked nodes (gi_node_cook.h, trav_node_test_cooked): the COOK instantiation of the same kernel, where there is one and the larger node image costs no
+  // resident block -- the instructions a node test saves are worth less than a wave per SIMD.  Derived from the two LDS sizes, nothing tuned.
+  if (nodeCook != 0u) {
+    PathKernel kc = stack == 4u
+        ? pickPathKernel<4u>(classMask, textured, neeOn, sc.hasCutouts != 0u, count, upsTraits, true)
+        : pickPathKernel<8u>(classMask, textured, neeOn, sc.hasCutouts != 0u, count, upsTraits, true);
+    hipFuncAttributes fr{}, fc{};
+    if (kc && hipFuncGetAttributes(&fr, reinterpret_cast<const void*>(k)) == hipSuccess
+        && hipFuncGetAttributes(&fc, reinterpret_cast<const void*>(kc)) == hipSuccess) {
+      const uint32_t cookedBytes = pathCookedLdsBytes(stack, ldsNodes, ldsTris);
+      if (blocksPerCuByLds(cookedBytes, (uint32_t)fc.sharedSizeBytes) >= blocksPerCuByLds(bytes, (uint32_t)fr.sharedSizeBytes)) {
+        k = kc; bytes = cookedBytes;
+        if (cooked) *cooked = 1u;
+      }
+    }
+  }
   // Resident blocks per CU (4 waves per block = 1 wave per SIMD and block): the smaller of what the 160 KiB of LDS and the 512-entry
   // register file of a SIMD hold.  (hipOccupancyMaxActiveBlocksPerMultiprocessor answered 3 for a 35 KiB block: it does not know gfx950's LDS size.)
   int perCu = 2;
@@ -558,6 +595,39 @@ __global__ void k_debug_div(uint32_t mode, unsigned long long count, uint32_t se
 void launchDebugDiv(hipStream_t s, uint32_t mode, unsigned long long count, uint32_t seed, const uint32_t* words, unsigned long long* mismatches)
 {
   hipLaunchKernelGGL(k_debug_div, dim3(4096), dim3(256), 0, s, mode, count, seed, words, mismatches);
+}
+
+// k_debug_node_cook: trav_node_test against trav_node_test_cooked.  Every block cooks the `nodeCount` (<= DEBUG_COOK_NODES) nodes into its LDS as k_path's stage
+// does (cook_place) and then takes pairs: pair i = ray i (eight words: origin, direction, tMin, tBest) on node i % nodeCount.  Counts the pairs for which R.G or
+// the returned triangle group differ in a bit.  The cooked test's child loop ends at a bound of the wave, so a wave of mixed nodes is part of what is held.
+constexpr uint32_t DEBUG_COOK_NODES = 64;
+__global__ __launch_bounds__(TRACE_BLOCK) void k_debug_node_cook(const Node8* __restrict__ nodes, uint32_t nodeCount, const float* __restrict__ rays,
+                                                                 unsigned long long count, unsigned long long* mismatches)
+{
+  __shared__ uint4 s_image[(DEBUG_COOK_NODES * COOK_NODE_BYTES + DEBUG_COOK_NODES * COOK_OCT_DWORDS * 4u) / sizeof(uint4)];
+  if (nodeCount == 0u || nodeCount > DEBUG_COOK_NODES) return;
+  for (uint32_t i = threadIdx.x; i < nodeCount; i += TRACE_BLOCK) cook_place(nodes, i, nodeCount, DEBUG_COOK_NODES, reinterpret_cast<uint32_t*>(s_image));
+  __syncthreads();
+  unsigned long long bad = 0ull;
+  for (unsigned long long i = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; i < count; i += (unsigned long long)gridDim.x * blockDim.x) {
+    const float* r = rays + 8ull * i;
+    const uint32_t nodeIdx = (uint32_t)(i % nodeCount);
+    RayWalk A, B;
+    walk_init(A, v3(r[0], r[1], r[2]), v3(r[3], r[4], r[5]), r[6], r[7]);
+    B = A;
+    const uint4* p = reinterpret_cast<const uint4*>(nodes) + nodeIdx * 5u;
+    const uint2 ga = trav_node_test<false, true>(A, p[0], p[1], p[2], p[3], p[4]);
+    const uint2 gb = trav_node_test_cooked(B, (const GI_LDS gi_u4*)((const GI_LDS char*)s_image + __umul24(nodeIdx, COOK_NODE_BYTES)));
+    if (A.G.x != B.G.x || A.G.y != B.G.y || ga.x != gb.x || ga.y != gb.y) bad++;
+  }
+  if (bad) atomicAdd(mismatches, bad);
+}
+
+int launchDebugNodeCook(hipStream_t s, const Node8* nodes, uint32_t nodeCount, const float* rays, unsigned long long count, unsigned long long* mismatches)
+{
+  if (nodeCount == 0u || nodeCount > DEBUG_COOK_NODES) return -1;
+  hipLaunchKernelGGL(k_debug_node_cook, dim3(256), dim3(TRACE_BLOCK), 0, s, nodes, nodeCount, rays, count, mismatches);
+  return 0;
 }
 
 } // namespace gi

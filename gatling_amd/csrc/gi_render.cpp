@@ -444,6 +444,7 @@ struct Schedule {
   uint32_t walkCarry = 0u;      // k_path: the closest-hit loop of a trip ends once at most this many lanes are still walking (0: never early)
   uint32_t lobePark = 0u;       // k_path: hits that drew a glossy lobe are parked and shaded together once this many wait (0: shaded where they are)
   uint32_t ringCarry = 0u;      // k_path: the triangle ring is carried across the steps of a trip's closest-hit loop (0: every step empties it)
+  uint32_t nodeCook = 0u;       // k_path: the variants that have one stage their nodes cooked (gi_node_cook.h; 0: never)
   uint32_t upsTraits = 0u;      // k_path: the traits of the scene's class-1 materials its plain variant may be compiled for (0: the general kernel)
   int32_t shadowOrderNow = -1;  // visiting order of the shadow walks; -1: not chosen yet -- alternate, and count (chooseShadowOrder)
 };
@@ -545,6 +546,10 @@ static Schedule scheduleFrame(Frame& f)
   // launchPath's rule (pathUpsVariant); counting builds run the general kernel, whose counters the tests read.
   f.s->upsPlainLaunched = 0u; // giCDebugSceneUpsPlain: until a fused batch of this render launches (runFusedBatch)
   sch.upsTraits = !s->countTraversal && optionValue("ups_plain", UPS_PLAIN_DEFAULT) != 0 ? s->upsTraits : 0u;
+  // Cooked nodes of k_path (gi_node_cook.h): wanted unless switched off; which kernels have the variant and whether the tree's cooked image may take its
+  // place in LDS is launchPath's rule (counting builds run the general kernel, which has none).
+  f.s->nodeCookLaunched = 0u; // giCDebugSceneNodeCook: until a fused batch of this render launches (runFusedBatch)
+  sch.nodeCook = optionValue("node_cook", NODE_COOK_DEFAULT) != 0 ? 1u : 0u;
   sch.dynRefill = traceDynRefill(s);
   // (GATLING_OPTIONS=shadow_order=0|1 pins it)
   sch.shadowOrderNow = optionSet("shadow_order") ? (int32_t)optionValue("shadow_order", -1) : s->shadowOrder.load();
@@ -610,10 +615,12 @@ static int runFusedBatch(Frame& f, uint32_t batch)
   // ... 2048 measure the same)
   chunk = (uint32_t)std::min<uint64_t>(chunk, std::max<uint64_t>(64u, ((uint64_t)U.workTotal / (waves * 16u)) & ~63ull));
   f.tm.beginIteration(true); // one launch per batch: timed whatever the stride
+  uint32_t cooked = 0u;
   f.tm.timed(f.st, StageTimers::TRACE, [&] {
     launchPath(f.st, (uint32_t)f.ctx.cuCount, s->classMask, s->classTextured != 0u, s->countTraversal, chunk, f.sch.walkCarry, f.sch.lobePark, f.sch.ringCarry,
-               f.sch.upsTraits, U, f.view, f.ps, D.dCounters.ptr, D.sampleBuf.ptr);
+               f.sch.upsTraits, f.sch.nodeCook, U, f.view, f.ps, D.dCounters.ptr, D.sampleBuf.ptr, &cooked);
   });
+  s->nodeCookLaunched = cooked; // (every device of the render launches the same variant, as below)
   // (every device of the render launches the same variant: one value, whoever writes it)
   s->upsPlainLaunched = pathUpsVariant(s->classMask, s->classTextured != 0u, (U.flags & FLAG_NEE) != 0u, f.view.hasCutouts != 0u, s->countTraversal, f.sch.upsTraits);
   f.iters++; f.tm.totalIters++; f.traceLaunches++;

@@ -4,6 +4,7 @@
 // its own step from the same pieces.  Included by gi_trace.hip, gi_path.hip, gi_aov.hip, gi_kernels.hip and gi_shade.hip.
 #pragma once
 
+#include "gi_node_cook.h"
 #include "gi_queues.h"
 #include "gi_texture.h"
 
@@ -57,6 +58,21 @@ __device__ __forceinline__ StagedScene stage_scene(const SceneView& sc, uint32_t
   uint4* s_nodes = s_dyn + (STACK * TRACE_BLOCK * sizeof(uint2)) / sizeof(uint4);
   uint4* s_tris = s_nodes + ldsNodes * 5u;
   for (uint32_t i = threadIdx.x; i < ldsNodes * 5u; i += TRACE_BLOCK) s_nodes[i] = reinterpret_cast<const uint4*>(sc.nodes)[i];
+  for (uint32_t i = threadIdx.x; i < ldsTris * 3u; i += TRACE_BLOCK) s_tris[i] = reinterpret_cast<const uint4*>(sc.tris)[(i / 3u) * 4u + (i % 3u)];
+  __syncthreads();
+  return StagedScene{reinterpret_cast<uint2 (*)[TRACE_BLOCK]>(s_dyn), s_nodes, s_tris, ldsNodes, ldsTris};
+}
+
+// stage_scene for k_path's COOK variants: the nodes are staged in their cooked form (gi_node_cook.h: cook_image_bytes(ldsNodes) bytes where stage_scene has
+// ldsNodes * LDS_NODE_BYTES; the launch sizes it: pathCookedLdsBytes), made here from sc.nodes by the threads of the block, one node each, before the one
+// barrier.  Nothing cooked lives in HBM: whatever edited the resident tree, the next launch cooks what it finds.  S.nodes points at the cooked image.
+template <uint32_t STACK>
+__device__ __forceinline__ StagedScene stage_scene_cooked(const SceneView& sc, uint32_t ldsNodes, uint32_t ldsTris)
+{
+  extern __shared__ uint4 s_dyn[];
+  uint4* s_nodes = s_dyn + (STACK * TRACE_BLOCK * sizeof(uint2)) / sizeof(uint4);
+  uint4* s_tris = s_nodes + cook_image_bytes(ldsNodes) / sizeof(uint4);
+  for (uint32_t i = threadIdx.x; i < ldsNodes; i += TRACE_BLOCK) cook_place(sc.nodes, i, ldsNodes, cook_oct_blocks_max(ldsNodes), reinterpret_cast<uint32_t*>(s_nodes));
   for (uint32_t i = threadIdx.x; i < ldsTris * 3u; i += TRACE_BLOCK) s_tris[i] = reinterpret_cast<const uint4*>(sc.tris)[(i / 3u) * 4u + (i % 3u)];
   __syncthreads();
   return StagedScene{reinterpret_cast<uint2 (*)[TRACE_BLOCK]>(s_dyn), s_nodes, s_tris, ldsNodes, ldsTris};
@@ -198,6 +214,60 @@ __device__ __forceinline__ uint2 trav_node_test(RayWalk& R, const uint4& n0, con
   return make_uint2(n1.y, hitmask & 0x00ffffffu);
 }
 
+// LDS accessors: through a C++ pointer or reference the compiler only sees a generic address and emits FLAT loads / stores (see WaveTri below); a cast back to
+// address space 3 makes them ds_read / ds_write
+#define GI_LDS __attribute__((address_space(3)))
+typedef uint32_t gi_u4 __attribute__((ext_vector_type(4)));
+
+// trav_node_test on a cooked node in LDS (gi_node_cook.h; k_path's COOK variants).  The floating-point part is trav_node_test's, operation for operation, on
+// the same plane bytes: the frame, WIDEN, the near / far selection by sign, the packed fma, min / max, tn <= tf.  What differs: the word a hit child
+// contributes is read from the node's table for the ray's octant instead of being decoded from the meta bytes (the table holds exactly those words, empty
+// children 0); the children come occupied slots first and the loop runs in pairs up to a wave-uniform bound -- a pair is skipped when no lane of the wave that
+// is in here has a node with that many occupied slots -- ; the table is loaded per half, right before its use.  Which child a contribution comes from decides
+// nothing (the hit mask is an OR), so R.G and the returned triangle group are trav_node_test's words.
+__device__ __forceinline__ uint2 trav_node_test_cooked(RayWalk& R, const GI_LDS gi_u4* p)
+{
+  const V3 o = R.o, d = R.d;
+  constexpr float WIDEN = 1.00001f;
+  const gi_u4 n0 = p[0], n1 = p[1], n2 = p[2], n3 = p[3], n4 = p[4]; // n1: childBase, triBase, occupied << 16 | octant mask, table offset
+  const GI_LDS gi_u4* table = (const GI_LDS gi_u4*)((const GI_LDS char*)p + (n1.w + ((R.octinv >> 3) & n1.z)));
+  // ray in the node's quantisation frame: t(q) = q * a + b per axis; .x = near plane, .y = far plane (widened)
+  const float sx = u2f((n0.w & 0xffu) << 23), sy = u2f(((n0.w >> 8) & 0xffu) << 23), sz = u2f(((n0.w >> 16) & 0xffu) << 23);
+  const float ax = sx * R.idx, ay = sy * R.idy, az = sz * R.idz;
+  const float bx = (u2f(n0.x) - o.x) * R.idx, by = (u2f(n0.y) - o.y) * R.idy, bz = (u2f(n0.z) - o.z) * R.idz;
+  const gi_f2 Ax = {ax, ax * WIDEN}, Ay = {ay, ay * WIDEN}, Az = {az, az * WIDEN};
+  const gi_f2 Bx = {bx, bx * WIDEN}, By = {by, by * WIDEN}, Bz = {bz, bz * WIDEN};
+  const float tFar = R.tBest * WIDEN, tNear = R.tMin;
+  const bool nxn = d.x < 0.0f, nyn = d.y < 0.0f, nzn = d.z < 0.0f;
+  const uint32_t qlox[2] = {n2.x, n2.y}, qloy[2] = {n2.z, n2.w}, qloz[2] = {n3.x, n3.y};
+  const uint32_t qhix[2] = {n3.z, n3.w}, qhiy[2] = {n4.x, n4.y}, qhiz[2] = {n4.z, n4.w};
+  const uint32_t occupied = n1.z; // (the octant mask in its low bits stays below every bound compared with)
+  uint32_t hitmask = 0u;
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    if (h == 1 && !__ballot(occupied >= (5u << 16))) break;
+    const uint32_t nearx = nxn ? qhix[h] : qlox[h], farx = nxn ? qlox[h] : qhix[h];
+    const uint32_t neary = nyn ? qhiy[h] : qloy[h], fary = nyn ? qloy[h] : qhiy[h];
+    const uint32_t nearz = nzn ? qhiz[h] : qloz[h], farz = nzn ? qloz[h] : qhiz[h];
+    const gi_u4 c4 = table[h];
+    const uint32_t contribs[4] = {c4.x, c4.y, c4.z, c4.w};
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      if (k == 2 && !__ballot(occupied >= ((uint32_t)(4 * h + 3) << 16))) break;
+      const uint32_t sh = 8u * (uint32_t)k;
+      const gi_f2 qx = {(float)((nearx >> sh) & 0xffu), (float)((farx >> sh) & 0xffu)};
+      const gi_f2 qy = {(float)((neary >> sh) & 0xffu), (float)((fary >> sh) & 0xffu)};
+      const gi_f2 qz = {(float)((nearz >> sh) & 0xffu), (float)((farz >> sh) & 0xffu)};
+      const gi_f2 tx = __builtin_elementwise_fma(qx, Ax, Bx), ty = __builtin_elementwise_fma(qy, Ay, By), tz = __builtin_elementwise_fma(qz, Az, Bz);
+      const float tn = fmaxf(fmaxf(tx.x, ty.x), fmaxf(tz.x, tNear));
+      const float tf = fminf(fminf(tx.y, ty.y), fminf(tz.y, tFar));
+      hitmask |= (tn <= tf) ? contribs[k] : 0u;
+    }
+  }
+  R.G = make_uint2(n1.x, (hitmask & 0xff000000u) | (n0.w >> 24));
+  return make_uint2(n1.y, hitmask & 0x00ffffffu);
+}
+
 // fetch of a node's five 16-byte pieces from global memory: 32-bit byte offset on the scalar base (a scene's node array stays below 4 GiB: the flat layout ends
 // at 2^26 triangles), two shift-adds instead of a 64-bit multiply-add
 __device__ __forceinline__ void node_load(const SceneView& sc, uint32_t nodeIdx, uint4& n0, uint4& n1, uint4& n2, uint4& n3, uint4& n4)
@@ -210,11 +280,16 @@ __device__ __forceinline__ void node_load(const SceneView& sc, uint32_t nodeIdx,
 }
 
 // The per-lane composition (each lane fetches its own node: from LDS when staged there, else from global memory)
-template <bool COUNT, uint32_t STACK, bool OVERFLOW, Staged STAGED, bool ORDERED = true>
+// COOK: S.nodes is the cooked image of stage_scene_cooked (the whole tree, near-to-far order)
+template <bool COUNT, uint32_t STACK, bool OVERFLOW, Staged STAGED, bool ORDERED = true, bool COOK = false>
 __device__ __forceinline__ uint2 trav_node(RayWalk& R, const SceneView& sc, StagedScene S, uint2 (&overflow)[OVERFLOW ? OVF_STACK : 1],
                                            WalkCounters<COUNT>& tc)
 {
   const uint32_t nodeIdx = trav_node_pick<STACK, OVERFLOW, ORDERED>(R, S.stack, overflow);
+  if constexpr (COOK) {
+    static_assert(STAGED == STAGED_ALL && ORDERED && !COUNT, "the cooked walk: the whole tree in LDS, near-to-far, no counters");
+    return trav_node_test_cooked(R, (const GI_LDS gi_u4*)((const GI_LDS char*)S.nodes + __umul24(nodeIdx, COOK_NODE_BYTES)));
+  }
   uint4 n0, n1, n2, n3, n4;
   if (STAGED == STAGED_ALL || (STAGED == STAGED_SOME && nodeIdx < S.ldsNodes)) { const uint4* p = S.nodes + nodeIdx * 5u; n0 = p[0]; n1 = p[1]; n2 = p[2]; n3 = p[3]; n4 = p[4]; }
   else node_load(sc, nodeIdx, n0, n1, n2, n3, n4);
@@ -306,8 +381,6 @@ struct WaveTri {
 // WaveTri lives in LDS, but through a C++ reference the compiler only sees a generic pointer and emits FLAT loads / stores (vector-memory
 // path, each volatile one followed by s_waitcnt vmcnt(0), i.e. a stall on every outstanding global load).  These accessors cast back to
 // address space 3, so the exchanges are ds_read / ds_write with lgkmcnt waits.
-#define GI_LDS __attribute__((address_space(3)))
-typedef uint32_t gi_u4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void wt_queue_put(WaveTri& W, uint32_t i, uint32_t v) { *(volatile GI_LDS uint32_t*)&((GI_LDS WaveTri*)&W)->queue[i] = v; }
 __device__ __forceinline__ uint32_t wt_queue_get(WaveTri& W, uint32_t i) { return *(volatile GI_LDS uint32_t*)&((GI_LDS WaveTri*)&W)->queue[i]; }
 __device__ __forceinline__ void wt_best_put(WaveTri& W, uint32_t i, unsigned long long v)
@@ -470,13 +543,13 @@ __device__ __forceinline__ void wave_ring_batch(WaveTri& W, uint32_t& pend, uint
   if (COUNT) { rs.batches++; rs.pairs += n; if (n < 64u) rs.partial++; }
 }
 // node phase, append, the full batches, pop; returns true when this lane's walk has ended (its R.tBest / R.found: wave_ring_refresh, after the flush)
-template <bool COUNT, uint32_t STACK, Staged STAGED, bool CUTOUT>
+template <bool COUNT, uint32_t STACK, Staged STAGED, bool CUTOUT, bool COOK = false>
 __device__ __forceinline__ bool wave_step_ring(RayTrav& R, bool alive, WaveTri& W, const SceneView& sc, StagedScene S, uint2 (&overflow)[1], WalkCounters<COUNT>& tc,
                                                uint32_t rng, uint32_t& pend, RingStats& rs)
 {
   const uint32_t lane = __lane_id();
   uint2 Gt = make_uint2(0u, 0u);
-  if (alive) Gt = trav_node<COUNT, STACK, false, STAGED>(R, sc, S, overflow, tc);
+  if (alive) Gt = trav_node<COUNT, STACK, false, STAGED, true, COOK>(R, sc, S, overflow, tc);
   const uint32_t cntL = (uint32_t)__popc(Gt.y);
   const uint32_t scan = wave_scan_inclusive(cntL);
   const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)scan, 63);

@@ -404,7 +404,8 @@ int giCInitializeDevices(const int32_t* deviceOrdinals, uint32_t count);
  * giCDebugUpsTraits, and for GI_C_SCENE_OPTION_BLAS_DEVICE_BUILD, giCDebugBuildBlasHost, giCDebugBuildBlas and giCDebugSceneBlasBuildStats, and for
  * GI_C_SCENE_OPTION_TLAS_COMPACTION, giCDebugSceneCompactionCount, giCDebugCompactRanges and giCDebugCompactRangesHost, and for giCCreateHostRenderBuffer,
  * giCDenoiseDefaults, giCDenoise and giCGetDenoiseStats, and for GI_C_SCENE_OPTION_LEAF_LIFT, giCDebugSceneLeafLift and giCDebugLeafLift, and for
- * GI_C_AOV_EXT_MOMENTS, giCDebugSampleMoments, giCDebugSampleMomentsHost, giCDenoiseVarianceDefaults and giCDenoiseVariance. */
+ * GI_C_AOV_EXT_MOMENTS, giCDebugSampleMoments, giCDebugSampleMomentsHost, giCDenoiseVarianceDefaults and giCDenoiseVariance, and for giCDebugSceneNodeCook,
+ * giCDebugNodeCook and giCDebugCheckNodeCook. */
 #define GI_C_API_VERSION 8u
 uint32_t giCGetApiVersion(void);
 uint32_t giCGetDeviceCount(void);
@@ -1095,6 +1096,17 @@ int giCDebugSceneLeafLift(const GiCScene* scene, uint32_t* out /* 2 */);
  * Returns the violations of the result's conservativeness contract as giCDebugValidateBvh counts them (0 = none), <0 on error. */
 int giCDebugLeafLift(const float* triVerts, uint32_t triCount, int32_t mode, const void* treeNodes, uint32_t treeNodeCount, uint32_t treeDepth,
                      void* outNodes, uint32_t nodeCap, uint32_t* outOrder, uint32_t* outInfo /* 4 */, double* outCost /* 2 */);
+/* [ext] cooked nodes ($GATLING_OPTIONS node_cook, default 1): out[0] is 1 when the fused kernel of the scene's last render ran a variant that stages its nodes
+ * in cooked form -- each child's hit-mask word in a table, occupied slots first -- and 0 otherwise: node_cook=0, next-event estimation, a class mix, textures,
+ * cutouts, a counting build, a tree whose cooked image would cost a resident block, or no fused kernel.  Host only: no device work. */
+int giCDebugSceneNodeCook(const GiCScene* scene, uint32_t* out /* 1 */);
+/* [ext] host-only: the cooked image of `nodeCount` 80-byte nodes as a block of the fused kernel stages it: nodeCount records of 112 bytes, then the octant area
+ * of `octBlocks` blocks of 256 bytes (octBlocks < 0: what a tree of that many nodes can need, nodeCount - 1).  outImage: room for `imageCap` bytes, zeroed first
+ * (blocks no node takes stay zero); outInfo[0] the bytes of the image, [1] the record stride, [2] the bytes of an octant block.  <0 on error. */
+int giCDebugNodeCook(const void* nodes, uint32_t nodeCount, int32_t octBlocks, void* outImage, uint32_t imageCap, uint32_t* outInfo /* 3 */);
+/* [ext] the cooked node test against the plain one on the device: pair i of `count` is ray i (8 floats: origin, direction, tMin, tBest) on node
+ * i % nodeCount of `nodes` (1 .. 64 nodes of 80 bytes; they need not form a tree).  Returns the pairs whose hit groups differ in a bit, <0 on error. */
+int64_t giCDebugCheckNodeCook(const void* nodes, uint32_t nodeCount, const float* rays, uint64_t count);
 /* [ext] the fused path kernel's walk counters of the scene's last render, for renders with GI_C_SCENE_OPTION_COUNT_TRAVERSAL (all zero otherwise): out[0] trips
  * of all waves, [1 + k] the trips whose closest-hit loop reached step k (k = 7: every step from the eighth on), [9 + k] the lanes walking when those steps
  * began, [17] the steps that began with fewer than 8 lanes walking.  With $GATLING_OPTIONS walk_carry=K set explicitly a counting build carries walks as other
